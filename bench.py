@@ -1,6 +1,6 @@
 """bench.py - mention x candidate pairs scored per second on WikiMEL-shaped synthetic batches.
 
-    python bench.py [--gpus N --steps K --warmup W] [--workload wikimel|wikidiverse|table] [--mode score|train] ...
+    python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR] [--workload wikimel|wikidiverse|table] [--mode score|train] ...
 
 One "step" = one pass of the DRIN scoring path (Model.forward, drin/model.py:164-209) over one batch of B mentions
 x N candidates of seeded synthetic features that are already resident in HBM.
@@ -11,9 +11,17 @@ makes any GPU call and relays rank 0's JSON line and the children's exit code; s
 is a rank.  Every rank scores its own shard of mentions (weak scaling, no data-path collective - mentions are
 independent); the timed region is bracketed by barrier + synchronize and the max over ranks is used.
 
-Prints ONE JSON line (rank 0) of at most 4 KB, strict JSON: the contract fields of the headline (BASELINE.json's metric on its WikiMEL-100
-config) plus
-  roofline     : dominant kernel of the headline, HIP-event timed inside this process on the launch stream
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0) of at most 4 KB, strict JSON: the contract
+fields of the headline (BASELINE.json's metric on its WikiMEL-100 config: metric, value, unit, higher_is_better, dtype,
+ms_per_step = milliseconds of one timed step), the configuration and the per-rank step times - nothing that needs work of
+its own.
+
+--dump-outputs DIR: after the timed steps rank 0 writes what the timed path returned in its last step as DIR/<name>.npy
+(float32; scores.npy for the scoring path, loss.npy + parameters.npy for a training step; at most 64 MB in all, a fixed
+seeded sample of anything larger).  Inputs and weights are seeded: the same arguments give the same inputs in every run.
+
+--full adds everything else the benchmark measures and checks:
+  roofline     : dominant kernel of the headline, HIP-event timed inside this process on the launch stream (a pass of its own)
   cpu_baseline : the CPU oracle (oracle/drin_oracle.py) timed on this host's cores on a bounded sample (N = 1)
   parity       : slices of the TIMED batch re-scored by the oracle (N = 1)
   legs         : value / ms_per_step / roofline fraction / parity error of every other leg, <= 150 bytes each
@@ -525,8 +533,9 @@ def make_model(cfg, sd, dev, precision, fused=True):
     return model
 
 
-def run_score(ctx, model, batch, steps, warmup, graph=False):
-    """Timed K steps of model(batch) + an instrumented pass (HIP events on the launch stream, per kernel class)."""
+def run_score(ctx, model, batch, steps, warmup, graph=False, profile=True):
+    """Timed K steps of model(batch) + (profile) an instrumented pass (HIP events on the launch stream, per kernel class);
+    prof is None without it."""
     from drin_amd import _lib
     with torch.no_grad():
         run = lambda: model(batch)  # noqa: E731
@@ -549,6 +558,9 @@ def run_score(ctx, model, batch, steps, warmup, graph=False):
                 return static_out
         elapsed, per_rank, out = ctx.timed(run, steps, warmup)
         assert torch.isfinite(out).all()
+        if not profile:
+            return elapsed, per_rank, out, None
+        out = out.clone()                      # the timed steps' result, whatever the instrumented pass writes
         _lib.profile_begin(1 << 16)
         for _ in range(steps):
             model(batch)
@@ -558,11 +570,31 @@ def run_score(ctx, model, batch, steps, warmup, graph=False):
 
 def score_line(ctx, cfg, args, B, batch, elapsed, per_rank, prof, steps, warmup, precision, features, workload, cached, fused, graph=False,
                cache_format=None):
+    """The leg's line; prof None (no instrumented pass): the contract fields, the configuration and the per-rank times only."""
     D, R, N = cfg.bert_embed_dim, cfg.resnet_embed_dim, cfg.num_candidates_model
     pairs = B * N
     cache_format = cache_format or getattr(args, "cache_format", "f32")
-    roof, ab, stream_bytes_pair, flops_pair = score_roofline(cfg, batch, B, prof, steps, precision, features, workload, cached, fused, cache_format)
     value = pairs * ctx.world * steps / elapsed
+    line = {
+        "metric": "mention x candidate pairs scored/sec",
+        "value": value, "unit": "pairs/s", "n_gpus": ctx.world, "steps": steps, "warmup": warmup,
+        "ms_per_step": elapsed / steps * 1e3, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": precision, "data": "synthetic",
+        "config": {"workload": f"{cfg.dataset_name}-shaped scoring forward: {N - 1}-cand (+1 answer slot), D={D}, R={R}, "
+                               f"L={cfg.max_mention_sentence_len}, P={cfg.resnet_num_region}"
+                               + (f", T={cfg.max_entity_attr_token_len} token-level entity text" if cfg.token_level_entities else "")
+                               + (", candidates gathered on the device from an entity table" if workload == "table" else ""),
+                   "mentions_per_step_per_gpu": B, "pairs_per_step": pairs * ctx.world,
+                   "parallelism": f"dp{ctx.world} (mentions sharded, no collective)"},
+        "rank_ms_per_step": [t / steps * 1e3 for t in per_rank],
+        "launch": "hipGraph replay" if graph else "eager",
+        "path": ((f"per-entity cache ({cache_format} rows) + layer 2") if cached else "fused two-layer" if fused else "layer-by-layer") + ", "
+                + ("bf16x3 (the fp16 image contraction is not taken at this shape)" if (precision == "bf16x3_if16" and not if16_taken(precision, cfg, workload, B, features))
+                   else precision) + (", features stored as bf16" if features == "bf16" else ""),
+    }
+    if prof is None:
+        return line
+    roof, ab, stream_bytes_pair, flops_pair = score_roofline(cfg, batch, B, prof, steps, precision, features, workload, cached, fused, cache_format)
     fr, ref_flops = whole_path_fractions(cfg, ab, flops_pair, value / ctx.world, precision, workload, B, features)
     # the one HBM-bound pass over the entity bytes, whichever class is the longest of this leg
     s_ms, s_n = prof.get("stream", (0.0, 0))
@@ -576,18 +608,7 @@ def score_line(ctx, cfg, args, B, batch, elapsed, per_rank, prof, steps, warmup,
     whole_traffic = (measured_whole_path_traffic("kernels_table_cache_mixed_f16" if cache_format == "mixed_f16" else "kernels_table_cache",
                                                  B == 4096 and features == "f32") if cached
                      else measured_whole_path_traffic("kernels", default_cfg))
-    line = {
-        "metric": "mention x candidate pairs scored/sec",
-        "value": value, "unit": "pairs/s", "n_gpus": ctx.world, "steps": steps, "warmup": warmup,
-        "ms_per_step": elapsed / steps * 1e3, "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": precision, "data": "synthetic",
-        "config": {"workload": f"{cfg.dataset_name}-shaped scoring forward: {N - 1}-cand (+1 answer slot), D={D}, R={R}, "
-                               f"L={cfg.max_mention_sentence_len}, P={cfg.resnet_num_region}"
-                               + (f", T={cfg.max_entity_attr_token_len} token-level entity text" if cfg.token_level_entities else "")
-                               + (", candidates gathered on the device from an entity table" if workload == "table" else ""),
-                   "mentions_per_step_per_gpu": B, "pairs_per_step": pairs * ctx.world,
-                   "parallelism": f"dp{ctx.world} (mentions sharded, no collective)"},
-        "rank_ms_per_step": [t / steps * 1e3 for t in per_rank],
+    line.update({
         "roofline": roof,
         "hbm_kernel": hbm_kernel,
         "kernel_ms_per_step": {k: v[0] / steps for k, v in prof.items()},
@@ -600,13 +621,9 @@ def score_line(ctx, cfg, args, B, batch, elapsed, per_rank, prof, steps, warmup,
                                                                       else ab["whole_path"]) * pairs)) if whole_traffic else None,
         "hbm_traffic_whole_path_source": (f"{TRAFFIC_FILE} whole_path: launches per call x FETCH_SIZE / WRITE_SIZE bytes per launch of every "
                                           "kernel of the call (tools/collect_pmc.py), replayed - not re-measured in this run") if whole_traffic else None,
-        "launch": "hipGraph replay" if graph else "eager",
-        "path": ((f"per-entity cache ({cache_format} rows) + layer 2") if cached else "fused two-layer" if fused else "layer-by-layer") + ", "
-                + ("bf16x3 (the fp16 image contraction is not taken at this shape)" if (precision == "bf16x3_if16" and not if16_taken(precision, cfg, workload, B, features))
-                   else precision) + (", features stored as bf16" if features == "bf16" else ""),
         "algorithmic": {"bytes_per_pair": ab["whole_path"], "dominant_kernel_bytes_per_pair": stream_bytes_pair,
                         "bytes_per_pair_split": ab, "flops_per_pair_executed": flops_pair, "flops_per_pair_reference": ref_flops},
-    }
+    })
     return line
 
 
@@ -737,13 +754,14 @@ def gather_ranks(ctx, value):
 
 
 def bench_train(ctx, cfg, sd, B, steps, warmup, precision="bf16x3", features="f32", train_form="gathered", train_entities=50_000,
-                graph=False, fused_adam=False, torch_loss=False, library_adam=True, force_collective=False):
+                graph=False, fused_adam=False, torch_loss=False, library_adam=True, force_collective=False, full_run=True, outputs=None):
     """One optimisation step of train.py:30-56 per "step": forward (intermediates kept), TripletLoss, backward
     through the HIP kernels, the RCCL all-reduce of the flat gradient bucket (world > 1, or a forced world of one), Adam.
     With collectives the all-reduce and Adam run on a side stream under the next step's parameter-free head
     (drin_amd.train.OverlappedStep; DRIN_OVERLAP selects another mode).  `allreduce_ms` = the one-piece collective when it
     runs serially after backward (HIP events), `allreduce_exposed_ms` = the timed step minus the same step without any
-    collective: what the overlap leaves on the critical path."""
+    collective: what the overlap leaves on the critical path.  Without `full_run` only the timed steps run (none of these passes).
+    `outputs` (a dict): receives the loss and the flat parameters after the last timed step."""
     from drin_amd import _lib
     from drin_amd.metrics import DeviceLossMetric
     from drin_amd.model import Model
@@ -835,6 +853,26 @@ def bench_train(ctx, cfg, sd, B, steps, warmup, precision="bf16x3", features="f3
     elapsed, per_rank, loss = ctx.timed(step, steps, warmup)
     if pipe is not None:
         pipe.finish()
+    if outputs is not None:
+        outputs["loss"] = loss.detach().reshape(1)
+        outputs["parameters"] = torch.cat([p.detach().reshape(-1) for p in model.parameters()])
+    N = cfg.num_candidates_model
+    line = {
+        "metric": "mention x candidate pairs trained/sec (forward + backward + Adam)" + (" [hipGraph replay]" if graph else ""),
+        "value": B * N * world * steps / elapsed, "unit": "pairs/s", "n_gpus": world, "steps": steps,
+        "warmup": warmup, "ms_per_step": elapsed / steps * 1e3, "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": precision, "data": "synthetic",
+        "config": {"workload": f"{cfg.dataset_name}-shaped training step, {N - 1}-cand, per-GPU batch {B} (args.py:118)"
+                               + (", features stored as bf16 (token blocks pooled in place, the rest widened)" if features == "bf16" else "")
+                               + ({"gathered": "", "table": f", candidates indexed into a device-resident table of {train_entities} entities (tokens pooled once per entity)",
+                                   "table-tokens": f", candidates gathered from a device-resident table of {train_entities} entities with torch indexing every step"}[train_form]),
+                   "global_batch": B * world, "parallelism": f"dp{world}, one flat-bucket RCCL all-reduce per step"},
+        "rank_ms_per_step": [t / steps * 1e3 for t in per_rank],
+        "optimizer": opt.describe() if hasattr(opt, "describe") else type(opt).__name__,
+        "final_loss": float(loss.detach())}
+    if not full_run:
+        bucket.close()
+        return line
     serial_ms = none_ms = None
     hook = model._layers_ready_hook
     if collectives:
@@ -852,7 +890,6 @@ def bench_train(ctx, cfg, sd, B, steps, warmup, precision="bf16x3", features="f3
     model._layers_ready_hook = hook
     ar_ms = sum(a.elapsed_time(b) for a, b in ar_events) / max(len(ar_events), 1) if ar_events else 0.0
     exposed_ms = max(0.0, elapsed / steps * 1e3 - none_ms) if none_ms is not None else 0.0
-    N = cfg.num_candidates_model
     ab = algorithmic_bytes(cfg, full[:14]) if full is not None else None
     roof = train_roofline(cfg, B, N, prof, steps, precision)
     floor = step_floor(cfg, B, N, ab["whole_path"], roof["flops_per_pair"], precision) if (ab and roof) else None
@@ -872,25 +909,14 @@ def bench_train(ctx, cfg, sd, B, steps, warmup, precision="bf16x3", features="f3
     rank_gemm_ms = gather_ranks(ctx, roof["avg_launch_ms"] if roof else 0.0)
     if coll is not None:
         coll["rank_gemm_avg_launch_ms"] = rank_gemm_ms
-    return {
-        "metric": "mention x candidate pairs trained/sec (forward + backward + Adam)" + (" [hipGraph replay]" if graph else ""),
-        "value": B * N * world * steps / elapsed, "unit": "pairs/s", "n_gpus": world, "steps": steps,
-        "warmup": warmup, "ms_per_step": elapsed / steps * 1e3, "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": precision, "data": "synthetic",
-        "config": {"workload": f"{cfg.dataset_name}-shaped training step, {N - 1}-cand, per-GPU batch {B} (args.py:118)"
-                               + (", features stored as bf16 (token blocks pooled in place, the rest widened)" if features == "bf16" else "")
-                               + ({"gathered": "", "table": f", candidates indexed into a device-resident table of {train_entities} entities (tokens pooled once per entity)",
-                                   "table-tokens": f", candidates gathered from a device-resident table of {train_entities} entities with torch indexing every step"}[train_form]),
-                   "global_batch": B * world, "parallelism": f"dp{world}, one flat-bucket RCCL all-reduce per step"},
-        "rank_ms_per_step": [t / steps * 1e3 for t in per_rank],
+    line.update({
         "allreduce_ms": ar_ms, "allreduce_exposed_ms": exposed_ms, "allreduce_bytes": plain_bucket.nbytes(), "collective": coll,
         "scaling_model": model_of_scaling, "rank_roofline_avg_launch_ms": rank_gemm_ms,
         "step_floor_ms": floor["ms"] if floor else None, "step_floor": floor,
-        "optimizer": opt.describe() if hasattr(opt, "describe") else type(opt).__name__,
         "library_launches_per_step": sum(v[1] for v in prof.values()) / steps,
         "kernel_ms_per_step": {k: v[0] / steps for k, v in prof.items()},
-        "roofline": roof,
-        "final_loss": float(loss.detach())}
+        "roofline": roof})
+    return line
 
 
 def train_parity(dev, steps=10):
@@ -990,22 +1016,33 @@ def parse_args(argv=None):
     ap.add_argument("--force-collective", action="store_true",
                     help="N = 1: initialise a process group of ONE rank (RCCL unless DRIN_BENCH_BACKEND=gloo) and run the training step's "
                          "gradient all-reduce in it - the real collective code path on a one-GPU box; allreduce_ms is then non-zero")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the instrumented pass (roofline, per-kernel times), parity against the CPU oracle, the CPU "
+                         "baseline, the secondary legs, the extra training-step passes (collective costs, step floor) and the full record "
+                         "in --legs-file; a plain run times the headline steps and nothing else")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the timed path returned in its last step as DIR/<name>.npy (float32, rank 0, "
+                         "at most 64 MB: a fixed seeded sample of anything larger)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: no CPU baseline, no parity against the CPU oracle")
     ap.add_argument("--legs", default="auto",
-                    help="secondary legs of the default run, comma separated: f32_exact,wikimel_mixed_f16,wikimel_bf16_features,wikidiverse_b4,train_step,train_b512,wikidiverse,table_cache | all | none "
+                    help="--full: secondary legs, comma separated: f32_exact,wikimel_mixed_f16,wikimel_bf16_features,wikidiverse_b4,train_step,train_b512,wikidiverse,table_cache | all | none "
                          "(auto: all for the default headline at N = 1, train_step at N > 1, none when a non-default workload / mode / batch is asked for)")
-    ap.add_argument("--legs-file", default=LEGS_FILE,
+    ap.add_argument("--legs-file", default=None,
                     help="where the FULL record goes (every leg, scaling model, step floors, provenance); stdout carries the <= 4 KB headline "
-                         "line only; '' = do not write the file")
+                         "line only; default: bench_legs.json next to this file with --full, not written without; '' = do not write the file")
     ap.add_argument("--stub", action="store_true", help="CPU + gloo stand-in step (no GPU, no library): exercises the launcher and the timing plumbing only")
     args = ap.parse_args(argv)
     if args.warmup is None:
         args.warmup = 30 if args.mode == "train" else 3
+    if args.legs not in ("auto", "none") and not args.full:
+        ap.error("--legs needs --full")
     return args
 
 
 def wanted_legs(args, world):
     names = ("f32_exact", "wikimel_mixed_f16", "wikimel_bf16_features", "wikidiverse_b4", "train_step", "train_b512", "wikidiverse", "table_cache")
+    if not args.full:
+        return ()
     default_headline = (args.workload == "wikimel" and args.mode == "score" and not args.batch and not args.generic
                         and args.precision == "bf16x3" and args.features == "f32" and not args.graph)
     if args.legs == "auto":
@@ -1053,6 +1090,7 @@ def quiet_stdout():
 
 
 LEGS_FILE = os.path.join(REPO, "bench_legs.json")
+DUMP_LIMIT = 64 << 20             # bytes of --dump-outputs in all
 LINE_LIMIT = 4096                 # bytes of the stdout line (the driver keeps an 8 KB tail; round 4's 32 KB line was not parsed)
 
 _ROOF_KEYS = ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic", "traffic_replayed", "traffic_file", "launches", "avg_launch_ms",
@@ -1176,9 +1214,29 @@ def emit(line, legs_file=""):
     out.flush()
 
 
+def dump_outputs(out_dir, arrays, seed=0):
+    """DIR/<name>.npy of every array, float32 (float64 stays float64).  Past DUMP_LIMIT bytes in all, every array keeps its
+    share of the limit as a fixed seeded sample of its flattened elements (sorted indices, the same in every run)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    host = {name: (t.detach().cpu().double() if t.dtype == torch.float64 else t.detach().cpu().float()).numpy()
+            for name, t in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    budget = DUMP_LIMIT - 4096 * len(host)                       # (room for the .npy headers)
+    for name, a in host.items():
+        if total > budget:
+            keep = max(1, a.size * budget // total)
+            idx = np.sort(np.random.default_rng(seed).choice(a.size, size=keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    sys.stderr.write(f"[bench.py] outputs of the last timed step: {', '.join(sorted(host))} -> {out_dir}\n")
+
+
 def main(argv=None):
     global LEGS_FILE
     args = parse_args(argv)
+    if args.legs_file is None:
+        args.legs_file = LEGS_FILE if args.full else ""
     LEGS_FILE = os.path.abspath(args.legs_file) if args.legs_file else None
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_children(args))                     # before anything touches the GPU in this process
@@ -1195,12 +1253,15 @@ def main(argv=None):
     sd = synth.make_state_dict(cfg, 7)
 
     if args.mode == "train":
+        outputs = {} if (rank == 0 and args.dump_outputs) else None
         line = bench_train(ctx, cfg, sd, args.batch or 64, args.steps, args.warmup, args.precision, args.features, args.train_form,
                            args.train_entities, args.graph, args.fused_adam, args.torch_loss, not args.torch_adam,
-                           force_collective=args.force_collective)
+                           force_collective=args.force_collective, full_run=args.full, outputs=outputs)
         if ctx.pg_error:
             line["collective_error"] = ctx.pg_error
         if rank == 0:
+            if outputs is not None:
+                dump_outputs(args.dump_outputs, outputs)
             emit(line)
         return ctx.finish()
 
@@ -1224,6 +1285,8 @@ def main(argv=None):
                 model(make_table_chunk(cfg, table, min(args.chunk, 64), 99, dev, g))    # folds the weights / builds the cache
             el, n_chunks, out, last = stream_table(ctx, model, cfg, table, g, args.mentions, args.chunk)
             assert torch.isfinite(out).all()
+            if rank == 0 and args.dump_outputs:
+                dump_outputs(args.dump_outputs, {"scores": out})
             N = cfg.num_candidates_model
             line = {"metric": "mention x candidate pairs scored/sec", "value": args.mentions * N * world / el, "unit": "pairs/s",
                     "n_gpus": world, "steps": n_chunks, "warmup": 1, "ms_per_step": el / n_chunks * 1e3, "higher_is_better": True,
@@ -1234,17 +1297,24 @@ def main(argv=None):
                                "parallelism": f"dp{world} (mentions sharded, no collective)"},
                     "path": (f"per-entity cache ({args.cache_format} rows) + layer 2" if args.entity_cache else "fused two-layer") + ", " + args.precision}
             if rank == 0:
-                line["parity"] = parity_of_timed_batch(cfg, sd, last, out, n_slices=2, width=1)
+                if args.full:
+                    line["parity"] = parity_of_timed_batch(cfg, sd, last, out, n_slices=2, width=1)
                 emit(line)
             return ctx.finish()
         batch = make_table_chunk(cfg, table, B, 100 + rank, dev, g)
     else:
         batch = synth.make_device_batch(cfg, B, 100 + rank, dev, dtype=torch.bfloat16 if args.features == "bf16" else torch.float32)[:14]
 
-    elapsed, per_rank, out, prof = run_score(ctx, model, batch, args.steps, args.warmup, args.graph)
+    elapsed, per_rank, out, prof = run_score(ctx, model, batch, args.steps, args.warmup, args.graph, profile=args.full)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"scores": out})
     cached = args.workload == "table" and args.entity_cache
     line = score_line(ctx, cfg, args, B, batch, elapsed, per_rank, prof, args.steps, args.warmup, args.precision, args.features,
                       args.workload, cached, fused, args.graph)
+    if not args.full:
+        if rank == 0:
+            emit(line)
+        return ctx.finish()
     line["rank_roofline_avg_launch_ms"] = gather_ranks(ctx, line["roofline"]["avg_launch_ms"])
     line["scaling_model"] = {"collectives_in_the_scoring_path": 0,
                              "expected": "every rank scores its own mentions with the N = 1 schedule: ms_per_step and the dominant kernel's "

@@ -183,3 +183,34 @@ def test_the_fp16_pass_gate_bench_reports_is_the_librarys():
     assert bench.if16_taken("bf16x3_if16", wm, "table", 4096) is False
     assert bench.if16_taken("bf16x3_if16", wd, "wikidiverse", 16384) is False   # N = 11 < 64
     assert bench.if16_taken("bf16x3", wm, "wikimel", 4096) is False
+
+
+def test_legs_ask_for_full_and_a_full_stub_run_still_reports(tmp_path):
+    r = _run("--stub", "--legs", "train_step")
+    assert r.returncode != 0 and "--legs needs --full" in r.stderr
+    r = _run("--stub", "--full", "--steps", "2", "--warmup", "0", "--legs-file", str(tmp_path / "full.json"))
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert json.loads(r.stdout.strip().splitlines()[-1])["steps"] == 2 and (tmp_path / "full.json").exists()
+
+
+def test_dumped_outputs_are_float32_and_a_fixed_seeded_sample_past_the_limit(tmp_path, monkeypatch):
+    """--dump-outputs: DIR/<name>.npy in float32 (float64 kept); past the byte limit every array keeps its share as the same
+    seeded sample in every run."""
+    sys.path.insert(0, REPO)
+    import numpy as np
+    import torch
+    import bench
+    bench.dump_outputs(str(tmp_path / "a"), {"scores": torch.arange(12, dtype=torch.bfloat16).reshape(3, 4),
+                                             "loss": torch.tensor([0.5], dtype=torch.float64)})
+    a = np.load(tmp_path / "a" / "scores.npy")
+    assert a.dtype == np.float32 and a.shape == (3, 4) and (a == np.arange(12).reshape(3, 4)).all()
+    assert np.load(tmp_path / "a" / "loss.npy").dtype == np.float64
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 64 << 10)
+    x = torch.randn(40000, generator=torch.Generator().manual_seed(1))
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"x": x, "y": x[:10000] * 2})
+    files = [tmp_path / d / f"{n}.npy" for d in ("b", "c") for n in ("x", "y")]
+    assert sum(os.path.getsize(f) for f in files[:2]) <= 64 << 10
+    xb, xc = np.load(files[0]), np.load(files[2])
+    assert xb.dtype == np.float32 and 10000 < xb.size < 40000 and (xb == xc).all() and np.isin(xb, x.numpy()).all()
+    assert (np.load(files[1]) == np.load(files[3])).all()

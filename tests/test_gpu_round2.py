@@ -419,7 +419,7 @@ def test_bench_two_ranks_on_one_gpu_over_gloo():
     import tempfile
     full_path = os.path.join(tempfile.mkdtemp(prefix="drin_bench_"), "full.json")
     r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--mode", "train", "--batch", "16", "--steps", "3",
-                        "--warmup", "2", "--legs-file", full_path], capture_output=True, text=True, env=env, timeout=600)
+                        "--warmup", "2", "--full", "--legs-file", full_path], capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1 and len(lines[0]) < 4096                  # ONE headline line the driver can parse (round 4's was 32 KB)

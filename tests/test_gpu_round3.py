@@ -391,7 +391,7 @@ def test_bench_force_collective_reports_a_nonzero_rccl_allreduce():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     full_path = os.path.join(tempfile.mkdtemp(prefix="drin_bench_"), "full.json")
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--mode", "train", "--gpus", "1", "--force-collective", "--batch", "64",
-                        "--steps", "5", "--warmup", "5", "--legs-file", full_path], capture_output=True, text=True, env=env, timeout=900)
+                        "--steps", "5", "--warmup", "5", "--full", "--legs-file", full_path], capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     head = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert len([ln for ln in r.stdout.splitlines() if ln.strip()]) == 1, r.stdout[:500]   # RCCL's banner went to stderr

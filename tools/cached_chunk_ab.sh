@@ -3,7 +3,7 @@
 # sizes), one box; the full-width cached-path tests run under every setting first
 O=gpurun_out/cached_chunk_ab.txt
 : > $O
-run() { env "$@" timeout -k 10 300 python bench.py --workload table --batch 4096 --entity-cache --steps 5 --warmup 2 --no-cpu-baseline --legs none 2>/dev/null | python -c "
+run() { env "$@" timeout -k 10 300 python bench.py --full --workload table --batch 4096 --entity-cache --steps 5 --warmup 2 --no-cpu-baseline --legs none 2>/dev/null | python -c "
 import json,sys
 l=json.loads(sys.stdin.read()); print('$*', round(l['ms_per_step'],3), 'ms', round(l['value']/1e6,2), 'M pairs/s', {k:round(v,3) for k,v in l['kernel_ms_per_step'].items() if v}, (l.get('parity') or {}).get('max_abs_score_err'))" >> $O; }
 for c in 16 64 128 256; do

@@ -6,7 +6,7 @@ O=gpurun_out/cached_floor.txt
 : > $O
 for E in ${ENTS:-1000 8000 1000000}; do
   echo "== entities $E" >> $O
-  python3 bench.py --workload table --batch 4096 --entity-cache --entities $E --steps 5 --warmup 2 --no-cpu-baseline --legs none 2>> gpurun_out/cached_floor.err | python3 -c "
+  python3 bench.py --full --workload table --batch 4096 --entity-cache --entities $E --steps 5 --warmup 2 --no-cpu-baseline --legs none 2>> "$(dirname $O)"/cached_floor.err | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().split('\n')[-1])
 print('ms_per_step', d['ms_per_step'], 'value', d['value'])

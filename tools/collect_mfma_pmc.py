@@ -3,7 +3,7 @@ were and where the waves' cycles went.
 
 Run on the GPU box (program directly after `--`, counters alone in the pass - tools/pmc_mfma.sh):
     rocprofv3 --pmc SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY \
-              SQ_ACTIVE_INST_LDS SQ_WAVES GRBM_GUI_ACTIVE --output-format csv -d DIR -- python3 bench.py ...
+              SQ_ACTIVE_INST_LDS SQ_WAVES GRBM_GUI_ACTIVE --output-format csv -d DIR -- python3 bench.py --full ...
     python3 tools/collect_mfma_pmc.py DIR OUT.json SECTION "COMMAND"
 
 Units (MI355X_MICROARCH.md, 'Per-instruction cycle constants' / 's_memtime tick vs SQ PMC units'):

@@ -2,9 +2,9 @@
 
 Run on the GPU box, FETCH_SIZE and WRITE_SIZE in SEPARATE passes (TCC slots, MI355X_MICROARCH.md
 'rocprofv3 PMC slots'):
-    rocprofv3 --pmc FETCH_SIZE --output-format csv -d gpurun_out/pmc_fetch -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline
-    rocprofv3 --pmc WRITE_SIZE --output-format csv -d gpurun_out/pmc_write -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline
-    python3 tools/collect_pmc.py gpurun_out/pmc_fetch gpurun_out/pmc_write profiles/r2_hbm_traffic.json [section] [command]
+    rocprofv3 --pmc FETCH_SIZE --output-format csv -d OUT/pmc_fetch -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline
+    rocprofv3 --pmc WRITE_SIZE --output-format csv -d OUT/pmc_write -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline
+    python3 tools/collect_pmc.py OUT/pmc_fetch OUT/pmc_write profiles/r2_hbm_traffic.json [section] [command]
 Corrections (MI355X_MICROARCH.md, HBM): the counters are in KiB; on gfx950 FETCH_SIZE reports exactly half of
 the bytes of a wide (16 B/lane) coalesced streaming read, so it is doubled; WRITE_SIZE is exact for 16-byte
 streaming stores.
@@ -25,7 +25,7 @@ def per_kernel(d):
     return {k: sum(v) / len(v) for k, v in acc.items()}
 
 section = sys.argv[4] if len(sys.argv) > 4 else "kernels"          # e.g. kernels_table_cache: merged into an existing file
-command = sys.argv[5] if len(sys.argv) > 5 else "python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --legs none (defaults: wikimel B=4096 bf16x3 fused)"
+command = sys.argv[5] if len(sys.argv) > 5 else "python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --legs none (defaults: wikimel B=4096 bf16x3 fused)"
 fetch, write = per_kernel(sys.argv[1]), per_kernel(sys.argv[2])
 out = {}
 for k in sorted(set(fetch) | set(write)):

@@ -2,7 +2,7 @@
 # BASELINE config 2: WikiDiverse-shaped inference swept over the batch size, fp32- and bf16-stored features,
 # with the parity leg (max |score - oracle| and top-1 agreement on the same synthetic inputs).  Run on the GPU box.
 for b in 4 64 1024 16384; do for f in f32 bf16; do
-  timeout -k 10 300 python3 bench.py --workload wikidiverse --features $f --batch $b --steps 50 --warmup 10 2>/dev/null | python3 -c "
+  timeout -k 10 300 python3 bench.py --full --workload wikidiverse --features $f --batch $b --steps 50 --warmup 10 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 p=d.get('parity') or {}

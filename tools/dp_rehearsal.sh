@@ -6,9 +6,9 @@ set -e
 export DRIN_BENCH_SHARE_GPU=1 DRIN_BENCH_BACKEND=gloo
 O=gpurun_out/dp_rehearsal
 mkdir -p $O
-python bench.py --gpus 2 --batch 512 --steps 5 --warmup 2 --legs train_step --no-cpu-baseline --legs-file $O/score2_full.json > $O/score2.json 2> $O/score2.err
-python bench.py --gpus 2 --mode train --batch 64 --steps 10 --warmup 10 > $O/train2.json 2> $O/train2.err
-python bench.py --gpus 1 --mode train --batch 64 --steps 10 --warmup 10 > $O/train1.json 2> $O/train1.err
+python bench.py --full --gpus 2 --batch 512 --steps 5 --warmup 2 --legs train_step --no-cpu-baseline --legs-file $O/score2_full.json > $O/score2.json 2> $O/score2.err
+python bench.py --full --gpus 2 --mode train --batch 64 --steps 10 --warmup 10 > $O/train2.json 2> $O/train2.err
+python bench.py --full --gpus 1 --mode train --batch 64 --steps 10 --warmup 10 > $O/train1.json 2> $O/train1.err
 python - <<'PY'
 import json
 for f in ("score2", "train2", "train1"):

@@ -5,10 +5,10 @@
 O=gpurun_out/dp_rehearsal4
 rm -rf $O; mkdir -p $O
 export DRIN_BENCH_SHARE_GPU=1 DRIN_BENCH_BACKEND=gloo
-python bench.py --gpus 4 --batch 256 --steps 5 --warmup 2 --legs train_step --no-cpu-baseline --legs-file $O/score_n4_full.json > $O/score_n4.json 2> $O/score_n4.err
+python bench.py --full --gpus 4 --batch 256 --steps 5 --warmup 2 --legs train_step --no-cpu-baseline --legs-file $O/score_n4_full.json > $O/score_n4.json 2> $O/score_n4.err
 echo "score rc=$?"
 for m in forward none backward both; do
-  DRIN_OVERLAP=$m python bench.py --gpus 4 --mode train --batch 16 --steps 5 --warmup 3 --legs-file $O/train_n4_$m.json > $O/train_n4_${m}_stdout.json 2> $O/train_n4_$m.err
+  DRIN_OVERLAP=$m python bench.py --full --gpus 4 --mode train --batch 16 --steps 5 --warmup 3 --legs-file $O/train_n4_$m.json > $O/train_n4_${m}_stdout.json 2> $O/train_n4_$m.err
   echo "train $m rc=$?"
 done
 python - <<'PY'

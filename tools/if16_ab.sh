@@ -7,7 +7,7 @@ O=gpurun_out/if16_ab.txt
 for i in $(seq $N); do
   for f in f32 bf16; do
     for p in bf16x3 bf16x3_if16; do
-      timeout -k 10 300 python bench.py --precision $p --features $f --steps 10 --warmup 3 --no-cpu-baseline --legs none --legs-file /tmp/x.json > /dev/null 2>> gpurun_out/if16_ab.err
+      timeout -k 10 300 python bench.py --full --precision $p --features $f --steps 10 --warmup 3 --no-cpu-baseline --legs none --legs-file /tmp/x.json > /dev/null 2>> "$(dirname $O)"/if16_ab.err
       python - "$p" "$f" <<'PY' >> $O
 import json, sys
 l = json.load(open('/tmp/x.json'))

@@ -4,13 +4,13 @@
 O=gpurun_out/lib_ab
 mkdir -p $O
 for i in 1 2; do
-  python bench.py --legs none --no-cpu-baseline --steps 10 > $O/score_new_$i.json 2>> $O/err.log
-  DRIN_LIB_PATH=$PWD/drin_amd/libdrin_hip_prev.so python bench.py --legs none --no-cpu-baseline --steps 10 > $O/score_prev_$i.json 2>> $O/err.log
+  python bench.py --full --legs none --no-cpu-baseline --steps 10 > $O/score_new_$i.json 2>> $O/err.log
+  DRIN_LIB_PATH=$PWD/drin_amd/libdrin_hip_prev.so python bench.py --full --legs none --no-cpu-baseline --steps 10 > $O/score_prev_$i.json 2>> $O/err.log
 done
 for i in 1 2 3; do
   for b in 64 512; do
-    python bench.py --mode train --batch $b > $O/new_${b}_$i.json 2>> $O/err.log
-    DRIN_LIB_PATH=$PWD/drin_amd/libdrin_hip_prev.so python bench.py --mode train --batch $b > $O/prev_${b}_$i.json 2>> $O/err.log
+    python bench.py --full --mode train --batch $b > $O/new_${b}_$i.json 2>> $O/err.log
+    DRIN_LIB_PATH=$PWD/drin_amd/libdrin_hip_prev.so python bench.py --full --mode train --batch $b > $O/prev_${b}_$i.json 2>> $O/err.log
   done
 done
 python - <<'PY'

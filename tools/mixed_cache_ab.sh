@@ -6,7 +6,7 @@ O=gpurun_out/mixed_cache_ab.txt
 for i in 1 2; do
 for F in f32 mixed_f16; do
   echo "== cache format $F (run $i)" >> $O
-  python3 bench.py --workload table --batch 4096 --entity-cache --cache-format $F --steps 5 --warmup 2 --no-cpu-baseline --legs none 2>> gpurun_out/mixed_cache_ab.err | python3 -c "
+  python3 bench.py --full --workload table --batch 4096 --entity-cache --cache-format $F --steps 5 --warmup 2 --no-cpu-baseline --legs none 2>> "$(dirname $O)"/mixed_cache_ab.err | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().split('\n')[-1])
 print('ms_per_step', round(d['ms_per_step'],3), 'M pairs/s', round(d['value']/1e6,2), d['path'])

@@ -8,8 +8,8 @@ python tools/probes/inprocess_lib_ab.py drin_amd/libdrin_hip_scalar.so 3 > $O/he
 TAB="--workload table --batch 4096 --entity-cache --steps 5 --warmup 2 --no-cpu-baseline --legs none"
 for i in 1 2; do
   for fmt in f32 mixed_f16; do
-    python bench.py $TAB --cache-format $fmt --legs-file $O/packed_${fmt}_$i.json > /dev/null 2>> $O/err.log
-    DRIN_LIB_PATH=$PWD/drin_amd/libdrin_hip_scalar.so python bench.py $TAB --cache-format $fmt --legs-file $O/scalar_${fmt}_$i.json > /dev/null 2>> $O/err.log
+    python bench.py --full $TAB --cache-format $fmt --legs-file $O/packed_${fmt}_$i.json > /dev/null 2>> $O/err.log
+    DRIN_LIB_PATH=$PWD/drin_amd/libdrin_hip_scalar.so python bench.py --full $TAB --cache-format $fmt --legs-file $O/scalar_${fmt}_$i.json > /dev/null 2>> $O/err.log
   done
 done
 python - "$O" <<'PY'

@@ -12,8 +12,8 @@ for i in 1 2; do
 done
 sort $O/gemm.txt
 for i in 1 2 3; do
-  python bench.py --legs none --no-cpu-baseline --steps 10 > $O/score_0_$i.json 2>> $O/err.log
-  for v in 1 2; do DRIN_LIB_PATH=$PWD/drin_amd/libdrin_hip_place$v.so python bench.py --legs none --no-cpu-baseline --steps 10 > $O/score_${v}_$i.json 2>> $O/err.log; done
+  python bench.py --full --legs none --no-cpu-baseline --steps 10 > $O/score_0_$i.json 2>> $O/err.log
+  for v in 1 2; do DRIN_LIB_PATH=$PWD/drin_amd/libdrin_hip_place$v.so python bench.py --full --legs none --no-cpu-baseline --steps 10 > $O/score_${v}_$i.json 2>> $O/err.log; done
 done
 python - <<'PY'
 import json, glob

@@ -8,7 +8,7 @@ O=gpurun_out/placement_channels
 rm -rf $O; mkdir -p $O
 export PYTHONUNBUFFERED=1
 for i in $(seq 1 $N); do
-  rocprofv3 --pmc TCC_REQ TCC_EA0_RDREQ --output-format json -d $O/raw_$i -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --legs none > $O/run_$i.log 2>&1 || echo "[placement_channels] run $i FAILED"
+  rocprofv3 --pmc TCC_REQ TCC_EA0_RDREQ --output-format json -d $O/raw_$i -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --legs none > $O/run_$i.log 2>&1 || echo "[placement_channels] run $i FAILED"
   python3 tools/reduce_channel_json.py $O/raw_$i $O/channels_$i.json >> $O/table.txt 2>> $O/reduce.err || echo "[placement_channels] reduce $i failed"
   rm -rf $O/raw_$i
   echo "[placement_channels] $i done"

@@ -15,11 +15,11 @@ SETB=${SETB:-"TCC_REQ_sum TCC_HIT_sum TCC_MISS_sum TCC_TAG_STALL_sum GRBM_GUI_AC
 #  SETA="TCP_UTCL1_TRANSLATION_MISS_sum TCP_UTCL1_TRANSLATION_HIT_sum TCP_TCC_READ_REQ_LATENCY_sum TCP_PENDING_STALL_CYCLES_sum GRBM_GUI_ACTIVE"
 #  SETB="TCP_UTCL1_STALL_UTCL2_REQ_OUT_OF_CREDITS_sum TCP_UTCL1_STALL_MULTI_MISS_sum TCP_UTCL1_STALL_INFLIGHT_MAX_sum TCP_UTCL1_TRANSLATION_MISS_UNDER_MISS_sum GRBM_GUI_ACTIVE")
 for i in $(seq 1 $N); do
-  rocprofv3 --pmc $SETA --output-format csv -d $O/a_$i -- python3 bench.py $HEAD > $O/a_$i.log 2>&1 || echo "[placement_pmc] set A run $i FAILED"
+  rocprofv3 --pmc $SETA --output-format csv -d $O/a_$i -- python3 bench.py --full $HEAD > $O/a_$i.log 2>&1 || echo "[placement_pmc] set A run $i FAILED"
   echo "[placement_pmc] A $i done"
 done
 for i in $(seq 1 $N); do
-  rocprofv3 --pmc $SETB --output-format csv -d $O/b_$i -- python3 bench.py $HEAD > $O/b_$i.log 2>&1 || echo "[placement_pmc] set B run $i FAILED (counter names?)"
+  rocprofv3 --pmc $SETB --output-format csv -d $O/b_$i -- python3 bench.py --full $HEAD > $O/b_$i.log 2>&1 || echo "[placement_pmc] set B run $i FAILED (counter names?)"
   echo "[placement_pmc] B $i done"
 done
 python3 - "$O" <<'PY'

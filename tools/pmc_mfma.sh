@@ -9,8 +9,8 @@ rm -rf $O && mkdir -p $O
 CNT="SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_LDS SQ_WAVES GRBM_GUI_ACTIVE"
 run() {  # section, bench arguments
   local sec=$1; shift
-  rocprofv3 --pmc $CNT --output-format csv -d $O/$sec -- python3 bench.py "$@" > $O/$sec.log 2>&1
-  python3 tools/collect_mfma_pmc.py $O/$sec $O/${TAG}_mfma_pmc.json $sec "python3 bench.py $*" >> $O/summary.txt
+  rocprofv3 --pmc $CNT --output-format csv -d $O/$sec -- python3 bench.py --full "$@" > $O/$sec.log 2>&1
+  python3 tools/collect_mfma_pmc.py $O/$sec $O/${TAG}_mfma_pmc.json $sec "python3 bench.py --full $*" >> $O/summary.txt
   echo "[pmc_mfma] $sec done"
 }
 run wikimel_b4096 --steps 3 --warmup 1 --no-cpu-baseline --legs none

@@ -15,11 +15,11 @@ SQ="SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_AN
 SQ2="SQ_INSTS_VALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_SCA SQ_WAIT_INST_LDS"
 run() {  # section, bench arguments
   local sec=$1; shift
-  rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/${sec}_fetch -- python3 bench.py "$@" $HEAD > $O/${sec}_fetch.log 2>&1 || { echo "[pmc_stream] $sec fetch FAILED"; return 1; }
-  rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/${sec}_write -- python3 bench.py "$@" $HEAD > $O/${sec}_write.log 2>&1 || { echo "[pmc_stream] $sec write FAILED"; return 1; }
-  python3 tools/collect_pmc.py $O/${sec}_fetch $O/${sec}_write $O/${TAG}_hbm_traffic.json kernels_$sec "python3 bench.py $* $HEAD" >> $O/hbm_traffic.txt
-  rocprofv3 --pmc $SQ --output-format csv -d $O/${sec}_sq -- python3 bench.py "$@" $HEAD > $O/${sec}_sq.log 2>&1 || echo "[pmc_stream] $sec SQ pass FAILED"
-  rocprofv3 --pmc $SQ2 --output-format csv -d $O/${sec}_sq2 -- python3 bench.py "$@" $HEAD > $O/${sec}_sq2.log 2>&1 || echo "[pmc_stream] $sec SQ2 pass FAILED (counter names?)"
+  rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/${sec}_fetch -- python3 bench.py --full "$@" $HEAD > $O/${sec}_fetch.log 2>&1 || { echo "[pmc_stream] $sec fetch FAILED"; return 1; }
+  rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/${sec}_write -- python3 bench.py --full "$@" $HEAD > $O/${sec}_write.log 2>&1 || { echo "[pmc_stream] $sec write FAILED"; return 1; }
+  python3 tools/collect_pmc.py $O/${sec}_fetch $O/${sec}_write $O/${TAG}_hbm_traffic.json kernels_$sec "python3 bench.py --full $* $HEAD" >> $O/hbm_traffic.txt
+  rocprofv3 --pmc $SQ --output-format csv -d $O/${sec}_sq -- python3 bench.py --full "$@" $HEAD > $O/${sec}_sq.log 2>&1 || echo "[pmc_stream] $sec SQ pass FAILED"
+  rocprofv3 --pmc $SQ2 --output-format csv -d $O/${sec}_sq2 -- python3 bench.py --full "$@" $HEAD > $O/${sec}_sq2.log 2>&1 || echo "[pmc_stream] $sec SQ2 pass FAILED (counter names?)"
   echo "[pmc_stream] $sec done"
 }
 run bf16_features --features bf16 || exit 1

@@ -7,13 +7,13 @@ python -m pytest tests/test_gpu_round5.py tests/test_gpu_parity.py -m gpu -x -q 
 H="--steps 10 --warmup 3 --no-cpu-baseline --legs none"
 TAB="--workload table --batch 4096 --entity-cache --steps 5 --warmup 2 --no-cpu-baseline --legs none"
 for i in 1 2; do
-  python bench.py $H --legs-file $O/head_rows_$i.json > /dev/null 2>> $O/err.log
-  DRIN_ROWS_FINAL=0 python bench.py $H --legs-file $O/head_two_$i.json > /dev/null 2>> $O/err.log
-  python bench.py $TAB --legs-file $O/tab_rows_$i.json > /dev/null 2>> $O/err.log
-  DRIN_ROWS_FINAL=0 python bench.py $TAB --legs-file $O/tab_two_$i.json > /dev/null 2>> $O/err.log
+  python bench.py --full $H --legs-file $O/head_rows_$i.json > /dev/null 2>> $O/err.log
+  DRIN_ROWS_FINAL=0 python bench.py --full $H --legs-file $O/head_two_$i.json > /dev/null 2>> $O/err.log
+  python bench.py --full $TAB --legs-file $O/tab_rows_$i.json > /dev/null 2>> $O/err.log
+  DRIN_ROWS_FINAL=0 python bench.py --full $TAB --legs-file $O/tab_two_$i.json > /dev/null 2>> $O/err.log
 done
-DRIN_LIB_PATH=$PWD/drin_amd/libdrin_hip_rowsstub.so python bench.py $H --legs-file $O/head_stub_1.json > /dev/null 2>> $O/err.log
-DRIN_LIB_PATH=$PWD/drin_amd/libdrin_hip_rowsstub.so python bench.py $TAB --legs-file $O/tab_stub_1.json > /dev/null 2>> $O/err.log
+DRIN_LIB_PATH=$PWD/drin_amd/libdrin_hip_rowsstub.so python bench.py --full $H --legs-file $O/head_stub_1.json > /dev/null 2>> $O/err.log
+DRIN_LIB_PATH=$PWD/drin_amd/libdrin_hip_rowsstub.so python bench.py --full $TAB --legs-file $O/tab_stub_1.json > /dev/null 2>> $O/err.log
 python - "$O" <<'PY'
 import json, glob, sys
 for f in sorted(glob.glob(sys.argv[1] + "/*.json")):

@@ -8,7 +8,7 @@ echo "pytest rc=$?" >> $O/gpu_tests.log
 tail -3 $O/gpu_tests.log
 bash tools/train_quick.sh > $O/train_quick.txt 2>&1 && cat $O/train_quick.txt
 for m in forward none backward both; do
-  DRIN_OVERLAP=$m python bench.py --mode train --batch 64 --force-collective > $O/b64_rccl_world1_$m.json 2>> $O/err.log
+  DRIN_OVERLAP=$m python bench.py --full --mode train --batch 64 --force-collective > $O/b64_rccl_world1_$m.json 2>> $O/err.log
 done
 python - <<'PY'
 import json

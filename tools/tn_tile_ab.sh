@@ -5,11 +5,11 @@ O=gpurun_out/tn_ab
 mkdir -p $O
 for i in 1 2 3; do
   for t in 128 256; do
-    DRIN_TN_TILE=$t python bench.py --mode train --batch 64 > $O/b64_t${t}_$i.json 2>> $O/err.log
+    DRIN_TN_TILE=$t python bench.py --full --mode train --batch 64 > $O/b64_t${t}_$i.json 2>> $O/err.log
   done
 done
 for t in 128 256; do
-  DRIN_TN_TILE=$t python bench.py --mode train --batch 512 > $O/b512_t${t}.json 2>> $O/err.log
+  DRIN_TN_TILE=$t python bench.py --full --mode train --batch 512 > $O/b512_t${t}.json 2>> $O/err.log
 done
 python - <<'PY'
 import json, glob

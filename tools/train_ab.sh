@@ -5,11 +5,11 @@ set -e
 O=gpurun_out/train_ab
 mkdir -p $O
 for i in 1 2 3; do
-  python bench.py --mode train --batch 64 > $O/folded_$i.json 2>> $O/err.log
-  DRIN_UNFOLDED=1 python bench.py --mode train --batch 64 > $O/unfolded_$i.json 2>> $O/err.log
+  python bench.py --full --mode train --batch 64 > $O/folded_$i.json 2>> $O/err.log
+  DRIN_UNFOLDED=1 python bench.py --full --mode train --batch 64 > $O/unfolded_$i.json 2>> $O/err.log
 done
-python bench.py --mode train --batch 64 --torch-adam > $O/folded_torchadam.json 2>> $O/err.log
-python bench.py --mode train --batch 64 --graph --torch-adam > $O/folded_graph.json 2>> $O/err.log || true
+python bench.py --full --mode train --batch 64 --torch-adam > $O/folded_torchadam.json 2>> $O/err.log
+python bench.py --full --mode train --batch 64 --graph --torch-adam > $O/folded_graph.json 2>> $O/err.log || true
 python - <<'PY'
 import json, glob
 for f in sorted(glob.glob("gpurun_out/train_ab/*.json")):

@@ -3,9 +3,9 @@
 set -e
 O=gpurun_out/train_quick
 mkdir -p $O
-for i in 1 2 3; do python bench.py --mode train --batch 64 > $O/b64_$i.json 2>> $O/err.log; done
-python bench.py --mode train --batch 512 > $O/b512.json 2>> $O/err.log
-python bench.py --mode train --batch 512 --train-form table > $O/b512_table.json 2>> $O/err.log
+for i in 1 2 3; do python bench.py --full --mode train --batch 64 > $O/b64_$i.json 2>> $O/err.log; done
+python bench.py --full --mode train --batch 512 > $O/b512.json 2>> $O/err.log
+python bench.py --full --mode train --batch 512 --train-form table > $O/b512_table.json 2>> $O/err.log
 python - <<'PY'
 import json, glob
 for f in sorted(glob.glob("gpurun_out/train_quick/*.json")):

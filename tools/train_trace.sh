@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 B=${1:-64}
 O=gpurun_out/train_trace
 rm -rf $O && mkdir -p $O
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/t -- python3 bench.py --mode train --batch $B --steps 20 --warmup 30 > $O/bench_under_rocprof.json 2> $O/err.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/t -- python3 bench.py --full --mode train --batch $B --steps 20 --warmup 30 > $O/bench_under_rocprof.json 2> $O/err.log
 python3 - <<'PY'
 import csv, glob
 f = glob.glob("gpurun_out/train_trace/t/*/*kernel_stats.csv")[0]

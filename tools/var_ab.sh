@@ -6,7 +6,7 @@ rm -rf $O; mkdir -p $O
 for i in 1 2 3 4; do
   for v in cur var; do
     if [ $v = var ]; then export DRIN_LIB_PATH=$PWD/drin_amd/libdrin_hip_var.so; else unset DRIN_LIB_PATH; fi
-    python bench.py --legs none --no-cpu-baseline --steps 10 --warmup 3 $EXTRA > $O/${v}_$i.json 2>> $O/err.log
+    python bench.py --full --legs none --no-cpu-baseline --steps 10 --warmup 3 $EXTRA > $O/${v}_$i.json 2>> $O/err.log
     python - "$O/${v}_$i.json" "$v $i" <<'PY'
 import json, sys
 l = json.load(open(sys.argv[1]))

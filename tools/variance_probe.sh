@@ -9,7 +9,7 @@ N=${RUNS:-16}
 for i in $(seq 1 $N); do
   for v in "$@"; do
     if [ "$v" = "-" ]; then e=""; else e="$v"; fi
-    env $e python bench.py --legs none --no-cpu-baseline --steps 8 --warmup 2 > $O/run_${i}_$v.json 2>> $O/err.log
+    env $e python bench.py --full --legs none --no-cpu-baseline --steps 8 --warmup 2 > $O/run_${i}_$v.json 2>> $O/err.log
     python - "$O/run_${i}_$v.json" "$i $v" <<'PY'
 import json, sys
 l = json.load(open(sys.argv[1]))

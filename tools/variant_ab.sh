@@ -8,11 +8,11 @@ O=gpurun_out/variant_ab_$V
 mkdir -p $O
 for i in 1 2 3; do
   for b in 64 512; do
-    python bench.py --mode train --batch $b > $O/new_train${b}_$i.json 2>> $O/err.log
-    DRIN_LIB_PATH=$PWD/drin_amd/libdrin_hip_$V.so python bench.py --mode train --batch $b > $O/${V}_train${b}_$i.json 2>> $O/err.log
+    python bench.py --full --mode train --batch $b > $O/new_train${b}_$i.json 2>> $O/err.log
+    DRIN_LIB_PATH=$PWD/drin_amd/libdrin_hip_$V.so python bench.py --full --mode train --batch $b > $O/${V}_train${b}_$i.json 2>> $O/err.log
   done
-  python bench.py --legs none --no-cpu-baseline --steps 10 --precision $P > $O/new_score_$i.json 2>> $O/err.log
-  DRIN_LIB_PATH=$PWD/drin_amd/libdrin_hip_$V.so python bench.py --legs none --no-cpu-baseline --steps 10 --precision $P > $O/${V}_score_$i.json 2>> $O/err.log
+  python bench.py --full --legs none --no-cpu-baseline --steps 10 --precision $P > $O/new_score_$i.json 2>> $O/err.log
+  DRIN_LIB_PATH=$PWD/drin_amd/libdrin_hip_$V.so python bench.py --full --legs none --no-cpu-baseline --steps 10 --precision $P > $O/${V}_score_$i.json 2>> $O/err.log
 done
 python - "$O" <<'PY'
 import json, glob, sys

@@ -95,15 +95,11 @@ __device__ __forceinline__ void split_bf16x4(float4 v, bf16x4_t& hi, bf16x4_t& l
 
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 // once-read streaming loads (entity rows of k_entity_stream): non-temporal cache policy
-#ifdef DRIN_NO_NT_LOADS
-__device__ __forceinline__ float4 ld4_stream(const float* p) { return ld4(p); }
-#else
 __device__ __forceinline__ float4 ld4_stream(const float* p) {
   typedef float f4_t __attribute__((ext_vector_type(4)));
   const f4_t v = __builtin_nontemporal_load(reinterpret_cast<const f4_t*>(p));
   return make_float4(v[0], v[1], v[2], v[3]);
 }
-#endif
 // features stored as bf16 (drin_config.feature_dtype): four values in 8 bytes, widened exactly
 __device__ __forceinline__ float4 ld4(const __bf16* p) {
   typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
@@ -112,30 +108,18 @@ __device__ __forceinline__ float4 ld4(const __bf16* p) {
 }
 __device__ __forceinline__ float4 ld4_stream(const __bf16* p) {
   typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
-#ifdef DRIN_NO_NT_LOADS
-  const bf16x4_t v = *reinterpret_cast<const bf16x4_t*>(p);
-#else
   const bf16x4_t v = __builtin_nontemporal_load(reinterpret_cast<const bf16x4_t*>(p));
-#endif
   return make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
 }
 // sixteen raw bytes (eight bf16) per lane with the streaming policy: the flat walk of bf16 token rows (fused_kernels.hip)
 typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ u32x4_t ld16_stream(const char* p) {
-#ifdef DRIN_NO_NT_LOADS
-  return *reinterpret_cast<const u32x4_t*>(p);
-#else
   return __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(p));
-#endif
 }
 // eight raw bytes (four fp16 of a DRIN_CACHE_MIXED_F16 row) per lane, same policy
 typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ u32x2_t ld8_stream(const char* p) {
-#ifdef DRIN_NO_NT_LOADS
-  return *reinterpret_cast<const u32x2_t*>(p);
-#else
   return __builtin_nontemporal_load(reinterpret_cast<const u32x2_t*>(p));
-#endif
 }
 // four fp16 values in two dwords <-> float4 (widening is exact; narrowing rounds to nearest even)
 __device__ __forceinline__ float4 f16x4_to_float4(uint32_t a, uint32_t b) {

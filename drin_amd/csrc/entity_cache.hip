@@ -40,8 +40,6 @@
 // ten times the error for 4 % of the chunk time is the wrong trade on a 1e-4 bar: profiles/r4_mixed_cache_ab.txt.)
 #include <string.h>
 
-#include <stdlib.h>
-
 #include "fused.h"
 #include "internal.h"
 #include "layout.h"
@@ -230,9 +228,7 @@ __global__ void __launch_bounds__(256) k_check_entity_index(const int64_t* __res
 }
 
 // grid (chunks, B), 256 threads; wave w takes candidates c0 + w, c0 + w + 4, ... of its chunk
-#ifndef DRIN_CACHED_PAIRS_WG_PER_CU
-#define DRIN_CACHED_PAIRS_WG_PER_CU 2
-#endif
+constexpr int kCachedPairsWgPerCu = 2;
 // EXACT: D = 256 DV and R = 256 RV exactly (768 / 2048) - the column guards of the row helpers fold away and the
 // loop body becomes straight-line code
 // the edge-phase operands of one cache row: 17 KB of the 23.5 KB fp32 row; in the mixed format 10.2 KB - c^ and the raw
@@ -259,7 +255,7 @@ struct CachedPairRow<DV, RV, true> {
 
 // MIXED: rows in the DRIN_CACHE_MIXED_F16 format (RV even)
 template <int DV, int RV, bool EXACT, bool GENERIC_ACT = false, bool MIXED = false>
-__global__ void __launch_bounds__(256, DRIN_CACHED_PAIRS_WG_PER_CU) k_cached_pairs(const CachedArgs a) {
+__global__ void __launch_bounds__(256, kCachedPairsWgPerCu) k_cached_pairs(const CachedArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int D4 = EXACT ? DV * 64 : a.D4, R4 = EXACT ? RV * 64 : a.R4, D = D4 * 4, R = R4 * 4;
   float* l_s = lds;               // [D]   span mean / max(|.|, eps)
@@ -562,17 +558,12 @@ __global__ void __launch_bounds__(256) k_mention_layer1_cached(const float* __re
 // 256 mentions 2.44 / 2.29 / 2.38, 1 024 mentions 9.7 / 9.45 / 9.38, 4 096 mentions 38.0 / 35.3 / 35.1 (k_cached_pairs 21.6 -> 19.5 ms,
 // the row kernels behind it 4.16 -> 3.35): profiles/r3_cached_chunk_ab.txt.  (Round 2's "64 candidates: slower" was a version that
 // lost the index / row look-ahead at the group boundary.)
-static int cached_chunk_default(const drin_config& c) { return c.batch >= 2048 ? 128 : 64; }
-
-// Candidates per workgroup of the cached path's kernels.  16 unless the exact-width kernel runs (see k_cached_pairs) on a
-// call large enough that the mentions alone fill the chip; DRIN_CACHED_CHUNK = candidates (multiple of 16) for probes.
+// Candidates per workgroup of the cached path's kernels: 16 unless the exact-width kernel runs (see k_cached_pairs), then 64, or
+// 128 on a call large enough that the mentions alone fill the chip.
 static int cached_chunk_candidates(const drin_config& c) {
   const bool exact = c.embed_dim == 768 && c.image_dim == 2048 && vertex_act(&c) == DRIN_ACT_GELU;
   if (!exact) return 16;
-  static const char* cc_env = getenv("DRIN_CACHED_CHUNK");
-  const int per = cc_env ? atoi(cc_env) : 0;
-  if (per >= 16) return per - per % 16;
-  return cached_chunk_default(c);
+  return c.batch >= 2048 ? 128 : 64;
 }
 
 struct CachedLayout {  // workspace of drin_forward_cached, offsets in floats
@@ -938,11 +929,6 @@ DRIN_API int drin_forward_cached(const drin_config* cfg, const drin_batch* b, co
   fa.N = N;
   fa.D4 = D / 4;
   fa.chunks = L.chunks;
-  {
-    static const char* fc_env = getenv("DRIN_CACHED_FINAL_CHUNK");   // probe: k_pair_final alone (it reads no partial sums)
-    const int per = fc_env ? atoi(fc_env) : 0;
-    if (per >= 16) fa.chunks = (int)cdiv(N, per);
-  }
   fa.ln_eps = cfg->layer_norm_eps;
   fa.act_v = vertex_act(cfg);
   fa.cos_eps = cfg->cosine_eps;

@@ -17,10 +17,7 @@
 // 5.5 MFLOP - plus ONE streaming pass over the entity bytes (k_entity_stream) and two row kernels.
 // The folded matrices depend only on the weights: drin_prepare computes them once per weight version
 // into a caller-owned buffer.
-#include <stdlib.h>
 #include <string.h>
-
-#include <algorithm>
 
 #include "fused.h"
 #include "internal.h"
@@ -45,11 +42,6 @@ struct FusedLayout {  // workspace offsets in floats
     // mention's scores in a small and in a large call differ by fp32 re-association (as through the tile choices of the
     // mention-sized products), within one call size they are the same bits every run.
     chunks = (int)(B >= 2048 ? (N + 127) / 128 : B >= 1024 ? (N + 47) / 48 : (N + 15) / 16);   // (1 024 mentions: 48 candidates, 4.56 -> 4.49 ms)
-    {
-      static const char* sc_env = getenv("DRIN_STREAM_CHUNK");   // probe: candidates per workgroup of the stream kernel
-      const int per = sc_env ? atoi(sc_env) : 0;
-      if (per >= 16) chunks = (int)((N + per - 1) / per);
-    }
     size_t off = 0;
     auto take = [&off](size_t n) {
       const size_t o = off;
@@ -476,13 +468,7 @@ static int forward_prepared_on_stream(const drin_config* cfg, const drin_batch* 
   }
   // The two pair kernels walk the same candidate chunks as the stream kernel (FusedLayout::chunks: whole mentions from 2 048
   // mentions up - their share of that change: row kernels 1.385 -> 1.27 ms at 4 096 mentions; 64 mentions with whole-mention
-  // workgroups 0.55 -> 0.63 ms, which is why small calls keep 16 candidates).  DRIN_PAIR_CHUNK = candidates per workgroup (probes).
-  int pair_chunks = L.chunks;
-  {
-    static const char* pc_env = getenv("DRIN_PAIR_CHUNK");
-    const int per = pc_env ? atoi(pc_env) : 0;
-    if (per >= 16) pair_chunks = std::max(1, std::min(L.chunks, (int)cdiv(N, per)));
-  }
+  // workgroups 0.55 -> 0.63 ms, which is why small calls keep 16 candidates).
   // (6) layer-1 entity vertices + layer-2 mention aggregates
   PairArgs pa;
   memset(&pa, 0, sizeof(pa));
@@ -505,12 +491,12 @@ static int forward_prepared_on_stream(const drin_config* cfg, const drin_batch* 
   pa.B = B;
   pa.N = N;
   pa.D4 = D / 4;
-  pa.chunks = pair_chunks;
+  pa.chunks = L.chunks;
   pa.ln_eps = cfg->layer_norm_eps;
   pa.act_v = vertex_act(cfg);
   DRIN_TRY(launch_pair_layer1(pa, st));
   // (7) layer-2 mention-text vertex
-  DRIN_TRY(launch_mention_input2(ws + L.s2_part, vm1, ws + L.agg2, B, D, N, pair_chunks, st));
+  DRIN_TRY(launch_mention_input2(ws + L.s2_part, vm1, ws + L.agg2, B, D, N, L.chunks, st));
   DRIN_TRY(lin(ws + L.agg2, D, L2.w_h, D, P.p_wh2, DD, L2.b_h, ws + L.mt2, D, B, D, D));
   DRIN_TRY(launch_layernorm_gelu(ws + L.mt2, L2.ln_weight, L2.ln_bias, ws + L.mt2, nullptr, nullptr, B, D, cfg->layer_norm_eps, st,
                                  vertex_act(cfg)));
@@ -539,7 +525,7 @@ static int forward_prepared_on_stream(const drin_config* cfg, const drin_batch* 
   fa.B = B;
   fa.N = N;
   fa.D4 = D / 4;
-  fa.chunks = pair_chunks;
+  fa.chunks = L.chunks;
   fa.ln_eps = cfg->layer_norm_eps;
   fa.act_v = vertex_act(cfg);
   fa.cos_eps = cfg->cosine_eps;

@@ -20,19 +20,9 @@ namespace drin {
 // the bytes of this HBM-bound pass; all arithmetic stays fp32)
 // XSCALE: also hand over the image row as ONE fp16 plane under a power-of-two scale per row (DRIN_PREC_BF16X3_IF16) - a separate
 // instantiation, so that the code (and the register allocation: 230 VGPRs) of every other call is what it was
-#ifdef DRIN_STREAM_STAMPS   // probe build (tools/stream_stamps_probe.py): cycle stamps of 64 workgroups, wave 0
-__device__ unsigned long long g_stream_stamps[64 * 8];
-#define STREAM_STAMP(i)                                                                                        \
-  if (threadIdx.x == 0 && blockIdx.x == 0 && (blockIdx.y % (gridDim.y / 64 ? gridDim.y / 64 : 1)) == 0 &&       \
-      blockIdx.y / (gridDim.y / 64 ? gridDim.y / 64 : 1) < 64)                                                   \
-  g_stream_stamps[(blockIdx.y / (gridDim.y / 64 ? gridDim.y / 64 : 1)) * 8 + (i)] = __builtin_readcyclecounter()
-#else
-#define STREAM_STAMP(i)
-#endif
 template <int DV, int RV, bool TOKENS, bool EXACT, typename FT, bool XSCALE = false>
 __global__ void __launch_bounds__(256, 2) k_entity_stream(const StreamArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  STREAM_STAMP(0);
   const FT* const f_text = static_cast<const FT*>(a.entity_text);
   const FT* const f_image = static_cast<const FT*>(a.entity_image);
   const FT* const f_object = static_cast<const FT*>(a.entity_object);
@@ -76,7 +66,6 @@ __global__ void __launch_bounds__(256, 2) k_entity_stream(const StreamArgs a) {
   //  22.7 k cycles of 82 k, the kernel 1.16 -> 1.23 ms.  The stage does not wait for dependent round trips: its loads queue behind
   //  the ~100 KB the CU's other workgroup keeps in flight, and a burst of 2 048 of them queues longer.)
   __syncthreads();
-  STREAM_STAMP(1);
   for (int i = wave; i < a.Km; i += 4) {  // |mobj_i| (model.py:88: every pair re-normalises the same rows)
     float s = 0.f;
     for (int c4 = lane; c4 < R4; c4 += 64) {
@@ -101,9 +90,7 @@ __global__ void __launch_bounds__(256, 2) k_entity_stream(const StreamArgs a) {
     kap_it = wave_sum(dot_rows<DV>(fu_i, k_t));
     kap_ii = wave_sum(dot_rows<DV>(fu_i, k_i));
   }
-  STREAM_STAMP(2);
   __syncthreads();
-  STREAM_STAMP(3);
 
   Row<DV> S_tt = zero_row<DV>(), S_it = zero_row<DV>();
   Row<RV> S_ti = zero_row<RV>(), S_ii = zero_row<RV>();
@@ -313,7 +300,6 @@ __global__ void __launch_bounds__(256, 2) k_entity_stream(const StreamArgs a) {
     sg_ii += e_ii;
   }
 
-  STREAM_STAMP(4);
   // ---- fixed-order cross-wave reduction through LDS, then one partial per (mention, chunk) -----------
   for (int w = 0; w < 4; ++w) {
     __syncthreads();
@@ -348,7 +334,6 @@ __global__ void __launch_bounds__(256, 2) k_entity_stream(const StreamArgs a) {
     }
   }
   __syncthreads();
-  STREAM_STAMP(5);
   if (a.chunks == 1) {
     // short candidate lists (N <= 16, WikiDiverse): the workgroup holds the whole mention - write the layout
     // the mention-side GEMMs read and skip the partial buffer and its reduction pass
@@ -361,21 +346,12 @@ __global__ void __launch_bounds__(256, 2) k_entity_stream(const StreamArgs a) {
       st4(a.s_img + ((int64_t)which * a.B + b) * R + c4 * 4, ld4(l_red + 2 * D + i * 4));
     }
     if (threadIdx.x < 4) a.sig[(int64_t)threadIdx.x * a.B + b] = l_small[a.Km + threadIdx.x];
-    STREAM_STAMP(6);
     return;
   }
   float* out = a.s_part + (b * a.chunks + blockIdx.x) * (int64_t)(2 * D + 2 * R + 4);
   for (int i = threadIdx.x; i < (2 * D + 2 * R) / 4; i += 256) st4(out + i * 4, ld4(l_red + i * 4));
   if (threadIdx.x < 4) out[2 * D + 2 * R + threadIdx.x] = l_small[a.Km + threadIdx.x];
 }
-
-#ifdef DRIN_STREAM_STAMPS
-}  // namespace drin
-extern "C" __attribute__((visibility("default"))) int drin_debug_stream_stamps(unsigned long long* host_out) {
-  return (int)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(drin::g_stream_stamps), sizeof(unsigned long long) * 64 * 8);
-}
-namespace drin {
-#endif
 
 size_t entity_stream_lds_bytes(const StreamArgs& a) {
   const size_t D = (size_t)a.D4 * 4, R = (size_t)a.R4 * 4;
@@ -557,23 +533,13 @@ __global__ void __launch_bounds__(256) k_pair_layer1(const PairArgs a) {
   Row<DV> S_t = zero_row<DV>(), S_i = zero_row<DV>();
   for (int n = n_begin + wave; n < n_end; n += 4) {
     const int64_t p = b * a.N + n;
-#ifdef DRIN_ABLATE_ROW_TRAFFIC   // timing ablation only (wrong results): the same arithmetic on four cache-resident rows, nothing stored
-    const int64_t p_ld = b * a.N + (n & 3);
-    const Row<DV> ht = load_row<DV>(a.h_text + p_ld * D, lane, D4);
-    const Row<DV> hi = load_row<DV>(a.h_image + p_ld * D, lane, D4);
-#else
     const Row<DV> ht = load_row_stream<DV>(a.h_text + p * D, lane, D4);  // read once: streaming cache policy
     const Row<DV> hi = load_row_stream<DV>(a.h_image + p * D, lane, D4);
-#endif
     const float e_tt = a.e0m[p], e_ti = a.e0m[M + p], e_it = a.e0m[2 * M + p], e_ii = a.e0m[3 * M + p];
     const Row<DV> et1 = ln_gelu_row_lds<DV, GENERIC_ACT>(combine_rows_lds<DV>(ht, e_tt, l_hm_t, e_it, l_hm_i, l_ct, lane, D4),
                                                          l_gamma, l_beta, lane, D4, a.ln_eps, a.act_v);
-#ifdef DRIN_ABLATE_ROW_TRAFFIC
-    if (a.ln_eps < 0.f) store_row_planes<DV>(a.et1_hi, a.et1_lo, p * D, et1, lane, D4);   // never: keeps the values live
-#else
     if (a.et1) store_row<DV>(a.et1 + p * D, et1, lane, D4);
     if (a.et1_hi) store_row_planes<DV>(a.et1_hi, a.et1_lo, p * D, et1, lane, D4);
-#endif
     axpy_row_pk<DV>(S_t, a.e1m[p], et1);
     const Row<DV> ei1 = ln_gelu_row_lds<DV, GENERIC_ACT>(combine_rows_lds<DV>(hi, e_ti, l_hm_t, e_ii, l_hm_i, l_ci, lane, D4),
                                                          l_gamma, l_beta, lane, D4, a.ln_eps, a.act_v);
@@ -675,11 +641,7 @@ __global__ void __launch_bounds__(256) k_pair_final(const FinalArgs a) {
   const float xx = wave_sum(dot_rows<DV>(mt2, mt2));
   for (int n = n_begin + wave; n < n_end; n += 4) {
     const int64_t p = b * a.N + n;
-#ifdef DRIN_ABLATE_ROW_TRAFFIC
-    const Row<DV> h = load_row<DV>(a.h2 + (b * a.N + (n & 3)) * D, lane, D4);
-#else
     const Row<DV> h = load_row_stream<DV>(a.h2 + p * D, lane, D4);
-#endif
     const Row<DV> et2 = ln_gelu_row_lds<DV, GENERIC_ACT>(
         combine_rows_lds<DV>(h, a.e1m[p], l_const, a.e1m[2 * M + p], l_const + LD, l_const + 2 * LD, lane, D4),
         l_const + 3 * LD, l_const + 4 * LD, lane, D4, a.ln_eps, a.act_v);

@@ -253,28 +253,18 @@ __global__ void __launch_bounds__(64 * WM * WN, (64 * WM * WN) / 256)
     const char* buf = smem + cur * G::BUF_BYTES;
     char* nb = smem + (cur ^ 1) * G::BUF_BYTES;
     const bool more = kb + 1 < nkb;
-#ifndef DRIN_ABLATE_NO_LOADS   // timing ablations only (wrong results): the K-loop without its global traffic / without its MFMAs
     if (W_PLANES && more) dma.template issue<true>(nb + 2 * G::A_PLANE, kb + 1);
-#endif
     load_b(buf);
-#ifndef DRIN_ABLATE_NO_MFMA
     row_tiles(buf, 0, G::MI / 2);
-#endif
     if (more) {
       stage_a(nb);
       if (!W_PLANES) sb.store(nb + 2 * G::A_PLANE, nb + 2 * G::A_PLANE + G::B_PLANE);
-#ifndef DRIN_ABLATE_NO_LOADS
       if (kb + 2 < nkb) {
         sa.load((kb + 2) * KSTEP);
         if (!W_PLANES) sb.load((kb + 2) * KSTEP);
       }
-#endif
     }
-#ifndef DRIN_ABLATE_NO_MFMA
     row_tiles(buf, G::MI / 2, G::MI);
-#else
-    row_tiles(buf, 0, 1);
-#endif
     // (a counted wait that keeps the register loads of block kb + 2 outstanding across a raw barrier measured inside 1 % of this
     //  either way for the three-pass product - profiles/r4_one_pass_ab.txt)
     __syncthreads();

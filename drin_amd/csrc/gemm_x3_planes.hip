@@ -115,7 +115,7 @@ __device__ __forceinline__ Pieces make_pieces(const __bf16* a_hi, const __bf16* 
 // (Tried: weight fragments fetched straight into registers by global_load_dwordx4 - a lane's fragment of the
 // K-contiguous planes is 16 contiguous bytes - so that the weights never touch LDS: 291 vs 346 TF/s on the same box.
 // The K-loop is not LDS-bound; the extra vector-memory traffic costs more than the LDS traffic it removes.
-// Cycle stamps (-DDRIN_STAMPS, tools/stamps_probe.py) of one tile at K = 768: prologue 6 k cycles, K-loop 109 k (4 400
+// Cycle stamps of one tile at K = 768: prologue 6 k cycles, K-loop 109 k (4 400
 // per K-block against 3 072 of pure MFMA issue: ~300 of fragment reads before the first MFMA, ~700 of barrier skew),
 // epilogue 24 k.  Tried against that: a mid-block barrier that publishes the next block early so that its first
 // fragments are prefetched across the block boundary (-8 %: the second barrier costs more than the bubble), a
@@ -123,9 +123,6 @@ __device__ __forceinline__ Pieces make_pieces(const __bf16* a_hi, const __bf16* 
 // Also tried: persistent workgroups (one per CU walking a tile list, the next tile's first K-block requested before
 // the epilogue of the finished one): 1411 vs 1365 us at 413 696 x 768 x 768 - the hardware's dynamic dispatch of
 // 4 848 independent tiles balances better than a static list, and the fill it would hide is small.)
-#ifdef DRIN_STAMPS
-__device__ unsigned long long g_stamps[8 * 64 * 4 + 64];  // [wave][kb][4]: loop top, first MFMA issued, last MFMA issued, after barrier
-#endif
 template <bool A_LO, bool B_LO>
 __global__ void __launch_bounds__(THREADS, 2)
     k_gemm_x3_planes(const __bf16* __restrict__ a_hi, const __bf16* __restrict__ a_lo, int64_t lda,
@@ -144,9 +141,6 @@ __global__ void __launch_bounds__(THREADS, 2)
     ldc = N;
     bias = nullptr;
   }
-#ifdef DRIN_STAMPS
-  const unsigned long long t_start = __builtin_readcyclecounter();
-#endif
   int tx, kpart;
   int64_t ty;
   unsigned tail_slot;
@@ -177,15 +171,8 @@ __global__ void __launch_bounds__(THREADS, 2)
   const Pieces pieces = make_pieces(a_hi, A_LO ? a_lo : a_hi, lda, m0, M, b_hi, B_LO ? b_lo : b_hi, ldb, n0, N);
   issue_tile<A_LO, B_LO>(pieces, smem, 0);
   __syncthreads();
-#ifdef DRIN_STAMPS
-  const unsigned long long t_prologue = __builtin_readcyclecounter();
-#endif
 
   for (int kb = 0; kb < nkb; ++kb) {
-#ifdef DRIN_STAMPS
-    const bool stamp = blockIdx.x == 121 && lane == 0 && kb < 64;
-    if (stamp) g_stamps[(wave * 64 + kb) * 4 + 0] = __builtin_readcyclecounter();
-#endif
     const int cur = kb & 1;
     const char* buf = smem + cur * BUF_BYTES;
     const bool more = kb + 1 < nkb;
@@ -202,9 +189,6 @@ __global__ void __launch_bounds__(THREADS, 2)
       ah[0] = *reinterpret_cast<const bf16x8*>(buf + off);
       if (A_LO) al[0] = *reinterpret_cast<const bf16x8*>(buf + PLANE_BYTES + off);
     }
-#ifdef DRIN_STAMPS
-    if (stamp) g_stamps[(wave * 64 + kb) * 4 + 1] = __builtin_readcyclecounter();
-#endif
 #pragma unroll
     for (int t = 0; t < 8; ++t) {  // eight row tiles; the next one's fragments are read one stage ahead
       if (more) issue_piece<A_LO, B_LO>(pieces, nbuf, kb + 1, t);
@@ -225,13 +209,7 @@ __global__ void __launch_bounds__(THREADS, 2)
 #pragma unroll
       for (int j = 0; j < 4; ++j) acc[t][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh[j], ah[t & 1], acc[t][j], 0, 0, 0);
     }
-#ifdef DRIN_STAMPS
-    if (stamp) g_stamps[(wave * 64 + kb) * 4 + 2] = __builtin_readcyclecounter();
-#endif
     __syncthreads();
-#ifdef DRIN_STAMPS
-    if (stamp) g_stamps[(wave * 64 + kb) * 4 + 3] = __builtin_readcyclecounter();
-#endif
   }
 
   // The MFMAs take the WEIGHT fragment as their first operand, so a lane's four accumulator registers of a 16 x 16
@@ -268,17 +246,6 @@ __global__ void __launch_bounds__(THREADS, 2)
       }
     }
   }
-#ifdef DRIN_STAMPS
-  if (blockIdx.x == 121 && (threadIdx.x & 63) == 0) {
-    __builtin_amdgcn_s_waitcnt(0);  // stores issued and acknowledged
-    const int wv = threadIdx.x >> 6;
-    unsigned long long* o = g_stamps + 8 * 64 * 4 + wv * 4;
-    o[0] = t_start;
-    o[1] = t_prologue;
-    o[2] = g_stamps[(wv * 64 + (K / BK - 1 < 63 ? K / BK - 1 : 63)) * 4 + 3];
-    o[3] = __builtin_readcyclecounter();
-  }
-#endif
 }
 
 
@@ -311,34 +278,8 @@ __device__ __forceinline__ float4 scale_pow2(float4 v, int e) { return make_floa
 
 namespace p4 {
 
-#ifndef DRIN_P4_TERM_MAJOR
-#define DRIN_P4_TERM_MAJOR 1
-#endif
-constexpr bool kTermMajor = DRIN_P4_TERM_MAJOR != 0;
-#ifndef DRIN_P4_DMA_PLACE
-#define DRIN_P4_DMA_PLACE 0
-#endif
-constexpr int kDmaPlace = DRIN_P4_DMA_PLACE;
-#ifndef DRIN_P4_REBALANCE
-#define DRIN_P4_REBALANCE 1
-#endif
-constexpr bool kRebalance = DRIN_P4_REBALANCE != 0 && kDmaPlace == 0;   // the fp32-A kernel's phase schedule (see there)
-// fp32-A kernel, rebalanced schedule: the split of a landed activation unit (24 vector instructions + 4 LDS writes per thread) runs
-// INSIDE the MFMA half of its phase - one vector instruction per MFMA gap (an MFMA holds the SIMD's vector issue for 8 of its 16
-// cycles: MI355X_MICROARCH.md) - instead of between the counted wait and the phase's first barrier, where its ~250 cycles
-// delayed all eight waves twice per K-block.
-#ifndef DRIN_P4_SPLIT_IN_MMA
-#define DRIN_P4_SPLIT_IN_MMA 1
-#endif
-constexpr bool kSplitInMma = DRIN_P4_SPLIT_IN_MMA != 0 && kRebalance;
 // the counted wait before a phase's first barrier (two DMA / load instructions per unit per wave)
-__device__ __forceinline__ void wait_units() {
-  if (kDmaPlace == 0) {
-    asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-  } else {
-    asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-  }
-}
+__device__ __forceinline__ void wait_units() { asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); }
 constexpr int UNIT_BYTES = 2 * 128 * 64;       // two planes x 128 rows x 64 B
 constexpr int BUF = 4 * UNIT_BYTES;            // A0, A1, B0, B1
 constexpr int LDS = 2 * BUF;
@@ -369,17 +310,6 @@ __device__ __forceinline__ void issue_unit(const Src& s, char* buf, int kb) {
 // 16 x 16 tile takes two MFMAs per K-block (sub-block 0, sub-block 1: the k order of 32-wide blocks), 16 per phase, for half
 // the K-blocks.  Row m of A was divided by row_scale[m] and B by *b_scale when their planes were written (powers of two: exact;
 // fp16's range never matters): the epilogue multiplies output row m by row_scale[m] * *b_scale.
-// -DDRIN_P4_STAMPS (tools/probes/p4_stamps_probe.py): cycle stamps of one workgroup (block 121 of a launch of more than 100 000 rows) of
-// the two four-phase kernels - per K-block and phase: phase start, after the first barrier (MFMAs may start), after the MFMAs - for one
-// wave of each wave group.  Stamps sit only where the wave has no LDS read in flight anyway (s_memtime counts in lgkmcnt).
-#ifdef DRIN_P4_STAMPS
-__device__ unsigned long long g_p4_stamps[2 * 2 * 32 * 4 * 3];   // [kernel: 0 planes, 1 fp32-A][wave group][K-block][phase][point]
-#define DRIN_P4_STAMP(KERNEL, KB, PHASE, POINT)                                                                               \
-  if (stamp_on && (KB) < 32)                                                                                                  \
-    g_p4_stamps[((((KERNEL) * 2 + (int)(threadIdx.x >> 8)) * 32 + (KB)) * 4 + (PHASE)) * 3 + (POINT)] = __builtin_readcyclecounter()
-#else
-#define DRIN_P4_STAMP(KERNEL, KB, PHASE, POINT)
-#endif
 template <bool A_LO = true, bool F16 = false>
 __global__ void __launch_bounds__(THREADS, 2)
     k_gemm_x3_planes_p4(const __bf16* __restrict__ a_hi, const __bf16* __restrict__ a_lo, int64_t lda,
@@ -459,7 +389,7 @@ __global__ void __launch_bounds__(THREADS, 2)
       bl[j] = *reinterpret_cast<const bf16x8*>(p + 128 * 64);
     }
   };
-  auto mma = [&](f32x4 (&cc)[4][2], auto&& mid) {
+  auto mma = [&](f32x4 (&cc)[4][2]) {
     __builtin_amdgcn_s_setprio(1);
     if constexpr (F16) {   // (ah, bh): k sub-block 0 of the 64-wide block, (al, bl): sub-block 1 - fp16 bit patterns in the planes
       typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
@@ -468,7 +398,6 @@ __global__ void __launch_bounds__(THREADS, 2)
 #pragma unroll
         for (int j = 0; j < 2; ++j)
           cc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, bh[j]), __builtin_bit_cast(f16x8, ah[i]), cc[i][j], 0, 0, 0);
-      mid();
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -479,34 +408,20 @@ __global__ void __launch_bounds__(THREADS, 2)
     }
     // term-major over the quadrant's eight tiles: an accumulator's next MFMA is eight issues away (same order of the three
     // terms per accumulator as everywhere: hi lo, lo hi, hi hi - same bits)
-    if (p4::kTermMajor) {
-      if (A_LO) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int j = 0; j < 2; ++j) cc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh[j], al[i], cc[i][j], 0, 0, 0);
-      }
-      mid();
+    if (A_LO) {
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) cc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bl[j], ah[i], cc[i][j], 0, 0, 0);
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) cc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh[j], ah[i], cc[i][j], 0, 0, 0);
-    } else {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          if (A_LO) cc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh[j], al[i], cc[i][j], 0, 0, 0);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) cc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bl[j], ah[i], cc[i][j], 0, 0, 0);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) cc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh[j], ah[i], cc[i][j], 0, 0, 0);
-      }
+        for (int j = 0; j < 2; ++j) cc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh[j], al[i], cc[i][j], 0, 0, 0);
     }
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) cc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bl[j], ah[i], cc[i][j], 0, 0, 0);
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) cc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh[j], ah[i], cc[i][j], 0, 0, 0);
     __builtin_amdgcn_s_setprio(0);
   };
   auto barrier = [&]() {
@@ -525,41 +440,30 @@ __global__ void __launch_bounds__(THREADS, 2)
 
   // Every K-block issues the units of block min(kb + 1, last): the last one fetches itself again into the idle buffer, so that
   // all blocks are the same straight-line code with the same counted wait (one block's worth of L2 reads per tile more).
-  // Where in the phase the unit's two DMA instructions go (p4::kDmaPlace): an LDS-DMA costs its wave 100-185 cycles of issue
-  // among LDS reads and ~60 among MFMAs (MI355X_MICROARCH.md), and the reading half of a phase must not outlast the other wave
-  // group's 24 MFMAs.  0: with the fragment reads; 1: behind the first barrier, before the MFMAs; 2: between the first and the
-  // second third of the MFMAs.  The unit a phase's wait must retire was issued two phases earlier: with the phase's own issue
-  // in front of the wait (0) two newer units are outstanding - vmcnt(4) - with it behind the barrier (1, 2) one - vmcnt(2).
-  auto none = [] {};
-#ifdef DRIN_P4_STAMPS
-  const bool stamp_on = blockIdx.x == 121 && M > 100000 && (threadIdx.x & 255) == 0 && !F16;
-#endif
-#define DRIN_P4_PHASE(READS, UNIT, ACC, PH)                              \
-  {                                                                      \
-    DRIN_P4_STAMP(0, kb, PH, 0);                                         \
-    READS;                                                               \
-    if (p4::kDmaPlace == 0) p4::issue_unit<UNIT, KB_BYTES>(src, nbuf, kn);         \
-    p4::wait_units();                                                    \
-    barrier();                                                           \
-    DRIN_P4_STAMP(0, kb, PH, 1);                                         \
-    if (p4::kDmaPlace == 1) p4::issue_unit<UNIT, KB_BYTES>(src, nbuf, kn);         \
-    if (p4::kDmaPlace == 2)                                              \
-      mma(ACC, [&] { p4::issue_unit<UNIT, KB_BYTES>(src, nbuf, kn); });            \
-    else                                                                 \
-      mma(ACC, none);                                                    \
-    DRIN_P4_STAMP(0, kb, PH, 2);                                         \
-    barrier();                                                           \
+  // The unit's two DMA instructions go with the fragment reads: an LDS-DMA costs its wave 100-185 cycles of issue among LDS
+  // reads and ~60 among MFMAs (MI355X_MICROARCH.md), and the reading half of a phase must not outlast the other wave group's
+  // 24 MFMAs (issuing them behind the first barrier, or between the first and the second third of the MFMAs, measured slower:
+  // profiles/r3_p4_ab.txt).  The unit a phase's wait must retire was issued two phases earlier: with the phase's own issue in
+  // front of the wait two newer units are outstanding - vmcnt(4).
+#define P4_PHASE(READS, UNIT, ACC)                 \
+  {                                                \
+    READS;                                         \
+    p4::issue_unit<UNIT, KB_BYTES>(src, nbuf, kn); \
+    p4::wait_units();                              \
+    barrier();                                     \
+    mma(ACC);                                      \
+    barrier();                                     \
   }
   for (int kb = 0; kb < nkb; ++kb) {
     const char* buf = smem + (kb & 1) * p4::BUF;
     char* nbuf = smem + ((kb + 1) & 1) * p4::BUF;
     const int kn = kb + 1 < nkb ? kb + 1 : kb;
-    DRIN_P4_PHASE((read_a(buf, 0), read_b(buf, 0)), 0, acc[0][0], 0)   // quadrant 00
-    DRIN_P4_PHASE(read_b(buf, 1), 2, acc[0][1], 1)                      // quadrant 01 (A0 fragments stay)
-    DRIN_P4_PHASE(read_a(buf, 1), 3, acc[1][1], 2)                      // quadrant 11 (B1 fragments stay)
-    DRIN_P4_PHASE(read_b(buf, 0), 1, acc[1][0], 3)                      // quadrant 10 (A1 fragments stay)
+    P4_PHASE((read_a(buf, 0), read_b(buf, 0)), 0, acc[0][0])   // quadrant 00
+    P4_PHASE(read_b(buf, 1), 2, acc[0][1])                     // quadrant 01 (A0 fragments stay)
+    P4_PHASE(read_a(buf, 1), 3, acc[1][1])                     // quadrant 11 (B1 fragments stay)
+    P4_PHASE(read_b(buf, 0), 1, acc[1][0])                     // quadrant 10 (A1 fragments stay)
   }
-#undef DRIN_P4_PHASE
+#undef P4_PHASE
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the redundant units of the last block
   if (wm == 0) barrier();   // pairs with the delayed half's last barrier
 
@@ -607,11 +511,7 @@ __global__ void __launch_bounds__(THREADS, 2)
           if (col >= N) continue;   // N % 4 == 0 (checked by the launcher)
           float4 o = make_float4(acc[a][b][i][j][0], acc[a][b][i][j][1], acc[a][b][i][j][2], acc[a][b][i][j][3]);
           if (F16) o = scale_pow2(o, rs);
-#ifdef DRIN_ABLATE_GEMM_STORES   // timing ablation only: the product without its [M, N] fp32 result leaving the chip
-          if (ldc < 0) st4(C + row * ldc + col, o + bv[b][j]);
-#else
           st4(C + row * ldc + col, o + bv[b][j]);
-#endif
         }
     }
 }
@@ -628,15 +528,7 @@ typedef __bf16 bf16x4p __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ void split_store(f32x4v v, char* hi_plane, int off) {
   bf16x4p h, l;
-#ifdef DRIN_P4_ABLATE_CVT   // timing ablation only (plain-bf16 results): a third of the split arithmetic, the same two LDS writes
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    h[k] = (__bf16)v[k];
-    l[k] = (__bf16)0.0f;
-  }
-#else
   split_bf16x4(make_float4(v[0], v[1], v[2], v[3]), h, l);
-#endif
   *reinterpret_cast<bf16x4p*>(hi_plane + off) = h;
   *reinterpret_cast<bf16x4p*>(hi_plane + 128 * 64 + off) = l;
 }
@@ -682,13 +574,12 @@ __global__ void __launch_bounds__(THREADS, 2)
       }
     src.ptr[0][0] = src.ptr[0][1] = src.ptr[1][0] = src.ptr[1][1] = nullptr;
     const int c4 = threadIdx.x & 7;
-    // which two rows of a 128-row unit this thread loads and splits.  kSplitInMma: a wave GROUP splits exactly the 64 rows its own
-    // waves read (group g: rows 64 g .. 64 g + 63), so that the split may run inside the group's MFMA half - nobody of the other
-    // group, which runs one barrier apart, ever reads what this group has not yet written.  Otherwise rows t / 8 and t / 8 + 64.
+    // which two rows of a 128-row unit this thread loads and splits: a wave GROUP splits exactly the 64 rows its own waves read
+    // (group g: rows 64 g .. 64 g + 63), so that the split may run inside the group's MFMA half - nobody of the other group,
+    // which runs one barrier apart, ever reads what this group has not yet written.
     int urow[2];
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
-      urow[i] = p4::kSplitInMma ? (int)(threadIdx.x >> 8) * 64 + (int)((threadIdx.x & 255) >> 3) + 32 * i : (int)(threadIdx.x >> 3) + 64 * i;
+    for (int i = 0; i < 2; ++i) urow[i] = (int)(threadIdx.x >> 8) * 64 + (int)((threadIdx.x & 255) >> 3) + 32 * i;
 #pragma unroll
     for (int h = 0; h < 2; ++h)
 #pragma unroll
@@ -730,36 +621,46 @@ __global__ void __launch_bounds__(THREADS, 2)
       bl[j] = *reinterpret_cast<const bf16x8*>(p + 128 * 64);
     }
   };
-  auto mma = [&](f32x4 (&cc)[4][2], auto&& mid) {
+  // term-major over the quadrant's eight tiles: an accumulator's next MFMA is eight issues away (same order of the three terms
+  // per accumulator as everywhere: hi lo, lo hi, hi hi - same bits)
+  auto mma_b = [&](f32x4 (&cc)[4][2], const bf16x8 (&fh)[2], const bf16x8 (&fl)[2]) {
     __builtin_amdgcn_s_setprio(1);
-    // term-major over the quadrant's eight tiles: an accumulator's next MFMA is eight issues away (same order of the three
-    // terms per accumulator as everywhere: hi lo, lo hi, hi hi - same bits)
-    if (p4::kTermMajor) {
 #pragma unroll
-      for (int i = 0; i < 4; ++i)
+    for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) cc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh[j], al[i], cc[i][j], 0, 0, 0);
-      mid();
+      for (int j = 0; j < 2; ++j) cc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fh[j], al[i], cc[i][j], 0, 0, 0);
 #pragma unroll
-      for (int i = 0; i < 4; ++i)
+    for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) cc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bl[j], ah[i], cc[i][j], 0, 0, 0);
+      for (int j = 0; j < 2; ++j) cc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fl[j], ah[i], cc[i][j], 0, 0, 0);
 #pragma unroll
-      for (int i = 0; i < 4; ++i)
+    for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) cc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh[j], ah[i], cc[i][j], 0, 0, 0);
-    } else {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j) cc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh[j], al[i], cc[i][j], 0, 0, 0);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) cc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bl[j], ah[i], cc[i][j], 0, 0, 0);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) cc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh[j], ah[i], cc[i][j], 0, 0, 0);
-      }
-    }
+      for (int j = 0; j < 2; ++j) cc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fh[j], ah[i], cc[i][j], 0, 0, 0);
     __builtin_amdgcn_s_setprio(0);
+  };
+  // The same MFMAs with the split of one landed activation unit (24 vector instructions + 4 LDS writes per thread) between the
+  // three groups of eight - one vector instruction per MFMA gap (an MFMA holds the SIMD's vector issue for 8 of its 16 cycles:
+  // MI355X_MICROARCH.md) - instead of between the counted wait and the phase's first barrier, where its ~250 cycles delayed all
+  // eight waves twice per K-block.
+  auto mma_split = [&](f32x4 (&cc)[4][2], const bf16x8 (&fh)[2], const bf16x8 (&fl)[2], char* dst_buf, int half, f32x4v v0, f32x4v v1) {
+    __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) cc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fh[j], al[i], cc[i][j], 0, 0, 0);
+    split_store(v0, dst_buf + half * p4::UNIT_BYTES, a_off[0]);
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) cc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fl[j], ah[i], cc[i][j], 0, 0, 0);
+    split_store(v1, dst_buf + half * p4::UNIT_BYTES, a_off[1]);
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) cc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fh[j], ah[i], cc[i][j], 0, 0, 0);
+    __builtin_amdgcn_s_setprio(0);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the planes are in LDS before the barrier that publishes them to this group
   };
   auto barrier = [&]() {
     __builtin_amdgcn_sched_barrier(0);
@@ -799,165 +700,54 @@ __global__ void __launch_bounds__(THREADS, 2)
   // Every K-block issues the units of block min(kb + 1, last): the last one fetches itself again into the idle buffer, so
   // that all blocks are the same straight-line code with the same counted waits (one block's worth of L2 reads per tile
   // more: 4 % at K = 768).
-  if (p4::kRebalance) {
-    // The phases' reading halves evened out (an LDS-DMA costs its wave ~150 cycles of issue among LDS reads, a register load
-    // ~40, a unit's split ~250 with its two writes: with the DMA of B0 and the split of A1 in one phase that phase's reading
-    // half lasted ~600 cycles against the 384 of the other group's MFMAs).  DMA in the phases that read most fragments, loads
-    // and splits in the others; the B0 fragments stay in registers from quadrant 00 to quadrant 10, so B0's slot is free for
-    // the next block's DMA four phases after its only read:
-    //   phase 0 (00): read A0 B0 | DMA  B0(kn)        phase 1 (01): read B1 | load A0(kn) | split A1(kb)
-    //   phase 2 (11): read A1    | DMA  B1(kn)        phase 3 (10): -       | load A1(kn) | split A0(kn)
-    // Issue order B0', A0', B1', A1': vmcnt(4) before a phase's barrier retires the unit issued two phases earlier - A1(kb)
-    // for phase 1's split, A0(kn) for phase 3's, B0(kn) / B1(kn) one or more phases before their first read.
-    bf16x8 b0h[2], b0l[2];
-    auto mma_b = [&](f32x4 (&cc)[4][2], const bf16x8 (&fh)[2], const bf16x8 (&fl)[2]) {
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) cc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fh[j], al[i], cc[i][j], 0, 0, 0);
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) cc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fl[j], ah[i], cc[i][j], 0, 0, 0);
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) cc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fh[j], ah[i], cc[i][j], 0, 0, 0);
-      __builtin_amdgcn_s_setprio(0);
-    };
-    // the same MFMAs with the split of one activation unit between the three groups of eight (kSplitInMma)
-    auto mma_split = [&](f32x4 (&cc)[4][2], const bf16x8 (&fh)[2], const bf16x8 (&fl)[2], char* dst_buf, int half, f32x4v v0, f32x4v v1) {
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) cc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fh[j], al[i], cc[i][j], 0, 0, 0);
-      split_store(v0, dst_buf + half * p4::UNIT_BYTES, a_off[0]);
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) cc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fl[j], ah[i], cc[i][j], 0, 0, 0);
-      split_store(v1, dst_buf + half * p4::UNIT_BYTES, a_off[1]);
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) cc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fh[j], ah[i], cc[i][j], 0, 0, 0);
-      __builtin_amdgcn_s_setprio(0);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the planes are in LDS before the barrier that publishes them to this group
-    };
-#ifdef DRIN_P4_STAMPS
-    const bool stamp_on = blockIdx.x == 121 && M > 100000 && (threadIdx.x & 255) == 0;
-#endif
-    for (int kb = 0; kb < nkb; ++kb) {
-      char* buf = smem + (kb & 1) * p4::BUF;
-      char* nbuf = smem + ((kb + 1) & 1) * p4::BUF;
-      const int kn = kb + 1 < nkb ? kb + 1 : kb;
-      // phase 0: quadrant 00
-      DRIN_P4_STAMP(1, kb, 0, 0);
-      read_a(buf, 0);
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const char* p = buf + 2 * p4::UNIT_BYTES + swz16(wn * 32 + j * 16 + r, c);
-        b0h[j] = *reinterpret_cast<const bf16x8*>(p);
-        b0l[j] = *reinterpret_cast<const bf16x8*>(p + 128 * 64);
-      }
-      p4::issue_unit<2>(src, nbuf, kn);
-      wait4();
-      barrier();
-      DRIN_P4_STAMP(1, kb, 0, 1);
-      mma_b(acc[0][0], b0h, b0l);
-      DRIN_P4_STAMP(1, kb, 0, 2);
-      barrier();
-      // phase 1: quadrant 01
-      DRIN_P4_STAMP(1, kb, 1, 0);
-      read_b(buf, 1);
-      load_a(0, kn, a0v0, a0v1);
-      wait4();
-      landed(a1v0, a1v1);
-      if (p4::kSplitInMma) {
-        barrier();
-        DRIN_P4_STAMP(1, kb, 1, 1);
-        mma_split(acc[0][1], bh, bl, buf, 1, a1v0, a1v1);
-      } else {
-        store_a(buf, 1, a1v0, a1v1);
-        barrier();
-        DRIN_P4_STAMP(1, kb, 1, 1);
-        mma_b(acc[0][1], bh, bl);
-      }
-      DRIN_P4_STAMP(1, kb, 1, 2);
-      barrier();
-      // phase 2: quadrant 11
-      DRIN_P4_STAMP(1, kb, 2, 0);
-      read_a(buf, 1);
-      p4::issue_unit<3>(src, nbuf, kn);
-      wait4();
-      barrier();
-      DRIN_P4_STAMP(1, kb, 2, 1);
-      mma_b(acc[1][1], bh, bl);
-      DRIN_P4_STAMP(1, kb, 2, 2);
-      barrier();
-      // phase 3: quadrant 10
-      DRIN_P4_STAMP(1, kb, 3, 0);
-      load_a(1, kn, a1v0, a1v1);
-      wait4();
-      landed(a0v0, a0v1);
-      if (p4::kSplitInMma) {
-        barrier();
-        DRIN_P4_STAMP(1, kb, 3, 1);
-        mma_split(acc[1][0], b0h, b0l, nbuf, 0, a0v0, a0v1);
-      } else {
-        store_a(nbuf, 0, a0v0, a0v1);
-        barrier();
-        DRIN_P4_STAMP(1, kb, 3, 1);
-        mma_b(acc[1][0], b0h, b0l);
-      }
-      DRIN_P4_STAMP(1, kb, 3, 2);
-      barrier();
-    }
-  } else
+  // The phases' reading halves evened out (an LDS-DMA costs its wave ~150 cycles of issue among LDS reads, a register load ~40, a
+  // unit's split ~250 with its two writes: with the DMA of B0 and the split of A1 in one phase that phase's reading half lasted
+  // ~600 cycles against the 384 of the other group's MFMAs).  DMA in the phases that read most fragments, loads and splits in
+  // the others; the B0 fragments stay in registers from quadrant 00 to quadrant 10, so B0's slot is free for the next block's
+  // DMA four phases after its only read:
+  //   phase 0 (00): read A0 B0 | DMA  B0(kn)        phase 1 (01): read B1 | load A0(kn) | split A1(kb)
+  //   phase 2 (11): read A1    | DMA  B1(kn)        phase 3 (10): -       | load A1(kn) | split A0(kn)
+  // Issue order B0', A0', B1', A1': vmcnt(4) before a phase's barrier retires the unit issued two phases earlier - A1(kb) for
+  // phase 1's split, A0(kn) for phase 3's, B0(kn) / B1(kn) one or more phases before their first read.
+  bf16x8 b0h[2], b0l[2];
   for (int kb = 0; kb < nkb; ++kb) {
     char* buf = smem + (kb & 1) * p4::BUF;
     char* nbuf = smem + ((kb + 1) & 1) * p4::BUF;
     const int kn = kb + 1 < nkb ? kb + 1 : kb;
-    auto none = [] {};
-    // (p4::kDmaPlace: where the phase's two loads / DMA instructions go - see k_gemm_x3_planes_p4)
-    // phase 0: quadrant 00; A0(kn) leaves for the registers
+    // phase 0: quadrant 00
     read_a(buf, 0);
-    read_b(buf, 0);
-    if (p4::kDmaPlace == 0) load_a(0, kn, a0v0, a0v1);
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const char* p = buf + 2 * p4::UNIT_BYTES + swz16(wn * 32 + j * 16 + r, c);
+      b0h[j] = *reinterpret_cast<const bf16x8*>(p);
+      b0l[j] = *reinterpret_cast<const bf16x8*>(p + 128 * 64);
+    }
+    p4::issue_unit<2>(src, nbuf, kn);
     wait4();
     barrier();
-    if (p4::kDmaPlace == 1) load_a(0, kn, a0v0, a0v1);
-    if (p4::kDmaPlace == 2) mma(acc[0][0], [&] { load_a(0, kn, a0v0, a0v1); }); else mma(acc[0][0], none);
+    mma_b(acc[0][0], b0h, b0l);
     barrier();
-    // phase 1: quadrant 01; B0(kn) leaves; A1(kb) has landed: split and publish it
+    // phase 1: quadrant 01
     read_b(buf, 1);
-    if (p4::kDmaPlace == 0) p4::issue_unit<2>(src, nbuf, kn);
+    load_a(0, kn, a0v0, a0v1);
     wait4();
     landed(a1v0, a1v1);
-    store_a(buf, 1, a1v0, a1v1);
     barrier();
-    if (p4::kDmaPlace == 1) p4::issue_unit<2>(src, nbuf, kn);
-    if (p4::kDmaPlace == 2) mma(acc[0][1], [&] { p4::issue_unit<2>(src, nbuf, kn); }); else mma(acc[0][1], none);
+    mma_split(acc[0][1], bh, bl, buf, 1, a1v0, a1v1);
     barrier();
-    // phase 2: quadrant 11; B1(kn) leaves
+    // phase 2: quadrant 11
     read_a(buf, 1);
-    if (p4::kDmaPlace == 0) p4::issue_unit<3>(src, nbuf, kn);
+    p4::issue_unit<3>(src, nbuf, kn);
     wait4();
     barrier();
-    if (p4::kDmaPlace == 1) p4::issue_unit<3>(src, nbuf, kn);
-    if (p4::kDmaPlace == 2) mma(acc[1][1], [&] { p4::issue_unit<3>(src, nbuf, kn); }); else mma(acc[1][1], none);
+    mma_b(acc[1][1], bh, bl);
     barrier();
-    // phase 3: quadrant 10; A1(kn) leaves; A0(kn) has landed: split and publish it
-    read_b(buf, 0);
-    if (p4::kDmaPlace == 0) load_a(1, kn, a1v0, a1v1);
+    // phase 3: quadrant 10
+    load_a(1, kn, a1v0, a1v1);
     wait4();
     landed(a0v0, a0v1);
-    store_a(nbuf, 0, a0v0, a0v1);
     barrier();
-    if (p4::kDmaPlace == 1) load_a(1, kn, a1v0, a1v1);
-    if (p4::kDmaPlace == 2) mma(acc[1][0], [&] { load_a(1, kn, a1v0, a1v1); }); else mma(acc[1][0], none);
+    mma_split(acc[1][0], b0h, b0l, nbuf, 0, a0v0, a0v1);
     barrier();
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the redundant units of the last block
@@ -1000,9 +790,6 @@ __global__ void __launch_bounds__(THREADS, 2)
           float* dst = C + row * ldc + col;
           float4 o = make_float4(acc[a][b][i][j][0], acc[a][b][i][j][1], acc[a][b][i][j][2], acc[a][b][i][j][3]) + bv[b][j];
           if (accumulate) o = o + ld4(dst);
-#ifdef DRIN_ABLATE_GEMM_STORES
-          if (ldc < 0)
-#endif
           st4(dst, o);
         }
     }
@@ -1063,16 +850,6 @@ __global__ void __launch_bounds__(256) k_transpose_split_batch(const SplitBatch 
 
 }  // namespace x3p
 
-#ifdef DRIN_P4_STAMPS
-extern "C" __attribute__((visibility("default"))) int drin_debug_p4_stamps(unsigned long long* host_out) {
-  return (int)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(drin::x3p::g_p4_stamps), sizeof(unsigned long long) * 2 * 2 * 32 * 4 * 3);
-}
-#endif
-#ifdef DRIN_STAMPS
-extern "C" __attribute__((visibility("default"))) int drin_debug_stamps(unsigned long long* host_out) {
-  return (int)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(x3p::g_stamps), sizeof(unsigned long long) * (8 * 64 * 4 + 64));
-}
-#endif
 
 int launch_split_planes(const float* x, void* hi, void* lo, int64_t n, hipStream_t st) {
   if (n <= 0) return DRIN_OK;

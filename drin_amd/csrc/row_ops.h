@@ -15,10 +15,7 @@ struct Row {
 // 100 % of its cycles, k_pair_layer1 78 %; ~33 vector instructions per element, none packed).  LayerNorm + GELU + the combine and the
 // dots on PAIRS of columns: every fma / mul / add serves two elements; the two transcendentals (v_rcp_f32, v_exp_f32) and |x| stay
 // per element.  Same operations on every element as the scalar form (the sums of a row are associated differently: a few ulps on
-// mean / variance).  -DDRIN_PK_ROWS=0 builds the scalar form (A/B: tools/variant_ab.sh).
-#ifndef DRIN_PK_ROWS
-#define DRIN_PK_ROWS 1
-#endif
+// mean / variance).
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ f32x2 pk(float a, float b) { return f32x2{a, b}; }
 __device__ __forceinline__ f32x2 splat2(float a) { return f32x2{a, a}; }
@@ -175,18 +172,13 @@ __device__ __forceinline__ void axpy_row(Row<V>& acc, float w, const Row<V>& x) 
 // the same two on the packed pipe (row kernels of the folded paths; a dot's terms are summed in another association)
 template <int V>
 __device__ __forceinline__ float dot_rows_pk(const Row<V>& a, const Row<V>& b) {
-#if DRIN_PK_ROWS
   f32x2 s2 = {0.f, 0.f};
 #pragma unroll
   for (int j = 0; j < V; ++j) s2 = pk_fma(hi2(a.v[j]), hi2(b.v[j]), pk_fma(lo2(a.v[j]), lo2(b.v[j]), s2));
   return s2.x + s2.y;
-#else
-  return dot_rows<V>(a, b);
-#endif
 }
 template <int V>
 __device__ __forceinline__ void axpy_row_pk(Row<V>& acc, float w, const Row<V>& x) {
-#if DRIN_PK_ROWS
   const f32x2 w2 = {w, w};
 #pragma unroll
   for (int j = 0; j < V; ++j) {
@@ -194,9 +186,6 @@ __device__ __forceinline__ void axpy_row_pk(Row<V>& acc, float w, const Row<V>& 
     const f32x2 h = pk_fma(w2, f32x2{x.v[j].z, x.v[j].w}, f32x2{acc.v[j].z, acc.v[j].w});
     acc.v[j] = make_float4(l.x, l.y, h.x, h.y);
   }
-#else
-  axpy_row<V>(acc, w, x);
-#endif
 }
 template <int V>
 __device__ __forceinline__ Row<V> zero_row() {
@@ -224,7 +213,6 @@ template <int DV, bool GENERIC_ACT = false>
 __device__ __forceinline__ Row<DV> ln_gelu_row_lds(const Row<DV>& h, const float* gamma, const float* beta, int lane,
                                                    int D4, float eps, int act = DRIN_ACT_GELU) {
   const float inv_d = 1.0f / (float)(D4 * 4);
-#if DRIN_PK_ROWS
   if constexpr (!GENERIC_ACT) {
     f32x2 s2 = splat2(0.f);
 #pragma unroll
@@ -257,7 +245,7 @@ __device__ __forceinline__ Row<DV> ln_gelu_row_lds(const Row<DV>& h, const float
     }
     return y;
   }
-#endif
+  // the scalar form: the generic activation
   float s = 0.f;
 #pragma unroll
   for (int j = 0; j < DV; ++j) s += (h.v[j].x + h.v[j].y) + (h.v[j].z + h.v[j].w);
@@ -302,14 +290,10 @@ __device__ __forceinline__ Row<DV> combine_rows_lds(const Row<DV>& base, float w
   for (int j = 0; j < DV; ++j) {
     const int c4 = lane + 64 * j;
     if (c4 < D4) {
-#if DRIN_PK_ROWS
       const float4 a1 = ld4(u1 + c4 * 4), a2 = ld4(u2 + c4 * 4), cc = ld4(c + c4 * 4);
       const f32x2 w1_ = splat2(w1), w2_ = splat2(w2);
       r.v[j] = join2(pk_fma(w1_, lo2(a1), pk_fma(w2_, lo2(a2), lo2(base.v[j]) + lo2(cc))),
                      pk_fma(w1_, hi2(a1), pk_fma(w2_, hi2(a2), hi2(base.v[j]) + hi2(cc))));
-#else
-      r.v[j] = fma4(w1, ld4(u1 + c4 * 4), fma4(w2, ld4(u2 + c4 * 4), base.v[j] + ld4(c + c4 * 4)));
-#endif
     } else
       r.v[j] = make_float4(0.f, 0.f, 0.f, 0.f);
   }

@@ -13,8 +13,8 @@
  *     thread-local message for the last failure on the calling thread.
  *   - all data pointers are DEVICE pointers unless a parameter says "host".  The caller owns every
  *     buffer, including the workspace (size from drin_workspace_bytes); the library allocates
- *     nothing and keeps no mutable global state (the opt-in profile of drin_profile_begin apart; environment
- *     probes are read once), so calls are re-entrant.
+ *     nothing and keeps no mutable global state (the opt-in profile of drin_profile_begin apart), so calls are
+ *     re-entrant.
  *   - every kernel is launched on the caller's `stream` (a hipStream_t passed as void*); the
  *     library never synchronises (drin_index_status apart, which exists to be the caller's synchronisation point).
  *   - THE DEVICE OF A CALL IS THE DEVICE OF ITS STREAM, not the calling thread's current device: every launching entry

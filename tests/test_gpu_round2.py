@@ -281,7 +281,7 @@ def test_config5_full_width_against_the_oracle(million_entity_table, path):
 
 def test_config5_timed_instantiation_128_candidate_workgroups(million_entity_table):
     """`bench.py`'s config-5 leg scores chunks of 4 096 mentions, where a workgroup of `k_cached_pairs` /
-    `k_pair_final` walks 128 candidates (`csrc/entity_cache.hip` cached_chunk_default: B >= 2 048) - every other full-width test
+    `k_pair_final` walks 128 candidates (`csrc/entity_cache.hip` cached_chunk_candidates: B >= 2 048) - every other full-width test
     of the cached path stayed at B = 37 (64-candidate workgroups).  B = 2 048 x N = 1 001 on the 1 000 003-row table through the
     per-entity cache: mentions (first, middle, last) against the CPU oracle on the gathered rows, <= 1e-5, and against the
     same mentions scored in a small call (64-candidate workgroups), <= 5e-6."""

@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # DRIN_LIB_PATH: another build of the same library (the sanitizer build of `python -m drin_amd.build --asan-host`)
 LIB_PATH = os.environ.get("DRIN_LIB_PATH") or os.path.join(_HERE, "libdrin_hip.so")
 MAX_LAYERS = 8
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 OK, E_SHAPE, E_NULL, E_ALIGN, E_WORKSPACE, E_HIP, E_UNSUPPORTED, E_INDEX = 0, -1, -2, -3, -4, -5, -6, -7
 PREC_F32, PREC_BF16X3, PREC_BF16X3_ALL, PREC_BF16X3_IF16 = 0, 1, 3, 5     # (2 and 4: removed with ABI 6 - outside the 1e-4 bar)
@@ -66,6 +66,13 @@ class DrinParamGradsC(C.Structure):  # same shape as DrinParamsC, mutable pointe
     _fields_ = DrinParamsC._fields_
 
 
+class DrinInputGradsC(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in (
+        "mention_text", "mention_image", "mention_object", "mention_object_score", "entity_text", "entity_text_cls",
+        "entity_image", "entity_object", "entity_object_score", "miet_similarity", "mtei_similarity", "scratch")] + [
+        ("scratch_bytes", C.c_size_t)]
+
+
 class DrinTraceC(C.Structure):
     _fields_ = [(n, C.c_void_p * (MAX_LAYERS + 1)) for n in (
         "mention_text_vertex", "mention_image_vertex", "entity_text_vertex", "entity_image_vertex", "edges")]
@@ -92,6 +99,11 @@ EXPORTS = {
                                 C.c_size_t, C.c_void_p, C.POINTER(DrinParamGradsC), C.c_void_p]),
     "drin_backward_staged": (C.c_int, [C.POINTER(DrinConfigC), C.POINTER(DrinBatchC), C.POINTER(DrinParamsC), C.c_void_p,
                                        C.c_size_t, C.c_void_p, C.POINTER(DrinParamGradsC), C.c_void_p, C.c_void_p]),
+    "drin_backward_ex": (C.c_int, [C.POINTER(DrinConfigC), C.POINTER(DrinBatchC), C.POINTER(DrinParamsC), C.c_void_p,
+                                   C.c_size_t, C.c_void_p, C.POINTER(DrinParamGradsC), C.POINTER(DrinInputGradsC), C.c_void_p,
+                                   C.c_void_p]),
+    "drin_input_grad_scratch_bytes": (C.c_size_t, [C.POINTER(DrinConfigC)]),
+    "drin_pool_bwd": (C.c_int, [C.POINTER(DrinConfigC), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "drin_fused_supported": (C.c_int, [C.POINTER(DrinConfigC)]),
     "drin_prepared_bytes": (C.c_size_t, [C.POINTER(DrinConfigC)]),
     "drin_fused_workspace_bytes": (C.c_size_t, [C.POINTER(DrinConfigC)]),

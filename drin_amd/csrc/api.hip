@@ -396,6 +396,201 @@ static int indexed_supported(const drin_config* c, const drin_batch* b, const ch
   return DRIN_OK;
 }
 
+// ---- input gradients (drin_backward_ex) -----------------------------------------------------------------------------
+// Scratch of drin_input_grads (floats, every region on a 256-byte boundary).  Sized from the config alone.
+struct InputGradScratch {
+  size_t total_floats = 0;
+  size_t g_span = 0, g_raw = 0, cls_stage = 0, g_pool = 0, cos3 = 0, g_mimg = 0, g_eimg = 0, g_mobj = 0, g_eobj = 0;
+  size_t g_ms = 0, g_es = 0, g_edge = 0, planes_ei = 0, planes_et = 0, miei = 0;
+  size_t take(size_t n) {
+    const size_t o = total_floats;
+    total_floats += (n + 63) & ~(size_t)63;
+    return o;
+  }
+  void build(const drin_config& c) {
+    const size_t B = (size_t)c.batch, N = (size_t)c.num_candidates, D = (size_t)c.embed_dim, R = (size_t)c.image_dim;
+    const size_t M = B * N, Km = (size_t)c.mention_objects, Ke = (size_t)c.entity_objects;
+    const bool x3 = c.precision == DRIN_PREC_BF16X3 || c.precision == DRIN_PREC_BF16X3_ALL;
+    total_floats = 0;
+    g_span = take(B * D);
+    g_raw = take(M * D);                                     // text-text edge: gradient of the entity rows it reads
+    cls_stage = take(c.entity_tokens > 0 ? M * D : 0);       // token 0 of every token block, contiguous
+    g_pool = take(c.entity_tokens > 0 ? M * D : 0);
+    cos3 = take(3 * M);
+    g_mimg = take(B * R);
+    g_eimg = take(c.entity_image_inner > 1 ? M * R : 0);
+    g_mobj = take(B * Km * R);
+    g_eobj = take(M * Ke * R);
+    g_ms = take(B * Km);
+    g_es = take(M * Ke);
+    g_edge = take(4 * M);
+    planes_ei = take(x3 ? D * R : 0);                        // bf16 (hi, lo) planes of W_ei^T [R][D]
+    planes_et = take(x3 ? D * D : 0);
+    miei = take(miei_bwd_scratch_floats((int64_t)M, (int)B, (int)Km, (int)Ke));
+  }
+};
+
+static int validate_input_grads(const drin_config* c, const drin_batch* b, const drin_input_grads* g) {
+  if (b->entity_index) {
+    set_error("drin_backward_ex: input gradients of a table-form batch (entity_index) are not built; gather the rows");
+    return DRIN_E_UNSUPPORTED;
+  }
+  if (g->entity_text_cls && !b->entity_text_cls) {
+    set_error("drin_backward_ex: input_grads.entity_text_cls needs batch.entity_text_cls (the pooled-ahead form)");
+    return DRIN_E_NULL;
+  }
+  if (c->mention_objects * c->entity_objects > 64) {
+    set_error("drin_backward_ex: more than 64 object pairs (mention_objects x entity_objects) is not built");
+    return DRIN_E_UNSUPPORTED;
+  }
+  const void* outs[] = {g->mention_text, g->mention_image, g->mention_object, g->mention_object_score, g->entity_text,
+                        g->entity_text_cls, g->entity_image, g->entity_object, g->entity_object_score, g->miet_similarity,
+                        g->mtei_similarity};
+  for (const void* o : outs)
+    if (!aligned16(o)) {
+      set_error("drin_backward_ex: input gradient outputs must be 16-byte aligned");
+      return DRIN_E_ALIGN;
+    }
+  InputGradScratch S;
+  S.build(*c);
+  if (!g->scratch || !aligned16(g->scratch) || g->scratch_bytes < S.total_floats * sizeof(float)) {
+    set_error("drin_backward_ex: input_grads.scratch is NULL, unaligned or smaller than drin_input_grad_scratch_bytes (%zu)",
+              S.total_floats * sizeof(float));
+    return g->scratch ? DRIN_E_WORKSPACE : DRIN_E_NULL;
+  }
+  return DRIN_OK;
+}
+
+static int zero_out(void* p, size_t floats, hipStream_t st) {
+  if (!p) return DRIN_OK;
+  hipError_t e = hipMemsetAsync(p, 0, floats * sizeof(float), st);
+  return e == hipSuccess ? DRIN_OK : hip_fail(e, "hipMemsetAsync(input gradient)");
+}
+
+// ge: the layer-0 edge gradients [4][B N (x D with vector edges)] (w.r.t. the edges before the edge_enabled mask), NULL
+// without GCN layers (the score then reads neither the edges nor the image vertices); g_vm0 = [d mt | d mi],
+// g_ve0 = [d et | d ei]: the vertex encoders' output gradients.
+static int run_input_grads(const drin_config* c, const drin_batch* b, const drin_params* W, const Pooled& P, const float* ge,
+                           const float* g_vm0, const float* g_ve0, const drin_input_grads* ig, hipStream_t st) {
+  const int B = c->batch, N = c->num_candidates, D = c->embed_dim, R = c->image_dim, T = c->entity_tokens;
+  const int Km = c->mention_objects, Ke = c->entity_objects;
+  const size_t M = (size_t)B * N, BD = (size_t)B * D, MD = M * D;
+  const int mobj_in = c->mention_object_inner > 1 ? c->mention_object_inner : 1;
+  const int eimg_in = c->entity_image_inner > 1 ? c->entity_image_inner : 1;
+  const int eobj_in = c->entity_object_inner > 1 ? c->entity_object_inner : 1;
+  const bool x3 = c->precision == DRIN_PREC_BF16X3 || c->precision == DRIN_PREC_BF16X3_ALL;
+  InputGradScratch S;
+  S.build(*c);
+  float* sc = (float*)ig->scratch;
+  const bool live = ge != nullptr;   // edges and image vertices reach the score
+  const float* g_mt = g_vm0;
+  const float* g_mi = g_vm0 + BD;
+  const float* g_et = g_ve0;
+  const float* g_ei = g_ve0 + MD;
+  // pair-sized dX = dY W (W [D][n_out]): split-bf16 on the NT kernel against W^T planes, as the layer loop's pair-sized
+  // products; exact fp32 otherwise
+  auto pair_dx = [&](const float* g, const float* w, float* planes, float* out, int n_out, bool acc) -> int {
+    if (x3 && M >= 1024 && (D % 32) == 0 && (n_out % 4) == 0) {
+      SplitBatch tb;
+      DRIN_TRY(tb.add(w, planes, (int64_t)D * n_out));
+      DRIN_TRY(launch_transpose_split_batch(tb, D, n_out, st));
+      const __bf16* hi = reinterpret_cast<const __bf16*>(planes);
+      return launch_gemm_nt_bf16x3(g, D, nullptr, D, nullptr, out, n_out, (int64_t)M, n_out, D, st, hi, hi + (size_t)D * n_out,
+                                   acc, nullptr, 0);
+    }
+    return launch_gemm_nn(g, D, w, n_out, out, n_out, (int64_t)M, n_out, D, acc, DRIN_PREC_F32, st);
+  };
+
+  // the scalar layer-0 edges: vector edges are the scalar ones broadcast over D (model.py:202) - their row sums
+  const float* gs = ge;
+  if (live && c->vector_edges) {
+    DRIN_TRY(launch_row_sum(ge, sc + S.g_edge, 4 * (int64_t)M, D, st));
+    gs = sc + S.g_edge;
+  }
+
+  // text-text edge cos(span mean, raw entity rows) (model.py:71-76): d span mean and d raw rows
+  const bool has_cls = b->entity_text_cls != nullptr;
+  float* d_raw = sc + S.g_raw;
+  if (T == 0 && !has_cls && ig->entity_text) d_raw = ig->entity_text;   // the raw rows ARE entity_text
+  if (T == 0 && has_cls && ig->entity_text_cls) d_raw = ig->entity_text_cls;
+  const bool want_raw = (T > 0 && ig->entity_text) || (T == 0 && !has_cls && ig->entity_text) || (has_cls && ig->entity_text_cls);
+  const bool tt = live && (ig->mention_text || want_raw);
+  if (tt) {
+    const float* y = has_cls ? b->entity_text_cls : b->entity_text;
+    if (T > 0) {   // token 0 of each block (model.py:73-75), staged contiguous for the row kernel
+      hipError_t e = hipMemcpy2DAsync(sc + S.cls_stage, (size_t)D * sizeof(float), b->entity_text, (size_t)T * D * sizeof(float),
+                                      (size_t)D * sizeof(float), M, hipMemcpyDeviceToDevice, st);
+      if (e != hipSuccess) return hip_fail(e, "hipMemcpy2DAsync(token 0 rows)");
+      y = sc + S.cls_stage;
+    }
+    DRIN_TRY(launch_cosine_bwd(P.span_mean, y, gs, sc + S.g_span, d_raw, sc + S.cos3, B, N, D, c->cosine_eps, st));
+  } else if (has_cls && ig->entity_text_cls) {
+    DRIN_TRY(zero_out(ig->entity_text_cls, MD, st));
+  }
+  // mention text: d span = d mt W_mt (+ the edge term), then the span mean's backward (ghmfc.py:54-60)
+  if (ig->mention_text) {
+    DRIN_TRY(launch_gemm_nn(g_mt, D, W->w_mention_text, D, sc + S.g_span, D, B, D, D, tt, DRIN_PREC_F32, st));
+    DRIN_TRY(launch_span_mean_bwd(sc + S.g_span, b->mention_start, b->mention_end, ig->mention_text, B, c->mention_tokens, D, st));
+  }
+  // entity text: d x_et = d et W_et (+ the edge term when the raw rows are entity_text itself); token blocks: the pooling's
+  // backward (ghmfc.py:245-249) with token 0 taking the edge term
+  if (ig->entity_text) {
+    float* dst = T > 0 ? sc + S.g_pool : ig->entity_text;
+    DRIN_TRY(pair_dx(g_et, W->w_entity_text, sc + S.planes_et, dst, D, tt && T == 0 && !has_cls));
+    if (T > 0)
+      DRIN_TRY(launch_token_block_bwd(sc + S.g_pool, tt ? sc + S.g_raw : nullptr, b->entity_text_mask, ig->entity_text,
+                                      (int64_t)M, T, D, false, st));
+  }
+  // images: d x = d v W (model.py:41-45), then the means' backward
+  if (ig->mention_image) {
+    if (live) {
+      DRIN_TRY(launch_gemm_nn(g_mi, D, W->w_mention_image, R, sc + S.g_mimg, R, B, R, D, false, DRIN_PREC_F32, st));
+      DRIN_TRY(launch_axis_mean_bwd(sc + S.g_mimg, ig->mention_image, B, c->image_regions, R, st));
+    } else {
+      DRIN_TRY(zero_out(ig->mention_image, (size_t)B * c->image_regions * R, st));
+    }
+  }
+  if (ig->entity_image) {
+    if (live) {
+      float* dst = eimg_in > 1 ? sc + S.g_eimg : ig->entity_image;
+      DRIN_TRY(pair_dx(g_ei, W->w_entity_image, sc + S.planes_ei, dst, R, false));
+      if (eimg_in > 1) DRIN_TRY(launch_axis_mean_bwd(dst, ig->entity_image, (int64_t)M, eimg_in, R, st));
+    } else {
+      DRIN_TRY(zero_out(ig->entity_image, M * eimg_in * R, st));
+    }
+  }
+  // image-image edge (model.py:78-92)
+  if (ig->mention_object || ig->mention_object_score || ig->entity_object || ig->entity_object_score) {
+    if (live) {
+      float* d_mobj = mobj_in > 1 || !ig->mention_object ? sc + S.g_mobj : ig->mention_object;
+      float* d_eobj = eobj_in > 1 || !ig->entity_object ? sc + S.g_eobj : ig->entity_object;
+      float* d_ms = ig->mention_object_score ? ig->mention_object_score : sc + S.g_ms;
+      float* d_es = ig->entity_object_score ? ig->entity_object_score : sc + S.g_es;
+      DRIN_TRY(launch_miei_bwd(P.mention_object, b->mention_object_score, P.entity_object, b->entity_object_score, gs + 3 * M,
+                               d_mobj, d_ms, d_eobj, d_es, sc + S.miei, B, N, Km, Ke, R, c->cosine_eps, c->miei_eps, st));
+      if (ig->mention_object && mobj_in > 1)
+        DRIN_TRY(launch_axis_mean_bwd(d_mobj, ig->mention_object, (int64_t)B * Km, mobj_in, R, st));
+      if (ig->entity_object && eobj_in > 1)
+        DRIN_TRY(launch_axis_mean_bwd(d_eobj, ig->entity_object, (int64_t)M * Ke, eobj_in, R, st));
+    } else {
+      DRIN_TRY(zero_out(ig->mention_object, (size_t)B * Km * mobj_in * R, st));
+      DRIN_TRY(zero_out(ig->entity_object, M * Ke * eobj_in * R, st));
+      DRIN_TRY(zero_out(ig->mention_object_score, (size_t)B * Km, st));
+      DRIN_TRY(zero_out(ig->entity_object_score, M * Ke, st));
+    }
+  }
+  // CLIP edges ti = mtei / clip_scale, it = miet / clip_scale (model.py:203)
+  if (ig->mtei_similarity) {
+    if (live) DRIN_TRY(launch_scale_div(gs + M, ig->mtei_similarity, (int64_t)M, 1.0f, c->clip_scale, st));
+    else DRIN_TRY(zero_out(ig->mtei_similarity, M, st));
+  }
+  if (ig->miet_similarity) {
+    if (live) DRIN_TRY(launch_scale_div(gs + 2 * M, ig->miet_similarity, (int64_t)M, 1.0f, c->clip_scale, st));
+    else DRIN_TRY(zero_out(ig->miet_similarity, M, st));
+  }
+  return DRIN_OK;
+}
+
 }  // namespace drin
 
 using namespace drin;
@@ -846,17 +1041,60 @@ int drin_backward(const drin_config* cfg, const drin_batch* batch, const drin_pa
 int drin_backward_staged(const drin_config* cfg, const drin_batch* batch, const drin_params* params, void* workspace,
                          size_t workspace_bytes, const float* grad_scores, const drin_param_grads* grads,
                          void* layers_ready_event, void* stream) {
+  if (!grads) {
+    set_error("drin_backward: grad_scores / grads is NULL");
+    return DRIN_E_NULL;
+  }
+  return drin_backward_ex(cfg, batch, params, workspace, workspace_bytes, grad_scores, grads, nullptr, layers_ready_event,
+                          stream);
+}
+
+size_t drin_input_grad_scratch_bytes(const drin_config* cfg) {
+  if (validate_config(cfg) != DRIN_OK) return 0;
+  InputGradScratch S;
+  S.build(*cfg);
+  return S.total_floats * sizeof(float);
+}
+
+int drin_pool_bwd(const drin_config* cfg, const int64_t* entity_text_mask, const float* grad_pooled, const float* grad_cls,
+                  void* grad_entity_text, void* stream) {
+  DRIN_BIND_DEVICE(stream, grad_entity_text, "drin_pool_bwd");
+  DRIN_TRY(validate_config(cfg));
+  if (!entity_text_mask || !grad_pooled || !grad_entity_text) {
+    set_error("drin_pool_bwd: mask, pooled gradient or output is NULL");
+    return DRIN_E_NULL;
+  }
+  if (cfg->entity_tokens <= 0) {
+    set_error("drin_pool_bwd: entity_tokens must be > 0 (a token block)");
+    return DRIN_E_SHAPE;
+  }
+  if (!aligned16(grad_pooled) || !aligned16(grad_cls) || !aligned16(grad_entity_text)) {
+    set_error("drin_pool_bwd: gradients must be 16-byte aligned");
+    return DRIN_E_ALIGN;
+  }
+  const int64_t M = (int64_t)cfg->batch * cfg->num_candidates;
+  return launch_token_block_bwd(grad_pooled, grad_cls, entity_text_mask, grad_entity_text, M, cfg->entity_tokens,
+                                cfg->embed_dim, cfg->feature_dtype == DRIN_FEAT_BF16, (hipStream_t)stream);
+}
+
+int drin_backward_ex(const drin_config* cfg, const drin_batch* batch, const drin_params* params, void* workspace,
+                     size_t workspace_bytes, const float* grad_scores, const drin_param_grads* grads_in,
+                     const drin_input_grads* input_grads, void* layers_ready_event, void* stream) {
   DRIN_BIND_DEVICE(stream, workspace, "drin_backward_staged");
   RoctxRange range("drin_backward");
   DRIN_TRY(validate_config(cfg));
   DRIN_TRY(validate_batch(cfg, batch));
   DRIN_TRY(validate_params(cfg, params));
-  if (!grad_scores || !grads) {
+  if (!grad_scores) {
     set_error("drin_backward: grad_scores / grads is NULL");
     return DRIN_E_NULL;
   }
+  // no parameter gradients wanted: every dW / db destination is NULL, so no weight-gradient product is issued
+  static const drin_param_grads kNoGrads = {};
+  const drin_param_grads* grads = grads_in ? grads_in : &kNoGrads;
   const int64_t* eidx = batch->entity_index;
   if (eidx) DRIN_TRY(indexed_supported(cfg, batch, "drin_backward"));
+  if (input_grads) DRIN_TRY(validate_input_grads(cfg, batch, input_grads));
   Layout L;
   L.build(*cfg, true);
   if (!workspace || !aligned16(workspace)) {
@@ -1158,11 +1396,18 @@ int drin_backward_staged(const drin_config* cfg, const drin_batch* batch, const 
     DRIN_TRY(launch_gemm_tn_group(tg, st, tnp, tnf, &sums, target));
     return launch_slice_sum(sums, st);
   };
-  if (layers_ready_event == nullptr) return flush(0, bias_sums.n, 0, dw_small.n, 0, dw_group.n, true);
-  DRIN_TRY(flush(0, layer_sums, 0, layer_small, 0, layer_group, true));
-  hipError_t ev = hipEventRecord((hipEvent_t)layers_ready_event, st);
-  if (ev != hipSuccess) return hip_fail(ev, "hipEventRecord(layers_ready)");
-  return flush(layer_sums, bias_sums.n, layer_small, dw_small.n, layer_group, dw_group.n, false);
+  if (layers_ready_event == nullptr) {
+    DRIN_TRY(flush(0, bias_sums.n, 0, dw_small.n, 0, dw_group.n, true));
+  } else {
+    DRIN_TRY(flush(0, layer_sums, 0, layer_small, 0, layer_group, true));
+    hipError_t ev = hipEventRecord((hipEvent_t)layers_ready_event, st);
+    if (ev != hipSuccess) return hip_fail(ev, "hipEventRecord(layers_ready)");
+    DRIN_TRY(flush(layer_sums, bias_sums.n, layer_small, dw_small.n, layer_group, dw_group.n, false));
+  }
+  if (input_grads == nullptr) return DRIN_OK;
+  // the batch tensors' gradients (drin_backward_ex): from the vertex encoders' output gradients and the layer-0 edge
+  // gradients, which the layer loop left in g_vm[0] / g_ve[0] / g_e[nl & 1] (nothing above writes them after the loop)
+  return run_input_grads(cfg, batch, params, P, nl > 0 ? g_e[nl & 1] : nullptr, g_vm[0], g_ve[0], input_grads, st);
 }
 
 // ---- host-side self-checks (sanitizer build / CI; no launch is made, no GPU needed) -----------------------------------

@@ -361,6 +361,23 @@ int launch_entity_side_bwd(const float* dA_mt, const float* dA_mi, const float* 
                            const float* de_extra, float* d_et, float* d_ei, float* de, int B, int N, int D,
                            const float* mask, bool accumulate, hipStream_t st);  // accumulate: d_et, d_ei += ...
 
+// ---- input gradients (input_grad_kernels.hip): backward of the parameter-free input stages -----------------
+// out[b, t, :] = g[b, :] / (e - s) on the (clipped) span s <= t < e, 0 elsewhere (ghmfc.py:54-60)
+int launch_span_mean_bwd(const float* g, const int64_t* start, const int64_t* end, float* out, int B, int L, int D,
+                         hipStream_t st);
+// out[g, s, c] = in[g, c] / inner (torch.mean(dim=-2) backward)
+int launch_axis_mean_bwd(const float* in, float* out, int64_t groups, int inner, int cols, hipStream_t st);
+// token-block gradient of the entity pooling + token-0 read (ghmfc.py:245-249, model.py:73-75); out fp32 or bf16
+int launch_token_block_bwd(const float* g_pool, const float* g_cls, const int64_t* mask, void* out, int64_t pairs, int T,
+                           int D, bool bf16, hipStream_t st);
+// out[r] = sum_c in[r, c]
+int launch_row_sum(const float* in, float* out, int64_t rows, int C, hipStream_t st);
+// backward of launch_miei w.r.t. its four inputs; scratch: miei_bwd_scratch_floats
+size_t miei_bwd_scratch_floats(int64_t pairs, int B, int Km, int Ke);
+int launch_miei_bwd(const float* mobj, const float* mscore, const float* eobj, const float* escore, const float* g,
+                    float* d_mobj, float* d_mscore, float* d_eobj, float* d_escore, float* scratch, int B, int N, int Km,
+                    int Ke, int R, float cos_eps, float miei_eps, hipStream_t st);
+
 // ---- vector-edge ablation (vector_kernels.hip) --------------------------------------------------
 int launch_expand_edges(const float* es, float* out, int64_t pairs4, int D, hipStream_t st);
 int launch_mention_reduce_vec(const float* w1, const float* v1, const float* w2, const float* v2, const float* u,

@@ -487,12 +487,49 @@ def _bucket_layout(params: Sequence[torch.Tensor], per_layer: int, dynamic: bool
     return offsets, live, off
 
 
+# the floating-point batch tensors autograd reaches through the reference's plain-torch Model.forward (drin/model.py:164-209):
+# drin_input_grads field -> position in _Call.keep (the tensors after _Call's conversions)
+_INPUT_FIELDS = {"mention_text": 0, "mention_image": 3, "mention_object": 4, "mention_object_score": 5, "entity_text": 6,
+                 "entity_image": 8, "entity_object": 9, "entity_object_score": 10, "miet_similarity": 11, "mtei_similarity": 12,
+                 "entity_text_cls": 14}
+_BATCH_FLOAT = (0, 4, 5, 6, 7, 9, 10, 11, 12, 13)      # float tensors of the 14-sequence (the mask and positions are integer)
+
+
+def _feature_inputs(call: _Call, block: Optional[torch.Tensor] = None):
+    """`(roles, tensors)`: the batch tensors of `call` that require grad (after `_Call`'s conversions, so that torch's own
+    ToCopyBackward hands a bf16 leaf a bf16 gradient), plus a bf16 token block pooled in place (`block`, role "token_block")."""
+    roles, feats = [], []
+    for role, i in _INPUT_FIELDS.items():
+        t = call.keep[i]
+        if t is not None and t.requires_grad:
+            roles.append(role)
+            feats.append(t)
+    if block is not None and block.requires_grad:
+        roles.append("token_block")
+        feats.append(block)
+    return tuple(roles), tuple(feats)
+
+
+def _batch_requires_grad(batch) -> bool:
+    if isinstance(batch, IndexedBatch):
+        t = batch.table
+        ts = list(batch.mention) + [t.text, t.image, t.object, t.object_score, batch.miet_similarity, batch.mtei_similarity]
+    else:
+        ts = [batch[i] for i in _BATCH_FLOAT if i < len(batch)]
+    return any(torch.is_tensor(x) and x.is_floating_point() and x.requires_grad for x in ts)
+
+
 class _DrinScore(torch.autograd.Function):
-    """Autograd edge around drin_forward / drin_backward (loss.backward() of train.py:33-34)."""
+    """Autograd edge around drin_forward / drin_backward (loss.backward() of train.py:33-34).  `call.input_roles` (default
+    empty) names the batch tensors that follow the parameters in `tensors` (drin_input_grads fields; "token_block": a bf16
+    [B, N, T, D] block that was pooled in place, whose gradient drin_pool_bwd writes in bf16)."""
 
     @staticmethod
-    def forward(ctx, call: _Call, prepared: Optional[_Prepared], training: bool, *params: torch.Tensor):
+    def forward(ctx, call: _Call, prepared: Optional[_Prepared], training: bool, *tensors: torch.Tensor):
         lib = _lib.load()
+        roles = getattr(call, "input_roles", ())
+        params = tensors[:len(tensors) - len(roles)]
+        ctx.roles = roles
         versions = params
         params = tuple(p.detach().contiguous() for p in params)
         pc = _lib.DrinParamsC()
@@ -524,7 +561,11 @@ class _DrinScore(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_scores: torch.Tensor):
         lib = _lib.load()
-        call, params = ctx.call, ctx.params
+        call, params, roles = ctx.call, ctx.params, ctx.roles
+        need_params = any(ctx.needs_input_grad[3:3 + len(params)])
+        need_feats = [r for r, n in zip(roles, ctx.needs_input_grad[3 + len(params):]) if n]
+        if need_feats:
+            return _DrinScore._backward_inputs(ctx, grad_scores, need_params, need_feats)
         owner = getattr(call, "owner", None)
         if owner is not None and owner.grad_bucket_enabled:
             # every gradient is a view of ONE flat fp32 bucket, zeroed with one memset: autograd's AccumulateGrad adopts the
@@ -556,7 +597,73 @@ class _DrinScore(torch.autograd.Function):
         # the last layer's edge update is dead (model.py:130-134), and static edges never use w_u / w_v (/ w_m)
         for i in _dead_param_indices(len(params), call.per_layer, bool(call.cfg.dynamic_edges)):
             out[i] = None
-        return (None, None, None, *out)
+        return (None, None, None, *out, *([None] * len(roles)))
+
+    @staticmethod
+    def _backward_inputs(ctx, grad_scores: torch.Tensor, need_params: bool, need_feats):
+        """drin_backward_ex: the parameter gradients (when any parameter wants one: the same launches and bits as
+        drin_backward) and the gradients of the batch tensors in `need_feats`."""
+        lib = _lib.load()
+        call, params, roles = ctx.call, ctx.params, ctx.roles
+        dev = call.device
+        owner = getattr(call, "owner", None)
+        gc, out = None, [None] * len(params)
+        if need_params:
+            if owner is not None and owner.grad_bucket_enabled:
+                grads = owner._bucket_grads(params)
+            else:
+                grads = [torch.empty_like(p) for p in params]
+                torch._foreach_zero_(grads)
+            gc = _lib.DrinParamGradsC()
+            _fill_params(gc, grads, call.per_layer)
+            out = list(grads)
+            for i in _dead_param_indices(len(params), call.per_layer, bool(call.cfg.dynamic_edges)):
+                out[i] = None
+        ig = _lib.DrinInputGradsC()
+        feat_out = {}
+        for role in need_feats:
+            if role == "token_block":
+                continue
+            ref = call.keep[_INPUT_FIELDS[role]]
+            feat_out[role] = torch.empty(ref.shape, dtype=torch.float32, device=dev)
+        if "token_block" in need_feats:   # pooled and token-0 gradients first, then the block in bf16 (drin_pool_bwd)
+            feat_out.setdefault("entity_text", torch.empty(call.keep[6].shape, dtype=torch.float32, device=dev))
+            feat_out.setdefault("entity_text_cls", torch.empty(call.keep[14].shape, dtype=torch.float32, device=dev))
+        for role, t in feat_out.items():
+            setattr(ig, role, t.data_ptr())
+        n = lib.drin_input_grad_scratch_bytes(C.byref(call.cfg))
+        scratch = torch.empty(max(n, 16), dtype=torch.uint8, device=dev)
+        ig.scratch, ig.scratch_bytes = scratch.data_ptr(), scratch.numel()
+        g = grad_scores.to(torch.float32).contiguous()
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        # data-parallel overlap exactly as in backward() (drin_backward_staged's event and the bucket's hook)
+        hook = getattr(owner, "_layers_ready_hook", None) if need_params and owner is not None and owner.grad_bucket_enabled else None
+        staged = hook is not None and owner._grad_flat is not None and out[0].data_ptr() == owner._grad_flat.data_ptr()
+        ready = None
+        if staged:
+            ready = torch.cuda.Event()
+            ready.record(torch.cuda.current_stream(dev))
+        _lib.check(lib.drin_backward_ex(C.byref(call.cfg), C.byref(call.batch), C.byref(ctx.pc), ctx.ws.data_ptr(), ctx.ws.numel(),
+                                        g.data_ptr(), C.byref(gc) if gc is not None else None, C.byref(ig),
+                                        ready.cuda_event if staged else None, stream))
+        if staged:
+            offsets, live, _total = owner.bucket_layout()
+            hook(owner._grad_flat[:live], offsets[8], ready)
+        feats = []
+        for role, needed in zip(roles, ctx.needs_input_grad[3 + len(params):]):
+            if not needed:
+                feats.append(None)
+            elif role == "token_block":
+                block = call.token_block
+                gb = torch.empty(block.shape, dtype=torch.bfloat16, device=dev)
+                c = _lib.DrinConfigC.from_buffer_copy(call.cfg)
+                c.entity_tokens, c.feature_dtype = block.shape[2], _lib.FEAT_BF16
+                _lib.check(lib.drin_pool_bwd(C.byref(c), call.token_mask.data_ptr(), feat_out["entity_text"].data_ptr(),
+                                             feat_out["entity_text_cls"].data_ptr(), gb.data_ptr(), stream))
+                feats.append(gb)
+            else:
+                feats.append(feat_out[role])
+        return (None, None, None, *out, *feats)
 
 
 def _invalidate_after_load(module, _incompatible_keys) -> None:
@@ -777,7 +884,10 @@ class Model(nn.Module):
         if isinstance(batch, IndexedBatch):
             # table form: inference gathers inside the stream kernel; everything else (training,
             # exact-fp32 precision, geometries off the fused path) gathers with torch indexing first
-            inference = not (torch.is_grad_enabled() and any(p.requires_grad for p in params))
+            # batch tensors that require grad (a table being trained, attribution): the gathered torch path, so that torch's
+            # indexing backward accumulates into the table rows
+            feat_grad = torch.is_grad_enabled() and _batch_requires_grad(batch)
+            inference = not (torch.is_grad_enabled() and any(p.requires_grad for p in params)) and not feat_grad
             planes = self.precision in _PLANES
             t = batch.table
             if inference and self._prepared is not None and self.cfg.num_gcn_layers == 2 and (planes or t.cache_enabled):
@@ -798,7 +908,10 @@ class Model(nn.Module):
                         out = self._score(call, self._prepared, False, *params)
                         self._watch_indices(call.device)
                         return out
-            if not inference and t.text.dim() == 3:
+            if feat_grad:
+                batch = self._clamped(batch).gathered()
+                self._watch_indices(batch[0].device)
+            elif not inference and t.text.dim() == 3:
                 # training on a token-level table: every entity's tokens pooled once; the step then reads the pooled /
                 # token-0 / image / object tables through the candidate index inside the kernels, or gathers those rows
                 call = self._indexed_training_call(batch, planes)
@@ -815,7 +928,9 @@ class Model(nn.Module):
                 self._watch_indices(batch[0].device)
         # grad mode is already off inside Function.forward (and needs_input_grad ignores no_grad), so the
         # caller's mode is read here
-        training = torch.is_grad_enabled() and any(p.requires_grad for p in params)
+        # (any parameter or any float batch tensor requiring grad: the layer-by-layer forward that keeps what backward reads)
+        training = torch.is_grad_enabled() and (any(p.requires_grad for p in params) or _batch_requires_grad(batch))
+        block = None
         # features stored as bf16 are read in place by the fused inference path in split-bf16 precision; every
         # other path (training, exact fp32, geometries off the fused path) gets them widened to fp32 - exact
         in_place = (not training and self._prepared is not None and self.cfg.num_gcn_layers == 2
@@ -826,23 +941,28 @@ class Model(nn.Module):
                 and batch[7].is_cuda and batch[7].shape[0] > 0):
             # a training step on bf16-stored token blocks: pooled in place by the library - half
             # the bytes, no widened copy of the 197 KB per candidate - then the pooled-ahead form below
-            etf = batch[7]
-            batch = list(batch[:7]) + [_pool_tokens(etf, batch[8]), torch.zeros(etf.shape[0], dtype=torch.int64, device=etf.device)] \
+            etf, emask = batch[7], batch[8]
+            batch = list(batch[:7]) + [_pool_tokens(etf, emask), torch.zeros(etf.shape[0], dtype=torch.int64, device=etf.device)] \
                 + list(batch[9:])
             cls = etf[:, :, 0, :]
+            if etf.requires_grad:
+                # the block's gradient comes from drin_pool_bwd, written in bf16 (never widened): token 0 is not a graph input
+                block, cls = etf, cls.detach()
         if cls is not None:
             # pooled-ahead batch: the layer-by-layer entry points (the fused path folds the pooling into its one pass)
             call = _Call(self.cfg, batch, _lib.PREC_BF16X3 if prec in _FUSED_ONLY else prec, entity_text_cls=cls)
             if call.B == 0:
                 return torch.zeros(0, call.N, dtype=torch.float32, device=call.device)
-            return self._score(call, None, training, *params)
+            if block is not None:
+                call.token_block, call.token_mask = block, emask.to(device=block.device, dtype=torch.int64).contiguous()
+            return self._score(call, None, training, *params, feats=_feature_inputs(call, block))
         call = _Call(self.cfg, batch, prec, keep_bf16=in_place)
         if ((call.cfg.feature_dtype != _lib.FEAT_F32 or prec in _FUSED_ONLY)
                 and _lib.load().drin_fused_supported(C.byref(call.cfg)) != _lib.OK):
             call = _Call(self.cfg, batch, _lib.PREC_BF16X3 if prec in _FUSED_ONLY else prec)
         if call.B == 0:
             return torch.zeros(0, call.N, dtype=torch.float32, device=call.device)
-        return self._score(call, self._prepared, training, *params)
+        return self._score(call, self._prepared, training, *params, feats=_feature_inputs(call) if training else ((), ()))
 
     def wait_for_parameters(self) -> None:
         """Make the current stream wait for an optimiser update `train.OverlappedStep` left running on its side stream (no-op
@@ -852,8 +972,9 @@ class Model(nn.Module):
         if ev is not None:
             torch.cuda.current_stream(next(self.parameters()).device).wait_event(ev)
 
-    def _score(self, call: _Call, prepared, training: bool, *params):
+    def _score(self, call: _Call, prepared, training: bool, *params, feats=((), ())):
         call.owner = self
+        call.input_roles, inputs = feats
         ev = self._params_ready
         if ev is not None:
             if training or prepared is None:                 # the layer-by-layer entry point: staged
@@ -861,7 +982,7 @@ class Model(nn.Module):
             else:
                 self.wait_for_parameters()
         try:
-            return _DrinScore.apply(call, prepared, training, *params)
+            return _DrinScore.apply(call, prepared, training, *params, *inputs)
         except BaseException:
             # a staged call that failed before the library enqueued its wait (validation / workspace error) must not lose the
             # ordering behind the update still running on the side stream: the current stream waits here (harmless if the

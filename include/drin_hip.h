@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define DRIN_ABI_VERSION 7
+#define DRIN_ABI_VERSION 8
 #define DRIN_API __attribute__((visibility("default")))
 
 typedef enum {
@@ -223,6 +223,20 @@ typedef struct {
   struct { float *w_h, *b_h, *w_u, *b_u, *w_v, *b_v, *ln_weight, *ln_bias, *w_m, *b_m; } layer[DRIN_MAX_LAYERS];
 } drin_param_grads;
 
+/* Gradients w.r.t. the floating-point batch tensors (drin_backward_ex): what autograd gives every float tensor of the
+ * reference's 14-item batch, since its Model.forward is plain torch (drin/model.py:164-209).  Each output has the shape of its
+ * drin_batch counterpart (inner dims, the [B, N, T, D] token block when entity_tokens > 0, pooled [B, N, D] text plus
+ * entity_text_cls in the pooled-ahead form), is fp32, 16-byte aligned and WRITTEN (not accumulated).  A NULL output is not
+ * wanted and nothing is computed for it.  `scratch` (device, 16-byte aligned): drin_input_grad_scratch_bytes(cfg) bytes,
+ * used only while the call runs. */
+typedef struct {
+  float *mention_text, *mention_image, *mention_object, *mention_object_score;
+  float *entity_text, *entity_text_cls, *entity_image, *entity_object, *entity_object_score;
+  float *miet_similarity, *mtei_similarity;
+  void* scratch;
+  size_t scratch_bytes;
+} drin_input_grads;
+
 /* Optional taps of intermediate values for tests/debugging (any pointer may be NULL).
  * Index l = 0 is the VertexEncoder/EdgeEncoder output, l >= 1 the output of GCN layer l. */
 typedef struct {
@@ -306,8 +320,8 @@ DRIN_API int drin_forward_staged(const drin_config* cfg, const drin_batch* batch
                  const drin_trace* trace, void* params_ready_event, void* stream);
 
 /* Backward of drin_forward: given grad_scores[B, N], accumulates parameter gradients into `grads`
- * (loss.backward() of train.py:33-34 through model.py:164-209).  Inputs carry no gradient in the
- * reference (precomputed features), so none is produced. */
+ * (loss.backward() of train.py:33-34 through model.py:164-209).  drin_backward_ex adds the gradients of the batch
+ * tensors. */
 DRIN_API int drin_backward(const drin_config* cfg, const drin_batch* batch, const drin_params* params,
                   void* workspace, size_t workspace_bytes, const float* grad_scores,
                   const drin_param_grads* grads, void* stream);
@@ -324,6 +338,30 @@ DRIN_API int drin_backward(const drin_config* cfg, const drin_batch* batch, cons
 DRIN_API int drin_backward_staged(const drin_config* cfg, const drin_batch* batch, const drin_params* params,
                   void* workspace, size_t workspace_bytes, const float* grad_scores,
                   const drin_param_grads* grads, void* layers_ready_event, void* stream);
+
+/* drin_backward_staged with input gradients: the one backward entry point the two above call (input_grads = NULL), with
+ * their launches and results.  `grads` may be NULL: no weight-gradient product runs (frozen-model attribution: gradient x
+ * input, or training something upstream of the model).  `input_grads` may be NULL (= drin_backward_staged); else the
+ * gradients of the batch tensors are written after every parameter gradient, from the vertex-encoder output gradients and
+ * the layer-0 edge gradients the pass computes anyway: the Linear dX products (the two pair-sized ones - entity image
+ * [B N, D] x [D, R], entity text - in split-bf16 against transposed weight planes when the precision is split-bf16, exact
+ * fp32 otherwise), the span / token / axis mean backward, the text-text cosine, the image-image edge (model.py:78-92), the
+ * CLIP edges (/ clip_scale, model.py:203) and the edge_enabled mask (model.py:122).  Not with entity_index (gather the
+ * rows: DRIN_E_UNSUPPORTED), and at most 64 object pairs (mention_objects x entity_objects). */
+DRIN_API int drin_backward_ex(const drin_config* cfg, const drin_batch* batch, const drin_params* params,
+                              void* workspace, size_t workspace_bytes, const float* grad_scores,
+                              const drin_param_grads* grads, const drin_input_grads* input_grads,
+                              void* layers_ready_event, void* stream);
+/* Bytes of drin_input_grads.scratch for `cfg` (0 on error). */
+DRIN_API size_t drin_input_grad_scratch_bytes(const drin_config* cfg);
+
+/* Backward of drin_pool_fwd's entity token mean (ghmfc.py:245-249) plus the token-0 row the text-text edge reads
+ * (model.py:73-75): from the pooled gradient grad_pooled [B, N, D], the token-0 gradient grad_cls [B, N, D] (NULL: zero) and
+ * entity_text_mask [B, N, T], WRITES the whole token-block gradient [B, N, T, D] (T = cfg.entity_tokens): token 0 gets
+ * grad_cls, tokens 1 .. ntok - 2 grad_pooled / (ntok - 2) (ntok = 0: tokens 1 .. T - 2, the slice's -1 stop), every other
+ * token 0.  Stored as fp32 or, with cfg.feature_dtype == DRIN_FEAT_BF16, bf16 (embed_dim % 8 == 0). */
+DRIN_API int drin_pool_bwd(const drin_config* cfg, const int64_t* entity_text_mask, const float* grad_pooled,
+                           const float* grad_cls, void* grad_entity_text, void* stream);
 
 /* ---- fused two-layer inference path ------------------------------------------------------------
  * Same result as drin_forward (fp32 re-association only) for the default geometry num_layers == 2,

@@ -31,10 +31,13 @@ EDGE_GRAPH = [[0, 2], [0, 3], [1, 2], [1, 3]]
 def span_mean(seq: torch.Tensor, begin: torch.Tensor, end: torch.Tensor) -> torch.Tensor:
     """`Avg.avg` (baselines/ghmfc.py:54-60): mean of seq[i, begin[i]:end[i]] over tokens.
 
-    Python slice semantics are kept (end clipped to L); an empty span is 0/0 = NaN exactly
-    like `torch.mean` of an empty slice.
+    Python slice semantics are kept: a negative bound counts from L (and stops at 0), both are
+    clipped to L; an empty span (start >= end after that) is 0/0 = NaN exactly like `torch.mean`
+    of an empty slice.
     """
     L = seq.shape[1]
+    begin = torch.where(begin < 0, begin + L, begin).clamp(min=0, max=L)
+    end = torch.where(end < 0, end + L, end).clamp(min=0, max=L)
     idx = torch.arange(L)
     m = (idx[None, :] >= begin[:, None]) & (idx[None, :] < end[:, None])
     total = torch.where(m[..., None], seq, torch.zeros((), dtype=seq.dtype)).sum(1)

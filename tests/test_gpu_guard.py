@@ -4,7 +4,9 @@ buffer the host side allocates while a path runs (workspaces sized by the librar
 per-entity caches, score and gradient tensors) gets a poisoned guard band in FRONT of and BEHIND it, and the bands are checked
 after the call.  Paths: folded inference at the headline's own width (whole-mention and 16-candidate workgroups) and at the
 tiny widths, WikiDiverse layout, bf16-stored features, the fp16 image contraction, table form, the per-entity cache in both row
-formats (build + scoring), training forward + backward + library Adam + the loss / metric kernels, vector edges."""
+formats (build + scoring), training forward + backward + library Adam + the loss / metric kernels, vector edges, and the
+gradients of the batch tensors (drin_backward_ex, drin_pool_bwd) - there with every allocation of backward() also poisoned
+with NaN, so that an output element left unwritten or scratch read before it is written cannot pass."""
 import math
 
 import pytest
@@ -29,6 +31,8 @@ class Guarded:
 
     def __init__(self, monkeypatch):
         self.bufs = []
+        self.poison = False        # True: the body of every torch.empty / empty_like tensor is 0xFF bytes (NaN) - an element a
+        #                            path leaves unwritten, or scratch it reads before writing, shows up as a NaN in its output
         self._orig = {name: getattr(torch, name) for name in ("empty", "zeros", "empty_like")}
         for name in ("empty", "zeros"):
             monkeypatch.setattr(torch, name, self._wrap(name))
@@ -42,7 +46,11 @@ class Guarded:
         raw[GUARD + nbytes:] = 0x5A
         self.bufs.append((raw, nbytes, shape, str(dtype)))
         t = raw[GUARD:GUARD + nbytes].view(dtype).view(shape)
-        return t.zero_() if zero else t
+        if zero:
+            return t.zero_()
+        if self.poison:
+            raw[GUARD:GUARD + nbytes] = 0xFF
+        return t
 
     def _wrap(self, name):
         orig = self._orig[name]
@@ -165,3 +173,58 @@ def test_the_guard_bands_do_catch_a_stray_store(guarded):
         guarded.check("stray store in front")
     ws = torch.empty(64, dtype=torch.uint8, device=DEV)
     assert guarded.check("clean") == 1 and ws.numel() == 64
+    guarded.poison = True                  # poison mode: one element left unwritten is a NaN
+    t = torch.empty(5, dtype=torch.float32, device=DEV)
+    t[:4] = 1.0
+    assert bool(torch.isfinite(t[:4]).all()) and bool(torch.isnan(t[4]))
+
+
+FLOAT_INPUTS = (0, 4, 5, 6, 7, 9, 10, 11, 12, 13)
+
+
+@pytest.mark.parametrize("name,cfg,B,precision,features,frozen", [
+    ("reference_batch_bf16x3", wikimel_config(), 64, "bf16x3", "f32", False),
+    ("reference_batch_f32", wikimel_config(), 64, "f32", "f32", False),
+    ("bf16_token_block_d768", wikimel_config(max_entity_attr_token_len=9), 12, "bf16x3", "bf16", False),
+    ("bf16_token_block_tiny", DrinConfig(dataset_name="wikimel", num_candidates_data=20, max_entity_attr_token_len=7, **TINY), 5,
+     "bf16x3", "bf16", False),
+    ("three_layers_vector_edges", DrinConfig(num_candidates_data=12, num_gcn_layers=3, gcn_edge_feature="vector", **TINY), 6,
+     "bf16x3_all", "f32", False),
+    ("inner_dims", DrinConfig(num_candidates_data=9, object_topk_entity=2, **TINY), 5, "f32", "inner", False),
+    ("object_pairs_64", DrinConfig(num_candidates_data=7, object_topk_mention=8, object_topk_entity=8, **TINY), 4, "bf16x3", "f32",
+     False),
+    ("frozen_model", wikimel_config(max_entity_attr_token_len=6), 11, "bf16x3", "f32", True),
+])
+def test_input_gradients_stay_inside_their_buffers_and_write_every_element(guarded, name, cfg, B, precision, features, frozen):
+    """drin_backward_ex (and drin_pool_bwd for a bf16 token block) with every float batch tensor a leaf: the guard bands hold,
+    and with backward()'s allocations poisoned every gradient of a batch with finite scores is finite."""
+    batch = _dev_batch(cfg, B, 13, torch.bfloat16 if features == "bf16" else torch.float32)[:14]
+    if features == "inner":                   # mention objects [B, Km, 2, R], entity image [B, N, 3, R], entity objects [B, N, Ke, 2, R]
+        g = torch.Generator(device=DEV).manual_seed(4)
+        N, R, Km, Ke = cfg.num_candidates_model, cfg.resnet_embed_dim, cfg.object_topk_mention, cfg.object_topk_entity
+        batch[5] = torch.randn((B, Km, 2, R), generator=g, device=DEV)
+        batch[9] = torch.randn((B, N, 3, R), generator=g, device=DEV)
+        batch[10] = torch.randn((B, N, Ke, 2, R), generator=g, device=DEV)
+    guarded.check("batch generation")
+    model = Model(cfg, precision=precision).to(DEV)
+    if frozen:
+        model.requires_grad_(False)
+    x = list(batch)
+    for i in FLOAT_INPUTS:
+        x[i] = x[i].detach().clone().requires_grad_(True)
+    scores = model(x)
+    assert bool(torch.isfinite(scores).all())
+    w = torch.linspace(-1.0, 1.0, scores.numel(), device=DEV).view(scores.shape)
+    guarded.check(f"{name}: forward")
+    guarded.poison = True
+    try:
+        (scores * w).sum().backward()
+        n = guarded.check(f"{name}: backward into the batch tensors")
+    finally:
+        guarded.poison = False
+    assert n >= 2
+    for i in FLOAT_INPUTS:
+        assert x[i].grad is not None and x[i].grad.dtype == x[i].dtype, i
+        assert bool(torch.isfinite(x[i].grad).all()), f"{name}: batch tensor {i} has a non-finite gradient (an unwritten element?)"
+    for p in model.parameters():
+        assert (p.grad is None) if frozen else (p.grad is None or bool(torch.isfinite(p.grad).all()))

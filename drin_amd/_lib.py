@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # DRIN_LIB_PATH: another build of the same library (the sanitizer build of `python -m drin_amd.build --asan-host`)
 LIB_PATH = os.environ.get("DRIN_LIB_PATH") or os.path.join(_HERE, "libdrin_hip.so")
 MAX_LAYERS = 8
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 OK, E_SHAPE, E_NULL, E_ALIGN, E_WORKSPACE, E_HIP, E_UNSUPPORTED, E_INDEX = 0, -1, -2, -3, -4, -5, -6, -7
 PREC_F32, PREC_BF16X3, PREC_BF16X3_ALL, PREC_BF16X3_IF16 = 0, 1, 3, 5     # (2 and 4: removed with ABI 6 - outside the 1e-4 bar)
@@ -73,6 +73,29 @@ class DrinInputGradsC(C.Structure):
         ("scratch_bytes", C.c_size_t)]
 
 
+class DrinMelhiConfigC(C.Structure):
+    _fields_ = [("batch", C.c_int32), ("num_candidates", C.c_int32), ("embed_dim", C.c_int32), ("image_dim", C.c_int32),
+                ("mention_tokens", C.c_int32), ("image_regions", C.c_int32), ("precision", C.c_int32),
+                ("cosine_eps", C.c_float), ("thres_tmim", C.c_float), ("thres_imie", C.c_float)]
+
+
+class DrinMelhiBatchC(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in (
+        "mention_feature", "mention_mask", "start", "end", "mention_image", "entity_feature", "entity_image")]
+
+
+MELHI_PARAMS = ("w_image_map_text", "b_image_map_text", "w_ih", "w_hh", "b_ih", "b_hh", "w_mention_final_map",
+                "b_mention_final_map", "w_entity_final_map", "b_entity_final_map")
+
+
+class DrinMelhiParamsC(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in MELHI_PARAMS]
+
+
+class DrinMelhiParamGradsC(C.Structure):  # same shape, mutable pointers
+    _fields_ = DrinMelhiParamsC._fields_
+
+
 class DrinTraceC(C.Structure):
     _fields_ = [(n, C.c_void_p * (MAX_LAYERS + 1)) for n in (
         "mention_text_vertex", "mention_image_vertex", "entity_text_vertex", "entity_image_vertex", "edges")]
@@ -128,11 +151,17 @@ EXPORTS = {
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "drin_adam_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_float,
                                  C.c_float, C.c_float, C.c_float, C.c_void_p]),
+    "drin_melhi_workspace_bytes": (C.c_size_t, [C.POINTER(DrinMelhiConfigC), C.c_int]),
+    "drin_melhi_forward": (C.c_int, [C.POINTER(DrinMelhiConfigC), C.POINTER(DrinMelhiBatchC), C.POINTER(DrinMelhiParamsC), C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "drin_melhi_backward": (C.c_int, [C.POINTER(DrinMelhiConfigC), C.POINTER(DrinMelhiBatchC), C.POINTER(DrinMelhiParamsC),
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(DrinMelhiParamGradsC),
+                                      C.c_void_p]),
     "drin_profile_begin": (C.c_int, [C.c_int]),
     "drin_profile_end": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "drin_kernel_class_name": (C.c_char_p, [C.c_int]),
 }
-KERNEL_CLASSES = 8
+KERNEL_CLASSES = 10
 
 
 class DrinError(RuntimeError):

@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define DRIN_ABI_VERSION 8
+#define DRIN_ABI_VERSION 9
 #define DRIN_API __attribute__((visibility("default")))
 
 typedef enum {
@@ -460,6 +460,70 @@ DRIN_API int drin_adam_step(float* param, const float* grad, float* exp_avg, flo
                             float lerp_weight, float beta2, float one_minus_beta2, float bias_correction2_sqrt, float eps,
                             float neg_step_size, void* stream);
 
+/* ---- the MELHI baseline (reference baselines/melhi.py, WikiDiverse) ------------------------------ *
+ * The reference's train.py selects it with model_type "melhi".  Scores [B, N] = cos(mention_final_map([left | right]),
+ * entity_final_map([entity_feature | eim])) where left / right are what the reference's lstm_extract_last returns for the
+ * two context sequences of each mention.  H = 3 embed_dim. */
+typedef struct {
+  int32_t batch;           /* B mentions (1 .. 16384)                                                   */
+  int32_t num_candidates;  /* N = num_candidates_model                                                  */
+  int32_t embed_dim;       /* D = bert_embed_dim (multiple of 4, <= 1024)                               */
+  int32_t image_dim;       /* R = resnet_embed_dim (multiple of 4)                                      */
+  int32_t mention_tokens;  /* L = max_mention_sentence_len (>= 2)                                       */
+  int32_t image_regions;   /* P = resnet_num_region                                                     */
+  int32_t precision;       /* DRIN_PREC_BF16X3 or DRIN_PREC_F32 (the contractions; the recurrence is fp32 FMA) */
+  float cosine_eps;        /* 1e-8  (nn.CosineSimilarity default)                                        */
+  float thres_tmim;        /* 0.3   (args.py thres_tmim: text / mention-image cosine, strict >)          */
+  float thres_imie;        /* 0.3   (args.py thres_imie: mention-image / entity-image cosine, strict >)  */
+} drin_melhi_config;
+
+/* The WikiDiverse batch of melhi.py (entity_mask is not read).  Device pointers, fp32 unless int64. */
+typedef struct {
+  const float* mention_feature;  /* [B, L, D]                                                            */
+  const int64_t* mention_mask;   /* [B, L]   0 / 1; its row sum ends the right context                  */
+  const int64_t* start;          /* [B]      already +1 for CLS                                          */
+  const int64_t* end;            /* [B]                                                                  */
+  const float* mention_image;    /* [B, P, R]                                                            */
+  const float* entity_feature;   /* [B, N, D]                                                            */
+  const float* entity_image;     /* [B, N, R]                                                            */
+} drin_melhi_batch;
+
+/* The 10 state_dict tensors (nn.Linear layout weight[out][in]). */
+typedef struct {
+  const float *w_image_map_text, *b_image_map_text;       /* image_map_text                  [D, R], [D]     */
+  const float *w_ih, *w_hh, *b_ih, *b_hh;                 /* mention_encoder.mention_lstm    [4H, H] x2, [4H] x2 */
+  const float *w_mention_final_map, *b_mention_final_map; /* mention_encoder.mention_final_map [D, 2H], [D]  */
+  const float *w_entity_final_map, *b_entity_final_map;   /* entity_final_map                [D, 2D], [D]    */
+} drin_melhi_params;
+
+/* Gradients of the same tensors, ACCUMULATED (+=); NULL: not wanted. */
+typedef struct {
+  float *w_image_map_text, *b_image_map_text;
+  float *w_ih, *w_hh, *b_ih, *b_hh;
+  float *w_mention_final_map, *b_mention_final_map;
+  float *w_entity_final_map, *b_entity_final_map;
+} drin_melhi_param_grads;
+
+/* Bytes of workspace for drin_melhi_forward (for_training = 0) or for a forward kept for drin_melhi_backward (1); 0 on error. */
+DRIN_API size_t drin_melhi_workspace_bytes(const drin_melhi_config* cfg, int for_training);
+
+/* Model.forward of melhi.py.  `order` and `lengths` are HOST int32 [2, B] (row 0 the left contexts, row 1 the right ones):
+ * lengths[s][b] is the length of the sequence the reference packs (the context length, 1 for its all-zero placeholder row:
+ * left = min(start, L) - 1 if start > 1, right = sum(mention_mask) - end if that is > end), and order[s] is the permutation
+ * torch.sort(torch.as_tensor(lengths[s], dtype=int64), descending=True) returns on the CPU - NOT stable, so the caller
+ * computes it with that call and the library never sorts.  Refused on the host (DRIN_E_INDEX): an order that is not a
+ * permutation or not sorted by descending length; lengths outside [1, L - 1] (left) / [1, L] (right): DRIN_E_SHAPE.  The
+ * gather tables derived from the order are copied into the workspace with hipMemcpyAsync on `stream`.  The workspace
+ * (drin_melhi_workspace_bytes) keeps what drin_melhi_backward needs. */
+DRIN_API int drin_melhi_forward(const drin_melhi_config* cfg, const drin_melhi_batch* batch, const drin_melhi_params* params,
+                                const int32_t* order, const int32_t* lengths, void* workspace, size_t workspace_bytes,
+                                float* scores, void* stream);
+/* Backward of the drin_melhi_forward that left `workspace` (sized for training), same batch, params, order and lengths:
+ * accumulates the parameter gradients for grad_scores [B, N].  No gradients of the batch tensors. */
+DRIN_API int drin_melhi_backward(const drin_melhi_config* cfg, const drin_melhi_batch* batch, const drin_melhi_params* params,
+                                 const int32_t* order, const int32_t* lengths, void* workspace, size_t workspace_bytes,
+                                 const float* grad_scores, const drin_melhi_param_grads* grads, void* stream);
+
 /* ---- in-process kernel timing (bench.py's roofline leg) ---------------------------------------- */
 
 /* Kernel classes the launches are attributed to. */
@@ -472,7 +536,9 @@ typedef enum {
   DRIN_KC_GEMM_X3 = 5,     /* k_gemm_bf16x3: split-bf16 contraction, fp32 operands split on the fly */
   DRIN_KC_GEMM_PLANES = 6, /* k_gemm_x3_planes: split-bf16 contraction on pre-split planes (LDS-DMA) */
   DRIN_KC_OPTIM = 7,       /* drin_adam_step                                                        */
-  DRIN_KC_COUNT = 8
+  DRIN_KC_LSTM = 8,        /* drin_melhi_*: one step of the long LSTM recurrences (forward or backward) */
+  DRIN_KC_CELL = 9,        /* drin_melhi_*: mask, time-0 cells, gathers and their backward           */
+  DRIN_KC_COUNT = 10
 } drin_kernel_class;
 
 /* While a profile is open, every launch the library makes - from any thread, e.g. drin_backward on

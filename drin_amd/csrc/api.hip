@@ -478,7 +478,6 @@ static int run_input_grads(const drin_config* c, const drin_batch* b, const drin
   const int mobj_in = c->mention_object_inner > 1 ? c->mention_object_inner : 1;
   const int eimg_in = c->entity_image_inner > 1 ? c->entity_image_inner : 1;
   const int eobj_in = c->entity_object_inner > 1 ? c->entity_object_inner : 1;
-  const bool x3 = c->precision == DRIN_PREC_BF16X3 || c->precision == DRIN_PREC_BF16X3_ALL;
   InputGradScratch S;
   S.build(*c);
   float* sc = (float*)ig->scratch;
@@ -487,18 +486,14 @@ static int run_input_grads(const drin_config* c, const drin_batch* b, const drin
   const float* g_mi = g_vm0 + BD;
   const float* g_et = g_ve0;
   const float* g_ei = g_ve0 + MD;
-  // pair-sized dX = dY W (W [D][n_out]): split-bf16 on the NT kernel against W^T planes, as the layer loop's pair-sized
-  // products; exact fp32 otherwise
+  // pair-sized dX = dY W (W [D][n_out]): launch_gemm_nn, against W^T planes written here when it takes split-bf16
   auto pair_dx = [&](const float* g, const float* w, float* planes, float* out, int n_out, bool acc) -> int {
-    if (x3 && M >= 1024 && (D % 32) == 0 && (n_out % 4) == 0) {
+    if (gemm_nn_takes_bf16x3(c->precision, (int64_t)M, n_out, D)) {
       SplitBatch tb;
       DRIN_TRY(tb.add(w, planes, (int64_t)D * n_out));
       DRIN_TRY(launch_transpose_split_batch(tb, D, n_out, st));
-      const __bf16* hi = reinterpret_cast<const __bf16*>(planes);
-      return launch_gemm_nt_bf16x3(g, D, nullptr, D, nullptr, out, n_out, (int64_t)M, n_out, D, st, hi, hi + (size_t)D * n_out,
-                                   acc, nullptr, 0);
     }
-    return launch_gemm_nn(g, D, w, n_out, out, n_out, (int64_t)M, n_out, D, acc, DRIN_PREC_F32, st);
+    return launch_gemm_nn(g, D, w, n_out, out, n_out, (int64_t)M, n_out, D, acc, c->precision, st, nullptr, 0, {planes});
   };
 
   // the scalar layer-0 edges: vector edges are the scalar ones broadcast over D (model.py:202) - their row sums
@@ -743,19 +738,13 @@ int drin_linear_bwd(const float* x, const float* w, const float* dy, float* dx, 
   }
   if (rows == 0) return DRIN_OK;
   hipStream_t st = (hipStream_t)stream;
-  const bool x3 = precision == DRIN_PREC_BF16X3 || precision == DRIN_PREC_BF16X3_ALL;
   if (dx) {
-    // the contraction index of dx = dy W is n: the NT kernel needs W^T [k][n_out]
-    if (x3 && scratch && scratch_floats >= (size_t)n_out * k && rows >= 1024 && (n_out % 32) == 0 && (k % 4) == 0) {
-      DRIN_TRY(launch_transpose(w, scratch, n_out, k, st));
-      // what the transposed weight leaves of the scratch lets a partly filled last round of tiles split along K
-      const size_t used = ((size_t)n_out * k + 63) & ~(size_t)63;
-      float* tail = scratch_floats > used ? scratch + used : nullptr;
-      DRIN_TRY(launch_gemm_nt_bf16x3(dy, n_out, scratch, n_out, nullptr, dx, k, rows, k, n_out, st, nullptr, nullptr, false,
-                                     tail, tail ? scratch_floats - used : 0));
-    } else {
-      DRIN_TRY(launch_gemm_nn(dy, n_out, w, k, dx, k, rows, k, n_out, false, precision, st));
-    }
+    // the scratch holds W^T [k][n_out] for the split-bf16 form; what that leaves of it lets a partly filled last round of
+    // tiles split along K
+    const size_t used = ((size_t)n_out * k + 63) & ~(size_t)63;
+    float* tail = scratch && scratch_floats > used ? scratch + used : nullptr;
+    DRIN_TRY(launch_gemm_nn(dy, n_out, w, k, dx, k, rows, k, n_out, false, precision, st, nullptr, 0,
+                            {nullptr, scratch, scratch_floats, tail, tail ? scratch_floats - used : 0}));
   }
   // (stream order makes the scratch reusable product after product; every split reduction goes through it and is added in
   //  order - without scratch one workgroup per output tile / per 256 columns walks the whole reduction: no atomics either way)
@@ -1156,15 +1145,14 @@ int drin_backward_ex(const drin_config* cfg, const drin_batch* batch, const drin
   const int act_eb = from_z ? (act_e | 0x100) : act_e;   // device_utils.h: kActFromPre
   float* const smp = ws + L.small_part;     // slices of the mention-sized exact-fp32 dW products
   float* const csp = ws + L.colsum_part;    // partial rows of the bias column sums
-  // dX (+)= dY W.  Pair-sized products in split-bf16 precision run on the NT kernel against W^T, transposed into
-  // workspace scratch right before use (a D x D transpose is ~3 us; the product it feeds is 2.5x faster than
-  // the exact-fp32 MFMA one); everything else takes the exact fp32 NN kernel.
   const bool x3 = prec == DRIN_PREC_BF16X3 || prec == DRIN_PREC_BF16X3_ALL;
-  // scalar edges: W_h^T and W_v^T of every layer in ONE batched transpose up front (slots 2 l and 2 l + 1 of L.wt);
-  // anything else (W_u at 512+ mentions; the half-width W_u / W_v and W_m of vector edges) is transposed per product into the last slot
-  const bool pre_t = x3 && !cfg->vector_edges && M >= 1024 && (D % 32) == 0;
+  // dX (+)= dY W (launch_gemm_nn).  Scalar edges: W_h^T and W_v^T of every layer in ONE batched transpose up front (slots
+  // 2 l and 2 l + 1 of L.wt), split into bf16 (hi, lo) planes in the same pass - the NT kernel streams them by LDS-DMA;
+  // anything else (W_u at 512+ mentions; the half-width W_u / W_v and W_m of vector edges) that takes split-bf16 is
+  // transposed per product into the last slot, never one of the pre-transposed weights
+  const bool pre_t = !cfg->vector_edges && gemm_nn_takes_bf16x3(prec, (int64_t)M, D, D);
   auto wt_slot = [&](int l, int which) { return ws + L.wt + ((size_t)2 * l + which) * D * D; };
-  if (pre_t) {  // ... and split into bf16 (hi, lo) planes in the same pass: the NT kernel streams them by LDS-DMA
+  if (pre_t) {
     SplitBatch tb;
     for (int l = 0; l < nl; ++l) {
       DRIN_TRY(tb.add(params->layer[l].w_h, wt_slot(l, 0), (int64_t)D * D));
@@ -1175,22 +1163,9 @@ int drin_backward_ex(const drin_config* cfg, const drin_batch* batch, const drin
   auto gemm_nn = [&](const float* dy, int64_t lddy, const float* w, float* dx, int64_t lddx, int64_t rows, int n_out,
                      int k_red, bool accumulate, const float* w_t = nullptr) -> int {
     // w is [k_red][n_out] contiguous; w_t: bf16 (hi, lo) planes of its transpose, already in the workspace
-    if (x3 && rows >= 1024 && (k_red % 32) == 0 && (n_out % 4) == 0 && (size_t)k_red * n_out <= (size_t)D * D) {
-      if (w_t != nullptr) {
-        const __bf16* hi = reinterpret_cast<const __bf16*>(w_t);
-        return launch_gemm_nt_bf16x3(dy, lddy, nullptr, k_red, nullptr, dx, lddx, rows, n_out, k_red, st, hi, hi + (size_t)k_red * n_out,
-                                     accumulate, tnp, tnf);
-      }
-      if (w_t == nullptr) {
-        float* wt = ws + L.wt + (size_t)2 * nl * D * D;   // the scratch slot: never one of the pre-transposed weights
-        DRIN_TRY(launch_transpose(w, wt, k_red, n_out, st));
-        w_t = wt;
-      }
-      return launch_gemm_nt_bf16x3(dy, lddy, w_t, k_red, nullptr, dx, lddx, rows, n_out, k_red, st, nullptr, nullptr, accumulate,
-                                   tnp, tnf);
-    }
     return launch_gemm_nn(dy, lddy, w, n_out, dx, lddx, rows, n_out, k_red, accumulate, prec, st,
-                          L.splitk_floats ? ws + L.splitk : nullptr, L.splitk_floats);
+                          L.splitk_floats ? ws + L.splitk : nullptr, L.splitk_floats,
+                          {w_t, wt_slot(nl, 0), (size_t)D * D, tnp, tnf});
   };
   SliceSum ln_sums;        // second level of the LayerNorm backward's column sums (dgamma, dbeta, db_h of every layer)
   ColsumBatch bias_sums;   // the bias gradients of W_u / W_v and of the vertex encoders: one launch

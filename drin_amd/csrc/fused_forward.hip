@@ -308,50 +308,11 @@ static int forward_prepared_on_stream(const drin_config* cfg, const drin_batch* 
   const drin_layer_params& L1 = params->layer[0];
   const drin_layer_params& L2 = params->layer[1];
 
-  // Mention-sized contractions: the configured precision; in split-bf16 precision problems of >= 256 rows stream
-  // the pre-split weight planes by LDS-DMA, smaller ones (latency-bound) stay on the exact fp32 kernel
-  auto lin = [&](const float* x, int64_t ldx, const float* w, int64_t ldw, size_t plane_off, size_t plane_elems,
-                 const float* bias, float* y, int64_t ldy, int64_t rows, int n_out, int k) -> int {
-    if (planes && (rows >= 256 || prec == DRIN_PREC_BF16X3_ALL) && (k % 32) == 0 && (ldw % 8) == 0) {
-      const __bf16* hi = reinterpret_cast<const __bf16*>(pb + plane_off);
-      return launch_gemm_nt_bf16x3(x, ldx, w, ldw, bias, y, ldy, rows, n_out, k, st, hi, hi + plane_elems, false,
-                                   L.splitk_floats ? ws + L.splitk : nullptr, L.splitk_floats);
-    }
-    return launch_gemm_nt(x, ldx, w, ldw, bias, y, ldy, rows, n_out, k, false, prec, st,
-                          L.splitk_floats ? ws + L.splitk : nullptr, L.splitk_floats);
-  };
-  // Two such products that do not depend on each other, both on the exact-fp32 split-K kernel (small batches): one launch for
-  // the two kernels, one for the two slice reductions (gemm_f32.hip: F32GemmGroup; same slices, same order, same bits)
-  struct Lin {
-    const float* x;
-    int64_t ldx;
-    const float* w;
-    int64_t ldw;
-    size_t plane_off, plane_elems;
-    const float* bias;
-    float* y;
-    int64_t ldy, rows;
-    int n_out, k;
-  };
-  auto lin_pair = [&](const Lin& a, const Lin& b) -> int {
-    const Lin* two[2] = {&a, &b};
-    bool grouped = L.splitk_floats > 0;
-    size_t need = 8;
-    for (const Lin* q : two) {
-      const bool x3 = planes && (q->rows >= 256 || prec == DRIN_PREC_BF16X3_ALL) && (q->k % 32) == 0 && (q->ldw % 8) == 0;
-      grouped = grouped && !x3 && gemm_nt_f32_group_fits(q->x, q->ldx, q->w, q->ldw, q->y, q->ldy, q->rows, q->n_out, q->k, prec);
-      need += (size_t)8 * q->rows * q->n_out;
-    }
-    if (grouped && need <= L.splitk_floats) {
-      F32GemmGroup g;
-      for (const Lin* q : two) DRIN_TRY(g.add_nt(q->x, q->ldx, q->w, q->ldw, q->bias, q->y, q->ldy, q->rows, q->n_out, q->k));
-      return launch_gemm_nt_f32_group(g, st, ws + L.splitk, L.splitk_floats);
-    }
-    for (const Lin* q : two)
-      DRIN_TRY(lin(q->x, q->ldx, q->w, q->ldw, q->plane_off, q->plane_elems, q->bias, q->y, q->ldy, q->rows, q->n_out, q->k));
-    return DRIN_OK;
-  };
-  const size_t DD = (size_t)D * D, DR = (size_t)D * R;
+  // Mention-sized contractions: launch_gemm_nt / launch_gemm_nt_pair choose the kernel; the split-bf16 ones read the prepared
+  // weight planes when this path has them (`planes` also asks R % 32, which those cannot see)
+  auto wp = [&](size_t plane_off) -> const float* { return planes ? pb + plane_off : nullptr; };
+  float* const sk = L.splitk_floats ? ws + L.splitk : nullptr;
+  const size_t skf = L.splitk_floats;
   float* vm0 = ws + L.vm0;
   float* hmfu = ws + L.hmfu;
   // pooled entity text stored as bf16 is exact in its hi plane: no lo plane, two MFMAs per tile pair
@@ -366,14 +327,16 @@ static int forward_prepared_on_stream(const drin_config* cfg, const drin_batch* 
                               cfg->mention_tokens, D, st));
     DRIN_TRY(launch_axis_mean(b->mention_image, ws + L.mimg, B, cfg->image_regions, R, st));
   }
-  // mention-sized contractions take the configured precision too: launch_gemm_nt keeps problems of fewer
-  // than 1024 rows on the fp32 kernel (latency-bound), larger ones (WikiDiverse batches) go split-bf16
-  DRIN_TRY(lin_pair({ws + L.span_mean, D, params->w_mention_text, D, P.p_wmt, DD, params->b_mention_text, vm0, D, B, D, D},
-                    {ws + L.mimg, R, params->w_mention_image, R, P.p_wmi, DR, params->b_mention_image, vm0 + (size_t)B * D, D, B, D, R}));
+  DRIN_TRY(launch_gemm_nt_pair({ws + L.span_mean, params->w_mention_text, params->b_mention_text, vm0, D, D, D, B, D, D, wp(P.p_wmt)},
+                               {ws + L.mimg, params->w_mention_image, params->b_mention_image, vm0 + (size_t)B * D, R, R, D, B, D, R,
+                                wp(P.p_wmi)},
+                               prec, st, sk, skf));
   // (2) [hm | fu] = [mt0; mi0] [W_h1; W_u1]^T + [0; b_u1], then q = fu [W_v1 W_et | W_v1 W_ei]
-  DRIN_TRY(lin(vm0, D, pb + P.wcat1, D, P.p_wcat1, 2 * DD, pb + P.bcat1, hmfu, 2 * D, 2 * (int64_t)B, 2 * D, D));
+  DRIN_TRY(launch_gemm_nt(vm0, D, pb + P.wcat1, D, pb + P.bcat1, hmfu, 2 * D, 2 * (int64_t)B, 2 * D, D, false, prec, st, sk, skf,
+                          wp(P.p_wcat1)));
   if (dyn)
-    DRIN_TRY(lin(hmfu + D, 2 * D, pb + P.ecat, D, P.p_ecat, DD + DR, nullptr, ws + L.q, D + R, 2 * (int64_t)B, D + R, D));
+    DRIN_TRY(launch_gemm_nt(hmfu + D, 2 * D, pb + P.ecat, D, nullptr, ws + L.q, D + R, 2 * (int64_t)B, D + R, D, false, prec, st, sk,
+                            skf, wp(P.p_ecat)));
   // (3) one pass over the entity-side bytes
   StreamArgs sa;
   memset(&sa, 0, sizeof(sa));
@@ -432,18 +395,20 @@ static int forward_prepared_on_stream(const drin_config* cfg, const drin_batch* 
   if (L.chunks > 1)
     DRIN_TRY(launch_reduce_stream_partials(ws + L.s_part, ws + L.s_text, ws + L.s_img, ws + L.sig, B, D, R, L.chunks, st));
   // (4) layer-1 mention vertices: T = S_text W_et^T + S_img W_ei^T, then the W_h input, W_h, LN, GELU
-  DRIN_TRY(lin_pair({ws + L.s_text, D, params->w_entity_text, D, P.p_wet, DD, nullptr, ws + L.tm, D, 2 * (int64_t)B, D, D},
-                    {ws + L.s_img, R, params->w_entity_image, R, P.p_wei, DR, nullptr, ws + L.tm2, D, 2 * (int64_t)B, D, R}));
+  DRIN_TRY(launch_gemm_nt_pair({ws + L.s_text, params->w_entity_text, nullptr, ws + L.tm, D, D, D, 2 * (int64_t)B, D, D, wp(P.p_wet)},
+                               {ws + L.s_img, params->w_entity_image, nullptr, ws + L.tm2, R, R, D, 2 * (int64_t)B, D, R,
+                                wp(P.p_wei)},
+                               prec, st, sk, skf));
   DRIN_TRY(launch_mention_input1(ws + L.tm, ws + L.tm2, ws + L.sig, params->b_entity_text, params->b_entity_image, vm0, ws + L.agg1, B, D, N, st));
   float* vm1 = ws + L.vm1;
-  DRIN_TRY(lin(ws + L.agg1, D, L1.w_h, D, P.p_wh1, DD, L1.b_h, vm1, D, 2 * (int64_t)B, D, D));
+  DRIN_TRY(launch_gemm_nt(ws + L.agg1, D, L1.w_h, D, L1.b_h, vm1, D, 2 * (int64_t)B, D, D, false, prec, st, sk, skf, wp(P.p_wh1)));
   DRIN_TRY(launch_layernorm_gelu(vm1, L1.ln_weight, L1.ln_bias, vm1, nullptr, nullptr, 2 * (int64_t)B, D, cfg->layer_norm_eps, st,
                                  vertex_act(cfg)));
-  DRIN_TRY(lin(vm1, D, L2.w_h, D, P.p_wh2, DD, nullptr, ws + L.hm2, D, 2 * (int64_t)B, D, D));
+  DRIN_TRY(launch_gemm_nt(vm1, D, L2.w_h, D, nullptr, ws + L.hm2, D, 2 * (int64_t)B, D, D, false, prec, st, sk, skf, wp(P.p_wh2)));
   // (5) the two pair-sized layer-1 contractions on the folded weights
   // split-K scratch: the whole-product split when the batch is a few tiles, else the tail-split scratch
-  float* const psk = L.pair_splitk_floats ? ws + L.pair_splitk : (L.splitk_floats ? ws + L.splitk : nullptr);
-  const size_t pskf = L.pair_splitk_floats ? L.pair_splitk_floats : L.splitk_floats;
+  float* const psk = L.pair_splitk_floats ? ws + L.pair_splitk : sk;
+  const size_t pskf = L.pair_splitk_floats ? L.pair_splitk_floats : skf;
   if (planes) {
     const __bf16* ct = reinterpret_cast<const __bf16*>(pb + P.p_ctxt);
     const __bf16* ci = reinterpret_cast<const __bf16*>(pb + P.p_cimg);
@@ -497,7 +462,7 @@ static int forward_prepared_on_stream(const drin_config* cfg, const drin_batch* 
   DRIN_TRY(launch_pair_layer1(pa, st));
   // (7) layer-2 mention-text vertex
   DRIN_TRY(launch_mention_input2(ws + L.s2_part, vm1, ws + L.agg2, B, D, N, L.chunks, st));
-  DRIN_TRY(lin(ws + L.agg2, D, L2.w_h, D, P.p_wh2, DD, L2.b_h, ws + L.mt2, D, B, D, D));
+  DRIN_TRY(launch_gemm_nt(ws + L.agg2, D, L2.w_h, D, L2.b_h, ws + L.mt2, D, B, D, D, false, prec, st, sk, skf, wp(P.p_wh2)));
   DRIN_TRY(launch_layernorm_gelu(ws + L.mt2, L2.ln_weight, L2.ln_bias, ws + L.mt2, nullptr, nullptr, B, D, cfg->layer_norm_eps, st,
                                  vertex_act(cfg)));
   // (8) layer-2 entity-text contraction, vertex and score

@@ -233,9 +233,22 @@ struct SplitBatch {
 };
 int launch_split_planes_batch(const SplitBatch& b, hipStream_t st);
 int launch_transpose_split_batch(const SplitBatch& b, int rows, int cols, hipStream_t st);
+// out [cols][rows] = in [rows][cols]^T, fp32 (fused_kernels.hip)
+int launch_transpose(const float* in, float* out, int rows, int cols, hipStream_t st);
 // y[m, n] (+)= sum_k x[m, k] * w[k, n]        (used by backward: dX = dY * W)
+// Pair-sized products in split-bf16 precision (gemm_nn_takes_bf16x3) run on the split-bf16 NT kernel against w^T when the
+// caller supplies it in one of the forms below; everything else takes the exact fp32 NN kernel (splitk: as launch_gemm_nt's).
+struct WtForms {
+  const float* planes = nullptr;   // bf16 hi / lo planes of w^T [N][K], already written (a caller that writes them asks the predicate)
+  float* scratch = nullptr;        // else: room for an fp32 w^T, transposed here; taken with w contiguous and N K floats of it
+  size_t scratch_floats = 0;
+  float* tail = nullptr;           // the NT kernel's tail-split scratch (launch_gemm_nt_bf16x3)
+  size_t tail_floats = 0;
+};
+bool gemm_nn_takes_bf16x3(int precision, int64_t M, int N, int K);
 int launch_gemm_nn(const float* x, int64_t ldx, const float* w, int64_t ldw, float* y, int64_t ldy, int64_t M, int N,
-                   int K, bool accumulate, int precision, hipStream_t st, float* splitk = nullptr, size_t splitk_floats = 0);
+                   int K, bool accumulate, int precision, hipStream_t st, float* splitk = nullptr, size_t splitk_floats = 0,
+                   const WtForms& wt = WtForms());
 // up to 8 MENTION-sized (M <= 2048 reduction rows) exact-fp32 products y[n, k] += sum_m a[m, n] b[m, k] in one launch
 struct F32GemmGroup {
   static constexpr int MAX = 8;

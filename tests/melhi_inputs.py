@@ -1,7 +1,11 @@
 """Deterministic MELHI batches for the golden cases (tools/gen_melhi_golden.py) and the tests that read them: numpy Philox
 streams keyed by the case name, so a batch is regenerated bit for bit anywhere.  The cases cover the extraction rule's
 corners: B = 1 (the row is the true last output), tie-heavy orders at B = 64 and 300 (ties at the longest length too),
-all-placeholder sides, an empty mention span (a NaN row), and image masks all on, all off and mixed."""
+all-placeholder sides, an empty mention span (a NaN row), and image masks all on, all off and mixed.
+
+A case runs at the TINY widths, at the reference's (`full`), or at a geometry of its own (`geom`: the shape cases of
+tests/golden/melhi_shapes.npz - widths off the GEMM tiles, one candidate and one region, L = 3 and L = 300 contexts, the
+validated maximum left length, D = 1024)."""
 from __future__ import annotations
 
 import numpy as np
@@ -29,7 +33,24 @@ CASES = {
     "b16_mask_off": dict(B=16, seed=10, spans="random", thres=(2.0, 2.0)),
     "full_b4": dict(B=4, seed=11, spans="random", image="mixed", full=True),
     "full_b64": dict(B=64, seed=12, spans="ties", image="mixed", full=True),
+    # shape cases: one geometry each
+    "odd_w": dict(B=64, seed=13, spans="ties", image="mixed", geom=dict(D=20, R=36, L=12, P=1, N=1)),
+    "short_L": dict(B=300, seed=14, spans="short", image="mixed", geom=dict(D=32, R=260, L=3, P=5, N=3)),
+    "long_lanes": dict(B=8, seed=15, spans="long_lanes", image="mixed", geom=dict(D=32, R=64, L=300, P=2, N=4)),
+    "max_len_nan": dict(B=64, seed=16, spans="max_len_nan", image="mixed", geom=dict(D=20, R=36, L=12, P=3, N=4)),
+    "wide_D": dict(B=128, seed=17, spans="ties", image="mixed", geom=dict(D=1024, R=128, L=16, P=2, N=8)),
 }
+SHAPE_CASES = [n for n, c in CASES.items() if "geom" in c]
+# gradient goldens in full for the small shape widths, in the checksum form of melhi_full.npz for wide_D, none for a case
+# whose scores hold NaN
+SHAPE_CHECKSUM = ("wide_D",)
+SHAPE_FORWARD_ONLY = ("max_len_nan",)
+
+
+def geometry(name: str) -> dict:
+    """D, R, L, P, N of case `name`."""
+    case = CASES[name]
+    return case["geom"] if "geom" in case else (FULL if case.get("full", False) else TINY)
 
 
 def _rng(name: str, stream: int) -> np.random.Generator:
@@ -44,7 +65,7 @@ def melhi_inputs(name: str, sd: dict):
     """The 8-item batch of case `name` (numpy float32 / int64 arrays; entity_mask is the int 0 of the WikiDiverse loader).
     `sd`: the case's state dict, used to aim the "mixed" images at the mask's thresholds."""
     case = CASES[name]
-    g = FULL if case.get("full", False) else TINY
+    g = geometry(name)
     B, D, R, L, P, N = case["B"], g["D"], g["R"], g["L"], g["P"], g["N"]
     r = _rng(name, 1)
     mf = r.standard_normal((B, L, D), dtype=np.float32)
@@ -64,6 +85,19 @@ def melhi_inputs(name: str, sd: dict):
         s = np.where(r.random(B) < 0.5, L - 4, r.integers(0, 3, size=B))
         e = np.minimum(s + 1, L - 2)
         mlen = np.where(r.random(B) < 0.5, L, e + 2)
+    elif spans == "short":     # L = 3: every context has length <= 1, real ones on both sides
+        s = r.integers(0, 2, size=B)   # start 1 (left placeholder) or 2 (left token 1)
+        e = s + 1
+        mlen = np.where(s == 0, r.integers(2, 4, size=B), L)   # start 1, end 2 with a full mask: right token 2
+    elif spans in ("long_lanes", "max_len_nan"):   # "ties", plus the longest contexts the validation admits
+        s = np.where(r.random(B) < 0.4, 0, r.integers(1, 4, size=B))
+        e = s + 1
+        mlen = np.minimum(e + 1 + r.integers(0, 3, size=B), L)
+        if spans == "long_lanes":
+            s[0], e[0] = L - 2, L - 1                   # start L - 1, end L: left context 1 .. L - 2
+            s[1], e[1], mlen[1] = 0, 1, L               # start 1, end 2, full mask: right context 2 .. L - 1
+        else:
+            s[::11] = e[::11] = L - 1                   # start = end = L: left length L - 1, an empty span (a NaN row)
     elif spans == "placeholder":   # both contexts empty everywhere
         s = np.zeros(B, dtype=np.int64)
         e = s + 1
@@ -84,5 +118,6 @@ def melhi_inputs(name: str, sd: dict):
         on = np.arange(B) % 2 == 0
         mimg = mimage.mean(1)
         mf[on, 0] = (mimg @ w.T + b)[on] + 0.3 * mf[on, 0]
-        eimage[on, 1] = mimg[on] + 0.1 * eimage[on, 1]
+        n1 = min(1, N - 1)
+        eimage[on, n1] = mimg[on] + 0.1 * eimage[on, n1]
     return [mf, mmask, torch.from_numpy(start), torch.from_numpy(end), mimage, ef, 0, eimage]

@@ -1,5 +1,6 @@
-"""CPU checks of the MELHI baseline: the test-side restatement against the reference's goldens, torch's tie order, the
-Module's keys / initialisation / dataset refusal, and the C ABI's structs and host-side refusals."""
+"""CPU checks of the MELHI baseline: the test-side restatement against the reference's goldens (the tiny cases and the
+shape cases of melhi_shapes.npz, with what each shape case must reach), torch's tie order, the Module's keys /
+initialisation / dataset refusal, and the C ABI's structs and host-side refusals."""
 import ctypes as C
 import os
 import subprocess
@@ -11,12 +12,13 @@ from torch import nn
 
 from drin_amd import _lib
 from drin_amd.melhi import MelhiConfig, Model, orders_and_lengths, torch_order
-from tests.melhi_inputs import CASES, FULL, KEYS, TINY, grad_weights, melhi_inputs
+from tests.melhi_inputs import (CASES, KEYS, SHAPE_CASES, SHAPE_CHECKSUM, SHAPE_FORWARD_ONLY, TINY, geometry, grad_weights,
+                                melhi_inputs)
 from tests.melhi_restatement import melhi_scores
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(REPO, "tests", "golden")
-TINY_CASES = [n for n, c in CASES.items() if not c.get("full")]
+TINY_CASES = [n for n, c in CASES.items() if not c.get("full") and "geom" not in c]
 
 
 def tiny_cfg() -> MelhiConfig:
@@ -24,8 +26,8 @@ def tiny_cfg() -> MelhiConfig:
                        image_regions=TINY["P"])
 
 
-def case_model(name: str, full: bool = False) -> Model:
-    g = FULL if full else TINY
+def case_model(name: str) -> Model:
+    g = geometry(name)
     cfg = MelhiConfig(num_candidates=g["N"], embed_dim=g["D"], image_dim=g["R"], mention_tokens=g["L"], image_regions=g["P"])
     torch.manual_seed(CASES[name]["seed"])
     return Model(cfg)
@@ -47,28 +49,83 @@ def tiny_golden():
     return np.load(os.path.join(GOLDEN, "melhi_tiny.npz"))
 
 
-@pytest.mark.parametrize("name", TINY_CASES)
-def test_restatement_matches_reference_goldens(name, tiny_golden):
+@pytest.fixture(scope="module")
+def shapes_golden():
+    return np.load(os.path.join(GOLDEN, "melhi_shapes.npz"))
+
+
+def restated(name: str, grads: bool = True):
+    """(scores, mask, fp64 state dict) of case `name` by the restatement on the CPU; with `grads`, the state dict's .grad hold
+    the gradients of sum(scores * grad_weights) (when no score is NaN)."""
     model = case_model(name)
-    sd = {k: v.detach().double().requires_grad_(True) for k, v in model.state_dict().items()}
+    sd = {k: v.detach().double().requires_grad_(grads) for k, v in model.state_dict().items()}
     assert list(sd) == KEYS
-    np.testing.assert_allclose([sd[k].detach().sum().item() for k in KEYS], tiny_golden[f"{name}/w_sums"], rtol=1e-9, atol=1e-9)
     batch = melhi_inputs(name, {k: v.detach().float().numpy() for k, v in sd.items()})
     t1, t2 = CASES[name].get("thres", (0.3, 0.3))
     scores, mask = melhi_scores(as_torch(batch), sd, t1, t2, return_mask=True)
-    want = tiny_golden[f"{name}/scores"]
-    got = scores.detach().numpy()
+    if grads and not torch.isnan(scores).any():
+        (scores * torch.from_numpy(grad_weights(name, scores.shape)).double()).sum().backward()
+    return scores.detach(), mask, sd, batch
+
+
+@pytest.mark.parametrize("name", TINY_CASES + SHAPE_CASES)
+def test_restatement_matches_reference_goldens(name, tiny_golden, shapes_golden):
+    golden = shapes_golden if name in SHAPE_CASES else tiny_golden
+    scores, mask, sd, _ = restated(name)
+    np.testing.assert_allclose([sd[k].detach().sum().item() for k in KEYS], golden[f"{name}/w_sums"], rtol=1e-9, atol=1e-9)
+    assert np.array_equal(mask.numpy().astype(np.uint8), golden[f"{name}/mask"])
+    got = scores.numpy()
+    if name in SHAPE_CHECKSUM:   # sums, L2 norms and leading elements (the melhi_full.npz form)
+        assert not np.isnan(got).any()
+        assert abs(got.sum() - golden[f"{name}/scores_sum"]) < 2e-6 * got.size
+        assert abs(np.linalg.norm(got) - golden[f"{name}/scores_l2"]) < 2e-6 * np.sqrt(got.size)
+        assert np.abs(got.flatten()[:32] - golden[f"{name}/scores_head"]).max() < 2e-6
+        for k in KEYS:
+            g = sd[k].grad.numpy() if sd[k].grad is not None else np.zeros(sd[k].shape)
+            scale = max(np.abs(g).max(), 1e-6)
+            want_l2 = float(golden[f"{name}/grad_l2/{k}"])
+            assert abs(np.linalg.norm(g) - want_l2) <= 2e-5 * max(want_l2, 1e-12), k
+            assert np.abs(g.flatten()[:16] - golden[f"{name}/grad_head/{k}"]).max() / scale < 2e-5, k
+        return
+    want = golden[f"{name}/scores"]
     assert np.array_equal(np.isnan(got), np.isnan(want))
     ok = ~np.isnan(want)
     assert np.abs(got[ok] - want[ok]).max(initial=0.0) < 2e-6
-    assert np.array_equal(mask.numpy().astype(np.uint8), tiny_golden[f"{name}/mask"])
-    if f"{name}/grad/{KEYS[0]}" in tiny_golden:
-        (scores * torch.from_numpy(grad_weights(name, scores.shape)).double()).sum().backward()
+    if name in SHAPE_FORWARD_ONLY:
+        assert f"{name}/grad/{KEYS[0]}" not in golden
+    if f"{name}/grad/{KEYS[0]}" in golden:
         for k in KEYS:
-            ref = tiny_golden[f"{name}/grad/{k}"]
+            ref = golden[f"{name}/grad/{k}"]
             got = sd[k].grad.numpy() if sd[k].grad is not None else np.zeros_like(ref)   # W_hh unused: no recurrence
             err = np.abs(got - ref).max() / max(np.abs(ref).max(), 1e-6)
             assert err < 2e-5, (k, err)
+    else:
+        assert name in SHAPE_FORWARD_ONLY or np.isnan(want).any()
+
+
+def test_shape_cases_reach_their_corners():
+    """What each shape case is for holds on its inputs (a case that missed it would pass vacuously)."""
+    for name in SHAPE_CASES:
+        scores, _, _, batch = restated(name, grads=False)
+        rows_nan = torch.isnan(scores).any(-1)
+        if name == "max_len_nan":
+            assert 0 < rows_nan.sum().item() <= len(rows_nan) // 4, rows_nan.sum().item()
+        else:
+            assert not rows_nan.any(), name
+        L = geometry(name)["L"]
+        order, lengths = orders_and_lengths(batch[2], batch[3], torch.from_numpy(batch[1]), L)
+        start, end, mlen = batch[2].numpy(), batch[3].numpy(), batch[1].sum(-1)
+        if name == "long_lanes":
+            assert all(lengths[s].max() >= 256 for s in range(2)), lengths.max(1)
+        if name == "short_L":
+            assert lengths.max() == 1            # T0 = T1 = 0: no long recurrence on either side
+            assert (start > 1).any()             # a real length-1 left context (token 1)
+            assert (mlen > end).any()            # a real length-1 right context
+        if name == "max_len_nan":
+            assert lengths[0].max() == L - 1
+        if CASES[name]["B"] >= 64:              # ties in both orders
+            for s in range(2):
+                assert (np.diff(lengths[s][order[s]]) == 0).sum() > len(order[s]) // 2, (name, s)
 
 
 def test_golden_cases_cover_the_corners(tiny_golden):

@@ -1143,9 +1143,7 @@ int drin_backward_ex(const drin_config* cfg, const drin_batch* batch, const drin
   // gelu / silu edges: the derivative is taken at the pre-activation the forward kept (Layout::edge_z)
   const bool from_z = act_e == DRIN_ACT_GELU || act_e == DRIN_ACT_SILU;
   const int act_eb = from_z ? (act_e | 0x100) : act_e;   // device_utils.h: kActFromPre
-  float* const smp = ws + L.small_part;     // slices of the mention-sized exact-fp32 dW products
   float* const csp = ws + L.colsum_part;    // partial rows of the bias column sums
-  const bool x3 = prec == DRIN_PREC_BF16X3 || prec == DRIN_PREC_BF16X3_ALL;
   // dX (+)= dY W (launch_gemm_nn).  Scalar edges: W_h^T and W_v^T of every layer in ONE batched transpose up front (slots
   // 2 l and 2 l + 1 of L.wt), split into bf16 (hi, lo) planes in the same pass - the NT kernel streams them by LDS-DMA;
   // anything else (W_u at 512+ mentions; the half-width W_u / W_v and W_m of vector edges) that takes split-bf16 is
@@ -1167,49 +1165,8 @@ int drin_backward_ex(const drin_config* cfg, const drin_batch* batch, const drin
                           L.splitk_floats ? ws + L.splitk : nullptr, L.splitk_floats,
                           {w_t, wt_slot(nl, 0), (size_t)D * D, tnp, tnf});
   };
-  SliceSum ln_sums;        // second level of the LayerNorm backward's column sums (dgamma, dbeta, db_h of every layer)
-  ColsumBatch bias_sums;   // the bias gradients of W_u / W_v and of the vertex encoders: one launch
-  // dW (+)= dY^T X.  The pair-sized products of the whole pass (dW_h, dW_v of every layer, the two entity encoders) are
-  // collected and run as ONE launch at the end: alone, each deals its ~15-stage slices over the chip between a pipeline
-  // fill and a partial tile per workgroup; together the workgroups walk ~4x longer slices.  Mention-sized products
-  // (exact fp32) and the vector-edge ones (their operands are overwritten layer by layer) run where they arise.
-  TnGroup dw_group;
-  F32GemmGroup dw_small;   // the mention-sized ones (exact fp32): one launch as well
-  // drin_backward_staged: how many entries of the three collections belong to the GCN layers (-1: still collecting them).
-  // An instalment flushed while the vertex encoders' products are being added takes every layer entry with it: 0 remain.
-  int layer_sums = -1, layer_small = -1, layer_group = -1;
-  const bool defer_dw = x3 && !vec && tnp != nullptr;
-  // (db: the bias gradient that goes with it = the column sums of dy; the group takes them from the rows it stages)
-  auto dw_product = [&](const float* dy, int64_t lddy, const float* x, int64_t ldx, float* dw, int64_t lddw, int64_t rows,
-                        int n_out, int k_red, const int64_t* x_index = nullptr, float* db = nullptr) -> int {
-    const bool grouped = dw != nullptr && defer_dw && gemm_tn_bf16x3_fits(lddy, ldx, rows, n_out, k_red, dy, x) &&
-                         gemm_tn_bf16x3_scratch_ok(dw, lddw, n_out, k_red, tnp, tnf);
-    if (db != nullptr && !(grouped && lddy == n_out)) {
-      DRIN_TRY(bias_sums.add(dy, db, rows, n_out));
-      db = nullptr;
-    }
-    if (dw == nullptr) return DRIN_OK;
-    if (grouped) {
-      if (dw_group.n == TnGroup::MAX) {   // deeper than three layers: the group goes in instalments
-        DRIN_TRY(launch_gemm_tn_group(dw_group, st, tnp, tnf));
-        dw_group = TnGroup();
-        if (layer_group >= 0) layer_group = 0;
-      }
-      return dw_group.add(dy, lddy, x, ldx, dw, lddw, rows, n_out, k_red, x_index, db);
-    }
-    if (x_index != nullptr) return launch_gemm_tn_bf16x3(dy, lddy, x, ldx, dw, lddw, rows, n_out, k_red, st, tnp, tnf, x_index);
-    const bool takes_x3 = x3 && gemm_tn_bf16x3_fits(lddy, ldx, rows, n_out, k_red, dy, x);
-    if (!vec && !takes_x3 && rows <= 2048 && (n_out % 4) == 0 && (k_red % 4) == 0 && (prec == DRIN_PREC_F32 || x3) &&
-        aligned16(dw) && (lddw % 4) == 0) {
-      if (dw_small.n == F32GemmGroup::MAX) {
-        DRIN_TRY(launch_gemm_tn_f32_group(dw_small, st, smp, L.small_part_floats));
-        dw_small = F32GemmGroup();
-        if (layer_small >= 0) layer_small = 0;
-      }
-      return dw_small.add_tn(dy, lddy, x, ldx, dw, lddw, rows, n_out, k_red);
-    }
-    return launch_gemm_tn(dy, lddy, x, ldx, dw, lddw, rows, n_out, k_red, prec, st, tnp, tnf);
-  };
+  // dW (+)= dY^T X with its bias gradient: kernel choice, grouped launches and the order of landing are the GEMM module's
+  WeightGradPass dw{prec, vec, st, {tnp, tnf}, {ws + L.small_part, L.small_part_floats}, {csp, L.colsum_part_floats}};
 
   // score = cos(mt_L, et_L) (model.py:207-209)
   DRIN_TRY(launch_cosine_bwd(ws + L.vm[nl], ws + L.ve[nl], grad_scores, g_vm[nl], g_ve[nl], cos_scratch, B, N, D,
@@ -1235,12 +1192,12 @@ int drin_backward_ex(const drin_config* cfg, const drin_batch* batch, const drin
     // (its column sums' second level rides in the slice sum at the end of the pass: per-layer level-1 rows behind the block rows)
     DRIN_TRY(launch_layernorm_gelu_bwd2(ws + L.h_m[l], st_m, st_m + 2 * (size_t)B, gm, (int64_t)types * B, ws + L.h_e[l], st_e,
                                         st_e + 2 * M, ge, (int64_t)types * M, W.ln_weight, W.ln_bias, G.ln_weight, G.ln_bias,
-                                        G.b_h, ws + L.ln_part, D, st, act_v, nl <= 2 ? &ln_sums : nullptr,
+                                        G.b_h, ws + L.ln_part, D, st, act_v, nl <= 2 ? &dw.ln_sums : nullptr,
                                         ws + L.ln_part + ((size_t)(1024 + 16) + (size_t)16 * l) * 3 * D));
     // (b) dW_h += dH^T A
     if (G.w_h) {
-      DRIN_TRY(dw_product(gm, D, ws + L.agg_m[l], D, G.w_h, D, (int64_t)types * B, D, D));
-      DRIN_TRY(dw_product(ge, D, ws + L.agg_e[l], D, G.w_h, D, (int64_t)types * M, D, D));
+      DRIN_TRY(dw.add(gm, D, ws + L.agg_m[l], D, G.w_h, D, (int64_t)types * B, D, D));
+      DRIN_TRY(dw.add(ge, D, ws + L.agg_e[l], D, G.w_h, D, (int64_t)types * M, D, D));
     }
     // (c) dA = dH W_h
     DRIN_TRY(gemm_nn(gm, D, W.w_h, dA_m, D, (int64_t)types * B, D, D, false));
@@ -1283,9 +1240,9 @@ int drin_backward_ex(const drin_config* cfg, const drin_batch* batch, const drin
       if (B > 65535) {
         DRIN_TRY(launch_mention_reduce(dpre, fv, dpre + M, fv + MD, nullptr, dfu, B, N, D, inv_d, st));
         DRIN_TRY(launch_mention_reduce(dpre + 2 * M, fv, dpre + 3 * M, fv + MD, nullptr, dfu + BD, B, N, D, inv_d, st));
-        DRIN_TRY(dw_product(dfu, D, mt, D, G.w_u, D, 2 * (int64_t)B, D, D, nullptr, G.b_u));
+        DRIN_TRY(dw.add(dfu, D, mt, D, G.w_u, D, 2 * (int64_t)B, D, D, nullptr, G.b_u));
       }
-      DRIN_TRY(dw_product(dfv, D, et, D, G.w_v, D, 2 * (int64_t)M, D, D, nullptr, G.b_v));
+      DRIN_TRY(dw.add(dfv, D, et, D, G.w_v, D, 2 * (int64_t)M, D, D, nullptr, G.b_v));
       de_extra = dpre;
     } else if (!cfg->dynamic_edges && have_edge) {
       de_extra = g_e[cur];  // static edges pass through (model.py:136)
@@ -1311,7 +1268,7 @@ int drin_backward_ex(const drin_config* cfg, const drin_batch* batch, const drin
         const float* fv = ws + L.fv[l];
         DRIN_TRY(launch_mention_reduce2_pair(dpre, fv, fv + MD, nullptr, nullptr, dfu, dfu + BD, 1.0f / (float)D,          // (d): dfu
                                              e, dA_et, dA_ei, dA_mt, dA_mi, gm_next, gm_next + BD, 1.0f, B, N, D, st));   // (f)
-        DRIN_TRY(dw_product(dfu, D, mt, D, G.w_u, D, 2 * (int64_t)B, D, D, nullptr, G.b_u));
+        DRIN_TRY(dw.add(dfu, D, mt, D, G.w_u, D, 2 * (int64_t)B, D, D, nullptr, G.b_u));
       } else if (B <= 65535) {
         DRIN_TRY(launch_mention_reduce2(e, dA_et, dA_ei, dA_mt, dA_mi, gm_next, gm_next + BD, B, N, D, 1.0f, st));
       } else {
@@ -1324,61 +1281,22 @@ int drin_backward_ex(const drin_config* cfg, const drin_batch* batch, const drin
     have_edge = true;
     // dfv / dfu are overwritten by the next layer down: their column sums go now - except layer 0's, which share the
     // launch of the vertex encoders' bias gradients below
-    if (l > 0 && bias_sums.n > 0) {
-      DRIN_TRY(launch_colsum_batch(bias_sums, st, csp, L.colsum_part_floats));
-      bias_sums = ColsumBatch();
-    }
+    if (l > 0) DRIN_TRY(dw.flush_bias_sums());
   }
 
-  // what is collected up to here belongs to the GCN layers, what follows to the vertex encoders (drin_backward_staged)
-  layer_sums = bias_sums.n, layer_small = dw_small.n, layer_group = dw_group.n;
+  dw.layers_done();   // (drin_backward_staged: what follows belongs to the vertex encoders)
   // VertexEncoder (model.py:26-46): four Linears over the pooled inputs
   const float* g_mt = g_vm[0];
   const float* g_mi = g_vm[0] + BD;
   const float* g_et = g_ve[0];
   const float* g_ei = g_ve[0] + MD;
-  DRIN_TRY(dw_product(g_mt, D, P.span_mean, D, grads->w_mention_text, D, B, D, D, nullptr, grads->b_mention_text));
-  DRIN_TRY(dw_product(g_et, D, P.entity_text, D, grads->w_entity_text, D, (int64_t)M, D, D, eidx, grads->b_entity_text));
+  DRIN_TRY(dw.add(g_mt, D, P.span_mean, D, grads->w_mention_text, D, B, D, D, nullptr, grads->b_mention_text));
+  DRIN_TRY(dw.add(g_et, D, P.entity_text, D, grads->w_entity_text, D, (int64_t)M, D, D, eidx, grads->b_entity_text));
   if (have_image) {
-    DRIN_TRY(dw_product(g_mi, D, P.mention_image, R, grads->w_mention_image, R, B, D, R, nullptr, grads->b_mention_image));
-    DRIN_TRY(dw_product(g_ei, D, P.entity_image, R, grads->w_entity_image, R, (int64_t)M, D, R, eidx, grads->b_entity_image));
+    DRIN_TRY(dw.add(g_mi, D, P.mention_image, R, grads->w_mention_image, R, B, D, R, nullptr, grads->b_mention_image));
+    DRIN_TRY(dw.add(g_ei, D, P.entity_image, R, grads->w_entity_image, R, (int64_t)M, D, R, eidx, grads->b_entity_image));
   }
-  // The split reductions left at the end of the pass - the bias column sums, the mention-sized and the pair-sized weight
-  // gradients - each store their slices, and ONE slice-sum launch adds them all to the gradients in a fixed order (two
-  // products of one destination, dW_h's mention and entity rows, as two segments of one entry).
-  // Staged (layers_ready_event): the same launches in two parts - first everything that lands in a GCN layer's gradients,
-  // then the event, then the vertex encoders' part; the scratch regions are reused in stream order.  Each part deals the
-  // chip's workgroups over ITS products (handing both parts the whole group's slice length keeps every bit of the one-part
-  // launch, but leaves the chip half empty twice: measured 0.73 -> 0.95 ms of split-bf16 GEMM time per B = 64 step), so the
-  // pair-sized weight gradients of the staged pass differ from drin_backward's in the last bits - by the summation
-  // split only; each is reproducible.
-  const int64_t target = 0;
-  auto flush = [&](int s0, int s1, int f0, int f1, int g0, int g1, bool with_layernorm) -> int {
-    ColsumBatch cs;
-    for (int i = s0; i < s1; ++i) {
-      cs.x[cs.n] = bias_sums.x[i], cs.out[cs.n] = bias_sums.out[i], cs.rows[cs.n] = bias_sums.rows[i];
-      cs.c4[cs.n] = bias_sums.c4[i], cs.by[cs.n] = bias_sums.by[i];
-      ++cs.n;
-    }
-    F32GemmGroup fg;
-    for (int i = f0; i < f1; ++i) fg.item[fg.n] = dw_small.item[i], fg.bias_of[fg.n] = nullptr, ++fg.n;
-    TnGroup tg;
-    for (int i = g0; i < g1; ++i) tg.item[tg.n++] = dw_group.item[i];
-    SliceSum sums;
-    if (with_layernorm) sums = ln_sums;   // (layer gradients: they belong to the first part of a staged pass)
-    DRIN_TRY(launch_colsum_batch(cs, st, csp, L.colsum_part_floats, &sums));
-    DRIN_TRY(launch_gemm_tn_f32_group(fg, st, smp, L.small_part_floats, &sums));
-    DRIN_TRY(launch_gemm_tn_group(tg, st, tnp, tnf, &sums, target));
-    return launch_slice_sum(sums, st);
-  };
-  if (layers_ready_event == nullptr) {
-    DRIN_TRY(flush(0, bias_sums.n, 0, dw_small.n, 0, dw_group.n, true));
-  } else {
-    DRIN_TRY(flush(0, layer_sums, 0, layer_small, 0, layer_group, true));
-    hipError_t ev = hipEventRecord((hipEvent_t)layers_ready_event, st);
-    if (ev != hipSuccess) return hip_fail(ev, "hipEventRecord(layers_ready)");
-    DRIN_TRY(flush(layer_sums, bias_sums.n, layer_small, dw_small.n, layer_group, dw_group.n, false));
-  }
+  DRIN_TRY(dw.finish(layers_ready_event));   // everything collected lands; staged: the layers' part, the event, the encoders' part
   if (input_grads == nullptr) return DRIN_OK;
   // the batch tensors' gradients (drin_backward_ex): from the vertex encoders' output gradients and the layer-0 edge
   // gradients, which the layer loop left in g_vm[0] / g_ve[0] / g_e[nl & 1] (nothing above writes them after the loop)
@@ -1386,26 +1304,6 @@ int drin_backward_ex(const drin_config* cfg, const drin_batch* batch, const drin
 }
 
 // ---- host-side self-checks (sanitizer build / CI; no launch is made, no GPU needed) -----------------------------------
-// What the mention-sized exact-fp32 weight-gradient group of drin_backward may have to hold at once, at worst: every
-// weight-gradient product of the pass whose reduction has at most 2048 rows (dw_product above: in exact-fp32 precision all
-// of them, in split-bf16 precision the ones gemm_tn_bf16x3_fits refuses), each with small_tn_slices(rows) stored slices.
-// Layout::small_part_floats must cover it for every batch size (it did not for 1024 < B N <= 2048).
-static size_t small_group_worst_case_floats(const drin_config& c) {
-  const size_t B = c.batch, M = B * c.num_candidates, D = c.embed_dim, R = c.image_dim;
-  const int nl = c.num_layers;
-  size_t need = 0;
-  auto product = [&need](size_t rows, size_t n_out, size_t k_red) {
-    if (rows >= 1 && rows <= 2048) need += (size_t)small_tn_slices((int64_t)rows) * n_out * k_red;
-  };
-  for (int l = nl - 1; l >= 0; --l) {
-    const size_t types = l == nl - 1 ? 1 : 2;       // the top layer's image vertices are dead
-    product(types * B, D, D), product(types * M, D, D);                          // dW_h: mention rows, entity rows
-    if (c.dynamic_edges && l < nl - 1) product(2 * M, D, D), product(2 * B, D, D);   // dW_v, dW_u
-  }
-  product(B, D, D), product(M, D, D), product(B, D, R), product(M, D, R);        // the four vertex encoders
-  return need;
-}
-
 int drin_host_selftest(void) {
   // (1) the slice scratch of the mention-sized weight-gradient group covers its worst case at every batch size
   for (int precision : {(int)DRIN_PREC_F32, (int)DRIN_PREC_BF16X3})
@@ -1419,7 +1317,7 @@ int drin_host_selftest(void) {
             if (dims) c.embed_dim = 64, c.image_dim = 128;
             Layout L;
             L.build(c, true);
-            const size_t need = small_group_worst_case_floats(c);
+            const size_t need = small_group_worst_case_floats(c, L.tn_part_floats);
             if (need > L.small_part_floats) {
               set_error("selftest: B=%d N=%d layers=%d D=%d precision=%d: the mention-sized weight-gradient group may store %zu "
                         "floats of slices, Layout::small_part_floats = %zu", b, n, nl, c.embed_dim, precision, need, L.small_part_floats);

@@ -696,18 +696,23 @@ int launch_gemm_tn_f32_group(const F32GemmGroup& grp, hipStream_t st, float* scr
   return defer != nullptr ? DRIN_OK : launch_slice_sum(local, st);
 }
 
+TnKernel gemm_tn_kernel(int precision, const float* a, int64_t lda, const float* b, int64_t ldb, const float* y, int64_t ldy,
+                        int64_t M, int N, int K, const float* scratch, size_t scratch_floats) {
+  if ((precision == DRIN_PREC_BF16X3 || precision == DRIN_PREC_BF16X3_ALL) && gemm_tn_bf16x3_fits(lda, ldb, M, N, K, a, b) &&
+      gemm_tn_bf16x3_scratch_ok(y, ldy, N, K, scratch, scratch_floats))
+    return TN_BF16X3;
+  return M <= 2048 ? TN_F32_SMALL : TN_F32_LARGE;   // mention-sized reductions (a few hundred rows): 64 x 64 tiles, 4x the workgroups
+}
+
 int launch_gemm_tn(const float* a, int64_t lda, const float* b, int64_t ldb, float* y, int64_t ldy, int64_t M, int N,
                    int K, int precision, hipStream_t st, float* scratch, size_t scratch_floats) {
   // y[n, k] += sum_m a[m, n] * b[m, k]: both operands k-major over the reduction index m.
   // The reduction runs over all B*N pairs while the output is one weight matrix, so it is split over m: the slices
   // store their tiles to the scratch and are added to y in order (launch_splitk_reduce) - reproducible bit for bit.
   // Without scratch one workgroup per output tile walks the whole reduction and adds to y in place.
-  if (precision == DRIN_PREC_BF16X3 || precision == DRIN_PREC_BF16X3_ALL) {
-    // pair-sized weight gradients: split-bf16 MFMA (gemm_tn_bf16x3.hip); mention-sized ones stay exact fp32
-    if (gemm_tn_bf16x3_fits(lda, ldb, M, N, K, a, b) && gemm_tn_bf16x3_scratch_ok(y, ldy, N, K, scratch, scratch_floats))
-      return launch_gemm_tn_bf16x3(a, lda, b, ldb, y, ldy, M, N, K, st, scratch, scratch_floats);
-    precision = DRIN_PREC_F32;
-  }
+  const TnKernel kernel = gemm_tn_kernel(precision, a, lda, b, ldb, y, ldy, M, N, K, scratch, scratch_floats);
+  if (kernel == TN_BF16X3) return launch_gemm_tn_bf16x3(a, lda, b, ldb, y, ldy, M, N, K, st, scratch, scratch_floats);
+  if (precision == DRIN_PREC_BF16X3 || precision == DRIN_PREC_BF16X3_ALL) precision = DRIN_PREC_F32;
   DRIN_TRY(check_precision(precision, "gemm_tn"));
   if ((N % 4) || (K % 4)) {
     set_error("gemm_tn: N=%d and K=%d must be multiples of 4", N, K);
@@ -718,7 +723,7 @@ int launch_gemm_tn(const float* a, int64_t lda, const float* b, int64_t ldb, flo
     return DRIN_E_SHAPE;
   }
   if (M == 0) return DRIN_OK;   // an empty sum adds nothing (and no slice length is derived from it)
-  const bool small = M <= 2048;   // mention-sized reductions (a few hundred rows): 64 x 64 tiles, 4x the workgroups
+  const bool small = kernel == TN_F32_SMALL;
   int splits;
   if (small) {
     splits = small_tn_slices(M);
@@ -746,6 +751,80 @@ int launch_gemm_tn(const float* a, int64_t lda, const float* b, int64_t ldb, flo
   }
   if (splits > 1) return launch_splitk_reduce(scratch, used, (int64_t)tile_floats, nullptr, y, ldy, N, K, true, st);
   return DRIN_OK;
+}
+
+// ---- the weight and bias gradients of one backward pass (WeightGradPass, internal.h) ----------------------------------
+int WeightGradPass::add(const float* dy, int64_t lddy, const float* x, int64_t ldx, float* dw, int64_t lddw, int64_t rows,
+                        int n_out, int k_red, const int64_t* x_index, float* db) {
+  const TnKernel kernel = gemm_tn_kernel(prec, dy, lddy, x, ldx, dw, lddw, rows, n_out, k_red, tn.p, tn.floats);
+  const bool grouped = dw != nullptr && !vec && kernel == TN_BF16X3;
+  const bool db_rides = grouped && lddy == n_out;   // the group sums the columns of the rows it stages
+  if (!db_rides) DRIN_TRY(bias_sums.add(dy, db, rows, n_out));   // (no-op for db == NULL)
+  if (dw == nullptr) return DRIN_OK;
+  if (grouped) {
+    if (dw_group.n == TnGroup::MAX) {   // deeper than three layers: the group goes in instalments
+      DRIN_TRY(launch_gemm_tn_group(dw_group, st, tn.p, tn.floats));
+      dw_group = TnGroup(), layer_group = 0;
+    }
+    return dw_group.add(dy, lddy, x, ldx, dw, lddw, rows, n_out, k_red, x_index, db_rides ? db : nullptr);
+  }
+  if (x_index != nullptr) return launch_gemm_tn_bf16x3(dy, lddy, x, ldx, dw, lddw, rows, n_out, k_red, st, tn.p, tn.floats, x_index);
+  if (!vec && kernel == TN_F32_SMALL && (n_out % 4) == 0 && (k_red % 4) == 0 && aligned16(dw) && (lddw % 4) == 0) {   // (SliceSum's contract)
+    if (dw_small.n == F32GemmGroup::MAX) {
+      DRIN_TRY(launch_gemm_tn_f32_group(dw_small, st, small.p, small.floats));
+      dw_small = F32GemmGroup(), layer_small = 0;
+    }
+    return dw_small.add_tn(dy, lddy, x, ldx, dw, lddw, rows, n_out, k_red);
+  }
+  return launch_gemm_tn(dy, lddy, x, ldx, dw, lddw, rows, n_out, k_red, prec, st, tn.p, tn.floats);
+}
+
+// The split reductions left at the end of the pass - the bias column sums, the mention-sized and the pair-sized weight gradients -
+// each store their slices, and ONE slice-sum launch adds them all to the gradients in a fixed order (two products of one destination,
+// dW_h's mention and entity rows, as two segments of one entry).  Staged (layers_ready_event): the same launches in two parts -
+// first everything that lands in a GCN layer's gradients (the LayerNorm sums with it), then the event, then the vertex encoders'
+// part; the scratch regions are reused in stream order.  Each part deals the chip's workgroups over ITS products (handing both
+// parts the whole group's slice length keeps every bit of the one-part launch, but leaves the chip half empty twice: measured
+// 0.73 -> 0.95 ms of split-bf16 GEMM time per B = 64 step), so the pair-sized weight gradients of the staged pass differ from the
+// plain one's in the last bits - by the summation split only; each is reproducible.
+int WeightGradPass::finish(void* layers_ready_event) {
+  auto part = [this](const ColsumBatch& cs, const F32GemmGroup& fg, const TnGroup& tg, SliceSum sums) -> int {
+    DRIN_TRY(launch_colsum_batch(cs, st, colsum.p, colsum.floats, &sums));
+    DRIN_TRY(launch_gemm_tn_f32_group(fg, st, small.p, small.floats, &sums));
+    DRIN_TRY(launch_gemm_tn_group(tg, st, tn.p, tn.floats, &sums));
+    return launch_slice_sum(sums, st);
+  };
+  if (layers_ready_event == nullptr) return part(bias_sums, dw_small, dw_group, ln_sums);
+  ColsumBatch cs[2];
+  F32GemmGroup fg[2];
+  TnGroup tg[2];
+  for (int i = 0; i < bias_sums.n; ++i)
+    DRIN_TRY(cs[i >= layer_sums].add(bias_sums.x[i], bias_sums.out[i], bias_sums.rows[i], 4 * bias_sums.c4[i]));
+  for (int i = 0; i < dw_small.n; ++i) fg[i >= layer_small].item[fg[i >= layer_small].n++] = dw_small.item[i];
+  for (int i = 0; i < dw_group.n; ++i) tg[i >= layer_group].item[tg[i >= layer_group].n++] = dw_group.item[i];
+  DRIN_TRY(part(cs[0], fg[0], tg[0], ln_sums));
+  if (hipError_t ev = hipEventRecord((hipEvent_t)layers_ready_event, st); ev != hipSuccess) return hip_fail(ev, "hipEventRecord(layers_ready)");
+  return part(cs[1], fg[1], tg[1], SliceSum());
+}
+
+// Every product of the pass that takes the mention-sized exact-fp32 kernel, each with small_tn_slices(rows) stored slices:
+// Layout::small_part_floats must cover it for every batch size (it once did not for 1024 < B N <= 2048).
+size_t small_group_worst_case_floats(const drin_config& c, size_t tn_part_floats) {
+  const size_t B = c.batch, M = B * c.num_candidates, D = c.embed_dim, R = c.image_dim;
+  alignas(16) static float at[4];   // the operands' and the scratch's place: the workspace is 16-byte aligned, rows contiguous
+  size_t need = 0;
+  auto product = [&](size_t rows, size_t n_out, size_t k_red) {
+    if (rows >= 1 && gemm_tn_kernel(c.precision, at, (int64_t)n_out, at, (int64_t)k_red, at, (int64_t)k_red, (int64_t)rows, (int)n_out,
+                                    (int)k_red, at, tn_part_floats) == TN_F32_SMALL)
+      need += (size_t)small_tn_slices((int64_t)rows) * n_out * k_red;
+  };
+  for (int l = c.num_layers - 1; l >= 0; --l) {
+    const size_t types = l == c.num_layers - 1 ? 1 : 2;       // the top layer's image vertices are dead
+    product(types * B, D, D), product(types * M, D, D);                          // dW_h: mention rows, entity rows
+    if (c.dynamic_edges && l < c.num_layers - 1) product(2 * M, D, D), product(2 * B, D, D);   // dW_v, dW_u
+  }
+  product(B, D, D), product(M, D, D), product(B, D, R), product(M, D, R);        // the four vertex encoders
+  return need;
 }
 
 }  // namespace drin

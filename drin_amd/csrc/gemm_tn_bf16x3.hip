@@ -309,7 +309,7 @@ static int64_t tn_slices_of(const TnGroup::Item& it, int64_t target, int64_t* ro
 // grown until the group fits - the chip and the scratch.  (Five products of one B = 64 backward pass: slices of ~62 stages
 // instead of 15, same box 0.835 -> 0.74 ms of split-bf16 GEMM time per step; at B = 512, 58 .. 160 stages per slice
 // already, neither better nor worse.)
-int64_t tn_group_target(const TnGroup& grp, size_t scratch_floats) {
+static int64_t tn_group_target(const TnGroup& grp, size_t scratch_floats) {
   int64_t work = 0, longest = 0;
   for (int i = 0; i < grp.n; ++i) {
     const auto& it = grp.item[i];
@@ -332,17 +332,13 @@ int64_t tn_group_target(const TnGroup& grp, size_t scratch_floats) {
   return target;
 }
 
-int launch_gemm_tn_group(const TnGroup& grp, hipStream_t st, float* scratch, size_t scratch_floats, SliceSum* defer,
-                         int64_t target_rows) {
+int launch_gemm_tn_group(const TnGroup& grp, hipStream_t st, float* scratch, size_t scratch_floats, SliceSum* defer) {
   if (grp.n == 0) return DRIN_OK;
   if (scratch == nullptr || !aligned16(scratch)) {
     set_error("gemm_tn_bf16x3: the slice scratch is NULL or not 16-byte aligned");
     return DRIN_E_WORKSPACE;
   }
-  const int64_t target = target_rows > 0 ? target_rows : tn_group_target(grp, scratch_floats);
-  int tiles[TnGroup::MAX];
-  for (int i = 0; i < grp.n; ++i) tiles[i] = (int)(cdiv(grp.item[i].N, x3tn::TILE) * cdiv(grp.item[i].K, x3tn::TILE));
-  auto slices_of = [&](int i, int64_t tgt, int64_t* rows_out) { return tn_slices_of(grp.item[i], tgt, rows_out); };
+  const int64_t target = tn_group_target(grp, scratch_floats);
   // products of one destination next to one another (their slices: segments of one slice-sum entry, added in this order)
   SliceSum local;
   SliceSum& sums = defer != nullptr ? *defer : local;
@@ -353,14 +349,14 @@ int launch_gemm_tn_group(const TnGroup& grp, hipStream_t st, float* scratch, siz
   for (int i = 0; i < grp.n; ++i) {
     const auto& it = grp.item[i];
     int64_t rows = 0;
-    const int64_t slices = slices_of(i, target, &rows);
+    const int64_t slices = tn_slices_of(it, target, &rows);
     auto& P = ga.p[i];
     P.a = it.a, P.b = it.b, P.b_index = it.b_index;
     P.lda = it.lda, P.ldb = it.ldb, P.M = it.M, P.rows_per_slice = rows;
-    P.N = it.N, P.K = it.K, P.k_tiles = (int)cdiv(it.K, x3tn::TILE), P.tiles = tiles[i];
+    P.N = it.N, P.K = it.K, P.k_tiles = (int)cdiv(it.K, x3tn::TILE), P.tiles = (int)cdiv(it.N, x3tn::TILE) * P.k_tiles;
     P.first = (unsigned)items, P.slices = (int)slices;
     P.partial = scratch + part;
-    items += slices * tiles[i];
+    items += slices * P.tiles;
     part += (size_t)slices * it.N * it.K;
     P.colsum_partial = nullptr;
     if (it.colsum != nullptr) {

@@ -193,12 +193,7 @@ struct TnGroup {
 };
 // (defer: the slice sums are appended to it instead of being launched - the caller launches it, after which the scratch
 //  may be reused; NULL: launched here)
-// (target_rows: the slice length to deal the products by, 0 = tn_group_target of this group - a caller that launches one
-//  group in two parts passes the whole group's target to both, so that every product keeps the slices, hence the bits, of
-//  the single launch)
-int launch_gemm_tn_group(const TnGroup& g, hipStream_t st, float* scratch, size_t scratch_floats, SliceSum* defer = nullptr,
-                         int64_t target_rows = 0);
-int64_t tn_group_target(const TnGroup& g, size_t scratch_floats);
+int launch_gemm_tn_group(const TnGroup& g, hipStream_t st, float* scratch, size_t scratch_floats, SliceSum* defer = nullptr);
 // same, operands pre-split into bf16 hi / lo planes (gemm_x3_planes.hip); K % 32 == 0
 // (a_lo NULL: A exact in bf16, two MFMAs per tile pair)
 int launch_gemm_x3_planes(const void* a_hi, const void* a_lo, int64_t lda, const void* b_hi, const void* b_lo,
@@ -292,6 +287,11 @@ int launch_gemm_nt_pair(const NtProduct& a, const NtProduct& b, int precision, h
 // y[n, k] += sum_m a[m, n] * b[m, k]          (used by backward: dW = dY^T * X), split over m
 int launch_gemm_tn(const float* a, int64_t lda, const float* b, int64_t ldb, float* y, int64_t ldy, int64_t M, int N,
                    int K, int precision, hipStream_t st, float* scratch = nullptr, size_t scratch_floats = 0);
+// the kernel such a product takes, decided here only: split-bf16 MFMA (gemm_tn_bf16x3_fits, gemm_tn_bf16x3_scratch_ok) |
+// exact fp32, mention-sized (M <= 2048): 64 x 64 tiles, small_tn_slices(M) slices | exact fp32, 128 x 128 tiles
+enum TnKernel { TN_BF16X3, TN_F32_SMALL, TN_F32_LARGE };
+TnKernel gemm_tn_kernel(int precision, const float* a, int64_t lda, const float* b, int64_t ldb, const float* y, int64_t ldy,
+                        int64_t M, int N, int K, const float* scratch, size_t scratch_floats);
 
 // ---- GCN elementwise / reduction kernels (gcn_kernels.hip) --------------------------------------
 // model.py:143-144 + :128 input: out[b,:] = mean_n(e1[b,n] v1[b,n,:]) + mean_n(e2[b,n] v2[b,n,:]) + u[b,:]
@@ -405,5 +405,32 @@ int launch_entity_side_bwd_vec(const float* dA_mt, const float* dA_mi, const flo
                                const float* mt, const float* mi, const float* et, const float* ei, const float* e,
                                const float* de_extra, float* d_et, float* d_ei, float* de, int B, int N, int D,
                                const float* mask, hipStream_t st);
+
+// ---- the weight and bias gradients of one backward pass (gemm_f32.hip) -----------------------------------------------
+// dW (+)= dY^T X, db (+)= column sums of dY.  The pair-sized products of the whole pass (dW_h, dW_v of every layer, the two entity
+// encoders) run as ONE launch at the end: alone, each deals its ~15-stage slices over the chip between a pipeline fill and a partial
+// tile per workgroup; together the workgroups walk ~4x longer slices.  The mention-sized ones (exact fp32) and the bias column sums:
+// one launch each as well; a full group (deeper than three layers) goes in instalments.  Vector edges: products run where they arise.
+struct WeightGradPass {
+  struct Scratch { float* p; size_t floats; };
+  const int prec;       // DRIN_PREC_F32 or a split-bf16 one
+  const bool vec;       // vector edges
+  const hipStream_t st;
+  const Scratch tn, small, colsum;   // Layout::tn_part (it holds a slice of every product), small_part, colsum_part
+  // no-op for dw == NULL (x_index: as TnGroup's b_index).  db: the bias gradient that goes with the product = the column
+  // sums of dy; the split-bf16 group takes them from the rows it stages, any other product's join the batch of column sums
+  int add(const float* dy, int64_t lddy, const float* x, int64_t ldx, float* dw, int64_t lddw, int64_t rows, int n_out,
+          int k_red, const int64_t* x_index = nullptr, float* db = nullptr);
+  SliceSum ln_sums;        // launch_layernorm_gelu_bwd2's deferred second level: lands with (the first part of) finish
+  int flush_bias_sums() { const int rc = launch_colsum_batch(bias_sums, st, colsum.p, colsum.floats); bias_sums = ColsumBatch(); return rc; }
+  // what was added up to here lands in the GCN layers' gradients, what follows in the vertex encoders'
+  void layers_done() { layer_sums = bias_sums.n, layer_small = dw_small.n, layer_group = dw_group.n; }
+  int finish(void* layers_ready_event);   // NULL: everything lands in one part; else the layers' part, the hipEvent_t, the encoders'
+  ColsumBatch bias_sums;
+  F32GemmGroup dw_small;
+  TnGroup dw_group;
+  int layer_sums = 0, layer_small = 0, layer_group = 0;   // entries of each that belong to the GCN layers (an instalment takes them all: 0 remain)
+};
+size_t small_group_worst_case_floats(const drin_config& c, size_t tn_part_floats);   // of dw_small at once (drin_host_selftest)
 
 }  // namespace drin

@@ -225,11 +225,9 @@ class EntityTable:
                 raise _lib.DrinError(_lib.E_UNSUPPORTED, lib.drin_last_error().decode())
             self._cache = None                                        # release the stale one before allocating
             cache = torch.empty(n, dtype=torch.uint8, device=call.device)
-            ws = torch.empty(max(lib.drin_entity_cache_build_workspace_bytes(C.byref(call.cfg)), 16), dtype=torch.uint8,
-                             device=call.device)
-            stream = torch.cuda.current_stream(call.device).cuda_stream
+            ws = call.byte_buffer(lib.drin_entity_cache_build_workspace_bytes(C.byref(call.cfg)))
             _lib.check(lib.drin_build_entity_cache(C.byref(call.cfg), C.byref(call.batch), C.byref(pc), prepared.data_ptr(),
-                                                   cache.data_ptr(), n, ws.data_ptr(), ws.numel(), stream))
+                                                   cache.data_ptr(), n, ws.data_ptr(), ws.numel(), call.stream()))
             self._cache, self._cache_key = cache, key
         return self._cache
 
@@ -432,12 +430,35 @@ class _Call:
                             "entity_index", "entity_text_cls", "index_status"), self.keep):
             setattr(b, name, _ptr(t))
         self.batch = b
+        # what `Model._score` / `Model._forward` add for the autograd edge (a bare call scores and trains without them)
+        self.owner: Optional["Model"] = None                  # whose gradient bucket and layers-ready hook backward uses
+        self.input_roles: Sequence[str] = ()                  # batch tensors that follow the parameters into `_DrinScore.apply`
+        self.params_ready: Optional[torch.cuda.Event] = None  # train.OverlappedStep: an update still running on a side stream
+        self.token_block: Optional[torch.Tensor] = None       # a bf16 [B, N, T, D] block pooled in place, and its int64 mask
+        self.token_mask: Optional[torch.Tensor] = None
+
+    def stream(self) -> int:
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def scores(self) -> torch.Tensor:
+        """Uninitialised `[B, N]` fp32 for the library to fill; of an empty batch, already the result."""
+        return torch.empty(self.B, self.N, dtype=torch.float32, device=self.device)
+
+    def byte_buffer(self, n: int) -> torch.Tensor:
+        return torch.empty(max(n, 16), dtype=torch.uint8, device=self.device)
 
     def workspace(self, training: bool) -> torch.Tensor:
         n = _lib.load().drin_workspace_bytes(C.byref(self.cfg), 1 if training else 0)
         if n == 0 and self.B > 0:
             raise _lib.DrinError(_lib.E_SHAPE, _lib.load().drin_last_error().decode())
-        return torch.empty(max(n, 16), dtype=torch.uint8, device=self.device)
+        return self.byte_buffer(n)
+
+    def param_struct(self, params: Sequence[torch.Tensor]):
+        """`(tensors, drin_params)`: the parameters detached and contiguous, and the struct that points at them."""
+        tensors = tuple(p.detach().contiguous() for p in params)
+        pc = _lib.DrinParamsC()
+        _fill_params(pc, tensors, self.per_layer)
+        return tensors, pc
 
 
 class _Prepared:
@@ -457,8 +478,7 @@ class _Prepared:
             lib = _lib.load()
             n = lib.drin_prepared_bytes(C.byref(call.cfg))
             self.buf = torch.empty(n, dtype=torch.uint8, device=call.device)
-            stream = torch.cuda.current_stream(call.device).cuda_stream
-            _lib.check(lib.drin_prepare(C.byref(call.cfg), C.byref(pc), self.buf.data_ptr(), n, stream))
+            _lib.check(lib.drin_prepare(C.byref(call.cfg), C.byref(pc), self.buf.data_ptr(), n, call.stream()))
             self.key = key
             self.generation += 1
         return self.buf
@@ -519,42 +539,53 @@ def _batch_requires_grad(batch) -> bool:
     return any(torch.is_tensor(x) and x.is_floating_point() and x.requires_grad for x in ts)
 
 
+def _param_grads(call: _Call, params: Sequence[torch.Tensor]):
+    """`(drin_param_grads, gradients to return)`: zeroed destinations for every parameter - views of the owner's flat bucket,
+    or fresh tensors - with the positions the score does not depend on returned as None."""
+    owner = call.owner
+    if owner is not None and owner.grad_bucket_enabled:
+        # every gradient is a view of ONE flat fp32 bucket, zeroed with one memset: autograd's AccumulateGrad adopts the
+        # views as .grad, so the data-parallel all-reduce and the one-launch Adam run on the bucket itself, copy-free
+        grads = owner._bucket_grads(params)
+    else:
+        grads = [torch.empty_like(p) for p in params]
+        torch._foreach_zero_(grads)                               # one multi-tensor launch instead of 24 fills
+    gc = _lib.DrinParamGradsC()
+    _fill_params(gc, grads, call.per_layer)
+    out = list(grads)
+    # parameters the score does not depend on get no gradient at all in the reference (.grad is None):
+    # the last layer's edge update is dead (model.py:130-134), and static edges never use w_u / w_v (/ w_m)
+    for i in _dead_param_indices(len(params), call.per_layer, bool(call.cfg.dynamic_edges)):
+        out[i] = None
+    return gc, out
+
+
 class _DrinScore(torch.autograd.Function):
-    """Autograd edge around drin_forward / drin_backward (loss.backward() of train.py:33-34).  `call.input_roles` (default
-    empty) names the batch tensors that follow the parameters in `tensors` (drin_input_grads fields; "token_block": a bf16
+    """Autograd edge around drin_forward_staged / drin_backward_ex (loss.backward() of train.py:33-34).  `call.input_roles`
+    names the batch tensors that follow the parameters in `tensors` (drin_input_grads fields; "token_block": a bf16
     [B, N, T, D] block that was pooled in place, whose gradient drin_pool_bwd writes in bf16)."""
 
     @staticmethod
     def forward(ctx, call: _Call, prepared: Optional[_Prepared], training: bool, *tensors: torch.Tensor):
         lib = _lib.load()
-        roles = getattr(call, "input_roles", ())
-        params = tensors[:len(tensors) - len(roles)]
-        ctx.roles = roles
-        versions = params
-        params = tuple(p.detach().contiguous() for p in params)
-        pc = _lib.DrinParamsC()
-        _fill_params(pc, params, call.per_layer)
+        ctx.roles = call.input_roles
+        versions = tensors[:len(tensors) - len(ctx.roles)]
+        params, pc = call.param_struct(versions)
         if not training and prepared is not None and lib.drin_fused_supported(C.byref(call.cfg)) == _lib.OK:
             # inference: fused two-layer path on weights folded once per weight version
             pbuf = prepared.get(call, versions, pc)
-            n = lib.drin_fused_workspace_bytes(C.byref(call.cfg))
-            ws = torch.empty(max(n, 16), dtype=torch.uint8, device=call.device)
-            scores = torch.empty(call.B, call.N, dtype=torch.float32, device=call.device)
-            stream = torch.cuda.current_stream(call.device).cuda_stream
+            ws = call.byte_buffer(lib.drin_fused_workspace_bytes(C.byref(call.cfg)))
+            scores = call.scores()
             _lib.check(lib.drin_forward_prepared(C.byref(call.cfg), C.byref(call.batch), C.byref(pc), pbuf.data_ptr(),
-                                                 ws.data_ptr(), ws.numel(), scores.data_ptr(), stream))
+                                                 ws.data_ptr(), ws.numel(), scores.data_ptr(), call.stream()))
             return scores
-        ws = call.workspace(training)
-        scores = torch.empty(call.B, call.N, dtype=torch.float32, device=call.device)
-        stream = torch.cuda.current_stream(call.device).cuda_stream
-        ready = getattr(call, "params_ready", None)       # train.OverlappedStep: the previous update is still running on a side stream
-        if ready is not None:
-            # the pooling passes and static edges of THIS step run under it; the stream waits before the first weight is read
-            _lib.check(lib.drin_forward_staged(C.byref(call.cfg), C.byref(call.batch), C.byref(pc), ws.data_ptr(), ws.numel(),
-                                               scores.data_ptr(), 1 if training else 0, None, ready.cuda_event, stream))
-        else:
-            _lib.check(lib.drin_forward(C.byref(call.cfg), C.byref(call.batch), C.byref(pc), ws.data_ptr(), ws.numel(),
-                                        scores.data_ptr(), 1 if training else 0, None, stream))
+        ws, scores = call.workspace(training), call.scores()
+        # train.OverlappedStep: the previous update is still running on a side stream.  The pooling passes and static edges
+        # of THIS step run under it; the stream waits for the event before the first weight is read
+        ready = call.params_ready
+        _lib.check(lib.drin_forward_staged(C.byref(call.cfg), C.byref(call.batch), C.byref(pc), ws.data_ptr(), ws.numel(),
+                                           scores.data_ptr(), 1 if training else 0, None,
+                                           None if ready is None else ready.cuda_event, call.stream()))
         ctx.call, ctx.ws, ctx.pc, ctx.params = call, ws, pc, params
         return scores
 
@@ -562,107 +593,50 @@ class _DrinScore(torch.autograd.Function):
     def backward(ctx, grad_scores: torch.Tensor):
         lib = _lib.load()
         call, params, roles = ctx.call, ctx.params, ctx.roles
-        need_params = any(ctx.needs_input_grad[3:3 + len(params)])
-        need_feats = [r for r, n in zip(roles, ctx.needs_input_grad[3 + len(params):]) if n]
-        if need_feats:
-            return _DrinScore._backward_inputs(ctx, grad_scores, need_params, need_feats)
-        owner = getattr(call, "owner", None)
-        if owner is not None and owner.grad_bucket_enabled:
-            # every gradient is a view of ONE flat fp32 bucket, zeroed with one memset: autograd's AccumulateGrad adopts the
-            # views as .grad, so the data-parallel all-reduce and the one-launch Adam run on the bucket itself, copy-free
-            grads = owner._bucket_grads(params)
-        else:
-            grads = [torch.empty_like(p) for p in params]
-            torch._foreach_zero_(grads)                               # one multi-tensor launch instead of 24 fills
-        gc = _lib.DrinParamGradsC()
-        _fill_params(gc, grads, call.per_layer)
-        g = grad_scores.to(torch.float32).contiguous()
-        stream = torch.cuda.current_stream(call.device).cuda_stream
-        # data-parallel overlap (drin_backward_staged): the library records `ready` once the GCN layers' gradients are
-        # complete; the hook - GradBucket's - starts their all-reduce behind it, under the vertex encoders' dW products
-        hook = getattr(owner, "_layers_ready_hook", None) if owner is not None and owner.grad_bucket_enabled else None
-        staged = hook is not None and owner._grad_flat is not None and grads[0].data_ptr() == owner._grad_flat.data_ptr()
-        if staged:
-            ready = torch.cuda.Event()
-            ready.record(torch.cuda.current_stream(call.device))        # creates the hipEvent_t; the library records it again
-            _lib.check(lib.drin_backward_staged(C.byref(call.cfg), C.byref(call.batch), C.byref(ctx.pc), ctx.ws.data_ptr(),
-                                                ctx.ws.numel(), g.data_ptr(), C.byref(gc), ready.cuda_event, stream))
-            offsets, live, _total = owner.bucket_layout()
-            hook(owner._grad_flat[:live], offsets[8], ready)             # [vertex encoders | GCN layers | dead]: the layers start at slot 8
-        else:
-            _lib.check(lib.drin_backward(C.byref(call.cfg), C.byref(call.batch), C.byref(ctx.pc), ctx.ws.data_ptr(),
-                                         ctx.ws.numel(), g.data_ptr(), C.byref(gc), stream))
-        out = list(grads)
-        # parameters the score does not depend on get no gradient at all in the reference (.grad is None):
-        # the last layer's edge update is dead (model.py:130-134), and static edges never use w_u / w_v (/ w_m)
-        for i in _dead_param_indices(len(params), call.per_layer, bool(call.cfg.dynamic_edges)):
-            out[i] = None
-        return (None, None, None, *out, *([None] * len(roles)))
-
-    @staticmethod
-    def _backward_inputs(ctx, grad_scores: torch.Tensor, need_params: bool, need_feats):
-        """drin_backward_ex: the parameter gradients (when any parameter wants one: the same launches and bits as
-        drin_backward) and the gradients of the batch tensors in `need_feats`."""
-        lib = _lib.load()
-        call, params, roles = ctx.call, ctx.params, ctx.roles
-        dev = call.device
-        owner = getattr(call, "owner", None)
+        dev, owner = call.device, call.owner
+        needs = ctx.needs_input_grad[3 + len(params):]
+        need_feats = [r for r, n in zip(roles, needs) if n]
         gc, out = None, [None] * len(params)
-        if need_params:
-            if owner is not None and owner.grad_bucket_enabled:
-                grads = owner._bucket_grads(params)
-            else:
-                grads = [torch.empty_like(p) for p in params]
-                torch._foreach_zero_(grads)
-            gc = _lib.DrinParamGradsC()
-            _fill_params(gc, grads, call.per_layer)
-            out = list(grads)
-            for i in _dead_param_indices(len(params), call.per_layer, bool(call.cfg.dynamic_edges)):
-                out[i] = None
-        ig = _lib.DrinInputGradsC()
-        feat_out = {}
-        for role in need_feats:
-            if role == "token_block":
-                continue
-            ref = call.keep[_INPUT_FIELDS[role]]
-            feat_out[role] = torch.empty(ref.shape, dtype=torch.float32, device=dev)
-        if "token_block" in need_feats:   # pooled and token-0 gradients first, then the block in bf16 (drin_pool_bwd)
-            feat_out.setdefault("entity_text", torch.empty(call.keep[6].shape, dtype=torch.float32, device=dev))
-            feat_out.setdefault("entity_text_cls", torch.empty(call.keep[14].shape, dtype=torch.float32, device=dev))
-        for role, t in feat_out.items():
-            setattr(ig, role, t.data_ptr())
-        n = lib.drin_input_grad_scratch_bytes(C.byref(call.cfg))
-        scratch = torch.empty(max(n, 16), dtype=torch.uint8, device=dev)
-        ig.scratch, ig.scratch_bytes = scratch.data_ptr(), scratch.numel()
+        if any(ctx.needs_input_grad[3:3 + len(params)]):
+            gc, out = _param_grads(call, params)
+        ig, feat_out = None, {}
+        if need_feats:
+            ig = _lib.DrinInputGradsC()
+            for role in need_feats:
+                if role != "token_block":
+                    feat_out[role] = torch.empty(call.keep[_INPUT_FIELDS[role]].shape, dtype=torch.float32, device=dev)
+            if "token_block" in need_feats:   # pooled and token-0 gradients first, then the block in bf16 (drin_pool_bwd)
+                for role in ("entity_text", "entity_text_cls"):
+                    feat_out.setdefault(role, torch.empty(call.keep[_INPUT_FIELDS[role]].shape, dtype=torch.float32, device=dev))
+            for role, t in feat_out.items():
+                setattr(ig, role, t.data_ptr())
+            scratch = call.byte_buffer(lib.drin_input_grad_scratch_bytes(C.byref(call.cfg)))
+            ig.scratch, ig.scratch_bytes = scratch.data_ptr(), scratch.numel()
         g = grad_scores.to(torch.float32).contiguous()
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        # data-parallel overlap exactly as in backward() (drin_backward_staged's event and the bucket's hook)
-        hook = getattr(owner, "_layers_ready_hook", None) if need_params and owner is not None and owner.grad_bucket_enabled else None
+        stream = call.stream()
+        # data-parallel overlap: the library records `ready` once the GCN layers' gradients are complete; the hook -
+        # GradBucket's - starts their all-reduce behind it, under the vertex encoders' dW products
+        hook = owner._layers_ready_hook if gc is not None and owner is not None and owner.grad_bucket_enabled else None
         staged = hook is not None and owner._grad_flat is not None and out[0].data_ptr() == owner._grad_flat.data_ptr()
         ready = None
         if staged:
             ready = torch.cuda.Event()
-            ready.record(torch.cuda.current_stream(dev))
+            ready.record(torch.cuda.current_stream(dev))              # creates the hipEvent_t; the library records it again
         _lib.check(lib.drin_backward_ex(C.byref(call.cfg), C.byref(call.batch), C.byref(ctx.pc), ctx.ws.data_ptr(), ctx.ws.numel(),
-                                        g.data_ptr(), C.byref(gc) if gc is not None else None, C.byref(ig),
+                                        g.data_ptr(), None if gc is None else C.byref(gc), None if ig is None else C.byref(ig),
                                         ready.cuda_event if staged else None, stream))
         if staged:
             offsets, live, _total = owner.bucket_layout()
-            hook(owner._grad_flat[:live], offsets[8], ready)
-        feats = []
-        for role, needed in zip(roles, ctx.needs_input_grad[3 + len(params):]):
-            if not needed:
-                feats.append(None)
-            elif role == "token_block":
-                block = call.token_block
-                gb = torch.empty(block.shape, dtype=torch.bfloat16, device=dev)
-                c = _lib.DrinConfigC.from_buffer_copy(call.cfg)
-                c.entity_tokens, c.feature_dtype = block.shape[2], _lib.FEAT_BF16
-                _lib.check(lib.drin_pool_bwd(C.byref(c), call.token_mask.data_ptr(), feat_out["entity_text"].data_ptr(),
-                                             feat_out["entity_text_cls"].data_ptr(), gb.data_ptr(), stream))
-                feats.append(gb)
-            else:
-                feats.append(feat_out[role])
+            hook(owner._grad_flat[:live], offsets[8], ready)          # [vertex encoders | GCN layers | dead]: the layers start at slot 8
+        feats = [feat_out.get(role) if n else None for role, n in zip(roles, needs)]
+        if "token_block" in need_feats:
+            block = call.token_block
+            gb = torch.empty(block.shape, dtype=torch.bfloat16, device=dev)
+            c = _lib.DrinConfigC.from_buffer_copy(call.cfg)
+            c.entity_tokens, c.feature_dtype = block.shape[2], _lib.FEAT_BF16
+            _lib.check(lib.drin_pool_bwd(C.byref(c), call.token_mask.data_ptr(), feat_out["entity_text"].data_ptr(),
+                                         feat_out["entity_text_cls"].data_ptr(), gb.data_ptr(), stream))
+            feats[roles.index("token_block")] = gb
         return (None, None, None, *out, *feats)
 
 
@@ -878,65 +852,61 @@ class Model(nn.Module):
             return torch.cat([self._forward(part) for part in _split_mentions(batch, self.MAX_CALL_MENTIONS)], 0)
         return self._forward(batch)
 
+    def _unfused_precision(self) -> int:
+        """"bf16x3_if16" is a mode of the fused inference path; anything else it meets runs split-bf16."""
+        return _lib.PREC_BF16X3 if self.precision in _FUSED_ONLY else self.precision
+
+    def _forward_table(self, batch: "IndexedBatch", params):
+        """Table form: the scores, where the kernels read the tables through the candidate index (fused or
+        cached inference, training on pooled tables); everything else (exact-fp32 precision, geometries off those paths,
+        batch tensors that require grad - so that torch's indexing backward accumulates into the table rows) gathers with
+        torch indexing and returns `(14-sequence, token-0 rows or None)` for the common tail of `_forward`."""
+        feat_grad = torch.is_grad_enabled() and _batch_requires_grad(batch)
+        inference = not (torch.is_grad_enabled() and any(p.requires_grad for p in params)) and not feat_grad
+        planes = self.precision in _PLANES
+        t = batch.table
+        call = out = None
+        if inference and self._prepared is not None and self.cfg.num_gcn_layers == 2 and (planes or t.cache_enabled):
+            seq = batch.mention + [t.text, t.mask, t.image, t.object, t.object_score,
+                                   batch.miet_similarity, batch.mtei_similarity]
+            if t.cache_enabled and t.text.dtype == torch.bfloat16:
+                raise ValueError("the per-entity cache is built from fp32 tables; give EntityTable fp32 features")
+            # bf16-stored features are read in place by the fused path (never widened: the table is large)
+            call = _Call(self.cfg, seq, self._unfused_precision() if t.cache_enabled else self.precision,
+                         entity_index=batch.candidates, keep_bf16=planes and not t.cache_enabled,
+                         index_status=self._status_words(batch.candidates.device))
+            if _lib.load().drin_fused_supported(C.byref(call.cfg)) == _lib.OK:
+                if t.cache_enabled:                                    # per-entity precompute cache (SURVEY.md 8f-2)
+                    out = self._forward_cached(call, t, params)
+                else:                                                  # an empty batch too: the library validates its geometry
+                    out = self._score(call, self._prepared, False, *params)
+        # training on a token-level table: every entity's tokens pooled once; the step then reads the pooled / token-0 /
+        # image / object tables through the candidate index inside the kernels, or gathers those rows
+        pooled = not inference and not feat_grad and t.text.dim() == 3
+        if pooled:
+            call = self._indexed_training_call(batch, planes)
+            if call is not None:
+                out = self._score(call, None, True, *params)
+        if out is not None:
+            self._watch_indices(call.device)                           # the kernels clamp and report: after their launches
+            return out
+        batch = self._clamped(batch)
+        seq, cls = batch.gathered_pooled(self.cfg) if pooled else (batch.gathered(), None)
+        self._watch_indices(seq[0].device)                             # before scoring: with validate_indices, the raise
+        return seq, cls
+
     def _forward(self, batch) -> torch.Tensor:
         params = _param_list(self)
-        cls = None
+        cls = block = None
         if isinstance(batch, IndexedBatch):
-            # table form: inference gathers inside the stream kernel; everything else (training,
-            # exact-fp32 precision, geometries off the fused path) gathers with torch indexing first
-            # batch tensors that require grad (a table being trained, attribution): the gathered torch path, so that torch's
-            # indexing backward accumulates into the table rows
-            feat_grad = torch.is_grad_enabled() and _batch_requires_grad(batch)
-            inference = not (torch.is_grad_enabled() and any(p.requires_grad for p in params)) and not feat_grad
-            planes = self.precision in _PLANES
-            t = batch.table
-            if inference and self._prepared is not None and self.cfg.num_gcn_layers == 2 and (planes or t.cache_enabled):
-                seq = batch.mention + [t.text, t.mask, t.image, t.object, t.object_score,
-                                       batch.miet_similarity, batch.mtei_similarity]
-                if t.cache_enabled and t.text.dtype == torch.bfloat16:
-                    raise ValueError("the per-entity cache is built from fp32 tables; give EntityTable fp32 features")
-                # bf16-stored features are read in place by the fused path (never widened: the table is large)
-                prec = _lib.PREC_BF16X3 if (t.cache_enabled and self.precision in _FUSED_ONLY) else self.precision
-                call = _Call(self.cfg, seq, prec, entity_index=batch.candidates, keep_bf16=planes and not t.cache_enabled,
-                             index_status=self._status_words(batch.candidates.device))
-                if _lib.load().drin_fused_supported(C.byref(call.cfg)) == _lib.OK:
-                    if t.cache_enabled:                                # per-entity precompute cache
-                        out = self._forward_cached(call, t, params)
-                        self._watch_indices(call.device)
-                        return out
-                    if planes:
-                        out = self._score(call, self._prepared, False, *params)
-                        self._watch_indices(call.device)
-                        return out
-            if feat_grad:
-                batch = self._clamped(batch).gathered()
-                self._watch_indices(batch[0].device)
-            elif not inference and t.text.dim() == 3:
-                # training on a token-level table: every entity's tokens pooled once; the step then reads the pooled /
-                # token-0 / image / object tables through the candidate index inside the kernels, or gathers those rows
-                call = self._indexed_training_call(batch, planes)
-                if call is not None:
-                    if call.B == 0:
-                        return torch.zeros(0, call.N, dtype=torch.float32, device=call.device)
-                    out = self._score(call, None, True, *params)
-                    self._watch_indices(call.device)
-                    return out
-                batch, cls = self._clamped(batch).gathered_pooled(self.cfg)
-                self._watch_indices(batch[0].device)
-            else:
-                batch = self._clamped(batch).gathered()
-                self._watch_indices(batch[0].device)
+            got = self._forward_table(batch, params)
+            if torch.is_tensor(got):
+                return got
+            batch, cls = got
         # grad mode is already off inside Function.forward (and needs_input_grad ignores no_grad), so the
         # caller's mode is read here
         # (any parameter or any float batch tensor requiring grad: the layer-by-layer forward that keeps what backward reads)
         training = torch.is_grad_enabled() and (any(p.requires_grad for p in params) or _batch_requires_grad(batch))
-        block = None
-        # features stored as bf16 are read in place by the fused inference path in split-bf16 precision; every
-        # other path (training, exact fp32, geometries off the fused path) gets them widened to fp32 - exact
-        in_place = (not training and self._prepared is not None and self.cfg.num_gcn_layers == 2
-                    and self.precision in _PLANES)
-        # "bf16x3_if16" is a mode of the fused inference path; anything else it meets runs split-bf16
-        prec = self.precision if (in_place or self.precision not in _FUSED_ONLY) else _lib.PREC_BF16X3
         if (cls is None and training and len(batch) >= 14 and batch[7].dtype == torch.bfloat16 and batch[7].dim() == 4
                 and batch[7].is_cuda and batch[7].shape[0] > 0):
             # a training step on bf16-stored token blocks: pooled in place by the library - half
@@ -950,19 +920,23 @@ class Model(nn.Module):
                 block, cls = etf, cls.detach()
         if cls is not None:
             # pooled-ahead batch: the layer-by-layer entry points (the fused path folds the pooling into its one pass)
-            call = _Call(self.cfg, batch, _lib.PREC_BF16X3 if prec in _FUSED_ONLY else prec, entity_text_cls=cls)
-            if call.B == 0:
-                return torch.zeros(0, call.N, dtype=torch.float32, device=call.device)
+            prepared = None
+            call = _Call(self.cfg, batch, self._unfused_precision(), entity_text_cls=cls)
             if block is not None:
                 call.token_block, call.token_mask = block, emask.to(device=block.device, dtype=torch.int64).contiguous()
-            return self._score(call, None, training, *params, feats=_feature_inputs(call, block))
-        call = _Call(self.cfg, batch, prec, keep_bf16=in_place)
-        if ((call.cfg.feature_dtype != _lib.FEAT_F32 or prec in _FUSED_ONLY)
-                and _lib.load().drin_fused_supported(C.byref(call.cfg)) != _lib.OK):
-            call = _Call(self.cfg, batch, _lib.PREC_BF16X3 if prec in _FUSED_ONLY else prec)
+        else:
+            # features stored as bf16 are read in place by the fused inference path in split-bf16 precision; every
+            # other path (training, exact fp32, geometries off the fused path) gets them widened to fp32 - exact
+            prepared = self._prepared
+            in_place = not training and prepared is not None and self.cfg.num_gcn_layers == 2 and self.precision in _PLANES
+            prec = self.precision if in_place else self._unfused_precision()
+            call = _Call(self.cfg, batch, prec, keep_bf16=in_place)
+            if ((call.cfg.feature_dtype != _lib.FEAT_F32 or prec in _FUSED_ONLY)
+                    and _lib.load().drin_fused_supported(C.byref(call.cfg)) != _lib.OK):
+                call = _Call(self.cfg, batch, self._unfused_precision())
         if call.B == 0:
-            return torch.zeros(0, call.N, dtype=torch.float32, device=call.device)
-        return self._score(call, self._prepared, training, *params, feats=_feature_inputs(call) if training else ((), ()))
+            return call.scores()
+        return self._score(call, prepared, training, *params, feats=_feature_inputs(call, block) if training else ((), ()))
 
     def wait_for_parameters(self) -> None:
         """Make the current stream wait for an optimiser update `train.OverlappedStep` left running on its side stream (no-op
@@ -1018,29 +992,22 @@ class Model(nn.Module):
         # the layer-by-layer kernels trust the index (the stream kernel of the fused path clamps it): clamp here, so that a
         # bad candidate row can never become an out-of-bounds read on the device - and report it like the kernels do
         # (four small launches, no synchronisation: word 0 of the status words becomes 1, the value words stay 0)
-        prec = _lib.PREC_BF16X3 if self.precision in _FUSED_ONLY else self.precision
-        safe = cand.clamp(0, t.num_entities - 1)
-        self._status_words(cand.device)[0:1].bitwise_or_((safe != cand).any().view(1).to(torch.int32))
-        return _Call(self.cfg, seq, prec, entity_index=safe, entity_text_cls=cls)
+        safe = self._clamped(batch).candidates
+        return _Call(self.cfg, seq, self._unfused_precision(), entity_index=safe, entity_text_cls=cls)
 
     @torch.no_grad()
     def _forward_cached(self, call: _Call, table: EntityTable, params) -> torch.Tensor:
         """Table-form inference from the per-entity cache (`drin_forward_cached`)."""
         lib = _lib.load()
         if call.B == 0:
-            return torch.zeros(0, call.N, dtype=torch.float32, device=call.device)
+            return call.scores()
         self.wait_for_parameters()
-        det = tuple(p.detach().contiguous() for p in params)
-        pc = _lib.DrinParamsC()
-        _fill_params(pc, det, call.per_layer)
+        _det, pc = call.param_struct(params)                      # `_det` lives to the end of the call: `pc` points into it
         pbuf = self._prepared.get(call, params, pc)
         cache = table._get_cache(call, (id(self._prepared), self._prepared.generation), pc, pbuf)
-        n = lib.drin_cached_workspace_bytes(C.byref(call.cfg))
-        ws = torch.empty(max(n, 16), dtype=torch.uint8, device=call.device)
-        scores = torch.empty(call.B, call.N, dtype=torch.float32, device=call.device)
-        stream = torch.cuda.current_stream(call.device).cuda_stream
+        ws, scores = call.byte_buffer(lib.drin_cached_workspace_bytes(C.byref(call.cfg))), call.scores()
         _lib.check(lib.drin_forward_cached(C.byref(call.cfg), C.byref(call.batch), C.byref(pc), pbuf.data_ptr(),
-                                           cache.data_ptr(), ws.data_ptr(), ws.numel(), scores.data_ptr(), stream))
+                                           cache.data_ptr(), ws.data_ptr(), ws.numel(), scores.data_ptr(), call.stream()))
         return scores
 
     @torch.no_grad()
@@ -1048,10 +1015,8 @@ class Model(nn.Module):
         """Scores plus every stage's vertices and edges (tests / debugging)."""
         lib = _lib.load()
         self.wait_for_parameters()
-        call = _Call(self.cfg, batch, _lib.PREC_BF16X3 if self.precision in _FUSED_ONLY else self.precision)
-        params = tuple(p.detach().contiguous() for p in _param_list(self))
-        pc = _lib.DrinParamsC()
-        _fill_params(pc, params, call.per_layer)
+        call = _Call(self.cfg, batch, self._unfused_precision())
+        _det, pc = call.param_struct(_param_list(self))
         B, N, D, nl, dev = call.B, call.N, call.D, self.cfg.num_gcn_layers, call.device
         edge_shape = (4, B, N, D) if call.cfg.vector_edges else (4, B, N)
         tr = _lib.DrinTraceC()
@@ -1063,10 +1028,8 @@ class Model(nn.Module):
                 t = torch.full(shape, float("nan"), dtype=torch.float32, device=dev)
                 out[key] = t
                 getattr(tr, field)[l] = t.data_ptr()
-        ws = call.workspace(False)
-        scores = torch.empty(B, N, dtype=torch.float32, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        ws, scores = call.workspace(False), call.scores()
         _lib.check(lib.drin_forward(C.byref(call.cfg), C.byref(call.batch), C.byref(pc), ws.data_ptr(), ws.numel(),
-                                    scores.data_ptr(), 0, C.byref(tr), stream))
+                                    scores.data_ptr(), 0, C.byref(tr), call.stream()))
         out["scores"] = scores
         return out

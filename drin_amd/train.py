@@ -53,7 +53,7 @@ class GradBucket:
     on that bucket in place - no gather copy before, no scatter copy after.  Any other set of gradients (a foreign
     module, `grad_bucket=False`, gradients accumulated over several backward passes) is packed into a staging bucket.
 
-    `overlap=True` (with a `drin_amd.model.Model`): the bucket is reduced in TWO pieces.  `drin_backward_staged` records an
+    `overlap=True` (with a `drin_amd.model.Model`): the bucket is reduced in TWO pieces.  `drin_backward_ex` records the caller's
     event once the GCN layers' gradients are complete (only the four vertex encoders' weight-gradient products run after
     it); the layers' piece - the bucket's tail, 9.4 of the 26.8 MB - is all-reduced behind that event on a side stream,
     under those products, and `allreduce_mean()` reduces the vertex encoders' piece and joins.  Element for element the
@@ -77,7 +77,7 @@ class GradBucket:
             self.model._layers_ready_hook = self._layers_ready
 
     def close(self) -> None:
-        """Detach from the model (its backward goes back to the one-stage drin_backward)."""
+        """Detach from the model (its backward hands drin_backward_ex no event again)."""
         if self.model is not None and self.model._layers_ready_hook == self._layers_ready:
             self.model._layers_ready_hook = None
         self.model = None
@@ -114,8 +114,9 @@ class GradBucket:
         return work, (None if avg else dist.get_world_size())
 
     def _layers_ready(self, live_flat: torch.Tensor, split: int, ready: "torch.cuda.Event") -> None:
-        """Called inside `_DrinScore.backward` right after `drin_backward_staged` was enqueued: `live_flat[split:]` (the GCN
-        layers' gradients) is final once `ready` fires; the vertex encoders' products behind it write `live_flat[:split]` only."""
+        """Called inside `_DrinScore.backward` right after `drin_backward_ex` was enqueued with the event `ready`:
+        `live_flat[split:]` (the GCN layers' gradients) is final once `ready` fires; the vertex encoders' products
+        behind it write `live_flat[:split]` only."""
         if not _collectives(self.force) or self._early is not None or split <= 0 or split >= live_flat.numel():
             return
         piece = live_flat[split:]

@@ -148,13 +148,13 @@ def test_param_grads_unchanged_by_feature_grads_and_repeat_bits():
     cfg, sd, batch = _tiny_wm()
     G = weights((3, cfg.num_candidates_model), 2).to(DEV)
     m = model_for(cfg, sd)
-    (m([t.to(DEV) for t in batch[:14]]) * G).sum().backward()        # drin_backward: no batch tensor requires grad
+    (m([t.to(DEV) for t in batch[:14]]) * G).sum().backward()        # drin_backward_ex, no input_grads: no batch tensor requires grad
     plain = [p.grad.clone() for p in m.parameters() if p.grad is not None]
     runs = []
     for _ in range(2):
         m.zero_grad(set_to_none=True)
         x = leaves(batch)
-        (m(x) * G).sum().backward()                                   # drin_backward_ex
+        (m(x) * G).sum().backward()                                   # drin_backward_ex with input_grads
         with_feats = [p.grad.clone() for p in m.parameters() if p.grad is not None]
         assert len(with_feats) == len(plain) and all(torch.equal(a, b) for a, b in zip(plain, with_feats))
         runs.append([x[i].grad.clone() for i in FLOAT_INPUTS])

@@ -290,55 +290,48 @@ static int validate_params(const drin_config* c, const drin_params* p) {
   return DRIN_OK;
 }
 
+// Operand pointers of the static edges without a workspace, hence without pooled copies (inner dims <= 1): the caller's
+// tensors and span-mean scratch.
+static Pooled unpooled(const drin_config* c, const drin_batch* b, const float* span_mean) {
+  Pooled p;
+  p.span_mean = span_mean;
+  p.mention_object = b->mention_object;
+  p.entity_object = b->entity_object;
+  p.entity_image = b->entity_image;
+  p.entity_text = b->entity_text;
+  // the raw CLS / pooler row of a pair: token 0 of its block (model.py:73-75), or the pooled row as delivered
+  p.entity_text_raw_stride = c->entity_tokens > 0 ? (int64_t)c->entity_tokens * c->embed_dim : c->embed_dim;
+  return p;
+}
+
 // Operand pointers of the vertex / edge encoders: pooled copies in the workspace where the reference
 // averages an axis, the caller's tensors where it does not.
 void resolve_pooled(const drin_config* c, const drin_batch* b, const Layout& L, float* ws, Pooled* out) {
-  const int D = c->embed_dim;
-  out->span_mean = ws + L.span_mean;
+  *out = unpooled(c, b, ws + L.span_mean);
   out->mention_image = ws + L.mimg_pool;
-  out->mention_object = c->mention_object_inner > 1 ? ws + L.mobj_pool : b->mention_object;
-  out->entity_object = c->entity_object_inner > 1 ? ws + L.eobj_pool : b->entity_object;
-  out->entity_image = c->entity_image_inner > 1 ? ws + L.eimg_pool : b->entity_image;
-  out->entity_text = c->entity_tokens > 0 ? ws + L.xet_pool : b->entity_text;
-  out->entity_text_raw_stride = c->entity_tokens > 0 ? (int64_t)c->entity_tokens * D : D;
+  if (c->mention_object_inner > 1) out->mention_object = ws + L.mobj_pool;
+  if (c->entity_object_inner > 1) out->entity_object = ws + L.eobj_pool;
+  if (c->entity_image_inner > 1) out->entity_image = ws + L.eimg_pool;
+  if (c->entity_tokens > 0) out->entity_text = ws + L.xet_pool;
 }
 
-// Resolves the pooled / raw operand pointers of the vertex and edge encoders and runs the pooling.
+// Resolves the pooled / raw operand pointers of the vertex and edge encoders and runs the pooling: a pass for every operand
+// that resolve_pooled pointed into the workspace.
 int run_pooling(const drin_config* c, const drin_batch* b, const Layout& L, float* ws, Pooled* out, hipStream_t st) {
   const int B = c->batch, N = c->num_candidates, D = c->embed_dim, R = c->image_dim;
   const int64_t M = (int64_t)B * N;
-  out->span_mean = ws + L.span_mean;
-  DRIN_TRY(launch_span_mean(b->mention_text, b->mention_start, b->mention_end, ws + L.span_mean, B, c->mention_tokens,
-                            D, st));
-  out->mention_image = ws + L.mimg_pool;
+  resolve_pooled(c, b, L, ws, out);
+  auto copy_of = [](const float* resolved, const float* raw) { return resolved != raw ? const_cast<float*>(resolved) : nullptr; };
+  DRIN_TRY(launch_span_mean(b->mention_text, b->mention_start, b->mention_end, ws + L.span_mean, B, c->mention_tokens, D, st));
   DRIN_TRY(launch_axis_mean(b->mention_image, ws + L.mimg_pool, B, c->image_regions, R, st));
-  if (c->mention_object_inner > 1) {
-    DRIN_TRY(launch_axis_mean(b->mention_object, ws + L.mobj_pool, (int64_t)B * c->mention_objects,
-                              c->mention_object_inner, R, st));
-    out->mention_object = ws + L.mobj_pool;
-  } else {
-    out->mention_object = b->mention_object;
-  }
-  if (c->entity_object_inner > 1) {
-    DRIN_TRY(launch_axis_mean(b->entity_object, ws + L.eobj_pool, M * c->entity_objects, c->entity_object_inner, R, st));
-    out->entity_object = ws + L.eobj_pool;
-  } else {
-    out->entity_object = b->entity_object;
-  }
-  if (c->entity_image_inner > 1) {
-    DRIN_TRY(launch_axis_mean(b->entity_image, ws + L.eimg_pool, M, c->entity_image_inner, R, st));
-    out->entity_image = ws + L.eimg_pool;
-  } else {
-    out->entity_image = b->entity_image;
-  }
-  if (c->entity_tokens > 0) {
-    DRIN_TRY(launch_entity_token_mean(b->entity_text, b->entity_text_mask, ws + L.xet_pool, M, c->entity_tokens, D, st));
-    out->entity_text = ws + L.xet_pool;
-    out->entity_text_raw_stride = (int64_t)c->entity_tokens * D;  // token 0 = CLS (model.py:73-75)
-  } else {
-    out->entity_text = b->entity_text;
-    out->entity_text_raw_stride = D;
-  }
+  if (float* dst = copy_of(out->mention_object, b->mention_object))
+    DRIN_TRY(launch_axis_mean(b->mention_object, dst, (int64_t)B * c->mention_objects, c->mention_object_inner, R, st));
+  if (float* dst = copy_of(out->entity_object, b->entity_object))
+    DRIN_TRY(launch_axis_mean(b->entity_object, dst, M * c->entity_objects, c->entity_object_inner, R, st));
+  if (float* dst = copy_of(out->entity_image, b->entity_image))
+    DRIN_TRY(launch_axis_mean(b->entity_image, dst, M, c->entity_image_inner, R, st));
+  if (float* dst = copy_of(out->entity_text, b->entity_text))
+    DRIN_TRY(launch_entity_token_mean(b->entity_text, b->entity_text_mask, dst, M, c->entity_tokens, D, st));
   return DRIN_OK;
 }
 
@@ -654,12 +647,7 @@ int drin_edges_fwd(const drin_config* cfg, const drin_batch* batch, float* edges
   }
   DRIN_TRY(launch_span_mean(batch->mention_text, batch->mention_start, batch->mention_end, span_mean, B,
                             cfg->mention_tokens, D, st));
-  Pooled P;
-  P.span_mean = span_mean;
-  P.mention_object = batch->mention_object;
-  P.entity_object = batch->entity_object;
-  P.entity_text_raw_stride = cfg->entity_tokens > 0 ? (int64_t)cfg->entity_tokens * D : D;
-  return run_static_edges(cfg, batch, P, edges, st);
+  return run_static_edges(cfg, batch, unpooled(cfg, batch, span_mean), edges, st);
 }
 
 int drin_pool_fwd(const drin_config* cfg, const drin_batch* batch, float* pooled_entity_text,

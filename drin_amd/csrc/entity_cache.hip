@@ -790,7 +790,7 @@ DRIN_API int drin_forward_cached(const drin_config* cfg, const drin_batch* b, co
   hipStream_t st = (hipStream_t)stream;
   float* ws = (float*)workspace;
   const float* pb = (const float*)prepared;
-  const int B = cfg->batch, N = cfg->num_candidates, D = cfg->embed_dim, R = cfg->image_dim;
+  const int B = cfg->batch, N = cfg->num_candidates, D = cfg->embed_dim;
   const int64_t M = (int64_t)B * N;
   if (B == 0) return DRIN_OK;
   if (B > 65535) {
@@ -800,7 +800,6 @@ DRIN_API int drin_forward_cached(const drin_config* cfg, const drin_batch* b, co
   const int prec = cfg->precision;
   const bool planes = (prec == DRIN_PREC_BF16X3 || prec == DRIN_PREC_BF16X3_ALL) && (D % 32 == 0);
   const drin_layer_params& L1 = params->layer[0];
-  const drin_layer_params& L2 = params->layer[1];
   __bf16* e1_hi = reinterpret_cast<__bf16*>(ws + L.p_et1);
   const size_t MD = (size_t)M * D;
   if (!planes && (prec == DRIN_PREC_BF16X3 || prec == DRIN_PREC_BF16X3_ALL)) {
@@ -808,17 +807,12 @@ DRIN_API int drin_forward_cached(const drin_config* cfg, const drin_batch* b, co
     return DRIN_E_UNSUPPORTED;
   }
 
-  float* const sk = L.splitk_floats ? ws + L.splitk : nullptr;
-  const size_t skf = L.splitk_floats;
+  const GemmScratch msk{L.splitk_floats ? ws + L.splitk : nullptr, L.splitk_floats};
+  // The mention-sized products of this path never read the prepared weight planes (kept as built: passing them changes the kernel, hence bits)
+  const bool weight_planes = false;
   // (1) mention-side pooling and vertex-encoder Linears, [hm | fu] = [mt0; mi0] [W_h1; W_u1]^T + [0; b_u1]
-  DRIN_TRY(launch_span_mean(b->mention_text, b->mention_start, b->mention_end, ws + L.span_mean, B, cfg->mention_tokens, D, st));
-  DRIN_TRY(launch_axis_mean(b->mention_image, ws + L.mimg, B, cfg->image_regions, R, st));
-  float* vm0 = ws + L.vm0;
-  DRIN_TRY(launch_gemm_nt_pair({ws + L.span_mean, params->w_mention_text, params->b_mention_text, vm0, D, D, D, B, D, D, nullptr},
-                               {ws + L.mimg, params->w_mention_image, params->b_mention_image, vm0 + (size_t)B * D, R, R, D, B, D, R, nullptr},
-                               prec, st, sk, skf));
   float* hmfu = ws + L.hmfu;
-  DRIN_TRY(launch_gemm_nt(vm0, D, pb + P.wcat1, D, pb + P.bcat1, hmfu, 2 * D, 2 * (int64_t)B, 2 * D, D, false, prec, st, sk, skf));
+  DRIN_TRY(run_folded_head(cfg, b, params, pb, P, weight_planes, ws + L.span_mean, ws + L.mimg, ws + L.vm0, hmfu, msk, st));
 
   // candidate rows outside the tables: clamped by k_cached_pairs, reported here (drin_batch.index_status)
   if (b->index_status) {
@@ -829,8 +823,9 @@ DRIN_API int drin_forward_cached(const drin_config* cfg, const drin_batch* b, co
     DRIN_CHECK_LAUNCH("k_check_entity_index");
   }
   // (2) one gathered pass over the cache rows: edges, layer-1 entity vertices, all cross-candidate sums
-  CachedArgs a;
-  memset(&a, 0, sizeof(a));
+  CachedArgs a = shaped_args<CachedArgs>(*cfg);
+  set_vertex_fields(a, *cfg);
+  set_edge_fields(a, *cfg);
   a.cache = (const float*)cache;
   a.ldc = (int64_t)cache_row_floats(*cfg);
   a.num_entities = cfg->num_entities;
@@ -854,20 +849,7 @@ DRIN_API int drin_forward_cached(const drin_config* cfg, const drin_batch* b, co
   a.et1_lo = planes ? e1_hi + MD : nullptr;
   a.c_part = ws + L.c_part;
   a.s2_part = ws + L.s2_part;
-  a.B = B;
-  a.N = N;
-  a.D4 = D / 4;
-  a.R4 = R / 4;
-  a.Km = cfg->mention_objects;
   a.chunks = L.chunks;
-  a.dynamic = cfg->dynamic_edges != 0;
-  for (int k = 0; k < 4; ++k) a.mask[k] = cfg->edge_enabled[k];
-  a.cos_eps = cfg->cosine_eps;
-  a.miei_eps = cfg->miei_eps;
-  a.clip = cfg->clip_scale;
-  a.ln_eps = cfg->layer_norm_eps;
-  a.act_v = vertex_act(cfg);
-  a.act_e = edge_act(cfg);
   if (cache_mixed(*cfg)) {   // DRIN_CACHE_MIXED_F16 rows (the o^ row is read in the PAIR layout: an even number of slots)
     const bool gen = a.act_v != DRIN_ACT_GELU, tiny = a.D4 <= 64 && a.R4 <= 128;
     if (gen && tiny)
@@ -899,40 +881,10 @@ DRIN_API int drin_forward_cached(const drin_config* cfg, const drin_batch* b, co
                        hmfu, 2 * D, pb + P.cb_t, pb + P.cb_i, L1.b_h, vm1, B, D, L.chunks, 1.0f / (float)N);
     DRIN_CHECK_LAUNCH("k_mention_layer1_cached");
   }
-  DRIN_TRY(launch_layernorm_gelu(vm1, L1.ln_weight, L1.ln_bias, vm1, nullptr, nullptr, 2 * (int64_t)B, D, cfg->layer_norm_eps, st,
-                                 vertex_act(cfg)));
-  DRIN_TRY(launch_gemm_nt(vm1, D, L2.w_h, D, nullptr, ws + L.hm2, D, 2 * (int64_t)B, D, D, false, prec, st, sk, skf));
-  // (4) layer-2 mention-text vertex
-  DRIN_TRY(launch_mention_input2(ws + L.s2_part, vm1, ws + L.agg2, B, D, N, L.chunks, st));
-  DRIN_TRY(launch_gemm_nt(ws + L.agg2, D, L2.w_h, D, L2.b_h, ws + L.mt2, D, B, D, D, false, prec, st, sk, skf));
-  DRIN_TRY(launch_layernorm_gelu(ws + L.mt2, L2.ln_weight, L2.ln_bias, ws + L.mt2, nullptr, nullptr, B, D, cfg->layer_norm_eps, st,
-                                 vertex_act(cfg)));
-  // (5) layer-2 entity-text contraction, vertex and score
-  float* h2 = ws + L.h2;
-  if (planes) {
-    const __bf16* w2 = reinterpret_cast<const __bf16*>(pb + P.p_wh2);
-    DRIN_TRY(launch_gemm_x3_planes(e1_hi, e1_hi + MD, D, w2, w2 + (size_t)D * D, D, nullptr, h2, D, M, D, D, st));
-  } else {
-    DRIN_TRY(launch_gemm_nt(ws + L.et1, D, L2.w_h, D, nullptr, h2, D, M, D, D, false, prec, st));
-  }
-  FinalArgs fa;
-  memset(&fa, 0, sizeof(fa));
-  fa.h2 = h2;
-  fa.hm2 = ws + L.hm2;
-  fa.b_h2 = L2.b_h;
-  fa.gamma = L2.ln_weight;
-  fa.beta = L2.ln_bias;
-  fa.e1m = ws + L.e1m;
-  fa.mt2 = ws + L.mt2;
-  fa.scores = scores;
-  fa.B = B;
-  fa.N = N;
-  fa.D4 = D / 4;
-  fa.chunks = L.chunks;
-  fa.ln_eps = cfg->layer_norm_eps;
-  fa.act_v = vertex_act(cfg);
-  fa.cos_eps = cfg->cosine_eps;
-  return launch_pair_final(fa, st);
+  DRIN_TRY(run_folded_mention_finish(cfg, params, pb, P, weight_planes, vm1, ws + L.hm2, msk, st));
+  // (4), (5) layer 2; no scratch for its pair-sized contraction on this path
+  return run_folded_tail(cfg, params, pb, P, L.chunks, ws + L.s2_part, vm1, ws + L.agg2, ws + L.mt2, ws + L.hm2, ws + L.e1m, ws + L.h2,
+                         planes ? nullptr : ws + L.et1, planes ? e1_hi : nullptr, weight_planes, msk, {}, scores, st);
 }
 
 }  // extern "C"

@@ -3,8 +3,10 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <string.h>
 
 #include "../../include/drin_hip.h"
+#include "layout.h"
 
 namespace drin {
 
@@ -127,6 +129,29 @@ struct FinalArgs {
   float ln_eps, cos_eps;
 };
 
+// An argument block starts zeroed; the fields that restate the configuration are derived here and nowhere else (shape: every
+// block; vertex fields: PairArgs, FinalArgs, CachedArgs; edge fields: StreamArgs, CachedArgs); the rest is the call site's.
+template <class Args>
+Args shaped_args(const drin_config& c) {
+  Args a;
+  memset(&a, 0, sizeof(a));
+  a.B = c.batch, a.N = c.num_candidates, a.D4 = c.embed_dim / 4;
+  return a;
+}
+template <class Args>
+void set_vertex_fields(Args& a, const drin_config& c) {
+  a.ln_eps = c.layer_norm_eps, a.act_v = vertex_act(&c);
+}
+template <class Args>
+void set_edge_fields(Args& a, const drin_config& c) {
+  a.R4 = c.image_dim / 4;
+  a.Km = c.mention_objects;
+  a.dynamic = c.dynamic_edges != 0;
+  a.act_e = edge_act(&c);
+  for (int k = 0; k < 4; ++k) a.mask[k] = c.edge_enabled[k];
+  a.cos_eps = c.cosine_eps, a.miei_eps = c.miei_eps, a.clip = c.clip_scale;
+}
+
 size_t entity_stream_lds_bytes(const StreamArgs& a);
 int launch_entity_stream(const StreamArgs& a, hipStream_t st);
 int launch_reduce_stream_partials(const float* part, float* s_text, float* s_img, float* sig, int B, int D, int R,
@@ -137,4 +162,26 @@ int launch_pair_layer1(const PairArgs& a, hipStream_t st);
 int launch_mention_input2(const float* part, const float* mt1, float* out, int B, int D, int N, int chunks,
                           hipStream_t st);
 int launch_pair_final(const FinalArgs& a, hipStream_t st);
+
+// ---- what drin_forward_prepared and drin_forward_cached share (fused_forward.hip) ----------------------------------------------
+// The two are one folded model around two ways of getting a pair's layer-1 entity quantities: run_folded_head, the path's own
+// middle with run_folded_mention_finish inside, run_folded_tail.  `weight_planes` (the mention-sized products read the prepared bf16
+// planes of their weights) and the scratch a path hands over select kernels inside the GEMM module, hence bits: passed on as given.
+struct GemmScratch {  // split-K / tail-split partials of a product; none: {}
+  float* p = nullptr;
+  size_t floats = 0;
+};
+// Mention-side pooling (ghmfc.py:54-60, model.py:41; fp32 or bf16 features by cfg->feature_dtype), the two vertex-encoder Linears
+// -> vm0 = [mt0; mi0], then hmfu = [hm | fu] = vm0 [W_h1; W_u1]^T + [0; b_u1].
+int run_folded_head(const drin_config* cfg, const drin_batch* b, const drin_params* params, const float* prepared, const Prepared& P,
+                    bool weight_planes, float* span_mean, float* mimg, float* vm0, float* hmfu, GemmScratch mention_sk, hipStream_t st);
+// Layer-1 mention vertices from their W_h1 output (LayerNorm + activation in place), then hm2 = vm1 W_h2^T.
+int run_folded_mention_finish(const drin_config* cfg, const drin_params* params, const float* prepared, const Prepared& P,
+                              bool weight_planes, float* vm1, float* hm2, GemmScratch mention_sk, hipStream_t st);
+// Layer 2: the mention-text vertex mt2 (through agg2), the contraction h2 = et1 W_h2^T - on et1's bf16 planes (hi at et1_hi, lo
+// behind it; the LDS-DMA kernel, pair_sk its scratch) or, et1_hi == NULL, on fp32 et1 - then k_pair_final's vertex and score.
+int run_folded_tail(const drin_config* cfg, const drin_params* params, const float* prepared, const Prepared& P, int chunks,
+                    const float* s2_part, const float* vm1, float* agg2, float* mt2, const float* hm2, const float* e1m, float* h2,
+                    const float* et1, const void* et1_hi, bool weight_planes, GemmScratch mention_sk, GemmScratch pair_sk,
+                    float* scores, hipStream_t st);
 }  // namespace drin

@@ -245,6 +245,77 @@ int drin_prepare(const drin_config* cfg, const drin_params* params, void* prepar
 
 namespace drin {
 
+// split-bf16 widths of every product of the folded paths (DRIN_PREC_BF16X3_IF16 differs in the image contraction's passes only)
+static int folded_precision(const drin_config* c) { return c->precision == DRIN_PREC_BF16X3_IF16 ? (int)DRIN_PREC_BF16X3 : c->precision; }
+
+int run_folded_head(const drin_config* cfg, const drin_batch* b, const drin_params* params, const float* pb, const Prepared& P,
+                    bool weight_planes, float* span_mean, float* mimg, float* vm0, float* hmfu, GemmScratch sk, hipStream_t st) {
+  const int B = cfg->batch, D = cfg->embed_dim, R = cfg->image_dim, prec = folded_precision(cfg);
+  auto wp = [&](size_t plane_off) -> const float* { return weight_planes ? pb + plane_off : nullptr; };
+  if (cfg->feature_dtype == DRIN_FEAT_BF16) {
+    DRIN_TRY(launch_span_mean_bf16(b->mention_text, b->mention_start, b->mention_end, span_mean, B, cfg->mention_tokens, D, st));
+    DRIN_TRY(launch_axis_mean_bf16(b->mention_image, mimg, B, cfg->image_regions, R, st));
+  } else {
+    DRIN_TRY(launch_span_mean(b->mention_text, b->mention_start, b->mention_end, span_mean, B, cfg->mention_tokens, D, st));
+    DRIN_TRY(launch_axis_mean(b->mention_image, mimg, B, cfg->image_regions, R, st));
+  }
+  DRIN_TRY(launch_gemm_nt_pair({span_mean, params->w_mention_text, params->b_mention_text, vm0, D, D, D, B, D, D, wp(P.p_wmt)},
+                               {mimg, params->w_mention_image, params->b_mention_image, vm0 + (size_t)B * D, R, R, D, B, D, R, wp(P.p_wmi)},
+                               prec, st, sk.p, sk.floats));
+  return launch_gemm_nt(vm0, D, pb + P.wcat1, D, pb + P.bcat1, hmfu, 2 * D, 2 * (int64_t)B, 2 * D, D, false, prec, st, sk.p, sk.floats,
+                        wp(P.p_wcat1));
+}
+
+int run_folded_mention_finish(const drin_config* cfg, const drin_params* params, const float* pb, const Prepared& P,
+                              bool weight_planes, float* vm1, float* hm2, GemmScratch sk, hipStream_t st) {
+  const int B = cfg->batch, D = cfg->embed_dim;
+  const drin_layer_params& L1 = params->layer[0];
+  DRIN_TRY(launch_layernorm_gelu(vm1, L1.ln_weight, L1.ln_bias, vm1, nullptr, nullptr, 2 * (int64_t)B, D, cfg->layer_norm_eps, st,
+                                 vertex_act(cfg)));
+  return launch_gemm_nt(vm1, D, params->layer[1].w_h, D, nullptr, hm2, D, 2 * (int64_t)B, D, D, false, folded_precision(cfg), st, sk.p,
+                        sk.floats, weight_planes ? pb + P.p_wh2 : nullptr);
+}
+
+int run_folded_tail(const drin_config* cfg, const drin_params* params, const float* pb, const Prepared& P, int chunks,
+                    const float* s2_part, const float* vm1, float* agg2, float* mt2, const float* hm2, const float* e1m, float* h2,
+                    const float* et1, const void* et1_hi, bool weight_planes, GemmScratch sk, GemmScratch pair_sk, float* scores,
+                    hipStream_t st) {
+  const int B = cfg->batch, N = cfg->num_candidates, D = cfg->embed_dim, prec = folded_precision(cfg);
+  const int64_t M = (int64_t)B * N;
+  const drin_layer_params& L2 = params->layer[1];
+  // layer-2 mention-text vertex
+  DRIN_TRY(launch_mention_input2(s2_part, vm1, agg2, B, D, N, chunks, st));
+  DRIN_TRY(launch_gemm_nt(agg2, D, L2.w_h, D, L2.b_h, mt2, D, B, D, D, false, prec, st, sk.p, sk.floats,
+                          weight_planes ? pb + P.p_wh2 : nullptr));
+  DRIN_TRY(launch_layernorm_gelu(mt2, L2.ln_weight, L2.ln_bias, mt2, nullptr, nullptr, B, D, cfg->layer_norm_eps, st, vertex_act(cfg)));
+  // layer-2 entity-text contraction, vertex and score
+  // (Round 6, built and dropped - profiles/r6_full_row_ab.txt, tools/probes/r6_full_row/, commit 8a5bc6b: this contraction and k_pair_final's
+  //  arithmetic in ONE launch on 96-row x 768-column tiles, so that h2 never goes to HBM.  Correct, and slower: a full-row tile needs all
+  //  768 weight rows per K-step for 96 activation rows - 1.56 x the LDS-DMA instructions per MFMA of the 256 x 256 tile - and its K-loop
+  //  alone took what the 256 x 256 kernel takes including its store (1.20 against 1.15 ms); the epilogue's vector work came on top.)
+  if (et1_hi) {
+    const __bf16* e1 = static_cast<const __bf16*>(et1_hi);
+    const __bf16* w2 = reinterpret_cast<const __bf16*>(pb + P.p_wh2);
+    DRIN_TRY(launch_gemm_x3_planes(e1, e1 + (size_t)M * D, D, w2, w2 + (size_t)D * D, D, nullptr, h2, D, M, D, D, st, pair_sk.p,
+                                   pair_sk.floats));
+  } else {
+    DRIN_TRY(launch_gemm_nt(et1, D, L2.w_h, D, nullptr, h2, D, M, D, D, false, prec, st));
+  }
+  FinalArgs fa = shaped_args<FinalArgs>(*cfg);
+  set_vertex_fields(fa, *cfg);
+  fa.h2 = h2;
+  fa.hm2 = hm2;
+  fa.b_h2 = L2.b_h;
+  fa.gamma = L2.ln_weight;
+  fa.beta = L2.ln_bias;
+  fa.e1m = e1m;
+  fa.mt2 = mt2;
+  fa.scores = scores;
+  fa.chunks = chunks;
+  fa.cos_eps = cfg->cosine_eps;
+  return launch_pair_final(fa, st);
+}
+
 // The whole forward on the caller's stream: the one pass over the entity bytes (HBM-bound), then the contractions and row kernels
 // behind it (MFMA-bound).  (Running the two halves of consecutive mention chunks side by side - two streams, forced co-residency,
 // disjoint CU masks - was built in round 3 and measured slower every time; removed in round 5: profiles/r3_pipeline_probe.txt.)
@@ -259,7 +330,7 @@ static int forward_prepared_on_stream(const drin_config* cfg, const drin_batch* 
   const int B = cfg->batch, N = cfg->num_candidates, D = cfg->embed_dim, R = cfg->image_dim;
   const int64_t M = (int64_t)B * N;
   if (B == 0) return DRIN_OK;
-  const int prec = cfg->precision == DRIN_PREC_BF16X3_IF16 ? (int)DRIN_PREC_BF16X3 : cfg->precision;
+  const int prec = folded_precision(cfg);
   const bool dyn = cfg->dynamic_edges != 0;
   const bool tokens = cfg->entity_tokens > 0;
   // split-bf16 precision: the producers write bf16 hi / lo planes and the three pair-sized contractions
@@ -306,40 +377,23 @@ static int forward_prepared_on_stream(const drin_config* cfg, const drin_batch* 
   __bf16* e1_hi = reinterpret_cast<__bf16*>(ws + L.p_et1);
   const size_t MD = (size_t)M * D, MR = (size_t)M * R;
   const drin_layer_params& L1 = params->layer[0];
-  const drin_layer_params& L2 = params->layer[1];
 
   // Mention-sized contractions: launch_gemm_nt / launch_gemm_nt_pair choose the kernel; the split-bf16 ones read the prepared
   // weight planes when this path has them (`planes` also asks R % 32, which those cannot see)
   auto wp = [&](size_t plane_off) -> const float* { return planes ? pb + plane_off : nullptr; };
-  float* const sk = L.splitk_floats ? ws + L.splitk : nullptr;
-  const size_t skf = L.splitk_floats;
+  const GemmScratch msk{L.splitk_floats ? ws + L.splitk : nullptr, L.splitk_floats};
   float* vm0 = ws + L.vm0;
   float* hmfu = ws + L.hmfu;
   // pooled entity text stored as bf16 is exact in its hi plane: no lo plane, two MFMAs per tile pair
   const bool xt_exact = bf16_feat && !tokens;
-  // (1) mention-side pooling (ghmfc.py:54-60, model.py:41) and vertex-encoder Linears
-  if (bf16_feat) {
-    DRIN_TRY(launch_span_mean_bf16(b->mention_text, b->mention_start, b->mention_end, ws + L.span_mean, B,
-                                   cfg->mention_tokens, D, st));
-    DRIN_TRY(launch_axis_mean_bf16(b->mention_image, ws + L.mimg, B, cfg->image_regions, R, st));
-  } else {
-    DRIN_TRY(launch_span_mean(b->mention_text, b->mention_start, b->mention_end, ws + L.span_mean, B,
-                              cfg->mention_tokens, D, st));
-    DRIN_TRY(launch_axis_mean(b->mention_image, ws + L.mimg, B, cfg->image_regions, R, st));
-  }
-  DRIN_TRY(launch_gemm_nt_pair({ws + L.span_mean, params->w_mention_text, params->b_mention_text, vm0, D, D, D, B, D, D, wp(P.p_wmt)},
-                               {ws + L.mimg, params->w_mention_image, params->b_mention_image, vm0 + (size_t)B * D, R, R, D, B, D, R,
-                                wp(P.p_wmi)},
-                               prec, st, sk, skf));
-  // (2) [hm | fu] = [mt0; mi0] [W_h1; W_u1]^T + [0; b_u1], then q = fu [W_v1 W_et | W_v1 W_ei]
-  DRIN_TRY(launch_gemm_nt(vm0, D, pb + P.wcat1, D, pb + P.bcat1, hmfu, 2 * D, 2 * (int64_t)B, 2 * D, D, false, prec, st, sk, skf,
-                          wp(P.p_wcat1)));
+  // (1) mention-side pooling and vertex-encoder Linears, [hm | fu]; (2) q = fu [W_v1 W_et | W_v1 W_ei]
+  DRIN_TRY(run_folded_head(cfg, b, params, pb, P, planes, ws + L.span_mean, ws + L.mimg, vm0, hmfu, msk, st));
   if (dyn)
-    DRIN_TRY(launch_gemm_nt(hmfu + D, 2 * D, pb + P.ecat, D, nullptr, ws + L.q, D + R, 2 * (int64_t)B, D + R, D, false, prec, st, sk,
-                            skf, wp(P.p_ecat)));
+    DRIN_TRY(launch_gemm_nt(hmfu + D, 2 * D, pb + P.ecat, D, nullptr, ws + L.q, D + R, 2 * (int64_t)B, D + R, D, false, prec, st, msk.p,
+                            msk.floats, wp(P.p_ecat)));
   // (3) one pass over the entity-side bytes
-  StreamArgs sa;
-  memset(&sa, 0, sizeof(sa));
+  StreamArgs sa = shaped_args<StreamArgs>(*cfg);
+  set_edge_fields(sa, *cfg);
   sa.entity_text = b->entity_text;
   sa.entity_mask = b->entity_text_mask;
   sa.entity_image = b->entity_image;
@@ -373,21 +427,10 @@ static int forward_prepared_on_stream(const drin_config* cfg, const drin_batch* 
   sa.e0m = ws + L.e0m;
   sa.e1m = ws + L.e1m;
   sa.s_part = ws + L.s_part;
-  sa.B = B;
-  sa.N = N;
-  sa.D4 = D / 4;
-  sa.R4 = R / 4;
   sa.T = cfg->entity_tokens;
-  sa.Km = cfg->mention_objects;
   sa.Ke = cfg->entity_objects;
   sa.chunks = L.chunks;
-  sa.dynamic = dyn ? 1 : 0;
-  sa.act_e = edge_act(cfg);
   sa.bf16_features = bf16_feat ? 1 : 0;
-  for (int k = 0; k < 4; ++k) sa.mask[k] = cfg->edge_enabled[k];
-  sa.cos_eps = cfg->cosine_eps;
-  sa.miei_eps = cfg->miei_eps;
-  sa.clip = cfg->clip_scale;
   sa.s_text = ws + L.s_text;
   sa.s_img = ws + L.s_img;
   sa.sig = ws + L.sig;
@@ -398,34 +441,31 @@ static int forward_prepared_on_stream(const drin_config* cfg, const drin_batch* 
   DRIN_TRY(launch_gemm_nt_pair({ws + L.s_text, params->w_entity_text, nullptr, ws + L.tm, D, D, D, 2 * (int64_t)B, D, D, wp(P.p_wet)},
                                {ws + L.s_img, params->w_entity_image, nullptr, ws + L.tm2, R, R, D, 2 * (int64_t)B, D, R,
                                 wp(P.p_wei)},
-                               prec, st, sk, skf));
+                               prec, st, msk.p, msk.floats));
   DRIN_TRY(launch_mention_input1(ws + L.tm, ws + L.tm2, ws + L.sig, params->b_entity_text, params->b_entity_image, vm0, ws + L.agg1, B, D, N, st));
   float* vm1 = ws + L.vm1;
-  DRIN_TRY(launch_gemm_nt(ws + L.agg1, D, L1.w_h, D, L1.b_h, vm1, D, 2 * (int64_t)B, D, D, false, prec, st, sk, skf, wp(P.p_wh1)));
-  DRIN_TRY(launch_layernorm_gelu(vm1, L1.ln_weight, L1.ln_bias, vm1, nullptr, nullptr, 2 * (int64_t)B, D, cfg->layer_norm_eps, st,
-                                 vertex_act(cfg)));
-  DRIN_TRY(launch_gemm_nt(vm1, D, L2.w_h, D, nullptr, ws + L.hm2, D, 2 * (int64_t)B, D, D, false, prec, st, sk, skf, wp(P.p_wh2)));
+  DRIN_TRY(launch_gemm_nt(ws + L.agg1, D, L1.w_h, D, L1.b_h, vm1, D, 2 * (int64_t)B, D, D, false, prec, st, msk.p, msk.floats, wp(P.p_wh1)));
+  DRIN_TRY(run_folded_mention_finish(cfg, params, pb, P, planes, vm1, ws + L.hm2, msk, st));
   // (5) the two pair-sized layer-1 contractions on the folded weights
   // split-K scratch: the whole-product split when the batch is a few tiles, else the tail-split scratch
-  float* const psk = L.pair_splitk_floats ? ws + L.pair_splitk : sk;
-  const size_t pskf = L.pair_splitk_floats ? L.pair_splitk_floats : skf;
+  const GemmScratch psk = L.pair_splitk_floats ? GemmScratch{ws + L.pair_splitk, L.pair_splitk_floats} : msk;
   if (planes) {
     const __bf16* ct = reinterpret_cast<const __bf16*>(pb + P.p_ctxt);
     const __bf16* ci = reinterpret_cast<const __bf16*>(pb + P.p_cimg);
     DRIN_TRY(launch_gemm_x3_planes(xt_hi, xt_exact ? nullptr : xt_hi + MD, D, ct, ct + (size_t)D * D, D, nullptr, ws + L.h_text, D, M, D,
-                                   D, st, psk, pskf));
+                                   D, st, psk.p, psk.floats));
     if (if16)        // one fp16 pass on the plane the stream kernel wrote
       DRIN_TRY(launch_gemm_f16_planes(xi_hi, R, pb + P.p_cimg_f16, R, ws + L.xi_scale, pb + P.cimg_f16_scale, ws + L.h_image, D, M, D, R,
-                                      st, psk, pskf));
+                                      st, psk.p, psk.floats));
     else if (xi_planes)
       DRIN_TRY(launch_gemm_x3_planes(xi_hi, bf16_feat ? nullptr : xi_hi + MR, R, ci, ci + (size_t)D * R, R, nullptr, ws + L.h_image, D, M,
-                                     D, R, st, psk, pskf));
+                                     D, R, st, psk.p, psk.floats));
     else if (bf16_feat)  // the bf16 image rows are read in place as the (only) plane of the A operand
-      DRIN_TRY(launch_gemm_x3_planes(b->entity_image, nullptr, R, ci, ci + (size_t)D * R, R, nullptr, ws + L.h_image, D, M, D, R, st, psk,
-                                     pskf));
+      DRIN_TRY(launch_gemm_x3_planes(b->entity_image, nullptr, R, ci, ci + (size_t)D * R, R, nullptr, ws + L.h_image, D, M, D, R, st, psk.p,
+                                     psk.floats));
     else
       DRIN_TRY(launch_gemm_nt_bf16x3(b->entity_image, R, pb + P.c_img, R, nullptr, ws + L.h_image, D, M, D, R, st, ci, ci + (size_t)D * R,
-                                     false, psk, pskf));
+                                     false, psk.p, psk.floats));
   } else {
     const float* x_t = tokens ? ws + L.xt : b->entity_text;
     DRIN_TRY(launch_gemm_nt(x_t, D, pb + P.c_txt, D, nullptr, ws + L.h_text, D, M, D, D, false, prec, st));
@@ -435,8 +475,8 @@ static int forward_prepared_on_stream(const drin_config* cfg, const drin_batch* 
   // mentions up - their share of that change: row kernels 1.385 -> 1.27 ms at 4 096 mentions; 64 mentions with whole-mention
   // workgroups 0.55 -> 0.63 ms, which is why small calls keep 16 candidates).
   // (6) layer-1 entity vertices + layer-2 mention aggregates
-  PairArgs pa;
-  memset(&pa, 0, sizeof(pa));
+  PairArgs pa = shaped_args<PairArgs>(*cfg);
+  set_vertex_fields(pa, *cfg);
   pa.h_text = ws + L.h_text;
   pa.h_image = ws + L.h_image;
   pa.hm = hmfu;
@@ -453,48 +493,11 @@ static int forward_prepared_on_stream(const drin_config* cfg, const drin_batch* 
     pa.et1_lo = e1_hi + MD;
   }
   pa.s2_part = ws + L.s2_part;
-  pa.B = B;
-  pa.N = N;
-  pa.D4 = D / 4;
   pa.chunks = L.chunks;
-  pa.ln_eps = cfg->layer_norm_eps;
-  pa.act_v = vertex_act(cfg);
   DRIN_TRY(launch_pair_layer1(pa, st));
-  // (7) layer-2 mention-text vertex
-  DRIN_TRY(launch_mention_input2(ws + L.s2_part, vm1, ws + L.agg2, B, D, N, L.chunks, st));
-  DRIN_TRY(launch_gemm_nt(ws + L.agg2, D, L2.w_h, D, L2.b_h, ws + L.mt2, D, B, D, D, false, prec, st, sk, skf, wp(P.p_wh2)));
-  DRIN_TRY(launch_layernorm_gelu(ws + L.mt2, L2.ln_weight, L2.ln_bias, ws + L.mt2, nullptr, nullptr, B, D, cfg->layer_norm_eps, st,
-                                 vertex_act(cfg)));
-  // (8) layer-2 entity-text contraction, vertex and score
-  float* h2 = ws + L.h_text;
-  // (Round 6, built and dropped - profiles/r6_full_row_ab.txt, tools/probes/r6_full_row/, commit 8a5bc6b: this contraction and k_pair_final's
-  //  arithmetic in ONE launch on 96-row x 768-column tiles, so that h2 never goes to HBM.  Correct, and slower: a full-row tile needs all
-  //  768 weight rows per K-step for 96 activation rows - 1.56 x the LDS-DMA instructions per MFMA of the 256 x 256 tile - and its K-loop
-  //  alone took what the 256 x 256 kernel takes including its store (1.20 against 1.15 ms); the epilogue's vector work came on top.)
-  if (planes) {
-    const __bf16* w2 = reinterpret_cast<const __bf16*>(pb + P.p_wh2);
-    DRIN_TRY(launch_gemm_x3_planes(e1_hi, e1_hi + MD, D, w2, w2 + (size_t)D * D, D, nullptr, h2, D, M, D, D, st, psk, pskf));
-  } else {
-    DRIN_TRY(launch_gemm_nt(ws + L.et1, D, L2.w_h, D, nullptr, h2, D, M, D, D, false, prec, st));
-  }
-  FinalArgs fa;
-  memset(&fa, 0, sizeof(fa));
-  fa.h2 = h2;
-  fa.hm2 = ws + L.hm2;
-  fa.b_h2 = L2.b_h;
-  fa.gamma = L2.ln_weight;
-  fa.beta = L2.ln_bias;
-  fa.e1m = ws + L.e1m;
-  fa.mt2 = ws + L.mt2;
-  fa.scores = scores;
-  fa.B = B;
-  fa.N = N;
-  fa.D4 = D / 4;
-  fa.chunks = L.chunks;
-  fa.ln_eps = cfg->layer_norm_eps;
-  fa.act_v = vertex_act(cfg);
-  fa.cos_eps = cfg->cosine_eps;
-  return launch_pair_final(fa, st);
+  // (7), (8) layer 2; its contraction writes over h_text
+  return run_folded_tail(cfg, params, pb, P, L.chunks, ws + L.s2_part, vm1, ws + L.agg2, ws + L.mt2, ws + L.hm2, ws + L.e1m, ws + L.h_text,
+                         planes ? nullptr : ws + L.et1, planes ? e1_hi : nullptr, planes, msk, psk, scores, st);
 }
 
 }  // namespace drin

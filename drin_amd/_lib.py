@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # DRIN_LIB_PATH: another build of the same library (the sanitizer build of `python -m drin_amd.build --asan-host`)
 LIB_PATH = os.environ.get("DRIN_LIB_PATH") or os.path.join(_HERE, "libdrin_hip.so")
 MAX_LAYERS = 8
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 OK, E_SHAPE, E_NULL, E_ALIGN, E_WORKSPACE, E_HIP, E_UNSUPPORTED, E_INDEX = 0, -1, -2, -3, -4, -5, -6, -7
 PREC_F32, PREC_BF16X3, PREC_BF16X3_ALL, PREC_BF16X3_IF16 = 0, 1, 3, 5     # (2 and 4: removed with ABI 6 - outside the 1e-4 bar)
@@ -96,6 +96,31 @@ class DrinMelhiParamGradsC(C.Structure):  # same shape, mutable pointers
     _fields_ = DrinMelhiParamsC._fields_
 
 
+class DrinGhmfcConfigC(C.Structure):
+    _fields_ = [("batch", C.c_int32), ("num_candidates", C.c_int32), ("embed_dim", C.c_int32), ("image_dim", C.c_int32),
+                ("mention_tokens", C.c_int32), ("image_regions", C.c_int32), ("num_heads", C.c_int32),
+                ("entity_tokens", C.c_int32), ("precision", C.c_int32), ("layer_norm_eps", C.c_float), ("cosine_eps", C.c_float)]
+
+
+class DrinGhmfcBatchC(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("mention_feature", "mention_mask", "mention_image", "entity_feature", "entity_mask")]
+
+
+GHMFC_CROSS_PARAMS = ("a2b_wq", "a2b_wk", "a2b_wv", "a2b_in_bias", "a2b_wo", "a2b_bo", "a2b_ffn_w", "a2b_ffn_b", "b2a_in_w",
+                      "b2a_in_bias", "b2a_wo", "b2a_bo", "b2a_ffn_w", "b2a_ffn_b", "ln0_w", "ln0_b", "ln1_w", "ln1_b", "ln2_w",
+                      "ln2_b", "ln3_w", "ln3_b")
+
+
+class DrinGhmfcCrossParamsC(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in GHMFC_CROSS_PARAMS]
+
+
+class DrinGhmfcParamsC(C.Structure):   # the 52 state-dict tensors, in state-dict order
+    _fields_ = [("t2v", DrinGhmfcCrossParamsC), ("v2t", DrinGhmfcCrossParamsC)] + [(n, C.c_void_p) for n in (
+        "w_text_linear", "b_text_linear", "w_image_linear", "b_image_linear", "w_score_linear", "b_score_linear", "w_entity",
+        "b_entity")]
+
+
 class DrinTraceC(C.Structure):
     _fields_ = [(n, C.c_void_p * (MAX_LAYERS + 1)) for n in (
         "mention_text_vertex", "mention_image_vertex", "entity_text_vertex", "entity_image_vertex", "edges")]
@@ -157,11 +182,16 @@ EXPORTS = {
     "drin_melhi_backward": (C.c_int, [C.POINTER(DrinMelhiConfigC), C.POINTER(DrinMelhiBatchC), C.POINTER(DrinMelhiParamsC),
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(DrinMelhiParamGradsC),
                                       C.c_void_p]),
+    "drin_ghmfc_workspace_bytes": (C.c_size_t, [C.POINTER(DrinGhmfcConfigC)]),
+    "drin_ghmfc_forward": (C.c_int, [C.POINTER(DrinGhmfcConfigC), C.POINTER(DrinGhmfcBatchC), C.POINTER(DrinGhmfcParamsC), C.c_void_p,
+                                     C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "drin_attention": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                 C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "drin_profile_begin": (C.c_int, [C.c_int]),
     "drin_profile_end": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "drin_kernel_class_name": (C.c_char_p, [C.c_int]),
 }
-KERNEL_CLASSES = 10
+KERNEL_CLASSES = 12
 
 
 class DrinError(RuntimeError):

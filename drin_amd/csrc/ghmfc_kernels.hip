@@ -1,0 +1,509 @@
+// The GHMFC baseline of the reference (baselines/ghmfc.py, model_type "ghmfc") on gfx950, eval-mode scoring only: the
+// softmax-attention core, LayerNorm with a fused residual, the max over a sequence, the gated mix, and the entry points
+// drin_attention / drin_ghmfc_*.  What the reference computes and how the launches are laid out: DESIGN.md section 15.
+//
+// Every x W^T + b goes through launch_gemm_nt (the GEMM module picks the kernel); the kernels here are everything else.
+// No atomics, no scratch, at most 53 KB of static LDS per workgroup: the same bits every run.
+#include "device_utils.h"
+#include "internal.h"
+#include "row_ops.h"
+
+namespace drin {
+namespace {
+
+// ---- softmax attention (ghmfc.py:120,124: nn.MultiheadAttention -> scaled_dot_product_attention) ----------------------
+// One workgroup per (mention, head, 16 query rows): wave w owns query rows 4 w .. 4 w + 3.  Keys go through LDS in tiles
+// of KT (64 when the padded head dim is <= 128, else 32: fp32 K and V of one (mention, head) at Lk = 128, dh = 256 are
+// 256 KB) with a running max and sum per query row; K and V of a tile take turns in ONE buffer.
+//   scores: lane = key.  K rows sit at a stride of 4 * odd floats, so the 16 lanes of a ds_read_b128 group (each group is a
+//           complete residue set mod 16, MI355X_MICROARCH.md) meet 16 different bank quads; the q values are broadcast reads.
+//           With KT = 32 the two half-waves take two query rows each.
+//   p V:    lane = output column (lane, lane + 64, ...: consecutive banks), p of the four rows is one broadcast float4 per key.
+// q is staged multiplied by log2(e) / sqrt(dh): the exponentials are exp2.  A key is dropped when mask[b, key] == 0; a row
+// with no kept key keeps l = 0 and writes zeros (what torch's kernel gives for an all-masked row: zero weights).
+constexpr int kAttnRows = 4, kAttnWaves = 4, kAttnQT = kAttnRows * kAttnWaves;
+constexpr int kAttnMaxDh = 256, kAttnMaxLk = 512;
+constexpr int kAttnKvFloats = 64 * 132;   // 64 keys x (128 + 4) >= 32 keys x (256 + 4)
+
+template <int CTRL>
+__device__ __forceinline__ float dpp_max_self(float v) {   // every lane of these four controls has a source lane: no fill value
+  const int b = __builtin_bit_cast(int, v);
+  return fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(b, b, CTRL, 0xF, 0xF, false)));
+}
+__device__ __forceinline__ float wave_max_any(float v) {   // max over the 64 lanes of any values (-inf included)
+  v = dpp_max_self<0xB1>(v);
+  v = dpp_max_self<0x4E>(v);
+  v = dpp_max_self<0x141>(v);
+  v = dpp_max_self<0x140>(v);
+  const int b = __builtin_bit_cast(int, v);
+  const float r0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 0));
+  const float r1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 16));
+  const float r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 32));
+  const float r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 48));
+  return fmaxf(fmaxf(r0, r1), fmaxf(r2, r3));
+}
+
+// `valid` rows x dh columns of a row-major global block -> LDS rows of stride ds, times mul; rows valid .. rows - 1 and the
+// columns dh .. dhp - 1 are zero.  vec: dh % 4 == 0 and the source rows are 16-byte aligned.
+__device__ __forceinline__ void stage_rows(float* dst, int ds, const float* src, int64_t ld, int rows, int valid, int dh, int dhp,
+                                           bool vec, float mul) {
+  if (vec) {
+    const int n4 = dh >> 2;
+    for (int i = threadIdx.x; i < rows * n4; i += 256) {
+      const int r = i / n4, c4 = i - r * n4;
+      const float4 x = r < valid ? ld4(src + r * ld + c4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+      st4(dst + r * ds + c4 * 4, x * mul);
+    }
+  } else {
+    for (int i = threadIdx.x; i < rows * dhp; i += 256) {
+      const int r = i / dhp, c = i - r * dhp;
+      dst[r * ds + c] = (r < valid && c < dh) ? src[r * ld + c] * mul : 0.f;
+    }
+  }
+}
+
+template <int KT>
+__global__ void __launch_bounds__(256) k_attention(const float* __restrict__ q, int64_t ldq, const float* __restrict__ k, int64_t ldk,
+                                                   const float* __restrict__ v, int64_t ldv, const int64_t* __restrict__ mask,
+                                                   float* __restrict__ out, int64_t ldo, int Lq, int Lk, int dh, float q_scale,
+                                                   int vec) {
+  constexpr int G = 64 / KT;             // half-waves of the score phase
+  constexpr int RPL = kAttnRows / G;     // query rows per lane there
+  __shared__ __attribute__((aligned(16))) float kv[kAttnKvFloats];
+  __shared__ __attribute__((aligned(16))) float qs[kAttnQT * kAttnMaxDh];
+  __shared__ __attribute__((aligned(16))) float ps[kAttnWaves * 64 * kAttnRows];   // [wave][key][row]
+  const int b = blockIdx.z, h = blockIdx.y, q0 = blockIdx.x * kAttnQT;
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int dhp = (dh + 3) & ~3;
+  const int ks = 4 * ((dhp >> 2) | 1);
+  const float ninf = -__builtin_inff();
+  const int q_valid = Lq - q0 < kAttnQT ? Lq - q0 : kAttnQT;
+  stage_rows(qs, dhp, q + ((int64_t)b * Lq + q0) * ldq + (int64_t)h * dh, ldq, kAttnQT, q_valid, dh, dhp, vec != 0, q_scale);
+  k += (int64_t)b * Lk * ldk + (int64_t)h * dh;
+  v += (int64_t)b * Lk * ldv + (int64_t)h * dh;
+  if (mask != nullptr) mask += (int64_t)b * Lk;
+
+  float m[kAttnRows], l[kAttnRows], acc[kAttnRows][4];
+#pragma unroll
+  for (int r = 0; r < kAttnRows; ++r) {
+    m[r] = ninf, l[r] = 0.f;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) acc[r][s] = 0.f;
+  }
+  const int g = G == 1 ? 0 : lane / KT, j = lane & (KT - 1);
+  const float* qg = qs + (w * kAttnRows + g * RPL) * dhp;
+  const float* kr = kv + j * ks;
+  float* pw = ps + w * 64 * kAttnRows;
+
+  for (int j0 = 0; j0 < Lk; j0 += KT) {
+    const int jn = Lk - j0 < KT ? Lk - j0 : KT;
+    __syncthreads();   // the previous tile's V has been read (first tile: nothing)
+    stage_rows(kv, ks, k + j0 * ldk, ldk, jn, jn, dh, dhp, vec != 0, 1.0f);
+    __syncthreads();   // K (and, the first time, q) are in LDS
+    float s[RPL];
+#pragma unroll
+    for (int rr = 0; rr < RPL; ++rr) s[rr] = 0.f;
+    for (int c = 0; c < dhp; c += 4) {
+      const float4 kk = ld4(kr + c);
+#pragma unroll
+      for (int rr = 0; rr < RPL; ++rr) {
+        const float4 qq = ld4(qg + rr * dhp + c);
+        s[rr] = fmaf(qq.x, kk.x, fmaf(qq.y, kk.y, fmaf(qq.z, kk.z, fmaf(qq.w, kk.w, s[rr]))));
+      }
+    }
+    const bool keep = j < jn && (mask == nullptr || mask[j0 + j] != 0);
+    float p[kAttnRows];
+#pragma unroll
+    for (int r = 0; r < kAttnRows; ++r) {
+      const float sr = (keep && r / RPL == g) ? s[r % RPL] : ninf;   // rows of the other half-wave: no part in this lane
+      const float mn = fmaxf(m[r], wave_max_any(sr));
+      const bool none = mn == ninf;                                 // no kept key so far
+      const float alpha = none ? 1.0f : exp2f(m[r] - mn);
+      p[r] = none ? 0.f : exp2f(sr - mn);
+      l[r] = fmaf(l[r], alpha, wave_sum(p[r]));
+      m[r] = mn;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) acc[r][c] *= alpha;
+    }
+#pragma unroll
+    for (int rr = 0; rr < RPL; ++rr)   // (p of the other half-wave's rows is exactly 0 in this lane: the sum is a select)
+      pw[j * kAttnRows + g * RPL + rr] = G == 2 ? p[rr] + p[(RPL + rr) % kAttnRows] : p[rr];
+    __syncthreads();   // every wave is through with K; p of this wave is in LDS
+    stage_rows(kv, dh, v + j0 * ldv, ldv, jn, jn, dh, dh, vec != 0, 1.0f);
+    __syncthreads();
+    for (int jj = 0; jj < jn; ++jj) {
+      const float4 pp = ld4(pw + jj * kAttnRows);
+      const float* vr = kv + jj * dh + lane;
+#pragma unroll
+      for (int c = 0; c < 4; ++c)
+        if (64 * c < dh) {   // uniform; a lane past dh in the last slot reads inside kv and is never stored
+          const float vv = vr[64 * c];
+          acc[0][c] = fmaf(pp.x, vv, acc[0][c]);
+          acc[1][c] = fmaf(pp.y, vv, acc[1][c]);
+          acc[2][c] = fmaf(pp.z, vv, acc[2][c]);
+          acc[3][c] = fmaf(pp.w, vv, acc[3][c]);
+        }
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < kAttnRows; ++r) {
+    const int row = q0 + w * kAttnRows + r;
+    if (row >= Lq) continue;
+    const float inv = l[r] > 0.f ? 1.0f / l[r] : 0.f;
+    float* o = out + ((int64_t)b * Lq + row) * ldo + (int64_t)h * dh;
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      if (lane + 64 * c < dh) o[lane + 64 * c] = acc[r][c] * inv;
+  }
+}
+
+// ---- y = LayerNorm(x [+ res]) (ghmfc.py:121-127), one wave per row, the row in registers (row_ops.h) -------------------
+// y may be x or res: a wave holds its whole row before it stores.
+template <int DV>
+__global__ void __launch_bounds__(256) k_layernorm_res(const float* x, const float* res, const float* __restrict__ gamma,
+                                                       const float* __restrict__ beta, float* y, int64_t rows, int E4, float eps) {
+  const int lane = threadIdx.x & 63;
+  const float inv_e = 1.0f / (float)(E4 * 4);
+  for (int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); row < rows; row += (int64_t)gridDim.x * 4) {
+    Row<DV> h = load_row<DV>(x + row * E4 * 4, lane, E4);
+    if (res != nullptr) {
+      const Row<DV> r = load_row<DV>(res + row * E4 * 4, lane, E4);
+#pragma unroll
+      for (int jj = 0; jj < DV; ++jj) h.v[jj] = h.v[jj] + r.v[jj];
+    }
+    float s = 0.f;
+#pragma unroll
+    for (int jj = 0; jj < DV; ++jj) s += (h.v[jj].x + h.v[jj].y) + (h.v[jj].z + h.v[jj].w);
+    const float mu = wave_sum(s) * inv_e;
+    float qv = 0.f;
+#pragma unroll
+    for (int jj = 0; jj < DV; ++jj)
+      if (lane + 64 * jj < E4) {
+        const float dx = h.v[jj].x - mu, dy = h.v[jj].y - mu, dz = h.v[jj].z - mu, dw = h.v[jj].w - mu;
+        qv += (dx * dx + dy * dy) + (dz * dz + dw * dw);
+      }
+    const float rstd = 1.0f / sqrtf(wave_sum(qv) * inv_e + eps);
+#pragma unroll
+    for (int jj = 0; jj < DV; ++jj) {
+      const int c4 = lane + 64 * jj;
+      if (c4 < E4) {
+        const float4 gm = ld4(gamma + c4 * 4), bt = ld4(beta + c4 * 4);
+        h.v[jj] = make_float4(fmaf((h.v[jj].x - mu) * rstd, gm.x, bt.x), fmaf((h.v[jj].y - mu) * rstd, gm.y, bt.y),
+                              fmaf((h.v[jj].z - mu) * rstd, gm.z, bt.z), fmaf((h.v[jj].w - mu) * rstd, gm.w, bt.w));
+      }
+    }
+    store_row<DV>(y + row * E4 * 4, h, lane, E4);
+  }
+}
+
+// ---- out[b, :] = max over ALL s of x[b, s, :] (ghmfc.py:143,145: padded positions take part; a NaN wins, as torch.max) ----
+// grid (cdiv(E4, 64), B): thread (column quad, row group of four), the four groups meet in LDS.
+__device__ __forceinline__ float max_nan(float a, float b) { return (b > a || b != b) ? b : a; }
+__global__ void __launch_bounds__(256) k_seq_max(const float* __restrict__ x, float* __restrict__ out, int S, int E4) {
+  __shared__ float4 part[4][64];
+  const int c4 = blockIdx.x * 64 + (threadIdx.x & 63), rg = threadIdx.x >> 6;
+  const int64_t b = blockIdx.y;
+  const float ninf = -__builtin_inff();
+  float4 mx = make_float4(ninf, ninf, ninf, ninf);
+  if (c4 < E4)
+    for (int s = rg; s < S; s += 4) {
+      const float4 t = ld4(x + ((b * S + s) * E4 + c4) * 4);
+      mx = make_float4(max_nan(mx.x, t.x), max_nan(mx.y, t.y), max_nan(mx.z, t.z), max_nan(mx.w, t.w));
+    }
+  part[rg][threadIdx.x & 63] = mx;
+  __syncthreads();
+  if (rg != 0 || c4 >= E4) return;
+#pragma unroll
+  for (int i = 1; i < 4; ++i) {
+    const float4 t = part[i][threadIdx.x];
+    mx = make_float4(max_nan(mx.x, t.x), max_nan(mx.y, t.y), max_nan(mx.z, t.z), max_nan(mx.w, t.w));
+  }
+  st4(out + (b * E4 + c4) * 4, mx);
+}
+
+// ---- the gate (ghmfc.py:144-149): t = gelu(tl), v = gelu(vl), s = softmax(score_linear([t | v])), out = s0 t + s1 v ----------
+// One wave per mention; tl / vl are the outputs of text_linear / image_linear, ws [2, 2 D] and bs [2] the score Linear.
+__global__ void __launch_bounds__(256) k_gate_mix(const float* __restrict__ tl, const float* __restrict__ vl, const float* __restrict__ ws,
+                                                  const float* __restrict__ bs, float* __restrict__ out, int B, int D4) {
+  const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= B) return;
+  const int lane = threadIdx.x & 63;
+  const int64_t D = (int64_t)D4 * 4;
+  auto gelu4 = [](float4 a) { return make_float4(gelu_erf(a.x), gelu_erf(a.y), gelu_erf(a.z), gelu_erf(a.w)); };
+  float z0 = 0.f, z1 = 0.f;
+  for (int c4 = lane; c4 < D4; c4 += 64) {
+    const float4 t = gelu4(ld4(tl + b * D + c4 * 4)), v = gelu4(ld4(vl + b * D + c4 * 4));
+    z0 += dot4(t, ld4(ws + c4 * 4)) + dot4(v, ld4(ws + D + c4 * 4));
+    z1 += dot4(t, ld4(ws + 2 * D + c4 * 4)) + dot4(v, ld4(ws + 3 * D + c4 * 4));
+  }
+  z0 = wave_sum(z0) + bs[0];
+  z1 = wave_sum(z1) + bs[1];
+  const float zm = fmaxf(z0, z1);
+  const float e0 = expf(z0 - zm), e1 = expf(z1 - zm);
+  const float s0 = e0 / (e0 + e1), s1 = e1 / (e0 + e1);
+  for (int c4 = lane; c4 < D4; c4 += 64) {
+    const float4 t = gelu4(ld4(tl + b * D + c4 * 4)), v = gelu4(ld4(vl + b * D + c4 * 4));
+    st4(out + b * D + c4 * 4, fma4(s0, t, v * s1));
+  }
+}
+
+template <typename F>
+int timed(int cls, hipStream_t st, const char* what, F&& launch) {
+  KernelTimer timer(cls, st);
+  launch();
+  DRIN_CHECK_LAUNCH(what);
+  return DRIN_OK;
+}
+
+// ---- launchers ------------------------------------------------------------------------------------------
+int check_attention_shape(int64_t B, int H, int Lq, int Lk, int dh) {
+  if (B < 1 || B > 65535 || H < 1 || H > 65535 || Lq < 1 || Lk < 1 || Lk > kAttnMaxLk || dh < 1 || dh > kAttnMaxDh) {
+    set_error("attention: batch and heads in [1, 65535], q_len >= 1, k_len in [1, %d], head_dim in [1, %d] (got B=%lld H=%d Lq=%d Lk=%d dh=%d)",
+              kAttnMaxLk, kAttnMaxDh, (long long)B, H, Lq, Lk, dh);
+    return DRIN_E_SHAPE;
+  }
+  return DRIN_OK;
+}
+
+int launch_attention(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv, const int64_t* mask,
+                     float* out, int64_t ldo, int B, int H, int Lq, int Lk, int dh, hipStream_t st) {
+  DRIN_TRY(check_attention_shape(B, H, Lq, Lk, dh));
+  const int64_t E = (int64_t)H * dh;
+  if (ldq < E || ldk < E || ldv < E || ldo < E) {
+    set_error("attention: row strides (%lld, %lld, %lld, %lld) must be >= heads * head_dim = %lld", (long long)ldq, (long long)ldk,
+              (long long)ldv, (long long)ldo, (long long)E);
+    return DRIN_E_SHAPE;
+  }
+  const bool vec = dh % 4 == 0 && ldq % 4 == 0 && ldk % 4 == 0 && ldv % 4 == 0 && aligned16(q) && aligned16(k) && aligned16(v);
+  const float q_scale = 1.44269504088896340736f / sqrtf((float)dh);
+  const dim3 grid((unsigned)cdiv(Lq, kAttnQT), (unsigned)H, (unsigned)B);
+  return timed(DRIN_KC_ATTN, st, "k_attention", [&] {
+    if (((dh + 3) & ~3) <= 128)
+      hipLaunchKernelGGL(k_attention<64>, grid, dim3(256), 0, st, q, ldq, k, ldk, v, ldv, mask, out, ldo, Lq, Lk, dh, q_scale, (int)vec);
+    else
+      hipLaunchKernelGGL(k_attention<32>, grid, dim3(256), 0, st, q, ldq, k, ldk, v, ldv, mask, out, ldo, Lq, Lk, dh, q_scale, (int)vec);
+  });
+}
+
+constexpr int kLnMaxWidth = 2048;   // Row<8>
+int launch_layernorm_res(const float* x, const float* res, const float* gamma, const float* beta, float* y, int64_t rows, int E,
+                         float eps, hipStream_t st) {
+  if (rows <= 0) return DRIN_OK;
+  if (E % 4 || E <= 0 || E > kLnMaxWidth) {
+    set_error("layernorm_res: width %d must be a multiple of 4 in [4, %d]", E, kLnMaxWidth);
+    return DRIN_E_SHAPE;
+  }
+  const int E4 = E / 4;
+  const dim3 grid((unsigned)(cdiv(rows, 4) < 65535 * 16 ? cdiv(rows, 4) : 65535 * 16));
+  return timed(DRIN_KC_NORM, st, "k_layernorm_res", [&] {
+    if (E4 <= 64)
+      hipLaunchKernelGGL(k_layernorm_res<1>, grid, dim3(256), 0, st, x, res, gamma, beta, y, rows, E4, eps);
+    else if (E4 <= 128)
+      hipLaunchKernelGGL(k_layernorm_res<2>, grid, dim3(256), 0, st, x, res, gamma, beta, y, rows, E4, eps);
+    else if (E4 <= 256)
+      hipLaunchKernelGGL(k_layernorm_res<4>, grid, dim3(256), 0, st, x, res, gamma, beta, y, rows, E4, eps);
+    else
+      hipLaunchKernelGGL(k_layernorm_res<8>, grid, dim3(256), 0, st, x, res, gamma, beta, y, rows, E4, eps);
+  });
+}
+
+int launch_seq_max(const float* x, float* out, int B, int S, int E, hipStream_t st) {
+  return timed(DRIN_KC_NORM, st, "k_seq_max", [&] {
+    hipLaunchKernelGGL(k_seq_max, dim3((unsigned)cdiv(E / 4, 64), (unsigned)B), dim3(256), 0, st, x, out, S, E / 4);
+  });
+}
+
+int launch_gate_mix(const float* tl, const float* vl, const float* ws, const float* bs, float* out, int B, int D, hipStream_t st) {
+  return timed(DRIN_KC_NORM, st, "k_gate_mix", [&] {
+    hipLaunchKernelGGL(k_gate_mix, dim3((unsigned)cdiv(B, 4)), dim3(256), 0, st, tl, vl, ws, bs, out, B, D / 4);
+  });
+}
+
+// ---- the forward pass ------------------------------------------------------------------------------------
+constexpr int kChunk = 256;   // mentions per pass over the workspace
+
+struct GhmfcLayout {
+  size_t a, b, kv, pool_t, pool_v, tl, vl, men, epool, ent, total_floats;   // offsets in floats
+  void build(const drin_ghmfc_config& c) {
+    const size_t Bc = c.batch < kChunk ? c.batch : kChunk, N = c.num_candidates, D = c.embed_dim, R = c.image_dim;
+    const size_t L = c.mention_tokens, P = c.image_regions;
+    size_t o = 0;
+    auto take = [&](size_t n) {
+      const size_t at = o;
+      o += (n + 63) & ~(size_t)63;   // 256-byte aligned pieces
+      return at;
+    };
+    auto mx = [](size_t x, size_t y) { return x > y ? x : y; };
+    const size_t rows = mx(L * D, P * R);
+    a = take(Bc * rows), b = take(Bc * rows);
+    kv = take(Bc * 2 * mx(mx(L, P) * D, mx(L, P) * R));
+    pool_t = take(Bc * D), pool_v = take(Bc * R), tl = take(Bc * D), vl = take(Bc * D), men = take(Bc * D);
+    epool = take(c.entity_tokens > 0 ? Bc * N * D : 0), ent = take(Bc * N * D);
+    total_floats = o;
+  }
+};
+
+int validate_ghmfc_config(const drin_ghmfc_config* c) {
+  if (!c) {
+    set_error("ghmfc config is NULL");
+    return DRIN_E_NULL;
+  }
+  if (c->batch <= 0 || c->batch > (1 << 20) || c->num_candidates <= 0 || c->num_candidates > 65535 || c->embed_dim <= 0 ||
+      c->image_dim <= 0 || c->mention_tokens <= 0 || c->image_regions <= 0 || c->num_heads <= 0 || c->entity_tokens < 0) {
+    set_error("ghmfc config: batch in [1, 2^20], num_candidates in [1, 65535], widths, token counts and heads >= 1, entity_tokens >= 0 "
+              "(got B=%d N=%d D=%d R=%d L=%d P=%d H=%d T=%d)", c->batch, c->num_candidates, c->embed_dim, c->image_dim,
+              c->mention_tokens, c->image_regions, c->num_heads, c->entity_tokens);
+    return DRIN_E_SHAPE;
+  }
+  if (c->embed_dim % 4 || c->image_dim % 4) {
+    set_error("ghmfc config: embed_dim=%d and image_dim=%d must be multiples of 4 (16-byte lane accesses)", c->embed_dim, c->image_dim);
+    return DRIN_E_SHAPE;
+  }
+  if (c->embed_dim % c->num_heads || c->image_dim % c->num_heads) {
+    set_error("ghmfc config: embed_dim=%d and image_dim=%d must be divisible by num_heads=%d", c->embed_dim, c->image_dim, c->num_heads);
+    return DRIN_E_SHAPE;
+  }
+  if (c->embed_dim / c->num_heads > kAttnMaxDh || c->image_dim / c->num_heads > kAttnMaxDh) {
+    set_error("ghmfc config: head dims %d and %d exceed %d", c->embed_dim / c->num_heads, c->image_dim / c->num_heads, kAttnMaxDh);
+    return DRIN_E_UNSUPPORTED;
+  }
+  if (c->mention_tokens > kAttnMaxLk || c->image_regions > kAttnMaxLk || c->entity_tokens > kAttnMaxLk) {
+    set_error("ghmfc config: mention_tokens=%d, image_regions=%d and entity_tokens=%d must be <= %d", c->mention_tokens,
+              c->image_regions, c->entity_tokens, kAttnMaxLk);
+    return DRIN_E_UNSUPPORTED;
+  }
+  if (c->embed_dim > kLnMaxWidth || c->image_dim > kLnMaxWidth) {
+    set_error("ghmfc config: embed_dim=%d and image_dim=%d must be <= %d (LayerNorm keeps a row in registers)", c->embed_dim,
+              c->image_dim, kLnMaxWidth);
+    return DRIN_E_UNSUPPORTED;
+  }
+  if (c->precision != DRIN_PREC_F32 && c->precision != DRIN_PREC_BF16X3) {
+    set_error("ghmfc config: precision %d is not DRIN_PREC_F32 / DRIN_PREC_BF16X3", c->precision);
+    return DRIN_E_UNSUPPORTED;
+  }
+  return DRIN_OK;
+}
+
+// CrossAttention(dim_a = Ea, dim_b = Eb)(seq_a, mask_a, seq_b, mask_b) followed by the max over the La positions
+// (ghmfc.py:114-128, :143 / :145).  A, Bf: [Bc La, Ea] row buffers, KV: [Bc max(La, Lb), 2 Ea].  A NULL mask keeps every key.
+int cross_attention_max(const drin_ghmfc_cross_params& W, const float* sa, const int64_t* ma, int La, int Ea, const float* sb,
+                        const int64_t* mb, int Lb, int Eb, int Bc, int H, float* A, float* Bf, float* KV, float* pooled, int prec,
+                        float eps, hipStream_t st) {
+  const int64_t Ma = (int64_t)Bc * La, Mb = (int64_t)Bc * Lb;
+  const int dh = Ea / H;
+  auto gemm = [&](const float* x, int64_t ldx, const float* w, const float* bias, float* y, int64_t ldy, int64_t M, int N, int K) {
+    return launch_gemm_nt(x, ldx, w, K, bias, y, ldy, M, N, K, false, prec, st);
+  };
+  // a attends to b: separate q / k / v weights (kdim = vdim = Eb), one in_proj_bias [3 Ea]; K | V side by side
+  DRIN_TRY(gemm(sa, Ea, W.a2b_wq, W.a2b_in_bias, A, Ea, Ma, Ea, Ea));
+  DRIN_TRY(gemm(sb, Eb, W.a2b_wk, W.a2b_in_bias + Ea, KV, 2 * (int64_t)Ea, Mb, Ea, Eb));
+  DRIN_TRY(gemm(sb, Eb, W.a2b_wv, W.a2b_in_bias + 2 * Ea, KV + Ea, 2 * (int64_t)Ea, Mb, Ea, Eb));
+  DRIN_TRY(launch_attention(A, Ea, KV, 2 * (int64_t)Ea, KV + Ea, 2 * (int64_t)Ea, mb, Bf, Ea, Bc, H, La, Lb, dh, st));
+  DRIN_TRY(gemm(Bf, Ea, W.a2b_wo, W.a2b_bo, A, Ea, Ma, Ea, Ea));
+  DRIN_TRY(launch_layernorm_res(A, nullptr, W.ln0_w, W.ln0_b, A, Ma, Ea, eps, st));
+  DRIN_TRY(gemm(A, Ea, W.a2b_ffn_w, W.a2b_ffn_b, Bf, Ea, Ma, Ea, Ea));
+  DRIN_TRY(launch_layernorm_res(Bf, A, W.ln1_w, W.ln1_b, A, Ma, Ea, eps, st));
+  // the result attends to a: packed in_proj_weight [3 Ea, Ea]; K | V of seq_a are its rows Ea .. 3 Ea, ONE product
+  DRIN_TRY(gemm(A, Ea, W.b2a_in_w, W.b2a_in_bias, Bf, Ea, Ma, Ea, Ea));
+  DRIN_TRY(gemm(sa, Ea, W.b2a_in_w + (int64_t)Ea * Ea, W.b2a_in_bias + Ea, KV, 2 * (int64_t)Ea, Ma, 2 * Ea, Ea));
+  DRIN_TRY(launch_attention(Bf, Ea, KV, 2 * (int64_t)Ea, KV + Ea, 2 * (int64_t)Ea, ma, A, Ea, Bc, H, La, La, dh, st));
+  DRIN_TRY(gemm(A, Ea, W.b2a_wo, W.b2a_bo, Bf, Ea, Ma, Ea, Ea));
+  DRIN_TRY(launch_layernorm_res(Bf, nullptr, W.ln2_w, W.ln2_b, Bf, Ma, Ea, eps, st));
+  DRIN_TRY(gemm(Bf, Ea, W.b2a_ffn_w, W.b2a_ffn_b, A, Ea, Ma, Ea, Ea));
+  DRIN_TRY(launch_layernorm_res(A, Bf, W.ln3_w, W.ln3_b, A, Ma, Ea, eps, st));
+  return launch_seq_max(A, pooled, Bc, La, Ea, st);
+}
+
+}  // namespace
+}  // namespace drin
+
+using namespace drin;
+
+int drin_attention(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv, const int64_t* key_mask,
+                   float* out, int64_t ldo, int32_t batch, int32_t num_heads, int32_t q_len, int32_t k_len, int32_t head_dim,
+                   void* stream) {
+  DRIN_TRY(check_attention_shape(batch, num_heads, q_len, k_len, head_dim));
+  if (!q || !k || !v || !out) {
+    set_error("drin_attention: q / k / v / out is NULL");
+    return DRIN_E_NULL;
+  }
+  DRIN_BIND_DEVICE(stream, out, "drin_attention");
+  return launch_attention(q, ldq, k, ldk, v, ldv, key_mask, out, ldo, batch, num_heads, q_len, k_len, head_dim, (hipStream_t)stream);
+}
+
+size_t drin_ghmfc_workspace_bytes(const drin_ghmfc_config* cfg) {
+  if (validate_ghmfc_config(cfg) != DRIN_OK) return 0;
+  GhmfcLayout W;
+  W.build(*cfg);
+  return W.total_floats * sizeof(float);
+}
+
+int drin_ghmfc_forward(const drin_ghmfc_config* cfg, const drin_ghmfc_batch* bt, const drin_ghmfc_params* p, void* workspace,
+                       size_t workspace_bytes, float* scores, float* mention_repr, void* stream) {
+  DRIN_TRY(validate_ghmfc_config(cfg));
+  if (!bt || !p || !workspace || !scores) {
+    set_error("drin_ghmfc_forward: batch / params / workspace / scores is NULL");
+    return DRIN_E_NULL;
+  }
+  const drin_ghmfc_config& c = *cfg;
+  if (!bt->mention_feature || !bt->mention_mask || !bt->mention_image || !bt->entity_feature || (c.entity_tokens > 0 && !bt->entity_mask)) {
+    set_error("drin_ghmfc_forward: a batch tensor is NULL (entity_mask is read when entity_tokens > 0)");
+    return DRIN_E_NULL;
+  }
+  static_assert(sizeof(drin_ghmfc_params) == 52 * sizeof(const float*), "the 52 state-dict tensors, nothing else");
+  const float* const* tensors = reinterpret_cast<const float* const*>(p);
+  for (int i = 0; i < 52; ++i) {
+    if (!tensors[i]) {
+      set_error("drin_ghmfc_forward: parameter %d (state-dict order) is NULL", i);
+      return DRIN_E_NULL;
+    }
+    if (!aligned16(tensors[i])) {
+      set_error("drin_ghmfc_forward: parameter %d (state-dict order) is not 16-byte aligned", i);
+      return DRIN_E_ALIGN;
+    }
+  }
+  GhmfcLayout W;
+  W.build(c);
+  if (workspace_bytes < W.total_floats * sizeof(float)) {
+    set_error("drin_ghmfc_forward: workspace %zu bytes < %zu", workspace_bytes, W.total_floats * sizeof(float));
+    return DRIN_E_WORKSPACE;
+  }
+  if (!aligned16(workspace) || !aligned16(bt->mention_feature) || !aligned16(bt->mention_image) || !aligned16(bt->entity_feature) ||
+      (mention_repr && !aligned16(mention_repr))) {
+    set_error("drin_ghmfc_forward: workspace, feature tensors and mention_repr must be 16-byte aligned");
+    return DRIN_E_ALIGN;
+  }
+  DRIN_BIND_DEVICE(stream, scores, "drin_ghmfc_forward");
+  RoctxRange range("drin_ghmfc_forward");
+  hipStream_t st = (hipStream_t)stream;
+  float* ws = static_cast<float*>(workspace);
+  const int N = c.num_candidates, D = c.embed_dim, R = c.image_dim, L = c.mention_tokens, P = c.image_regions, H = c.num_heads;
+  const int T = c.entity_tokens, prec = c.precision;
+  // rows are independent: the chunking changes no result
+  for (int b0 = 0; b0 < c.batch; b0 += kChunk) {
+    const int Bc = c.batch - b0 < kChunk ? c.batch - b0 : kChunk;
+    const float* text = bt->mention_feature + (int64_t)b0 * L * D;
+    const int64_t* tmask = bt->mention_mask + (int64_t)b0 * L;
+    const float* image = bt->mention_image + (int64_t)b0 * P * R;
+    // MultimodalFusion (ghmfc.py:141-149); the image mask is all ones: NULL
+    DRIN_TRY(cross_attention_max(p->t2v, text, tmask, L, D, image, nullptr, P, R, Bc, H, ws + W.a, ws + W.b, ws + W.kv, ws + W.pool_t,
+                                 prec, c.layer_norm_eps, st));
+    DRIN_TRY(cross_attention_max(p->v2t, image, nullptr, P, R, text, tmask, L, D, Bc, H, ws + W.a, ws + W.b, ws + W.kv, ws + W.pool_v,
+                                 prec, c.layer_norm_eps, st));
+    DRIN_TRY(launch_gemm_nt(ws + W.pool_t, D, p->w_text_linear, D, p->b_text_linear, ws + W.tl, D, Bc, D, D, false, prec, st));
+    DRIN_TRY(launch_gemm_nt(ws + W.pool_v, R, p->w_image_linear, R, p->b_image_linear, ws + W.vl, D, Bc, D, R, false, prec, st));
+    float* men = mention_repr ? mention_repr + (int64_t)b0 * D : ws + W.men;
+    DRIN_TRY(launch_gate_mix(ws + W.tl, ws + W.vl, p->w_score_linear, p->b_score_linear, men, Bc, D, st));
+    // EntityEncoder (ghmfc.py:237-250) and the cosine (:297-298)
+    const int64_t pairs = (int64_t)Bc * N;
+    const float* ent_in = bt->entity_feature + (int64_t)b0 * N * D;
+    if (T > 0) {
+      DRIN_TRY(launch_entity_token_mean(bt->entity_feature + (int64_t)b0 * N * T * D, bt->entity_mask + (int64_t)b0 * N * T,
+                                        ws + W.epool, pairs, T, D, st));
+      ent_in = ws + W.epool;
+    }
+    DRIN_TRY(launch_gemm_nt(ent_in, D, p->w_entity, D, p->b_entity, ws + W.ent, D, pairs, D, D, false, prec, st));
+    DRIN_TRY(launch_cosine_rows(men, ws + W.ent, D, scores + (int64_t)b0 * N, Bc, N, D, c.cosine_eps, 1.0f, st));
+  }
+  return DRIN_OK;
+}

@@ -1,0 +1,178 @@
+"""The reference's GHMFC baseline (`baselines/ghmfc.py`) on the HIP library, for scoring: `Model(nn.Module)` with the
+reference's 52 state-dict keys and initialisation order, evaluated by `drin_ghmfc_forward`.
+
+This is the default configuration of `common/args.py` for `model_type = "ghmfc"` (bidirectional cross-attention fusion with
+a GELU gate for the mention, Linear for the entity, offline BERT features) in `eval()` mode, where the dropout inside the four
+attentions is the identity.  Training is not implemented; what is computed and how: section 15.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass
+
+import torch
+from torch import nn
+
+from . import _lib
+
+PRECISIONS = {"bf16x3": _lib.PREC_BF16X3, "f32": _lib.PREC_F32}
+
+
+@dataclass
+class GhmfcConfig:
+    """Geometry of `common/args.py` that GHMFC reads (`bert_embed_dim`, `resnet_embed_dim`, `resnet_num_region`,
+    `max_mention_sentence_len`, `num_candidates_model`, `transformer_num_heads`, `max_entity_attr_token_len`).
+    `entity_tokens` is the token count of the WikiMEL entity features [B, N, T, D] and ignored on WikiDiverse ([B, N, D])."""
+    dataset_name: str = "wikidiverse"
+    num_candidates: int = 11
+    embed_dim: int = 768
+    image_dim: int = 2048
+    mention_tokens: int = 128
+    image_regions: int = 49
+    num_heads: int = 8
+    entity_tokens: int = 64
+    layer_norm_eps: float = 1e-5
+    cosine_eps: float = 1e-8
+
+    def __post_init__(self):
+        if self.dataset_name not in ("wikidiverse", "wikimel"):
+            raise ValueError(f"dataset_name {self.dataset_name!r} is neither 'wikidiverse' nor 'wikimel'")
+
+
+def config_from_reference_args(args) -> GhmfcConfig:
+    """GhmfcConfig from a `common.args` module (or any object with its names); refuses the variants that are not built."""
+    want = dict(mention_final_layer_name="multimodal", mention_multimodal_attention="bi", multimodal_subspace_activation="gelu",
+                entity_final_layer_name="linear", entity_final_pooling="avg", online_bert=False)
+    for name, value in want.items():
+        got = getattr(args, name, value)
+        if got != value:
+            raise NotImplementedError(f"ghmfc: {name} = {got!r} is not implemented (only {value!r}; DESIGN.md section 11)")
+    D = args.bert_embed_dim
+    for name in ("mention_final_output_dim", "entity_final_output_dim"):
+        if getattr(args, name, D) != D:
+            raise NotImplementedError(f"ghmfc: {name} = {getattr(args, name)} != bert_embed_dim = {D} is not implemented")
+    return GhmfcConfig(dataset_name=args.dataset_name, num_candidates=args.num_candidates_model, embed_dim=D,
+                       image_dim=args.resnet_embed_dim, mention_tokens=args.max_mention_sentence_len,
+                       image_regions=args.resnet_num_region, num_heads=getattr(args, "transformer_num_heads", 8),
+                       entity_tokens=getattr(args, "max_entity_attr_token_len", 64))
+
+
+def _ptr(t) -> C.c_void_p:
+    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+
+
+class _CrossAttention(nn.Module):
+    """Parameter container of ghmfc.py's CrossAttention(dim_a, dim_b): same modules, same order."""
+
+    def __init__(self, dim_a: int, dim_b: int, heads: int, dropout: float = 0.1):
+        super().__init__()
+        self.a2b_attention = nn.MultiheadAttention(dim_a, heads, dropout, kdim=dim_b, vdim=dim_b, batch_first=True)
+        self.a2b_ffn = nn.Linear(dim_a, dim_a)
+        self.b2a_attention = nn.MultiheadAttention(dim_a, heads, dropout, batch_first=True)
+        self.b2a_ffn = nn.Linear(dim_a, dim_a)
+        self.layernorms = nn.ModuleList([nn.LayerNorm(dim_a) for _ in range(4)])
+
+    def param_list(self) -> list:
+        a, b = self.a2b_attention, self.b2a_attention
+        out = [a.q_proj_weight, a.k_proj_weight, a.v_proj_weight, a.in_proj_bias, a.out_proj.weight, a.out_proj.bias,
+               self.a2b_ffn.weight, self.a2b_ffn.bias, b.in_proj_weight, b.in_proj_bias, b.out_proj.weight, b.out_proj.bias,
+               self.b2a_ffn.weight, self.b2a_ffn.bias]
+        for ln in self.layernorms:
+            out += [ln.weight, ln.bias]
+        return out
+
+
+class _MultimodalFusion(nn.Module):
+    def __init__(self, cfg: GhmfcConfig):
+        super().__init__()
+        D, R = cfg.embed_dim, cfg.image_dim
+        self.t2v_attention = _CrossAttention(D, R, cfg.num_heads)
+        self.v2t_attention = _CrossAttention(R, D, cfg.num_heads)
+        self.text_linear = nn.Linear(D, D)
+        self.image_linear = nn.Linear(R, D)
+        self.score_linear = nn.Linear(2 * D, 2)
+
+
+class _MentionEncoder(nn.Module):
+    def __init__(self, cfg: GhmfcConfig):
+        super().__init__()
+        self.intermediate_layer = _MultimodalFusion(cfg)
+
+
+class _EntityEncoder(nn.Module):
+    def __init__(self, cfg: GhmfcConfig):
+        super().__init__()
+        self.final_layer = nn.Linear(cfg.embed_dim, cfg.embed_dim)
+
+
+class Model(nn.Module):
+    """ghmfc.py's `Model` for scoring: the same modules, created in the same order (so `torch.manual_seed(s); Model()` draws the
+    reference's weights) and the same 52 state-dict keys; a trained checkpoint loads with `load_state_dict`.
+    `forward(batch)` takes the reference's 8-item offline batch (mention_feature, mention_mask, begin, end, mention_image,
+    entity_feature, entity_mask, entity_image) and returns scores [B, N]; `encode_mentions(batch)` the [B, D] mention
+    representations.  Eval mode only, no gradients.  `precision`: "bf16x3" (split-bf16 products, the default) or "f32"
+    (exact fp32 MFMA); attention, LayerNorm and the gate are fp32 FMA in both."""
+
+    def __init__(self, cfg: GhmfcConfig | None = None, precision: str = "bf16x3"):
+        super().__init__()
+        cfg = cfg or GhmfcConfig()
+        if precision not in PRECISIONS:
+            raise ValueError(f"precision {precision!r} not in {sorted(PRECISIONS)}")
+        self.cfg, self.precision = cfg, precision
+        self.mention_encoder = _MentionEncoder(cfg)
+        self.entity_encoder = _EntityEncoder(cfg)
+
+    def param_list(self) -> list:
+        """The 52 parameters in drin_ghmfc_params (= state-dict) order."""
+        f = self.mention_encoder.intermediate_layer
+        return (f.t2v_attention.param_list() + f.v2t_attention.param_list()
+                + [f.text_linear.weight, f.text_linear.bias, f.image_linear.weight, f.image_linear.bias, f.score_linear.weight,
+                   f.score_linear.bias, self.entity_encoder.final_layer.weight, self.entity_encoder.final_layer.bias])
+
+    def _run(self, batch, want_scores: bool):
+        if self.training:
+            raise RuntimeError("drin_amd.ghmfc.Model is scoring only: call .eval(); GHMFC training is not implemented, DESIGN.md §11")
+        mf, mmask, _begin, _end, mimage, ef, emask = batch[:7]
+        dev = self.entity_encoder.final_layer.weight.device
+        if dev.type != "cuda" or (isinstance(mf, torch.Tensor) and mf.device.type != "cuda"):
+            raise RuntimeError("drin_amd.ghmfc.Model runs on the GPU only (no CPU fallback): move the model and the batch with .cuda()")
+        cfg = self.cfg
+        f = lambda t: t.detach().to(dev, torch.float32).contiguous()          # noqa: E731
+        mf, mimage, ef = f(mf), f(mimage), f(ef)
+        mmask = torch.as_tensor(mmask).to(dev, torch.int64).contiguous()
+        B = mf.shape[0]
+        tokens = 0
+        if ef.dim() == 4:                                                      # WikiMEL: [B, N, T, D] + entity_mask [B, N, T]
+            tokens = ef.shape[2]
+            emask = torch.as_tensor(emask).to(dev, torch.int64).contiguous()
+            if tuple(emask.shape) != tuple(ef.shape[:3]):
+                raise ValueError(f"entity_mask {tuple(emask.shape)} does not match entity_feature {tuple(ef.shape)}")
+        else:
+            emask = None
+        want = (B, cfg.mention_tokens, cfg.embed_dim), (B, cfg.mention_tokens), (B, cfg.image_regions, cfg.image_dim)
+        got = tuple(mf.shape), tuple(mmask.shape), tuple(mimage.shape)
+        if got != want or tuple(ef.shape[:2]) != (B, cfg.num_candidates) or ef.shape[-1] != cfg.embed_dim:
+            raise ValueError(f"ghmfc batch shapes {got}, entity_feature {tuple(ef.shape)} do not match the configuration {cfg}")
+        lib = _lib.load()
+        c = _lib.DrinGhmfcConfigC(batch=B, num_candidates=cfg.num_candidates, embed_dim=cfg.embed_dim, image_dim=cfg.image_dim,
+                                  mention_tokens=cfg.mention_tokens, image_regions=cfg.image_regions, num_heads=cfg.num_heads,
+                                  entity_tokens=tokens, precision=PRECISIONS[self.precision], layer_norm_eps=cfg.layer_norm_eps,
+                                  cosine_eps=cfg.cosine_eps)
+        params = [p.detach().contiguous() for p in self.param_list()]
+        bt = _lib.DrinGhmfcBatchC(_ptr(mf), _ptr(mmask), _ptr(mimage), _ptr(ef), _ptr(emask))
+        pc = _lib.DrinGhmfcParamsC.from_buffer_copy((C.c_void_p * 52)(*[p.data_ptr() for p in params]))
+        nbytes = lib.drin_ghmfc_workspace_bytes(C.byref(c))
+        if nbytes == 0:
+            _lib.check(_lib.E_SHAPE)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        scores = torch.empty(B, cfg.num_candidates, dtype=torch.float32, device=dev)
+        mention = torch.empty(B, cfg.embed_dim, dtype=torch.float32, device=dev)
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(lib.drin_ghmfc_forward(C.byref(c), C.byref(bt), C.byref(pc), _ptr(ws), nbytes, _ptr(scores), _ptr(mention), stream))
+        return scores if want_scores else mention
+
+    def forward(self, batch) -> torch.Tensor:
+        return self._run(batch, True)
+
+    def encode_mentions(self, batch) -> torch.Tensor:
+        return self._run(batch, False)

@@ -1,0 +1,89 @@
+"""The two modules the reference's driver binds for `model_type = "ghmfc"` (`train.py:9-14`), backed by this library, for
+scoring a trained checkpoint (`trainer.test`): GHMFC training is not implemented.
+
+In a checkout of the reference the binding is one changed line of `train.py`:
+
+    from drin_amd import ghmfc_shim as data_module, ghmfc_shim as model_module      # was: from baselines import ...
+
+`Model()` takes no argument and reads `common.args` (imported at call time); `create_datasets()` gives the [train, valid,
+test] loaders of the offline path of `baselines/data.py` (the same `.npy` files, the same 9-item batches) on either dataset.
+"""
+from __future__ import annotations
+
+import importlib
+import json
+import os
+from typing import List
+
+import numpy as np
+import torch
+from torch.utils.data import DataLoader, Dataset
+
+from .ghmfc import Model as _Model
+from .ghmfc import config_from_reference_args
+from .melhi_shim import SPLITS
+
+
+def _args():
+    return importlib.import_module("common.args")
+
+
+class Model(_Model):
+    """`model_module.Model()`: geometry from `common.args`; split-bf16 products unless DRIN_PRECISION=f32."""
+
+    def __init__(self):
+        super().__init__(config_from_reference_args(_args()), precision=os.environ.get("DRIN_PRECISION", "bf16x3"))
+
+
+class GhmfcData(Dataset):
+    """One split of the offline features (`baselines/data.py:85-122,169-192`): (mention_feature, mention_mask, start + 1,
+    end + 1, mention_image, entity_feature, entity_mask, 0, answer one-hot) per mention.  WikiDiverse: entity_feature [N, D]
+    and entity_mask 0; WikiMEL: entity rows gathered from the shared table through `qid2idx.json`, [N, T, D] and [N, T]."""
+
+    def __init__(self, root: str, split: str, dataset_name: str, num_candidates: int, embed_dim: int, entity_text_type: str = "attr",
+                 mention_mmap=None):
+        p = lambda name: os.path.join(root, name)   # noqa: E731
+        self.wikimel = dataset_name == "wikimel"
+        self.mention_feature = np.load(p(f"mention-text-feature_{split}.npy"), mmap_mode=mention_mmap)
+        self.mention_mask = np.load(p(f"mention-text-mask_{split}.npy"))
+        if self.wikimel:
+            self.entity_qid = np.load(p(f"entity-name-raw_{split}.npy")).reshape((-1, num_candidates))
+            self.entity_feature = np.load(p(f"entity-{entity_text_type}-feature.npy"))
+            self.entity_mask = np.load(p(f"entity-{entity_text_type}-mask.npy"))
+            with open(p("qid2idx.json")) as f:
+                self.qid2idx = json.load(f)
+        else:
+            self.entity_feature = np.load(p(f"entity-{entity_text_type}-feature_{split}.npy")).reshape((-1, num_candidates, embed_dim))
+        self.start = np.load(p(f"start-pos_{split}.npy"))
+        self.end = np.load(p(f"end-pos_{split}.npy"))
+        self.answer = np.load(p(f"answer_{split}.npy"))
+        self.mention_image = np.load(p(f"mention-image-feature_{split}.npy"), mmap_mode=mention_mmap)
+        n = num_candidates - 1
+        self.lookup = torch.cat([torch.eye(n, dtype=torch.int8), torch.zeros(1, n, dtype=torch.int8)])
+
+    def __len__(self):
+        return len(self.answer)
+
+    def __getitem__(self, i):
+        if self.wikimel:
+            rows = [self.qid2idx[q] for q in self.entity_qid[i]]
+            entity_feature = torch.from_numpy(np.asarray(self.entity_feature[rows], dtype=np.float32))
+            entity_mask = torch.from_numpy(np.asarray(self.entity_mask[rows], dtype=np.int64))
+        else:
+            entity_feature, entity_mask = torch.from_numpy(self.entity_feature[i].copy()), 0
+        return (torch.from_numpy(self.mention_feature[i].copy()), torch.from_numpy(np.asarray(self.mention_mask[i])),
+                int(self.start[i]) + 1, int(self.end[i]) + 1, torch.from_numpy(np.asarray(self.mention_image[i]).copy()),
+                entity_feature, entity_mask, 0, self.lookup[int(self.answer[i])])
+
+
+def create_datasets() -> List[DataLoader]:
+    """`data_module.create_datasets()` for GHMFC: loaders over `args.preprocess_dir` with `args.batch_size`."""
+    a = _args()
+    cfg = config_from_reference_args(a)
+    loaders = []
+    for split in SPLITS:
+        ds = GhmfcData(a.preprocess_dir, split, cfg.dataset_name, cfg.num_candidates, cfg.embed_dim,
+                       getattr(a, "entity_text_type", "attr"), getattr(a, "mention_mmap", None))
+        loaders.append(DataLoader(ds, a.batch_size, shuffle=(split == "train" and getattr(a, "shuffle_train_data", True)),
+                                  num_workers=getattr(a, "dataloader_workers", 0)))
+    return loaders

@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define DRIN_ABI_VERSION 9
+#define DRIN_ABI_VERSION 10
 #define DRIN_API __attribute__((visibility("default")))
 
 typedef enum {
@@ -524,6 +524,78 @@ DRIN_API int drin_melhi_backward(const drin_melhi_config* cfg, const drin_melhi_
                                  const int32_t* order, const int32_t* lengths, void* workspace, size_t workspace_bytes,
                                  const float* grad_scores, const drin_melhi_param_grads* grads, void* stream);
 
+/* ---- the GHMFC baseline (reference baselines/ghmfc.py), eval-mode scoring ------------------------- *
+ * The reference's train.py selects it with model_type "ghmfc"; this is its default configuration (args.py: mention_final_layer_name
+ * "multimodal", mention_multimodal_attention "bi", multimodal_subspace_activation "gelu", entity_final_layer_name "linear",
+ * entity_final_pooling "avg", online_bert False) in eval() mode, where the dropout inside the four attentions is the identity.
+ * Scores [B, N] = cos(MultimodalFusion(text, mask, image), Linear(entity)) (ghmfc.py:131-149, :237-251, :287-298; DESIGN.md
+ * section 15).  Training is not implemented. */
+typedef struct {
+  int32_t batch;           /* B mentions (1 .. 2^20); processed in chunks of 256 inside the call           */
+  int32_t num_candidates;  /* N = num_candidates_model                                                    */
+  int32_t embed_dim;       /* D = bert_embed_dim   (multiple of 4 and of num_heads, <= 2048, D / H <= 256) */
+  int32_t image_dim;       /* R = resnet_embed_dim (the same rules)                                        */
+  int32_t mention_tokens;  /* L = max_mention_sentence_len (1 .. 512)                                      */
+  int32_t image_regions;   /* P = resnet_num_region (1 .. 512)                                             */
+  int32_t num_heads;       /* H = transformer_num_heads (8)                                                */
+  int32_t entity_tokens;   /* 0: entity_feature is pooled [B, N, D] (WikiDiverse); T > 0: [B, N, T, D] + entity_mask (WikiMEL) */
+  int32_t precision;       /* DRIN_PREC_BF16X3 or DRIN_PREC_F32 (the products; attention, LayerNorm, gate are fp32 FMA) */
+  float layer_norm_eps;    /* 1e-5  (nn.LayerNorm default)                                                  */
+  float cosine_eps;        /* 1e-8  (nn.CosineSimilarity default)                                           */
+} drin_ghmfc_config;
+
+/* The tensors of the reference's offline batch that this configuration reads (begin, end, entity_image are not).
+ * Device pointers, fp32 unless int64. */
+typedef struct {
+  const float* mention_feature;  /* [B, L, D]                                                            */
+  const int64_t* mention_mask;   /* [B, L]   nonzero = token; zero = padding (dropped as a KEY, kept as a query) */
+  const float* mention_image;    /* [B, P, R]                                                            */
+  const float* entity_feature;   /* [B, N, D], or [B, N, T, D] when entity_tokens = T > 0                */
+  const int64_t* entity_mask;    /* [B, N, T] when entity_tokens > 0 (mean of tokens 1 : sum - 1), else not read */
+} drin_ghmfc_batch;
+
+/* One CrossAttention(dim_a, dim_b) (ghmfc.py:93-128), its 22 tensors in state-dict order; E = dim_a, Eb = dim_b. */
+typedef struct {
+  const float *a2b_wq, *a2b_wk, *a2b_wv;         /* a2b_attention.{q,k,v}_proj_weight   [E, E], [E, Eb], [E, Eb] */
+  const float *a2b_in_bias;                      /* a2b_attention.in_proj_bias          [3 E]                    */
+  const float *a2b_wo, *a2b_bo;                  /* a2b_attention.out_proj              [E, E], [E]              */
+  const float *a2b_ffn_w, *a2b_ffn_b;            /* a2b_ffn                             [E, E], [E]              */
+  const float *b2a_in_w, *b2a_in_bias;           /* b2a_attention.in_proj_{weight,bias} [3 E, E], [3 E]          */
+  const float *b2a_wo, *b2a_bo;                  /* b2a_attention.out_proj              [E, E], [E]              */
+  const float *b2a_ffn_w, *b2a_ffn_b;            /* b2a_ffn                             [E, E], [E]              */
+  const float *ln0_w, *ln0_b, *ln1_w, *ln1_b, *ln2_w, *ln2_b, *ln3_w, *ln3_b;   /* layernorms.0 .. 3  [E] each */
+} drin_ghmfc_cross_params;
+
+/* The 52 state_dict tensors of ghmfc.py's Model, in state-dict order (nn.Linear layout weight[out][in]). */
+typedef struct {
+  drin_ghmfc_cross_params t2v;                   /* mention_encoder.intermediate_layer.t2v_attention  (E = D, Eb = R) */
+  drin_ghmfc_cross_params v2t;                   /* mention_encoder.intermediate_layer.v2t_attention  (E = R, Eb = D) */
+  const float *w_text_linear, *b_text_linear;    /* ....text_linear    [D, D], [D]                                    */
+  const float *w_image_linear, *b_image_linear;  /* ....image_linear   [D, R], [D]                                    */
+  const float *w_score_linear, *b_score_linear;  /* ....score_linear   [2, 2 D], [2]                                  */
+  const float *w_entity, *b_entity;              /* entity_encoder.final_layer [D, D], [D]                            */
+} drin_ghmfc_params;
+
+/* Bytes of workspace for drin_ghmfc_forward: one chunk of min(B, 256) mentions; 0 on error (drin_last_error). */
+DRIN_API size_t drin_ghmfc_workspace_bytes(const drin_ghmfc_config* cfg);
+
+/* Model.forward of ghmfc.py in eval() mode: scores [B, N]; mention_repr (may be NULL) receives the [B, D] output of
+ * mention_encoder.  Writes `scores`, `mention_repr` and the workspace, nothing else.  A mention whose mask is all zero has
+ * zero attention weights wherever the text is the key (the out-projection then returns its bias), as torch's kernel: finite. */
+DRIN_API int drin_ghmfc_forward(const drin_ghmfc_config* cfg, const drin_ghmfc_batch* batch, const drin_ghmfc_params* params,
+                                void* workspace, size_t workspace_bytes, float* scores, float* mention_repr, void* stream);
+
+/* The multi-head softmax-attention core on projected operands (what nn.MultiheadAttention runs between its in- and
+ * out-projections, ghmfc.py:120,124): out[b, i, h] = softmax_j(q[b, i, h] . k[b, j, h] / sqrt(head_dim) + mask) v[b, j, h].
+ * q [batch * q_len, E], k, v [batch * k_len, E], out [batch * q_len, E] are row-major with row strides ldq, ldk, ldv, ldo
+ * (floats, >= E = num_heads * head_dim); head h is columns h * head_dim .. (h + 1) * head_dim - 1, so K | V packed in one
+ * [rows, 2 E] buffer are k = buf, v = buf + E, ldk = ldv = 2 E.  key_mask: int64 [batch, k_len], nonzero = keep, or NULL.
+ * A query row with no kept key gets zeros.  fp32 FMA, max-subtracted, no atomics: the same bits every run.
+ * Any q_len >= 1, k_len in [1, 512], head_dim in [1, 256], batch and num_heads in [1, 65535]. */
+DRIN_API int drin_attention(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv,
+                            const int64_t* key_mask, float* out, int64_t ldo, int32_t batch, int32_t num_heads, int32_t q_len,
+                            int32_t k_len, int32_t head_dim, void* stream);
+
 /* ---- in-process kernel timing (bench.py's roofline leg) ---------------------------------------- */
 
 /* Kernel classes the launches are attributed to. */
@@ -538,7 +610,9 @@ typedef enum {
   DRIN_KC_OPTIM = 7,       /* drin_adam_step                                                        */
   DRIN_KC_LSTM = 8,        /* drin_melhi_*: one step of the long LSTM recurrences (forward or backward) */
   DRIN_KC_CELL = 9,        /* drin_melhi_*: mask, time-0 cells, gathers and their backward           */
-  DRIN_KC_COUNT = 10
+  DRIN_KC_ATTN = 10,       /* drin_attention / drin_ghmfc_forward: k_attention, the softmax-attention core    */
+  DRIN_KC_NORM = 11,       /* drin_ghmfc_forward: LayerNorm (+ residual), max over a sequence, the gated mix  */
+  DRIN_KC_COUNT = 12
 } drin_kernel_class;
 
 /* While a profile is open, every launch the library makes - from any thread, e.g. drin_backward on

@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # DRIN_LIB_PATH: another build of the same library (the sanitizer build of `python -m drin_amd.build --asan-host`)
 LIB_PATH = os.environ.get("DRIN_LIB_PATH") or os.path.join(_HERE, "libdrin_hip.so")
 MAX_LAYERS = 8
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 OK, E_SHAPE, E_NULL, E_ALIGN, E_WORKSPACE, E_HIP, E_UNSUPPORTED, E_INDEX = 0, -1, -2, -3, -4, -5, -6, -7
 PREC_F32, PREC_BF16X3, PREC_BF16X3_ALL, PREC_BF16X3_IF16 = 0, 1, 3, 5     # (2 and 4: removed with ABI 6 - outside the 1e-4 bar)
@@ -153,6 +153,7 @@ EXPORTS = {
     "drin_input_grad_scratch_bytes": (C.c_size_t, [C.POINTER(DrinConfigC)]),
     "drin_pool_bwd": (C.c_int, [C.POINTER(DrinConfigC), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "drin_fused_supported": (C.c_int, [C.POINTER(DrinConfigC)]),
+    "drin_indexed_supported": (C.c_int, [C.POINTER(DrinConfigC)]),
     "drin_prepared_bytes": (C.c_size_t, [C.POINTER(DrinConfigC)]),
     "drin_fused_workspace_bytes": (C.c_size_t, [C.POINTER(DrinConfigC)]),
     "drin_workgroups_per_mention": (C.c_int32, [C.POINTER(DrinConfigC), C.c_int32]),

@@ -373,7 +373,7 @@ static int tap(const drin_trace* t, int l, const Layout& L, const float* ws, int
 // Table form of the layer-by-layer entry points (training over device-resident entity tables): the entity tensors of the
 // batch are TABLES of cfg.num_entities rows and pair p reads row entity_index[p] - inside the static-edge kernels and in
 // the row addressing of the vertex-encoder GEMMs (forward x W^T, backward dY^T x), never as gathered copies.
-static int indexed_supported(const drin_config* c, const drin_batch* b, const char* who) {
+static int indexed_supported(const drin_config* c, const char* who) {
   const int64_t M = (int64_t)c->batch * c->num_candidates;
   const int D = c->embed_dim, R = c->image_dim;
   const bool x3 = c->precision == DRIN_PREC_BF16X3 || c->precision == DRIN_PREC_BF16X3_ALL;
@@ -385,7 +385,6 @@ static int indexed_supported(const drin_config* c, const drin_batch* b, const ch
               "1024 pairs; gather on the caller side otherwise", who);
     return DRIN_E_UNSUPPORTED;
   }
-  (void)b;
   return DRIN_OK;
 }
 
@@ -627,6 +626,11 @@ size_t drin_workspace_bytes(const drin_config* cfg, int for_training) {
   return L.total_floats * sizeof(float);
 }
 
+int drin_indexed_supported(const drin_config* cfg) {
+  DRIN_TRY(validate_config(cfg));
+  return indexed_supported(cfg, "drin_indexed_supported");
+}
+
 int drin_edges_fwd(const drin_config* cfg, const drin_batch* batch, float* edges, float* span_mean, void* stream) {
   DRIN_BIND_DEVICE(stream, edges, "drin_edges_fwd");
   DRIN_TRY(validate_config(cfg));
@@ -755,7 +759,7 @@ int drin_forward_staged(const drin_config* cfg, const drin_batch* batch, const d
   DRIN_TRY(validate_batch(cfg, batch));
   DRIN_TRY(validate_params(cfg, params));
   const int64_t* eidx = batch->entity_index;
-  if (eidx) DRIN_TRY(indexed_supported(cfg, batch, "drin_forward"));
+  if (eidx) DRIN_TRY(indexed_supported(cfg, "drin_forward"));
   if (!scores) {
     set_error("scores is NULL");
     return DRIN_E_NULL;
@@ -1070,7 +1074,7 @@ int drin_backward_ex(const drin_config* cfg, const drin_batch* batch, const drin
   static const drin_param_grads kNoGrads = {};
   const drin_param_grads* grads = grads_in ? grads_in : &kNoGrads;
   const int64_t* eidx = batch->entity_index;
-  if (eidx) DRIN_TRY(indexed_supported(cfg, batch, "drin_backward"));
+  if (eidx) DRIN_TRY(indexed_supported(cfg, "drin_backward"));
   if (input_grads) DRIN_TRY(validate_input_grads(cfg, batch, input_grads));
   Layout L;
   L.build(*cfg, true);

@@ -13,7 +13,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, NamedTuple, Optional, Sequence
 
 import torch
 from torch import nn
@@ -312,45 +312,38 @@ class _Call:
         otherwise bf16 features are widened to fp32 here (exact) - e.g. for training.
         `entity_text_cls` `[B, N, D]`: the token-0 rows of the text-text edge when `entity_text_feature` holds token
         means pooled ahead of time (`EntityTable.pooled_text`)."""
+        self._describe(cfg, batch, precision, entity_index, keep_bf16, entity_text_cls, index_status)
+        self.convert(precision if keep_bf16 else None)
+
+    @classmethod
+    def described(cls, cfg: DrinConfig, batch: Sequence[torch.Tensor], precision: int, **kw) -> "_Call":
+        """The shape / config half of the constructor alone: `cfg` is complete - it is what the library's `drin_*_supported`
+        predicates read - and no tensor is converted or copied yet; `convert` completes the call."""
+        return cls.__new__(cls)._describe(cfg, batch, precision, **kw)
+
+    _PARTLY_BF16 = ("bf16 feature storage: give all six feature tensors (mention text / image / object, entity "
+                    "text / image / object) as bfloat16, or none")
+
+    def _describe(self, cfg, batch, precision, entity_index=None, keep_bf16=False, entity_text_cls=None, index_status=None):
         if len(batch) not in (14, 15):
             raise ValueError(f"batch must be the 14-sequence of drin/data.py:110-126 (got {len(batch)} items)")
         (mtf, _mask, start, end, mimg, mobj, mscore, etf, emask, eimg, eobj, escore, miet, mtei) = batch[:14]
         dev = mtf.device
         if dev.type != "cuda":
             raise RuntimeError("drin_amd.Model runs on an AMD GPU only (no CPU / eager fallback); move the batch to 'cuda'")
-
-        def f32(t):
-            if t.device != dev:
-                raise RuntimeError("all batch tensors must be on the same device")
-            return t.to(torch.float32).contiguous()
-
         # bf16 feature storage (BASELINE configs 2-3): all six feature tensors, or none
         feats = (mtf, mimg, mobj, etf, eimg, eobj)
-        n_bf16 = sum(t.dtype == torch.bfloat16 for t in feats)
-        bf16 = keep_bf16 and n_bf16 == len(feats)
-        if keep_bf16 and 0 < n_bf16 < len(feats):
-            raise ValueError("bf16 feature storage: give all six feature tensors (mention text / image / object, entity "
-                             "text / image / object) as bfloat16, or none")
-
-        def feat(t):
+        self._n_bf16 = sum(t.dtype == torch.bfloat16 for t in feats)
+        if keep_bf16 and 0 < self._n_bf16 < len(feats):
+            raise ValueError(self._PARTLY_BF16)
+        for t in feats + (mscore, escore, miet, mtei):
             if t.device != dev:
                 raise RuntimeError("all batch tensors must be on the same device")
-            return t.contiguous() if bf16 else t.to(torch.float32).contiguous()
-
-        def i64(t):
-            return t.to(device=dev, dtype=torch.int64).contiguous()
-
-        mtf, mimg, mobj, etf, eimg, eobj = map(feat, feats)
-        mscore, escore, miet, mtei = map(f32, (mscore, escore, miet, mtei))
-        start, end = i64(start), i64(end)
-        B, L, D = mtf.shape
-        N = cfg.num_candidates_model
-        R = mimg.shape[-1]
+        (B, L, D), N, R = mtf.shape, cfg.num_candidates_model, mimg.shape[-1]
         table = entity_index is not None
         if table:
             # entity tensors are tables [E, ...]: give them the per-pair ranks by viewing E as (E, 1)
             E = etf.shape[0]
-            entity_index = i64(entity_index)
             if tuple(entity_index.shape) != (B, N):
                 raise ValueError(f"candidates has shape {tuple(entity_index.shape)}, expected {(B, N)}")
             etf, eimg, eobj, escore = (t.unsqueeze(1) for t in (etf, eimg, eobj, escore))
@@ -366,8 +359,7 @@ class _Call:
             raise ValueError(f"entity_text_feature leads with {tuple(etf.shape[:2])}, expected {lead}")
         if mobj.dim() not in (3, 4) or eobj.dim() not in (4, 5) or eimg.dim() not in (3, 4):
             raise ValueError("unexpected rank for object / image features (model.py:43-44,78-83)")
-        Km = mobj.shape[1]
-        Ke = eobj.shape[2]
+        Km, Ke = mobj.shape[1], eobj.shape[2]
         for name, t, shape in (
             ("mention_image_feature", mimg, (B, mimg.shape[1], R)),
             ("mention_object_score", mscore, (B, Km)),
@@ -382,7 +374,6 @@ class _Call:
         if tuple(eimg.shape[0:2]) != lead or tuple(eobj.shape[0:2]) != lead or eimg.shape[-1] != R or eobj.shape[-1] != R or mobj.shape[-1] != R:
             raise ValueError("entity/mention image or object feature shape mismatch")
         if token_level:
-            emask = i64(emask)
             if tuple(emask.shape) != tuple(etf.shape[:3]):
                 raise ValueError(f"entity_text_mask has shape {tuple(emask.shape)}, expected {tuple(etf.shape[:3])}")
         else:
@@ -390,7 +381,8 @@ class _Call:
         if entity_text_cls is not None:
             if token_level:
                 raise ValueError("entity_text_cls goes with pooled entity text")
-            entity_text_cls = f32(entity_text_cls)
+            if entity_text_cls.device != dev:
+                raise RuntimeError("all batch tensors must be on the same device")
             want = (etf.shape[0], D) if table else (B, N, D)       # a table of token-0 rows, or per-pair rows
             if tuple(entity_text_cls.shape) != want:
                 raise ValueError(f"entity_text_cls has shape {tuple(entity_text_cls.shape)}, expected {want}")
@@ -398,8 +390,7 @@ class _Call:
             raise ValueError("index_status: int32[4] on the batch's device")
         self.keep = [mtf, start, end, mimg, mobj, mscore, etf, emask, eimg, eobj, escore, miet, mtei, entity_index,
                      entity_text_cls, index_status if table else None]
-        self.device = dev
-        self.B, self.N, self.D = B, N, D
+        self.device, self.B, self.N, self.D = dev, B, N, D
         c = _lib.DrinConfigC()
         _lib.check(_lib.load().drin_default_config(C.byref(c)))
         c.batch, c.num_candidates, c.embed_dim, c.image_dim = B, N, D, R
@@ -418,11 +409,31 @@ class _Call:
         c.precision = precision
         c.num_entities = etf.shape[0] if table else 0
         c.vector_edges = 1 if cfg.gcn_edge_feature == "vector" else 0
-        c.feature_dtype = _lib.FEAT_BF16 if bf16 else _lib.FEAT_F32
+        c.feature_dtype = _lib.FEAT_F32                       # (bf16 kept in place: `convert` says so)
         c.vertex_activation = _lib.ACTIVATIONS[cfg.gcn_vertex_activation]
         c.edge_activation = _lib.ACTIVATIONS[cfg.gcn_edge_activation]
         self.per_layer = 10 if c.vector_edges else 8
         self.cfg = c
+        # what `Model._score` / `Model._route` add for the autograd edge (a bare call scores and trains without them)
+        self.owner: Optional["Model"] = None                  # whose gradient bucket and layers-ready hook backward uses
+        self.input_roles: Sequence[str] = ()                  # batch tensors that follow the parameters into `_DrinScore.apply`
+        self.params_ready: Optional[torch.cuda.Event] = None  # train.OverlappedStep: an update still running on a side stream
+        self.token_block: Optional[torch.Tensor] = None       # a bf16 [B, N, T, D] block pooled in place, and its int64 mask
+        self.token_mask: Optional[torch.Tensor] = None
+        return self
+
+    def convert(self, in_place: Optional[int] = None) -> "_Call":
+        """The conversion half: fp32 / int64, contiguous, and the `drin_batch` that points at the results.  `in_place`: what
+        `keep_bf16` gives the constructor - that precision, and features stored as bf16 (all six, or none) stay as they are."""
+        if in_place is not None:
+            if 0 < self._n_bf16 < 6:
+                raise ValueError(self._PARTLY_BF16)
+            self.cfg.precision, self.cfg.feature_dtype = in_place, _lib.FEAT_BF16 if self._n_bf16 else _lib.FEAT_F32
+        f32 = lambda t: t.to(torch.float32).contiguous()  # noqa: E731
+        feat = (lambda t: t.contiguous()) if self.cfg.feature_dtype == _lib.FEAT_BF16 else f32  # noqa: E731
+        i64 = lambda t: t.to(device=self.device, dtype=torch.int64).contiguous()  # noqa: E731
+        kinds = (feat, i64, i64, feat, feat, f32, feat, i64, feat, feat, f32, f32, f32, i64, f32, lambda t: t)
+        self.keep = [None if t is None else kind(t) for kind, t in zip(kinds, self.keep)]
         b = _lib.DrinBatchC()
         for name, t in zip(("mention_text", "mention_start", "mention_end", "mention_image", "mention_object",
                             "mention_object_score", "entity_text", "entity_text_mask", "entity_image",
@@ -430,12 +441,7 @@ class _Call:
                             "entity_index", "entity_text_cls", "index_status"), self.keep):
             setattr(b, name, _ptr(t))
         self.batch = b
-        # what `Model._score` / `Model._forward` add for the autograd edge (a bare call scores and trains without them)
-        self.owner: Optional["Model"] = None                  # whose gradient bucket and layers-ready hook backward uses
-        self.input_roles: Sequence[str] = ()                  # batch tensors that follow the parameters into `_DrinScore.apply`
-        self.params_ready: Optional[torch.cuda.Event] = None  # train.OverlappedStep: an update still running on a side stream
-        self.token_block: Optional[torch.Tensor] = None       # a bf16 [B, N, T, D] block pooled in place, and its int64 mask
-        self.token_mask: Optional[torch.Tensor] = None
+        return self
 
     def stream(self) -> int:
         return torch.cuda.current_stream(self.device).cuda_stream
@@ -560,6 +566,15 @@ def _param_grads(call: _Call, params: Sequence[torch.Tensor]):
     return gc, out
 
 
+class _Route(NamedTuple):
+    """What `Model._route` decides for one library call."""
+    path: str                                      # "prepared" (drin_forward_prepared), "cached" (drin_forward_cached), "layers" (drin_forward_staged)
+    call: _Call
+    training: bool                                 # keep what backward reads; tensors that require grad join the autograd edge
+    token_block: Optional[torch.Tensor] = None     # a bf16 [B, N, T, D] block that was pooled in place ahead of the call
+    clamped: bool = False                          # table form: the candidate rows were clamped into the tables in Python
+
+
 class _DrinScore(torch.autograd.Function):
     """Autograd edge around drin_forward_staged / drin_backward_ex (loss.backward() of train.py:33-34).  `call.input_roles`
     names the batch tensors that follow the parameters in `tensors` (drin_input_grads fields; "token_block": a bf16
@@ -571,8 +586,8 @@ class _DrinScore(torch.autograd.Function):
         ctx.roles = call.input_roles
         versions = tensors[:len(tensors) - len(ctx.roles)]
         params, pc = call.param_struct(versions)
-        if not training and prepared is not None and lib.drin_fused_supported(C.byref(call.cfg)) == _lib.OK:
-            # inference: fused two-layer path on weights folded once per weight version
+        if prepared is not None:
+            # the route says "prepared": fused two-layer inference on weights folded once per weight version
             pbuf = prepared.get(call, versions, pc)
             ws = call.byte_buffer(lib.drin_fused_workspace_bytes(C.byref(call.cfg)))
             scores = call.scores()
@@ -856,87 +871,93 @@ class Model(nn.Module):
         """"bf16x3_if16" is a mode of the fused inference path; anything else it meets runs split-bf16."""
         return _lib.PREC_BF16X3 if self.precision in _FUSED_ONLY else self.precision
 
-    def _forward_table(self, batch: "IndexedBatch", params):
-        """Table form: the scores, where the kernels read the tables through the candidate index (fused or
-        cached inference, training on pooled tables); everything else (exact-fp32 precision, geometries off those paths,
-        batch tensors that require grad - so that torch's indexing backward accumulates into the table rows) gathers with
-        torch indexing and returns `(14-sequence, token-0 rows or None)` for the common tail of `_forward`."""
+    def _route(self, batch, params) -> _Route:
+        """THE place where the library path of one call is chosen (`_forward` runs what it returns).  Geometry is the library's
+        to judge - `drin_fused_supported`, `drin_indexed_supported`, each asked at most once; what is tested here is what only
+        this side knows.  Table form: the kernels read the tables through the candidate index on the folded and
+        cached inference paths and when training on pooled tables; everything else (exact-fp32 precision, geometries off those
+        paths, batch tensors that require grad) gathers the rows with torch indexing."""
+        lib = _lib.load()
+        # grad mode is already off inside Function.forward (and needs_input_grad ignores no_grad), so the caller's mode is read
+        # here.  Any parameter or float batch tensor requiring grad: the layer-by-layer forward that keeps what backward reads
         feat_grad = torch.is_grad_enabled() and _batch_requires_grad(batch)
-        inference = not (torch.is_grad_enabled() and any(p.requires_grad for p in params)) and not feat_grad
-        planes = self.precision in _PLANES
-        t = batch.table
-        call = out = None
-        if inference and self._prepared is not None and self.cfg.num_gcn_layers == 2 and (planes or t.cache_enabled):
-            seq = batch.mention + [t.text, t.mask, t.image, t.object, t.object_score,
-                                   batch.miet_similarity, batch.mtei_similarity]
-            if t.cache_enabled and t.text.dtype == torch.bfloat16:
-                raise ValueError("the per-entity cache is built from fp32 tables; give EntityTable fp32 features")
-            # bf16-stored features are read in place by the fused path (never widened: the table is large)
-            call = _Call(self.cfg, seq, self._unfused_precision() if t.cache_enabled else self.precision,
-                         entity_index=batch.candidates, keep_bf16=planes and not t.cache_enabled,
-                         index_status=self._status_words(batch.candidates.device))
-            if _lib.load().drin_fused_supported(C.byref(call.cfg)) == _lib.OK:
-                if t.cache_enabled:                                    # per-entity precompute cache (SURVEY.md 8f-2)
-                    out = self._forward_cached(call, t, params)
-                else:                                                  # an empty batch too: the library validates its geometry
-                    out = self._score(call, self._prepared, False, *params)
-        # training on a token-level table: every entity's tokens pooled once; the step then reads the pooled / token-0 /
-        # image / object tables through the candidate index inside the kernels, or gathers those rows
-        pooled = not inference and not feat_grad and t.text.dim() == 3
-        if pooled:
-            call = self._indexed_training_call(batch, planes)
-            if call is not None:
-                out = self._score(call, None, True, *params)
-        if out is not None:
-            self._watch_indices(call.device)                           # the kernels clamp and report: after their launches
-            return out
-        batch = self._clamped(batch)
-        seq, cls = batch.gathered_pooled(self.cfg) if pooled else (batch.gathered(), None)
-        self._watch_indices(seq[0].device)                             # before scoring: with validate_indices, the raise
-        return seq, cls
+        training = feat_grad or (torch.is_grad_enabled() and any(p.requires_grad for p in params))
+        folds = not training and self._prepared is not None
+        planes, unfused = self.precision in _PLANES, self._unfused_precision()
+        fused = None
 
-    def _forward(self, batch) -> torch.Tensor:
-        params = _param_list(self)
-        cls = block = None
+        def fused_supported(call: _Call) -> bool:      # asked once per route: gathering the rows does not change the answer
+            nonlocal fused
+            if fused is None:
+                fused = lib.drin_fused_supported(C.byref(call.cfg)) == _lib.OK
+            return fused
+        seq, cls, block, clamped = batch, None, None, False
         if isinstance(batch, IndexedBatch):
-            got = self._forward_table(batch, params)
-            if torch.is_tensor(got):
-                return got
-            batch, cls = got
-        # grad mode is already off inside Function.forward (and needs_input_grad ignores no_grad), so the
-        # caller's mode is read here
-        # (any parameter or any float batch tensor requiring grad: the layer-by-layer forward that keeps what backward reads)
-        training = torch.is_grad_enabled() and (any(p.requires_grad for p in params) or _batch_requires_grad(batch))
-        if (cls is None and training and len(batch) >= 14 and batch[7].dtype == torch.bfloat16 and batch[7].dim() == 4
-                and batch[7].is_cuda and batch[7].shape[0] > 0):
-            # a training step on bf16-stored token blocks: pooled in place by the library - half
-            # the bytes, no widened copy of the 197 KB per candidate - then the pooled-ahead form below
-            etf, emask = batch[7], batch[8]
-            batch = list(batch[:7]) + [_pool_tokens(etf, emask), torch.zeros(etf.shape[0], dtype=torch.int64, device=etf.device)] \
-                + list(batch[9:])
+            t = batch.table
+            tables = lambda text, mask: batch.mention + [text, mask, t.image, t.object, t.object_score,  # noqa: E731
+                                                         batch.miet_similarity, batch.mtei_similarity]
+            if folds and (planes or t.cache_enabled):
+                call = _Call.described(self.cfg, tables(t.text, t.mask), unfused, entity_index=batch.candidates,
+                                       index_status=self._status_words(batch.candidates.device))
+                if fused_supported(call):
+                    if not t.cache_enabled:    # bf16-stored features are read in place (never widened: the table is large)
+                        return _Route("prepared", call.convert(in_place=self.precision), False)
+                    if t.text.dtype == torch.bfloat16:
+                        raise ValueError("the per-entity cache is built from fp32 tables; give EntityTable fp32 features")
+                    return _Route("cached", call.convert(), False)         # per-entity precompute cache (SURVEY.md 8f-2)
+            batch, clamped = self._clamped(batch), True                # whatever follows trusts the index
+            # training on a token-level table: every entity's tokens pooled once; the step then reads the pooled / token-0 /
+            # image / object tables through the candidate index inside the kernels, or gathers those rows (always from a bf16
+            # table, which `_Call` would widen whole).  With a batch tensor that requires grad the token rows themselves are
+            # gathered: torch's indexing backward must reach them
+            pooled = training and not feat_grad and t.text.dim() == 3
+            if pooled and all(x.dtype == torch.float32 for x in (t.text, t.image, t.object)):
+                text, rows0 = t.pooled_text(self.cfg)
+                dummy = torch.zeros(batch.candidates.shape[0], dtype=torch.int64, device=batch.candidates.device)
+                call = _Call.described(self.cfg, tables(text, dummy), unfused, entity_index=batch.candidates, entity_text_cls=rows0)
+                if lib.drin_indexed_supported(C.byref(call.cfg)) == _lib.OK:
+                    return _Route("layers", call.convert(), True, None, True)
+            seq, cls = batch.gathered_pooled(self.cfg) if pooled else (batch.gathered(), None)
+        if (cls is None and training and len(seq) >= 14 and seq[7].dtype == torch.bfloat16 and seq[7].dim() == 4
+                and seq[7].is_cuda and seq[7].shape[0] > 0):
+            # a training step on bf16-stored token blocks: pooled in place by the library - half the bytes, no widened copy of
+            # the 197 KB per candidate - then the pooled-ahead form below
+            etf, emask = seq[7], seq[8]
+            seq = list(seq[:7]) + [_pool_tokens(etf, emask), torch.zeros(etf.shape[0], dtype=torch.int64, device=etf.device)] \
+                + list(seq[9:])
             cls = etf[:, :, 0, :]
             if etf.requires_grad:
                 # the block's gradient comes from drin_pool_bwd, written in bf16 (never widened): token 0 is not a graph input
                 block, cls = etf, cls.detach()
         if cls is not None:
             # pooled-ahead batch: the layer-by-layer entry points (the fused path folds the pooling into its one pass)
-            prepared = None
-            call = _Call(self.cfg, batch, self._unfused_precision(), entity_text_cls=cls)
+            call = _Call(self.cfg, seq, unfused, entity_text_cls=cls)
             if block is not None:
                 call.token_block, call.token_mask = block, emask.to(device=block.device, dtype=torch.int64).contiguous()
-        else:
+            return _Route("layers", call, True, block, clamped)
+        call = _Call.described(self.cfg, seq, unfused)
+        if folds and fused_supported(call):
             # features stored as bf16 are read in place by the fused inference path in split-bf16 precision; every
             # other path (training, exact fp32, geometries off the fused path) gets them widened to fp32 - exact
-            prepared = self._prepared
-            in_place = not training and prepared is not None and self.cfg.num_gcn_layers == 2 and self.precision in _PLANES
-            prec = self.precision if in_place else self._unfused_precision()
-            call = _Call(self.cfg, batch, prec, keep_bf16=in_place)
-            if ((call.cfg.feature_dtype != _lib.FEAT_F32 or prec in _FUSED_ONLY)
-                    and _lib.load().drin_fused_supported(C.byref(call.cfg)) != _lib.OK):
-                call = _Call(self.cfg, batch, self._unfused_precision())
-        if call.B == 0:
-            return call.scores()
-        return self._score(call, prepared, training, *params, feats=_feature_inputs(call, block) if training else ((), ()))
+            return _Route("prepared", call.convert(in_place=self.precision if planes else None), False, None, clamped)
+        return _Route("layers", call.convert(), training, None, clamped)
+
+    def _forward(self, batch) -> torch.Tensor:
+        params = _param_list(self)
+        route = self._route(batch, params)
+        call, indexed = route.call, route.call.cfg.num_entities > 0       # the kernels read the tables through the index
+        if route.clamped and not indexed:
+            self._watch_indices(call.device)                           # before scoring: with validate_indices, the raise
+        if call.B == 0 and not (indexed and route.path == "prepared"):  # (that one goes on: the library validates its geometry)
+            out = call.scores()
+        elif route.path == "cached":
+            out = self._forward_cached(call, batch.table, params)
+        else:
+            out = self._score(call, self._prepared if route.path == "prepared" else None, route.training, *params,
+                              feats=_feature_inputs(call, route.token_block) if route.training else ((), ()))
+        if indexed:
+            self._watch_indices(call.device)                           # the kernels clamp and report: after their launches
+        return out
 
     def wait_for_parameters(self) -> None:
         """Make the current stream wait for an optimiser update `train.OverlappedStep` left running on its side stream (no-op
@@ -951,7 +972,7 @@ class Model(nn.Module):
         call.input_roles, inputs = feats
         ev = self._params_ready
         if ev is not None:
-            if training or prepared is None:                 # the layer-by-layer entry point: staged
+            if prepared is None:                             # route "layers", the layer-by-layer entry point: staged
                 call.params_ready, self._params_ready = ev, None
             else:
                 self.wait_for_parameters()
@@ -966,41 +987,20 @@ class Model(nn.Module):
             raise
 
     def _clamped(self, batch: "IndexedBatch") -> "IndexedBatch":
-        """The batch with its candidate rows clamped into the tables and any clamped row reported in the status words: the torch
-        gathers of the paths off the fused kernels must never see a row >= E (a device-side assert), and a negative row wraps
-        silently there."""
+        """The batch with its candidate rows clamped into the tables and any clamped row reported in the status words like the
+        kernels do (four small launches, no synchronisation: word 0 becomes 1, the value words stay 0): the torch gathers of
+        the paths off the fused kernels must never see a row >= E (a device-side assert), a negative row wraps silently there,
+        and the layer-by-layer kernels trust the index (only the stream kernel of the fused path clamps it) - a bad candidate
+        row can never become an out-of-bounds read on the device."""
         cand = batch.candidates
         safe = cand.clamp(0, batch.table.num_entities - 1)
         self._status_words(cand.device)[0:1].bitwise_or_((safe != cand).any().view(1).to(torch.int32))
         return IndexedBatch(batch.mention, batch.table, safe, batch.miet_similarity, batch.mtei_similarity)
 
-    def _indexed_training_call(self, batch: "IndexedBatch", planes: bool) -> Optional[_Call]:
-        """The table form of `drin_forward` / `drin_backward` (`drin_batch.entity_index` over tables pooled ahead of time),
-        when the library builds it for this geometry (`indexed_supported` in csrc/api.hip); None: gather the rows."""
-        t, cand = batch.table, batch.candidates
-        D, R = self.cfg.bert_embed_dim, self.cfg.resnet_embed_dim
-        ok = (planes and self.cfg.gcn_edge_feature != "vector"
-              and t.text.dtype == torch.float32 and t.image.dtype == torch.float32 and t.object.dtype == torch.float32
-              and cand.numel() >= 1024 and cand.shape[0] <= 65535 and D % 32 == 0 and R % 32 == 0 and D >= 128
-              and 128 <= R <= 2048 and t.object.shape[1] == 1 and t.image.dim() in (2, 3) and t.object.dim() in (3, 4)
-              and (t.image.dim() == 2 or t.image.shape[1] == 1) and (t.object.dim() == 3 or t.object.shape[2] == 1))
-        if not ok:
-            return None
-        pooled, cls = t.pooled_text(self.cfg)
-        dummy = torch.zeros(cand.shape[0], dtype=torch.int64, device=cand.device)
-        seq = batch.mention + [pooled, dummy, t.image, t.object, t.object_score, batch.miet_similarity, batch.mtei_similarity]
-        # the layer-by-layer kernels trust the index (the stream kernel of the fused path clamps it): clamp here, so that a
-        # bad candidate row can never become an out-of-bounds read on the device - and report it like the kernels do
-        # (four small launches, no synchronisation: word 0 of the status words becomes 1, the value words stay 0)
-        safe = self._clamped(batch).candidates
-        return _Call(self.cfg, seq, self._unfused_precision(), entity_index=safe, entity_text_cls=cls)
-
     @torch.no_grad()
     def _forward_cached(self, call: _Call, table: EntityTable, params) -> torch.Tensor:
         """Table-form inference from the per-entity cache (`drin_forward_cached`)."""
         lib = _lib.load()
-        if call.B == 0:
-            return call.scores()
         self.wait_for_parameters()
         _det, pc = call.param_struct(params)                      # `_det` lives to the end of the call: `pc` points into it
         pbuf = self._prepared.get(call, params, pc)

@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define DRIN_ABI_VERSION 10
+#define DRIN_ABI_VERSION 11
 #define DRIN_API __attribute__((visibility("default")))
 
 typedef enum {
@@ -308,6 +308,12 @@ DRIN_API int drin_linear_bwd(const float* x, const float* w, const float* dy, fl
 DRIN_API int drin_forward(const drin_config* cfg, const drin_batch* batch, const drin_params* params,
                  void* workspace, size_t workspace_bytes, float* scores, int keep_for_backward,
                  const drin_trace* trace, void* stream);
+
+/* DRIN_OK when drin_forward / drin_forward_staged / drin_backward* take `cfg` in table form (drin_batch.entity_index over
+ * tables of cfg.num_entities rows, entity text pooled ahead of time); DRIN_E_UNSUPPORTED (drin_last_error says what the
+ * table form needs): gather the rows on the caller side.  Host-only, like drin_fused_supported; the entry points apply
+ * the same predicate. */
+DRIN_API int drin_indexed_supported(const drin_config* cfg);
 
 /* drin_forward for a training loop that runs the previous step's gradient all-reduce and optimiser update on ANOTHER
  * stream (the reference runs one device, train.py:117-118, and has no counterpart).  `params_ready_event`: a

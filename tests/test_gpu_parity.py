@@ -1337,11 +1337,14 @@ def test_training_reads_entity_tables_through_the_index():
     sd = synth.make_state_dict(cfg, 6)
     model = Model(cfg, precision="bf16x3").to(DEV)
     model.load_state_dict(sd)
-    assert model._indexed_training_call(ib, True) is not None
+    from tests.test_gpu_routing import recorded
     _lib.profile_begin()
-    a = model(ib)
-    a.sum().backward()
+    with recorded() as route:
+        a = model(ib)
+        a.sum().backward()
     prof = _lib.profile_end()
+    assert route == ["pool_fwd p0 f0 E0 T128 c0 B300", "forward_staged p1 f0 E300 T0 c0 B12 idx cls keep1",
+                     "backward_ex p1 f0 E300 T0 c0 B12 idx cls"]
     assert prof["pool"][1] <= 2 + 1          # span + region means (+ the one-off table pooling): no per-pair token pooling
     g1 = [p.grad.clone() if p.grad is not None else None for p in model.parameters()]
     model.zero_grad()
@@ -1369,6 +1372,9 @@ def test_training_reads_entity_tables_through_the_index():
     _fill_params(pc, tuple(p.detach().contiguous() for p in _param_list(model)), bad.per_layer)
     assert lib.drin_forward(C.byref(bad.cfg), C.byref(bad.batch), C.byref(pc), ws.data_ptr(), ws.numel(), sc.data_ptr(), 1, None,
                             torch.cuda.current_stream().cuda_stream) == _lib.E_UNSUPPORTED
+    assert lib.drin_indexed_supported(C.byref(bad.cfg)) == _lib.E_UNSUPPORTED
+    bad.cfg.precision = _lib.PREC_BF16X3                      # the config of the call the model made above
+    assert lib.drin_indexed_supported(C.byref(bad.cfg)) == _lib.OK
 
 
 @pytest.mark.parametrize("seed", range(12))

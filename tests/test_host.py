@@ -460,3 +460,38 @@ def test_library_reports_how_it_runs_the_image_contraction():
     c.num_candidates, c.batch = 101, 64                                                                 # fewer than 128 tiles
     assert lib.drin_image_contraction_passes(C.byref(c), 0) == 3
     assert lib.drin_index_status(None, None) == _lib.E_NULL
+
+
+def test_library_says_which_configs_train_in_table_form():
+    """`drin_indexed_supported` one step either side of every bound of the table form of the layer-by-layer entry points
+    (host-side, no launch).  Expected values read off `indexed_supported` in csrc/api.hip."""
+    import ctypes as C
+    from drin_amd import _lib
+    lib = _lib.load()
+    OK, NO = _lib.OK, _lib.E_UNSUPPORTED
+    base = dict(batch=11, num_candidates=101, embed_dim=128, image_dim=128, entity_objects=1, entity_image_inner=1,
+                entity_object_inner=1, vector_edges=0, precision=_lib.PREC_BF16X3, num_entities=64, entity_tokens=0)
+    for change, want in (
+            (dict(), OK),
+            (dict(batch=341, num_candidates=3), NO), (dict(batch=1024, num_candidates=1), OK),      # 1023 / 1024 pairs
+            (dict(embed_dim=96), NO), (dict(embed_dim=144), NO), (dict(embed_dim=160), OK),       # D >= 128, a multiple of 32
+            (dict(image_dim=96), NO), (dict(image_dim=2048), OK), (dict(image_dim=2080), NO),     # 128 <= R <= 2048
+            (dict(image_dim=144), NO),
+            (dict(batch=65535), OK), (dict(batch=65536), NO),
+            (dict(entity_objects=2), NO),
+            (dict(entity_image_inner=0), OK), (dict(entity_image_inner=2), NO),
+            (dict(entity_object_inner=0), OK), (dict(entity_object_inner=2), NO),
+            (dict(vector_edges=1), NO),
+            (dict(precision=_lib.PREC_F32), NO), (dict(precision=_lib.PREC_BF16X3_ALL), OK),
+            (dict(precision=_lib.PREC_BF16X3_IF16), NO),
+            (dict(num_entities=0), NO), (dict(entity_tokens=8), NO)):
+        c = _lib.DrinConfigC()
+        _lib.check(lib.drin_default_config(C.byref(c)))
+        for k, v in {**base, **change}.items():
+            setattr(c, k, v)
+        assert lib.drin_indexed_supported(C.byref(c)) == want, change
+        if want == NO:
+            assert b"drin_indexed_supported: entity_index needs pooled entity text tables" in lib.drin_last_error(), change
+    assert lib.drin_indexed_supported(None) == _lib.E_NULL
+    c.precision = 2                                                    # not a drin_precision: validate_config speaks first
+    assert lib.drin_indexed_supported(C.byref(c)) == NO and b"precision 2" in lib.drin_last_error()

@@ -1,9 +1,11 @@
 // The GHMFC baseline of the reference (baselines/ghmfc.py, model_type "ghmfc") on gfx950, eval-mode scoring only: the
 // softmax-attention core, LayerNorm with a fused residual, the max over a sequence, the gated mix, and the entry points
 // drin_attention / drin_ghmfc_*.  What the reference computes and how the launches are laid out: DESIGN.md section 15.
+// The attention core also trains: drin_attention_train_fwd keeps the rows' log-sum-exp, drin_attention_bwd is its
+// backward.
 //
 // Every x W^T + b goes through launch_gemm_nt (the GEMM module picks the kernel); the kernels here are everything else.
-// No atomics, no scratch, at most 53 KB of static LDS per workgroup: the same bits every run.
+// No atomics, no scratch, at most 54 KB of static LDS per workgroup: the same bits every run.
 #include "device_utils.h"
 #include "internal.h"
 #include "row_ops.h"
@@ -65,8 +67,8 @@ __device__ __forceinline__ void stage_rows(float* dst, int ds, const float* src,
 template <int KT>
 __global__ void __launch_bounds__(256) k_attention(const float* __restrict__ q, int64_t ldq, const float* __restrict__ k, int64_t ldk,
                                                    const float* __restrict__ v, int64_t ldv, const int64_t* __restrict__ mask,
-                                                   float* __restrict__ out, int64_t ldo, int Lq, int Lk, int dh, float q_scale,
-                                                   int vec) {
+                                                   float* __restrict__ out, int64_t ldo, float* __restrict__ lse, int Lq, int Lk,
+                                                   int dh, float q_scale, int vec) {
   constexpr int G = 64 / KT;             // half-waves of the score phase
   constexpr int RPL = kAttnRows / G;     // query rows per lane there
   __shared__ __attribute__((aligned(16))) float kv[kAttnKvFloats];
@@ -150,10 +152,216 @@ __global__ void __launch_bounds__(256) k_attention(const float* __restrict__ q, 
     const int row = q0 + w * kAttnRows + r;
     if (row >= Lq) continue;
     const float inv = l[r] > 0.f ? 1.0f / l[r] : 0.f;
+    if (lse != nullptr && lane == 0)   // natural log of the row's sum of exp(score); m is in log2 units (q_scale)
+      lse[((int64_t)b * gridDim.y + h) * Lq + row] = l[r] > 0.f ? (m[r] + log2f(l[r])) * 0.69314718055994530942f : ninf;
     float* o = out + ((int64_t)b * Lq + row) * ldo + (int64_t)h * dh;
 #pragma unroll
     for (int c = 0; c < 4; ++c)
       if (lane + 64 * c < dh) o[lane + 64 * c] = acc[r][c] * inv;
+  }
+}
+
+// ---- backward of the softmax-attention core (what autograd runs for ghmfc.py:120,124 under train.py:33-34) -----------
+// With p = exp(s - lse) recomputed from the forward's row statistic, delta_i = sum_c dO[i, c] O[i, c], dp = dO V^T and
+// ds = p (dp - delta):  dQ = ds K / sqrt(dh),  dK = ds^T Q / sqrt(dh),  dV = p^T dO.  Three kernels, no atomics:
+//   k_attention_bwd_delta  one wave per (mention, head, query row): delta into the caller's scratch
+//   k_attention_bwd_dq     one workgroup per (mention, head, QT query rows), loops over tiles of KT keys
+//   k_attention_bwd_dkv    one workgroup per (mention, head, KT keys) owns those keys' dK and dV rows, loops over query tiles
+// Tiles: (KT, QT) = (32, 16) when the padded head dim is <= 128, else (16, 8): Q, dO, K and V tiles are all resident
+// (50 - 54 KB of static LDS).  Every tile row sits at a stride of 4 * odd floats.  The probabilities of a tile are formed
+// one (query, key) pair per thread: the operand that differs over the 16 lanes of a ds_read_b128 group meets 16 different
+// bank quads, the other one is a broadcast.  The products into the gradients run lane = column (consecutive banks) with
+// the tile's p / ds as broadcast reads.  A dropped key, a key past Lk, a row past Lq and a row whose lse is -inf (no
+// kept key) have p = ds = 0 exactly, so their gradient rows are exactly 0.  Gradients are written, not accumulated.
+// LS = DHMAX + 4 floats is the 4 * odd row stride of an instance's widest head dim: what its LDS tiles are sized for.
+__global__ void __launch_bounds__(256) k_attention_bwd_delta(const float* __restrict__ out, int64_t ldo, const float* __restrict__ dout,
+                                                             int64_t lddo, float* __restrict__ delta, int64_t total, int H, int Lq,
+                                                             int dh) {
+  const int lane = threadIdx.x & 63;
+  for (int64_t idx = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); idx < total; idx += (int64_t)gridDim.x * 4) {   // wave-uniform
+    const int64_t bh = idx / Lq;
+    const int i = (int)(idx - bh * Lq), h = (int)(bh % H);
+    const int64_t row = (bh / H) * Lq + i;
+    const float* o = out + row * ldo + (int64_t)h * dh;
+    const float* g = dout + row * lddo + (int64_t)h * dh;
+    float s = 0.f;
+    for (int c = lane; c < dh; c += 64) s = fmaf(o[c], g[c], s);
+    s = wave_sum(s);
+    if (lane == 0) delta[idx] = s;
+  }
+}
+
+// p and ds of one (QT x KT) tile from the staged rows; I_FAST: consecutive threads take consecutive query rows (the result
+// is stored [key][row]), else consecutive keys ([row][key]).  p_out may be NULL.
+template <int KT, int QT, bool I_FAST>
+__device__ __forceinline__ void attn_bwd_tile_probs(const float* qs, const float* gs, const float* ks, const float* vs, int ls, int dhp,
+                                                    const float* lse2, const float* dl, const int* keep, int q_valid,
+                                                    float q_scale, float* p_out, float* ds_out) {
+  const float ninf = -__builtin_inff();
+  for (int t = threadIdx.x; t < QT * KT; t += 256) {
+    const int i = I_FAST ? t % QT : t / KT, j = I_FAST ? t / QT : t % KT;
+    const float *qr = qs + i * ls, *gr = gs + i * ls, *kr = ks + j * ls, *vr = vs + j * ls;
+    float s = 0.f, dp = 0.f;
+    for (int c = 0; c < dhp; c += 4) {
+      const float4 qq = ld4(qr + c), kk = ld4(kr + c), gg = ld4(gr + c), vv = ld4(vr + c);
+      s = fmaf(qq.x, kk.x, fmaf(qq.y, kk.y, fmaf(qq.z, kk.z, fmaf(qq.w, kk.w, s))));
+      dp = fmaf(gg.x, vv.x, fmaf(gg.y, vv.y, fmaf(gg.z, vv.z, fmaf(gg.w, vv.w, dp))));
+    }
+    const float l2 = lse2[i];
+    const bool on = i < q_valid && keep[j] != 0 && l2 != ninf;
+    const float p = on ? exp2f(fmaf(s, q_scale, -l2)) : 0.f;
+    const int o = I_FAST ? j * QT + i : i * KT + j;
+    if (p_out != nullptr) p_out[o] = p;
+    ds_out[o] = on ? p * (dp - dl[i]) : 0.f;
+  }
+}
+
+// the row statistics of QT query rows from q0 on: lse in log2 units, delta; rows past Lq: -inf, 0
+template <int QT>
+__device__ __forceinline__ void attn_bwd_stage_stats(float* lse2, float* dl, const float* lse, const float* delta, int64_t at,
+                                                     int q_valid) {
+  if (threadIdx.x < QT) {
+    const bool ok = (int)threadIdx.x < q_valid;
+    lse2[threadIdx.x] = ok ? lse[at + threadIdx.x] * 1.44269504088896340736f : -__builtin_inff();
+    dl[threadIdx.x] = ok ? delta[at + threadIdx.x] : 0.f;
+  }
+}
+
+template <int KT, int QT, int DHMAX>
+__global__ void __launch_bounds__(256) k_attention_bwd_dq(const float* __restrict__ q, int64_t ldq, const float* __restrict__ k, int64_t ldk,
+                                                          const float* __restrict__ v, int64_t ldv, const int64_t* __restrict__ mask,
+                                                          const float* __restrict__ lse, const float* __restrict__ dout, int64_t lddo,
+                                                          const float* __restrict__ delta, float* __restrict__ dq, int64_t lddq, int Lq,
+                                                          int Lk, int dh, float q_scale, float out_scale, int vec) {
+  constexpr int LS = DHMAX + 4, RPW = QT / 4, SLOTS = DHMAX / 64;
+  __shared__ __attribute__((aligned(16))) float qs[QT * LS];
+  __shared__ __attribute__((aligned(16))) float gs[QT * LS];
+  __shared__ __attribute__((aligned(16))) float ks[KT * LS];
+  __shared__ __attribute__((aligned(16))) float vs[KT * LS];
+  __shared__ __attribute__((aligned(16))) float dst[KT * QT];   // ds, [key][row]
+  __shared__ float lse2[QT], dl[QT];
+  __shared__ int keep[KT];
+  const int b = blockIdx.z, h = blockIdx.y, H = gridDim.y, q0 = blockIdx.x * QT;
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int dhp = (dh + 3) & ~3, ls = 4 * ((dhp >> 2) | 1);
+  const int q_valid = Lq - q0 < QT ? Lq - q0 : QT;
+  stage_rows(qs, ls, q + ((int64_t)b * Lq + q0) * ldq + (int64_t)h * dh, ldq, QT, q_valid, dh, dhp, vec != 0, 1.0f);
+  stage_rows(gs, ls, dout + ((int64_t)b * Lq + q0) * lddo + (int64_t)h * dh, lddo, QT, q_valid, dh, dhp, vec != 0, 1.0f);
+  attn_bwd_stage_stats<QT>(lse2, dl, lse, delta, ((int64_t)b * H + h) * Lq + q0, q_valid);
+  k += (int64_t)b * Lk * ldk + (int64_t)h * dh;
+  v += (int64_t)b * Lk * ldv + (int64_t)h * dh;
+  if (mask != nullptr) mask += (int64_t)b * Lk;
+
+  float acc[RPW][SLOTS];
+#pragma unroll
+  for (int r = 0; r < RPW; ++r)
+#pragma unroll
+    for (int c = 0; c < SLOTS; ++c) acc[r][c] = 0.f;
+
+  for (int j0 = 0; j0 < Lk; j0 += KT) {
+    const int jn = Lk - j0 < KT ? Lk - j0 : KT;
+    __syncthreads();   // the previous tile's K and ds have been read (first tile: nothing)
+    stage_rows(ks, ls, k + j0 * ldk, ldk, KT, jn, dh, dhp, vec != 0, 1.0f);
+    stage_rows(vs, ls, v + j0 * ldv, ldv, KT, jn, dh, dhp, vec != 0, 1.0f);
+    if (threadIdx.x < KT) keep[threadIdx.x] = (int)threadIdx.x < jn && (mask == nullptr || mask[j0 + threadIdx.x] != 0);
+    __syncthreads();
+    attn_bwd_tile_probs<KT, QT, true>(qs, gs, ks, vs, ls, dhp, lse2, dl, keep, q_valid, q_scale, nullptr, dst);
+    __syncthreads();
+    for (int jj = 0; jj < jn; ++jj) {
+      float d[RPW];
+#pragma unroll
+      for (int r = 0; r < RPW; ++r) d[r] = dst[jj * QT + w * RPW + r];
+      const float* kr = ks + jj * ls + lane;
+#pragma unroll
+      for (int c = 0; c < SLOTS; ++c)
+        if (64 * c < dh) {   // uniform; a lane past dh in the last slot reads inside ks and is never stored
+          const float kk = kr[64 * c];
+#pragma unroll
+          for (int r = 0; r < RPW; ++r) acc[r][c] = fmaf(d[r], kk, acc[r][c]);
+        }
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < RPW; ++r) {
+    const int row = q0 + w * RPW + r;
+    if (row >= Lq) continue;
+    float* o = dq + ((int64_t)b * Lq + row) * lddq + (int64_t)h * dh;
+#pragma unroll
+    for (int c = 0; c < SLOTS; ++c)
+      if (lane + 64 * c < dh) o[lane + 64 * c] = acc[r][c] * out_scale;
+  }
+}
+
+template <int KT, int QT, int DHMAX>
+__global__ void __launch_bounds__(256) k_attention_bwd_dkv(const float* __restrict__ q, int64_t ldq, const float* __restrict__ k, int64_t ldk,
+                                                           const float* __restrict__ v, int64_t ldv, const int64_t* __restrict__ mask,
+                                                           const float* __restrict__ lse, const float* __restrict__ dout, int64_t lddo,
+                                                           const float* __restrict__ delta, float* __restrict__ dk, int64_t lddk,
+                                                           float* __restrict__ dv, int64_t lddv, int Lq, int Lk, int dh, float q_scale,
+                                                           float out_scale, int vec) {
+  constexpr int LS = DHMAX + 4, KPW = KT / 4, SLOTS = DHMAX / 64;
+  __shared__ __attribute__((aligned(16))) float qs[QT * LS];
+  __shared__ __attribute__((aligned(16))) float gs[QT * LS];
+  __shared__ __attribute__((aligned(16))) float ks[KT * LS];
+  __shared__ __attribute__((aligned(16))) float vs[KT * LS];
+  __shared__ __attribute__((aligned(16))) float ps[QT * KT];    // p, [row][key]
+  __shared__ __attribute__((aligned(16))) float dss[QT * KT];   // ds, [row][key]
+  __shared__ float lse2[QT], dl[QT];
+  __shared__ int keep[KT];
+  const int b = blockIdx.z, h = blockIdx.y, H = gridDim.y, j0 = blockIdx.x * KT;
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int dhp = (dh + 3) & ~3, ls = 4 * ((dhp >> 2) | 1);
+  const int jn = Lk - j0 < KT ? Lk - j0 : KT;
+  stage_rows(ks, ls, k + ((int64_t)b * Lk + j0) * ldk + (int64_t)h * dh, ldk, KT, jn, dh, dhp, vec != 0, 1.0f);
+  stage_rows(vs, ls, v + ((int64_t)b * Lk + j0) * ldv + (int64_t)h * dh, ldv, KT, jn, dh, dhp, vec != 0, 1.0f);
+  if (threadIdx.x < KT)
+    keep[threadIdx.x] = (int)threadIdx.x < jn && (mask == nullptr || mask[(int64_t)b * Lk + j0 + threadIdx.x] != 0);
+  q += (int64_t)b * Lq * ldq + (int64_t)h * dh;
+  dout += (int64_t)b * Lq * lddo + (int64_t)h * dh;
+
+  float accv[KPW][SLOTS], acck[KPW][SLOTS];
+#pragma unroll
+  for (int r = 0; r < KPW; ++r)
+#pragma unroll
+    for (int c = 0; c < SLOTS; ++c) accv[r][c] = 0.f, acck[r][c] = 0.f;
+
+  for (int q0 = 0; q0 < Lq; q0 += QT) {
+    const int q_valid = Lq - q0 < QT ? Lq - q0 : QT;
+    __syncthreads();   // the previous tile's Q, dO, p and ds have been read (first tile: nothing)
+    stage_rows(qs, ls, q + q0 * ldq, ldq, QT, q_valid, dh, dhp, vec != 0, 1.0f);
+    stage_rows(gs, ls, dout + q0 * lddo, lddo, QT, q_valid, dh, dhp, vec != 0, 1.0f);
+    attn_bwd_stage_stats<QT>(lse2, dl, lse, delta, ((int64_t)b * H + h) * Lq + q0, q_valid);
+    __syncthreads();
+    attn_bwd_tile_probs<KT, QT, false>(qs, gs, ks, vs, ls, dhp, lse2, dl, keep, q_valid, q_scale, ps, dss);
+    __syncthreads();
+    for (int i = 0; i < q_valid; ++i) {
+      float pp[KPW], dd[KPW];
+#pragma unroll
+      for (int r = 0; r < KPW; ++r) pp[r] = ps[i * KT + w * KPW + r], dd[r] = dss[i * KT + w * KPW + r];
+#pragma unroll
+      for (int c = 0; c < SLOTS; ++c)
+        if (64 * c < dh) {   // uniform; a lane past dh in the last slot reads inside qs / gs and is never stored
+          const float gg = gs[i * ls + lane + 64 * c], qq = qs[i * ls + lane + 64 * c];
+#pragma unroll
+          for (int r = 0; r < KPW; ++r) {
+            accv[r][c] = fmaf(pp[r], gg, accv[r][c]);
+            acck[r][c] = fmaf(dd[r], qq, acck[r][c]);
+          }
+        }
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < KPW; ++r) {
+    const int key = j0 + w * KPW + r;
+    if (key >= Lk) continue;
+    float* ok = dk + ((int64_t)b * Lk + key) * lddk + (int64_t)h * dh;
+    float* ov = dv + ((int64_t)b * Lk + key) * lddv + (int64_t)h * dh;
+#pragma unroll
+    for (int c = 0; c < SLOTS; ++c)
+      if (lane + 64 * c < dh) {
+        ok[lane + 64 * c] = acck[r][c] * out_scale;
+        ov[lane + 64 * c] = accv[r][c];
+      }
   }
 }
 
@@ -266,7 +474,7 @@ int check_attention_shape(int64_t B, int H, int Lq, int Lk, int dh) {
 }
 
 int launch_attention(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv, const int64_t* mask,
-                     float* out, int64_t ldo, int B, int H, int Lq, int Lk, int dh, hipStream_t st) {
+                     float* out, int64_t ldo, int B, int H, int Lq, int Lk, int dh, hipStream_t st, float* lse = nullptr) {
   DRIN_TRY(check_attention_shape(B, H, Lq, Lk, dh));
   const int64_t E = (int64_t)H * dh;
   if (ldq < E || ldk < E || ldv < E || ldo < E) {
@@ -279,9 +487,48 @@ int launch_attention(const float* q, int64_t ldq, const float* k, int64_t ldk, c
   const dim3 grid((unsigned)cdiv(Lq, kAttnQT), (unsigned)H, (unsigned)B);
   return timed(DRIN_KC_ATTN, st, "k_attention", [&] {
     if (((dh + 3) & ~3) <= 128)
-      hipLaunchKernelGGL(k_attention<64>, grid, dim3(256), 0, st, q, ldq, k, ldk, v, ldv, mask, out, ldo, Lq, Lk, dh, q_scale, (int)vec);
+      hipLaunchKernelGGL(k_attention<64>, grid, dim3(256), 0, st, q, ldq, k, ldk, v, ldv, mask, out, ldo, lse, Lq, Lk, dh, q_scale, (int)vec);
     else
-      hipLaunchKernelGGL(k_attention<32>, grid, dim3(256), 0, st, q, ldq, k, ldk, v, ldv, mask, out, ldo, Lq, Lk, dh, q_scale, (int)vec);
+      hipLaunchKernelGGL(k_attention<32>, grid, dim3(256), 0, st, q, ldq, k, ldk, v, ldv, mask, out, ldo, lse, Lq, Lk, dh, q_scale, (int)vec);
+  });
+}
+
+// dq may be NULL (skipped); dk and dv are both given or both NULL.  delta: [B, H, Lq] floats of scratch.
+int launch_attention_bwd(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv, const int64_t* mask,
+                         const float* out, int64_t ldo, const float* lse, const float* dout, int64_t lddo, float* dq, int64_t lddq,
+                         float* dk, int64_t lddk, float* dv, int64_t lddv, float* delta, int B, int H, int Lq, int Lk, int dh,
+                         hipStream_t st) {
+  const bool vec = dh % 4 == 0 && ldq % 4 == 0 && ldk % 4 == 0 && ldv % 4 == 0 && lddo % 4 == 0 && aligned16(q) && aligned16(k) &&
+                   aligned16(v) && aligned16(dout);
+  const float inv_sqrt = 1.0f / sqrtf((float)dh), q_scale = 1.44269504088896340736f * inv_sqrt;
+  const bool wide = ((dh + 3) & ~3) > 128;
+  const int KT = wide ? 16 : 32, QT = wide ? 8 : 16;
+  const int64_t rows = (int64_t)B * H * Lq;
+  DRIN_TRY(timed(DRIN_KC_ATTN, st, "k_attention_bwd_delta", [&] {
+    const int64_t blocks = cdiv(rows, 4);
+    hipLaunchKernelGGL(k_attention_bwd_delta, dim3((unsigned)(blocks < (1 << 20) ? blocks : (1 << 20))), dim3(256), 0, st, out, ldo, dout,
+                       lddo, delta, rows, H, Lq, dh);
+  }));
+  if (dq != nullptr) {
+    const dim3 grid((unsigned)cdiv(Lq, QT), (unsigned)H, (unsigned)B);
+    DRIN_TRY(timed(DRIN_KC_ATTN, st, "k_attention_bwd_dq", [&] {
+      if (!wide)
+        hipLaunchKernelGGL((k_attention_bwd_dq<32, 16, 128>), grid, dim3(256), 0, st, q, ldq, k, ldk, v, ldv, mask, lse, dout, lddo, delta,
+                           dq, lddq, Lq, Lk, dh, q_scale, inv_sqrt, (int)vec);
+      else
+        hipLaunchKernelGGL((k_attention_bwd_dq<16, 8, 256>), grid, dim3(256), 0, st, q, ldq, k, ldk, v, ldv, mask, lse, dout, lddo, delta,
+                           dq, lddq, Lq, Lk, dh, q_scale, inv_sqrt, (int)vec);
+    }));
+  }
+  if (dk == nullptr) return DRIN_OK;
+  const dim3 grid((unsigned)cdiv(Lk, KT), (unsigned)H, (unsigned)B);
+  return timed(DRIN_KC_ATTN, st, "k_attention_bwd_dkv", [&] {
+    if (!wide)
+      hipLaunchKernelGGL((k_attention_bwd_dkv<32, 16, 128>), grid, dim3(256), 0, st, q, ldq, k, ldk, v, ldv, mask, lse, dout, lddo, delta,
+                         dk, lddk, dv, lddv, Lq, Lk, dh, q_scale, inv_sqrt, (int)vec);
+    else
+      hipLaunchKernelGGL((k_attention_bwd_dkv<16, 8, 256>), grid, dim3(256), 0, st, q, ldq, k, ldk, v, ldv, mask, lse, dout, lddo, delta,
+                         dk, lddk, dv, lddv, Lq, Lk, dh, q_scale, inv_sqrt, (int)vec);
   });
 }
 
@@ -429,6 +676,53 @@ int drin_attention(const float* q, int64_t ldq, const float* k, int64_t ldk, con
   }
   DRIN_BIND_DEVICE(stream, out, "drin_attention");
   return launch_attention(q, ldq, k, ldk, v, ldv, key_mask, out, ldo, batch, num_heads, q_len, k_len, head_dim, (hipStream_t)stream);
+}
+
+int drin_attention_train_fwd(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv,
+                             const int64_t* key_mask, float* out, int64_t ldo, float* lse, int32_t batch, int32_t num_heads,
+                             int32_t q_len, int32_t k_len, int32_t head_dim, void* stream) {
+  DRIN_TRY(check_attention_shape(batch, num_heads, q_len, k_len, head_dim));
+  if (!q || !k || !v || !out || !lse) {
+    set_error("drin_attention_train_fwd: q / k / v / out / lse is NULL");
+    return DRIN_E_NULL;
+  }
+  const int64_t E = (int64_t)num_heads * head_dim;
+  if (ldq < E || ldk < E || ldv < E || ldo < E) {   // (launch_attention's check, ahead of the device binding: host-only)
+    set_error("drin_attention_train_fwd: row strides ldq, ldk, ldv, ldo (%lld, %lld, %lld, %lld) must be >= heads * head_dim = %lld",
+              (long long)ldq, (long long)ldk, (long long)ldv, (long long)ldo, (long long)E);
+    return DRIN_E_SHAPE;
+  }
+  DRIN_BIND_DEVICE(stream, out, "drin_attention_train_fwd");
+  return launch_attention(q, ldq, k, ldk, v, ldv, key_mask, out, ldo, batch, num_heads, q_len, k_len, head_dim, (hipStream_t)stream,
+                          lse);
+}
+
+int drin_attention_bwd(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv, const int64_t* key_mask,
+                       const float* out, int64_t ldo, const float* lse, const float* dout, int64_t lddo, float* dq, int64_t lddq,
+                       float* dk, int64_t lddk, float* dv, int64_t lddv, float* delta_scratch, int32_t batch, int32_t num_heads,
+                       int32_t q_len, int32_t k_len, int32_t head_dim, void* stream) {
+  DRIN_TRY(check_attention_shape(batch, num_heads, q_len, k_len, head_dim));
+  if (!q || !k || !v || !out || !lse || !dout || !delta_scratch) {
+    set_error("drin_attention_bwd: q / k / v / out / lse / dout / delta_scratch is NULL");
+    return DRIN_E_NULL;
+  }
+  if ((dk == nullptr) != (dv == nullptr)) {
+    set_error("drin_attention_bwd: dk and dv are both given or both NULL (dk %s, dv %s)", dk ? "given" : "NULL", dv ? "given" : "NULL");
+    return DRIN_E_NULL;
+  }
+  const int64_t E = (int64_t)num_heads * head_dim;
+  const struct { const char* name; int64_t ld; bool used; } strides[] = {
+      {"ldq", ldq, true}, {"ldk", ldk, true}, {"ldv", ldv, true}, {"ldo", ldo, true}, {"lddo", lddo, true},
+      {"lddq", lddq, dq != nullptr}, {"lddk", lddk, dk != nullptr}, {"lddv", lddv, dv != nullptr}};
+  for (const auto& s : strides)
+    if (s.used && s.ld < E) {
+      set_error("drin_attention_bwd: row stride %s = %lld must be >= heads * head_dim = %lld", s.name, (long long)s.ld, (long long)E);
+      return DRIN_E_SHAPE;
+    }
+  if (!dq && !dk) return DRIN_OK;
+  DRIN_BIND_DEVICE(stream, delta_scratch, "drin_attention_bwd");
+  return launch_attention_bwd(q, ldq, k, ldk, v, ldv, key_mask, out, ldo, lse, dout, lddo, dq, lddq, dk, lddk, dv, lddv, delta_scratch,
+                              batch, num_heads, q_len, k_len, head_dim, (hipStream_t)stream);
 }
 
 size_t drin_ghmfc_workspace_bytes(const drin_ghmfc_config* cfg) {

@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define DRIN_ABI_VERSION 11
+#define DRIN_ABI_VERSION 12
 #define DRIN_API __attribute__((visibility("default")))
 
 typedef enum {
@@ -602,6 +602,31 @@ DRIN_API int drin_attention(const float* q, int64_t ldq, const float* k, int64_t
                             const int64_t* key_mask, float* out, int64_t ldo, int32_t batch, int32_t num_heads, int32_t q_len,
                             int32_t k_len, int32_t head_dim, void* stream);
 
+/* drin_attention for training: the same kernel (out has drin_attention's bits) also writes the row statistic the backward
+ * recomputes the probabilities from: lse [batch, num_heads, q_len] = log sum_j exp(score) (natural log) over the kept keys
+ * of the scaled scores, -inf for a row with no kept key (its out row is zero).  The forward half of what
+ * nn.MultiheadAttention runs between its projections at ghmfc.py:120,124 when train.py:33-34 backpropagates. */
+DRIN_API int drin_attention_train_fwd(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv,
+                                      const int64_t* key_mask, float* out, int64_t ldo, float* lse, int32_t batch,
+                                      int32_t num_heads, int32_t q_len, int32_t k_len, int32_t head_dim, void* stream);
+
+/* Backward of the core (what autograd does for ghmfc.py:120,124 under train.py:33-34).  q, k, v, key_mask: the forward's
+ * operands; out, lse: what drin_attention_train_fwd wrote; dout [batch * q_len, E] with row stride lddo: the gradient of out.
+ * With p = exp(score - lse), delta[i] = sum_c dout[i, c] out[i, c] and ds = p (dout v^T - delta):
+ *   dq = ds k / sqrt(head_dim)      [batch * q_len, E], row stride lddq   (may be NULL: not computed)
+ *   dk = ds^T q / sqrt(head_dim)    [batch * k_len, E], row stride lddk
+ *   dv = p^T dout                   [batch * k_len, E], row stride lddv   (dk and dv: both given or both NULL)
+ * Gradients are WRITTEN, not accumulated, and only into their own E columns of each row (strides >= E; dK | dV packed in one
+ * [rows, 2 E] buffer are dk = buf, dv = buf + E, lddk = lddv = 2 E).  A dropped key's dk and dv rows are exactly 0; a query
+ * row with no kept key has a dq row of exactly 0 and adds nothing to dk or dv.  delta_scratch: [batch, num_heads, q_len]
+ * floats, overwritten.  fp32 FMA, no atomics (a workgroup owns its query rows / its keys): the same bits every run, and the
+ * bits of dk and dv do not depend on whether dq is asked for.  Limits as drin_attention. */
+DRIN_API int drin_attention_bwd(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv,
+                                const int64_t* key_mask, const float* out, int64_t ldo, const float* lse, const float* dout,
+                                int64_t lddo, float* dq, int64_t lddq, float* dk, int64_t lddk, float* dv, int64_t lddv,
+                                float* delta_scratch, int32_t batch, int32_t num_heads, int32_t q_len, int32_t k_len,
+                                int32_t head_dim, void* stream);
+
 /* ---- in-process kernel timing (bench.py's roofline leg) ---------------------------------------- */
 
 /* Kernel classes the launches are attributed to. */
@@ -616,7 +641,7 @@ typedef enum {
   DRIN_KC_OPTIM = 7,       /* drin_adam_step                                                        */
   DRIN_KC_LSTM = 8,        /* drin_melhi_*: one step of the long LSTM recurrences (forward or backward) */
   DRIN_KC_CELL = 9,        /* drin_melhi_*: mask, time-0 cells, gathers and their backward           */
-  DRIN_KC_ATTN = 10,       /* drin_attention / drin_ghmfc_forward: k_attention, the softmax-attention core    */
+  DRIN_KC_ATTN = 10,       /* drin_attention* / drin_ghmfc_forward: the softmax-attention core and its backward */
   DRIN_KC_NORM = 11,       /* drin_ghmfc_forward: LayerNorm (+ residual), max over a sequence, the gated mix  */
   DRIN_KC_COUNT = 12
 } drin_kernel_class;

@@ -85,6 +85,31 @@ DeviceScope::~DeviceScope() {
   if (switched) (void)hipSetDevice(prev);
 }
 
+// ---- the library's side stream of a device (internal.h: SideLane) --------------------------------
+static SideLane g_side_lanes[64];
+static std::mutex g_side_lanes_mutex;
+
+int side_lane(SideLane** out) {
+  const int dev = call_device();
+  if (dev < 0 || dev >= 64) {
+    set_error("side stream: device %d outside the 64 the library keeps state for", dev);
+    return DRIN_E_UNSUPPORTED;
+  }
+  SideLane& lane = g_side_lanes[dev];
+  if (!lane.ready.load(std::memory_order_acquire)) {
+    std::lock_guard<std::mutex> lock(g_side_lanes_mutex);
+    if (!lane.ready.load(std::memory_order_relaxed)) {
+      hipError_t e = hipStreamCreateWithFlags(&lane.stream, hipStreamNonBlocking);
+      if (e == hipSuccess) e = hipEventCreateWithFlags(&lane.fork, hipEventDisableTiming);
+      if (e == hipSuccess) e = hipEventCreateWithFlags(&lane.join, hipEventDisableTiming);
+      if (e != hipSuccess) return hip_fail(e, "side stream of the device");
+      lane.ready.store(true, std::memory_order_release);
+    }
+  }
+  *out = &lane;
+  return DRIN_OK;
+}
+
 // ---- roctx ranges (opt-in: DRIN_ROCTX) ----------------------------------------------------------
 struct Roctx {
   int (*push)(const char*) = nullptr;

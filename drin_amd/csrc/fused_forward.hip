@@ -111,6 +111,77 @@ static bool if16_gate(const drin_config* c, bool indexed) {
          cdiv(M, 256) * cdiv(c->embed_dim, 256) >= 128;
 }
 
+// The schedule of the gathered-row image contraction x_i C_i^T (forward_prepared_on_stream): row tiles [0, S) as G persistent
+// workgroups on the library's side stream, under the entity stream pass, the rest at full grid behind it.  {0, 0}: one launch on
+// the caller's stream, as under capture.  The contraction reads the batch's image rows in place and the prepared weight planes -
+// nothing the stream pass writes - and a 128 KiB-LDS GEMM workgroup shares no CU with a stream workgroup, so G resident workgroups
+// take G CUs from a pass that does not need all 256 of them.  Only where both kernels' four-phase contract holds (gathered rows,
+// split-bf16 widths, at least kSideMinTiles tiles, the three- or two-pass contraction) and S row tiles lie outside the product's
+// tail split.  G, f and the least tile count: profiles/image_overlap_ab.txt - G in {32, 48, 64, 96} x f in 0.1 .. 0.9 on one resident
+// headline batch: the side part may outlast the stream pass (it goes on under the layer-1 mention chain and x_t C_t^T), so the step
+// falls with f until the side part ends at the join: G = 64, f = 0.9 (side kernel 11.3 ms, join 11.3 ms after the fork; stream pass
+// 8.4 -> 9.6 ms on its 192 CUs; headline 16.00 -> 14.60 ms over fresh processes).  Fewer workgroups cannot finish in time, 96 cost the
+// stream pass and x_t C_t^T more than they save.  Below ~1 200 tiles (B = 1 024 at N = 101) the gain sinks into the noise (B = 512: -3.5 %
+// fp32 rows, -1 .. -3 % bf16 rows), so smaller calls keep the one launch.  (The three macros exist for probe builds of that file's grid.)
+#ifndef DRIN_SIDE_WGS
+#define DRIN_SIDE_WGS 64
+#endif
+#ifndef DRIN_SIDE_PERMILLE
+#define DRIN_SIDE_PERMILLE 900
+#endif
+#ifndef DRIN_SIDE_MIN_TILES
+#define DRIN_SIDE_MIN_TILES 1200
+#endif
+constexpr int kSideWgs = DRIN_SIDE_WGS;             // G
+constexpr int kSidePermille = DRIN_SIDE_PERMILLE;   // f, in thousandths of the row tiles
+constexpr int64_t kSideMinTiles = DRIN_SIDE_MIN_TILES;
+#ifdef DRIN_SIDE_PROBE   // probe builds only (tools/probes/image_overlap_ab.py): G and f set between calls of one process
+static int g_probe_wgs = kSideWgs, g_probe_permille = kSidePermille;
+extern "C" __attribute__((visibility("default"))) void drin_probe_side_plan(int wgs, int permille) { g_probe_wgs = wgs, g_probe_permille = permille; }
+#endif
+struct SidePlan {
+  int64_t S = 0;   // row tiles on the side stream
+  int G = 0;       // persistent workgroups that walk them
+};
+static SidePlan image_side_plan(const drin_config* c, bool indexed, bool capturing) {
+  SidePlan plan;
+  int wgs = kSideWgs, permille = kSidePermille;
+#ifdef DRIN_SIDE_PROBE
+  wgs = g_probe_wgs, permille = g_probe_permille;
+#endif
+  const bool split = c->precision == DRIN_PREC_BF16X3 || c->precision == DRIN_PREC_BF16X3_ALL || c->precision == DRIN_PREC_BF16X3_IF16;
+  if (capturing || indexed || !split || if16_gate(c, indexed) || wgs <= 0 || permille <= 0) return plan;
+  const int D = c->embed_dim, R = c->image_dim;
+  if ((D % 32) || (R % 32) || c->batch <= 0) return plan;
+  const int64_t M = (int64_t)c->batch * c->num_candidates;
+  const int64_t nx = cdiv(D, 256), row_tiles = cdiv(M, 256), tiles = row_tiles * nx;
+  // (192: below it the fp32-row product leaves the 256 x 256 kernel - launch_gemm_nt_bf16x3; the bf16-row one from 129 up)
+  if (tiles < 192 || tiles < kSideMinTiles || tiles > ((int64_t)1 << 28)) return plan;
+  FusedLayout L;
+  L.build(*c);
+  const int64_t whole_rows = gemm_p4_whole_tiles(tiles, R, L.splitk_floats > 0, L.splitk_floats) / nx;
+  int64_t S = (row_tiles * permille + 500) / 1000;
+  S = S < whole_rows ? S : whole_rows;
+  S = S < row_tiles - 1 ? S : row_tiles - 1;   // the plain launch behind the join keeps the last row tile (and the tail split)
+  if (S <= 0) return plan;
+  plan.S = S;
+  plan.G = (int)(wgs < S * nx ? wgs : S * nx);
+  return plan;
+}
+
+// The caller's stream joins the side stream when the call leaves, whatever way it leaves
+struct SideJoin {
+  SideLane* lane = nullptr;
+  hipStream_t st = nullptr;
+  int join() {
+    if (!lane) return DRIN_OK;
+    const hipError_t e = hipStreamWaitEvent(st, lane->join, 0);
+    lane = nullptr;
+    return e == hipSuccess ? DRIN_OK : hip_fail(e, "hipStreamWaitEvent(side stream)");
+  }
+  ~SideJoin() { (void)join(); }
+};
+
 int fused_supported(const drin_config* c) {
   if (c->num_layers != 2) {
     set_error("fused path: built for num_layers == 2 (got %d); use drin_forward", c->num_layers);
@@ -319,6 +390,12 @@ int run_folded_tail(const drin_config* cfg, const drin_params* params, const flo
 // The whole forward on the caller's stream: the one pass over the entity bytes (HBM-bound), then the contractions and row kernels
 // behind it (MFMA-bound).  (Running the two halves of consecutive mention chunks side by side - two streams, forced co-residency,
 // disjoint CU masks - was built in round 3 and measured slower every time; removed in round 5: profiles/r3_pipeline_probe.txt.)
+// One product leaves the caller's stream where image_side_plan engages: the first S row tiles of x_i C_i^T, which depend on nothing
+// the call computes, run as a few persistent workgroups on the library's side stream from the START of the call (fork event first:
+// the previous call's readers of h_image are in front of it; the workgroups are resident before the stream pass is dispatched) and
+// the caller's stream waits for them before it launches the other row tiles at full grid.  Same kernel code and the same tail split
+// per tile as the one launch, so the scores are the same bits.  A captured call (hipStreamIsCapturing) keeps the one launch: no
+// parallel branches in a graph.  Measured: profiles/image_overlap_ab.txt.
 static int forward_prepared_on_stream(const drin_config* cfg, const drin_batch* b, const drin_params* params, const void* prepared,
                                       void* workspace, float* scores, hipStream_t st) {
   FusedLayout L;
@@ -353,6 +430,13 @@ static int forward_prepared_on_stream(const drin_config* cfg, const drin_batch* 
   //  TRAINED the vertex -> score map steepens and 11 candidates average too little - 1.2e-4 after 200 Adam steps, outside the bar;
   //  at N = 101 the same weights give 2e-5: profiles/r4_precision_on_trained_weights.txt)
   const bool if16 = if16_gate(cfg, indexed) && gemm_f16_planes_fits(ws + L.p_xi, R, pb + P.p_cimg_f16, R, ws + L.h_image, D, M, D, R);
+  hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(st, &capture) != hipSuccess) {
+    (void)hipGetLastError();
+    capture = hipStreamCaptureStatusActive;   // a stream that cannot say: the serial order
+  }
+  SidePlan side = image_side_plan(cfg, indexed, capture != hipStreamCaptureStatusNone);
+  if (!aligned16(b->entity_image) || !aligned16(ws + L.h_image) || !b->entity_image) side = SidePlan();   // (the plain launch reports it)
   if (b->entity_text_cls) {
     set_error("drin_forward_prepared: entity_text_cls (text pooled ahead of time) is a form of the training entry points");
     return DRIN_E_UNSUPPORTED;
@@ -386,6 +470,31 @@ static int forward_prepared_on_stream(const drin_config* cfg, const drin_batch* 
   float* hmfu = ws + L.hmfu;
   // pooled entity text stored as bf16 is exact in its hi plane: no lo plane, two MFMAs per tile pair
   const bool xt_exact = bf16_feat && !tokens;
+  // split-K scratch of the pair-sized products: the whole-product split when the batch is a few tiles, else the tail-split scratch
+  const GemmScratch psk = L.pair_splitk_floats ? GemmScratch{ws + L.pair_splitk, L.pair_splitk_floats} : msk;
+  // x_i C_i^T on rows read in place (fp32: split on the fly; bf16: the rows are the one plane), whole or a slice of its row tiles
+  auto image_rows_product = [&](hipStream_t on, RowTiles rows) -> int {
+    const __bf16* ci = reinterpret_cast<const __bf16*>(pb + P.p_cimg);
+    if (bf16_feat)
+      return launch_gemm_x3_planes(b->entity_image, nullptr, R, ci, ci + (size_t)D * R, R, nullptr, ws + L.h_image, D, M, D, R, on, psk.p,
+                                   psk.floats, rows);
+    return launch_gemm_nt_bf16x3_p4((const float*)b->entity_image, R, ci, ci + (size_t)D * R, R, nullptr, ws + L.h_image, D, M, D, R, on, false,
+                                    aligned16(psk.p) ? psk.p : nullptr, psk.floats, rows);
+  };
+  SideJoin side_join;
+  if (side.S > 0) {
+    SideLane* lane = nullptr;
+    DRIN_TRY(side_lane(&lane));
+    std::lock_guard<std::mutex> order(lane->order);
+    hipError_t e = hipEventRecord(lane->fork, st);
+    if (e == hipSuccess) e = hipStreamWaitEvent(lane->stream, lane->fork, 0);
+    if (e != hipSuccess) return hip_fail(e, "fork to the side stream");
+    const int rc = image_rows_product(lane->stream, RowTiles{0, side.S, side.G});
+    e = hipEventRecord(lane->join, lane->stream);
+    side_join.lane = lane, side_join.st = st;
+    if (rc != DRIN_OK) return rc;
+    if (e != hipSuccess) return hip_fail(e, "hipEventRecord(side stream)");
+  }
   // (1) mention-side pooling and vertex-encoder Linears, [hm | fu]; (2) q = fu [W_v1 W_et | W_v1 W_ei]
   DRIN_TRY(run_folded_head(cfg, b, params, pb, P, planes, ws + L.span_mean, ws + L.mimg, vm0, hmfu, msk, st));
   if (dyn)
@@ -447,8 +556,6 @@ static int forward_prepared_on_stream(const drin_config* cfg, const drin_batch* 
   DRIN_TRY(launch_gemm_nt(ws + L.agg1, D, L1.w_h, D, L1.b_h, vm1, D, 2 * (int64_t)B, D, D, false, prec, st, msk.p, msk.floats, wp(P.p_wh1)));
   DRIN_TRY(run_folded_mention_finish(cfg, params, pb, P, planes, vm1, ws + L.hm2, msk, st));
   // (5) the two pair-sized layer-1 contractions on the folded weights
-  // split-K scratch: the whole-product split when the batch is a few tiles, else the tail-split scratch
-  const GemmScratch psk = L.pair_splitk_floats ? GemmScratch{ws + L.pair_splitk, L.pair_splitk_floats} : msk;
   if (planes) {
     const __bf16* ct = reinterpret_cast<const __bf16*>(pb + P.p_ctxt);
     const __bf16* ci = reinterpret_cast<const __bf16*>(pb + P.p_cimg);
@@ -460,7 +567,10 @@ static int forward_prepared_on_stream(const drin_config* cfg, const drin_batch* 
     else if (xi_planes)
       DRIN_TRY(launch_gemm_x3_planes(xi_hi, bf16_feat ? nullptr : xi_hi + MR, R, ci, ci + (size_t)D * R, R, nullptr, ws + L.h_image, D, M,
                                      D, R, st, psk.p, psk.floats));
-    else if (bf16_feat)  // the bf16 image rows are read in place as the (only) plane of the A operand
+    else if (side.S > 0) {   // the row tiles the side stream did not take, once it is done with its own
+      DRIN_TRY(side_join.join());
+      DRIN_TRY(image_rows_product(st, RowTiles{side.S, -1, 0}));
+    } else if (bf16_feat)  // the bf16 image rows are read in place as the (only) plane of the A operand
       DRIN_TRY(launch_gemm_x3_planes(b->entity_image, nullptr, R, ci, ci + (size_t)D * R, R, nullptr, ws + L.h_image, D, M, D, R, st, psk.p,
                                      psk.floats));
     else
@@ -510,6 +620,11 @@ int32_t drin_workgroups_per_mention(const drin_config* cfg, int32_t cached) {
   FusedLayout L;
   L.build(*cfg);
   return L.chunks;
+}
+
+int32_t drin_image_contraction_side_tiles(const drin_config* cfg, int32_t indexed) {
+  if (validate_config(cfg) != DRIN_OK || fused_supported(cfg) != DRIN_OK) return 0;
+  return (int32_t)image_side_plan(cfg, indexed != 0, false).S;
 }
 
 int32_t drin_image_contraction_passes(const drin_config* cfg, int32_t indexed) {

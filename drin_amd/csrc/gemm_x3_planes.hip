@@ -13,6 +13,7 @@
 
 #include "device_utils.h"
 #include "internal.h"
+#include "tile_walk.h"
 
 namespace drin {
 
@@ -27,25 +28,20 @@ constexpr int PLANE_BYTES = 256 * 64;
 constexpr int BUF_BYTES = 4 * PLANE_BYTES;
 constexpr int LDS_BYTES = 2 * BUF_BYTES;
 
-// XCD-aware tile order.  Workgroups are dealt round-robin over the 8 XCDs (id % 8), each with its own L2.
-// The column tiles of one row tile all stream the same A rows, so they should run on ONE XCD at the same
-// time: XCD x takes a contiguous range of the tile sequence (column index fastest).  Without this the
-// A operand is fetched from HBM once per column tile (3x for N = 768).  Placement only affects speed.
-// Tail split (as in gemm_bf16x3.hip): the grid is 1-D; ids below `full` are whole tiles in the XCD order above, the
+// XCD-aware tile order: tile_walk.h.  A launch covers the tiles from position `tile0` of the product's tile sequence on (0: the
+// whole product; row_tile_begin * nx: a slice of row tiles).
+// Tail split (as in gemm_bf16x3.hip): the work items are 1-D; ids below `full` are whole tiles in the XCD order, the
 // `tail_tiles` of a partly filled last round follow as `ksplit` work items each, one per slice of K.
-__device__ __forceinline__ void tile_of_block(int& tile_x, int64_t& tile_y, int nx, unsigned full, int ksplit, int& kpart,
-                                              unsigned& tail_slot) {
-  const unsigned id = blockIdx.x;
+__device__ __forceinline__ void tile_of_block(unsigned id, unsigned tile0, int& tile_x, int64_t& tile_y, int nx, unsigned full, int ksplit,
+                                              int& kpart, unsigned& tail_slot) {
   unsigned t;
   kpart = 0;
   tail_slot = 0;
   if (id < full) {
-    const unsigned xcd = id & 7, k = id >> 3;
-    const unsigned q = full >> 3, rem = full & 7;
-    t = (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + k;
+    t = tile0 + xcd_tile_of_item(id, full);
   } else {
     const unsigned u = id - full;
-    t = full + u / (unsigned)ksplit;
+    t = tile0 + full + u / (unsigned)ksplit;
     kpart = (int)(u % (unsigned)ksplit);
     tail_slot = (u / (unsigned)ksplit) * (unsigned)(ksplit - 1) + (unsigned)(kpart - 1);
   }
@@ -144,7 +140,7 @@ __global__ void __launch_bounds__(THREADS, 2)
   int tx, kpart;
   int64_t ty;
   unsigned tail_slot;
-  tile_of_block(tx, ty, nx, full, ksplit, kpart, tail_slot);
+  tile_of_block(blockIdx.x, 0u, tx, ty, nx, full, ksplit, kpart, tail_slot);
   const int64_t m0 = ty * BM;
   const int n0 = tx * BN;
   if (blockIdx.x >= full) {  // a K-slice of a tail tile
@@ -310,13 +306,16 @@ __device__ __forceinline__ void issue_unit(const Src& s, char* buf, int kb) {
 // 16 x 16 tile takes two MFMAs per K-block (sub-block 0, sub-block 1: the k order of 32-wide blocks), 16 per phase, for half
 // the K-blocks.  Row m of A was divided by row_scale[m] and B by *b_scale when their planes were written (powers of two: exact;
 // fp16's range never matters): the epilogue multiplies output row m by row_scale[m] * *b_scale.
-template <bool A_LO = true, bool F16 = false>
-__global__ void __launch_bounds__(THREADS, 2)
-    k_gemm_x3_planes_p4(const __bf16* __restrict__ a_hi, const __bf16* __restrict__ a_lo, int64_t lda,
-                        const __bf16* __restrict__ b_hi, const __bf16* __restrict__ b_lo, int64_t ldb,
-                        const float* __restrict__ bias, float* __restrict__ C, int64_t ldc, int64_t M, int N, int K, int nx,
-                        unsigned full, int ksplit, float* __restrict__ tail, const float* __restrict__ row_scale,
-                        const float* __restrict__ b_scale) {
+// One work item (`id`: a whole tile, or a K-slice of a tail tile) from the prologue to the last store.  It leaves the workgroup as it
+// found it - nothing in flight (vmcnt(0) before the last barrier; the prologue's own vmcnt(0) drains the epilogue's stores), both
+// wave groups level again, every LDS read behind a barrier - so a persistent workgroup runs it once per tile of its list.
+template <bool A_LO, bool F16>
+__device__ __forceinline__ void p4_planes_item(char* smem, unsigned id, unsigned tile0, const __bf16* __restrict__ a_hi,
+                                               const __bf16* __restrict__ a_lo, int64_t lda, const __bf16* __restrict__ b_hi,
+                                               const __bf16* __restrict__ b_lo, int64_t ldb, const float* __restrict__ bias,
+                                               float* __restrict__ C, int64_t ldc, int64_t M, int N, int K, int nx, unsigned full, int ksplit,
+                                               float* __restrict__ tail, const float* __restrict__ row_scale,
+                                               const float* __restrict__ b_scale) {
   static_assert(!F16 || A_LO, "the fp16 form uses both slots of every unit");
   constexpr int KSTEP = F16 ? 2 * BK : BK;       // elements of K per K-block
   constexpr int KB_BYTES = KSTEP * 2;
@@ -324,15 +323,14 @@ __global__ void __launch_bounds__(THREADS, 2)
     a_lo = a_hi + BK;
     b_lo = b_hi + BK;
   }
-  extern __shared__ __attribute__((aligned(16))) char smem[];
   int tx, kpart;
   int64_t ty;
   unsigned tail_slot;
-  tile_of_block(tx, ty, nx, full, ksplit, kpart, tail_slot);   // ids >= full: K-slices of the tail tiles (as in k_gemm_x3_planes)
+  tile_of_block(id, tile0, tx, ty, nx, full, ksplit, kpart, tail_slot);   // ids >= full: K-slices of the tail tiles (as in k_gemm_x3_planes)
   const int64_t m0 = ty * BM;
   const int n0 = tx * BN;
   int64_t k0 = 0;
-  if (blockIdx.x >= full) {
+  if (id >= full) {
     K /= ksplit;
     k0 = (int64_t)kpart * K;
   }
@@ -516,6 +514,26 @@ __global__ void __launch_bounds__(THREADS, 2)
     }
 }
 
+// PERSIST: gridDim.x workgroups walk the `full` whole tiles of the launch (tile_walk.h: work items g, g + gridDim.x, ...; no tail
+// split, no prefetch across tiles) - a SMALL grid that stays resident on a few CUs beside another kernel.  The 1 411 against 1 365 us
+// of the persistent full-chip walk noted above is what a static list costs against dynamic dispatch; a full grid keeps the plain launch.
+template <bool A_LO = true, bool F16 = false, bool PERSIST = false>
+__global__ void __launch_bounds__(THREADS, 2)
+    k_gemm_x3_planes_p4(const __bf16* __restrict__ a_hi, const __bf16* __restrict__ a_lo, int64_t lda,
+                        const __bf16* __restrict__ b_hi, const __bf16* __restrict__ b_lo, int64_t ldb,
+                        const float* __restrict__ bias, float* __restrict__ C, int64_t ldc, int64_t M, int N, int K, int nx,
+                        unsigned full, int ksplit, float* __restrict__ tail, const float* __restrict__ row_scale,
+                        const float* __restrict__ b_scale, unsigned tile0) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  if (PERSIST) {
+    for (unsigned id = blockIdx.x; id < full; id += gridDim.x)
+      p4_planes_item<A_LO, F16>(smem, id, tile0, a_hi, a_lo, lda, b_hi, b_lo, ldb, bias, C, ldc, M, N, K, nx, full, 1, tail, row_scale, b_scale);
+  } else {
+    p4_planes_item<A_LO, F16>(smem, blockIdx.x, tile0, a_hi, a_lo, lda, b_hi, b_lo, ldb, bias, C, ldc, M, N, K, nx, full, ksplit, tail, row_scale,
+                              b_scale);
+  }
+}
+
 
 // The four-phase pipeline for an fp32 A operand (the image rows of the folded path, the activations of the big training
 // products): the B units stream by LDS-DMA as above; an A unit (128 rows x 32 k of fp32 = 16 KiB) is fetched into registers
@@ -533,18 +551,17 @@ __device__ __forceinline__ void split_store(f32x4v v, char* hi_plane, int off) {
   *reinterpret_cast<bf16x4p*>(hi_plane + 128 * 64 + off) = l;
 }
 
-__global__ void __launch_bounds__(THREADS, 2)
-    k_gemm_bf16x3_p4(const float* __restrict__ A, int64_t lda, const __bf16* __restrict__ b_hi, const __bf16* __restrict__ b_lo,
-                     int64_t ldb, const float* __restrict__ bias, float* __restrict__ C, int64_t ldc, int64_t M, int N, int K,
-                     int accumulate, int nx, unsigned full, int ksplit, float* __restrict__ tail) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
+__device__ __forceinline__ void p4_f32a_item(char* smem, unsigned id, unsigned tile0, const float* __restrict__ A, int64_t lda,
+                                            const __bf16* __restrict__ b_hi, const __bf16* __restrict__ b_lo, int64_t ldb,
+                                            const float* __restrict__ bias, float* __restrict__ C, int64_t ldc, int64_t M, int N, int K,
+                                            int accumulate, int nx, unsigned full, int ksplit, float* __restrict__ tail) {
   int tx, kpart;
   int64_t ty;
   unsigned tail_slot;
-  tile_of_block(tx, ty, nx, full, ksplit, kpart, tail_slot);
+  tile_of_block(id, tile0, tx, ty, nx, full, ksplit, kpart, tail_slot);
   const int64_t m0 = ty * BM;
   const int n0 = tx * BN;
-  if (blockIdx.x >= full) {  // a K-slice of a tail tile
+  if (id >= full) {  // a K-slice of a tail tile
     K /= ksplit;
     const int64_t k0 = (int64_t)kpart * K;
     A += k0;
@@ -795,6 +812,22 @@ __global__ void __launch_bounds__(THREADS, 2)
     }
 }
 
+// PERSIST: as k_gemm_x3_planes_p4 - every tile by the same work-item code, the registers of the A units and the LDS ring set up
+// afresh by each item's prologue
+template <bool PERSIST = false>
+__global__ void __launch_bounds__(THREADS, 2)
+    k_gemm_bf16x3_p4(const float* __restrict__ A, int64_t lda, const __bf16* __restrict__ b_hi, const __bf16* __restrict__ b_lo,
+                     int64_t ldb, const float* __restrict__ bias, float* __restrict__ C, int64_t ldc, int64_t M, int N, int K,
+                     int accumulate, int nx, unsigned full, int ksplit, float* __restrict__ tail, unsigned tile0) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  if (PERSIST) {
+    for (unsigned id = blockIdx.x; id < full; id += gridDim.x)
+      p4_f32a_item(smem, id, tile0, A, lda, b_hi, b_lo, ldb, bias, C, ldc, M, N, K, accumulate, nx, full, 1, tail);
+  } else {
+    p4_f32a_item(smem, blockIdx.x, tile0, A, lda, b_hi, b_lo, ldb, bias, C, ldc, M, N, K, accumulate, nx, full, ksplit, tail);
+  }
+}
+
 // fp32 -> (hi, lo) bf16 planes, 4 values per thread
 __global__ void __launch_bounds__(256) k_split_planes(const float* __restrict__ x, __bf16* __restrict__ hi,
                                                       __bf16* __restrict__ lo, int64_t n4) {
@@ -910,11 +943,43 @@ static void tail_split_256(int64_t tiles, int nkb, const float* tail, size_t tai
     }
 }
 
+int64_t gemm_p4_whole_tiles(int64_t tiles, int K, bool tail_scratch, size_t tail_floats) {
+  alignas(16) static const float some_scratch[4] = {0.f, 0.f, 0.f, 0.f};   // (the split asks whether there is aligned scratch, not where)
+  unsigned full;
+  int ksplit;
+  tail_split_256(tiles, K / x3p::BK, tail_scratch ? some_scratch : nullptr, tail_floats, &full, &ksplit);
+  return (int64_t)full;
+}
+
+// A slice of row tiles (RowTiles, internal.h) against the product's own tail split: the slice's first tile in the tile sequence, how
+// many WHOLE tiles the launch covers and whether the product's tail (K-slices + tail add) belongs to it.  The tail split is always
+// the WHOLE product's, so that every tile is computed the same way whichever launch covers it.
+struct SliceItems {
+  unsigned tile0, whole;
+  bool with_tail;
+};
+static int slice_items(const RowTiles& rows, int64_t row_tiles, int nx, unsigned full, SliceItems* out) {
+  const int64_t begin = rows.begin, end = rows.end < 0 ? row_tiles : rows.end;
+  if (begin < 0 || end > row_tiles || begin > end || rows.wgs < 0) {
+    set_error("gemm p4: row tiles [%lld, %lld) outside the product's %lld", (long long)begin, (long long)end, (long long)row_tiles);
+    return DRIN_E_SHAPE;
+  }
+  out->with_tail = end == row_tiles && rows.wgs == 0;
+  const int64_t last = end == row_tiles ? (int64_t)full : end * nx;   // a slice that ends early must end in the whole tiles
+  if (begin * nx > (int64_t)full || last > (int64_t)full || (end == row_tiles && rows.wgs > 0 && (int64_t)full != row_tiles * nx)) {
+    set_error("gemm p4: a slice of row tiles must lie in the product's whole tiles (the tail split goes with the last plain launch)");
+    return DRIN_E_UNSUPPORTED;
+  }
+  out->tile0 = (unsigned)(begin * nx);
+  out->whole = (unsigned)(last - begin * nx);
+  return DRIN_OK;
+}
+
 // The four-phase pipeline on an fp32 A operand against pre-split weight planes (256 x 256 tiles; DRIN_E_UNSUPPORTED outside
 // its contract: the caller keeps its other kernel).  tail: optional scratch for the tail split, as launch_gemm_nt_bf16x3.
 int launch_gemm_nt_bf16x3_p4(const float* x, int64_t ldx, const void* w_hi, const void* w_lo, int64_t ldw, const float* bias,
                              float* y, int64_t ldy, int64_t M, int N, int K, hipStream_t st, bool accumulate, float* tail,
-                             size_t tail_floats) {
+                             size_t tail_floats, RowTiles rows) {
   if (M <= 0 || N <= 0) return DRIN_OK;
   if (K <= 0 || (K % x3p::BK) || (ldx % 4) || (ldw % 8) || (N % 4) || (ldy % 4) || !aligned16(x) || !aligned16(w_hi) || !aligned16(w_lo) ||
       !aligned16(y) || (bias != nullptr && !aligned16(bias))) {
@@ -927,23 +992,28 @@ int launch_gemm_nt_bf16x3_p4(const float* x, int64_t ldx, const void* w_hi, cons
   unsigned full;
   int ksplit;
   tail_split_256(tiles, K / x3p::BK, tail, tail_floats, &full, &ksplit);
-  const unsigned items = full + ((unsigned)tiles - full) * (unsigned)ksplit;
-  static DynLdsOptIn opt;
-  DRIN_TRY(ensure_dynamic_lds(opt, reinterpret_cast<const void*>(x3p::k_gemm_bf16x3_p4), x3p::p4::LDS, "hipFuncSetAttribute(gemm_bf16x3_p4)"));
+  SliceItems sl;
+  DRIN_TRY(slice_items(rows, cdiv(M, x3p::BM), nx, full, &sl));
+  static DynLdsOptIn opt[2];
+  auto kern = rows.wgs > 0 ? x3p::k_gemm_bf16x3_p4<true> : x3p::k_gemm_bf16x3_p4<false>;
+  DRIN_TRY(ensure_dynamic_lds(opt[rows.wgs > 0 ? 1 : 0], reinterpret_cast<const void*>(kern), x3p::p4::LDS, "hipFuncSetAttribute(gemm_bf16x3_p4)"));
+  const unsigned items = rows.wgs > 0 ? (unsigned)rows.wgs : sl.whole + (sl.with_tail ? ((unsigned)tiles - full) * (unsigned)ksplit : 0u);
+  if (items == 0 || sl.whole + (sl.with_tail ? (unsigned)tiles - full : 0u) == 0) return DRIN_OK;
   {
     KernelTimer timer(DRIN_KC_GEMM_X3, st);
-    hipLaunchKernelGGL(x3p::k_gemm_bf16x3_p4, dim3(items), dim3(x3p::THREADS), x3p::p4::LDS, st, x, ldx, (const __bf16*)w_hi,
-                       (const __bf16*)w_lo, ldw, bias, y, ldy, M, N, K, accumulate ? 1 : 0, nx, full, ksplit, tail);
+    hipLaunchKernelGGL(kern, dim3(items), dim3(x3p::THREADS), x3p::p4::LDS, st, x, ldx, (const __bf16*)w_hi, (const __bf16*)w_lo, ldw, bias, y,
+                       ldy, M, N, K, accumulate ? 1 : 0, nx, sl.whole, ksplit, tail, sl.tile0);
     DRIN_CHECK_LAUNCH("k_gemm_bf16x3_p4");
   }
-  if (ksplit > 1) DRIN_TRY(launch_tail_add_256(tail, y, ldy, M, N, (unsigned)nx, full, (unsigned)tiles - full, ksplit, st));
+  if (ksplit > 1 && sl.with_tail) DRIN_TRY(launch_tail_add_256(tail, y, ldy, M, N, (unsigned)nx, full, (unsigned)tiles - full, ksplit, st));
   return DRIN_OK;
 }
 
 int launch_gemm_x3_planes(const void* a_hi, const void* a_lo, int64_t lda, const void* b_hi, const void* b_lo,
                           int64_t ldb, const float* bias, float* y, int64_t ldy, int64_t M, int N, int K,
-                          hipStream_t st, float* splitk, size_t splitk_floats) {
+                          hipStream_t st, float* splitk, size_t splitk_floats, RowTiles rows) {
   if (M <= 0 || N <= 0) return DRIN_OK;
+  const bool sliced = rows.begin != 0 || rows.end >= 0 || rows.wgs != 0;
   const bool a_lo_plane = a_lo != nullptr;  // NULL: A is exact in bf16 (one plane, two MFMAs per tile pair)
   if (b_lo == nullptr) {
     set_error("gemm_x3_planes: the weight operand needs both planes");
@@ -987,19 +1057,32 @@ int launch_gemm_x3_planes(const void* a_hi, const void* a_lo, int64_t lda, const
   // (an activation operand without a lo plane - exact in bf16 - takes the A_LO = false instantiation from half a round of tiles up;
   //  smaller grids of it keep the two-phase kernel and its split-K forms)
   if ((a_lo_plane || tiles >= 128) && splits == 1 && (N % 4) == 0 && (ldy % 4) == 0 && aligned16(y) && (bias == nullptr || aligned16(bias))) {
-    static DynLdsOptIn opt[2];
-    auto kern = a_lo_plane ? x3p::k_gemm_x3_planes_p4<true, false> : x3p::k_gemm_x3_planes_p4<false, false>;
-    DRIN_TRY(ensure_dynamic_lds(opt[a_lo_plane ? 0 : 1], reinterpret_cast<const void*>(kern), x3p::p4::LDS, "hipFuncSetAttribute(gemm_x3_planes_p4)"));
-    const unsigned p4_items = full + ((unsigned)tiles - full) * (unsigned)ksplit;
+    SliceItems sl;
+    DRIN_TRY(slice_items(rows, mt, nx, full, &sl));
+    const bool persist = rows.wgs > 0;
+    if (persist && a_lo_plane) {
+      set_error("gemm_x3_planes: the persistent grid is built for an activation operand that is exact in bf16 (no lo plane)");
+      return DRIN_E_UNSUPPORTED;
+    }
+    static DynLdsOptIn opt[3];
+    auto kern = persist ? x3p::k_gemm_x3_planes_p4<false, false, true>
+                        : a_lo_plane ? x3p::k_gemm_x3_planes_p4<true, false, false> : x3p::k_gemm_x3_planes_p4<false, false, false>;
+    DRIN_TRY(ensure_dynamic_lds(opt[persist ? 2 : a_lo_plane ? 0 : 1], reinterpret_cast<const void*>(kern), x3p::p4::LDS, "hipFuncSetAttribute(gemm_x3_planes_p4)"));
+    const unsigned p4_items = persist ? (unsigned)rows.wgs : sl.whole + (sl.with_tail ? ((unsigned)tiles - full) * (unsigned)ksplit : 0u);
+    if (p4_items == 0 || sl.whole + (sl.with_tail ? (unsigned)tiles - full : 0u) == 0) return DRIN_OK;
     {
       KernelTimer timer(DRIN_KC_GEMM_PLANES, st);
       hipLaunchKernelGGL(kern, dim3(p4_items), dim3(x3p::THREADS), x3p::p4::LDS, st, (const __bf16*)a_hi,
                          (const __bf16*)(a_lo_plane ? a_lo : a_hi), lda, (const __bf16*)b_hi, (const __bf16*)b_lo, ldb, bias, y, ldy, M, N, K, nx,
-                         full, ksplit, splitk, (const float*)nullptr, (const float*)nullptr);
+                         sl.whole, ksplit, splitk, (const float*)nullptr, (const float*)nullptr, sl.tile0);
       DRIN_CHECK_LAUNCH("k_gemm_x3_planes_p4");
     }
-    if (ksplit > 1) DRIN_TRY(launch_tail_add_256(splitk, y, ldy, M, N, (unsigned)nx, full, (unsigned)tiles - full, ksplit, st));
+    if (ksplit > 1 && sl.with_tail) DRIN_TRY(launch_tail_add_256(splitk, y, ldy, M, N, (unsigned)nx, full, (unsigned)tiles - full, ksplit, st));
     return DRIN_OK;
+  }
+  if (sliced) {
+    set_error("gemm_x3_planes: a slice of row tiles runs on the four-phase kernel only (outside its contract here)");
+    return DRIN_E_UNSUPPORTED;
   }
   const unsigned items = full + ((unsigned)tiles - full) * (unsigned)ksplit;
   dim3 grid(items, 1, (unsigned)splits);
@@ -1049,7 +1132,7 @@ int launch_gemm_f16_planes(const void* a_f16, int64_t lda, const void* b_f16, in
     KernelTimer timer(DRIN_KC_GEMM_X3, st);   // (the class of the product it replaces: x_i C_i^T)
     hipLaunchKernelGGL(kern, dim3(items), dim3(x3p::THREADS), x3p::p4::LDS, st, (const __bf16*)a_f16, (const __bf16*)a_f16, lda,
                        (const __bf16*)b_f16, (const __bf16*)b_f16, ldb, (const float*)nullptr, y, ldy, M, N, K, nx, full, ksplit, tail, row_scale,
-                       b_scale);
+                       b_scale, 0u);
     DRIN_CHECK_LAUNCH("k_gemm_f16_planes");
   }
   if (ksplit > 1) DRIN_TRY(launch_tail_add_256(tail, y, ldy, M, N, (unsigned)nx, full, (unsigned)tiles - full, ksplit, st));

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include <atomic>
+#include <mutex>
 
 #include "../../include/drin_hip.h"
 
@@ -54,6 +55,19 @@ int call_device();
 #define DRIN_BIND_DEVICE(stream, device_pointer, entry_point)               \
   ::drin::DeviceScope _device_scope((stream), (device_pointer), (entry_point)); \
   if (_device_scope.status != DRIN_OK) return _device_scope.status
+
+// One side stream and a fork / join event pair per device, owned by the library for the life of the process: work of a call that
+// does not depend on what the caller's stream is doing (fused_forward.hip: the first row tiles of x_i C_i^T) runs there between
+// `fork` (recorded on the caller's stream) and `join` (recorded on the side stream, waited for by the caller's).  Non-blocking
+// stream, events without timing; created by the first call that needs them - never inside a stream capture, whose calls do not
+// ask for it.  `order` serialises the record + wait pairs of calls from different threads, which share the pair of events.
+struct SideLane {
+  hipStream_t stream = nullptr;
+  hipEvent_t fork = nullptr, join = nullptr;
+  std::mutex order;
+  std::atomic<bool> ready{false};
+};
+int side_lane(SideLane** out);   // the lane of call_device()
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a per-DEVICE attribute of a kernel: one high-water mark per (call site,
 // device), so a process that runs on cuda:0 and later on cuda:1 opts in on both, and a later call that needs more LDS
@@ -196,9 +210,20 @@ struct TnGroup {
 int launch_gemm_tn_group(const TnGroup& g, hipStream_t st, float* scratch, size_t scratch_floats, SliceSum* defer = nullptr);
 // same, operands pre-split into bf16 hi / lo planes (gemm_x3_planes.hip); K % 32 == 0
 // (a_lo NULL: A exact in bf16, two MFMAs per tile pair)
+// RowTiles: a slice of a product on the four-phase 256 x 256 kernels - row tiles [begin, end) (end < 0: to the last one).  wgs > 0:
+// that many PERSISTENT workgroups walk the slice's tiles (tile_walk.h) instead of one workgroup per tile; such a slice holds whole
+// tiles only.  The product's tail split (K-slices of a partly filled last round + tail add) goes with the plain launch that ends at
+// the last row tile.  Every tile is computed by the same code with the same split whichever slice covers it: slices that
+// partition the row tiles write, bit for bit, what one launch of the whole product writes.
+struct RowTiles {
+  int64_t begin = 0, end = -1;
+  int wgs = 0;
+};
+// how many tiles of a `tiles`-tile product (reduction length K, this tail scratch) are computed whole, i.e. outside the tail split
+int64_t gemm_p4_whole_tiles(int64_t tiles, int K, bool tail_scratch, size_t tail_floats);
 int launch_gemm_x3_planes(const void* a_hi, const void* a_lo, int64_t lda, const void* b_hi, const void* b_lo,
                           int64_t ldb, const float* bias, float* y, int64_t ldy, int64_t M, int N, int K,
-                          hipStream_t st, float* splitk = nullptr, size_t splitk_floats = 0);
+                          hipStream_t st, float* splitk = nullptr, size_t splitk_floats = 0, RowTiles rows = RowTiles());
 // y = a b^T in ONE fp16 MFMA pass on single fp16 planes (DRIN_PREC_BF16X3_IF16; gemm_x3_planes.hip): a_f16 [M][K] holds row m of the
 // activation divided by row_scale[m], b_f16 [N][K] the weight divided by *b_scale (powers of two: exact); output row m is multiplied
 // by row_scale[m] * *b_scale.  Whole 256 x 256 tiles, K % 64 == 0, 16-byte aligned: gemm_f16_planes_fits, DRIN_E_UNSUPPORTED otherwise.
@@ -208,7 +233,7 @@ int launch_gemm_f16_planes(const void* a_f16, int64_t lda, const void* b_f16, in
 // the four-phase pipeline (gemm_x3_planes.hip) on an fp32 x against pre-split weight planes: whole 256 x 256 tiles
 int launch_gemm_nt_bf16x3_p4(const float* x, int64_t ldx, const void* w_hi, const void* w_lo, int64_t ldw, const float* bias,
                              float* y, int64_t ldy, int64_t M, int N, int K, hipStream_t st, bool accumulate, float* tail = nullptr,
-                             size_t tail_floats = 0);
+                             size_t tail_floats = 0, RowTiles rows = RowTiles());
 // y[tail tile] += its ksplit - 1 partial 256 x 256 tiles, in order (tail split of the two split-bf16 NT kernels)
 int launch_tail_add_256(const float* tail, float* y, int64_t ldy, int64_t M, int N, unsigned col_tiles, unsigned full,
                         unsigned tail_tiles, int ksplit, hipStream_t st);

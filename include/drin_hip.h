@@ -400,6 +400,13 @@ DRIN_API int32_t drin_workgroups_per_mention(const drin_config* cfg, int32_t cac
  * gate holds: see drin_precision).  The library's own gate, for callers that account executed FLOPs (bench.py). */
 DRIN_API int32_t drin_image_contraction_passes(const drin_config* cfg, int32_t indexed);
 
+/* How an EAGER drin_forward_prepared call schedules that contraction (`indexed` as above): the number of its 256-row tiles that run
+ * as a few persistent workgroups on the library's own side stream, under the entity stream pass, before the caller's stream takes
+ * the rest at full grid; 0 = one launch on the caller's stream (always so for indexed rows, DRIN_PREC_F32, the one-pass fp16
+ * contraction, small calls, and for a call made under stream capture, whatever this returns).  The scores are the same bits either
+ * way.  The library owns one non-blocking side stream per device for this, created by the first call that uses it. */
+DRIN_API int32_t drin_image_contraction_side_tiles(const drin_config* cfg, int32_t indexed);
+
 /* The caller-side check of drin_batch.index_status: waits for `stream` (the ONE entry point that synchronises: it exists to be
  * the point where the caller would synchronise anyway), copies the four words to the host and returns DRIN_OK, or
  * DRIN_E_INDEX with the pair and the value in drin_last_error() - what drin/data.py:87-93 reports as an IndexError - after

@@ -121,6 +121,24 @@ class DrinGhmfcParamsC(C.Structure):   # the 52 state-dict tensors, in state-dic
         "b_entity")]
 
 
+class DrinGemmRouteC(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("launches", "family", "bm", "bn", "w_planes", "a_lo", "f16", "persist", "indexed", "accumulate",
+                                         "ksplit", "splits")] + [(n, C.c_int64) for n in ("tiles", "whole_tiles", "tile0", "work_items")]
+
+
+class DrinGemmProbeArgsC(C.Structure):   # drin_gemm_probe: a test and tuning entry, no stability promise beyond struct_size
+    _fields_ = [("struct_size", C.c_size_t), ("op", C.c_int32), ("precision", C.c_int32), ("accumulate", C.c_int32),
+                ("row_tile_wgs", C.c_int32), ("row_tile_begin", C.c_int64), ("row_tile_end", C.c_int64), ("a", C.c_void_p),
+                ("a_lo", C.c_void_p), ("lda", C.c_int64), ("b", C.c_void_p), ("b_hi", C.c_void_p), ("b_lo", C.c_void_p),
+                ("ldb", C.c_int64), ("bias", C.c_void_p), ("y", C.c_void_p), ("ldy", C.c_int64), ("rows", C.c_int64),
+                ("n_out", C.c_int32), ("k", C.c_int32), ("scratch", C.c_void_p), ("scratch_floats", C.c_size_t),
+                ("a_index", C.c_void_p), ("row_scale", C.c_void_p), ("b_scale", C.c_void_p), ("route", DrinGemmRouteC)]
+
+
+PROBE_GEMM_NT, PROBE_GEMM_NT_BF16X3, PROBE_GEMM_NT_BF16X3_P4, PROBE_GEMM_X3_PLANES, PROBE_GEMM_F16_PLANES, PROBE_TO_F16_SCALED = range(1, 7)
+GEMM_FAMILY = {0: "none", 1: "bf16x3", 2: "bf16x3_p4", 3: "planes", 4: "planes_p4", 5: "f32", 6: "f32_gemv"}
+
+
 class DrinTraceC(C.Structure):
     _fields_ = [(n, C.c_void_p * (MAX_LAYERS + 1)) for n in (
         "mention_text_vertex", "mention_image_vertex", "entity_text_vertex", "entity_image_vertex", "edges")]
@@ -173,6 +191,7 @@ EXPORTS = {
     "drin_split_planes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "drin_linear_planes_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
+    "drin_gemm_probe": (C.c_int, [C.POINTER(DrinGemmProbeArgsC), C.c_void_p]),
     "drin_loss_workspace_bytes": (C.c_size_t, [C.c_int32]),
     "drin_triplet_topk": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.POINTER(C.c_int32), C.c_int32,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -10,6 +10,7 @@
 #include <string.h>
 
 #include "fused.h"
+#include "gemm_probe_check.h"
 #include "internal.h"
 #include "layout.h"
 
@@ -31,6 +32,8 @@ int hip_fail(hipError_t e, const char* what) {
 
 // ---- the device of a call (internal.h: DeviceScope) -----------------------------------------------
 static thread_local int g_call_device = -1;
+static thread_local drin_gemm_route g_gemm_route = {};
+drin_gemm_route& gemm_route() { return g_gemm_route; }
 
 int call_device() {
   if (g_call_device >= 0) return g_call_device;
@@ -768,6 +771,52 @@ int drin_linear_bwd(const float* x, const float* w, const float* dy, float* dx, 
   if (dw) DRIN_TRY(launch_gemm_tn(dy, n_out, x, k, dw, k, rows, n_out, k, precision, st, scratch, scratch ? scratch_floats : 0));
   if (db) DRIN_TRY(launch_colsum(dy, db, rows, n_out, st, scratch, scratch ? scratch_floats : 0));
   return DRIN_OK;
+}
+
+int drin_gemm_probe(drin_gemm_probe_args* p, void* stream) {
+  char msg[256];
+  const int bad = gemm_probe_check(p, msg, sizeof msg);   // (host only: before anything asks the runtime about a pointer)
+  if (bad != DRIN_OK) {
+    set_error("%s", msg);
+    if (p != nullptr && p->struct_size == sizeof(drin_gemm_probe_args)) p->route = drin_gemm_route{};
+    return bad;
+  }
+  p->route = drin_gemm_route{};
+  DRIN_BIND_DEVICE(stream, p->y, "drin_gemm_probe");
+  hipStream_t st = (hipStream_t)stream;
+  gemm_route() = drin_gemm_route{};
+  RowTiles rt;
+  rt.begin = p->row_tile_begin, rt.end = p->row_tile_end, rt.wgs = p->row_tile_wgs;
+  float* y = static_cast<float*>(p->y);
+  const float* a = static_cast<const float*>(p->a);
+  const bool acc = p->accumulate != 0;
+  int rc = DRIN_E_UNSUPPORTED;
+  switch (p->op) {
+    case DRIN_PROBE_GEMM_NT:
+      rc = launch_gemm_nt(a, p->lda, static_cast<const float*>(p->b), p->ldb, p->bias, y, p->ldy, p->rows, p->n_out, p->k, acc, p->precision,
+                          st, p->scratch, p->scratch_floats, static_cast<const float*>(p->b_hi));
+      break;
+    case DRIN_PROBE_GEMM_NT_BF16X3:
+      rc = launch_gemm_nt_bf16x3(a, p->lda, static_cast<const float*>(p->b), p->ldb, p->bias, y, p->ldy, p->rows, p->n_out, p->k, st, p->b_hi,
+                                 p->b_lo, acc, p->scratch, p->scratch_floats, p->a_index);
+      break;
+    case DRIN_PROBE_GEMM_NT_BF16X3_P4:
+      rc = launch_gemm_nt_bf16x3_p4(a, p->lda, p->b_hi, p->b_lo, p->ldb, p->bias, y, p->ldy, p->rows, p->n_out, p->k, st, acc, p->scratch,
+                                    p->scratch_floats, rt);
+      break;
+    case DRIN_PROBE_GEMM_X3_PLANES:
+      rc = launch_gemm_x3_planes(p->a, p->a_lo, p->lda, p->b_hi, p->b_lo, p->ldb, p->bias, y, p->ldy, p->rows, p->n_out, p->k, st, p->scratch,
+                                 p->scratch_floats, rt);
+      break;
+    case DRIN_PROBE_GEMM_F16_PLANES:
+      rc = launch_gemm_f16_planes(p->a, p->lda, p->b_hi, p->ldb, p->row_scale, p->b_scale, y, p->ldy, p->rows, p->n_out, p->k, st, p->scratch,
+                                  p->scratch_floats);
+      break;
+    case DRIN_PROBE_TO_F16_SCALED: rc = launch_to_f16_scaled(a, p->y, p->rows, p->scratch, st); break;
+    default: break;
+  }
+  p->route = gemm_route();
+  return rc;
 }
 
 int drin_forward(const drin_config* cfg, const drin_batch* batch, const drin_params* params, void* workspace,

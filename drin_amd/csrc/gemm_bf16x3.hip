@@ -358,6 +358,12 @@ static int launch(const float* x, int64_t ldx, const float* w, const void* w_hi,
   }
   const unsigned items = full + (tiles - full) * (unsigned)ksplit;
   KernelTimer timer(DRIN_KC_GEMM_X3, st);
+  {
+    RouteNote n{DRIN_GEMM_FAMILY_BF16X3, BM, BN};
+    n.w_planes = W_PLANES, n.indexed = a_index != nullptr, n.accumulate = accumulate, n.ksplit = ksplit;
+    n.tiles = tiles, n.whole_tiles = full, n.work_items = items;
+    note_route(n);
+  }
   hipLaunchKernelGGL(kern, dim3(items), dim3(G::THREADS), G::LDS_BYTES, st, x, ldx, w, (const __bf16*)w_hi,
                      (const __bf16*)w_lo, ldw, bias, y, ldy, M, N, K, accumulate ? 1 : 0, (unsigned)nt, full, ksplit, tail, a_index);
   DRIN_CHECK_LAUNCH("k_gemm_bf16x3");
@@ -457,16 +463,19 @@ int launch_gemm_nt_bf16x3(const float* x, int64_t ldx, const float* w, int64_t l
   // Mid-sized products (a few thousand to a few ten thousand rows: the training step at the reference's batch): 64 x 128 tiles
   // fill the chip but run at the L2 -> LDS bandwidth so small a tile needs (SQ counters: an MFMA executing in 0.30 of the
   // cycles, waves parked 0.51 of their time - profiles/r3_mfma_pmc.json).  Where a BM x 256 tile of eight waves comes to at
-  // least three quarters of a whole number of rounds of the chip's 256 CUs, it is taken instead - BM in {96, 128, 160, 192},
+  // least three quarters of a whole number of rounds of the chip's 256 CUs, it is taken instead - BM in {96, 128, 160},
   // the one with the least rounds x rows: 6 464 rows -> 96 (204 tiles), 12 928 -> 160 (243), 25 856 -> 160 (486).  Same
   // box, the B = 64 step's split-bf16 GEMM time 0.730 -> 0.679 ms, B = 128 1.360 -> 1.249 (profiles/r3_tile_shapes_ab.txt).
   // Measured there, NOT adopted and since removed: the same tiles at a fixed BM for every product (0.726 - 0.855 ms), and three
   // stream-K forms (every CU the same number of K-blocks, but below one round every tile is cut and takes a scratch + fix-up
   // path: 64 x 128 0.859, 128 x 256 0.781, 256 x 256 0.955 ms).
+  // (BM = 192 was a fourth candidate until a scan of the gate's whole domain - every M >= 2048 below 192 tiles of 256 x 256, every
+  //  number of column tiles - showed that it is never the one taken: where its rounds fill, 160 or 128 fill one round at fewer
+  //  rows, or 96 ties it at two rounds and the tie goes to the smaller tile.  DESIGN.md section 17.)
   if (!big && M >= 2048 && planes) {
     int best = 0;
     int64_t cost = 0;
-    for (int cand : {192, 160, 128, 96}) {
+    for (int cand : {160, 128, 96}) {
       const int64_t tiles = cdiv(M, cand) * cdiv(N, 256), rounds = cdiv(tiles, x3::kCUs);
       const bool filled = 4 * tiles >= 3 * rounds * (int64_t)x3::kCUs;
       if (filled && (best == 0 || rounds * cand <= cost)) cost = rounds * cand, best = cand;
@@ -475,7 +484,6 @@ int launch_gemm_nt_bf16x3(const float* x, int64_t ldx, const float* w, int64_t l
       case 96: return x3::launch<96, 256, 2, 4, true>(x, ldx, w, w_hi, w_lo, ldw, bias, y, ldy, M, N, K, st, accumulate, nullptr, 0, a_index);
       case 128: return x3::launch<128, 256, 2, 4, true>(x, ldx, w, w_hi, w_lo, ldw, bias, y, ldy, M, N, K, st, accumulate, nullptr, 0, a_index);
       case 160: return x3::launch<160, 256, 2, 4, true>(x, ldx, w, w_hi, w_lo, ldw, bias, y, ldy, M, N, K, st, accumulate, nullptr, 0, a_index);
-      case 192: return x3::launch<192, 256, 2, 4, true>(x, ldx, w, w_hi, w_lo, ldw, bias, y, ldy, M, N, K, st, accumulate, nullptr, 0, a_index);
       default: break;   // no tall tile fills its rounds: the 64 x 128 tiles below
     }
   }

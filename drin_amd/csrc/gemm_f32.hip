@@ -264,6 +264,12 @@ static int launch(const float* A, int64_t lda, const float* B, int64_t ldb, cons
   DRIN_TRY(ensure_dynamic_lds(opt_in, reinterpret_cast<const void*>(kern), (int)lds, "hipFuncSetAttribute(gemm)"));
   dim3 grid((unsigned)cdiv(N, BN), (unsigned)mt, (unsigned)splits);
   KernelTimer timer(DRIN_KC_GEMM, st);
+  if (!A_KMAJOR && !B_KMAJOR) {   // the NT form
+    RouteNote n{DRIN_GEMM_FAMILY_F32, BM, BN};
+    n.a_lo = false, n.accumulate = (flags & GEMM_ACCUMULATE) != 0, n.splits = splits;
+    n.tiles = mt * cdiv(N, BN), n.whole_tiles = n.tiles, n.work_items = n.tiles * splits;
+    note_route(n);
+  }
   hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, A, lda, B, ldb, bias, C, ldc, M, N, K, kps, flags, part_stride);
   DRIN_CHECK_LAUNCH(what);
   return DRIN_OK;
@@ -433,6 +439,11 @@ static int launch_gemv(const float* x, int64_t ldx, const float* w, int64_t ldw,
                        int64_t M, int N, int K, bool accumulate, hipStream_t st) {
   KernelTimer timer(DRIN_KC_GEMM, st);
   const dim3 grid((unsigned)cdiv(N, 4));
+  {
+    RouteNote n{DRIN_GEMM_FAMILY_F32_GEMV, 2, 4};
+    n.a_lo = false, n.accumulate = accumulate, n.tiles = n.whole_tiles = n.work_items = grid.x;
+    note_route(n);
+  }
   hipLaunchKernelGGL(k_gemv_rows<2>, grid, dim3(256), 0, st, x, ldx, w, ldw, bias, y, ldy, (int)M, N, K / 4, accumulate ? 1 : 0);
   DRIN_CHECK_LAUNCH("k_gemv_rows");
   return DRIN_OK;

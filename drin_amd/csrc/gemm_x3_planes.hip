@@ -1001,6 +1001,10 @@ int launch_gemm_nt_bf16x3_p4(const float* x, int64_t ldx, const void* w_hi, cons
   if (items == 0 || sl.whole + (sl.with_tail ? (unsigned)tiles - full : 0u) == 0) return DRIN_OK;
   {
     KernelTimer timer(DRIN_KC_GEMM_X3, st);
+    RouteNote n{DRIN_GEMM_FAMILY_BF16X3_P4, x3p::BM, x3p::BN};
+    n.w_planes = true, n.persist = rows.wgs > 0, n.accumulate = accumulate, n.ksplit = sl.with_tail ? ksplit : 1;
+    n.tiles = tiles, n.whole_tiles = sl.whole, n.tile0 = sl.tile0, n.work_items = items;
+    note_route(n);
     hipLaunchKernelGGL(kern, dim3(items), dim3(x3p::THREADS), x3p::p4::LDS, st, x, ldx, (const __bf16*)w_hi, (const __bf16*)w_lo, ldw, bias, y,
                        ldy, M, N, K, accumulate ? 1 : 0, nx, sl.whole, ksplit, tail, sl.tile0);
     DRIN_CHECK_LAUNCH("k_gemm_bf16x3_p4");
@@ -1072,6 +1076,10 @@ int launch_gemm_x3_planes(const void* a_hi, const void* a_lo, int64_t lda, const
     if (p4_items == 0 || sl.whole + (sl.with_tail ? (unsigned)tiles - full : 0u) == 0) return DRIN_OK;
     {
       KernelTimer timer(DRIN_KC_GEMM_PLANES, st);
+      RouteNote n{DRIN_GEMM_FAMILY_PLANES_P4, x3p::BM, x3p::BN};
+      n.w_planes = true, n.a_lo = a_lo_plane, n.persist = persist, n.ksplit = sl.with_tail ? ksplit : 1;
+      n.tiles = tiles, n.whole_tiles = sl.whole, n.tile0 = sl.tile0, n.work_items = p4_items;
+      note_route(n);
       hipLaunchKernelGGL(kern, dim3(p4_items), dim3(x3p::THREADS), x3p::p4::LDS, st, (const __bf16*)a_hi,
                          (const __bf16*)(a_lo_plane ? a_lo : a_hi), lda, (const __bf16*)b_hi, (const __bf16*)b_lo, ldb, bias, y, ldy, M, N, K, nx,
                          sl.whole, ksplit, splitk, (const float*)nullptr, (const float*)nullptr, sl.tile0);
@@ -1091,6 +1099,10 @@ int launch_gemm_x3_planes(const void* a_hi, const void* a_lo, int64_t lda, const
   {
     KernelTimer timer(DRIN_KC_GEMM_PLANES, st);
     const __bf16 *ah = (const __bf16*)a_hi, *al = (const __bf16*)a_lo, *bh = (const __bf16*)b_hi, *bl = (const __bf16*)b_lo;
+    RouteNote n{DRIN_GEMM_FAMILY_PLANES, x3p::BM, x3p::BN};
+    n.w_planes = true, n.a_lo = a_lo_plane, n.ksplit = ksplit, n.splits = splits;
+    n.tiles = tiles, n.whole_tiles = full, n.work_items = (int64_t)items * splits;
+    note_route(n);
     if (a_lo_plane)
       hipLaunchKernelGGL((x3p::k_gemm_x3_planes<true, true>), grid, dim3(x3p::THREADS), x3p::LDS_BYTES, st, ah, al, lda, bh,
                          bl, ldb, bias, out, ldy, M, N, K, part_stride, nx, full, ksplit, splitk);
@@ -1130,6 +1142,10 @@ int launch_gemm_f16_planes(const void* a_f16, int64_t lda, const void* b_f16, in
   DRIN_TRY(ensure_dynamic_lds(opt, reinterpret_cast<const void*>(kern), x3p::p4::LDS, "hipFuncSetAttribute(gemm_f16_planes)"));
   {
     KernelTimer timer(DRIN_KC_GEMM_X3, st);   // (the class of the product it replaces: x_i C_i^T)
+    RouteNote n{DRIN_GEMM_FAMILY_PLANES_P4, x3p::BM, x3p::BN};
+    n.w_planes = true, n.f16 = true, n.ksplit = ksplit;
+    n.tiles = tiles, n.whole_tiles = full, n.work_items = items;
+    note_route(n);
     hipLaunchKernelGGL(kern, dim3(items), dim3(x3p::THREADS), x3p::p4::LDS, st, (const __bf16*)a_f16, (const __bf16*)a_f16, lda,
                        (const __bf16*)b_f16, (const __bf16*)b_f16, ldb, (const float*)nullptr, y, ldy, M, N, K, nx, full, ksplit, tail, row_scale,
                        b_scale, 0u);

@@ -155,6 +155,25 @@ struct SliceSum {
 };
 int launch_slice_sum(SliceSum& s, hipStream_t st);   // no-op for an empty one
 
+// ---- which NT GEMM form ran (drin_gemm_probe) -----------------------------------------------------
+// This thread's record of the last NT product's GEMM kernel, written by the dispatch code next to the launch itself (a handful of
+// host stores): tests assert it instead of restating the size gates, so a gate that moves cannot leave a form silently untested.
+drin_gemm_route& gemm_route();
+struct RouteNote {
+  int family, bm, bn;
+  bool w_planes = false, a_lo = true, f16 = false, persist = false, indexed = false, accumulate = false;
+  int ksplit = 1, splits = 1;
+  int64_t tiles = 0, whole_tiles = 0, tile0 = 0, work_items = 0;
+};
+inline void note_route(const RouteNote& n) {
+  drin_gemm_route& r = gemm_route();
+  r.launches += 1;
+  r.family = n.family, r.bm = n.bm, r.bn = n.bn;
+  r.w_planes = n.w_planes, r.a_lo = n.a_lo, r.f16 = n.f16, r.persist = n.persist, r.indexed = n.indexed, r.accumulate = n.accumulate;
+  r.ksplit = n.ksplit, r.splits = n.splits;
+  r.tiles = n.tiles, r.whole_tiles = n.whole_tiles, r.tile0 = n.tile0, r.work_items = n.work_items;
+}
+
 // ---- GEMM (gemm_f32.hip) ------------------------------------------------------------------------
 // y[m, n] (+)= sum_k x[m, k] * w[n, k] + bias[n];  x row stride ldx, w row stride ldw, y row stride ldy
 // (splitk: optional scratch; mention-sized exact-fp32 products with K >= 512 then split K over workgroups into it

@@ -443,6 +443,75 @@ DRIN_API int drin_linear_planes_fwd(const void* x_hi, const void* x_lo, const vo
                                     const float* bias, float* y, int64_t rows, int32_t n_out, int32_t k,
                                     void* stream);
 
+/* ---- test and tuning entry into the GEMM module ------------------------------------------------ *
+ * drin_gemm_probe calls ONE of the module's internal NT launchers (y = x w^T (+ bias)) with caller-chosen arguments - leading
+ * dimensions, bias or NULL, accumulate, scratch, weight planes, indexed rows, a slice of row tiles - and reports which kernel
+ * form the module's own dispatch code chose for them.  It exists so that every form behind a size gate can be compared with a
+ * high-precision product on its own (tests/test_gpu_gemm_forms.py) and so that a gate can be tuned from outside; no product
+ * code calls it, and nothing but `struct_size` is promised about it: the struct may change with any version of the library
+ * (a caller built against another layout gets DRIN_E_SHAPE).  Pointers are device pointers unless said otherwise. */
+enum drin_gemm_probe_op {
+  DRIN_PROBE_GEMM_NT = 1,        /* launch_gemm_nt: a fp32 [rows][lda], b fp32 [n_out][ldb]; b_hi: NULL or the weight planes
+                                    ([n_out][k] bf16 hi followed by [n_out][k] bf16 lo); precision; scratch = the split scratch */
+  DRIN_PROBE_GEMM_NT_BF16X3 = 2, /* launch_gemm_nt_bf16x3: a fp32; b fp32 or (b_hi, b_lo) bf16 planes of row stride ldb;
+                                    accumulate; a_index; scratch = the tail-split scratch */
+  DRIN_PROBE_GEMM_NT_BF16X3_P4 = 3, /* launch_gemm_nt_bf16x3_p4: a fp32, (b_hi, b_lo); accumulate; scratch; row tiles */
+  DRIN_PROBE_GEMM_X3_PLANES = 4, /* launch_gemm_x3_planes: (a, a_lo or NULL) and (b_hi, b_lo) bf16 planes; scratch; row tiles */
+  DRIN_PROBE_GEMM_F16_PLANES = 5,/* launch_gemm_f16_planes: a, b_hi single fp16 planes; row_scale [rows], b_scale [1]; scratch */
+  DRIN_PROBE_TO_F16_SCALED = 6   /* launch_to_f16_scaled: a fp32 [rows] (rows = element count, % 4) -> y fp16 [rows] under one
+                                    power-of-two scale, written to scratch[0] (scratch: two floats) */
+};
+enum drin_gemm_family {            /* drin_gemm_route.family */
+  DRIN_GEMM_FAMILY_NONE = 0,       /* nothing was launched */
+  DRIN_GEMM_FAMILY_BF16X3 = 1,     /* k_gemm_bf16x3<bm, bn, ., ., w_planes>: fp32 activation split while staged */
+  DRIN_GEMM_FAMILY_BF16X3_P4 = 2,  /* k_gemm_bf16x3_p4<persist>: fp32 activation on weight planes, four-phase pipeline */
+  DRIN_GEMM_FAMILY_PLANES = 3,     /* k_gemm_x3_planes<a_lo, true>: both operands as planes, two-phase kernel */
+  DRIN_GEMM_FAMILY_PLANES_P4 = 4,  /* k_gemm_x3_planes_p4<a_lo, f16, persist> */
+  DRIN_GEMM_FAMILY_F32 = 5,        /* k_gemm_f32<bm, bn>: exact fp32 */
+  DRIN_GEMM_FAMILY_F32_GEMV = 6    /* k_gemv_rows: exact fp32, a handful of rows */
+};
+typedef struct drin_gemm_route {   /* filled by the dispatch code next to the launch of the product's GEMM kernel */
+  int32_t launches;                /* GEMM kernels launched by the call (tail add and split-K reduction not counted) */
+  int32_t family;                  /* drin_gemm_family of the last one */
+  int32_t bm, bn;                  /* tile */
+  int32_t w_planes, a_lo, f16, persist, indexed, accumulate;   /* 0 / 1 */
+  int32_t ksplit;                  /* K-slices per tile of the tail split carried by this launch (1: none) */
+  int32_t splits;                  /* split K over grid z into the scratch + ordered reduction (1: none) */
+  int64_t tiles;                   /* output tiles of the whole product */
+  int64_t whole_tiles;             /* tiles this launch computes whole, i.e. not as K-slices */
+  int64_t tile0;                   /* its first tile in the product's tile sequence */
+  int64_t work_items;              /* its grid */
+} drin_gemm_route;
+typedef struct drin_gemm_probe_args {
+  size_t struct_size;              /* sizeof(drin_gemm_probe_args) */
+  int32_t op;                      /* drin_gemm_probe_op */
+  int32_t precision;               /* drin_precision (DRIN_PROBE_GEMM_NT) */
+  int32_t accumulate;              /* y += instead of y = */
+  int32_t row_tile_wgs;            /* RowTiles: > 0 = that many persistent workgroups walk the slice */
+  int64_t row_tile_begin, row_tile_end;   /* RowTiles: 256-row tiles [begin, end) of the product; end < 0: to the last one */
+  const void* a;
+  const void* a_lo;
+  int64_t lda;
+  const void* b;
+  const void* b_hi;
+  const void* b_lo;
+  int64_t ldb;
+  const float* bias;               /* [n_out] or NULL */
+  void* y;
+  int64_t ldy;
+  int64_t rows;
+  int32_t n_out, k;
+  float* scratch;                  /* or NULL */
+  size_t scratch_floats;
+  const int64_t* a_index;          /* [rows] or NULL: row m of the activation is row a_index[m] of the table `a` (not range-checked) */
+  const float* row_scale;
+  const float* b_scale;
+  drin_gemm_route route;           /* out (host memory, like the struct itself) */
+} drin_gemm_probe_args;
+/* DRIN_E_NULL / DRIN_E_SHAPE / DRIN_E_UNSUPPORTED from the host checks (NULL struct or required operand, struct_size, negative
+ * shape, a leading dimension below its row, unknown op), else whatever the launcher returns; `route` is filled either way. */
+DRIN_API int drin_gemm_probe(drin_gemm_probe_args* args, void* stream);
+
 /* ---- caller-side loss and metric of one batch --------------------------------- *
  * Replaces, for scores already on the device, `TripletLoss.forward` (common/utils.py:26-43, called at
  * train.py:34) and `TopkAccuracy.update` (utils.py:60-66, train.py:36-37), and the autograd backward of

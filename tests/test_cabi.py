@@ -134,7 +134,8 @@ def test_ctypes_mirrors_match_the_header_layout(tmp_path):
     """Every struct of include/drin_hip.h as a plain C compiler lays it out == its ctypes mirror in drin_amd/_lib.py
     (size and the offset of every field): the binding a maintainer writes from the header alone stays in step."""
     pairs = [("drin_config", _lib.DrinConfigC), ("drin_batch", _lib.DrinBatchC), ("drin_layer_params", _lib.DrinLayerParamsC),
-             ("drin_params", _lib.DrinParamsC), ("drin_param_grads", _lib.DrinParamGradsC), ("drin_trace", _lib.DrinTraceC)]
+             ("drin_params", _lib.DrinParamsC), ("drin_param_grads", _lib.DrinParamGradsC), ("drin_trace", _lib.DrinTraceC),
+             ("drin_gemm_route", _lib.DrinGemmRouteC), ("drin_gemm_probe_args", _lib.DrinGemmProbeArgsC)]
     lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{HEADER}"', 'int main(void) {']
     for cname, cls in pairs:
         lines.append(f'  printf("{cname} %zu\\n", sizeof({cname}));')
@@ -200,6 +201,52 @@ def test_adam_entry_point_validates_on_host():
     assert lib.drin_adam_step(one, one, one, one, 0, *args) == _lib.OK    # nothing to do, nothing launched
     assert lib.drin_adam_step(C.c_void_p(20), one, one, one, 8, *args) == _lib.E_ALIGN
     assert lib.drin_adam_step(one, one, one, one, 8, 0.75, 0.999, 0.001, 1.0, 1e-8, -1e-3, None) == _lib.E_UNSUPPORTED
+
+
+def probe_args(**kw):
+    one = 16   # never dereferenced: every check fails before anything is asked about a pointer
+    a = _lib.DrinGemmProbeArgsC(struct_size=C.sizeof(_lib.DrinGemmProbeArgsC), op=_lib.PROBE_GEMM_X3_PLANES, a=one, b_hi=one, b_lo=one, y=one,
+                                rows=300, n_out=768, k=64, lda=64, ldb=64, ldy=772, row_tile_end=-1)
+    for name, value in kw.items():
+        setattr(a, name, value)
+    return a
+
+
+def test_gemm_probe_validates_on_host():
+    """drin_gemm_probe (the test and tuning entry into the GEMM module): NULL pointers, negative shapes, leading dimensions, struct_size
+    and the op are refused on the host, before a launch and before the runtime is asked about any pointer; the route record of a
+    refused call says that nothing ran.  (The same checks as a stand-alone program under ASan / UBSan: test_gemm_probe_host.py.)"""
+    lib = _lib.load()
+    assert lib.drin_gemm_probe(None, None) == _lib.E_NULL and b"NULL" in lib.drin_last_error()
+
+    def call(**kw):
+        a = probe_args(**kw)
+        a.route.launches, a.route.family = 7, 7
+        rc = lib.drin_gemm_probe(C.byref(a), None)
+        if a.struct_size == C.sizeof(_lib.DrinGemmProbeArgsC):
+            assert (a.route.launches, a.route.family) == (0, 0)
+        else:
+            assert (a.route.launches, a.route.family) == (7, 7)         # a struct of another layout is not written to
+        return rc
+
+    assert call(struct_size=C.sizeof(_lib.DrinGemmProbeArgsC) - 8) == _lib.E_SHAPE and b"struct_size" in lib.drin_last_error()
+    assert call(struct_size=0) == _lib.E_SHAPE
+    assert call(op=0) == _lib.E_UNSUPPORTED and call(op=7) == _lib.E_UNSUPPORTED and b"unknown op 7" in lib.drin_last_error()
+    assert call(a=None) == _lib.E_NULL and call(y=None) == _lib.E_NULL and call(b_lo=None) == _lib.E_NULL
+    assert call(scratch_floats=64) == _lib.E_NULL and b"scratch" in lib.drin_last_error()
+    assert call(rows=-1) == _lib.E_SHAPE and b"rows=-1" in lib.drin_last_error()
+    assert call(n_out=0) == _lib.E_SHAPE and call(k=-32) == _lib.E_SHAPE
+    assert call(lda=63) == _lib.E_SHAPE and b"lda=63" in lib.drin_last_error()
+    assert call(ldb=-64) == _lib.E_SHAPE and call(ldy=767) == _lib.E_SHAPE
+    assert call(row_tile_begin=-1) == _lib.E_SHAPE and call(row_tile_wgs=-8) == _lib.E_SHAPE
+    assert call(a_index=16) == _lib.E_UNSUPPORTED and b"indexed" in lib.drin_last_error()
+    assert call(op=_lib.PROBE_GEMM_NT) == _lib.E_NULL                     # no fp32 weight
+    assert call(op=_lib.PROBE_GEMM_NT, b=16, row_tile_wgs=8) == _lib.E_UNSUPPORTED
+    assert call(op=_lib.PROBE_GEMM_NT_BF16X3, b_lo=None) == _lib.E_NULL   # one weight plane and no fp32 weight
+    assert call(op=_lib.PROBE_GEMM_F16_PLANES) == _lib.E_NULL             # no scales
+    assert call(op=_lib.PROBE_TO_F16_SCALED, scratch=16, scratch_floats=1) == _lib.E_SHAPE and b"two floats" in lib.drin_last_error()
+    assert call(op=_lib.PROBE_TO_F16_SCALED, scratch=16, scratch_floats=2, rows=-4) == _lib.E_SHAPE
+    assert lib.drin_version() == _lib.ABI_VERSION == 12                   # an additive export
 
 
 @pytest.mark.skipif(os.environ.get("DRIN_LIB_PATH") is not None, reason="already running against another build of the library")

@@ -422,33 +422,43 @@ struct InputGradScratch {
   size_t total_floats = 0;
   size_t g_span = 0, g_raw = 0, cls_stage = 0, g_pool = 0, cos3 = 0, g_mimg = 0, g_eimg = 0, g_mobj = 0, g_eobj = 0;
   size_t g_ms = 0, g_es = 0, g_edge = 0, planes_ei = 0, planes_et = 0, miei = 0;
-  size_t take(size_t n) {
-    const size_t o = total_floats;
-    total_floats += (n + 63) & ~(size_t)63;
-    return o;
-  }
   void build(const drin_config& c) {
     const size_t B = (size_t)c.batch, N = (size_t)c.num_candidates, D = (size_t)c.embed_dim, R = (size_t)c.image_dim;
     const size_t M = B * N, Km = (size_t)c.mention_objects, Ke = (size_t)c.entity_objects;
     const bool x3 = c.precision == DRIN_PREC_BF16X3 || c.precision == DRIN_PREC_BF16X3_ALL;
-    total_floats = 0;
-    g_span = take(B * D);
-    g_raw = take(M * D);                                     // text-text edge: gradient of the entity rows it reads
-    cls_stage = take(c.entity_tokens > 0 ? M * D : 0);       // token 0 of every token block, contiguous
-    g_pool = take(c.entity_tokens > 0 ? M * D : 0);
-    cos3 = take(3 * M);
-    g_mimg = take(B * R);
-    g_eimg = take(c.entity_image_inner > 1 ? M * R : 0);
-    g_mobj = take(B * Km * R);
-    g_eobj = take(M * Ke * R);
-    g_ms = take(B * Km);
-    g_es = take(M * Ke);
-    g_edge = take(4 * M);
-    planes_ei = take(x3 ? D * R : 0);                        // bf16 (hi, lo) planes of W_ei^T [R][D]
-    planes_et = take(x3 ? D * D : 0);
-    miei = take(miei_bwd_scratch_floats((int64_t)M, (int)B, (int)Km, (int)Ke));
+    Arena A;
+    g_span = A.take(B * D);
+    g_raw = A.take(M * D);                                     // text-text edge: gradient of the entity rows it reads
+    cls_stage = A.take(c.entity_tokens > 0 ? M * D : 0);       // token 0 of every token block, contiguous
+    g_pool = A.take(c.entity_tokens > 0 ? M * D : 0);
+    cos3 = A.take(3 * M);
+    g_mimg = A.take(B * R);
+    g_eimg = A.take(c.entity_image_inner > 1 ? M * R : 0);
+    g_mobj = A.take(B * Km * R);
+    g_eobj = A.take(M * Ke * R);
+    g_ms = A.take(B * Km);
+    g_es = A.take(M * Ke);
+    g_edge = A.take(4 * M);
+    planes_ei = A.take(x3 ? D * R : 0);                        // bf16 (hi, lo) planes of W_ei^T [R][D]
+    planes_et = A.take(x3 ? D * D : 0);
+    miei = A.take(miei_bwd_scratch_floats((int64_t)M, (int)B, (int)Km, (int)Ke));
+    total_floats = A.total;
   }
 };
+
+static int input_grad_scratch_selfcheck(const drin_config& c) {
+  const size_t B = c.batch, M = B * c.num_candidates, D = c.embed_dim, R = c.image_dim, Km = c.mention_objects, Ke = c.entity_objects;
+  const size_t x3 = split_bf16(c.precision), tok = c.entity_tokens > 0;
+  InputGradScratch S;
+  S.build(c);
+  const Region sc[] = {
+      {"g_span", S.g_span, B * D}, {"g_raw", S.g_raw, M * D}, {"cls_stage", S.cls_stage, tok * M * D}, {"g_pool", S.g_pool, tok * M * D},
+      {"cos3", S.cos3, 3 * M}, {"g_mimg", S.g_mimg, B * R}, {"g_eimg", S.g_eimg, c.entity_image_inner > 1 ? M * R : 0},
+      {"g_mobj", S.g_mobj, B * Km * R}, {"g_eobj", S.g_eobj, M * Ke * R}, {"g_ms", S.g_ms, B * Km}, {"g_es", S.g_es, M * Ke},
+      {"g_edge", S.g_edge, 4 * M}, {"planes_ei", S.planes_ei, x3 * D * R}, {"planes_et", S.planes_et, x3 * D * D},
+      {"miei", S.miei, miei_bwd_scratch_floats((int64_t)M, (int)B, (int)Km, (int)Ke)}};
+  return regions_hold("InputGradScratch", sc, (int)(sizeof(sc) / sizeof(sc[0])), S.total_floats);
+}
 
 static int validate_input_grads(const drin_config* c, const drin_batch* b, const drin_input_grads* g) {
   if (b->entity_index) {
@@ -761,8 +771,8 @@ int drin_linear_bwd(const float* x, const float* w, const float* dy, float* dx, 
   if (dx) {
     // the scratch holds W^T [k][n_out] for the split-bf16 form; what that leaves of it lets a partly filled last round of
     // tiles split along K
-    const size_t used = ((size_t)n_out * k + 63) & ~(size_t)63;
-    float* tail = scratch && scratch_floats > used ? scratch + used : nullptr;
+    const size_t used = Arena::rounded((size_t)n_out * k);
+    float* tail = scratch && scratch_floats > used ? Arena::at(scratch, used) : nullptr;
     DRIN_TRY(launch_gemm_nn(dy, n_out, w, k, dx, k, rows, k, n_out, false, precision, st, nullptr, 0,
                             {nullptr, scratch, scratch_floats, tail, tail ? scratch_floats - used : 0}));
   }
@@ -1172,35 +1182,18 @@ int drin_backward_ex(const drin_config* cfg, const drin_batch* batch, const drin
   Pooled P;
   resolve_pooled(cfg, batch, L, ws, &P);
 
-  // carve the backward scratch (Layout::bwd_scratch): two generations of vertex / edge gradients,
-  // W_h-input gradients, edge-update gradients
-  float* sp = ws + L.bwd_scratch;
-  auto carve = [&sp](size_t n) {
-    float* p = sp;
-    sp += (n + 63) & ~(size_t)63;
-    return p;
-  };
-  // vertex gradients: one generation per level (g_v?[l + 1] = dL/dH of layer l, g_v?[0] = the vertex encoders' output
-  // gradient) - they are operands of the weight-gradient products, which run as grouped launches at the end of the pass
-  float* g_vm[DRIN_MAX_LAYERS + 1];
-  for (int l = 0; l <= nl; ++l) g_vm[l] = carve(2 * BD);
-  float* g_ve[DRIN_MAX_LAYERS + 1];
-  for (int l = 0; l <= nl; ++l) g_ve[l] = carve(2 * MD);
+  // the pass's temporaries (layout.h: BackwardScratch), in Layout::bwd_scratch
+  BackwardScratch S;
+  S.build(*cfg);
+  float* const sc = Arena::at(ws, L.bwd_scratch);
+  auto g_vm = [&](int l) { return sc + S.g_vm[l]; };
+  auto g_ve = [&](int l) { return sc + S.g_ve[l]; };
+  float* const g_e[2] = {sc + S.g_e[0], sc + S.g_e[1]};
+  float* const dA_m = sc + S.dA_m;
+  float* const dA_e = sc + S.dA_e;
+  float* const dpre = sc + S.dpre;
   const bool vec = cfg->vector_edges != 0;
   const size_t EW = vec ? (size_t)D : 1, ES = M * EW;  // floats per edge per pair, stride between edge types
-  float* g_e[2] = {carve(4 * ES), carve(4 * ES)};
-  float* dA_m = carve(2 * BD);
-  float* dA_e = carve(2 * MD);
-  float* dfu_of[DRIN_MAX_LAYERS];
-  for (int l = 0; l < (nl > 1 ? nl - 1 : 1); ++l) dfu_of[l] = carve(2 * BD);
-  float* dfv_of[DRIN_MAX_LAYERS];   // per layer, for the same reason (the last layer has no live edge update)
-  for (int l = 0; l < (nl > 1 ? nl - 1 : 1); ++l) dfv_of[l] = carve(2 * MD);
-  float* dpre = carve(4 * ES);
-  float* cos_scratch = carve(3 * M);
-  if ((size_t)(sp - (ws + L.bwd_scratch)) > L.bwd_scratch_floats) {
-    set_error("internal: backward scratch overflow");
-    return DRIN_E_WORKSPACE;
-  }
 
   bool all_enabled = true;
   for (int k = 0; k < 4; ++k) all_enabled = all_enabled && cfg->edge_enabled[k] == 1.0f;
@@ -1235,7 +1228,7 @@ int drin_backward_ex(const drin_config* cfg, const drin_batch* batch, const drin
   WeightGradPass dw{prec, vec, st, {tnp, tnf}, {ws + L.small_part, L.small_part_floats}, {csp, L.colsum_part_floats}};
 
   // score = cos(mt_L, et_L) (model.py:207-209)
-  DRIN_TRY(launch_cosine_bwd(ws + L.vm[nl], ws + L.ve[nl], grad_scores, g_vm[nl], g_ve[nl], cos_scratch, B, N, D,
+  DRIN_TRY(launch_cosine_bwd(ws + L.vm[nl], ws + L.ve[nl], grad_scores, g_vm(nl), g_ve(nl), sc + S.cos_scratch, B, N, D,
                              cfg->cosine_eps, st));
   bool have_image = false;  // gradients w.r.t. the image vertices of the current level exist
   bool have_edge = false;   // gradients w.r.t. the current level's edges exist
@@ -1244,12 +1237,12 @@ int drin_backward_ex(const drin_config* cfg, const drin_batch* batch, const drin
     const drin_layer_params& W = params->layer[l];
     const auto& G = grads->layer[l];
     const int types = have_image ? 2 : 1;
-    float* gm = g_vm[l + 1];  // dL/d(new mention vertices) -> dL/dH in place
-    float* ge = g_ve[l + 1];
-    float* gm_next = g_vm[l];
-    float* ge_next = g_ve[l];
-    float* dfv = dfv_of[l < nl - 1 ? l : 0];
-    float* dfu = dfu_of[l < nl - 1 ? l : 0];
+    float* gm = g_vm(l + 1);  // dL/d(new mention vertices) -> dL/dH in place
+    float* ge = g_ve(l + 1);
+    float* gm_next = g_vm(l);
+    float* ge_next = g_ve(l);
+    float* dfv = sc + S.dfv_of[l];
+    float* dfu = sc + S.dfu_of[l];
     const int cur = (nl - 1 - l) & 1, nxt = cur ^ 1;  // the edge gradients keep two generations
     const float* st_m = ws + L.ln_stat_m[l];
     const float* st_e = ws + L.ln_stat_e[l];
@@ -1259,7 +1252,7 @@ int drin_backward_ex(const drin_config* cfg, const drin_batch* batch, const drin
     DRIN_TRY(launch_layernorm_gelu_bwd2(ws + L.h_m[l], st_m, st_m + 2 * (size_t)B, gm, (int64_t)types * B, ws + L.h_e[l], st_e,
                                         st_e + 2 * M, ge, (int64_t)types * M, W.ln_weight, W.ln_bias, G.ln_weight, G.ln_bias,
                                         G.b_h, ws + L.ln_part, D, st, act_v, nl <= 2 ? &dw.ln_sums : nullptr,
-                                        ws + L.ln_part + ((size_t)(1024 + 16) + (size_t)16 * l) * 3 * D));
+                                        ws + L.ln_part + ln_bwd_level1((size_t)D, l)));
     // (b) dW_h += dH^T A
     if (G.w_h) {
       DRIN_TRY(dw.add(gm, D, ws + L.agg_m[l], D, G.w_h, D, (int64_t)types * B, D, D));
@@ -1352,10 +1345,10 @@ int drin_backward_ex(const drin_config* cfg, const drin_batch* batch, const drin
 
   dw.layers_done();   // (drin_backward_staged: what follows belongs to the vertex encoders)
   // VertexEncoder (model.py:26-46): four Linears over the pooled inputs
-  const float* g_mt = g_vm[0];
-  const float* g_mi = g_vm[0] + BD;
-  const float* g_et = g_ve[0];
-  const float* g_ei = g_ve[0] + MD;
+  const float* g_mt = g_vm(0);
+  const float* g_mi = g_vm(0) + BD;
+  const float* g_et = g_ve(0);
+  const float* g_ei = g_ve(0) + MD;
   DRIN_TRY(dw.add(g_mt, D, P.span_mean, D, grads->w_mention_text, D, B, D, D, nullptr, grads->b_mention_text));
   DRIN_TRY(dw.add(g_et, D, P.entity_text, D, grads->w_entity_text, D, (int64_t)M, D, D, eidx, grads->b_entity_text));
   if (have_image) {
@@ -1365,8 +1358,8 @@ int drin_backward_ex(const drin_config* cfg, const drin_batch* batch, const drin
   DRIN_TRY(dw.finish(layers_ready_event));   // everything collected lands; staged: the layers' part, the event, the encoders' part
   if (input_grads == nullptr) return DRIN_OK;
   // the batch tensors' gradients (drin_backward_ex): from the vertex encoders' output gradients and the layer-0 edge
-  // gradients, which the layer loop left in g_vm[0] / g_ve[0] / g_e[nl & 1] (nothing above writes them after the loop)
-  return run_input_grads(cfg, batch, params, P, nl > 0 ? g_e[nl & 1] : nullptr, g_vm[0], g_ve[0], input_grads, st);
+  // gradients, which the layer loop left in g_vm(0) / g_ve(0) / g_e[nl & 1] (nothing above writes them after the loop)
+  return run_input_grads(cfg, batch, params, P, nl > 0 ? g_e[nl & 1] : nullptr, g_vm(0), g_ve(0), input_grads, st);
 }
 
 // ---- host-side self-checks (sanitizer build / CI; no launch is made, no GPU needed) -----------------------------------
@@ -1422,6 +1415,28 @@ int drin_host_selftest(void) {
       return DRIN_E_SHAPE;
     }
   }
+  // (4) the workspaces declared beside their kernels (the layer-by-layer one: tests/host/workspace_main.cpp): every region on a
+  //     256-byte boundary, disjoint, inside the total
+  for (int precision : {(int)DRIN_PREC_F32, (int)DRIN_PREC_BF16X3, (int)DRIN_PREC_BF16X3_IF16})
+    for (int b : {1, 2, 255, 256, 257, 300, 1024, 2049, 4096})
+      for (int n : {1, 11, 101})
+        for (int dims = 0; dims < 2; ++dims)
+          for (int form = 0; form < 2; ++form) {   // gathered rows | tables with token blocks
+            drin_config c;
+            drin_default_config(&c);
+            c.batch = b, c.num_candidates = n, c.precision = precision;
+            if (dims) c.embed_dim = 64, c.image_dim = 128;
+            if (form) c.num_entities = 500, c.entity_tokens = 8, c.entity_image_inner = 2;
+            DRIN_TRY(fused_layout_selfcheck(c));
+            if (precision != DRIN_PREC_BF16X3_IF16) {
+              DRIN_TRY(cached_layout_selfcheck(c));
+              DRIN_TRY(input_grad_scratch_selfcheck(c));
+            }
+            if (precision == DRIN_PREC_F32) {
+              DRIN_TRY(melhi_layout_selfcheck(b, n, c.embed_dim, c.image_dim, form ? 128 : 7));
+              DRIN_TRY(ghmfc_layout_selfcheck(b, n, c.embed_dim, c.image_dim, form ? 128 : 7, form ? 49 : 4, form ? 8 : 0));
+            }
+          }
   set_error("");
   return DRIN_OK;
 }

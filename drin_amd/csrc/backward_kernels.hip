@@ -9,7 +9,6 @@
 namespace drin {
 
 constexpr int MAXV = 4;  // float4 columns per lane: D <= 1024
-constexpr int kLnBwdMaxBlocks = 1024;
 
 // ------------------------------------------------------------------------------------------------
 // score = cos(x[b], y[p]) (model.py:207-209), torch>=2 form: xn = x / max(|x|, eps), yn likewise.
@@ -323,8 +322,8 @@ int launch_layernorm_gelu_bwd2(const float* h, const float* mean, const float* r
   const LnBwdSeg sb{h2, mean2, rstd2, g2, h2 != nullptr ? rows2 : 0};
   hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, st, sa, sb, gamma, beta, partial, D / 4, act);
   DRIN_CHECK_LAUNCH("k_layernorm_gelu_bwd");
-  // partial: [kLnBwdMaxBlocks][3][D] block rows, then [kLnBwdMaxBlocks / 64][3][D] for the first reduction level
-  const int z = (int)cdiv(blocks, 64);
+  // partial (ln_bwd_partial_floats): [kLnBwdMaxBlocks][3][D] block rows, then [kLnBwdLevel1Rows][3][D] for the first reduction level
+  const int z = (int)cdiv(blocks, kLnBwdGroup);
   // defer: the second level - up to 16 rows per quantity - is handed to the caller's ordered slice sum (one launch at the end
   // of the backward pass for every split reduction) instead of being a launch of its own; the level-1 rows then live in
   // `level1_own`, which nothing overwrites before that launch (one area per layer)
@@ -332,7 +331,7 @@ int launch_layernorm_gelu_bwd2(const float* h, const float* mean, const float* r
                         defer->n_seg + 3 <= SliceSum::MAX_SEG && (D % 4) == 0 && aligned16(level1_own) &&
                         (dgamma == nullptr || aligned16(dgamma)) && (dbeta == nullptr || aligned16(dbeta)) &&
                         (dbias == nullptr || aligned16(dbias));
-  float* level1 = deferred ? level1_own : partial + (int64_t)kLnBwdMaxBlocks * 3 * D;
+  float* level1 = deferred ? level1_own : partial + ln_bwd_block_floats((size_t)D);
   hipLaunchKernelGGL(k_sum_partials, dim3((unsigned)cdiv(D, 64), 3, (unsigned)z), dim3(256), 0, st, partial, (int)blocks, D,
                      level1, (float*)nullptr, (float*)nullptr, (float*)nullptr, deferred ? 1 : 0);
   DRIN_CHECK_LAUNCH("k_sum_partials");
@@ -393,12 +392,12 @@ __global__ void __launch_bounds__(256) k_colsum(const float* __restrict__ x, flo
   colsum_block(x, out, partial, rows, C4, (int)gridDim.y, comb);
 }
 
-// up to 8 column sums in one launch (blockIdx.z = which): the bias gradients of one backward pass
+// up to kColsumBatchMax column sums in one launch (blockIdx.z = which): the bias gradients of one backward pass
 struct ColsumArgs {
-  const float* x[8];
-  float* partial[8];
-  int64_t rows[8];
-  int c4[8], by[8];
+  const float* x[kColsumBatchMax];
+  float* partial[kColsumBatchMax];
+  int64_t rows[kColsumBatchMax];
+  int c4[kColsumBatchMax], by[kColsumBatchMax];
 };
 __global__ void __launch_bounds__(256) k_colsum_batch(const ColsumArgs b) {
   __shared__ float4 comb[4][64];
@@ -414,7 +413,7 @@ static int colsum_slices(int64_t nrows) {
 
 int ColsumBatch::add(const float* src, float* dst, int64_t nrows, int C) {
   if (nrows <= 0 || !dst) return DRIN_OK;
-  if (C % 4 || n >= 8) {
+  if (C % 4 || n >= kColsumBatchMax) {
     set_error("colsum: C=%d must be a multiple of 4 (and at most 8 sums per batch)", C);
     return DRIN_E_SHAPE;
   }

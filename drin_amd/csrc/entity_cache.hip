@@ -575,32 +575,41 @@ struct CachedLayout {  // workspace of drin_forward_cached, offsets in floats
     // R = 2048, default activation) has the registers to look ahead across groups, every other one gets ONE group per
     // workgroup.  cached_chunk_candidates() is the one place that knows.
     chunks = (int)((N + cached_chunk_candidates(c) - 1) / cached_chunk_candidates(c));
-    size_t off = 0;
-    auto take = [&off](size_t n) {
-      const size_t o = off;
-      off += (n + 63) & ~(size_t)63;
-      return o;
-    };
+    Arena A;
     const bool planes = c.precision == DRIN_PREC_BF16X3 || c.precision == DRIN_PREC_BF16X3_ALL;
-    span_mean = take(B * D);
-    mimg = take(B * R);
-    vm0 = take(2 * B * D);
-    hmfu = take(2 * B * 2 * D);
-    e1m = take(4 * M);
-    c_part = take(B * chunks * (2 * D + 4));
-    s2_part = take(B * chunks * 2 * D);
-    vm1 = take(2 * B * D);
-    hm2 = take(2 * B * D);
-    agg2 = take(B * D);
-    mt2 = take(B * D);
-    et1 = take(planes ? 0 : M * D);
-    p_et1 = take(planes ? M * D : 0);  // hi plane (M*D bf16) then lo plane
-    h2 = take(M * D);
-    splitk_floats = 2 * B <= 512 ? 8 * 2 * B * 2 * D : 0;  // split-K partials of the mention-sized fp32 products
-    splitk = take(splitk_floats);
-    total = off;
+    span_mean = A.take(B * D);
+    mimg = A.take(B * R);
+    vm0 = A.take(2 * B * D);
+    hmfu = A.take(2 * B * 2 * D);
+    e1m = A.take(4 * M);
+    c_part = A.take(B * chunks * (2 * D + 4));
+    s2_part = A.take(B * chunks * 2 * D);
+    vm1 = A.take(2 * B * D);
+    hm2 = A.take(2 * B * D);
+    agg2 = A.take(B * D);
+    mt2 = A.take(B * D);
+    et1 = A.take(planes ? 0 : M * D);
+    p_et1 = A.take(planes ? M * D : 0);  // hi plane (M*D bf16) then lo plane
+    h2 = A.take(M * D);
+    // split-K partials of the mention-sized fp32 products; the widest: hmfu [2 B][2 D]
+    splitk_floats = 2 * B <= (size_t)kSmallSplitkMaxRows ? small_splitk_floats(2 * B, 2 * D) : 0;
+    splitk = A.take(splitk_floats);
+    total = A.total;
   }
 };
+
+int cached_layout_selfcheck(const drin_config& c) {
+  const size_t B = c.batch, M = B * c.num_candidates, D = c.embed_dim, R = c.image_dim;
+  CachedLayout L;
+  L.build(c);
+  const size_t ch = (size_t)L.chunks, planes = c.precision != DRIN_PREC_F32;
+  const Region ws[] = {
+      {"span_mean", L.span_mean, B * D}, {"mimg", L.mimg, B * R}, {"vm0", L.vm0, 2 * B * D}, {"hmfu", L.hmfu, 4 * B * D},
+      {"e1m", L.e1m, 4 * M}, {"c_part", L.c_part, B * ch * (2 * D + 4)}, {"s2_part", L.s2_part, B * ch * 2 * D},
+      {"vm1", L.vm1, 2 * B * D}, {"hm2", L.hm2, 2 * B * D}, {"agg2", L.agg2, B * D}, {"mt2", L.mt2, B * D},
+      {"et1", L.et1, (1 - planes) * M * D}, {"p_et1", L.p_et1, planes * M * D}, {"h2", L.h2, M * D}, {"splitk", L.splitk, L.splitk_floats}};
+  return regions_hold("CachedLayout", ws, (int)(sizeof(ws) / sizeof(ws[0])), L.total);
+}
 
 int cached_chunks_per_mention(const drin_config& c) {
   CachedLayout L;

@@ -19,35 +19,30 @@ struct Prepared {  // offsets in floats
   size_t cimg_f16_scale;         // [2]: that scale, and the scratch word of its reduction
   void build(const drin_config& c) {
     const size_t D = c.embed_dim, R = c.image_dim;
-    size_t off = 0;
-    auto take = [&off](size_t n) {
-      const size_t o = off;
-      off += (n + 63) & ~(size_t)63;
-      return o;
-    };
-    wcat1 = take(2 * D * D);      // [W_h1; W_u1]           [2D, D]
-    bcat1 = take(2 * D);          // [0; b_u1]
-    ecat = take(D * (D + R));     // ([W_v1 W_et | W_v1 W_ei])^T  [D + R, D]  (nn.Linear layout: q = fu ecat^T)
-    etmp = take(D * (D + R));     // scratch of drin_prepare: the un-transposed product
-    k_t = take(D);                // W_v1 b_et + b_v1
-    k_i = take(D);                // W_v1 b_ei + b_v1
-    c_txt = take(D * D);          // W_h1 W_et              [D, D]
-    c_img = take(D * R);          // W_h1 W_ei              [D, R]
-    cb_t = take(D);               // W_h1 b_et + b_h1
-    cb_i = take(D);               // W_h1 b_ei + b_h1
-    p_ctxt = take(D * D);         // hi plane D*D bf16 (= D*D/2 floats) then lo plane
-    p_cimg = take(D * R);
-    p_wh2 = take(D * D);
-    p_wmt = take(D * D);          // W_mt
-    p_wmi = take(D * R);          // W_mi
-    p_wcat1 = take(2 * D * D);    // [W_h1; W_u1]
-    p_ecat = take(D * (D + R));   // ([W_v1 W_et | W_v1 W_ei])^T
-    p_wet = take(D * D);          // W_et
-    p_wei = take(D * R);          // W_ei
-    p_wh1 = take(D * D);          // W_h1
-    p_cimg_f16 = take(D * R / 2 + 2);   // D R halves
-    cimg_f16_scale = take(2);
-    total = off;
+    Arena A;
+    wcat1 = A.take(2 * D * D);      // [W_h1; W_u1]           [2D, D]
+    bcat1 = A.take(2 * D);          // [0; b_u1]
+    ecat = A.take(D * (D + R));     // ([W_v1 W_et | W_v1 W_ei])^T  [D + R, D]  (nn.Linear layout: q = fu ecat^T)
+    etmp = A.take(D * (D + R));     // scratch of drin_prepare: the un-transposed product
+    k_t = A.take(D);                // W_v1 b_et + b_v1
+    k_i = A.take(D);                // W_v1 b_ei + b_v1
+    c_txt = A.take(D * D);          // W_h1 W_et              [D, D]
+    c_img = A.take(D * R);          // W_h1 W_ei              [D, R]
+    cb_t = A.take(D);               // W_h1 b_et + b_h1
+    cb_i = A.take(D);               // W_h1 b_ei + b_h1
+    p_ctxt = A.take(D * D);         // hi plane D*D bf16 (= D*D/2 floats) then lo plane
+    p_cimg = A.take(D * R);
+    p_wh2 = A.take(D * D);
+    p_wmt = A.take(D * D);          // W_mt
+    p_wmi = A.take(D * R);          // W_mi
+    p_wcat1 = A.take(2 * D * D);    // [W_h1; W_u1]
+    p_ecat = A.take(D * (D + R));   // ([W_v1 W_et | W_v1 W_ei])^T
+    p_wet = A.take(D * D);          // W_et
+    p_wei = A.take(D * R);          // W_ei
+    p_wh1 = A.take(D * D);          // W_h1
+    p_cimg_f16 = A.take(D * R / 2 + 2);   // D R halves
+    cimg_f16_scale = A.take(2);
+    total = A.total;
   }
 };
 

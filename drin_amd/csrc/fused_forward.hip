@@ -42,64 +42,78 @@ struct FusedLayout {  // workspace offsets in floats
     // mention's scores in a small and in a large call differ by fp32 re-association (as through the tile choices of the
     // mention-sized products), within one call size they are the same bits every run.
     chunks = (int)(B >= 2048 ? (N + 127) / 128 : B >= 1024 ? (N + 47) / 48 : (N + 15) / 16);   // (1 024 mentions: 48 candidates, 4.56 -> 4.49 ms)
-    size_t off = 0;
-    auto take = [&off](size_t n) {
-      const size_t o = off;
-      off += (n + 63) & ~(size_t)63;
-      return o;
-    };
-    span_mean = take(B * D);
-    mimg = take(B * R);
-    vm0 = take(2 * B * D);
-    hmfu = take(2 * B * 2 * D);
-    q = take(2 * B * (D + R));
-    e0m = take(4 * M);
-    e1m = take(4 * M);
-    xt = take(c.entity_tokens > 0 ? M * D : 0);
-    s_part = take(B * chunks * (2 * D + 2 * R + 4));
-    s_text = take(2 * B * D);
-    s_img = take(2 * B * R);
-    sig = take(4 * B);
-    tm = take(2 * B * D);
-    tm2 = take(2 * B * D);
-    agg1 = take(2 * B * D);
-    vm1 = take(2 * B * D);
-    hm2 = take(2 * B * D);
-    h_text = take(M * D);   // re-used for et1 W_h2^T once layer 1 is done
-    h_image = take(M * D);
-    et1 = take(M * D);
-    s2_part = take(B * chunks * 2 * D);
-    agg2 = take(B * D);
-    mt2 = take(B * D);
+    Arena A;
+    span_mean = A.take(B * D);
+    mimg = A.take(B * R);
+    vm0 = A.take(2 * B * D);
+    hmfu = A.take(2 * B * 2 * D);
+    q = A.take(2 * B * (D + R));
+    e0m = A.take(4 * M);
+    e1m = A.take(4 * M);
+    xt = A.take(c.entity_tokens > 0 ? M * D : 0);
+    s_part = A.take(B * chunks * (2 * D + 2 * R + 4));
+    s_text = A.take(2 * B * D);
+    s_img = A.take(2 * B * R);
+    sig = A.take(4 * B);
+    tm = A.take(2 * B * D);
+    tm2 = A.take(2 * B * D);
+    agg1 = A.take(2 * B * D);
+    vm1 = A.take(2 * B * D);
+    hm2 = A.take(2 * B * D);
+    h_text = A.take(M * D);   // re-used for et1 W_h2^T once layer 1 is done
+    h_image = A.take(M * D);
+    et1 = A.take(M * D);
+    s2_part = A.take(B * chunks * 2 * D);
+    agg2 = A.take(B * D);
+    mt2 = A.take(B * D);
     const bool planes = c.precision == DRIN_PREC_BF16X3 || c.precision == DRIN_PREC_BF16X3_ALL || c.precision == DRIN_PREC_BF16X3_IF16;
-    p_xt = take(planes ? M * D : 0);   // hi plane (M*D bf16) then lo plane
+    p_xt = A.take(planes ? M * D : 0);   // hi plane (M*D bf16) then lo plane
     // image planes, sized by use: the table form (cfg.num_entities > 0: entity_index gathers rows, so the stream kernel
     // writes them as (hi, lo) bf16 planes) M R floats; DRIN_PREC_BF16X3_IF16 the one fp16 plane, M R / 2; gathered split-bf16
     // batches read the image rows in place: nothing (3.4 GB less workspace at the headline batch)
-    p_xi = take(!planes ? 0 : c.num_entities > 0 ? M * R : c.precision == DRIN_PREC_BF16X3_IF16 ? M * R / 2 : 0);
-    p_et1 = take(planes ? M * D : 0);
-    xi_scale = take(c.precision == DRIN_PREC_BF16X3_IF16 ? M : 0);   // per-pair power-of-two scale of the image row
+    p_xi = A.take(!planes ? 0 : c.num_entities > 0 ? M * R : c.precision == DRIN_PREC_BF16X3_IF16 ? M * R / 2 : 0);
+    p_et1 = A.take(planes ? M * D : 0);
+    xi_scale = A.take(c.precision == DRIN_PREC_BF16X3_IF16 ? M : 0);   // per-pair power-of-two scale of the image row
     // split-K partials of the mention-sized exact-fp32 products (small batches: the call is a chain of ~25 launches)
-    // (in split-bf16 precision at least 192 partial 256 x 256 tiles, so that a partly filled last round of tiles of the
+    // (in split-bf16 precision at least tail_split_floor_floats(), so that a partly filled last round of tiles of the
     //  larger products can split K over the idle CUs - gemm_bf16x3.hip)
-    splitk_floats = 2 * B <= 512 ? 8 * 2 * B * (D + R) : 0;
-    if (planes && splitk_floats < (size_t)192 * 65536) splitk_floats = (size_t)192 * 65536;   // 64 tail tiles x 3 partials
-    splitk = take(splitk_floats);
+    // (the widest: q [2 B][D + R])
+    splitk_floats = 2 * B <= (size_t)kSmallSplitkMaxRows ? small_splitk_floats(2 * B, D + R) : 0;
+    if (planes && splitk_floats < tail_split_floor_floats()) splitk_floats = tail_split_floor_floats();
+    splitk = A.take(splitk_floats);
     // ... and of the pair-sized split-bf16 products when the whole batch is less than half a round of 256 x 256 tiles
-    pair_splitk_floats = 0;
-    {
-      const size_t tiles = ((M + 255) / 256) * ((D + 255) / 256);
-      if (planes && tiles <= 128)
-        for (size_t s : {16, 8, 6, 4, 3, 2})
-          if (tiles * s <= 256) {
-            pair_splitk_floats = s * ((M + 255) / 256 * 256) * D;
-            break;
-          }
-    }
-    pair_splitk = take(pair_splitk_floats);
-    total = off;
+    pair_splitk_floats = planes ? drin::pair_splitk_floats(M, D) : 0;
+    pair_splitk = A.take(pair_splitk_floats);
+    total = A.total;
   }
 };
+
+int fused_layout_selfcheck(const drin_config& c) {
+  const size_t B = c.batch, M = B * c.num_candidates, D = c.embed_dim, R = c.image_dim;
+  FusedLayout L;
+  L.build(c);
+  const size_t ch = (size_t)L.chunks, planes = c.precision != DRIN_PREC_F32;
+  const Region ws[] = {
+      {"span_mean", L.span_mean, B * D}, {"mimg", L.mimg, B * R}, {"vm0", L.vm0, 2 * B * D}, {"hmfu", L.hmfu, 4 * B * D},
+      {"q", L.q, 2 * B * (D + R)}, {"e0m", L.e0m, 4 * M}, {"e1m", L.e1m, 4 * M}, {"xt", L.xt, c.entity_tokens > 0 ? M * D : 0},
+      {"s_part", L.s_part, B * ch * (2 * D + 2 * R + 4)}, {"s_text", L.s_text, 2 * B * D}, {"s_img", L.s_img, 2 * B * R},
+      {"sig", L.sig, 4 * B}, {"tm", L.tm, 2 * B * D}, {"tm2", L.tm2, 2 * B * D}, {"agg1", L.agg1, 2 * B * D}, {"vm1", L.vm1, 2 * B * D},
+      {"hm2", L.hm2, 2 * B * D}, {"h_text", L.h_text, M * D}, {"h_image", L.h_image, M * D}, {"et1", L.et1, M * D},
+      {"s2_part", L.s2_part, B * ch * 2 * D}, {"agg2", L.agg2, B * D}, {"mt2", L.mt2, B * D}, {"p_xt", L.p_xt, planes * M * D},
+      {"p_xi", L.p_xi, !planes ? 0 : c.num_entities > 0 ? M * R : c.precision == DRIN_PREC_BF16X3_IF16 ? M * R / 2 : 0},
+      {"p_et1", L.p_et1, planes * M * D}, {"xi_scale", L.xi_scale, c.precision == DRIN_PREC_BF16X3_IF16 ? M : 0},
+      {"splitk", L.splitk, L.splitk_floats}, {"pair_splitk", L.pair_splitk, L.pair_splitk_floats}};
+  DRIN_TRY(regions_hold("FusedLayout", ws, (int)(sizeof(ws) / sizeof(ws[0])), L.total));
+  Prepared P;
+  P.build(c);
+  const Region pr[] = {
+      {"wcat1", P.wcat1, 2 * D * D}, {"bcat1", P.bcat1, 2 * D}, {"ecat", P.ecat, D * (D + R)}, {"etmp", P.etmp, D * (D + R)},
+      {"k_t", P.k_t, D}, {"k_i", P.k_i, D}, {"c_txt", P.c_txt, D * D}, {"c_img", P.c_img, D * R}, {"cb_t", P.cb_t, D}, {"cb_i", P.cb_i, D},
+      {"p_ctxt", P.p_ctxt, D * D}, {"p_cimg", P.p_cimg, D * R}, {"p_wh2", P.p_wh2, D * D}, {"p_wmt", P.p_wmt, D * D},
+      {"p_wmi", P.p_wmi, D * R}, {"p_wcat1", P.p_wcat1, 2 * D * D}, {"p_ecat", P.p_ecat, D * (D + R)}, {"p_wet", P.p_wet, D * D},
+      {"p_wei", P.p_wei, D * R}, {"p_wh1", P.p_wh1, D * D}, {"p_cimg_f16", P.p_cimg_f16, D * R / 2}, {"cimg_f16_scale", P.cimg_f16_scale, 2}};
+  return regions_hold("Prepared", pr, (int)(sizeof(pr) / sizeof(pr[0])), P.total);
+}
 
 // The configuration part of the DRIN_PREC_BF16X3_IF16 gate (what is left - 16-byte alignment of workspace slots - holds by the
 // workspace contract): split-bf16 widths, per-pair fp32-stored rows, a list long enough to average the pass's rounding, the exact

@@ -384,8 +384,7 @@ template <bool B_KMAJOR>
 static int launch_small_splitk(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* bias, float* y,
                                int64_t ldy, int64_t M, int N, int K, bool accumulate, float* scratch, size_t scratch_floats,
                                hipStream_t st, const char* what) {
-  int splits = K / 128;  // >= 4 stages of 32 per slice
-  if (splits > 8) splits = 8;
+  int splits = small_splitk_slices(K);
   while (splits > 1 && (size_t)splits * M * N > scratch_floats) --splits;
   const int64_t part_stride = M * (int64_t)N;
   int used = 1;
@@ -450,7 +449,7 @@ static int launch_gemv(const float* x, int64_t ldx, const float* w, int64_t ldw,
 }
 
 static bool small_splitk_fits(int64_t M, int N, int K, int64_t ldy, const float* y, float* scratch, size_t scratch_floats) {
-  return scratch != nullptr && M <= 512 && K >= 512 && (N % 4) == 0 && (ldy % 4) == 0 && aligned16(y) && aligned16(scratch) &&
+  return scratch != nullptr && small_splitk_shape(M, K) && (N % 4) == 0 && (ldy % 4) == 0 && aligned16(y) && aligned16(scratch) &&
          scratch_floats >= (size_t)2 * M * N;
 }
 
@@ -481,10 +480,10 @@ __global__ void __launch_bounds__(256) k_splitk_reduce_group(const ReduceGroupAr
 bool gemm_nt_f32_group_fits(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* y, int64_t ldy, int64_t M, int N,
                             int K, int precision) {
   // exactly the products launch_gemm_nt sends to the exact-fp32 split-K pair (kernel + slice reduction)
-  if (precision == DRIN_PREC_BF16X3_ALL || (precision == DRIN_PREC_BF16X3 && M >= 256)) return false;
+  if (nt_takes_bf16x3(precision, M)) return false;
   if (precision != DRIN_PREC_F32 && precision != DRIN_PREC_BF16X3) return false;
   if ((K % 4) || gemv_fits(x, ldx, w, ldw, M, K)) return false;
-  return M >= 1 && M <= 512 && K >= 512 && (N % 4) == 0 && (ldy % 4) == 0 && (ldx % 4) == 0 && (ldw % 4) == 0 && aligned16(y) &&
+  return M >= 1 && small_splitk_shape(M, K) && (N % 4) == 0 && (ldy % 4) == 0 && (ldx % 4) == 0 && (ldw % 4) == 0 && aligned16(y) &&
          aligned16(x) && aligned16(w);
 }
 
@@ -514,9 +513,7 @@ int launch_gemm_nt_f32_group(const F32GemmGroup& grp, hipStream_t st, float* scr
       set_error("gemm_nt group: item %d has M=%lld N=%d K=%d", i, (long long)it.M, it.N, it.K);
       return DRIN_E_SHAPE;
     }
-    int splits = it.K / 128;   // as launch_small_splitk
-    if (splits > 8) splits = 8;
-    if (splits < 1) splits = 1;
+    int splits = small_splitk_slices(it.K);   // as launch_small_splitk
     const int kps = (int)(cdiv(cdiv(it.K, splits), BK) * BK);
     splits = (int)cdiv(it.K, kps);
     const int64_t part_stride = it.M * (int64_t)it.N;
@@ -554,9 +551,9 @@ int launch_gemm_nt(const float* x, int64_t ldx, const float* w, int64_t ldw, con
   // the exact fp32 kernel: they are latency-bound, not rate-bound
   // (the 256-row threshold measured again in round 2, same box, 16 / 64 rows instead: a 64-mention scoring call 0.551 -> 0.576 ms,
   //  the B = 64 training step 1.406 -> 1.424 - below a tile row of the 256-wide kernel the exact one is as fast and exact)
-  if (!accumulate && ((precision == DRIN_PREC_BF16X3 && M >= 256) || precision == DRIN_PREC_BF16X3_ALL)) {
+  if (!accumulate && nt_takes_bf16x3(precision, M)) {
     // (pre-split weight planes: contiguous [N][K] weights only, K a multiple of 32 - what the LDS-DMA path reads)
-    const bool planes = w_planes != nullptr && ldw == K && (K % 32) == 0;
+    const bool planes = w_planes != nullptr && ldw == K && nt_planes_width(K);
     const __bf16* hi = reinterpret_cast<const __bf16*>(w_planes);
     return launch_gemm_nt_bf16x3(x, ldx, w, ldw, bias, y, ldy, M, N, K, st, planes ? (const void*)hi : nullptr,
                                  planes ? (const void*)(hi + (int64_t)N * K) : nullptr, false, splitk, splitk_floats);
@@ -572,7 +569,7 @@ int launch_gemm_nt(const float* x, int64_t ldx, const float* w, int64_t ldw, con
     return launch_small_splitk<false>(x, ldx, w, ldw, bias, y, ldy, M, N, K, accumulate, splitk, splitk_floats, st, "gemm_nt");
   // mention-sized problems (a few hundred rows): 64 x 64 tiles give 4x the workgroups of 128 x 128 and
   // keep more of the chip busy on what is a latency-bound launch
-  if (M <= 2048)
+  if (M <= kMentionSizedMaxRows)
     return launch<64, 64, false, false>(x, ldx, w, ldw, bias, y, ldy, M, N, K, 1, accumulate ? GEMM_ACCUMULATE : 0, st,
                                         "gemm_nt");
   return launch<128, 128, false, false>(x, ldx, w, ldw, bias, y, ldy, M, N, K, 1, accumulate ? GEMM_ACCUMULATE : 0, st,
@@ -582,12 +579,9 @@ int launch_gemm_nt(const float* x, int64_t ldx, const float* w, int64_t ldw, con
 int launch_gemm_nt_pair(const NtProduct& a, const NtProduct& b, int precision, hipStream_t st, float* splitk, size_t splitk_floats) {
   const NtProduct* two[2] = {&a, &b};
   bool grouped = splitk != nullptr;
-  size_t need = 8;
-  for (const NtProduct* q : two) {
+  for (const NtProduct* q : two)
     grouped = grouped && gemm_nt_f32_group_fits(q->x, q->ldx, q->w, q->ldw, q->y, q->ldy, q->rows, q->n_out, q->k_red, precision);
-    need += (size_t)8 * q->rows * q->n_out;
-  }
-  if (grouped && need <= splitk_floats) {
+  if (grouped && small_splitk_pair_floats((size_t)a.rows, (size_t)a.n_out, (size_t)b.rows, (size_t)b.n_out) <= splitk_floats) {
     F32GemmGroup g;
     for (const NtProduct* q : two) DRIN_TRY(g.add_nt(q->x, q->ldx, q->w, q->ldw, q->bias, q->y, q->ldy, q->rows, q->n_out, q->k_red));
     return launch_gemm_nt_f32_group(g, st, splitk, splitk_floats);
@@ -627,7 +621,7 @@ int launch_gemm_nn(const float* x, int64_t ldx, const float* w, int64_t ldw, flo
   }
   if (small_splitk_fits(M, N, K, ldy, y, splitk, splitk_floats))
     return launch_small_splitk<true>(x, ldx, w, ldw, nullptr, y, ldy, M, N, K, accumulate, splitk, splitk_floats, st, "gemm_nn");
-  if (M <= 2048)
+  if (M <= kMentionSizedMaxRows)
     return launch<64, 64, false, true>(x, ldx, w, ldw, nullptr, y, ldy, M, N, K, 1, accumulate ? GEMM_ACCUMULATE : 0, st,
                                        "gemm_nn");
   return launch<128, 128, false, true>(x, ldx, w, ldw, nullptr, y, ldy, M, N, K, 1, accumulate ? GEMM_ACCUMULATE : 0, st,
@@ -636,7 +630,7 @@ int launch_gemm_nn(const float* x, int64_t ldx, const float* w, int64_t ldw, flo
 
 int F32GemmGroup::add_tn(const float* a, int64_t lda, const float* b, int64_t ldb, float* y, int64_t ldy, int64_t M, int N, int K) {
   if (y == nullptr || M <= 0 || N <= 0 || K <= 0) return DRIN_OK;
-  if ((N % 4) || (K % 4) || M > 2048 || !aligned16(a) || !aligned16(b) || (lda % 4) || (ldb % 4)) {
+  if ((N % 4) || (K % 4) || M > kMentionSizedMaxRows || !aligned16(a) || !aligned16(b) || (lda % 4) || (ldb % 4)) {
     set_error("gemm_tn group: M=%lld N=%d K=%d outside the mention-sized kernel's contract", (long long)M, N, K);
     return DRIN_E_SHAPE;
   }
@@ -665,7 +659,7 @@ int launch_gemm_tn_f32_group(const F32GemmGroup& grp, hipStream_t st, float* scr
     // add_tn never stores an empty product; an item with a non-positive extent can only be a caller's slip (round 3's staged
     // backward once handed over value-initialised items past a group it had already flushed: M == 0 made kps 0 and the next
     // line's division raised SIGFPE on the host) - refused, never divided by
-    if (it.M <= 0 || it.N <= 0 || it.K <= 0 || it.M > 2048 || it.a == nullptr || it.b == nullptr || it.y == nullptr) {
+    if (it.M <= 0 || it.N <= 0 || it.K <= 0 || it.M > kMentionSizedMaxRows || it.a == nullptr || it.b == nullptr || it.y == nullptr) {
       set_error("gemm_tn group: item %d of %d has M=%lld N=%d K=%d (or a NULL operand) - outside [1, 2048] reduction rows", i,
                 grp.n, (long long)it.M, it.N, it.K);
       return DRIN_E_SHAPE;
@@ -712,7 +706,7 @@ TnKernel gemm_tn_kernel(int precision, const float* a, int64_t lda, const float*
   if ((precision == DRIN_PREC_BF16X3 || precision == DRIN_PREC_BF16X3_ALL) && gemm_tn_bf16x3_fits(lda, ldb, M, N, K, a, b) &&
       gemm_tn_bf16x3_scratch_ok(y, ldy, N, K, scratch, scratch_floats))
     return TN_BF16X3;
-  return M <= 2048 ? TN_F32_SMALL : TN_F32_LARGE;   // mention-sized reductions (a few hundred rows): 64 x 64 tiles, 4x the workgroups
+  return M <= kMentionSizedMaxRows ? TN_F32_SMALL : TN_F32_LARGE;   // mention-sized reductions (a few hundred rows): 64 x 64 tiles, 4x the workgroups
 }
 
 int launch_gemm_tn(const float* a, int64_t lda, const float* b, int64_t ldb, float* y, int64_t ldy, int64_t M, int N,

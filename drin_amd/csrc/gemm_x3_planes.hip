@@ -933,10 +933,11 @@ int launch_transpose_split_batch(const SplitBatch& b, int rows, int cols, hipStr
 static void tail_split_256(int64_t tiles, int nkb, const float* tail, size_t tail_floats, unsigned* full, int* ksplit) {
   *full = (unsigned)tiles;
   *ksplit = 1;
-  if (tail == nullptr || !aligned16(tail) || tiles > 16 * 256) return;
-  const unsigned frac = (unsigned)(tiles % 256);
-  for (int s = 4; s >= 2 && frac > 0; --s)
-    if ((unsigned)s * frac <= 256 && nkb % s == 0 && nkb / s >= 4 && (size_t)frac * (s - 1) * (x3p::BM * x3p::BN) <= tail_floats) {
+  static_assert((size_t)x3p::BM * x3p::BN == kTile256Floats, "scratch_sizes.h sizes the tail scratch in these tiles");
+  if (tail == nullptr || !aligned16(tail) || tiles > kTailSplitMaxRounds * kTileRound) return;
+  const unsigned frac = (unsigned)(tiles % kTileRound);
+  for (int s = kTailSplitMax; s >= 2 && frac > 0; --s)
+    if ((unsigned)s * frac <= (unsigned)kTileRound && nkb % s == 0 && nkb / s >= 4 && (size_t)frac * (s - 1) * kTile256Floats <= tail_floats) {
       *ksplit = s;
       *full = (unsigned)tiles - frac;
       return;
@@ -1045,9 +1046,9 @@ int launch_gemm_x3_planes(const void* a_hi, const void* a_lo, int64_t lda, const
   int splits = 1;
   const int nkb = K / x3p::BK;
   const int64_t tiles = mt * cdiv(N, x3p::BN);
-  if (splitk != nullptr && tiles <= 128 && (N % 4) == 0 && (ldy % 4) == 0 && aligned16(y) && aligned16(splitk)) {
-    for (int s : {16, 8, 6, 4, 3, 2})
-      if (tiles * s <= 256 && nkb % s == 0 && nkb / s >= 3 && (size_t)s * M * N <= splitk_floats) {
+  if (splitk != nullptr && tiles <= kPairSplitkMaxTiles && (N % 4) == 0 && (ldy % 4) == 0 && aligned16(y) && aligned16(splitk)) {
+    for (int s : kPairSplitkLadder)   // (scratch for it: pair_splitk_floats)
+      if (tiles * s <= kTileRound && nkb % s == 0 && nkb / s >= 3 && (size_t)s * M * N <= splitk_floats) {
         splits = s;
         break;
       }

@@ -574,19 +574,14 @@ struct GhmfcLayout {
   void build(const drin_ghmfc_config& c) {
     const size_t Bc = c.batch < kChunk ? c.batch : kChunk, N = c.num_candidates, D = c.embed_dim, R = c.image_dim;
     const size_t L = c.mention_tokens, P = c.image_regions;
-    size_t o = 0;
-    auto take = [&](size_t n) {
-      const size_t at = o;
-      o += (n + 63) & ~(size_t)63;   // 256-byte aligned pieces
-      return at;
-    };
+    Arena A;
     auto mx = [](size_t x, size_t y) { return x > y ? x : y; };
     const size_t rows = mx(L * D, P * R);
-    a = take(Bc * rows), b = take(Bc * rows);
-    kv = take(Bc * 2 * mx(mx(L, P) * D, mx(L, P) * R));
-    pool_t = take(Bc * D), pool_v = take(Bc * R), tl = take(Bc * D), vl = take(Bc * D), men = take(Bc * D);
-    epool = take(c.entity_tokens > 0 ? Bc * N * D : 0), ent = take(Bc * N * D);
-    total_floats = o;
+    a = A.take(Bc * rows), b = A.take(Bc * rows);
+    kv = A.take(Bc * 2 * mx(mx(L, P) * D, mx(L, P) * R));
+    pool_t = A.take(Bc * D), pool_v = A.take(Bc * R), tl = A.take(Bc * D), vl = A.take(Bc * D), men = A.take(Bc * D);
+    epool = A.take(c.entity_tokens > 0 ? Bc * N * D : 0), ent = A.take(Bc * N * D);
+    total_floats = A.total;
   }
 };
 
@@ -662,6 +657,22 @@ int cross_attention_max(const drin_ghmfc_cross_params& W, const float* sa, const
 }
 
 }  // namespace
+
+int ghmfc_layout_selfcheck(int batch, int n, int d, int r, int tokens, int regions, int entity_tokens) {
+  drin_ghmfc_config c = {};
+  c.batch = batch, c.num_candidates = n, c.embed_dim = d, c.image_dim = r, c.mention_tokens = tokens, c.image_regions = regions;
+  c.entity_tokens = entity_tokens;
+  const size_t Bc = batch < kChunk ? batch : kChunk, N = n, D = d, R = r, L = tokens, P = regions;
+  const size_t rows = L * D > P * R ? L * D : P * R, longest = L > P ? L : P, widest = D > R ? D : R;
+  GhmfcLayout W;
+  W.build(c);
+  const Region ws[] = {
+      {"a", W.a, Bc * rows}, {"b", W.b, Bc * rows}, {"kv", W.kv, Bc * 2 * longest * widest}, {"pool_t", W.pool_t, Bc * D},
+      {"pool_v", W.pool_v, Bc * R}, {"tl", W.tl, Bc * D}, {"vl", W.vl, Bc * D}, {"men", W.men, Bc * D},
+      {"epool", W.epool, entity_tokens > 0 ? Bc * N * D : 0}, {"ent", W.ent, Bc * N * D}};
+  return regions_hold("GhmfcLayout", ws, (int)(sizeof(ws) / sizeof(ws[0])), W.total_floats);
+}
+
 }  // namespace drin
 
 using namespace drin;

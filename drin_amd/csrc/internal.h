@@ -8,6 +8,7 @@
 #include <mutex>
 
 #include "../../include/drin_hip.h"
+#include "scratch_sizes.h"
 
 namespace drin {
 
@@ -102,6 +103,12 @@ inline dim3 pair_grid(int B, int N) {
   return (B > 1 && B <= 65535) ? dim3((unsigned)cdiv(N, 4), (unsigned)B) : dim3((unsigned)cdiv((int64_t)B * N, 4));
 }
 
+// ---- pooling and static edges of the layer-by-layer entry points (api.hip; Layout, Pooled: layout.h) -------------------
+struct Layout;
+struct Pooled;
+int run_pooling(const drin_config* c, const drin_batch* b, const Layout& L, float* ws, Pooled* out, hipStream_t st);
+int run_static_edges(const drin_config* c, const drin_batch* b, const Pooled& P, float* edges, hipStream_t st);
+
 // ---- streaming / pooling kernels (stream_kernels.hip) -------------------------------------------
 // out[g, c] = mean_s in[g, s, c]
 int launch_axis_mean(const float* in, float* out, int64_t groups, int inner, int cols, hipStream_t st);
@@ -176,8 +183,8 @@ inline void note_route(const RouteNote& n) {
 
 // ---- GEMM (gemm_f32.hip) ------------------------------------------------------------------------
 // y[m, n] (+)= sum_k x[m, k] * w[n, k] + bias[n];  x row stride ldx, w row stride ldw, y row stride ldy
-// (splitk: optional scratch; mention-sized exact-fp32 products with K >= 512 then split K over workgroups into it
-//  and reduce in order - deterministic - instead of walking K serially in 24 tiles)
+// (splitk: optional scratch; mention-sized exact-fp32 products with a long reduction (scratch_sizes.h: small_splitk_shape)
+//  then split K over workgroups into it and reduce in order - deterministic - instead of walking K serially in 24 tiles)
 // (w_planes: optional bf16 hi / lo planes of w - launch_split_planes_batch - taken when the product runs split-bf16)
 int launch_gemm_nt(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* bias, float* y, int64_t ldy,
                    int64_t M, int N, int K, bool accumulate, int precision, hipStream_t st, float* splitk = nullptr,
@@ -203,9 +210,10 @@ int launch_gemm_tn_bf16x3(const float* a, int64_t lda, const float* b, int64_t l
 // what launch_gemm_tn_bf16x3 / launch_gemm_tn_group need of y and the scratch besides gemm_tn_bf16x3_fits
 bool gemm_tn_bf16x3_scratch_ok(const float* y, int64_t ldy, int N, int K, const float* scratch, size_t scratch_floats);
 // (b_index: reduction row m of b is row b_index[m] of a table - the gathered form never materialised)
-// up to 8 such products in ONE launch (+ one for the slice reduction): the chip's workgroups are dealt over all of them
+// up to kTnGroupMax such products in ONE launch (+ one for the slice reduction): the chip's workgroups are dealt over all of
+// them (scratch for a whole pass: tn_group_floats)
 struct TnGroup {
-  static constexpr int MAX = 8;
+  static constexpr int MAX = kTnGroupMax;
   struct Item {
     const float* a;
     int64_t lda;
@@ -288,7 +296,7 @@ bool gemm_nn_takes_bf16x3(int precision, int64_t M, int N, int K);
 int launch_gemm_nn(const float* x, int64_t ldx, const float* w, int64_t ldw, float* y, int64_t ldy, int64_t M, int N,
                    int K, bool accumulate, int precision, hipStream_t st, float* splitk = nullptr, size_t splitk_floats = 0,
                    const WtForms& wt = WtForms());
-// up to 8 MENTION-sized (M <= 2048 reduction rows) exact-fp32 products y[n, k] += sum_m a[m, n] b[m, k] in one launch
+// up to 8 MENTION-sized (M <= kMentionSizedMaxRows reduction rows) exact-fp32 products y[n, k] += sum_m a[m, n] b[m, k] in one launch
 struct F32GemmGroup {
   static constexpr int MAX = 8;
   struct Item {
@@ -310,10 +318,6 @@ struct F32GemmGroup {
 // (a product alone on its destination with one slice adds to it in place; any other stores its slices to the scratch and
 //  goes through the slice sum - defer as for launch_gemm_tn_group; floats needed: small_tn_scratch_floats per item)
 int launch_gemm_tn_f32_group(const F32GemmGroup& g, hipStream_t st, float* scratch, size_t scratch_floats, SliceSum* defer = nullptr);
-inline int small_tn_slices(int64_t reduction_rows) {   // slices of a mention-sized (<= 2048 rows) weight-gradient product
-  const int64_t s = (reduction_rows + 127) / 128;
-  return (int)(s > 4 ? 4 : (s < 1 ? 1 : s));
-}
 bool gemm_nt_f32_group_fits(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* y, int64_t ldy, int64_t M, int N,
                             int K, int precision);
 int launch_gemm_nt_f32_group(const F32GemmGroup& g, hipStream_t st, float* scratch, size_t scratch_floats);
@@ -332,7 +336,7 @@ int launch_gemm_nt_pair(const NtProduct& a, const NtProduct& b, int precision, h
 int launch_gemm_tn(const float* a, int64_t lda, const float* b, int64_t ldb, float* y, int64_t ldy, int64_t M, int N,
                    int K, int precision, hipStream_t st, float* scratch = nullptr, size_t scratch_floats = 0);
 // the kernel such a product takes, decided here only: split-bf16 MFMA (gemm_tn_bf16x3_fits, gemm_tn_bf16x3_scratch_ok) |
-// exact fp32, mention-sized (M <= 2048): 64 x 64 tiles, small_tn_slices(M) slices | exact fp32, 128 x 128 tiles
+// exact fp32, mention-sized (M <= kMentionSizedMaxRows): 64 x 64 tiles, small_tn_slices(M) slices | exact fp32, 128 x 128 tiles
 enum TnKernel { TN_BF16X3, TN_F32_SMALL, TN_F32_LARGE };
 TnKernel gemm_tn_kernel(int precision, const float* a, int64_t lda, const float* b, int64_t ldb, const float* y, int64_t ldy,
                         int64_t M, int N, int K, const float* scratch, size_t scratch_floats);
@@ -365,7 +369,7 @@ int launch_edge_update4(const float* fu, const float* fv, const float* e, float*
 int launch_cosine_bwd(const float* x, const float* y, const float* g, float* dx, float* dy, float* scratch3, int B,
                       int N, int D, float eps, hipStream_t st);
 // in place: g (dL/dy) -> dL/dh for y = gelu(LN(h)); accumulates dgamma, dbeta and dbias (= column sum of dL/dh);
-// partial: (1024 + 16) * 3 * D floats of scratch for the per-block column sums
+// partial: ln_bwd_partial_floats(D) floats of scratch for the per-block column sums
 int launch_layernorm_gelu_bwd(const float* h, const float* mean, const float* rstd, const float* gamma,
                               const float* beta, float* g, float* dgamma, float* dbeta, float* dbias, float* partial,
                               int64_t rows, int D, hipStream_t st, int act = DRIN_ACT_GELU);
@@ -374,24 +378,23 @@ int launch_layernorm_gelu_bwd2(const float* h, const float* mean, const float* r
                                const float* mean2, const float* rstd2, float* g2, int64_t rows2, const float* gamma,
                                const float* beta, float* dgamma, float* dbeta, float* dbias, float* partial, int D,
                                hipStream_t st, int act = DRIN_ACT_GELU, SliceSum* defer = nullptr, float* level1_own = nullptr);
-// (defer + level1_own [3][16][D] floats: the second level of the column-sum reduction joins the caller's slice sum)
+// (defer + level1_own [3][kLnBwdLevel1Rows][D] floats, ln_bwd_level1(D, layer) into the partial buffer: the second level of the column-sum reduction joins the caller's slice sum)
 // out[c] += sum_rows x[row, c].  The rows are dealt over up to kColsumMaxSlices workgroups per 256 columns, whose sums go to
 // the scratch ([slices][C] floats) and from there to out in order (SliceSum); without scratch one workgroup per 256 columns
 // walks all rows and adds to out itself - slower, the same kind of result: no atomics either way.
-constexpr int kColsumMaxSlices = 64;
 int launch_colsum(const float* x, float* out, int64_t rows, int C, hipStream_t st, float* scratch = nullptr,
                   size_t scratch_floats = 0);
-// up to 8 such column sums in ONE launch
+// up to kColsumBatchMax such column sums in ONE launch
 struct ColsumBatch {
-  const float* x[8];
-  float* out[8];
-  int64_t rows[8];
-  int c4[8];
-  int by[8];
+  const float* x[kColsumBatchMax];
+  float* out[kColsumBatchMax];
+  int64_t rows[kColsumBatchMax];
+  int c4[kColsumBatchMax];
+  int by[kColsumBatchMax];
   int n = 0;
   int add(const float* src, float* dst, int64_t nrows, int C);   // no-op for dst == NULL or nrows <= 0
 };
-// (scratch: sum over the entries of by * C floats <= 8 * kColsumMaxSlices * C; defer as for launch_gemm_tn_group)
+// (scratch: sum over the entries of by * C floats <= colsum_batch_floats(C); defer as for launch_gemm_tn_group)
 int launch_colsum_batch(const ColsumBatch& b, hipStream_t st, float* scratch, size_t scratch_floats, SliceSum* defer = nullptr);
 // sigmoid backward of the scalar edge update + both entity-side gradients dfv_t, dfv_i in one pass (see the kernel)
 // (act | kActFromPre (device_utils.h: 0x100): e_new holds the pre-activation instead of the stored edge; also launch_sigmoid_bwd)
@@ -476,5 +479,19 @@ struct WeightGradPass {
   int layer_sums = 0, layer_small = 0, layer_group = 0;   // entries of each that belong to the GCN layers (an instalment takes them all: 0 remain)
 };
 size_t small_group_worst_case_floats(const drin_config& c, size_t tn_part_floats);   // of dw_small at once (drin_host_selftest)
+
+// ---- workspace self-checks (drin_host_selftest) ----------------------------------------------------------------------
+// The layouts that live beside their kernels state their regions (arena.h: Region) with the floats the kernels index; all must
+// start on a 256-byte boundary, be disjoint and end inside the layout's total.  DRIN_E_WORKSPACE with the region named otherwise.
+inline int regions_hold(const char* layout, const Region* r, int n, size_t total) {
+  const char* bad = first_bad_region(r, n, total);
+  if (bad == nullptr) return DRIN_OK;
+  set_error("selftest: %s: region %s is misaligned, overlaps another one or ends past the total of %zu floats", layout, bad, total);
+  return DRIN_E_WORKSPACE;
+}
+int fused_layout_selfcheck(const drin_config& c);    // FusedLayout, Prepared (fused_forward.hip)
+int cached_layout_selfcheck(const drin_config& c);   // CachedLayout (entity_cache.hip)
+int melhi_layout_selfcheck(int B, int N, int D, int R, int L);           // MelhiLayout (melhi_kernels.hip)
+int ghmfc_layout_selfcheck(int B, int N, int D, int R, int L, int P, int T);   // GhmfcLayout (ghmfc_kernels.hip)
 
 }  // namespace drin

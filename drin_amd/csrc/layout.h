@@ -3,12 +3,16 @@
 //
 // Inference (training == false) re-uses the per-layer scratch regions across layers and ping-pongs
 // the vertex buffers; training keeps every layer's intermediates because backward reads them.
+//
+// Host only, no HIP include: every region is declared once, by a take() from the arena (arena.h), and every scratch size is
+// the owning module's (scratch_sizes.h).
 #pragma once
-#include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/drin_hip.h"
+#include "arena.h"
+#include "scratch_sizes.h"
 
 namespace drin {
 
@@ -20,6 +24,39 @@ struct Pooled {
   const float* entity_image = nullptr;   // [B, N, R]
   const float* entity_text = nullptr;    // [B, N, D] pooled (ghmfc.py:245-249) or as delivered
   int64_t entity_text_raw_stride = 0;    // row stride of the raw CLS / pooler vector (model.py:73-75)
+};
+
+// Temporaries of drin_backward_ex, offsets in floats from Layout::bwd_scratch.  Vertex gradients keep one generation per level
+// (g_v?[l + 1] = dL/dH of layer l, g_v?[0] = the vertex encoders' output gradient): they are operands of the weight-gradient
+// products, which run as grouped launches at the end of the pass; the edge gradients keep two generations.
+struct BackwardScratch {
+  size_t total_floats = 0;
+  size_t g_vm[DRIN_MAX_LAYERS + 1] = {};   // [2][B][D]
+  size_t g_ve[DRIN_MAX_LAYERS + 1] = {};   // [2][M][D]
+  size_t g_e[2] = {};                      // [4][M](x D)
+  size_t dA_m = 0, dA_e = 0;               // [2][B][D], [2][M][D]  W_h-input gradients
+  size_t dfu_of[DRIN_MAX_LAYERS] = {};     // [2][B][D]  edge-update gradients of layer l: operands of dW_u / dW_v, hence per layer -
+  size_t dfv_of[DRIN_MAX_LAYERS] = {};     // [2][M][D]  except the last layer's (no live edge update), which shares slot 0
+  size_t dpre = 0;                         // [4][M](x D)
+  size_t cos_scratch = 0;                  // [3][M]
+
+  void build(const drin_config& c) {
+    const size_t B = (size_t)c.batch, M = B * (size_t)c.num_candidates, D = (size_t)c.embed_dim;
+    const size_t EW = c.vector_edges ? D : 1;
+    const int nl = c.num_layers, slots = nl > 1 ? nl - 1 : 1;
+    Arena A;
+    for (int l = 0; l <= nl; ++l) g_vm[l] = A.take(2 * B * D);
+    for (int l = 0; l <= nl; ++l) g_ve[l] = A.take(2 * M * D);
+    g_e[0] = A.take(4 * M * EW), g_e[1] = A.take(4 * M * EW);
+    dA_m = A.take(2 * B * D);
+    dA_e = A.take(2 * M * D);
+    for (int l = 0; l < slots; ++l) dfu_of[l] = A.take(2 * B * D);
+    for (int l = 0; l < slots; ++l) dfv_of[l] = A.take(2 * M * D);
+    for (int l = slots; l < nl; ++l) dfu_of[l] = dfu_of[0], dfv_of[l] = dfv_of[0];
+    dpre = A.take(4 * M * EW);
+    cos_scratch = A.take(3 * M);
+    total_floats = A.total;
+  }
 };
 
 struct Layout {
@@ -55,92 +92,86 @@ struct Layout {
   size_t bwd_scratch = 0;                   // backward temporaries (training only)
   size_t bwd_scratch_floats = 0;
 
-  size_t take(size_t n) {
-    const size_t o = total_floats;
-    total_floats += (n + 63) & ~(size_t)63;
-    return o;
-  }
-
   void build(const drin_config& c, bool train) {
     training = train;
-    total_floats = 0;
+    Arena A;
     const size_t B = (size_t)c.batch, N = (size_t)c.num_candidates, D = (size_t)c.embed_dim, R = (size_t)c.image_dim;
     const size_t M = B * N;
     const int nl = c.num_layers;
     const size_t EW = c.vector_edges ? D : 1;  // floats per edge per pair
-    edges_scalar = take(c.vector_edges ? 4 * M : 0);
-    span_mean = take(B * D);
-    mimg_pool = take(B * R);
-    mobj_pool = take(c.mention_object_inner > 1 ? B * c.mention_objects * R : 0);
-    eobj_pool = take(c.entity_object_inner > 1 ? M * c.entity_objects * R : 0);
-    eimg_pool = take(c.entity_image_inner > 1 ? M * R : 0);
-    xet_pool = take(c.entity_tokens > 0 ? M * D : 0);
-    splitk_floats = 2 * B <= 512 ? 16 * 2 * B * D + 64 : 0;   // 8 slices of two [2 B][D] products (grouped launches, gemm_f32.hip)
-    splitk = take(splitk_floats);
+    edges_scalar = A.take(c.vector_edges ? 4 * M : 0);
+    span_mean = A.take(B * D);
+    mimg_pool = A.take(B * R);
+    mobj_pool = A.take(c.mention_object_inner > 1 ? B * c.mention_objects * R : 0);
+    eobj_pool = A.take(c.entity_object_inner > 1 ? M * c.entity_objects * R : 0);
+    eimg_pool = A.take(c.entity_image_inner > 1 ? M * R : 0);
+    xet_pool = A.take(c.entity_tokens > 0 ? M * D : 0);
+    // two [2 B][D] products in one grouped launch (W_h and W_u of the mention vertices)
+    splitk_floats = 2 * B <= (size_t)kSmallSplitkMaxRows ? Arena::rounded(small_splitk_pair_floats(2 * B, D, 2 * B, D)) : 0;
+    splitk = A.take(splitk_floats);
     // split-bf16 precision with scalar edges and at least a tile row of pairs: the weights as planes
-    weight_planes = (c.precision == DRIN_PREC_BF16X3 || c.precision == DRIN_PREC_BF16X3_ALL) && !c.vector_edges && M >= 256 &&
-                    (D % 32) == 0 && (R % 32) == 0;
+    weight_planes = !c.vector_edges && nt_weights_as_planes(c.precision, (int64_t)M, (int)D, (int)R);
     if (weight_planes) {
-      wp_enc[0] = take(D * D), wp_enc[1] = take(D * R), wp_enc[2] = take(D * D), wp_enc[3] = take(D * R);
-      for (int l = 0; l < nl; ++l) wp_h[l] = take(D * D), wp_u[l] = take(D * D), wp_v[l] = take(D * D);
+      wp_enc[0] = A.take(D * D), wp_enc[1] = A.take(D * R), wp_enc[2] = A.take(D * D), wp_enc[3] = A.take(D * R);
+      for (int l = 0; l < nl; ++l) wp_h[l] = A.take(D * D), wp_u[l] = A.take(D * D), wp_v[l] = A.take(D * D);
     }
     if (train) {
       for (int l = 0; l <= nl; ++l) {
-        edges[l] = take(4 * M * EW);
-        vm[l] = take(2 * B * D);
-        ve[l] = take(2 * M * D);
+        edges[l] = A.take(4 * M * EW);
+        vm[l] = A.take(2 * B * D);
+        ve[l] = A.take(2 * M * D);
       }
       for (int l = 0; l < nl; ++l) {
-        masked[l] = take(4 * M * EW);
-        pre[l] = take(c.vector_edges ? 4 * M * D : 0);
-        edge_z[l] = take((c.edge_activation == DRIN_ACT_GELU || c.edge_activation == DRIN_ACT_SILU) && c.dynamic_edges ? 4 * M * EW : 0);
-        agg_m[l] = take(2 * B * D);
-        agg_e[l] = take(2 * M * D);
-        h_m[l] = take(2 * B * D);
-        h_e[l] = take(2 * M * D);
-        ln_stat_m[l] = take(4 * B);
-        ln_stat_e[l] = take(4 * M);
-        fu[l] = take(2 * B * D);
-        fv[l] = take(2 * M * D);
+        masked[l] = A.take(4 * M * EW);
+        pre[l] = A.take(c.vector_edges ? 4 * M * D : 0);
+        edge_z[l] = A.take((c.edge_activation == DRIN_ACT_GELU || c.edge_activation == DRIN_ACT_SILU) && c.dynamic_edges ? 4 * M * EW : 0);
+        agg_m[l] = A.take(2 * B * D);
+        agg_e[l] = A.take(2 * M * D);
+        h_m[l] = A.take(2 * B * D);
+        h_e[l] = A.take(2 * M * D);
+        ln_stat_m[l] = A.take(4 * B);
+        ln_stat_e[l] = A.take(4 * M);
+        fu[l] = A.take(2 * B * D);
+        fv[l] = A.take(2 * M * D);
       }
       // backward temporaries: gradients w.r.t. two generations of vertices/edges + GEMM operands
-      wt = take(((size_t)2 * nl + 1) * D * D);   // slots 2 l, 2 l + 1: W_h^T, W_v^T of layer l; slot 2 nl: the product in flight
-      ln_part = take((size_t)(1024 + 16 + 16 * (nl > 0 ? nl : 1)) * 3 * D);   // + one level-1 area per layer (deferred second level)
-      {  // one workgroup per CU over the whole group of weight-gradient products (launch_gemm_tn_group): at most 256 partial
-        // tiles of 256 x 256 - or, where one product alone has more tiles than that, one slice of each product
-        const size_t one_slice = ((size_t)2 * nl + 1) * D * D + D * R;
-        tn_part_floats = ((size_t)256 * 65536 > one_slice ? (size_t)256 * 65536 : one_slice) + (size_t)8 * 256 * D;  // + column sums
-        tn_part = take(tn_part_floats);
-      }
-      {  // every weight-gradient product of at most 2048 reduction rows may store up to four slices (internal.h:
-        // small_tn_slices); the mention side has 2 B rows at most, the entity side 2 M
+      wt = A.take(((size_t)2 * nl + 1) * D * D);   // slots 2 l, 2 l + 1: W_h^T, W_v^T of layer l; slot 2 nl: the product in flight
+      ln_part = A.take(ln_bwd_level1(D, nl > 0 ? nl : 1));   // + one level-1 area per layer (deferred second level)
+      // dW_h, dW_u | dW_v of every layer, a text and an image encoder: one slice of each
+      const size_t per_side = ((size_t)2 * nl + 1) * D * D + D * R;
+      tn_part_floats = tn_group_floats(per_side, D);
+      tn_part = A.take(tn_part_floats);
+      {  // every mention-sized weight-gradient product may store up to four slices (small_tn_stored_slices); the mention
+        // side has 2 B rows at most, the entity side 2 M
         // (a side's products have `rows` or 2 x `rows` reduction rows - dW_h[top] and the vertex encoders see one vertex type,
-        //  the others both - and the ones past 2048 rows leave the group: each side is sized for whichever of its two row
+        //  the others both - and the ones past the mention-sized limit leave the group: each side is sized for whichever of its two row
         //  counts stores more.  Sized at 2 x rows alone - ADVICE r3 - a side with rows <= 2048 < 2 rows got NO scratch while
         //  its single-type products still stored four slices: DRIN_E_WORKSPACE in exact fp32 at 1024 < B N <= 2048.)
-        auto slices = [](size_t rows) { return rows > 2048 ? (size_t)0 : (rows + 127) / 128 > 4 ? (size_t)4 : (rows + 127) / 128 < 1 ? (size_t)1 : (rows + 127) / 128; };
-        auto side = [&slices](size_t rows) { return slices(rows) > slices(2 * rows) ? slices(rows) : slices(2 * rows); };
-        const size_t per_side = ((size_t)2 * nl + 1) * D * D + D * R;   // dW_h, dW_u | dW_v of every layer, a text and an image encoder
+        auto side = [](size_t rows) {
+          const size_t one = small_tn_stored_slices(rows), both = small_tn_stored_slices(2 * rows);
+          return one > both ? one : both;
+        };
         small_part_floats = (side(B) + side(M)) * per_side + 64;
-        small_part = take(small_part_floats);
-        colsum_part_floats = (size_t)8 * 64 * D;
-        colsum_part = take(colsum_part_floats);
+        small_part = A.take(small_part_floats);
+        colsum_part_floats = colsum_batch_floats(D);
+        colsum_part = A.take(colsum_part_floats);
       }
-      // backward temporaries: vertex gradients per level (nl + 1) + dA + dfv / dfu per layer, entity and mention side; edges x3
-      bwd_scratch_floats = ((size_t)2 * nl + 2) * (2 * M * D + 64 + 2 * B * D + 64) + 3 * (4 * M * EW + 64) + (3 * M + 64);
-      bwd_scratch = take(bwd_scratch_floats);
+      BackwardScratch S;   // last: nothing follows it
+      S.build(c);
+      bwd_scratch_floats = S.total_floats;
+      bwd_scratch = A.take(bwd_scratch_floats);
     } else {
-      size_t e2[2] = {take(4 * M * EW), take(4 * M * EW)};
-      size_t vm2[2] = {take(2 * B * D), take(2 * B * D)};
-      size_t ve2[2] = {take(2 * M * D), take(2 * M * D)};
+      size_t e2[2] = {A.take(4 * M * EW), A.take(4 * M * EW)};
+      size_t vm2[2] = {A.take(2 * B * D), A.take(2 * B * D)};
+      size_t ve2[2] = {A.take(2 * M * D), A.take(2 * M * D)};
       for (int l = 0; l <= nl; ++l) {
         edges[l] = e2[l & 1];
         vm[l] = vm2[l & 1];
         ve[l] = ve2[l & 1];
       }
-      const size_t s_masked = take(4 * M * EW), s_agg_m = take(2 * B * D), s_agg_e = take(2 * M * D);
-      const size_t s_fu = take(2 * B * D);
-      const size_t s_pre = take(c.vector_edges ? 4 * M * D : 0);
+      const size_t s_masked = A.take(4 * M * EW), s_agg_m = A.take(2 * B * D), s_agg_e = A.take(2 * M * D);
+      const size_t s_fu = A.take(2 * B * D);
+      const size_t s_pre = A.take(c.vector_edges ? 4 * M * D : 0);
       for (int l = 0; l < nl; ++l) {
         masked[l] = s_masked;
         pre[l] = s_pre;
@@ -154,6 +185,7 @@ struct Layout {
         fv[l] = s_agg_e;
       }
     }
+    total_floats = A.total;
   }
 };
 
@@ -161,7 +193,5 @@ int validate_config(const drin_config* c);
 int vertex_act(const drin_config* c);   // drin_activation with DRIN_ACT_DEFAULT resolved (gelu)
 int edge_act(const drin_config* c);     // (sigmoid)
 void resolve_pooled(const drin_config* c, const drin_batch* b, const Layout& L, float* ws, Pooled* out);
-int run_pooling(const drin_config* c, const drin_batch* b, const Layout& L, float* ws, Pooled* out, hipStream_t st);
-int run_static_edges(const drin_config* c, const drin_batch* b, const Pooled& P, float* edges, hipStream_t st);
 
 }  // namespace drin

@@ -287,25 +287,20 @@ struct MelhiLayout {
   void build(const drin_melhi_config& c) {
     const size_t B = c.batch, N = c.num_candidates, D = c.embed_dim, R = c.image_dim, L = c.mention_tokens;
     const size_t H = 3 * D, G = 4 * H, BN = B * N;
-    size_t o = 0;
-    auto take = [&](size_t n) {
-      const size_t at = o;
-      o += (n + 63) & ~(size_t)63;   // 256-byte aligned pieces
-      return at;
-    };
-    mimg = take(B * R), mim = take(B * D), eim = take(BN * D), cos1 = take(B), cos2 = take(BN), mask = take(B);
-    word = take(B * D), bsum = take(G), cst = take(B * G), xtok0 = take(2 * B * D), g0 = take(2 * B * G);
-    c0 = take(2 * B * H), h0 = take(2 * B * H), xlane = take(2 * L * D), p = take(2 * L * G), cs = take(2 * L * H);
-    hs = take(2 * L * H), men_in = take(B * 2 * H), men = take(B * D), ent = take(BN * D);
-    ph = take(2 * B), src = take(2 * B), recv = take(2 * B);
-    fwd_floats = o;
-    dmen = take(B * D), dent = take(BN * D), cscr = take(3 * BN), deim = take(BN * D), dmen_in = take(B * 2 * H);
-    dh0 = take(2 * B * H), dg0 = take(2 * B * G), whh_t = take(G * H), dgl = take(2 * L * G), dcc = take(2 * H);
-    dcst = take(B * G), dmim = take(B * D);
+    Arena A;
+    mimg = A.take(B * R), mim = A.take(B * D), eim = A.take(BN * D), cos1 = A.take(B), cos2 = A.take(BN), mask = A.take(B);
+    word = A.take(B * D), bsum = A.take(G), cst = A.take(B * G), xtok0 = A.take(2 * B * D), g0 = A.take(2 * B * G);
+    c0 = A.take(2 * B * H), h0 = A.take(2 * B * H), xlane = A.take(2 * L * D), p = A.take(2 * L * G), cs = A.take(2 * L * H);
+    hs = A.take(2 * L * H), men_in = A.take(B * 2 * H), men = A.take(B * D), ent = A.take(BN * D);
+    ph = A.take(2 * B), src = A.take(2 * B), recv = A.take(2 * B);
+    fwd_floats = A.total;
+    dmen = A.take(B * D), dent = A.take(BN * D), cscr = A.take(3 * BN), deim = A.take(BN * D), dmen_in = A.take(B * 2 * H);
+    dh0 = A.take(2 * B * H), dg0 = A.take(2 * B * G), whh_t = A.take(G * H), dgl = A.take(2 * L * G), dcc = A.take(2 * H);
+    dcst = A.take(B * G), dmim = A.take(B * D);
     // slice scratch of the weight-gradient products (launch_gemm_tn deals its splits by what it is given: fixed per config)
     scratch_floats = 2 * G * H;
-    scratch = take(scratch_floats);
-    total_floats = o;
+    scratch = A.take(scratch_floats);
+    total_floats = A.total;
   }
 };
 
@@ -427,6 +422,27 @@ int timed(int cls, hipStream_t st, const char* what, F&& launch) {
 }
 
 }  // namespace
+
+int melhi_layout_selfcheck(int batch, int n, int d, int r, int tokens) {
+  drin_melhi_config c = {};
+  c.batch = batch, c.num_candidates = n, c.embed_dim = d, c.image_dim = r, c.mention_tokens = tokens;
+  const size_t B = batch, BN = B * n, D = d, R = r, L = tokens, H = 3 * D, G = 4 * H;
+  MelhiLayout W;
+  W.build(c);
+  const Region fwd[] = {
+      {"mimg", W.mimg, B * R}, {"mim", W.mim, B * D}, {"eim", W.eim, BN * D}, {"cos1", W.cos1, B}, {"cos2", W.cos2, BN}, {"mask", W.mask, B},
+      {"word", W.word, B * D}, {"bsum", W.bsum, G}, {"cst", W.cst, B * G}, {"xtok0", W.xtok0, 2 * B * D}, {"g0", W.g0, 2 * B * G},
+      {"c0", W.c0, 2 * B * H}, {"h0", W.h0, 2 * B * H}, {"xlane", W.xlane, 2 * L * D}, {"p", W.p, 2 * L * G}, {"cs", W.cs, 2 * L * H},
+      {"hs", W.hs, 2 * L * H}, {"men_in", W.men_in, 2 * B * H}, {"men", W.men, B * D}, {"ent", W.ent, BN * D}, {"ph", W.ph, 2 * B},
+      {"src", W.src, 2 * B}, {"recv", W.recv, 2 * B}};
+  DRIN_TRY(regions_hold("MelhiLayout (forward)", fwd, (int)(sizeof(fwd) / sizeof(fwd[0])), W.fwd_floats));
+  const Region bwd[] = {
+      {"forward", 0, W.fwd_floats}, {"dmen", W.dmen, B * D}, {"dent", W.dent, BN * D}, {"cscr", W.cscr, 3 * BN}, {"deim", W.deim, BN * D},
+      {"dmen_in", W.dmen_in, 2 * B * H}, {"dh0", W.dh0, 2 * B * H}, {"dg0", W.dg0, 2 * B * G}, {"whh_t", W.whh_t, G * H},
+      {"dgl", W.dgl, 2 * L * G}, {"dcc", W.dcc, 2 * H}, {"dcst", W.dcst, B * G}, {"dmim", W.dmim, B * D}, {"scratch", W.scratch, W.scratch_floats}};
+  return regions_hold("MelhiLayout", bwd, (int)(sizeof(bwd) / sizeof(bwd[0])), W.total_floats);
+}
+
 }  // namespace drin
 
 using namespace drin;

@@ -180,7 +180,9 @@ def test_host_selftest_layout_scratch_and_empty_reductions():
     """`drin_host_selftest` (runs under the ASan / UBSan build through the test below): the slice scratch of the mention-sized
     weight-gradient group covers its worst case at every batch size (exact fp32 at 1024 < B N <= 2048 got none),
     and a grouped GEMM launch handed an item with an empty reduction - what round 3's staged backward once did, SIGFPE on the
-    host - answers DRIN_E_SHAPE instead of dividing by the slice length it would derive from it."""
+    host - answers DRIN_E_SHAPE instead of dividing by the slice length it would derive from it; the
+    regions of the workspaces declared beside their kernels (folded, cached, MELHI, GHMFC, input-gradient scratch, prepared
+    buffer) start on 256-byte boundaries, are disjoint and end inside their totals."""
     lib = _lib.load()
     assert lib.drin_host_selftest() == _lib.OK, lib.drin_last_error()
     # the window ADVICE r3 names, through the public size query: WikiMEL widths, exact fp32, B = 16 (M = 1 616 <= 2 048 < 2 M):

@@ -2,7 +2,9 @@
 out-projections, forward `drin_attention_train_fwd`, backward `drin_attention_bwd`) and `MultiheadAttention`, a drop-in
 `nn.MultiheadAttention` (torch's parameters, state-dict keys and initial draw) whose projections run through
 `drin_linear_fwd` / `drin_linear_bwd`.  This is the block GHMFC runs four times per forward (`baselines/ghmfc.py:96-110`);
-`drin_amd.ghmfc.Model` itself still scores only.  What the kernels compute and what is left: DESIGN.md sections 16 and 11.
+`drin_amd.ghmfc.Model` itself still scores only; `drin_amd.ghmfc_train.TrainableModel` trains.  Attention dropout in training
+mode is an opt-in: a `DropoutStream` handed to the module selects the library's own counter-based mask
+(`drin_attention_dropout_fwd` / `_bwd`).  What the kernels compute and what is left: DESIGN.md sections 16, 18 and 11.
 
 GPU only: there is no CPU fallback and no torch math between the module's input and its output.
 """
@@ -55,14 +57,45 @@ def _as_rows(t: torch.Tensor, width: int) -> Tuple[torch.Tensor, int]:
     return t, ld
 
 
+# ---- dropout --------------------------------------------------------------------------------------------
+class DropoutStream:
+    """The numbering of the library's attention-dropout draws: a `seed` that keys the generator and a counter that gives every
+    forward its own `call` number (csrc/dropout_mask.h: the mask is a pure function of seed, call and element index, not
+    torch's random stream).  Modules that share one stream draw distinct masks.  `log` keeps (call, B, H, Lq, Lk) of the most
+    recent draws, which is what `drin_attention_dropout_keep` needs to regenerate a mask on the host; setting `counter` back
+    reproduces the draws from there."""
+    LOG_LENGTH = 64
+
+    def __init__(self, seed: int = 0):
+        self.seed = int(seed) & (2 ** 64 - 1)
+        self.counter = 0
+        self.log = []
+
+    def draw(self, B: int, H: int, Lq: int, Lk: int) -> int:
+        call = self.counter
+        self.counter += 1
+        self.log.append((call, B, H, Lq, Lk))
+        del self.log[:-self.LOG_LENGTH]
+        return call
+
+
+def dropout_keep(seed: int, call: int, B: int, H: int, Lq: int, Lk: int, p: float) -> torch.Tensor:
+    """The keep mask of one draw, bool [B, H, Lq, Lk] on the CPU, from the library's host function (no GPU)."""
+    keep = torch.empty(B, H, Lq, Lk, dtype=torch.uint8)
+    _lib.check(_lib.load().drin_attention_dropout_keep(seed, call, B, H, Lq, Lk, p, C.c_void_p(keep.data_ptr())))
+    return keep.bool()
+
+
 # ---- the core ---------------------------------------------------------------------------------------------
 class _CoreCall:
     """One forward (+ backward) of the core through the library: geometry, operands with their row strides and the mask; the
     forward's (out, lse) are the autograd node's saved tensors.  `packed`: k is a [B, Lk, 2 E] buffer K | V and the gradient comes
-    back the same way."""
+    back the same way.  `drop`: (p, seed, call) of the dropout entry points, or None for the undropped ones."""
 
-    def __init__(self, q: torch.Tensor, k: torch.Tensor, v: Optional[torch.Tensor], key_mask: Optional[torch.Tensor], num_heads: int):
+    def __init__(self, q: torch.Tensor, k: torch.Tensor, v: Optional[torch.Tensor], key_mask: Optional[torch.Tensor], num_heads: int,
+                 drop: Optional[Tuple[float, int, int]] = None):
         self.lib = _lib.load()
+        self.drop = drop
         self.packed = v is None
         for name, t in (("q", q), ("k", k)) + (() if self.packed else (("v", v),)):
             _require_gpu_f32(name, t)
@@ -95,8 +128,14 @@ class _CoreCall:
         """(out [B, Lq, E], lse [B, H, Lq]): what the backward needs beside the operands."""
         out = torch.empty(self.B, self.Lq, self.E, dtype=torch.float32, device=self.device)
         lse = torch.empty(self.B, self.H, self.Lq, dtype=torch.float32, device=self.device)
-        _lib.check(self.lib.drin_attention_train_fwd(_ptr(self.q), self.ldq, _ptr(self.k), self.ldk, _ptr(self.v), self.ldv,
-                                                     _ptr(self.mask), _ptr(out), self.E, _ptr(lse), *self._geometry()))
+        B, H, Lq, Lk, dh, stream = self._geometry()
+        if self.drop is None:
+            _lib.check(self.lib.drin_attention_train_fwd(_ptr(self.q), self.ldq, _ptr(self.k), self.ldk, _ptr(self.v), self.ldv,
+                                                         _ptr(self.mask), _ptr(out), self.E, _ptr(lse), B, H, Lq, Lk, dh, stream))
+        else:
+            _lib.check(self.lib.drin_attention_dropout_fwd(_ptr(self.q), self.ldq, _ptr(self.k), self.ldk, _ptr(self.v), self.ldv,
+                                                           _ptr(self.mask), _ptr(out), self.E, _ptr(lse), B, H, Lq, Lk, dh, *self.drop,
+                                                           stream))
         return out, lse
 
     def backward(self, out: torch.Tensor, lse: torch.Tensor, dout: torch.Tensor, need_q: bool, need_kv: bool):
@@ -112,16 +151,20 @@ class _CoreCall:
         elif need_kv:
             dk, dv = (torch.empty(self.B, self.Lk, E, dtype=torch.float32, device=self.device) for _ in range(2))
         delta = torch.empty(self.B, self.H, self.Lq, dtype=torch.float32, device=self.device)
-        _lib.check(self.lib.drin_attention_bwd(_ptr(self.q), self.ldq, _ptr(self.k), self.ldk, _ptr(self.v), self.ldv, _ptr(self.mask),
-                                               _ptr(out), E, _ptr(lse), _ptr(dout), lddo, _ptr(dq), E, _ptr(dk), ldd,
-                                               _ptr(dv), ldd, _ptr(delta), *self._geometry()))
+        B, H, Lq, Lk, dh, stream = self._geometry()
+        operands = (_ptr(self.q), self.ldq, _ptr(self.k), self.ldk, _ptr(self.v), self.ldv, _ptr(self.mask), _ptr(out), E, _ptr(lse),
+                    _ptr(dout), lddo, _ptr(dq), E, _ptr(dk), ldd, _ptr(dv), ldd, _ptr(delta), B, H, Lq, Lk, dh)
+        if self.drop is None:
+            _lib.check(self.lib.drin_attention_bwd(*operands, stream))
+        else:
+            _lib.check(self.lib.drin_attention_dropout_bwd(*operands, *self.drop, stream))
         return (dq, dkv, None) if self.packed else (dq, dk, dv)
 
 
 class _CoreFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, key_mask, num_heads):
-        call = _CoreCall(q.detach(), k.detach(), None if v is None else v.detach(), key_mask, num_heads)
+    def forward(ctx, q, k, v, key_mask, num_heads, drop=None):
+        call = _CoreCall(q.detach(), k.detach(), None if v is None else v.detach(), key_mask, num_heads, drop)
         out, lse = call.forward()
         ctx.call = call
         ctx.save_for_backward(out, lse)
@@ -132,20 +175,23 @@ class _CoreFunction(torch.autograd.Function):
         need_q, need_k, need_v = ctx.needs_input_grad[:3]
         out, lse = ctx.saved_tensors
         dq, dk, dv = ctx.call.backward(out, lse, dout, need_q, need_k or need_v)
-        return dq, dk if need_k else None, dv if need_v else None, None, None
+        return dq, dk if need_k else None, dv if need_v else None, None, None, None
 
 
-def attention_core(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, key_mask: Optional[torch.Tensor], num_heads: int) -> torch.Tensor:
+def attention_core(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, key_mask: Optional[torch.Tensor], num_heads: int,
+                   drop: Optional[Tuple[float, int, int]] = None) -> torch.Tensor:
     """out [B, Lq, E] = softmax over the kept keys of (q k^T / sqrt(E / num_heads)) v per head, differentiable in q, k, v.
     q [B, Lq, E], k, v [B, Lk, E]: float32 on the GPU; views with a contiguous last dimension and one row stride (a column
     slice of a wider buffer) are read in place.  key_mask: [B, Lk], nonzero = keep, or None.  A query row with no kept key
-    gives zeros and passes no gradient.  k_len <= 512, head dim <= 256."""
-    return _CoreFunction.apply(q, k, v, key_mask, num_heads)
+    gives zeros and passes no gradient.  k_len <= 512, head dim <= 256.  drop = (p, seed, call): the weights go through the
+    library's dropout mask of that draw (csrc/dropout_mask.h), forward and backward."""
+    return _CoreFunction.apply(q, k, v, key_mask, num_heads, drop)
 
 
-def attention_core_packed(q: torch.Tensor, kv: torch.Tensor, key_mask: Optional[torch.Tensor], num_heads: int) -> torch.Tensor:
+def attention_core_packed(q: torch.Tensor, kv: torch.Tensor, key_mask: Optional[torch.Tensor], num_heads: int,
+                          drop: Optional[Tuple[float, int, int]] = None) -> torch.Tensor:
     """attention_core with K | V side by side in one [B, Lk, 2 E] buffer; its gradient comes back as one buffer dK | dV."""
-    return _CoreFunction.apply(q, kv, None, key_mask, num_heads)
+    return _CoreFunction.apply(q, kv, None, key_mask, num_heads, drop)
 
 
 # ---- the projections ----------------------------------------------------------------------------------------
@@ -206,10 +252,13 @@ class MultiheadAttention(nn.MultiheadAttention):
     With one embedding width and `key is value`, K | V are one product on rows E .. 3 E of `in_proj_weight` and the core's
     packed dK | dV goes back through one.  Refused, each with the reason: CPU tensors, `batch_first=False`, `attn_mask`,
     `need_weights=True`, `add_bias_kv`, `add_zero_attn`, widths that are no multiple of 4, and `dropout > 0` in training
-    mode."""
+    mode without a `dropout_stream`.  With `dropout_stream=DropoutStream(seed)` a training-mode
+    forward draws one call number from the stream and drops attention weights with the library's own mask (not torch's
+    random stream); `eval()` ignores dropout either way."""
 
     def __init__(self, embed_dim, num_heads, dropout=0.0, bias=True, add_bias_kv=False, add_zero_attn=False, kdim=None, vdim=None,
-                 batch_first=False, device=None, dtype=None, precision: str = "bf16x3"):
+                 batch_first=False, device=None, dtype=None, precision: str = "bf16x3",
+                 dropout_stream: Optional[DropoutStream] = None):
         if precision not in PRECISIONS:
             raise ValueError(f"precision {precision!r} not in {sorted(PRECISIONS)}")
         if not batch_first:
@@ -230,6 +279,7 @@ class MultiheadAttention(nn.MultiheadAttention):
         super().__init__(embed_dim, num_heads, dropout=dropout, bias=bias, add_bias_kv=False, add_zero_attn=False, kdim=kdim,
                          vdim=vdim, batch_first=True, device=device, dtype=dtype)
         self.precision = precision
+        self.dropout_stream = dropout_stream
 
     def forward(self, query, key, value, key_padding_mask=None, need_weights=False, attn_mask=None, average_attn_weights=True,
                 is_causal=False):
@@ -239,7 +289,7 @@ class MultiheadAttention(nn.MultiheadAttention):
         if attn_mask is not None or is_causal:
             raise NotImplementedError("drin_amd.attention.MultiheadAttention: attn_mask / is_causal are not implemented; only "
                                       "key_padding_mask is")
-        if self.training and self.dropout > 0:
+        if self.training and self.dropout > 0 and self.dropout_stream is None:
             raise NotImplementedError(f"drin_amd.attention.MultiheadAttention: attention dropout ({self.dropout}) in training mode is "
                                       "not implemented (DESIGN.md section 11); call eval() or build the module with dropout=0")
         _require_gpu_f32("the module (out_proj.weight)", self.out_proj.weight)
@@ -262,6 +312,12 @@ class MultiheadAttention(nn.MultiheadAttention):
             if tuple(key_padding_mask.shape) != (B, Lk):
                 raise RuntimeError(f"key_padding_mask {tuple(key_padding_mask.shape)} is not [batch, k_len] = {(B, Lk)}")
             mask = (~key_padding_mask).to(query.device, torch.int64)
+        drop = None
+        if self.training and self.dropout > 0:
+            if not 0.0 < self.dropout < 1.0:
+                raise ValueError(f"drin_amd.attention.MultiheadAttention: dropout {self.dropout} is not in [0, 1)")
+            stream = self.dropout_stream
+            drop = (float(self.dropout), stream.seed, stream.draw(B, self.num_heads, Lq, Lk))
         prec = PRECISIONS[self.precision]
         bias = self.in_proj_bias
         bq, bk, bv = (None, None, None) if bias is None else (bias[:E], bias[E:2 * E], bias[2 * E:])
@@ -271,15 +327,15 @@ class MultiheadAttention(nn.MultiheadAttention):
             q = _linear(xq, w[:E], bq, prec).view(B, Lq, E)
             if key is value:                       # K | V: one product, one [rows, 2 E] buffer, one backward
                 kv = _linear(key.reshape(B * Lk, E), w[E:], None if bias is None else bias[E:], prec)
-                ctx = attention_core_packed(q, kv.view(B, Lk, 2 * E), mask, self.num_heads)
+                ctx = attention_core_packed(q, kv.view(B, Lk, 2 * E), mask, self.num_heads, drop)
             else:
                 k = _linear(key.reshape(B * Lk, E), w[E:2 * E], bk, prec).view(B, Lk, E)
                 v = _linear(value.reshape(B * Lk, E), w[2 * E:], bv, prec).view(B, Lk, E)
-                ctx = attention_core(q, k, v, mask, self.num_heads)
+                ctx = attention_core(q, k, v, mask, self.num_heads, drop)
         else:
             q = _linear(xq, self.q_proj_weight, bq, prec).view(B, Lq, E)
             k = _linear(key.reshape(B * Lk, self.kdim), self.k_proj_weight, bk, prec).view(B, Lk, E)
             v = _linear(value.reshape(B * Lk, self.vdim), self.v_proj_weight, bv, prec).view(B, Lk, E)
-            ctx = attention_core(q, k, v, mask, self.num_heads)
+            ctx = attention_core(q, k, v, mask, self.num_heads, drop)
         out = _linear(ctx.view(B * Lq, E), self.out_proj.weight, self.out_proj.bias, prec)
         return out.view(B, Lq, E), None

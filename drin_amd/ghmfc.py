@@ -3,7 +3,8 @@ reference's 52 state-dict keys and initialisation order, evaluated by `drin_ghmf
 
 This is the default configuration of `common/args.py` for `model_type = "ghmfc"` (bidirectional cross-attention fusion with
 a GELU gate for the mention, Linear for the entity, offline BERT features) in `eval()` mode, where the dropout inside the four
-attentions is the identity.  Training is not implemented; what is computed and how: section 15.
+attentions is the identity.  This class scores only; `drin_amd.ghmfc_train.TrainableModel` derives from it and trains
+(DESIGN.md section 18).  What is computed and how: section 15.
 """
 from __future__ import annotations
 
@@ -62,13 +63,14 @@ def _ptr(t) -> C.c_void_p:
 
 
 class _CrossAttention(nn.Module):
-    """Parameter container of ghmfc.py's CrossAttention(dim_a, dim_b): same modules, same order."""
+    """Parameter container of ghmfc.py's CrossAttention(dim_a, dim_b): same modules, same order.  `attention`: the class (or
+    a factory with nn.MultiheadAttention's arguments) of the two attentions - a subclass draws the same initial weights."""
 
-    def __init__(self, dim_a: int, dim_b: int, heads: int, dropout: float = 0.1):
+    def __init__(self, dim_a: int, dim_b: int, heads: int, dropout: float = 0.1, attention=nn.MultiheadAttention):
         super().__init__()
-        self.a2b_attention = nn.MultiheadAttention(dim_a, heads, dropout, kdim=dim_b, vdim=dim_b, batch_first=True)
+        self.a2b_attention = attention(dim_a, heads, dropout, kdim=dim_b, vdim=dim_b, batch_first=True)
         self.a2b_ffn = nn.Linear(dim_a, dim_a)
-        self.b2a_attention = nn.MultiheadAttention(dim_a, heads, dropout, batch_first=True)
+        self.b2a_attention = attention(dim_a, heads, dropout, batch_first=True)
         self.b2a_ffn = nn.Linear(dim_a, dim_a)
         self.layernorms = nn.ModuleList([nn.LayerNorm(dim_a) for _ in range(4)])
 
@@ -83,20 +85,20 @@ class _CrossAttention(nn.Module):
 
 
 class _MultimodalFusion(nn.Module):
-    def __init__(self, cfg: GhmfcConfig):
+    def __init__(self, cfg: GhmfcConfig, dropout: float = 0.1, attention=nn.MultiheadAttention):
         super().__init__()
         D, R = cfg.embed_dim, cfg.image_dim
-        self.t2v_attention = _CrossAttention(D, R, cfg.num_heads)
-        self.v2t_attention = _CrossAttention(R, D, cfg.num_heads)
+        self.t2v_attention = _CrossAttention(D, R, cfg.num_heads, dropout, attention)
+        self.v2t_attention = _CrossAttention(R, D, cfg.num_heads, dropout, attention)
         self.text_linear = nn.Linear(D, D)
         self.image_linear = nn.Linear(R, D)
         self.score_linear = nn.Linear(2 * D, 2)
 
 
 class _MentionEncoder(nn.Module):
-    def __init__(self, cfg: GhmfcConfig):
+    def __init__(self, cfg: GhmfcConfig, dropout: float = 0.1, attention=nn.MultiheadAttention):
         super().__init__()
-        self.intermediate_layer = _MultimodalFusion(cfg)
+        self.intermediate_layer = _MultimodalFusion(cfg, dropout, attention)
 
 
 class _EntityEncoder(nn.Module):
@@ -119,8 +121,11 @@ class Model(nn.Module):
         if precision not in PRECISIONS:
             raise ValueError(f"precision {precision!r} not in {sorted(PRECISIONS)}")
         self.cfg, self.precision = cfg, precision
-        self.mention_encoder = _MentionEncoder(cfg)
+        self.mention_encoder = self._make_mention_encoder(cfg)
         self.entity_encoder = _EntityEncoder(cfg)
+
+    def _make_mention_encoder(self, cfg: GhmfcConfig) -> nn.Module:
+        return _MentionEncoder(cfg)
 
     def param_list(self) -> list:
         """The 52 parameters in drin_ghmfc_params (= state-dict) order."""
@@ -129,9 +134,9 @@ class Model(nn.Module):
                 + [f.text_linear.weight, f.text_linear.bias, f.image_linear.weight, f.image_linear.bias, f.score_linear.weight,
                    f.score_linear.bias, self.entity_encoder.final_layer.weight, self.entity_encoder.final_layer.bias])
 
-    def _run(self, batch, want_scores: bool):
-        if self.training:
-            raise RuntimeError("drin_amd.ghmfc.Model is scoring only: call .eval(); GHMFC training is not implemented, DESIGN.md §11")
+    def _batch_tensors(self, batch):
+        """(mention_feature, mention_mask, mention_image, entity_feature, entity_mask or None, entity tokens or 0) of the
+        reference's batch: detached, float32 / int64, contiguous, on the model's device, checked against the configuration."""
         mf, mmask, _begin, _end, mimage, ef, emask = batch[:7]
         dev = self.entity_encoder.final_layer.weight.device
         if dev.type != "cuda" or (isinstance(mf, torch.Tensor) and mf.device.type != "cuda"):
@@ -153,6 +158,16 @@ class Model(nn.Module):
         got = tuple(mf.shape), tuple(mmask.shape), tuple(mimage.shape)
         if got != want or tuple(ef.shape[:2]) != (B, cfg.num_candidates) or ef.shape[-1] != cfg.embed_dim:
             raise ValueError(f"ghmfc batch shapes {got}, entity_feature {tuple(ef.shape)} do not match the configuration {cfg}")
+        return mf, mmask, mimage, ef, emask, tokens
+
+    def _run(self, batch, want_scores: bool):
+        if self.training:
+            raise RuntimeError("drin_amd.ghmfc.Model is scoring only: call .eval(); GHMFC training is not implemented, DESIGN.md §11")
+        return self._score(batch, want_scores)
+
+    def _score(self, batch, want_scores: bool):
+        mf, mmask, mimage, ef, emask, tokens = self._batch_tensors(batch)
+        cfg, dev, B = self.cfg, mf.device, mf.shape[0]
         lib = _lib.load()
         c = _lib.DrinGhmfcConfigC(batch=B, num_candidates=cfg.num_candidates, embed_dim=cfg.embed_dim, image_dim=cfg.image_dim,
                                   mention_tokens=cfg.mention_tokens, image_regions=cfg.image_regions, num_heads=cfg.num_heads,

@@ -1,5 +1,5 @@
 """The two modules the reference's driver binds for `model_type = "ghmfc"` (`train.py:9-14`), backed by this library, for
-scoring a trained checkpoint (`trainer.test`): GHMFC training is not implemented.
+training (`trainer.fit`) and for scoring a trained checkpoint (`trainer.test`); DESIGN.md sections 15 and 18.
 
 In a checkout of the reference the binding is one changed line of `train.py`:
 
@@ -19,8 +19,8 @@ import numpy as np
 import torch
 from torch.utils.data import DataLoader, Dataset
 
-from .ghmfc import Model as _Model
 from .ghmfc import config_from_reference_args
+from .ghmfc_train import TrainableModel as _Model
 from .melhi_shim import SPLITS
 
 
@@ -29,10 +29,13 @@ def _args():
 
 
 class Model(_Model):
-    """`model_module.Model()`: geometry from `common.args`; split-bf16 products unless DRIN_PRECISION=f32."""
+    """`model_module.Model()`: geometry and `transformer_dropout` from `common.args`; split-bf16 products unless
+    DRIN_PRECISION=f32.  The attention dropout of train() mode is the library's own mask, seeded by `args.seed`."""
 
     def __init__(self):
-        super().__init__(config_from_reference_args(_args()), precision=os.environ.get("DRIN_PRECISION", "bf16x3"))
+        a = _args()
+        super().__init__(config_from_reference_args(a), precision=os.environ.get("DRIN_PRECISION", "bf16x3"),
+                         dropout=getattr(a, "transformer_dropout", 0.1), seed=getattr(a, "seed", 0))
 
 
 class GhmfcData(Dataset):

@@ -1,0 +1,188 @@
+"""GHMFC's row operations as differentiable functions on the HIP library: LayerNorm with a fused residual, the max over a
+sequence, the gate, the cosine against the candidates and the entity token mean - one `torch.autograd.Function` per pair of
+entry points (`drin_layernorm_res_train_fwd` / `_bwd`, `drin_seq_max_train_fwd` / `_bwd`, `drin_gate_mix_fwd` / `_bwd`,
+`drin_cosine_rows_fwd` / `_bwd`, `drin_entity_token_mean`).  What the kernels compute: DESIGN.md section 18.
+
+GPU only, float32, contiguous rows; there is no CPU fallback and no torch math inside.
+"""
+from __future__ import annotations
+
+from typing import Optional, Tuple
+
+import torch
+
+from . import _lib
+from .attention import _ptr, _require_gpu_f32, _stream
+
+_scratch = {}
+
+
+def _row_scratch(device, stream_id: int, floats: int) -> torch.Tensor:
+    """Scratch of the ordered column sums, one per (device, stream) and grown to the largest need: calls on one stream run
+    in order, so they share it."""
+    key = (device, stream_id)
+    buf = _scratch.get(key)
+    if buf is None or buf.numel() < floats:
+        buf = _scratch[key] = torch.empty(max(floats, 1), dtype=torch.float32, device=device)
+    return buf
+
+
+def _rows(name: str, t: torch.Tensor) -> torch.Tensor:
+    _require_gpu_f32(name, t)
+    return t.detach().contiguous()
+
+
+class _LayerNormRes(torch.autograd.Function):
+    """y = LayerNorm(x [+ res]); the gradient of the pre-norm sum goes to x and to res alike."""
+
+    @staticmethod
+    def forward(ctx, x, res, gamma, beta, eps):
+        x, gamma, beta = _rows("x", x), _rows("gamma", gamma), _rows("beta", beta)
+        res = None if res is None else _rows("res", res)
+        if res is not None and res.shape != x.shape:
+            raise RuntimeError(f"layer_norm_res: x {tuple(x.shape)} and res {tuple(res.shape)} differ")
+        E = x.shape[-1]
+        rows = x.numel() // E
+        y = torch.empty_like(x)
+        mean, rstd = (torch.empty(rows, dtype=torch.float32, device=x.device) for _ in range(2))
+        _lib.check(_lib.load().drin_layernorm_res_train_fwd(_ptr(x), _ptr(res), _ptr(gamma), _ptr(beta), _ptr(y), _ptr(mean), _ptr(rstd),
+                                                            rows, E, eps, _stream(x.device)))
+        ctx.save_for_backward(x, res, gamma, mean, rstd)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, res, gamma, mean, rstd = ctx.saved_tensors
+        need_x, need_res, need_g, need_b = ctx.needs_input_grad[:4]
+        if not (need_x or need_res or need_g or need_b):
+            return None, None, None, None, None
+        lib = _lib.load()
+        E = x.shape[-1]
+        rows = x.numel() // E
+        dy = dy.contiguous()
+        dh = torch.empty_like(x)
+        dgamma = torch.empty_like(gamma) if need_g else None
+        dbeta = torch.empty_like(gamma) if need_b else None
+        stream = _stream(x.device)
+        floats = lib.drin_layernorm_res_bwd_scratch_floats(rows, E) if (need_g or need_b) else 0
+        scratch = _row_scratch(x.device, stream.value or 0, floats) if floats else None
+        _lib.check(lib.drin_layernorm_res_bwd(_ptr(x), _ptr(res), _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(dy), _ptr(dh), _ptr(dgamma),
+                                              _ptr(dbeta), _ptr(scratch), floats, rows, E, stream))
+        return dh if need_x else None, dh if (need_res and res is not None) else None, dgamma, dbeta, None
+
+
+def layer_norm_res(x: torch.Tensor, res: Optional[torch.Tensor], gamma: torch.Tensor, beta: torch.Tensor, eps: float = 1e-5):
+    """LayerNorm(x + res) over the last dimension (res may be None), widths that are multiples of 4 up to 2048."""
+    return _LayerNormRes.apply(x, res, gamma, beta, eps)
+
+
+class _SeqMax(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        x = _rows("x", x)
+        B, S, E = x.shape
+        out = torch.empty(B, E, dtype=torch.float32, device=x.device)
+        idx = torch.empty(B, E, dtype=torch.int32, device=x.device)
+        _lib.check(_lib.load().drin_seq_max_train_fwd(_ptr(x), _ptr(out), _ptr(idx), B, S, E, _stream(x.device)))
+        ctx.save_for_backward(idx)
+        ctx.seq_len = S
+        ctx.mark_non_differentiable(idx)
+        return out, idx
+
+    @staticmethod
+    def backward(ctx, dout, _didx):
+        (idx,) = ctx.saved_tensors
+        B, E = idx.shape
+        dout = dout.contiguous()
+        dx = torch.empty(B, ctx.seq_len, E, dtype=torch.float32, device=idx.device)
+        _lib.check(_lib.load().drin_seq_max_bwd(_ptr(dout), _ptr(idx), _ptr(dx), B, ctx.seq_len, E, _stream(idx.device)))
+        return dx
+
+
+def seq_max(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(max over dim 1 of x [B, S, E], idx int32 [B, E]): idx is the lowest position that attains the maximum (the lowest NaN
+    position when the column holds one); the gradient goes to that position alone."""
+    return _SeqMax.apply(x)
+
+
+class _GateMix(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, tl, vl, ws, bs):
+        tl, vl, ws, bs = _rows("tl", tl), _rows("vl", vl), _rows("ws", ws), _rows("bs", bs)
+        B, D = tl.shape
+        if tuple(vl.shape) != (B, D) or tuple(ws.shape) != (2, 2 * D) or tuple(bs.shape) != (2,):
+            raise RuntimeError(f"gate_mix: tl {tuple(tl.shape)}, vl {tuple(vl.shape)}, ws {tuple(ws.shape)}, bs {tuple(bs.shape)} do not fit")
+        out = torch.empty_like(tl)
+        _lib.check(_lib.load().drin_gate_mix_fwd(_ptr(tl), _ptr(vl), _ptr(ws), _ptr(bs), _ptr(out), B, D, _stream(tl.device)))
+        ctx.save_for_backward(tl, vl, ws, bs)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        tl, vl, ws, bs = ctx.saved_tensors
+        need_t, need_v, need_w, need_b = ctx.needs_input_grad
+        if not any(ctx.needs_input_grad):
+            return None, None, None, None
+        lib = _lib.load()
+        B, D = tl.shape
+        dout = dout.contiguous()
+        dtl, dvl = torch.empty_like(tl), torch.empty_like(vl)
+        dws = torch.empty_like(ws) if need_w else None
+        dbs = torch.empty(2, dtype=torch.float32, device=tl.device) if need_b else None
+        stream = _stream(tl.device)
+        floats = lib.drin_gate_mix_bwd_scratch_floats(B, D) if (need_w or need_b) else 0
+        scratch = _row_scratch(tl.device, stream.value or 0, floats) if floats else None
+        _lib.check(lib.drin_gate_mix_bwd(_ptr(tl), _ptr(vl), _ptr(ws), _ptr(bs), _ptr(dout), _ptr(dtl), _ptr(dvl), _ptr(dws), _ptr(dbs),
+                                         _ptr(scratch), floats, B, D, stream))
+        return dtl if need_t else None, dvl if need_v else None, dws, dbs
+
+
+def gate_mix(tl: torch.Tensor, vl: torch.Tensor, ws: torch.Tensor, bs: torch.Tensor) -> torch.Tensor:
+    """s0 gelu(tl) + s1 gelu(vl) with s = softmax([gelu(tl) | gelu(vl)] ws^T + bs): tl, vl [B, D], ws [2, 2 D], bs [2]."""
+    return _GateMix.apply(tl, vl, ws, bs)
+
+
+class _CosineRows(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, y, eps):
+        x, y = _rows("x", x), _rows("y", y)
+        B, D = x.shape
+        if y.dim() != 3 or y.shape[0] != B or y.shape[2] != D:
+            raise RuntimeError(f"cosine_rows: x {tuple(x.shape)} and y {tuple(y.shape)} do not fit")
+        N = y.shape[1]
+        out = torch.empty(B, N, dtype=torch.float32, device=x.device)
+        _lib.check(_lib.load().drin_cosine_rows_fwd(_ptr(x), _ptr(y), _ptr(out), B, N, D, eps, _stream(x.device)))
+        ctx.save_for_backward(x, y)
+        ctx.eps = eps
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, y = ctx.saved_tensors
+        need_x, need_y = ctx.needs_input_grad[:2]
+        if not (need_x or need_y):
+            return None, None, None
+        B, N, D = y.shape
+        dout = dout.contiguous()
+        dx, dy = torch.empty_like(x), torch.empty_like(y)
+        stream = _stream(x.device)
+        scratch = _row_scratch(x.device, stream.value or 0, 3 * B * N)
+        _lib.check(_lib.load().drin_cosine_rows_bwd(_ptr(x), _ptr(y), _ptr(dout), _ptr(dx), _ptr(dy), _ptr(scratch), scratch.numel(), B, N, D,
+                                                    ctx.eps, stream))
+        return dx if need_x else None, dy if need_y else None, None
+
+
+def cosine_rows(x: torch.Tensor, y: torch.Tensor, eps: float = 1e-8) -> torch.Tensor:
+    """out [B, N] = cos(x[b], y[b, n]) with nn.CosineSimilarity's clamp: x [B, D], y [B, N, D]."""
+    return _CosineRows.apply(x, y, eps)
+
+
+def entity_token_mean(feat: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
+    """[B, N, D] = mean of tokens 1 : ntok - 1 of feat [B, N, T, D], ntok = mask.sum(-1) (mask [B, N, T]); an entity with
+    fewer than 3 tokens gives a NaN row, as the reference's empty mean.  An input: no gradient."""
+    feat = _rows("entity_feature", feat)
+    B, N, T, D = feat.shape
+    mask = mask.to(feat.device, torch.int64).contiguous()
+    out = torch.empty(B, N, D, dtype=torch.float32, device=feat.device)
+    _lib.check(_lib.load().drin_entity_token_mean(_ptr(feat), _ptr(mask), _ptr(out), B * N, T, D, _stream(feat.device)))
+    return out

@@ -703,6 +703,90 @@ DRIN_API int drin_attention_bwd(const float* q, int64_t ldq, const float* k, int
                                 float* delta_scratch, int32_t batch, int32_t num_heads, int32_t q_len, int32_t k_len,
                                 int32_t head_dim, void* stream);
 
+/* ---- attention dropout (what nn.MultiheadAttention(dropout = transformer_dropout) does in train() mode, ghmfc.py:96-110) -- *
+ * The library's own mask, NOT torch's random stream: element (b, h, i, j) of the [batch, num_heads, q_len, k_len] attention
+ * weights is kept iff the Philox4x32-10 word of (seed, call, flat index) is >= llrint(p * 2^32), and a kept weight is
+ * multiplied by 1 / (1 - p): out[i] = sum_j P[i, j] M[i, j] / (1 - p) v[j] with P the undropped softmax.  The function is
+ * defined once for host and device in csrc/dropout_mask.h (the contract) and exported to the host as
+ * drin_attention_dropout_keep.  p in [0, 1), anything else (a NaN too) is DRIN_E_SHAPE; p = 0 gives
+ * drin_attention_train_fwd / drin_attention_bwd's bits.  `seed` keys the generator, `call` numbers the draw: the caller
+ * gives every forward its own call number and hands the same (p, seed, call) to its backward. */
+
+/* drin_attention_train_fwd with dropout on the weights; lse is unchanged: the log-sum-exp of the undropped scores. */
+DRIN_API int drin_attention_dropout_fwd(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv,
+                                        const int64_t* key_mask, float* out, int64_t ldo, float* lse, int32_t batch,
+                                        int32_t num_heads, int32_t q_len, int32_t k_len, int32_t head_dim, float p, uint64_t seed,
+                                        uint64_t call, void* stream);
+/* drin_attention_bwd of that forward.  With Pd = P M / (1 - p): dv = Pd^T dout, dp = (dout v^T) M / (1 - p),
+ * ds = P (dp - delta), delta[i] = sum_c dout[i, c] out[i, c] as before (out = Pd v).  A key dropped by key_mask still has
+ * dk and dv rows of exactly 0. */
+DRIN_API int drin_attention_dropout_bwd(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv,
+                                        const int64_t* key_mask, const float* out, int64_t ldo, const float* lse,
+                                        const float* dout, int64_t lddo, float* dq, int64_t lddq, float* dk, int64_t lddk,
+                                        float* dv, int64_t lddv, float* delta_scratch, int32_t batch, int32_t num_heads,
+                                        int32_t q_len, int32_t k_len, int32_t head_dim, float p, uint64_t seed, uint64_t call,
+                                        void* stream);
+/* HOST only, no GPU: keep_host[((b * num_heads + h) * q_len + i) * k_len + j] = 1 if the weight is kept, else 0. */
+DRIN_API int drin_attention_dropout_keep(uint64_t seed, uint64_t call, int32_t batch, int32_t num_heads, int32_t q_len,
+                                         int32_t k_len, float p, uint8_t* keep_host);
+
+/* ---- GHMFC's row operations one by one, forward and backward --------------- *
+ * What drin_ghmfc_forward runs between its products, exposed so that a training step can be composed from them, and their
+ * backward kernels.  Every pointer is a 16-byte aligned device pointer, rows are contiguous, widths are multiples of 4.
+ * All arguments are checked on the host before a launch.  fp32 FMA, no atomics: the same bits every run.  Gradients are
+ * WRITTEN, not accumulated.  Profiler class DRIN_KC_NORM (the cosine and the token mean keep their own classes). */
+
+/* y = LayerNorm(x [+ res]) * gamma + beta over rows of `width` (<= 2048) floats; res may be NULL; y may be x or res.
+ * y has the bits drin_ghmfc_forward's LayerNorm gives; mean, rstd [rows] are the statistics the backward needs. */
+DRIN_API int drin_layernorm_res_train_fwd(const float* x, const float* res, const float* gamma, const float* beta, float* y,
+                                          float* mean, float* rstd, int64_t rows, int32_t width, float eps, void* stream);
+/* Floats of scratch for drin_layernorm_res_bwd's column sums (0: rows < 1 or a bad width). */
+DRIN_API size_t drin_layernorm_res_bwd_scratch_floats(int64_t rows, int32_t width);
+/* Backward of it: x, res, gamma, mean, rstd as in the forward, dy [rows, width] the gradient of y.  With xhat recomputed and
+ * g = dy gamma: dh = rstd (g - mean_c(g) - xhat mean_c(g xhat)) [rows, width] is the gradient of the pre-norm sum, i.e. of
+ * x AND of res (dh may be dy).  dgamma = sum_rows dy xhat, dbeta = sum_rows dy [width]: per-workgroup partial sums in
+ * `scratch`, then added in a fixed order.  dgamma and dbeta may be NULL (frozen LayerNorm; with both NULL the reduction is
+ * skipped and scratch is not read); dh has the same bits either way. */
+DRIN_API int drin_layernorm_res_bwd(const float* x, const float* res, const float* mean, const float* rstd, const float* gamma,
+                                    const float* dy, float* dh, float* dgamma, float* dbeta, float* scratch,
+                                    size_t scratch_floats, int64_t rows, int32_t width, void* stream);
+
+/* out[b, c] = max_s x[b, s, c] over ALL seq_len positions of x [batch, seq_len, width] (a NaN wins, as torch.max), with
+ * drin_ghmfc_forward's bits, and idx[b, c] (int32) = the LOWEST position that attains it; a column that holds a NaN reports
+ * its lowest NaN position.  batch <= 65535. */
+DRIN_API int drin_seq_max_train_fwd(const float* x, float* out, int32_t* idx, int32_t batch, int32_t seq_len, int32_t width,
+                                    void* stream);
+/* dx [batch, seq_len, width], every element written: dout[b, c] at (b, idx[b, c], c), exactly 0 elsewhere. */
+DRIN_API int drin_seq_max_bwd(const float* dout, const int32_t* idx, float* dx, int32_t batch, int32_t seq_len, int32_t width,
+                              void* stream);
+
+/* The gate (ghmfc.py:144-149): t = gelu(tl), v = gelu(vl) [batch, width], z = [t | v] ws^T + bs (ws [2, 2 width], bs [2]),
+ * s = softmax(z), out = s0 t + s1 v, with drin_ghmfc_forward's bits. */
+DRIN_API int drin_gate_mix_fwd(const float* tl, const float* vl, const float* ws, const float* bs, float* out, int32_t batch,
+                               int32_t width, void* stream);
+DRIN_API size_t drin_gate_mix_bwd_scratch_floats(int32_t batch, int32_t width);
+/* Backward of it (width <= 2048): t, v, z, s are recomputed.  With a = sum_c dout_c (t_c - v_c): dz0 = s0 s1 a = -dz1,
+ * dt = s0 dout + dz0 ws[0, :width] + dz1 ws[1, :width], dv likewise with s1 and the right halves, dtl = dt gelu'(tl),
+ * dvl = dv gelu'(vl) (exact-erf gelu').  dws [2, 2 width] and dbs [2] are sums over the mentions, reduced in order through
+ * `scratch`; each may be NULL. */
+DRIN_API int drin_gate_mix_bwd(const float* tl, const float* vl, const float* ws, const float* bs, const float* dout, float* dtl,
+                               float* dvl, float* dws, float* dbs, float* scratch, size_t scratch_floats, int32_t batch,
+                               int32_t width, void* stream);
+
+/* out[b, n] = cos(x[b, :], y[b, n, :]) with nn.CosineSimilarity's eps clamp; x [batch, width], y [batch, num_candidates, width]
+ * (num_candidates <= 65535). */
+DRIN_API int drin_cosine_rows_fwd(const float* x, const float* y, float* out, int32_t batch, int32_t num_candidates, int32_t width,
+                                  float eps, void* stream);
+/* dx [batch, width], dy [batch, num_candidates, width] for dout [batch, num_candidates]; scratch: 3 batch num_candidates
+ * floats; width <= 1024. */
+DRIN_API int drin_cosine_rows_bwd(const float* x, const float* y, const float* dout, float* dx, float* dy, float* scratch,
+                                  size_t scratch_floats, int32_t batch, int32_t num_candidates, int32_t width, float eps,
+                                  void* stream);
+/* out[p, :] = mean(feat[p, 1 : ntok - 1, :]), ntok = sum(mask[p, :]) (ghmfc.py:245-249); feat [pairs, tokens, width], mask
+ * int64 [pairs, tokens].  Fewer than 3 tokens: a NaN row, as the reference's empty mean. */
+DRIN_API int drin_entity_token_mean(const float* feat, const int64_t* mask, float* out, int64_t pairs, int32_t tokens,
+                                    int32_t width, void* stream);
+
 /* ---- in-process kernel timing (bench.py's roofline leg) ---------------------------------------- */
 
 /* Kernel classes the launches are attributed to. */
@@ -718,7 +802,7 @@ typedef enum {
   DRIN_KC_LSTM = 8,        /* drin_melhi_*: one step of the long LSTM recurrences (forward or backward) */
   DRIN_KC_CELL = 9,        /* drin_melhi_*: mask, time-0 cells, gathers and their backward           */
   DRIN_KC_ATTN = 10,       /* drin_attention* / drin_ghmfc_forward: the softmax-attention core and its backward */
-  DRIN_KC_NORM = 11,       /* drin_ghmfc_forward: LayerNorm (+ residual), max over a sequence, the gated mix  */
+  DRIN_KC_NORM = 11,       /* drin_ghmfc_forward and the row-op entry points: LayerNorm (+ residual), max over a sequence, the gate, their backward */
   DRIN_KC_COUNT = 12
 } drin_kernel_class;
 

@@ -135,6 +135,34 @@ class DrinGemmProbeArgsC(C.Structure):   # drin_gemm_probe: a test and tuning en
                 ("a_index", C.c_void_p), ("row_scale", C.c_void_p), ("b_scale", C.c_void_p), ("route", DrinGemmRouteC)]
 
 
+class DrinWgradProductC(C.Structure):
+    _fields_ = [("dy", C.c_void_p), ("lddy", C.c_int64), ("x", C.c_void_p), ("ldx", C.c_int64), ("x_index", C.c_void_p), ("dw", C.c_void_p),
+                ("lddw", C.c_int64), ("db", C.c_void_p), ("rows", C.c_int64), ("n_out", C.c_int32), ("k", C.c_int32)]
+
+
+class DrinWgradProductRouteC(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("kernel", "slices", "in_place", "db_rode", "db_slices", "launch")] + [("rows_per_slice", C.c_int64)]
+
+
+WGRAD_PROBE_MAX, WGRAD_ROUTE_LAUNCHES = 16, 8
+
+
+class DrinWgradRouteC(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("gemm_launches", "colsum_launches", "sum_launches", "reduce_launches", "sum_dsts", "sum_segs",
+                                         "nn_family", "nn_bm", "nn_bn", "nn_splits", "nn_wt_form", "nn_accumulate")] + [
+        ("grid", C.c_int64 * WGRAD_ROUTE_LAUNCHES), ("product", DrinWgradProductRouteC * WGRAD_PROBE_MAX)]
+
+
+class DrinWgradProbeArgsC(C.Structure):   # drin_wgrad_probe: a test and tuning entry, no stability promise beyond struct_size
+    _fields_ = [("struct_size", C.c_size_t), ("op", C.c_int32), ("precision", C.c_int32), ("staged", C.c_int32), ("n_products", C.c_int32),
+                ("layers_done_after", C.c_int32), ("accumulate", C.c_int32), ("wt_form", C.c_int32), ("reserved", C.c_int32),
+                ("scratch", C.c_void_p), ("scratch_floats", C.c_size_t), ("wt", C.c_void_p), ("wt_floats", C.c_size_t),
+                ("product", DrinWgradProductC * WGRAD_PROBE_MAX), ("route", DrinWgradRouteC)]
+
+
+WGRAD_TN_GROUP, WGRAD_TN_F32_GROUP, WGRAD_TN, WGRAD_COLSUM_BATCH, WGRAD_PASS, WGRAD_NN = range(1, 7)
+WGRAD_KERNEL = {0: "none", 1: "tn_bf16x3", 2: "tn_f32_small", 3: "tn_f32_large"}
+WGRAD_WT_NONE, WGRAD_WT_F32_SCRATCH, WGRAD_WT_PLANES = range(3)
 PROBE_GEMM_NT, PROBE_GEMM_NT_BF16X3, PROBE_GEMM_NT_BF16X3_P4, PROBE_GEMM_X3_PLANES, PROBE_GEMM_F16_PLANES, PROBE_TO_F16_SCALED = range(1, 7)
 GEMM_FAMILY = {0: "none", 1: "bf16x3", 2: "bf16x3_p4", 3: "planes", 4: "planes_p4", 5: "f32", 6: "f32_gemv"}
 
@@ -192,6 +220,7 @@ EXPORTS = {
     "drin_linear_planes_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
     "drin_gemm_probe": (C.c_int, [C.POINTER(DrinGemmProbeArgsC), C.c_void_p]),
+    "drin_wgrad_probe": (C.c_int, [C.POINTER(DrinWgradProbeArgsC), C.c_void_p]),
     "drin_loss_workspace_bytes": (C.c_size_t, [C.c_int32]),
     "drin_triplet_topk": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.POINTER(C.c_int32), C.c_int32,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),

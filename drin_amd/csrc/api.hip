@@ -13,6 +13,7 @@
 #include "gemm_probe_check.h"
 #include "internal.h"
 #include "layout.h"
+#include "wgrad_probe_check.h"
 
 namespace drin {
 
@@ -34,6 +35,8 @@ int hip_fail(hipError_t e, const char* what) {
 static thread_local int g_call_device = -1;
 static thread_local drin_gemm_route g_gemm_route = {};
 drin_gemm_route& gemm_route() { return g_gemm_route; }
+static thread_local WgradTrace g_wgrad_trace = {};
+WgradTrace& wgrad_trace() { return g_wgrad_trace; }
 
 int call_device() {
   if (g_call_device >= 0) return g_call_device;
@@ -826,6 +829,104 @@ int drin_gemm_probe(drin_gemm_probe_args* p, void* stream) {
     default: break;
   }
   p->route = gemm_route();
+  return rc;
+}
+
+// the ops of drin_wgrad_probe, each the module's own launcher on the caller's products
+static int wgrad_probe_run(const drin_wgrad_probe_args* p, hipStream_t st) {
+  const drin_wgrad_product* q = p->product;
+  const int n = p->n_products;
+  switch (p->op) {
+    case DRIN_WGRAD_TN_GROUP: {
+      TnGroup g;
+      for (int i = 0; i < n; ++i)
+        DRIN_TRY(g.add(q[i].dy, q[i].lddy, q[i].x, q[i].ldx, q[i].dw, q[i].lddw, q[i].rows, q[i].n_out, q[i].k, q[i].x_index, q[i].db));
+      return launch_gemm_tn_group(g, st, p->scratch, p->scratch_floats);
+    }
+    case DRIN_WGRAD_TN_F32_GROUP: {
+      F32GemmGroup g;
+      for (int i = 0; i < n; ++i) DRIN_TRY(g.add_tn(q[i].dy, q[i].lddy, q[i].x, q[i].ldx, q[i].dw, q[i].lddw, q[i].rows, q[i].n_out, q[i].k));
+      return launch_gemm_tn_f32_group(g, st, p->scratch, p->scratch_floats);
+    }
+    case DRIN_WGRAD_TN:
+      return launch_gemm_tn(q->dy, q->lddy, q->x, q->ldx, q->dw, q->lddw, q->rows, q->n_out, q->k, p->precision, st, p->scratch,
+                            p->scratch_floats);
+    case DRIN_WGRAD_COLSUM_BATCH: {
+      ColsumBatch b;
+      for (int i = 0; i < n; ++i) DRIN_TRY(b.add(q[i].dy, q[i].db, q[i].rows, q[i].n_out, q[i].lddy));
+      return launch_colsum_batch(b, st, p->scratch, p->scratch_floats);
+    }
+    case DRIN_WGRAD_PASS: {
+      // the three parts of the pass, sized by the functions the workspace layouts size them with
+      size_t tile = 0, widest = 0, small_floats = 0;
+      for (int i = 0; i < n; ++i) {
+        const size_t nk = (size_t)q[i].n_out * q[i].k;
+        tile = nk > tile ? nk : tile;
+        widest = (size_t)q[i].n_out > widest ? (size_t)q[i].n_out : widest;
+        small_floats += Arena::rounded((size_t)small_tn_slices(q[i].rows) * nk);
+      }
+      Arena arena;
+      const size_t tn_floats = tn_group_floats(tile, widest), cs_floats = colsum_batch_floats(widest);
+      const size_t tn_at = arena.take(tn_floats), cs_at = arena.take(cs_floats), small_at = arena.take(small_floats);
+      if (p->scratch == nullptr || arena.total > p->scratch_floats) {
+        set_error("drin_wgrad_probe: the pass needs %zu floats of scratch, %zu given", arena.total, p->scratch_floats);
+        return DRIN_E_WORKSPACE;
+      }
+      WeightGradPass pass{p->precision, false, st, {Arena::at(p->scratch, tn_at), tn_floats}, {Arena::at(p->scratch, small_at), small_floats},
+                          {Arena::at(p->scratch, cs_at), cs_floats}};
+      for (int i = 0; i < n; ++i) {
+        DRIN_TRY(pass.add(q[i].dy, q[i].lddy, q[i].x, q[i].ldx, q[i].dw, q[i].lddw, q[i].rows, q[i].n_out, q[i].k, q[i].x_index, q[i].db));
+        if (i == p->layers_done_after) pass.layers_done();
+      }
+      if (!p->staged) return pass.finish(nullptr);
+      hipEvent_t ev = nullptr;
+      if (hipError_t e = hipEventCreateWithFlags(&ev, hipEventDisableTiming); e != hipSuccess) return hip_fail(e, "hipEventCreate(wgrad probe)");
+      const int rc = pass.finish(ev);
+      (void)hipEventDestroy(ev);   // (a recorded event is released once it has completed)
+      return rc;
+    }
+    case DRIN_WGRAD_NN: {
+      // dX [rows][k] (+)= dY [rows][n_out] W [n_out][k]: launch_gemm_nn's (M, N, K) = (rows, k, n_out)
+      WtForms wt;
+      if (p->wt_form != DRIN_WGRAD_WT_NONE && p->wt_floats < (size_t)q->n_out * q->k) {
+        set_error("drin_wgrad_probe: %zu floats for W^T, %zu needed", p->wt_floats, (size_t)q->n_out * q->k);
+        return DRIN_E_WORKSPACE;
+      }
+      if (p->wt_form == DRIN_WGRAD_WT_F32_SCRATCH) wt.scratch = p->wt, wt.scratch_floats = p->wt_floats;
+      if (p->wt_form == DRIN_WGRAD_WT_PLANES) {
+        if (q->ldx != q->k) {
+          set_error("drin_wgrad_probe: the planes of W^T are written from a contiguous W (ldx == k)");
+          return DRIN_E_SHAPE;
+        }
+        SplitBatch tb;
+        DRIN_TRY(tb.add(q->x, p->wt, (int64_t)q->n_out * q->k));
+        DRIN_TRY(launch_transpose_split_batch(tb, q->n_out, q->k, st));
+        wt.planes = p->wt;
+      }
+      return launch_gemm_nn(q->dy, q->lddy, q->x, q->ldx, q->dw, q->lddw, q->rows, q->k, q->n_out, p->accumulate != 0, p->precision, st,
+                            p->scratch, p->scratch_floats, wt);
+    }
+    default: return DRIN_E_UNSUPPORTED;
+  }
+}
+
+int drin_wgrad_probe(drin_wgrad_probe_args* p, void* stream) {
+  char msg[256];
+  const int bad = wgrad_probe_check(p, msg, sizeof msg);   // (host only: before anything asks the runtime about a pointer)
+  if (bad != DRIN_OK) {
+    set_error("%s", msg);
+    if (p != nullptr && p->struct_size == sizeof(drin_wgrad_probe_args)) p->route = drin_wgrad_route{};
+    return bad;
+  }
+  p->route = drin_wgrad_route{};
+  DRIN_BIND_DEVICE(stream, p->product[0].dy, "drin_wgrad_probe");
+  gemm_route() = drin_gemm_route{};
+  WgradTrace& t = wgrad_trace();
+  t.route = drin_wgrad_route{};
+  t.product = p->product, t.n = p->n_products;
+  const int rc = wgrad_probe_run(p, (hipStream_t)stream);
+  t.product = nullptr, t.n = 0;
+  p->route = t.route;
   return rc;
 }
 

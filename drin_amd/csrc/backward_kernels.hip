@@ -355,11 +355,11 @@ int launch_layernorm_gelu_bwd(const float* h, const float* mean, const float* rs
 
 // ------------------------------------------------------------------------------------------------
 // out[c] += sum_rows x[row, c]      (bias gradients of W_u / W_v / the vertex encoders)
-// Workgroup (x, y) sums the rows y, y + gridDim.y, ... of 256 columns (four waves interleaved, combined through LDS in a
+// (ld: the row stride of x in floats.)  Workgroup (x, y) sums the rows y, y + gridDim.y, ... of 256 columns (four waves interleaved, combined through LDS in a
 // fixed order) and stores the sums as row y of `partial` ([gridDim.y][C]); a SliceSum launch adds the rows to out in
 // order.  partial == NULL (one workgroup per 256 columns, gridDim.y == 1): added to out in place.  No atomics.
 __device__ __forceinline__ void colsum_block(const float* __restrict__ x, float* __restrict__ out, float* __restrict__ partial,
-                                             int64_t rows, int C4, int by, float4 (*comb)[64]) {
+                                             int64_t rows, int C4, int64_t ld, int by, float4 (*comb)[64]) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int c4 = blockIdx.x * 64 + lane;
   float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -368,11 +368,11 @@ __device__ __forceinline__ void colsum_block(const float* __restrict__ x, float*
     const float* col = x + (int64_t)c4 * 4;
     int64_t row = (int64_t)blockIdx.y * 4 + wave;
     for (; row + 3 * step < rows; row += 4 * step) {  // four independent loads in flight per wave
-      const float4 v0 = ld4(col + row * (int64_t)C4 * 4), v1 = ld4(col + (row + step) * (int64_t)C4 * 4);
-      const float4 v2 = ld4(col + (row + 2 * step) * (int64_t)C4 * 4), v3 = ld4(col + (row + 3 * step) * (int64_t)C4 * 4);
+      const float4 v0 = ld4(col + row * ld), v1 = ld4(col + (row + step) * ld);
+      const float4 v2 = ld4(col + (row + 2 * step) * ld), v3 = ld4(col + (row + 3 * step) * ld);
       acc = acc + ((v0 + v1) + (v2 + v3));
     }
-    for (; row < rows; row += step) acc = acc + ld4(col + row * (int64_t)C4 * 4);
+    for (; row < rows; row += step) acc = acc + ld4(col + row * ld);
   }
   comb[wave][lane] = acc;
   __syncthreads();
@@ -389,21 +389,21 @@ __device__ __forceinline__ void colsum_block(const float* __restrict__ x, float*
 __global__ void __launch_bounds__(256) k_colsum(const float* __restrict__ x, float* __restrict__ out, float* __restrict__ partial,
                                                 int64_t rows, int C4) {
   __shared__ float4 comb[4][64];
-  colsum_block(x, out, partial, rows, C4, (int)gridDim.y, comb);
+  colsum_block(x, out, partial, rows, C4, (int64_t)C4 * 4, (int)gridDim.y, comb);
 }
 
 // up to kColsumBatchMax column sums in one launch (blockIdx.z = which): the bias gradients of one backward pass
 struct ColsumArgs {
   const float* x[kColsumBatchMax];
   float* partial[kColsumBatchMax];
-  int64_t rows[kColsumBatchMax];
+  int64_t rows[kColsumBatchMax], ld[kColsumBatchMax];
   int c4[kColsumBatchMax], by[kColsumBatchMax];
 };
 __global__ void __launch_bounds__(256) k_colsum_batch(const ColsumArgs b) {
   __shared__ float4 comb[4][64];
   const int seg = blockIdx.z;
   if ((int)blockIdx.y >= b.by[seg] || (int)blockIdx.x * 64 >= b.c4[seg]) return;   // uniform per block
-  colsum_block(b.x[seg], nullptr, b.partial[seg], b.rows[seg], b.c4[seg], b.by[seg], comb);
+  colsum_block(b.x[seg], nullptr, b.partial[seg], b.rows[seg], b.c4[seg], b.ld[seg], b.by[seg], comb);
 }
 
 static int colsum_slices(int64_t nrows) {
@@ -411,13 +411,15 @@ static int colsum_slices(int64_t nrows) {
   return (int)(want < 1 ? 1 : (want > kColsumMaxSlices ? kColsumMaxSlices : want));
 }
 
-int ColsumBatch::add(const float* src, float* dst, int64_t nrows, int C) {
+int ColsumBatch::add(const float* src, float* dst, int64_t nrows, int C, int64_t ld_src) {
   if (nrows <= 0 || !dst) return DRIN_OK;
-  if (C % 4 || n >= kColsumBatchMax) {
-    set_error("colsum: C=%d must be a multiple of 4 (and at most 8 sums per batch)", C);
+  if (ld_src == 0) ld_src = C;
+  if (C % 4 || ld_src % 4 || ld_src < C || n >= kColsumBatchMax) {
+    set_error("colsum: C=%d and the row stride %lld must be multiples of 4, the stride at least C (and at most 8 sums per batch)", C,
+              (long long)ld_src);
     return DRIN_E_SHAPE;
   }
-  x[n] = src, out[n] = dst, rows[n] = nrows, c4[n] = C / 4, by[n] = colsum_slices(nrows);
+  x[n] = src, out[n] = dst, rows[n] = nrows, ld[n] = ld_src, c4[n] = C / 4, by[n] = colsum_slices(nrows);
   ++n;
   return DRIN_OK;
 }
@@ -437,12 +439,14 @@ int launch_colsum_batch(const ColsumBatch& b, hipStream_t st, float* scratch, si
       set_error("colsum batch: %zu floats of slice scratch, %zu needed", scratch_floats, used + need);
       return DRIN_E_WORKSPACE;
     }
-    a.x[i] = b.x[i], a.partial[i] = scratch + used, a.rows[i] = b.rows[i], a.c4[i] = b.c4[i], a.by[i] = b.by[i];
+    a.x[i] = b.x[i], a.partial[i] = scratch + used, a.rows[i] = b.rows[i], a.ld[i] = b.ld[i], a.c4[i] = b.c4[i], a.by[i] = b.by[i];
     DRIN_TRY(sums.add(b.out[i], b.c4[i] * 4, 1, b.c4[i] * 4, scratch + used, b.by[i]));
     used += need;
   }
   {
     KernelTimer timer(DRIN_KC_GCN, st);
+    for (int i = 0; i < b.n; ++i) note_wgrad_colsum(b.x[i], b.out[i], b.by[i]);
+    if (drin_wgrad_route* r = wgrad_route()) r->colsum_launches += 1;
     hipLaunchKernelGGL(k_colsum_batch, dim3((unsigned)gx, (unsigned)gy, (unsigned)b.n), dim3(256), 0, st, a);
     DRIN_CHECK_LAUNCH("k_colsum_batch");
   }

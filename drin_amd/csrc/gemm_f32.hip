@@ -239,7 +239,7 @@ __global__ void __launch_bounds__(256, 2) k_gemm_f32_group(const GroupArgs g) {
 template <int BM, int BN, bool A_KMAJOR, bool B_KMAJOR>
 static int launch(const float* A, int64_t lda, const float* B, int64_t ldb, const float* bias, float* C, int64_t ldc,
                   int64_t M, int N, int K, int splits, int flags, hipStream_t st, const char* what,
-                  int64_t part_stride = 0, int* splits_used = nullptr) {
+                  int64_t part_stride = 0, int* splits_used = nullptr, int* k_per_split_used = nullptr) {
   if (M <= 0 || N <= 0) return DRIN_OK;
   const int64_t mt = cdiv(M, BM);
   if (mt > 65535) {
@@ -258,6 +258,7 @@ static int launch(const float* A, int64_t lda, const float* B, int64_t ldb, cons
     splits = 1;
   }
   if (splits_used) *splits_used = splits;
+  if (k_per_split_used) *k_per_split_used = kps;
   const size_t lds = sizeof(float) * 2 * (Tile<BM>::FLOATS + Tile<BN>::FLOATS);
   static DynLdsOptIn opt_in;  // one per template instantiation; > 64 KiB of dynamic LDS needs the opt-in
   auto kern = k_gemm_f32<BM, BN, A_KMAJOR, B_KMAJOR>;
@@ -269,6 +270,10 @@ static int launch(const float* A, int64_t lda, const float* B, int64_t ldb, cons
     n.a_lo = false, n.accumulate = (flags & GEMM_ACCUMULATE) != 0, n.splits = splits;
     n.tiles = mt * cdiv(N, BN), n.whole_tiles = n.tiles, n.work_items = n.tiles * splits;
     note_route(n);
+  } else {   // the backward forms: NN (dX) and TN (dW)
+    if (drin_wgrad_route* r = A_KMAJOR ? nullptr : wgrad_route())
+      r->nn_family = DRIN_GEMM_FAMILY_F32, r->nn_bm = BM, r->nn_bn = BN, r->nn_splits = splits;
+    note_wgrad_gemm_launch((int64_t)grid.x * grid.y * grid.z);
   }
   hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, A, lda, B, ldb, bias, C, ldc, M, N, K, kps, flags, part_stride);
   DRIN_CHECK_LAUNCH(what);
@@ -303,6 +308,7 @@ __global__ void __launch_bounds__(256) k_splitk_reduce(const float* __restrict__
 int launch_splitk_reduce(const float* partial, int splits, int64_t part_stride, const float* bias, float* y, int64_t ldy,
                          int64_t M, int N, bool accumulate, hipStream_t st) {
   KernelTimer timer(DRIN_KC_GEMM, st);
+  if (drin_wgrad_route* r = wgrad_route()) r->reduce_launches += 1;
   hipLaunchKernelGGL(k_splitk_reduce, dim3((unsigned)cdiv(M * (N / 4), 256)), dim3(256), 0, st, partial, splits, part_stride,
                      bias, y, ldy, M, N / 4, accumulate ? 1 : 0);
   DRIN_CHECK_LAUNCH("k_splitk_reduce");
@@ -374,6 +380,7 @@ int launch_slice_sum(SliceSum& s, hipStream_t st) {
     blocks += cdiv((int64_t)s.dst[i].rows * s.dst[i].c4, 256);
   }
   KernelTimer timer(DRIN_KC_GEMM, st);
+  if (drin_wgrad_route* r = wgrad_route()) r->sum_launches += 1, r->sum_dsts += s.n, r->sum_segs += s.n_seg;
   hipLaunchKernelGGL(k_slice_sum, dim3((unsigned)blocks), dim3(256), 0, st, s);
   DRIN_CHECK_LAUNCH("k_slice_sum");
   return DRIN_OK;
@@ -601,17 +608,27 @@ int launch_gemm_nn(const float* x, int64_t ldx, const float* w, int64_t ldw, flo
                    int K, bool accumulate, int precision, hipStream_t st, float* splitk, size_t splitk_floats, const WtForms& wt) {
   // y[m, n] = sum_k x[m, k] * w[k, n]: b(n, k) = w[k * ldw + n] is k-major
   if (gemm_nn_takes_bf16x3(precision, M, N, K)) {
+    // (the NT kernel notes its own route: the dX record takes it from there)
+    auto note_nn = [](int wt_form, int rc) {
+      drin_wgrad_route* r = wgrad_route();
+      if (r == nullptr || rc != DRIN_OK) return rc;   // (a launcher that failed noted nothing: gemm_route() would be another call's)
+      const drin_gemm_route& nt = gemm_route();
+      r->nn_family = nt.family, r->nn_bm = nt.bm, r->nn_bn = nt.bn, r->nn_splits = nt.splits, r->nn_accumulate = nt.accumulate, r->nn_wt_form = wt_form;
+      note_wgrad_gemm_launch(nt.work_items);
+      return rc;
+    };
     if (wt.planes != nullptr) {
       const __bf16* hi = reinterpret_cast<const __bf16*>(wt.planes);
-      return launch_gemm_nt_bf16x3(x, ldx, nullptr, K, nullptr, y, ldy, M, N, K, st, hi, hi + (size_t)N * K, accumulate, wt.tail,
-                                   wt.tail_floats);
+      return note_nn(DRIN_WGRAD_WT_PLANES, launch_gemm_nt_bf16x3(x, ldx, nullptr, K, nullptr, y, ldy, M, N, K, st, hi, hi + (size_t)N * K,
+                                                                accumulate, wt.tail, wt.tail_floats));
     }
     if (wt.scratch != nullptr && ldw == N && wt.scratch_floats >= (size_t)N * K) {
       DRIN_TRY(launch_transpose(w, wt.scratch, K, N, st));
-      return launch_gemm_nt_bf16x3(x, ldx, wt.scratch, K, nullptr, y, ldy, M, N, K, st, nullptr, nullptr, accumulate, wt.tail,
-                                   wt.tail_floats);
+      return note_nn(DRIN_WGRAD_WT_F32_SCRATCH, launch_gemm_nt_bf16x3(x, ldx, wt.scratch, K, nullptr, y, ldy, M, N, K, st, nullptr, nullptr,
+                                                                     accumulate, wt.tail, wt.tail_floats));
     }
   }
+  if (drin_wgrad_route* r = wgrad_route()) r->nn_wt_form = DRIN_WGRAD_WT_NONE, r->nn_accumulate = accumulate;
   // everything else (and split-bf16 without W^T in hand) on the exact fp32 kernel
   if (precision == DRIN_PREC_BF16X3 || precision == DRIN_PREC_BF16X3_ALL) precision = DRIN_PREC_F32;
   DRIN_TRY(check_precision(precision, "gemm_nn"));
@@ -695,6 +712,12 @@ int launch_gemm_tn_f32_group(const F32GemmGroup& grp, hipStream_t st, float* scr
   DRIN_TRY(ensure_dynamic_lds(opt_in, reinterpret_cast<const void*>(kern), (int)lds, "hipFuncSetAttribute(gemm group)"));
   {
     KernelTimer timer(DRIN_KC_GEMM, st);
+    for (int i = 0; i < grp.n; ++i) {
+      const auto& P = ga.p[i];
+      note_wgrad_product(P.a, P.b, grp.item[i].y, DRIN_WGRAD_KERNEL_TN_F32_SMALL, (int)cdiv(P.K, P.k_per_split), P.k_per_split,
+                         P.flags == GEMM_ACCUMULATE, false);
+    }
+    note_wgrad_gemm_launch(items);
     hipLaunchKernelGGL(kern, dim3(items), dim3(256), lds, st, ga);
     DRIN_CHECK_LAUNCH("k_gemm_f32_group");
   }
@@ -746,14 +769,16 @@ int launch_gemm_tn(const float* a, int64_t lda, const float* b, int64_t ldb, flo
   float* c = splits > 1 ? scratch : y;
   const int64_t ldc = splits > 1 ? K : ldy;
   const int flags = splits > 1 ? GEMM_PARTIAL : GEMM_ACCUMULATE;
-  int used = 1;
+  int used = 1, rows_per_slice = 0;
   if (small) {
     DRIN_TRY((launch<64, 64, true, true>(a, lda, b, ldb, nullptr, c, ldc, /*M=*/N, /*N=*/K, /*K=*/(int)M, splits, flags, st,
-                                         "gemm_tn", (int64_t)tile_floats, &used)));
+                                         "gemm_tn", (int64_t)tile_floats, &used, &rows_per_slice)));
   } else {
     DRIN_TRY((launch<128, 128, true, true>(a, lda, b, ldb, nullptr, c, ldc, /*M=*/N, /*N=*/K, /*K=*/(int)M, splits, flags, st,
-                                           "gemm_tn", (int64_t)tile_floats, &used)));
+                                           "gemm_tn", (int64_t)tile_floats, &used, &rows_per_slice)));
   }
+  note_wgrad_product(a, b, y, small ? DRIN_WGRAD_KERNEL_TN_F32_SMALL : DRIN_WGRAD_KERNEL_TN_F32_LARGE, used, rows_per_slice, splits == 1, false,
+                     /*launch=*/-1);
   if (splits > 1) return launch_splitk_reduce(scratch, used, (int64_t)tile_floats, nullptr, y, ldy, N, K, true, st);
   return DRIN_OK;
 }
@@ -764,7 +789,7 @@ int WeightGradPass::add(const float* dy, int64_t lddy, const float* x, int64_t l
   const TnKernel kernel = gemm_tn_kernel(prec, dy, lddy, x, ldx, dw, lddw, rows, n_out, k_red, tn.p, tn.floats);
   const bool grouped = dw != nullptr && !vec && kernel == TN_BF16X3;
   const bool db_rides = grouped && lddy == n_out;   // the group sums the columns of the rows it stages
-  if (!db_rides) DRIN_TRY(bias_sums.add(dy, db, rows, n_out));   // (no-op for db == NULL)
+  if (!db_rides) DRIN_TRY(bias_sums.add(dy, db, rows, n_out, lddy));   // (no-op for db == NULL)
   if (dw == nullptr) return DRIN_OK;
   if (grouped) {
     if (dw_group.n == TnGroup::MAX) {   // deeper than three layers: the group goes in instalments
@@ -804,7 +829,7 @@ int WeightGradPass::finish(void* layers_ready_event) {
   F32GemmGroup fg[2];
   TnGroup tg[2];
   for (int i = 0; i < bias_sums.n; ++i)
-    DRIN_TRY(cs[i >= layer_sums].add(bias_sums.x[i], bias_sums.out[i], bias_sums.rows[i], 4 * bias_sums.c4[i]));
+    DRIN_TRY(cs[i >= layer_sums].add(bias_sums.x[i], bias_sums.out[i], bias_sums.rows[i], 4 * bias_sums.c4[i], bias_sums.ld[i]));
   for (int i = 0; i < dw_small.n; ++i) fg[i >= layer_small].item[fg[i >= layer_small].n++] = dw_small.item[i];
   for (int i = 0; i < dw_group.n; ++i) tg[i >= layer_group].item[tg[i >= layer_group].n++] = dw_group.item[i];
   DRIN_TRY(part(cs[0], fg[0], tg[0], ln_sums));

@@ -381,6 +381,10 @@ int launch_gemm_tn_group(const TnGroup& grp, hipStream_t st, float* scratch, siz
   }
   {
     KernelTimer timer(DRIN_KC_GEMM_X3, st);
+    for (int i = 0; i < grp.n; ++i)
+      note_wgrad_product(grp.item[i].a, grp.item[i].b, grp.item[i].y, DRIN_WGRAD_KERNEL_TN_BF16X3, ga.p[i].slices, ga.p[i].rows_per_slice,
+                         false, grp.item[i].colsum != nullptr);
+    note_wgrad_gemm_launch(items);
     hipLaunchKernelGGL(x3tn::k_gemm_tn_bf16x3, dim3((unsigned)items), dim3(x3tn::THREADS), x3tn::LDS_BYTES, st, ga);
     DRIN_CHECK_LAUNCH("k_gemm_tn_bf16x3");
   }

@@ -181,6 +181,44 @@ inline void note_route(const RouteNote& n) {
   r.tiles = n.tiles, r.whole_tiles = n.whole_tiles, r.tile0 = n.tile0, r.work_items = n.work_items;
 }
 
+// ---- what the backward products did (drin_wgrad_probe) ----------------------------------------------
+// This thread's record of the weight-gradient, bias-gradient and dX launches, written by the dispatch code next to each launch like
+// the NT record above.  The probe names its products here while it runs; a launcher that carries one of them (the same dy, x and dw)
+// notes what it chose for it.  The record is written ONLY while the probe runs on this thread (wgrad_route() is NULL otherwise):
+// a product call stores nothing and counts nothing, so no counter grows over the life of a training process.
+struct WgradTrace {
+  drin_wgrad_route route;
+  const drin_wgrad_product* product;
+  int n;
+};
+WgradTrace& wgrad_trace();
+inline drin_wgrad_route* wgrad_route() {   // the record while drin_wgrad_probe runs on this thread, else NULL
+  WgradTrace& t = wgrad_trace();
+  return t.product != nullptr ? &t.route : nullptr;
+}
+inline void note_wgrad_product(const float* dy, const float* x, const float* dw, int kernel, int slices, int64_t rows_per_slice, bool in_place,
+                               bool db_rode, int launch = 0) {   // launch: -1 when noted after its note_wgrad_gemm_launch
+  WgradTrace& t = wgrad_trace();
+  for (int i = 0; i < t.n; ++i) {
+    const drin_wgrad_product& p = t.product[i];
+    if (p.dy != dy || p.x != x || p.dw != dw) continue;
+    drin_wgrad_product_route& r = t.route.product[i];
+    r.kernel = kernel, r.slices = slices, r.rows_per_slice = rows_per_slice, r.in_place = in_place, r.db_rode = db_rode;
+    r.launch = t.route.gemm_launches + launch;
+  }
+}
+inline void note_wgrad_gemm_launch(int64_t workgroups) {   // after the note_wgrad_product calls of the products it carries
+  drin_wgrad_route* r = wgrad_route();
+  if (r == nullptr) return;
+  if (r->gemm_launches >= 0 && r->gemm_launches < DRIN_WGRAD_ROUTE_LAUNCHES) r->grid[r->gemm_launches] = workgroups;
+  r->gemm_launches += 1;
+}
+inline void note_wgrad_colsum(const float* dy, const float* db, int row_slices) {
+  WgradTrace& t = wgrad_trace();
+  for (int i = 0; i < t.n; ++i)
+    if (t.product[i].dy == dy && t.product[i].db == db) t.route.product[i].db_slices = row_slices;
+}
+
 // ---- GEMM (gemm_f32.hip) ------------------------------------------------------------------------
 // y[m, n] (+)= sum_k x[m, k] * w[n, k] + bias[n];  x row stride ldx, w row stride ldw, y row stride ldy
 // (splitk: optional scratch; mention-sized exact-fp32 products with a long reduction (scratch_sizes.h: small_splitk_shape)
@@ -389,10 +427,12 @@ struct ColsumBatch {
   const float* x[kColsumBatchMax];
   float* out[kColsumBatchMax];
   int64_t rows[kColsumBatchMax];
+  int64_t ld[kColsumBatchMax];
   int c4[kColsumBatchMax];
   int by[kColsumBatchMax];
   int n = 0;
-  int add(const float* src, float* dst, int64_t nrows, int C);   // no-op for dst == NULL or nrows <= 0
+  // no-op for dst == NULL or nrows <= 0; ld_src: the row stride of src in floats (0: C, contiguous rows)
+  int add(const float* src, float* dst, int64_t nrows, int C, int64_t ld_src = 0);
 };
 // (scratch: sum over the entries of by * C floats <= colsum_batch_floats(C); defer as for launch_gemm_tn_group)
 int launch_colsum_batch(const ColsumBatch& b, hipStream_t st, float* scratch, size_t scratch_floats, SliceSum* defer = nullptr);

@@ -512,6 +512,86 @@ typedef struct drin_gemm_probe_args {
  * shape, a leading dimension below its row, unknown op), else whatever the launcher returns; `route` is filled either way. */
 DRIN_API int drin_gemm_probe(drin_gemm_probe_args* args, void* stream);
 
+/* drin_wgrad_probe: the same standing for the BACKWARD products - dW (+)= dY^T X, db (+)= column sums of dY, dX (+)= dY W.  It calls
+ * ONE of the module's internal launchers (or a whole WeightGradPass) on up to DRIN_WGRAD_PROBE_MAX caller-chosen products and reports
+ * what the module's dispatch code did with each (tests/test_gpu_wgrad_forms.py).  No product code calls it; nothing but
+ * `struct_size` is promised about it. */
+enum drin_wgrad_probe_op {
+  DRIN_WGRAD_TN_GROUP = 1,     /* TnGroup::add per product (db = its colsum argument), launch_gemm_tn_group */
+  DRIN_WGRAD_TN_F32_GROUP = 2, /* F32GemmGroup::add_tn per product, launch_gemm_tn_f32_group */
+  DRIN_WGRAD_TN = 3,           /* launch_gemm_tn on product[0]; precision */
+  DRIN_WGRAD_COLSUM_BATCH = 4, /* ColsumBatch::add(dy, db, rows, n_out) per product, launch_colsum_batch */
+  DRIN_WGRAD_PASS = 5,         /* a WeightGradPass (precision) whose three scratch parts are carved from `scratch` - tn_group_floats of
+                                  the largest n_out x k and n_out, colsum_batch_floats of the largest n_out, then small_tn_slices x
+                                  n_out x k per product: DRIN_E_WORKSPACE if that does not fit; add per product, layers_done() after
+                                  product[layers_done_after], finish(NULL) or, staged, finish(an event made and destroyed here) */
+  DRIN_WGRAD_NN = 6            /* launch_gemm_nn on product[0]: dw [rows][k] (+)= dy [rows][n_out] x [n_out][k]; precision, accumulate,
+                                  wt_form, wt; scratch = the split-K scratch */
+};
+enum drin_wgrad_kernel {           /* drin_wgrad_product_route.kernel */
+  DRIN_WGRAD_KERNEL_NONE = 0,      /* no GEMM kernel ran for this product */
+  DRIN_WGRAD_KERNEL_TN_BF16X3 = 1, /* k_gemm_tn_bf16x3: split-bf16, 256 x 256 tiles */
+  DRIN_WGRAD_KERNEL_TN_F32_SMALL = 2, /* exact fp32, 64 x 64 tiles (k_gemm_f32_group<true, true> / k_gemm_f32<64, 64, true, true>) */
+  DRIN_WGRAD_KERNEL_TN_F32_LARGE = 3  /* exact fp32, 128 x 128 tiles */
+};
+enum drin_wgrad_wt_form { DRIN_WGRAD_WT_NONE = 0, DRIN_WGRAD_WT_F32_SCRATCH = 1, DRIN_WGRAD_WT_PLANES = 2 };
+#define DRIN_WGRAD_PROBE_MAX 16
+#define DRIN_WGRAD_ROUTE_LAUNCHES 8
+typedef struct drin_wgrad_product {
+  const float* dy;                 /* [rows][lddy], n_out columns used (DRIN_WGRAD_NN: the activation gradient) */
+  int64_t lddy;
+  const float* x;                  /* [rows][ldx] or the table, k columns used (DRIN_WGRAD_NN: the weight [n_out][ldx]) */
+  int64_t ldx;
+  const int64_t* x_index;          /* or NULL: reduction row m of x is row x_index[m] of the table (not range-checked) */
+  float* dw;                       /* [n_out][lddw] += (DRIN_WGRAD_NN: dX [rows][lddw]); NULL where the op allows it */
+  int64_t lddw;
+  float* db;                       /* [n_out] += or NULL */
+  int64_t rows;
+  int32_t n_out, k;
+} drin_wgrad_product;
+typedef struct drin_wgrad_product_route {   /* filled by the dispatch code next to the launch that carries the product */
+  int32_t kernel;                  /* drin_wgrad_kernel */
+  int32_t slices;                  /* slices of the reduction over the rows */
+  int32_t in_place;                /* 1: added to dw by the GEMM kernel itself; 0: slices stored, added by the slice sum */
+  int32_t db_rode;                 /* 1: the column sums of dy were taken by the split-bf16 TN kernel from the rows it stages */
+  int32_t db_slices;               /* the column-sum kernel's row slices (0: no column-sum kernel ran for this product) */
+  int32_t launch;                  /* which of the call's GEMM launches carried it (0-based) */
+  int64_t rows_per_slice;
+} drin_wgrad_product_route;
+typedef struct drin_wgrad_route {
+  int32_t gemm_launches;           /* GEMM kernels launched by the call */
+  int32_t colsum_launches;         /* k_colsum_batch launches */
+  int32_t sum_launches;            /* slice-sum kernels (k_slice_sum); the split-K reduction of launch_gemm_tn is counted in reduce_launches */
+  int32_t reduce_launches;
+  int32_t sum_dsts, sum_segs;      /* destinations and segments over all slice-sum launches */
+  int32_t nn_family;               /* DRIN_WGRAD_NN: drin_gemm_family, tile, split K, W^T form taken, accumulate */
+  int32_t nn_bm, nn_bn, nn_splits, nn_wt_form, nn_accumulate;
+  int64_t grid[DRIN_WGRAD_ROUTE_LAUNCHES];   /* workgroups of each GEMM launch, in order (the first DRIN_WGRAD_ROUTE_LAUNCHES) */
+  drin_wgrad_product_route product[DRIN_WGRAD_PROBE_MAX];
+} drin_wgrad_route;
+typedef struct drin_wgrad_probe_args {
+  size_t struct_size;              /* sizeof(drin_wgrad_probe_args) */
+  int32_t op;                      /* drin_wgrad_probe_op */
+  int32_t precision;               /* drin_precision (TN, PASS, NN) */
+  int32_t staged;                  /* PASS: finish(event) instead of finish(NULL) */
+  int32_t n_products;              /* 1 .. DRIN_WGRAD_PROBE_MAX */
+  int32_t layers_done_after;       /* PASS: layers_done() after this product; < 0: never */
+  int32_t accumulate;              /* NN */
+  int32_t wt_form;                 /* NN: drin_wgrad_wt_form */
+  int32_t reserved;
+  float* scratch;                  /* or NULL */
+  size_t scratch_floats;
+  float* wt;                       /* NN with a wt_form: n_out x k floats of caller memory for W^T (fp32, or its bf16 hi / lo planes,
+                                      written here by launch_transpose_split_batch before the product) */
+  size_t wt_floats;
+  drin_wgrad_product product[DRIN_WGRAD_PROBE_MAX];
+  drin_wgrad_route route;          /* out (host memory, like the struct itself) */
+} drin_wgrad_probe_args;
+/* DRIN_E_NULL / DRIN_E_SHAPE / DRIN_E_UNSUPPORTED from the host checks (NULL struct or operand, struct_size, negative shape, a leading
+ * dimension below its row, more than DRIN_WGRAD_PROBE_MAX products, unknown op), else what the launcher returns; `route` is filled either way - zeroed by a refused call - except under
+ * another `struct_size`, where the struct is of an unknown layout and nothing in it is written. */
+DRIN_API int drin_wgrad_probe(drin_wgrad_probe_args* args, void* stream);
+
 /* ---- caller-side loss and metric of one batch --------------------------------- *
  * Replaces, for scores already on the device, `TripletLoss.forward` (common/utils.py:26-43, called at
  * train.py:34) and `TopkAccuracy.update` (utils.py:60-66, train.py:36-37), and the autograd backward of

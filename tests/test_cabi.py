@@ -135,7 +135,9 @@ def test_ctypes_mirrors_match_the_header_layout(tmp_path):
     (size and the offset of every field): the binding a maintainer writes from the header alone stays in step."""
     pairs = [("drin_config", _lib.DrinConfigC), ("drin_batch", _lib.DrinBatchC), ("drin_layer_params", _lib.DrinLayerParamsC),
              ("drin_params", _lib.DrinParamsC), ("drin_param_grads", _lib.DrinParamGradsC), ("drin_trace", _lib.DrinTraceC),
-             ("drin_gemm_route", _lib.DrinGemmRouteC), ("drin_gemm_probe_args", _lib.DrinGemmProbeArgsC)]
+             ("drin_gemm_route", _lib.DrinGemmRouteC), ("drin_gemm_probe_args", _lib.DrinGemmProbeArgsC),
+             ("drin_wgrad_product", _lib.DrinWgradProductC), ("drin_wgrad_product_route", _lib.DrinWgradProductRouteC),
+             ("drin_wgrad_route", _lib.DrinWgradRouteC), ("drin_wgrad_probe_args", _lib.DrinWgradProbeArgsC)]
     lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{HEADER}"', 'int main(void) {']
     for cname, cls in pairs:
         lines.append(f'  printf("{cname} %zu\\n", sizeof({cname}));')
@@ -248,6 +250,58 @@ def test_gemm_probe_validates_on_host():
     assert call(op=_lib.PROBE_GEMM_F16_PLANES) == _lib.E_NULL             # no scales
     assert call(op=_lib.PROBE_TO_F16_SCALED, scratch=16, scratch_floats=1) == _lib.E_SHAPE and b"two floats" in lib.drin_last_error()
     assert call(op=_lib.PROBE_TO_F16_SCALED, scratch=16, scratch_floats=2, rows=-4) == _lib.E_SHAPE
+    assert lib.drin_version() == _lib.ABI_VERSION == 12                   # an additive export
+
+
+def wgrad_args(n=2, **kw):
+    one = 16   # never dereferenced
+    a = _lib.DrinWgradProbeArgsC(struct_size=C.sizeof(_lib.DrinWgradProbeArgsC), op=_lib.WGRAD_TN_GROUP, n_products=n, layers_done_after=-1)
+    for i in range(min(max(n, 0), _lib.WGRAD_PROBE_MAX)):
+        a.product[i] = _lib.DrinWgradProductC(dy=one, lddy=132, x=one, ldx=264, dw=one, lddw=264, rows=1055, n_out=132, k=260)
+    product = {k[2:]: kw.pop(k) for k in list(kw) if k.startswith("p_")}
+    for name, value in kw.items():
+        setattr(a, name, value)
+    for name, value in product.items():
+        setattr(a.product[1], name, value)
+    return a
+
+
+def test_wgrad_probe_validates_on_host():
+    """drin_wgrad_probe (the test entry into the backward products): NULL struct or operand, struct_size, negative shapes, leading
+    dimensions below their rows, more than 16 products and an unknown op are refused on the host, before a launch and before the
+    runtime is asked about any pointer; the route record of a refused call says that nothing ran.  (The same checks as a stand-alone
+    program under ASan / UBSan: test_wgrad_probe_host.py.)"""
+    lib = _lib.load()
+    assert lib.drin_wgrad_probe(None, None) == _lib.E_NULL and b"NULL" in lib.drin_last_error()
+
+    def call(**kw):
+        a = wgrad_args(**kw)
+        a.route.gemm_launches, a.route.product[15].kernel = 7, 7
+        rc = lib.drin_wgrad_probe(C.byref(a), None)
+        if a.struct_size == C.sizeof(_lib.DrinWgradProbeArgsC):
+            assert (a.route.gemm_launches, a.route.product[15].kernel) == (0, 0)
+        else:
+            assert (a.route.gemm_launches, a.route.product[15].kernel) == (7, 7)   # a struct of another layout is not written to
+        return rc
+
+    assert call(struct_size=C.sizeof(_lib.DrinWgradProbeArgsC) - 8) == _lib.E_SHAPE and b"struct_size" in lib.drin_last_error()
+    assert call(struct_size=0) == _lib.E_SHAPE
+    assert call(op=0) == _lib.E_UNSUPPORTED and call(op=7) == _lib.E_UNSUPPORTED and b"unknown op 7" in lib.drin_last_error()
+    assert call(n=17) == _lib.E_SHAPE and b"17 products" in lib.drin_last_error()
+    assert call(n=0) == _lib.E_SHAPE and call(n=-1) == _lib.E_SHAPE
+    assert call(p_dy=None) == _lib.E_NULL and b"product 1" in lib.drin_last_error()
+    assert call(p_x=None) == _lib.E_NULL and call(p_dw=None) == _lib.E_NULL
+    assert call(op=_lib.WGRAD_COLSUM_BATCH) == _lib.E_NULL                # no db
+    assert call(scratch_floats=64) == _lib.E_NULL and b"scratch" in lib.drin_last_error()
+    assert call(p_rows=-1) == _lib.E_SHAPE and b"rows=-1" in lib.drin_last_error()
+    assert call(p_n_out=0) == _lib.E_SHAPE and call(p_k=-4) == _lib.E_SHAPE
+    assert call(p_lddy=131) == _lib.E_SHAPE and b"lddy=131" in lib.drin_last_error()
+    assert call(p_ldx=259) == _lib.E_SHAPE and call(p_lddw=-264) == _lib.E_SHAPE
+    assert call(op=_lib.WGRAD_TN) == _lib.E_SHAPE and b"one product" in lib.drin_last_error()
+    assert call(op=_lib.WGRAD_NN, n=1, wt_form=3) == _lib.E_UNSUPPORTED
+    assert call(op=_lib.WGRAD_NN, n=1, wt_form=_lib.WGRAD_WT_PLANES) == _lib.E_NULL
+    assert call(op=_lib.WGRAD_TN_F32_GROUP, p_x_index=16) == _lib.E_UNSUPPORTED and b"indexed" in lib.drin_last_error()
+    assert call(op=_lib.WGRAD_PASS, layers_done_after=2) == _lib.E_SHAPE
     assert lib.drin_version() == _lib.ABI_VERSION == 12                   # an additive export
 
 

@@ -19,6 +19,7 @@ ABI_VERSION = 12
 
 OK, E_SHAPE, E_NULL, E_ALIGN, E_WORKSPACE, E_HIP, E_UNSUPPORTED, E_INDEX = 0, -1, -2, -3, -4, -5, -6, -7
 PREC_F32, PREC_BF16X3, PREC_BF16X3_ALL, PREC_BF16X3_IF16 = 0, 1, 3, 5     # (2 and 4: removed with ABI 6 - outside the 1e-4 bar)
+ROW_ACT = {"none": 0, "relu": 1, "gelu": 2}                               # drin_row_activation (drin_act_dropout_*)
 FEAT_F32, FEAT_BF16 = 0, 1
 CACHE_F32, CACHE_MIXED_F16 = 0, 1                                      # drin_cache_format
 CACHE_FORMATS = {"f32": CACHE_F32, "mixed_f16": CACHE_MIXED_F16}
@@ -267,6 +268,12 @@ EXPORTS = {
     "drin_cosine_rows_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32,
                                        C.c_int32, C.c_int32, C.c_float, C.c_void_p]),
     "drin_entity_token_mean": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
+    "drin_act_dropout_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_uint64, C.c_uint64,
+                                       C.c_void_p]),
+    "drin_act_dropout_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_uint64,
+                                       C.c_uint64, C.c_void_p]),
+    "drin_span_mean_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "drin_span_mean_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "drin_profile_begin": (C.c_int, [C.c_int]),
     "drin_profile_end": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "drin_kernel_class_name": (C.c_char_p, [C.c_int]),

@@ -78,6 +78,10 @@ class DropoutStream:
         del self.log[:-self.LOG_LENGTH]
         return call
 
+    def draw_rows(self, rows: int, width: int) -> int:
+        """The draw of a row dropout (`row_ops.act_dropout`) over [rows, width]: the mask of geometry (rows, 1, 1, width)."""
+        return self.draw(rows, 1, 1, width)
+
 
 def dropout_keep(seed: int, call: int, B: int, H: int, Lq: int, Lk: int, p: float) -> torch.Tensor:
     """The keep mask of one draw, bool [B, H, Lq, Lk] on the CPU, from the library's host function (no GPU)."""
@@ -243,6 +247,62 @@ def _linear(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], precisi
     return _LinearFunction.apply(x.contiguous(), w.contiguous(), None if b is None else b.contiguous(), precision)
 
 
+def multihead_attention_forward(query, key, value, key_padding_mask=None, *, embed_dim, num_heads, kdim, vdim, in_proj_weight,
+                                q_proj_weight, k_proj_weight, v_proj_weight, in_proj_bias, out_proj_weight, out_proj_bias, precision,
+                                dropout=0.0, dropout_stream=None) -> torch.Tensor:
+    """`MultiheadAttention.forward` on parameter tensors, wherever they live (the module's own, or torch's
+    `nn.TransformerEncoderLayer.self_attn`): out [B, Lq, E].  `in_proj_weight` is None when the three widths differ (then
+    `q_proj_weight`, `k_proj_weight`, `v_proj_weight` are read).  `dropout` is the rate that applies to this call (0 outside
+    training); a rate > 0 takes one draw from `dropout_stream`."""
+    _require_gpu_f32("the module (out_proj.weight)", out_proj_weight)
+    for name, t in (("query", query), ("key", key), ("value", value)):
+        _require_gpu_f32(name, t)
+        if t.dim() != 3:
+            raise RuntimeError(f"drin_amd.attention.MultiheadAttention: {name} must be [batch, length, width], got {tuple(t.shape)}")
+    B, Lq, E = query.shape
+    Lk = key.shape[1]
+    if E != embed_dim or key.shape[2] != kdim or value.shape[2] != vdim or key.shape[0] != B or (
+            tuple(value.shape[:2]) != (B, Lk)):
+        raise RuntimeError(f"drin_amd.attention.MultiheadAttention: query {tuple(query.shape)}, key {tuple(key.shape)}, value "
+                           f"{tuple(value.shape)} do not fit embed_dim={embed_dim}, kdim={kdim}, vdim={vdim}")
+    if Lk > MAX_KEYS:
+        raise NotImplementedError(f"drin_amd.attention.MultiheadAttention: {Lk} keys exceed {MAX_KEYS}")
+    mask = None
+    if key_padding_mask is not None:           # torch: bool, True = drop (a float mask is additive: not implemented)
+        if key_padding_mask.dtype != torch.bool:
+            raise NotImplementedError("drin_amd.attention.MultiheadAttention: key_padding_mask must be bool (True = drop)")
+        if tuple(key_padding_mask.shape) != (B, Lk):
+            raise RuntimeError(f"key_padding_mask {tuple(key_padding_mask.shape)} is not [batch, k_len] = {(B, Lk)}")
+        mask = (~key_padding_mask).to(query.device, torch.int64)
+    drop = None
+    if dropout > 0:
+        if not 0.0 < dropout < 1.0:
+            raise ValueError(f"drin_amd.attention.MultiheadAttention: dropout {dropout} is not in [0, 1)")
+        stream = dropout_stream
+        drop = (float(dropout), stream.seed, stream.draw(B, num_heads, Lq, Lk))
+    prec = PRECISIONS[precision]
+    bias = in_proj_bias
+    bq, bk, bv = (None, None, None) if bias is None else (bias[:E], bias[E:2 * E], bias[2 * E:])
+    xq = query.reshape(B * Lq, E)
+    if in_proj_weight is not None:
+        w = in_proj_weight
+        q = _linear(xq, w[:E], bq, prec).view(B, Lq, E)
+        if key is value:                       # K | V: one product, one [rows, 2 E] buffer, one backward
+            kv = _linear(key.reshape(B * Lk, E), w[E:], None if bias is None else bias[E:], prec)
+            ctx = attention_core_packed(q, kv.view(B, Lk, 2 * E), mask, num_heads, drop)
+        else:
+            k = _linear(key.reshape(B * Lk, E), w[E:2 * E], bk, prec).view(B, Lk, E)
+            v = _linear(value.reshape(B * Lk, E), w[2 * E:], bv, prec).view(B, Lk, E)
+            ctx = attention_core(q, k, v, mask, num_heads, drop)
+    else:
+        q = _linear(xq, q_proj_weight, bq, prec).view(B, Lq, E)
+        k = _linear(key.reshape(B * Lk, kdim), k_proj_weight, bk, prec).view(B, Lk, E)
+        v = _linear(value.reshape(B * Lk, vdim), v_proj_weight, bv, prec).view(B, Lk, E)
+        ctx = attention_core(q, k, v, mask, num_heads, drop)
+    out = _linear(ctx.view(B * Lq, E), out_proj_weight, out_proj_bias, prec)
+    return out.view(B, Lq, E)
+
+
 # ---- the module ---------------------------------------------------------------------------------------------
 class MultiheadAttention(nn.MultiheadAttention):
     """`nn.MultiheadAttention(..., batch_first=True)` on the HIP library, forward and backward.  The constructor takes
@@ -292,50 +352,9 @@ class MultiheadAttention(nn.MultiheadAttention):
         if self.training and self.dropout > 0 and self.dropout_stream is None:
             raise NotImplementedError(f"drin_amd.attention.MultiheadAttention: attention dropout ({self.dropout}) in training mode is "
                                       "not implemented (DESIGN.md section 11); call eval() or build the module with dropout=0")
-        _require_gpu_f32("the module (out_proj.weight)", self.out_proj.weight)
-        for name, t in (("query", query), ("key", key), ("value", value)):
-            _require_gpu_f32(name, t)
-            if t.dim() != 3:
-                raise RuntimeError(f"drin_amd.attention.MultiheadAttention: {name} must be [batch, length, width], got {tuple(t.shape)}")
-        B, Lq, E = query.shape
-        Lk = key.shape[1]
-        if E != self.embed_dim or key.shape[2] != self.kdim or value.shape[2] != self.vdim or key.shape[0] != B or (
-                tuple(value.shape[:2]) != (B, Lk)):
-            raise RuntimeError(f"drin_amd.attention.MultiheadAttention: query {tuple(query.shape)}, key {tuple(key.shape)}, value "
-                               f"{tuple(value.shape)} do not fit embed_dim={self.embed_dim}, kdim={self.kdim}, vdim={self.vdim}")
-        if Lk > MAX_KEYS:
-            raise NotImplementedError(f"drin_amd.attention.MultiheadAttention: {Lk} keys exceed {MAX_KEYS}")
-        mask = None
-        if key_padding_mask is not None:           # torch: bool, True = drop (a float mask is additive: not implemented)
-            if key_padding_mask.dtype != torch.bool:
-                raise NotImplementedError("drin_amd.attention.MultiheadAttention: key_padding_mask must be bool (True = drop)")
-            if tuple(key_padding_mask.shape) != (B, Lk):
-                raise RuntimeError(f"key_padding_mask {tuple(key_padding_mask.shape)} is not [batch, k_len] = {(B, Lk)}")
-            mask = (~key_padding_mask).to(query.device, torch.int64)
-        drop = None
-        if self.training and self.dropout > 0:
-            if not 0.0 < self.dropout < 1.0:
-                raise ValueError(f"drin_amd.attention.MultiheadAttention: dropout {self.dropout} is not in [0, 1)")
-            stream = self.dropout_stream
-            drop = (float(self.dropout), stream.seed, stream.draw(B, self.num_heads, Lq, Lk))
-        prec = PRECISIONS[self.precision]
-        bias = self.in_proj_bias
-        bq, bk, bv = (None, None, None) if bias is None else (bias[:E], bias[E:2 * E], bias[2 * E:])
-        xq = query.reshape(B * Lq, E)
-        if self._qkv_same_embed_dim:
-            w = self.in_proj_weight
-            q = _linear(xq, w[:E], bq, prec).view(B, Lq, E)
-            if key is value:                       # K | V: one product, one [rows, 2 E] buffer, one backward
-                kv = _linear(key.reshape(B * Lk, E), w[E:], None if bias is None else bias[E:], prec)
-                ctx = attention_core_packed(q, kv.view(B, Lk, 2 * E), mask, self.num_heads, drop)
-            else:
-                k = _linear(key.reshape(B * Lk, E), w[E:2 * E], bk, prec).view(B, Lk, E)
-                v = _linear(value.reshape(B * Lk, E), w[2 * E:], bv, prec).view(B, Lk, E)
-                ctx = attention_core(q, k, v, mask, self.num_heads, drop)
-        else:
-            q = _linear(xq, self.q_proj_weight, bq, prec).view(B, Lq, E)
-            k = _linear(key.reshape(B * Lk, self.kdim), self.k_proj_weight, bk, prec).view(B, Lk, E)
-            v = _linear(value.reshape(B * Lk, self.vdim), self.v_proj_weight, bv, prec).view(B, Lk, E)
-            ctx = attention_core(q, k, v, mask, self.num_heads, drop)
-        out = _linear(ctx.view(B * Lq, E), self.out_proj.weight, self.out_proj.bias, prec)
-        return out.view(B, Lq, E), None
+        return multihead_attention_forward(
+            query, key, value, key_padding_mask, embed_dim=self.embed_dim, num_heads=self.num_heads, kdim=self.kdim, vdim=self.vdim,
+            in_proj_weight=self.in_proj_weight, q_proj_weight=self.q_proj_weight, k_proj_weight=self.k_proj_weight,
+            v_proj_weight=self.v_proj_weight, in_proj_bias=self.in_proj_bias, out_proj_weight=self.out_proj.weight,
+            out_proj_bias=self.out_proj.bias, precision=self.precision, dropout=self.dropout if self.training else 0.0,
+            dropout_stream=self.dropout_stream), None

@@ -704,6 +704,57 @@ __global__ void __launch_bounds__(256) k_gate_mix_bwd_sums(const float* __restri
     dbs[0] = s, dbs[1] = -s;
 }
 
+// ---- y = act(x) m / (1 - p): the FFN activation and the dropouts of nn.TransformerEncoderLayer (ghmfc.py:75-86) -----------
+// Element-wise over [rows, width] contiguous floats, width % 4 == 0: thread = one float4, i.e. the elements 4 i .. 4 i + 3 of
+// the flat index e = row * width + col - exactly one Philox evaluation of dropout_mask.h, whose mask this is with the
+// geometry (B, H, Lq, Lk) = (rows, 1, 1, width).  A dropped element is exactly 0 (a select, not a product: a dropped NaN
+// goes too); DROP = false has no generator code.  relu and relu' are torch's (a NaN passes; relu'(0) = 0); gelu and gelu'
+// are the gate's expressions.  y may be x and dx may be dy (no __restrict__ on them).  At most kActBlocks workgroups, the
+// rest by grid stride.
+constexpr int kActNone = DRIN_ROW_ACT_NONE, kActRelu = DRIN_ROW_ACT_RELU, kActGelu = DRIN_ROW_ACT_GELU;
+constexpr int kActBlocks = 2048;
+template <int ACT>
+__device__ __forceinline__ float row_act(float x) {
+  if constexpr (ACT == kActRelu) return x <= 0.f ? 0.f : x;
+  if constexpr (ACT == kActGelu) return gelu_erf(x);
+  return x;
+}
+// g act'(x)
+template <int ACT>
+__device__ __forceinline__ float row_act_bwd(float x, float g) {
+  if constexpr (ACT == kActRelu) return x <= 0.f ? 0.f : g;
+  if constexpr (ACT == kActGelu) return g * gelu_erf_grad_exact(x);
+  return g;
+}
+__device__ __forceinline__ float4 drop4(float4 v, int64_t quad, const DropArgs& d) {
+  const Philox4 r = philox4x32_10(d.seed, d.call, (uint64_t)quad);
+  return make_float4(r.w[0] >= d.threshold ? v.x * d.scale : 0.f, r.w[1] >= d.threshold ? v.y * d.scale : 0.f,
+                     r.w[2] >= d.threshold ? v.z * d.scale : 0.f, r.w[3] >= d.threshold ? v.w * d.scale : 0.f);
+}
+template <int ACT, bool DROP>
+__global__ void __launch_bounds__(256) k_act_dropout(const float* x, float* y, int64_t n4, DropArgs drop) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+    const float4 a = ld4(x + i * 4);
+    float4 v = make_float4(row_act<ACT>(a.x), row_act<ACT>(a.y), row_act<ACT>(a.z), row_act<ACT>(a.w));
+    if constexpr (DROP) v = drop4(v, i, drop);
+    st4(y + i * 4, v);
+  }
+}
+// dx = dy act'(x) m / (1 - p), act' recomputed from x; ACT = none never reads x (which may be NULL): the forward's bits
+template <int ACT, bool DROP>
+__global__ void __launch_bounds__(256) k_act_dropout_bwd(const float* __restrict__ x, const float* dy, float* dx, int64_t n4,
+                                                         DropArgs drop) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+    float4 v = ld4(dy + i * 4);
+    if constexpr (ACT != kActNone) {
+      const float4 a = ld4(x + i * 4);
+      v = make_float4(row_act_bwd<ACT>(a.x, v.x), row_act_bwd<ACT>(a.y, v.y), row_act_bwd<ACT>(a.z, v.z), row_act_bwd<ACT>(a.w, v.w));
+    }
+    if constexpr (DROP) v = drop4(v, i, drop);
+    st4(dx + i * 4, v);
+  }
+}
+
 template <typename F>
 int timed(int cls, hipStream_t st, const char* what, F&& launch) {
   KernelTimer timer(cls, st);
@@ -888,6 +939,39 @@ int launch_gate_mix(const float* tl, const float* vl, const float* ws, const flo
   return timed(DRIN_KC_NORM, st, "k_gate_mix", [&] {
     hipLaunchKernelGGL(k_gate_mix, dim3((unsigned)cdiv(B, 4)), dim3(256), 0, st, tl, vl, ws, bs, out, B, D / 4);
   });
+}
+
+// KERNEL<act, DROP> of the three activations; n4 float4s, at most kActBlocks workgroups
+#define DRIN_ACT_DISPATCH(KERNEL, act, dropped, ...)                         \
+  do {                                                                       \
+    if ((act) == kActGelu) {                                                 \
+      if (dropped)                                                           \
+        hipLaunchKernelGGL((KERNEL<kActGelu, true>), __VA_ARGS__);           \
+      else                                                                   \
+        hipLaunchKernelGGL((KERNEL<kActGelu, false>), __VA_ARGS__);          \
+    } else if ((act) == kActRelu) {                                          \
+      if (dropped)                                                           \
+        hipLaunchKernelGGL((KERNEL<kActRelu, true>), __VA_ARGS__);           \
+      else                                                                   \
+        hipLaunchKernelGGL((KERNEL<kActRelu, false>), __VA_ARGS__);          \
+    } else {                                                                 \
+      if (dropped)                                                           \
+        hipLaunchKernelGGL((KERNEL<kActNone, true>), __VA_ARGS__);           \
+      else                                                                   \
+        hipLaunchKernelGGL((KERNEL<kActNone, false>), __VA_ARGS__);          \
+    }                                                                        \
+  } while (0)
+dim3 act_grid(int64_t n4) { return dim3((unsigned)(cdiv(n4, 256) < kActBlocks ? cdiv(n4, 256) : kActBlocks)); }
+
+int launch_act_dropout(const float* x, float* y, int64_t n4, int act, const DropArgs* drop, hipStream_t st) {
+  const DropArgs da = drop ? *drop : DropArgs{};
+  return timed(DRIN_KC_NORM, st, "k_act_dropout",
+               [&] { DRIN_ACT_DISPATCH(k_act_dropout, act, drop != nullptr, act_grid(n4), dim3(256), 0, st, x, y, n4, da); });
+}
+int launch_act_dropout_bwd(const float* x, const float* dy, float* dx, int64_t n4, int act, const DropArgs* drop, hipStream_t st) {
+  const DropArgs da = drop ? *drop : DropArgs{};
+  return timed(DRIN_KC_NORM, st, "k_act_dropout_bwd",
+               [&] { DRIN_ACT_DISPATCH(k_act_dropout_bwd, act, drop != nullptr, act_grid(n4), dim3(256), 0, st, x, dy, dx, n4, da); });
 }
 
 // ---- the forward pass ------------------------------------------------------------------------------------
@@ -1319,6 +1403,70 @@ int drin_entity_token_mean(const float* feat, const int64_t* mask, float* out, i
   DRIN_TRY(check_count(who, "tokens", tokens, 1, INT32_MAX));
   DRIN_BIND_DEVICE(stream, out, who);
   return launch_entity_token_mean(feat, mask, out, pairs, tokens, width, (hipStream_t)stream);
+}
+
+// ---- the FFN activation, row dropout and the span mean of GHMFC's other mention encoders ------------
+namespace {
+int act_dropout_args(const char* who, int64_t rows, int32_t width, int32_t act, float p, uint64_t seed, uint64_t call, DropArgs* drop,
+                     bool* use) {
+  DRIN_TRY(check_width4(who, width));
+  DRIN_TRY(check_count(who, "rows", rows, 1, INT64_MAX / 4096 / width));
+  if (act != DRIN_ROW_ACT_NONE && act != DRIN_ROW_ACT_RELU && act != DRIN_ROW_ACT_GELU) {
+    set_error("%s: act = %d is none of DRIN_ROW_ACT_NONE / _RELU / _GELU (%d, %d, %d)", who, act, DRIN_ROW_ACT_NONE, DRIN_ROW_ACT_RELU,
+              DRIN_ROW_ACT_GELU);
+    return DRIN_E_SHAPE;
+  }
+  return dropout_args(who, p, seed, call, drop, use);
+}
+int span_args(const char* who, const int64_t* start, const int64_t* end, int32_t batch, int32_t seq_len, int32_t width) {
+  if (!start || !end) {
+    set_error("%s: start / end is NULL", who);
+    return DRIN_E_NULL;
+  }
+  DRIN_TRY(check_width4(who, width));
+  DRIN_TRY(check_count(who, "batch", batch, 1, INT32_MAX));
+  return check_count(who, "seq_len", seq_len, 1, INT32_MAX);
+}
+}  // namespace
+
+int drin_act_dropout_fwd(const float* x, float* y, int64_t rows, int32_t width, int32_t act, float p, uint64_t seed, uint64_t call,
+                         void* stream) {
+  const char* who = "drin_act_dropout_fwd";
+  DRIN_CHECK_POINTERS(who, {"x", x, true}, {"y", y, true});
+  DropArgs drop;
+  bool use;
+  DRIN_TRY(act_dropout_args(who, rows, width, act, p, seed, call, &drop, &use));
+  DRIN_BIND_DEVICE(stream, y, who);
+  return launch_act_dropout(x, y, rows * (width / 4), act, use ? &drop : nullptr, (hipStream_t)stream);
+}
+
+int drin_act_dropout_bwd(const float* x, const float* dy, float* dx, int64_t rows, int32_t width, int32_t act, float p, uint64_t seed,
+                         uint64_t call, void* stream) {
+  const char* who = "drin_act_dropout_bwd";
+  DRIN_CHECK_POINTERS(who, {"x", x, act != DRIN_ROW_ACT_NONE}, {"dy", dy, true}, {"dx", dx, true});
+  DropArgs drop;
+  bool use;
+  DRIN_TRY(act_dropout_args(who, rows, width, act, p, seed, call, &drop, &use));
+  DRIN_BIND_DEVICE(stream, dx, who);
+  return launch_act_dropout_bwd(x, dy, dx, rows * (width / 4), act, use ? &drop : nullptr, (hipStream_t)stream);
+}
+
+int drin_span_mean_fwd(const float* seq, const int64_t* start, const int64_t* end, float* out, int32_t batch, int32_t seq_len,
+                       int32_t width, void* stream) {
+  const char* who = "drin_span_mean_fwd";
+  DRIN_CHECK_POINTERS(who, {"seq", seq, true}, {"out", out, true});
+  DRIN_TRY(span_args(who, start, end, batch, seq_len, width));
+  DRIN_BIND_DEVICE(stream, out, who);
+  return launch_span_mean(seq, start, end, out, batch, seq_len, width, (hipStream_t)stream);
+}
+
+int drin_span_mean_bwd(const float* dout, const int64_t* start, const int64_t* end, float* dseq, int32_t batch, int32_t seq_len,
+                       int32_t width, void* stream) {
+  const char* who = "drin_span_mean_bwd";
+  DRIN_CHECK_POINTERS(who, {"dout", dout, true}, {"dseq", dseq, true});
+  DRIN_TRY(span_args(who, start, end, batch, seq_len, width));
+  DRIN_BIND_DEVICE(stream, dseq, who);
+  return launch_span_mean_bwd(dout, start, end, dseq, batch, seq_len, width, (hipStream_t)stream);
 }
 
 size_t drin_ghmfc_workspace_bytes(const drin_ghmfc_config* cfg) {

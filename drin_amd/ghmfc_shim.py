@@ -21,6 +21,7 @@ from torch.utils.data import DataLoader, Dataset
 
 from .ghmfc import config_from_reference_args
 from .ghmfc_train import TrainableModel as _Model
+from .ghmfc_variants import VariantModel, variant_config_from_reference_args
 from .melhi_shim import SPLITS
 
 
@@ -30,7 +31,17 @@ def _args():
 
 class Model(_Model):
     """`model_module.Model()`: geometry and `transformer_dropout` from `common.args`; split-bf16 products unless
-    DRIN_PRECISION=f32.  The attention dropout of train() mode is the library's own mask, seeded by `args.seed`."""
+    DRIN_PRECISION=f32.  The attention dropout of train() mode is the library's own mask, seeded by `args.seed`.  With another
+    mention encoder selected in `common.args` (`mention_final_layer_name`, `mention_multimodal_attention`: "transformer",
+    "multimodal" + "text", "linear", "none") `Model()` is a `drin_amd.ghmfc_variants.VariantModel` built the same way."""
+
+    def __new__(cls):
+        a = _args()
+        cfg = variant_config_from_reference_args(a)
+        if cfg.is_default:
+            return super().__new__(cls)
+        return VariantModel(cfg, precision=os.environ.get("DRIN_PRECISION", "bf16x3"), dropout=getattr(a, "transformer_dropout", 0.1),
+                            seed=getattr(a, "seed", 0))
 
     def __init__(self):
         a = _args()
@@ -41,10 +52,12 @@ class Model(_Model):
 class GhmfcData(Dataset):
     """One split of the offline features (`baselines/data.py:85-122,169-192`): (mention_feature, mention_mask, start + 1,
     end + 1, mention_image, entity_feature, entity_mask, 0, answer one-hot) per mention.  WikiDiverse: entity_feature [N, D]
-    and entity_mask 0; WikiMEL: entity rows gathered from the shared table through `qid2idx.json`, [N, T, D] and [N, T]."""
+    and entity_mask 0; WikiMEL: entity rows gathered from the shared table through `qid2idx.json`, [N, T, D] and [N, T].
+    `mention_image=False` (a mention encoder other than "multimodal", `baselines/data.py:113,130`): the image file is not
+    opened and the item is 0."""
 
     def __init__(self, root: str, split: str, dataset_name: str, num_candidates: int, embed_dim: int, entity_text_type: str = "attr",
-                 mention_mmap=None):
+                 mention_mmap=None, mention_image: bool = True):
         p = lambda name: os.path.join(root, name)   # noqa: E731
         self.wikimel = dataset_name == "wikimel"
         self.mention_feature = np.load(p(f"mention-text-feature_{split}.npy"), mmap_mode=mention_mmap)
@@ -60,7 +73,7 @@ class GhmfcData(Dataset):
         self.start = np.load(p(f"start-pos_{split}.npy"))
         self.end = np.load(p(f"end-pos_{split}.npy"))
         self.answer = np.load(p(f"answer_{split}.npy"))
-        self.mention_image = np.load(p(f"mention-image-feature_{split}.npy"), mmap_mode=mention_mmap)
+        self.mention_image = np.load(p(f"mention-image-feature_{split}.npy"), mmap_mode=mention_mmap) if mention_image else None
         n = num_candidates - 1
         self.lookup = torch.cat([torch.eye(n, dtype=torch.int8), torch.zeros(1, n, dtype=torch.int8)])
 
@@ -75,18 +88,21 @@ class GhmfcData(Dataset):
         else:
             entity_feature, entity_mask = torch.from_numpy(self.entity_feature[i].copy()), 0
         return (torch.from_numpy(self.mention_feature[i].copy()), torch.from_numpy(np.asarray(self.mention_mask[i])),
-                int(self.start[i]) + 1, int(self.end[i]) + 1, torch.from_numpy(np.asarray(self.mention_image[i]).copy()),
+                int(self.start[i]) + 1, int(self.end[i]) + 1,
+                0 if self.mention_image is None else torch.from_numpy(np.asarray(self.mention_image[i]).copy()),
                 entity_feature, entity_mask, 0, self.lookup[int(self.answer[i])])
 
 
 def create_datasets() -> List[DataLoader]:
     """`data_module.create_datasets()` for GHMFC: loaders over `args.preprocess_dir` with `args.batch_size`."""
     a = _args()
-    cfg = config_from_reference_args(a)
+    cfg = variant_config_from_reference_args(a)
+    if cfg.is_default:
+        config_from_reference_args(a)                                          # the default's own refusals
     loaders = []
     for split in SPLITS:
         ds = GhmfcData(a.preprocess_dir, split, cfg.dataset_name, cfg.num_candidates, cfg.embed_dim,
-                       getattr(a, "entity_text_type", "attr"), getattr(a, "mention_mmap", None))
+                       getattr(a, "entity_text_type", "attr"), getattr(a, "mention_mmap", None), cfg.reads_mention_image)
         loaders.append(DataLoader(ds, a.batch_size, shuffle=(split == "train" and getattr(a, "shuffle_train_data", True)),
                                   num_workers=getattr(a, "dataloader_workers", 0)))
     return loaders

@@ -1,7 +1,9 @@
 """GHMFC's row operations as differentiable functions on the HIP library: LayerNorm with a fused residual, the max over a
 sequence, the gate, the cosine against the candidates and the entity token mean - one `torch.autograd.Function` per pair of
 entry points (`drin_layernorm_res_train_fwd` / `_bwd`, `drin_seq_max_train_fwd` / `_bwd`, `drin_gate_mix_fwd` / `_bwd`,
-`drin_cosine_rows_fwd` / `_bwd`, `drin_entity_token_mean`).  What the kernels compute: DESIGN.md section 18.
+`drin_cosine_rows_fwd` / `_bwd`, `drin_entity_token_mean`).  What the kernels compute: DESIGN.md section 18.  For GHMFC's other
+mention encoders (section 20): the FFN activation with row dropout (`drin_act_dropout_fwd` / `_bwd`) and the mean over the
+mention span (`drin_span_mean_fwd` / `_bwd`).
 
 GPU only, float32, contiguous rows; there is no CPU fallback and no torch math inside.
 """
@@ -175,6 +177,70 @@ class _CosineRows(torch.autograd.Function):
 def cosine_rows(x: torch.Tensor, y: torch.Tensor, eps: float = 1e-8) -> torch.Tensor:
     """out [B, N] = cos(x[b], y[b, n]) with nn.CosineSimilarity's clamp: x [B, D], y [B, N, D]."""
     return _CosineRows.apply(x, y, eps)
+
+
+class _ActDropout(torch.autograd.Function):
+    """y = act(x) m / (1 - p); the backward recomputes act' from x (plain dropout keeps nothing)."""
+
+    @staticmethod
+    def forward(ctx, x, act, drop):
+        x = _rows("x", x)
+        if act not in _lib.ROW_ACT:
+            raise ValueError(f"act_dropout: act {act!r} not in {sorted(_lib.ROW_ACT)}")
+        width = x.shape[-1]
+        rows = x.numel() // width
+        p, seed, call = drop if drop is not None else (0.0, 0, 0)
+        y = torch.empty_like(x)
+        _lib.check(_lib.load().drin_act_dropout_fwd(_ptr(x), _ptr(y), rows, width, _lib.ROW_ACT[act], p, seed, call, _stream(x.device)))
+        ctx.save_for_backward(*(() if act == "none" else (x,)))
+        ctx.setup = (rows, width, _lib.ROW_ACT[act], p, seed, call)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        x = ctx.saved_tensors[0] if ctx.saved_tensors else None
+        dy = dy.contiguous()
+        dx = torch.empty_like(dy)
+        _lib.check(_lib.load().drin_act_dropout_bwd(_ptr(x), _ptr(dy), _ptr(dx), *ctx.setup, _stream(dy.device)))
+        return dx, None, None
+
+
+def act_dropout(x: torch.Tensor, act: str = "none", drop: Optional[Tuple[float, int, int]] = None) -> torch.Tensor:
+    """act(x) m / (1 - p) over the last dimension's rows: act "none" | "relu" | "gelu" (exact erf), drop = (p, seed, call) of a
+    `DropoutStream.draw_rows(rows, width)` or None for no dropout.  Widths that are multiples of 4."""
+    return _ActDropout.apply(x, act, drop)
+
+
+class _SpanMean(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, seq, start, end):
+        seq = _rows("seq", seq)
+        B, L, D = seq.shape
+        start, end = (torch.as_tensor(t).to(seq.device, torch.int64).contiguous() for t in (start, end))
+        if tuple(start.shape) != (B,) or tuple(end.shape) != (B,):
+            raise RuntimeError(f"span_mean: start {tuple(start.shape)} / end {tuple(end.shape)} are not [batch] = {(B,)}")
+        out = torch.empty(B, D, dtype=torch.float32, device=seq.device)
+        _lib.check(_lib.load().drin_span_mean_fwd(_ptr(seq), _ptr(start), _ptr(end), _ptr(out), B, L, D, _stream(seq.device)))
+        ctx.save_for_backward(start, end)
+        ctx.seq_len = L
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        start, end = ctx.saved_tensors
+        dout = dout.contiguous()
+        B, D = dout.shape
+        dseq = torch.empty(B, ctx.seq_len, D, dtype=torch.float32, device=dout.device)
+        _lib.check(_lib.load().drin_span_mean_bwd(_ptr(dout), _ptr(start), _ptr(end), _ptr(dseq), B, ctx.seq_len, D, _stream(dout.device)))
+        return dseq, None, None
+
+
+def span_mean(seq: torch.Tensor, start: torch.Tensor, end: torch.Tensor) -> torch.Tensor:
+    """[B, D] = mean of seq[b, start[b] : end[b]] (seq [B, L, D]) with Python's slice clipping; an empty span gives a NaN row
+    forward, as the reference's `Avg.avg`, and passes a zero gradient."""
+    return _SpanMean.apply(seq, start, end)
 
 
 def entity_token_mean(feat: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:

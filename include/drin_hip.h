@@ -867,6 +867,39 @@ DRIN_API int drin_cosine_rows_bwd(const float* x, const float* y, const float* d
 DRIN_API int drin_entity_token_mean(const float* feat, const int64_t* mask, float* out, int64_t pairs, int32_t tokens,
                                     int32_t width, void* stream);
 
+/* ---- activation, row dropout and the span mean (GHMFC's other mention encoders) ---------------- *
+ * What nn.TransformerEncoderLayer runs beside its products, attention and LayerNorms (ghmfc.py:72-90), and Avg.avg
+ * (ghmfc.py:54-60) as an entry point of its own.  Checked on the host before a launch like the row operations above. */
+
+/* Activation codes of drin_act_dropout_*: NOT drin_activation (whose 0 means "the reference's default"). */
+typedef enum {
+  DRIN_ROW_ACT_NONE = 0, /* identity: plain dropout                                   */
+  DRIN_ROW_ACT_RELU = 1, /* max(x, 0), relu'(0) = 0; a NaN passes, as torch.relu     */
+  DRIN_ROW_ACT_GELU = 2  /* exact-erf gelu, the expressions of the gate              */
+} drin_row_activation;
+
+/* y = act(x) m / (1 - p), element-wise over [rows, width] contiguous floats (width % 4 == 0, 16-byte aligned pointers, any
+ * rows >= 1).  m is the keep mask of drin_attention_dropout_keep(seed, call, rows, 1, 1, width, p, ...): element
+ * (row, col) is element row * width + col of csrc/dropout_mask.h.  A dropped element is exactly 0 (a NaN there too).
+ * p = 0: no mask, the plain activation's bits; p outside [0, 1), a NaN too: DRIN_E_SHAPE; an unknown act: DRIN_E_SHAPE.
+ * y may be x.  Profiler class DRIN_KC_NORM. */
+DRIN_API int drin_act_dropout_fwd(const float* x, float* y, int64_t rows, int32_t width, int32_t act, float p, uint64_t seed,
+                                  uint64_t call, void* stream);
+/* dx = dy act'(x) m / (1 - p) with act' recomputed from the forward's x and the same (p, seed, call).  With
+ * DRIN_ROW_ACT_NONE x is not read and may be NULL: the forward applied to dy, bit for bit.  dx may be dy. */
+DRIN_API int drin_act_dropout_bwd(const float* x, const float* dy, float* dx, int64_t rows, int32_t width, int32_t act, float p,
+                                  uint64_t seed, uint64_t call, void* stream);
+
+/* out[b, :] = mean(seq[b, start[b] : end[b], :]) with Python's slice clipping (negative positions count from seq_len, the
+ * range is cut to [0, seq_len]); seq [batch, seq_len, width], start, end int64 [batch].  An empty range gives a NaN row, as
+ * torch.mean of an empty slice.  The bits of drin_edges_fwd's span mean.  Profiler class DRIN_KC_POOL. */
+DRIN_API int drin_span_mean_fwd(const float* seq, const int64_t* start, const int64_t* end, float* out, int32_t batch,
+                                int32_t seq_len, int32_t width, void* stream);
+/* dseq [batch, seq_len, width], every element written: dout[b, :] / (end - start) on the rows of the clipped range, exactly
+ * 0 elsewhere; an empty range gives a block of zeros. */
+DRIN_API int drin_span_mean_bwd(const float* dout, const int64_t* start, const int64_t* end, float* dseq, int32_t batch,
+                                int32_t seq_len, int32_t width, void* stream);
+
 /* ---- in-process kernel timing (bench.py's roofline leg) ---------------------------------------- */
 
 /* Kernel classes the launches are attributed to. */
@@ -882,7 +915,7 @@ typedef enum {
   DRIN_KC_LSTM = 8,        /* drin_melhi_*: one step of the long LSTM recurrences (forward or backward) */
   DRIN_KC_CELL = 9,        /* drin_melhi_*: mask, time-0 cells, gathers and their backward           */
   DRIN_KC_ATTN = 10,       /* drin_attention* / drin_ghmfc_forward: the softmax-attention core and its backward */
-  DRIN_KC_NORM = 11,       /* drin_ghmfc_forward and the row-op entry points: LayerNorm (+ residual), max over a sequence, the gate, their backward */
+  DRIN_KC_NORM = 11,       /* drin_ghmfc_forward and the row-op entry points: LayerNorm (+ residual), max over a sequence, the gate, activation + row dropout, their backward */
   DRIN_KC_COUNT = 12
 } drin_kernel_class;
 

@@ -253,6 +253,14 @@ EXPORTS = {
                                              C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                              C.c_float, C.c_uint64, C.c_uint64, C.c_void_p]),
     "drin_attention_dropout_keep": (C.c_int, [C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p]),
+    # the matrix-core attention core (csrc/attention_mfma.hip): the dropout entry points' argument lists, p = 0 = no dropout
+    "drin_attention_mfma_fwd": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                          C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float,
+                                          C.c_uint64, C.c_uint64, C.c_void_p]),
+    "drin_attention_mfma_bwd": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                          C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                          C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                          C.c_float, C.c_uint64, C.c_uint64, C.c_void_p]),
     "drin_layernorm_res_train_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.c_int64, C.c_int32, C.c_float, C.c_void_p]),
     "drin_layernorm_res_bwd_scratch_floats": (C.c_size_t, [C.c_int64, C.c_int32]),

@@ -2,7 +2,8 @@
 out-projections, forward `drin_attention_train_fwd`, backward `drin_attention_bwd`) and `MultiheadAttention`, a drop-in
 `nn.MultiheadAttention` (torch's parameters, state-dict keys and initial draw) whose projections run through
 `drin_linear_fwd` / `drin_linear_bwd`.  This is the block GHMFC runs four times per forward (`baselines/ghmfc.py:96-110`);
-`drin_amd.ghmfc.Model` itself still scores only; `drin_amd.ghmfc_train.TrainableModel` trains.  Attention dropout in training
+`drin_amd.ghmfc.Model` itself still scores only; `drin_amd.ghmfc_train.TrainableModel` trains.  `core="mfma"` moves the core
+onto the matrix pipes in split-bf16 arithmetic (`drin_attention_mfma_fwd` / `_bwd`).  Attention dropout in training
 mode is an opt-in: a `DropoutStream` handed to the module selects the library's own counter-based mask
 (`drin_attention_dropout_fwd` / `_bwd`).  What the kernels compute and what is left: DESIGN.md sections 16, 18 and 11.
 
@@ -20,7 +21,14 @@ from . import _lib
 
 PRECISIONS = {"bf16x3": _lib.PREC_BF16X3, "f32": _lib.PREC_F32}
 MAX_KEYS, MAX_HEAD_DIM = 512, 256          # check_attention_shape of the library
+CORES = ("fma", "mfma")                    # the softmax-attention core: fp32 FMA (the default) | split-bf16 MFMA (attention_core)
 ORDERED_DW_SCRATCH = 28                    # drin_linear_bwd: scratch floats per weight element of the ordered dW reduction
+
+
+def _check_core(core: str) -> str:
+    if core not in CORES:
+        raise ValueError(f"core {core!r} not in {list(CORES)}")
+    return core
 
 
 def _ptr(t) -> C.c_void_p:
@@ -94,10 +102,12 @@ def dropout_keep(seed: int, call: int, B: int, H: int, Lq: int, Lk: int, p: floa
 class _CoreCall:
     """One forward (+ backward) of the core through the library: geometry, operands with their row strides and the mask; the
     forward's (out, lse) are the autograd node's saved tensors.  `packed`: k is a [B, Lk, 2 E] buffer K | V and the gradient comes
-    back the same way.  `drop`: (p, seed, call) of the dropout entry points, or None for the undropped ones."""
+    back the same way.  `drop`: (p, seed, call) of the dropout entry points, or None for the undropped ones.  `core`: "fma"
+    (drin_attention_train_fwd / _bwd and their dropout forms) or "mfma" (drin_attention_mfma_fwd / _bwd, drop = None as p = 0)."""
 
     def __init__(self, q: torch.Tensor, k: torch.Tensor, v: Optional[torch.Tensor], key_mask: Optional[torch.Tensor], num_heads: int,
-                 drop: Optional[Tuple[float, int, int]] = None):
+                 drop: Optional[Tuple[float, int, int]] = None, core: str = "fma"):
+        self.core = _check_core(core)
         self.lib = _lib.load()
         self.drop = drop
         self.packed = v is None
@@ -133,7 +143,11 @@ class _CoreCall:
         out = torch.empty(self.B, self.Lq, self.E, dtype=torch.float32, device=self.device)
         lse = torch.empty(self.B, self.H, self.Lq, dtype=torch.float32, device=self.device)
         B, H, Lq, Lk, dh, stream = self._geometry()
-        if self.drop is None:
+        if self.core == "mfma":
+            _lib.check(self.lib.drin_attention_mfma_fwd(_ptr(self.q), self.ldq, _ptr(self.k), self.ldk, _ptr(self.v), self.ldv,
+                                                        _ptr(self.mask), _ptr(out), self.E, _ptr(lse), B, H, Lq, Lk, dh,
+                                                        *(self.drop or (0.0, 0, 0)), stream))
+        elif self.drop is None:
             _lib.check(self.lib.drin_attention_train_fwd(_ptr(self.q), self.ldq, _ptr(self.k), self.ldk, _ptr(self.v), self.ldv,
                                                          _ptr(self.mask), _ptr(out), self.E, _ptr(lse), B, H, Lq, Lk, dh, stream))
         else:
@@ -158,7 +172,9 @@ class _CoreCall:
         B, H, Lq, Lk, dh, stream = self._geometry()
         operands = (_ptr(self.q), self.ldq, _ptr(self.k), self.ldk, _ptr(self.v), self.ldv, _ptr(self.mask), _ptr(out), E, _ptr(lse),
                     _ptr(dout), lddo, _ptr(dq), E, _ptr(dk), ldd, _ptr(dv), ldd, _ptr(delta), B, H, Lq, Lk, dh)
-        if self.drop is None:
+        if self.core == "mfma":
+            _lib.check(self.lib.drin_attention_mfma_bwd(*operands, *(self.drop or (0.0, 0, 0)), stream))
+        elif self.drop is None:
             _lib.check(self.lib.drin_attention_bwd(*operands, stream))
         else:
             _lib.check(self.lib.drin_attention_dropout_bwd(*operands, *self.drop, stream))
@@ -167,8 +183,8 @@ class _CoreCall:
 
 class _CoreFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, key_mask, num_heads, drop=None):
-        call = _CoreCall(q.detach(), k.detach(), None if v is None else v.detach(), key_mask, num_heads, drop)
+    def forward(ctx, q, k, v, key_mask, num_heads, drop=None, core="fma"):
+        call = _CoreCall(q.detach(), k.detach(), None if v is None else v.detach(), key_mask, num_heads, drop, core)
         out, lse = call.forward()
         ctx.call = call
         ctx.save_for_backward(out, lse)
@@ -179,23 +195,30 @@ class _CoreFunction(torch.autograd.Function):
         need_q, need_k, need_v = ctx.needs_input_grad[:3]
         out, lse = ctx.saved_tensors
         dq, dk, dv = ctx.call.backward(out, lse, dout, need_q, need_k or need_v)
-        return dq, dk if need_k else None, dv if need_v else None, None, None, None
+        return dq, dk if need_k else None, dv if need_v else None, None, None, None, None
 
 
 def attention_core(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, key_mask: Optional[torch.Tensor], num_heads: int,
-                   drop: Optional[Tuple[float, int, int]] = None) -> torch.Tensor:
+                   drop: Optional[Tuple[float, int, int]] = None, core: str = "fma") -> torch.Tensor:
     """out [B, Lq, E] = softmax over the kept keys of (q k^T / sqrt(E / num_heads)) v per head, differentiable in q, k, v.
     q [B, Lq, E], k, v [B, Lk, E]: float32 on the GPU; views with a contiguous last dimension and one row stride (a column
     slice of a wider buffer) are read in place.  key_mask: [B, Lk], nonzero = keep, or None.  A query row with no kept key
     gives zeros and passes no gradient.  k_len <= 512, head dim <= 256.  drop = (p, seed, call): the weights go through the
-    library's dropout mask of that draw (csrc/dropout_mask.h), forward and backward."""
-    return _CoreFunction.apply(q, k, v, key_mask, num_heads, drop)
+    library's dropout mask of that draw (csrc/dropout_mask.h), forward and backward.
+    core: "fma" (the default) is the fp32 FMA core.  "mfma" runs every product of the forward and the backward on the matrix
+    pipes in split-bf16 arithmetic (each fp32 operand as bf16 hi + lo, three MFMA passes, fp32 accumulation; softmax in fp32):
+    close to fp32 but not exact - against fp64 within 1e-4 of max|out| and 2e-4 of the gradient scale on standard-normal
+    operands.  Same domain, mask, dropout draws and ownership (no atomics, the same bits every run).
+    Measured faster than "fma" at all four GHMFC shapes (Lq, Lk, dh) at B = 64, H = 8 (tools/attention_core_bench.py):
+    (128, 49, 96) and (128, 128, 96) 6.5 - 9.0 x forward and 3.9 - 4.6 x backward, (49, 128, 256) and (49, 49, 256) 2.8 - 3.1 x
+    and 1.7 - 1.8 x.  "fma" stays the default: the choice changes every bit downstream."""
+    return _CoreFunction.apply(q, k, v, key_mask, num_heads, drop, _check_core(core))
 
 
 def attention_core_packed(q: torch.Tensor, kv: torch.Tensor, key_mask: Optional[torch.Tensor], num_heads: int,
-                          drop: Optional[Tuple[float, int, int]] = None) -> torch.Tensor:
+                          drop: Optional[Tuple[float, int, int]] = None, core: str = "fma") -> torch.Tensor:
     """attention_core with K | V side by side in one [B, Lk, 2 E] buffer; its gradient comes back as one buffer dK | dV."""
-    return _CoreFunction.apply(q, kv, None, key_mask, num_heads, drop)
+    return _CoreFunction.apply(q, kv, None, key_mask, num_heads, drop, _check_core(core))
 
 
 # ---- the projections ----------------------------------------------------------------------------------------
@@ -249,11 +272,13 @@ def _linear(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], precisi
 
 def multihead_attention_forward(query, key, value, key_padding_mask=None, *, embed_dim, num_heads, kdim, vdim, in_proj_weight,
                                 q_proj_weight, k_proj_weight, v_proj_weight, in_proj_bias, out_proj_weight, out_proj_bias, precision,
-                                dropout=0.0, dropout_stream=None) -> torch.Tensor:
+                                dropout=0.0, dropout_stream=None, core="fma") -> torch.Tensor:
     """`MultiheadAttention.forward` on parameter tensors, wherever they live (the module's own, or torch's
     `nn.TransformerEncoderLayer.self_attn`): out [B, Lq, E].  `in_proj_weight` is None when the three widths differ (then
     `q_proj_weight`, `k_proj_weight`, `v_proj_weight` are read).  `dropout` is the rate that applies to this call (0 outside
-    training); a rate > 0 takes one draw from `dropout_stream`."""
+    training); a rate > 0 takes one draw from `dropout_stream`.  `core`: the softmax-attention core (`attention_core`),
+    whatever the projections' `precision`."""
+    _check_core(core)
     _require_gpu_f32("the module (out_proj.weight)", out_proj_weight)
     for name, t in (("query", query), ("key", key), ("value", value)):
         _require_gpu_f32(name, t)
@@ -289,16 +314,16 @@ def multihead_attention_forward(query, key, value, key_padding_mask=None, *, emb
         q = _linear(xq, w[:E], bq, prec).view(B, Lq, E)
         if key is value:                       # K | V: one product, one [rows, 2 E] buffer, one backward
             kv = _linear(key.reshape(B * Lk, E), w[E:], None if bias is None else bias[E:], prec)
-            ctx = attention_core_packed(q, kv.view(B, Lk, 2 * E), mask, num_heads, drop)
+            ctx = attention_core_packed(q, kv.view(B, Lk, 2 * E), mask, num_heads, drop, core)
         else:
             k = _linear(key.reshape(B * Lk, E), w[E:2 * E], bk, prec).view(B, Lk, E)
             v = _linear(value.reshape(B * Lk, E), w[2 * E:], bv, prec).view(B, Lk, E)
-            ctx = attention_core(q, k, v, mask, num_heads, drop)
+            ctx = attention_core(q, k, v, mask, num_heads, drop, core)
     else:
         q = _linear(xq, q_proj_weight, bq, prec).view(B, Lq, E)
         k = _linear(key.reshape(B * Lk, kdim), k_proj_weight, bk, prec).view(B, Lk, E)
         v = _linear(value.reshape(B * Lk, vdim), v_proj_weight, bv, prec).view(B, Lk, E)
-        ctx = attention_core(q, k, v, mask, num_heads, drop)
+        ctx = attention_core(q, k, v, mask, num_heads, drop, core)
     out = _linear(ctx.view(B * Lq, E), out_proj_weight, out_proj_bias, prec)
     return out.view(B, Lq, E)
 
@@ -306,8 +331,9 @@ def multihead_attention_forward(query, key, value, key_padding_mask=None, *, emb
 # ---- the module ---------------------------------------------------------------------------------------------
 class MultiheadAttention(nn.MultiheadAttention):
     """`nn.MultiheadAttention(..., batch_first=True)` on the HIP library, forward and backward.  The constructor takes
-    torch's arguments plus `precision`: "bf16x3" (split-bf16 projections, the default) or "f32" (exact fp32 MFMA); the
-    core is fp32 FMA in both.  `forward(query, key, value, key_padding_mask=None, need_weights=False)` returns
+    torch's arguments plus `precision`: "bf16x3" (split-bf16 projections, the default) or "f32" (exact fp32 MFMA), and
+    `core`: "fma" (the fp32 FMA softmax-attention core, the default) or "mfma" (the split-bf16 matrix-core one: `attention_core`),
+    chosen independently of `precision`.  `forward(query, key, value, key_padding_mask=None, need_weights=False)` returns
     `(out [B, Lq, E], None)`; gradients reach every parameter that requires one and `query` / `key` / `value` when they do.
     With one embedding width and `key is value`, K | V are one product on rows E .. 3 E of `in_proj_weight` and the core's
     packed dK | dV goes back through one.  Refused, each with the reason: CPU tensors, `batch_first=False`, `attn_mask`,
@@ -318,9 +344,10 @@ class MultiheadAttention(nn.MultiheadAttention):
 
     def __init__(self, embed_dim, num_heads, dropout=0.0, bias=True, add_bias_kv=False, add_zero_attn=False, kdim=None, vdim=None,
                  batch_first=False, device=None, dtype=None, precision: str = "bf16x3",
-                 dropout_stream: Optional[DropoutStream] = None):
+                 dropout_stream: Optional[DropoutStream] = None, core: str = "fma"):
         if precision not in PRECISIONS:
             raise ValueError(f"precision {precision!r} not in {sorted(PRECISIONS)}")
+        _check_core(core)
         if not batch_first:
             raise NotImplementedError("drin_amd.attention.MultiheadAttention: batch_first=False is not implemented; the library "
                                       "reads [batch, length, width] rows (pass batch_first=True)")
@@ -340,6 +367,7 @@ class MultiheadAttention(nn.MultiheadAttention):
                          vdim=vdim, batch_first=True, device=device, dtype=dtype)
         self.precision = precision
         self.dropout_stream = dropout_stream
+        self.core = core
 
     def forward(self, query, key, value, key_padding_mask=None, need_weights=False, attn_mask=None, average_attn_weights=True,
                 is_causal=False):
@@ -357,4 +385,4 @@ class MultiheadAttention(nn.MultiheadAttention):
             in_proj_weight=self.in_proj_weight, q_proj_weight=self.q_proj_weight, k_proj_weight=self.k_proj_weight,
             v_proj_weight=self.v_proj_weight, in_proj_bias=self.in_proj_bias, out_proj_weight=self.out_proj.weight,
             out_proj_bias=self.out_proj.bias, precision=self.precision, dropout=self.dropout if self.training else 0.0,
-            dropout_stream=self.dropout_stream), None
+            dropout_stream=self.dropout_stream, core=self.core), None

@@ -9,6 +9,7 @@
 // Every x W^T + b goes through launch_gemm_nt (the GEMM module picks the kernel); the kernels here are everything else.
 // No atomics (column sums go through per-workgroup partial rows added in a fixed order), no scratch memory, at most 54 KB of
 // static LDS per workgroup: the same bits every run.
+#include "attention_common.h"
 #include "device_utils.h"
 #include "dropout_mask.h"
 #include "internal.h"
@@ -28,7 +29,6 @@ namespace {
 // q is staged multiplied by log2(e) / sqrt(dh): the exponentials are exp2.  A key is dropped when mask[b, key] == 0; a row
 // with no kept key keeps l = 0 and writes zeros (what torch's kernel gives for an all-masked row: zero weights).
 constexpr int kAttnRows = 4, kAttnWaves = 4, kAttnQT = kAttnRows * kAttnWaves;
-constexpr int kAttnMaxDh = 256, kAttnMaxLk = 512;
 constexpr int kAttnKvFloats = 64 * 132;   // 64 keys x (128 + 4) >= 32 keys x (256 + 4)
 
 template <int CTRL>
@@ -70,12 +70,7 @@ __device__ __forceinline__ void stage_rows(float* dst, int ds, const float* src,
 
 // DROP (drin_attention_dropout_fwd): the weight of (query i, key j) that goes into p V is multiplied by keep / (1 - rate)
 // (dropout_mask.h); the running max, the sum l and lse are those of the undropped scores.  A separate instantiation: the
-// code of DROP = false is what it was.
-struct DropArgs {
-  uint32_t threshold;   // dropout_threshold(rate)
-  float scale;          // 1 / (1 - rate)
-  uint64_t seed, call;
-};
+// code of DROP = false is what it was.  (DropArgs: attention_common.h)
 
 template <int KT, bool DROP = false>
 __global__ void __launch_bounds__(256) k_attention(const float* __restrict__ q, int64_t ldq, const float* __restrict__ k, int64_t ldk,
@@ -764,15 +759,6 @@ int timed(int cls, hipStream_t st, const char* what, F&& launch) {
 }
 
 // ---- launchers ------------------------------------------------------------------------------------------
-int check_attention_shape(int64_t B, int H, int Lq, int Lk, int dh) {
-  if (B < 1 || B > 65535 || H < 1 || H > 65535 || Lq < 1 || Lk < 1 || Lk > kAttnMaxLk || dh < 1 || dh > kAttnMaxDh) {
-    set_error("attention: batch and heads in [1, 65535], q_len >= 1, k_len in [1, %d], head_dim in [1, %d] (got B=%lld H=%d Lq=%d Lk=%d dh=%d)",
-              kAttnMaxLk, kAttnMaxDh, (long long)B, H, Lq, Lk, dh);
-    return DRIN_E_SHAPE;
-  }
-  return DRIN_OK;
-}
-
 int launch_attention(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv, const int64_t* mask,
                      float* out, int64_t ldo, int B, int H, int Lq, int Lk, int dh, hipStream_t st, float* lse = nullptr,
                      const DropArgs* drop = nullptr) {
@@ -799,6 +785,19 @@ int launch_attention(const float* q, int64_t ldq, const float* k, int64_t ldk, c
   });
 }
 
+}  // namespace
+
+int launch_attention_bwd_delta(const float* out, int64_t ldo, const float* dout, int64_t lddo, float* delta, int B, int H, int Lq,
+                               int dh, hipStream_t st) {
+  const int64_t rows = (int64_t)B * H * Lq;
+  return timed(DRIN_KC_ATTN, st, "k_attention_bwd_delta", [&] {
+    const int64_t blocks = cdiv(rows, 4);
+    hipLaunchKernelGGL(k_attention_bwd_delta, dim3((unsigned)(blocks < (1 << 20) ? blocks : (1 << 20))), dim3(256), 0, st, out, ldo, dout,
+                       lddo, delta, rows, H, Lq, dh);
+  });
+}
+
+namespace {
 // dq may be NULL (skipped); dk and dv are both given or both NULL.  delta: [B, H, Lq] floats of scratch.
 int launch_attention_bwd(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv, const int64_t* mask,
                          const float* out, int64_t ldo, const float* lse, const float* dout, int64_t lddo, float* dq, int64_t lddq,
@@ -809,13 +808,8 @@ int launch_attention_bwd(const float* q, int64_t ldq, const float* k, int64_t ld
   const float inv_sqrt = 1.0f / sqrtf((float)dh), q_scale = 1.44269504088896340736f * inv_sqrt;
   const bool wide = ((dh + 3) & ~3) > 128;
   const int KT = wide ? 16 : 32, QT = wide ? 8 : 16;
-  const int64_t rows = (int64_t)B * H * Lq;
   const DropArgs da = drop ? *drop : DropArgs{};
-  DRIN_TRY(timed(DRIN_KC_ATTN, st, "k_attention_bwd_delta", [&] {
-    const int64_t blocks = cdiv(rows, 4);
-    hipLaunchKernelGGL(k_attention_bwd_delta, dim3((unsigned)(blocks < (1 << 20) ? blocks : (1 << 20))), dim3(256), 0, st, out, ldo, dout,
-                       lddo, delta, rows, H, Lq, dh);
-  }));
+  DRIN_TRY(launch_attention_bwd_delta(out, ldo, dout, lddo, delta, B, H, Lq, dh, st));
   if (dq != nullptr) {
     const dim3 grid((unsigned)cdiv(Lq, QT), (unsigned)H, (unsigned)B);
     DRIN_TRY(timed(DRIN_KC_ATTN, st, "k_attention_bwd_dq", [&] {
@@ -1098,17 +1092,6 @@ int drin_attention(const float* q, int64_t ldq, const float* k, int64_t ldk, con
 }
 
 namespace {
-// rate in [0, 1) -> the kernels' arguments; a rate of 0 is the plain path (use = false): the undropped entry points' bits
-int dropout_args(const char* who, float p, uint64_t seed, uint64_t call, DropArgs* out, bool* use) {
-  if (!(p >= 0.f && p < 1.f)) {
-    set_error("%s: dropout rate %g is not in [0, 1)", who, (double)p);
-    return DRIN_E_SHAPE;
-  }
-  *use = p > 0.f;
-  *out = DropArgs{dropout_threshold(p), 1.0f / (1.0f - p), seed, call};
-  return DRIN_OK;
-}
-
 int attention_train_fwd(const char* who, const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv,
                         const int64_t* key_mask, float* out, int64_t ldo, float* lse, int32_t batch, int32_t num_heads, int32_t q_len,
                         int32_t k_len, int32_t head_dim, void* stream, const DropArgs* drop) {

@@ -31,7 +31,7 @@ def _args():
 
 class Model(_Model):
     """`model_module.Model()`: geometry and `transformer_dropout` from `common.args`; split-bf16 products unless
-    DRIN_PRECISION=f32.  The attention dropout of train() mode is the library's own mask, seeded by `args.seed`.  With another
+    DRIN_PRECISION=f32; the softmax-attention core of DRIN_ATTENTION_CORE ("fma", the default, or "mfma").  The attention dropout of train() mode is the library's own mask, seeded by `args.seed`.  With another
     mention encoder selected in `common.args` (`mention_final_layer_name`, `mention_multimodal_attention`: "transformer",
     "multimodal" + "text", "linear", "none") `Model()` is a `drin_amd.ghmfc_variants.VariantModel` built the same way."""
 
@@ -41,12 +41,13 @@ class Model(_Model):
         if cfg.is_default:
             return super().__new__(cls)
         return VariantModel(cfg, precision=os.environ.get("DRIN_PRECISION", "bf16x3"), dropout=getattr(a, "transformer_dropout", 0.1),
-                            seed=getattr(a, "seed", 0))
+                            seed=getattr(a, "seed", 0), core=os.environ.get("DRIN_ATTENTION_CORE", "fma"))
 
     def __init__(self):
         a = _args()
         super().__init__(config_from_reference_args(a), precision=os.environ.get("DRIN_PRECISION", "bf16x3"),
-                         dropout=getattr(a, "transformer_dropout", 0.1), seed=getattr(a, "seed", 0))
+                         dropout=getattr(a, "transformer_dropout", 0.1), seed=getattr(a, "seed", 0),
+                         core=os.environ.get("DRIN_ATTENTION_CORE", "fma"))
 
 
 class GhmfcData(Dataset):

@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import torch
 
-from .attention import PRECISIONS, DropoutStream, MultiheadAttention, _linear
+from .attention import CORES, PRECISIONS, DropoutStream, MultiheadAttention, _linear
 from .ghmfc import GhmfcConfig, Model, _MentionEncoder
 from .row_ops import cosine_rows, entity_token_mean, gate_mix, layer_norm_res, seq_max
 
@@ -24,22 +24,28 @@ class TrainableModel(Model):
     dropped at rate `dropout` by the library's mask; `dropout=0` trains without.  After each training forward
     `max_indices == {"text": idx [B, D], "image": idx [B, R]}` (int32) holds the position each max over the sequence took its
     value from - the lowest one on a tie, which is where the gradient goes.  The batch tensors are detached: their gradients
-    are out of scope.  A 2-token WikiMEL entity gives a NaN row, as in the reference.  CPU tensors are refused."""
+    are out of scope.  A 2-token WikiMEL entity gives a NaN row, as in the reference.  CPU tensors are refused.
+    `core`: the softmax-attention core of the training forward and backward, "fma" (the default) or "mfma"
+    (`drin_amd.attention.attention_core`); `eval()` scores through `drin_ghmfc_forward`, whose core is the FMA one."""
 
-    def __init__(self, cfg: GhmfcConfig | None = None, precision: str = "bf16x3", dropout: float = 0.1, seed: int = 0):
+    def __init__(self, cfg: GhmfcConfig | None = None, precision: str = "bf16x3", dropout: float = 0.1, seed: int = 0,
+                 core: str = "fma"):
         if not 0.0 <= dropout < 1.0:
             raise ValueError(f"dropout {dropout} is not in [0, 1)")
+        if core not in CORES:
+            raise ValueError(f"core {core!r} not in {list(CORES)}")
         # read by _make_mention_encoder, which the parent's __init__ calls: set ahead of nn.Module.__init__, past its __setattr__
-        object.__setattr__(self, "_attention_setup", (float(dropout), DropoutStream(seed), precision))
+        object.__setattr__(self, "_attention_setup", (float(dropout), DropoutStream(seed), precision, core))
         super().__init__(cfg, precision)
         self.dropout, self.dropout_stream = self._attention_setup[:2]
+        self.core = core
         self.max_indices = {}
 
     def _make_mention_encoder(self, cfg: GhmfcConfig):
-        dropout, stream, precision = self._attention_setup
+        dropout, stream, precision, core = self._attention_setup
 
         def attention(*args, **kwargs):
-            return MultiheadAttention(*args, precision=precision, dropout_stream=stream, **kwargs)
+            return MultiheadAttention(*args, precision=precision, dropout_stream=stream, core=core, **kwargs)
         return _MentionEncoder(cfg, dropout, attention)
 
     def _cross_attention_max(self, ca, seq_a, drop_a, seq_b, drop_b):

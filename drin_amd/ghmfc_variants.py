@@ -15,7 +15,7 @@ from dataclasses import dataclass, fields
 import torch
 from torch import nn
 
-from .attention import PRECISIONS, DropoutStream, MultiheadAttention, _linear, multihead_attention_forward
+from .attention import CORES, PRECISIONS, DropoutStream, MultiheadAttention, _linear, multihead_attention_forward
 from .ghmfc import GhmfcConfig, _CrossAttention, _EntityEncoder
 from .ghmfc_train import TrainableModel
 from .row_ops import act_dropout, cosine_rows, entity_token_mean, layer_norm_res, seq_max, span_mean
@@ -145,26 +145,32 @@ class VariantModel(nn.Module):
 
     A mention whose mask is all zero: in the transformer its attention rows are zero (the core's rule for a query with no
     kept key), so its scores are finite - the library's definition; torch has two answers there (NaN on its fused inference
-    path, finite under autograd).  Batch tensors are detached: their gradients are out of scope.  CPU tensors are refused."""
+    path, finite under autograd).  Batch tensors are detached: their gradients are out of scope.  CPU tensors are refused.
+    `core`: the softmax-attention core of every attention of the model, "fma" (the default) or "mfma"
+    (`drin_amd.attention.attention_core`), in `train()` and `eval()` alike."""
 
-    def __new__(cls, cfg: VariantConfig | None = None, precision: str = "bf16x3", dropout: float = 0.1, seed: int = 0):
+    def __new__(cls, cfg: VariantConfig | None = None, precision: str = "bf16x3", dropout: float = 0.1, seed: int = 0,
+                core: str = "fma"):
         cfg = cfg or VariantConfig()
         if cfg.is_default:
-            return TrainableModel(cfg.base(), precision=precision, dropout=dropout, seed=seed)
+            return TrainableModel(cfg.base(), precision=precision, dropout=dropout, seed=seed, core=core)
         return super().__new__(cls)
 
-    def __init__(self, cfg: VariantConfig | None = None, precision: str = "bf16x3", dropout: float = 0.1, seed: int = 0):
+    def __init__(self, cfg: VariantConfig | None = None, precision: str = "bf16x3", dropout: float = 0.1, seed: int = 0,
+                 core: str = "fma"):
         super().__init__()
         if precision not in PRECISIONS:
             raise ValueError(f"precision {precision!r} not in {sorted(PRECISIONS)}")
+        if core not in CORES:
+            raise ValueError(f"core {core!r} not in {list(CORES)}")
         if not 0.0 <= dropout < 1.0:
             raise ValueError(f"dropout {dropout} is not in [0, 1)")
-        self.cfg, self.precision, self.dropout = cfg, precision, float(dropout)
+        self.cfg, self.precision, self.dropout, self.core = cfg, precision, float(dropout), core
         self.dropout_stream = stream = DropoutStream(seed)
         self.max_indices = {}
 
         def attention(*args, **kwargs):
-            return MultiheadAttention(*args, precision=precision, dropout_stream=stream, **kwargs)
+            return MultiheadAttention(*args, precision=precision, dropout_stream=stream, core=core, **kwargs)
         self.mention_encoder = _VariantMentionEncoder(cfg, self.dropout, attention)
         self.entity_encoder = _EntityEncoder(cfg)
 
@@ -213,7 +219,7 @@ class VariantModel(nn.Module):
                 x, x, x, padding, embed_dim=D, num_heads=cfg.num_heads, kdim=D, vdim=D, in_proj_weight=sa.in_proj_weight,
                 q_proj_weight=None, k_proj_weight=None, v_proj_weight=None, in_proj_bias=sa.in_proj_bias,
                 out_proj_weight=sa.out_proj.weight, out_proj_bias=sa.out_proj.bias, precision=self.precision, dropout=p,
-                dropout_stream=self.dropout_stream)
+                dropout_stream=self.dropout_stream, core=self.core)
             drop1 = self._drop(rows, D)
             if drop1 is not None:
                 a = act_dropout(a, "none", drop1)

@@ -810,6 +810,32 @@ DRIN_API int drin_attention_dropout_bwd(const float* q, int64_t ldq, const float
 DRIN_API int drin_attention_dropout_keep(uint64_t seed, uint64_t call, int32_t batch, int32_t num_heads, int32_t q_len,
                                          int32_t k_len, float p, uint8_t* keep_host);
 
+/* ---- the same core on the matrix pipes (csrc/attention_mfma.hip) --------------------------------- *
+ * An opt-in beside the FMA entry points above, which keep their bits.  Every product (q k^T, p v, dout v^T, p^T dout, ds k,
+ * ds^T q) is the library's split-bf16 form: each fp32 operand x is hi = bf16(x), lo = bf16(x - hi), and hi hi + hi lo + lo hi
+ * accumulate in fp32 through v_mfma_f32_16x16x32_bf16 - close to fp32, not exact.  Softmax, max, sum, lse, delta and
+ * ds = p (dp - delta) stay fp32.  Operands, strides, key_mask, limits and the dropout mask (same (p, seed, call), same kept
+ * weights) are those of drin_attention_dropout_fwd / _bwd; p in [0, 1), anything else is DRIN_E_SHAPE; p = 0 means no
+ * dropout (seed and call are then not read).  No atomics (a workgroup owns its query rows / its keys): the same bits every
+ * run.  All arguments are checked on the host before a launch. */
+
+/* out, and lse [batch, num_heads, q_len] unless lse is NULL (inference; out has the same bits either way): the natural
+ * log-sum-exp over the kept keys of the undropped scaled scores, -inf for a row with no kept key (its out row is zero). */
+DRIN_API int drin_attention_mfma_fwd(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv,
+                                     const int64_t* key_mask, float* out, int64_t ldo, float* lse, int32_t batch,
+                                     int32_t num_heads, int32_t q_len, int32_t k_len, int32_t head_dim, float p, uint64_t seed,
+                                     uint64_t call, void* stream);
+/* Backward of that forward (out, lse: what it wrote).  dq may be NULL (not computed); dk and dv are both given or both NULL.
+ * Gradients are WRITTEN, not accumulated, and only into their own E columns of each row (strides >= E; dK | dV packed in one
+ * [rows, 2 E] buffer are dk = buf, dv = buf + E, lddk = lddv = 2 E).  A dropped key's dk and dv rows are exactly 0; a query
+ * row with no kept key has a dq row of exactly 0 and adds nothing to dk or dv.  delta_scratch: [batch, num_heads, q_len]
+ * floats, overwritten.  The bits of dk and dv do not depend on whether dq is asked for. */
+DRIN_API int drin_attention_mfma_bwd(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv,
+                                     const int64_t* key_mask, const float* out, int64_t ldo, const float* lse, const float* dout,
+                                     int64_t lddo, float* dq, int64_t lddq, float* dk, int64_t lddk, float* dv, int64_t lddv,
+                                     float* delta_scratch, int32_t batch, int32_t num_heads, int32_t q_len, int32_t k_len,
+                                     int32_t head_dim, float p, uint64_t seed, uint64_t call, void* stream);
+
 /* ---- GHMFC's row operations one by one, forward and backward --------------- *
  * What drin_ghmfc_forward runs between its products, exposed so that a training step can be composed from them, and their
  * backward kernels.  Every pointer is a 16-byte aligned device pointer, rows are contiguous, widths are multiples of 4.

@@ -4,7 +4,10 @@ N = 11 candidates, batch 64, max pool, in both precisions, with the per-class ke
 step, the host time between launches, and the same parameters through torch's own nn.TransformerEncoder (same process) for
 scale - not a gate.  GPU only.
 
-    python tools/ghmfc_variant_bench.py [--out profiles/ghmfc_variant_bench.jsonl] [--processes 3] [--iters 10]
+    python tools/ghmfc_variant_bench.py [--out profiles/ghmfc_variant_bench.jsonl] [--processes 3] [--iters 10] [--core fma]
+
+--core mfma builds the model on the matrix-core attention core (drin_amd.attention.attention_core); its default output is
+profiles/ghmfc_variant_bench_mfma.jsonl, and the record carries the core's name.
 
 Every process is a fresh child (its own HIP context and code-object loads) under its own time limit.  The first line of the
 output is the median over the processes, the lines behind it are the processes' own records.  The columns are those of
@@ -26,7 +29,7 @@ sys.path.insert(0, REPO)
 BATCH, CANDIDATES, DROPOUT, WARMUP = 64, 11, 0.1, 3
 
 
-def child(iters: int) -> dict:
+def child(iters: int, core: str = "fma") -> dict:
     import torch
     import torch.nn.functional as F
 
@@ -73,10 +76,10 @@ def child(iters: int) -> dict:
         return {k: ms / iters for k, (ms, n) in prof.items() if n}, sum(n for _ms, n in prof.values()) / iters
 
     record = {"batch": BATCH, "candidates": CANDIDATES, "dropout": DROPOUT, "layers": cfg.transformer_num_layers, "iters": iters,
-              "warmup": WARMUP, "device": torch.cuda.get_device_name(0), "cases": {}}
+              "warmup": WARMUP, "device": torch.cuda.get_device_name(0), "core": core, "cases": {}}
     for precision in ("bf16x3", "f32"):
         torch.manual_seed(0)
-        model = VariantModel(cfg, precision=precision, dropout=DROPOUT, seed=0).to(dev)
+        model = VariantModel(cfg, precision=precision, dropout=DROPOUT, seed=0, core=core).to(dev)
         params = list(model.parameters())
 
         def forward():
@@ -125,14 +128,17 @@ def median_of(records):
 
 
 def main(argv):
-    if "--child" in argv:
-        print("RECORD " + json.dumps(child(int(argv[argv.index("--iters") + 1]))), flush=True)
-        return 0
     opt = lambda name, default: argv[argv.index(name) + 1] if name in argv else default   # noqa: E731
-    out, processes, iters = opt("--out", os.path.join(REPO, "profiles", "ghmfc_variant_bench.jsonl")), int(opt("--processes", 3)), opt("--iters", "10")
+    core = opt("--core", "fma")
+    if "--child" in argv:
+        print("RECORD " + json.dumps(child(int(argv[argv.index("--iters") + 1]), core)), flush=True)
+        return 0
+    default_out = "ghmfc_variant_bench.jsonl" if core == "fma" else f"ghmfc_variant_bench_{core}.jsonl"
+    out, processes, iters = opt("--out", os.path.join(REPO, "profiles", default_out)), int(opt("--processes", 3)), opt("--iters", "10")
     records = []
     for i in range(processes):
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "--iters", iters], capture_output=True, text=True, timeout=150)
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "--iters", iters, "--core", core], capture_output=True,
+                           text=True, timeout=150)
         lines = [ln for ln in r.stdout.splitlines() if ln.startswith("RECORD ")]
         if r.returncode != 0 or not lines:
             sys.stderr.write(r.stdout[-2000:] + r.stderr[-4000:])
@@ -141,7 +147,7 @@ def main(argv):
         rec["process"] = i
         records.append(rec)
         print(f"process {i}: done", flush=True)
-    head = {k: records[0][k] for k in ("batch", "candidates", "dropout", "layers", "iters", "warmup", "device")}
+    head = {k: records[0][k] for k in ("batch", "candidates", "dropout", "layers", "iters", "warmup", "device", "core")}
     head.update(summary=f"median of {processes} fresh processes", cases=median_of(records))
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
     with open(out, "w") as f:

@@ -341,3 +341,23 @@ def profile_end() -> dict:
 def check(status: int) -> None:
     if status != OK:
         raise DrinError(status, load().drin_last_error().decode())
+
+
+# ---- what every torch caller of the entry points needs -------------------------------------------------------------
+def _ptr(t) -> C.c_void_p:
+    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+
+
+def _stream(device) -> C.c_void_p:
+    import torch
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def _scratch(pool: dict, device, stream_id: int, floats: int):
+    """A float32 scratch buffer of `pool` (one dictionary per purpose: buffers of different pools never alias), one per
+    (device, stream) and grown to the largest need seen: calls on one stream run in order, so they share it."""
+    import torch
+    buf = pool.get((device, stream_id))
+    if buf is None or buf.numel() < floats:
+        buf = pool[(device, stream_id)] = torch.empty(max(floats, 1), dtype=torch.float32, device=device)
+    return buf

@@ -1,5 +1,5 @@
 """A multi-head attention that trains on the HIP library: `attention_core` (the softmax-attention core between the in- and
-out-projections, forward `drin_attention_train_fwd`, backward `drin_attention_bwd`) and `MultiheadAttention`, a drop-in
+out-projections, forward `drin_attention_dropout_fwd`, backward `drin_attention_dropout_bwd`) and `MultiheadAttention`, a drop-in
 `nn.MultiheadAttention` (torch's parameters, state-dict keys and initial draw) whose projections run through
 `drin_linear_fwd` / `drin_linear_bwd`.  This is the block GHMFC runs four times per forward (`baselines/ghmfc.py:96-110`);
 `drin_amd.ghmfc.Model` itself still scores only; `drin_amd.ghmfc_train.TrainableModel` trains.  `core="mfma"` moves the core
@@ -18,6 +18,7 @@ import torch
 from torch import nn
 
 from . import _lib
+from ._lib import _ptr, _scratch, _stream
 
 PRECISIONS = {"bf16x3": _lib.PREC_BF16X3, "f32": _lib.PREC_F32}
 MAX_KEYS, MAX_HEAD_DIM = 512, 256          # check_attention_shape of the library
@@ -29,14 +30,6 @@ def _check_core(core: str) -> str:
     if core not in CORES:
         raise ValueError(f"core {core!r} not in {list(CORES)}")
     return core
-
-
-def _ptr(t) -> C.c_void_p:
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def _stream(device) -> C.c_void_p:
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 def _require_gpu_f32(name: str, t: torch.Tensor) -> None:
@@ -102,14 +95,15 @@ def dropout_keep(seed: int, call: int, B: int, H: int, Lq: int, Lk: int, p: floa
 class _CoreCall:
     """One forward (+ backward) of the core through the library: geometry, operands with their row strides and the mask; the
     forward's (out, lse) are the autograd node's saved tensors.  `packed`: k is a [B, Lk, 2 E] buffer K | V and the gradient comes
-    back the same way.  `drop`: (p, seed, call) of the dropout entry points, or None for the undropped ones.  `core`: "fma"
-    (drin_attention_train_fwd / _bwd and their dropout forms) or "mfma" (drin_attention_mfma_fwd / _bwd, drop = None as p = 0)."""
+    back the same way.  `core`: "fma" (drin_attention_dropout_fwd / _bwd) or "mfma" (drin_attention_mfma_fwd / _bwd).  `drop`:
+    (p, seed, call) of the draw, or None, which goes as p = 0: the library's plain path, the undropped entry points' bits."""
 
     def __init__(self, q: torch.Tensor, k: torch.Tensor, v: Optional[torch.Tensor], key_mask: Optional[torch.Tensor], num_heads: int,
                  drop: Optional[Tuple[float, int, int]] = None, core: str = "fma"):
-        self.core = _check_core(core)
-        self.lib = _lib.load()
-        self.drop = drop
+        lib = _lib.load()
+        self.fwd, self.bwd = {"fma": (lib.drin_attention_dropout_fwd, lib.drin_attention_dropout_bwd),
+                              "mfma": (lib.drin_attention_mfma_fwd, lib.drin_attention_mfma_bwd)}[_check_core(core)]
+        self.drop = drop or (0.0, 0, 0)
         self.packed = v is None
         for name, t in (("q", q), ("k", k)) + (() if self.packed else (("v", v),)):
             _require_gpu_f32(name, t)
@@ -143,17 +137,8 @@ class _CoreCall:
         out = torch.empty(self.B, self.Lq, self.E, dtype=torch.float32, device=self.device)
         lse = torch.empty(self.B, self.H, self.Lq, dtype=torch.float32, device=self.device)
         B, H, Lq, Lk, dh, stream = self._geometry()
-        if self.core == "mfma":
-            _lib.check(self.lib.drin_attention_mfma_fwd(_ptr(self.q), self.ldq, _ptr(self.k), self.ldk, _ptr(self.v), self.ldv,
-                                                        _ptr(self.mask), _ptr(out), self.E, _ptr(lse), B, H, Lq, Lk, dh,
-                                                        *(self.drop or (0.0, 0, 0)), stream))
-        elif self.drop is None:
-            _lib.check(self.lib.drin_attention_train_fwd(_ptr(self.q), self.ldq, _ptr(self.k), self.ldk, _ptr(self.v), self.ldv,
-                                                         _ptr(self.mask), _ptr(out), self.E, _ptr(lse), B, H, Lq, Lk, dh, stream))
-        else:
-            _lib.check(self.lib.drin_attention_dropout_fwd(_ptr(self.q), self.ldq, _ptr(self.k), self.ldk, _ptr(self.v), self.ldv,
-                                                           _ptr(self.mask), _ptr(out), self.E, _ptr(lse), B, H, Lq, Lk, dh, *self.drop,
-                                                           stream))
+        _lib.check(self.fwd(_ptr(self.q), self.ldq, _ptr(self.k), self.ldk, _ptr(self.v), self.ldv, _ptr(self.mask), _ptr(out), self.E,
+                            _ptr(lse), B, H, Lq, Lk, dh, *self.drop, stream))
         return out, lse
 
     def backward(self, out: torch.Tensor, lse: torch.Tensor, dout: torch.Tensor, need_q: bool, need_kv: bool):
@@ -170,14 +155,8 @@ class _CoreCall:
             dk, dv = (torch.empty(self.B, self.Lk, E, dtype=torch.float32, device=self.device) for _ in range(2))
         delta = torch.empty(self.B, self.H, self.Lq, dtype=torch.float32, device=self.device)
         B, H, Lq, Lk, dh, stream = self._geometry()
-        operands = (_ptr(self.q), self.ldq, _ptr(self.k), self.ldk, _ptr(self.v), self.ldv, _ptr(self.mask), _ptr(out), E, _ptr(lse),
-                    _ptr(dout), lddo, _ptr(dq), E, _ptr(dk), ldd, _ptr(dv), ldd, _ptr(delta), B, H, Lq, Lk, dh)
-        if self.core == "mfma":
-            _lib.check(self.lib.drin_attention_mfma_bwd(*operands, *(self.drop or (0.0, 0, 0)), stream))
-        elif self.drop is None:
-            _lib.check(self.lib.drin_attention_bwd(*operands, stream))
-        else:
-            _lib.check(self.lib.drin_attention_dropout_bwd(*operands, *self.drop, stream))
+        _lib.check(self.bwd(_ptr(self.q), self.ldq, _ptr(self.k), self.ldk, _ptr(self.v), self.ldv, _ptr(self.mask), _ptr(out), E, _ptr(lse),
+                            _ptr(dout), lddo, _ptr(dq), E, _ptr(dk), ldd, _ptr(dv), ldd, _ptr(delta), B, H, Lq, Lk, dh, *self.drop, stream))
         return (dq, dkv, None) if self.packed else (dq, dk, dv)
 
 
@@ -222,17 +201,7 @@ def attention_core_packed(q: torch.Tensor, kv: torch.Tensor, key_mask: Optional[
 
 
 # ---- the projections ----------------------------------------------------------------------------------------
-_scratch = {}
-
-
-def _bwd_scratch(device, stream_id: int, floats: int) -> torch.Tensor:
-    """The scratch of drin_linear_bwd, one per (device, stream) and grown to the largest product seen: calls on one stream
-    run in order, so they share it."""
-    key = (device, stream_id)
-    buf = _scratch.get(key)
-    if buf is None or buf.numel() < floats:
-        buf = _scratch[key] = torch.empty(floats, dtype=torch.float32, device=device)
-    return buf
+_linear_pool = {}                          # _lib._scratch: the ordered dW reduction of drin_linear_bwd
 
 
 class _LinearFunction(torch.autograd.Function):
@@ -260,7 +229,7 @@ class _LinearFunction(torch.autograd.Function):
         dw = torch.zeros_like(w) if need_w else None
         db = torch.zeros(n, dtype=torch.float32, device=x.device) if need_b and ctx.has_bias else None
         stream = _stream(x.device)
-        scratch = _bwd_scratch(x.device, stream.value or 0, ORDERED_DW_SCRATCH * n * k)
+        scratch = _scratch(_linear_pool, x.device, stream.value or 0, ORDERED_DW_SCRATCH * n * k)
         _lib.check(_lib.load().drin_linear_bwd(_ptr(x), _ptr(w), _ptr(dy), _ptr(dx), _ptr(dw), _ptr(db), rows, n, k, ctx.precision,
                                                _ptr(scratch), scratch.numel(), stream))
         return dx, dw, db, None

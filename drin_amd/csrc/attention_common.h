@@ -1,6 +1,6 @@
-// What the two softmax-attention cores share on the host side: the FMA core of ghmfc_kernels.hip (DESIGN.md sections 15,
-// 16, 18) and the matrix-core one of attention_mfma.hip (section 21).  The domain, the dropout arguments and the launcher of
-// the row statistic delta_i = sum_c dO[i, c] O[i, c], which both backwards read.
+// What the two softmax-attention cores share on the host side: the FMA core of attention_fma.hip (DESIGN.md sections 15,
+// 16, 18) and the matrix-core one of attention_mfma.hip (section 21).  The domain, the dropout arguments, one attention call
+// as a struct, and the launchers of both cores, which take it.  The entry points and their checks: attention_api.hip.
 #pragma once
 #include "dropout_mask.h"
 #include "internal.h"
@@ -17,10 +17,28 @@ struct DropArgs {
   uint64_t seed, call;
 };
 
-inline int check_attention_shape(int64_t B, int H, int Lq, int Lk, int dh) {
+// One call of an attention core.  Rows of head h of mention b, position i start at ptr + (b * L + i) * ld + h * dh.
+// The forward writes out and lse (lse may be NULL where the entry point allows it); the backward only reads them.
+struct AttnCall {
+  const float* q; int64_t ldq;
+  const float* k; int64_t ldk;
+  const float* v; int64_t ldv;
+  const int64_t* mask;            // [B, Lk], 0 drops the key; NULL keeps every key
+  float* out; int64_t ldo;
+  float* lse;                     // [B, H, Lq]
+  int B, H, Lq, Lk, dh;
+  // the backward alone: dq may be NULL (skipped); dk and dv are both given or both NULL; delta: [B, H, Lq] floats of scratch
+  const float* dout = nullptr; int64_t lddo = 0;
+  float* dq = nullptr; int64_t lddq = 0;
+  float* dk = nullptr; int64_t lddk = 0;
+  float* dv = nullptr; int64_t lddv = 0;
+  float* delta = nullptr;
+};
+
+inline int check_attention_shape(const char* who, int64_t B, int H, int Lq, int Lk, int dh) {
   if (B < 1 || B > 65535 || H < 1 || H > 65535 || Lq < 1 || Lk < 1 || Lk > kAttnMaxLk || dh < 1 || dh > kAttnMaxDh) {
-    set_error("attention: batch and heads in [1, 65535], q_len >= 1, k_len in [1, %d], head_dim in [1, %d] (got B=%lld H=%d Lq=%d Lk=%d dh=%d)",
-              kAttnMaxLk, kAttnMaxDh, (long long)B, H, Lq, Lk, dh);
+    set_error("%s: batch and heads in [1, 65535], q_len >= 1, k_len in [1, %d], head_dim in [1, %d] (got B=%lld H=%d Lq=%d Lk=%d dh=%d)",
+              who, kAttnMaxLk, kAttnMaxDh, (long long)B, H, Lq, Lk, dh);
     return DRIN_E_SHAPE;
   }
   return DRIN_OK;
@@ -37,8 +55,15 @@ inline int dropout_args(const char* who, float p, uint64_t seed, uint64_t call, 
   return DRIN_OK;
 }
 
-// delta [B, H, Lq] of the backward, one wave per (mention, head, query row) (k_attention_bwd_delta, ghmfc_kernels.hip)
-int launch_attention_bwd_delta(const float* out, int64_t ldo, const float* dout, int64_t lddo, float* delta, int B, int H, int Lq,
-                               int dh, hipStream_t st);
+// The launchers check nothing: shape, pointers and strides are the caller's (attention_api.hip: attention_forward /
+// attention_backward; ghmfc_forward.hip: validate_ghmfc_config).  drop: NULL is the plain path.
+// attention_fma.hip
+int launch_attention(const AttnCall& c, const DropArgs* drop, hipStream_t st);
+int launch_attention_bwd(const AttnCall& c, const DropArgs* drop, hipStream_t st);
+// delta [B, H, Lq] of both backwards, one wave per (mention, head, query row) (k_attention_bwd_delta)
+int launch_attention_bwd_delta(const AttnCall& c, hipStream_t st);
+// attention_mfma.hip
+int launch_attention_mfma(const AttnCall& c, const DropArgs* drop, hipStream_t st);
+int launch_attention_mfma_bwd(const AttnCall& c, const DropArgs* drop, hipStream_t st);
 
 }  // namespace drin

@@ -1,4 +1,4 @@
-// The softmax-attention core on the matrix pipes: the forward and the backward of ghmfc_kernels.hip's
+// The softmax-attention core on the matrix pipes: the forward and the backward of attention_fma.hip's
 // FMA core with every product as the library's split-bf16 form - each fp32 operand x is hi = bf16(x), lo = bf16(x - hi),
 // and hi hi + hi lo + lo hi accumulate in fp32 through v_mfma_f32_16x16x32_bf16.  Softmax, the running max and sum, lse,
 // delta and ds = p (dp - delta) stay fp32; the exponentials are exp2 on scores in log2 units.  An opt-in
@@ -465,15 +465,7 @@ __global__ void __launch_bounds__(256, 2) k_attention_mfma_bwd_dkv(const float* 
     }
 }
 
-// ---- launchers --------------------------------------------------------------------------------------------
-template <typename F>
-int timed(hipStream_t st, const char* what, F&& launch) {
-  KernelTimer timer(DRIN_KC_ATTN, st);
-  launch();
-  DRIN_CHECK_LAUNCH(what);
-  return DRIN_OK;
-}
-
+// ---- launchers (AttnCall: attention_common.h; the checks are the callers') -----------------------------------------------
 // planes: 4 (the walked tile), or 8 where the owned rows live in LDS too
 int tile_lds_bytes(int dh, int planes) { return planes * kTile * (((dh + 31) & ~31) + 8) * 2 + 256; }
 
@@ -487,118 +479,57 @@ int tile_lds_bytes(int dh, int planes) { return planes * kTile * (((dh + 31) & ~
                      : _i == 2 ? reinterpret_cast<const void*>(KERNEL<256, false>)                             \
                                : reinterpret_cast<const void*>(KERNEL<256, true>);                             \
     DRIN_TRY(ensure_dynamic_lds(opt_in[_i], _k, (lds), "hipFuncSetAttribute(" what ")"));                      \
-    DRIN_TRY(timed(st, what, [&] {                                                                             \
+    DRIN_TRY(timed(DRIN_KC_ATTN, st, what, [&] {                                                               \
       _i == 0 ? go(KERNEL<128, false>) : _i == 1 ? go(KERNEL<128, true>) : _i == 2 ? go(KERNEL<256, false>) : go(KERNEL<256, true>); \
     }));                                                                                                       \
   } while (0)
 
 bool rows16(const void* p, int64_t ld) { return aligned16(p) && ld % 4 == 0; }
 
-int launch_attention_mfma(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv, const int64_t* mask,
-                          float* out, int64_t ldo, float* lse, int B, int H, int Lq, int Lk, int dh, const DropArgs* drop,
-                          hipStream_t st) {
-  const bool vec = dh % 4 == 0 && rows16(q, ldq) && rows16(k, ldk) && rows16(v, ldv), ovec = dh % 4 == 0 && rows16(out, ldo);
+}  // namespace
+
+int launch_attention_mfma(const AttnCall& c, const DropArgs* drop, hipStream_t st) {
+  const int dh = c.dh;
+  const bool vec = dh % 4 == 0 && rows16(c.q, c.ldq) && rows16(c.k, c.ldk) && rows16(c.v, c.ldv);
+  const bool ovec = dh % 4 == 0 && rows16(c.out, c.ldo);
   const float q_scale = kLog2e / sqrtf((float)dh);
-  const dim3 grid((unsigned)cdiv(Lq, dh > 128 ? 32 : 64), (unsigned)H, (unsigned)B);   // Shape::OWN
+  const dim3 grid((unsigned)cdiv(c.Lq, dh > 128 ? 32 : 64), (unsigned)c.H, (unsigned)c.B);   // Shape::OWN
   const int lds = tile_lds_bytes(dh, 4);
   const DropArgs da = drop ? *drop : DropArgs{};
   auto go = [&](auto kern) {
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, q, ldq, k, ldk, v, ldv, mask, out, ldo, lse, Lq, Lk, dh, q_scale, (int)vec,
-                       (int)ovec, da);
+    hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, c.q, c.ldq, c.k, c.ldk, c.v, c.ldv, c.mask, c.out, c.ldo, c.lse, c.Lq, c.Lk, dh,
+                       q_scale, (int)vec, (int)ovec, da);
   };
   DRIN_MFMA_PICK(k_attention_mfma, dh > 128, drop != nullptr, lds, "k_attention_mfma", go);
   return DRIN_OK;
 }
 
-int launch_attention_mfma_bwd(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv,
-                              const int64_t* mask, const float* out, int64_t ldo, const float* lse, const float* dout, int64_t lddo,
-                              float* dq, int64_t lddq, float* dk, int64_t lddk, float* dv, int64_t lddv, float* delta, int B, int H,
-                              int Lq, int Lk, int dh, const DropArgs* drop, hipStream_t st) {
-  const bool vec = dh % 4 == 0 && rows16(q, ldq) && rows16(k, ldk) && rows16(v, ldv) && rows16(dout, lddo);
+int launch_attention_mfma_bwd(const AttnCall& c, const DropArgs* drop, hipStream_t st) {
+  const int dh = c.dh;
+  const bool vec = dh % 4 == 0 && rows16(c.q, c.ldq) && rows16(c.k, c.ldk) && rows16(c.v, c.ldv) && rows16(c.dout, c.lddo);
   const float inv_sqrt = 1.0f / sqrtf((float)dh), q_scale = kLog2e * inv_sqrt;
   const bool wide = dh > 128;
   const int lds = tile_lds_bytes(dh, wide ? 8 : 4), own = wide ? 32 : 64;   // Shape::OWN_LDS, Shape::OWN
   const DropArgs da = drop ? *drop : DropArgs{};
-  DRIN_TRY(launch_attention_bwd_delta(out, ldo, dout, lddo, delta, B, H, Lq, dh, st));
-  if (dq != nullptr) {
-    const dim3 grid((unsigned)cdiv(Lq, own), (unsigned)H, (unsigned)B);
-    const bool ovec = dh % 4 == 0 && rows16(dq, lddq);
+  DRIN_TRY(launch_attention_bwd_delta(c, st));
+  if (c.dq != nullptr) {
+    const dim3 grid((unsigned)cdiv(c.Lq, own), (unsigned)c.H, (unsigned)c.B);
+    const bool ovec = dh % 4 == 0 && rows16(c.dq, c.lddq);
     auto go = [&](auto kern) {
-      hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, q, ldq, k, ldk, v, ldv, mask, lse, dout, lddo, delta, dq, lddq, Lq, Lk, dh,
-                         q_scale, inv_sqrt, (int)vec, (int)ovec, da);
+      hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, c.q, c.ldq, c.k, c.ldk, c.v, c.ldv, c.mask, c.lse, c.dout, c.lddo, c.delta,
+                         c.dq, c.lddq, c.Lq, c.Lk, dh, q_scale, inv_sqrt, (int)vec, (int)ovec, da);
     };
     DRIN_MFMA_PICK(k_attention_mfma_bwd_dq, wide, drop != nullptr, lds, "k_attention_mfma_bwd_dq", go);
   }
-  if (dk == nullptr) return DRIN_OK;
-  const dim3 grid((unsigned)cdiv(Lk, own), (unsigned)H, (unsigned)B);
-  const bool ovec = dh % 4 == 0 && rows16(dk, lddk) && rows16(dv, lddv);
+  if (c.dk == nullptr) return DRIN_OK;
+  const dim3 grid((unsigned)cdiv(c.Lk, own), (unsigned)c.H, (unsigned)c.B);
+  const bool ovec = dh % 4 == 0 && rows16(c.dk, c.lddk) && rows16(c.dv, c.lddv);
   auto go = [&](auto kern) {
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, q, ldq, k, ldk, v, ldv, mask, lse, dout, lddo, delta, dk, lddk, dv, lddv, Lq, Lk,
-                       dh, q_scale, inv_sqrt, (int)vec, (int)ovec, da);
+    hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, c.q, c.ldq, c.k, c.ldk, c.v, c.ldv, c.mask, c.lse, c.dout, c.lddo, c.delta, c.dk,
+                       c.lddk, c.dv, c.lddv, c.Lq, c.Lk, dh, q_scale, inv_sqrt, (int)vec, (int)ovec, da);
   };
   DRIN_MFMA_PICK(k_attention_mfma_bwd_dkv, wide, drop != nullptr, lds, "k_attention_mfma_bwd_dkv", go);
   return DRIN_OK;
 }
 
-int check_strides(const char* who, int64_t E, const char* const* names, const int64_t* lds, const bool* used, int n) {
-  for (int i = 0; i < n; ++i)
-    if (used[i] && lds[i] < E) {
-      set_error("%s: row stride %s = %lld must be >= heads * head_dim = %lld", who, names[i], (long long)lds[i], (long long)E);
-      return DRIN_E_SHAPE;
-    }
-  return DRIN_OK;
-}
-
-}  // namespace
 }  // namespace drin
-
-using namespace drin;
-
-int drin_attention_mfma_fwd(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv,
-                            const int64_t* key_mask, float* out, int64_t ldo, float* lse, int32_t batch, int32_t num_heads,
-                            int32_t q_len, int32_t k_len, int32_t head_dim, float p, uint64_t seed, uint64_t call, void* stream) {
-  const char* who = "drin_attention_mfma_fwd";
-  DropArgs drop;
-  bool use;
-  DRIN_TRY(dropout_args(who, p, seed, call, &drop, &use));
-  DRIN_TRY(check_attention_shape(batch, num_heads, q_len, k_len, head_dim));
-  if (!q || !k || !v || !out) {
-    set_error("%s: q / k / v / out is NULL", who);
-    return DRIN_E_NULL;
-  }
-  const char* const names[] = {"ldq", "ldk", "ldv", "ldo"};
-  const int64_t lds[] = {ldq, ldk, ldv, ldo};
-  const bool used[] = {true, true, true, true};
-  DRIN_TRY(check_strides(who, (int64_t)num_heads * head_dim, names, lds, used, 4));
-  DRIN_BIND_DEVICE(stream, out, who);
-  return launch_attention_mfma(q, ldq, k, ldk, v, ldv, key_mask, out, ldo, lse, batch, num_heads, q_len, k_len, head_dim,
-                               use ? &drop : nullptr, (hipStream_t)stream);
-}
-
-int drin_attention_mfma_bwd(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv,
-                            const int64_t* key_mask, const float* out, int64_t ldo, const float* lse, const float* dout, int64_t lddo,
-                            float* dq, int64_t lddq, float* dk, int64_t lddk, float* dv, int64_t lddv, float* delta_scratch,
-                            int32_t batch, int32_t num_heads, int32_t q_len, int32_t k_len, int32_t head_dim, float p, uint64_t seed,
-                            uint64_t call, void* stream) {
-  const char* who = "drin_attention_mfma_bwd";
-  DropArgs drop;
-  bool use;
-  DRIN_TRY(dropout_args(who, p, seed, call, &drop, &use));
-  DRIN_TRY(check_attention_shape(batch, num_heads, q_len, k_len, head_dim));
-  if (!q || !k || !v || !out || !lse || !dout || !delta_scratch) {
-    set_error("%s: q / k / v / out / lse / dout / delta_scratch is NULL", who);
-    return DRIN_E_NULL;
-  }
-  if ((dk == nullptr) != (dv == nullptr)) {
-    set_error("%s: dk and dv are both given or both NULL (dk %s, dv %s)", who, dk ? "given" : "NULL", dv ? "given" : "NULL");
-    return DRIN_E_NULL;
-  }
-  const char* const names[] = {"ldq", "ldk", "ldv", "ldo", "lddo", "lddq", "lddk", "lddv"};
-  const int64_t lds[] = {ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv};
-  const bool used[] = {true, true, true, true, true, dq != nullptr, dk != nullptr, dv != nullptr};
-  DRIN_TRY(check_strides(who, (int64_t)num_heads * head_dim, names, lds, used, 8));
-  if (!dq && !dk) return DRIN_OK;
-  DRIN_BIND_DEVICE(stream, delta_scratch, who);
-  return launch_attention_mfma_bwd(q, ldq, k, ldk, v, ldv, key_mask, out, ldo, lse, dout, lddo, dq, lddq, dk, lddk, dv, lddv,
-                                   delta_scratch, batch, num_heads, q_len, k_len, head_dim, use ? &drop : nullptr, (hipStream_t)stream);
-}

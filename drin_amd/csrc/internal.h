@@ -35,6 +35,14 @@ struct KernelTimer {
   int slot;
   hipStream_t stream;
 };
+// the launches of `launch` under a KernelTimer of class `cls`, then the launch check
+template <typename F>
+int timed(int cls, hipStream_t st, const char* what, F&& launch) {
+  KernelTimer timer(cls, st);
+  launch();
+  DRIN_CHECK_LAUNCH(what);
+  return DRIN_OK;
+}
 
 // The device a call runs on is the device of the caller's STREAM, not whatever device happens to be current on the calling
 // thread: every entry point that launches opens a DeviceScope first.  It asks the stream (hipStreamGetDevice) - or, for the NULL
@@ -129,6 +137,12 @@ int launch_entity_token_mean_bf16(const void* feat, const int64_t* mask, float* 
 int launch_cosine_rows(const float* x, const float* y, int64_t y_stride, float* out, int B, int N, int D, float eps,
                        float scale, hipStream_t st, const int64_t* y_index = nullptr, const float* sim1 = nullptr,
                        const float* sim2 = nullptr, float* out1 = nullptr, float* out2 = nullptr, float div = 1.0f);
+// the GHMFC row kernels (ghmfc_rows.hip) that the scoring forward composes (ghmfc_forward.hip)
+constexpr int kLnMaxWidth = 2048;   // Row<8>
+int launch_layernorm_res(const float* x, const float* res, const float* gamma, const float* beta, float* y, int64_t rows, int E,
+                         float eps, hipStream_t st, float* mean = nullptr, float* rstd = nullptr);
+int launch_seq_max(const float* x, float* out, int B, int S, int E, hipStream_t st, int* idx = nullptr);
+int launch_gate_mix(const float* tl, const float* vl, const float* ws, const float* bs, float* out, int B, int D, hipStream_t st);
 // model.py:84-92: weighted object-pair similarity
 int launch_miei(const float* mobj, const float* mscore, const float* eobj, const float* escore, float* out, int B,
                 int N, int Km, int Ke, int R, float cos_eps, float miei_eps, float scale, hipStream_t st,
@@ -532,6 +546,6 @@ inline int regions_hold(const char* layout, const Region* r, int n, size_t total
 int fused_layout_selfcheck(const drin_config& c);    // FusedLayout, Prepared (fused_forward.hip)
 int cached_layout_selfcheck(const drin_config& c);   // CachedLayout (entity_cache.hip)
 int melhi_layout_selfcheck(int B, int N, int D, int R, int L);           // MelhiLayout (melhi_kernels.hip)
-int ghmfc_layout_selfcheck(int B, int N, int D, int R, int L, int P, int T);   // GhmfcLayout (ghmfc_kernels.hip)
+int ghmfc_layout_selfcheck(int B, int N, int D, int R, int L, int P, int T);   // GhmfcLayout (ghmfc_forward.hip)
 
 }  // namespace drin

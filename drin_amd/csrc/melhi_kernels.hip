@@ -413,14 +413,6 @@ int check_ptrs(const drin_melhi_batch* bt, const drin_melhi_params* p) {
   return DRIN_OK;
 }
 
-template <typename F>
-int timed(int cls, hipStream_t st, const char* what, F&& launch) {
-  KernelTimer timer(cls, st);
-  launch();
-  DRIN_CHECK_LAUNCH(what);
-  return DRIN_OK;
-}
-
 }  // namespace
 
 int melhi_layout_selfcheck(int batch, int n, int d, int r, int tokens) {

@@ -15,6 +15,7 @@ import torch
 from torch import nn
 
 from . import _lib
+from ._lib import _ptr, _stream
 
 PRECISIONS = {"bf16x3": _lib.PREC_BF16X3, "f32": _lib.PREC_F32}
 
@@ -56,10 +57,6 @@ def config_from_reference_args(args) -> GhmfcConfig:
                        image_dim=args.resnet_embed_dim, mention_tokens=args.max_mention_sentence_len,
                        image_regions=args.resnet_num_region, num_heads=getattr(args, "transformer_num_heads", 8),
                        entity_tokens=getattr(args, "max_entity_attr_token_len", 64))
-
-
-def _ptr(t) -> C.c_void_p:
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
 class _CrossAttention(nn.Module):
@@ -182,8 +179,8 @@ class Model(nn.Module):
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         scores = torch.empty(B, cfg.num_candidates, dtype=torch.float32, device=dev)
         mention = torch.empty(B, cfg.embed_dim, dtype=torch.float32, device=dev)
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(lib.drin_ghmfc_forward(C.byref(c), C.byref(bt), C.byref(pc), _ptr(ws), nbytes, _ptr(scores), _ptr(mention), stream))
+        _lib.check(lib.drin_ghmfc_forward(C.byref(c), C.byref(bt), C.byref(pc), _ptr(ws), nbytes, _ptr(scores), _ptr(mention),
+                                          _stream(dev)))
         return scores if want_scores else mention
 
     def forward(self, batch) -> torch.Tensor:

@@ -8,9 +8,50 @@ from __future__ import annotations
 
 import torch
 
-from .attention import CORES, PRECISIONS, DropoutStream, MultiheadAttention, _linear
+from .attention import PRECISIONS, DropoutStream, MultiheadAttention, _check_core, _linear
 from .ghmfc import GhmfcConfig, Model, _MentionEncoder
 from .row_ops import cosine_rows, entity_token_mean, gate_mix, layer_norm_res, seq_max
+
+
+# ---- what TrainableModel and drin_amd.ghmfc_variants.VariantModel share ---------------------------------------------
+def check_setup(precision: str, core: str, dropout: float) -> float:
+    """The constructor arguments of both models, refused before any module is built; returns the rate as a float."""
+    if precision not in PRECISIONS:
+        raise ValueError(f"precision {precision!r} not in {sorted(PRECISIONS)}")
+    _check_core(core)
+    if not 0.0 <= dropout < 1.0:
+        raise ValueError(f"dropout {dropout} is not in [0, 1)")
+    return float(dropout)
+
+
+def attention_factory(precision: str, stream: DropoutStream, core: str):
+    """nn.MultiheadAttention's arguments -> a `MultiheadAttention` of the model's precision, dropout stream and core."""
+    def attention(*args, **kwargs):
+        return MultiheadAttention(*args, precision=precision, dropout_stream=stream, core=core, **kwargs)
+    return attention
+
+
+def cross_attention(ca, seq_a, drop_a, seq_b, drop_b, precision: str, eps: float) -> torch.Tensor:
+    """CrossAttention(seq_a, mask_a, seq_b, mask_b) of ghmfc.py:114-128: [B, La, E].  drop_a / drop_b: bool key padding masks
+    (True = drop the key) or None, which keeps every key."""
+    B, La, E = seq_a.shape
+    prec, ln = PRECISIONS[precision], ca.layernorms
+    ffn = lambda m, t: _linear(t.view(B * La, E), m.weight, m.bias, prec).view(B, La, E)   # noqa: E731
+    x, _ = ca.a2b_attention(seq_a, seq_b, seq_b, key_padding_mask=drop_b)
+    x = layer_norm_res(x, None, ln[0].weight, ln[0].bias, eps)
+    x = layer_norm_res(ffn(ca.a2b_ffn, x), x, ln[1].weight, ln[1].bias, eps)
+    y, _ = ca.b2a_attention(x, seq_a, seq_a, key_padding_mask=drop_a)
+    y = layer_norm_res(y, None, ln[2].weight, ln[2].bias, eps)
+    return layer_norm_res(ffn(ca.b2a_ffn, y), y, ln[3].weight, ln[3].bias, eps)
+
+
+def entity_scores(mention, ef, emask, final, cfg: GhmfcConfig, precision: str) -> torch.Tensor:
+    """EntityEncoder and the cosine (ghmfc.py:237-250, :297-298): scores [B, N] of mention [B, D] against the candidates.
+    ef: [B, N, D], or [B, N, T, D] with emask [B, N, T] (WikiMEL: the token mean first); final: the encoder's last linear."""
+    B, N, D = mention.shape[0], cfg.num_candidates, cfg.embed_dim
+    ent = entity_token_mean(ef, emask) if emask is not None else ef
+    ent = _linear(ent.view(B * N, D), final.weight, final.bias, PRECISIONS[precision]).view(B, N, D)
+    return cosine_rows(mention, ent, cfg.cosine_eps)
 
 
 class TrainableModel(Model):
@@ -30,12 +71,9 @@ class TrainableModel(Model):
 
     def __init__(self, cfg: GhmfcConfig | None = None, precision: str = "bf16x3", dropout: float = 0.1, seed: int = 0,
                  core: str = "fma"):
-        if not 0.0 <= dropout < 1.0:
-            raise ValueError(f"dropout {dropout} is not in [0, 1)")
-        if core not in CORES:
-            raise ValueError(f"core {core!r} not in {list(CORES)}")
+        dropout = check_setup(precision, core, dropout)
         # read by _make_mention_encoder, which the parent's __init__ calls: set ahead of nn.Module.__init__, past its __setattr__
-        object.__setattr__(self, "_attention_setup", (float(dropout), DropoutStream(seed), precision, core))
+        object.__setattr__(self, "_attention_setup", (dropout, DropoutStream(seed), precision, core))
         super().__init__(cfg, precision)
         self.dropout, self.dropout_stream = self._attention_setup[:2]
         self.core = core
@@ -43,41 +81,22 @@ class TrainableModel(Model):
 
     def _make_mention_encoder(self, cfg: GhmfcConfig):
         dropout, stream, precision, core = self._attention_setup
-
-        def attention(*args, **kwargs):
-            return MultiheadAttention(*args, precision=precision, dropout_stream=stream, core=core, **kwargs)
-        return _MentionEncoder(cfg, dropout, attention)
-
-    def _cross_attention_max(self, ca, seq_a, drop_a, seq_b, drop_b):
-        """CrossAttention(seq_a, seq_b) and the max over seq_a's positions (ghmfc.py:114-128, :143 / :145)."""
-        B, La, E = seq_a.shape
-        prec, eps, ln = PRECISIONS[self.precision], self.cfg.layer_norm_eps, ca.layernorms
-        ffn = lambda m, t: _linear(t.view(B * La, E), m.weight, m.bias, prec).view(B, La, E)   # noqa: E731
-        x, _ = ca.a2b_attention(seq_a, seq_b, seq_b, key_padding_mask=drop_b)
-        x = layer_norm_res(x, None, ln[0].weight, ln[0].bias, eps)
-        x = layer_norm_res(ffn(ca.a2b_ffn, x), x, ln[1].weight, ln[1].bias, eps)
-        y, _ = ca.b2a_attention(x, seq_a, seq_a, key_padding_mask=drop_a)
-        y = layer_norm_res(y, None, ln[2].weight, ln[2].bias, eps)
-        y = layer_norm_res(ffn(ca.b2a_ffn, y), y, ln[3].weight, ln[3].bias, eps)
-        return seq_max(y)
+        return _MentionEncoder(cfg, dropout, attention_factory(precision, stream, core))
 
     def _run(self, batch, want_scores: bool):
         if not self.training:
             return self._score(batch, want_scores)
         mf, mmask, mimage, ef, emask, tokens = self._batch_tensors(batch)
         cfg, prec = self.cfg, PRECISIONS[self.precision]
-        B, N, D = mf.shape[0], cfg.num_candidates, cfg.embed_dim
         f = self.mention_encoder.intermediate_layer
         padding = mmask == 0                                                   # nn.MultiheadAttention: True = drop the key
-        t, idx_t = self._cross_attention_max(f.t2v_attention, mf, padding, mimage, None)
-        v, idx_v = self._cross_attention_max(f.v2t_attention, mimage, None, mf, padding)
+        # CrossAttention and the max over seq_a's positions (ghmfc.py:143 / :145)
+        t, idx_t = seq_max(cross_attention(f.t2v_attention, mf, padding, mimage, None, self.precision, cfg.layer_norm_eps))
+        v, idx_v = seq_max(cross_attention(f.v2t_attention, mimage, None, mf, padding, self.precision, cfg.layer_norm_eps))
         self.max_indices = {"text": idx_t, "image": idx_v}
         tl = _linear(t, f.text_linear.weight, f.text_linear.bias, prec)
         vl = _linear(v, f.image_linear.weight, f.image_linear.bias, prec)
         mention = gate_mix(tl, vl, f.score_linear.weight, f.score_linear.bias)
         if not want_scores:
             return mention
-        ent = entity_token_mean(ef, emask) if tokens else ef
-        final = self.entity_encoder.final_layer
-        ent = _linear(ent.view(B * N, D), final.weight, final.bias, prec).view(B, N, D)
-        return cosine_rows(mention, ent, cfg.cosine_eps)
+        return entity_scores(mention, ef, emask, self.entity_encoder.final_layer, cfg, self.precision)

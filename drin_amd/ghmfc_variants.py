@@ -15,10 +15,10 @@ from dataclasses import dataclass, fields
 import torch
 from torch import nn
 
-from .attention import CORES, PRECISIONS, DropoutStream, MultiheadAttention, _linear, multihead_attention_forward
+from .attention import PRECISIONS, DropoutStream, _linear, multihead_attention_forward
 from .ghmfc import GhmfcConfig, _CrossAttention, _EntityEncoder
-from .ghmfc_train import TrainableModel
-from .row_ops import act_dropout, cosine_rows, entity_token_mean, layer_norm_res, seq_max, span_mean
+from .ghmfc_train import TrainableModel, attention_factory, check_setup, cross_attention, entity_scores
+from .row_ops import act_dropout, layer_norm_res, seq_max, span_mean
 
 FINAL_LAYERS = ("multimodal", "transformer", "linear", "none")
 ATTENTIONS = ("bi", "text")
@@ -159,19 +159,10 @@ class VariantModel(nn.Module):
     def __init__(self, cfg: VariantConfig | None = None, precision: str = "bf16x3", dropout: float = 0.1, seed: int = 0,
                  core: str = "fma"):
         super().__init__()
-        if precision not in PRECISIONS:
-            raise ValueError(f"precision {precision!r} not in {sorted(PRECISIONS)}")
-        if core not in CORES:
-            raise ValueError(f"core {core!r} not in {list(CORES)}")
-        if not 0.0 <= dropout < 1.0:
-            raise ValueError(f"dropout {dropout} is not in [0, 1)")
-        self.cfg, self.precision, self.dropout, self.core = cfg, precision, float(dropout), core
-        self.dropout_stream = stream = DropoutStream(seed)
+        self.cfg, self.precision, self.dropout, self.core = cfg, precision, check_setup(precision, core, dropout), core
+        self.dropout_stream = DropoutStream(seed)
         self.max_indices = {}
-
-        def attention(*args, **kwargs):
-            return MultiheadAttention(*args, precision=precision, dropout_stream=stream, core=core, **kwargs)
-        self.mention_encoder = _VariantMentionEncoder(cfg, self.dropout, attention)
+        self.mention_encoder = _VariantMentionEncoder(cfg, self.dropout, attention_factory(precision, self.dropout_stream, core))
         self.entity_encoder = _EntityEncoder(cfg)
 
     # ---- the batch ---------------------------------------------------------------------------------------------
@@ -233,19 +224,6 @@ class VariantModel(nn.Module):
             x = layer_norm_res(h.view(B, L, D), x, layer.norm2.weight, layer.norm2.bias, layer.norm2.eps)
         return x
 
-    def _cross_attention(self, seq_a, drop_a, seq_b):
-        """CrossAttention(seq_a, mask_a, seq_b) of ghmfc.py:114-128 (every key of seq_b is kept)"""
-        ca = self.mention_encoder.intermediate_layer
-        B, La, E = seq_a.shape
-        prec, eps, ln = PRECISIONS[self.precision], self.cfg.layer_norm_eps, ca.layernorms
-        ffn = lambda m, t: _linear(t.view(B * La, E), m.weight, m.bias, prec).view(B, La, E)   # noqa: E731
-        x, _ = ca.a2b_attention(seq_a, seq_b, seq_b, key_padding_mask=None)
-        x = layer_norm_res(x, None, ln[0].weight, ln[0].bias, eps)
-        x = layer_norm_res(ffn(ca.a2b_ffn, x), x, ln[1].weight, ln[1].bias, eps)
-        y, _ = ca.b2a_attention(x, seq_a, seq_a, key_padding_mask=drop_a)
-        y = layer_norm_res(y, None, ln[2].weight, ln[2].bias, eps)
-        return layer_norm_res(ffn(ca.b2a_ffn, y), y, ln[3].weight, ln[3].bias, eps)
-
     def _mention(self, mf, mmask, begin, end, mimage):
         cfg, prec = self.cfg, PRECISIONS[self.precision]
         name = cfg.mention_final_layer_name
@@ -253,7 +231,8 @@ class VariantModel(nn.Module):
         if name == "transformer":
             x = self._transformer(mf, padding)
         elif name == "multimodal":
-            x = self._cross_attention(mf, padding, mimage)
+            x = cross_attention(self.mention_encoder.intermediate_layer, mf, padding, mimage, None, self.precision,
+                                cfg.layer_norm_eps)                            # every key of the image is kept
         else:
             x = mf
         self.max_indices = {}
@@ -274,15 +253,10 @@ class VariantModel(nn.Module):
 
     def _compose(self, batch, want_scores: bool):
         mf, mmask, begin, end, mimage, ef, emask = self._batch_tensors(batch)
-        cfg, prec = self.cfg, PRECISIONS[self.precision]
-        B, N, D = mf.shape[0], cfg.num_candidates, cfg.embed_dim
         mention = self._mention(mf, mmask, begin, end, mimage)
         if not want_scores:
             return mention
-        ent = entity_token_mean(ef, emask) if emask is not None else ef
-        final = self.entity_encoder.final_layer
-        ent = _linear(ent.view(B * N, D), final.weight, final.bias, prec).view(B, N, D)
-        return cosine_rows(mention, ent, cfg.cosine_eps)
+        return entity_scores(mention, ef, emask, self.entity_encoder.final_layer, self.cfg, self.precision)
 
     def forward(self, batch) -> torch.Tensor:
         return self._run(batch, True)

@@ -16,6 +16,7 @@ import torch
 from torch import nn
 
 from . import _lib
+from ._lib import _ptr, _stream
 
 PRECISIONS = {"bf16x3": _lib.PREC_BF16X3, "f32": _lib.PREC_F32}
 
@@ -75,10 +76,6 @@ def orders_and_lengths(start, end, mention_mask, L: int) -> Tuple[np.ndarray, np
     return np.ascontiguousarray(order), np.ascontiguousarray(lengths)
 
 
-def _ptr(t) -> C.c_void_p:
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
 class _Call:
     """One forward (+ backward) through the library: the C structs, the host order arrays and the kept workspace."""
 
@@ -102,14 +99,11 @@ class _Call:
         self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=self.device)
         self.B, self.N = B, cfg.num_candidates
 
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def forward(self) -> torch.Tensor:
         scores = torch.empty(self.B, self.N, dtype=torch.float32, device=self.device)
         _lib.check(self.lib.drin_melhi_forward(C.byref(self.cfg), C.byref(self.batch), C.byref(self.params),
                                                self.order.ctypes.data_as(C.c_void_p), self.lengths.ctypes.data_as(C.c_void_p),
-                                               _ptr(self.ws), self.ws_bytes, _ptr(scores), self._stream()))
+                                               _ptr(self.ws), self.ws_bytes, _ptr(scores), _stream(self.device)))
         return scores
 
     def backward(self, grad_scores: torch.Tensor, needs: Sequence[bool]) -> list:
@@ -119,7 +113,7 @@ class _Call:
         g = grad_scores.detach().to(torch.float32).contiguous()
         _lib.check(self.lib.drin_melhi_backward(C.byref(self.cfg), C.byref(self.batch), C.byref(self.params),
                                                 self.order.ctypes.data_as(C.c_void_p), self.lengths.ctypes.data_as(C.c_void_p),
-                                                _ptr(self.ws), self.ws_bytes, _ptr(g), C.byref(gc), self._stream()))
+                                                _ptr(self.ws), self.ws_bytes, _ptr(g), C.byref(gc), _stream(self.device)))
         return grads
 
 

@@ -19,14 +19,13 @@ _FIELDS = ("private_segment_fixed_size", "vgpr_count", "vgpr_spill_count", "sgpr
 
 
 def kernel_resources(obj_dir: str | None = None) -> List[Dict]:
-    """One dict per kernel of every object under `drin_amd/csrc/build/`: demangled-ish name, source object, and the note's
+    """One dict per kernel of the objects of `build.SOURCES` under `drin_amd/csrc/build/` (an object left behind by a source
+    file that is gone is not the library's): demangled-ish name, source object, and the note's
     `.private_segment_fixed_size` (scratch bytes per lane), `.vgpr_count`, `.vgpr_spill_count`, `.sgpr_spill_count`, ..."""
     obj_dir = obj_dir or os.path.join(_build.CSRC, "build")
     out: List[Dict] = []
     with tempfile.TemporaryDirectory() as tmp:
-        for name in sorted(os.listdir(obj_dir)):
-            if not name.endswith(".o"):
-                continue
+        for name in sorted(src.replace(".hip", ".o") for src in _build.SOURCES):
             fat, co = os.path.join(tmp, name + ".fat"), os.path.join(tmp, name + ".co")
             r = subprocess.run([f"{LLVM}/llvm-objcopy", f"--dump-section=.hip_fatbin={fat}", os.path.join(obj_dir, name)],
                                capture_output=True)

@@ -14,19 +14,10 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
-from .attention import _ptr, _require_gpu_f32, _stream
+from ._lib import _ptr, _scratch, _stream
+from .attention import _require_gpu_f32
 
-_scratch = {}
-
-
-def _row_scratch(device, stream_id: int, floats: int) -> torch.Tensor:
-    """Scratch of the ordered column sums, one per (device, stream) and grown to the largest need: calls on one stream run
-    in order, so they share it."""
-    key = (device, stream_id)
-    buf = _scratch.get(key)
-    if buf is None or buf.numel() < floats:
-        buf = _scratch[key] = torch.empty(max(floats, 1), dtype=torch.float32, device=device)
-    return buf
+_row_pool = {}                             # _lib._scratch: the ordered column sums of the row backwards
 
 
 def _rows(name: str, t: torch.Tensor) -> torch.Tensor:
@@ -67,7 +58,7 @@ class _LayerNormRes(torch.autograd.Function):
         dbeta = torch.empty_like(gamma) if need_b else None
         stream = _stream(x.device)
         floats = lib.drin_layernorm_res_bwd_scratch_floats(rows, E) if (need_g or need_b) else 0
-        scratch = _row_scratch(x.device, stream.value or 0, floats) if floats else None
+        scratch = _scratch(_row_pool, x.device, stream.value or 0, floats) if floats else None
         _lib.check(lib.drin_layernorm_res_bwd(_ptr(x), _ptr(res), _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(dy), _ptr(dh), _ptr(dgamma),
                                               _ptr(dbeta), _ptr(scratch), floats, rows, E, stream))
         return dh if need_x else None, dh if (need_res and res is not None) else None, dgamma, dbeta, None
@@ -133,7 +124,7 @@ class _GateMix(torch.autograd.Function):
         dbs = torch.empty(2, dtype=torch.float32, device=tl.device) if need_b else None
         stream = _stream(tl.device)
         floats = lib.drin_gate_mix_bwd_scratch_floats(B, D) if (need_w or need_b) else 0
-        scratch = _row_scratch(tl.device, stream.value or 0, floats) if floats else None
+        scratch = _scratch(_row_pool, tl.device, stream.value or 0, floats) if floats else None
         _lib.check(lib.drin_gate_mix_bwd(_ptr(tl), _ptr(vl), _ptr(ws), _ptr(bs), _ptr(dout), _ptr(dtl), _ptr(dvl), _ptr(dws), _ptr(dbs),
                                          _ptr(scratch), floats, B, D, stream))
         return dtl if need_t else None, dvl if need_v else None, dws, dbs
@@ -168,7 +159,7 @@ class _CosineRows(torch.autograd.Function):
         dout = dout.contiguous()
         dx, dy = torch.empty_like(x), torch.empty_like(y)
         stream = _stream(x.device)
-        scratch = _row_scratch(x.device, stream.value or 0, 3 * B * N)
+        scratch = _scratch(_row_pool, x.device, stream.value or 0, 3 * B * N)
         _lib.check(_lib.load().drin_cosine_rows_bwd(_ptr(x), _ptr(y), _ptr(dout), _ptr(dx), _ptr(dy), _ptr(scratch), scratch.numel(), B, N, D,
                                                     ctx.eps, stream))
         return dx if need_x else None, dy if need_y else None, None

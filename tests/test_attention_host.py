@@ -1,6 +1,6 @@
 """The trainable attention without a GPU: the restatement (tests/attention_restatement.py) against torch's own
 nn.MultiheadAttention in float64, the module's parameters against torch's under one seed, every refusal of
-drin_amd.attention.MultiheadAttention, and the host-side validation of drin_attention_train_fwd / drin_attention_bwd."""
+drin_amd.attention.MultiheadAttention, and the host-side validation of every attention entry point of both cores."""
 import ctypes as C
 
 import pytest
@@ -98,30 +98,68 @@ def test_refusals():
         d(x, x, x)
 
 
-def test_new_entry_points_validate_on_host():
+# entry-point family -> (forward, backward or None, takes a dropout rate, the forward's lse: "required" | "optional" | None)
+FAMILIES = {"plain": ("drin_attention", None, False, None),
+            "train": ("drin_attention_train_fwd", "drin_attention_bwd", False, "required"),
+            "dropout": ("drin_attention_dropout_fwd", "drin_attention_dropout_bwd", True, "required"),
+            "mfma": ("drin_attention_mfma_fwd", "drin_attention_mfma_bwd", True, "optional")}
+
+
+@pytest.mark.parametrize("family", sorted(FAMILIES))
+def test_entry_points_validate_on_host(family):
+    """Every check of the attention front (csrc/attention_api.hip) through every entry point that has it: the same code and an
+    error text with the entry point's name, whichever core is behind it."""
     lib = _lib.load()
+    fwd_name, bwd_name, has_rate, fwd_lse = FAMILIES[family]
     one = C.c_void_p(16)   # never dereferenced: every check below fails before a launch
 
-    def fwd(q=one, lse=one, Lk=8, dh=16, ldq=64, ldo=64):
-        return lib.drin_attention_train_fwd(q, ldq, one, 64, one, 64, None, one, ldo, lse, 2, 4, 7, Lk, dh, None)
+    def fwd(q=one, out=one, lse=one, Lk=8, dh=16, ldq=64, ldo=64, p=0.0, B=2, H=4):
+        rate = (p, 1, 2) if has_rate else ()
+        lse = () if fwd_lse is None else (lse,)
+        return getattr(lib, fwd_name)(q, ldq, one, 64, one, 64, None, out, ldo, *lse, B, H, 7, Lk, dh, *rate, None)
 
-    def bwd(q=one, lse=one, dout=one, dq=one, dk=one, dv=one, delta=one, Lk=8, dh=16, ldk=64, lddo=64, lddq=64, lddv=64):
-        return lib.drin_attention_bwd(q, 64, one, ldk, one, 64, None, one, 64, lse, dout, lddo, dq, lddq, dk, 64, dv, lddv, delta,
-                                      2, 4, 7, Lk, dh, None)
+    def bwd(q=one, lse=one, dout=one, dq=one, dk=one, dv=one, delta=one, Lk=8, dh=16, ldk=64, lddo=64, lddq=64, lddv=64, p=0.0, B=2,
+            H=4):
+        rate = (p, 1, 2) if has_rate else ()
+        return getattr(lib, bwd_name)(q, 64, one, ldk, one, 64, None, one, 64, lse, dout, lddo, dq, lddq, dk, 64, dv, lddv, delta,
+                                      B, H, 7, Lk, dh, *rate, None)
 
-    for call in (fwd, bwd):
-        assert call(q=None) == _lib.E_NULL and call(lse=None) == _lib.E_NULL
-        assert call(Lk=0) == _lib.E_SHAPE
-        assert call(Lk=513) == _lib.E_SHAPE and b"k_len" in lib.drin_last_error()
-        assert call(dh=257) == _lib.E_SHAPE and b"head_dim" in lib.drin_last_error()
-    assert fwd(ldq=63) == _lib.E_SHAPE and b"ldq" in lib.drin_last_error()
-    assert fwd(ldo=63) == _lib.E_SHAPE
-    assert bwd(dout=None) == _lib.E_NULL and bwd(delta=None) == _lib.E_NULL
-    assert bwd(ldk=63) == _lib.E_SHAPE and b"ldk" in lib.drin_last_error()
-    assert bwd(lddo=63) == _lib.E_SHAPE and b"lddo" in lib.drin_last_error()
-    assert bwd(lddq=63) == _lib.E_SHAPE and b"lddq" in lib.drin_last_error()
-    assert bwd(lddv=63) == _lib.E_SHAPE and b"lddv" in lib.drin_last_error()
-    assert bwd(dq=None, lddq=0, Lk=513) == _lib.E_SHAPE               # dq may be NULL (its stride is then not read) ...
-    assert bwd(dv=None) == _lib.E_NULL and b"dk and dv" in lib.drin_last_error()   # ... dk without dv may not
-    assert bwd(dk=None) == _lib.E_NULL and b"dk and dv" in lib.drin_last_error()
+    def refused(name, status, code, *words):
+        error = lib.drin_last_error()
+        assert status == code, (name, status, error)
+        for word in (name,) + words:
+            assert word.encode() in error, (name, word, error)
+
+    for name, call in ((fwd_name, fwd),) + (((bwd_name, bwd),) if bwd_name else ()):
+        refused(name, call(q=None), _lib.E_NULL)
+        refused(name, call(Lk=0), _lib.E_SHAPE)
+        refused(name, call(Lk=513), _lib.E_SHAPE, "k_len")
+        refused(name, call(dh=257), _lib.E_SHAPE, "head_dim")
+        for bad in (dict(dh=0), dict(B=0), dict(B=65536), dict(H=65536)):
+            refused(name, call(**bad), _lib.E_SHAPE)
+        if has_rate:
+            for p in (1.0, -0.1, float("nan")):
+                refused(name, call(p=p), _lib.E_SHAPE, "dropout rate")
+            refused(name, call(p=1.0, q=None, Lk=513), _lib.E_SHAPE, "dropout rate")    # the rate is looked at first
+    refused(fwd_name, fwd(out=None), _lib.E_NULL)
+    refused(fwd_name, fwd(ldq=63), _lib.E_SHAPE, "ldq")
+    refused(fwd_name, fwd(ldo=63), _lib.E_SHAPE, "ldo")
+    if fwd_lse == "required":
+        refused(fwd_name, fwd(lse=None), _lib.E_NULL)
+    elif fwd_lse == "optional":                           # accepted: the next check is the one that reports
+        refused(fwd_name, fwd(lse=None, ldo=63), _lib.E_SHAPE, "ldo")
+    if bwd_name is None:
+        return
+    for missing in ("lse", "dout", "delta"):
+        refused(bwd_name, bwd(**{missing: None}), _lib.E_NULL)
+    refused(bwd_name, bwd(ldk=63), _lib.E_SHAPE, "ldk")
+    refused(bwd_name, bwd(lddo=63), _lib.E_SHAPE, "lddo")
+    refused(bwd_name, bwd(lddq=63), _lib.E_SHAPE, "lddq")
+    refused(bwd_name, bwd(lddv=63), _lib.E_SHAPE, "lddv")
+    refused(bwd_name, bwd(dq=None, lddq=0, Lk=513), _lib.E_SHAPE)       # dq may be NULL (its stride is then not read) ...
+    refused(bwd_name, bwd(dq=None, lddq=0, ldk=63), _lib.E_SHAPE, "ldk")
+    refused(bwd_name, bwd(dv=None), _lib.E_NULL, "dk and dv")          # ... dk without dv may not
+    refused(bwd_name, bwd(dk=None), _lib.E_NULL, "dk and dv")
+    assert bwd(dq=None, dk=None, dv=None) == _lib.OK                    # nothing asked for: nothing launched
+    assert bwd(dq=None, dk=None, dv=None, lddq=0, lddv=0) == _lib.OK    # ... and the absent gradients' strides are not read
     assert lib.drin_version() == _lib.ABI_VERSION == 12

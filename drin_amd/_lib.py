@@ -168,6 +168,16 @@ PROBE_GEMM_NT, PROBE_GEMM_NT_BF16X3, PROBE_GEMM_NT_BF16X3_P4, PROBE_GEMM_X3_PLAN
 GEMM_FAMILY = {0: "none", 1: "bf16x3", 2: "bf16x3_p4", 3: "planes", 4: "planes_p4", 5: "f32", 6: "f32_gemv"}
 
 
+MENTION_LINEAR, MENTION_ROWS = 0, 1                                    # drin_mention_encoder
+REPR_AVG_EXTRACT, REPR_MAX_POOL = 0, 1                                 # drin_mention_repr
+MENTION_REPR = {"avg extract": REPR_AVG_EXTRACT, "max pool": REPR_MAX_POOL}   # common/args.py:29's spellings
+
+
+class DrinMentionHeadC(C.Structure):     # drin_mention_head: the settings of the *_head entry points, with the struct's own size
+    _fields_ = [("struct_size", C.c_size_t), ("encoder", C.c_int32), ("representation", C.c_int32), ("encoded", C.c_void_p),
+                ("max_index", C.c_void_p), ("grad_encoded", C.c_void_p)]
+
+
 class DrinTraceC(C.Structure):
     _fields_ = [(n, C.c_void_p * (MAX_LAYERS + 1)) for n in (
         "mention_text_vertex", "mention_image_vertex", "entity_text_vertex", "entity_image_vertex", "edges")]
@@ -282,6 +292,20 @@ EXPORTS = {
                                        C.c_uint64, C.c_void_p]),
     "drin_span_mean_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "drin_span_mean_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "drin_forward_staged_head": (C.c_int, [C.POINTER(DrinConfigC), C.POINTER(DrinBatchC), C.POINTER(DrinParamsC), C.c_void_p,
+                                           C.c_size_t, C.c_void_p, C.c_int, C.POINTER(DrinTraceC), C.c_void_p,
+                                           C.POINTER(DrinMentionHeadC), C.c_void_p]),
+    "drin_backward_head": (C.c_int, [C.POINTER(DrinConfigC), C.POINTER(DrinBatchC), C.POINTER(DrinParamsC), C.c_void_p,
+                                     C.c_size_t, C.c_void_p, C.POINTER(DrinParamGradsC), C.POINTER(DrinInputGradsC), C.c_void_p,
+                                     C.POINTER(DrinMentionHeadC), C.c_void_p]),
+    "drin_forward_prepared_head": (C.c_int, [C.POINTER(DrinConfigC), C.POINTER(DrinBatchC), C.POINTER(DrinParamsC), C.c_void_p,
+                                             C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(DrinMentionHeadC), C.c_void_p]),
+    # (raw, raw_dtype, encoded, start, end, representation, edge_row, vertex_row, max_index, batch, seq_len, width, stream)
+    "drin_mention_rows_fwd": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    # (g_edge_row, g_vertex_row, start, end, max_index, representation, has_encoded, grad_raw, grad_encoded, batch, seq_len, width, stream)
+    "drin_mention_rows_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                        C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "drin_profile_begin": (C.c_int, [C.c_int]),
     "drin_profile_end": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "drin_kernel_class_name": (C.c_char_p, [C.c_int]),

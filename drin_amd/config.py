@@ -32,6 +32,16 @@ class DrinConfig:
     gcn_edge_enabled: Tuple[float, float, float, float] = (1, 1, 1, 1)
     gcn_vertex_activation: str = "gelu"
     gcn_edge_activation: str = "sigmoid"
+    # the mention-text vertex encoder (args.py:28-29; baselines/ghmfc.py:152-199 with inline_bert=False)
+    mention_final_layer_name: str = "linear"                 # "linear" | "transformer" | "none"
+    mention_final_representation: str = "avg extract"        # "avg extract" | "max pool" (the text-text edge's row too, model.py:58);
+    #                                                          "linear" never reads it: forced to avg extract (args.py:12-13)
+    # the transformer encoder of "transformer" (args.py:60-64)
+    transformer_num_layers: int = 8
+    transformer_num_heads: int = 8
+    transformer_ffn_hidden_size: int = 512
+    transformer_ffn_activation: str = "gelu"
+    transformer_dropout: float = 0.1
     # train (args.py:104-126)
     seed: int = 0
     num_epoch: int = 30
@@ -57,6 +67,11 @@ class DrinConfig:
         """WikiMEL delivers entity text as token features + mask (baselines/ghmfc.py:241-249)."""
         return self.dataset_name == "wikimel"
 
+    @property
+    def linear_mention_encoder(self) -> bool:
+        """The `AvgLinear` encoder (args.py:28's default): what `drin_amd.model.Model` itself runs."""
+        return self.mention_final_layer_name == "linear"
+
     def with_(self, **kw) -> "DrinConfig":
         return replace(self, **kw)
 
@@ -78,19 +93,42 @@ class DrinConfig:
             raise ValueError("gcn_embed_dim must equal bert_embed_dim (args.py:38-39 force the output dims)")
         if len(self.gcn_edge_enabled) != 4:
             raise ValueError("gcn_edge_enabled has one entry per edge type (tt, ti, it, ii)")
+        if self.mention_final_layer_name not in MENTION_FINAL_LAYERS:
+            raise ValueError(f"unknown mention_final_layer_name {self.mention_final_layer_name!r}: one of {MENTION_FINAL_LAYERS} "
+                             "(args.py:28; 'multimodal' belongs to model_type 'ghmfc')")
+        if self.mention_final_representation not in MENTION_REPRESENTATIONS:
+            raise ValueError(f"unknown mention_final_representation {self.mention_final_representation!r}: one of {MENTION_REPRESENTATIONS}")
+        if self.mention_final_layer_name == "transformer":
+            if self.transformer_ffn_activation not in ("gelu", "relu"):
+                raise NotImplementedError(f"transformer_ffn_activation {self.transformer_ffn_activation!r}: built are gelu, relu")
+            if (self.transformer_num_layers < 1 or self.transformer_num_heads < 1 or self.bert_embed_dim % self.transformer_num_heads
+                    or self.transformer_ffn_hidden_size < 4 or self.transformer_ffn_hidden_size % 4):
+                raise ValueError("transformer: num_layers >= 1, num_heads dividing bert_embed_dim, ffn_hidden_size a positive multiple of 4")
+            if not 0.0 <= self.transformer_dropout < 1.0:
+                raise ValueError(f"transformer_dropout {self.transformer_dropout} must be in [0, 1)")
 
+
+MENTION_FINAL_LAYERS = ("linear", "transformer", "none")
+MENTION_REPRESENTATIONS = ("avg extract", "max pool")
 
 # names of common/args.py the scoring path and its caller read, -> DrinConfig fields of the same name
 _ARGS_FIELDS = ("dataset_name", "num_candidates_data", "bert_embed_dim", "resnet_embed_dim", "resnet_num_region",
                 "max_mention_sentence_len", "max_entity_attr_token_len", "gcn_embed_dim", "num_gcn_layers", "gcn_edge_type",
                 "gcn_edge_feature", "gcn_vertex_activation", "gcn_edge_activation", "seed", "num_epoch", "test_epoch_interval",
-                "learning_rate", "triplet_margin", "batch_size", "shuffle_train_data")
+                "learning_rate", "triplet_margin", "batch_size", "shuffle_train_data", "mention_final_layer_name",
+                "mention_final_representation", "transformer_num_layers", "transformer_num_heads", "transformer_ffn_hidden_size",
+                "transformer_ffn_activation", "transformer_dropout")
 
 
 def config_from_reference_args(args=None) -> DrinConfig:
     """The `DrinConfig` a reference checkout's `common.args` module describes (`common/args.py:24-40,45,52-57,72,77,83-101,
     109-126`): what the reference's no-argument `Model()` (`drin/model.py:157-162`, `train.py:136`) reads as star-imported
-    globals.  `args`: the module (default: `import common.args`).  `model_type` must be "drin" (`args.py:7`)."""
+    globals.  `args`: the module (default: `import common.args`).  `model_type` must be "drin" (`args.py:7`).
+    The mention encoder's names (`args.py:28-29`) and the transformer's (`args.py:60-64`) are read as they stand.  This is the one
+    place that refuses `("linear", "max pool")`; `validate()` refuses unknown names.  Also refused here, because DRIN's block of
+    `args.py` offers nothing else and the library builds nothing else: `entity_final_layer_name != "linear"`,
+    `entity_final_pooling != "avg"`, `online_bert` (the parent commit read none of the three and built the linear / avg model
+    whatever they said)."""
     if args is None:
         import importlib
         args = importlib.import_module("common.args")
@@ -102,6 +140,17 @@ def config_from_reference_args(args=None) -> DrinConfig:
     for k in ("gcn_edge_enabled", "metrics_topk", "acc_correction"):   # lists there, tuples here (frozen dataclass)
         if hasattr(args, k):
             kw[k] = tuple(getattr(args, k))
+    for name, built in (("entity_final_layer_name", "linear"), ("entity_final_pooling", "avg"), ("online_bert", False)):
+        if getattr(args, name, built) != built:     # DRIN's block of args.py offers nothing else (args.py:30,40,49)
+            raise NotImplementedError(f"common.args.{name} = {getattr(args, name)!r} is not built (only {built!r}; DESIGN.md section 11)")
+    if kw.get("mention_final_layer_name", "linear") == "linear" and kw.get("mention_final_representation", "avg extract") == "max pool":
+        # args.py:12-13 declares the representation "forced to avg extract" for "linear"; the reference's DRIN code would
+        # nevertheless take the text-text edge by max there (model.py:58 reads the global as it stands).  Not built, and refused
+        # HERE only, where a reference configuration enters: a DrinConfig built by hand follows the declared rule (the linear
+        # encoder never reads mention_final_representation).
+        raise NotImplementedError("common.args: mention_final_layer_name 'linear' with mention_final_representation 'max pool': "
+                                  "common/args.py:12-13 forces 'avg extract' for 'linear' (the reference's DRIN code would take the "
+                                  "text-text edge by max there); not built - DESIGN.md section 22")
     cfg = DrinConfig(**kw)
     if hasattr(args, "num_candidates_model") and args.num_candidates_model != cfg.num_candidates_model:
         raise ValueError("common.args.num_candidates_model != num_candidates_data + 1 (args.py:101)")

@@ -293,18 +293,21 @@ static int validate_batch(const drin_config* c, const drin_batch* b) {
   return DRIN_OK;
 }
 
-static int validate_params(const drin_config* c, const drin_params* p) {
+// rows_head: the mention-text Linear is not part of the model (DRIN_MENTION_ROWS): its two tensors are never read, may be NULL
+static int validate_params(const drin_config* c, const drin_params* p, bool rows_head = false) {
   if (!p) {
     set_error("params is NULL");
     return DRIN_E_NULL;
   }
   const void* req[] = {p->w_mention_text,  p->b_mention_text,  p->w_entity_text,  p->b_entity_text,
                        p->w_mention_image, p->b_mention_image, p->w_entity_image, p->b_entity_image};
-  for (const void* q : req)
+  for (int i = rows_head ? 2 : 0; i < 8; ++i) {   // by position: the first two are the mention-text Linear
+    const void* q = req[i];
     if (!q || !aligned16(q)) {
       set_error("params: vertex encoder tensor NULL or not 16-byte aligned");
       return q ? DRIN_E_ALIGN : DRIN_E_NULL;
     }
+  }
   for (int l = 0; l < c->num_layers; ++l) {
     const drin_layer_params& L = p->layer[l];
     const void* lr[] = {L.w_h, L.b_h, L.w_u, L.b_u, L.w_v, L.b_v, L.ln_weight, L.ln_bias};
@@ -319,6 +322,53 @@ static int validate_params(const drin_config* c, const drin_params* p) {
     }
   }
   return DRIN_OK;
+}
+
+// The mention head of the *_head entry points (drin_hip.h: drin_mention_head).  NULL: the linear encoder.
+bool rows_head(const drin_mention_head* h) { return h != nullptr && h->encoder == DRIN_MENTION_ROWS; }
+int validate_head(const drin_mention_head* h, const char* who) {
+  if (!h) return DRIN_OK;
+  if (h->struct_size != sizeof(drin_mention_head)) {
+    set_error("%s: head.struct_size = %zu, this library's drin_mention_head has %zu bytes", who, h->struct_size, sizeof(drin_mention_head));
+    return DRIN_E_SHAPE;
+  }
+  if ((h->encoder != DRIN_MENTION_LINEAR && h->encoder != DRIN_MENTION_ROWS) ||
+      (h->representation != DRIN_REPR_AVG_EXTRACT && h->representation != DRIN_REPR_MAX_POOL)) {
+    set_error("%s: head.encoder = %d / head.representation = %d: not a drin_mention_encoder / drin_mention_repr", who, h->encoder,
+              h->representation);
+    return DRIN_E_SHAPE;
+  }
+  if (h->encoder == DRIN_MENTION_LINEAR) {
+    if (h->representation == DRIN_REPR_MAX_POOL) {
+      set_error("%s: {DRIN_MENTION_LINEAR, DRIN_REPR_MAX_POOL} is not built: common/args.py:12-13 forces avg extract for \"linear\" "
+                "(the reference's DRIN code would take the text-text edge by max there; DESIGN.md section 22)", who);
+      return DRIN_E_UNSUPPORTED;
+    }
+    if (h->encoded || h->grad_encoded) {
+      set_error("%s: head.encoded / head.grad_encoded go with DRIN_MENTION_ROWS only", who);
+      return DRIN_E_SHAPE;
+    }
+    return DRIN_OK;
+  }
+  if (h->grad_encoded && !h->encoded) {
+    set_error("%s: head.grad_encoded without head.encoded (both rows are then functions of mention_text: ask for its gradient)", who);
+    return DRIN_E_SHAPE;
+  }
+  if (h->representation == DRIN_REPR_MAX_POOL && !h->max_index) {
+    set_error("%s: head.max_index is NULL (DRIN_REPR_MAX_POOL keeps the positions of the maxima there)", who);
+    return DRIN_E_NULL;
+  }
+  if (!aligned16(h->encoded) || !aligned16(h->max_index) || !aligned16(h->grad_encoded)) {
+    set_error("%s: head.encoded / max_index / grad_encoded must be 16-byte aligned", who);
+    return DRIN_E_ALIGN;
+  }
+  return DRIN_OK;
+}
+// the positions of the edge row's and the vertex row's maxima in head.max_index [2][B, D] (NULL, NULL without a max)
+void head_positions(const drin_config* c, const drin_mention_head* h, int32_t** edge, int32_t** vertex) {
+  const bool mx = h->representation == DRIN_REPR_MAX_POOL;
+  *edge = mx ? h->max_index : nullptr;
+  *vertex = mx ? h->max_index + (size_t)c->batch * c->embed_dim : nullptr;
 }
 
 // Operand pointers of the static edges without a workspace, hence without pooled copies (inner dims <= 1): the caller's
@@ -348,12 +398,22 @@ void resolve_pooled(const drin_config* c, const drin_batch* b, const Layout& L, 
 
 // Resolves the pooled / raw operand pointers of the vertex and edge encoders and runs the pooling: a pass for every operand
 // that resolve_pooled pointed into the workspace.
-int run_pooling(const drin_config* c, const drin_batch* b, const Layout& L, float* ws, Pooled* out, hipStream_t st) {
+// (head, DRIN_MENTION_ROWS: the span mean's place takes the edge row repr(mention_text) and the layer-0 mention-text vertex
+//  takes repr(encoded) - k_mention_rows, one launch - instead of the span mean that the mention-text Linear would read)
+int run_pooling(const drin_config* c, const drin_batch* b, const Layout& L, float* ws, Pooled* out, hipStream_t st,
+                const drin_mention_head* head) {
   const int B = c->batch, N = c->num_candidates, D = c->embed_dim, R = c->image_dim;
   const int64_t M = (int64_t)B * N;
   resolve_pooled(c, b, L, ws, out);
   auto copy_of = [](const float* resolved, const float* raw) { return resolved != raw ? const_cast<float*>(resolved) : nullptr; };
-  DRIN_TRY(launch_span_mean(b->mention_text, b->mention_start, b->mention_end, ws + L.span_mean, B, c->mention_tokens, D, st));
+  if (rows_head(head)) {
+    int32_t *ie, *iv;
+    head_positions(c, head, &ie, &iv);
+    DRIN_TRY(launch_mention_rows(b->mention_text, false, head->encoded, b->mention_start, b->mention_end, head->representation,
+                                 ws + L.span_mean, ws + L.vm[0], ie, iv, B, c->mention_tokens, D, st));
+  } else {
+    DRIN_TRY(launch_span_mean(b->mention_text, b->mention_start, b->mention_end, ws + L.span_mean, B, c->mention_tokens, D, st));
+  }
   DRIN_TRY(launch_axis_mean(b->mention_image, ws + L.mimg_pool, B, c->image_regions, R, st));
   if (float* dst = copy_of(out->mention_object, b->mention_object))
     DRIN_TRY(launch_axis_mean(b->mention_object, dst, (int64_t)B * c->mention_objects, c->mention_object_inner, R, st));
@@ -504,7 +564,8 @@ static int zero_out(void* p, size_t floats, hipStream_t st) {
 // without GCN layers (the score then reads neither the edges nor the image vertices); g_vm0 = [d mt | d mi],
 // g_ve0 = [d et | d ei]: the vertex encoders' output gradients.
 static int run_input_grads(const drin_config* c, const drin_batch* b, const drin_params* W, const Pooled& P, const float* ge,
-                           const float* g_vm0, const float* g_ve0, const drin_input_grads* ig, hipStream_t st) {
+                           const float* g_vm0, const float* g_ve0, const drin_input_grads* ig, hipStream_t st,
+                           const drin_mention_head* head = nullptr) {
   const int B = c->batch, N = c->num_candidates, D = c->embed_dim, R = c->image_dim, T = c->entity_tokens;
   const int Km = c->mention_objects, Ke = c->entity_objects;
   const size_t M = (size_t)B * N, BD = (size_t)B * D, MD = M * D;
@@ -542,6 +603,7 @@ static int run_input_grads(const drin_config* c, const drin_batch* b, const drin
   if (T == 0 && !has_cls && ig->entity_text) d_raw = ig->entity_text;   // the raw rows ARE entity_text
   if (T == 0 && has_cls && ig->entity_text_cls) d_raw = ig->entity_text_cls;
   const bool want_raw = (T > 0 && ig->entity_text) || (T == 0 && !has_cls && ig->entity_text) || (has_cls && ig->entity_text_cls);
+  const bool rows = rows_head(head);
   const bool tt = live && (ig->mention_text || want_raw);
   if (tt) {
     const float* y = has_cls ? b->entity_text_cls : b->entity_text;
@@ -556,7 +618,14 @@ static int run_input_grads(const drin_config* c, const drin_batch* b, const drin
     DRIN_TRY(zero_out(ig->entity_text_cls, MD, st));
   }
   // mention text: d span = d mt W_mt (+ the edge term), then the span mean's backward (ghmfc.py:54-60)
-  if (ig->mention_text) {
+  // (a rows head: no Linear - the edge row's gradient goes to the raw block, the vertex row's to the encoded block, or both to
+  //  the raw block when there is no encoded one: k_mention_rows_bwd, every element written once)
+  if (rows) {
+    int32_t *ie, *iv;
+    head_positions(c, head, &ie, &iv);
+    DRIN_TRY(launch_mention_rows_bwd(tt ? sc + S.g_span : nullptr, g_mt, b->mention_start, b->mention_end, ie, iv, head->representation,
+                                     head->encoded != nullptr, ig->mention_text, head->grad_encoded, B, c->mention_tokens, D, st));
+  } else if (ig->mention_text) {
     DRIN_TRY(launch_gemm_nn(g_mt, D, W->w_mention_text, D, sc + S.g_span, D, B, D, D, tt, DRIN_PREC_F32, st));
     DRIN_TRY(launch_span_mean_bwd(sc + S.g_span, b->mention_start, b->mention_end, ig->mention_text, B, c->mention_tokens, D, st));
   }
@@ -938,11 +1007,21 @@ int drin_forward(const drin_config* cfg, const drin_batch* batch, const drin_par
 int drin_forward_staged(const drin_config* cfg, const drin_batch* batch, const drin_params* params, void* workspace,
                         size_t workspace_bytes, float* scores, int keep_for_backward, const drin_trace* trace,
                         void* params_ready_event, void* stream) {
-  DRIN_BIND_DEVICE(stream, workspace, "drin_forward_staged");
+  return drin_forward_staged_head(cfg, batch, params, workspace, workspace_bytes, scores, keep_for_backward, trace, params_ready_event,
+                                  nullptr, stream);
+}
+
+int drin_forward_staged_head(const drin_config* cfg, const drin_batch* batch, const drin_params* params, void* workspace,
+                             size_t workspace_bytes, float* scores, int keep_for_backward, const drin_trace* trace,
+                             void* params_ready_event, const drin_mention_head* head, void* stream) {
+  const char* const who = head ? "drin_forward_staged_head" : "drin_forward_staged";
+  DRIN_BIND_DEVICE(stream, workspace, who);
   RoctxRange range("drin_forward");
   DRIN_TRY(validate_config(cfg));
+  DRIN_TRY(validate_head(head, who));
+  const bool rows = rows_head(head);
   DRIN_TRY(validate_batch(cfg, batch));
-  DRIN_TRY(validate_params(cfg, params));
+  DRIN_TRY(validate_params(cfg, params, rows));
   const int64_t* eidx = batch->entity_index;
   if (eidx) DRIN_TRY(indexed_supported(cfg, "drin_forward"));
   if (!scores) {
@@ -972,7 +1051,7 @@ int drin_forward_staged(const drin_config* cfg, const drin_batch* batch, const d
   const bool full = trace != nullptr;
 
   Pooled P;
-  DRIN_TRY(run_pooling(cfg, batch, L, ws, &P, st));
+  DRIN_TRY(run_pooling(cfg, batch, L, ws, &P, st, head));
   const bool vec = cfg->vector_edges != 0;
   const size_t EW = vec ? (size_t)D : 1;   // floats per edge per pair
   const size_t ES = (size_t)M * EW;        // stride between the four edge types
@@ -1009,7 +1088,7 @@ int drin_forward_staged(const drin_config* cfg, const drin_batch* batch, const d
   auto wp = [&](size_t off) -> const float* { return L.weight_planes ? ws + off : nullptr; };
   if (L.weight_planes) {
     SplitBatch sb;
-    DRIN_TRY(sb.add(params->w_mention_text, ws + L.wp_enc[0], (int64_t)D * D));
+    if (!rows) DRIN_TRY(sb.add(params->w_mention_text, ws + L.wp_enc[0], (int64_t)D * D));
     DRIN_TRY(sb.add(params->w_mention_image, ws + L.wp_enc[1], (int64_t)D * R));
     DRIN_TRY(sb.add(params->w_entity_text, ws + L.wp_enc[2], (int64_t)D * D));
     DRIN_TRY(sb.add(params->w_entity_image, ws + L.wp_enc[3], (int64_t)D * R));
@@ -1023,9 +1102,13 @@ int drin_forward_staged(const drin_config* cfg, const drin_batch* batch, const d
     DRIN_TRY(launch_split_planes_batch(sb, st));
   }
   auto nt_pair = [&](const NtProduct& a, const NtProduct& b) -> int { return launch_gemm_nt_pair(a, b, prec, st, msk, mskf); };
-  DRIN_TRY(nt_pair({P.span_mean, params->w_mention_text, params->b_mention_text, vm0, D, D, D, B, D, D, wp(L.wp_enc[0])},
-                   {P.mention_image, params->w_mention_image, params->b_mention_image, vm0 + (size_t)B * D, R, R, D, B, D, R,
-                    wp(L.wp_enc[1])}));
+  if (rows)   // the mention-text vertex is in vm0 already (run_pooling): the mention-image product alone
+    DRIN_TRY(launch_gemm_nt(P.mention_image, R, params->w_mention_image, R, params->b_mention_image, vm0 + (size_t)B * D, D, B, D, R,
+                            false, prec, st, msk, mskf, wp(L.wp_enc[1])));
+  else
+    DRIN_TRY(nt_pair({P.span_mean, params->w_mention_text, params->b_mention_text, vm0, D, D, D, B, D, D, wp(L.wp_enc[0])},
+                     {P.mention_image, params->w_mention_image, params->b_mention_image, vm0 + (size_t)B * D, R, R, D, B, D, R,
+                      wp(L.wp_enc[1])}));
   if (eidx) {  // rows of the entity tables, addressed through the candidate index by the GEMM's stager
     const __bf16* pt = reinterpret_cast<const __bf16*>(wp(L.wp_enc[2]));
     const __bf16* pi = reinterpret_cast<const __bf16*>(wp(L.wp_enc[3]));
@@ -1246,11 +1329,21 @@ int drin_pool_bwd(const drin_config* cfg, const int64_t* entity_text_mask, const
 int drin_backward_ex(const drin_config* cfg, const drin_batch* batch, const drin_params* params, void* workspace,
                      size_t workspace_bytes, const float* grad_scores, const drin_param_grads* grads_in,
                      const drin_input_grads* input_grads, void* layers_ready_event, void* stream) {
-  DRIN_BIND_DEVICE(stream, workspace, "drin_backward_staged");
+  return drin_backward_head(cfg, batch, params, workspace, workspace_bytes, grad_scores, grads_in, input_grads, layers_ready_event,
+                            nullptr, stream);
+}
+
+int drin_backward_head(const drin_config* cfg, const drin_batch* batch, const drin_params* params, void* workspace,
+                       size_t workspace_bytes, const float* grad_scores, const drin_param_grads* grads_in,
+                       const drin_input_grads* input_grads, void* layers_ready_event, const drin_mention_head* head, void* stream) {
+  const char* const who = head ? "drin_backward_head" : "drin_backward_staged";
+  DRIN_BIND_DEVICE(stream, workspace, who);
   RoctxRange range("drin_backward");
   DRIN_TRY(validate_config(cfg));
+  DRIN_TRY(validate_head(head, who));
+  const bool rows = rows_head(head);
   DRIN_TRY(validate_batch(cfg, batch));
-  DRIN_TRY(validate_params(cfg, params));
+  DRIN_TRY(validate_params(cfg, params, rows));
   if (!grad_scores) {
     set_error("drin_backward: grad_scores / grads is NULL");
     return DRIN_E_NULL;
@@ -1450,17 +1543,26 @@ int drin_backward_ex(const drin_config* cfg, const drin_batch* batch, const drin
   const float* g_mi = g_vm(0) + BD;
   const float* g_et = g_ve(0);
   const float* g_ei = g_ve(0) + MD;
-  DRIN_TRY(dw.add(g_mt, D, P.span_mean, D, grads->w_mention_text, D, B, D, D, nullptr, grads->b_mention_text));
+  if (!rows) DRIN_TRY(dw.add(g_mt, D, P.span_mean, D, grads->w_mention_text, D, B, D, D, nullptr, grads->b_mention_text));
   DRIN_TRY(dw.add(g_et, D, P.entity_text, D, grads->w_entity_text, D, (int64_t)M, D, D, eidx, grads->b_entity_text));
   if (have_image) {
     DRIN_TRY(dw.add(g_mi, D, P.mention_image, R, grads->w_mention_image, R, B, D, R, nullptr, grads->b_mention_image));
     DRIN_TRY(dw.add(g_ei, D, P.entity_image, R, grads->w_entity_image, R, (int64_t)M, D, R, eidx, grads->b_entity_image));
   }
   DRIN_TRY(dw.finish(layers_ready_event));   // everything collected lands; staged: the layers' part, the event, the encoders' part
-  if (input_grads == nullptr) return DRIN_OK;
+  if (input_grads == nullptr) {
+    // parameters alone are training: the intermediate layer's still need the gradient of its output (the vertex row's term)
+    if (rows && head->grad_encoded != nullptr) {
+      int32_t *ie, *iv;
+      head_positions(cfg, head, &ie, &iv);
+      DRIN_TRY(launch_mention_rows_bwd(nullptr, g_mt, batch->mention_start, batch->mention_end, ie, iv, head->representation, true, nullptr,
+                                       head->grad_encoded, B, cfg->mention_tokens, D, st));
+    }
+    return DRIN_OK;
+  }
   // the batch tensors' gradients (drin_backward_ex): from the vertex encoders' output gradients and the layer-0 edge
   // gradients, which the layer loop left in g_vm(0) / g_ve(0) / g_e[nl & 1] (nothing above writes them after the loop)
-  return run_input_grads(cfg, batch, params, P, nl > 0 ? g_e[nl & 1] : nullptr, g_vm(0), g_ve(0), input_grads, st);
+  return run_input_grads(cfg, batch, params, P, nl > 0 ? g_e[nl & 1] : nullptr, g_vm(0), g_ve(0), input_grads, st, head);
 }
 
 // ---- host-side self-checks (sanitizer build / CI; no launch is made, no GPU needed) -----------------------------------

@@ -243,4 +243,15 @@ __device__ __forceinline__ bool wave_pair(int64_t pairs, int N, int64_t& p, int6
   return p < pairs;
 }
 
+// max over a sequence as torch.max takes it (k_seq_max of ghmfc_rows.hip, k_mention_rows of mention_rows.hip): a NaN wins.
+__device__ __forceinline__ float max_nan(float a, float b) { return (b > a || b != b) ? b : a; }
+// IDX (drin_seq_max_train_fwd): idx[b, c] = the LOWEST position that attains out[b, c]; when the column holds a NaN, the
+// lowest NaN position (numpy.argmax's answer).  The values go through the same max_nan sequence either way: same bits.
+// where(a, ia, b, ib): the position that goes with max_nan(a, b) when a sits at ia and b at ib
+__device__ __forceinline__ int max_nan_pos(float a, int ia, float b, int ib) {
+  const bool b_wins = b > a || (b != b && a == a);
+  const bool tie = b == a || (b != b && a != a);
+  return b_wins ? ib : (tie && ib < ia ? ib : ia);
+}
+
 }  // namespace drin

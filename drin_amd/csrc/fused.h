@@ -169,7 +169,8 @@ struct GemmScratch {  // split-K / tail-split partials of a product; none: {}
 // Mention-side pooling (ghmfc.py:54-60, model.py:41; fp32 or bf16 features by cfg->feature_dtype), the two vertex-encoder Linears
 // -> vm0 = [mt0; mi0], then hmfu = [hm | fu] = vm0 [W_h1; W_u1]^T + [0; b_u1].
 int run_folded_head(const drin_config* cfg, const drin_batch* b, const drin_params* params, const float* prepared, const Prepared& P,
-                    bool weight_planes, float* span_mean, float* mimg, float* vm0, float* hmfu, GemmScratch mention_sk, hipStream_t st);
+                    bool weight_planes, float* span_mean, float* mimg, float* vm0, float* hmfu, GemmScratch mention_sk, hipStream_t st,
+                    const drin_mention_head* head = nullptr);   // a rows head: k_mention_rows and the mention-image product alone
 // Layer-1 mention vertices from their W_h1 output (LayerNorm + activation in place), then hm2 = vm1 W_h2^T.
 int run_folded_mention_finish(const drin_config* cfg, const drin_params* params, const float* prepared, const Prepared& P,
                               bool weight_planes, float* vm1, float* hm2, GemmScratch mention_sk, hipStream_t st);

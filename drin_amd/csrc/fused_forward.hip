@@ -265,6 +265,16 @@ int drin_prepare(const drin_config* cfg, const drin_params* params, void* prepar
     set_error("drin_prepare: NULL argument");
     return DRIN_E_NULL;
   }
+  {   // every weight the folds read; w_mention_text alone may be NULL (a DRIN_MENTION_ROWS model: its plane is skipped below)
+    const void* need[] = {params->w_entity_text, params->b_entity_text, params->w_mention_image, params->w_entity_image,
+                          params->b_entity_image, params->layer[0].w_h, params->layer[0].b_h, params->layer[0].w_u, params->layer[0].b_u,
+                          params->layer[0].w_v, params->layer[0].b_v, params->layer[1].w_h};
+    for (const void* q : need)
+      if (!q) {
+        set_error("drin_prepare: a weight the folds read is NULL (only w_mention_text may be, for a DRIN_MENTION_ROWS model)");
+        return DRIN_E_NULL;
+      }
+  }
   Prepared P;
   P.build(*cfg);
   if (prepared_bytes < P.total * sizeof(float) || !aligned16(prepared)) {
@@ -319,6 +329,13 @@ int drin_prepare(const drin_config* cfg, const drin_params* params, void* prepar
         {P.p_wet, params->w_entity_text, dd},   {P.p_wei, params->w_entity_image, dr},
         {P.p_wh1, L1.w_h, dd}};
     for (const auto& e : extra) {
+      // w_mention_text NULL: a model whose mention head is DRIN_MENTION_ROWS has no such Linear; its plane is zeroed, so a later call
+      // without a rows head on this buffer reads zeros, never uninitialised memory (drin_hip.h: drin_forward_prepared_head)
+      if (e.off == P.p_wmt && e.w == nullptr) {
+        const hipError_t me = hipMemsetAsync(pb + e.off, 0, e.n * sizeof(float), st);
+        if (me != hipSuccess) return hip_fail(me, "hipMemsetAsync(prepare)");
+        continue;
+      }
       q = reinterpret_cast<__bf16*>(pb + e.off);
       DRIN_TRY(launch_split_planes(e.w, q, q + e.n, e.n, st));
     }
@@ -334,19 +351,34 @@ namespace drin {
 static int folded_precision(const drin_config* c) { return c->precision == DRIN_PREC_BF16X3_IF16 ? (int)DRIN_PREC_BF16X3 : c->precision; }
 
 int run_folded_head(const drin_config* cfg, const drin_batch* b, const drin_params* params, const float* pb, const Prepared& P,
-                    bool weight_planes, float* span_mean, float* mimg, float* vm0, float* hmfu, GemmScratch sk, hipStream_t st) {
+                    bool weight_planes, float* span_mean, float* mimg, float* vm0, float* hmfu, GemmScratch sk, hipStream_t st,
+                    const drin_mention_head* head) {
   const int B = cfg->batch, D = cfg->embed_dim, R = cfg->image_dim, prec = folded_precision(cfg);
   auto wp = [&](size_t plane_off) -> const float* { return weight_planes ? pb + plane_off : nullptr; };
-  if (cfg->feature_dtype == DRIN_FEAT_BF16) {
+  const bool bf16 = cfg->feature_dtype == DRIN_FEAT_BF16;
+  const bool rows = rows_head(head);
+  if (rows) {
+    // the edge row where the span mean lives (the stream pass reads it there), the vertex row straight into vm0; no Linear
+    int32_t *ie, *iv;
+    head_positions(cfg, head, &ie, &iv);
+    DRIN_TRY(launch_mention_rows(b->mention_text, bf16, head->encoded, b->mention_start, b->mention_end, head->representation, span_mean,
+                                 vm0, ie, iv, B, cfg->mention_tokens, D, st));
+  } else if (bf16) {
     DRIN_TRY(launch_span_mean_bf16(b->mention_text, b->mention_start, b->mention_end, span_mean, B, cfg->mention_tokens, D, st));
-    DRIN_TRY(launch_axis_mean_bf16(b->mention_image, mimg, B, cfg->image_regions, R, st));
   } else {
     DRIN_TRY(launch_span_mean(b->mention_text, b->mention_start, b->mention_end, span_mean, B, cfg->mention_tokens, D, st));
-    DRIN_TRY(launch_axis_mean(b->mention_image, mimg, B, cfg->image_regions, R, st));
   }
-  DRIN_TRY(launch_gemm_nt_pair({span_mean, params->w_mention_text, params->b_mention_text, vm0, D, D, D, B, D, D, wp(P.p_wmt)},
-                               {mimg, params->w_mention_image, params->b_mention_image, vm0 + (size_t)B * D, R, R, D, B, D, R, wp(P.p_wmi)},
-                               prec, st, sk.p, sk.floats));
+  if (bf16)
+    DRIN_TRY(launch_axis_mean_bf16(b->mention_image, mimg, B, cfg->image_regions, R, st));
+  else
+    DRIN_TRY(launch_axis_mean(b->mention_image, mimg, B, cfg->image_regions, R, st));
+  if (rows)   // the mention-text vertex is in vm0 already: the mention-image product alone
+    DRIN_TRY(launch_gemm_nt(mimg, R, params->w_mention_image, R, params->b_mention_image, vm0 + (size_t)B * D, D, B, D, R, false, prec, st,
+                            sk.p, sk.floats, wp(P.p_wmi)));
+  else
+    DRIN_TRY(launch_gemm_nt_pair({span_mean, params->w_mention_text, params->b_mention_text, vm0, D, D, D, B, D, D, wp(P.p_wmt)},
+                                 {mimg, params->w_mention_image, params->b_mention_image, vm0 + (size_t)B * D, R, R, D, B, D, R, wp(P.p_wmi)},
+                                 prec, st, sk.p, sk.floats));
   return launch_gemm_nt(vm0, D, pb + P.wcat1, D, pb + P.bcat1, hmfu, 2 * D, 2 * (int64_t)B, 2 * D, D, false, prec, st, sk.p, sk.floats,
                         wp(P.p_wcat1));
 }
@@ -411,7 +443,7 @@ int run_folded_tail(const drin_config* cfg, const drin_params* params, const flo
 // per tile as the one launch, so the scores are the same bits.  A captured call (hipStreamIsCapturing) keeps the one launch: no
 // parallel branches in a graph.  Measured: profiles/image_overlap_ab.txt.
 static int forward_prepared_on_stream(const drin_config* cfg, const drin_batch* b, const drin_params* params, const void* prepared,
-                                      void* workspace, float* scores, hipStream_t st) {
+                                      void* workspace, float* scores, hipStream_t st, const drin_mention_head* head) {
   FusedLayout L;
   L.build(*cfg);
   Prepared P;
@@ -510,7 +542,7 @@ static int forward_prepared_on_stream(const drin_config* cfg, const drin_batch* 
     if (e != hipSuccess) return hip_fail(e, "hipEventRecord(side stream)");
   }
   // (1) mention-side pooling and vertex-encoder Linears, [hm | fu]; (2) q = fu [W_v1 W_et | W_v1 W_ei]
-  DRIN_TRY(run_folded_head(cfg, b, params, pb, P, planes, ws + L.span_mean, ws + L.mimg, vm0, hmfu, msk, st));
+  DRIN_TRY(run_folded_head(cfg, b, params, pb, P, planes, ws + L.span_mean, ws + L.mimg, vm0, hmfu, msk, st, head));
   if (dyn)
     DRIN_TRY(launch_gemm_nt(hmfu + D, 2 * D, pb + P.ecat, D, nullptr, ws + L.q, D + R, 2 * (int64_t)B, D + R, D, false, prec, st, msk.p,
                             msk.floats, wp(P.p_ecat)));
@@ -676,9 +708,15 @@ size_t drin_fused_workspace_bytes(const drin_config* cfg) {
 
 int drin_forward_prepared(const drin_config* cfg, const drin_batch* b, const drin_params* params, const void* prepared,
                           void* workspace, size_t workspace_bytes, float* scores, void* stream) {
-  DRIN_BIND_DEVICE(stream, workspace, "drin_forward_prepared");
+  return drin_forward_prepared_head(cfg, b, params, prepared, workspace, workspace_bytes, scores, nullptr, stream);
+}
+
+int drin_forward_prepared_head(const drin_config* cfg, const drin_batch* b, const drin_params* params, const void* prepared,
+                               void* workspace, size_t workspace_bytes, float* scores, const drin_mention_head* head, void* stream) {
+  DRIN_BIND_DEVICE(stream, workspace, head ? "drin_forward_prepared_head" : "drin_forward_prepared");
   RoctxRange range("drin_forward_prepared");
   DRIN_TRY(validate_config(cfg));
+  DRIN_TRY(validate_head(head, "drin_forward_prepared_head"));
   DRIN_TRY(fused_supported(cfg));
   if (!b || !params || !prepared || !workspace || !scores) {
     set_error("drin_forward_prepared: NULL argument");
@@ -691,7 +729,7 @@ int drin_forward_prepared(const drin_config* cfg, const drin_batch* b, const dri
               L.total * sizeof(float));
     return DRIN_E_WORKSPACE;
   }
-  return forward_prepared_on_stream(cfg, b, params, prepared, workspace, scores, (hipStream_t)stream);
+  return forward_prepared_on_stream(cfg, b, params, prepared, workspace, scores, (hipStream_t)stream, head);
 }
 
 }  // extern "C"

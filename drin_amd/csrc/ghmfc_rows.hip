@@ -6,6 +6,7 @@
 // every run.
 #include "attention_common.h"
 #include "device_utils.h"
+#include "row_checks.h"
 #include "row_ops.h"
 
 namespace drin {
@@ -55,15 +56,7 @@ __global__ void __launch_bounds__(256) k_layernorm_res(const float* x, const flo
 
 // ---- out[b, :] = max over ALL s of x[b, s, :] (ghmfc.py:143,145: padded positions take part; a NaN wins, as torch.max) ----
 // grid (cdiv(E4, 64), B): thread (column quad, row group of four), the four groups meet in LDS.
-__device__ __forceinline__ float max_nan(float a, float b) { return (b > a || b != b) ? b : a; }
-// IDX (drin_seq_max_train_fwd): idx[b, c] = the LOWEST position that attains out[b, c]; when the column holds a NaN, the
-// lowest NaN position (numpy.argmax's answer).  The values go through the same max_nan sequence either way: same bits.
-// where(a, ia, b, ib): the position that goes with max_nan(a, b) when a sits at ia and b at ib
-__device__ __forceinline__ int max_nan_pos(float a, int ia, float b, int ib) {
-  const bool b_wins = b > a || (b != b && a == a);
-  const bool tie = b == a || (b != b && a != a);
-  return b_wins ? ib : (tie && ib < ia ? ib : ia);
-}
+// (max_nan / max_nan_pos: device_utils.h - k_mention_rows of mention_rows.hip runs the same sequence)
 template <bool IDX>
 __global__ void __launch_bounds__(256) k_seq_max(const float* __restrict__ x, float* __restrict__ out, int* __restrict__ idx, int S,
                                                  int E4) {
@@ -469,44 +462,7 @@ int launch_act_dropout_bwd(const float* x, const float* dy, float* dx, int64_t n
                [&] { DRIN_ACT_DISPATCH(k_act_dropout_bwd, act, drop != nullptr, act_grid(n4), dim3(256), 0, st, x, dy, dx, n4, da); });
 }
 
-// the row-op entry points: every pointer is read or written 16 bytes per lane
-struct NamedPtr {
-  const char* name;
-  const void* p;
-  bool required;
-};
-int check_pointers(const char* who, const NamedPtr* ptrs, int n) {
-  for (int i = 0; i < n; ++i) {
-    if (ptrs[i].required && !ptrs[i].p) {
-      set_error("%s: %s is NULL", who, ptrs[i].name);
-      return DRIN_E_NULL;
-    }
-    if (ptrs[i].p && !aligned16(ptrs[i].p)) {
-      set_error("%s: %s is not 16-byte aligned", who, ptrs[i].name);
-      return DRIN_E_ALIGN;
-    }
-  }
-  return DRIN_OK;
-}
-#define DRIN_CHECK_POINTERS(who, ...)                                                     \
-  do {                                                                                    \
-    const NamedPtr _ptrs[] = {__VA_ARGS__};                                               \
-    DRIN_TRY(check_pointers(who, _ptrs, (int)(sizeof(_ptrs) / sizeof(_ptrs[0]))));        \
-  } while (0)
-int check_count(const char* who, const char* name, int64_t v, int64_t lo, int64_t hi) {
-  if (v < lo || v > hi) {
-    set_error("%s: %s = %lld is not in [%lld, %lld]", who, name, (long long)v, (long long)lo, (long long)hi);
-    return DRIN_E_SHAPE;
-  }
-  return DRIN_OK;
-}
-int check_width4(const char* who, int E) {
-  if (E <= 0 || E % 4) {
-    set_error("%s: width %d must be a positive multiple of 4 (16-byte lane accesses)", who, E);
-    return DRIN_E_SHAPE;
-  }
-  return DRIN_OK;
-}
+// (NamedPtr, DRIN_CHECK_POINTERS, check_count, check_width4: row_checks.h)
 int check_scratch(const char* who, const float* scratch, size_t have, size_t need) {
   if (!scratch) {
     set_error("%s: scratch is NULL (%zu floats are needed)", who, need);

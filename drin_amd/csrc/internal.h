@@ -114,7 +114,8 @@ inline dim3 pair_grid(int B, int N) {
 // ---- pooling and static edges of the layer-by-layer entry points (api.hip; Layout, Pooled: layout.h) -------------------
 struct Layout;
 struct Pooled;
-int run_pooling(const drin_config* c, const drin_batch* b, const Layout& L, float* ws, Pooled* out, hipStream_t st);
+int run_pooling(const drin_config* c, const drin_batch* b, const Layout& L, float* ws, Pooled* out, hipStream_t st,
+                const drin_mention_head* head = nullptr);
 int run_static_edges(const drin_config* c, const drin_batch* b, const Pooled& P, float* edges, hipStream_t st);
 
 // ---- streaming / pooling kernels (stream_kernels.hip) -------------------------------------------
@@ -491,6 +492,22 @@ size_t miei_bwd_scratch_floats(int64_t pairs, int B, int Km, int Ke);
 int launch_miei_bwd(const float* mobj, const float* mscore, const float* eobj, const float* escore, const float* g,
                     float* d_mobj, float* d_mscore, float* d_eobj, float* d_escore, float* scratch, int B, int N, int Km,
                     int Ke, int R, float cos_eps, float miei_eps, hipStream_t st);
+
+// ---- the mention representation head (mention_rows.hip) ----------------------------------------------
+// the drin_mention_head of the *_head entry points (api.hip): its checks (NULL: the linear encoder, DRIN_OK), whether it replaces
+// the mention-text Linear, and where the two rows' max positions sit in head->max_index (NULL, NULL without a max)
+int validate_head(const drin_mention_head* h, const char* who);
+bool rows_head(const drin_mention_head* h);
+void head_positions(const drin_config* c, const drin_mention_head* h, int32_t** edge, int32_t** vertex);
+// edge_row[b] = repr(raw[b]), vertex_row[b] = repr(enc[b]) (enc NULL: the edge row's values); repr: drin_mention_repr.
+// raw fp32 or bf16 [B, L, D], enc fp32; start / end read by the span mean only, idx_edge / idx_vertex [B, D] written by the max only
+int launch_mention_rows(const void* raw, bool raw_bf16, const float* enc, const int64_t* start, const int64_t* end, int repr,
+                        float* edge_row, float* vertex_row, int* idx_edge, int* idx_vertex, int B, int L, int D, hipStream_t st);
+// d_raw / d_enc [B, L, D], each WRITTEN whole or NULL: d_raw takes the edge row's term (and the vertex row's without an encoded
+// block), d_enc the vertex row's; g_edge / g_vertex [B, D] or NULL (no gradient through that row)
+int launch_mention_rows_bwd(const float* g_edge, const float* g_vertex, const int64_t* start, const int64_t* end, const int* idx_edge,
+                            const int* idx_vertex, int repr, bool has_encoded, float* d_raw, float* d_enc, int B, int L, int D,
+                            hipStream_t st);
 
 // ---- vector-edge ablation (vector_kernels.hip) --------------------------------------------------
 int launch_expand_edges(const float* es, float* out, int64_t pairs4, int D, hipStream_t st);

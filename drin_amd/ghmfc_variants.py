@@ -94,6 +94,42 @@ def variant_config_from_reference_args(args) -> VariantConfig:
     return cfg
 
 
+def transformer_stack(layers, x, padding, *, num_heads: int, ffn_hidden_size: int, ffn_activation: str, precision: str, core: str,
+                      dropout: float, dropout_stream: DropoutStream):
+    """nn.TransformerEncoder(x, src_key_padding_mask=padding) over the `layers` of torch's own encoder (the parameter container):
+    post-norm layers, no final norm (ghmfc.py:75-90), composed from the library's differentiable functions.  x [B, L, D] fp32 on
+    the GPU, padding [B, L] bool (True = drop the key).  `dropout` > 0 (the caller passes 0 outside training): every layer takes
+    four draws from `dropout_stream` in the order attention weights, drop1 (on the attention output), drop (on the activated FFN
+    hidden rows), drop2 (on the FFN output), layers ascending.  Shared by `VariantModel` (GHMFC's "transformer" encoder) and
+    `drin_amd.drin_encoders.EncoderModel` (DRIN's)."""
+    prec = PRECISIONS[precision]
+    B, L, D = x.shape
+    rows = B * L
+
+    def drop(width: int):
+        """(p, seed, call) of the next row draw, or None when nothing is dropped"""
+        return (dropout, dropout_stream.seed, dropout_stream.draw_rows(rows, width)) if dropout > 0 else None
+    for layer in layers:
+        sa = layer.self_attn
+        a = multihead_attention_forward(
+            x, x, x, padding, embed_dim=D, num_heads=num_heads, kdim=D, vdim=D, in_proj_weight=sa.in_proj_weight,
+            q_proj_weight=None, k_proj_weight=None, v_proj_weight=None, in_proj_bias=sa.in_proj_bias,
+            out_proj_weight=sa.out_proj.weight, out_proj_bias=sa.out_proj.bias, precision=precision, dropout=dropout,
+            dropout_stream=dropout_stream, core=core)
+        drop1 = drop(D)
+        if drop1 is not None:
+            a = act_dropout(a, "none", drop1)
+        x = layer_norm_res(a, x, layer.norm1.weight, layer.norm1.bias, layer.norm1.eps)
+        h = _linear(x.view(rows, D), layer.linear1.weight, layer.linear1.bias, prec)
+        h = act_dropout(h, ffn_activation, drop(ffn_hidden_size))
+        h = _linear(h, layer.linear2.weight, layer.linear2.bias, prec)
+        drop2 = drop(D)
+        if drop2 is not None:
+            h = act_dropout(h, "none", drop2)
+        x = layer_norm_res(h.view(B, L, D), x, layer.norm2.weight, layer.norm2.bias, layer.norm2.eps)
+    return x
+
+
 class _MultilayerTransformer(nn.Module):
     """Parameter container of ghmfc.py's MultilayerTransformer: torch's own encoder, so the 12 keys per layer and the initial
     draw (one layer drawn, then deep-copied: all layers start equal) are torch's.  Its `forward` is never called."""
@@ -192,37 +228,13 @@ class VariantModel(nn.Module):
         return mf, mmask, begin, end, mimage, ef, emask
 
     # ---- the encoders ------------------------------------------------------------------------------------------
-    def _drop(self, rows: int, width: int):
-        """(p, seed, call) of the next row draw, or None when nothing is dropped"""
-        if not (self.training and self.dropout > 0):
-            return None
-        return self.dropout, self.dropout_stream.seed, self.dropout_stream.draw_rows(rows, width)
-
     def _transformer(self, x, padding):
         """nn.TransformerEncoder(x, src_key_padding_mask=padding): post-norm layers, no final norm (ghmfc.py:75-90)"""
-        cfg, prec = self.cfg, PRECISIONS[self.precision]
-        B, L, D = x.shape
-        rows, F, act = B * L, cfg.transformer_ffn_hidden_size, cfg.transformer_ffn_activation
-        p = self.dropout if self.training else 0.0
-        for layer in self.mention_encoder.intermediate_layer.transformer.layers:
-            sa = layer.self_attn
-            a = multihead_attention_forward(
-                x, x, x, padding, embed_dim=D, num_heads=cfg.num_heads, kdim=D, vdim=D, in_proj_weight=sa.in_proj_weight,
-                q_proj_weight=None, k_proj_weight=None, v_proj_weight=None, in_proj_bias=sa.in_proj_bias,
-                out_proj_weight=sa.out_proj.weight, out_proj_bias=sa.out_proj.bias, precision=self.precision, dropout=p,
-                dropout_stream=self.dropout_stream, core=self.core)
-            drop1 = self._drop(rows, D)
-            if drop1 is not None:
-                a = act_dropout(a, "none", drop1)
-            x = layer_norm_res(a, x, layer.norm1.weight, layer.norm1.bias, layer.norm1.eps)
-            h = _linear(x.view(rows, D), layer.linear1.weight, layer.linear1.bias, prec)
-            h = act_dropout(h, act, self._drop(rows, F))
-            h = _linear(h, layer.linear2.weight, layer.linear2.bias, prec)
-            drop2 = self._drop(rows, D)
-            if drop2 is not None:
-                h = act_dropout(h, "none", drop2)
-            x = layer_norm_res(h.view(B, L, D), x, layer.norm2.weight, layer.norm2.bias, layer.norm2.eps)
-        return x
+        cfg = self.cfg
+        return transformer_stack(self.mention_encoder.intermediate_layer.transformer.layers, x, padding, num_heads=cfg.num_heads,
+                                 ffn_hidden_size=cfg.transformer_ffn_hidden_size, ffn_activation=cfg.transformer_ffn_activation,
+                                 precision=self.precision, core=self.core, dropout=self.dropout if self.training else 0.0,
+                                 dropout_stream=self.dropout_stream)
 
     def _mention(self, mf, mmask, begin, end, mimage):
         cfg, prec = self.cfg, PRECISIONS[self.precision]

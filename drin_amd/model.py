@@ -29,10 +29,15 @@ class _AvgLinear(nn.Module):  # baselines/ghmfc.py:63-69
         self.linear = nn.Linear(in_dim, out_dim)
 
 
-class _MentionEncoder(nn.Module):  # baselines/ghmfc.py:152-165 (linear / offline branch)
-    def __init__(self, dim: int):
+class _MentionEncoder(nn.Module):  # baselines/ghmfc.py:152-175 (offline branch): the parameters of args.py:28's three encoders
+    def __init__(self, cfg: DrinConfig):
         super().__init__()
-        self.final_layer = _AvgLinear(dim, dim)
+        dim = cfg.bert_embed_dim
+        if cfg.mention_final_layer_name == "linear":
+            self.final_layer = _AvgLinear(dim, dim)
+        elif cfg.mention_final_layer_name == "transformer":            # ghmfc.py:166-167; "none" owns nothing (ghmfc.py:174-175)
+            from .drin_encoders import MultilayerTransformer
+            self.intermediate_layer = MultilayerTransformer(cfg)
 
 
 class _EntityEncoder(nn.Module):  # baselines/ghmfc.py:202-214 (linear / offline branch)
@@ -44,7 +49,7 @@ class _EntityEncoder(nn.Module):  # baselines/ghmfc.py:202-214 (linear / offline
 class VertexEncoder(nn.Module):  # drin/model.py:13-24
     def __init__(self, cfg: DrinConfig):
         super().__init__()
-        self.mention_text_encoder = _MentionEncoder(cfg.bert_embed_dim)
+        self.mention_text_encoder = _MentionEncoder(cfg)
         self.entity_text_encoder = _EntityEncoder(cfg.bert_embed_dim)
         self.mention_image_linear = nn.Linear(cfg.resnet_embed_dim, cfg.gcn_embed_dim)
         self.entity_image_linear = nn.Linear(cfg.resnet_embed_dim, cfg.gcn_embed_dim)
@@ -667,6 +672,15 @@ class Model(nn.Module):
     # workgroups - so a mention's scores in calls of different sizes agree to fp32 re-association, <= 5e-6, and are the same
     # bits every run within one call size); the one-workgroup-per-(mention, chunk) grids of the row kernels stop at 65 535 mentions
     MAX_CALL_MENTIONS = 32768
+    flat_buckets = True       # flatten_parameters / grad_bucket / LibraryAdam's flat form are built (EncoderModel: not)
+
+    def __new__(cls, cfg: Optional[DrinConfig] = None, *args, **kwargs):
+        """`Model(cfg)` with `mention_final_layer_name` "transformer" or "none" (args.py:28) is a
+        `drin_amd.drin_encoders.EncoderModel`; the linear encoder - the default - is this class, untouched."""
+        if cls is Model and not (cfg or default_config()).linear_mention_encoder:
+            from .drin_encoders import EncoderModel
+            return super().__new__(EncoderModel)
+        return super().__new__(cls)
 
     def __init__(self, cfg: Optional[DrinConfig] = None, precision: str = "bf16x3", fused: bool = True,
                  grad_bucket: bool = True):

@@ -26,9 +26,16 @@ def _args():
 
 class Model(_Model):
     """`model_module.Model()`: geometry, layer count, edge switches and activations from `common.args`
-    (`args.py:24-40,45,52-57,72,77,83-101`).  Contractions run split-bf16 (`precision="bf16x3"`: <= 1.4e-6 on the scores
+    (`args.py:24-40,45,52-57,60-64,72,77,83-101`), the mention encoder of `args.py:28-29` included.  Contractions run split-bf16 (`precision="bf16x3"`: <= 1.4e-6 on the scores
     against the reference's fp32 forward, the 1e-4 bar of the path); `DRIN_PRECISION=f32` in the environment selects the
     exact fp32 MFMA kernels."""
+
+    def __new__(cls):
+        """`mention_final_layer_name` "transformer" / "none" (`args.py:28`): a `drin_amd.drin_encoders.EncoderModel`, built here."""
+        cfg = config_from_reference_args(_args())
+        if cfg.linear_mention_encoder:
+            return super().__new__(cls)
+        return _Model(cfg, precision=os.environ.get("DRIN_PRECISION", "bf16x3"))
 
     def __init__(self):
         super().__init__(config_from_reference_args(_args()), precision=os.environ.get("DRIN_PRECISION", "bf16x3"))

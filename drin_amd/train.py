@@ -45,6 +45,14 @@ def _collectives(force: bool) -> bool:
     return dist.get_world_size() > 1 or force
 
 
+def _refuse_without_flat_buckets(model, what: str) -> None:
+    """`drin_encoders.EncoderModel` (`flat_buckets = False`): its autograd edge hands the library no layers-ready event and takes no
+    parameters-ready event, so the overlapped forms would silently run unordered - refused instead."""
+    if not getattr(model, "flat_buckets", True):
+        raise NotImplementedError(f"{what} is not built for the transformer / none mention encoders (DESIGN.md section 22, 'not done'): "
+                                  "use GradBucket(overlap=False) with bucket.allreduce_mean(); optimizer.step()")
+
+
 class GradBucket:
     """The gradients of all parameters that receive one (26.8 MB of the 31.5 MB carry gradients),
     all-reduced once per step.
@@ -72,6 +80,7 @@ class GradBucket:
         self._comm: Optional[torch.cuda.Stream] = None
         self.model = model if overlap else None
         if self.model is not None:
+            _refuse_without_flat_buckets(self.model, "GradBucket(overlap=True)")
             if not hasattr(self.model, "_layers_ready_hook"):
                 raise ValueError("overlap=True needs a drin_amd.model.Model (drin_backward_staged)")
             self.model._layers_ready_hook = self._layers_ready
@@ -184,6 +193,7 @@ class OverlappedStep:
     first (`MELRunner` does at the end of every training epoch).  Host tensors / no GPU: runs inline."""
 
     def __init__(self, model, bucket: GradBucket, optimizer):
+        _refuse_without_flat_buckets(model, "OverlappedStep")
         self.model, self.bucket, self.optimizer = model, bucket, optimizer
         self._comm: Optional[torch.cuda.Stream] = None
         self.steps = 0
@@ -227,6 +237,8 @@ class LibraryAdam:
     the per-parameter counts), not interchangeable with `torch.optim.Adam.state_dict()`."""
 
     def __init__(self, model, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8):
+        if not getattr(model, "flat_buckets", True):
+            model.flatten_parameters()                       # drin_encoders.EncoderModel: raises NotImplementedError, naming why
         self.model, self.lr, self.betas, self.eps = model, float(lr), (float(betas[0]), float(betas[1])), float(eps)
         self.t = 0
         self.steps: List[int] = []                           # per parameter, `_param_list` order
@@ -314,7 +326,7 @@ def make_adam(model, lr: float, library: Optional[bool] = None, capturable: bool
     variant, whose rounding differs)."""
     from .model import Model
     p0 = next(model.parameters())
-    can = isinstance(model, Model) and p0.is_cuda and not capturable and not fused
+    can = isinstance(model, Model) and model.flat_buckets and p0.is_cuda and not capturable and not fused
     if library is None:
         library = can
     if library and not can:

@@ -926,6 +926,80 @@ DRIN_API int drin_span_mean_fwd(const float* seq, const int64_t* start, const in
 DRIN_API int drin_span_mean_bwd(const float* dout, const int64_t* start, const int64_t* end, float* dseq, int32_t batch,
                                 int32_t seq_len, int32_t width, void* stream);
 
+/* ---- DRIN's other mention encoders: the representation head ---------------------------------- *
+ * Reference: common/args.py:28-29 (mention_final_layer_name "linear" | "transformer" | "none", mention_final_representation),
+ * baselines/ghmfc.py:54-70 (Avg, MaxPool), :152-199 (MentionEncoder(inline_bert=False)), drin/model.py:21,58,71-76.  With
+ * "none" / "transformer" the mention-text vertex is repr(intermediate(mention_text)) with no Linear behind it, and the
+ * text-text edge takes repr(mention_text) of the RAW block; repr is the mean over the mention span or the max over all L
+ * positions (padded ones take part; neither the mask nor the span is read).  The intermediate layer (the transformer stack)
+ * is the caller's: its output travels as `encoded`. */
+typedef enum {
+  DRIN_MENTION_LINEAR = 0, /* mt0 = span mean W_mt^T + b_mt: what the entry points without a head compute   */
+  DRIN_MENTION_ROWS = 1    /* mt0 = repr(encoded, or mention_text itself), no Linear                         */
+} drin_mention_encoder;
+typedef enum {
+  DRIN_REPR_AVG_EXTRACT = 0, /* Avg.avg (ghmfc.py:54-60): Python slice clipping, an empty span gives a NaN row */
+  DRIN_REPR_MAX_POOL = 1     /* MaxPool (ghmfc.py:63-70): a NaN wins, the lowest position attains a tie        */
+} drin_mention_repr;
+/* Additive under ABI 12: no existing struct changes; the settings travel here, with the struct's own size. */
+typedef struct drin_mention_head {
+  size_t struct_size;     /* sizeof(drin_mention_head)                                                                      */
+  int32_t encoder;        /* drin_mention_encoder                                                                           */
+  int32_t representation; /* drin_mention_repr; DRIN_MENTION_LINEAR takes DRIN_REPR_AVG_EXTRACT only (args.py:12-13)        */
+  const float* encoded;   /* [B, L, D] fp32: the intermediate layer's output, or NULL = mention_text itself; ROWS only      */
+  int32_t* max_index;     /* [2][B, D] (edge row, vertex row), caller-owned, written by forward, read by backward; MAX_POOL */
+  float* grad_encoded;    /* backward: [B, L, D], WRITTEN; NULL = not wanted                                                */
+} drin_mention_head;
+
+/* drin_forward_staged with a mention head.  head NULL or {DRIN_MENTION_LINEAR, DRIN_REPR_AVG_EXTRACT, NULL}: exactly
+ * drin_forward_staged (the same launches, the same bits).  DRIN_MENTION_ROWS: params->w_mention_text / b_mention_text are not
+ * read and may be NULL; the edge row lives where the span mean lives and the vertex row goes straight into the layer-0
+ * mention-text vertex, so workspace sizes and layouts are those of drin_workspace_bytes.  Vector edges, static edges,
+ * edge_enabled, every activation and num_layers = 0 work under a head: it ends at the span-mean row and the layer-0 vertex.
+ * DRIN_E_SHAPE: struct_size, an unknown encoder / representation, `encoded` under LINEAR, grad_encoded without encoded;
+ * DRIN_E_UNSUPPORTED: {LINEAR, MAX_POOL} (args.py:12-13 forces avg extract for "linear"); DRIN_E_NULL: max_index under MAX_POOL. */
+DRIN_API int drin_forward_staged_head(const drin_config* cfg, const drin_batch* batch, const drin_params* params, void* workspace,
+                                      size_t workspace_bytes, float* scores, int keep_for_backward, const drin_trace* trace,
+                                      void* params_ready_event, const drin_mention_head* head, void* stream);
+/* drin_backward_ex with the head of the forward pass (the same encoder, representation, encoded and max_index).  Under
+ * DRIN_MENTION_ROWS grads->w_mention_text / b_mention_text are never written.  Works with grads only, input_grads only or
+ * both: head->grad_encoded (the gradient of `encoded`, what the caller's intermediate layer backpropagates) is written
+ * whenever it is non-NULL.  With input_grads->mention_text wanted too, the text-text edge's term goes to the raw block and
+ * the vertex's term to the encoded block; with encoded == NULL both terms land in input_grads->mention_text in one write.
+ * num_layers = 0: the score reads the vertex alone and the raw block's edge term is zero. */
+DRIN_API int drin_backward_head(const drin_config* cfg, const drin_batch* batch, const drin_params* params, void* workspace,
+                                size_t workspace_bytes, const float* grad_scores, const drin_param_grads* grads,
+                                const drin_input_grads* input_grads, void* layers_ready_event, const drin_mention_head* head,
+                                void* stream);
+
+/* drin_forward_prepared (the folded two-layer inference path) with a mention head; NULL or {LINEAR, AVG_EXTRACT}: its bits.
+ * DRIN_MENTION_ROWS: the head runs k_mention_rows and the mention-image product alone; with cfg.feature_dtype = DRIN_FEAT_BF16
+ * the raw block is read as bf16 (head->encoded stays fp32).  drin_prepare accepts params->w_mention_text == NULL for such a
+ * model (and no other NULL weight: DRIN_E_NULL) and zeroes that plane: a prepared buffer built without the Linear belongs to
+ * DRIN_MENTION_ROWS calls - passed with a NULL / LINEAR head it scores with a zero mention-text weight, silently.  drin_forward_cached takes no head (the per-entity cache is not built for these encoders). */
+DRIN_API int drin_forward_prepared_head(const drin_config* cfg, const drin_batch* batch, const drin_params* params,
+                                        const void* prepared, void* workspace, size_t workspace_bytes, float* scores,
+                                        const drin_mention_head* head, void* stream);
+
+/* The head's forward kernel on its own: edge_row [batch, width] = repr(raw), vertex_row [batch, width] = repr(encoded), or the
+ * edge row's values when encoded is NULL (the block is read once).  raw [batch, seq_len, width] is fp32 (raw_dtype =
+ * DRIN_FEAT_F32) or bf16 (DRIN_FEAT_BF16: widened exactly); encoded is fp32.  DRIN_REPR_AVG_EXTRACT reads start / end (int64
+ * [batch], drin_span_mean_fwd's clipping; an empty span gives NaN rows) and ignores max_index; DRIN_REPR_MAX_POOL ignores
+ * start / end and writes max_index [2][batch, width] (edge row's positions, then the vertex row's) with
+ * drin_seq_max_train_fwd's bits and positions.  16-byte aligned pointers, width % 4 == 0.  Profiler class DRIN_KC_POOL. */
+DRIN_API int drin_mention_rows_fwd(const void* raw, int32_t raw_dtype, const float* encoded, const int64_t* start,
+                                   const int64_t* end, int32_t representation, float* edge_row, float* vertex_row,
+                                   int32_t* max_index, int32_t batch, int32_t seq_len, int32_t width, void* stream);
+/* Its backward: grad_raw and grad_encoded [batch, seq_len, width], every element of a non-NULL one written exactly once (no
+ * atomics: the same bits every run).  An element receives g / (end - start) inside the clipped span (avg; an empty span
+ * passes zeros) or g where its position is max_index's (max), exactly 0 elsewhere.  has_encoded != 0: grad_raw takes
+ * g_edge_row's term, grad_encoded g_vertex_row's; has_encoded == 0: grad_raw takes the sum of both terms and grad_encoded
+ * must be NULL.  g_edge_row / g_vertex_row [batch, width] may be NULL (that row passes no gradient); either destination may
+ * be NULL. */
+DRIN_API int drin_mention_rows_bwd(const float* g_edge_row, const float* g_vertex_row, const int64_t* start, const int64_t* end,
+                                   const int32_t* max_index, int32_t representation, int32_t has_encoded, float* grad_raw,
+                                   float* grad_encoded, int32_t batch, int32_t seq_len, int32_t width, void* stream);
+
 /* ---- in-process kernel timing (bench.py's roofline leg) ---------------------------------------- */
 
 /* Kernel classes the launches are attributed to. */

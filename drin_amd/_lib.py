@@ -122,6 +122,11 @@ class DrinGhmfcParamsC(C.Structure):   # the 52 state-dict tensors, in state-dic
         "b_entity")]
 
 
+class DrinGhmfcTableC(C.Structure):    # drin_ghmfc_table: the table form of drin_ghmfc_forward, with the struct's own size
+    _fields_ = [("size", C.c_size_t), ("text", C.c_void_p), ("mask", C.c_void_p), ("num_entities", C.c_int64),
+                ("entity_tokens", C.c_int32), ("candidates", C.c_void_p), ("index_status", C.c_void_p), ("rows", C.c_void_p)]
+
+
 class DrinGemmRouteC(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("launches", "family", "bm", "bn", "w_planes", "a_lo", "f16", "persist", "indexed", "accumulate",
                                          "ksplit", "splits")] + [(n, C.c_int64) for n in ("tiles", "whole_tiles", "tile0", "work_items")]
@@ -246,6 +251,21 @@ EXPORTS = {
     "drin_ghmfc_workspace_bytes": (C.c_size_t, [C.POINTER(DrinGhmfcConfigC)]),
     "drin_ghmfc_forward": (C.c_int, [C.POINTER(DrinGhmfcConfigC), C.POINTER(DrinGhmfcBatchC), C.POINTER(DrinGhmfcParamsC), C.c_void_p,
                                      C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "drin_ghmfc_table_workspace_bytes": (C.c_size_t, [C.POINTER(DrinGhmfcConfigC), C.POINTER(DrinGhmfcTableC)]),
+    "drin_ghmfc_forward_table": (C.c_int, [C.POINTER(DrinGhmfcConfigC), C.POINTER(DrinGhmfcBatchC), C.POINTER(DrinGhmfcParamsC),
+                                           C.POINTER(DrinGhmfcTableC), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "drin_ghmfc_entity_rows_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
+    # (text, mask, num_entities, entity_tokens, width, w_entity, b_entity, precision, rows, workspace, workspace_bytes, stream)
+    "drin_ghmfc_entity_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                         C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    # the indexed row operations: (table, index, num_entities, out, count, width, index_status, stream),
+    # (text, mask, index, num_entities, out, pairs, tokens, width, index_status, stream),
+    # (x, rows, index, num_entities, out, batch, num_candidates, width, eps, index_status, stream)
+    "drin_gather_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
+    "drin_entity_token_mean_indexed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32,
+                                                 C.c_int32, C.c_void_p, C.c_void_p]),
+    "drin_cosine_rows_indexed_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32,
+                                               C.c_int32, C.c_float, C.c_void_p, C.c_void_p]),
     "drin_attention": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
                                  C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "drin_attention_train_fwd": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,

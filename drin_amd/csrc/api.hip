@@ -1638,8 +1638,19 @@ int drin_host_selftest(void) {
             if (precision == DRIN_PREC_F32) {
               DRIN_TRY(melhi_layout_selfcheck(b, n, c.embed_dim, c.image_dim, form ? 128 : 7));
               DRIN_TRY(ghmfc_layout_selfcheck(b, n, c.embed_dim, c.image_dim, form ? 128 : 7, form ? 49 : 4, form ? 8 : 0));
+              for (int rows = 0; rows < 2; ++rows)
+                DRIN_TRY(ghmfc_table_layout_selfcheck(b, n, c.embed_dim, c.image_dim, form ? 128 : 7, form ? 49 : 4, form ? 8 : 0, rows != 0,
+                                                      form ? 100000 : 9));
             }
           }
+  // GHMFC's table form at its tiny test widths, the reference widths and a long candidate list
+  for (int rows = 0; rows < 2; ++rows)
+    for (int b : {3, 300}) {
+      DRIN_TRY(ghmfc_table_layout_selfcheck(b, 4, 16, 32, 12, 3, 6, rows != 0, 9));
+      DRIN_TRY(ghmfc_table_layout_selfcheck(b, 4, 16, 32, 12, 3, 0, rows != 0, 9));
+      DRIN_TRY(ghmfc_table_layout_selfcheck(b, 101, 768, 2048, 128, 49, 64, rows != 0, 150));
+      DRIN_TRY(ghmfc_table_layout_selfcheck(b, 1001, 768, 2048, 128, 49, 64, rows != 0, 1 << 20));
+    }
   set_error("");
   return DRIN_OK;
 }

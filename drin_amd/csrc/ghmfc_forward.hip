@@ -1,8 +1,11 @@
 // The GHMFC baseline of the reference (baselines/ghmfc.py, model_type "ghmfc"), eval-mode scoring in one call: the workspace
 // layout, the configuration check and drin_ghmfc_forward.  What the reference computes and how the launches are laid out:
 // DESIGN.md section 15.  Every x W^T + b goes through launch_gemm_nt (the GEMM module picks the kernel); attention is the FMA
-// core (attention_fma.hip), the row kernels are ghmfc_rows.hip's.  Host code only.
+// core (attention_fma.hip), the row kernels are ghmfc_rows.hip's.  The table form (drin_ghmfc_forward_table,
+// drin_ghmfc_entity_rows) shares the mention half and reads the entity side through candidate rows of a
+// device-resident table (row kernels: ghmfc_table.hip).  Host code only.
 #include "attention_common.h"
+#include "row_checks.h"
 
 namespace drin {
 namespace {
@@ -11,7 +14,10 @@ constexpr int kChunk = 256;   // mentions per pass over the workspace
 
 struct GhmfcLayout {
   size_t a, b, kv, pool_t, pool_v, tl, vl, men, epool, ent, total_floats;   // offsets in floats
-  void build(const drin_ghmfc_config& c) {
+  // form: the gathered batch of drin_ghmfc_forward | drin_ghmfc_forward_table, whose epool also takes the gathered rows of a
+  // pooled table | the same scoring from per-entity rows: no entity regions
+  enum Form { GATHERED, TABLE, TABLE_ROWS };
+  void build(const drin_ghmfc_config& c, Form form = GATHERED) {
     const size_t Bc = c.batch < kChunk ? c.batch : kChunk, N = c.num_candidates, D = c.embed_dim, R = c.image_dim;
     const size_t L = c.mention_tokens, P = c.image_regions;
     Arena A;
@@ -20,7 +26,8 @@ struct GhmfcLayout {
     a = A.take(Bc * rows), b = A.take(Bc * rows);
     kv = A.take(Bc * 2 * mx(mx(L, P) * D, mx(L, P) * R));
     pool_t = A.take(Bc * D), pool_v = A.take(Bc * R), tl = A.take(Bc * D), vl = A.take(Bc * D), men = A.take(Bc * D);
-    epool = A.take(c.entity_tokens > 0 ? Bc * N * D : 0), ent = A.take(Bc * N * D);
+    epool = A.take(form == TABLE || (form == GATHERED && c.entity_tokens > 0) ? Bc * N * D : 0);
+    ent = A.take(form != TABLE_ROWS ? Bc * N * D : 0);
     total_floats = A.total;
   }
 };
@@ -99,6 +106,85 @@ int cross_attention_max(const drin_ghmfc_cross_params& W, const float* sa, const
   return launch_seq_max(A, pooled, Bc, La, Ea, st);
 }
 
+// the 52 state-dict tensors: none NULL, all 16-byte aligned
+int check_ghmfc_params(const char* who, const drin_ghmfc_params* p) {
+  static_assert(sizeof(drin_ghmfc_params) == 52 * sizeof(const float*), "the 52 state-dict tensors, nothing else");
+  const float* const* tensors = reinterpret_cast<const float* const*>(p);
+  for (int i = 0; i < 52; ++i) {
+    if (!tensors[i]) {
+      set_error("%s: parameter %d (state-dict order) is NULL", who, i);
+      return DRIN_E_NULL;
+    }
+    if (!aligned16(tensors[i])) {
+      set_error("%s: parameter %d (state-dict order) is not 16-byte aligned", who, i);
+      return DRIN_E_ALIGN;
+    }
+  }
+  return DRIN_OK;
+}
+
+// MultimodalFusion (ghmfc.py:141-149) of the Bc mentions from b0 on: men [Bc, D].  The mention half of drin_ghmfc_forward and
+// drin_ghmfc_forward_table: one function, the same launches.  The image mask is all ones: NULL.
+int mention_half(const drin_ghmfc_config& c, const drin_ghmfc_batch* bt, const drin_ghmfc_params* p, const GhmfcLayout& W, float* ws,
+                 int b0, int Bc, float* men, hipStream_t st) {
+  const int D = c.embed_dim, R = c.image_dim, L = c.mention_tokens, P = c.image_regions, H = c.num_heads, prec = c.precision;
+  const float* text = bt->mention_feature + (int64_t)b0 * L * D;
+  const int64_t* tmask = bt->mention_mask + (int64_t)b0 * L;
+  const float* image = bt->mention_image + (int64_t)b0 * P * R;
+  DRIN_TRY(cross_attention_max(p->t2v, text, tmask, L, D, image, nullptr, P, R, Bc, H, ws + W.a, ws + W.b, ws + W.kv, ws + W.pool_t,
+                               prec, c.layer_norm_eps, st));
+  DRIN_TRY(cross_attention_max(p->v2t, image, nullptr, P, R, text, tmask, L, D, Bc, H, ws + W.a, ws + W.b, ws + W.kv, ws + W.pool_v,
+                               prec, c.layer_norm_eps, st));
+  DRIN_TRY(launch_gemm_nt(ws + W.pool_t, D, p->w_text_linear, D, p->b_text_linear, ws + W.tl, D, Bc, D, D, false, prec, st));
+  DRIN_TRY(launch_gemm_nt(ws + W.pool_v, R, p->w_image_linear, R, p->b_image_linear, ws + W.vl, D, Bc, D, R, false, prec, st));
+  return launch_gate_mix(ws + W.tl, ws + W.vl, p->w_score_linear, p->b_score_linear, men, Bc, D, st);
+}
+
+// ---- the table form ---------------------------------------------------------------------------
+constexpr int64_t kRowsChunk = 65536;   // entities per pass of drin_ghmfc_entity_rows
+
+int check_ghmfc_table(const char* who, const drin_ghmfc_table* t, int D) {
+  if (!t) {
+    set_error("%s: table is NULL", who);
+    return DRIN_E_NULL;
+  }
+  if (t->size != sizeof(drin_ghmfc_table)) {
+    set_error("%s: table.size = %zu is not sizeof(drin_ghmfc_table) = %zu", who, t->size, sizeof(drin_ghmfc_table));
+    return DRIN_E_SHAPE;
+  }
+  if (t->num_entities < 1 || t->num_entities > INT64_MAX / 4096 / D) {
+    set_error("%s: table.num_entities = %lld is not in [1, %lld]", who, (long long)t->num_entities, (long long)(INT64_MAX / 4096 / D));
+    return DRIN_E_SHAPE;
+  }
+  if (t->entity_tokens < 0 || t->entity_tokens > kAttnMaxLk) {
+    set_error("%s: table.entity_tokens = %d is not in [0, %d]", who, t->entity_tokens, kAttnMaxLk);
+    return DRIN_E_SHAPE;
+  }
+  return DRIN_OK;
+}
+
+// the configuration the layout is built from: the call's, with the table's token count
+drin_ghmfc_config table_config(const drin_ghmfc_config& cfg, const drin_ghmfc_table& t) {
+  drin_ghmfc_config c = cfg;
+  c.entity_tokens = t.entity_tokens;
+  return c;
+}
+
+struct EntityRowsLayout {
+  size_t pool, total_floats;
+  void build(int64_t E, int T, int D) {
+    Arena A;
+    pool = A.take(T > 0 ? (size_t)(E < kRowsChunk ? E : kRowsChunk) * D : 0);
+    total_floats = A.total;
+  }
+};
+
+int check_entity_rows_shape(const char* who, int64_t E, int T, int D) {
+  DRIN_TRY(check_width4(who, D));
+  DRIN_TRY(check_count(who, "num_entities", E, 1, INT64_MAX / 4096 / D));
+  return check_count(who, "entity_tokens", T, 0, kAttnMaxLk);
+}
+
 }  // namespace
 
 int ghmfc_layout_selfcheck(int batch, int n, int d, int r, int tokens, int regions, int entity_tokens) {
@@ -114,6 +200,26 @@ int ghmfc_layout_selfcheck(int batch, int n, int d, int r, int tokens, int regio
       {"pool_v", W.pool_v, Bc * R}, {"tl", W.tl, Bc * D}, {"vl", W.vl, Bc * D}, {"men", W.men, Bc * D},
       {"epool", W.epool, entity_tokens > 0 ? Bc * N * D : 0}, {"ent", W.ent, Bc * N * D}};
   return regions_hold("GhmfcLayout", ws, (int)(sizeof(ws) / sizeof(ws[0])), W.total_floats);
+}
+
+int ghmfc_table_layout_selfcheck(int batch, int n, int d, int r, int tokens, int regions, int entity_tokens, bool from_rows, int64_t E) {
+  drin_ghmfc_config c = {};
+  c.batch = batch, c.num_candidates = n, c.embed_dim = d, c.image_dim = r, c.mention_tokens = tokens, c.image_regions = regions;
+  c.entity_tokens = entity_tokens;
+  const size_t Bc = batch < kChunk ? batch : kChunk, N = n, D = d, R = r, L = tokens, P = regions;
+  const size_t rows = L * D > P * R ? L * D : P * R, longest = L > P ? L : P, widest = D > R ? D : R;
+  GhmfcLayout W;
+  W.build(c, from_rows ? GhmfcLayout::TABLE_ROWS : GhmfcLayout::TABLE);
+  // what the launches index: the mention half as above; the gathered (or pooled) rows and their products unless from_rows
+  const Region ws[] = {
+      {"a", W.a, Bc * rows}, {"b", W.b, Bc * rows}, {"kv", W.kv, Bc * 2 * longest * widest}, {"pool_t", W.pool_t, Bc * D},
+      {"pool_v", W.pool_v, Bc * R}, {"tl", W.tl, Bc * D}, {"vl", W.vl, Bc * D}, {"men", W.men, Bc * D},
+      {"epool", W.epool, from_rows ? 0 : Bc * N * D}, {"ent", W.ent, from_rows ? 0 : Bc * N * D}};
+  DRIN_TRY(regions_hold("GhmfcLayout (table)", ws, (int)(sizeof(ws) / sizeof(ws[0])), W.total_floats));
+  EntityRowsLayout Q;
+  Q.build(E, entity_tokens, d);
+  const Region qs[] = {{"pool", Q.pool, entity_tokens > 0 ? (size_t)(E < kRowsChunk ? E : kRowsChunk) * D : 0}};
+  return regions_hold("EntityRowsLayout", qs, 1, Q.total_floats);
 }
 
 }  // namespace drin
@@ -139,18 +245,7 @@ int drin_ghmfc_forward(const drin_ghmfc_config* cfg, const drin_ghmfc_batch* bt,
     set_error("drin_ghmfc_forward: a batch tensor is NULL (entity_mask is read when entity_tokens > 0)");
     return DRIN_E_NULL;
   }
-  static_assert(sizeof(drin_ghmfc_params) == 52 * sizeof(const float*), "the 52 state-dict tensors, nothing else");
-  const float* const* tensors = reinterpret_cast<const float* const*>(p);
-  for (int i = 0; i < 52; ++i) {
-    if (!tensors[i]) {
-      set_error("drin_ghmfc_forward: parameter %d (state-dict order) is NULL", i);
-      return DRIN_E_NULL;
-    }
-    if (!aligned16(tensors[i])) {
-      set_error("drin_ghmfc_forward: parameter %d (state-dict order) is not 16-byte aligned", i);
-      return DRIN_E_ALIGN;
-    }
-  }
+  DRIN_TRY(check_ghmfc_params("drin_ghmfc_forward", p));
   GhmfcLayout W;
   W.build(c);
   if (workspace_bytes < W.total_floats * sizeof(float)) {
@@ -166,23 +261,12 @@ int drin_ghmfc_forward(const drin_ghmfc_config* cfg, const drin_ghmfc_batch* bt,
   RoctxRange range("drin_ghmfc_forward");
   hipStream_t st = (hipStream_t)stream;
   float* ws = static_cast<float*>(workspace);
-  const int N = c.num_candidates, D = c.embed_dim, R = c.image_dim, L = c.mention_tokens, P = c.image_regions, H = c.num_heads;
-  const int T = c.entity_tokens, prec = c.precision;
+  const int N = c.num_candidates, D = c.embed_dim, T = c.entity_tokens, prec = c.precision;
   // rows are independent: the chunking changes no result
   for (int b0 = 0; b0 < c.batch; b0 += kChunk) {
     const int Bc = c.batch - b0 < kChunk ? c.batch - b0 : kChunk;
-    const float* text = bt->mention_feature + (int64_t)b0 * L * D;
-    const int64_t* tmask = bt->mention_mask + (int64_t)b0 * L;
-    const float* image = bt->mention_image + (int64_t)b0 * P * R;
-    // MultimodalFusion (ghmfc.py:141-149); the image mask is all ones: NULL
-    DRIN_TRY(cross_attention_max(p->t2v, text, tmask, L, D, image, nullptr, P, R, Bc, H, ws + W.a, ws + W.b, ws + W.kv, ws + W.pool_t,
-                                 prec, c.layer_norm_eps, st));
-    DRIN_TRY(cross_attention_max(p->v2t, image, nullptr, P, R, text, tmask, L, D, Bc, H, ws + W.a, ws + W.b, ws + W.kv, ws + W.pool_v,
-                                 prec, c.layer_norm_eps, st));
-    DRIN_TRY(launch_gemm_nt(ws + W.pool_t, D, p->w_text_linear, D, p->b_text_linear, ws + W.tl, D, Bc, D, D, false, prec, st));
-    DRIN_TRY(launch_gemm_nt(ws + W.pool_v, R, p->w_image_linear, R, p->b_image_linear, ws + W.vl, D, Bc, D, R, false, prec, st));
     float* men = mention_repr ? mention_repr + (int64_t)b0 * D : ws + W.men;
-    DRIN_TRY(launch_gate_mix(ws + W.tl, ws + W.vl, p->w_score_linear, p->b_score_linear, men, Bc, D, st));
+    DRIN_TRY(mention_half(c, bt, p, W, ws, b0, Bc, men, st));
     // EntityEncoder (ghmfc.py:237-250) and the cosine (:297-298)
     const int64_t pairs = (int64_t)Bc * N;
     const float* ent_in = bt->entity_feature + (int64_t)b0 * N * D;
@@ -196,3 +280,119 @@ int drin_ghmfc_forward(const drin_ghmfc_config* cfg, const drin_ghmfc_batch* bt,
   }
   return DRIN_OK;
 }
+
+size_t drin_ghmfc_table_workspace_bytes(const drin_ghmfc_config* cfg, const drin_ghmfc_table* table) {
+  if (validate_ghmfc_config(cfg) != DRIN_OK || check_ghmfc_table("drin_ghmfc_table_workspace_bytes", table, cfg->embed_dim) != DRIN_OK)
+    return 0;
+  GhmfcLayout W;
+  W.build(table_config(*cfg, *table), table->rows ? GhmfcLayout::TABLE_ROWS : GhmfcLayout::TABLE);
+  return W.total_floats * sizeof(float);
+}
+
+int drin_ghmfc_forward_table(const drin_ghmfc_config* cfg, const drin_ghmfc_batch* bt, const drin_ghmfc_params* p,
+                             const drin_ghmfc_table* table, void* workspace, size_t workspace_bytes, float* scores, float* mention_repr,
+                             void* stream) {
+  const char* who = "drin_ghmfc_forward_table";
+  DRIN_TRY(validate_ghmfc_config(cfg));
+  if (!bt || !p || !workspace || !scores) {
+    set_error("%s: batch / params / workspace / scores is NULL", who);
+    return DRIN_E_NULL;
+  }
+  DRIN_TRY(check_ghmfc_table(who, table, cfg->embed_dim));
+  const drin_ghmfc_table& t = *table;
+  const drin_ghmfc_config c = table_config(*cfg, t);
+  if (!bt->mention_feature || !bt->mention_mask || !bt->mention_image || !t.candidates ||
+      (!t.rows && (!t.text || (t.entity_tokens > 0 && !t.mask)))) {
+    set_error("%s: a mention tensor, table.candidates or - without table.rows - table.text / table.mask (read when entity_tokens > 0) is NULL",
+              who);
+    return DRIN_E_NULL;
+  }
+  DRIN_TRY(check_ghmfc_params(who, p));
+  GhmfcLayout W;
+  W.build(c, t.rows ? GhmfcLayout::TABLE_ROWS : GhmfcLayout::TABLE);
+  if (workspace_bytes < W.total_floats * sizeof(float)) {
+    set_error("%s: workspace %zu bytes < %zu", who, workspace_bytes, W.total_floats * sizeof(float));
+    return DRIN_E_WORKSPACE;
+  }
+  if (!aligned16(workspace) || !aligned16(bt->mention_feature) || !aligned16(bt->mention_image) || (mention_repr && !aligned16(mention_repr)) ||
+      (t.rows ? !aligned16(t.rows) : !aligned16(t.text)) || (reinterpret_cast<uintptr_t>(t.candidates) & 7u) != 0 ||
+      (reinterpret_cast<uintptr_t>(t.index_status) & 3u) != 0) {
+    set_error("%s: workspace, feature tensors, table.text / table.rows and mention_repr must be 16-byte aligned, table.candidates 8-byte, "
+              "table.index_status 4-byte", who);
+    return DRIN_E_ALIGN;
+  }
+  DRIN_BIND_DEVICE(stream, scores, who);
+  RoctxRange range(who);
+  hipStream_t st = (hipStream_t)stream;
+  float* ws = static_cast<float*>(workspace);
+  const int N = c.num_candidates, D = c.embed_dim, T = c.entity_tokens, prec = c.precision;
+  for (int b0 = 0; b0 < c.batch; b0 += kChunk) {
+    const int Bc = c.batch - b0 < kChunk ? c.batch - b0 : kChunk;
+    float* men = mention_repr ? mention_repr + (int64_t)b0 * D : ws + W.men;
+    DRIN_TRY(mention_half(c, bt, p, W, ws, b0, Bc, men, st));
+    const int64_t pairs = (int64_t)Bc * N, p0 = (int64_t)b0 * N;
+    const int64_t* cand = t.candidates + p0;
+    if (t.rows) {   // per-entity rows (drin_ghmfc_entity_rows): the entity half is one cosine against gathered rows
+      DRIN_TRY(launch_cosine_gather(men, t.rows, cand, t.num_entities, scores + p0, Bc, N, D, c.cosine_eps, t.index_status, p0, st));
+      continue;
+    }
+    // EntityEncoder (ghmfc.py:237-250) on the rows data.py's qid2idx gather would have delivered, and the cosine (:297-298): the
+    // operands of the product and of k_cosine_rows are drin_ghmfc_forward's values in its shapes
+    if (T > 0)
+      DRIN_TRY(launch_entity_token_mean_indexed(t.text, t.mask, cand, t.num_entities, ws + W.epool, pairs, T, D, t.index_status, p0, st));
+    else
+      DRIN_TRY(launch_gather_rows(t.text, cand, t.num_entities, ws + W.epool, pairs, D, t.index_status, p0, st));
+    DRIN_TRY(launch_gemm_nt(ws + W.epool, D, p->w_entity, D, p->b_entity, ws + W.ent, D, pairs, D, D, false, prec, st));
+    DRIN_TRY(launch_cosine_rows(men, ws + W.ent, D, scores + p0, Bc, N, D, c.cosine_eps, 1.0f, st));
+  }
+  return DRIN_OK;
+}
+
+size_t drin_ghmfc_entity_rows_workspace_bytes(int64_t num_entities, int32_t entity_tokens, int32_t width) {
+  if (check_entity_rows_shape("drin_ghmfc_entity_rows_workspace_bytes", num_entities, entity_tokens, width) != DRIN_OK) return 0;
+  EntityRowsLayout Q;
+  Q.build(num_entities, entity_tokens, width);
+  return Q.total_floats * sizeof(float);
+}
+
+int drin_ghmfc_entity_rows(const float* text, const int64_t* mask, int64_t num_entities, int32_t entity_tokens, int32_t width,
+                           const float* w_entity, const float* b_entity, int32_t precision, float* rows, void* workspace,
+                           size_t workspace_bytes, void* stream) {
+  const char* who = "drin_ghmfc_entity_rows";
+  if (!text || !w_entity || !b_entity || !rows || (entity_tokens > 0 && (!mask || !workspace))) {
+    set_error("%s: text / w_entity / b_entity / rows is NULL (mask and the workspace are read when entity_tokens > 0)", who);
+    return DRIN_E_NULL;
+  }
+  DRIN_TRY(check_entity_rows_shape(who, num_entities, entity_tokens, width));
+  if (precision != DRIN_PREC_F32 && precision != DRIN_PREC_BF16X3) {
+    set_error("%s: precision %d is not DRIN_PREC_F32 / DRIN_PREC_BF16X3", who, precision);
+    return DRIN_E_UNSUPPORTED;
+  }
+  if (!aligned16(text) || !aligned16(w_entity) || !aligned16(b_entity) || !aligned16(rows) || !aligned16(workspace)) {
+    set_error("%s: text, w_entity, b_entity, rows and the workspace must be 16-byte aligned", who);
+    return DRIN_E_ALIGN;
+  }
+  EntityRowsLayout Q;
+  Q.build(num_entities, entity_tokens, width);
+  if (workspace_bytes < Q.total_floats * sizeof(float)) {
+    set_error("%s: workspace %zu bytes < %zu", who, workspace_bytes, Q.total_floats * sizeof(float));
+    return DRIN_E_WORKSPACE;
+  }
+  DRIN_BIND_DEVICE(stream, rows, who);
+  RoctxRange range(who);
+  hipStream_t st = (hipStream_t)stream;
+  const int T = entity_tokens, D = width;
+  // final_layer(pool(text[e])) (ghmfc.py:245-250) once per ENTITY instead of once per pair; entities are independent
+  for (int64_t e0 = 0; e0 < num_entities; e0 += kRowsChunk) {
+    const int64_t n = num_entities - e0 < kRowsChunk ? num_entities - e0 : kRowsChunk;
+    const float* in = text + e0 * D;
+    if (T > 0) {
+      float* pool = static_cast<float*>(workspace) + Q.pool;
+      DRIN_TRY(launch_entity_token_mean(text + e0 * T * D, mask + e0 * T, pool, n, T, D, st));
+      in = pool;
+    }
+    DRIN_TRY(launch_gemm_nt(in, D, w_entity, D, b_entity, rows + e0 * D, D, n, D, D, false, precision, st));
+  }
+  return DRIN_OK;
+}
+

@@ -133,6 +133,17 @@ int launch_entity_token_mean(const float* feat, const int64_t* mask, float* out,
                              hipStream_t st);
 int launch_entity_token_mean_bf16(const void* feat, const int64_t* mask, float* out, int64_t pairs, int T, int D,
                                   hipStream_t st);
+// the same mean of row index[p] of the tables text [E, T, D] / mask [E, T] (fp32): the index is clamped into [0, E - 1] before
+// it is used and reported into status (int32[4] or NULL; device_utils.h: report_bad_index) as pair pair_base + p
+int launch_entity_token_mean_indexed(const float* text, const int64_t* mask, const int64_t* index, int64_t num_rows, float* out,
+                                     int64_t pairs, int T, int D, int32_t* status, int64_t pair_base, hipStream_t st);
+// the other row kernels of GHMFC's table form (ghmfc_table.hip), the same clamp and report:
+// out[i, :] = table[index[i], :] for [E, width] fp32 rows
+int launch_gather_rows(const float* table, const int64_t* index, int64_t num_rows, float* out, int64_t count, int width,
+                       int32_t* status, int64_t pair_base, hipStream_t st);
+// out[b * N + n] = cos(x[b, :], rows[index[b * N + n], :]): k_cosine_rows' lane loop on a clamped row
+int launch_cosine_gather(const float* x, const float* rows, const int64_t* index, int64_t num_rows, float* out, int B, int N, int D,
+                         float eps, int32_t* status, int64_t pair_base, hipStream_t st);
 // out[b*N + n] = scale * cos(x[b, :], y[(b*N + n) * y_stride : +D])
 // (sim1 / sim2 -> out1 / out2: optional [B*N] arrays divided by `div` in the same pass: the CLIP edges of model.py:203)
 int launch_cosine_rows(const float* x, const float* y, int64_t y_stride, float* out, int B, int N, int D, float eps,
@@ -564,5 +575,8 @@ int fused_layout_selfcheck(const drin_config& c);    // FusedLayout, Prepared (f
 int cached_layout_selfcheck(const drin_config& c);   // CachedLayout (entity_cache.hip)
 int melhi_layout_selfcheck(int B, int N, int D, int R, int L);           // MelhiLayout (melhi_kernels.hip)
 int ghmfc_layout_selfcheck(int B, int N, int D, int R, int L, int P, int T);   // GhmfcLayout (ghmfc_forward.hip)
+// the same layout as drin_ghmfc_forward_table carves it (rows: scored from per-entity rows, no entity regions), and the chunk
+// buffer of drin_ghmfc_entity_rows for E entities
+int ghmfc_table_layout_selfcheck(int B, int N, int D, int R, int L, int P, int T, bool rows, int64_t E);
 
 }  // namespace drin

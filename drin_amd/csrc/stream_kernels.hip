@@ -115,21 +115,37 @@ int launch_span_mean_bf16(const void* seq, const int64_t* start, const int64_t* 
 // Only the rows inside the slice are read (the compulsory bytes).  One block per pair;
 // each thread owns float4 columns and keeps 8 token rows in flight.
 // T_ = float or __bf16 (features stored as bf16: values widen exactly, the sums are the fp32 sums of the widened rows).
-template <typename T_>
+// INDEXED (drin_entity_token_mean_indexed; the table form of GHMFC): feat / mask are tables [E, T, D] /
+// [E, T] and pair p pools row rows.index[p], clamped into [0, E - 1] BEFORE any address is formed and reported
+// (report_bad_index, pair rows.pair_base + p); out stays per pair.  The same walk over the same values: the bits of the
+// plain form on the gathered block.  INDEXED = false never looks at `rows`.
+struct TableRows {
+  const int64_t* index;   // [pairs]
+  int64_t num_rows;       // E
+  int64_t pair_base;      // what is added to p in a report (a chunk of a larger call)
+  int32_t* status;        // int32[4] or NULL
+};
+template <typename T_, bool INDEXED>
 __global__ void __launch_bounds__(256) k_entity_token_mean(const T_* __restrict__ feat,
                                                            const int64_t* __restrict__ mask, float* __restrict__ out,
-                                                           int T, int D4) {
+                                                           int T, int D4, TableRows rows) {
   const int64_t p = blockIdx.x;
+  int64_t src = p;
+  if constexpr (INDEXED) {
+    const int64_t raw = rows.index[p];
+    src = raw < 0 ? 0 : (raw >= rows.num_rows ? rows.num_rows - 1 : raw);
+    if (src != raw && threadIdx.x == 0) report_bad_index(rows.status, rows.pair_base + p, raw);
+  }
   // every wave recomputes ntok (T <= 512 int64 values, L2/L1 resident) - cheaper than a barrier
   int cnt = 0;
-  for (int t = threadIdx.x & 63; t < T; t += 64) cnt += (int)mask[p * T + t];
+  for (int t = threadIdx.x & 63; t < T; t += 64) cnt += (int)mask[src * T + t];
   cnt = (int)wave_sum((float)cnt);  // T <= 2^24: exact in fp32
   int stop = cnt - 1;
   if (stop < 0) stop += T;  // python negative stop index (ntok == 0 -> 1:-1)
   if (stop < 0) stop = 0;
   if (stop > T) stop = T;
   const int n = stop - 1;  // rows 1 .. stop-1
-  const T_* base = feat + p * (int64_t)T * D4 * 4;
+  const T_* base = feat + src * (int64_t)T * D4 * 4;
   for (int c4 = threadIdx.x; c4 < D4; c4 += blockDim.x) {
     const T_* col = base + (int64_t)c4 * 4;
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -147,9 +163,9 @@ __global__ void __launch_bounds__(256) k_entity_token_mean(const T_* __restrict_
   }
 }
 
-template <typename T_>
+template <typename T_, bool INDEXED = false>
 static int launch_entity_token_mean_t(const T_* feat, const int64_t* mask, float* out, int64_t pairs, int T, int D,
-                                      hipStream_t st) {
+                                      hipStream_t st, TableRows rows = TableRows{}) {
   if (pairs <= 0) return DRIN_OK;
   if (D % 4 != 0 || T <= 0) {
     set_error("entity_token_mean: D=%d must be a multiple of 4, T=%d positive", D, T);
@@ -158,7 +174,7 @@ static int launch_entity_token_mean_t(const T_* feat, const int64_t* mask, float
   const int D4 = D / 4;
   int threads = D4 >= 192 ? 192 : (D4 > 64 ? 128 : 64);  // D = 768 -> one float4 column per thread, 3 waves
   KernelTimer timer(DRIN_KC_POOL, st);
-  hipLaunchKernelGGL(k_entity_token_mean<T_>, dim3((unsigned)pairs), dim3(threads), 0, st, feat, mask, out, T, D4);
+  hipLaunchKernelGGL((k_entity_token_mean<T_, INDEXED>), dim3((unsigned)pairs), dim3(threads), 0, st, feat, mask, out, T, D4, rows);
   DRIN_CHECK_LAUNCH("k_entity_token_mean");
   return DRIN_OK;
 }
@@ -170,6 +186,10 @@ int launch_entity_token_mean(const float* feat, const int64_t* mask, float* out,
 int launch_entity_token_mean_bf16(const void* feat, const int64_t* mask, float* out, int64_t pairs, int T, int D,
                                   hipStream_t st) {
   return launch_entity_token_mean_t<__bf16>(static_cast<const __bf16*>(feat), mask, out, pairs, T, D, st);
+}
+int launch_entity_token_mean_indexed(const float* text, const int64_t* mask, const int64_t* index, int64_t num_rows, float* out,
+                                     int64_t pairs, int T, int D, int32_t* status, int64_t pair_base, hipStream_t st) {
+  return launch_entity_token_mean_t<float, true>(text, mask, out, pairs, T, D, st, TableRows{index, num_rows, pair_base, status});
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -16,6 +16,7 @@ from torch import nn
 
 from . import _lib
 from ._lib import _ptr, _stream
+from .ghmfc_table import GhmfcIndexedBatch, TableForm
 
 PRECISIONS = {"bf16x3": _lib.PREC_BF16X3, "f32": _lib.PREC_F32}
 
@@ -104,13 +105,16 @@ class _EntityEncoder(nn.Module):
         self.final_layer = nn.Linear(cfg.embed_dim, cfg.embed_dim)
 
 
-class Model(nn.Module):
+class Model(TableForm, nn.Module):
     """ghmfc.py's `Model` for scoring: the same modules, created in the same order (so `torch.manual_seed(s); Model()` draws the
     reference's weights) and the same 52 state-dict keys; a trained checkpoint loads with `load_state_dict`.
     `forward(batch)` takes the reference's 8-item offline batch (mention_feature, mention_mask, begin, end, mention_image,
     entity_feature, entity_mask, entity_image) and returns scores [B, N]; `encode_mentions(batch)` the [B, D] mention
     representations.  Eval mode only, no gradients.  `precision`: "bf16x3" (split-bf16 products, the default) or "f32"
-    (exact fp32 MFMA); attention, LayerNorm and the gate are fp32 FMA in both."""
+    (exact fp32 MFMA); attention, LayerNorm and the gate are fp32 FMA in both.
+    The table form (`drin_amd.ghmfc_table.TableForm`): a `GhmfcIndexedBatch`, or - after
+    `attach_entity_table(table)` - an 8-item batch whose item 5 is the integer tensor `[B, N]` of candidate rows, is scored by
+    `drin_ghmfc_forward_table` with the bits of the gathered batch; `enable_entity_cache()` scores against per-entity rows."""
 
     def __init__(self, cfg: GhmfcConfig | None = None, precision: str = "bf16x3"):
         super().__init__()
@@ -157,12 +161,65 @@ class Model(nn.Module):
             raise ValueError(f"ghmfc batch shapes {got}, entity_feature {tuple(ef.shape)} do not match the configuration {cfg}")
         return mf, mmask, mimage, ef, emask, tokens
 
+    def _mention_tensors(self, mention):
+        """(mention_feature, mention_mask, mention_image) of the five mention-side items of a table-form batch, prepared and
+        checked like `_batch_tensors`' (begin and end are not read)."""
+        mf, mmask, _begin, _end, mimage = mention
+        dev = self.entity_encoder.final_layer.weight.device
+        if dev.type != "cuda" or (isinstance(mf, torch.Tensor) and mf.device.type != "cuda"):
+            raise RuntimeError("drin_amd.ghmfc.Model runs on the GPU only (no CPU fallback): move the model and the batch with .cuda()")
+        cfg = self.cfg
+        f = lambda t: t.detach().to(dev, torch.float32).contiguous()          # noqa: E731
+        mf, mimage = f(mf), f(mimage)
+        mmask = torch.as_tensor(mmask).to(dev, torch.int64).contiguous()
+        B = mf.shape[0]
+        want = (B, cfg.mention_tokens, cfg.embed_dim), (B, cfg.mention_tokens), (B, cfg.image_regions, cfg.image_dim)
+        got = tuple(mf.shape), tuple(mmask.shape), tuple(mimage.shape)
+        if got != want:
+            raise ValueError(f"ghmfc batch shapes {got} do not match the configuration {cfg}")
+        return mf, mmask, mimage
+
+    def _score_table(self, tb: GhmfcIndexedBatch, want_scores: bool):
+        """`_score` of a table-form batch: `drin_ghmfc_forward_table`, from the cached per-entity rows when enabled."""
+        mf, mmask, mimage = self._mention_tensors(tb.mention)
+        cfg, dev, B = self.cfg, mf.device, mf.shape[0]
+        if tb.candidates.shape[0] != B:
+            raise ValueError(f"ghmfc table form: candidates {tuple(tb.candidates.shape)} for {B} mentions")
+        lib = _lib.load()
+        text = tb.table.text.contiguous()
+        tokens = text.shape[1] if text.dim() == 3 else 0
+        mask = tb.table.mask.to(torch.int64).contiguous() if tokens else None
+        rows = self._entity_rows(tb.table) if (self._tf.cache_on and want_scores) else None
+        c = _lib.DrinGhmfcConfigC(batch=B, num_candidates=cfg.num_candidates, embed_dim=cfg.embed_dim, image_dim=cfg.image_dim,
+                                  mention_tokens=cfg.mention_tokens, image_regions=cfg.image_regions, num_heads=cfg.num_heads,
+                                  entity_tokens=tokens, precision=PRECISIONS[self.precision], layer_norm_eps=cfg.layer_norm_eps,
+                                  cosine_eps=cfg.cosine_eps)
+        params = [p.detach().contiguous() for p in self.param_list()]
+        bt = _lib.DrinGhmfcBatchC(_ptr(mf), _ptr(mmask), _ptr(mimage), None, None)
+        pc = _lib.DrinGhmfcParamsC.from_buffer_copy((C.c_void_p * 52)(*[p.data_ptr() for p in params]))
+        status = self._status_words(dev)
+        tc = _lib.DrinGhmfcTableC(size=C.sizeof(_lib.DrinGhmfcTableC), text=_ptr(text), mask=_ptr(mask), num_entities=text.shape[0],
+                                  entity_tokens=tokens, candidates=_ptr(tb.candidates), index_status=_ptr(status), rows=_ptr(rows))
+        nbytes = lib.drin_ghmfc_table_workspace_bytes(C.byref(c), C.byref(tc))
+        if nbytes == 0:
+            _lib.check(_lib.E_SHAPE)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        scores = torch.empty(B, cfg.num_candidates, dtype=torch.float32, device=dev)
+        mention = torch.empty(B, cfg.embed_dim, dtype=torch.float32, device=dev)
+        _lib.check(lib.drin_ghmfc_forward_table(C.byref(c), C.byref(bt), C.byref(pc), C.byref(tc), _ptr(ws), nbytes, _ptr(scores),
+                                                _ptr(mention), _stream(dev)))
+        self._watch_indices(dev)
+        return scores if want_scores else mention
+
     def _run(self, batch, want_scores: bool):
         if self.training:
             raise RuntimeError("drin_amd.ghmfc.Model is scoring only: call .eval(); GHMFC training is not implemented, DESIGN.md §11")
         return self._score(batch, want_scores)
 
     def _score(self, batch, want_scores: bool):
+        tb = self._table_form(batch)
+        if tb is not None:
+            return self._score_table(tb, want_scores)
         mf, mmask, mimage, ef, emask, tokens = self._batch_tensors(batch)
         cfg, dev, B = self.cfg, mf.device, mf.shape[0]
         lib = _lib.load()

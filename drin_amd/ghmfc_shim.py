@@ -7,6 +7,7 @@ In a checkout of the reference the binding is one changed line of `train.py`:
 
 `Model()` takes no argument and reads `common.args` (imported at call time); `create_datasets()` gives the [train, valid,
 test] loaders of the offline path of `baselines/data.py` (the same `.npy` files, the same 9-item batches) on either dataset.
+DRIN_GHMFC_TABLE=1 (WikiMEL) selects the table form of both (`drin_amd.ghmfc_table`, `drin_amd.ghmfc_data`).
 """
 from __future__ import annotations
 
@@ -29,6 +30,18 @@ def _args():
     return importlib.import_module("common.args")
 
 
+def _table_form() -> bool:
+    """DRIN_GHMFC_TABLE=1: the table form - `create_datasets()` gives the indexed loaders and `Model()`
+    loads the WikiMEL entity table and attaches it (it follows the model to its device)."""
+    return os.environ.get("DRIN_GHMFC_TABLE", "") not in ("", "0")
+
+
+def _attach_table(model, a):
+    from .ghmfc_data import _setup, load_entity_table
+    _setup(a)                                                                  # WikiDiverse has no shared table: refused
+    return model.attach_entity_table(load_entity_table(a.preprocess_dir, "cpu", getattr(a, "entity_text_type", "attr")))
+
+
 class Model(_Model):
     """`model_module.Model()`: geometry and `transformer_dropout` from `common.args`; split-bf16 products unless
     DRIN_PRECISION=f32; the softmax-attention core of DRIN_ATTENTION_CORE ("fma", the default, or "mfma").  The attention dropout of train() mode is the library's own mask, seeded by `args.seed`.  With another
@@ -40,14 +53,17 @@ class Model(_Model):
         cfg = variant_config_from_reference_args(a)
         if cfg.is_default:
             return super().__new__(cls)
-        return VariantModel(cfg, precision=os.environ.get("DRIN_PRECISION", "bf16x3"), dropout=getattr(a, "transformer_dropout", 0.1),
-                            seed=getattr(a, "seed", 0), core=os.environ.get("DRIN_ATTENTION_CORE", "fma"))
+        model = VariantModel(cfg, precision=os.environ.get("DRIN_PRECISION", "bf16x3"), dropout=getattr(a, "transformer_dropout", 0.1),
+                             seed=getattr(a, "seed", 0), core=os.environ.get("DRIN_ATTENTION_CORE", "fma"))
+        return _attach_table(model, a) if _table_form() else model
 
     def __init__(self):
         a = _args()
         super().__init__(config_from_reference_args(a), precision=os.environ.get("DRIN_PRECISION", "bf16x3"),
                          dropout=getattr(a, "transformer_dropout", 0.1), seed=getattr(a, "seed", 0),
                          core=os.environ.get("DRIN_ATTENTION_CORE", "fma"))
+        if _table_form():
+            _attach_table(self, a)
 
 
 class GhmfcData(Dataset):
@@ -100,6 +116,9 @@ def create_datasets() -> List[DataLoader]:
     cfg = variant_config_from_reference_args(a)
     if cfg.is_default:
         config_from_reference_args(a)                                          # the default's own refusals
+    if _table_form():
+        from .ghmfc_data import create_indexed_datasets
+        return create_indexed_datasets(a)
     loaders = []
     for split in SPLITS:
         ds = GhmfcData(a.preprocess_dir, split, cfg.dataset_name, cfg.num_candidates, cfg.embed_dim,

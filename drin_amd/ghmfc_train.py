@@ -66,6 +66,8 @@ class TrainableModel(Model):
     `max_indices == {"text": idx [B, D], "image": idx [B, R]}` (int32) holds the position each max over the sequence took its
     value from - the lowest one on a tie, which is where the gradient goes.  The batch tensors are detached: their gradients
     are out of scope.  A 2-token WikiMEL entity gives a NaN row, as in the reference.  CPU tensors are refused.
+    Table form (`drin_amd.ghmfc_table`): a training step gathers the candidates' rows of the once-pooled table and runs the
+    same `entity_scores` on them - the scores and gradients of the gathered-batch step, bit for bit.
     `core`: the softmax-attention core of the training forward and backward, "fma" (the default) or "mfma"
     (`drin_amd.attention.attention_core`); `eval()` scores through `drin_ghmfc_forward`, whose core is the FMA one."""
 
@@ -86,7 +88,12 @@ class TrainableModel(Model):
     def _run(self, batch, want_scores: bool):
         if not self.training:
             return self._score(batch, want_scores)
-        mf, mmask, mimage, ef, emask, tokens = self._batch_tensors(batch)
+        tb = self._table_form(batch)
+        if tb is None:
+            mf, mmask, mimage, ef, emask, tokens = self._batch_tensors(batch)
+        else:                                                                  # table form: pooled candidate rows [B, N, D], gathered
+            mf, mmask, mimage = self._mention_tensors(tb.mention)
+            ef, emask = (self._train_candidates(tb) if want_scores else None), None
         cfg, prec = self.cfg, PRECISIONS[self.precision]
         f = self.mention_encoder.intermediate_layer
         padding = mmask == 0                                                   # nn.MultiheadAttention: True = drop the key

@@ -17,6 +17,7 @@ from torch import nn
 
 from .attention import PRECISIONS, DropoutStream, _linear, multihead_attention_forward
 from .ghmfc import GhmfcConfig, _CrossAttention, _EntityEncoder
+from .ghmfc_table import TableForm
 from .ghmfc_train import TrainableModel, attention_factory, check_setup, cross_attention, entity_scores
 from .row_ops import act_dropout, layer_norm_res, seq_max, span_mean
 
@@ -164,7 +165,7 @@ class _VariantMentionEncoder(nn.Module):
             self.intermediate_layer = _CrossAttention(D, cfg.image_dim, cfg.num_heads, dropout, attention)
 
 
-class VariantModel(nn.Module):
+class VariantModel(TableForm, nn.Module):
     """ghmfc.py's `Model` with one of the other mention encoders: the reference's modules created in its order (the same
     state-dict keys and the same initial draw under one `torch.manual_seed`; a reference checkpoint loads).  With the default
     configuration (`"multimodal"`, `"bi"`) the constructor returns a `TrainableModel`.
@@ -183,7 +184,9 @@ class VariantModel(nn.Module):
     kept key), so its scores are finite - the library's definition; torch has two answers there (NaN on its fused inference
     path, finite under autograd).  Batch tensors are detached: their gradients are out of scope.  CPU tensors are refused.
     `core`: the softmax-attention core of every attention of the model, "fma" (the default) or "mfma"
-    (`drin_amd.attention.attention_core`), in `train()` and `eval()` alike."""
+    (`drin_amd.attention.attention_core`), in `train()` and `eval()` alike.
+    Table form (`drin_amd.ghmfc_table.TableForm`): the mention representation as above, the entity side through the indexed row
+    kernels - the bits of the gathered batch; `enable_entity_cache()` scores `eval()` calls against per-entity rows."""
 
     def __new__(cls, cfg: VariantConfig | None = None, precision: str = "bf16x3", dropout: float = 0.1, seed: int = 0,
                 core: str = "fma"):
@@ -202,8 +205,10 @@ class VariantModel(nn.Module):
         self.entity_encoder = _EntityEncoder(cfg)
 
     # ---- the batch ---------------------------------------------------------------------------------------------
-    def _batch_tensors(self, batch):
-        mf, mmask, begin, end, mimage, ef, emask = batch[:7]
+    def _batch_tensors(self, batch, table_form: bool = False):
+        """table_form: items 5 and 6 are not the entity features (ef comes back as None: the caller reads the table)"""
+        mf, mmask, begin, end, mimage = batch[:5]
+        ef, emask = (None, None) if table_form else batch[5:7]
         dev = self.entity_encoder.final_layer.weight.device
         if dev.type != "cuda" or (isinstance(mf, torch.Tensor) and mf.device.type != "cuda"):
             raise RuntimeError("drin_amd.ghmfc_variants.VariantModel runs on the GPU only (no CPU fallback): move the model and the "
@@ -211,9 +216,16 @@ class VariantModel(nn.Module):
         cfg = self.cfg
         f = lambda t: t.detach().to(dev, torch.float32).contiguous()          # noqa: E731
         i = lambda t: torch.as_tensor(t).detach().to(dev, torch.int64).contiguous()   # noqa: E731
-        mf, ef, mmask, begin, end = f(mf), f(ef), i(mmask), i(begin), i(end)
+        mf, mmask, begin, end = f(mf), i(mmask), i(begin), i(end)
         mimage = f(mimage) if cfg.reads_mention_image else None
         B = mf.shape[0]
+        if table_form:
+            got = tuple(mf.shape), tuple(mmask.shape), tuple(begin.shape), tuple(end.shape)
+            want = (B, cfg.mention_tokens, cfg.embed_dim), (B, cfg.mention_tokens), (B,), (B,)
+            if got != want or (mimage is not None and tuple(mimage.shape) != (B, cfg.image_regions, cfg.image_dim)):
+                raise ValueError(f"ghmfc batch shapes {got} do not match the configuration {cfg}")
+            return mf, mmask, begin, end, mimage, None, None
+        ef = f(ef)
         if ef.dim() == 4:                                                      # WikiMEL: [B, N, T, D] + entity_mask [B, N, T]
             emask = i(emask)
             if tuple(emask.shape) != tuple(ef.shape[:3]):
@@ -264,10 +276,17 @@ class VariantModel(nn.Module):
         return self._compose(batch, want_scores)
 
     def _compose(self, batch, want_scores: bool):
-        mf, mmask, begin, end, mimage, ef, emask = self._batch_tensors(batch)
+        tb = self._table_form(batch)
+        mf, mmask, begin, end, mimage, ef, emask = self._batch_tensors(batch if tb is None else tb.mention, tb is not None)
         mention = self._mention(mf, mmask, begin, end, mimage)
         if not want_scores:
             return mention
+        if tb is not None:
+            if tb.candidates.shape[0] != mf.shape[0]:
+                raise ValueError(f"ghmfc table form: candidates {tuple(tb.candidates.shape)} for {mf.shape[0]} mentions")
+            if not self.training:
+                return self._eval_scores(tb, mention)
+            ef = self._train_candidates(tb)
         return entity_scores(mention, ef, emask, self.entity_encoder.final_layer, self.cfg, self.precision)
 
     def forward(self, batch) -> torch.Tensor:

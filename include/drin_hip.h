@@ -747,6 +747,41 @@ DRIN_API size_t drin_ghmfc_workspace_bytes(const drin_ghmfc_config* cfg);
 DRIN_API int drin_ghmfc_forward(const drin_ghmfc_config* cfg, const drin_ghmfc_batch* batch, const drin_ghmfc_params* params,
                                 void* workspace, size_t workspace_bytes, float* scores, float* mention_repr, void* stream);
 
+/* The table form of drin_ghmfc_forward: the candidates of a mention are rows of a device-resident entity
+ * table, as on WikiMEL, where the reference's loader gathers them on the host (baselines/data.py: the qid2idx gather,
+ * `entity_feature[rows]`, 19.9 MB per mention at the reference widths).  `size` = sizeof(drin_ghmfc_table). */
+typedef struct {
+  size_t size;
+  const float* text;         /* [num_entities, entity_tokens, D], or pooled [num_entities, D] when entity_tokens = 0; not read with rows */
+  const int64_t* mask;       /* [num_entities, entity_tokens] when entity_tokens > 0, else not read                                     */
+  int64_t num_entities;      /* E >= 1                                                                                                   */
+  int32_t entity_tokens;     /* T of the TABLE (0 .. 512); drin_ghmfc_config.entity_tokens is not read by the table form                 */
+  const int64_t* candidates; /* [B, N] rows of the table; outside [0, E - 1]: clamped and reported (drin_gather_rows above)              */
+  int32_t* index_status;     /* int32[4] or NULL                                                                                         */
+  const float* rows;         /* NULL, or drin_ghmfc_entity_rows' [num_entities, D]: then the entity half is ONE cosine against them     */
+} drin_ghmfc_table;
+
+/* Bytes of workspace for drin_ghmfc_forward_table (less with table->rows: no entity regions); 0 on error (drin_last_error). */
+DRIN_API size_t drin_ghmfc_table_workspace_bytes(const drin_ghmfc_config* cfg, const drin_ghmfc_table* table);
+
+/* drin_ghmfc_forward with the entity side (ghmfc.py:237-250, :297-298) read through table->candidates; batch->entity_feature
+ * and batch->entity_mask are not read.  The mention half is drin_ghmfc_forward's own.  With table->rows == NULL, per chunk of 256
+ * mentions: the indexed token mean (the row gather, for a pooled table), the same [chunk N, D] product, the same cosine - the
+ * same values in the same shapes, so scores and mention_repr have the BITS of drin_ghmfc_forward on the gathered batch.  With
+ * table->rows the scores agree with it to the rounding of one product evaluated per entity instead of per pair. */
+DRIN_API int drin_ghmfc_forward_table(const drin_ghmfc_config* cfg, const drin_ghmfc_batch* batch, const drin_ghmfc_params* params,
+                                      const drin_ghmfc_table* table, void* workspace, size_t workspace_bytes, float* scores,
+                                      float* mention_repr, void* stream);
+
+/* rows[e, :] = final_layer(pool(text[e])) for every entity (ghmfc.py:245-250 once per ENTITY instead of once per pair): text
+ * [num_entities, entity_tokens, width] with mask, or pooled [num_entities, width] when entity_tokens = 0 (no workspace then);
+ * w_entity [width, width], b_entity [width]; precision: DRIN_PREC_BF16X3 or DRIN_PREC_F32.  Chunks of 65536 entities: token
+ * mean into the workspace, then the product.  The rows depend on entity_encoder.final_layer only: rebuild after it changes. */
+DRIN_API size_t drin_ghmfc_entity_rows_workspace_bytes(int64_t num_entities, int32_t entity_tokens, int32_t width);
+DRIN_API int drin_ghmfc_entity_rows(const float* text, const int64_t* mask, int64_t num_entities, int32_t entity_tokens, int32_t width,
+                                    const float* w_entity, const float* b_entity, int32_t precision, float* rows, void* workspace,
+                                    size_t workspace_bytes, void* stream);
+
 /* The multi-head softmax-attention core on projected operands (what nn.MultiheadAttention runs between its in- and
  * out-projections, ghmfc.py:120,124): out[b, i, h] = softmax_j(q[b, i, h] . k[b, j, h] / sqrt(head_dim) + mask) v[b, j, h].
  * q [batch * q_len, E], k, v [batch * k_len, E], out [batch * q_len, E] are row-major with row strides ldq, ldk, ldv, ldo
@@ -892,6 +927,28 @@ DRIN_API int drin_cosine_rows_bwd(const float* x, const float* y, const float* d
  * int64 [pairs, tokens].  Fewer than 3 tokens: a NaN row, as the reference's empty mean. */
 DRIN_API int drin_entity_token_mean(const float* feat, const int64_t* mask, float* out, int64_t pairs, int32_t tokens,
                                     int32_t width, void* stream);
+
+/* ---- the row operations of GHMFC's table form -------------------------------------------------- *
+ * The entity side read through candidate ROWS of a device-resident table instead of gathered features: what the reference
+ * gathers on the host per mention (baselines/data.py: `[self.qid2idx[q] ...]`, `entity_feature[rows]`) and then encodes per
+ * pair (baselines/ghmfc.py:237-250, :297-298).  `index` is int64; an index outside [0, num_entities - 1] is clamped BEFORE
+ * any address is formed from it (nothing out of range is read) and reported into `index_status`, int32[4] on the device,
+ * with the semantics of drin_batch.index_status: the first reporter leaves {1, position in index, value low, value high},
+ * sticky until drin_index_status - the caller's check - zeroes it; NULL clamps silently.  width % 4 == 0 is the only width
+ * condition; table / text, x, rows and out are 16-byte aligned. */
+/* out[i, :] = table[index[i], :]; table [num_entities, width] fp32, out [count, width] (count <= 2^31 - 1). */
+DRIN_API int drin_gather_rows(const float* table, const int64_t* index, int64_t num_entities, float* out, int64_t count, int32_t width,
+                              int32_t* index_status, void* stream);
+/* drin_entity_token_mean of table row index[p]: text [num_entities, tokens, width], mask int64 [num_entities, tokens], out
+ * [pairs, width] - the slice rules, the summation order and the bits of drin_entity_token_mean on the gathered block. */
+DRIN_API int drin_entity_token_mean_indexed(const float* text, const int64_t* mask, const int64_t* index, int64_t num_entities,
+                                            float* out, int64_t pairs, int32_t tokens, int32_t width, int32_t* index_status,
+                                            void* stream);
+/* out[b, n] = cos(x[b, :], rows[index[b, n], :]); x [batch, width], rows [num_entities, width], index [batch, num_candidates]:
+ * the bits of drin_cosine_rows_fwd on the gathered rows. */
+DRIN_API int drin_cosine_rows_indexed_fwd(const float* x, const float* rows, const int64_t* index, int64_t num_entities, float* out,
+                                          int32_t batch, int32_t num_candidates, int32_t width, float eps, int32_t* index_status,
+                                          void* stream);
 
 /* ---- activation, row dropout and the span mean (GHMFC's other mention encoders) ---------------- *
  * What nn.TransformerEncoderLayer runs beside its products, attention and LayerNorms (ghmfc.py:72-90), and Avg.avg

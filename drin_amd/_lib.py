@@ -18,6 +18,7 @@ MAX_LAYERS = 8
 ABI_VERSION = 12
 
 OK, E_SHAPE, E_NULL, E_ALIGN, E_WORKSPACE, E_HIP, E_UNSUPPORTED, E_INDEX = 0, -1, -2, -3, -4, -5, -6, -7
+TOPK_SLICE, TOPK_MAX_K = 4096, 256                                         # DRIN_TOPK_SLICE; k of the cosine top-k
 PREC_F32, PREC_BF16X3, PREC_BF16X3_ALL, PREC_BF16X3_IF16 = 0, 1, 3, 5     # (2 and 4: removed with ABI 6 - outside the 1e-4 bar)
 ROW_ACT = {"none": 0, "relu": 1, "gelu": 2}                               # drin_row_activation (drin_act_dropout_*)
 FEAT_F32, FEAT_BF16 = 0, 1
@@ -266,6 +267,20 @@ EXPORTS = {
                                                  C.c_int32, C.c_void_p, C.c_void_p]),
     "drin_cosine_rows_indexed_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32,
                                                C.c_int32, C.c_float, C.c_void_p, C.c_void_p]),
+    # cosine top-k against the whole table: (rows, num_entities, width, eps, out, stream),
+    # (block, ld, batch, cols, col_base, col_inv_norms, k, state_keys, state_rows, scratch, scratch_bytes, first, out_keys, out_rows, stream),
+    # (batch, num_entities, width, k, chunk_entities),
+    # (x, rows, row_inv_norms, num_entities, batch, width, k, cosine_eps, precision, chunk_entities, workspace, workspace_bytes,
+    #  out_scores, out_rows, stream)
+    "drin_row_inv_norms": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_void_p, C.c_void_p]),
+    "drin_topk_update": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "drin_table_topk_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int64]),
+    "drin_table_topk": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32,
+                                  C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "drin_ghmfc_mention_forward_workspace_bytes": (C.c_size_t, [C.POINTER(DrinGhmfcConfigC)]),
+    "drin_ghmfc_mention_forward": (C.c_int, [C.POINTER(DrinGhmfcConfigC), C.POINTER(DrinGhmfcBatchC), C.POINTER(DrinGhmfcParamsC), C.c_void_p,
+                                             C.c_size_t, C.c_void_p, C.c_void_p]),
     "drin_attention": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
                                  C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "drin_attention_train_fwd": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,

@@ -1651,6 +1651,14 @@ int drin_host_selftest(void) {
       DRIN_TRY(ghmfc_table_layout_selfcheck(b, 101, 768, 2048, 128, 49, 64, rows != 0, 150));
       DRIN_TRY(ghmfc_table_layout_selfcheck(b, 1001, 768, 2048, 128, 49, 64, rows != 0, 1 << 20));
     }
+  // the cosine top-k workspace (table_topk.hip): tiny, the reference width, E = 1 M at B = 4096; default and explicit chunks
+  for (int k : {1, 100, 256}) {
+    DRIN_TRY(table_topk_layout_selfcheck(3, 300, 16, k, 64));
+    DRIN_TRY(table_topk_layout_selfcheck(3, 300, 16, k, 0));
+    DRIN_TRY(table_topk_layout_selfcheck(64, 65536, 768, k, 0));
+    DRIN_TRY(table_topk_layout_selfcheck(4096, 1000000, 768, k, 0));
+    DRIN_TRY(table_topk_layout_selfcheck(65535, 1000000, 768, k, 512));
+  }
   set_error("");
   return DRIN_OK;
 }

@@ -281,6 +281,57 @@ int drin_ghmfc_forward(const drin_ghmfc_config* cfg, const drin_ghmfc_batch* bt,
   return DRIN_OK;
 }
 
+// the configuration of the mention half alone: the candidate side is not the caller's to state (TABLE_ROWS: no entity regions)
+static int mention_config(const drin_ghmfc_config* cfg, drin_ghmfc_config* out) {
+  if (!cfg) return validate_ghmfc_config(cfg);
+  *out = *cfg;
+  out->num_candidates = 1, out->entity_tokens = 0;
+  return validate_ghmfc_config(out);
+}
+
+size_t drin_ghmfc_mention_forward_workspace_bytes(const drin_ghmfc_config* cfg) {
+  drin_ghmfc_config c;
+  if (mention_config(cfg, &c) != DRIN_OK) return 0;
+  GhmfcLayout W;
+  W.build(c, GhmfcLayout::TABLE_ROWS);
+  return W.total_floats * sizeof(float);
+}
+
+int drin_ghmfc_mention_forward(const drin_ghmfc_config* cfg, const drin_ghmfc_batch* bt, const drin_ghmfc_params* p, void* workspace,
+                               size_t workspace_bytes, float* mention_repr, void* stream) {
+  const char* who = "drin_ghmfc_mention_forward";
+  drin_ghmfc_config c;
+  DRIN_TRY(mention_config(cfg, &c));
+  if (!bt || !p || !workspace || !mention_repr) {
+    set_error("%s: batch / params / workspace / mention_repr is NULL", who);
+    return DRIN_E_NULL;
+  }
+  if (!bt->mention_feature || !bt->mention_mask || !bt->mention_image) {
+    set_error("%s: a mention tensor of the batch is NULL", who);
+    return DRIN_E_NULL;
+  }
+  DRIN_TRY(check_ghmfc_params(who, p));
+  GhmfcLayout W;
+  W.build(c, GhmfcLayout::TABLE_ROWS);
+  if (workspace_bytes < W.total_floats * sizeof(float)) {
+    set_error("%s: workspace %zu bytes < %zu", who, workspace_bytes, W.total_floats * sizeof(float));
+    return DRIN_E_WORKSPACE;
+  }
+  if (!aligned16(workspace) || !aligned16(bt->mention_feature) || !aligned16(bt->mention_image) || !aligned16(mention_repr)) {
+    set_error("%s: workspace, feature tensors and mention_repr must be 16-byte aligned", who);
+    return DRIN_E_ALIGN;
+  }
+  DRIN_BIND_DEVICE(stream, mention_repr, who);
+  RoctxRange range(who);
+  float* ws = static_cast<float*>(workspace);
+  // drin_ghmfc_forward's chunks, so every launch has that call's shape
+  for (int b0 = 0; b0 < c.batch; b0 += kChunk) {
+    const int Bc = c.batch - b0 < kChunk ? c.batch - b0 : kChunk;
+    DRIN_TRY(mention_half(c, bt, p, W, ws, b0, Bc, mention_repr + (int64_t)b0 * c.embed_dim, (hipStream_t)stream));
+  }
+  return DRIN_OK;
+}
+
 size_t drin_ghmfc_table_workspace_bytes(const drin_ghmfc_config* cfg, const drin_ghmfc_table* table) {
   if (validate_ghmfc_config(cfg) != DRIN_OK || check_ghmfc_table("drin_ghmfc_table_workspace_bytes", table, cfg->embed_dim) != DRIN_OK)
     return 0;

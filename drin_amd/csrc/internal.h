@@ -578,5 +578,7 @@ int ghmfc_layout_selfcheck(int B, int N, int D, int R, int L, int P, int T);   /
 // the same layout as drin_ghmfc_forward_table carves it (rows: scored from per-entity rows, no entity regions), and the chunk
 // buffer of drin_ghmfc_entity_rows for E entities
 int ghmfc_table_layout_selfcheck(int B, int N, int D, int R, int L, int P, int T, bool rows, int64_t E);
+// TopkLayout (table_topk.hip): the workspace of drin_table_topk, and the rules of its kp, chunk and slice count
+int table_topk_layout_selfcheck(int B, int64_t E, int D, int k, int64_t chunk_entities);
 
 }  // namespace drin

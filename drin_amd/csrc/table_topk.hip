@@ -1,0 +1,505 @@
+// Linking against the whole entity table: the k best rows of a table [E, D] for every mention of a batch
+// [B, D] by cosine, without a [B, E] score matrix.  The ordering contract is stated once in include/drin_hip.h ("cosine top-k")
+// and followed by every kernel here through ONE comparison: an order key of the score (order_key: NaN lowest, then -inf ... +inf,
+// -0.0 = +0.0) and, between equal keys, the lower row.
+//   k_row_inv_norms   inv[e] = 1 / max(|rows[e]|, eps), one wave per row
+//   k_topk_partial    (slice of kSlice columns, tile of kTile mentions): the kp best (key, column) of the slice per mention,
+//                     kept by a threshold, an LDS candidate buffer and a bitonic sort in registers
+//   k_topk_merge      per mention: the running list and the slice lists -> the new running list of kp (key, row), sorted
+//   k_topk_finish     per mention: sort kp (score, row) by the contract, write the first k
+//   k_pad_rows        x [B, D] -> [round4(B), D], zero rows behind
+// and the entry points drin_row_inv_norms, drin_topk_update, drin_table_topk(_workspace_bytes).  The block of dot products is
+// ENTITY-major, as the product y[Ec, Bp] = rows_chunk x^T leaves it: element (mention b, column c) at block[c * ld + b].
+// No atomics, no scratch memory; a workgroup of the three selection kernels is ONE wave, so its barriers order that wave's LDS
+// traffic and wait for nobody.
+#include "device_utils.h"
+#include "row_checks.h"
+
+namespace drin {
+namespace {
+
+constexpr int kSlice = DRIN_TOPK_SLICE;   // columns per partial workgroup
+constexpr int kTile = 8;                  // mentions per partial workgroup: 32 contiguous bytes of every block row
+constexpr int kMaxKp = 256;
+constexpr int kStageLd = 65;              // floats per staged mention row (64 columns + 1: the transposing writes spread over banks)
+constexpr int64_t kBlockBudgetBytes = (int64_t)256 << 20;   // the default chunk bounds the score block to this
+constexpr int64_t kMaxChunk = (int64_t)1 << 30;
+
+static_assert(DRIN_TOPK_KP(1) == 64 && DRIN_TOPK_KP(65) == 128 && DRIN_TOPK_KP(256) == kMaxKp, "kp: the power of two >= max(k, 64)");
+
+constexpr int64_t kNoRow = INT64_MAX;     // the row of an empty list entry inside the kernels (-1 in the state buffers)
+
+// Order key of a score: a > b as unsigned iff score a ranks before score b.  0 is kept for "empty", NaN is 1, -inf 0x007FFFFF.
+__device__ __forceinline__ uint32_t order_key(float v) {
+  if (v != v) return 1u;
+  const uint32_t u = v == 0.0f ? 0u : __float_as_uint(v);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float key_of_order(uint32_t k) {
+  if (k <= 1u) return __uint_as_float(0x7FC00000u);
+  return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
+}
+__device__ __forceinline__ bool ranks_before(uint32_t ka, int64_t ra, uint32_t kb, int64_t rb) { return ka > kb || (ka == kb && ra < rb); }
+
+__device__ __forceinline__ int lanes_below(uint64_t mask) {
+  return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+}
+__device__ __forceinline__ uint64_t shfl64(uint64_t v, int src) {
+  const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, src), hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), src);
+  return (uint64_t)hi << 32 | lo;
+}
+
+// One wave per row, four rows per workgroup, the rest by grid stride: k_cosine_gather's lane loop and wave sum of its yy.
+__global__ void __launch_bounds__(256) k_row_inv_norms(const float* __restrict__ rows, int64_t num_rows, int D4, float eps,
+                                                       float* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  for (int64_t e = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); e < num_rows; e += (int64_t)gridDim.x * 4) {
+    const float* yr = rows + e * (int64_t)D4 * 4;
+    float yy = 0.f;
+    for (int c4 = lane; c4 < D4; c4 += 64) {
+      const float4 b = ld4(yr + c4 * 4);
+      yy += dot4(b, b);
+    }
+    yy = wave_sum(yy);
+    if (lane == 0) out[e] = 1.0f / fmaxf(sqrtf(yy), eps);
+  }
+}
+
+__global__ void __launch_bounds__(256) k_pad_rows(const float* __restrict__ x, float* __restrict__ out, int64_t n4_in, int64_t n4_out) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4_out; i += (int64_t)gridDim.x * 256)
+    st4(out + i * 4, i < n4_in ? ld4(x + i * 4) : make_float4(0.f, 0.f, 0.f, 0.f));
+}
+
+// Descending bitonic sort of 64 R composites held R per lane (element r * 64 + lane), in registers: a stride below 64 exchanges
+// lanes (__shfl_xor: no LDS traffic, no barrier), a stride from 64 up exchanges two of the lane's own registers.
+__device__ __forceinline__ uint64_t shfl_xor64(uint64_t v, int mask) {
+  const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, mask), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), mask);
+  return (uint64_t)hi << 32 | lo;
+}
+// one pass at a stride below 64: element r * 64 + lane meets lane ^ j's
+template <int R>
+__device__ __forceinline__ void lane_stage(uint64_t (&v)[R], int lane, int k2, int j) {
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const uint64_t other = shfl_xor64(v[r], j);
+    const bool want_max = ((((r << 6) | lane) & k2) == 0) == ((lane & j) == 0);
+    v[r] = (want_max == (other > v[r])) ? other : v[r];
+  }
+}
+template <int R>
+__device__ __forceinline__ void sort_desc_regs(uint64_t (&v)[R], int lane) {
+  // runs of up to 64: lane passes only, the pass loops stay rolled (the stride is a run-time operand of the exchange)
+#pragma unroll 1
+  for (int k2 = 2; k2 <= 64; k2 <<= 1)
+#pragma unroll 1
+    for (int j = k2 >> 1; j > 0; j >>= 1) lane_stage<R>(v, lane, k2, j);
+  // runs of 128 and up: the strides from 64 up pair REGISTERS, so these few levels unroll and v[] is indexed by constants only
+#pragma unroll
+  for (int k2 = 128; k2 <= 64 * R; k2 <<= 1) {
+#pragma unroll
+    for (int j = k2 >> 1; j >= 64; j >>= 1) {
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        if ((r & (j >> 6)) != 0) continue;
+        const uint64_t a = v[r], b = v[r | (j >> 6)];
+        const bool swap = (((r << 6) & k2) == 0) ? a < b : a > b;   // k2 >= 128: the direction is the register's
+        v[r] = swap ? b : a, v[r | (j >> 6)] = swap ? a : b;
+      }
+    }
+#pragma unroll 1
+    for (int j = 32; j > 0; j >>= 1) lane_stage<R>(v, lane, k2, j);
+  }
+}
+
+// The KP best columns of one slice for each mention of one tile.  A candidate is ONE 64-bit composite, order key above, 2^32 - 1 -
+// column below: composites of a slice are distinct and a larger one ranks first, so the order inside a slice is the contract's.
+// Per mention: a threshold (0, or - from the second call on - just under the running list's last key: what ranks after KP known
+// rows cannot enter), a buffer of 2 KP composites that takes what beats the threshold (ballot + lane count: the columns' order,
+// no atomics), and - when the next 64 may not fit, and after the slice's last step - a sort that keeps the KP best and raises the
+// threshold to the KP-th.  Lane m keeps count and threshold of mention m.  slices [gridDim.x][batch][KP], sorted, 0 = empty.
+template <int KP>
+__global__ void __launch_bounds__(64) k_topk_partial(const float* __restrict__ block, int64_t ld, int batch, int64_t cols,
+                                                     const float* __restrict__ inv, const float* __restrict__ run_keys,
+                                                     const int64_t* __restrict__ run_rows, uint64_t* __restrict__ slices) {
+  constexpr int cap = 2 * KP, R = cap / 64;
+  __shared__ uint64_t buf[kTile * cap];
+  __shared__ float stage[kTile * kStageLd];
+  const int lane = threadIdx.x;
+  const int64_t c_begin = (int64_t)blockIdx.x * kSlice, c_end = cols < c_begin + kSlice ? cols : c_begin + kSlice;
+  const int b0 = (int)blockIdx.y * kTile, nm = batch - b0 < kTile ? batch - b0 : kTile;
+  int cnt = 0;
+  uint64_t thr = 0;
+  if (run_rows != nullptr && lane < nm) {
+    const int64_t last = ((int64_t)(b0 + lane) + 1) * KP - 1;
+    if (run_rows[last] >= 0) thr = ((uint64_t)order_key(run_keys[last]) << 32) - 1;   // keys >= the list's last one pass
+  }
+  for (int64_t c0 = c_begin; c0 < c_end; c0 += 64) {
+    const bool last_step = c0 + 64 >= c_end;
+    // 64 columns x kTile mentions: two 16-byte loads per lane, transposed into the stage
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int col = (lane >> 1) + 32 * i, b = b0 + 4 * (lane & 1);
+      const int64_t c = c0 + col;
+      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (c < c_end && b < ld) v = ld4(block + c * ld + b);   // ld % 4 == 0: the four floats lie inside row c
+      float* s = stage + 4 * (lane & 1) * kStageLd + col;
+      s[0] = v.x, s[kStageLd] = v.y, s[2 * kStageLd] = v.z, s[3 * kStageLd] = v.w;
+    }
+    const int64_t cl = c0 + lane;
+    const bool valid = cl < c_end;
+    const float scale = (inv != nullptr && valid) ? inv[cl] : 1.0f;
+    __syncthreads();
+    for (int m = 0; m < nm; ++m) {
+      const float key = stage[m * kStageLd + lane] * scale;
+      const uint64_t comp = valid ? ((uint64_t)order_key(key) << 32 | (uint64_t)(0xFFFFFFFFu - (uint32_t)cl)) : 0;
+      int n = __shfl(cnt, m);
+      uint64_t t = shfl64(thr, m);
+      const bool pass = comp > t;
+      const uint64_t mask = __ballot(pass);
+      uint64_t* mine = buf + m * cap;
+      if (pass) mine[n + lanes_below(mask)] = comp;           // n <= cap - 64 here
+      n += __popcll(mask);
+      if (n > cap - 64 || last_step) {                         // wave-uniform
+        __syncthreads();                                       // the appends of other lanes
+        uint64_t v[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) v[r] = r * 64 + lane < n ? mine[r * 64 + lane] : 0;
+        sort_desc_regs<R>(v, lane);
+        if (n >= KP) n = KP, t = shfl64(v[R / 2 - 1], 63);     // element KP - 1
+        if (last_step) {
+          uint64_t* out = slices + ((int64_t)blockIdx.x * batch + b0 + m) * KP;
+#pragma unroll
+          for (int r = 0; r < R / 2; ++r) out[r * 64 + lane] = v[r];
+        } else {
+#pragma unroll
+          for (int r = 0; r < R / 2; ++r) mine[r * 64 + lane] = v[r];   // each lane rewrites elements it alone read
+        }
+      }
+      if (lane == m) cnt = n, thr = t;
+    }
+    __syncthreads();
+  }
+}
+
+// One mention: fold the slice lists of this call into the running list.  Both are sorted, so a step is a bitonic MERGE (the
+// slice list read backwards behind the running one) of 2 kp entries, log2(2 kp) passes; a slice list whose best entry ranks
+// after the running list's last is skipped.  Entries here are (order key, table row): rows need 64 bits.
+__global__ void __launch_bounds__(64) k_topk_merge(const uint64_t* __restrict__ slices, int num_slices, int batch, int kp,
+                                                   int64_t col_base, float* __restrict__ run_keys, int64_t* __restrict__ run_rows,
+                                                   int first) {
+  __shared__ uint32_t sk[2 * kMaxKp];
+  __shared__ int64_t sr[2 * kMaxKp];
+  const int lane = threadIdx.x;
+  const int64_t b = blockIdx.x;
+  for (int i = lane; i < kp; i += 64) {
+    const int64_t r = first ? -1 : run_rows[b * kp + i];
+    sk[i] = r < 0 ? 0u : order_key(run_keys[b * kp + i]);
+    sr[i] = r < 0 ? kNoRow : r;
+  }
+  __syncthreads();
+  for (int s = 0; s < num_slices; ++s) {
+    const uint64_t* list = slices + ((int64_t)s * batch + b) * kp;
+    const uint64_t best = list[0];
+    if (best == 0) continue;
+    if (!ranks_before((uint32_t)(best >> 32), col_base + (int64_t)(0xFFFFFFFFu - (uint32_t)best), sk[kp - 1], sr[kp - 1])) continue;
+    for (int i = lane; i < kp; i += 64) {
+      const uint64_t c = list[kp - 1 - i];
+      sk[kp + i] = (uint32_t)(c >> 32);
+      sr[kp + i] = c == 0 ? kNoRow : col_base + (int64_t)(0xFFFFFFFFu - (uint32_t)c);
+    }
+    __syncthreads();
+    for (int j = kp; j > 0; j >>= 1) {
+      for (int t = lane; t < kp; t += 64) {
+        const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), p = i | j;
+        const uint32_t ki = sk[i], kq = sk[p];
+        const int64_t ri = sr[i], rq = sr[p];
+        if (ranks_before(kq, rq, ki, ri)) sk[i] = kq, sr[i] = rq, sk[p] = ki, sr[p] = ri;
+      }
+      __syncthreads();
+    }
+  }
+  for (int i = lane; i < kp; i += 64) {
+    run_keys[b * kp + i] = key_of_order(sk[i]);
+    run_rows[b * kp + i] = sk[i] == 0 ? -1 : sr[i];
+  }
+}
+
+// One mention: kp (score, row) pairs (row < 0: empty, ranks last) sorted by the contract; the first k are written, the scores
+// with the bits they came with.
+__global__ void __launch_bounds__(64) k_topk_finish(const float* __restrict__ keys, const int64_t* __restrict__ rows, int kp, int k,
+                                                    float* __restrict__ out_keys, int64_t* __restrict__ out_rows) {
+  __shared__ uint32_t sk[kMaxKp];
+  __shared__ int64_t sr[kMaxKp];
+  __shared__ float sf[kMaxKp];
+  const int lane = threadIdx.x;
+  const int64_t b = blockIdx.x;
+  for (int i = lane; i < kp; i += 64) {
+    const int64_t r = rows[b * kp + i];
+    const float f = keys[b * kp + i];
+    sk[i] = r < 0 ? 0u : order_key(f);
+    sr[i] = r < 0 ? kNoRow : r;
+    sf[i] = f;
+  }
+  __syncthreads();
+  for (int k2 = 2; k2 <= kp; k2 <<= 1)
+    for (int j = k2 >> 1; j > 0; j >>= 1) {
+      for (int t = lane; t < (kp >> 1); t += 64) {
+        const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), p = i | j;
+        const uint32_t ki = sk[i], kq = sk[p];
+        const int64_t ri = sr[i], rq = sr[p];
+        const bool swap = ((i & k2) == 0) ? ranks_before(kq, rq, ki, ri) : ranks_before(ki, ri, kq, rq);
+        if (swap) {
+          const float fi = sf[i], fq = sf[p];
+          sk[i] = kq, sr[i] = rq, sf[i] = fq, sk[p] = ki, sr[p] = ri, sf[p] = fi;
+        }
+      }
+      __syncthreads();
+    }
+  for (int i = lane; i < k; i += 64) {
+    out_keys[b * k + i] = sk[i] == 0 ? __uint_as_float(0x7FC00000u) : sf[i];
+    out_rows[b * k + i] = sk[i] == 0 ? -1 : sr[i];
+  }
+}
+
+size_t topk_scratch_bytes(int64_t batch, int64_t cols, int kp) { return (size_t)cdiv(cols, kSlice) * (size_t)batch * kp * sizeof(uint64_t); }
+int64_t slices_of(int64_t cols) { return cdiv(cols, kSlice); }
+
+// the selection of one block: partial lists per slice, then the merge into the running list
+int launch_topk_update(const float* block, int64_t ld, int batch, int64_t cols, int64_t col_base, const float* inv, int kp,
+                       float* keys, int64_t* rows, uint64_t* slices, bool first, hipStream_t st) {
+  const int64_t ns = slices_of(cols);
+  auto partial = kp == 64 ? k_topk_partial<64> : (kp == 128 ? k_topk_partial<128> : k_topk_partial<256>);
+  DRIN_TRY(timed(DRIN_KC_EDGE, st, "k_topk_partial", [&] {
+    hipLaunchKernelGGL(partial, dim3((unsigned)ns, (unsigned)cdiv(batch, kTile)), dim3(64), 0, st, block, ld, batch, cols, inv,
+                       first ? nullptr : keys, first ? nullptr : rows, slices);
+  }));
+  return timed(DRIN_KC_EDGE, st, "k_topk_merge", [&] {
+    hipLaunchKernelGGL(k_topk_merge, dim3((unsigned)batch), dim3(64), 0, st, slices, (int)ns, batch, kp, col_base, keys, rows, first ? 1 : 0);
+  });
+}
+
+int launch_topk_finish(const float* keys, const int64_t* rows, int batch, int kp, int k, float* out_keys, int64_t* out_rows, hipStream_t st) {
+  return timed(DRIN_KC_EDGE, st, "k_topk_finish", [&] {
+    hipLaunchKernelGGL(k_topk_finish, dim3((unsigned)batch), dim3(64), 0, st, keys, rows, kp, k, out_keys, out_rows);
+  });
+}
+
+int launch_row_inv_norms(const float* rows, int64_t num_rows, int width, float eps, float* out, hipStream_t st) {
+  const int64_t blocks = cdiv(num_rows, 4) < 65535 * 16 ? cdiv(num_rows, 4) : 65535 * 16;
+  return timed(DRIN_KC_EDGE, st, "k_row_inv_norms", [&] {
+    hipLaunchKernelGGL(k_row_inv_norms, dim3((unsigned)blocks), dim3(256), 0, st, rows, num_rows, width / 4, eps, out);
+  });
+}
+
+// ---- the workspace of drin_table_topk: sized and carved from this one description -------------------------------------
+struct TopkLayout {
+  size_t xpad, block, keys, rows, slices, scores, total_floats;   // offsets in floats
+  int64_t chunk, num_slices;
+  int kp, Bp;
+  // false: a region does not fit in size_t / the chunk is out of range
+  bool build(int batch, int64_t E, int D, int k, int64_t chunk_entities) {
+    kp = DRIN_TOPK_KP(k), Bp = (batch + 3) & ~3;
+    if (chunk_entities > 0) {
+      chunk = chunk_entities;
+    } else {   // a multiple of 256 rows whose block stays inside the budget (at least 256)
+      chunk = kBlockBudgetBytes / ((int64_t)Bp * 4) / 256 * 256;
+      chunk = chunk < 256 ? 256 : chunk;
+    }
+    chunk = chunk < E ? chunk : E;
+    if (chunk > kMaxChunk) return false;
+    num_slices = slices_of(chunk);
+    const size_t limit = SIZE_MAX / 64;   // of floats: the sum of six regions and the byte count stay representable
+    auto fits = [&](size_t a, size_t b) { return a == 0 || b <= limit / a; };
+    if (!fits((size_t)chunk, (size_t)Bp) || !fits((size_t)num_slices * 2, (size_t)batch * kp)) return false;
+    Arena A;
+    xpad = A.take((size_t)Bp * D);
+    block = A.take((size_t)chunk * Bp);
+    keys = A.take((size_t)batch * kp);
+    rows = A.take((size_t)batch * kp * 2);
+    slices = A.take((size_t)num_slices * batch * kp * 2);
+    scores = A.take((size_t)batch * kp);
+    total_floats = A.total;
+    return true;
+  }
+};
+
+int check_topk_shape(const char* who, int64_t E, int batch, int width, int k) {
+  DRIN_TRY(check_count(who, "num_entities", E, 1, INT64_MAX / 4096));
+  DRIN_TRY(check_count(who, "batch", batch, 1, 65535));
+  DRIN_TRY(check_width4(who, width));
+  DRIN_TRY(check_count(who, "k", k, 1, kMaxKp));
+  if (k > E) {
+    set_error("%s: k = %lld exceeds num_entities = %lld", who, (long long)k, (long long)E);
+    return DRIN_E_SHAPE;
+  }
+  return DRIN_OK;
+}
+
+int check_precision_topk(const char* who, int precision) {
+  if (precision != DRIN_PREC_F32 && precision != DRIN_PREC_BF16X3) {
+    set_error("%s: precision %d is not DRIN_PREC_F32 / DRIN_PREC_BF16X3", who, precision);
+    return DRIN_E_UNSUPPORTED;
+  }
+  return DRIN_OK;
+}
+
+}  // namespace
+
+int table_topk_layout_selfcheck(int batch, int64_t E, int D, int k, int64_t chunk_entities) {
+  TopkLayout W;
+  if (!W.build(batch, E, D, k, chunk_entities)) {
+    set_error("selftest: TopkLayout does not build for B=%d E=%lld D=%d k=%d chunk=%lld", batch, (long long)E, D, k, (long long)chunk_entities);
+    return DRIN_E_WORKSPACE;
+  }
+  const size_t B = batch, kp = W.kp;
+  if (W.kp < k || W.kp > kMaxKp || (W.kp & (W.kp - 1)) || W.chunk < 1 || W.chunk > E || W.num_slices * kSlice < W.chunk ||
+      (chunk_entities == 0 && W.chunk != E && (W.chunk % 256 || (W.chunk > 256 && W.chunk * W.Bp * 4 > kBlockBudgetBytes)))) {
+    set_error("selftest: TopkLayout kp=%d chunk=%lld slices=%lld break their rules", W.kp, (long long)W.chunk, (long long)W.num_slices);
+    return DRIN_E_WORKSPACE;
+  }
+  // what the launches index: the padded mentions, one block of dot products, the running list, every slice's list, the re-scores
+  const Region ws[] = {{"xpad", W.xpad, (size_t)W.Bp * D},   {"block", W.block, (size_t)W.chunk * W.Bp},
+                       {"keys", W.keys, B * kp},             {"rows", W.rows, B * kp * 2},
+                       {"slices", W.slices, (size_t)cdiv(W.chunk, kSlice) * B * kp * 2}, {"scores", W.scores, B * kp}};
+  return regions_hold("TopkLayout", ws, (int)(sizeof(ws) / sizeof(ws[0])), W.total_floats);
+}
+
+}  // namespace drin
+
+using namespace drin;
+
+int drin_row_inv_norms(const float* rows, int64_t num_entities, int32_t width, float eps, float* out, void* stream) {
+  const char* who = "drin_row_inv_norms";
+  DRIN_CHECK_POINTERS(who, {"rows", rows, true});
+  if (!out) {
+    set_error("%s: out is NULL", who);
+    return DRIN_E_NULL;
+  }
+  if ((reinterpret_cast<uintptr_t>(out) & 3u) != 0) {
+    set_error("%s: out is not 4-byte aligned", who);
+    return DRIN_E_ALIGN;
+  }
+  DRIN_TRY(check_count(who, "num_entities", num_entities, 1, INT64_MAX / 4096));
+  DRIN_TRY(check_width4(who, width));
+  if (!(eps > 0.0f)) {
+    set_error("%s: eps must be positive", who);
+    return DRIN_E_SHAPE;
+  }
+  DRIN_BIND_DEVICE(stream, out, who);
+  return launch_row_inv_norms(rows, num_entities, width, eps, out, (hipStream_t)stream);
+}
+
+int drin_topk_update(const float* block, int64_t ld, int32_t batch, int64_t cols, int64_t col_base, const float* col_inv_norms, int32_t k,
+                     float* state_keys, int64_t* state_rows, void* scratch, size_t scratch_bytes, int32_t first, float* out_keys,
+                     int64_t* out_rows, void* stream) {
+  const char* who = "drin_topk_update";
+  DRIN_CHECK_POINTERS(who, {"block", block, cols > 0}, {"state_keys", state_keys, true}, {"state_rows", state_rows, true},
+                      {"scratch", scratch, cols > 0});
+  if ((reinterpret_cast<uintptr_t>(col_inv_norms) & 3u) != 0 || (reinterpret_cast<uintptr_t>(out_keys) & 3u) != 0 ||
+      (reinterpret_cast<uintptr_t>(out_rows) & 7u) != 0) {
+    set_error("%s: col_inv_norms and out_keys must be 4-byte, out_rows 8-byte aligned", who);
+    return DRIN_E_ALIGN;
+  }
+  if ((out_keys == nullptr) != (out_rows == nullptr)) {
+    set_error("%s: out_keys and out_rows go together (both NULL: no finishing pass)", who);
+    return DRIN_E_NULL;
+  }
+  DRIN_TRY(check_count(who, "batch", batch, 1, 65535));
+  DRIN_TRY(check_count(who, "k", k, 1, kMaxKp));
+  DRIN_TRY(check_count(who, "cols", cols, 0, INT32_MAX));
+  DRIN_TRY(check_count(who, "col_base", col_base, 0, INT64_MAX / 4096));
+  if (cols == 0 && (first || out_keys == nullptr)) {
+    set_error("%s: cols = 0 is the finishing call: it needs out_keys / out_rows and first = 0", who);
+    return DRIN_E_SHAPE;
+  }
+  if (cols > 0 && (ld % 4 != 0 || ld < ((int64_t)batch + 3) / 4 * 4 || ld > INT32_MAX)) {
+    set_error("%s: ld = %lld must be a multiple of 4, at least batch rounded up to one and at most 2^31 - 1", who, (long long)ld);
+    return DRIN_E_SHAPE;
+  }
+  const int kp = DRIN_TOPK_KP(k);
+  const size_t need = topk_scratch_bytes(batch, cols, kp);
+  if (scratch_bytes < need) {
+    set_error("%s: scratch %zu bytes < %zu", who, scratch_bytes, need);
+    return DRIN_E_WORKSPACE;
+  }
+  DRIN_BIND_DEVICE(stream, state_keys, who);
+  hipStream_t st = (hipStream_t)stream;
+  if (cols > 0)
+    DRIN_TRY(launch_topk_update(block, ld, batch, cols, col_base, col_inv_norms, kp, state_keys, state_rows, static_cast<uint64_t*>(scratch),
+                                first != 0, st));
+  if (out_keys != nullptr) DRIN_TRY(launch_topk_finish(state_keys, state_rows, batch, kp, k, out_keys, out_rows, st));
+  return DRIN_OK;
+}
+
+size_t drin_table_topk_workspace_bytes(int32_t batch, int64_t num_entities, int32_t width, int32_t k, int64_t chunk_entities) {
+  const char* who = "drin_table_topk_workspace_bytes";
+  if (check_topk_shape(who, num_entities, batch, width, k) != DRIN_OK) return 0;
+  if (chunk_entities < 0) {
+    set_error("%s: chunk_entities = %lld is negative", who, (long long)chunk_entities);
+    return 0;
+  }
+  TopkLayout W;
+  if (!W.build(batch, num_entities, width, k, chunk_entities)) {
+    set_error("%s: chunk_entities = %lld is out of range (at most 2^30 rows, the workspace must fit in size_t)", who,
+              (long long)chunk_entities);
+    return 0;
+  }
+  return W.total_floats * sizeof(float);
+}
+
+int drin_table_topk(const float* x, const float* rows, const float* row_inv_norms, int64_t num_entities, int32_t batch, int32_t width,
+                    int32_t k, float cosine_eps, int32_t precision, int64_t chunk_entities, void* workspace, size_t workspace_bytes,
+                    float* out_scores, int64_t* out_rows, void* stream) {
+  const char* who = "drin_table_topk";
+  DRIN_CHECK_POINTERS(who, {"x", x, true}, {"rows", rows, true}, {"row_inv_norms", row_inv_norms, true}, {"workspace", workspace, true});
+  if (!out_scores || !out_rows) {
+    set_error("%s: out_scores / out_rows is NULL", who);
+    return DRIN_E_NULL;
+  }
+  if ((reinterpret_cast<uintptr_t>(out_scores) & 3u) != 0 || (reinterpret_cast<uintptr_t>(out_rows) & 7u) != 0) {
+    set_error("%s: out_scores must be 4-byte and out_rows 8-byte aligned", who);
+    return DRIN_E_ALIGN;
+  }
+  DRIN_TRY(check_topk_shape(who, num_entities, batch, width, k));
+  DRIN_TRY(check_precision_topk(who, precision));
+  if (chunk_entities < 0) {
+    set_error("%s: chunk_entities = %lld is negative", who, (long long)chunk_entities);
+    return DRIN_E_SHAPE;
+  }
+  TopkLayout W;
+  if (!W.build(batch, num_entities, width, k, chunk_entities)) {
+    set_error("%s: chunk_entities = %lld is out of range (at most 2^30 rows, the workspace must fit in size_t)", who,
+              (long long)chunk_entities);
+    return DRIN_E_SHAPE;
+  }
+  if (workspace_bytes < W.total_floats * sizeof(float)) {
+    set_error("%s: workspace %zu bytes < %zu", who, workspace_bytes, W.total_floats * sizeof(float));
+    return DRIN_E_WORKSPACE;
+  }
+  DRIN_BIND_DEVICE(stream, out_scores, who);
+  RoctxRange range(who);
+  hipStream_t st = (hipStream_t)stream;
+  float* ws = static_cast<float*>(workspace);
+  const int B = batch, D = width, kp = W.kp, Bp = W.Bp;
+  float* xpad = ws + W.xpad;
+  float* block = ws + W.block;
+  float* keys = ws + W.keys;
+  int64_t* list = reinterpret_cast<int64_t*>(ws + W.rows);
+  uint64_t* slices = reinterpret_cast<uint64_t*>(ws + W.slices);
+  float* scores = ws + W.scores;
+  const int64_t n4_in = (int64_t)B * D / 4, n4_out = (int64_t)Bp * D / 4;
+  DRIN_TRY(timed(DRIN_KC_EDGE, st, "k_pad_rows", [&] {
+    hipLaunchKernelGGL(k_pad_rows, dim3((unsigned)(cdiv(n4_out, 256) < 4096 ? cdiv(n4_out, 256) : 4096)), dim3(256), 0, st, x, xpad, n4_in, n4_out);
+  }));
+  // per chunk of table rows: y[n, Bp] = rows_chunk x^T - the entities are the ROW side, so launch_gemm_nt routes every chunk by the
+  // chunk's size, not by the batch's - then the selection on that block
+  for (int64_t e0 = 0; e0 < num_entities; e0 += W.chunk) {
+    const int64_t n = num_entities - e0 < W.chunk ? num_entities - e0 : W.chunk;
+    DRIN_TRY(launch_gemm_nt(rows + e0 * D, D, xpad, D, nullptr, block, Bp, n, Bp, D, false, precision, st));
+    DRIN_TRY(launch_topk_update(block, Bp, B, n, e0, row_inv_norms + e0, kp, keys, list, slices, e0 == 0, st));
+  }
+  // the kp selected rows of every mention, scored as drin_cosine_rows_indexed_fwd scores them (an empty entry, row -1, is clamped
+  // silently and stays last), ordered by the contract
+  DRIN_TRY(launch_cosine_gather(x, rows, list, num_entities, scores, B, kp, D, cosine_eps, nullptr, 0, st));
+  return launch_topk_finish(scores, list, B, kp, k, out_scores, out_rows, st);
+}

@@ -211,6 +211,27 @@ class Model(TableForm, nn.Module):
         self._watch_indices(dev)
         return scores if want_scores else mention
 
+    def _mention_only(self, mention) -> torch.Tensor:
+        """`[B, D]` mention representations from the five mention-side items alone (`drin_ghmfc_mention_forward`: the mention
+        half of `drin_ghmfc_forward`, its bits) - what `link` ranks the table with."""
+        mf, mmask, mimage = self._mention_tensors(mention)
+        cfg, dev, B = self.cfg, mf.device, mf.shape[0]
+        lib = _lib.load()
+        c = _lib.DrinGhmfcConfigC(batch=B, num_candidates=cfg.num_candidates, embed_dim=cfg.embed_dim, image_dim=cfg.image_dim,
+                                  mention_tokens=cfg.mention_tokens, image_regions=cfg.image_regions, num_heads=cfg.num_heads,
+                                  entity_tokens=0, precision=PRECISIONS[self.precision], layer_norm_eps=cfg.layer_norm_eps,
+                                  cosine_eps=cfg.cosine_eps)
+        params = [p.detach().contiguous() for p in self.param_list()]
+        bt = _lib.DrinGhmfcBatchC(_ptr(mf), _ptr(mmask), _ptr(mimage), None, None)
+        pc = _lib.DrinGhmfcParamsC.from_buffer_copy((C.c_void_p * 52)(*[p.data_ptr() for p in params]))
+        nbytes = lib.drin_ghmfc_mention_forward_workspace_bytes(C.byref(c))
+        if nbytes == 0:
+            _lib.check(_lib.E_SHAPE)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        mention_repr = torch.empty(B, cfg.embed_dim, dtype=torch.float32, device=dev)
+        _lib.check(lib.drin_ghmfc_mention_forward(C.byref(c), C.byref(bt), C.byref(pc), _ptr(ws), nbytes, _ptr(mention_repr), _stream(dev)))
+        return mention_repr
+
     def _run(self, batch, want_scores: bool):
         if self.training:
             raise RuntimeError("drin_amd.ghmfc.Model is scoring only: call .eval(); GHMFC training is not implemented, DESIGN.md §11")

@@ -11,6 +11,9 @@
 * `train()`: every entity's tokens are pooled once per table version, a step gathers `[B, N, D]` pooled rows
   (`drin_gather_rows`) and runs the gathered step's `entity_scores` on them - the same bits, scores and gradients.
 
+`model.link(batch, k)` ranks every mention against the WHOLE table instead of a candidate list: the k best
+rows by cosine (`drin_table_topk` on the per-entity rows), scores with the bits of the cached table-form scoring.
+
 A row outside the table is clamped by the kernels and reported: `check_indices()` / `validate_indices` raise `IndexError`.
 GPU only, fp32 tables; the table is an input and gets no gradient.
 """
@@ -18,7 +21,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Optional, Sequence
+from typing import NamedTuple, Optional, Sequence
 
 import torch
 
@@ -110,6 +113,36 @@ def cosine_rows_indexed(x: torch.Tensor, rows: torch.Tensor, index: torch.Tensor
     return out
 
 
+class LinkResult(NamedTuple):
+    """`model.link`: `scores [B, k]` float32 and `rows [B, k]` int64 table rows, best first (the ordering contract of
+    include/drin_hip.h: higher score first, the lower row between equal scores, NaN last)."""
+    scores: torch.Tensor
+    rows: torch.Tensor
+
+
+def row_inv_norms(rows: torch.Tensor, eps: float) -> torch.Tensor:
+    """`[E]` = 1 / max(|rows[e]|, eps) by `drin_row_inv_norms`."""
+    out = torch.empty(rows.shape[0], dtype=torch.float32, device=rows.device)
+    _lib.check(_lib.load().drin_row_inv_norms(_ptr(rows), rows.shape[0], rows.shape[1], eps, _ptr(out), _stream(rows.device)))
+    return out
+
+
+def table_topk(x: torch.Tensor, rows: torch.Tensor, inv_norms: torch.Tensor, k: int, eps: float, precision: str,
+               chunk_entities: int = 0) -> LinkResult:
+    """The k best of `rows [E, D]` for every `x [B, D]` by cosine (`drin_table_topk`); `inv_norms`: `row_inv_norms(rows, eps)`."""
+    lib = _lib.load()
+    (B, D), E = x.shape, rows.shape[0]
+    nbytes = lib.drin_table_topk_workspace_bytes(B, E, D, k, chunk_entities)
+    if nbytes == 0:
+        _lib.check(_lib.E_SHAPE)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    scores = torch.empty(B, k, dtype=torch.float32, device=x.device)
+    best = torch.empty(B, k, dtype=torch.int64, device=x.device)
+    _lib.check(lib.drin_table_topk(_ptr(x), _ptr(rows), _ptr(inv_norms), E, B, D, k, eps, PRECISIONS[precision], chunk_entities, _ptr(ws),
+                                   nbytes, _ptr(scores), _ptr(best), _stream(x.device)))
+    return LinkResult(scores, best)
+
+
 class _TableState:
     """What a model keeps for its table form (per process: not part of the state dict)."""
 
@@ -119,6 +152,8 @@ class _TableState:
         self.rows: Optional[torch.Tensor] = None      # per-entity rows [E, D] of the cache
         self.rows_key = None
         self.rows_builds = 0
+        self.inv: Optional[torch.Tensor] = None       # 1 / norm of every row of `rows` [E], under rows_key (link)
+        self.inv_key = None
         self.pooled: Optional[torch.Tensor] = None    # per-entity token means [E, D] of train()
         self.pooled_key = None
         self.status = {}                              # device -> int32[4]
@@ -160,6 +195,7 @@ class TableForm:
             check_table(table, self.cfg.embed_dim, on_gpu=False)
         st = self._tf
         st.table, st.rows, st.rows_key, st.pooled, st.pooled_key = table, None, None, None, None
+        st.inv, st.inv_key = None, None
         return self
 
     @property
@@ -174,13 +210,52 @@ class TableForm:
         st = self._tf
         st.cache_on = bool(on)
         if not on:
-            st.rows, st.rows_key = None, None
+            st.rows, st.rows_key, st.inv, st.inv_key = None, None, None, None
         return self
 
     @property
     def entity_cache_builds(self) -> int:
         """how many times the per-entity rows were built"""
         return self._tf.rows_builds
+
+    @torch.no_grad()
+    def link(self, batch, k: int, table: Optional[EntityTable] = None) -> LinkResult:
+        """Rank every mention of `batch` against the WHOLE `table` (default: the attached one): `(scores [B, k], rows [B, k])`,
+        the k best table rows by the model's cosine, best first.  `batch`: the five mention-side items, a `GhmfcIndexedBatch`
+        or any 8-item batch (items 5-7 are not read).  The mention representation is the mention half alone, the entity side
+        the per-entity rows `final_layer(pool(text[e]))` (built as for `enable_entity_cache()`, whether or not it is enabled,
+        and rebuilt when the entity weights, the precision or the table change), so `scores` are, bit for bit, what the cached
+        table form scores on `rows`.  `eval()` only, no gradient, GPU only; 1 <= k <= min(256, E)."""
+        if self.training:
+            raise RuntimeError("ghmfc link: ranking against the table is eval() only (no gradient flows through a top-k): call .eval()")
+        mention = batch.mention if isinstance(batch, GhmfcIndexedBatch) else list(batch)[:5]
+        if len(mention) != 5:
+            raise ValueError("ghmfc link: batch must hold the five mention-side items (mention_feature, mention_mask, begin, end, "
+                             "mention_image), optionally followed by the three entity-side ones")
+        attached = table is None
+        table = self._tf.table if attached else table
+        if table is None:
+            raise ValueError("ghmfc link: no table given and none attached: call model.attach_entity_table(table)")
+        check_table(table, self.cfg.embed_dim, on_gpu=False)
+        k, E = int(k), table.text.shape[0]
+        if k < 1 or k > _lib.TOPK_MAX_K:
+            raise ValueError(f"ghmfc link: k = {k} is not in [1, {_lib.TOPK_MAX_K}]")
+        if k > E:
+            raise ValueError(f"ghmfc link: k = {k} exceeds the table's {E} entities")
+        dev = self.entity_encoder.final_layer.weight.device
+        if dev.type != "cuda":
+            raise RuntimeError("ghmfc link runs on the GPU only (no CPU fallback): move the model and the batch with .cuda()")
+        if table.text.device != dev:
+            table = table.to(dev)
+            if attached:
+                self.attach_entity_table(table)
+        check_table(table, self.cfg.embed_dim)
+        x = self._mention_only(mention).contiguous()
+        st, rows = self._tf, self._entity_rows(table)
+        if st.inv is None or st.inv_key != st.rows_key:
+            st.inv = None
+            st.inv, st.inv_key = row_inv_norms(rows, self.cfg.cosine_eps), st.rows_key
+        return table_topk(x, rows, st.inv, k, self.cfg.cosine_eps, self.precision)
 
     def check_indices(self, wait: bool = True) -> None:
         """Raise `IndexError` if any table-form call since the last check met a candidate row outside `[0, E - 1]`, naming the

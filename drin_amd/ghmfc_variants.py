@@ -269,6 +269,12 @@ class VariantModel(TableForm, nn.Module):
             return out
         return span_mean(x, begin, end)
 
+    def _mention_only(self, mention) -> torch.Tensor:
+        """`[B, D]` mention representations from the five mention-side items alone (the eval composition's mention encoder):
+        what `link` ranks the table with."""
+        mf, mmask, begin, end, mimage, _ef, _emask = self._batch_tensors(mention, True)
+        return self._mention(mf, mmask, begin, end, mimage)
+
     def _run(self, batch, want_scores: bool):
         if not self.training:
             with torch.no_grad():

@@ -69,6 +69,19 @@ def corrected_topk(metrics: Sequence[TopkAccuracy], acc_correction: float):
     return [float(m.compute()) / (1 - acc_correction) for m in metrics]
 
 
+def link_recall(rows: torch.Tensor, answer_rows: torch.Tensor, ks: Sequence[int]) -> List[float]:
+    """What a first stage is judged by: for each `k` in `ks`, the fraction of mentions whose answer row is among the first `k`
+    of `rows [B, K]` (the ranked table rows of `model.link`, best first); `answer_rows [B]`.  Plain torch, host or device."""
+    rows, answer_rows = torch.as_tensor(rows), torch.as_tensor(answer_rows)
+    if rows.dim() != 2 or answer_rows.shape != (rows.shape[0],):
+        raise ValueError(f"link_recall: rows {tuple(rows.shape)} must be [B, K] and answer_rows {tuple(answer_rows.shape)} [B]")
+    ks = [int(k) for k in ks]
+    if any(k < 1 or k > rows.shape[1] for k in ks):
+        raise ValueError(f"link_recall: every k of {ks} must be in [1, {rows.shape[1]}] (the rows returned per mention)")
+    hit = rows == answer_rows.to(rows.device)[:, None]
+    return [float(hit[:, :k].any(dim=1).float().mean()) if rows.shape[0] else 0.0 for k in ks]
+
+
 class _TripletTopk(torch.autograd.Function):
     @staticmethod
     def forward(ctx, y_pred: torch.Tensor, y_true: torch.Tensor, margin: float, topk, correct):

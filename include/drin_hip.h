@@ -747,6 +747,13 @@ DRIN_API size_t drin_ghmfc_workspace_bytes(const drin_ghmfc_config* cfg);
 DRIN_API int drin_ghmfc_forward(const drin_ghmfc_config* cfg, const drin_ghmfc_batch* batch, const drin_ghmfc_params* params,
                                 void* workspace, size_t workspace_bytes, float* scores, float* mention_repr, void* stream);
 
+/* The mention half of drin_ghmfc_forward alone: mention_repr [B, D] with that call's bits (the same launches in the same
+ * shapes).  Neither batch->entity_feature / entity_mask nor cfg->num_candidates / entity_tokens is read: what a caller that
+ * links mentions against the whole table (drin_table_topk) needs.  The workspace has no entity regions; 0 bytes on error. */
+DRIN_API size_t drin_ghmfc_mention_forward_workspace_bytes(const drin_ghmfc_config* cfg);
+DRIN_API int drin_ghmfc_mention_forward(const drin_ghmfc_config* cfg, const drin_ghmfc_batch* batch, const drin_ghmfc_params* params,
+                                        void* workspace, size_t workspace_bytes, float* mention_repr, void* stream);
+
 /* The table form of drin_ghmfc_forward: the candidates of a mention are rows of a device-resident entity
  * table, as on WikiMEL, where the reference's loader gathers them on the host (baselines/data.py: the qid2idx gather,
  * `entity_feature[rows]`, 19.9 MB per mention at the reference widths).  `size` = sizeof(drin_ghmfc_table). */
@@ -949,6 +956,52 @@ DRIN_API int drin_entity_token_mean_indexed(const float* text, const int64_t* ma
 DRIN_API int drin_cosine_rows_indexed_fwd(const float* x, const float* rows, const int64_t* index, int64_t num_entities, float* out,
                                           int32_t batch, int32_t num_candidates, int32_t width, float eps, int32_t* index_status,
                                           void* stream);
+
+/* ---- cosine top-k against the whole table ------------------------------------------------------ *
+ * The k best rows of rows [num_entities, width] for every mention x [batch, width] by cosine, without a [batch, num_entities]
+ * score matrix: what a first stage does (baselines/data.py ranks num_candidates_model candidates that one chose).
+ *
+ * THE ORDERING CONTRACT, followed by every kernel and every entry point below.  For one mention, row a ranks before row b iff
+ * score(a) > score(b), or the scores compare equal and a < b.  A NaN score ranks below -inf and all NaNs compare equal;
+ * -0.0 == +0.0.  This is a total order: a top-k is ONE defined list, whatever way the columns are cut into slices, chunks or
+ * calls.  No floating-point atomics anywhere: two runs give the same bits.
+ *
+ * The selection keeps, per mention, a running list of kp = DRIN_TOPK_KP(k) >= k entries (key, row) in that order, where
+ * key = dot(x, row) * inv_norm[row]: the mention's own norm is one positive factor per mention and changes no ranking.
+ * 1 <= k <= 256.  A block of dot products is ENTITY-major, as the product rows_chunk x^T leaves it: the dot product of mention
+ * b with column c (table row col_base + c) is block[c * ld + b]; ld % 4 == 0, ld >= batch rounded up to a multiple of 4. */
+#define DRIN_TOPK_SLICE 4096 /* columns per workgroup of the partial selection */
+#define DRIN_TOPK_KP(k) ((k) <= 64 ? 64 : (k) <= 128 ? 128 : 256)
+
+/* out[e] = 1 / max(sqrt(sum_d rows[e, d]^2), eps) for rows [num_entities, width]; eps > 0. */
+DRIN_API int drin_row_inv_norms(const float* rows, int64_t num_entities, int32_t width, float eps, float* out, void* stream);
+
+/* The selection alone, on caller-supplied dot products: merges the `cols` columns of `block` (table rows col_base ..
+ * col_base + cols - 1, keys block[c * ld + b] * col_inv_norms[c]; col_inv_norms NULL = 1) into the running lists state_keys
+ * [batch, kp] (float) / state_rows [batch, kp] (int64; -1 = an empty entry, its key is NaN), which `first` != 0 initialises
+ * instead of reading.  scratch: at least ceil(cols / DRIN_TOPK_SLICE) * batch * kp * 8 bytes.  With out_keys / out_rows (both or
+ * neither) the first k entries of the lists - sorted by the contract - are written to out_keys [batch, k], out_rows int64
+ * [batch, k] after the merge; cols = 0 (block and scratch not read, first = 0) only does that.  Keys come back canonical
+ * (+0.0 for -0.0, one quiet NaN).  block, state_keys, state_rows and scratch are 16-byte aligned; batch 1 .. 65535.  Columns
+ * may arrive in any order and any cut; a row fed twice is listed twice. */
+DRIN_API int drin_topk_update(const float* block, int64_t ld, int32_t batch, int64_t cols, int64_t col_base, const float* col_inv_norms,
+                              int32_t k, float* state_keys, int64_t* state_rows, void* scratch, size_t scratch_bytes, int32_t first,
+                              float* out_keys, int64_t* out_rows, void* stream);
+
+/* Bytes of workspace for drin_table_topk; 0 on error (drin_last_error: a bad shape, or a chunk_entities whose block does not
+ * fit).  chunk_entities = 0: the default chunk, a multiple of 256 rows whose block of dot products stays within 256 MiB. */
+DRIN_API size_t drin_table_topk_workspace_bytes(int32_t batch, int64_t num_entities, int32_t width, int32_t k, int64_t chunk_entities);
+
+/* out_rows [batch, k] (int64) = the k best rows of the table for each mention, out_scores [batch, k] their cosines, ordered by
+ * the contract.  Per chunk of chunk_entities rows: ONE product block[chunk, Bp] = rows_chunk x^T (x padded to Bp = batch rounded
+ * up to 4 rows in the workspace; `precision`: DRIN_PREC_BF16X3 or DRIN_PREC_F32, the kernel is the GEMM module's choice by the
+ * chunk's row count), then the selection with row_inv_norms (drin_row_inv_norms of rows with cosine_eps).  After the last chunk
+ * the kp selected rows are scored again as drin_cosine_rows_indexed_fwd scores them (fp32 FMA) and sorted: out_scores ARE that
+ * entry point's bits on out_rows; the product's precision only decides which rows reach the list of kp.  batch 1 .. 65535,
+ * width % 4 == 0, 1 <= k <= min(256, num_entities).  Writes out_scores, out_rows and the workspace, nothing else. */
+DRIN_API int drin_table_topk(const float* x, const float* rows, const float* row_inv_norms, int64_t num_entities, int32_t batch,
+                             int32_t width, int32_t k, float cosine_eps, int32_t precision, int64_t chunk_entities, void* workspace,
+                             size_t workspace_bytes, float* out_scores, int64_t* out_rows, void* stream);
 
 /* ---- activation, row dropout and the span mean (GHMFC's other mention encoders) ---------------- *
  * What nn.TransformerEncoderLayer runs beside its products, attention and LayerNorms (ghmfc.py:72-90), and Avg.avg

@@ -23,6 +23,10 @@ PREC_F32, PREC_BF16X3, PREC_BF16X3_ALL, PREC_BF16X3_IF16 = 0, 1, 3, 5     # (2 a
 ROW_ACT = {"none": 0, "relu": 1, "gelu": 2}                               # drin_row_activation (drin_act_dropout_*)
 FEAT_F32, FEAT_BF16 = 0, 1
 CACHE_F32, CACHE_MIXED_F16 = 0, 1                                      # drin_cache_format
+WIDTH_NOT_BUILT, WIDTH_TINY, WIDTH_GUARDED, WIDTH_EXACT = 0, 1, 2, 3      # drin_width_band
+WIDTH_BANDS = {WIDTH_NOT_BUILT: "not-built", WIDTH_TINY: "tiny", WIDTH_GUARDED: "guarded", WIDTH_EXACT: "exact"}
+# drin_width_family (the last one answers with V, the register slots of k_layernorm_gelu_bwd<V>)
+WIDTH_FAMILIES = {"entity_stream": 0, "pair_rows": 1, "cache_rows": 2, "cache_pack": 3, "cached_pairs": 4, "ln_backward": 5}
 CACHE_FORMATS = {"f32": CACHE_F32, "mixed_f16": CACHE_MIXED_F16}
 ACTIVATIONS = {"gelu": 1, "sigmoid": 2, "relu": 3, "tanh": 4, "silu": 5}   # drin_activation
 
@@ -217,6 +221,7 @@ EXPORTS = {
     "drin_pool_bwd": (C.c_int, [C.POINTER(DrinConfigC), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "drin_fused_supported": (C.c_int, [C.POINTER(DrinConfigC)]),
     "drin_indexed_supported": (C.c_int, [C.POINTER(DrinConfigC)]),
+    "drin_width_class": (C.c_int, [C.POINTER(DrinConfigC), C.c_int]),
     "drin_prepared_bytes": (C.c_size_t, [C.POINTER(DrinConfigC)]),
     "drin_fused_workspace_bytes": (C.c_size_t, [C.POINTER(DrinConfigC)]),
     "drin_workgroups_per_mention": (C.c_int32, [C.POINTER(DrinConfigC), C.c_int32]),

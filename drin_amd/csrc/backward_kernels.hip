@@ -9,6 +9,7 @@
 namespace drin {
 
 constexpr int MAXV = 4;  // float4 columns per lane: D <= 1024
+static_assert(MAXV == kLnBwdMaxSlots, "ln_bwd_slots (internal.h) names the instantiations below");
 
 // ------------------------------------------------------------------------------------------------
 // score = cos(x[b], y[p]) (model.py:207-209), torch>=2 form: xn = x / max(|x|, eps), yn likewise.
@@ -307,7 +308,8 @@ int launch_layernorm_gelu_bwd2(const float* h, const float* mean, const float* r
                                hipStream_t st, int act, SliceSum* defer, float* level1_own) {
   const int64_t total = rows + (h2 != nullptr ? rows2 : 0);
   if (total <= 0) return DRIN_OK;
-  if (D % 4 || D > 256 * MAXV) {
+  const int v = ln_bwd_slots(D);
+  if (v == 0) {
     set_error("layernorm_gelu_bwd: D=%d must be a multiple of 4 and <= %d", D, 256 * MAXV);
     return DRIN_E_SHAPE;
   }
@@ -315,8 +317,7 @@ int launch_layernorm_gelu_bwd2(const float* h, const float* mean, const float* r
   const int64_t cap = 768;
   const int64_t blocks = cdiv(total, 4) < cap ? cdiv(total, 4) : cap;
   KernelTimer timer(DRIN_KC_GCN, st);
-  const int v = (int)cdiv(D / 4, 64);
-  auto kern = v <= 1 ? k_layernorm_gelu_bwd<1> : v == 2 ? k_layernorm_gelu_bwd<2> : v == 3 ? k_layernorm_gelu_bwd<3>
+  auto kern = v == 1 ? k_layernorm_gelu_bwd<1> : v == 2 ? k_layernorm_gelu_bwd<2> : v == 3 ? k_layernorm_gelu_bwd<3>
                                                                                          : k_layernorm_gelu_bwd<4>;
   const LnBwdSeg sa{h, mean, rstd, g, rows};
   const LnBwdSeg sb{h2, mean2, rstd2, g2, h2 != nullptr ? rows2 : 0};

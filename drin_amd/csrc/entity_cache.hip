@@ -735,15 +735,24 @@ DRIN_API int drin_build_entity_cache(const drin_config* cfg, const drin_batch* t
     {
       KernelTimer timer(DRIN_KC_STREAM, st);
       const dim3 grid((unsigned)cdiv(rows, 4)), block(256);
-      const bool tiny = a.D4 <= 64 && a.R4 <= 64;
-      if (tiny && T > 0)
-        hipLaunchKernelGGL((k_entity_cache_rows<1, 1, true>), grid, block, 0, st, a);
-      else if (tiny)
-        hipLaunchKernelGGL((k_entity_cache_rows<1, 1, false>), grid, block, 0, st, a);
-      else if (T > 0)
-        hipLaunchKernelGGL((k_entity_cache_rows<3, 8, true>), grid, block, 0, st, a);
-      else
-        hipLaunchKernelGGL((k_entity_cache_rows<3, 8, false>), grid, block, 0, st, a);
+      switch (cache_rows_width_band(a.D4, a.R4)) {
+        case DRIN_WIDTH_TINY:
+          if (T > 0)
+            hipLaunchKernelGGL((k_entity_cache_rows<1, 1, true>), grid, block, 0, st, a);
+          else
+            hipLaunchKernelGGL((k_entity_cache_rows<1, 1, false>), grid, block, 0, st, a);
+          break;
+        case DRIN_WIDTH_GUARDED:
+        case DRIN_WIDTH_EXACT:   // (no instantiation of its own: the guarded one with every lane full)
+          if (T > 0)
+            hipLaunchKernelGGL((k_entity_cache_rows<3, 8, true>), grid, block, 0, st, a);
+          else
+            hipLaunchKernelGGL((k_entity_cache_rows<3, 8, false>), grid, block, 0, st, a);
+          break;
+        default:   // cache_supported has refused these widths
+          set_error("entity cache: D=%d R=%d outside the built instantiations", D, R);
+          return DRIN_E_UNSUPPORTED;
+      }
       DRIN_CHECK_LAUNCH("k_entity_cache_rows");
     }
     const float* ximg = tables->entity_image + e0 * (int64_t)R;
@@ -762,10 +771,18 @@ DRIN_API int drin_build_entity_cache(const drin_config* cfg, const drin_batch* t
     if (mixed) {   // (static edges: zero units, unit scales)
       KernelTimer timer(DRIN_KC_STREAM, st);
       const dim3 grid((unsigned)cdiv(rows, 4)), block(256);
-      if (D / 4 <= 64)
-        hipLaunchKernelGGL((k_cache_pack_mixed<1>), grid, block, 0, st, tmp, crow, ldc, rows, D / 4, R / 4, dyn ? 1 : 0);
-      else
-        hipLaunchKernelGGL((k_cache_pack_mixed<3>), grid, block, 0, st, tmp, crow, ldc, rows, D / 4, R / 4, dyn ? 1 : 0);
+      switch (cache_pack_width_band(D / 4)) {
+        case DRIN_WIDTH_TINY:
+          hipLaunchKernelGGL((k_cache_pack_mixed<1>), grid, block, 0, st, tmp, crow, ldc, rows, D / 4, R / 4, dyn ? 1 : 0);
+          break;
+        case DRIN_WIDTH_GUARDED:
+        case DRIN_WIDTH_EXACT:
+          hipLaunchKernelGGL((k_cache_pack_mixed<3>), grid, block, 0, st, tmp, crow, ldc, rows, D / 4, R / 4, dyn ? 1 : 0);
+          break;
+        default:
+          set_error("entity cache: D=%d outside the built instantiations", D);
+          return DRIN_E_UNSUPPORTED;
+      }
       DRIN_CHECK_LAUNCH("k_cache_pack_mixed");
     }
   }
@@ -859,28 +876,31 @@ DRIN_API int drin_forward_cached(const drin_config* cfg, const drin_batch* b, co
   a.c_part = ws + L.c_part;
   a.s2_part = ws + L.s2_part;
   a.chunks = L.chunks;
-  if (cache_mixed(*cfg)) {   // DRIN_CACHE_MIXED_F16 rows (the o^ row is read in the PAIR layout: an even number of slots)
-    const bool gen = a.act_v != DRIN_ACT_GELU, tiny = a.D4 <= 64 && a.R4 <= 128;
-    if (gen && tiny)
-      DRIN_TRY((launch_cached_pairs_t<1, 2, false, true, true>(a, st)));
-    else if (gen)
-      DRIN_TRY((launch_cached_pairs_t<3, 8, false, true, true>(a, st)));
-    else if (tiny)
-      DRIN_TRY((launch_cached_pairs_t<1, 2, false, false, true>(a, st)));
-    else if (a.D4 == 192 && a.R4 == 512)
-      DRIN_TRY((launch_cached_pairs_t<3, 8, true, false, true>(a, st)));
-    else
-      DRIN_TRY((launch_cached_pairs_t<3, 8, false, false, true>(a, st)));
-  } else if (a.act_v != DRIN_ACT_GELU && a.D4 <= 64 && a.R4 <= 64)   // non-default vertex activation: the generic-width instantiations
-    DRIN_TRY((launch_cached_pairs_t<1, 1, false, true>(a, st)));
-  else if (a.act_v != DRIN_ACT_GELU)
-    DRIN_TRY((launch_cached_pairs_t<3, 8, false, true>(a, st)));
-  else if (a.D4 <= 64 && a.R4 <= 64)
-    DRIN_TRY((launch_cached_pairs_t<1, 1, false>(a, st)));
-  else if (a.D4 == 192 && a.R4 == 512)
-    DRIN_TRY((launch_cached_pairs_t<3, 8, true>(a, st)));
-  else
-    DRIN_TRY((launch_cached_pairs_t<3, 8, false>(a, st)));
+  {
+    // DRIN_CACHE_MIXED_F16 rows: the o^ row is read in the PAIR layout, an even number of image slots; a non-default vertex
+    // activation: the GENERIC_ACT twins (none at the exact width, which then runs the guarded form)
+    const bool mixed = cache_mixed(*cfg), gen = a.act_v != DRIN_ACT_GELU;
+    switch (cached_pairs_width_band(a.D4, a.R4, mixed, gen)) {
+      case DRIN_WIDTH_TINY:
+        if (mixed)
+          DRIN_TRY((gen ? launch_cached_pairs_t<1, 2, false, true, true>(a, st) : launch_cached_pairs_t<1, 2, false, false, true>(a, st)));
+        else
+          DRIN_TRY((gen ? launch_cached_pairs_t<1, 1, false, true>(a, st) : launch_cached_pairs_t<1, 1, false>(a, st)));
+        break;
+      case DRIN_WIDTH_EXACT:
+        DRIN_TRY((mixed ? launch_cached_pairs_t<3, 8, true, false, true>(a, st) : launch_cached_pairs_t<3, 8, true>(a, st)));
+        break;
+      case DRIN_WIDTH_GUARDED:
+        if (mixed)
+          DRIN_TRY((gen ? launch_cached_pairs_t<3, 8, false, true, true>(a, st) : launch_cached_pairs_t<3, 8, false, false, true>(a, st)));
+        else
+          DRIN_TRY((gen ? launch_cached_pairs_t<3, 8, false, true>(a, st) : launch_cached_pairs_t<3, 8, false>(a, st)));
+        break;
+      default:   // cache_supported has refused these widths
+        set_error("drin_forward_cached: D=%d R=%d outside the built instantiations", D, a.R4 * 4);
+        return DRIN_E_UNSUPPORTED;
+    }
+  }
 
   // (3) layer-1 mention vertices, then what layer 2 needs from them
   float* vm1 = ws + L.vm1;

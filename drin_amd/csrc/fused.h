@@ -124,6 +124,43 @@ struct FinalArgs {
   float ln_eps, cos_eps;
 };
 
+// ---- which width band a family's launcher takes (drin_width_class) ----------------------------------------------------------------
+// Every width-templated kernel of the folded and cached paths is built in three forms: `tiny` (one float4 per lane in every slot the
+// family has), `exact` (D = 768 and, where the family reads image rows, R = 2048: every lane of every slot full, widths compile-time
+// constants) and `guarded` (the exact form's register slots with `c4 < D4` guards: part of the lanes, or whole slots, hold nothing).
+// Each family's choice is made HERE, once: its launcher switches on the result and drin_width_class exports it, so a test asks the
+// dispatch which form a shape takes instead of restating the gates (the argument of the GEMM route record, internal.h) - a pure
+// function of the widths is enough, no per-thread record.  D4 / R4: widths in float4 quads.
+constexpr int kTinyQuads = 64;                        // one quad per lane of a wave
+constexpr int kExactTextQuads = 192, kExactImageQuads = 512;   // D = 768 (three slots), R = 2048 (eight)
+// k_entity_stream<1,1> / <3,8,EXACT> / <3,8,false>; also what fused_supported accepts
+inline int stream_width_band(int D4, int R4) {
+  if (D4 <= kTinyQuads && R4 <= kTinyQuads) return DRIN_WIDTH_TINY;
+  if (D4 == kExactTextQuads && R4 == kExactImageQuads) return DRIN_WIDTH_EXACT;
+  if (D4 <= kExactTextQuads && R4 <= kExactImageQuads) return DRIN_WIDTH_GUARDED;
+  return DRIN_WIDTH_NOT_BUILT;
+}
+// k_pair_layer1 / k_pair_final <1> / <3,true> / <3,false>: text rows only.  A non-default vertex activation has the GENERIC_ACT
+// twins of the tiny and the guarded form; at D = 768 it runs the guarded one
+inline int pair_width_band(int D4, bool generic_act) {
+  if (D4 <= kTinyQuads) return DRIN_WIDTH_TINY;
+  if (D4 == kExactTextQuads && !generic_act) return DRIN_WIDTH_EXACT;
+  if (D4 <= kExactTextQuads) return DRIN_WIDTH_GUARDED;
+  return DRIN_WIDTH_NOT_BUILT;
+}
+// k_entity_cache_rows<1,1> / <3,8>: one guarded instantiation serves the exact width too (`exact` then says every lane is full)
+inline int cache_rows_width_band(int D4, int R4) { return stream_width_band(D4, R4); }
+// k_cache_pack_mixed<1> / <3>: text-width fields only; the same remark
+inline int cache_pack_width_band(int D4) { return pair_width_band(D4, false); }
+// k_cached_pairs: fp32 rows <1,1> / <3,8,EXACT> / <3,8,false>; DRIN_CACHE_MIXED_F16 rows read the object row in the pair layout,
+// an even number of image slots: <1,2> up to R = 512.  GENERIC_ACT twins as for the pair kernels
+inline int cached_pairs_width_band(int D4, int R4, bool mixed, bool generic_act) {
+  if (D4 <= kTinyQuads && R4 <= (mixed ? 2 * kTinyQuads : kTinyQuads)) return DRIN_WIDTH_TINY;
+  if (D4 == kExactTextQuads && R4 == kExactImageQuads && !generic_act) return DRIN_WIDTH_EXACT;
+  if (D4 <= kExactTextQuads && R4 <= kExactImageQuads) return DRIN_WIDTH_GUARDED;
+  return DRIN_WIDTH_NOT_BUILT;
+}
+
 // An argument block starts zeroed; the fields that restate the configuration are derived here and nowhere else (shape: every
 // block; vertex fields: PairArgs, FinalArgs, CachedArgs; edge fields: StreamArgs, CachedArgs); the rest is the call site's.
 template <class Args>

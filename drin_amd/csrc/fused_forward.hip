@@ -209,9 +209,7 @@ int fused_supported(const drin_config* c) {
     set_error("fused path: inner feature dims > 1 need the pooled path of drin_forward");
     return DRIN_E_UNSUPPORTED;
   }
-  const bool tiny = c->embed_dim <= 256 && c->image_dim <= 256;
-  const bool full = c->embed_dim <= 768 && c->image_dim <= 2048;
-  if (!tiny && !full) {
+  if (stream_width_band(c->embed_dim / 4, c->image_dim / 4) == DRIN_WIDTH_NOT_BUILT) {   // every family is built where this one is
     set_error("fused path: D=%d R=%d outside the built instantiations", c->embed_dim, c->image_dim);
     return DRIN_E_UNSUPPORTED;
   }
@@ -246,6 +244,31 @@ int drin_linear_planes_fwd(const void* x_hi, const void* x_lo, const void* w_hi,
 int drin_fused_supported(const drin_config* cfg) {
   DRIN_TRY(validate_config(cfg));
   return fused_supported(cfg);
+}
+
+int drin_width_class(const drin_config* cfg, int family) {
+  DRIN_TRY(validate_config(cfg));
+  if (family < DRIN_WIDTH_FAMILY_ENTITY_STREAM || family > DRIN_WIDTH_FAMILY_LN_BACKWARD) {
+    set_error("drin_width_class: family %d is not a drin_width_family", family);
+    return DRIN_E_SHAPE;
+  }
+  if (family == DRIN_WIDTH_FAMILY_LN_BACKWARD) return ln_bwd_slots(cfg->embed_dim);   // the layer-by-layer path: any validated width
+  if (fused_supported(cfg) != DRIN_OK) return DRIN_WIDTH_NOT_BUILT;
+  const int D4 = cfg->embed_dim / 4, R4 = cfg->image_dim / 4;
+  const bool gen = vertex_act(cfg) != DRIN_ACT_GELU, mixed = cfg->cache_format == DRIN_CACHE_MIXED_F16;
+  const bool mixed_rows_fit = cfg->embed_dim % 8 == 0 && cfg->image_dim % 8 == 0;   // (cache_supported, entity_cache.hip)
+  switch (family) {
+    case DRIN_WIDTH_FAMILY_ENTITY_STREAM:
+      return stream_width_band(D4, R4);
+    case DRIN_WIDTH_FAMILY_PAIR_ROWS:
+      return pair_width_band(D4, gen);
+    case DRIN_WIDTH_FAMILY_CACHE_ROWS:
+      return mixed && !mixed_rows_fit ? DRIN_WIDTH_NOT_BUILT : cache_rows_width_band(D4, R4);
+    case DRIN_WIDTH_FAMILY_CACHE_PACK:   // runs for DRIN_CACHE_MIXED_F16 rows only
+      return mixed && mixed_rows_fit ? cache_pack_width_band(D4) : DRIN_WIDTH_NOT_BUILT;
+    default:
+      return mixed && !mixed_rows_fit ? DRIN_WIDTH_NOT_BUILT : cached_pairs_width_band(D4, R4, mixed, gen);
+  }
 }
 
 size_t drin_prepared_bytes(const drin_config* cfg) {

@@ -395,12 +395,16 @@ int launch_entity_stream(const StreamArgs& a, hipStream_t st) {
     return DRIN_E_SHAPE;
   }
   const bool tok = a.T > 0;
-  if (a.D4 <= 64 && a.R4 <= 64)
-    return tok ? launch_stream_t<1, 1, true, false>(a, st) : launch_stream_t<1, 1, false, false>(a, st);
-  if (a.D4 == 192 && a.R4 == 512)
-    return tok ? launch_stream_t<3, 8, true, true>(a, st) : launch_stream_t<3, 8, false, true>(a, st);
-  if (a.D4 <= 192 && a.R4 <= 512)
-    return tok ? launch_stream_t<3, 8, true, false>(a, st) : launch_stream_t<3, 8, false, false>(a, st);
+  switch (stream_width_band(a.D4, a.R4)) {
+    case DRIN_WIDTH_TINY:
+      return tok ? launch_stream_t<1, 1, true, false>(a, st) : launch_stream_t<1, 1, false, false>(a, st);
+    case DRIN_WIDTH_EXACT:
+      return tok ? launch_stream_t<3, 8, true, true>(a, st) : launch_stream_t<3, 8, false, true>(a, st);
+    case DRIN_WIDTH_GUARDED:
+      return tok ? launch_stream_t<3, 8, true, false>(a, st) : launch_stream_t<3, 8, false, false>(a, st);
+    default:
+      break;
+  }
   set_error("entity_stream: D=%d R=%d outside the built instantiations", a.D4 * 4, a.R4 * 4);
   return DRIN_E_UNSUPPORTED;
 }
@@ -568,19 +572,27 @@ __global__ void __launch_bounds__(256) k_pair_layer1(const PairArgs a) {
 int launch_pair_layer1(const PairArgs& a, hipStream_t st) {
   if (a.B <= 0) return DRIN_OK;
   KernelTimer timer(DRIN_KC_GCN, st);
-  if (a.act_v != DRIN_ACT_GELU && a.D4 <= 64)          // non-default vertex activation (args.py:35): the generic-width instantiations
-    hipLaunchKernelGGL((k_pair_layer1<1, false, true>), dim3((unsigned)a.chunks, (unsigned)a.B), dim3(256), 0, st, a);
-  else if (a.act_v != DRIN_ACT_GELU && a.D4 <= 192)
-    hipLaunchKernelGGL((k_pair_layer1<3, false, true>), dim3((unsigned)a.chunks, (unsigned)a.B), dim3(256), 0, st, a);
-  else if (a.D4 <= 64)
-    hipLaunchKernelGGL((k_pair_layer1<1, false>), dim3((unsigned)a.chunks, (unsigned)a.B), dim3(256), 0, st, a);
-  else if (a.D4 == 192)
-    hipLaunchKernelGGL((k_pair_layer1<3, true>), dim3((unsigned)a.chunks, (unsigned)a.B), dim3(256), 0, st, a);
-  else if (a.D4 < 192)
-    hipLaunchKernelGGL((k_pair_layer1<3, false>), dim3((unsigned)a.chunks, (unsigned)a.B), dim3(256), 0, st, a);
-  else {
-    set_error("pair_layer1: D=%d outside the built instantiations", a.D4 * 4);
-    return DRIN_E_UNSUPPORTED;
+  const bool gen = a.act_v != DRIN_ACT_GELU;   // non-default vertex activation (args.py:35): the GENERIC_ACT twins
+  const dim3 grid((unsigned)a.chunks, (unsigned)a.B), block(256);
+  switch (pair_width_band(a.D4, gen)) {
+    case DRIN_WIDTH_TINY:
+      if (gen)
+        hipLaunchKernelGGL((k_pair_layer1<1, false, true>), grid, block, 0, st, a);
+      else
+        hipLaunchKernelGGL((k_pair_layer1<1, false>), grid, block, 0, st, a);
+      break;
+    case DRIN_WIDTH_EXACT:
+      hipLaunchKernelGGL((k_pair_layer1<3, true>), grid, block, 0, st, a);
+      break;
+    case DRIN_WIDTH_GUARDED:
+      if (gen)
+        hipLaunchKernelGGL((k_pair_layer1<3, false, true>), grid, block, 0, st, a);
+      else
+        hipLaunchKernelGGL((k_pair_layer1<3, false>), grid, block, 0, st, a);
+      break;
+    default:
+      set_error("pair_layer1: D=%d outside the built instantiations", a.D4 * 4);
+      return DRIN_E_UNSUPPORTED;
   }
   DRIN_CHECK_LAUNCH("k_pair_layer1");
   return DRIN_OK;
@@ -654,19 +666,27 @@ __global__ void __launch_bounds__(256) k_pair_final(const FinalArgs a) {
 int launch_pair_final(const FinalArgs& a, hipStream_t st) {
   if (a.B <= 0) return DRIN_OK;
   KernelTimer timer(DRIN_KC_GCN, st);
-  if (a.act_v != DRIN_ACT_GELU && a.D4 <= 64)          // non-default vertex activation (args.py:35): the generic-width instantiations
-    hipLaunchKernelGGL((k_pair_final<1, false, true>), dim3((unsigned)a.chunks, (unsigned)a.B), dim3(256), 0, st, a);
-  else if (a.act_v != DRIN_ACT_GELU && a.D4 <= 192)
-    hipLaunchKernelGGL((k_pair_final<3, false, true>), dim3((unsigned)a.chunks, (unsigned)a.B), dim3(256), 0, st, a);
-  else if (a.D4 <= 64)
-    hipLaunchKernelGGL((k_pair_final<1, false>), dim3((unsigned)a.chunks, (unsigned)a.B), dim3(256), 0, st, a);
-  else if (a.D4 == 192)
-    hipLaunchKernelGGL((k_pair_final<3, true>), dim3((unsigned)a.chunks, (unsigned)a.B), dim3(256), 0, st, a);
-  else if (a.D4 < 192)
-    hipLaunchKernelGGL((k_pair_final<3, false>), dim3((unsigned)a.chunks, (unsigned)a.B), dim3(256), 0, st, a);
-  else {
-    set_error("pair_final: D=%d outside the built instantiations", a.D4 * 4);
-    return DRIN_E_UNSUPPORTED;
+  const bool gen = a.act_v != DRIN_ACT_GELU;   // non-default vertex activation (args.py:35): the GENERIC_ACT twins
+  const dim3 grid((unsigned)a.chunks, (unsigned)a.B), block(256);
+  switch (pair_width_band(a.D4, gen)) {
+    case DRIN_WIDTH_TINY:
+      if (gen)
+        hipLaunchKernelGGL((k_pair_final<1, false, true>), grid, block, 0, st, a);
+      else
+        hipLaunchKernelGGL((k_pair_final<1, false>), grid, block, 0, st, a);
+      break;
+    case DRIN_WIDTH_EXACT:
+      hipLaunchKernelGGL((k_pair_final<3, true>), grid, block, 0, st, a);
+      break;
+    case DRIN_WIDTH_GUARDED:
+      if (gen)
+        hipLaunchKernelGGL((k_pair_final<3, false, true>), grid, block, 0, st, a);
+      else
+        hipLaunchKernelGGL((k_pair_final<3, false>), grid, block, 0, st, a);
+      break;
+    default:
+      set_error("pair_final: D=%d outside the built instantiations", a.D4 * 4);
+      return DRIN_E_UNSUPPORTED;
   }
   DRIN_CHECK_LAUNCH("k_pair_final");
   return DRIN_OK;

@@ -207,6 +207,14 @@ inline void note_route(const RouteNote& n) {
   r.tiles = n.tiles, r.whole_tiles = n.whole_tiles, r.tile0 = n.tile0, r.work_items = n.work_items;
 }
 
+// ---- which LayerNorm-backward instantiation a width takes (drin_width_class) ------------------------------------------------------
+// k_layernorm_gelu_bwd<V> keeps a row in V float4 register slots per lane: V = ceil(D / 256), 0 when the width is not built.  The one
+// place this is decided, like the width bands of the folded path's families (fused.h): the launcher and drin_width_class call it.
+constexpr int kLnBwdMaxSlots = 4;
+inline int ln_bwd_slots(int D) {
+  return (D <= 0 || D % 4 || D > 256 * kLnBwdMaxSlots) ? 0 : (D / 4 + 63) / 64;
+}
+
 // ---- what the backward products did (drin_wgrad_probe) ----------------------------------------------
 // This thread's record of the weight-gradient, bias-gradient and dX launches, written by the dispatch code next to each launch like
 // the NT record above.  The probe names its products here while it runs; a launcher that carries one of them (the same dy, x and dw)

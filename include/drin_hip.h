@@ -369,6 +369,38 @@ DRIN_API size_t drin_input_grad_scratch_bytes(const drin_config* cfg);
 DRIN_API int drin_pool_bwd(const drin_config* cfg, const int64_t* entity_text_mask, const float* grad_pooled,
                            const float* grad_cls, void* grad_entity_text, void* stream);
 
+/* ---- which width form a configuration takes (additive under ABI 12) -------------------------------
+ * The width-templated row kernels of the folded and cached inference paths, and the LayerNorm backward of training, are built
+ * in a few forms per family, chosen from the widths alone: `tiny` (embed_dim and - where the family reads image rows -
+ * image_dim up to 256: one 16-byte quad per lane and register slot), `exact` (768 / 2048: every lane of every slot full, the
+ * widths compile-time constants) and `guarded` (anything between: the exact form's slots behind column guards, so that part of
+ * the lanes, or whole slots, hold nothing).  drin_width_class answers with the form the family's launcher takes for `cfg` - the
+ * launchers switch on the same host function - so that a caller, or a test, asks instead of restating the gates.
+ * Returns a drin_width_band (>= 0), or a negative drin_status for a NULL / invalid config or an unknown family.
+ * DRIN_WIDTH_NOT_BUILT where the family does not run for `cfg`: a geometry drin_fused_supported refuses (every family but the
+ * LayerNorm backward), DRIN_WIDTH_FAMILY_CACHE_PACK with cfg.cache_format == DRIN_CACHE_F32 (fp32 rows are not packed), the
+ * cache families with DRIN_CACHE_MIXED_F16 at a width that is no multiple of 8.
+ * DRIN_WIDTH_FAMILY_LN_BACKWARD returns V = ceil(embed_dim / 256) in 1 .. 4 instead: the register slots of
+ * k_layernorm_gelu_bwd<V> (the training path, any validated width). Host-only. */
+typedef enum {
+  DRIN_WIDTH_NOT_BUILT = 0,
+  DRIN_WIDTH_TINY = 1,
+  DRIN_WIDTH_GUARDED = 2,
+  DRIN_WIDTH_EXACT = 3
+} drin_width_band;
+typedef enum {
+  DRIN_WIDTH_FAMILY_ENTITY_STREAM = 0, /* k_entity_stream (drin_forward_prepared)                                            */
+  DRIN_WIDTH_FAMILY_PAIR_ROWS = 1,     /* k_pair_layer1, k_pair_final: embed_dim and cfg.vertex_activation (a non-default one
+                                          has no exact form: guarded at 768)                                                 */
+  DRIN_WIDTH_FAMILY_CACHE_ROWS = 2,    /* k_entity_cache_rows (drin_build_entity_cache); one guarded kernel serves 768 / 2048
+                                          too, where the answer is still `exact`                                              */
+  DRIN_WIDTH_FAMILY_CACHE_PACK = 3,    /* k_cache_pack_mixed: embed_dim alone; the same remark                                */
+  DRIN_WIDTH_FAMILY_CACHED_PAIRS = 4,  /* k_cached_pairs (drin_forward_cached): cfg.cache_format (mixed rows are tiny up to
+                                          image_dim 512) and cfg.vertex_activation                                           */
+  DRIN_WIDTH_FAMILY_LN_BACKWARD = 5    /* k_layernorm_gelu_bwd<V>: returns V                                                  */
+} drin_width_family;
+DRIN_API int drin_width_class(const drin_config* cfg, int family);
+
 /* ---- fused two-layer inference path ------------------------------------------------------------
  * Same result as drin_forward (fp32 re-association only) for the default geometry num_layers == 2,
  * with the weight-only products folded once per weight version (csrc/fused_forward.hip):

@@ -33,9 +33,12 @@ def _adam_call(p, g, m, v, t, lr):
 
 def test_library_adam_matches_torch_adam_bitwise():
     """drin_adam_step == torch.optim.Adam (default multi-tensor implementation) BIT FOR BIT over several steps, on values
-    spanning many magnitudes: the training loop's trajectory is then the reference loop's (Adam amplifies rounding)."""
+    spanning many magnitudes: the training loop's trajectory is then the reference loop's (Adam amplifies rounding).
+    One size: 1728 blocks - under the 2048-block cap, so one trip of the grid-stride loop - and a tail of one element, torch's
+    default betas and eps.  Sizes without a float4, the second trip, other hyper-parameters and non-finite gradients:
+    tests/test_gpu_step_kernels.py."""
     g = torch.Generator(device=DEV).manual_seed(5)
-    n = 3 * 768 * 768 + 13                                    # ragged tail included
+    n = 3 * 768 * 768 + 13                                    # n % 4 = 1: a ragged tail of one element
     p0 = torch.randn(n, device=DEV, generator=g) * torch.logspace(-6, 2, n, device=DEV)
     grads = [torch.randn(n, device=DEV, generator=g) * torch.logspace(-8, 1, n, device=DEV).flip(0) for _ in range(6)]
     ref = torch.nn.Parameter(p0.clone())

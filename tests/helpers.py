@@ -60,7 +60,7 @@ class _relu_spy:
 
 
 def every_path_against_the_oracle(cfg, B, precision, seed, label, weights_seed=None, index_seed=None, table_refusal=None,
-                                  cached_refusal=None):
+                                  cached_refusal=None, same_bits=False):
     """Every path the product offers for `cfg` against the CPU oracle on the same inputs: inference (the folded path where it
     applies, else layer by layer), the training-mode forward, the parameter gradients of the caller's loss against fp64 autograd
     through the oracle (the conditioning yardstick, the bounded relu excuse, WHICH gradients are None), the table form and the
@@ -69,6 +69,8 @@ def every_path_against_the_oracle(cfg, B, precision, seed, label, weights_seed=N
     `table_refusal` / `cached_refusal`: a regular expression - the table form without a cache / the per-entity cache in both row
     formats is then EXPECTED to refuse the call with the library's own error of that text (split-bf16 precision at a width that
     is no multiple of 32) instead of scoring: a route scores inside its bar or says why it does not, nothing else.
+    `same_bits`: every inference route (gathered batch, table form, each cache format) is scored a second time and must return
+    the same bits.
     Returns what it measured and built: {"inference", "training", "table", "cache": {format: error}, "model", "batch"}."""
     import pytest
     from drin_amd import _lib, synth
@@ -104,7 +106,10 @@ def every_path_against_the_oracle(cfg, B, precision, seed, label, weights_seed=N
 
     model.eval()
     with torch.no_grad():
-        e_inf = check(model(dbatch[:14]), "inference")
+        first = model(dbatch[:14])
+        e_inf = check(first, "inference")
+        if same_bits:
+            assert torch.equal(first, model(dbatch[:14])), f"case {label} inference: a second run gives other bits"
     model.train()
     out = model(dbatch[:14])
     e_trn = check(out, "training forward")
@@ -208,6 +213,8 @@ def every_path_against_the_oracle(cfg, B, precision, seed, label, weights_seed=N
                         cache_errs[fmt] = "refused"
                     continue
                 got = model(ib).cpu()
+                if same_bits:
+                    assert torch.equal(got, model(ib).cpu()), f"case {label} table form (cache {fmt}): a second run gives other bits"
                 assert torch.equal(torch.isnan(got), torch.isnan(ref_t)), f"case {label} table form ({fmt}): NaN pattern"
                 err = (got - ref_t)[fin_t].abs().max().item()
                 # (mixed rows at D = 64: the fp16 operands' rounding is averaged over 64 columns only)
@@ -253,3 +260,22 @@ def width_classes(cfg, cache_format="f32"):
     return {f: width_class(cfg.gcn_embed_dim, cfg.resnet_embed_dim, f, cache_format, cfg.gcn_vertex_activation,
                            num_layers=cfg.num_gcn_layers, vector_edges=1 if cfg.gcn_edge_feature == "vector" else 0)
             for f in _lib.WIDTH_FAMILIES}
+
+
+# ---- how the library cuts a mention's candidate list into workgroups (drin_workgroups_per_mention) ---------------------------------
+def workgroups_per_mention(D, R, B, N, cached, vertex_activation="gelu", **fields):
+    """`drin_workgroups_per_mention` of a default `drin_config` of B mentions x N candidates at widths D / R: the chunks of the
+    folded path (`cached` false) or of the per-entity-cache path; 0 where the geometry has neither.  Host-only."""
+    import ctypes as C
+    from drin_amd import _lib
+    c = config_c(D, R, vertex_activation=vertex_activation, batch=B, num_candidates=N, **fields)
+    return _lib.load().drin_workgroups_per_mention(C.byref(c), 1 if cached else 0)
+
+
+def workgroups_of(cfg, B, cached, precision="f32", num_entities=0):
+    """... of a `DrinConfig` (widths, candidates, token count, vertex activation) at B mentions."""
+    from drin_amd import _lib
+    prec = {"f32": _lib.PREC_F32, "bf16x3": _lib.PREC_BF16X3, "bf16x3_all": _lib.PREC_BF16X3_ALL}[precision]
+    return workgroups_per_mention(cfg.gcn_embed_dim, cfg.resnet_embed_dim, B, cfg.num_candidates_model, cached,
+                                  cfg.gcn_vertex_activation, precision=prec, num_entities=num_entities,
+                                  entity_tokens=cfg.max_entity_attr_token_len if cfg.token_level_entities else 0)

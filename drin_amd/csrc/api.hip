@@ -587,7 +587,7 @@ static int run_input_grads(const drin_config* c, const drin_batch* b, const drin
       DRIN_TRY(tb.add(w, planes, (int64_t)D * n_out));
       DRIN_TRY(launch_transpose_split_batch(tb, D, n_out, st));
     }
-    return launch_gemm_nn(g, D, w, n_out, out, n_out, (int64_t)M, n_out, D, acc, c->precision, st, nullptr, 0, {planes});
+    return launch_gemm_nn({{g, D}, {w, n_out}, out, n_out, (int64_t)M, n_out, D, acc}, c->precision, st, {}, {planes});
   };
 
   // the scalar layer-0 edges: vector edges are the scalar ones broadcast over D (model.py:202) - their row sums
@@ -626,7 +626,7 @@ static int run_input_grads(const drin_config* c, const drin_batch* b, const drin
     DRIN_TRY(launch_mention_rows_bwd(tt ? sc + S.g_span : nullptr, g_mt, b->mention_start, b->mention_end, ie, iv, head->representation,
                                      head->encoded != nullptr, ig->mention_text, head->grad_encoded, B, c->mention_tokens, D, st));
   } else if (ig->mention_text) {
-    DRIN_TRY(launch_gemm_nn(g_mt, D, W->w_mention_text, D, sc + S.g_span, D, B, D, D, tt, DRIN_PREC_F32, st));
+    DRIN_TRY(launch_gemm_nn({{g_mt, D}, {W->w_mention_text, D}, sc + S.g_span, D, B, D, D, tt}, DRIN_PREC_F32, st));
     DRIN_TRY(launch_span_mean_bwd(sc + S.g_span, b->mention_start, b->mention_end, ig->mention_text, B, c->mention_tokens, D, st));
   }
   // entity text: d x_et = d et W_et (+ the edge term when the raw rows are entity_text itself); token blocks: the pooling's
@@ -641,7 +641,7 @@ static int run_input_grads(const drin_config* c, const drin_batch* b, const drin
   // images: d x = d v W (model.py:41-45), then the means' backward
   if (ig->mention_image) {
     if (live) {
-      DRIN_TRY(launch_gemm_nn(g_mi, D, W->w_mention_image, R, sc + S.g_mimg, R, B, R, D, false, DRIN_PREC_F32, st));
+      DRIN_TRY(launch_gemm_nn({{g_mi, D}, {W->w_mention_image, R}, sc + S.g_mimg, R, B, R, D}, DRIN_PREC_F32, st));
       DRIN_TRY(launch_axis_mean_bwd(sc + S.g_mimg, ig->mention_image, B, c->image_regions, R, st));
     } else {
       DRIN_TRY(zero_out(ig->mention_image, (size_t)B * c->image_regions * R, st));
@@ -824,7 +824,7 @@ int drin_linear_fwd(const float* x, const float* w, const float* bias, float* y,
     set_error("drin_linear_fwd: bad shape rows=%lld n_out=%d k=%d", (long long)rows, n_out, k);
     return DRIN_E_SHAPE;
   }
-  return launch_gemm_nt(x, k, w, k, bias, y, n_out, rows, n_out, k, false, precision, (hipStream_t)stream);
+  return launch_gemm_nt({{x, k}, {w, k}, bias, y, n_out, rows, n_out, k}, precision, (hipStream_t)stream);
 }
 
 int drin_linear_bwd(const float* x, const float* w, const float* dy, float* dx, float* dw, float* db, int64_t rows,
@@ -844,13 +844,12 @@ int drin_linear_bwd(const float* x, const float* w, const float* dy, float* dx, 
     // the scratch holds W^T [k][n_out] for the split-bf16 form; what that leaves of it lets a partly filled last round of
     // tiles split along K
     const size_t used = Arena::rounded((size_t)n_out * k);
-    float* tail = scratch && scratch_floats > used ? Arena::at(scratch, used) : nullptr;
-    DRIN_TRY(launch_gemm_nn(dy, n_out, w, k, dx, k, rows, k, n_out, false, precision, st, nullptr, 0,
-                            {nullptr, scratch, scratch_floats, tail, tail ? scratch_floats - used : 0}));
+    const GemmScratch tail = scratch_at(scratch, used, scratch_floats > used ? scratch_floats - used : 0);
+    DRIN_TRY(launch_gemm_nn({{dy, n_out}, {w, k}, dx, k, rows, k, n_out}, precision, st, {}, {nullptr, {scratch, scratch_floats}, tail}));
   }
   // (stream order makes the scratch reusable product after product; every split reduction goes through it and is added in
   //  order - without scratch one workgroup per output tile / per 256 columns walks the whole reduction: no atomics either way)
-  if (dw) DRIN_TRY(launch_gemm_tn(dy, n_out, x, k, dw, k, rows, n_out, k, precision, st, scratch, scratch ? scratch_floats : 0));
+  if (dw) DRIN_TRY(launch_gemm_tn({{dy, n_out}, {x, k}, dw, k, rows, n_out, k}, precision, st, scratch_at(scratch, 0, scratch_floats)));
   if (db) DRIN_TRY(launch_colsum(dy, db, rows, n_out, st, scratch, scratch ? scratch_floats : 0));
   return DRIN_OK;
 }
@@ -871,28 +870,23 @@ int drin_gemm_probe(drin_gemm_probe_args* p, void* stream) {
   rt.begin = p->row_tile_begin, rt.end = p->row_tile_end, rt.wgs = p->row_tile_wgs;
   float* y = static_cast<float*>(p->y);
   const float* a = static_cast<const float*>(p->a);
-  const bool acc = p->accumulate != 0;
+  // the NT ops' product; DRIN_PROBE_GEMM_NT reads only b_hi, as the one-pointer "hi then lo" planes of a workspace
+  NtProduct nt{{a, p->lda}, {static_cast<const float*>(p->b), p->ldb}, p->bias, y, p->ldy, p->rows, p->n_out, p->k, p->b_hi, p->b_lo};
+  nt.accumulate = p->accumulate != 0;
+  const GemmScratch scratch{p->scratch, p->scratch_floats};
   int rc = DRIN_E_UNSUPPORTED;
   switch (p->op) {
-    case DRIN_PROBE_GEMM_NT:
-      rc = launch_gemm_nt(a, p->lda, static_cast<const float*>(p->b), p->ldb, p->bias, y, p->ldy, p->rows, p->n_out, p->k, acc, p->precision,
-                          st, p->scratch, p->scratch_floats, static_cast<const float*>(p->b_hi));
-      break;
+    case DRIN_PROBE_GEMM_NT: rc = launch_gemm_nt(nt.with_planes(static_cast<const float*>(p->b_hi)), p->precision, st, scratch); break;
     case DRIN_PROBE_GEMM_NT_BF16X3:
-      rc = launch_gemm_nt_bf16x3(a, p->lda, static_cast<const float*>(p->b), p->ldb, p->bias, y, p->ldy, p->rows, p->n_out, p->k, st, p->b_hi,
-                                 p->b_lo, acc, p->scratch, p->scratch_floats, p->a_index);
+      nt.x_index = p->a_index;
+      rc = launch_gemm_nt_bf16x3(nt, st, scratch);
       break;
-    case DRIN_PROBE_GEMM_NT_BF16X3_P4:
-      rc = launch_gemm_nt_bf16x3_p4(a, p->lda, p->b_hi, p->b_lo, p->ldb, p->bias, y, p->ldy, p->rows, p->n_out, p->k, st, acc, p->scratch,
-                                    p->scratch_floats, rt);
-      break;
+    case DRIN_PROBE_GEMM_NT_BF16X3_P4: rc = launch_gemm_nt_bf16x3_p4(nt, st, scratch, rt); break;
     case DRIN_PROBE_GEMM_X3_PLANES:
-      rc = launch_gemm_x3_planes(p->a, p->a_lo, p->lda, p->b_hi, p->b_lo, p->ldb, p->bias, y, p->ldy, p->rows, p->n_out, p->k, st, p->scratch,
-                                 p->scratch_floats, rt);
+      rc = launch_gemm_x3_planes(p->a, p->a_lo, p->lda, p->b_hi, p->b_lo, p->ldb, p->bias, y, p->ldy, p->rows, p->n_out, p->k, st, scratch, rt);
       break;
     case DRIN_PROBE_GEMM_F16_PLANES:
-      rc = launch_gemm_f16_planes(p->a, p->lda, p->b_hi, p->ldb, p->row_scale, p->b_scale, y, p->ldy, p->rows, p->n_out, p->k, st, p->scratch,
-                                  p->scratch_floats);
+      rc = launch_gemm_f16_planes(p->a, p->lda, p->b_hi, p->ldb, p->row_scale, p->b_scale, y, p->ldy, p->rows, p->n_out, p->k, st, scratch);
       break;
     case DRIN_PROBE_TO_F16_SCALED: rc = launch_to_f16_scaled(a, p->y, p->rows, p->scratch, st); break;
     default: break;
@@ -905,21 +899,21 @@ int drin_gemm_probe(drin_gemm_probe_args* p, void* stream) {
 static int wgrad_probe_run(const drin_wgrad_probe_args* p, hipStream_t st) {
   const drin_wgrad_product* q = p->product;
   const int n = p->n_products;
+  TnProduct tn[DRIN_WGRAD_PROBE_MAX];
+  for (int i = 0; i < n; ++i) tn[i] = {{q[i].dy, q[i].lddy}, {q[i].x, q[i].ldx}, q[i].dw, q[i].lddw, q[i].rows, q[i].n_out, q[i].k, q[i].x_index, q[i].db};
+  const GemmScratch scratch{p->scratch, p->scratch_floats};
   switch (p->op) {
     case DRIN_WGRAD_TN_GROUP: {
       TnGroup g;
-      for (int i = 0; i < n; ++i)
-        DRIN_TRY(g.add(q[i].dy, q[i].lddy, q[i].x, q[i].ldx, q[i].dw, q[i].lddw, q[i].rows, q[i].n_out, q[i].k, q[i].x_index, q[i].db));
-      return launch_gemm_tn_group(g, st, p->scratch, p->scratch_floats);
+      for (int i = 0; i < n; ++i) DRIN_TRY(g.add(tn[i]));
+      return launch_gemm_tn_group(g, st, scratch);
     }
     case DRIN_WGRAD_TN_F32_GROUP: {
       F32GemmGroup g;
-      for (int i = 0; i < n; ++i) DRIN_TRY(g.add_tn(q[i].dy, q[i].lddy, q[i].x, q[i].ldx, q[i].dw, q[i].lddw, q[i].rows, q[i].n_out, q[i].k));
-      return launch_gemm_tn_f32_group(g, st, p->scratch, p->scratch_floats);
+      for (int i = 0; i < n; ++i) DRIN_TRY(g.add_tn(tn[i]));
+      return launch_gemm_tn_f32_group(g, st, scratch);
     }
-    case DRIN_WGRAD_TN:
-      return launch_gemm_tn(q->dy, q->lddy, q->x, q->ldx, q->dw, q->lddw, q->rows, q->n_out, q->k, p->precision, st, p->scratch,
-                            p->scratch_floats);
+    case DRIN_WGRAD_TN: return launch_gemm_tn(tn[0], p->precision, st, scratch);
     case DRIN_WGRAD_COLSUM_BATCH: {
       ColsumBatch b;
       for (int i = 0; i < n; ++i) DRIN_TRY(b.add(q[i].dy, q[i].db, q[i].rows, q[i].n_out, q[i].lddy));
@@ -944,7 +938,7 @@ static int wgrad_probe_run(const drin_wgrad_probe_args* p, hipStream_t st) {
       WeightGradPass pass{p->precision, false, st, {Arena::at(p->scratch, tn_at), tn_floats}, {Arena::at(p->scratch, small_at), small_floats},
                           {Arena::at(p->scratch, cs_at), cs_floats}};
       for (int i = 0; i < n; ++i) {
-        DRIN_TRY(pass.add(q[i].dy, q[i].lddy, q[i].x, q[i].ldx, q[i].dw, q[i].lddw, q[i].rows, q[i].n_out, q[i].k, q[i].x_index, q[i].db));
+        DRIN_TRY(pass.add(tn[i]));
         if (i == p->layers_done_after) pass.layers_done();
       }
       if (!p->staged) return pass.finish(nullptr);
@@ -961,7 +955,7 @@ static int wgrad_probe_run(const drin_wgrad_probe_args* p, hipStream_t st) {
         set_error("drin_wgrad_probe: %zu floats for W^T, %zu needed", p->wt_floats, (size_t)q->n_out * q->k);
         return DRIN_E_WORKSPACE;
       }
-      if (p->wt_form == DRIN_WGRAD_WT_F32_SCRATCH) wt.scratch = p->wt, wt.scratch_floats = p->wt_floats;
+      if (p->wt_form == DRIN_WGRAD_WT_F32_SCRATCH) wt.scratch = {p->wt, p->wt_floats};
       if (p->wt_form == DRIN_WGRAD_WT_PLANES) {
         if (q->ldx != q->k) {
           set_error("drin_wgrad_probe: the planes of W^T are written from a contiguous W (ldx == k)");
@@ -972,8 +966,7 @@ static int wgrad_probe_run(const drin_wgrad_probe_args* p, hipStream_t st) {
         DRIN_TRY(launch_transpose_split_batch(tb, q->n_out, q->k, st));
         wt.planes = p->wt;
       }
-      return launch_gemm_nn(q->dy, q->lddy, q->x, q->ldx, q->dw, q->lddw, q->rows, q->k, q->n_out, p->accumulate != 0, p->precision, st,
-                            p->scratch, p->scratch_floats, wt);
+      return launch_gemm_nn({{q->dy, q->lddy}, {q->x, q->ldx}, q->dw, q->lddw, q->rows, q->k, q->n_out, p->accumulate != 0}, p->precision, st, scratch, wt);
     }
     default: return DRIN_E_UNSUPPORTED;
   }
@@ -1072,16 +1065,13 @@ int drin_forward_staged_head(const drin_config* cfg, const drin_batch* batch, co
   // VertexEncoder (model.py:26-46): four Linears
   float* vm0 = ws + L.vm[0];
   float* ve0 = ws + L.ve[0];
-  float* const sk = L.splitk_floats ? ws + L.splitk : nullptr;  // split-K scratch of the mention-sized products
-  const size_t skf = L.splitk_floats;
+  const GemmScratch sk = scratch_at(ws, L.splitk, L.splitk_floats);  // split-K scratch of the mention-sized products
   // tail-split scratch of the pair-sized split-bf16 products (training layouts only: the weight-gradient partial
   // buffer is idle during the forward pass and between the weight-gradient products of the backward pass)
-  float* const tl = L.tn_part_floats ? ws + L.tn_part : nullptr;
-  const size_t tlf = L.tn_part_floats;
+  const GemmScratch tl = scratch_at(ws, L.tn_part, L.tn_part_floats);
   // mention-sized products beyond the exact-fp32 split-K range (2 B > 512 rows) run split-bf16 on small tiles and split K
   // into the same scratch
-  float* const msk = sk ? sk : tl;
-  const size_t mskf = sk ? skf : tlf;
+  const GemmScratch msk = sk.p ? sk : tl;
   // split-bf16 precision: every weight an NT product runs against is split into bf16 (hi, lo) planes ONCE per call (one
   // batched launch) and then streamed by LDS-DMA, instead of being split by every workgroup in every K-block (the register
   // stager of the 64 x 128 tile spent as many VALU cycles on it as the tile has MFMA cycles)
@@ -1101,26 +1091,23 @@ int drin_forward_staged_head(const drin_config* cfg, const drin_batch* batch, co
     }
     DRIN_TRY(launch_split_planes_batch(sb, st));
   }
-  auto nt_pair = [&](const NtProduct& a, const NtProduct& b) -> int { return launch_gemm_nt_pair(a, b, prec, st, msk, mskf); };
+  const NtProduct enc_mi = NtProduct{{P.mention_image, R}, {params->w_mention_image, R}, params->b_mention_image, vm0 + (size_t)B * D, D, B, D, R}
+                               .with_planes(wp(L.wp_enc[1]));
   if (rows)   // the mention-text vertex is in vm0 already (run_pooling): the mention-image product alone
-    DRIN_TRY(launch_gemm_nt(P.mention_image, R, params->w_mention_image, R, params->b_mention_image, vm0 + (size_t)B * D, D, B, D, R,
-                            false, prec, st, msk, mskf, wp(L.wp_enc[1])));
+    DRIN_TRY(launch_gemm_nt(enc_mi, prec, st, msk));
   else
-    DRIN_TRY(nt_pair({P.span_mean, params->w_mention_text, params->b_mention_text, vm0, D, D, D, B, D, D, wp(L.wp_enc[0])},
-                     {P.mention_image, params->w_mention_image, params->b_mention_image, vm0 + (size_t)B * D, R, R, D, B, D, R,
-                      wp(L.wp_enc[1])}));
+    DRIN_TRY(launch_gemm_nt_pair(NtProduct{{P.span_mean, D}, {params->w_mention_text, D}, params->b_mention_text, vm0, D, B, D, D}.with_planes(wp(L.wp_enc[0])),
+                                 enc_mi, prec, st, msk));
+  NtProduct enc_et = NtProduct{{P.entity_text, D}, {params->w_entity_text, D}, params->b_entity_text, ve0, D, M, D, D}.with_planes(wp(L.wp_enc[2]));
+  NtProduct enc_ei = NtProduct{{P.entity_image, R}, {params->w_entity_image, R}, params->b_entity_image, ve0 + (size_t)M * D, D, M, D, R}
+                         .with_planes(wp(L.wp_enc[3]));
   if (eidx) {  // rows of the entity tables, addressed through the candidate index by the GEMM's stager
-    const __bf16* pt = reinterpret_cast<const __bf16*>(wp(L.wp_enc[2]));
-    const __bf16* pi = reinterpret_cast<const __bf16*>(wp(L.wp_enc[3]));
-    DRIN_TRY(launch_gemm_nt_bf16x3(P.entity_text, D, params->w_entity_text, D, params->b_entity_text, ve0, D, M, D, D, st,
-                                   pt, pt ? pt + (size_t)D * D : nullptr, false, tl, tlf, eidx));
-    DRIN_TRY(launch_gemm_nt_bf16x3(P.entity_image, R, params->w_entity_image, R, params->b_entity_image, ve0 + (size_t)M * D,
-                                   D, M, D, R, st, pi, pi ? pi + (size_t)D * R : nullptr, false, tl, tlf, eidx));
+    enc_et.x_index = enc_ei.x_index = eidx;
+    DRIN_TRY(launch_gemm_nt_bf16x3(enc_et, st, tl));
+    DRIN_TRY(launch_gemm_nt_bf16x3(enc_ei, st, tl));
   } else {
-    DRIN_TRY(launch_gemm_nt(P.entity_text, D, params->w_entity_text, D, params->b_entity_text, ve0, D, M, D, D, false,
-                            prec, st, tl, tlf, wp(L.wp_enc[2])));
-    DRIN_TRY(launch_gemm_nt(P.entity_image, R, params->w_entity_image, R, params->b_entity_image, ve0 + (size_t)M * D, D,
-                            M, D, R, false, prec, st, tl, tlf, wp(L.wp_enc[3])));
+    DRIN_TRY(launch_gemm_nt(enc_et, prec, st, tl));
+    DRIN_TRY(launch_gemm_nt(enc_ei, prec, st, tl));
   }
   DRIN_TRY(tap(trace, 0, L, ws, B, M, D, st, EW));
 
@@ -1173,13 +1160,14 @@ int drin_forward_staged_head(const drin_config* cfg, const drin_batch* batch, co
     float* h_m = ws + L.h_m[l];
     float* h_e = ws + L.h_e[l];
     const bool scalar_update = live_edges && !vec;   // then W_u(mt, mi) is due too and shares the launch of W_h(agg_m)
+    const NtProduct wh_m = NtProduct{{agg_m, D}, {W.w_h, D}, W.b_h, h_m, D, (int64_t)types * B, D, D}.with_planes(wp(L.wp_h[l]));
     if (scalar_update) {
-      DRIN_TRY(nt_pair({agg_m, W.w_h, W.b_h, h_m, D, D, D, (int64_t)types * B, D, D, wp(L.wp_h[l])},
-                       {mt, W.w_u, W.b_u, ws + L.fu[l], D, D, D, 2 * (int64_t)B, D, D, wp(L.wp_u[l])}));
+      DRIN_TRY(launch_gemm_nt_pair(wh_m, NtProduct{{mt, D}, {W.w_u, D}, W.b_u, ws + L.fu[l], D, 2 * (int64_t)B, D, D}.with_planes(wp(L.wp_u[l])),
+                                   prec, st, msk));
     } else {
-      DRIN_TRY(launch_gemm_nt(agg_m, D, W.w_h, D, W.b_h, h_m, D, (int64_t)types * B, D, D, false, prec, st, msk, mskf, wp(L.wp_h[l])));
+      DRIN_TRY(launch_gemm_nt(wh_m, prec, st, msk));
     }
-    DRIN_TRY(launch_gemm_nt(agg_e, D, W.w_h, D, W.b_h, h_e, D, (int64_t)types * M, D, D, false, prec, st, tl, tlf, wp(L.wp_h[l])));
+    DRIN_TRY(launch_gemm_nt(NtProduct{{agg_e, D}, {W.w_h, D}, W.b_h, h_e, D, (int64_t)types * M, D, D}.with_planes(wp(L.wp_h[l])), prec, st, tl));
     float* st_m = L.training ? ws + L.ln_stat_m[l] : nullptr;
     float* st_e = L.training ? ws + L.ln_stat_e[l] : nullptr;
     // one LayerNorm + GELU launch for the mention and the entity vertices (they share it, model.py:128)
@@ -1194,15 +1182,15 @@ int drin_forward_staged_head(const drin_config* cfg, const drin_batch* batch, co
       float* fv = ws + L.fv[l];
       float* pre = ws + L.pre[l];
       const int H = D / 2;
-      DRIN_TRY(launch_gemm_nt(mt, D, W.w_u, D, W.b_u, fu, H, 2 * (int64_t)B, H, D, false, prec, st, msk, mskf));
-      DRIN_TRY(launch_gemm_nt(et, D, W.w_v, D, W.b_v, fv, H, 2 * M, H, D, false, prec, st));
+      DRIN_TRY(launch_gemm_nt({{mt, D}, {W.w_u, D}, W.b_u, fu, H, 2 * (int64_t)B, H, D}, prec, st, msk));
+      DRIN_TRY(launch_gemm_nt({{et, D}, {W.w_v, D}, W.b_v, fv, H, 2 * M, H, D}, prec, st));
       DRIN_TRY(launch_edge_pre_vec(fu, fv, e, pre, B, N, D, st));
-      DRIN_TRY(launch_gemm_nt(pre, D, W.w_m, D, W.b_m, e_next, D, 4 * M, D, D, false, prec, st));
+      DRIN_TRY(launch_gemm_nt({{pre, D}, {W.w_m, D}, W.b_m, e_next, D, 4 * M, D, D}, prec, st));
       DRIN_TRY(launch_sigmoid_inplace(e_next, 4 * M * D, st, act_e, keep_z ? ws + L.edge_z[l] : nullptr));
     } else if (live_edges) {
       float* fu = ws + L.fu[l];
       float* fv = ws + L.fv[l];
-      DRIN_TRY(launch_gemm_nt(et, D, W.w_v, D, W.b_v, fv, D, 2 * M, D, D, false, prec, st, tl, tlf, wp(L.wp_v[l])));   // fu: with W_h above
+      DRIN_TRY(launch_gemm_nt(NtProduct{{et, D}, {W.w_v, D}, W.b_v, fv, D, 2 * M, D, D}.with_planes(wp(L.wp_v[l])), prec, st, tl));   // fu: with W_h above
       DRIN_TRY(launch_edge_update4(fu, fv, e, e_next, B, N, D, st, act_e, keep_z ? ws + L.edge_z[l] : nullptr));
     } else if (!cfg->dynamic_edges) {
       hipError_t err = hipMemcpyAsync(e_next, e, 4 * ES * sizeof(float), hipMemcpyDeviceToDevice, st);
@@ -1391,8 +1379,7 @@ int drin_backward_head(const drin_config* cfg, const drin_batch* batch, const dr
 
   bool all_enabled = true;
   for (int k = 0; k < 4; ++k) all_enabled = all_enabled && cfg->edge_enabled[k] == 1.0f;
-  float* const tnp = L.tn_part_floats ? ws + L.tn_part : nullptr;  // partial tiles of the split-bf16 dW products
-  const size_t tnf = L.tn_part_floats;
+  const GemmScratch tn = scratch_at(ws, L.tn_part, L.tn_part_floats);  // partial tiles of the split-bf16 dW products
   // gelu / silu edges: the derivative is taken at the pre-activation the forward kept (Layout::edge_z)
   const bool from_z = act_e == DRIN_ACT_GELU || act_e == DRIN_ACT_SILU;
   const int act_eb = from_z ? (act_e | 0x100) : act_e;   // device_utils.h: kActFromPre
@@ -1411,15 +1398,11 @@ int drin_backward_head(const drin_config* cfg, const drin_batch* batch, const dr
     }
     DRIN_TRY(launch_transpose_split_batch(tb, D, D, st));
   }
-  auto gemm_nn = [&](const float* dy, int64_t lddy, const float* w, float* dx, int64_t lddx, int64_t rows, int n_out,
-                     int k_red, bool accumulate, const float* w_t = nullptr) -> int {
-    // w is [k_red][n_out] contiguous; w_t: bf16 (hi, lo) planes of its transpose, already in the workspace
-    return launch_gemm_nn(dy, lddy, w, n_out, dx, lddx, rows, n_out, k_red, accumulate, prec, st,
-                          L.splitk_floats ? ws + L.splitk : nullptr, L.splitk_floats,
-                          {w_t, wt_slot(nl, 0), (size_t)D * D, tnp, tnf});
-  };
+  const GemmScratch nn_sk = scratch_at(ws, L.splitk, L.splitk_floats);
+  // w_t: bf16 (hi, lo) planes of w^T, already in the workspace
+  auto wt = [&](const float* w_t = nullptr) { return WtForms{w_t, {wt_slot(nl, 0), (size_t)D * D}, tn}; };
   // dW (+)= dY^T X with its bias gradient: kernel choice, grouped launches and the order of landing are the GEMM module's
-  WeightGradPass dw{prec, vec, st, {tnp, tnf}, {ws + L.small_part, L.small_part_floats}, {csp, L.colsum_part_floats}};
+  WeightGradPass dw{prec, vec, st, tn, {ws + L.small_part, L.small_part_floats}, {csp, L.colsum_part_floats}};
 
   // score = cos(mt_L, et_L) (model.py:207-209)
   DRIN_TRY(launch_cosine_bwd(ws + L.vm[nl], ws + L.ve[nl], grad_scores, g_vm(nl), g_ve(nl), sc + S.cos_scratch, B, N, D,
@@ -1449,12 +1432,12 @@ int drin_backward_head(const drin_config* cfg, const drin_batch* batch, const dr
                                         ws + L.ln_part + ln_bwd_level1((size_t)D, l)));
     // (b) dW_h += dH^T A
     if (G.w_h) {
-      DRIN_TRY(dw.add(gm, D, ws + L.agg_m[l], D, G.w_h, D, (int64_t)types * B, D, D));
-      DRIN_TRY(dw.add(ge, D, ws + L.agg_e[l], D, G.w_h, D, (int64_t)types * M, D, D));
+      DRIN_TRY(dw.add({{gm, D}, {ws + L.agg_m[l], D}, G.w_h, D, (int64_t)types * B, D, D}));
+      DRIN_TRY(dw.add({{ge, D}, {ws + L.agg_e[l], D}, G.w_h, D, (int64_t)(types * M), D, D}));
     }
     // (c) dA = dH W_h
-    DRIN_TRY(gemm_nn(gm, D, W.w_h, dA_m, D, (int64_t)types * B, D, D, false));
-    DRIN_TRY(gemm_nn(ge, D, W.w_h, dA_e, D, (int64_t)types * M, D, D, false, pre_t ? wt_slot(l, 0) : nullptr));
+    DRIN_TRY(launch_gemm_nn({{gm, D}, {W.w_h, D}, dA_m, D, (int64_t)types * B, D, D}, prec, st, nn_sk, wt()));
+    DRIN_TRY(launch_gemm_nn({{ge, D}, {W.w_h, D}, dA_e, D, (int64_t)(types * M), D, D}, prec, st, nn_sk, wt(pre_t ? wt_slot(l, 0) : nullptr)));
     const float* dA_mt = dA_m;
     const float* dA_mi = types == 2 ? dA_m + BD : nullptr;
     const float* dA_et = dA_e;
@@ -1471,13 +1454,13 @@ int drin_backward_head(const drin_config* cfg, const drin_batch* batch, const dr
       // (d, vector edges) e' = sigmoid(W_m(cat(W_u(u), W_v(v)) + e) + b_m)  (model.py:150-152,133)
       const int H = D / 2;
       DRIN_TRY(launch_sigmoid_bwd(g_e[cur], from_z ? ws + L.edge_z[l] : ws + L.edges[l + 1], dpre, 4 * (int64_t)ES, st, act_eb));  // dz
-      if (G.w_m) DRIN_TRY(launch_gemm_tn(dpre, D, ws + L.pre[l], D, G.w_m, D, 4 * (int64_t)M, D, D, prec, st, tnp, tnf));
+      if (G.w_m) DRIN_TRY(launch_gemm_tn({{dpre, D}, {ws + L.pre[l], D}, G.w_m, D, 4 * (int64_t)M, D, D}, prec, st, tn));
       DRIN_TRY(launch_colsum(dpre, G.b_m, 4 * (int64_t)M, D, st, csp, L.colsum_part_floats));
-      DRIN_TRY(gemm_nn(dpre, D, W.w_m, g_e[cur], D, 4 * (int64_t)M, D, D, false));  // d(cat + e)
+      DRIN_TRY(launch_gemm_nn({{dpre, D}, {W.w_m, D}, g_e[cur], D, 4 * (int64_t)M, D, D}, prec, st, nn_sk, wt()));  // d(cat + e)
       DRIN_TRY(launch_edge_pre_vec_bwd(g_e[cur], dfu, dfv, B, N, D, st));
-      if (G.w_v) DRIN_TRY(launch_gemm_tn(dfv, H, et, D, G.w_v, D, 2 * (int64_t)M, H, D, prec, st, tnp, tnf));
+      if (G.w_v) DRIN_TRY(launch_gemm_tn({{dfv, H}, {et, D}, G.w_v, D, 2 * (int64_t)M, H, D}, prec, st, tn));
       DRIN_TRY(launch_colsum(dfv, G.b_v, 2 * (int64_t)M, H, st, csp, L.colsum_part_floats));
-      if (G.w_u) DRIN_TRY(launch_gemm_tn(dfu, H, mt, D, G.w_u, D, 2 * (int64_t)B, H, D, prec, st, tnp, tnf));
+      if (G.w_u) DRIN_TRY(launch_gemm_tn({{dfu, H}, {mt, D}, G.w_u, D, 2 * (int64_t)B, H, D}, prec, st, tn));
       DRIN_TRY(launch_colsum(dfu, G.b_u, 2 * (int64_t)B, H, st, csp, L.colsum_part_floats));
       de_extra = g_e[cur];
     } else if (edge_update) {
@@ -1493,9 +1476,9 @@ int drin_backward_head(const drin_config* cfg, const drin_batch* batch, const dr
       if (B > 65535) {
         DRIN_TRY(launch_mention_reduce(dpre, fv, dpre + M, fv + MD, nullptr, dfu, B, N, D, inv_d, st));
         DRIN_TRY(launch_mention_reduce(dpre + 2 * M, fv, dpre + 3 * M, fv + MD, nullptr, dfu + BD, B, N, D, inv_d, st));
-        DRIN_TRY(dw.add(dfu, D, mt, D, G.w_u, D, 2 * (int64_t)B, D, D, nullptr, G.b_u));
+        DRIN_TRY(dw.add({{dfu, D}, {mt, D}, G.w_u, D, 2 * (int64_t)B, D, D, nullptr, G.b_u}));
       }
-      DRIN_TRY(dw.add(dfv, D, et, D, G.w_v, D, 2 * (int64_t)M, D, D, nullptr, G.b_v));
+      DRIN_TRY(dw.add({{dfv, D}, {et, D}, G.w_v, D, 2 * (int64_t)M, D, D, nullptr, G.b_v}));
       de_extra = dpre;
     } else if (!cfg->dynamic_edges && have_edge) {
       de_extra = g_e[cur];  // static edges pass through (model.py:136)
@@ -1505,15 +1488,16 @@ int drin_backward_head(const drin_config* cfg, const drin_batch* batch, const dr
       // (e) entity side of the aggregation backward + edge gradients, element-wise with vector edges
       DRIN_TRY(launch_entity_side_bwd_vec(dA_mt, dA_mi, dA_et, dA_ei, mt, mi, et, ei, e, de_extra, ge_next,
                                           ge_next + MD, g_e[nxt], B, N, D, cfg->edge_enabled, st));
-      if (edge_update) DRIN_TRY(gemm_nn(dfv, H, W.w_v, ge_next, D, 2 * (int64_t)M, D, H, true));
+      if (edge_update) DRIN_TRY(launch_gemm_nn({{dfv, H}, {W.w_v, D}, ge_next, D, 2 * (int64_t)M, D, H, true}, prec, st, nn_sk, wt()));
       // (f) mention side
       DRIN_TRY(launch_mention_reduce_vec(e, dA_et, e + ES, dA_ei, dA_mt, gm_next, B, N, D, 1.0f, false, st));
       DRIN_TRY(launch_mention_reduce_vec(e + 2 * ES, dA_et, e + 3 * ES, dA_ei, dA_mi, gm_next + BD, B, N, D, 1.0f, false, st));
-      if (edge_update) DRIN_TRY(gemm_nn(dfu, H, W.w_u, gm_next, D, 2 * (int64_t)B, D, H, true));
+      if (edge_update) DRIN_TRY(launch_gemm_nn({{dfu, H}, {W.w_u, D}, gm_next, D, 2 * (int64_t)B, D, H, true}, prec, st, nn_sk, wt()));
     } else {
       // (e) entity side of the aggregation backward + edge gradients
       // (the edge update's dfv W_v goes first and the row kernel adds onto it)
-      if (edge_update) DRIN_TRY(gemm_nn(dfv, D, W.w_v, ge_next, D, 2 * (int64_t)M, D, D, false, pre_t ? wt_slot(l, 1) : nullptr));
+      if (edge_update)
+        DRIN_TRY(launch_gemm_nn({{dfv, D}, {W.w_v, D}, ge_next, D, 2 * (int64_t)M, D, D}, prec, st, nn_sk, wt(pre_t ? wt_slot(l, 1) : nullptr)));
       DRIN_TRY(launch_entity_side_bwd(dA_mt, dA_mi, dA_et, dA_ei, mt, mi, et, ei, e, de_extra, ge_next, ge_next + MD,
                                       g_e[nxt], B, N, D, cfg->edge_enabled, edge_update, st));
       // (f) mention side
@@ -1521,14 +1505,14 @@ int drin_backward_head(const drin_config* cfg, const drin_batch* batch, const dr
         const float* fv = ws + L.fv[l];
         DRIN_TRY(launch_mention_reduce2_pair(dpre, fv, fv + MD, nullptr, nullptr, dfu, dfu + BD, 1.0f / (float)D,          // (d): dfu
                                              e, dA_et, dA_ei, dA_mt, dA_mi, gm_next, gm_next + BD, 1.0f, B, N, D, st));   // (f)
-        DRIN_TRY(dw.add(dfu, D, mt, D, G.w_u, D, 2 * (int64_t)B, D, D, nullptr, G.b_u));
+        DRIN_TRY(dw.add({{dfu, D}, {mt, D}, G.w_u, D, 2 * (int64_t)B, D, D, nullptr, G.b_u}));
       } else if (B <= 65535) {
         DRIN_TRY(launch_mention_reduce2(e, dA_et, dA_ei, dA_mt, dA_mi, gm_next, gm_next + BD, B, N, D, 1.0f, st));
       } else {
         DRIN_TRY(launch_mention_reduce(e, dA_et, e + M, dA_ei, dA_mt, gm_next, B, N, D, 1.0f, st));
         DRIN_TRY(launch_mention_reduce(e + 2 * M, dA_et, e + 3 * M, dA_ei, dA_mi, gm_next + BD, B, N, D, 1.0f, st));
       }
-      if (edge_update) DRIN_TRY(gemm_nn(dfu, D, W.w_u, gm_next, D, 2 * (int64_t)B, D, D, true));
+      if (edge_update) DRIN_TRY(launch_gemm_nn({{dfu, D}, {W.w_u, D}, gm_next, D, 2 * (int64_t)B, D, D, true}, prec, st, nn_sk, wt()));
     }
     have_image = true;
     have_edge = true;
@@ -1543,11 +1527,11 @@ int drin_backward_head(const drin_config* cfg, const drin_batch* batch, const dr
   const float* g_mi = g_vm(0) + BD;
   const float* g_et = g_ve(0);
   const float* g_ei = g_ve(0) + MD;
-  if (!rows) DRIN_TRY(dw.add(g_mt, D, P.span_mean, D, grads->w_mention_text, D, B, D, D, nullptr, grads->b_mention_text));
-  DRIN_TRY(dw.add(g_et, D, P.entity_text, D, grads->w_entity_text, D, (int64_t)M, D, D, eidx, grads->b_entity_text));
+  if (!rows) DRIN_TRY(dw.add({{g_mt, D}, {P.span_mean, D}, grads->w_mention_text, D, B, D, D, nullptr, grads->b_mention_text}));
+  DRIN_TRY(dw.add({{g_et, D}, {P.entity_text, D}, grads->w_entity_text, D, (int64_t)M, D, D, eidx, grads->b_entity_text}));
   if (have_image) {
-    DRIN_TRY(dw.add(g_mi, D, P.mention_image, R, grads->w_mention_image, R, B, D, R, nullptr, grads->b_mention_image));
-    DRIN_TRY(dw.add(g_ei, D, P.entity_image, R, grads->w_entity_image, R, (int64_t)M, D, R, eidx, grads->b_entity_image));
+    DRIN_TRY(dw.add({{g_mi, D}, {P.mention_image, R}, grads->w_mention_image, R, B, D, R, nullptr, grads->b_mention_image}));
+    DRIN_TRY(dw.add({{g_ei, D}, {P.entity_image, R}, grads->w_entity_image, R, (int64_t)M, D, R, eidx, grads->b_entity_image}));
   }
   DRIN_TRY(dw.finish(layers_ready_event));   // everything collected lands; staged: the layers' part, the event, the encoders' part
   if (input_grads == nullptr) {
@@ -1592,18 +1576,17 @@ int drin_host_selftest(void) {
   {
     F32GemmGroup g;
     g.n = 2;
-    g.item[0] = {dummy, 4, dummy, 4, dummy, 4, 4, 4, 4};
-    g.item[1] = F32GemmGroup::Item();   // M = N = K = 0, NULL operands
-    const int rc = launch_gemm_tn_f32_group(g, nullptr, nullptr, 0, nullptr);
+    g.item[0] = {{dummy, 4}, {dummy, 4}, dummy, 4, 4, 4, 4};
+    g.item[1] = TnProduct();   // M = N = K = 0, NULL operands
+    const int rc = launch_gemm_tn_f32_group(g, nullptr, {}, nullptr);
     if (rc != DRIN_E_SHAPE) {
       set_error("selftest: launch_gemm_tn_f32_group accepted an item with an empty reduction (status %d)", rc);
       return rc == DRIN_OK ? DRIN_E_SHAPE : rc;
     }
     F32GemmGroup h;
     h.n = 1;
-    h.item[0] = F32GemmGroup::Item();
-    h.bias_of[0] = nullptr;
-    const int rn = launch_gemm_nt_f32_group(h, nullptr, dummy, 16);
+    h.nt[0] = NtProduct();
+    const int rn = launch_gemm_nt_f32_group(h, nullptr, {dummy, 16});
     if (rn != DRIN_E_SHAPE) {
       set_error("selftest: launch_gemm_nt_f32_group accepted an empty item (status %d)", rn);
       return rn == DRIN_OK ? DRIN_E_SHAPE : rn;
@@ -1611,9 +1594,11 @@ int drin_host_selftest(void) {
   }
   // (3) an empty reduction through the single-product entry: nothing to add, nothing launched, nothing divided
   {
-    const int rc = launch_gemm_tn(dummy, 4, dummy, 4, dummy, 4, /*M=*/0, 4, 4, DRIN_PREC_F32, nullptr, dummy, 16);
+    TnProduct empty{{dummy, 4}, {dummy, 4}, dummy, 4, /*rows=*/0, 4, 4};
+    const int rc = launch_gemm_tn(empty, DRIN_PREC_F32, nullptr, {dummy, 16});
     if (rc != DRIN_OK) return rc;
-    if (launch_gemm_tn(dummy, 4, dummy, 4, dummy, 4, /*M=*/-1, 4, 4, DRIN_PREC_F32, nullptr, dummy, 16) != DRIN_E_SHAPE) {
+    empty.rows = -1;
+    if (launch_gemm_tn(empty, DRIN_PREC_F32, nullptr, {dummy, 16}) != DRIN_E_SHAPE) {
       set_error("selftest: launch_gemm_tn accepted a negative reduction length");
       return DRIN_E_SHAPE;
     }

@@ -269,7 +269,7 @@ __global__ void __launch_bounds__(256) k_layernorm_gelu_bwd(const LnBwdSeg sa, c
 // Block = 4 waves x 64 columns; wave w takes rows w, w + 4, ... of its slice (at most 16, all in flight at once);
 // the waves are combined through LDS in order.
 // (q_major: level-1 rows laid out [q][z][D] instead of [z][q][D] - one contiguous [z][D] slice array per quantity, the form
-//  the ordered slice sum at the end of the backward pass takes: level 2 then rides in that launch, internal.h SliceSum)
+//  the ordered slice sum at the end of the backward pass takes: level 2 then rides in that launch, gemm.h SliceSum)
 __global__ void __launch_bounds__(256) k_sum_partials(const float* __restrict__ partial, int blocks, int D,
                                                       float* __restrict__ out_partial, float* __restrict__ dgamma,
                                                       float* __restrict__ dbeta, float* __restrict__ dbias, int q_major) {

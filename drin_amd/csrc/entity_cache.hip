@@ -762,11 +762,11 @@ DRIN_API int drin_build_entity_cache(const drin_config* cfg, const drin_batch* t
     float* const y_fvt = mixed ? tmp : crow + 2 * D;
     float* const y_fvi = mixed ? tmp + D : crow + 3 * D;
     const int64_t ldy = mixed ? 2 * (int64_t)D : ldc;
-    DRIN_TRY(launch_gemm_nt(xt, D, pb + P.c_txt, D, nullptr, crow, ldc, rows, D, D, false, prec, st));
-    DRIN_TRY(launch_gemm_nt(ximg, R, pb + P.c_img, R, nullptr, y_hi, ldc, rows, D, R, false, prec, st));
+    DRIN_TRY(launch_gemm_nt({{xt, D}, {pb + P.c_txt, D}, nullptr, crow, ldc, rows, D, D}, prec, st));
+    DRIN_TRY(launch_gemm_nt({{ximg, R}, {pb + P.c_img, R}, nullptr, y_hi, ldc, rows, D, R}, prec, st));
     if (dyn) {  // fv = x (W_v1 W_e)^T + (W_v1 b_e + b_v1); etmp keeps W_v1 [W_et | W_ei] un-transposed, row stride D + R
-      DRIN_TRY(launch_gemm_nt(xt, D, pb + P.etmp, D + R, pb + P.k_t, y_fvt, ldy, rows, D, D, false, prec, st));
-      DRIN_TRY(launch_gemm_nt(ximg, R, pb + P.etmp + D, D + R, pb + P.k_i, y_fvi, ldy, rows, D, R, false, prec, st));
+      DRIN_TRY(launch_gemm_nt({{xt, D}, {pb + P.etmp, D + R}, pb + P.k_t, y_fvt, ldy, rows, D, D}, prec, st));
+      DRIN_TRY(launch_gemm_nt({{ximg, R}, {pb + P.etmp + D, D + R}, pb + P.k_i, y_fvi, ldy, rows, D, R}, prec, st));
     }
     if (mixed) {   // (static edges: zero units, unit scales)
       KernelTimer timer(DRIN_KC_STREAM, st);
@@ -833,7 +833,7 @@ DRIN_API int drin_forward_cached(const drin_config* cfg, const drin_batch* b, co
     return DRIN_E_UNSUPPORTED;
   }
 
-  const GemmScratch msk{L.splitk_floats ? ws + L.splitk : nullptr, L.splitk_floats};
+  const GemmScratch msk = scratch_at(ws, L.splitk, L.splitk_floats);
   // The mention-sized products of this path never read the prepared weight planes (kept as built: passing them changes the kernel, hence bits)
   const bool weight_planes = false;
   // (1) mention-side pooling and vertex-encoder Linears, [hm | fu] = [mt0; mi0] [W_h1; W_u1]^T + [0; b_u1]

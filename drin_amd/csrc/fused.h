@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include "../../include/drin_hip.h"
+#include "gemm.h"
 #include "layout.h"
 
 namespace drin {
@@ -129,7 +130,7 @@ struct FinalArgs {
 // family has), `exact` (D = 768 and, where the family reads image rows, R = 2048: every lane of every slot full, widths compile-time
 // constants) and `guarded` (the exact form's register slots with `c4 < D4` guards: part of the lanes, or whole slots, hold nothing).
 // Each family's choice is made HERE, once: its launcher switches on the result and drin_width_class exports it, so a test asks the
-// dispatch which form a shape takes instead of restating the gates (the argument of the GEMM route record, internal.h) - a pure
+// dispatch which form a shape takes instead of restating the gates (the argument of the GEMM route record, gemm.h) - a pure
 // function of the widths is enough, no per-thread record.  D4 / R4: widths in float4 quads.
 constexpr int kTinyQuads = 64;                        // one quad per lane of a wave
 constexpr int kExactTextQuads = 192, kExactImageQuads = 512;   // D = 768 (three slots), R = 2048 (eight)
@@ -199,10 +200,6 @@ int launch_pair_final(const FinalArgs& a, hipStream_t st);
 // The two are one folded model around two ways of getting a pair's layer-1 entity quantities: run_folded_head, the path's own
 // middle with run_folded_mention_finish inside, run_folded_tail.  `weight_planes` (the mention-sized products read the prepared bf16
 // planes of their weights) and the scratch a path hands over select kernels inside the GEMM module, hence bits: passed on as given.
-struct GemmScratch {  // split-K / tail-split partials of a product; none: {}
-  float* p = nullptr;
-  size_t floats = 0;
-};
 // Mention-side pooling (ghmfc.py:54-60, model.py:41; fp32 or bf16 features by cfg->feature_dtype), the two vertex-encoder Linears
 // -> vm0 = [mt0; mi0], then hmfu = [hm | fu] = vm0 [W_h1; W_u1]^T + [0; b_u1].
 int run_folded_head(const drin_config* cfg, const drin_batch* b, const drin_params* params, const float* prepared, const Prepared& P,

@@ -322,17 +322,17 @@ int drin_prepare(const drin_config* cfg, const drin_params* params, void* prepar
   }
   DRIN_TRY(copy(pb + P.bcat1 + D, L1.b_u, D));
   // E = W_v1 [W_et | W_ei]   (y[m, n] = sum_k x[m, k] w[k, n])
-  DRIN_TRY(launch_gemm_nn(L1.w_v, D, params->w_entity_text, D, pb + P.etmp, D + R, D, D, D, false, F32, st));
-  DRIN_TRY(launch_gemm_nn(L1.w_v, D, params->w_entity_image, R, pb + P.etmp + D, D + R, D, R, D, false, F32, st));
+  DRIN_TRY(launch_gemm_nn({{L1.w_v, D}, {params->w_entity_text, D}, pb + P.etmp, D + R, D, D, D}, F32, st));
+  DRIN_TRY(launch_gemm_nn({{L1.w_v, D}, {params->w_entity_image, R}, pb + P.etmp + D, D + R, D, R, D}, F32, st));
   DRIN_TRY(launch_transpose(pb + P.etmp, pb + P.ecat, D, D + R, st));
   // k = b_e W_v1^T + b_v1 as row vectors
-  DRIN_TRY(launch_gemm_nt(params->b_entity_text, D, L1.w_v, D, L1.b_v, pb + P.k_t, D, 1, D, D, false, F32, st));
-  DRIN_TRY(launch_gemm_nt(params->b_entity_image, D, L1.w_v, D, L1.b_v, pb + P.k_i, D, 1, D, D, false, F32, st));
+  DRIN_TRY(launch_gemm_nt({{params->b_entity_text, D}, {L1.w_v, D}, L1.b_v, pb + P.k_t, D, 1, D, D}, F32, st));
+  DRIN_TRY(launch_gemm_nt({{params->b_entity_image, D}, {L1.w_v, D}, L1.b_v, pb + P.k_i, D, 1, D, D}, F32, st));
   // C = W_h1 [W_et | W_ei],  cb = b_e W_h1^T + b_h1
-  DRIN_TRY(launch_gemm_nn(L1.w_h, D, params->w_entity_text, D, pb + P.c_txt, D, D, D, D, false, F32, st));
-  DRIN_TRY(launch_gemm_nn(L1.w_h, D, params->w_entity_image, R, pb + P.c_img, R, D, R, D, false, F32, st));
-  DRIN_TRY(launch_gemm_nt(params->b_entity_text, D, L1.w_h, D, L1.b_h, pb + P.cb_t, D, 1, D, D, false, F32, st));
-  DRIN_TRY(launch_gemm_nt(params->b_entity_image, D, L1.w_h, D, L1.b_h, pb + P.cb_i, D, 1, D, D, false, F32, st));
+  DRIN_TRY(launch_gemm_nn({{L1.w_h, D}, {params->w_entity_text, D}, pb + P.c_txt, D, D, D, D}, F32, st));
+  DRIN_TRY(launch_gemm_nn({{L1.w_h, D}, {params->w_entity_image, R}, pb + P.c_img, R, D, R, D}, F32, st));
+  DRIN_TRY(launch_gemm_nt({{params->b_entity_text, D}, {L1.w_h, D}, L1.b_h, pb + P.cb_t, D, 1, D, D}, F32, st));
+  DRIN_TRY(launch_gemm_nt({{params->b_entity_image, D}, {L1.w_h, D}, L1.b_h, pb + P.cb_i, D, 1, D, D}, F32, st));
   // bf16 hi / lo planes of the pair-sized GEMM weights (split-bf16 precision)
   {
     const size_t dd = (size_t)D * D, dr = (size_t)D * R;
@@ -395,15 +395,14 @@ int run_folded_head(const drin_config* cfg, const drin_batch* b, const drin_para
     DRIN_TRY(launch_axis_mean_bf16(b->mention_image, mimg, B, cfg->image_regions, R, st));
   else
     DRIN_TRY(launch_axis_mean(b->mention_image, mimg, B, cfg->image_regions, R, st));
+  const NtProduct enc_mi =
+      NtProduct{{mimg, R}, {params->w_mention_image, R}, params->b_mention_image, vm0 + (size_t)B * D, D, B, D, R}.with_planes(wp(P.p_wmi));
   if (rows)   // the mention-text vertex is in vm0 already: the mention-image product alone
-    DRIN_TRY(launch_gemm_nt(mimg, R, params->w_mention_image, R, params->b_mention_image, vm0 + (size_t)B * D, D, B, D, R, false, prec, st,
-                            sk.p, sk.floats, wp(P.p_wmi)));
+    DRIN_TRY(launch_gemm_nt(enc_mi, prec, st, sk));
   else
-    DRIN_TRY(launch_gemm_nt_pair({span_mean, params->w_mention_text, params->b_mention_text, vm0, D, D, D, B, D, D, wp(P.p_wmt)},
-                                 {mimg, params->w_mention_image, params->b_mention_image, vm0 + (size_t)B * D, R, R, D, B, D, R, wp(P.p_wmi)},
-                                 prec, st, sk.p, sk.floats));
-  return launch_gemm_nt(vm0, D, pb + P.wcat1, D, pb + P.bcat1, hmfu, 2 * D, 2 * (int64_t)B, 2 * D, D, false, prec, st, sk.p, sk.floats,
-                        wp(P.p_wcat1));
+    DRIN_TRY(launch_gemm_nt_pair(NtProduct{{span_mean, D}, {params->w_mention_text, D}, params->b_mention_text, vm0, D, B, D, D}.with_planes(wp(P.p_wmt)),
+                                 enc_mi, prec, st, sk));
+  return launch_gemm_nt(NtProduct{{vm0, D}, {pb + P.wcat1, D}, pb + P.bcat1, hmfu, 2 * D, 2 * (int64_t)B, 2 * D, D}.with_planes(wp(P.p_wcat1)), prec, st, sk);
 }
 
 int run_folded_mention_finish(const drin_config* cfg, const drin_params* params, const float* pb, const Prepared& P,
@@ -412,8 +411,8 @@ int run_folded_mention_finish(const drin_config* cfg, const drin_params* params,
   const drin_layer_params& L1 = params->layer[0];
   DRIN_TRY(launch_layernorm_gelu(vm1, L1.ln_weight, L1.ln_bias, vm1, nullptr, nullptr, 2 * (int64_t)B, D, cfg->layer_norm_eps, st,
                                  vertex_act(cfg)));
-  return launch_gemm_nt(vm1, D, params->layer[1].w_h, D, nullptr, hm2, D, 2 * (int64_t)B, D, D, false, folded_precision(cfg), st, sk.p,
-                        sk.floats, weight_planes ? pb + P.p_wh2 : nullptr);
+  const NtProduct wh2 = {{vm1, D}, {params->layer[1].w_h, D}, nullptr, hm2, D, 2 * (int64_t)B, D, D};
+  return launch_gemm_nt(wh2.with_planes(weight_planes ? pb + P.p_wh2 : nullptr), folded_precision(cfg), st, sk);
 }
 
 int run_folded_tail(const drin_config* cfg, const drin_params* params, const float* pb, const Prepared& P, int chunks,
@@ -425,8 +424,7 @@ int run_folded_tail(const drin_config* cfg, const drin_params* params, const flo
   const drin_layer_params& L2 = params->layer[1];
   // layer-2 mention-text vertex
   DRIN_TRY(launch_mention_input2(s2_part, vm1, agg2, B, D, N, chunks, st));
-  DRIN_TRY(launch_gemm_nt(agg2, D, L2.w_h, D, L2.b_h, mt2, D, B, D, D, false, prec, st, sk.p, sk.floats,
-                          weight_planes ? pb + P.p_wh2 : nullptr));
+  DRIN_TRY(launch_gemm_nt(NtProduct{{agg2, D}, {L2.w_h, D}, L2.b_h, mt2, D, B, D, D}.with_planes(weight_planes ? pb + P.p_wh2 : nullptr), prec, st, sk));
   DRIN_TRY(launch_layernorm_gelu(mt2, L2.ln_weight, L2.ln_bias, mt2, nullptr, nullptr, B, D, cfg->layer_norm_eps, st, vertex_act(cfg)));
   // layer-2 entity-text contraction, vertex and score
   // (Round 6, built and dropped - profiles/r6_full_row_ab.txt, tools/probes/r6_full_row/, commit 8a5bc6b: this contraction and k_pair_final's
@@ -436,10 +434,9 @@ int run_folded_tail(const drin_config* cfg, const drin_params* params, const flo
   if (et1_hi) {
     const __bf16* e1 = static_cast<const __bf16*>(et1_hi);
     const __bf16* w2 = reinterpret_cast<const __bf16*>(pb + P.p_wh2);
-    DRIN_TRY(launch_gemm_x3_planes(e1, e1 + (size_t)M * D, D, w2, w2 + (size_t)D * D, D, nullptr, h2, D, M, D, D, st, pair_sk.p,
-                                   pair_sk.floats));
+    DRIN_TRY(launch_gemm_x3_planes(e1, e1 + (size_t)M * D, D, w2, w2 + (size_t)D * D, D, nullptr, h2, D, M, D, D, st, pair_sk));
   } else {
-    DRIN_TRY(launch_gemm_nt(et1, D, L2.w_h, D, nullptr, h2, D, M, D, D, false, prec, st));
+    DRIN_TRY(launch_gemm_nt({{et1, D}, {L2.w_h, D}, nullptr, h2, D, M, D, D}, prec, st));
   }
   FinalArgs fa = shaped_args<FinalArgs>(*cfg);
   set_vertex_fields(fa, *cfg);
@@ -534,7 +531,7 @@ static int forward_prepared_on_stream(const drin_config* cfg, const drin_batch* 
   // Mention-sized contractions: launch_gemm_nt / launch_gemm_nt_pair choose the kernel; the split-bf16 ones read the prepared
   // weight planes when this path has them (`planes` also asks R % 32, which those cannot see)
   auto wp = [&](size_t plane_off) -> const float* { return planes ? pb + plane_off : nullptr; };
-  const GemmScratch msk{L.splitk_floats ? ws + L.splitk : nullptr, L.splitk_floats};
+  const GemmScratch msk = scratch_at(ws, L.splitk, L.splitk_floats);
   float* vm0 = ws + L.vm0;
   float* hmfu = ws + L.hmfu;
   // pooled entity text stored as bf16 is exact in its hi plane: no lo plane, two MFMAs per tile pair
@@ -542,13 +539,11 @@ static int forward_prepared_on_stream(const drin_config* cfg, const drin_batch* 
   // split-K scratch of the pair-sized products: the whole-product split when the batch is a few tiles, else the tail-split scratch
   const GemmScratch psk = L.pair_splitk_floats ? GemmScratch{ws + L.pair_splitk, L.pair_splitk_floats} : msk;
   // x_i C_i^T on rows read in place (fp32: split on the fly; bf16: the rows are the one plane), whole or a slice of its row tiles
+  const NtProduct xi_ci = NtProduct{{(const float*)b->entity_image, R}, {pb + P.c_img, R}, nullptr, ws + L.h_image, D, M, D, R}.with_planes(pb + P.p_cimg);
   auto image_rows_product = [&](hipStream_t on, RowTiles rows) -> int {
-    const __bf16* ci = reinterpret_cast<const __bf16*>(pb + P.p_cimg);
     if (bf16_feat)
-      return launch_gemm_x3_planes(b->entity_image, nullptr, R, ci, ci + (size_t)D * R, R, nullptr, ws + L.h_image, D, M, D, R, on, psk.p,
-                                   psk.floats, rows);
-    return launch_gemm_nt_bf16x3_p4((const float*)b->entity_image, R, ci, ci + (size_t)D * R, R, nullptr, ws + L.h_image, D, M, D, R, on, false,
-                                    aligned16(psk.p) ? psk.p : nullptr, psk.floats, rows);
+      return launch_gemm_x3_planes(b->entity_image, nullptr, R, xi_ci.w_hi, xi_ci.w_lo, R, nullptr, ws + L.h_image, D, M, D, R, on, psk, rows);
+    return launch_gemm_nt_bf16x3_p4(xi_ci, on, aligned16(psk.p) ? psk : GemmScratch{}, rows);
   };
   SideJoin side_join;
   if (side.S > 0) {
@@ -567,8 +562,8 @@ static int forward_prepared_on_stream(const drin_config* cfg, const drin_batch* 
   // (1) mention-side pooling and vertex-encoder Linears, [hm | fu]; (2) q = fu [W_v1 W_et | W_v1 W_ei]
   DRIN_TRY(run_folded_head(cfg, b, params, pb, P, planes, ws + L.span_mean, ws + L.mimg, vm0, hmfu, msk, st, head));
   if (dyn)
-    DRIN_TRY(launch_gemm_nt(hmfu + D, 2 * D, pb + P.ecat, D, nullptr, ws + L.q, D + R, 2 * (int64_t)B, D + R, D, false, prec, st, msk.p,
-                            msk.floats, wp(P.p_ecat)));
+    DRIN_TRY(launch_gemm_nt(NtProduct{{hmfu + D, 2 * D}, {pb + P.ecat, D}, nullptr, ws + L.q, D + R, 2 * (int64_t)B, D + R, D}.with_planes(wp(P.p_ecat)),
+                            prec, st, msk));
   // (3) one pass over the entity-side bytes
   StreamArgs sa = shaped_args<StreamArgs>(*cfg);
   set_edge_fields(sa, *cfg);
@@ -616,39 +611,36 @@ static int forward_prepared_on_stream(const drin_config* cfg, const drin_batch* 
   if (L.chunks > 1)
     DRIN_TRY(launch_reduce_stream_partials(ws + L.s_part, ws + L.s_text, ws + L.s_img, ws + L.sig, B, D, R, L.chunks, st));
   // (4) layer-1 mention vertices: T = S_text W_et^T + S_img W_ei^T, then the W_h input, W_h, LN, GELU
-  DRIN_TRY(launch_gemm_nt_pair({ws + L.s_text, params->w_entity_text, nullptr, ws + L.tm, D, D, D, 2 * (int64_t)B, D, D, wp(P.p_wet)},
-                               {ws + L.s_img, params->w_entity_image, nullptr, ws + L.tm2, R, R, D, 2 * (int64_t)B, D, R,
-                                wp(P.p_wei)},
-                               prec, st, msk.p, msk.floats));
+  DRIN_TRY(launch_gemm_nt_pair(NtProduct{{ws + L.s_text, D}, {params->w_entity_text, D}, nullptr, ws + L.tm, D, 2 * (int64_t)B, D, D}.with_planes(wp(P.p_wet)),
+                               NtProduct{{ws + L.s_img, R}, {params->w_entity_image, R}, nullptr, ws + L.tm2, D, 2 * (int64_t)B, D, R}.with_planes(wp(P.p_wei)),
+                               prec, st, msk));
   DRIN_TRY(launch_mention_input1(ws + L.tm, ws + L.tm2, ws + L.sig, params->b_entity_text, params->b_entity_image, vm0, ws + L.agg1, B, D, N, st));
   float* vm1 = ws + L.vm1;
-  DRIN_TRY(launch_gemm_nt(ws + L.agg1, D, L1.w_h, D, L1.b_h, vm1, D, 2 * (int64_t)B, D, D, false, prec, st, msk.p, msk.floats, wp(P.p_wh1)));
+  DRIN_TRY(launch_gemm_nt(NtProduct{{ws + L.agg1, D}, {L1.w_h, D}, L1.b_h, vm1, D, 2 * (int64_t)B, D, D}.with_planes(wp(P.p_wh1)), prec, st, msk));
   DRIN_TRY(run_folded_mention_finish(cfg, params, pb, P, planes, vm1, ws + L.hm2, msk, st));
   // (5) the two pair-sized layer-1 contractions on the folded weights
   if (planes) {
     const __bf16* ct = reinterpret_cast<const __bf16*>(pb + P.p_ctxt);
     const __bf16* ci = reinterpret_cast<const __bf16*>(pb + P.p_cimg);
     DRIN_TRY(launch_gemm_x3_planes(xt_hi, xt_exact ? nullptr : xt_hi + MD, D, ct, ct + (size_t)D * D, D, nullptr, ws + L.h_text, D, M, D,
-                                   D, st, psk.p, psk.floats));
+                                   D, st, psk));
     if (if16)        // one fp16 pass on the plane the stream kernel wrote
       DRIN_TRY(launch_gemm_f16_planes(xi_hi, R, pb + P.p_cimg_f16, R, ws + L.xi_scale, pb + P.cimg_f16_scale, ws + L.h_image, D, M, D, R,
-                                      st, psk.p, psk.floats));
+                                      st, psk));
     else if (xi_planes)
       DRIN_TRY(launch_gemm_x3_planes(xi_hi, bf16_feat ? nullptr : xi_hi + MR, R, ci, ci + (size_t)D * R, R, nullptr, ws + L.h_image, D, M,
-                                     D, R, st, psk.p, psk.floats));
+                                     D, R, st, psk));
     else if (side.S > 0) {   // the row tiles the side stream did not take, once it is done with its own
       DRIN_TRY(side_join.join());
       DRIN_TRY(image_rows_product(st, RowTiles{side.S, -1, 0}));
     } else if (bf16_feat)  // the bf16 image rows are read in place as the (only) plane of the A operand
-      DRIN_TRY(launch_gemm_x3_planes(b->entity_image, nullptr, R, ci, ci + (size_t)D * R, R, nullptr, ws + L.h_image, D, M, D, R, st, psk.p,
-                                     psk.floats));
+      DRIN_TRY(launch_gemm_x3_planes(b->entity_image, nullptr, R, ci, ci + (size_t)D * R, R, nullptr, ws + L.h_image, D, M, D, R, st, psk));
     else
-      DRIN_TRY(launch_gemm_nt_bf16x3(b->entity_image, R, pb + P.c_img, R, nullptr, ws + L.h_image, D, M, D, R, st, ci, ci + (size_t)D * R,
-                                     false, psk.p, psk.floats));
+      DRIN_TRY(launch_gemm_nt_bf16x3(xi_ci, st, psk));
   } else {
     const float* x_t = tokens ? ws + L.xt : b->entity_text;
-    DRIN_TRY(launch_gemm_nt(x_t, D, pb + P.c_txt, D, nullptr, ws + L.h_text, D, M, D, D, false, prec, st));
-    DRIN_TRY(launch_gemm_nt(b->entity_image, R, pb + P.c_img, R, nullptr, ws + L.h_image, D, M, D, R, false, prec, st));
+    DRIN_TRY(launch_gemm_nt({{x_t, D}, {pb + P.c_txt, D}, nullptr, ws + L.h_text, D, M, D, D}, prec, st));
+    DRIN_TRY(launch_gemm_nt({{(const float*)b->entity_image, R}, {pb + P.c_img, R}, nullptr, ws + L.h_image, D, M, D, R}, prec, st));
   }
   // The two pair kernels walk the same candidate chunks as the stream kernel (FusedLayout::chunks: whole mentions from 2 048
   // mentions up - their share of that change: row kernels 1.385 -> 1.27 ms at 4 096 mentions; 64 mentions with whole-mention

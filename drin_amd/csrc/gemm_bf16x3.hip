@@ -318,10 +318,12 @@ __global__ void __launch_bounds__(BN) k_tail_add(const float* __restrict__ tail,
 }
 
 template <int BM, int BN, int WM, int WN, bool W_PLANES>
-static int launch(const float* x, int64_t ldx, const float* w, const void* w_hi, const void* w_lo, int64_t ldw,
-                  const float* bias, float* y, int64_t ldy, int64_t M, int N, int K, hipStream_t st, bool accumulate,
-                  float* tail = nullptr, size_t tail_floats = 0, const int64_t* a_index = nullptr) {
+static int launch(const NtProduct& p, hipStream_t st, GemmScratch tail_scratch) {
   using G = Cfg<BM, BN, WM, WN>;
+  const int64_t M = p.rows;
+  const int N = p.n_out, K = p.k_red;
+  float* const tail = tail_scratch.p;
+  const size_t tail_floats = tail_scratch.floats;
   const int64_t mt = cdiv(M, BM), nt = cdiv(N, BN);
   if (mt * nt > (int64_t)1 << 30) {
     set_error("gemm_bf16x3: %lld tiles exceed the grid limit; split the batch", (long long)(mt * nt));
@@ -360,15 +362,15 @@ static int launch(const float* x, int64_t ldx, const float* w, const void* w_hi,
   KernelTimer timer(DRIN_KC_GEMM_X3, st);
   {
     RouteNote n{DRIN_GEMM_FAMILY_BF16X3, BM, BN};
-    n.w_planes = W_PLANES, n.indexed = a_index != nullptr, n.accumulate = accumulate, n.ksplit = ksplit;
+    n.w_planes = W_PLANES, n.indexed = p.x_index != nullptr, n.accumulate = p.accumulate, n.ksplit = ksplit;
     n.tiles = tiles, n.whole_tiles = full, n.work_items = items;
     note_route(n);
   }
-  hipLaunchKernelGGL(kern, dim3(items), dim3(G::THREADS), G::LDS_BYTES, st, x, ldx, w, (const __bf16*)w_hi,
-                     (const __bf16*)w_lo, ldw, bias, y, ldy, M, N, K, accumulate ? 1 : 0, (unsigned)nt, full, ksplit, tail, a_index);
+  hipLaunchKernelGGL(kern, dim3(items), dim3(G::THREADS), G::LDS_BYTES, st, p.x.p, p.x.ld, p.w.p, (const __bf16*)p.w_hi,
+                     (const __bf16*)p.w_lo, p.w.ld, p.bias, p.y, p.ldy, M, N, K, p.accumulate ? 1 : 0, (unsigned)nt, full, ksplit, tail, p.x_index);
   DRIN_CHECK_LAUNCH("k_gemm_bf16x3");
   if (ksplit > 1) {
-    hipLaunchKernelGGL((k_tail_add<BM, BN>), dim3(BM, tiles - full), dim3(BN), 0, st, tail, y, ldy, M, N, (unsigned)nt,
+    hipLaunchKernelGGL((k_tail_add<BM, BN>), dim3(BM, tiles - full), dim3(BN), 0, st, tail, p.y, p.ldy, M, N, (unsigned)nt,
                        full, ksplit);
     DRIN_CHECK_LAUNCH("k_tail_add");
   }
@@ -436,30 +438,30 @@ int launch_to_f16_scaled(const float* x, void* out, int64_t n, float* scale, hip
 }
 
 // w_hi / w_lo: optional pre-split bf16 planes of w (same row stride); when given, w itself is not read.
-int launch_gemm_nt_bf16x3(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* bias, float* y,
-                          int64_t ldy, int64_t M, int N, int K, hipStream_t st, const void* w_hi, const void* w_lo,
-                          bool accumulate, float* tail, size_t tail_floats, const int64_t* a_index) {
+int launch_gemm_nt_bf16x3(const NtProduct& p, hipStream_t st, GemmScratch tail) {
+  const int64_t M = p.rows;
+  const int N = p.n_out, K = p.k_red;
   if (M <= 0 || N <= 0) return DRIN_OK;
-  if (a_index != nullptr && ((K % x3::BK) || K <= 0)) {
+  if (p.x_index != nullptr && ((K % x3::BK) || K <= 0)) {
     set_error("gemm_bf16x3: indexed rows need K %% 32 == 0 (got %d) on the split-bf16 kernel", K);
     return DRIN_E_UNSUPPORTED;
   }
   if ((K % x3::BK) || K <= 0) {  // odd reduction lengths take the exact fp32 kernel (guarded loads)
-    if (!w) {
+    if (!p.w.p) {
       set_error("gemm_bf16x3: K=%d is not a multiple of 32 and no fp32 weights were given", K);
       return DRIN_E_SHAPE;
     }
-    return launch_gemm_nt(x, ldx, w, ldw, bias, y, ldy, M, N, K, accumulate, DRIN_PREC_F32, st);
+    return launch_gemm_nt(p, DRIN_PREC_F32, st);
   }
-  const bool planes = w_hi != nullptr && w_lo != nullptr;
-  if ((ldx % 4) || !aligned16(x) ||
-      (planes ? ((ldw % 8) || !aligned16(w_hi) || !aligned16(w_lo)) : ((ldw % 4) || !aligned16(w)))) {
+  const bool planes = p.w_hi != nullptr && p.w_lo != nullptr;
+  if ((p.x.ld % 4) || !aligned16(p.x.p) ||
+      (planes ? ((p.w.ld % 8) || !aligned16(p.w_hi) || !aligned16(p.w_lo)) : ((p.w.ld % 4) || !aligned16(p.w.p)))) {
     set_error("gemm_bf16x3: operands must be 16-byte aligned with leading dimensions multiples of 4 (fp32) / 8 (bf16)");
     return DRIN_E_ALIGN;
   }
   // pair-sized problems: 256 x 256 tiles; anything that would not fill the chip with them: 64 x 128 tiles
   const bool big = cdiv(M, 256) * cdiv(N, 256) >= 192;
-  if (tail != nullptr && !aligned16(tail)) tail = nullptr;
+  if (!aligned16(tail.p)) tail = {};
   // Mid-sized products (a few thousand to a few ten thousand rows: the training step at the reference's batch): 64 x 128 tiles
   // fill the chip but run at the L2 -> LDS bandwidth so small a tile needs (SQ counters: an MFMA executing in 0.30 of the
   // cycles, waves parked 0.51 of their time - profiles/r3_mfma_pmc.json).  Where a BM x 256 tile of eight waves comes to at
@@ -481,23 +483,23 @@ int launch_gemm_nt_bf16x3(const float* x, int64_t ldx, const float* w, int64_t l
       if (filled && (best == 0 || rounds * cand <= cost)) cost = rounds * cand, best = cand;
     }
     switch (best) {
-      case 96: return x3::launch<96, 256, 2, 4, true>(x, ldx, w, w_hi, w_lo, ldw, bias, y, ldy, M, N, K, st, accumulate, nullptr, 0, a_index);
-      case 128: return x3::launch<128, 256, 2, 4, true>(x, ldx, w, w_hi, w_lo, ldw, bias, y, ldy, M, N, K, st, accumulate, nullptr, 0, a_index);
-      case 160: return x3::launch<160, 256, 2, 4, true>(x, ldx, w, w_hi, w_lo, ldw, bias, y, ldy, M, N, K, st, accumulate, nullptr, 0, a_index);
+      case 96: return x3::launch<96, 256, 2, 4, true>(p, st, {});
+      case 128: return x3::launch<128, 256, 2, 4, true>(p, st, {});
+      case 160: return x3::launch<160, 256, 2, 4, true>(p, st, {});
       default: break;   // no tall tile fills its rounds: the 64 x 128 tiles below
     }
   }
   // big products on weight planes: the four-phase pipeline of gemm_x3_planes.hip (indexed rows and odd layouts: the two-phase kernel below)
-  if (big && planes && a_index == nullptr && (N % 4) == 0 && (ldy % 4) == 0 && aligned16(y) && (bias == nullptr || aligned16(bias)))
-    return launch_gemm_nt_bf16x3_p4(x, ldx, w_hi, w_lo, ldw, bias, y, ldy, M, N, K, st, accumulate, tail, tail_floats);
+  if (big && planes && p.x_index == nullptr && (N % 4) == 0 && (p.ldy % 4) == 0 && aligned16(p.y) && (p.bias == nullptr || aligned16(p.bias)))
+    return launch_gemm_nt_bf16x3_p4(p, st, tail);
   if (big)
-    return planes ? x3::launch<256, 256, 2, 4, true>(x, ldx, w, w_hi, w_lo, ldw, bias, y, ldy, M, N, K, st, accumulate, tail, tail_floats, a_index)
-                  : x3::launch<256, 256, 2, 4, false>(x, ldx, w, w_hi, w_lo, ldw, bias, y, ldy, M, N, K, st, accumulate, tail, tail_floats, a_index);
+    return planes ? x3::launch<256, 256, 2, 4, true>(p, st, tail)
+                  : x3::launch<256, 256, 2, 4, false>(p, st, tail);
   // (measured again in round 2, same box: 128 x 128 tiles with four waves of 64 x 64, two workgroups per CU, for 2 048 <= M <
   //  16 384 - the B = 64 training step's split-bf16 GEMMs 0.745 -> 0.827 ms, a 64-mention scoring call 0.100 -> 0.116: the
   //  three co-resident workgroups of the small tile hide each other's stage barriers better than the larger wave tile saves)
-  return planes ? x3::launch<64, 128, 2, 2, true>(x, ldx, w, w_hi, w_lo, ldw, bias, y, ldy, M, N, K, st, accumulate, tail, tail_floats, a_index)
-                : x3::launch<64, 128, 2, 2, false>(x, ldx, w, w_hi, w_lo, ldw, bias, y, ldy, M, N, K, st, accumulate, tail, tail_floats, a_index);
+  return planes ? x3::launch<64, 128, 2, 2, true>(p, st, tail)
+                : x3::launch<64, 128, 2, 2, false>(p, st, tail);
 }
 
 }  // namespace drin

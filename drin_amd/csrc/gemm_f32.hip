@@ -208,7 +208,7 @@ __global__ void __launch_bounds__(256, 2)
                                             blockIdx.y, blockIdx.z);
 }
 
-// Several mention-sized products of ONE operand layout in one launch (F32GemmGroup, internal.h): a 1-D grid, a problem's
+// Several mention-sized products of ONE operand layout in one launch (F32GemmGroup, gemm.h): a 1-D grid, a problem's
 // work items are (K slice, row tile, column tile), column tile fastest.  Each product alone is a launch of a few
 // microseconds of work between a fill and a drain; the chain of them is what a B = 64 training step spends 0.2 ms on.
 struct GroupItem {
@@ -315,7 +315,7 @@ int launch_splitk_reduce(const float* partial, int splits, int64_t part_stride, 
   return DRIN_OK;
 }
 
-// ---- SliceSum (internal.h): y += its segments' slices, in order --------------------------------------------------------
+// ---- SliceSum (gemm.h): y += its segments' slices, in order --------------------------------------------------------
 __global__ void __launch_bounds__(256) k_slice_sum(const SliceSum g) {
   int di = 0;
   for (int i = 1; i < g.n; ++i) di = blockIdx.x >= g.dst[i].first_block ? i : di;
@@ -389,15 +389,15 @@ int launch_slice_sum(SliceSum& s, hipStream_t st) {
 // mention-sized fp32 products with a long reduction: split K over workgroups into `scratch`, then reduce in order
 template <bool B_KMAJOR>
 static int launch_small_splitk(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* bias, float* y,
-                               int64_t ldy, int64_t M, int N, int K, bool accumulate, float* scratch, size_t scratch_floats,
-                               hipStream_t st, const char* what) {
+                               int64_t ldy, int64_t M, int N, int K, bool accumulate, GemmScratch scratch, hipStream_t st,
+                               const char* what) {
   int splits = small_splitk_slices(K);
-  while (splits > 1 && (size_t)splits * M * N > scratch_floats) --splits;
+  while (splits > 1 && (size_t)splits * M * N > scratch.floats) --splits;
   const int64_t part_stride = M * (int64_t)N;
   int used = 1;
-  DRIN_TRY((launch<64, 64, false, B_KMAJOR>(x, ldx, w, ldw, nullptr, scratch, N, M, N, K, splits, GEMM_PARTIAL, st, what,
+  DRIN_TRY((launch<64, 64, false, B_KMAJOR>(x, ldx, w, ldw, nullptr, scratch.p, N, M, N, K, splits, GEMM_PARTIAL, st, what,
                                             part_stride, &used)));
-  return launch_splitk_reduce(scratch, used, part_stride, bias, y, ldy, M, N, accumulate, st);
+  return launch_splitk_reduce(scratch.p, used, part_stride, bias, y, ldy, M, N, accumulate, st);
 }
 
 // y[m, n] (+)= bias[n] + sum_k x[m, k] w[n, k] for ONE mention's rows (M <= 2: its text and image vertex).  A GEMV per row: one
@@ -441,23 +441,23 @@ static bool gemv_fits(const float* x, int64_t ldx, const float* w, int64_t ldw, 
   return M >= 1 && M <= 2 && (K % 4) == 0 && (ldx % 4) == 0 && (ldw % 4) == 0 && aligned16(x) && aligned16(w);
 }
 
-static int launch_gemv(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* bias, float* y, int64_t ldy,
-                       int64_t M, int N, int K, bool accumulate, hipStream_t st) {
+static int launch_gemv(const NtProduct& p, hipStream_t st) {
   KernelTimer timer(DRIN_KC_GEMM, st);
-  const dim3 grid((unsigned)cdiv(N, 4));
+  const dim3 grid((unsigned)cdiv(p.n_out, 4));
   {
     RouteNote n{DRIN_GEMM_FAMILY_F32_GEMV, 2, 4};
-    n.a_lo = false, n.accumulate = accumulate, n.tiles = n.whole_tiles = n.work_items = grid.x;
+    n.a_lo = false, n.accumulate = p.accumulate, n.tiles = n.whole_tiles = n.work_items = grid.x;
     note_route(n);
   }
-  hipLaunchKernelGGL(k_gemv_rows<2>, grid, dim3(256), 0, st, x, ldx, w, ldw, bias, y, ldy, (int)M, N, K / 4, accumulate ? 1 : 0);
+  hipLaunchKernelGGL(k_gemv_rows<2>, grid, dim3(256), 0, st, p.x.p, p.x.ld, p.w.p, p.w.ld, p.bias, p.y, p.ldy, (int)p.rows, p.n_out, p.k_red / 4,
+                     p.accumulate ? 1 : 0);
   DRIN_CHECK_LAUNCH("k_gemv_rows");
   return DRIN_OK;
 }
 
-static bool small_splitk_fits(int64_t M, int N, int K, int64_t ldy, const float* y, float* scratch, size_t scratch_floats) {
-  return scratch != nullptr && small_splitk_shape(M, K) && (N % 4) == 0 && (ldy % 4) == 0 && aligned16(y) && aligned16(scratch) &&
-         scratch_floats >= (size_t)2 * M * N;
+static bool small_splitk_fits(int64_t M, int N, int K, int64_t ldy, const float* y, GemmScratch scratch) {
+  return scratch.p != nullptr && small_splitk_shape(M, K) && (N % 4) == 0 && (ldy % 4) == 0 && aligned16(y) && aligned16(scratch.p) &&
+         scratch.floats >= (size_t)2 * M * N;
 }
 
 // the slice reductions of a group of split-K products in one launch (k_splitk_reduce per item)
@@ -484,30 +484,28 @@ __global__ void __launch_bounds__(256) k_splitk_reduce_group(const ReduceGroupAr
   st4(g.y[pi] + m * g.ldy[pi] + c4 * 4, s);
 }
 
-bool gemm_nt_f32_group_fits(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* y, int64_t ldy, int64_t M, int N,
-                            int K, int precision) {
+bool gemm_nt_f32_group_fits(const NtProduct& p, int precision) {
+  const int64_t M = p.rows;
   // exactly the products launch_gemm_nt sends to the exact-fp32 split-K pair (kernel + slice reduction)
   if (nt_takes_bf16x3(precision, M)) return false;
   if (precision != DRIN_PREC_F32 && precision != DRIN_PREC_BF16X3) return false;
-  if ((K % 4) || gemv_fits(x, ldx, w, ldw, M, K)) return false;
-  return M >= 1 && small_splitk_shape(M, K) && (N % 4) == 0 && (ldy % 4) == 0 && (ldx % 4) == 0 && (ldw % 4) == 0 && aligned16(y) &&
-         aligned16(x) && aligned16(w);
+  if ((p.k_red % 4) || gemv_fits(p.x.p, p.x.ld, p.w.p, p.w.ld, M, p.k_red)) return false;
+  return M >= 1 && small_splitk_shape(M, p.k_red) && (p.n_out % 4) == 0 && (p.ldy % 4) == 0 && (p.x.ld % 4) == 0 && (p.w.ld % 4) == 0 &&
+         aligned16(p.y) && aligned16(p.x.p) && aligned16(p.w.p);
 }
 
-int F32GemmGroup::add_nt(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* bias, float* y, int64_t ldy, int64_t M,
-                         int N, int K) {
+int F32GemmGroup::add_nt(const NtProduct& p) {
   if (n == MAX) {
     set_error("internal: more than %d products in one exact-fp32 group", MAX);
     return DRIN_E_SHAPE;
   }
-  item[n] = {x, ldx, w, ldw, y, ldy, M, N, K};
-  bias_of[n++] = bias;
+  nt[n++] = p;
   return DRIN_OK;
 }
 
 // y = x w^T + bias for every item (each one passed gemm_nt_f32_group_fits): the split-K kernel of all items in one launch,
 // their slice reductions in a second - the same slices in the same order as launch_gemm_nt's own pair of launches
-int launch_gemm_nt_f32_group(const F32GemmGroup& grp, hipStream_t st, float* scratch, size_t scratch_floats) {
+int launch_gemm_nt_f32_group(const F32GemmGroup& grp, hipStream_t st, GemmScratch scratch) {
   if (grp.n == 0) return DRIN_OK;
   GroupArgs ga;
   ReduceGroupArgs ra;
@@ -515,27 +513,29 @@ int launch_gemm_nt_f32_group(const F32GemmGroup& grp, hipStream_t st, float* scr
   unsigned items = 0, blocks = 0;
   size_t used = 0;
   for (int i = 0; i < grp.n; ++i) {
-    const auto& it = grp.item[i];
-    if (it.M <= 0 || it.N <= 0 || it.K <= 0) {
-      set_error("gemm_nt group: item %d has M=%lld N=%d K=%d", i, (long long)it.M, it.N, it.K);
+    const NtProduct& it = grp.nt[i];
+    const int64_t M = it.rows;
+    const int N = it.n_out, K = it.k_red;
+    if (M <= 0 || N <= 0 || K <= 0) {
+      set_error("gemm_nt group: item %d has M=%lld N=%d K=%d", i, (long long)M, N, K);
       return DRIN_E_SHAPE;
     }
-    int splits = small_splitk_slices(it.K);   // as launch_small_splitk
-    const int kps = (int)(cdiv(cdiv(it.K, splits), BK) * BK);
-    splits = (int)cdiv(it.K, kps);
-    const int64_t part_stride = it.M * (int64_t)it.N;
-    if (scratch == nullptr || !aligned16(scratch) || used + (size_t)splits * part_stride > scratch_floats) {
-      set_error("gemm_nt group: split-K scratch of %zu floats is too small", scratch_floats);
+    int splits = small_splitk_slices(K);   // as launch_small_splitk
+    const int kps = (int)(cdiv(cdiv(K, splits), BK) * BK);
+    splits = (int)cdiv(K, kps);
+    const int64_t part_stride = M * (int64_t)N;
+    if (scratch.p == nullptr || !aligned16(scratch.p) || used + (size_t)splits * part_stride > scratch.floats) {
+      set_error("gemm_nt group: split-K scratch of %zu floats is too small", scratch.floats);
       return DRIN_E_WORKSPACE;
     }
     auto& P = ga.p[i];
-    P.a = it.a, P.b = it.b, P.c = scratch + used, P.lda = it.lda, P.ldb = it.ldb, P.ldc = it.N;
-    P.M = it.M, P.N = it.N, P.K = it.K, P.k_per_split = kps, P.flags = GEMM_PARTIAL, P.part_stride = part_stride;
-    P.col_tiles = (unsigned)cdiv(it.N, 64), P.row_tiles = (unsigned)cdiv(it.M, 64), P.first = items;
+    P.a = it.x.p, P.b = it.w.p, P.c = scratch.p + used, P.lda = it.x.ld, P.ldb = it.w.ld, P.ldc = N;
+    P.M = M, P.N = N, P.K = K, P.k_per_split = kps, P.flags = GEMM_PARTIAL, P.part_stride = part_stride;
+    P.col_tiles = (unsigned)cdiv(N, 64), P.row_tiles = (unsigned)cdiv(M, 64), P.first = items;
     items += P.col_tiles * P.row_tiles * (unsigned)splits;
-    ra.partial[i] = scratch + used, ra.bias[i] = grp.bias_of[i], ra.y[i] = it.y, ra.ldy[i] = it.ldy, ra.M[i] = it.M;
-    ra.part_stride[i] = part_stride, ra.N4[i] = it.N / 4, ra.splits[i] = splits, ra.first[i] = blocks;
-    blocks += (unsigned)cdiv(it.M * (it.N / 4), 256);
+    ra.partial[i] = scratch.p + used, ra.bias[i] = it.bias, ra.y[i] = it.y, ra.ldy[i] = it.ldy, ra.M[i] = M;
+    ra.part_stride[i] = part_stride, ra.N4[i] = N / 4, ra.splits[i] = splits, ra.first[i] = blocks;
+    blocks += (unsigned)cdiv(M * (N / 4), 256);
     used += (size_t)splits * part_stride;
     used = (used + 3) & ~(size_t)3;
   }
@@ -551,19 +551,25 @@ int launch_gemm_nt_f32_group(const F32GemmGroup& grp, hipStream_t st, float* scr
   return DRIN_OK;
 }
 
-int launch_gemm_nt(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* bias, float* y, int64_t ldy,
-                   int64_t M, int N, int K, bool accumulate, int precision, hipStream_t st, float* splitk,
-                   size_t splitk_floats, const float* w_planes) {
+int launch_gemm_nt(const NtProduct& p, int precision, hipStream_t st, GemmScratch splitk) {
+  const float *x = p.x.p, *w = p.w.p, *bias = p.bias;
+  float* const y = p.y;
+  const int64_t ldx = p.x.ld, ldw = p.w.ld, ldy = p.ldy, M = p.rows;
+  const int N = p.n_out, K = p.k_red;
+  const bool accumulate = p.accumulate;
   // split-bf16 contraction for the pair-sized GEMMs; the mention-sized ones (a few hundred rows) stay on
   // the exact fp32 kernel: they are latency-bound, not rate-bound
   // (the 256-row threshold measured again in round 2, same box, 16 / 64 rows instead: a 64-mention scoring call 0.551 -> 0.576 ms,
   //  the B = 64 training step 1.406 -> 1.424 - below a tile row of the 256-wide kernel the exact one is as fast and exact)
   if (!accumulate && nt_takes_bf16x3(precision, M)) {
     // (pre-split weight planes: contiguous [N][K] weights only, K a multiple of 32 - what the LDS-DMA path reads)
-    const bool planes = w_planes != nullptr && ldw == K && nt_planes_width(K);
-    const __bf16* hi = reinterpret_cast<const __bf16*>(w_planes);
-    return launch_gemm_nt_bf16x3(x, ldx, w, ldw, bias, y, ldy, M, N, K, st, planes ? (const void*)hi : nullptr,
-                                 planes ? (const void*)(hi + (int64_t)N * K) : nullptr, false, splitk, splitk_floats);
+    NtProduct q = p;
+    if (!(ldw == K && nt_planes_width(K))) q.w_hi = q.w_lo = nullptr;
+    return launch_gemm_nt_bf16x3(q, st, splitk);
+  }
+  if (p.x_index != nullptr) {
+    set_error("gemm_nt: indexed rows run on the split-bf16 kernel only");
+    return DRIN_E_UNSUPPORTED;
   }
   if (precision == DRIN_PREC_BF16X3 || precision == DRIN_PREC_BF16X3_ALL) precision = DRIN_PREC_F32;
   DRIN_TRY(check_precision(precision, "gemm_nt"));
@@ -571,9 +577,9 @@ int launch_gemm_nt(const float* x, int64_t ldx, const float* w, int64_t ldw, con
     set_error("gemm_nt: K=%d must be a multiple of 4", K);
     return DRIN_E_SHAPE;
   }
-  if (gemv_fits(x, ldx, w, ldw, M, K)) return launch_gemv(x, ldx, w, ldw, bias, y, ldy, M, N, K, accumulate, st);
-  if (small_splitk_fits(M, N, K, ldy, y, splitk, splitk_floats))
-    return launch_small_splitk<false>(x, ldx, w, ldw, bias, y, ldy, M, N, K, accumulate, splitk, splitk_floats, st, "gemm_nt");
+  if (gemv_fits(x, ldx, w, ldw, M, K)) return launch_gemv(p, st);
+  if (small_splitk_fits(M, N, K, ldy, y, splitk))
+    return launch_small_splitk<false>(x, ldx, w, ldw, bias, y, ldy, M, N, K, accumulate, splitk, st, "gemm_nt");
   // mention-sized problems (a few hundred rows): 64 x 64 tiles give 4x the workgroups of 128 x 128 and
   // keep more of the chip busy on what is a latency-bound launch
   if (M <= kMentionSizedMaxRows)
@@ -583,20 +589,17 @@ int launch_gemm_nt(const float* x, int64_t ldx, const float* w, int64_t ldw, con
                                         "gemm_nt");
 }
 
-int launch_gemm_nt_pair(const NtProduct& a, const NtProduct& b, int precision, hipStream_t st, float* splitk, size_t splitk_floats) {
-  const NtProduct* two[2] = {&a, &b};
-  bool grouped = splitk != nullptr;
-  for (const NtProduct* q : two)
-    grouped = grouped && gemm_nt_f32_group_fits(q->x, q->ldx, q->w, q->ldw, q->y, q->ldy, q->rows, q->n_out, q->k_red, precision);
-  if (grouped && small_splitk_pair_floats((size_t)a.rows, (size_t)a.n_out, (size_t)b.rows, (size_t)b.n_out) <= splitk_floats) {
+int launch_gemm_nt_pair(const NtProduct& a, const NtProduct& b, int precision, hipStream_t st, GemmScratch splitk) {
+  const bool grouped = splitk.p != nullptr && !a.accumulate && !b.accumulate && gemm_nt_f32_group_fits(a, precision) &&
+                       gemm_nt_f32_group_fits(b, precision);
+  if (grouped && small_splitk_pair_floats((size_t)a.rows, (size_t)a.n_out, (size_t)b.rows, (size_t)b.n_out) <= splitk.floats) {
     F32GemmGroup g;
-    for (const NtProduct* q : two) DRIN_TRY(g.add_nt(q->x, q->ldx, q->w, q->ldw, q->bias, q->y, q->ldy, q->rows, q->n_out, q->k_red));
-    return launch_gemm_nt_f32_group(g, st, splitk, splitk_floats);
+    DRIN_TRY(g.add_nt(a));
+    DRIN_TRY(g.add_nt(b));
+    return launch_gemm_nt_f32_group(g, st, splitk);
   }
-  for (const NtProduct* q : two)
-    DRIN_TRY(launch_gemm_nt(q->x, q->ldx, q->w, q->ldw, q->bias, q->y, q->ldy, q->rows, q->n_out, q->k_red, false, precision, st, splitk,
-                            splitk_floats, q->planes));
-  return DRIN_OK;
+  DRIN_TRY(launch_gemm_nt(a, precision, st, splitk));
+  return launch_gemm_nt(b, precision, st, splitk);
 }
 
 bool gemm_nn_takes_bf16x3(int precision, int64_t M, int N, int K) {
@@ -604,8 +607,12 @@ bool gemm_nn_takes_bf16x3(int precision, int64_t M, int N, int K) {
   return (precision == DRIN_PREC_BF16X3 || precision == DRIN_PREC_BF16X3_ALL) && M >= 1024 && (K % 32) == 0 && (N % 4) == 0;
 }
 
-int launch_gemm_nn(const float* x, int64_t ldx, const float* w, int64_t ldw, float* y, int64_t ldy, int64_t M, int N,
-                   int K, bool accumulate, int precision, hipStream_t st, float* splitk, size_t splitk_floats, const WtForms& wt) {
+int launch_gemm_nn(const NnProduct& p, int precision, hipStream_t st, GemmScratch splitk, const WtForms& wt) {
+  const float *x = p.dy.p, *w = p.w.p;
+  float* const y = p.dx;
+  const int64_t ldx = p.dy.ld, ldw = p.w.ld, ldy = p.lddx, M = p.rows;
+  const int N = p.n_out, K = p.k_red;
+  const bool accumulate = p.accumulate;
   // y[m, n] = sum_k x[m, k] * w[k, n]: b(n, k) = w[k * ldw + n] is k-major
   if (gemm_nn_takes_bf16x3(precision, M, N, K)) {
     // (the NT kernel notes its own route: the dX record takes it from there)
@@ -617,15 +624,13 @@ int launch_gemm_nn(const float* x, int64_t ldx, const float* w, int64_t ldw, flo
       note_wgrad_gemm_launch(nt.work_items);
       return rc;
     };
-    if (wt.planes != nullptr) {
-      const __bf16* hi = reinterpret_cast<const __bf16*>(wt.planes);
-      return note_nn(DRIN_WGRAD_WT_PLANES, launch_gemm_nt_bf16x3(x, ldx, nullptr, K, nullptr, y, ldy, M, N, K, st, hi, hi + (size_t)N * K,
-                                                                accumulate, wt.tail, wt.tail_floats));
-    }
-    if (wt.scratch != nullptr && ldw == N && wt.scratch_floats >= (size_t)N * K) {
-      DRIN_TRY(launch_transpose(w, wt.scratch, K, N, st));
-      return note_nn(DRIN_WGRAD_WT_F32_SCRATCH, launch_gemm_nt_bf16x3(x, ldx, wt.scratch, K, nullptr, y, ldy, M, N, K, st, nullptr, nullptr,
-                                                                     accumulate, wt.tail, wt.tail_floats));
+    NtProduct nt{p.dy, {nullptr, K}, nullptr, y, ldy, M, N, K};   // against w^T [N][K]
+    nt.accumulate = accumulate;
+    if (wt.planes != nullptr) return note_nn(DRIN_WGRAD_WT_PLANES, launch_gemm_nt_bf16x3(nt.with_planes(wt.planes), st, wt.tail));
+    if (wt.scratch.p != nullptr && ldw == N && wt.scratch.floats >= (size_t)N * K) {
+      DRIN_TRY(launch_transpose(w, wt.scratch.p, K, N, st));
+      nt.w.p = wt.scratch.p;
+      return note_nn(DRIN_WGRAD_WT_F32_SCRATCH, launch_gemm_nt_bf16x3(nt, st, wt.tail));
     }
   }
   if (drin_wgrad_route* r = wgrad_route()) r->nn_wt_form = DRIN_WGRAD_WT_NONE, r->nn_accumulate = accumulate;
@@ -636,8 +641,8 @@ int launch_gemm_nn(const float* x, int64_t ldx, const float* w, int64_t ldw, flo
     set_error("gemm_nn: K=%d and N=%d must be multiples of 4", K, N);
     return DRIN_E_SHAPE;
   }
-  if (small_splitk_fits(M, N, K, ldy, y, splitk, splitk_floats))
-    return launch_small_splitk<true>(x, ldx, w, ldw, nullptr, y, ldy, M, N, K, accumulate, splitk, splitk_floats, st, "gemm_nn");
+  if (small_splitk_fits(M, N, K, ldy, y, splitk))
+    return launch_small_splitk<true>(x, ldx, w, ldw, nullptr, y, ldy, M, N, K, accumulate, splitk, st, "gemm_nn");
   if (M <= kMentionSizedMaxRows)
     return launch<64, 64, false, true>(x, ldx, w, ldw, nullptr, y, ldy, M, N, K, 1, accumulate ? GEMM_ACCUMULATE : 0, st,
                                        "gemm_nn");
@@ -645,17 +650,18 @@ int launch_gemm_nn(const float* x, int64_t ldx, const float* w, int64_t ldw, flo
                                        "gemm_nn");
 }
 
-int F32GemmGroup::add_tn(const float* a, int64_t lda, const float* b, int64_t ldb, float* y, int64_t ldy, int64_t M, int N, int K) {
-  if (y == nullptr || M <= 0 || N <= 0 || K <= 0) return DRIN_OK;
-  if ((N % 4) || (K % 4) || M > kMentionSizedMaxRows || !aligned16(a) || !aligned16(b) || (lda % 4) || (ldb % 4)) {
-    set_error("gemm_tn group: M=%lld N=%d K=%d outside the mention-sized kernel's contract", (long long)M, N, K);
+int F32GemmGroup::add_tn(const TnProduct& p) {
+  if (p.dw == nullptr || p.rows <= 0 || p.n_out <= 0 || p.k_red <= 0) return DRIN_OK;
+  if ((p.n_out % 4) || (p.k_red % 4) || p.rows > kMentionSizedMaxRows || !aligned16(p.dy.p) || !aligned16(p.x.p) || (p.dy.ld % 4) ||
+      (p.x.ld % 4)) {
+    set_error("gemm_tn group: M=%lld N=%d K=%d outside the mention-sized kernel's contract", (long long)p.rows, p.n_out, p.k_red);
     return DRIN_E_SHAPE;
   }
   if (n == MAX) {
     set_error("internal: more than %d products in one exact-fp32 group", MAX);
     return DRIN_E_SHAPE;
   }
-  item[n++] = {a, lda, b, ldb, y, ldy, M, N, K};
+  item[n++] = p;
   return DRIN_OK;
 }
 
@@ -663,7 +669,7 @@ int F32GemmGroup::add_tn(const float* a, int64_t lda, const float* b, int64_t ld
 // slices of the reduction), all items in one launch.  A product that is alone on its destination and has one slice adds
 // to it in place (one workgroup per output tile: no race); any other stores its slices to the scratch and the slice sum
 // adds them in order - two products of one destination as two segments of one entry.
-int launch_gemm_tn_f32_group(const F32GemmGroup& grp, hipStream_t st, float* scratch, size_t scratch_floats, SliceSum* defer) {
+int launch_gemm_tn_f32_group(const F32GemmGroup& grp, hipStream_t st, GemmScratch scratch, SliceSum* defer) {
   if (grp.n == 0) return DRIN_OK;
   GroupArgs ga;
   ga.n = grp.n;
@@ -672,38 +678,40 @@ int launch_gemm_tn_f32_group(const F32GemmGroup& grp, hipStream_t st, float* scr
   unsigned items = 0;
   size_t used = 0;
   for (int i = 0; i < grp.n; ++i) {
-    const auto& it = grp.item[i];
+    const TnProduct& it = grp.item[i];
+    const int64_t M = it.rows;
+    const int N = it.n_out, K = it.k_red;
     // add_tn never stores an empty product; an item with a non-positive extent can only be a caller's slip (round 3's staged
     // backward once handed over value-initialised items past a group it had already flushed: M == 0 made kps 0 and the next
     // line's division raised SIGFPE on the host) - refused, never divided by
-    if (it.M <= 0 || it.N <= 0 || it.K <= 0 || it.M > kMentionSizedMaxRows || it.a == nullptr || it.b == nullptr || it.y == nullptr) {
+    if (M <= 0 || N <= 0 || K <= 0 || M > kMentionSizedMaxRows || it.dy.p == nullptr || it.x.p == nullptr || it.dw == nullptr) {
       set_error("gemm_tn group: item %d of %d has M=%lld N=%d K=%d (or a NULL operand) - outside [1, 2048] reduction rows", i,
-                grp.n, (long long)it.M, it.N, it.K);
+                grp.n, (long long)M, N, K);
       return DRIN_E_SHAPE;
     }
-    int splits = small_tn_slices(it.M);
-    const int kps = (int)(cdiv(cdiv(it.M, splits), BK) * BK);
-    splits = (int)cdiv(it.M, kps);
+    int splits = small_tn_slices(M);
+    const int kps = (int)(cdiv(cdiv(M, splits), BK) * BK);
+    splits = (int)cdiv(M, kps);
     bool shared = false;   // another product of this launch adds to the same destination
-    for (int j = 0; j < grp.n; ++j) shared = shared || (j != i && grp.item[j].y == it.y);
+    for (int j = 0; j < grp.n; ++j) shared = shared || (j != i && grp.item[j].dw == it.dw);
     const bool in_place = splits == 1 && !shared;
     auto& P = ga.p[i];
     // the kernel's (M, N, K) are (output rows, output columns, reduction length) = (N, K, M) of the product
-    P.a = it.a, P.b = it.b, P.lda = it.lda, P.ldb = it.ldb;
-    P.M = it.N, P.N = it.K, P.K = (int)it.M, P.k_per_split = kps;
+    P.a = it.dy.p, P.b = it.x.p, P.lda = it.dy.ld, P.ldb = it.x.ld;
+    P.M = N, P.N = K, P.K = (int)M, P.k_per_split = kps;
     if (in_place) {
-      P.c = it.y, P.ldc = it.ldy, P.flags = GEMM_ACCUMULATE, P.part_stride = 0;
+      P.c = it.dw, P.ldc = it.lddw, P.flags = GEMM_ACCUMULATE, P.part_stride = 0;
     } else {
-      const size_t need = (size_t)splits * it.N * it.K;
-      if (scratch == nullptr || !aligned16(scratch) || used + need > scratch_floats) {
-        set_error("gemm_tn group: %zu floats of slice scratch, %zu needed", scratch_floats, used + need);
+      const size_t need = (size_t)splits * N * K;
+      if (scratch.p == nullptr || !aligned16(scratch.p) || used + need > scratch.floats) {
+        set_error("gemm_tn group: %zu floats of slice scratch, %zu needed", scratch.floats, used + need);
         return DRIN_E_WORKSPACE;
       }
-      P.c = scratch + used, P.ldc = it.K, P.flags = GEMM_PARTIAL, P.part_stride = (int64_t)it.N * it.K;
-      DRIN_TRY(sums.add(it.y, it.ldy, it.N, it.K, scratch + used, splits));
+      P.c = scratch.p + used, P.ldc = K, P.flags = GEMM_PARTIAL, P.part_stride = (int64_t)N * K;
+      DRIN_TRY(sums.add(it.dw, it.lddw, N, K, scratch.p + used, splits));
       used += (need + 3) & ~(size_t)3;
     }
-    P.col_tiles = (unsigned)cdiv(it.K, 64), P.row_tiles = (unsigned)cdiv(it.N, 64), P.first = items;
+    P.col_tiles = (unsigned)cdiv(K, 64), P.row_tiles = (unsigned)cdiv(N, 64), P.first = items;
     items += P.col_tiles * P.row_tiles * (unsigned)splits;
   }
   const size_t lds = sizeof(float) * 2 * (Tile<64>::FLOATS + Tile<64>::FLOATS);
@@ -714,7 +722,7 @@ int launch_gemm_tn_f32_group(const F32GemmGroup& grp, hipStream_t st, float* scr
     KernelTimer timer(DRIN_KC_GEMM, st);
     for (int i = 0; i < grp.n; ++i) {
       const auto& P = ga.p[i];
-      note_wgrad_product(P.a, P.b, grp.item[i].y, DRIN_WGRAD_KERNEL_TN_F32_SMALL, (int)cdiv(P.K, P.k_per_split), P.k_per_split,
+      note_wgrad_product(P.a, P.b, grp.item[i].dw, DRIN_WGRAD_KERNEL_TN_F32_SMALL, (int)cdiv(P.K, P.k_per_split), P.k_per_split,
                          P.flags == GEMM_ACCUMULATE, false);
     }
     note_wgrad_gemm_launch(items);
@@ -724,22 +732,24 @@ int launch_gemm_tn_f32_group(const F32GemmGroup& grp, hipStream_t st, float* scr
   return defer != nullptr ? DRIN_OK : launch_slice_sum(local, st);
 }
 
-TnKernel gemm_tn_kernel(int precision, const float* a, int64_t lda, const float* b, int64_t ldb, const float* y, int64_t ldy,
-                        int64_t M, int N, int K, const float* scratch, size_t scratch_floats) {
-  if ((precision == DRIN_PREC_BF16X3 || precision == DRIN_PREC_BF16X3_ALL) && gemm_tn_bf16x3_fits(lda, ldb, M, N, K, a, b) &&
-      gemm_tn_bf16x3_scratch_ok(y, ldy, N, K, scratch, scratch_floats))
+TnKernel gemm_tn_kernel(const TnProduct& p, int precision, GemmScratch scratch) {
+  if ((precision == DRIN_PREC_BF16X3 || precision == DRIN_PREC_BF16X3_ALL) && gemm_tn_bf16x3_fits(p) && gemm_tn_bf16x3_scratch_ok(p, scratch))
     return TN_BF16X3;
-  return M <= kMentionSizedMaxRows ? TN_F32_SMALL : TN_F32_LARGE;   // mention-sized reductions (a few hundred rows): 64 x 64 tiles, 4x the workgroups
+  return p.rows <= kMentionSizedMaxRows ? TN_F32_SMALL : TN_F32_LARGE;   // mention-sized reductions (a few hundred rows): 64 x 64 tiles, 4x the workgroups
 }
 
-int launch_gemm_tn(const float* a, int64_t lda, const float* b, int64_t ldb, float* y, int64_t ldy, int64_t M, int N,
-                   int K, int precision, hipStream_t st, float* scratch, size_t scratch_floats) {
+int launch_gemm_tn(const TnProduct& p, int precision, hipStream_t st, GemmScratch scratch) {
+  const float *a = p.dy.p, *b = p.x.p;
+  float* const y = p.dw;
+  const int64_t lda = p.dy.ld, ldb = p.x.ld, ldy = p.lddw, M = p.rows;
+  const int N = p.n_out, K = p.k_red;
+  if (y == nullptr) return DRIN_OK;   // a gradient nobody asked for (as TnGroup::add, F32GemmGroup::add_tn)
   // y[n, k] += sum_m a[m, n] * b[m, k]: both operands k-major over the reduction index m.
   // The reduction runs over all B*N pairs while the output is one weight matrix, so it is split over m: the slices
   // store their tiles to the scratch and are added to y in order (launch_splitk_reduce) - reproducible bit for bit.
   // Without scratch one workgroup per output tile walks the whole reduction and adds to y in place.
-  const TnKernel kernel = gemm_tn_kernel(precision, a, lda, b, ldb, y, ldy, M, N, K, scratch, scratch_floats);
-  if (kernel == TN_BF16X3) return launch_gemm_tn_bf16x3(a, lda, b, ldb, y, ldy, M, N, K, st, scratch, scratch_floats);
+  const TnKernel kernel = gemm_tn_kernel(p, precision, scratch);
+  if (kernel == TN_BF16X3 || p.x_index != nullptr) return launch_gemm_tn_bf16x3(p, st, scratch);   // (indexed rows: that kernel or its refusal)
   if (precision == DRIN_PREC_BF16X3 || precision == DRIN_PREC_BF16X3_ALL) precision = DRIN_PREC_F32;
   DRIN_TRY(check_precision(precision, "gemm_tn"));
   if ((N % 4) || (K % 4)) {
@@ -762,11 +772,11 @@ int launch_gemm_tn(const float* a, int64_t lda, const float* b, int64_t ldb, flo
     if (splits > max_splits) splits = max_splits;
   }
   const size_t tile_floats = (size_t)N * K;
-  const bool can_slice = scratch != nullptr && aligned16(scratch) && aligned16(y) && (ldy % 4) == 0;
+  const bool can_slice = scratch.p != nullptr && aligned16(scratch.p) && aligned16(y) && (ldy % 4) == 0;
   if (!can_slice) splits = 1;
-  while (splits > 1 && (size_t)splits * tile_floats > scratch_floats) --splits;
+  while (splits > 1 && (size_t)splits * tile_floats > scratch.floats) --splits;
   if (splits < 1) splits = 1;
-  float* c = splits > 1 ? scratch : y;
+  float* c = splits > 1 ? scratch.p : y;
   const int64_t ldc = splits > 1 ? K : ldy;
   const int flags = splits > 1 ? GEMM_PARTIAL : GEMM_ACCUMULATE;
   int used = 1, rows_per_slice = 0;
@@ -779,34 +789,36 @@ int launch_gemm_tn(const float* a, int64_t lda, const float* b, int64_t ldb, flo
   }
   note_wgrad_product(a, b, y, small ? DRIN_WGRAD_KERNEL_TN_F32_SMALL : DRIN_WGRAD_KERNEL_TN_F32_LARGE, used, rows_per_slice, splits == 1, false,
                      /*launch=*/-1);
-  if (splits > 1) return launch_splitk_reduce(scratch, used, (int64_t)tile_floats, nullptr, y, ldy, N, K, true, st);
+  if (splits > 1) return launch_splitk_reduce(scratch.p, used, (int64_t)tile_floats, nullptr, y, ldy, N, K, true, st);
   return DRIN_OK;
 }
 
-// ---- the weight and bias gradients of one backward pass (WeightGradPass, internal.h) ----------------------------------
-int WeightGradPass::add(const float* dy, int64_t lddy, const float* x, int64_t ldx, float* dw, int64_t lddw, int64_t rows,
-                        int n_out, int k_red, const int64_t* x_index, float* db) {
-  const TnKernel kernel = gemm_tn_kernel(prec, dy, lddy, x, ldx, dw, lddw, rows, n_out, k_red, tn.p, tn.floats);
-  const bool grouped = dw != nullptr && !vec && kernel == TN_BF16X3;
-  const bool db_rides = grouped && lddy == n_out;   // the group sums the columns of the rows it stages
-  if (!db_rides) DRIN_TRY(bias_sums.add(dy, db, rows, n_out, lddy));   // (no-op for db == NULL)
-  if (dw == nullptr) return DRIN_OK;
+// ---- the weight and bias gradients of one backward pass (WeightGradPass, gemm.h) ----------------------------------
+int WeightGradPass::add(const TnProduct& product) {
+  TnProduct p = product;
+  const TnKernel kernel = gemm_tn_kernel(p, prec, tn);
+  const bool grouped = p.dw != nullptr && !vec && kernel == TN_BF16X3;
+  if (!(grouped && p.dy.ld == p.n_out)) {   // (else db rides: the group sums the columns of the rows it stages)
+    DRIN_TRY(bias_sums.add(p.dy.p, p.db, p.rows, p.n_out, p.dy.ld));   // (no-op for db == NULL)
+    p.db = nullptr;
+  }
+  if (p.dw == nullptr) return DRIN_OK;
   if (grouped) {
     if (dw_group.n == TnGroup::MAX) {   // deeper than three layers: the group goes in instalments
-      DRIN_TRY(launch_gemm_tn_group(dw_group, st, tn.p, tn.floats));
+      DRIN_TRY(launch_gemm_tn_group(dw_group, st, tn));
       dw_group = TnGroup(), layer_group = 0;
     }
-    return dw_group.add(dy, lddy, x, ldx, dw, lddw, rows, n_out, k_red, x_index, db_rides ? db : nullptr);
+    return dw_group.add(p);
   }
-  if (x_index != nullptr) return launch_gemm_tn_bf16x3(dy, lddy, x, ldx, dw, lddw, rows, n_out, k_red, st, tn.p, tn.floats, x_index);
-  if (!vec && kernel == TN_F32_SMALL && (n_out % 4) == 0 && (k_red % 4) == 0 && aligned16(dw) && (lddw % 4) == 0) {   // (SliceSum's contract)
+  if (p.x_index != nullptr) return launch_gemm_tn_bf16x3(p, st, tn);
+  if (!vec && kernel == TN_F32_SMALL && (p.n_out % 4) == 0 && (p.k_red % 4) == 0 && aligned16(p.dw) && (p.lddw % 4) == 0) {   // (SliceSum's contract)
     if (dw_small.n == F32GemmGroup::MAX) {
-      DRIN_TRY(launch_gemm_tn_f32_group(dw_small, st, small.p, small.floats));
+      DRIN_TRY(launch_gemm_tn_f32_group(dw_small, st, small));
       dw_small = F32GemmGroup(), layer_small = 0;
     }
-    return dw_small.add_tn(dy, lddy, x, ldx, dw, lddw, rows, n_out, k_red);
+    return dw_small.add_tn(p);
   }
-  return launch_gemm_tn(dy, lddy, x, ldx, dw, lddw, rows, n_out, k_red, prec, st, tn.p, tn.floats);
+  return launch_gemm_tn(p, prec, st, tn);
 }
 
 // The split reductions left at the end of the pass - the bias column sums, the mention-sized and the pair-sized weight gradients -
@@ -820,8 +832,8 @@ int WeightGradPass::add(const float* dy, int64_t lddy, const float* x, int64_t l
 int WeightGradPass::finish(void* layers_ready_event) {
   auto part = [this](const ColsumBatch& cs, const F32GemmGroup& fg, const TnGroup& tg, SliceSum sums) -> int {
     DRIN_TRY(launch_colsum_batch(cs, st, colsum.p, colsum.floats, &sums));
-    DRIN_TRY(launch_gemm_tn_f32_group(fg, st, small.p, small.floats, &sums));
-    DRIN_TRY(launch_gemm_tn_group(tg, st, tn.p, tn.floats, &sums));
+    DRIN_TRY(launch_gemm_tn_f32_group(fg, st, small, &sums));
+    DRIN_TRY(launch_gemm_tn_group(tg, st, tn, &sums));
     return launch_slice_sum(sums, st);
   };
   if (layers_ready_event == nullptr) return part(bias_sums, dw_small, dw_group, ln_sums);
@@ -844,8 +856,8 @@ size_t small_group_worst_case_floats(const drin_config& c, size_t tn_part_floats
   alignas(16) static float at[4];   // the operands' and the scratch's place: the workspace is 16-byte aligned, rows contiguous
   size_t need = 0;
   auto product = [&](size_t rows, size_t n_out, size_t k_red) {
-    if (rows >= 1 && gemm_tn_kernel(c.precision, at, (int64_t)n_out, at, (int64_t)k_red, at, (int64_t)k_red, (int64_t)rows, (int)n_out,
-                                    (int)k_red, at, tn_part_floats) == TN_F32_SMALL)
+    const TnProduct p{{at, (int64_t)n_out}, {at, (int64_t)k_red}, at, (int64_t)k_red, (int64_t)rows, (int)n_out, (int)k_red};
+    if (rows >= 1 && gemm_tn_kernel(p, c.precision, {at, tn_part_floats}) == TN_F32_SMALL)
       need += (size_t)small_tn_slices((int64_t)rows) * n_out * k_red;
   };
   for (int l = c.num_layers - 1; l >= 0; --l) {

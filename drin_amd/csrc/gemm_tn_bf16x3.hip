@@ -118,7 +118,7 @@ struct TransposeStager {
   }
 };
 
-// One launch runs a GROUP of such products (TnGroup, internal.h: the pair-sized weight gradients of a backward pass).
+// One launch runs a GROUP of such products (TnGroup, gemm.h: the pair-sized weight gradients of a backward pass).
 // grid: 1-D; a problem's work items are (slice of the reduction, output tile n-tile major), tile fastest; problems in order.
 struct Problem {
   const float* a;
@@ -271,35 +271,34 @@ __global__ void __launch_bounds__(THREADS, 1) k_gemm_tn_bf16x3(const GroupArgs g
 
 }  // namespace x3tn
 
-bool gemm_tn_bf16x3_fits(int64_t lda, int64_t ldb, int64_t M, int N, int K, const void* a, const void* b) {
-  return M >= 1024 && N >= 128 && K >= 128 && (N % 4) == 0 && (K % 4) == 0 && (lda % 4) == 0 && (ldb % 4) == 0 &&
-         aligned16(a) && aligned16(b);
+bool gemm_tn_bf16x3_fits(const TnProduct& p) {
+  return p.rows >= 1024 && p.n_out >= 128 && p.k_red >= 128 && (p.n_out % 4) == 0 && (p.k_red % 4) == 0 && (p.dy.ld % 4) == 0 &&
+         (p.x.ld % 4) == 0 && aligned16(p.dy.p) && aligned16(p.x.p);
 }
 
-int TnGroup::add(const float* a, int64_t lda, const float* b, int64_t ldb, float* y, int64_t ldy, int64_t M, int N, int K,
-                 const int64_t* b_index, float* colsum) {
-  if (y == nullptr || M <= 0 || N <= 0 || K <= 0) return DRIN_OK;
-  if (!gemm_tn_bf16x3_fits(lda, ldb, M, N, K, a, b)) {
-    set_error("gemm_tn_bf16x3: shape M=%lld N=%d K=%d / alignment outside the kernel's contract", (long long)M, N, K);
+int TnGroup::add(const TnProduct& p) {
+  if (p.dw == nullptr || p.rows <= 0 || p.n_out <= 0 || p.k_red <= 0) return DRIN_OK;
+  if (!gemm_tn_bf16x3_fits(p)) {
+    set_error("gemm_tn_bf16x3: shape M=%lld N=%d K=%d / alignment outside the kernel's contract", (long long)p.rows, p.n_out, p.k_red);
     return DRIN_E_SHAPE;
   }
   if (n == MAX) {
     set_error("internal: more than %d weight-gradient products in one group", MAX);
     return DRIN_E_SHAPE;
   }
-  item[n++] = {a, lda, b, ldb, y, ldy, M, N, K, b_index, colsum};
+  item[n++] = p;
   return DRIN_OK;
 }
 
-bool gemm_tn_bf16x3_scratch_ok(const float* y, int64_t ldy, int N, int K, const float* scratch, size_t scratch_floats) {
-  return scratch != nullptr && aligned16(scratch) && aligned16(y) && (ldy % 4) == 0 && scratch_floats >= (size_t)N * K;
+bool gemm_tn_bf16x3_scratch_ok(const TnProduct& p, GemmScratch scratch) {
+  return scratch.p != nullptr && aligned16(scratch.p) && aligned16(p.dw) && (p.lddw % 4) == 0 && scratch.floats >= (size_t)p.n_out * p.k_red;
 }
 
-static int64_t tn_slices_of(const TnGroup::Item& it, int64_t target, int64_t* rows_out) {   // equal slices of one product
-  int64_t slices = cdiv(it.M, target);
-  const int64_t rows = cdiv(cdiv(it.M, slices), x3tn::BK) * x3tn::BK;
+static int64_t tn_slices_of(const TnProduct& it, int64_t target, int64_t* rows_out) {   // equal slices of one product
+  int64_t slices = cdiv(it.rows, target);
+  const int64_t rows = cdiv(cdiv(it.rows, slices), x3tn::BK) * x3tn::BK;
   if (rows_out) *rows_out = rows;
-  return cdiv(it.M, rows);
+  return cdiv(it.rows, rows);
 }
 
 // One workgroup per CU in all (the 128 KiB tile buffers allow one per CU at a time): every extra slice adds a pipeline
@@ -313,8 +312,8 @@ static int64_t tn_group_target(const TnGroup& grp, size_t scratch_floats) {
   int64_t work = 0, longest = 0;
   for (int i = 0; i < grp.n; ++i) {
     const auto& it = grp.item[i];
-    work += cdiv(it.N, x3tn::TILE) * cdiv(it.K, x3tn::TILE) * it.M;
-    longest = it.M > longest ? it.M : longest;
+    work += cdiv(it.n_out, x3tn::TILE) * cdiv(it.k_red, x3tn::TILE) * it.rows;
+    longest = it.rows > longest ? it.rows : longest;
   }
   int64_t target = cdiv(cdiv(work, 256), x3tn::BK) * x3tn::BK;
   if (target < 4 * x3tn::BK) target = 4 * x3tn::BK;
@@ -324,21 +323,21 @@ static int64_t tn_group_target(const TnGroup& grp, size_t scratch_floats) {
     for (int i = 0; i < grp.n; ++i) {
       const auto& it = grp.item[i];
       const int64_t sl = tn_slices_of(it, target, nullptr);
-      wgs += cdiv(it.N, x3tn::TILE) * cdiv(it.K, x3tn::TILE) * sl;
-      part += (size_t)sl * it.N * ((size_t)it.K + (it.colsum ? 1 : 0));
+      wgs += cdiv(it.n_out, x3tn::TILE) * cdiv(it.k_red, x3tn::TILE) * sl;
+      part += (size_t)sl * it.n_out * ((size_t)it.k_red + (it.db ? 1 : 0));
     }
     if ((wgs <= 256 && part <= scratch_floats) || target >= longest) break;
   }
   return target;
 }
 
-int launch_gemm_tn_group(const TnGroup& grp, hipStream_t st, float* scratch, size_t scratch_floats, SliceSum* defer) {
+int launch_gemm_tn_group(const TnGroup& grp, hipStream_t st, GemmScratch scratch, SliceSum* defer) {
   if (grp.n == 0) return DRIN_OK;
-  if (scratch == nullptr || !aligned16(scratch)) {
+  if (scratch.p == nullptr || !aligned16(scratch.p)) {
     set_error("gemm_tn_bf16x3: the slice scratch is NULL or not 16-byte aligned");
     return DRIN_E_WORKSPACE;
   }
-  const int64_t target = tn_group_target(grp, scratch_floats);
+  const int64_t target = tn_group_target(grp, scratch.floats);
   // products of one destination next to one another (their slices: segments of one slice-sum entry, added in this order)
   SliceSum local;
   SliceSum& sums = defer != nullptr ? *defer : local;
@@ -351,24 +350,24 @@ int launch_gemm_tn_group(const TnGroup& grp, hipStream_t st, float* scratch, siz
     int64_t rows = 0;
     const int64_t slices = tn_slices_of(it, target, &rows);
     auto& P = ga.p[i];
-    P.a = it.a, P.b = it.b, P.b_index = it.b_index;
-    P.lda = it.lda, P.ldb = it.ldb, P.M = it.M, P.rows_per_slice = rows;
-    P.N = it.N, P.K = it.K, P.k_tiles = (int)cdiv(it.K, x3tn::TILE), P.tiles = (int)cdiv(it.N, x3tn::TILE) * P.k_tiles;
+    P.a = it.dy.p, P.b = it.x.p, P.b_index = it.x_index;
+    P.lda = it.dy.ld, P.ldb = it.x.ld, P.M = it.rows, P.rows_per_slice = rows;
+    P.N = it.n_out, P.K = it.k_red, P.k_tiles = (int)cdiv(it.k_red, x3tn::TILE), P.tiles = (int)cdiv(it.n_out, x3tn::TILE) * P.k_tiles;
     P.first = (unsigned)items, P.slices = (int)slices;
-    P.partial = scratch + part;
+    P.partial = scratch.p + part;
     items += slices * P.tiles;
-    part += (size_t)slices * it.N * it.K;
+    part += (size_t)slices * it.n_out * it.k_red;
     P.colsum_partial = nullptr;
-    if (it.colsum != nullptr) {
-      P.colsum_partial = scratch + part;
-      part += (size_t)slices * it.N;
+    if (it.db != nullptr) {
+      P.colsum_partial = scratch.p + part;
+      part += (size_t)slices * it.n_out;
     }
-    if (part > scratch_floats) {
-      set_error("gemm_tn_bf16x3: %zu floats of slice scratch, more than %zu needed", scratch_floats, part);
+    if (part > scratch.floats) {
+      set_error("gemm_tn_bf16x3: %zu floats of slice scratch, more than %zu needed", scratch.floats, part);
       return DRIN_E_WORKSPACE;
     }
-    DRIN_TRY(sums.add(it.y, it.ldy, it.N, it.K, P.partial, (int)slices));
-    if (it.colsum != nullptr) DRIN_TRY(sums.add(it.colsum, it.N, 1, it.N, P.colsum_partial, (int)slices));
+    DRIN_TRY(sums.add(it.dw, it.lddw, it.n_out, it.k_red, P.partial, (int)slices));
+    if (it.db != nullptr) DRIN_TRY(sums.add(it.db, it.n_out, 1, it.n_out, P.colsum_partial, (int)slices));
   }
   if (items > (int64_t)1 << 30) {
     set_error("gemm_tn_bf16x3: %lld work items exceed the grid limit", (long long)items);
@@ -382,8 +381,8 @@ int launch_gemm_tn_group(const TnGroup& grp, hipStream_t st, float* scratch, siz
   {
     KernelTimer timer(DRIN_KC_GEMM_X3, st);
     for (int i = 0; i < grp.n; ++i)
-      note_wgrad_product(grp.item[i].a, grp.item[i].b, grp.item[i].y, DRIN_WGRAD_KERNEL_TN_BF16X3, ga.p[i].slices, ga.p[i].rows_per_slice,
-                         false, grp.item[i].colsum != nullptr);
+      note_wgrad_product(grp.item[i].dy.p, grp.item[i].x.p, grp.item[i].dw, DRIN_WGRAD_KERNEL_TN_BF16X3, ga.p[i].slices, ga.p[i].rows_per_slice,
+                         false, grp.item[i].db != nullptr);
     note_wgrad_gemm_launch(items);
     hipLaunchKernelGGL(x3tn::k_gemm_tn_bf16x3, dim3((unsigned)items), dim3(x3tn::THREADS), x3tn::LDS_BYTES, st, ga);
     DRIN_CHECK_LAUNCH("k_gemm_tn_bf16x3");
@@ -391,12 +390,12 @@ int launch_gemm_tn_group(const TnGroup& grp, hipStream_t st, float* scratch, siz
   return defer != nullptr ? DRIN_OK : launch_slice_sum(local, st);
 }
 
-int launch_gemm_tn_bf16x3(const float* a, int64_t lda, const float* b, int64_t ldb, float* y, int64_t ldy, int64_t M,
-                          int N, int K, hipStream_t st, float* scratch, size_t scratch_floats, const int64_t* b_index) {
-  if (M <= 0 || N <= 0 || K <= 0) return DRIN_OK;
+int launch_gemm_tn_bf16x3(const TnProduct& p, hipStream_t st, GemmScratch scratch) {
+  if (p.rows <= 0 || p.n_out <= 0 || p.k_red <= 0) return DRIN_OK;
   TnGroup one;
-  DRIN_TRY(one.add(a, lda, b, ldb, y, ldy, M, N, K, b_index));
-  return launch_gemm_tn_group(one, st, scratch, scratch_floats);
+  DRIN_TRY(one.add(p));
+  one.item[0].db = nullptr;   // (the column sums are the groups' business: TnProduct)
+  return launch_gemm_tn_group(one, st, scratch);
 }
 
 }  // namespace drin

@@ -952,7 +952,7 @@ int64_t gemm_p4_whole_tiles(int64_t tiles, int K, bool tail_scratch, size_t tail
   return (int64_t)full;
 }
 
-// A slice of row tiles (RowTiles, internal.h) against the product's own tail split: the slice's first tile in the tile sequence, how
+// A slice of row tiles (RowTiles, gemm.h) against the product's own tail split: the slice's first tile in the tile sequence, how
 // many WHOLE tiles the launch covers and whether the product's tail (K-slices + tail add) belongs to it.  The tail split is always
 // the WHOLE product's, so that every tile is computed the same way whichever launch covers it.
 struct SliceItems {
@@ -978,12 +978,12 @@ static int slice_items(const RowTiles& rows, int64_t row_tiles, int nx, unsigned
 
 // The four-phase pipeline on an fp32 A operand against pre-split weight planes (256 x 256 tiles; DRIN_E_UNSUPPORTED outside
 // its contract: the caller keeps its other kernel).  tail: optional scratch for the tail split, as launch_gemm_nt_bf16x3.
-int launch_gemm_nt_bf16x3_p4(const float* x, int64_t ldx, const void* w_hi, const void* w_lo, int64_t ldw, const float* bias,
-                             float* y, int64_t ldy, int64_t M, int N, int K, hipStream_t st, bool accumulate, float* tail,
-                             size_t tail_floats, RowTiles rows) {
+int launch_gemm_nt_bf16x3_p4(const NtProduct& p, hipStream_t st, GemmScratch tail, RowTiles rows) {
+  const int64_t M = p.rows;
+  const int N = p.n_out, K = p.k_red;
   if (M <= 0 || N <= 0) return DRIN_OK;
-  if (K <= 0 || (K % x3p::BK) || (ldx % 4) || (ldw % 8) || (N % 4) || (ldy % 4) || !aligned16(x) || !aligned16(w_hi) || !aligned16(w_lo) ||
-      !aligned16(y) || (bias != nullptr && !aligned16(bias))) {
+  if (p.x_index != nullptr || K <= 0 || (K % x3p::BK) || (p.x.ld % 4) || (p.w.ld % 8) || (N % 4) || (p.ldy % 4) || !aligned16(p.x.p) ||
+      !aligned16(p.w_hi) || !aligned16(p.w_lo) || !aligned16(p.y) || (p.bias != nullptr && !aligned16(p.bias))) {
     set_error("gemm_bf16x3_p4: shape / alignment outside the kernel's contract");
     return DRIN_E_UNSUPPORTED;
   }
@@ -992,7 +992,7 @@ int launch_gemm_nt_bf16x3_p4(const float* x, int64_t ldx, const void* w_hi, cons
   if (tiles > ((int64_t)1 << 28)) return DRIN_E_UNSUPPORTED;
   unsigned full;
   int ksplit;
-  tail_split_256(tiles, K / x3p::BK, tail, tail_floats, &full, &ksplit);
+  tail_split_256(tiles, K / x3p::BK, tail.p, tail.floats, &full, &ksplit);
   SliceItems sl;
   DRIN_TRY(slice_items(rows, cdiv(M, x3p::BM), nx, full, &sl));
   static DynLdsOptIn opt[2];
@@ -1003,20 +1003,22 @@ int launch_gemm_nt_bf16x3_p4(const float* x, int64_t ldx, const void* w_hi, cons
   {
     KernelTimer timer(DRIN_KC_GEMM_X3, st);
     RouteNote n{DRIN_GEMM_FAMILY_BF16X3_P4, x3p::BM, x3p::BN};
-    n.w_planes = true, n.persist = rows.wgs > 0, n.accumulate = accumulate, n.ksplit = sl.with_tail ? ksplit : 1;
+    n.w_planes = true, n.persist = rows.wgs > 0, n.accumulate = p.accumulate, n.ksplit = sl.with_tail ? ksplit : 1;
     n.tiles = tiles, n.whole_tiles = sl.whole, n.tile0 = sl.tile0, n.work_items = items;
     note_route(n);
-    hipLaunchKernelGGL(kern, dim3(items), dim3(x3p::THREADS), x3p::p4::LDS, st, x, ldx, (const __bf16*)w_hi, (const __bf16*)w_lo, ldw, bias, y,
-                       ldy, M, N, K, accumulate ? 1 : 0, nx, sl.whole, ksplit, tail, sl.tile0);
+    hipLaunchKernelGGL(kern, dim3(items), dim3(x3p::THREADS), x3p::p4::LDS, st, p.x.p, p.x.ld, (const __bf16*)p.w_hi, (const __bf16*)p.w_lo, p.w.ld,
+                       p.bias, p.y, p.ldy, M, N, K, p.accumulate ? 1 : 0, nx, sl.whole, ksplit, tail.p, sl.tile0);
     DRIN_CHECK_LAUNCH("k_gemm_bf16x3_p4");
   }
-  if (ksplit > 1 && sl.with_tail) DRIN_TRY(launch_tail_add_256(tail, y, ldy, M, N, (unsigned)nx, full, (unsigned)tiles - full, ksplit, st));
+  if (ksplit > 1 && sl.with_tail) DRIN_TRY(launch_tail_add_256(tail.p, p.y, p.ldy, M, N, (unsigned)nx, full, (unsigned)tiles - full, ksplit, st));
   return DRIN_OK;
 }
 
 int launch_gemm_x3_planes(const void* a_hi, const void* a_lo, int64_t lda, const void* b_hi, const void* b_lo,
                           int64_t ldb, const float* bias, float* y, int64_t ldy, int64_t M, int N, int K,
-                          hipStream_t st, float* splitk, size_t splitk_floats, RowTiles rows) {
+                          hipStream_t st, GemmScratch scratch, RowTiles rows) {
+  float* const splitk = scratch.p;
+  const size_t splitk_floats = scratch.floats;
   if (M <= 0 || N <= 0) return DRIN_OK;
   const bool sliced = rows.begin != 0 || rows.end >= 0 || rows.wgs != 0;
   const bool a_lo_plane = a_lo != nullptr;  // NULL: A is exact in bf16 (one plane, two MFMAs per tile pair)
@@ -1117,7 +1119,7 @@ int launch_gemm_x3_planes(const void* a_hi, const void* a_lo, int64_t lda, const
   return DRIN_OK;
 }
 
-// ONE fp16 MFMA pass on single fp16 planes (the F16 instantiation of the four-phase kernel): see internal.h
+// ONE fp16 MFMA pass on single fp16 planes (the F16 instantiation of the four-phase kernel): see gemm.h
 bool gemm_f16_planes_fits(const void* a_f16, int64_t lda, const void* b_f16, int64_t ldb, const float* y, int64_t ldy, int64_t M, int N,
                           int K) {
   return cdiv(M, x3p::BM) * cdiv(N, x3p::BN) >= 128 && cdiv(M, x3p::BM) * cdiv(N, x3p::BN) <= ((int64_t)1 << 28) && K > 0 &&
@@ -1126,7 +1128,8 @@ bool gemm_f16_planes_fits(const void* a_f16, int64_t lda, const void* b_f16, int
 }
 
 int launch_gemm_f16_planes(const void* a_f16, int64_t lda, const void* b_f16, int64_t ldb, const float* row_scale, const float* b_scale,
-                           float* y, int64_t ldy, int64_t M, int N, int K, hipStream_t st, float* tail, size_t tail_floats) {
+                           float* y, int64_t ldy, int64_t M, int N, int K, hipStream_t st, GemmScratch tail_scratch) {
+  float* const tail = tail_scratch.p;
   if (M <= 0 || N <= 0) return DRIN_OK;
   if (row_scale == nullptr || b_scale == nullptr || !gemm_f16_planes_fits(a_f16, lda, b_f16, ldb, y, ldy, M, N, K)) {
     set_error("gemm_f16_planes: built for at least half a round of 256 x 256 tiles, K %% 64 == 0, 16-byte aligned planes and both scales");
@@ -1136,7 +1139,7 @@ int launch_gemm_f16_planes(const void* a_f16, int64_t lda, const void* b_f16, in
   const int64_t tiles = cdiv(M, x3p::BM) * nx;
   unsigned full;
   int ksplit;
-  tail_split_256(tiles, K / (2 * x3p::BK), tail, tail_floats, &full, &ksplit);
+  tail_split_256(tiles, K / (2 * x3p::BK), tail, tail_scratch.floats, &full, &ksplit);
   const unsigned items = full + ((unsigned)tiles - full) * (unsigned)ksplit;
   auto kern = x3p::k_gemm_x3_planes_p4<true, true>;
   static DynLdsOptIn opt;

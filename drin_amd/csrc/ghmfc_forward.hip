@@ -83,25 +83,22 @@ int cross_attention_max(const drin_ghmfc_cross_params& W, const float* sa, const
                         float eps, hipStream_t st) {
   const int64_t Ma = (int64_t)Bc * La, Mb = (int64_t)Bc * Lb;
   const int dh = Ea / H;
-  auto gemm = [&](const float* x, int64_t ldx, const float* w, const float* bias, float* y, int64_t ldy, int64_t M, int N, int K) {
-    return launch_gemm_nt(x, ldx, w, K, bias, y, ldy, M, N, K, false, prec, st);
-  };
   // a attends to b: separate q / k / v weights (kdim = vdim = Eb), one in_proj_bias [3 Ea]; K | V side by side
-  DRIN_TRY(gemm(sa, Ea, W.a2b_wq, W.a2b_in_bias, A, Ea, Ma, Ea, Ea));
-  DRIN_TRY(gemm(sb, Eb, W.a2b_wk, W.a2b_in_bias + Ea, KV, 2 * (int64_t)Ea, Mb, Ea, Eb));
-  DRIN_TRY(gemm(sb, Eb, W.a2b_wv, W.a2b_in_bias + 2 * Ea, KV + Ea, 2 * (int64_t)Ea, Mb, Ea, Eb));
+  DRIN_TRY(launch_gemm_nt({{sa, Ea}, {W.a2b_wq, Ea}, W.a2b_in_bias, A, Ea, Ma, Ea, Ea}, prec, st));
+  DRIN_TRY(launch_gemm_nt({{sb, Eb}, {W.a2b_wk, Eb}, W.a2b_in_bias + Ea, KV, 2 * (int64_t)Ea, Mb, Ea, Eb}, prec, st));
+  DRIN_TRY(launch_gemm_nt({{sb, Eb}, {W.a2b_wv, Eb}, W.a2b_in_bias + 2 * Ea, KV + Ea, 2 * (int64_t)Ea, Mb, Ea, Eb}, prec, st));
   DRIN_TRY(launch_attention(AttnCall{A, Ea, KV, 2 * (int64_t)Ea, KV + Ea, 2 * (int64_t)Ea, mb, Bf, Ea, nullptr, Bc, H, La, Lb, dh}, nullptr, st));
-  DRIN_TRY(gemm(Bf, Ea, W.a2b_wo, W.a2b_bo, A, Ea, Ma, Ea, Ea));
+  DRIN_TRY(launch_gemm_nt({{Bf, Ea}, {W.a2b_wo, Ea}, W.a2b_bo, A, Ea, Ma, Ea, Ea}, prec, st));
   DRIN_TRY(launch_layernorm_res(A, nullptr, W.ln0_w, W.ln0_b, A, Ma, Ea, eps, st));
-  DRIN_TRY(gemm(A, Ea, W.a2b_ffn_w, W.a2b_ffn_b, Bf, Ea, Ma, Ea, Ea));
+  DRIN_TRY(launch_gemm_nt({{A, Ea}, {W.a2b_ffn_w, Ea}, W.a2b_ffn_b, Bf, Ea, Ma, Ea, Ea}, prec, st));
   DRIN_TRY(launch_layernorm_res(Bf, A, W.ln1_w, W.ln1_b, A, Ma, Ea, eps, st));
   // the result attends to a: packed in_proj_weight [3 Ea, Ea]; K | V of seq_a are its rows Ea .. 3 Ea, ONE product
-  DRIN_TRY(gemm(A, Ea, W.b2a_in_w, W.b2a_in_bias, Bf, Ea, Ma, Ea, Ea));
-  DRIN_TRY(gemm(sa, Ea, W.b2a_in_w + (int64_t)Ea * Ea, W.b2a_in_bias + Ea, KV, 2 * (int64_t)Ea, Ma, 2 * Ea, Ea));
+  DRIN_TRY(launch_gemm_nt({{A, Ea}, {W.b2a_in_w, Ea}, W.b2a_in_bias, Bf, Ea, Ma, Ea, Ea}, prec, st));
+  DRIN_TRY(launch_gemm_nt({{sa, Ea}, {W.b2a_in_w + (int64_t)Ea * Ea, Ea}, W.b2a_in_bias + Ea, KV, 2 * (int64_t)Ea, Ma, 2 * Ea, Ea}, prec, st));
   DRIN_TRY(launch_attention(AttnCall{Bf, Ea, KV, 2 * (int64_t)Ea, KV + Ea, 2 * (int64_t)Ea, ma, A, Ea, nullptr, Bc, H, La, La, dh}, nullptr, st));
-  DRIN_TRY(gemm(A, Ea, W.b2a_wo, W.b2a_bo, Bf, Ea, Ma, Ea, Ea));
+  DRIN_TRY(launch_gemm_nt({{A, Ea}, {W.b2a_wo, Ea}, W.b2a_bo, Bf, Ea, Ma, Ea, Ea}, prec, st));
   DRIN_TRY(launch_layernorm_res(Bf, nullptr, W.ln2_w, W.ln2_b, Bf, Ma, Ea, eps, st));
-  DRIN_TRY(gemm(Bf, Ea, W.b2a_ffn_w, W.b2a_ffn_b, A, Ea, Ma, Ea, Ea));
+  DRIN_TRY(launch_gemm_nt({{Bf, Ea}, {W.b2a_ffn_w, Ea}, W.b2a_ffn_b, A, Ea, Ma, Ea, Ea}, prec, st));
   DRIN_TRY(launch_layernorm_res(A, Bf, W.ln3_w, W.ln3_b, A, Ma, Ea, eps, st));
   return launch_seq_max(A, pooled, Bc, La, Ea, st);
 }
@@ -135,8 +132,8 @@ int mention_half(const drin_ghmfc_config& c, const drin_ghmfc_batch* bt, const d
                                prec, c.layer_norm_eps, st));
   DRIN_TRY(cross_attention_max(p->v2t, image, nullptr, P, R, text, tmask, L, D, Bc, H, ws + W.a, ws + W.b, ws + W.kv, ws + W.pool_v,
                                prec, c.layer_norm_eps, st));
-  DRIN_TRY(launch_gemm_nt(ws + W.pool_t, D, p->w_text_linear, D, p->b_text_linear, ws + W.tl, D, Bc, D, D, false, prec, st));
-  DRIN_TRY(launch_gemm_nt(ws + W.pool_v, R, p->w_image_linear, R, p->b_image_linear, ws + W.vl, D, Bc, D, R, false, prec, st));
+  DRIN_TRY(launch_gemm_nt({{ws + W.pool_t, D}, {p->w_text_linear, D}, p->b_text_linear, ws + W.tl, D, Bc, D, D}, prec, st));
+  DRIN_TRY(launch_gemm_nt({{ws + W.pool_v, R}, {p->w_image_linear, R}, p->b_image_linear, ws + W.vl, D, Bc, D, R}, prec, st));
   return launch_gate_mix(ws + W.tl, ws + W.vl, p->w_score_linear, p->b_score_linear, men, Bc, D, st);
 }
 
@@ -275,7 +272,7 @@ int drin_ghmfc_forward(const drin_ghmfc_config* cfg, const drin_ghmfc_batch* bt,
                                         ws + W.epool, pairs, T, D, st));
       ent_in = ws + W.epool;
     }
-    DRIN_TRY(launch_gemm_nt(ent_in, D, p->w_entity, D, p->b_entity, ws + W.ent, D, pairs, D, D, false, prec, st));
+    DRIN_TRY(launch_gemm_nt({{ent_in, D}, {p->w_entity, D}, p->b_entity, ws + W.ent, D, pairs, D, D}, prec, st));
     DRIN_TRY(launch_cosine_rows(men, ws + W.ent, D, scores + (int64_t)b0 * N, Bc, N, D, c.cosine_eps, 1.0f, st));
   }
   return DRIN_OK;
@@ -393,7 +390,7 @@ int drin_ghmfc_forward_table(const drin_ghmfc_config* cfg, const drin_ghmfc_batc
       DRIN_TRY(launch_entity_token_mean_indexed(t.text, t.mask, cand, t.num_entities, ws + W.epool, pairs, T, D, t.index_status, p0, st));
     else
       DRIN_TRY(launch_gather_rows(t.text, cand, t.num_entities, ws + W.epool, pairs, D, t.index_status, p0, st));
-    DRIN_TRY(launch_gemm_nt(ws + W.epool, D, p->w_entity, D, p->b_entity, ws + W.ent, D, pairs, D, D, false, prec, st));
+    DRIN_TRY(launch_gemm_nt({{ws + W.epool, D}, {p->w_entity, D}, p->b_entity, ws + W.ent, D, pairs, D, D}, prec, st));
     DRIN_TRY(launch_cosine_rows(men, ws + W.ent, D, scores + p0, Bc, N, D, c.cosine_eps, 1.0f, st));
   }
   return DRIN_OK;
@@ -442,7 +439,7 @@ int drin_ghmfc_entity_rows(const float* text, const int64_t* mask, int64_t num_e
       DRIN_TRY(launch_entity_token_mean(text + e0 * T * D, mask + e0 * T, pool, n, T, D, st));
       in = pool;
     }
-    DRIN_TRY(launch_gemm_nt(in, D, w_entity, D, b_entity, rows + e0 * D, D, n, D, D, false, precision, st));
+    DRIN_TRY(launch_gemm_nt({{in, D}, {w_entity, D}, b_entity, rows + e0 * D, D, n, D, D}, precision, st));
   }
   return DRIN_OK;
 }

@@ -487,8 +487,8 @@ int drin_melhi_forward(const drin_melhi_config* cfg, const drin_melhi_batch* bt,
 
   // image side: region mean, the image Linear on the mention and the candidates, the two cosines, the mask
   DRIN_TRY(launch_axis_mean(bt->mention_image, ws + W.mimg, B, P, R, st));
-  DRIN_TRY(launch_gemm_nt(ws + W.mimg, R, p->w_image_map_text, R, p->b_image_map_text, ws + W.mim, D, B, D, R, false, prec, st));
-  DRIN_TRY(launch_gemm_nt(bt->entity_image, R, p->w_image_map_text, R, p->b_image_map_text, ws + W.eim, D, BN, D, R, false, prec, st));
+  DRIN_TRY(launch_gemm_nt({{ws + W.mimg, R}, {p->w_image_map_text, R}, p->b_image_map_text, ws + W.mim, D, B, D, R}, prec, st));
+  DRIN_TRY(launch_gemm_nt({{bt->entity_image, R}, {p->w_image_map_text, R}, p->b_image_map_text, ws + W.eim, D, BN, D, R}, prec, st));
   DRIN_TRY(launch_cosine_rows(ws + W.mim, bt->mention_feature, (int64_t)L * D, ws + W.cos1, B, 1, D, c.cosine_eps, 1.0f, st));
   DRIN_TRY(launch_cosine_rows(ws + W.mimg, bt->entity_image, R, ws + W.cos2, B, N, R, c.cosine_eps, 1.0f, st));
   DRIN_TRY(timed(DRIN_KC_CELL, st, "k_melhi_mask", [&] {
@@ -504,14 +504,14 @@ int drin_melhi_forward(const drin_melhi_config* cfg, const drin_melhi_batch* bt,
   DRIN_TRY(timed(DRIN_KC_CELL, st, "k_bias_sum", [&] {
     hipLaunchKernelGGL(k_bias_sum, dim3((unsigned)cdiv(G, 256)), dim3(256), 0, st, p->b_ih, p->b_hh, ws + W.bsum, G);
   }));
-  DRIN_TRY(launch_gemm_nt(ws + W.word, D, p->w_ih + D, H, ws + W.bsum, ws + W.cst, G, B, G, D, false, prec, st));
-  DRIN_TRY(launch_gemm_nt(ws + W.mim, D, p->w_ih + 2 * D, H, nullptr, ws + W.cst, G, B, G, D, true, prec, st));
+  DRIN_TRY(launch_gemm_nt({{ws + W.word, D}, {p->w_ih + D, H}, ws + W.bsum, ws + W.cst, G, B, G, D}, prec, st));
+  DRIN_TRY(launch_gemm_nt(NtProduct{{ws + W.mim, D}, {p->w_ih + 2 * D, H}, nullptr, ws + W.cst, G, B, G, D}.adding(), prec, st));
   // time-0 cells of all 2 B sequences
   DRIN_TRY(timed(DRIN_KC_CELL, st, "k_melhi_tok0", [&] {
     hipLaunchKernelGGL(k_melhi_tok0, dim3((unsigned)(2 * B)), dim3(256), 0, st, bt->mention_feature, bt->start, bt->end,
                        bt->mention_mask, ws + W.xtok0, ph, B, L, D / 4);
   }));
-  DRIN_TRY(launch_gemm_nt(ws + W.xtok0, D, p->w_ih, H, nullptr, ws + W.g0, G, 2 * (int64_t)B, G, D, false, prec, st));
+  DRIN_TRY(launch_gemm_nt({{ws + W.xtok0, D}, {p->w_ih, H}, nullptr, ws + W.g0, G, 2 * (int64_t)B, G, D}, prec, st));
   DRIN_TRY(timed(DRIN_KC_CELL, st, "k_melhi_cell0", [&] {
     hipLaunchKernelGGL(k_melhi_cell0, dim3((unsigned)cdiv(H, 256), (unsigned)(2 * B)), dim3(256), 0, st, ws + W.g0, ws + W.cst,
                        ws + W.bsum, ph, ws + W.c0, ws + W.h0, B, H);
@@ -525,8 +525,8 @@ int drin_melhi_forward(const drin_melhi_config* cfg, const drin_melhi_batch* bt,
     }));
     for (int s = 0; s < 2; ++s)
       if (side[s].T)
-        DRIN_TRY(launch_gemm_nt(ws + W.xlane + (size_t)s * L * D, D, p->w_ih, H, ws + W.cst + (size_t)side[s].jstar * G,
-                                ws + W.p + (size_t)s * L * G, G, side[s].T, G, D, false, prec, st));
+        DRIN_TRY(launch_gemm_nt({{ws + W.xlane + (size_t)s * L * D, D}, {p->w_ih, H}, ws + W.cst + (size_t)side[s].jstar * G,
+                                 ws + W.p + (size_t)s * L * G, G, side[s].T, G, D}, prec, st));
     const int steps = T0 > T1 ? T0 : T1;
     for (int t = 0; t < steps; ++t)
       DRIN_TRY(timed(DRIN_KC_LSTM, st, "k_lstm_step", [&] {
@@ -538,11 +538,9 @@ int drin_melhi_forward(const drin_melhi_config* cfg, const drin_melhi_batch* bt,
     hipLaunchKernelGGL(k_melhi_gather, dim3((unsigned)cdiv(H, 256), (unsigned)(2 * B)), dim3(256), 0, st, ws + W.h0, ws + W.hs, src,
                        ws + W.men_in, B, H, L, T0, T1);
   }));
-  DRIN_TRY(launch_gemm_nt(ws + W.men_in, 2 * H, p->w_mention_final_map, 2 * H, p->b_mention_final_map, ws + W.men, D, B, D, 2 * H,
-                          false, prec, st));
-  DRIN_TRY(launch_gemm_nt(bt->entity_feature, D, p->w_entity_final_map, 2 * D, p->b_entity_final_map, ws + W.ent, D, BN, D, D,
-                          false, prec, st));
-  DRIN_TRY(launch_gemm_nt(ws + W.eim, D, p->w_entity_final_map + D, 2 * D, nullptr, ws + W.ent, D, BN, D, D, true, prec, st));
+  DRIN_TRY(launch_gemm_nt({{ws + W.men_in, 2 * H}, {p->w_mention_final_map, 2 * H}, p->b_mention_final_map, ws + W.men, D, B, D, 2 * H}, prec, st));
+  DRIN_TRY(launch_gemm_nt({{bt->entity_feature, D}, {p->w_entity_final_map, 2 * D}, p->b_entity_final_map, ws + W.ent, D, BN, D, D}, prec, st));
+  DRIN_TRY(launch_gemm_nt(NtProduct{{ws + W.eim, D}, {p->w_entity_final_map + D, 2 * D}, nullptr, ws + W.ent, D, BN, D, D}.adding(), prec, st));
   DRIN_TRY(launch_cosine_rows(ws + W.men, ws + W.ent, D, scores, B, N, D, c.cosine_eps, 1.0f, st));
   return DRIN_OK;
 }
@@ -585,40 +583,35 @@ int drin_melhi_backward(const drin_melhi_config* cfg, const drin_melhi_batch* bt
   const int H = 3 * D, G = 4 * H, prec = c.precision;
   const int64_t BN = (int64_t)B * N;
   const int T0 = side[0].T, T1 = side[1].T;
-  float* scr = ws + W.scratch;
-  const size_t scr_n = W.scratch_floats;
+  const GemmScratch scr{ws + W.scratch, W.scratch_floats};
   const int* ph = reinterpret_cast<const int*>(ws + W.ph);
   const int* recv = reinterpret_cast<const int*>(ws + W.recv);
-  auto tn = [&](const float* a, int64_t lda, const float* b, int64_t ldb, float* y, int64_t ldy, int64_t M, int Nn, int K) {
-    if (!y || M <= 0) return (int)DRIN_OK;
-    return launch_gemm_tn(a, lda, b, ldb, y, ldy, M, Nn, K, prec, st, scr, scr_n);
-  };
   auto colsum = [&](const float* x, float* out, int64_t rows, int C) {
     if (!out || rows <= 0) return (int)DRIN_OK;
-    return launch_colsum(x, out, rows, C, st, scr, scr_n);
+    return launch_colsum(x, out, rows, C, st, scr.p, scr.floats);
   };
 
   // cosine head
   DRIN_TRY(launch_cosine_bwd(ws + W.men, ws + W.ent, grad_scores, ws + W.dmen, ws + W.dent, ws + W.cscr, B, N, D, c.cosine_eps, st));
   // entity_final_map over [entity_feature | eim]
-  DRIN_TRY(tn(ws + W.dent, D, bt->entity_feature, D, gr->w_entity_final_map, 2 * D, BN, D, D));
-  DRIN_TRY(tn(ws + W.dent, D, ws + W.eim, D, gr->w_entity_final_map ? gr->w_entity_final_map + D : nullptr, 2 * D, BN, D, D));
+  DRIN_TRY(launch_gemm_tn({{ws + W.dent, D}, {bt->entity_feature, D}, gr->w_entity_final_map, 2 * D, BN, D, D}, prec, st, scr));
+  DRIN_TRY(launch_gemm_tn({{ws + W.dent, D}, {ws + W.eim, D}, gr->w_entity_final_map ? gr->w_entity_final_map + D : nullptr, 2 * D, BN, D, D}, prec, st, scr));
   DRIN_TRY(colsum(ws + W.dent, gr->b_entity_final_map, BN, D));
   const bool want_img = gr->w_image_map_text || gr->b_image_map_text;
   if (want_img) {
-    DRIN_TRY(launch_gemm_nn(ws + W.dent, D, p->w_entity_final_map + D, 2 * D, ws + W.deim, D, BN, D, D, false, prec, st));
+    DRIN_TRY(launch_gemm_nn({{ws + W.dent, D}, {p->w_entity_final_map + D, 2 * D}, ws + W.deim, D, BN, D, D}, prec, st));
     DRIN_TRY(timed(DRIN_KC_CELL, st, "k_scale_rows", [&] {
       hipLaunchKernelGGL(k_scale_rows, row_grid(BN, D / 4), dim3(256), 0, st, ws + W.deim, ws + W.mask, BN, N, D / 4);
     }));
-    DRIN_TRY(tn(ws + W.deim, D, bt->entity_image, R, gr->w_image_map_text, R, BN, D, R));
+    DRIN_TRY(launch_gemm_tn({{ws + W.deim, D}, {bt->entity_image, R}, gr->w_image_map_text, R, BN, D, R}, prec, st, scr));
     DRIN_TRY(colsum(ws + W.deim, gr->b_image_map_text, BN, D));
   }
   // mention_final_map over [left | right]
-  DRIN_TRY(tn(ws + W.dmen, D, ws + W.men_in, 2 * H, gr->w_mention_final_map, 2 * H, B, D, 2 * H));
+  DRIN_TRY(launch_gemm_tn({{ws + W.dmen, D}, {ws + W.men_in, 2 * H}, gr->w_mention_final_map, 2 * H, B, D, 2 * H}, prec, st, scr));
   DRIN_TRY(colsum(ws + W.dmen, gr->b_mention_final_map, B, D));
   const bool want_lstm = gr->w_ih || gr->w_hh || gr->b_ih || gr->b_hh || want_img;
   if (!want_lstm) return DRIN_OK;
-  DRIN_TRY(launch_gemm_nn(ws + W.dmen, D, p->w_mention_final_map, 2 * H, ws + W.dmen_in, 2 * H, B, 2 * H, D, false, prec, st));
+  DRIN_TRY(launch_gemm_nn({{ws + W.dmen, D}, {p->w_mention_final_map, 2 * H}, ws + W.dmen_in, 2 * H, B, 2 * H, D}, prec, st));
   // the extraction rule backwards, then the time-0 cells
   const int xj0 = T0 ? -1 : side[0].jstar, xj1 = T1 ? -1 : side[1].jstar;
   DRIN_TRY(timed(DRIN_KC_CELL, st, "k_melhi_scatter_bwd", [&] {
@@ -646,17 +639,19 @@ int drin_melhi_backward(const drin_melhi_config* cfg, const drin_melhi_batch* bt
   // weight gradients over the saved states
   for (int s = 0; s < 2; ++s)
     if (side[s].T >= 2)
-      DRIN_TRY(tn(ws + W.dgl + ((size_t)s * L + 1) * G, G, ws + W.hs + (size_t)s * L * H, H, gr->w_hh, H, side[s].T - 1, G, H));
-  DRIN_TRY(tn(ws + W.dg0, G, ws + W.xtok0, D, gr->w_ih, H, 2 * (int64_t)B, G, D));
+      DRIN_TRY(launch_gemm_tn({{ws + W.dgl + ((size_t)s * L + 1) * G, G}, {ws + W.hs + (size_t)s * L * H, H}, gr->w_hh, H, side[s].T - 1, G, H},
+                              prec, st, scr));
+  DRIN_TRY(launch_gemm_tn({{ws + W.dg0, G}, {ws + W.xtok0, D}, gr->w_ih, H, 2 * (int64_t)B, G, D}, prec, st, scr));
   for (int s = 0; s < 2; ++s)
-    if (side[s].T) DRIN_TRY(tn(ws + W.dgl + (size_t)s * L * G, G, ws + W.xlane + (size_t)s * L * D, D, gr->w_ih, H, side[s].T, G, D));
+    if (side[s].T)
+      DRIN_TRY(launch_gemm_tn({{ws + W.dgl + (size_t)s * L * G, G}, {ws + W.xlane + (size_t)s * L * D, D}, gr->w_ih, H, side[s].T, G, D}, prec, st, scr));
   DRIN_TRY(timed(DRIN_KC_CELL, st, "k_melhi_dconst", [&] {
     hipLaunchKernelGGL(k_melhi_dconst, dim3((unsigned)cdiv(G, 256), (unsigned)B), dim3(256), 0, st, ws + W.dg0, ph, ws + W.dgl,
                        ws + W.dcst, B, G, L, side[0].jstar, T0, side[1].jstar, T1);
   }));
   if (gr->w_ih) {
-    DRIN_TRY(tn(ws + W.dcst, G, ws + W.word, D, gr->w_ih + D, H, B, G, D));
-    DRIN_TRY(tn(ws + W.dcst, G, ws + W.mim, D, gr->w_ih + 2 * D, H, B, G, D));
+    DRIN_TRY(launch_gemm_tn({{ws + W.dcst, G}, {ws + W.word, D}, gr->w_ih + D, H, B, G, D}, prec, st, scr));
+    DRIN_TRY(launch_gemm_tn({{ws + W.dcst, G}, {ws + W.mim, D}, gr->w_ih + 2 * D, H, B, G, D}, prec, st, scr));
   }
   float* const dbias[2] = {gr->b_ih, gr->b_hh};   // both biases enter every gate sum once
   for (float* db : dbias) {
@@ -666,11 +661,11 @@ int drin_melhi_backward(const drin_melhi_config* cfg, const drin_melhi_batch* bt
   }
   if (want_img) {
     // mim enters the constant through W_img' (and the mask, which carries no gradient)
-    DRIN_TRY(launch_gemm_nn(ws + W.dcst, G, p->w_ih + 2 * D, H, ws + W.dmim, D, B, D, G, false, prec, st));
+    DRIN_TRY(launch_gemm_nn({{ws + W.dcst, G}, {p->w_ih + 2 * D, H}, ws + W.dmim, D, B, D, G}, prec, st));
     DRIN_TRY(timed(DRIN_KC_CELL, st, "k_scale_rows", [&] {
       hipLaunchKernelGGL(k_scale_rows, row_grid(B, D / 4), dim3(256), 0, st, ws + W.dmim, ws + W.mask, (int64_t)B, 1, D / 4);
     }));
-    DRIN_TRY(tn(ws + W.dmim, D, ws + W.mimg, R, gr->w_image_map_text, R, B, D, R));
+    DRIN_TRY(launch_gemm_tn({{ws + W.dmim, D}, {ws + W.mimg, R}, gr->w_image_map_text, R, B, D, R}, prec, st, scr));
     DRIN_TRY(colsum(ws + W.dmim, gr->b_image_map_text, B, D));
   }
   return DRIN_OK;

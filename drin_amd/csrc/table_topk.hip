@@ -495,7 +495,7 @@ int drin_table_topk(const float* x, const float* rows, const float* row_inv_norm
   // chunk's size, not by the batch's - then the selection on that block
   for (int64_t e0 = 0; e0 < num_entities; e0 += W.chunk) {
     const int64_t n = num_entities - e0 < W.chunk ? num_entities - e0 : W.chunk;
-    DRIN_TRY(launch_gemm_nt(rows + e0 * D, D, xpad, D, nullptr, block, Bp, n, Bp, D, false, precision, st));
+    DRIN_TRY(launch_gemm_nt({{rows + e0 * D, D}, {xpad, D}, nullptr, block, Bp, n, Bp, D}, precision, st));
     DRIN_TRY(launch_topk_update(block, Bp, B, n, e0, row_inv_norms + e0, kp, keys, list, slices, e0 == 0, st));
   }
   // the kp selected rows of every mention, scored as drin_cosine_rows_indexed_fwd scores them (an empty entry, row -1, is clamped

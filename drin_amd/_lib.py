@@ -19,6 +19,8 @@ ABI_VERSION = 12
 
 OK, E_SHAPE, E_NULL, E_ALIGN, E_WORKSPACE, E_HIP, E_UNSUPPORTED, E_INDEX = 0, -1, -2, -3, -4, -5, -6, -7
 TOPK_SLICE, TOPK_MAX_K = 4096, 256                                         # DRIN_TOPK_SLICE; k of the cosine top-k
+POOL_AVG, POOL_MAX = 0, 1                                                  # drin_entity_pooling
+ENTITY_POOLINGS = {"avg": POOL_AVG, "max": POOL_MAX}                       # common/args.py entity_final_pooling -> its id
 PREC_F32, PREC_BF16X3, PREC_BF16X3_ALL, PREC_BF16X3_IF16 = 0, 1, 3, 5     # (2 and 4: removed with ABI 6 - outside the 1e-4 bar)
 ROW_ACT = {"none": 0, "relu": 1, "gelu": 2}                               # drin_row_activation (drin_act_dropout_*)
 FEAT_F32, FEAT_BF16 = 0, 1
@@ -264,6 +266,14 @@ EXPORTS = {
     # (text, mask, num_entities, entity_tokens, width, w_entity, b_entity, precision, rows, workspace, workspace_bytes, stream)
     "drin_ghmfc_entity_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
                                          C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    # (text, mask, num_entities, entity_tokens, width, pooling, w_entity, b_entity, precision, rows, workspace, workspace_bytes, stream)
+    "drin_ghmfc_entity_rows_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                            C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    # the token pool with a pooling (POOL_AVG / POOL_MAX): (feat, mask, out, pairs, tokens, width, pooling, stream),
+    # (text, mask, index, num_entities, out, pairs, tokens, width, pooling, index_status, stream)
+    "drin_entity_token_pool": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "drin_entity_token_pool_indexed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32,
+                                                 C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     # the indexed row operations: (table, index, num_entities, out, count, width, index_status, stream),
     # (text, mask, index, num_entities, out, pairs, tokens, width, index_status, stream),
     # (x, rows, index, num_entities, out, batch, num_candidates, width, eps, index_status, stream)

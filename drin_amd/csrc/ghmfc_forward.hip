@@ -403,15 +403,17 @@ size_t drin_ghmfc_entity_rows_workspace_bytes(int64_t num_entities, int32_t enti
   return Q.total_floats * sizeof(float);
 }
 
-int drin_ghmfc_entity_rows(const float* text, const int64_t* mask, int64_t num_entities, int32_t entity_tokens, int32_t width,
-                           const float* w_entity, const float* b_entity, int32_t precision, float* rows, void* workspace,
-                           size_t workspace_bytes, void* stream) {
-  const char* who = "drin_ghmfc_entity_rows";
-  if (!text || !w_entity || !b_entity || !rows || (entity_tokens > 0 && (!mask || !workspace))) {
+// drin_ghmfc_entity_rows and _ex: `identity` = final_layer is nn.Identity (entity_final_layer_name "none": no weights, no product)
+static int entity_rows(const char* who, const float* text, const int64_t* mask, int64_t num_entities, int32_t entity_tokens,
+                       int32_t width, int32_t pooling, const float* w_entity, const float* b_entity, bool identity, int32_t precision,
+                       float* rows, void* workspace, size_t workspace_bytes, void* stream) {
+  const bool pooled_in_ws = entity_tokens > 0 && !identity;
+  if (!text || (!identity && (!w_entity || !b_entity)) || !rows || (entity_tokens > 0 && !mask) || (pooled_in_ws && !workspace)) {
     set_error("%s: text / w_entity / b_entity / rows is NULL (mask and the workspace are read when entity_tokens > 0)", who);
     return DRIN_E_NULL;
   }
   DRIN_TRY(check_entity_rows_shape(who, num_entities, entity_tokens, width));
+  DRIN_TRY(check_entity_pooling(who, pooling));
   if (precision != DRIN_PREC_F32 && precision != DRIN_PREC_BF16X3) {
     set_error("%s: precision %d is not DRIN_PREC_F32 / DRIN_PREC_BF16X3", who, precision);
     return DRIN_E_UNSUPPORTED;
@@ -422,7 +424,7 @@ int drin_ghmfc_entity_rows(const float* text, const int64_t* mask, int64_t num_e
   }
   EntityRowsLayout Q;
   Q.build(num_entities, entity_tokens, width);
-  if (workspace_bytes < Q.total_floats * sizeof(float)) {
+  if (pooled_in_ws && workspace_bytes < Q.total_floats * sizeof(float)) {
     set_error("%s: workspace %zu bytes < %zu", who, workspace_bytes, Q.total_floats * sizeof(float));
     return DRIN_E_WORKSPACE;
   }
@@ -435,12 +437,35 @@ int drin_ghmfc_entity_rows(const float* text, const int64_t* mask, int64_t num_e
     const int64_t n = num_entities - e0 < kRowsChunk ? num_entities - e0 : kRowsChunk;
     const float* in = text + e0 * D;
     if (T > 0) {
-      float* pool = static_cast<float*>(workspace) + Q.pool;
-      DRIN_TRY(launch_entity_token_mean(text + e0 * T * D, mask + e0 * T, pool, n, T, D, st));
+      float* pool = identity ? rows + e0 * D : static_cast<float*>(workspace) + Q.pool;
+      DRIN_TRY(launch_entity_token_pool(text + e0 * T * D, mask + e0 * T, pool, n, T, D, pooling, st));
       in = pool;
     }
-    DRIN_TRY(launch_gemm_nt({{in, D}, {w_entity, D}, b_entity, rows + e0 * D, D, n, D, D}, precision, st));
+    if (!identity) {
+      DRIN_TRY(launch_gemm_nt({{in, D}, {w_entity, D}, b_entity, rows + e0 * D, D, n, D, D}, precision, st));
+    } else if (T == 0 && rows != text) {   // Identity over a pooled table: the rows are the table's
+      hipError_t e = hipMemcpyAsync(rows + e0 * D, in, (size_t)n * D * sizeof(float), hipMemcpyDeviceToDevice, st);
+      if (e != hipSuccess) return hip_fail(e, "drin_ghmfc_entity_rows_ex: hipMemcpyAsync(rows)");
+    }
   }
   return DRIN_OK;
 }
 
+int drin_ghmfc_entity_rows(const float* text, const int64_t* mask, int64_t num_entities, int32_t entity_tokens, int32_t width,
+                           const float* w_entity, const float* b_entity, int32_t precision, float* rows, void* workspace,
+                           size_t workspace_bytes, void* stream) {
+  return entity_rows("drin_ghmfc_entity_rows", text, mask, num_entities, entity_tokens, width, DRIN_POOL_AVG, w_entity, b_entity, false,
+                     precision, rows, workspace, workspace_bytes, stream);
+}
+
+int drin_ghmfc_entity_rows_ex(const float* text, const int64_t* mask, int64_t num_entities, int32_t entity_tokens, int32_t width,
+                              int32_t pooling, const float* w_entity, const float* b_entity, int32_t precision, float* rows,
+                              void* workspace, size_t workspace_bytes, void* stream) {
+  const char* who = "drin_ghmfc_entity_rows_ex";
+  if (!w_entity != !b_entity) {
+    set_error("%s: exactly one of w_entity / b_entity is NULL (both NULL: final_layer = Identity)", who);
+    return DRIN_E_NULL;
+  }
+  return entity_rows(who, text, mask, num_entities, entity_tokens, width, pooling, w_entity, b_entity, !w_entity, precision, rows,
+                     workspace, workspace_bytes, stream);
+}

@@ -657,6 +657,22 @@ int drin_entity_token_mean(const float* feat, const int64_t* mask, float* out, i
   return launch_entity_token_mean(feat, mask, out, pairs, tokens, width, (hipStream_t)stream);
 }
 
+int drin_entity_token_pool(const float* feat, const int64_t* mask, float* out, int64_t pairs, int32_t tokens, int32_t width,
+                           int32_t pooling, void* stream) {
+  const char* who = "drin_entity_token_pool";
+  DRIN_CHECK_POINTERS(who, {"feat", feat, true}, {"out", out, true});
+  if (!mask) {
+    set_error("%s: mask is NULL", who);
+    return DRIN_E_NULL;
+  }
+  DRIN_TRY(check_entity_pooling(who, pooling));
+  DRIN_TRY(check_width4(who, width));
+  DRIN_TRY(check_count(who, "pairs", pairs, 1, INT32_MAX));
+  DRIN_TRY(check_count(who, "tokens", tokens, 1, 512));
+  DRIN_BIND_DEVICE(stream, out, who);
+  return launch_entity_token_pool(feat, mask, out, pairs, tokens, width, pooling, (hipStream_t)stream);
+}
+
 // ---- the FFN activation, row dropout and the span mean of GHMFC's other mention encoders ------------
 namespace {
 int act_dropout_args(const char* who, int64_t rows, int32_t width, int32_t act, float p, uint64_t seed, uint64_t call, DropArgs* drop,

@@ -123,6 +123,24 @@ int drin_entity_token_mean_indexed(const float* text, const int64_t* mask, const
                                           (hipStream_t)stream);
 }
 
+int drin_entity_token_pool_indexed(const float* text, const int64_t* mask, const int64_t* index, int64_t num_entities, float* out,
+                                   int64_t pairs, int32_t tokens, int32_t width, int32_t pooling, int32_t* index_status, void* stream) {
+  const char* who = "drin_entity_token_pool_indexed";
+  DRIN_CHECK_POINTERS(who, {"text", text, true}, {"out", out, true});
+  if (!mask) {
+    set_error("%s: mask is NULL", who);
+    return DRIN_E_NULL;
+  }
+  DRIN_TRY(check_table_args(who, index, num_entities, index_status));
+  DRIN_TRY(check_entity_pooling(who, pooling));
+  DRIN_TRY(check_width4(who, width));
+  DRIN_TRY(check_count(who, "pairs", pairs, 1, INT32_MAX));
+  DRIN_TRY(check_count(who, "tokens", tokens, 1, 512));
+  DRIN_BIND_DEVICE(stream, out, who);
+  return launch_entity_token_pool_indexed(text, mask, index, num_entities, out, pairs, tokens, width, pooling, index_status, 0,
+                                          (hipStream_t)stream);
+}
+
 int drin_cosine_rows_indexed_fwd(const float* x, const float* rows, const int64_t* index, int64_t num_entities, float* out,
                                  int32_t batch, int32_t num_candidates, int32_t width, float eps, int32_t* index_status, void* stream) {
   const char* who = "drin_cosine_rows_indexed_fwd";

@@ -139,6 +139,13 @@ int launch_entity_token_mean_bf16(const void* feat, const int64_t* mask, float* 
 // it is used and reported into status (int32[4] or NULL; device_utils.h: report_bad_index) as pair pair_base + p
 int launch_entity_token_mean_indexed(const float* text, const int64_t* mask, const int64_t* index, int64_t num_rows, float* out,
                                      int64_t pairs, int T, int D, int32_t* status, int64_t pair_base, hipStream_t st);
+// both with a pooling (drin_entity_pooling, checked by the caller): DRIN_POOL_AVG is the two launches above, DRIN_POOL_MAX the
+// maximum over the same slice (a NaN inside it wins; an empty slice gives a NaN row)
+int check_entity_pooling(const char* who, int pooling);
+int launch_entity_token_pool(const float* feat, const int64_t* mask, float* out, int64_t pairs, int T, int D, int pooling,
+                             hipStream_t st);
+int launch_entity_token_pool_indexed(const float* text, const int64_t* mask, const int64_t* index, int64_t num_rows, float* out,
+                                     int64_t pairs, int T, int D, int pooling, int32_t* status, int64_t pair_base, hipStream_t st);
 // the other row kernels of GHMFC's table form (ghmfc_table.hip), the same clamp and report:
 // out[i, :] = table[index[i], :] for [E, width] fp32 rows
 int launch_gather_rows(const float* table, const int64_t* index, int64_t num_rows, float* out, int64_t count, int width,

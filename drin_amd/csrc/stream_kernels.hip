@@ -125,7 +125,15 @@ struct TableRows {
   int64_t pair_base;      // what is added to p in a report (a chunk of a larger call)
   int32_t* status;        // int32[4] or NULL
 };
-template <typename T_, bool INDEXED>
+// POOL (drin_entity_pooling; get_entity_final_pooling_fn of ghmfc.py:210-214): DRIN_POOL_AVG, the mean above, or DRIN_POOL_MAX,
+// x[p] = max over the same slice (torch.max(0)[0]: a NaN inside the slice wins - max_nan, as k_seq_max; rows outside are never
+// read).  Both share the ntok count, the slice rules, the launch and the loads; the mean's summation order is untouched.  An empty
+// slice (ntok 1 or 2) writes a NaN row under either pooling (the mean's 0 / 0; the reference's max raises IndexError there and a
+// kernel cannot).
+__device__ __forceinline__ float4 max_nan4(float4 a, float4 b) {
+  return make_float4(max_nan(a.x, b.x), max_nan(a.y, b.y), max_nan(a.z, b.z), max_nan(a.w, b.w));
+}
+template <typename T_, bool INDEXED, int POOL>
 __global__ void __launch_bounds__(256) k_entity_token_mean(const T_* __restrict__ feat,
                                                            const int64_t* __restrict__ mask, float* __restrict__ out,
                                                            int T, int D4, TableRows rows) {
@@ -148,22 +156,38 @@ __global__ void __launch_bounds__(256) k_entity_token_mean(const T_* __restrict_
   const T_* base = feat + src * (int64_t)T * D4 * 4;
   for (int c4 = threadIdx.x; c4 < D4; c4 += blockDim.x) {
     const T_* col = base + (int64_t)c4 * 4;
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    int t = 1;
-    for (; t + 8 <= stop; t += 8) {
-      float4 v[8];
+    float* dst = out + p * (int64_t)D4 * 4 + (int64_t)c4 * 4;
+    if constexpr (POOL == DRIN_POOL_MAX) {
+      const float start = n > 0 ? -INFINITY : __builtin_nanf("");  // empty slice: a NaN row, as the mean's 0 / 0
+      float4 acc = make_float4(start, start, start, start);
+      int t = 1;
+      for (; t + 8 <= stop; t += 8) {
+        float4 v[8];
 #pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = ld4_stream(col + (int64_t)(t + j) * D4 * 4);  // read once
+        for (int j = 0; j < 8; ++j) v[j] = ld4_stream(col + (int64_t)(t + j) * D4 * 4);  // read once
 #pragma unroll
-      for (int j = 0; j < 8; ++j) acc = acc + v[j];
+        for (int j = 0; j < 8; ++j) acc = max_nan4(acc, v[j]);
+      }
+      for (; t < stop; ++t) acc = max_nan4(acc, ld4_stream(col + (int64_t)t * D4 * 4));
+      st4(dst, acc);
+    } else {
+      float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+      int t = 1;
+      for (; t + 8 <= stop; t += 8) {
+        float4 v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = ld4_stream(col + (int64_t)(t + j) * D4 * 4);  // read once
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc = acc + v[j];
+      }
+      for (; t < stop; ++t) acc = acc + ld4_stream(col + (int64_t)t * D4 * 4);
+      const float den = n > 0 ? (float)n : 0.0f;  // empty slice: 0 / 0 = NaN, as the reference
+      st4(dst, make_float4(acc.x / den, acc.y / den, acc.z / den, acc.w / den));
     }
-    for (; t < stop; ++t) acc = acc + ld4_stream(col + (int64_t)t * D4 * 4);
-    const float den = n > 0 ? (float)n : 0.0f;  // empty slice: 0 / 0 = NaN, as the reference
-    st4(out + p * (int64_t)D4 * 4 + (int64_t)c4 * 4, make_float4(acc.x / den, acc.y / den, acc.z / den, acc.w / den));
   }
 }
 
-template <typename T_, bool INDEXED = false>
+template <typename T_, bool INDEXED = false, int POOL = DRIN_POOL_AVG>
 static int launch_entity_token_mean_t(const T_* feat, const int64_t* mask, float* out, int64_t pairs, int T, int D,
                                       hipStream_t st, TableRows rows = TableRows{}) {
   if (pairs <= 0) return DRIN_OK;
@@ -174,7 +198,7 @@ static int launch_entity_token_mean_t(const T_* feat, const int64_t* mask, float
   const int D4 = D / 4;
   int threads = D4 >= 192 ? 192 : (D4 > 64 ? 128 : 64);  // D = 768 -> one float4 column per thread, 3 waves
   KernelTimer timer(DRIN_KC_POOL, st);
-  hipLaunchKernelGGL((k_entity_token_mean<T_, INDEXED>), dim3((unsigned)pairs), dim3(threads), 0, st, feat, mask, out, T, D4, rows);
+  hipLaunchKernelGGL((k_entity_token_mean<T_, INDEXED, POOL>), dim3((unsigned)pairs), dim3(threads), 0, st, feat, mask, out, T, D4, rows);
   DRIN_CHECK_LAUNCH("k_entity_token_mean");
   return DRIN_OK;
 }
@@ -190,6 +214,24 @@ int launch_entity_token_mean_bf16(const void* feat, const int64_t* mask, float* 
 int launch_entity_token_mean_indexed(const float* text, const int64_t* mask, const int64_t* index, int64_t num_rows, float* out,
                                      int64_t pairs, int T, int D, int32_t* status, int64_t pair_base, hipStream_t st) {
   return launch_entity_token_mean_t<float, true>(text, mask, out, pairs, T, D, st, TableRows{index, num_rows, pair_base, status});
+}
+int check_entity_pooling(const char* who, int pooling) {
+  if (pooling == DRIN_POOL_AVG || pooling == DRIN_POOL_MAX) return DRIN_OK;
+  set_error("%s: pooling = %d is neither DRIN_POOL_AVG (%d) nor DRIN_POOL_MAX (%d)", who, pooling, DRIN_POOL_AVG, DRIN_POOL_MAX);
+  return DRIN_E_UNSUPPORTED;
+}
+// the pooling chosen at run time (pooling: DRIN_POOL_AVG / DRIN_POOL_MAX, checked by the entry points): fp32 features only
+int launch_entity_token_pool(const float* feat, const int64_t* mask, float* out, int64_t pairs, int T, int D, int pooling,
+                             hipStream_t st) {
+  if (pooling == DRIN_POOL_MAX) return launch_entity_token_mean_t<float, false, DRIN_POOL_MAX>(feat, mask, out, pairs, T, D, st);
+  return launch_entity_token_mean(feat, mask, out, pairs, T, D, st);
+}
+int launch_entity_token_pool_indexed(const float* text, const int64_t* mask, const int64_t* index, int64_t num_rows, float* out,
+                                     int64_t pairs, int T, int D, int pooling, int32_t* status, int64_t pair_base, hipStream_t st) {
+  if (pooling == DRIN_POOL_MAX)
+    return launch_entity_token_mean_t<float, true, DRIN_POOL_MAX>(text, mask, out, pairs, T, D, st,
+                                                                  TableRows{index, num_rows, pair_base, status});
+  return launch_entity_token_mean_indexed(text, mask, index, num_rows, out, pairs, T, D, status, pair_base, st);
 }
 
 // ------------------------------------------------------------------------------------------------

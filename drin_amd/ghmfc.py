@@ -19,13 +19,18 @@ from ._lib import _ptr, _stream
 from .ghmfc_table import GhmfcIndexedBatch, TableForm
 
 PRECISIONS = {"bf16x3": _lib.PREC_BF16X3, "f32": _lib.PREC_F32}
+ENTITY_FINAL_LAYERS = ("linear", "none")
+ENTITY_POOLINGS = _lib.ENTITY_POOLINGS
 
 
 @dataclass
 class GhmfcConfig:
     """Geometry of `common/args.py` that GHMFC reads (`bert_embed_dim`, `resnet_embed_dim`, `resnet_num_region`,
     `max_mention_sentence_len`, `num_candidates_model`, `transformer_num_heads`, `max_entity_attr_token_len`).
-    `entity_tokens` is the token count of the WikiMEL entity features [B, N, T, D] and ignored on WikiDiverse ([B, N, D])."""
+    `entity_tokens` is the token count of the WikiMEL entity features [B, N, T, D] and ignored on WikiDiverse ([B, N, D]).
+    `entity_final_layer_name` ("linear" | "none": `final_layer` is `nn.Identity`, the model has no entity keys) and
+    `entity_final_pooling` ("avg" | "max" over tokens 1 : ntok - 1; read for token features only, as in the reference) are
+    `common/args.py:15-16`; "bert default" is not offered: the reference's own `EntityEncoder.__init__` raises on it."""
     dataset_name: str = "wikidiverse"
     num_candidates: int = 11
     embed_dim: int = 768
@@ -36,10 +41,22 @@ class GhmfcConfig:
     entity_tokens: int = 64
     layer_norm_eps: float = 1e-5
     cosine_eps: float = 1e-8
+    entity_final_layer_name: str = "linear"
+    entity_final_pooling: str = "avg"
 
     def __post_init__(self):
         if self.dataset_name not in ("wikidiverse", "wikimel"):
             raise ValueError(f"dataset_name {self.dataset_name!r} is neither 'wikidiverse' nor 'wikimel'")
+        if self.entity_final_layer_name not in ENTITY_FINAL_LAYERS:
+            raise ValueError(f"entity_final_layer_name {self.entity_final_layer_name!r} is none of {ENTITY_FINAL_LAYERS}")
+        if self.entity_final_pooling not in ENTITY_POOLINGS:
+            raise ValueError(f"entity_final_pooling {self.entity_final_pooling!r} is none of {tuple(ENTITY_POOLINGS)} ('bert default': "
+                             "the reference's EntityEncoder cannot be constructed with it)")
+
+    @property
+    def entity_default(self) -> bool:
+        """Linear over the token mean: the entity side `drin_ghmfc_forward` runs"""
+        return self.entity_final_layer_name == "linear" and self.entity_final_pooling == "avg"
 
 
 def config_from_reference_args(args) -> GhmfcConfig:
@@ -58,6 +75,33 @@ def config_from_reference_args(args) -> GhmfcConfig:
                        image_dim=args.resnet_embed_dim, mention_tokens=args.max_mention_sentence_len,
                        image_regions=args.resnet_num_region, num_heads=getattr(args, "transformer_num_heads", 8),
                        entity_tokens=getattr(args, "max_entity_attr_token_len", 64))
+
+
+def entity_settings_from_reference_args(args) -> dict:
+    """`entity_final_layer_name` and `entity_final_pooling` of a `common.args` module as `GhmfcConfig` fields, validated."""
+    layer, pooling = getattr(args, "entity_final_layer_name", "linear"), getattr(args, "entity_final_pooling", "avg")
+    if getattr(args, "online_bert", False):
+        raise NotImplementedError("ghmfc: online_bert = True is not implemented (only the offline features; DESIGN.md section 11)")
+    if pooling == "bert default":
+        raise NotImplementedError("ghmfc: entity_final_pooling = 'bert default' is refused: the reference's own EntityEncoder constructor "
+                                  "raises ValueError on it (get_entity_final_pooling_fn, baselines/ghmfc.py:253-260), so no model to agree "
+                                  "with exists (DESIGN.md section 28)")
+    if layer not in ENTITY_FINAL_LAYERS:
+        raise NotImplementedError(f"ghmfc: entity_final_layer_name = {layer!r} is none of {ENTITY_FINAL_LAYERS}")
+    if pooling not in ENTITY_POOLINGS:
+        raise NotImplementedError(f"ghmfc: entity_final_pooling = {pooling!r} is none of {tuple(ENTITY_POOLINGS)}")
+    return dict(entity_final_layer_name=layer, entity_final_pooling=pooling)
+
+
+def model_device(model: nn.Module, *like) -> torch.device:
+    """Where a GHMFC model lives: the device of its first parameter; a model without one (mention encoder "none" with entity
+    "none") is where the first tensor of `like` is - the batch's mention features, or the table."""
+    for p in model.parameters():
+        return p.device
+    for t in like:
+        if isinstance(t, torch.Tensor):
+            return t.device
+    return torch.device("cpu")
 
 
 class _CrossAttention(nn.Module):
@@ -102,12 +146,18 @@ class _MentionEncoder(nn.Module):
 class _EntityEncoder(nn.Module):
     def __init__(self, cfg: GhmfcConfig):
         super().__init__()
-        self.final_layer = nn.Linear(cfg.embed_dim, cfg.embed_dim)
+        # ghmfc.py:210-213: "none" constructs no Linear, so the draws that follow under one seed stay the reference's
+        self.final_layer = nn.Linear(cfg.embed_dim, cfg.embed_dim) if cfg.entity_final_layer_name == "linear" else nn.Identity()
+
+    def param_list(self) -> list:
+        return list(self.final_layer.parameters())
 
 
 class Model(TableForm, nn.Module):
     """ghmfc.py's `Model` for scoring: the same modules, created in the same order (so `torch.manual_seed(s); Model()` draws the
-    reference's weights) and the same 52 state-dict keys; a trained checkpoint loads with `load_state_dict`.
+    reference's weights) and the same 52 state-dict keys (50 with `entity_final_layer_name = "none"`); a trained checkpoint loads with
+    `load_state_dict`.  With non-default entity settings (`GhmfcConfig.entity_final_pooling`, `entity_final_layer_name`; DESIGN.md
+    section 28) scoring is `drin_ghmfc_mention_forward` followed by `ghmfc_train.entity_scores`.
     `forward(batch)` takes the reference's 8-item offline batch (mention_feature, mention_mask, begin, end, mention_image,
     entity_feature, entity_mask, entity_image) and returns scores [B, N]; `encode_mentions(batch)` the [B, D] mention
     representations.  Eval mode only, no gradients.  `precision`: "bf16x3" (split-bf16 products, the default) or "f32"
@@ -129,17 +179,24 @@ class Model(TableForm, nn.Module):
         return _MentionEncoder(cfg)
 
     def param_list(self) -> list:
-        """The 52 parameters in drin_ghmfc_params (= state-dict) order."""
+        """The parameters in drin_ghmfc_params (= state-dict) order: 52, or 50 when the entity final layer is "none"."""
         f = self.mention_encoder.intermediate_layer
         return (f.t2v_attention.param_list() + f.v2t_attention.param_list()
                 + [f.text_linear.weight, f.text_linear.bias, f.image_linear.weight, f.image_linear.bias, f.score_linear.weight,
-                   f.score_linear.bias, self.entity_encoder.final_layer.weight, self.entity_encoder.final_layer.bias])
+                   f.score_linear.bias] + self.entity_encoder.param_list())
+
+    def _params_c(self):
+        """(drin_ghmfc_params, the tensors it points into).  Without an entity Linear its two slots hold text_linear's pointers:
+        valid addresses that only `drin_ghmfc_mention_forward` is given, which reads neither."""
+        params = [p.detach().contiguous() for p in self.param_list()]
+        params += params[44:46] if len(params) == 50 else []
+        return _lib.DrinGhmfcParamsC.from_buffer_copy((C.c_void_p * 52)(*[p.data_ptr() for p in params])), params
 
     def _batch_tensors(self, batch):
         """(mention_feature, mention_mask, mention_image, entity_feature, entity_mask or None, entity tokens or 0) of the
         reference's batch: detached, float32 / int64, contiguous, on the model's device, checked against the configuration."""
         mf, mmask, _begin, _end, mimage, ef, emask = batch[:7]
-        dev = self.entity_encoder.final_layer.weight.device
+        dev = model_device(self, mf)
         if dev.type != "cuda" or (isinstance(mf, torch.Tensor) and mf.device.type != "cuda"):
             raise RuntimeError("drin_amd.ghmfc.Model runs on the GPU only (no CPU fallback): move the model and the batch with .cuda()")
         cfg = self.cfg
@@ -165,7 +222,7 @@ class Model(TableForm, nn.Module):
         """(mention_feature, mention_mask, mention_image) of the five mention-side items of a table-form batch, prepared and
         checked like `_batch_tensors`' (begin and end are not read)."""
         mf, mmask, _begin, _end, mimage = mention
-        dev = self.entity_encoder.final_layer.weight.device
+        dev = model_device(self, mf)
         if dev.type != "cuda" or (isinstance(mf, torch.Tensor) and mf.device.type != "cuda"):
             raise RuntimeError("drin_amd.ghmfc.Model runs on the GPU only (no CPU fallback): move the model and the batch with .cuda()")
         cfg = self.cfg
@@ -185,6 +242,10 @@ class Model(TableForm, nn.Module):
         cfg, dev, B = self.cfg, mf.device, mf.shape[0]
         if tb.candidates.shape[0] != B:
             raise ValueError(f"ghmfc table form: candidates {tuple(tb.candidates.shape)} for {B} mentions")
+        if not cfg.entity_default:              # the mention half's own bits, then the entity side as the variants run it
+            with torch.no_grad():
+                mention = self._mention_only(tb.mention)
+                return self._eval_scores(tb, mention) if want_scores else mention
         lib = _lib.load()
         text = tb.table.text.contiguous()
         tokens = text.shape[1] if text.dim() == 3 else 0
@@ -194,9 +255,8 @@ class Model(TableForm, nn.Module):
                                   mention_tokens=cfg.mention_tokens, image_regions=cfg.image_regions, num_heads=cfg.num_heads,
                                   entity_tokens=tokens, precision=PRECISIONS[self.precision], layer_norm_eps=cfg.layer_norm_eps,
                                   cosine_eps=cfg.cosine_eps)
-        params = [p.detach().contiguous() for p in self.param_list()]
+        pc, _params = self._params_c()
         bt = _lib.DrinGhmfcBatchC(_ptr(mf), _ptr(mmask), _ptr(mimage), None, None)
-        pc = _lib.DrinGhmfcParamsC.from_buffer_copy((C.c_void_p * 52)(*[p.data_ptr() for p in params]))
         status = self._status_words(dev)
         tc = _lib.DrinGhmfcTableC(size=C.sizeof(_lib.DrinGhmfcTableC), text=_ptr(text), mask=_ptr(mask), num_entities=text.shape[0],
                                   entity_tokens=tokens, candidates=_ptr(tb.candidates), index_status=_ptr(status), rows=_ptr(rows))
@@ -221,9 +281,8 @@ class Model(TableForm, nn.Module):
                                   mention_tokens=cfg.mention_tokens, image_regions=cfg.image_regions, num_heads=cfg.num_heads,
                                   entity_tokens=0, precision=PRECISIONS[self.precision], layer_norm_eps=cfg.layer_norm_eps,
                                   cosine_eps=cfg.cosine_eps)
-        params = [p.detach().contiguous() for p in self.param_list()]
+        pc, _params = self._params_c()
         bt = _lib.DrinGhmfcBatchC(_ptr(mf), _ptr(mmask), _ptr(mimage), None, None)
-        pc = _lib.DrinGhmfcParamsC.from_buffer_copy((C.c_void_p * 52)(*[p.data_ptr() for p in params]))
         nbytes = lib.drin_ghmfc_mention_forward_workspace_bytes(C.byref(c))
         if nbytes == 0:
             _lib.check(_lib.E_SHAPE)
@@ -243,14 +302,18 @@ class Model(TableForm, nn.Module):
             return self._score_table(tb, want_scores)
         mf, mmask, mimage, ef, emask, tokens = self._batch_tensors(batch)
         cfg, dev, B = self.cfg, mf.device, mf.shape[0]
+        if not cfg.entity_default:              # drin_ghmfc_mention_forward, then the entity side operation by operation
+            from .ghmfc_train import entity_scores
+            with torch.no_grad():
+                mention = self._mention_only([mf, mmask, None, None, mimage])
+                return entity_scores(mention, ef, emask, self.entity_encoder.final_layer, cfg, self.precision) if want_scores else mention
         lib = _lib.load()
         c = _lib.DrinGhmfcConfigC(batch=B, num_candidates=cfg.num_candidates, embed_dim=cfg.embed_dim, image_dim=cfg.image_dim,
                                   mention_tokens=cfg.mention_tokens, image_regions=cfg.image_regions, num_heads=cfg.num_heads,
                                   entity_tokens=tokens, precision=PRECISIONS[self.precision], layer_norm_eps=cfg.layer_norm_eps,
                                   cosine_eps=cfg.cosine_eps)
-        params = [p.detach().contiguous() for p in self.param_list()]
+        pc, _params = self._params_c()
         bt = _lib.DrinGhmfcBatchC(_ptr(mf), _ptr(mmask), _ptr(mimage), _ptr(ef), _ptr(emask))
-        pc = _lib.DrinGhmfcParamsC.from_buffer_copy((C.c_void_p * 52)(*[p.data_ptr() for p in params]))
         nbytes = lib.drin_ghmfc_workspace_bytes(C.byref(c))
         if nbytes == 0:
             _lib.check(_lib.E_SHAPE)

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 from torch.utils.data import DataLoader, Dataset
 
-from .ghmfc import config_from_reference_args
+from .ghmfc import config_from_reference_args, entity_settings_from_reference_args
 from .ghmfc_train import TrainableModel as _Model
 from .ghmfc_variants import VariantModel, variant_config_from_reference_args
 from .melhi_shim import SPLITS
@@ -28,6 +28,31 @@ from .melhi_shim import SPLITS
 
 def _args():
     return importlib.import_module("common.args")
+
+
+class _DefaultEntityArgs:
+    """`common.args` as the two legacy config functions accept it: the default entity names in front of everything else."""
+    entity_final_layer_name, entity_final_pooling = "linear", "avg"
+
+    def __init__(self, args):
+        self._args = args
+
+    def __getattr__(self, name):
+        return getattr(self._args, name)
+
+
+def _configs(a):
+    """(VariantConfig, GhmfcConfig or None for a non-default mention encoder) of `common.args`, the entity settings
+    (`entity_final_layer_name`, `entity_final_pooling`: `ghmfc.entity_settings_from_reference_args`) set on both."""
+    entity = entity_settings_from_reference_args(a)
+    view = _DefaultEntityArgs(a)
+    cfg = variant_config_from_reference_args(view)
+    base = config_from_reference_args(view) if cfg.is_default else None       # the default's own refusals
+    for c in (cfg, base):
+        for name, value in entity.items():
+            if c is not None:
+                setattr(c, name, value)
+    return cfg, base
 
 
 def _table_form() -> bool:
@@ -38,7 +63,7 @@ def _table_form() -> bool:
 
 def _attach_table(model, a):
     from .ghmfc_data import _setup, load_entity_table
-    _setup(a)                                                                  # WikiDiverse has no shared table: refused
+    _setup(_DefaultEntityArgs(a))                                              # WikiDiverse has no shared table: refused
     return model.attach_entity_table(load_entity_table(a.preprocess_dir, "cpu", getattr(a, "entity_text_type", "attr")))
 
 
@@ -46,11 +71,12 @@ class Model(_Model):
     """`model_module.Model()`: geometry and `transformer_dropout` from `common.args`; split-bf16 products unless
     DRIN_PRECISION=f32; the softmax-attention core of DRIN_ATTENTION_CORE ("fma", the default, or "mfma").  The attention dropout of train() mode is the library's own mask, seeded by `args.seed`.  With another
     mention encoder selected in `common.args` (`mention_final_layer_name`, `mention_multimodal_attention`: "transformer",
-    "multimodal" + "text", "linear", "none") `Model()` is a `drin_amd.ghmfc_variants.VariantModel` built the same way."""
+    "multimodal" + "text", "linear", "none") `Model()` is a `drin_amd.ghmfc_variants.VariantModel` built the same way.
+    `entity_final_layer_name` ("linear" | "none") and `entity_final_pooling` ("avg" | "max") are honoured by either."""
 
     def __new__(cls):
         a = _args()
-        cfg = variant_config_from_reference_args(a)
+        cfg, _base = _configs(a)
         if cfg.is_default:
             return super().__new__(cls)
         model = VariantModel(cfg, precision=os.environ.get("DRIN_PRECISION", "bf16x3"), dropout=getattr(a, "transformer_dropout", 0.1),
@@ -59,7 +85,7 @@ class Model(_Model):
 
     def __init__(self):
         a = _args()
-        super().__init__(config_from_reference_args(a), precision=os.environ.get("DRIN_PRECISION", "bf16x3"),
+        super().__init__(_configs(a)[1], precision=os.environ.get("DRIN_PRECISION", "bf16x3"),
                          dropout=getattr(a, "transformer_dropout", 0.1), seed=getattr(a, "seed", 0),
                          core=os.environ.get("DRIN_ATTENTION_CORE", "fma"))
         if _table_form():
@@ -113,12 +139,10 @@ class GhmfcData(Dataset):
 def create_datasets() -> List[DataLoader]:
     """`data_module.create_datasets()` for GHMFC: loaders over `args.preprocess_dir` with `args.batch_size`."""
     a = _args()
-    cfg = variant_config_from_reference_args(a)
-    if cfg.is_default:
-        config_from_reference_args(a)                                          # the default's own refusals
+    cfg, _base = _configs(a)
     if _table_form():
         from .ghmfc_data import create_indexed_datasets
-        return create_indexed_datasets(a)
+        return create_indexed_datasets(_DefaultEntityArgs(a))                  # the loaders read no entity setting
     loaders = []
     for split in SPLITS:
         ds = GhmfcData(a.preprocess_dir, split, cfg.dataset_name, cfg.num_candidates, cfg.embed_dim,

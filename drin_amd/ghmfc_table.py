@@ -91,15 +91,21 @@ def gather_rows(rows: torch.Tensor, index: torch.Tensor, status: Optional[torch.
     return out
 
 
-def pooled_candidates(table: EntityTable, index: torch.Tensor, status: Optional[torch.Tensor]) -> torch.Tensor:
-    """`[B, N, D]`: the token mean of every candidate's table row (`drin_entity_token_mean_indexed`), or the gathered rows
-    of a pooled table - what `entity_token_mean` gives on the gathered block, bit for bit."""
+def pooled_candidates(table: EntityTable, index: torch.Tensor, status: Optional[torch.Tensor], pooling: str = "avg") -> torch.Tensor:
+    """`[B, N, D]`: the token mean of every candidate's table row (`drin_entity_token_mean_indexed`; `pooling` "max": the maximum,
+    `drin_entity_token_pool_indexed`), or the gathered rows of a pooled table - what `entity_token_pool` gives on the gathered
+    block, bit for bit."""
     text, mask, tokens = _table_tensors(table)
     if tokens == 0:
         return gather_rows(text, index, status)
+    lib = _lib.load()
     out = torch.empty(*index.shape, text.shape[2], dtype=torch.float32, device=text.device)
-    _lib.check(_lib.load().drin_entity_token_mean_indexed(_ptr(text), _ptr(mask), _ptr(index), text.shape[0], _ptr(out), index.numel(),
-                                                          tokens, text.shape[2], _ptr(status), _stream(text.device)))
+    if pooling == "avg":
+        _lib.check(lib.drin_entity_token_mean_indexed(_ptr(text), _ptr(mask), _ptr(index), text.shape[0], _ptr(out), index.numel(),
+                                                      tokens, text.shape[2], _ptr(status), _stream(text.device)))
+    else:
+        _lib.check(lib.drin_entity_token_pool_indexed(_ptr(text), _ptr(mask), _ptr(index), text.shape[0], _ptr(out), index.numel(),
+                                                      tokens, text.shape[2], _lib.ENTITY_POOLINGS[pooling], _ptr(status), _stream(text.device)))
     return out
 
 
@@ -162,7 +168,7 @@ class _TableState:
 
 class TableForm:
     """Mixin of the GHMFC models: the table form described in this module's docstring.  The model supplies `cfg`, `precision`
-    and `entity_encoder.final_layer`."""
+    and `entity_encoder` (its `final_layer` and `param_list()`)."""
 
     @property
     def validate_indices(self) -> bool:
@@ -242,7 +248,7 @@ class TableForm:
             raise ValueError(f"ghmfc link: k = {k} is not in [1, {_lib.TOPK_MAX_K}]")
         if k > E:
             raise ValueError(f"ghmfc link: k = {k} exceeds the table's {E} entities")
-        dev = self.entity_encoder.final_layer.weight.device
+        dev = self._device(table.text)
         if dev.type != "cuda":
             raise RuntimeError("ghmfc link runs on the GPU only (no CPU fallback): move the model and the batch with .cuda()")
         if table.text.device != dev:
@@ -295,7 +301,7 @@ class TableForm:
             if self._tf.table is None:
                 raise ValueError("ghmfc: item 5 of the batch is an integer tensor [B, N] (candidate rows) but no entity table is attached: "
                                  "call model.attach_entity_table(table)")
-            dev = self.entity_encoder.final_layer.weight.device
+            dev = self._device(batch[0])
             if dev.type != "cuda":
                 raise RuntimeError("ghmfc table form runs on the GPU only (no CPU fallback): move the model and the batch with .cuda()")
             if self._tf.table.text.device != dev:
@@ -307,11 +313,16 @@ class TableForm:
             raise RuntimeError("ghmfc table form runs on the GPU only (no CPU fallback): move the candidates with .cuda()")
         if cand.dim() != 2 or cand.shape[1] != self.cfg.num_candidates:
             raise ValueError(f"ghmfc table form: candidates {tuple(cand.shape)} are not [B, {self.cfg.num_candidates}]")
-        if self.entity_encoder.final_layer.weight.device != dev or cand.device != dev:
+        if self._device(tb.table.text) != dev or cand.device != dev:
             raise RuntimeError(f"ghmfc table form: the model, the candidates and the table must be on one device (table: {dev})")
         if self._tf.watch and not torch.cuda.is_current_stream_capturing():
             self.check_indices(wait=False)
         return GhmfcIndexedBatch(tb.mention, tb.table, cand.detach().to(torch.int64).contiguous())
+
+    def _device(self, *like) -> torch.device:
+        """the model's device (`ghmfc.model_device`): a model without parameters is where `like` is"""
+        from .ghmfc import model_device
+        return model_device(self, *like)
 
     def _status_words(self, device) -> torch.Tensor:
         t = self._tf.status.get(device)
@@ -334,8 +345,10 @@ class TableForm:
         st.watch.append((host, ev))
 
     def _entity_key(self, table: EntityTable):
-        fl = self.entity_encoder.final_layer
-        return ((fl.weight.data_ptr(), fl.weight._version, fl.bias.data_ptr(), fl.bias._version), self.precision, table._table_key())
+        """what the per-entity rows depend on: the entity weights' versions (none for an Identity final layer), the pooling, the
+        precision and the table"""
+        weights = tuple(x for p in self.entity_encoder.param_list() for x in (p.data_ptr(), p._version))
+        return (weights, self.cfg.entity_final_pooling, self.precision, table._table_key())
 
     @torch.no_grad()
     def _entity_rows(self, table: EntityTable) -> torch.Tensor:
@@ -345,28 +358,33 @@ class TableForm:
             lib = _lib.load()
             text, mask, tokens = _table_tensors(table)
             E, D = text.shape[0], text.shape[-1]
-            fl = self.entity_encoder.final_layer
-            w, b = fl.weight.detach().contiguous(), fl.bias.detach().contiguous()
+            w, b = [p.detach().contiguous() for p in self.entity_encoder.param_list()] or (None, None)
             nbytes = lib.drin_ghmfc_entity_rows_workspace_bytes(E, tokens, D)
             if nbytes == 0 and tokens > 0:
                 _lib.check(_lib.E_SHAPE)
             st.rows = None                                                     # release the stale one before allocating
             ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=text.device)
             rows = torch.empty(E, D, dtype=torch.float32, device=text.device)
-            _lib.check(lib.drin_ghmfc_entity_rows(_ptr(text), _ptr(mask), E, tokens, D, _ptr(w), _ptr(b), PRECISIONS[self.precision],
-                                                  _ptr(rows), _ptr(ws), nbytes, _stream(text.device)))
+            if self.cfg.entity_default:
+                _lib.check(lib.drin_ghmfc_entity_rows(_ptr(text), _ptr(mask), E, tokens, D, _ptr(w), _ptr(b), PRECISIONS[self.precision],
+                                                      _ptr(rows), _ptr(ws), nbytes, _stream(text.device)))
+            else:                                                              # "max" and / or an Identity final layer (w, b None)
+                _lib.check(lib.drin_ghmfc_entity_rows_ex(_ptr(text), _ptr(mask), E, tokens, D, _lib.ENTITY_POOLINGS[self.cfg.entity_final_pooling],
+                                                         _ptr(w), _ptr(b), PRECISIONS[self.precision], _ptr(rows), _ptr(ws), nbytes,
+                                                         _stream(text.device)))
             st.rows, st.rows_key = rows, key
             st.rows_builds += 1
         return st.rows
 
     @torch.no_grad()
     def _pooled_table(self, table: EntityTable) -> torch.Tensor:
-        """`[E, D]`: every entity's token mean (`drin_entity_token_mean`, the gathered step's kernel on the same rows), once per
-        table version - pooling depends on no weight; a pooled table is its own."""
+        """`[E, D]`: every entity's token mean or maximum (`drin_entity_token_mean` / `drin_entity_token_pool`, the gathered step's
+        kernel on the same rows), once per table version and pooling - pooling depends on no weight; a pooled table is its own."""
         text, mask, tokens = _table_tensors(table)
         if tokens == 0:
             return text
-        st, key = self._tf, table._table_key()
+        pooling = self.cfg.entity_final_pooling
+        st, key = self._tf, (table._table_key(), pooling)
         if st.pooled is None or st.pooled_key != key:
             lib = _lib.load()
             E, T, D = text.shape
@@ -375,8 +393,11 @@ class TableForm:
             step = 1 << 20
             for e0 in range(0, E, step):
                 n = min(E, e0 + step) - e0
-                _lib.check(lib.drin_entity_token_mean(_ptr(text[e0:e0 + n]), _ptr(mask[e0:e0 + n]), _ptr(pooled[e0:e0 + n]), n, T, D,
-                                                      _stream(text.device)))
+                args = _ptr(text[e0:e0 + n]), _ptr(mask[e0:e0 + n]), _ptr(pooled[e0:e0 + n]), n, T, D
+                if pooling == "avg":
+                    _lib.check(lib.drin_entity_token_mean(*args, _stream(text.device)))
+                else:
+                    _lib.check(lib.drin_entity_token_pool(*args, _lib.ENTITY_POOLINGS[pooling], _stream(text.device)))
             st.pooled, st.pooled_key = pooled, key
         return st.pooled
 
@@ -396,7 +417,7 @@ class TableForm:
         if self._tf.cache_on:
             scores = cosine_rows_indexed(mention, self._entity_rows(tb.table), tb.candidates, self.cfg.cosine_eps, status)
         else:
-            scores = entity_scores(mention, pooled_candidates(tb.table, tb.candidates, status), None, self.entity_encoder.final_layer,
-                                   self.cfg, self.precision)
+            pooled = pooled_candidates(tb.table, tb.candidates, status, self.cfg.entity_final_pooling)
+            scores = entity_scores(mention, pooled, None, self.entity_encoder.final_layer, self.cfg, self.precision)
         self._watch_indices(dev)
         return scores

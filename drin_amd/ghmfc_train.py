@@ -10,7 +10,7 @@ import torch
 
 from .attention import PRECISIONS, DropoutStream, MultiheadAttention, _check_core, _linear
 from .ghmfc import GhmfcConfig, Model, _MentionEncoder
-from .row_ops import cosine_rows, entity_token_mean, gate_mix, layer_norm_res, seq_max
+from .row_ops import cosine_rows, entity_token_pool, gate_mix, layer_norm_res, seq_max
 
 
 # ---- what TrainableModel and drin_amd.ghmfc_variants.VariantModel share ---------------------------------------------
@@ -47,10 +47,12 @@ def cross_attention(ca, seq_a, drop_a, seq_b, drop_b, precision: str, eps: float
 
 def entity_scores(mention, ef, emask, final, cfg: GhmfcConfig, precision: str) -> torch.Tensor:
     """EntityEncoder and the cosine (ghmfc.py:237-250, :297-298): scores [B, N] of mention [B, D] against the candidates.
-    ef: [B, N, D], or [B, N, T, D] with emask [B, N, T] (WikiMEL: the token mean first); final: the encoder's last linear."""
+    ef: [B, N, D], or [B, N, T, D] with emask [B, N, T] (WikiMEL: the token pool of `cfg.entity_final_pooling` first); final: the
+    encoder's last linear, or its nn.Identity (`entity_final_layer_name = "none"`): then no product, the cosine is of the pooled rows."""
     B, N, D = mention.shape[0], cfg.num_candidates, cfg.embed_dim
-    ent = entity_token_mean(ef, emask) if emask is not None else ef
-    ent = _linear(ent.view(B * N, D), final.weight, final.bias, PRECISIONS[precision]).view(B, N, D)
+    ent = entity_token_pool(ef, emask, cfg.entity_final_pooling) if emask is not None else ef
+    if not isinstance(final, torch.nn.Identity):
+        ent = _linear(ent.view(B * N, D), final.weight, final.bias, PRECISIONS[precision]).view(B, N, D)
     return cosine_rows(mention, ent, cfg.cosine_eps)
 
 

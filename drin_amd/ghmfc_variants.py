@@ -16,7 +16,7 @@ import torch
 from torch import nn
 
 from .attention import PRECISIONS, DropoutStream, _linear, multihead_attention_forward
-from .ghmfc import GhmfcConfig, _CrossAttention, _EntityEncoder
+from .ghmfc import GhmfcConfig, _CrossAttention, _EntityEncoder, model_device
 from .ghmfc_table import TableForm
 from .ghmfc_train import TrainableModel, attention_factory, check_setup, cross_attention, entity_scores
 from .row_ops import act_dropout, layer_norm_res, seq_max, span_mean
@@ -209,7 +209,7 @@ class VariantModel(TableForm, nn.Module):
         """table_form: items 5 and 6 are not the entity features (ef comes back as None: the caller reads the table)"""
         mf, mmask, begin, end, mimage = batch[:5]
         ef, emask = (None, None) if table_form else batch[5:7]
-        dev = self.entity_encoder.final_layer.weight.device
+        dev = model_device(self, mf)
         if dev.type != "cuda" or (isinstance(mf, torch.Tensor) and mf.device.type != "cuda"):
             raise RuntimeError("drin_amd.ghmfc_variants.VariantModel runs on the GPU only (no CPU fallback): move the model and the "
                                "batch with .cuda()")

@@ -243,3 +243,20 @@ def entity_token_mean(feat: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
     out = torch.empty(B, N, D, dtype=torch.float32, device=feat.device)
     _lib.check(_lib.load().drin_entity_token_mean(_ptr(feat), _ptr(mask), _ptr(out), B * N, T, D, _stream(feat.device)))
     return out
+
+
+def entity_token_pool(feat: torch.Tensor, mask: torch.Tensor, pooling: str) -> torch.Tensor:
+    """[B, N, D] = the mean ("avg": `entity_token_mean`, its call and bits) or the maximum ("max", `drin_entity_token_pool`) over
+    tokens 1 : ntok - 1 of feat [B, N, T, D].  The maximum is exact, a NaN inside the slice wins as in `torch.max`, and an entity with
+    fewer than 3 tokens gives a NaN row - where the reference's max raises IndexError.  An input: no gradient."""
+    if pooling not in _lib.ENTITY_POOLINGS:
+        raise ValueError(f"pooling {pooling!r} is none of {tuple(_lib.ENTITY_POOLINGS)}")
+    if pooling == "avg":
+        return entity_token_mean(feat, mask)
+    feat = _rows("entity_feature", feat)
+    B, N, T, D = feat.shape
+    mask = mask.to(feat.device, torch.int64).contiguous()
+    out = torch.empty(B, N, D, dtype=torch.float32, device=feat.device)
+    _lib.check(_lib.load().drin_entity_token_pool(_ptr(feat), _ptr(mask), _ptr(out), B * N, T, D, _lib.ENTITY_POOLINGS[pooling],
+                                                  _stream(feat.device)))
+    return out

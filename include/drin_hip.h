@@ -821,6 +821,22 @@ DRIN_API int drin_ghmfc_entity_rows(const float* text, const int64_t* mask, int6
                                     const float* w_entity, const float* b_entity, int32_t precision, float* rows, void* workspace,
                                     size_t workspace_bytes, void* stream);
 
+/* How the WikiMEL entity tokens are pooled (args.py entity_final_pooling, ghmfc.py:210-214,245-249): the mean or the maximum
+ * over tokens 1 : ntok - 1, ntok = sum(mask).  "bert default" has no id: the reference's own EntityEncoder constructor raises
+ * ValueError on it.  An empty slice (ntok 1 or 2) gives a NaN row under EITHER pooling: the mean is 0 / 0 there as in the
+ * reference, while the reference's max raises IndexError ("max(): Expected reduction dim 0 to have non-zero size"), which a
+ * kernel cannot do.  A NaN inside the slice wins the max, as torch.max; nothing outside the slice is read. */
+typedef enum { DRIN_POOL_AVG = 0, DRIN_POOL_MAX = 1 } drin_entity_pooling;
+
+/* drin_ghmfc_entity_rows with the entity encoder's settings: `pooling` (drin_entity_pooling; not read when entity_tokens = 0,
+ * as the reference pools WikiMEL tokens only) and entity_final_layer_name = "none" as w_entity == b_entity == NULL
+ * (final_layer = Identity): the pool then writes straight into `rows` (a pooled table is copied), there is no product and the
+ * workspace is not read.  Exactly one of the two being NULL is DRIN_E_NULL.  DRIN_POOL_AVG with both weights: the launches and
+ * the bits of drin_ghmfc_entity_rows.  drin_ghmfc_entity_rows_workspace_bytes is a sufficient size. */
+DRIN_API int drin_ghmfc_entity_rows_ex(const float* text, const int64_t* mask, int64_t num_entities, int32_t entity_tokens, int32_t width,
+                                       int32_t pooling, const float* w_entity, const float* b_entity, int32_t precision, float* rows,
+                                       void* workspace, size_t workspace_bytes, void* stream);
+
 /* The multi-head softmax-attention core on projected operands (what nn.MultiheadAttention runs between its in- and
  * out-projections, ghmfc.py:120,124): out[b, i, h] = softmax_j(q[b, i, h] . k[b, j, h] / sqrt(head_dim) + mask) v[b, j, h].
  * q [batch * q_len, E], k, v [batch * k_len, E], out [batch * q_len, E] are row-major with row strides ldq, ldk, ldv, ldo
@@ -966,6 +982,11 @@ DRIN_API int drin_cosine_rows_bwd(const float* x, const float* y, const float* d
  * int64 [pairs, tokens].  Fewer than 3 tokens: a NaN row, as the reference's empty mean. */
 DRIN_API int drin_entity_token_mean(const float* feat, const int64_t* mask, float* out, int64_t pairs, int32_t tokens,
                                     int32_t width, void* stream);
+/* The same slice with a pooling (drin_entity_pooling): DRIN_POOL_AVG is drin_entity_token_mean's launch and bits;
+ * DRIN_POOL_MAX: out[p, c] = max over t in [1, ntok - 1) of feat[p, t, c], exact (a NaN inside the slice wins, rows outside
+ * it are not read, an empty slice gives a NaN row where the reference raises IndexError).  fp32; tokens 1 .. 512. */
+DRIN_API int drin_entity_token_pool(const float* feat, const int64_t* mask, float* out, int64_t pairs, int32_t tokens, int32_t width,
+                                    int32_t pooling, void* stream);
 
 /* ---- the row operations of GHMFC's table form -------------------------------------------------- *
  * The entity side read through candidate ROWS of a device-resident table instead of gathered features: what the reference
@@ -983,6 +1004,11 @@ DRIN_API int drin_gather_rows(const float* table, const int64_t* index, int64_t 
 DRIN_API int drin_entity_token_mean_indexed(const float* text, const int64_t* mask, const int64_t* index, int64_t num_entities,
                                             float* out, int64_t pairs, int32_t tokens, int32_t width, int32_t* index_status,
                                             void* stream);
+/* drin_entity_token_pool of table row index[p] (clamped before any address is formed and reported, as above): the bits of the
+ * plain form on the gathered block; DRIN_POOL_AVG is drin_entity_token_mean_indexed. */
+DRIN_API int drin_entity_token_pool_indexed(const float* text, const int64_t* mask, const int64_t* index, int64_t num_entities,
+                                            float* out, int64_t pairs, int32_t tokens, int32_t width, int32_t pooling,
+                                            int32_t* index_status, void* stream);
 /* out[b, n] = cos(x[b, :], rows[index[b, n], :]); x [batch, width], rows [num_entities, width], index [batch, num_candidates]:
  * the bits of drin_cosine_rows_fwd on the gathered rows. */
 DRIN_API int drin_cosine_rows_indexed_fwd(const float* x, const float* rows, const int64_t* index, int64_t num_entities, float* out,

@@ -992,6 +992,45 @@ int drin_wgrad_probe(drin_wgrad_probe_args* p, void* stream) {
   return rc;
 }
 
+// The sizes a launcher of the layer-by-layer path refuses, asked of the launchers' own predicates among the argument checks: a
+// call of drin_forward* / drin_backward* runs to its end or is refused here, before its first launch - scores, gradients and
+// workspace untouched (include/drin_hip.h states the contract).  Past 65 535 mentions the path itself
+// runs (sliced launches, the flat pair grid); what does not:
+//   - the backward of the vector-edge update (k_edge_pre_vec_bwd_fu: one workgroup per mention, not sliced);
+//   - a pair-sized product of more rows than the exact-fp32 kernel's row tiles fit in one grid.  A product takes that kernel
+//     under DRIN_PREC_F32 and, under split-bf16, where its reduction length is no multiple of 32 (launch_gemm_nt,
+//     launch_gemm_nt_bf16x3, gemm_nn_takes_bf16x3); the products are walked below with their rows (M = batch * num_candidates).
+// both_types: both vertex types of a layer are live (two or more layers, or a traced forward of one); the dynamic edge update of
+// a layer runs under the same condition.
+static int layers_call_fits(const drin_config* c, bool backward, bool both_types, const char* who) {
+  const int64_t M = (int64_t)c->batch * c->num_candidates;
+  const int D = c->embed_dim, R = c->image_dim;
+  const bool edge_updates = c->dynamic_edges && both_types, vec_updates = c->vector_edges && edge_updates;
+  if (backward && vec_updates && !edge_pre_vec_bwd_fits(c->batch)) {
+    set_error("%s: batch = %d: the backward of the vector-edge update is built for at most %d mentions per call; split the batch", who,
+              c->batch, kMaxGridMentions);
+    return DRIN_E_SHAPE;
+  }
+  const bool x3 = split_bf16(c->precision);
+  int64_t rows = 0;   // of the largest product that runs exact fp32
+  auto exact_fp32 = [&](int64_t product_rows, int reduction) {
+    if ((!x3 || (reduction % 32)) && product_rows > rows) rows = product_rows;
+  };
+  exact_fp32(M, D), exact_fp32(M, R);                               // the entity vertex encoders (and the input gradients' dX)
+  if (c->num_layers >= 1) exact_fp32((both_types ? 2 : 1) * M, D);  // W_h over the live entity vertex types, and its dX
+  if (edge_updates) exact_fp32(2 * M, D);                           // W_v over both entity vertex types, and its dX
+  if (vec_updates) {
+    exact_fp32(4 * M, D);                                           // W_m over the four edge types, and its dX
+    if (backward) exact_fp32(2 * M, D / 2);                         // dfv W_v: the half-width update reduces over D / 2
+  }
+  if (!gemm_f32_rows_fit(rows)) {
+    set_error("%s: batch * num_candidates = %lld: the largest exact-fp32 product of the call has %lld rows, one such product takes "
+              "%lld; split the batch", who, (long long)M, (long long)rows, (long long)kF32MaxRows);
+    return DRIN_E_SHAPE;
+  }
+  return DRIN_OK;
+}
+
 int drin_forward(const drin_config* cfg, const drin_batch* batch, const drin_params* params, void* workspace,
                  size_t workspace_bytes, float* scores, int keep_for_backward, const drin_trace* trace, void* stream) {
   return drin_forward_staged(cfg, batch, params, workspace, workspace_bytes, scores, keep_for_backward, trace, nullptr, stream);
@@ -1017,6 +1056,7 @@ int drin_forward_staged_head(const drin_config* cfg, const drin_batch* batch, co
   DRIN_TRY(validate_params(cfg, params, rows));
   const int64_t* eidx = batch->entity_index;
   if (eidx) DRIN_TRY(indexed_supported(cfg, "drin_forward"));
+  DRIN_TRY(layers_call_fits(cfg, false, cfg->num_layers >= 2 || (trace != nullptr && cfg->num_layers >= 1), who));
   if (!scores) {
     set_error("scores is NULL");
     return DRIN_E_NULL;
@@ -1341,6 +1381,7 @@ int drin_backward_head(const drin_config* cfg, const drin_batch* batch, const dr
   const drin_param_grads* grads = grads_in ? grads_in : &kNoGrads;
   const int64_t* eidx = batch->entity_index;
   if (eidx) DRIN_TRY(indexed_supported(cfg, "drin_backward"));
+  DRIN_TRY(layers_call_fits(cfg, true, cfg->num_layers >= 2, who));
   if (input_grads) DRIN_TRY(validate_input_grads(cfg, batch, input_grads));
   Layout L;
   L.build(*cfg, true);

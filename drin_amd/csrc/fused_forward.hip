@@ -733,6 +733,13 @@ int drin_forward_prepared_head(const drin_config* cfg, const drin_batch* b, cons
   DRIN_TRY(validate_config(cfg));
   DRIN_TRY(validate_head(head, "drin_forward_prepared_head"));
   DRIN_TRY(fused_supported(cfg));
+  // (launch_entity_stream's own limit, asked before the first launch: the image product, the folded head and the q product run
+  //  ahead of the stream pass and would have written the workspace by the time it refused)
+  if (!entity_stream_fits(cfg->batch)) {
+    set_error("drin_forward_prepared: batch = %d: the entity stream pass is built for at most %d mentions per call; split the batch",
+              cfg->batch, kMaxGridMentions);
+    return DRIN_E_SHAPE;
+  }
   if (!b || !params || !prepared || !workspace || !scores) {
     set_error("drin_forward_prepared: NULL argument");
     return DRIN_E_NULL;

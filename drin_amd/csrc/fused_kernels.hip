@@ -390,7 +390,7 @@ static int launch_stream_t(const StreamArgs& a, hipStream_t st) {
 
 int launch_entity_stream(const StreamArgs& a, hipStream_t st) {
   if (a.B <= 0) return DRIN_OK;
-  if (a.B > 65535) {
+  if (!entity_stream_fits(a.B)) {
     set_error("entity_stream: batch %d exceeds the grid limit; split the batch", a.B);
     return DRIN_E_SHAPE;
   }

@@ -280,6 +280,16 @@ static int launch(const float* A, int64_t lda, const float* B, int64_t ldb, cons
   return DRIN_OK;
 }
 
+// (gemm_f32_rows_fit, scratch_sizes.h: the predicate the entry points ask before their first launch)
+static int check_f32_rows(int64_t rows, const char* what) {
+  if (!gemm_f32_rows_fit(rows)) {
+    set_error("%s: %lld rows exceed the %lld of one exact-fp32 product (the grid limit of its row tiles); split the batch", what,
+              (long long)rows, (long long)kF32MaxRows);
+    return DRIN_E_SHAPE;
+  }
+  return DRIN_OK;
+}
+
 static int check_precision(int precision, const char* what) {
   if (precision != DRIN_PREC_F32) {
     set_error("%s: precision %d is not built in the generic GEMM (fp32 MFMA only)", what, precision);
@@ -585,6 +595,7 @@ int launch_gemm_nt(const NtProduct& p, int precision, hipStream_t st, GemmScratc
   if (M <= kMentionSizedMaxRows)
     return launch<64, 64, false, false>(x, ldx, w, ldw, bias, y, ldy, M, N, K, 1, accumulate ? GEMM_ACCUMULATE : 0, st,
                                         "gemm_nt");
+  DRIN_TRY(check_f32_rows(M, "gemm_nt"));
   return launch<128, 128, false, false>(x, ldx, w, ldw, bias, y, ldy, M, N, K, 1, accumulate ? GEMM_ACCUMULATE : 0, st,
                                         "gemm_nt");
 }
@@ -646,6 +657,7 @@ int launch_gemm_nn(const NnProduct& p, int precision, hipStream_t st, GemmScratc
   if (M <= kMentionSizedMaxRows)
     return launch<64, 64, false, true>(x, ldx, w, ldw, nullptr, y, ldy, M, N, K, 1, accumulate ? GEMM_ACCUMULATE : 0, st,
                                        "gemm_nn");
+  DRIN_TRY(check_f32_rows(M, "gemm_nn"));
   return launch<128, 128, false, true>(x, ldx, w, ldw, nullptr, y, ldy, M, N, K, 1, accumulate ? GEMM_ACCUMULATE : 0, st,
                                        "gemm_nn");
 }

@@ -112,6 +112,12 @@ inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 inline dim3 pair_grid(int B, int N) {
   return (B > 1 && B <= 65535) ? dim3((unsigned)cdiv(N, 4), (unsigned)B) : dim3((unsigned)cdiv((int64_t)B * N, 4));
 }
+// mentions of one launch of a (column quads, mention, ...) grid that its launcher does not slice: the grid.y limit.  Such a
+// launcher refuses past it, and the entry points that reach it ask the same predicate among their argument checks (api.hip:
+// layers_call_fits): a size is refused before the first launch of a call or not at all
+constexpr int kMaxGridMentions = 65535;
+inline bool edge_pre_vec_bwd_fits(int B) { return B <= kMaxGridMentions; }   // k_edge_pre_vec_bwd_fu (vector_kernels.hip)
+inline bool entity_stream_fits(int B) { return B <= kMaxGridMentions; }      // k_entity_stream (fused_kernels.hip); drin_forward_prepared asks
 
 // ---- pooling and static edges of the layer-by-layer entry points (api.hip; Layout, Pooled: layout.h) -------------------
 struct Layout;

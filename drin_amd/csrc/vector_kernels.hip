@@ -186,7 +186,7 @@ __global__ void __launch_bounds__(64) k_edge_pre_vec_bwd_fu(const float* __restr
 int launch_edge_pre_vec_bwd(const float* dpre, float* dfu, float* dfv, int B, int N, int D, hipStream_t st) {
   const int64_t M = (int64_t)B * N;
   if (M <= 0) return DRIN_OK;
-  if (B > 65535) {
+  if (!edge_pre_vec_bwd_fits(B)) {
     set_error("edge_pre_vec_bwd: batch %d exceeds the grid limit", B);
     return DRIN_E_SHAPE;
   }

@@ -304,7 +304,19 @@ DRIN_API int drin_linear_bwd(const float* x, const float* w, const float* dy, fl
 
 /* Model.forward (drin/model.py:164-209): scores[B, N] = cos(mt'', et'').
  * `keep_for_backward` != 0 lays the intermediates backward needs out in `workspace`, which must
- * then stay untouched until drin_backward returns.  `trace` may be NULL. */
+ * then stay untouched until drin_backward returns.  `trace` may be NULL.
+ *
+ * Sizes: batch * num_candidates <= 2^30.  A call of the layer-by-layer entry points (drin_forward, drin_forward_staged[_head],
+ * drin_backward, drin_backward_staged, drin_backward_ex, drin_backward_head) either returns DRIN_OK with the right values or
+ * is refused among its argument checks, BEFORE its first launch: scores, gradients and workspace are then untouched.  More than
+ * 65 535 mentions in one call run (the per-mention launches are cut into slices of 65 535 mentions, the one-wave-per-pair
+ * kernels take a flat grid) with two exceptions, both DRIN_E_SHAPE ("split the batch"):
+ *   - drin_backward* with vector edges whose update is live (dynamic edges, two or more layers) above 65 535 mentions;
+ *   - a call one of whose products has more than 65 535 * 128 rows and runs exact fp32: every product under DRIN_PREC_F32, under
+ *     split-bf16 those whose reduction length is no multiple of 32.  With M = batch * num_candidates the products have M rows
+ *     (the entity encoders, over embed_dim and image_dim), 2 M (the layers' W_h and W_v over both entity vertex types, over
+ *     embed_dim; M in a single untraced layer) and, with live vector-edge updates, 4 M (W_m, over embed_dim) and in the backward
+ *     2 M over embed_dim / 2. */
 DRIN_API int drin_forward(const drin_config* cfg, const drin_batch* batch, const drin_params* params,
                  void* workspace, size_t workspace_bytes, float* scores, int keep_for_backward,
                  const drin_trace* trace, void* stream);
@@ -407,7 +419,9 @@ DRIN_API int drin_width_class(const drin_config* cfg, int family);
  *   drin_prepare           folds the weights into `prepared` (drin_prepared_bytes; caller-owned, reusable
  *                          for every batch until a parameter changes)
  *   drin_forward_prepared  Model.forward (drin/model.py:164-209) without autograd state
- * drin_fused_supported returns DRIN_OK when `cfg` can take this path (else use drin_forward). */
+ * drin_fused_supported returns DRIN_OK when `cfg` can take this path (else use drin_forward).
+ * drin_forward_prepared and drin_forward_cached take at most 65 535 mentions per call and refuse more (DRIN_E_SHAPE) among their
+ * argument checks, before the first launch. */
 DRIN_API int drin_fused_supported(const drin_config* cfg);
 DRIN_API size_t drin_prepared_bytes(const drin_config* cfg);
 DRIN_API size_t drin_fused_workspace_bytes(const drin_config* cfg);

@@ -279,3 +279,140 @@ def workgroups_of(cfg, B, cached, precision="f32", num_entities=0):
     return workgroups_per_mention(cfg.gcn_embed_dim, cfg.resnet_embed_dim, B, cfg.num_candidates_model, cached,
                                   cfg.gcn_vertex_activation, precision=prec, num_entities=num_entities,
                                   entity_tokens=cfg.max_entity_attr_token_len if cfg.token_level_entities else 0)
+
+
+# ---- callers of single entry points that several GPU test files share (tests/test_gpu_ghmfc_train.py, test_gpu_mention_rows.py,
+# test_gpu_step_kernels.py, test_gpu_launch_caps.py): outputs and scratch are filled with NaN or a sentinel before the call ----------
+import ctypes as C  # noqa: E402
+
+from drin_amd import _lib, row_ops  # noqa: E402
+from tests.step_restatement import cosine_rows64_grads  # noqa: E402
+
+DEV = "cuda"
+KERNEL_TOL = 1e-5                                                     # fp32-FMA kernels, DESIGN.md section 16
+NAN = float("nan")
+ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
+stream = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)   # noqa: E731
+bits = lambda t: t.contiguous().view(torch.int32)                      # noqa: E731  (NaN positions count)
+
+
+def rel_err(got, ref, what, scale=None):
+    ref = ref.double()
+    scale = ref.abs().max().item() if scale is None else scale
+    err = (got.double() - ref).abs().max().item()
+    print(f"{what}: max err {err:.3e} (max |ref| {scale:.3e}) ratio {err / max(scale, 1e-300):.2e}")
+    return err / max(scale, 1e-300)
+
+
+def ln_bwd(x, res, mean, rstd, gamma, dy, sums=True):
+    lib = _lib.load()
+    rows, E = x.shape
+    dh = torch.full_like(x, float("nan"))
+    dgamma, dbeta = (torch.full((E,), float("nan"), device=DEV) for _ in range(2)) if sums else (None, None)
+    floats = lib.drin_layernorm_res_bwd_scratch_floats(rows, E)
+    scratch = torch.full((floats,), float("nan"), device=DEV) if sums else None
+    _lib.check(lib.drin_layernorm_res_bwd(ptr(x), ptr(res), ptr(mean), ptr(rstd), ptr(gamma), ptr(dy), ptr(dh), ptr(dgamma), ptr(dbeta),
+                                          ptr(scratch), floats if sums else 0, rows, E, stream()))
+    return dh, dgamma, dbeta
+
+
+def mention_rows_fwd(raw, enc, start, end, representation):
+    """(edge_row, vertex_row, idx [2, B, D] int32) of drin_mention_rows_fwd; raw fp32 or bf16.  Outputs are prefilled with a
+    sentinel: a row the kernel skipped shows."""
+    B, L, D = raw.shape
+    edge, vert = torch.full((B, D), 7.0, device=DEV), torch.full((B, D), 7.0, device=DEV)
+    idx = torch.full((2, B, D), -5, dtype=torch.int32, device=DEV)
+    dtype = _lib.FEAT_BF16 if raw.dtype == torch.bfloat16 else _lib.FEAT_F32
+    _lib.check(_lib.load().drin_mention_rows_fwd(ptr(raw), dtype, ptr(enc), ptr(start), ptr(end), representation, ptr(edge), ptr(vert),
+                                                 ptr(idx), B, L, D, stream()))
+    return edge, vert, idx
+
+
+def mention_rows_bwd(g_edge, g_vert, start, end, idx, representation, has_encoded, shape, want_raw=True, want_enc=True):
+    """(d_raw, d_enc) of drin_mention_rows_bwd, prefilled with NaN: an element the kernel did not write shows."""
+    B, L, D = shape
+    d_raw = torch.full(shape, float("nan"), device=DEV) if want_raw else None
+    d_enc = torch.full(shape, float("nan"), device=DEV) if want_enc else None
+    _lib.check(_lib.load().drin_mention_rows_bwd(ptr(g_edge), ptr(g_vert), ptr(start), ptr(end), ptr(idx), representation, has_encoded,
+                                                 ptr(d_raw), ptr(d_enc), B, L, D, stream()))
+    return d_raw, d_enc
+
+
+def lowest_argmax(x):
+    """[B, D]: the lowest position that attains the max over dim 1; the lowest NaN position where the column holds one."""
+    L = x.shape[1]
+    pos = torch.arange(L, device=x.device)[None, :, None].expand_as(x)
+    nan = torch.isnan(x)
+    hit = torch.where(nan.any(1, keepdim=True), nan, x == x.nan_to_num(float("-inf")).max(1, keepdim=True)[0])
+    return torch.where(hit, pos, L).min(1)[0]
+
+
+def cos_case(B, N, D, seed):
+    """x [B, D], y [B, N, D] = a x + noise (cosines of 0.3 ... 0.8, none near 0), dout [B, N] with exact zeros in it."""
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(B, D, generator=g)
+    a = 0.3 + torch.rand(B, N, 1, generator=g)
+    y = a * x[:, None, :] + torch.randn(B, N, D, generator=g)
+    dout = torch.randn(B, N, generator=g)
+    dout.view(-1)[1::3] = 0.0
+    return x, y, dout
+
+
+def cos_fwd(x, y, eps):
+    B, N, D = y.shape
+    out = torch.full((B, N), NAN, device=DEV)
+    _lib.check(_lib.load().drin_cosine_rows_fwd(ptr(x), ptr(y), ptr(out), B, N, D, eps, stream()))
+    return out
+
+
+def cos_bwd(x, y, dout, eps, scratch_floats=None):
+    B, N, D = y.shape
+    floats = 3 * B * N if scratch_floats is None else scratch_floats
+    dx, dy = torch.full_like(x, NAN), torch.full_like(y, NAN)
+    scratch = torch.full((max(floats, 1),), NAN, device=DEV)
+    status = _lib.load().drin_cosine_rows_bwd(ptr(x), ptr(y), ptr(dout), ptr(dx), ptr(dy), ptr(scratch), floats, B, N, D, eps, stream())
+    return status, dx, dy
+
+
+def rows_ratio(got, ref, what):
+    """max over rows of max|got - ref| / max|ref| of that row; a row whose reference is all zero must be exactly zero."""
+    got, ref = got.reshape(-1, got.shape[-1]), ref.reshape(-1, ref.shape[-1]).to(got.device)
+    assert not torch.isnan(got).any(), what
+    scale = ref.abs().amax(1)
+    err = (got.double() - ref).abs().amax(1)
+    zero = scale == 0
+    assert torch.count_nonzero(got[zero]).item() == 0, what
+    ratio = (err[~zero] / scale[~zero]).max().item() if (~zero).any() else 0.0
+    print(f"{what}: worst row ratio {ratio:.2e} over {int((~zero).sum())} rows (row maxima {scale[~zero].min().item() if (~zero).any() else 0:.2e} ... "
+          f"{scale.max().item():.2e}), {int(zero.sum())} all-zero rows")
+    return ratio
+
+
+def check_cosine(x, y, dout, eps, tag):
+    out64, dx64, dy64 = cosine_rows64_grads(x, y, dout, eps)
+    xd, yd, gd = x.to(DEV), y.to(DEV), dout.to(DEV)
+    B, N, D = y.shape
+    out = cos_fwd(xd, yd, eps)
+    assert not torch.isnan(out).any()
+    ferr = (out.double().cpu() - out64).abs().max().item()
+    print(f"{tag}: forward max err {ferr:.2e} of max |ref| {out64.abs().max().item():.2e}")
+    assert ferr <= KERNEL_TOL * out64.abs().max().item() or (out64 == 0).all() and ferr == 0.0
+    status, dx, dy = cos_bwd(xd, yd, gd, eps)
+    _lib.check(status)
+    assert rows_ratio(dx, dx64, tag + " dx") <= KERNEL_TOL
+    assert rows_ratio(dy, dy64, tag + " dy") <= KERNEL_TOL
+    dead = (gd == 0).reshape(-1)
+    assert dead.any() or B * N == 1
+    assert torch.count_nonzero(dy.reshape(B * N, D)[dead]).item() == 0   # dout = 0: exactly-zero dy rows
+    _, dx2, dy2 = cos_bwd(xd, yd, gd, eps)
+    assert torch.equal(bits(dx), bits(dx2)) and torch.equal(bits(dy), bits(dy2)) and torch.equal(bits(out), bits(cos_fwd(xd, yd, eps)))
+    # the autograd edge GHMFC trains through: the same bits
+    xl, yl = xd.clone().requires_grad_(True), yd.clone().requires_grad_(True)
+    o = row_ops.cosine_rows(xl, yl, eps)
+    o.backward(gd)
+    assert torch.equal(bits(o.detach()), bits(out)) and torch.equal(bits(xl.grad), bits(dx)) and torch.equal(bits(yl.grad), bits(dy))
+    # one float of scratch short: refused, nothing written
+    status, ndx, ndy = cos_bwd(xd, yd, gd, eps, scratch_floats=3 * B * N - 1)
+    torch.cuda.synchronize()
+    assert status == _lib.E_WORKSPACE and torch.isnan(ndx).all() and torch.isnan(ndy).all()
+    return out, dx, dy

@@ -17,6 +17,7 @@ from drin_amd.ghmfc_train import TrainableModel
 from tests.ghmfc_inputs import CASES, KEYS, ghmfc_inputs, geometry
 from tests.ghmfc_train_inputs import TRAIN_CASES, train_inputs
 from tests.ghmfc_train_restatement import ghmfc_train_scores
+from tests.helpers import ln_bwd, rel_err
 from tests.test_ghmfc_host import as_tensors, cfg_for
 
 pytestmark = pytest.mark.gpu
@@ -28,27 +29,7 @@ ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E7
 stream = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)   # noqa: E731
 
 
-def rel_err(got, ref, what, scale=None):
-    ref = ref.double()
-    scale = ref.abs().max().item() if scale is None else scale
-    err = (got.double() - ref).abs().max().item()
-    print(f"{what}: max err {err:.3e} (max |ref| {scale:.3e}) ratio {err / max(scale, 1e-300):.2e}")
-    return err / max(scale, 1e-300)
-
-
 # ---- LayerNorm with a fused residual -----------------------------------------------------------------------
-def ln_bwd(x, res, mean, rstd, gamma, dy, sums=True):
-    lib = _lib.load()
-    rows, E = x.shape
-    dh = torch.full_like(x, float("nan"))
-    dgamma, dbeta = (torch.full((E,), float("nan"), device=DEV) for _ in range(2)) if sums else (None, None)
-    floats = lib.drin_layernorm_res_bwd_scratch_floats(rows, E)
-    scratch = torch.full((floats,), float("nan"), device=DEV) if sums else None
-    _lib.check(lib.drin_layernorm_res_bwd(ptr(x), ptr(res), ptr(mean), ptr(rstd), ptr(gamma), ptr(dy), ptr(dh), ptr(dgamma), ptr(dbeta),
-                                          ptr(scratch), floats if sums else 0, rows, E, stream()))
-    return dh, dgamma, dbeta
-
-
 @pytest.mark.parametrize("with_res", [False, True])
 @pytest.mark.parametrize("rows,E", [(1, 16), (5, 260), (1000, 768), (37, 2048)])
 def test_layernorm_backward_against_fp64(rows, E, with_res):

@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from drin_amd import _lib
+from tests.helpers import lowest_argmax, mention_rows_bwd, mention_rows_fwd
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -19,39 +20,8 @@ ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E7
 stream = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)   # noqa: E731
 
 
-def mention_rows_fwd(raw, enc, start, end, representation):
-    """(edge_row, vertex_row, idx [2, B, D] int32) of drin_mention_rows_fwd; raw fp32 or bf16.  Outputs are prefilled with a
-    sentinel: a row the kernel skipped shows."""
-    B, L, D = raw.shape
-    edge, vert = torch.full((B, D), 7.0, device=DEV), torch.full((B, D), 7.0, device=DEV)
-    idx = torch.full((2, B, D), -5, dtype=torch.int32, device=DEV)
-    dtype = _lib.FEAT_BF16 if raw.dtype == torch.bfloat16 else _lib.FEAT_F32
-    _lib.check(_lib.load().drin_mention_rows_fwd(ptr(raw), dtype, ptr(enc), ptr(start), ptr(end), representation, ptr(edge), ptr(vert),
-                                                 ptr(idx), B, L, D, stream()))
-    return edge, vert, idx
-
-
-def mention_rows_bwd(g_edge, g_vert, start, end, idx, representation, has_encoded, shape, want_raw=True, want_enc=True):
-    """(d_raw, d_enc) of drin_mention_rows_bwd, prefilled with NaN: an element the kernel did not write shows."""
-    B, L, D = shape
-    d_raw = torch.full(shape, float("nan"), device=DEV) if want_raw else None
-    d_enc = torch.full(shape, float("nan"), device=DEV) if want_enc else None
-    _lib.check(_lib.load().drin_mention_rows_bwd(ptr(g_edge), ptr(g_vert), ptr(start), ptr(end), ptr(idx), representation, has_encoded,
-                                                 ptr(d_raw), ptr(d_enc), B, L, D, stream()))
-    return d_raw, d_enc
-
-
 def bits(t):
     return t.contiguous().view(torch.int32)
-
-
-def lowest_argmax(x):
-    """[B, D]: the lowest position that attains the max over dim 1; the lowest NaN position where the column holds one."""
-    L = x.shape[1]
-    pos = torch.arange(L, device=x.device)[None, :, None].expand_as(x)
-    nan = torch.isnan(x)
-    hit = torch.where(nan.any(1, keepdim=True), nan, x == x.nan_to_num(float("-inf")).max(1, keepdim=True)[0])
-    return torch.where(hit, pos, L).min(1)[0]
 
 
 def planted(B, L, D, seed):

@@ -17,6 +17,7 @@ from drin_amd.model import Model, _param_list
 from drin_amd.train import LibraryAdam
 from oracle import drin_oracle as O
 from oracle.cases import TINY
+from tests.helpers import check_cosine, cos_bwd, cos_case, cos_fwd, rows_ratio
 from tests.step_restatement import cosine_rows64_grads, triplet_counts
 
 pytestmark = pytest.mark.gpu
@@ -303,77 +304,6 @@ def test_library_adam_with_its_own_betas_eps_and_a_rewritten_lr():
 COS_SHAPES = [(1, 1, 4), (5, 3, 4), (1, 4, 252), (5, 5, 252), (1, 3, 256), (5, 101, 256), (1, 1, 260), (5, 4, 260), (1, 101, 512),
               (5, 5, 512), (1, 4, 516), (5, 3, 516), (1, 5, 768), (5, 101, 768), (1, 3, 772), (5, 1, 772), (1, 101, 1024), (5, 4, 1024),
               (5, 5, 1024), (5, 3, 768)]                              # D4 = 1, 63, 64, 65, 128, 129, 192, 193, 256; every N of {1, 3, 4, 5, 101}
-
-
-def cos_case(B, N, D, seed):
-    """x [B, D], y [B, N, D] = a x + noise (cosines of 0.3 ... 0.8, none near 0), dout [B, N] with exact zeros in it."""
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randn(B, D, generator=g)
-    a = 0.3 + torch.rand(B, N, 1, generator=g)
-    y = a * x[:, None, :] + torch.randn(B, N, D, generator=g)
-    dout = torch.randn(B, N, generator=g)
-    dout.view(-1)[1::3] = 0.0
-    return x, y, dout
-
-
-def cos_fwd(x, y, eps):
-    B, N, D = y.shape
-    out = torch.full((B, N), NAN, device=DEV)
-    _lib.check(_lib.load().drin_cosine_rows_fwd(ptr(x), ptr(y), ptr(out), B, N, D, eps, stream()))
-    return out
-
-
-def cos_bwd(x, y, dout, eps, scratch_floats=None):
-    B, N, D = y.shape
-    floats = 3 * B * N if scratch_floats is None else scratch_floats
-    dx, dy = torch.full_like(x, NAN), torch.full_like(y, NAN)
-    scratch = torch.full((max(floats, 1),), NAN, device=DEV)
-    status = _lib.load().drin_cosine_rows_bwd(ptr(x), ptr(y), ptr(dout), ptr(dx), ptr(dy), ptr(scratch), floats, B, N, D, eps, stream())
-    return status, dx, dy
-
-
-def rows_ratio(got, ref, what):
-    """max over rows of max|got - ref| / max|ref| of that row; a row whose reference is all zero must be exactly zero."""
-    got, ref = got.reshape(-1, got.shape[-1]), ref.reshape(-1, ref.shape[-1]).to(got.device)
-    assert not torch.isnan(got).any(), what
-    scale = ref.abs().amax(1)
-    err = (got.double() - ref).abs().amax(1)
-    zero = scale == 0
-    assert torch.count_nonzero(got[zero]).item() == 0, what
-    ratio = (err[~zero] / scale[~zero]).max().item() if (~zero).any() else 0.0
-    print(f"{what}: worst row ratio {ratio:.2e} over {int((~zero).sum())} rows (row maxima {scale[~zero].min().item() if (~zero).any() else 0:.2e} ... "
-          f"{scale.max().item():.2e}), {int(zero.sum())} all-zero rows")
-    return ratio
-
-
-def check_cosine(x, y, dout, eps, tag):
-    out64, dx64, dy64 = cosine_rows64_grads(x, y, dout, eps)
-    xd, yd, gd = x.to(DEV), y.to(DEV), dout.to(DEV)
-    B, N, D = y.shape
-    out = cos_fwd(xd, yd, eps)
-    assert not torch.isnan(out).any()
-    ferr = (out.double().cpu() - out64).abs().max().item()
-    print(f"{tag}: forward max err {ferr:.2e} of max |ref| {out64.abs().max().item():.2e}")
-    assert ferr <= KERNEL_TOL * out64.abs().max().item() or (out64 == 0).all() and ferr == 0.0
-    status, dx, dy = cos_bwd(xd, yd, gd, eps)
-    _lib.check(status)
-    assert rows_ratio(dx, dx64, tag + " dx") <= KERNEL_TOL
-    assert rows_ratio(dy, dy64, tag + " dy") <= KERNEL_TOL
-    dead = (gd == 0).reshape(-1)
-    assert dead.any() or B * N == 1
-    assert torch.count_nonzero(dy.reshape(B * N, D)[dead]).item() == 0   # dout = 0: exactly-zero dy rows
-    _, dx2, dy2 = cos_bwd(xd, yd, gd, eps)
-    assert torch.equal(bits(dx), bits(dx2)) and torch.equal(bits(dy), bits(dy2)) and torch.equal(bits(out), bits(cos_fwd(xd, yd, eps)))
-    # the autograd edge GHMFC trains through: the same bits
-    xl, yl = xd.clone().requires_grad_(True), yd.clone().requires_grad_(True)
-    o = row_ops.cosine_rows(xl, yl, eps)
-    o.backward(gd)
-    assert torch.equal(bits(o.detach()), bits(out)) and torch.equal(bits(xl.grad), bits(dx)) and torch.equal(bits(yl.grad), bits(dy))
-    # one float of scratch short: refused, nothing written
-    status, ndx, ndy = cos_bwd(xd, yd, gd, eps, scratch_floats=3 * B * N - 1)
-    torch.cuda.synchronize()
-    assert status == _lib.E_WORKSPACE and torch.isnan(ndx).all() and torch.isnan(ndy).all()
-    return out, dx, dy
 
 
 @pytest.mark.parametrize("B,N,D", COS_SHAPES)

@@ -470,7 +470,7 @@ static int indexed_supported(const drin_config* c, const char* who) {
   const bool x3 = c->precision == DRIN_PREC_BF16X3 || c->precision == DRIN_PREC_BF16X3_ALL;
   if (c->num_entities <= 0 || c->entity_tokens != 0 || c->entity_image_inner > 1 || c->entity_object_inner > 1 ||
       c->entity_objects != 1 || c->vector_edges || !x3 || M < 1024 || (D % 32) || (R % 32) || D < 128 || R < 128 ||
-      R > 2048 || c->batch > 65535) {
+      R > 2048 || c->batch > kMaxGridY) {
     set_error("%s: entity_index needs pooled entity text tables (entity_tokens = 0, num_entities > 0), one object per entity, "
               "inner dims <= 1, scalar edges, split-bf16 precision, D and R multiples of 32 (>= 128, R <= 2048) and at least "
               "1024 pairs; gather on the caller side otherwise", who);
@@ -1008,7 +1008,7 @@ static int layers_call_fits(const drin_config* c, bool backward, bool both_types
   const bool edge_updates = c->dynamic_edges && both_types, vec_updates = c->vector_edges && edge_updates;
   if (backward && vec_updates && !edge_pre_vec_bwd_fits(c->batch)) {
     set_error("%s: batch = %d: the backward of the vector-edge update is built for at most %d mentions per call; split the batch", who,
-              c->batch, kMaxGridMentions);
+              c->batch, kMaxGridY);
     return DRIN_E_SHAPE;
   }
   const bool x3 = split_bf16(c->precision);
@@ -1184,16 +1184,7 @@ int drin_forward_staged_head(const drin_config* cfg, const drin_batch* batch, co
         DRIN_TRY(launch_entity_aggregate_vec(e_ti, mt, e_ii, mi, ei, agg_e + (size_t)M * D, B, N, D, st));
       }
     } else {
-      if (B <= 65535) {
-        DRIN_TRY(launch_layer_aggregate(e, (int64_t)ES, mt, et, agg_m, agg_e, B, N, D, live_image, st));
-      } else {
-        DRIN_TRY(launch_mention_aggregate(e_tt, et, e_ti, ei, mt, agg_m, B, N, D, st));
-        DRIN_TRY(launch_entity_aggregate(e_tt, mt, e_it, mi, et, agg_e, B, N, D, st));
-        if (live_image) {
-          DRIN_TRY(launch_mention_aggregate(e_it, et, e_ii, ei, mi, agg_m + (size_t)B * D, B, N, D, st));
-          DRIN_TRY(launch_entity_aggregate(e_ti, mt, e_ii, mi, ei, agg_e + (size_t)M * D, B, N, D, st));
-        }
-      }
+      DRIN_TRY(launch_layer_aggregate(e, (int64_t)ES, mt, et, agg_m, agg_e, B, N, D, live_image, st));
     }
     const int types = live_image ? 2 : 1;
     // shared W_h + LayerNorm + GELU for all vertex types of the layer (model.py:128)
@@ -1507,18 +1498,11 @@ int drin_backward_head(const drin_config* cfg, const drin_batch* batch, const dr
     } else if (edge_update) {
       // (d) e'_k = sigmoid(mean_d(fu fv) + e_k)  (model.py:148-153,133)
       const float* fu = ws + L.fu[l];
-      const float* fv = ws + L.fv[l];
       const float inv_d = 1.0f / (float)D;
       // dpre = g e' (1 - e');  dfv_t = (dpre_tt fu_t + dpre_it fu_i) / D ; dfv_i = (dpre_ti fu_t + dpre_ii fu_i) / D: one pass
       DRIN_TRY(launch_edge_update_bwd(g_e[cur], from_z ? ws + L.edge_z[l] : ws + L.edges[l + 1], fu, dpre, dfv, B, N, D, inv_d, st, act_eb));
-      // dfu_t = sum_n (dpre_tt fv_t + dpre_ti fv_i) / D ; dfu_i = sum_n (dpre_it fv_t + dpre_ii fv_i) / D
-      // (B <= 65535: nothing reads dfu before the mention side of the aggregation backward below, (f): the two reductions
-      //  share ONE launch there - and dW_u, which reads dfu, is collected behind it)
-      if (B > 65535) {
-        DRIN_TRY(launch_mention_reduce(dpre, fv, dpre + M, fv + MD, nullptr, dfu, B, N, D, inv_d, st));
-        DRIN_TRY(launch_mention_reduce(dpre + 2 * M, fv, dpre + 3 * M, fv + MD, nullptr, dfu + BD, B, N, D, inv_d, st));
-        DRIN_TRY(dw.add({{dfu, D}, {mt, D}, G.w_u, D, 2 * (int64_t)B, D, D, nullptr, G.b_u}));
-      }
+      // dfu_t = sum_n (dpre_tt fv_t + dpre_ti fv_i) / D ; dfu_i = sum_n (dpre_it fv_t + dpre_ii fv_i) / D: with the mention
+      // side of the aggregation backward, (f) below, in ONE launch; dW_u, which reads dfu, is collected behind it
       DRIN_TRY(dw.add({{dfv, D}, {et, D}, G.w_v, D, 2 * (int64_t)M, D, D, nullptr, G.b_v}));
       de_extra = dpre;
     } else if (!cfg->dynamic_edges && have_edge) {
@@ -1542,16 +1526,13 @@ int drin_backward_head(const drin_config* cfg, const drin_batch* batch, const dr
       DRIN_TRY(launch_entity_side_bwd(dA_mt, dA_mi, dA_et, dA_ei, mt, mi, et, ei, e, de_extra, ge_next, ge_next + MD,
                                       g_e[nxt], B, N, D, cfg->edge_enabled, edge_update, st));
       // (f) mention side
-      if (B <= 65535 && edge_update) {
+      if (edge_update) {
         const float* fv = ws + L.fv[l];
         DRIN_TRY(launch_mention_reduce2_pair(dpre, fv, fv + MD, nullptr, nullptr, dfu, dfu + BD, 1.0f / (float)D,          // (d): dfu
                                              e, dA_et, dA_ei, dA_mt, dA_mi, gm_next, gm_next + BD, 1.0f, B, N, D, st));   // (f)
         DRIN_TRY(dw.add({{dfu, D}, {mt, D}, G.w_u, D, 2 * (int64_t)B, D, D, nullptr, G.b_u}));
-      } else if (B <= 65535) {
-        DRIN_TRY(launch_mention_reduce2(e, dA_et, dA_ei, dA_mt, dA_mi, gm_next, gm_next + BD, B, N, D, 1.0f, st));
       } else {
-        DRIN_TRY(launch_mention_reduce(e, dA_et, e + M, dA_ei, dA_mt, gm_next, B, N, D, 1.0f, st));
-        DRIN_TRY(launch_mention_reduce(e + 2 * M, dA_et, e + 3 * M, dA_ei, dA_mi, gm_next + BD, B, N, D, 1.0f, st));
+        DRIN_TRY(launch_mention_reduce2(e, dA_et, dA_ei, dA_mt, dA_mi, gm_next, gm_next + BD, B, N, D, 1.0f, st));
       }
       if (edge_update) DRIN_TRY(launch_gemm_nn({{dfu, D}, {W.w_u, D}, gm_next, D, 2 * (int64_t)B, D, D, true}, prec, st, nn_sk, wt()));
     }
@@ -1683,7 +1664,32 @@ int drin_host_selftest(void) {
     DRIN_TRY(table_topk_layout_selfcheck(3, 300, 16, k, 0));
     DRIN_TRY(table_topk_layout_selfcheck(64, 65536, 768, k, 0));
     DRIN_TRY(table_topk_layout_selfcheck(4096, 1000000, 768, k, 0));
-    DRIN_TRY(table_topk_layout_selfcheck(65535, 1000000, 768, k, 512));
+    DRIN_TRY(table_topk_layout_selfcheck(kMaxGridY, 1000000, 768, k, 512));
+  }
+  // (5) for_grid_slices (internal.h), the launch loop of every sliced launcher: contiguous slices of at most kMaxGridY that cover
+  //     [0, count) exactly, none for an empty count; a failing slice ends the walk and its status comes back
+  for (int64_t count : {(int64_t)0, (int64_t)1, (int64_t)kMaxGridY, (int64_t)kMaxGridY + 1, 2 * (int64_t)kMaxGridY, 2 * (int64_t)kMaxGridY + 1}) {
+    int64_t next = 0;
+    int calls = 0;
+    bool sound = true;
+    const int rc = for_grid_slices(count, [&](int64_t first, int n) -> int {
+      sound = sound && first == next && n >= 1 && n <= kMaxGridY && first + n <= count;
+      next = first + n;
+      ++calls;
+      return DRIN_OK;
+    });
+    if (rc != DRIN_OK || !sound || next != count || calls != (int)cdiv(count, kMaxGridY)) {
+      set_error("selftest: for_grid_slices(%lld): status %d, %d slices ending at %lld%s", (long long)count, rc, calls, (long long)next,
+                sound ? "" : ", one of them out of order, empty or longer than the limit");
+      return rc != DRIN_OK ? rc : DRIN_E_SHAPE;
+    }
+    calls = 0;
+    const int stopped = for_grid_slices(count, [&](int64_t, int) -> int { return ++calls == 2 ? (int)DRIN_E_WORKSPACE : (int)DRIN_OK; });
+    const int slices = (int)cdiv(count, kMaxGridY);
+    if (stopped != (slices >= 2 ? DRIN_E_WORKSPACE : DRIN_OK) || calls != (slices < 2 ? slices : 2)) {
+      set_error("selftest: for_grid_slices(%lld): a failing second slice gave status %d after %d calls", (long long)count, stopped, calls);
+      return DRIN_E_SHAPE;
+    }
   }
   set_error("");
   return DRIN_OK;

@@ -36,9 +36,9 @@ struct AttnCall {
 };
 
 inline int check_attention_shape(const char* who, int64_t B, int H, int Lq, int Lk, int dh) {
-  if (B < 1 || B > 65535 || H < 1 || H > 65535 || Lq < 1 || Lk < 1 || Lk > kAttnMaxLk || dh < 1 || dh > kAttnMaxDh) {
-    set_error("%s: batch and heads in [1, 65535], q_len >= 1, k_len in [1, %d], head_dim in [1, %d] (got B=%lld H=%d Lq=%d Lk=%d dh=%d)",
-              who, kAttnMaxLk, kAttnMaxDh, (long long)B, H, Lq, Lk, dh);
+  if (B < 1 || B > kMaxGridY || H < 1 || H > kMaxGridY || Lq < 1 || Lk < 1 || Lk > kAttnMaxLk || dh < 1 || dh > kAttnMaxDh) {
+    set_error("%s: batch and heads in [1, %d], q_len >= 1, k_len in [1, %d], head_dim in [1, %d] (got B=%lld H=%d Lq=%d Lk=%d dh=%d)",
+              who, kMaxGridY, kAttnMaxLk, kAttnMaxDh, (long long)B, H, Lq, Lk, dh);
     return DRIN_E_SHAPE;
   }
   return DRIN_OK;

@@ -122,16 +122,14 @@ int launch_cosine_bwd(const float* x, const float* y, const float* g, float* dx,
                        xn, pairs, N, D / 4, eps);
     DRIN_CHECK_LAUNCH("k_cosine_bwd_entity");
   }
-  for (int b0 = 0; b0 < B; b0 += 65535) {
-    const int nb = B - b0 < 65535 ? B - b0 : 65535;
-    const int64_t po = (int64_t)b0 * N;
+  return for_grid_slices(B, [&](int64_t b0, int nb) -> int {
+    const int64_t po = b0 * N;
     KernelTimer timer(DRIN_KC_GCN, st);
-    hipLaunchKernelGGL(k_cosine_bwd_mention, dim3((unsigned)cdiv(D / 4, 64), (unsigned)nb), dim3(256), 0, st,
-                       x + (int64_t)b0 * D, y + po * D, coef + po, gcv + po, xn + po, dx + (int64_t)b0 * D, N, D / 4,
-                       eps);
+    hipLaunchKernelGGL(k_cosine_bwd_mention, dim3((unsigned)cdiv(D / 4, 64), (unsigned)nb), dim3(256), 0, st, x + b0 * D,
+                       y + po * D, coef + po, gcv + po, xn + po, dx + b0 * D, N, D / 4, eps);
     DRIN_CHECK_LAUNCH("k_cosine_bwd_mention");
-  }
-  return DRIN_OK;
+    return DRIN_OK;
+  });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -498,67 +496,16 @@ int launch_sigmoid_bwd(const float* g, const float* e_new, float* dpre, int64_t 
 }
 
 // ------------------------------------------------------------------------------------------------
-// out[b, :] = scale * (sum_n w1[b,n] v1[b,n,:] + sum_n w2[b,n] v2[b,n,:]) + u[b, :]
-// (v2 / u may be NULL).  The transposes of the entity<-mention and edge-update products.
-// Block = 4 waves x 64 float4 columns: wave w sums candidates w, w + 4, ... (four loads in flight), the waves are
-// combined through LDS in order - a mention-sized batch (B = 64) is only 3 B blocks, so the candidate loop must not
-// be one serial chain per thread.
-__global__ void __launch_bounds__(256) k_mention_reduce(const float* __restrict__ w1, const float* __restrict__ v1,
-                                                        const float* __restrict__ w2, const float* __restrict__ v2,
-                                                        const float* __restrict__ u, float* __restrict__ out, int N,
-                                                        int D4, float scale) {
-  __shared__ float4 comb[4][64];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int c4 = blockIdx.x * 64 + lane;
-  const int64_t b = blockIdx.y;
-  float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (c4 < D4) {
-    const int64_t off = (b * N) * (int64_t)D4 * 4 + (int64_t)c4 * 4, row = (int64_t)D4 * 4;
-    float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
-    int n = wave;
-    for (; n + 4 < N; n += 8) {  // two candidates of this wave per trip
-      const float4 a0 = ld4(v1 + off + n * row), a1 = ld4(v1 + off + (n + 4) * row);
-      s = fma4(w1[b * N + n], a0, s);
-      t = fma4(w1[b * N + n + 4], a1, t);
-      if (v2 != nullptr) {
-        const float4 c0 = ld4(v2 + off + n * row), c1 = ld4(v2 + off + (n + 4) * row);
-        s = fma4(w2[b * N + n], c0, s);
-        t = fma4(w2[b * N + n + 4], c1, t);
-      }
-    }
-    for (; n < N; n += 4) {
-      s = fma4(w1[b * N + n], ld4(v1 + off + n * row), s);
-      if (v2 != nullptr) s = fma4(w2[b * N + n], ld4(v2 + off + n * row), s);
-    }
-    s = s + t;
-  }
-  comb[wave][lane] = s;
-  __syncthreads();
-  if (wave != 0 || c4 >= D4) return;
-  s = ((comb[0][lane] + comb[1][lane]) + (comb[2][lane] + comb[3][lane])) * scale;
-  if (u != nullptr) s = s + ld4(u + b * (int64_t)D4 * 4 + (int64_t)c4 * 4);
-  st4(out + b * (int64_t)D4 * 4 + (int64_t)c4 * 4, s);
-}
-
-int launch_mention_reduce(const float* w1, const float* v1, const float* w2, const float* v2, const float* u,
-                          float* out, int B, int N, int D, float scale, hipStream_t st) {
-  if (B <= 0) return DRIN_OK;
-  for (int b0 = 0; b0 < B; b0 += 65535) {
-    const int nb = B - b0 < 65535 ? B - b0 : 65535;
-    const int64_t po = (int64_t)b0 * N, vo = po * D;
-    KernelTimer timer(DRIN_KC_GCN, st);
-    hipLaunchKernelGGL(k_mention_reduce, dim3((unsigned)cdiv(D / 4, 64), (unsigned)nb), dim3(256), 0, st, w1 + po,
-                       v1 + vo, w2 ? w2 + po : nullptr, v2 ? v2 + vo : nullptr, u ? u + (int64_t)b0 * D : nullptr,
-                       out + (int64_t)b0 * D, N, D / 4, scale);
-    DRIN_CHECK_LAUNCH("k_mention_reduce");
-  }
-  return DRIN_OK;
-}
-
 // Two reductions over the same rows in one pass (the text and the image mention of a layer):
 //   outA[b] = scale (sum_n w[0][p] v1[p] + sum_n w[1][p] v2[p]) + uA[b]
 //   outB[b] = scale (sum_n w[2][p] v1[p] + sum_n w[3][p] v2[p]) + uB[b]         w = [4][pairs]; v2 / uA / uB may be NULL
-// Candidate split and summation order are those of k_mention_reduce: bit-identical to two launches of it, v1 / v2 read once.
+// The transposes of the entity<-mention and edge-update products; v1 / v2 are read once for both.
+// Block = 4 waves x 64 float4 columns of mention b = blockIdx.y: wave w sums candidates w, w + 4, ... - two of them per trip into
+// two accumulators (s: w, w + 8, ...; t: w + 4, w + 12, ...; per candidate the v1 term, then the v2 term), s + t at the end - so
+// two to four loads of each thread are in flight: a mention-sized batch (B = 64) is only 3 B blocks, and the candidate loop must not be one
+// serial chain per thread.  The waves are combined through LDS as (0 + 1) + (2 + 3), scaled, then u is added.  No sum crosses
+// a mention, so a launch may cover any slice of the batch: the pointers moved to its first mention, `pairs` (the stride between the
+// planes of w) that of the whole call.
 struct MentionReduceJob {
   const float *w, *v1, *v2, *uA, *uB;
   float *outA, *outB;
@@ -644,30 +591,34 @@ int launch_mention_reduce2_pair(const float* wa, const float* va1, const float* 
                                 float* outaB, float scale_a, const float* wb, const float* vb1, const float* vb2, const float* ubA,
                                 const float* ubB, float* outbA, float* outbB, float scale_b, int B, int N, int D, hipStream_t st) {
   if (B <= 0 || N <= 0) return DRIN_OK;
-  if (B > 65535 || (D % 4)) {
-    set_error("mention_reduce2_pair: B=%d D=%d outside the grid / 16-byte contract", B, D);
+  if (D % 4) {
+    set_error("mention_reduce2_pair: D=%d outside the 16-byte contract", D);
     return DRIN_E_SHAPE;
   }
-  const MentionReduceJob ja{wa, va1, va2, uaA, uaB, outaA, outaB, scale_a}, jb{wb, vb1, vb2, ubA, ubB, outbA, outbB, scale_b};
-  KernelTimer timer(DRIN_KC_GCN, st);
-  hipLaunchKernelGGL(k_mention_reduce2_pair, dim3((unsigned)cdiv(D / 4, 64), (unsigned)B, 2), dim3(256), 0, st, ja, jb,
-                     (int64_t)B * N, N, D / 4);
-  DRIN_CHECK_LAUNCH("k_mention_reduce2_pair");
-  return DRIN_OK;
+  return for_grid_slices(B, [&](int64_t b0, int nb) -> int {
+    const int64_t po = b0 * N, vo = po * D, mo = b0 * D;
+    auto at = [](const float* p, int64_t off) { return p ? p + off : nullptr; };
+    const MentionReduceJob ja{wa + po, va1 + vo, at(va2, vo), at(uaA, mo), at(uaB, mo), outaA + mo, outaB + mo, scale_a},
+        jb{wb + po, vb1 + vo, at(vb2, vo), at(ubA, mo), at(ubB, mo), outbA + mo, outbB + mo, scale_b};
+    KernelTimer timer(DRIN_KC_GCN, st);
+    hipLaunchKernelGGL(k_mention_reduce2_pair, dim3((unsigned)cdiv(D / 4, 64), (unsigned)nb, 2), dim3(256), 0, st, ja, jb,
+                       (int64_t)B * N, N, D / 4);
+    DRIN_CHECK_LAUNCH("k_mention_reduce2_pair");
+    return DRIN_OK;
+  });
 }
 
 int launch_mention_reduce2(const float* w, const float* v1, const float* v2, const float* uA, const float* uB,
                            float* outA, float* outB, int B, int N, int D, float scale, hipStream_t st) {
-  if (B <= 0) return DRIN_OK;
-  if (B > 65535) {
-    set_error("mention_reduce2: batch %d exceeds the grid limit of 65535 mentions per launch", B);
-    return DRIN_E_SHAPE;
-  }
-  KernelTimer timer(DRIN_KC_GCN, st);
-  hipLaunchKernelGGL(k_mention_reduce2, dim3((unsigned)cdiv(D / 4, 64), (unsigned)B), dim3(256), 0, st, w,
-                     (int64_t)B * N, v1, v2, uA, uB, outA, outB, N, D / 4, scale);
-  DRIN_CHECK_LAUNCH("k_mention_reduce2");
-  return DRIN_OK;
+  return for_grid_slices(B, [&](int64_t b0, int nb) -> int {
+    const int64_t po = b0 * N, vo = po * D, mo = b0 * D;
+    KernelTimer timer(DRIN_KC_GCN, st);
+    hipLaunchKernelGGL(k_mention_reduce2, dim3((unsigned)cdiv(D / 4, 64), (unsigned)nb), dim3(256), 0, st, w + po,
+                       (int64_t)B * N, v1 + vo, v2 ? v2 + vo : nullptr, uA ? uA + mo : nullptr, uB ? uB + mo : nullptr,
+                       outA + mo, outB + mo, N, D / 4, scale);
+    DRIN_CHECK_LAUNCH("k_mention_reduce2");
+    return DRIN_OK;
+  });
 }
 
 // out[p, :] = scale * (w1[p] m1[b, :] + w2[p] m2[b, :])        (m2 may be NULL); one wave per pair

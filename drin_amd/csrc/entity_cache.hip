@@ -819,7 +819,7 @@ DRIN_API int drin_forward_cached(const drin_config* cfg, const drin_batch* b, co
   const int B = cfg->batch, N = cfg->num_candidates, D = cfg->embed_dim;
   const int64_t M = (int64_t)B * N;
   if (B == 0) return DRIN_OK;
-  if (B > 65535) {
+  if (B > kMaxGridY) {
     set_error("drin_forward_cached: batch %d exceeds the grid limit; split the batch", B);
     return DRIN_E_SHAPE;
   }

@@ -737,7 +737,7 @@ int drin_forward_prepared_head(const drin_config* cfg, const drin_batch* b, cons
   //  ahead of the stream pass and would have written the workspace by the time it refused)
   if (!entity_stream_fits(cfg->batch)) {
     set_error("drin_forward_prepared: batch = %d: the entity stream pass is built for at most %d mentions per call; split the batch",
-              cfg->batch, kMaxGridMentions);
+              cfg->batch, kMaxGridY);
     return DRIN_E_SHAPE;
   }
   if (!b || !params || !prepared || !workspace || !scores) {

@@ -7,74 +7,15 @@
 namespace drin {
 
 // ------------------------------------------------------------------------------------------------
-// mention <- entity (model.py:143-144) summed over the two neighbour types, plus the self term (:128):
-//   out[b, :] = mean_n(e1[b,n] v1[b,n,:]) + mean_n(e2[b,n] v2[b,n,:]) + u[b, :]
-// grid (ceil(D4/64), B): one wave per 64 float4 columns of a mention, walking the N candidates.
-__global__ void __launch_bounds__(64) k_mention_aggregate(const float* __restrict__ e1, const float* __restrict__ v1,
-                                                          const float* __restrict__ e2, const float* __restrict__ v2,
-                                                          const float* __restrict__ u, float* __restrict__ out, int N,
-                                                          int D4) {
-  const int c4 = blockIdx.x * 64 + threadIdx.x;
-  if (c4 >= D4) return;
-  const int64_t b = blockIdx.y;
-  const float* p1 = v1 + (b * N) * (int64_t)D4 * 4 + (int64_t)c4 * 4;
-  const float* p2 = v2 + (b * N) * (int64_t)D4 * 4 + (int64_t)c4 * 4;
-  float4 s1 = make_float4(0.f, 0.f, 0.f, 0.f), s2 = s1;
-  int n = 0;
-  for (; n + 4 <= N; n += 4) {
-    float4 a[4], c[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      a[j] = ld4(p1 + (int64_t)(n + j) * D4 * 4);
-      c[j] = ld4(p2 + (int64_t)(n + j) * D4 * 4);
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      s1 = fma4(e1[b * N + n + j], a[j], s1);
-      s2 = fma4(e2[b * N + n + j], c[j], s2);
-    }
-  }
-  for (; n < N; ++n) {
-    s1 = fma4(e1[b * N + n], ld4(p1 + (int64_t)n * D4 * 4), s1);
-    s2 = fma4(e2[b * N + n], ld4(p2 + (int64_t)n * D4 * 4), s2);
-  }
-  const float cnt = (float)N;
-  const float4 uu = ld4(u + b * (int64_t)D4 * 4 + (int64_t)c4 * 4);
-  float4 r;
-  r.x = (s1.x / cnt + s2.x / cnt) + uu.x;
-  r.y = (s1.y / cnt + s2.y / cnt) + uu.y;
-  r.z = (s1.z / cnt + s2.z / cnt) + uu.z;
-  r.w = (s1.w / cnt + s2.w / cnt) + uu.w;
-  st4(out + b * (int64_t)D4 * 4 + (int64_t)c4 * 4, r);
-}
-
-int launch_mention_aggregate(const float* e1, const float* v1, const float* e2, const float* v2, const float* u,
-                             float* out, int B, int N, int D, hipStream_t st) {
-  if (B <= 0) return DRIN_OK;
-  if (D % 4) {
-    set_error("mention_aggregate: D=%d must be a multiple of 4", D);
-    return DRIN_E_SHAPE;
-  }
-  for (int b0 = 0; b0 < B; b0 += 65535) {
-    const int nb = B - b0 < 65535 ? B - b0 : 65535;
-    const int64_t po = (int64_t)b0 * N, vo = po * D;
-    dim3 grid((unsigned)cdiv(D / 4, 64), (unsigned)nb);
-    KernelTimer timer(DRIN_KC_GCN, st);
-    hipLaunchKernelGGL(k_mention_aggregate, grid, dim3(64), 0, st, e1 + po, v1 + vo, e2 + po, v2 + vo,
-                       u + (int64_t)b0 * D, out + (int64_t)b0 * D, N, D / 4);
-    DRIN_CHECK_LAUNCH("k_mention_aggregate");
-  }
-  return DRIN_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
 // Both aggregations of a scalar-edge layer in ONE pass over the entity vertices (model.py:143-146 + the self terms of
 // :128): every et / ei element is read once and feeds the mention sums and its own entity update.
 //   agg_mt[b] = mean_n(e_tt et) + mean_n(e_ti ei) + mt[b]      agg_et[b,n] = e_tt mt[b] + e_it mi[b] + et[b,n]
 //   agg_mi[b] = mean_n(e_it et) + mean_n(e_ii ei) + mi[b]      agg_ei[b,n] = e_ti mt[b] + e_ii mi[b] + ei[b,n]
-// (the image rows only when LIVE_IMAGE: the last layer's image vertices never reach the score).  Same grid, same
-// per-column summation order as k_mention_aggregate / k_entity_aggregate: bit-identical to the four separate launches,
-// at half their HBM traffic.
+// (the image rows only when LIVE_IMAGE: the last layer's image vertices never reach the score).
+// grid (ceil(D4 / 64), mentions of the launch): one wave per 64 float4 columns of mention b = blockIdx.y, walking its N candidates
+// in order n = 0, 1, ...: each mention sum is one serial fma chain from 0 per column, then (s1 / N + s2 / N) + self; an entity row
+// is (a1 m1 + a2 m2) + v.  No sum crosses a mention, so a launch may cover any slice of the batch: the pointers moved to its first
+// mention, B (the stride between the text and the image halves) and ES those of the whole call.
 template <bool LIVE_IMAGE>
 __global__ void __launch_bounds__(64) k_layer_aggregate(const float* __restrict__ e, int64_t ES,
                                                         const float* __restrict__ vm, const float* __restrict__ ve,
@@ -160,56 +101,19 @@ int launch_layer_aggregate(const float* e, int64_t edge_stride, const float* vm,
     set_error("layer_aggregate: D=%d must be a multiple of 4", D);
     return DRIN_E_SHAPE;
   }
-  if (B > 65535) {
-    set_error("layer_aggregate: batch %d exceeds the grid limit of 65535 mentions per launch", B);
-    return DRIN_E_SHAPE;
-  }
-  dim3 grid((unsigned)cdiv(D / 4, 64), (unsigned)B);
-  KernelTimer timer(DRIN_KC_GCN, st);
-  if (live_image)
-    hipLaunchKernelGGL(k_layer_aggregate<true>, grid, dim3(64), 0, st, e, edge_stride, vm, ve, agg_m, agg_e, B, N, D / 4);
-  else
-    hipLaunchKernelGGL(k_layer_aggregate<false>, grid, dim3(64), 0, st, e, edge_stride, vm, ve, agg_m, agg_e, B, N, D / 4);
-  DRIN_CHECK_LAUNCH("k_layer_aggregate");
-  return DRIN_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// entity <- mention (model.py:146) summed over the two neighbour types, plus the self term (:128):
-//   out[b, n, :] = e1[b,n] m1[b, :] + e2[b,n] m2[b, :] + v[b, n, :]
-__global__ void __launch_bounds__(256) k_entity_aggregate(const float* __restrict__ e1, const float* __restrict__ m1,
-                                                          const float* __restrict__ e2, const float* __restrict__ m2,
-                                                          const float* __restrict__ v, float* __restrict__ out,
-                                                          int64_t total4, int N, int D4) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= total4) return;
-  const int64_t p = i / D4;
-  const int c4 = (int)(i - p * D4);
-  const int64_t b = p / N;
-  const float a1 = e1[p], a2 = e2[p];
-  const float4 x1 = ld4(m1 + b * (int64_t)D4 * 4 + c4 * 4), x2 = ld4(m2 + b * (int64_t)D4 * 4 + c4 * 4);
-  const float4 vv = ld4(v + i * 4);
-  float4 r;
-  r.x = (a1 * x1.x + a2 * x2.x) + vv.x;
-  r.y = (a1 * x1.y + a2 * x2.y) + vv.y;
-  r.z = (a1 * x1.z + a2 * x2.z) + vv.z;
-  r.w = (a1 * x1.w + a2 * x2.w) + vv.w;
-  st4(out + i * 4, r);
-}
-
-int launch_entity_aggregate(const float* e1, const float* m1, const float* e2, const float* m2, const float* v,
-                            float* out, int B, int N, int D, hipStream_t st) {
-  const int64_t total4 = (int64_t)B * N * (D / 4);
-  if (total4 <= 0) return DRIN_OK;
-  if (D % 4) {
-    set_error("entity_aggregate: D=%d must be a multiple of 4", D);
-    return DRIN_E_SHAPE;
-  }
-  KernelTimer timer(DRIN_KC_GCN, st);
-  hipLaunchKernelGGL(k_entity_aggregate, dim3((unsigned)cdiv(total4, 256)), dim3(256), 0, st, e1, m1, e2, m2, v, out,
-                     total4, N, D / 4);
-  DRIN_CHECK_LAUNCH("k_entity_aggregate");
-  return DRIN_OK;
+  return for_grid_slices(B, [&](int64_t b0, int nb) -> int {
+    const int64_t po = b0 * N, vo = po * D, mo = b0 * D;
+    dim3 grid((unsigned)cdiv(D / 4, 64), (unsigned)nb);
+    KernelTimer timer(DRIN_KC_GCN, st);
+    if (live_image)
+      hipLaunchKernelGGL(k_layer_aggregate<true>, grid, dim3(64), 0, st, e + po, edge_stride, vm + mo, ve + vo, agg_m + mo,
+                         agg_e + vo, B, N, D / 4);
+    else
+      hipLaunchKernelGGL(k_layer_aggregate<false>, grid, dim3(64), 0, st, e + po, edge_stride, vm + mo, ve + vo, agg_m + mo,
+                         agg_e + vo, B, N, D / 4);
+    DRIN_CHECK_LAUNCH("k_layer_aggregate");
+    return DRIN_OK;
+  });
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -242,7 +242,7 @@ static int launch(const float* A, int64_t lda, const float* B, int64_t ldb, cons
                   int64_t part_stride = 0, int* splits_used = nullptr, int* k_per_split_used = nullptr) {
   if (M <= 0 || N <= 0) return DRIN_OK;
   const int64_t mt = cdiv(M, BM);
-  if (mt > 65535) {
+  if (mt > kMaxGridY) {
     set_error("%s: %lld row tiles exceed the grid limit; split the batch", what, (long long)mt);
     return DRIN_E_SHAPE;
   }

@@ -1032,7 +1032,7 @@ int launch_gemm_x3_planes(const void* a_hi, const void* a_lo, int64_t lda, const
     return DRIN_E_ALIGN;
   }
   const int64_t mt = cdiv(M, x3p::BM);
-  if (mt > 65535) {
+  if (mt > kMaxGridY) {
     set_error("gemm_x3_planes: %lld row tiles exceed the grid limit; split the batch", (long long)mt);
     return DRIN_E_SHAPE;
   }

@@ -37,10 +37,10 @@ int validate_ghmfc_config(const drin_ghmfc_config* c) {
     set_error("ghmfc config is NULL");
     return DRIN_E_NULL;
   }
-  if (c->batch <= 0 || c->batch > (1 << 20) || c->num_candidates <= 0 || c->num_candidates > 65535 || c->embed_dim <= 0 ||
+  if (c->batch <= 0 || c->batch > (1 << 20) || c->num_candidates <= 0 || c->num_candidates > kMaxGridY || c->embed_dim <= 0 ||
       c->image_dim <= 0 || c->mention_tokens <= 0 || c->image_regions <= 0 || c->num_heads <= 0 || c->entity_tokens < 0) {
-    set_error("ghmfc config: batch in [1, 2^20], num_candidates in [1, 65535], widths, token counts and heads >= 1, entity_tokens >= 0 "
-              "(got B=%d N=%d D=%d R=%d L=%d P=%d H=%d T=%d)", c->batch, c->num_candidates, c->embed_dim, c->image_dim,
+    set_error("ghmfc config: batch in [1, 2^20], num_candidates in [1, %d], widths, token counts and heads >= 1, entity_tokens >= 0 "
+              "(got B=%d N=%d D=%d R=%d L=%d P=%d H=%d T=%d)", kMaxGridY, c->batch, c->num_candidates, c->embed_dim, c->image_dim,
               c->mention_tokens, c->image_regions, c->num_heads, c->entity_tokens);
     return DRIN_E_SHAPE;
   }

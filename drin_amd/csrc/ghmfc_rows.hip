@@ -482,7 +482,7 @@ int launch_layernorm_res(const float* x, const float* res, const float* gamma, c
   if (rows <= 0) return DRIN_OK;
   DRIN_TRY(check_row_width("layernorm_res", E));
   const int E4 = E / 4;
-  const dim3 grid((unsigned)(cdiv(rows, 4) < 65535 * 16 ? cdiv(rows, 4) : 65535 * 16));
+  const dim3 grid((unsigned)row_blocks(rows));
   return timed(DRIN_KC_NORM, st, "k_layernorm_res", [&] {
     if (E4 <= 64)
       hipLaunchKernelGGL(k_layernorm_res<1>, grid, dim3(256), 0, st, x, res, gamma, beta, y, mean, rstd, rows, E4, eps);
@@ -556,7 +556,7 @@ int drin_seq_max_train_fwd(const float* x, float* out, int32_t* idx, int32_t bat
   const char* who = "drin_seq_max_train_fwd";
   DRIN_CHECK_POINTERS(who, {"x", x, true}, {"out", out, true}, {"idx", idx, true});
   DRIN_TRY(check_width4(who, width));
-  DRIN_TRY(check_count(who, "batch", batch, 1, 65535));
+  DRIN_TRY(check_count(who, "batch", batch, 1, kMaxGridY));
   DRIN_TRY(check_count(who, "seq_len", seq_len, 1, INT32_MAX));
   DRIN_BIND_DEVICE(stream, out, who);
   return launch_seq_max(x, out, batch, seq_len, width, (hipStream_t)stream, idx);
@@ -566,7 +566,7 @@ int drin_seq_max_bwd(const float* dout, const int32_t* idx, float* dx, int32_t b
   const char* who = "drin_seq_max_bwd";
   DRIN_CHECK_POINTERS(who, {"dout", dout, true}, {"idx", idx, true}, {"dx", dx, true});
   DRIN_TRY(check_width4(who, width));
-  DRIN_TRY(check_count(who, "batch", batch, 1, 65535));
+  DRIN_TRY(check_count(who, "batch", batch, 1, kMaxGridY));
   DRIN_TRY(check_count(who, "seq_len", seq_len, 1, INT32_MAX));
   DRIN_BIND_DEVICE(stream, dx, who);
   return launch_seq_max_bwd(dout, idx, dx, batch, seq_len, width, (hipStream_t)stream);
@@ -617,7 +617,7 @@ int drin_cosine_rows_fwd(const float* x, const float* y, float* out, int32_t bat
   }
   DRIN_TRY(check_width4(who, width));
   DRIN_TRY(check_count(who, "batch", batch, 1, INT32_MAX));
-  DRIN_TRY(check_count(who, "num_candidates", num_candidates, 1, 65535));
+  DRIN_TRY(check_count(who, "num_candidates", num_candidates, 1, kMaxGridY));
   DRIN_BIND_DEVICE(stream, out, who);
   return launch_cosine_rows(x, y, width, out, batch, num_candidates, width, eps, 1.0f, (hipStream_t)stream);
 }
@@ -636,7 +636,7 @@ int drin_cosine_rows_bwd(const float* x, const float* y, const float* dout, floa
     return DRIN_E_UNSUPPORTED;
   }
   DRIN_TRY(check_count(who, "batch", batch, 1, INT32_MAX));
-  DRIN_TRY(check_count(who, "num_candidates", num_candidates, 1, 65535));
+  DRIN_TRY(check_count(who, "num_candidates", num_candidates, 1, kMaxGridY));
   DRIN_TRY(check_scratch(who, scratch, scratch_floats, 3 * (size_t)batch * (size_t)num_candidates));
   DRIN_BIND_DEVICE(stream, dx, who);
   return launch_cosine_bwd(x, y, dout, dx, dy, scratch, batch, num_candidates, width, eps, (hipStream_t)stream);

@@ -74,7 +74,7 @@ int check_table_args(const char* who, const int64_t* index, int64_t num_rows, co
 int launch_gather_rows(const float* table, const int64_t* index, int64_t num_rows, float* out, int64_t count, int width,
                        int32_t* status, int64_t pair_base, hipStream_t st) {
   if (count <= 0) return DRIN_OK;
-  const int64_t blocks = cdiv(count, 4) < 65535 * 16 ? cdiv(count, 4) : 65535 * 16;
+  const int64_t blocks = row_blocks(count);
   return timed(DRIN_KC_POOL, st, "k_gather_rows", [&] {
     hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)blocks), dim3(256), 0, st, table, index, num_rows, out, count, width / 4, status,
                        pair_base);
@@ -152,7 +152,7 @@ int drin_cosine_rows_indexed_fwd(const float* x, const float* rows, const int64_
   DRIN_TRY(check_table_args(who, index, num_entities, index_status));
   DRIN_TRY(check_width4(who, width));
   DRIN_TRY(check_count(who, "batch", batch, 1, INT32_MAX));
-  DRIN_TRY(check_count(who, "num_candidates", num_candidates, 1, 65535));
+  DRIN_TRY(check_count(who, "num_candidates", num_candidates, 1, kMaxGridY));
   DRIN_TRY(check_count(who, "batch * num_candidates", (int64_t)batch * num_candidates, 1, INT32_MAX));
   DRIN_BIND_DEVICE(stream, out, who);
   return launch_cosine_gather(x, rows, index, num_entities, out, batch, num_candidates, width, eps, index_status, 0,

@@ -38,14 +38,13 @@ __global__ void __launch_bounds__(256) k_span_mean_bwd(const float* __restrict__
 int launch_span_mean_bwd(const float* g, const int64_t* start, const int64_t* end, float* out, int B, int L, int D,
                          hipStream_t st) {
   if (B <= 0) return DRIN_OK;
-  for (int b0 = 0; b0 < B; b0 += 65535) {
-    const int nb = B - b0 < 65535 ? B - b0 : 65535;
+  return for_grid_slices(B, [&](int64_t b0, int nb) -> int {
     KernelTimer timer(DRIN_KC_POOL, st);
-    hipLaunchKernelGGL(k_span_mean_bwd, dim3((unsigned)L, (unsigned)nb), dim3(D / 4 >= 192 ? 192 : 64), 0, st,
-                       g + (int64_t)b0 * D, start + b0, end + b0, out + (int64_t)b0 * L * D, L, D / 4);
+    hipLaunchKernelGGL(k_span_mean_bwd, dim3((unsigned)L, (unsigned)nb), dim3(D / 4 >= 192 ? 192 : 64), 0, st, g + b0 * D,
+                       start + b0, end + b0, out + b0 * L * D, L, D / 4);
     DRIN_CHECK_LAUNCH("k_span_mean_bwd");
-  }
-  return DRIN_OK;
+    return DRIN_OK;
+  });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -328,17 +327,15 @@ int launch_miei_bwd(const float* mobj, const float* mscore, const float* eobj, c
                        d_escore, d_eobj, gcos, cosv, nyv, dms, nxv, pairs, N, Km, Ke, R / 4, cos_eps, miei_eps);
     DRIN_CHECK_LAUNCH("k_miei_bwd_pair");
   }
-  for (int b0 = 0; b0 < B; b0 += 65535) {
-    const int nb = B - b0 < 65535 ? B - b0 : 65535;
-    const int64_t po = (int64_t)b0 * N;
+  return for_grid_slices(B, [&](int64_t b0, int nb) -> int {
+    const int64_t po = b0 * N;
     KernelTimer timer(DRIN_KC_EDGE, st);
-    hipLaunchKernelGGL(k_miei_bwd_mention, dim3((unsigned)cdiv(R / 4, 64), (unsigned)nb), dim3(256), 0, st,
-                       mobj + (int64_t)b0 * Km * R, eobj + po * Ke * R, gcos + po * Km * Ke, cosv + po * Km * Ke, nyv + po * Ke,
-                       dms + po * Km, nxv + (int64_t)b0 * Km, d_mobj + (int64_t)b0 * Km * R, d_mscore + (int64_t)b0 * Km, N,
-                       Km, Ke, R / 4, cos_eps);
+    hipLaunchKernelGGL(k_miei_bwd_mention, dim3((unsigned)cdiv(R / 4, 64), (unsigned)nb), dim3(256), 0, st, mobj + b0 * Km * R,
+                       eobj + po * Ke * R, gcos + po * Km * Ke, cosv + po * Km * Ke, nyv + po * Ke, dms + po * Km, nxv + b0 * Km,
+                       d_mobj + b0 * Km * R, d_mscore + b0 * Km, N, Km, Ke, R / 4, cos_eps);
     DRIN_CHECK_LAUNCH("k_miei_bwd_mention");
-  }
-  return DRIN_OK;
+    return DRIN_OK;
+  });
 }
 
 }  // namespace drin

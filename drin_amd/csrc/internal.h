@@ -110,14 +110,28 @@ inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 // grid of the one-wave-per-pair kernels (device_utils.h: wave_pair)
 inline dim3 pair_grid(int B, int N) {
-  return (B > 1 && B <= 65535) ? dim3((unsigned)cdiv(N, 4), (unsigned)B) : dim3((unsigned)cdiv((int64_t)B * N, 4));
+  return (B > 1 && B <= kMaxGridY) ? dim3((unsigned)cdiv(N, 4), (unsigned)B) : dim3((unsigned)cdiv((int64_t)B * N, 4));
 }
-// mentions of one launch of a (column quads, mention, ...) grid that its launcher does not slice: the grid.y limit.  Such a
-// launcher refuses past it, and the entry points that reach it ask the same predicate among their argument checks (api.hip:
-// layers_call_fits): a size is refused before the first launch of a call or not at all
-constexpr int kMaxGridMentions = 65535;
-inline bool edge_pre_vec_bwd_fits(int B) { return B <= kMaxGridMentions; }   // k_edge_pre_vec_bwd_fu (vector_kernels.hip)
-inline bool entity_stream_fits(int B) { return B <= kMaxGridMentions; }      // k_entity_stream (fused_kernels.hip); drin_forward_prepared asks
+// [0, count) in slices of at most kMaxGridY (scratch_sizes.h), in order: launch(first, n) per slice, none for count <= 0; the
+// first status that is not DRIN_OK ends the walk and is returned.  The launch loop of every (column quads, mention, ...) grid:
+// the body moves each pointer by `first` mentions and takes n as grid.y
+template <typename F>
+int for_grid_slices(int64_t count, F&& launch) {
+  for (int64_t first = 0; first < count; first += kMaxGridY) {
+    const int64_t left = count - first;
+    DRIN_TRY(launch(first, (int)(left < kMaxGridY ? left : kMaxGridY)));
+  }
+  return DRIN_OK;
+}
+// workgroups of the one-wave-per-row grid-stride launchers (launch_layernorm_res, launch_gather_rows, launch_row_inv_norms):
+// four rows each, past the cap a wave walks several rows
+constexpr int64_t kMaxRowBlocks = (int64_t)kMaxGridY * 16;
+inline int64_t row_blocks(int64_t rows) { return cdiv(rows, 4) < kMaxRowBlocks ? cdiv(rows, 4) : kMaxRowBlocks; }
+// A launcher with a (column quads, mention, ...) grid that does not slice refuses past kMaxGridY mentions, and the entry points
+// that reach it ask the same predicate among their argument checks (api.hip: layers_call_fits): a size is refused before the
+// first launch of a call or not at all
+inline bool edge_pre_vec_bwd_fits(int B) { return B <= kMaxGridY; }   // k_edge_pre_vec_bwd_fu (vector_kernels.hip)
+inline bool entity_stream_fits(int B) { return B <= kMaxGridY; }      // k_entity_stream (fused_kernels.hip); drin_forward_prepared asks
 
 // ---- pooling and static edges of the layer-by-layer entry points (api.hip; Layout, Pooled: layout.h) -------------------
 struct Layout;
@@ -186,13 +200,8 @@ inline int ln_bwd_slots(int D) {
 }
 
 // ---- GCN elementwise / reduction kernels (gcn_kernels.hip) --------------------------------------
-// model.py:143-144 + :128 input: out[b,:] = mean_n(e1[b,n] v1[b,n,:]) + mean_n(e2[b,n] v2[b,n,:]) + u[b,:]
-int launch_mention_aggregate(const float* e1, const float* v1, const float* e2, const float* v2, const float* u,
-                             float* out, int B, int N, int D, hipStream_t st);
-// model.py:146 + :128 input: out[b,n,:] = e1[b,n] m1[b,:] + e2[b,n] m2[b,:] + v[b,n,:]
-int launch_entity_aggregate(const float* e1, const float* m1, const float* e2, const float* m2, const float* v,
-                            float* out, int B, int N, int D, hipStream_t st);
-// both aggregations of a scalar-edge layer in one pass; e = [4][edge_stride], vm = [2][B][D], ve = [2][B*N][D]
+// both aggregations of a scalar-edge layer in one pass (model.py:143-146 + the :128 inputs; the formulas: the kernel's comment);
+// e = [4][edge_stride], vm = [2][B][D], ve = [2][B*N][D]
 int launch_layer_aggregate(const float* e, int64_t edge_stride, const float* vm, const float* ve, float* agg_m,
                            float* agg_e, int B, int N, int D, bool live_image, hipStream_t st);
 // model.py:128: y = gelu(layer_norm(h)) row-wise; optionally keeps mean / rstd for backward
@@ -229,10 +238,8 @@ int launch_edge_update_bwd(const float* g, const float* e_new, const float* fu, 
                            float scale, hipStream_t st, int act = DRIN_ACT_SIGMOID);
 // dpre = g * e' * (1 - e')
 int launch_sigmoid_bwd(const float* g, const float* e_new, float* dpre, int64_t n, hipStream_t st, int act = DRIN_ACT_SIGMOID);
-// out[b,:] = scale (sum_n w1 v1 + sum_n w2 v2) + u      (v2, u optional)
-int launch_mention_reduce(const float* w1, const float* v1, const float* w2, const float* v2, const float* u,
-                          float* out, int B, int N, int D, float scale, hipStream_t st);
-// two such reductions over the same rows in one pass: w = [4][B*N]; outA takes planes 0 / 1, outB planes 2 / 3
+// out[b,:] = scale (sum_n w1 v1 + sum_n w2 v2) + u (v2, u optional), two of them over the same rows v1 / v2 in one pass:
+// w = [4][B*N]; outA takes planes 0 / 1 and uA, outB planes 2 / 3 and uB
 int launch_mention_reduce2(const float* w, const float* v1, const float* v2, const float* uA, const float* uB,
                            float* outA, float* outB, int B, int N, int D, float scale, hipStream_t st);
 // two independent launch_mention_reduce2 jobs (a, b) over the same B x N x D geometry in one launch; same bits

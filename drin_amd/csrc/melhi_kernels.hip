@@ -273,7 +273,7 @@ __global__ void __launch_bounds__(256) k_melhi_dconst(const float* __restrict__ 
 }
 
 inline dim3 row_grid(int64_t rows, int cols4) {
-  return dim3((unsigned)cdiv(cols4, 256), (unsigned)(rows < 65535 ? (rows > 0 ? rows : 1) : 65535));
+  return dim3((unsigned)cdiv(cols4, 256), (unsigned)(rows < kMaxGridY ? (rows > 0 ? rows : 1) : kMaxGridY));
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------

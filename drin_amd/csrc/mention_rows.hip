@@ -156,15 +156,14 @@ template <typename T>
 int launch_mention_rows_t(const T* raw, const float* enc, const int64_t* start, const int64_t* end, int repr, float* edge_row,
                           float* vertex_row, int* idx_edge, int* idx_vertex, int B, int L, int D, hipStream_t st) {
   const int D4 = D / 4;
-  for (int b0 = 0; b0 < B; b0 += 65535) {   // grid.y limit
-    const int nb = B - b0 < 65535 ? B - b0 : 65535;
+  return for_grid_slices(B, [&](int64_t b0, int nb) -> int {
     const dim3 grid((unsigned)cdiv(D4, 64), (unsigned)nb), block(256);
-    const int64_t in = (int64_t)b0 * L * D, out = (int64_t)b0 * D;
+    const int64_t in = b0 * L * D, out = b0 * D;
     const T* r = raw + in;
     const float* e = enc ? enc + in : nullptr;
     const int64_t *s = start ? start + b0 : nullptr, *t = end ? end + b0 : nullptr;
     int *ie = idx_edge ? idx_edge + out : nullptr, *iv = idx_vertex ? idx_vertex + out : nullptr;
-    DRIN_TRY(timed(DRIN_KC_POOL, st, "k_mention_rows", [&] {
+    return timed(DRIN_KC_POOL, st, "k_mention_rows", [&] {
       if (repr == kReprMax) {
         if (enc)
           hipLaunchKernelGGL((k_mention_rows<T, kReprMax, true>), grid, block, 0, st, r, e, s, t, edge_row + out, vertex_row + out, ie, iv, L, D4);
@@ -176,9 +175,8 @@ int launch_mention_rows_t(const T* raw, const float* enc, const int64_t* start, 
         else
           hipLaunchKernelGGL((k_mention_rows<T, kReprAvg, false>), grid, block, 0, st, r, e, s, t, edge_row + out, vertex_row + out, ie, iv, L, D4);
       }
-    }));
-  }
-  return DRIN_OK;
+    });
+  });
 }
 
 }  // namespace
@@ -199,15 +197,14 @@ int launch_mention_rows_bwd(const float* g_edge, const float* g_vertex, const in
   if (B <= 0 || (d_raw == nullptr && d_enc == nullptr)) return DRIN_OK;
   const int D4 = D / 4;
   const unsigned slices = (unsigned)(cdiv(L, 4) < kBwdRowSlices ? cdiv(L, 4) : kBwdRowSlices);
-  for (int b0 = 0; b0 < B; b0 += 65535) {
-    const int nb = B - b0 < 65535 ? B - b0 : 65535;
+  return for_grid_slices(B, [&](int64_t b0, int nb) -> int {
     const dim3 grid((unsigned)cdiv(D4, 64), (unsigned)nb, slices), block(256);
-    const int64_t blk = (int64_t)b0 * L * D, row = (int64_t)b0 * D;
+    const int64_t blk = b0 * L * D, row = b0 * D;
     const float *ge = g_edge ? g_edge + row : nullptr, *gv = g_vertex ? g_vertex + row : nullptr;
     const int64_t *s = start ? start + b0 : nullptr, *t = end ? end + b0 : nullptr;
     const int *ie = idx_edge ? idx_edge + row : nullptr, *iv = idx_vertex ? idx_vertex + row : nullptr;
     float *dr = d_raw ? d_raw + blk : nullptr, *de = d_enc ? d_enc + blk : nullptr;
-    DRIN_TRY(timed(DRIN_KC_POOL, st, "k_mention_rows_bwd", [&] {
+    return timed(DRIN_KC_POOL, st, "k_mention_rows_bwd", [&] {
       if (repr == kReprMax) {
         if (has_encoded)
           hipLaunchKernelGGL((k_mention_rows_bwd<kReprMax, false>), grid, block, 0, st, ge, gv, s, t, ie, iv, dr, de, L, D4);
@@ -219,9 +216,8 @@ int launch_mention_rows_bwd(const float* g_edge, const float* g_vertex, const in
         else
           hipLaunchKernelGGL((k_mention_rows_bwd<kReprAvg, true>), grid, block, 0, st, ge, gv, s, t, ie, iv, dr, de, L, D4);
       }
-    }));
-  }
-  return DRIN_OK;
+    });
+  });
 }
 
 }  // namespace drin

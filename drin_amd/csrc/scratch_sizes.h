@@ -12,12 +12,16 @@
 
 namespace drin {
 
+// The y (and z) extent a launch grid may have.  Every launcher whose grid.y counts mentions, groups, rows or row tiles slices at
+// it (internal.h: for_grid_slices), strides past it or refuses past it; it stands here because the row limit below derives from it.
+constexpr int kMaxGridY = 65535;
+
 // ---- exact-fp32 products (gemm_f32.hip) ------------------------------------------------------------------------------
 // mention-sized: at most this many rows (NT / NN) or reduction rows (TN) run on 64 x 64 tiles
 constexpr int64_t kMentionSizedMaxRows = 2048;
 // past that limit an NT / NN product runs on 128 x 128 tiles, one row tile per grid.y: the rows one product may have
 // (launch_gemm_nt / launch_gemm_nn refuse more; api.hip's layers_call_fits asks before a call's first launch)
-constexpr int64_t kF32MaxRows = (int64_t)65535 * 128;
+constexpr int64_t kF32MaxRows = (int64_t)kMaxGridY * 128;
 inline bool gemm_f32_rows_fit(int64_t rows) { return rows <= kF32MaxRows; }
 // small split-K (small_splitk_fits, launch_small_splitk, the NT group): products of a few hundred rows with a long reduction
 // split K over workgroups into scratch, at most kSmallSplitkMaxSlices slices of [rows][n_out]

@@ -38,19 +38,14 @@ static int launch_axis_mean_t(const T* in, float* out, int64_t groups, int inner
     set_error("axis_mean: cols=%d must be a multiple of 4 and inner=%d positive", cols, inner);
     return DRIN_E_SHAPE;
   }
-  if (groups > 65535) {  // grid.y limit: fold in chunks
-    for (int64_t g0 = 0; g0 < groups; g0 += 65535) {
-      const int64_t n = groups - g0 < 65535 ? groups - g0 : 65535;
-      DRIN_TRY(launch_axis_mean_t<T>(in + g0 * inner * cols, out + g0 * cols, n, inner, cols, st));
-    }
-    return DRIN_OK;
-  }
   const int cols4 = cols / 4;
-  dim3 grid((unsigned)cdiv(cols4, 256), (unsigned)groups);
-  KernelTimer timer(DRIN_KC_POOL, st);
-  hipLaunchKernelGGL(k_axis_mean<T>, grid, dim3(256), 0, st, in, out, inner, cols4);
-  DRIN_CHECK_LAUNCH("k_axis_mean");
-  return DRIN_OK;
+  return for_grid_slices(groups, [&](int64_t g0, int n) -> int {
+    dim3 grid((unsigned)cdiv(cols4, 256), (unsigned)n);
+    KernelTimer timer(DRIN_KC_POOL, st);
+    hipLaunchKernelGGL(k_axis_mean<T>, grid, dim3(256), 0, st, in + g0 * inner * cols, out + g0 * cols, inner, cols4);
+    DRIN_CHECK_LAUNCH("k_axis_mean");
+    return DRIN_OK;
+  });
 }
 
 int launch_axis_mean(const float* in, float* out, int64_t groups, int inner, int cols, hipStream_t st) {
@@ -90,15 +85,13 @@ static int launch_span_mean_t(const T* seq, const int64_t* start, const int64_t*
     set_error("span_mean: D=%d must be a multiple of 4", D);
     return DRIN_E_SHAPE;
   }
-  for (int b0 = 0; b0 < B; b0 += 65535) {
-    const int nb = B - b0 < 65535 ? B - b0 : 65535;
+  return for_grid_slices(B, [&](int64_t b0, int nb) -> int {
     dim3 grid((unsigned)cdiv(D / 4, 256), (unsigned)nb);
     KernelTimer timer(DRIN_KC_POOL, st);
-    hipLaunchKernelGGL(k_span_mean<T>, grid, dim3(256), 0, st, seq + (int64_t)b0 * L * D, start + b0, end + b0,
-                       out + (int64_t)b0 * D, L, D / 4);
+    hipLaunchKernelGGL(k_span_mean<T>, grid, dim3(256), 0, st, seq + b0 * L * D, start + b0, end + b0, out + b0 * D, L, D / 4);
     DRIN_CHECK_LAUNCH("k_span_mean");
-  }
-  return DRIN_OK;
+    return DRIN_OK;
+  });
 }
 
 int launch_span_mean(const float* seq, const int64_t* start, const int64_t* end, float* out, int B, int L, int D,
@@ -385,11 +378,11 @@ int launch_miei(const float* mobj, const float* mscore, const float* eobj, const
   }
   KernelTimer timer(DRIN_KC_EDGE, st);
   const size_t lds = ((size_t)Km * R + Km) * sizeof(float);
-  if (Ke == 1 && R <= 2048 && lds <= 64 * 1024 && B <= 65535) {
+  if (Ke == 1 && R <= 2048 && lds <= 64 * 1024 && B <= kMaxGridY) {
     hipLaunchKernelGGL(k_miei_lds, dim3((unsigned)cdiv(N, kMieiChunk), (unsigned)B), dim3(256), lds, st, mobj, mscore,
                        eobj, escore, out, N, Km, R / 4, cos_eps, miei_eps, scale, e_index);
   } else if (e_index != nullptr) {
-    set_error("miei: table form (entity_index) is built for Ke == 1, R <= 2048 and at most 65535 mentions per call");
+    set_error("miei: table form (entity_index) is built for Ke == 1, R <= 2048 and at most %d mentions per call", kMaxGridY);
     return DRIN_E_UNSUPPORTED;
   } else {
     hipLaunchKernelGGL(k_miei, dim3((unsigned)cdiv(pairs, 4)), dim3(256), 0, st, mobj, mscore, eobj, escore, out, pairs,

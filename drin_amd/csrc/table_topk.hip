@@ -285,7 +285,7 @@ int launch_topk_finish(const float* keys, const int64_t* rows, int batch, int kp
 }
 
 int launch_row_inv_norms(const float* rows, int64_t num_rows, int width, float eps, float* out, hipStream_t st) {
-  const int64_t blocks = cdiv(num_rows, 4) < 65535 * 16 ? cdiv(num_rows, 4) : 65535 * 16;
+  const int64_t blocks = row_blocks(num_rows);
   return timed(DRIN_KC_EDGE, st, "k_row_inv_norms", [&] {
     hipLaunchKernelGGL(k_row_inv_norms, dim3((unsigned)blocks), dim3(256), 0, st, rows, num_rows, width / 4, eps, out);
   });
@@ -325,7 +325,7 @@ struct TopkLayout {
 
 int check_topk_shape(const char* who, int64_t E, int batch, int width, int k) {
   DRIN_TRY(check_count(who, "num_entities", E, 1, INT64_MAX / 4096));
-  DRIN_TRY(check_count(who, "batch", batch, 1, 65535));
+  DRIN_TRY(check_count(who, "batch", batch, 1, kMaxGridY));
   DRIN_TRY(check_width4(who, width));
   DRIN_TRY(check_count(who, "k", k, 1, kMaxKp));
   if (k > E) {
@@ -404,7 +404,7 @@ int drin_topk_update(const float* block, int64_t ld, int32_t batch, int64_t cols
     set_error("%s: out_keys and out_rows go together (both NULL: no finishing pass)", who);
     return DRIN_E_NULL;
   }
-  DRIN_TRY(check_count(who, "batch", batch, 1, 65535));
+  DRIN_TRY(check_count(who, "batch", batch, 1, kMaxGridY));
   DRIN_TRY(check_count(who, "k", k, 1, kMaxKp));
   DRIN_TRY(check_count(who, "cols", cols, 0, INT32_MAX));
   DRIN_TRY(check_count(who, "col_base", col_base, 0, INT64_MAX / 4096));

@@ -58,17 +58,15 @@ __global__ void __launch_bounds__(64) k_mention_reduce_vec(const float* __restri
 
 int launch_mention_reduce_vec(const float* w1, const float* v1, const float* w2, const float* v2, const float* u,
                               float* out, int B, int N, int D, float scale, bool mean_style, hipStream_t st) {
-  if (B <= 0) return DRIN_OK;
-  for (int b0 = 0; b0 < B; b0 += 65535) {
-    const int nb = B - b0 < 65535 ? B - b0 : 65535;
-    const int64_t vo = (int64_t)b0 * N * D;
+  return for_grid_slices(B, [&](int64_t b0, int nb) -> int {
+    const int64_t vo = b0 * N * D;
     KernelTimer timer(DRIN_KC_GCN, st);
     hipLaunchKernelGGL(k_mention_reduce_vec, dim3((unsigned)cdiv(D / 4, 64), (unsigned)nb), dim3(64), 0, st, w1 + vo,
-                       v1 + vo, w2 ? w2 + vo : nullptr, v2 ? v2 + vo : nullptr, u ? u + (int64_t)b0 * D : nullptr,
-                       out + (int64_t)b0 * D, N, D / 4, scale, mean_style ? 1 : 0);
+                       v1 + vo, w2 ? w2 + vo : nullptr, v2 ? v2 + vo : nullptr, u ? u + b0 * D : nullptr, out + b0 * D, N,
+                       D / 4, scale, mean_style ? 1 : 0);
     DRIN_CHECK_LAUNCH("k_mention_reduce_vec");
-  }
-  return DRIN_OK;
+    return DRIN_OK;
+  });
 }
 
 // out[p, :] = e1[p, :] m1[b, :] + e2[p, :] m2[b, :] + v[p, :]          (model.py:146 + :128 self term)

@@ -591,9 +591,9 @@ def test_cached_forward_reports_a_bad_row_past_524288_pairs():
 
 
 # ---- drin_forward / drin_backward above 65 535 mentions, through the C ABI ----------------------------------------------------------
-# api.hip takes another kernel set there (launch_mention_aggregate + launch_entity_aggregate for launch_layer_aggregate,
-# launch_mention_reduce for launch_mention_reduce2[_pair]; the one-wave-per-pair kernels on the flat grid; every per-mention launch
-# in two slices).  Reference: the fp64 oracle on the same batch, at the bars of tests/test_gpu_parity.py (scores 1e-4, every
+# api.hip makes the calls it makes below the cap; the launchers differ there (launch_layer_aggregate and
+# launch_mention_reduce2[_pair] move their pointers to a second slice, the text / image and edge-type strides those of the whole
+# batch; the one-wave-per-pair kernels on the flat grid; every per-mention launch in two slices).  Reference: the fp64 oracle on the same batch, at the bars of tests/test_gpu_parity.py (scores 1e-4, every
 # parameter gradient 2e-4 of its norm); second, the same batch sent as slices of Model.MAX_CALL_MENTIONS mentions - scores to the
 # 5e-6 re-association bound documented there, the summed gradients to the gradient bar.
 ABI_VARIANTS = {"dynamic": {}, "static": dict(gcn_edge_type="static"), "vector": dict(gcn_edge_feature="vector"),

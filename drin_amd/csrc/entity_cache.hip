@@ -38,6 +38,7 @@
 // 2.3e-6 emulated on a homogeneous table.  Not kept: h_i is a VERTEX operand - the cached path forms the layer-1 mention
 // aggregates from sum_n e h_i - so its 2^-12 rounding is averaged only as long as the candidates' rows are of one size, and
 // ten times the error for 4 % of the chunk time is the wrong trade on a 1e-4 bar: profiles/r4_mixed_cache_ab.txt.)
+// Both layouts are decoded and every field checked against fp64 in tests/test_gpu_cache_rows.py.
 #include <string.h>
 
 #include "fused.h"
@@ -145,6 +146,27 @@ __global__ void __launch_bounds__(256) k_entity_cache_rows(const CacheBuildArgs 
   }
   store_row<RV>(row + 5 * D, o, lane, R4);
   if (lane == 0) st4(row + 5 * D + R, make_float4(sg, 0.f, 0.f, 0.f));
+}
+
+// The four table-sized products of the builder.  The exact-fp32 GEMM adds the K products of an output in ONE k-ordered fp32
+// chain (gemm_f32.hip), whose rounding grows with the chain: at K = 2048 it is 2.4e-6 on rows of size 1, five times what the
+// same product costs summed in blocks (tests/test_gpu_cache_rows.py measures it per field against fp64).  A cache row is
+// written once per weight version and read by every scoring call after it, so under DRIN_PREC_F32 - the precision that is
+// chosen for its accuracy - the builder adds K in slices of 512: each slice is a chain of its own from zero, added to the row
+// by the GEMM's accumulate epilogue.  Cost: one more pass over the [rows][D] output per slice (K = 2048: 3 of them, 24 bytes
+// of traffic per output element next to its 2 048 multiply-adds); no scratch.  The split-bf16 precisions keep their one launch.
+constexpr int kCacheGemmKSlice = 512;
+static int cache_gemm_nt(const NtProduct& p, int prec, hipStream_t st) {
+  if (prec != DRIN_PREC_F32 || p.k_red <= kCacheGemmKSlice) return launch_gemm_nt(p, prec, st);
+  for (int k0 = 0; k0 < p.k_red; k0 += kCacheGemmKSlice) {
+    NtProduct q = p;
+    q.x.p = p.x.p + k0;
+    q.w.p = p.w.p + k0;
+    q.k_red = p.k_red - k0 < kCacheGemmKSlice ? p.k_red - k0 : kCacheGemmKSlice;
+    if (k0) q.bias = nullptr, q.accumulate = true;
+    DRIN_TRY(launch_gemm_nt(q, prec, st));
+  }
+  return DRIN_OK;
 }
 
 // DRIN_CACHE_MIXED_F16: the two table-sized edge-update products fv_t, fv_i ([rows][2 D] fp32 scratch) -> scaled fp16 in the
@@ -762,11 +784,11 @@ DRIN_API int drin_build_entity_cache(const drin_config* cfg, const drin_batch* t
     float* const y_fvt = mixed ? tmp : crow + 2 * D;
     float* const y_fvi = mixed ? tmp + D : crow + 3 * D;
     const int64_t ldy = mixed ? 2 * (int64_t)D : ldc;
-    DRIN_TRY(launch_gemm_nt({{xt, D}, {pb + P.c_txt, D}, nullptr, crow, ldc, rows, D, D}, prec, st));
-    DRIN_TRY(launch_gemm_nt({{ximg, R}, {pb + P.c_img, R}, nullptr, y_hi, ldc, rows, D, R}, prec, st));
+    DRIN_TRY(cache_gemm_nt({{xt, D}, {pb + P.c_txt, D}, nullptr, crow, ldc, rows, D, D}, prec, st));
+    DRIN_TRY(cache_gemm_nt({{ximg, R}, {pb + P.c_img, R}, nullptr, y_hi, ldc, rows, D, R}, prec, st));
     if (dyn) {  // fv = x (W_v1 W_e)^T + (W_v1 b_e + b_v1); etmp keeps W_v1 [W_et | W_ei] un-transposed, row stride D + R
-      DRIN_TRY(launch_gemm_nt({{xt, D}, {pb + P.etmp, D + R}, pb + P.k_t, y_fvt, ldy, rows, D, D}, prec, st));
-      DRIN_TRY(launch_gemm_nt({{ximg, R}, {pb + P.etmp + D, D + R}, pb + P.k_i, y_fvi, ldy, rows, D, R}, prec, st));
+      DRIN_TRY(cache_gemm_nt({{xt, D}, {pb + P.etmp, D + R}, pb + P.k_t, y_fvt, ldy, rows, D, D}, prec, st));
+      DRIN_TRY(cache_gemm_nt({{ximg, R}, {pb + P.etmp + D, D + R}, pb + P.k_i, y_fvi, ldy, rows, D, R}, prec, st));
     }
     if (mixed) {   // (static edges: zero units, unit scales)
       KernelTimer timer(DRIN_KC_STREAM, st);

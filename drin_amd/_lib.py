@@ -356,6 +356,12 @@ EXPORTS = {
     # (g_edge_row, g_vertex_row, start, end, max_index, representation, has_encoded, grad_raw, grad_encoded, batch, seq_len, width, stream)
     "drin_mention_rows_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                                         C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    # gradient x input attribution (csrc/attribution_kernels.hip):
+    # (tokens, token_dtype, mask, entity_index, num_entities, index_status, grad_pooled, out, pairs, T, width, stream),
+    # (x, x_dtype, g, out, rows, width, stream)
+    "drin_token_attribution": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
+    "drin_rows_dot": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
     "drin_profile_begin": (C.c_int, [C.c_int]),
     "drin_profile_end": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "drin_kernel_class_name": (C.c_char_p, [C.c_int]),

@@ -179,6 +179,10 @@ class EncoderModel(Model):
     def grad_bucket(self):
         raise NotImplementedError(f"Model.grad_bucket (gradient bucket views, OverlappedStep) {NOT_BUILT}")
 
+    def attribute(self, batch, candidate=None, weights=None):
+        raise NotImplementedError("Model.attribute (gradient x input attribution) under a transformer / none mention encoder is out of "
+                                  "scope of DESIGN.md section 31: the linear mention encoder only")
+
     # ---- the forward -----------------------------------------------------------------------------------------------------
     def forward(self, batch) -> torch.Tensor:
         if isinstance(batch, IndexedBatch):

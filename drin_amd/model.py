@@ -660,6 +660,48 @@ class _DrinScore(torch.autograd.Function):
         return (None, None, None, *out, *feats)
 
 
+class Attribution(NamedTuple):
+    """What `Model.attribute` returns: `scores [B, N]`, the explained `candidate [B]` (None when `weights` was given) and, per
+    float tensor of the batch, input x gradient summed over the feature axis - fp32, on the batch's device."""
+    scores: torch.Tensor
+    candidate: Optional[torch.Tensor]
+    mention_text: torch.Tensor             # [B, L]
+    mention_image: torch.Tensor            # [B, P]
+    mention_object_score: torch.Tensor     # [B, Km]
+    entity_text: torch.Tensor              # [B, N, T] for token-level entities, [B, N] for pooled
+    entity_image: torch.Tensor             # [B, N], inner dims summed
+    entity_object_score: torch.Tensor      # [B, N, Ke]
+    miet_similarity: torch.Tensor          # [B, N]
+    mtei_similarity: torch.Tensor          # [B, N]
+
+
+# positions in the 14-sequence of the tensors `Model.attribute` explains, under their `_INPUT_FIELDS` names (the object feature
+# rows, positions 5 and 10, enter only cosines: their gradient x input is identically 0 and is not formed)
+_ATTRIBUTED = {0: "mention_text", 4: "mention_image", 6: "mention_object_score", 7: "entity_text", 9: "entity_image",
+               11: "entity_object_score", 12: "miet_similarity", 13: "mtei_similarity"}
+
+
+def _feat_dtype(t: torch.Tensor) -> int:
+    return _lib.FEAT_BF16 if t.dtype == torch.bfloat16 else _lib.FEAT_F32
+
+
+def _stored(t: torch.Tensor) -> torch.Tensor:
+    """`t` as the attribution kernels read it: contiguous, bf16 kept as it is, anything else fp32."""
+    return t.detach().contiguous() if t.dtype in (torch.float32, torch.bfloat16) else t.detach().to(torch.float32).contiguous()
+
+
+@torch.no_grad()
+def _rows_dot(x: torch.Tensor, g: torch.Tensor, lead: int) -> torch.Tensor:
+    """`(x * g).sum` over everything behind the first `lead` dims, by `drin_rows_dot`: `x` fp32 or bf16 (read in place), `g` fp32."""
+    x, g = _stored(x), g.contiguous()
+    shape = tuple(x.shape[:lead])
+    out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    if out.numel():
+        _lib.check(_lib.load().drin_rows_dot(x.data_ptr(), _feat_dtype(x), g.data_ptr(), out.data_ptr(), out.numel(),
+                                             x.numel() // out.numel(), torch.cuda.current_stream(x.device).cuda_stream))
+    return out
+
+
 def _invalidate_after_load(module, _incompatible_keys) -> None:
     module.invalidate()
 
@@ -971,6 +1013,129 @@ class Model(nn.Module):
                               feats=_feature_inputs(call, route.token_block) if route.training else ((), ()))
         if indexed:
             self._watch_indices(call.device)                           # the kernels clamp and report: after their launches
+        return out
+
+    def attribute(self, batch, candidate: Optional[torch.Tensor] = None, weights: Optional[torch.Tensor] = None) -> Attribution:
+        """Gradient x input of `sum(weights * scores)` for every float tensor of the batch, summed over the feature axis: what
+        `(x * x.grad).sum(-1)` gives on the reference's plain-torch forward with the model frozen.
+        `batch`: the 14-sequence (fp32 or bf16 features) or an `IndexedBatch`.  `weights [B, N]` float, or `candidate [B]` int64 (a
+        one-hot row per mention), not both; with neither, each mention's arg-max over the first N - 1 columns (the reference's
+        loss and metric drop the answer slot, common/utils.py:36-37,61-62).
+        Token-level entity text is attributed per token `[B, N, T]` WITHOUT its `[B, N, T, D]` gradient: the tokens are pooled
+        ahead, the scoring backward returns the pooled rows' gradient `[B, N, D]`, and `drin_token_attribution` contracts it with
+        the original block - or with the token table through the candidate index, nothing gathered.  Two identities are used:
+        token 0 feeds only the text-text cosine (model.py:73-75) and the object feature rows feed only cosines (model.py:78-92); a
+        cosine is homogeneous of degree 0 in each row, so `<x, d cos / dx> = 0` (Euler): token 0 is exactly 0 and the object
+        feature rows are NOT returned.
+        Works whatever `self.training` and the parameters' `requires_grad` say and changes neither; no parameter and no tensor of
+        the caller receives a `.grad`.  Precision "f32" or split-bf16 ("bf16x3_if16" runs as "bf16x3").  A mention with an empty
+        span is NaN in its own rows only.
+        The token kernel reads the tokens where they are, so their storage matters: a token TABLE must be contiguous float32 or
+        bfloat16 (`ValueError` otherwise: widening or copying a table is the caller's decision); a per-pair token BLOCK of another
+        dtype is widened to fp32 and a non-contiguous one is copied, once - the one case in which a block-sized tensor is made.
+        A `candidate` outside `[0, N - 1]` is clamped without a synchronisation; `validate_indices` raises `IndexError` instead."""
+        if candidate is not None and weights is not None:
+            raise ValueError("attribute: give `candidate` or `weights`, not both")
+        if isinstance(batch, IndexedBatch) and batch.table.text.dim() == 3:
+            text = batch.table.text
+            if text.dtype not in (torch.float32, torch.bfloat16) or not text.is_contiguous():
+                raise ValueError(f"attribute: the token table is read in place and must be contiguous float32 or bfloat16 (got {text.dtype}"
+                                 f"{'' if text.is_contiguous() else ', not contiguous'}); convert the EntityTable once")
+        if self._index_watch and not torch.cuda.is_current_stream_capturing():
+            self.check_indices(wait=False)
+        B = batch.candidates.shape[0] if isinstance(batch, IndexedBatch) else batch[0].shape[0]
+        N = self.cfg.num_candidates_model
+        for name, t, shape in (("weights", weights, (B, N)), ("candidate", candidate, (B,))):
+            if t is not None and tuple(t.shape) != shape:
+                raise ValueError(f"attribute: {name} has shape {tuple(t.shape)}, expected {shape}")
+        step = self.MAX_CALL_MENTIONS
+        if B <= step:
+            return self._attribute(batch, candidate, weights)
+        parts = [self._attribute(part, None if candidate is None else candidate[b0:b0 + step],
+                                 None if weights is None else weights[b0:b0 + step])
+                 for b0, part in zip(range(0, B, step), _split_mentions(batch, step))]
+        return Attribution(*(None if parts[0][k] is None else torch.cat([p[k] for p in parts], 0) for k in range(len(parts[0]))))
+
+    def _attribute(self, batch, candidate, weights) -> Attribution:
+        """One library call's worth of `attribute` (at most MAX_CALL_MENTIONS mentions)."""
+        lib = _lib.load()
+        table, index = None, None
+        if isinstance(batch, IndexedBatch):
+            batch = self._clamped(batch)                               # the torch gathers and the token kernel trust the index
+            self._watch_indices(batch.candidates.device)
+            table, index = batch.table, batch.candidates.contiguous()
+            if table.text.dim() == 3:
+                seq, cls = batch.gathered_pooled(self.cfg)             # pooled per ENTITY, once per table version
+                tokens, mask = table.text, table.mask
+            else:
+                seq, cls, tokens, mask = batch.gathered(), None, None, None
+        else:
+            if len(batch) not in (14, 15):
+                raise ValueError(f"batch must be the 14-sequence of drin/data.py:110-126 (got {len(batch)} items)")
+            seq, cls, tokens, mask = list(batch[:14]), None, None, None
+            etf = seq[7]
+            if etf.dim() == 4:                                         # token-level: pooled ahead, the block is read once in place
+                if etf.dtype not in (torch.float32, torch.bfloat16):
+                    etf = etf.to(torch.float32)
+                tokens, mask = etf.detach().contiguous(), seq[8]       # (a copy only of a non-contiguous block, and the only one)
+                cls = tokens[:, :, 0, :]
+                seq[7], seq[8] = _pool_tokens(tokens, mask), torch.zeros(etf.shape[0], dtype=torch.int64, device=etf.device)
+        dev = seq[0].device
+        # detached fp32 leaves of the small tensors (a view of the caller's storage where that is fp32 and contiguous already)
+        leaves = {}
+        for i, field in _ATTRIBUTED.items():
+            leaves[field] = seq[i].detach().to(torch.float32).contiguous().requires_grad_(True)
+        call_seq = [leaves[_ATTRIBUTED[i]] if i in _ATTRIBUTED else (t.detach() if torch.is_tensor(t) else t)
+                    for i, t in enumerate(seq[:14])]
+        params = [p.detach() for p in _param_list(self)]              # no parameter is asked for a gradient: drin_backward_ex gets grads = NULL
+        with torch.enable_grad():
+            call = _Call(self.cfg, call_seq, self._unfused_precision(), entity_text_cls=None if cls is None else cls.detach())
+            Bc, N = call.B, call.N
+            scores = call.scores() if Bc == 0 else self._score(call, None, True, *params, feats=_feature_inputs(call))
+        with torch.no_grad():
+            if weights is None:
+                if candidate is None:
+                    chosen = scores.detach()[:, :max(N - 1, 1)].argmax(1)
+                else:
+                    raw = candidate.to(device=dev, dtype=torch.int64)
+                    chosen = raw.clamp(0, N - 1)                       # never an out-of-range scatter; no synchronisation
+                    if self.validate_indices and Bc and not torch.cuda.is_current_stream_capturing() and not bool((chosen == raw).all()):
+                        raise IndexError(f"attribute: candidate must be in [0, {N - 1}]")
+                G = torch.zeros(Bc, N, dtype=torch.float32, device=dev)
+                G.scatter_(1, chosen.view(-1, 1), 1.0)
+            else:
+                chosen, G = None, weights.to(device=dev, dtype=torch.float32).contiguous()
+        fields = list(leaves)
+        if Bc == 0:
+            grads = [torch.zeros_like(leaves[f]) for f in fields]
+        else:
+            grads = torch.autograd.grad(scores, [leaves[f] for f in fields], grad_outputs=G)
+        g = dict(zip(fields, grads))
+        with torch.no_grad():
+            x = {field: seq[i] for i, field in _ATTRIBUTED.items()}
+            if tokens is not None and Bc == 0:
+                entity_text = torch.empty(0, N, tokens.shape[-2], dtype=torch.float32, device=dev)
+            elif tokens is not None:
+                T, D = tokens.shape[-2], tokens.shape[-1]
+                mask = mask.to(device=dev, dtype=torch.int64).contiguous()
+                entity_text = torch.empty(Bc, N, T, dtype=torch.float32, device=dev)
+                gp = g["entity_text"].contiguous()
+                _lib.check(lib.drin_token_attribution(
+                    tokens.data_ptr(), _feat_dtype(tokens), mask.data_ptr(), None if index is None else index.data_ptr(),
+                    0 if table is None else table.num_entities, None if index is None else self._status_words(dev).data_ptr(),
+                    gp.data_ptr(), entity_text.data_ptr(), Bc * N, T, D, call.stream()))
+            else:
+                entity_text = _rows_dot(x["entity_text"], g["entity_text"], 2)
+            out = Attribution(
+                scores=scores.detach(), candidate=chosen,
+                mention_text=_rows_dot(x["mention_text"], g["mention_text"], 2),
+                mention_image=_rows_dot(x["mention_image"], g["mention_image"], 2),
+                mention_object_score=leaves["mention_object_score"].detach() * g["mention_object_score"],
+                entity_text=entity_text,
+                entity_image=_rows_dot(x["entity_image"], g["entity_image"], 2),
+                entity_object_score=leaves["entity_object_score"].detach() * g["entity_object_score"],
+                miet_similarity=leaves["miet_similarity"].detach() * g["miet_similarity"],
+                mtei_similarity=leaves["mtei_similarity"].detach() * g["mtei_similarity"])
         return out
 
     def wait_for_parameters(self) -> None:

@@ -1182,6 +1182,33 @@ DRIN_API int drin_mention_rows_bwd(const float* g_edge_row, const float* g_verte
                                    const int32_t* max_index, int32_t representation, int32_t has_encoded, float* grad_raw,
                                    float* grad_encoded, int32_t batch, int32_t seq_len, int32_t width, void* stream);
 
+/* ---- gradient x input attribution (attribution_kernels.hip) ------------- */
+
+/* The contraction that stands where drin_pool_bwd expands: of the token block's gradient x input, summed over the width, only the
+ * terms the entity pooling passes a gradient to (ghmfc.py:245-249: entity_text_feature[1:ntok-1] with ntok = sum(mask), then the
+ * mean over the slice; drin_pool_bwd's share g / cnt):
+ *   out[p, t] = <tokens[row, t, :], grad_pooled[p, :]> / cnt   for 1 <= t <= cnt,   cnt = ntok - 2  (ntok == 0: the slice's -1
+ *   stop, cnt = T - 2),   exactly 0.0f elsewhere - token 0 too: it feeds only the text-text cosine (model.py:73-75), which is
+ *   homogeneous of degree 0 in that row, so its gradient x input is 0.
+ * tokens is [pairs, T, width] (row = p) or, with entity_index != NULL, a table [num_entities, T, width] read at row
+ * entity_index[p] (int64 [pairs]); mask (int64) has the same leading shape and is read through the same index.  A row outside
+ * [0, num_entities) is clamped before anything is read and reported in index_status (int32[4] or NULL: drin_batch.index_status'
+ * convention).  token_dtype: DRIN_FEAT_F32 or DRIN_FEAT_BF16 (widened exactly); grad_pooled [pairs, width] and out [pairs, T] are
+ * fp32.  Every element of out is WRITTEN; rows outside the kept slice are never loaded; a pair with an empty slice (ntok 1 or 2)
+ * gets a row of zeros; a NaN or an infinity in grad_pooled reaches the kept tokens of its own pair only.  No atomics: the same
+ * bits every run.  16-byte aligned tokens / grad_pooled / out, width % 4 == 0 (bf16: % 8), T >= 1, pairs >= 0 (any count: the
+ * launches are sliced).  Profiler class DRIN_KC_POOL. */
+DRIN_API int drin_token_attribution(const void* tokens, int32_t token_dtype, const int64_t* mask, const int64_t* entity_index,
+                                    int64_t num_entities, int32_t* index_status, const float* grad_pooled, float* out,
+                                    int64_t pairs, int32_t T, int32_t width, void* stream);
+
+/* out[r] = sum_c x[r, c] g[r, c]: what (x * x.grad).sum(-1) gives for every other feature of the batch (mention tokens, image
+ * regions, image rows with their inner dims flattened into the row, pooled entity text).  x [rows, width] fp32 or bf16
+ * (x_dtype, widened exactly), g [rows, width] and out [rows] fp32.  One wave per row up to width 2048, a workgroup per row above;
+ * fixed summation order: the same bits every run.  16-byte aligned x / g, width % 4 == 0 (bf16: % 8), 0 <= rows <= 2^31.
+ * Profiler class DRIN_KC_POOL. */
+DRIN_API int drin_rows_dot(const void* x, int32_t x_dtype, const float* g, float* out, int64_t rows, int32_t width, void* stream);
+
 /* ---- in-process kernel timing (bench.py's roofline leg) ---------------------------------------- */
 
 /* Kernel classes the launches are attributed to. */

@@ -598,7 +598,7 @@ struct CachedLayout {  // workspace of drin_forward_cached, offsets in floats
     // workgroup.  cached_chunk_candidates() is the one place that knows.
     chunks = (int)((N + cached_chunk_candidates(c) - 1) / cached_chunk_candidates(c));
     Arena A;
-    const bool planes = c.precision == DRIN_PREC_BF16X3 || c.precision == DRIN_PREC_BF16X3_ALL;
+    const bool planes = folded_planes(c);
     span_mean = A.take(B * D);
     mimg = A.take(B * R);
     vm0 = A.take(2 * B * D);
@@ -624,7 +624,7 @@ int cached_layout_selfcheck(const drin_config& c) {
   const size_t B = c.batch, M = B * c.num_candidates, D = c.embed_dim, R = c.image_dim;
   CachedLayout L;
   L.build(c);
-  const size_t ch = (size_t)L.chunks, planes = c.precision != DRIN_PREC_F32;
+  const size_t ch = (size_t)L.chunks, planes = folded_planes(c);
   const Region ws[] = {
       {"span_mean", L.span_mean, B * D}, {"mimg", L.mimg, B * R}, {"vm0", L.vm0, 2 * B * D}, {"hmfu", L.hmfu, 4 * B * D},
       {"e1m", L.e1m, 4 * M}, {"c_part", L.c_part, B * ch * (2 * D + 4)}, {"s2_part", L.s2_part, B * ch * 2 * D},
@@ -845,12 +845,11 @@ DRIN_API int drin_forward_cached(const drin_config* cfg, const drin_batch* b, co
     set_error("drin_forward_cached: batch %d exceeds the grid limit; split the batch", B);
     return DRIN_E_SHAPE;
   }
-  const int prec = cfg->precision;
-  const bool planes = (prec == DRIN_PREC_BF16X3 || prec == DRIN_PREC_BF16X3_ALL) && (D % 32 == 0);
+  const bool planes = folded_planes(*cfg) && nt_planes_width(D);
   const drin_layer_params& L1 = params->layer[0];
   __bf16* e1_hi = reinterpret_cast<__bf16*>(ws + L.p_et1);
   const size_t MD = (size_t)M * D;
-  if (!planes && (prec == DRIN_PREC_BF16X3 || prec == DRIN_PREC_BF16X3_ALL)) {
+  if (!planes && folded_planes(*cfg)) {
     set_error("drin_forward_cached: split-bf16 precision needs embed_dim %% 32 == 0 (got %d)", D);
     return DRIN_E_UNSUPPORTED;
   }
@@ -892,9 +891,8 @@ DRIN_API int drin_forward_cached(const drin_config* cfg, const drin_batch* b, co
   a.gamma = L1.ln_weight;
   a.beta = L1.ln_bias;
   a.e1m = ws + L.e1m;
-  a.et1 = planes ? nullptr : ws + L.et1;
-  a.et1_hi = planes ? e1_hi : nullptr;
-  a.et1_lo = planes ? e1_hi + MD : nullptr;
+  if (planes) a.et1_hi = e1_hi, a.et1_lo = e1_hi + MD;
+  else a.et1 = ws + L.et1;
   a.c_part = ws + L.c_part;
   a.s2_part = ws + L.s2_part;
   a.chunks = L.chunks;

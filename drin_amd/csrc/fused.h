@@ -49,6 +49,11 @@ struct Prepared {  // offsets in floats
 
 // DRIN_OK when `c` can take the folded two-layer pipelines (fused_forward.hip, entity_cache.hip)
 int fused_supported(const drin_config* c);
+// split-bf16 widths of every product of the folded paths (DRIN_PREC_BF16X3_IF16 differs in the image contraction's passes only)
+inline int folded_precision(const drin_config* c) { return c->precision == DRIN_PREC_BF16X3_IF16 ? (int)DRIN_PREC_BF16X3 : c->precision; }
+// "the pair-sized contractions of the folded paths run on bf16 planes", as far as the precision says: what the two layouts size
+// their plane regions by.  A call uses them where the widths allow it too (nt_planes_width) and refuses or falls back otherwise.
+inline bool folded_planes(const drin_config& c) { return split_bf16(folded_precision(&c)); }
 // workgroups (candidate chunks) per mention of the per-entity-cache path's kernels for this call (entity_cache.hip)
 int cached_chunks_per_mention(const drin_config& c);
 

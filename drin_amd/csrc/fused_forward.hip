@@ -28,11 +28,119 @@ namespace drin {
 // DRIN_PREC_BF16X3_IF16: the shortest candidate list whose mean averages the one-pass image contraction's noise far enough
 constexpr int kMixedMinCandidates = 64;
 
+// The side schedule's grid.  G, f and the least tile count: profiles/image_overlap_ab.txt - G in {32, 48, 64, 96} x f in 0.1 .. 0.9 on one
+// resident headline batch: the side part may outlast the stream pass (it goes on under the layer-1 mention chain and x_t C_t^T), so
+// the step falls with f until the side part ends at the join: G = 64, f = 0.9 (headline 16.00 -> 14.60 ms over fresh processes).  Fewer
+// workgroups cannot finish in time, 96 cost the stream pass and x_t C_t^T more than they save.  Below ~1 200 tiles (B = 1 024 at N = 101)
+// the gain sinks into the noise, so smaller calls keep the one launch.  (The three macros exist for probe builds of that file's grid.)
+#ifndef DRIN_SIDE_WGS
+#define DRIN_SIDE_WGS 64          // G
+#endif
+#ifndef DRIN_SIDE_PERMILLE
+#define DRIN_SIDE_PERMILLE 900    // f, in thousandths of the row tiles
+#endif
+#ifndef DRIN_SIDE_MIN_TILES
+#define DRIN_SIDE_MIN_TILES 1200
+#endif
+#ifdef DRIN_SIDE_PROBE   // probe builds only (tools/probes/image_overlap_ab.py): G and f set between calls of one process
+static int g_probe_wgs = DRIN_SIDE_WGS, g_probe_permille = DRIN_SIDE_PERMILLE;
+extern "C" __attribute__((visibility("default"))) void drin_probe_side_plan(int wgs, int permille) { g_probe_wgs = wgs, g_probe_permille = permille; }
+#endif
+
+// How a call runs x_i C_i^T.  The rows are read in place wherever they can be: writing 8 KB/pair of planes from the stream kernel costs
+// it more (measured twice on one box: +1.0 ms at B = 4096) than the LDS-DMA kernel gains on that GEMM (-0.35 ms).
+enum class ImageForm {
+  kGeneric,        // launch_gemm_nt at the call's precision: exact fp32 - or, at widths that keep a split-bf16 call off the planes, its own choice
+  kSplitRows,      // fp32 rows read in place, split on the fly: 3 passes
+  kBf16Rows,       // bf16 rows read in place, their own (only) plane: 2 passes
+  kStreamPlanes,   // the table form, which has to gather the rows anyway: the stream pass writes them as planes (hi, lo; bf16 rows: hi alone)
+  // DRIN_PREC_BF16X3_IF16: ONE pass of the fp16 matrix instruction on single planes.  k_entity_stream, which holds every image row in
+  // registers anyway, writes it as fp16(x / 2^ceil(log2 max|x|)) with the scale beside it; the folded weight is one fp16 plane under one
+  // scale (drin_prepare); the epilogue multiplies both back (bf16-STORED rows measured a wash and keep their two passes)
+  kF16Plane,
+};
+enum class Refusal { kNone, kIndexWithoutTable, kTableOffPlanes, kBf16OffPlanes };
+
+// The plan of one folded forward: which operands travel as bf16 planes and how x_i C_i^T runs - a pure function of the configuration
+// and of `indexed` (entity_index given): no HIP call, no pointer.  FusedLayout sizes its regions from it, the call launches by it (after
+// demoting it by what only the run knows), the drin_image_contraction_* queries answer its fields, fused_layout_selfcheck checks it.
+struct FoldedPlan {
+  bool plane_regions;   // the precision asks for planes: the regions exist (whichever way `indexed` falls, so do the sizes below)
+  bool planes;          // ... and the widths allow them: the three pair-sized contractions run on the LDS-DMA kernel of gemm_x3_planes.hip
+  bool xt_lo;           // x_t has a lo plane (pooled entity text stored as bf16 is exact in its hi plane: two MFMAs per tile pair)
+  ImageForm form;
+  int passes;           // what drin_image_contraction_passes answers
+  size_t plane_floats, p_xi_floats, xi_scale_floats, splitk_floats;   // p_xt and p_et1 each, p_xi, xi_scale, splitk
+  // The eager side schedule: row tiles [0, S) as G persistent workgroups on the library's side stream, under the entity stream
+  // pass, the rest at full grid behind it.  {0, 0}: one launch on the caller's stream.
+  int64_t S;
+  int G;
+  Refusal refusal;
+};
+static FoldedPlan folded_plan(const drin_config& c, bool indexed) {
+  FoldedPlan p = {};
+  const int D = c.embed_dim, R = c.image_dim;
+  const int64_t M = (int64_t)c.batch * c.num_candidates;
+  const size_t B = c.batch, MD = (size_t)M * D, MR = (size_t)M * R;
+  const bool bf16_rows = c.feature_dtype == DRIN_FEAT_BF16, if16 = c.precision == DRIN_PREC_BF16X3_IF16;
+  p.plane_regions = folded_planes(c);
+  p.planes = p.plane_regions && nt_planes_width(D) && nt_planes_width(R);
+  p.xt_lo = !(bf16_rows && c.entity_tokens <= 0);
+  // The one fp16 pass (what is left of its gate - 16-byte alignment of workspace slots - holds by the workspace contract): per-pair
+  // fp32-stored rows, the exact widths the stream kernel's fp16 hand-over is instantiated for, at least half a round of 256 x 256
+  // tiles, a list long enough to average the pass's rounding (on TRAINED weights 1.2e-4 at N = 11, outside the bar, 2e-5 at N = 101:
+  // profiles/r4_precision_on_trained_weights.txt).  Everything else: three passes, bit for bit.
+  const bool f16 = if16 && !indexed && !bf16_rows && c.num_candidates >= kMixedMinCandidates && D == 768 && R == 2048 &&
+                   cdiv(M, 256) * cdiv(D, 256) >= 128;
+  p.form = !p.planes ? ImageForm::kGeneric : indexed ? ImageForm::kStreamPlanes : f16 ? ImageForm::kF16Plane : bf16_rows ? ImageForm::kBf16Rows : ImageForm::kSplitRows;
+  // (kGeneric in a split-bf16 precision: launch_gemm_nt splits fp32 rows itself from 256 pairs up, and bf16 rows are refused)
+  p.passes = p.form == ImageForm::kGeneric && !p.plane_regions ? 0 : p.form == ImageForm::kF16Plane ? 1 : bf16_rows ? 2 : 3;
+  p.refusal = indexed && c.num_entities <= 0 ? Refusal::kIndexWithoutTable : indexed && !p.planes ? Refusal::kTableOffPlanes
+              : bf16_rows && !p.planes ? Refusal::kBf16OffPlanes : Refusal::kNone;
+  // The regions, sized by use as far as the configuration alone says it: tables (cfg.num_entities > 0, indexed in this call
+  // or not) M R floats of image planes; DRIN_PREC_BF16X3_IF16 the fp16 plane, M R / 2, and a scale per pair; else nothing (-3.4 GB at the headline)
+  p.plane_floats = p.plane_regions ? MD : 0;   // hi plane (M*D bf16) then lo plane
+  p.p_xi_floats = !p.plane_regions ? 0 : c.num_entities > 0 ? MR : if16 ? MR / 2 : 0;
+  p.xi_scale_floats = if16 ? (size_t)M : 0;
+  // split-K partials of the mention-sized exact-fp32 products (small batches: the call is a chain of ~25 launches)
+  // (the widest: q [2 B][D + R]; in split-bf16 precision at least tail_split_floor_floats(), so that a partly filled last round of
+  //  tiles of the larger products can split K over the idle CUs - gemm_bf16x3.hip)
+  p.splitk_floats = 2 * B <= (size_t)kSmallSplitkMaxRows ? small_splitk_floats(2 * B, (size_t)D + R) : 0;
+  if (p.plane_regions && p.splitk_floats < tail_split_floor_floats()) p.splitk_floats = tail_split_floor_floats();
+  // The side schedule: only where both kernels' four-phase contract holds (rows read in place on the planes' widths, at least
+  // DRIN_SIDE_MIN_TILES tiles) and S row tiles lie outside the product's tail split.
+  int wgs = DRIN_SIDE_WGS, permille = DRIN_SIDE_PERMILLE;
+#ifdef DRIN_SIDE_PROBE
+  wgs = g_probe_wgs, permille = g_probe_permille;
+#endif
+  const int64_t nx = cdiv(D, 256), row_tiles = cdiv(M, 256), tiles = row_tiles * nx;
+  // (192: below it the fp32-row product leaves the 256 x 256 kernel - launch_gemm_nt_bf16x3; the bf16-row one from 129 up)
+  const bool in_place = p.form == ImageForm::kSplitRows || p.form == ImageForm::kBf16Rows;
+  if (!in_place || wgs <= 0 || permille <= 0 || tiles < 192 || tiles < DRIN_SIDE_MIN_TILES || tiles > ((int64_t)1 << 28)) return p;
+  const int64_t whole_rows = gemm_p4_whole_tiles(tiles, R, p.splitk_floats > 0, p.splitk_floats) / nx;
+  int64_t S = (row_tiles * permille + 500) / 1000;
+  S = S < whole_rows ? S : whole_rows;
+  S = S < row_tiles - 1 ? S : row_tiles - 1;   // the plain launch behind the join keeps the last row tile (and the tail split)
+  if (S > 0) p.S = S, p.G = (int)(wgs < S * nx ? wgs : S * nx);
+  return p;
+}
+static int refuse(Refusal r, const drin_config* cfg) {
+  if (r == Refusal::kNone) return DRIN_OK;
+  if (r == Refusal::kIndexWithoutTable)
+    set_error("drin_forward_prepared: entity_index given but cfg.num_entities = %d", cfg->num_entities);
+  else if (r == Refusal::kTableOffPlanes)   // the fp32 contractions read the entity rows in place; with a table they need gathered copies
+    set_error("drin_forward_prepared: entity_index needs the split-bf16 precision (the stream kernel gathers the "
+              "GEMM operands as planes); gather on the caller side for DRIN_PREC_F32");
+  else
+    set_error("drin_forward_prepared: bf16 features need the split-bf16 precision (DRIN_PREC_BF16X3) and D, R multiples of 32");
+  return r == Refusal::kIndexWithoutTable ? DRIN_E_SHAPE : DRIN_E_UNSUPPORTED;
+}
+
 struct FusedLayout {  // workspace offsets in floats
   size_t span_mean, mimg, vm0, hmfu, q, e0m, e1m, xt, s_part, s_text, s_img, sig, tm, tm2, agg1, vm1, hm2, h_text, h_image,
       et1, s2_part, agg2, mt2, p_xt, p_xi, p_et1, xi_scale, splitk, splitk_floats, pair_splitk, pair_splitk_floats, total;
   int chunks;
-  void build(const drin_config& c) {
+  void build(const drin_config& c, const FoldedPlan& plan) {
     const size_t B = c.batch, N = c.num_candidates, D = c.embed_dim, R = c.image_dim, M = B * N;
     // a workgroup owns 16 consecutive candidates of one mention (4 per wave) - or, from 2 048 mentions up, where the mentions
     // alone fill the chip eight times over, up to 128 of them (WikiMEL: the whole list): one prologue of mention-side vectors
@@ -66,33 +174,43 @@ struct FusedLayout {  // workspace offsets in floats
     s2_part = A.take(B * chunks * 2 * D);
     agg2 = A.take(B * D);
     mt2 = A.take(B * D);
-    const bool planes = c.precision == DRIN_PREC_BF16X3 || c.precision == DRIN_PREC_BF16X3_ALL || c.precision == DRIN_PREC_BF16X3_IF16;
-    p_xt = A.take(planes ? M * D : 0);   // hi plane (M*D bf16) then lo plane
-    // image planes, sized by use: the table form (cfg.num_entities > 0: entity_index gathers rows, so the stream kernel
-    // writes them as (hi, lo) bf16 planes) M R floats; DRIN_PREC_BF16X3_IF16 the one fp16 plane, M R / 2; gathered split-bf16
-    // batches read the image rows in place: nothing (3.4 GB less workspace at the headline batch)
-    p_xi = A.take(!planes ? 0 : c.num_entities > 0 ? M * R : c.precision == DRIN_PREC_BF16X3_IF16 ? M * R / 2 : 0);
-    p_et1 = A.take(planes ? M * D : 0);
-    xi_scale = A.take(c.precision == DRIN_PREC_BF16X3_IF16 ? M : 0);   // per-pair power-of-two scale of the image row
-    // split-K partials of the mention-sized exact-fp32 products (small batches: the call is a chain of ~25 launches)
-    // (in split-bf16 precision at least tail_split_floor_floats(), so that a partly filled last round of tiles of the
-    //  larger products can split K over the idle CUs - gemm_bf16x3.hip)
-    // (the widest: q [2 B][D + R])
-    splitk_floats = 2 * B <= (size_t)kSmallSplitkMaxRows ? small_splitk_floats(2 * B, D + R) : 0;
-    if (planes && splitk_floats < tail_split_floor_floats()) splitk_floats = tail_split_floor_floats();
-    splitk = A.take(splitk_floats);
-    // ... and of the pair-sized split-bf16 products when the whole batch is less than half a round of 256 x 256 tiles
-    pair_splitk_floats = planes ? drin::pair_splitk_floats(M, D) : 0;
+    p_xt = A.take(plan.plane_floats);
+    p_xi = A.take(plan.p_xi_floats);
+    p_et1 = A.take(plan.plane_floats);
+    xi_scale = A.take(plan.xi_scale_floats);
+    splitk = A.take(splitk_floats = plan.splitk_floats);
+    // split-K partials of the pair-sized split-bf16 products when the whole batch is less than half a round of 256 x 256 tiles
+    pair_splitk_floats = plan.plane_regions ? drin::pair_splitk_floats(M, D) : 0;
     pair_splitk = A.take(pair_splitk_floats);
     total = A.total;
   }
 };
 
+// The regions with the floats the kernels index - of p_xi and xi_scale per form, not read off the plan's sizes - and, over both ways
+// `indexed` can fall, the plan against itself: form <-> passes, and a side schedule only on rows read in place, inside the row tiles.
 int fused_layout_selfcheck(const drin_config& c) {
   const size_t B = c.batch, M = B * c.num_candidates, D = c.embed_dim, R = c.image_dim;
+  const int64_t nx = cdiv((int64_t)D, 256), row_tiles = cdiv((int64_t)M, 256);
+  const bool bf16_rows = c.feature_dtype == DRIN_FEAT_BF16;
+  size_t xi = 0, scale = 0, planes = 0;
+  for (int indexed = 0; indexed < 2; ++indexed) {
+    const FoldedPlan p = folded_plan(c, indexed != 0);
+    if (p.refusal != Refusal::kNone) continue;
+    const bool in_place = p.form == ImageForm::kSplitRows || p.form == ImageForm::kBf16Rows;
+    static_assert((int)ImageForm::kF16Plane == 4, "by form, in ImageForm's order");   // p_xi: M R bf16 per plane the stream pass writes, M R halves (with M scales)
+    const int passes[] = {c.precision == DRIN_PREC_F32 ? 0 : 3, 3, 2, bf16_rows ? 2 : 3, 1};
+    const size_t need[] = {0, 0, 0, bf16_rows ? M * R / 2 : M * R, M * R / 2};
+    if (p.form == ImageForm::kF16Plane) scale = M;
+    if (p.passes != passes[(int)p.form] || p.S < 0 || (p.S > 0 ? !(in_place && p.S < row_tiles && p.G >= 1 && p.G <= p.S * nx) : p.G != 0)) {
+      set_error("selftest: FoldedPlan(indexed = %d): form %d with %d passes, side schedule {%lld, %d} of %lld row tiles", indexed, (int)p.form,
+                p.passes, (long long)p.S, p.G, (long long)row_tiles);
+      return DRIN_E_WORKSPACE;
+    }
+    xi = need[(int)p.form] > xi ? need[(int)p.form] : xi, planes |= p.planes;
+  }
   FusedLayout L;
-  L.build(c);
-  const size_t ch = (size_t)L.chunks, planes = c.precision != DRIN_PREC_F32;
+  L.build(c, folded_plan(c, false));
+  const size_t ch = (size_t)L.chunks;
   const Region ws[] = {
       {"span_mean", L.span_mean, B * D}, {"mimg", L.mimg, B * R}, {"vm0", L.vm0, 2 * B * D}, {"hmfu", L.hmfu, 4 * B * D},
       {"q", L.q, 2 * B * (D + R)}, {"e0m", L.e0m, 4 * M}, {"e1m", L.e1m, 4 * M}, {"xt", L.xt, c.entity_tokens > 0 ? M * D : 0},
@@ -100,8 +218,7 @@ int fused_layout_selfcheck(const drin_config& c) {
       {"sig", L.sig, 4 * B}, {"tm", L.tm, 2 * B * D}, {"tm2", L.tm2, 2 * B * D}, {"agg1", L.agg1, 2 * B * D}, {"vm1", L.vm1, 2 * B * D},
       {"hm2", L.hm2, 2 * B * D}, {"h_text", L.h_text, M * D}, {"h_image", L.h_image, M * D}, {"et1", L.et1, M * D},
       {"s2_part", L.s2_part, B * ch * 2 * D}, {"agg2", L.agg2, B * D}, {"mt2", L.mt2, B * D}, {"p_xt", L.p_xt, planes * M * D},
-      {"p_xi", L.p_xi, !planes ? 0 : c.num_entities > 0 ? M * R : c.precision == DRIN_PREC_BF16X3_IF16 ? M * R / 2 : 0},
-      {"p_et1", L.p_et1, planes * M * D}, {"xi_scale", L.xi_scale, c.precision == DRIN_PREC_BF16X3_IF16 ? M : 0},
+      {"p_xi", L.p_xi, xi}, {"p_et1", L.p_et1, planes * M * D}, {"xi_scale", L.xi_scale, scale},
       {"splitk", L.splitk, L.splitk_floats}, {"pair_splitk", L.pair_splitk, L.pair_splitk_floats}};
   DRIN_TRY(regions_hold("FusedLayout", ws, (int)(sizeof(ws) / sizeof(ws[0])), L.total));
   Prepared P;
@@ -113,74 +230,6 @@ int fused_layout_selfcheck(const drin_config& c) {
       {"p_wmi", P.p_wmi, D * R}, {"p_wcat1", P.p_wcat1, 2 * D * D}, {"p_ecat", P.p_ecat, D * (D + R)}, {"p_wet", P.p_wet, D * D},
       {"p_wei", P.p_wei, D * R}, {"p_wh1", P.p_wh1, D * D}, {"p_cimg_f16", P.p_cimg_f16, D * R / 2}, {"cimg_f16_scale", P.cimg_f16_scale, 2}};
   return regions_hold("Prepared", pr, (int)(sizeof(pr) / sizeof(pr[0])), P.total);
-}
-
-// The configuration part of the DRIN_PREC_BF16X3_IF16 gate (what is left - 16-byte alignment of workspace slots - holds by the
-// workspace contract): split-bf16 widths, per-pair fp32-stored rows, a list long enough to average the pass's rounding, the exact
-// widths the stream kernel's fp16 hand-over is instantiated for, at least half a round of 256 x 256 tiles.
-static bool if16_gate(const drin_config* c, bool indexed) {
-  const int64_t M = (int64_t)c->batch * c->num_candidates;
-  return c->precision == DRIN_PREC_BF16X3_IF16 && !indexed && c->feature_dtype == DRIN_FEAT_F32 &&
-         c->num_candidates >= kMixedMinCandidates && c->embed_dim == 768 && c->image_dim == 2048 &&
-         cdiv(M, 256) * cdiv(c->embed_dim, 256) >= 128;
-}
-
-// The schedule of the gathered-row image contraction x_i C_i^T (forward_prepared_on_stream): row tiles [0, S) as G persistent
-// workgroups on the library's side stream, under the entity stream pass, the rest at full grid behind it.  {0, 0}: one launch on
-// the caller's stream, as under capture.  The contraction reads the batch's image rows in place and the prepared weight planes -
-// nothing the stream pass writes - and a 128 KiB-LDS GEMM workgroup shares no CU with a stream workgroup, so G resident workgroups
-// take G CUs from a pass that does not need all 256 of them.  Only where both kernels' four-phase contract holds (gathered rows,
-// split-bf16 widths, at least kSideMinTiles tiles, the three- or two-pass contraction) and S row tiles lie outside the product's
-// tail split.  G, f and the least tile count: profiles/image_overlap_ab.txt - G in {32, 48, 64, 96} x f in 0.1 .. 0.9 on one resident
-// headline batch: the side part may outlast the stream pass (it goes on under the layer-1 mention chain and x_t C_t^T), so the step
-// falls with f until the side part ends at the join: G = 64, f = 0.9 (side kernel 11.3 ms, join 11.3 ms after the fork; stream pass
-// 8.4 -> 9.6 ms on its 192 CUs; headline 16.00 -> 14.60 ms over fresh processes).  Fewer workgroups cannot finish in time, 96 cost the
-// stream pass and x_t C_t^T more than they save.  Below ~1 200 tiles (B = 1 024 at N = 101) the gain sinks into the noise (B = 512: -3.5 %
-// fp32 rows, -1 .. -3 % bf16 rows), so smaller calls keep the one launch.  (The three macros exist for probe builds of that file's grid.)
-#ifndef DRIN_SIDE_WGS
-#define DRIN_SIDE_WGS 64
-#endif
-#ifndef DRIN_SIDE_PERMILLE
-#define DRIN_SIDE_PERMILLE 900
-#endif
-#ifndef DRIN_SIDE_MIN_TILES
-#define DRIN_SIDE_MIN_TILES 1200
-#endif
-constexpr int kSideWgs = DRIN_SIDE_WGS;             // G
-constexpr int kSidePermille = DRIN_SIDE_PERMILLE;   // f, in thousandths of the row tiles
-constexpr int64_t kSideMinTiles = DRIN_SIDE_MIN_TILES;
-#ifdef DRIN_SIDE_PROBE   // probe builds only (tools/probes/image_overlap_ab.py): G and f set between calls of one process
-static int g_probe_wgs = kSideWgs, g_probe_permille = kSidePermille;
-extern "C" __attribute__((visibility("default"))) void drin_probe_side_plan(int wgs, int permille) { g_probe_wgs = wgs, g_probe_permille = permille; }
-#endif
-struct SidePlan {
-  int64_t S = 0;   // row tiles on the side stream
-  int G = 0;       // persistent workgroups that walk them
-};
-static SidePlan image_side_plan(const drin_config* c, bool indexed, bool capturing) {
-  SidePlan plan;
-  int wgs = kSideWgs, permille = kSidePermille;
-#ifdef DRIN_SIDE_PROBE
-  wgs = g_probe_wgs, permille = g_probe_permille;
-#endif
-  const bool split = c->precision == DRIN_PREC_BF16X3 || c->precision == DRIN_PREC_BF16X3_ALL || c->precision == DRIN_PREC_BF16X3_IF16;
-  if (capturing || indexed || !split || if16_gate(c, indexed) || wgs <= 0 || permille <= 0) return plan;
-  const int D = c->embed_dim, R = c->image_dim;
-  if ((D % 32) || (R % 32) || c->batch <= 0) return plan;
-  const int64_t M = (int64_t)c->batch * c->num_candidates;
-  const int64_t nx = cdiv(D, 256), row_tiles = cdiv(M, 256), tiles = row_tiles * nx;
-  // (192: below it the fp32-row product leaves the 256 x 256 kernel - launch_gemm_nt_bf16x3; the bf16-row one from 129 up)
-  if (tiles < 192 || tiles < kSideMinTiles || tiles > ((int64_t)1 << 28)) return plan;
-  FusedLayout L;
-  L.build(*c);
-  const int64_t whole_rows = gemm_p4_whole_tiles(tiles, R, L.splitk_floats > 0, L.splitk_floats) / nx;
-  int64_t S = (row_tiles * permille + 500) / 1000;
-  S = S < whole_rows ? S : whole_rows;
-  S = S < row_tiles - 1 ? S : row_tiles - 1;   // the plain launch behind the join keeps the last row tile (and the tail split)
-  if (S <= 0) return plan;
-  plan.S = S;
-  plan.G = (int)(wgs < S * nx ? wgs : S * nx);
-  return plan;
 }
 
 // The caller's stream joins the side stream when the call leaves, whatever way it leaves
@@ -370,9 +419,6 @@ int drin_prepare(const drin_config* cfg, const drin_params* params, void* prepar
 
 namespace drin {
 
-// split-bf16 widths of every product of the folded paths (DRIN_PREC_BF16X3_IF16 differs in the image contraction's passes only)
-static int folded_precision(const drin_config* c) { return c->precision == DRIN_PREC_BF16X3_IF16 ? (int)DRIN_PREC_BF16X3 : c->precision; }
-
 int run_folded_head(const drin_config* cfg, const drin_batch* b, const drin_params* params, const float* pb, const Prepared& P,
                     bool weight_planes, float* span_mean, float* mimg, float* vm0, float* hmfu, GemmScratch sk, hipStream_t st,
                     const drin_mention_head* head) {
@@ -456,16 +502,13 @@ int run_folded_tail(const drin_config* cfg, const drin_params* params, const flo
 // The whole forward on the caller's stream: the one pass over the entity bytes (HBM-bound), then the contractions and row kernels
 // behind it (MFMA-bound).  (Running the two halves of consecutive mention chunks side by side - two streams, forced co-residency,
 // disjoint CU masks - was built in round 3 and measured slower every time; removed in round 5: profiles/r3_pipeline_probe.txt.)
-// One product leaves the caller's stream where image_side_plan engages: the first S row tiles of x_i C_i^T, which depend on nothing
-// the call computes, run as a few persistent workgroups on the library's side stream from the START of the call (fork event first:
-// the previous call's readers of h_image are in front of it; the workgroups are resident before the stream pass is dispatched) and
-// the caller's stream waits for them before it launches the other row tiles at full grid.  Same kernel code and the same tail split
-// per tile as the one launch, so the scores are the same bits.  A captured call (hipStreamIsCapturing) keeps the one launch: no
-// parallel branches in a graph.  Measured: profiles/image_overlap_ab.txt.
+// One product leaves the caller's stream where the plan has a side schedule: the first S row tiles of x_i C_i^T, which depend on nothing
+// the call computes, run on the library's side stream from the START of the call (fork event first: the previous call's readers of
+// h_image are in front of it; the workgroups are resident before the stream pass is dispatched) and the caller's stream waits for them
+// before it launches the other row tiles.  Same kernel code and the same tail split per tile as the one launch: the same bits.
 static int forward_prepared_on_stream(const drin_config* cfg, const drin_batch* b, const drin_params* params, const void* prepared,
-                                      void* workspace, float* scores, hipStream_t st, const drin_mention_head* head) {
-  FusedLayout L;
-  L.build(*cfg);
+                                      void* workspace, float* scores, hipStream_t st, const drin_mention_head* head, FoldedPlan plan,
+                                      const FusedLayout& L) {
   Prepared P;
   P.build(*cfg);
   float* ws = (float*)workspace;
@@ -473,55 +516,24 @@ static int forward_prepared_on_stream(const drin_config* cfg, const drin_batch* 
   const int B = cfg->batch, N = cfg->num_candidates, D = cfg->embed_dim, R = cfg->image_dim;
   const int64_t M = (int64_t)B * N;
   if (B == 0) return DRIN_OK;
-  const int prec = folded_precision(cfg);
-  const bool dyn = cfg->dynamic_edges != 0;
-  const bool tokens = cfg->entity_tokens > 0;
-  // split-bf16 precision: the producers write bf16 hi / lo planes and the three pair-sized contractions
-  // run on the LDS-DMA kernel of gemm_x3_planes.hip
-  const bool planes = (prec == DRIN_PREC_BF16X3 || prec == DRIN_PREC_BF16X3_ALL) && (D % 32 == 0) && (R % 32 == 0);
-  const bool indexed = b->entity_index != nullptr;
-  // The image rows are read in place by their contraction (fp32, split on the fly): writing 8 KB/pair of
-  // planes from the stream kernel costs it more (measured twice on one box: +1.0 ms at B = 4096) than the LDS-DMA
-  // kernel gains on that GEMM (-0.35 ms).  Only the table form, which has to gather the rows anyway, writes them.
-  const bool xi_planes = planes && indexed;
-  // DRIN_PREC_BF16X3_IF16: x_i C_i^T in ONE pass of the fp16 matrix instruction on single planes.  k_entity_stream, which holds every
-  // image row in registers anyway, writes it as fp16(x / 2^ceil(log2 max|x|)) - 4 KB per pair - with the scale beside it; the folded
-  // weight is one fp16 plane under one scale (drin_prepare); the all-DMA four-phase kernel multiplies both back in its epilogue.
-  // For gathered (per-pair) fp32-stored rows at the exact widths in calls of at least half a round of 256 x 256 tiles; everything
-  // else runs the three passes, bit for bit.  Measured (profiles/r5_*if16*): the contraction 3.4 -> 1.29 ms, the stream kernel +0.70 ms
-  // for the 1.69 GB it now writes (HBM writes inside a read-bound pass cost ~2.5 x their bytes) - the headline batch 15.8 -> 14.6 ms,
-  // what round 4's register-staged fp32-A kernel reached too (1.80 ms, nothing written).  bf16-STORED rows do NOT take the pass: their
-  // two-pass contraction reads them in place (2.07 ms); the plane costs their stream kernel +0.88 ms for -0.78 ms: measured, a wash.
-  // (the candidate-count gate: with freshly initialised weights the fp16 pass costs 8e-6 at N = 11, but once the weights are
-  //  TRAINED the vertex -> score map steepens and 11 candidates average too little - 1.2e-4 after 200 Adam steps, outside the bar;
-  //  at N = 101 the same weights give 2e-5: profiles/r4_precision_on_trained_weights.txt)
-  const bool if16 = if16_gate(cfg, indexed) && gemm_f16_planes_fits(ws + L.p_xi, R, pb + P.p_cimg_f16, R, ws + L.h_image, D, M, D, R);
-  hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(st, &capture) != hipSuccess) {
-    (void)hipGetLastError();
-    capture = hipStreamCaptureStatusActive;   // a stream that cannot say: the serial order
-  }
-  SidePlan side = image_side_plan(cfg, indexed, capture != hipStreamCaptureStatusNone);
-  if (!aligned16(b->entity_image) || !aligned16(ws + L.h_image) || !b->entity_image) side = SidePlan();   // (the plain launch reports it)
   if (b->entity_text_cls) {
     set_error("drin_forward_prepared: entity_text_cls (text pooled ahead of time) is a form of the training entry points");
     return DRIN_E_UNSUPPORTED;
   }
-  if (indexed && cfg->num_entities <= 0) {
-    set_error("drin_forward_prepared: entity_index given but cfg.num_entities = %d", cfg->num_entities);
-    return DRIN_E_SHAPE;
+  DRIN_TRY(refuse(plan.refusal, cfg));
+  // What only the run knows, and all of it: each fact demotes the plan, nothing below asks again.  The fp16 kernel's own fit failing:
+  // three passes.  A stream under capture (no parallel branches in a graph) or one that cannot say, misaligned image rows or h_image,
+  // no rows at all (the plain launch reports those): the one launch.
+  if (plan.form == ImageForm::kF16Plane && !gemm_f16_planes_fits(ws + L.p_xi, R, pb + P.p_cimg_f16, R, ws + L.h_image, D, M, D, R))
+    plan.form = ImageForm::kSplitRows;
+  hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
+  if (plan.S > 0 && hipStreamIsCapturing(st, &capture) != hipSuccess) {
+    (void)hipGetLastError();
+    capture = hipStreamCaptureStatusActive;
   }
-  if (indexed && !planes) {
-    // the fp32 contractions read the entity rows in place; with a table they need gathered copies
-    set_error("drin_forward_prepared: entity_index needs the split-bf16 precision (the stream kernel gathers the "
-              "GEMM operands as planes); gather on the caller side for DRIN_PREC_F32");
-    return DRIN_E_UNSUPPORTED;
-  }
-  const bool bf16_feat = cfg->feature_dtype == DRIN_FEAT_BF16;
-  if (bf16_feat && !planes) {
-    set_error("drin_forward_prepared: bf16 features need the split-bf16 precision (DRIN_PREC_BF16X3) and D, R multiples of 32");
-    return DRIN_E_UNSUPPORTED;
-  }
+  if (capture != hipStreamCaptureStatusNone || !aligned16(b->entity_image) || !aligned16(ws + L.h_image) || !b->entity_image) plan.S = plan.G = 0;
+  const int prec = folded_precision(cfg);
+  const bool dyn = cfg->dynamic_edges != 0, tokens = cfg->entity_tokens > 0, planes = plan.planes, bf16_feat = cfg->feature_dtype == DRIN_FEAT_BF16;
   __bf16* xt_hi = reinterpret_cast<__bf16*>(ws + L.p_xt);
   __bf16* xi_hi = reinterpret_cast<__bf16*>(ws + L.p_xi);
   __bf16* e1_hi = reinterpret_cast<__bf16*>(ws + L.p_et1);
@@ -534,8 +546,6 @@ static int forward_prepared_on_stream(const drin_config* cfg, const drin_batch* 
   const GemmScratch msk = scratch_at(ws, L.splitk, L.splitk_floats);
   float* vm0 = ws + L.vm0;
   float* hmfu = ws + L.hmfu;
-  // pooled entity text stored as bf16 is exact in its hi plane: no lo plane, two MFMAs per tile pair
-  const bool xt_exact = bf16_feat && !tokens;
   // split-K scratch of the pair-sized products: the whole-product split when the batch is a few tiles, else the tail-split scratch
   const GemmScratch psk = L.pair_splitk_floats ? GemmScratch{ws + L.pair_splitk, L.pair_splitk_floats} : msk;
   // x_i C_i^T on rows read in place (fp32: split on the fly; bf16: the rows are the one plane), whole or a slice of its row tiles
@@ -543,17 +553,18 @@ static int forward_prepared_on_stream(const drin_config* cfg, const drin_batch* 
   auto image_rows_product = [&](hipStream_t on, RowTiles rows) -> int {
     if (bf16_feat)
       return launch_gemm_x3_planes(b->entity_image, nullptr, R, xi_ci.w_hi, xi_ci.w_lo, R, nullptr, ws + L.h_image, D, M, D, R, on, psk, rows);
+    if (plan.S == 0) return launch_gemm_nt_bf16x3(xi_ci, on, psk);   // whole: the launcher chooses the kernel (a small product leaves the 256 x 256 one)
     return launch_gemm_nt_bf16x3_p4(xi_ci, on, aligned16(psk.p) ? psk : GemmScratch{}, rows);
   };
   SideJoin side_join;
-  if (side.S > 0) {
+  if (plan.S > 0) {
     SideLane* lane = nullptr;
     DRIN_TRY(side_lane(&lane));
     std::lock_guard<std::mutex> order(lane->order);
     hipError_t e = hipEventRecord(lane->fork, st);
     if (e == hipSuccess) e = hipStreamWaitEvent(lane->stream, lane->fork, 0);
     if (e != hipSuccess) return hip_fail(e, "fork to the side stream");
-    const int rc = image_rows_product(lane->stream, RowTiles{0, side.S, side.G});
+    const int rc = image_rows_product(lane->stream, RowTiles{0, plan.S, plan.G});
     e = hipEventRecord(lane->join, lane->stream);
     side_join.lane = lane, side_join.st = st;
     if (rc != DRIN_OK) return rc;
@@ -586,17 +597,13 @@ static int forward_prepared_on_stream(const drin_config* cfg, const drin_batch* 
   sa.ldq = D + R;  // q row = [q_text (D) | q_image (R)]
   sa.k_t = pb + P.k_t;
   sa.k_i = pb + P.k_i;
-  sa.xt_out = planes ? nullptr : ws + L.xt;
-  if (planes) {
-    sa.xt_hi = xt_hi;
-    sa.xt_lo = xt_exact ? nullptr : xt_hi + MD;
-    if (xi_planes) {
-      sa.xi_hi = xi_hi;
-      sa.xi_lo = bf16_feat ? nullptr : xi_hi + MR;  // bf16 image rows are their own hi plane: nothing left for lo
-    }
+  if (planes) sa.xt_hi = xt_hi, sa.xt_lo = plan.xt_lo ? xt_hi + MD : nullptr;
+  else sa.xt_out = ws + L.xt;
+  switch (plan.form) {   // the image outputs: only the forms whose A operand comes from this pass have any
+    case ImageForm::kStreamPlanes: sa.xi_hi = xi_hi, sa.xi_lo = bf16_feat ? nullptr : xi_hi + MR; break;   // (bf16 rows are their own hi plane)
+    case ImageForm::kF16Plane: sa.xi_scale = ws + L.xi_scale, sa.xi_f16 = xi_hi; break;
+    default: break;
   }
-  sa.xi_scale = if16 ? ws + L.xi_scale : nullptr;
-  sa.xi_f16 = if16 ? static_cast<void*>(xi_hi) : nullptr;
   sa.e0m = ws + L.e0m;
   sa.e1m = ws + L.e1m;
   sa.s_part = ws + L.s_part;
@@ -619,28 +626,27 @@ static int forward_prepared_on_stream(const drin_config* cfg, const drin_batch* 
   DRIN_TRY(launch_gemm_nt(NtProduct{{ws + L.agg1, D}, {L1.w_h, D}, L1.b_h, vm1, D, 2 * (int64_t)B, D, D}.with_planes(wp(P.p_wh1)), prec, st, msk));
   DRIN_TRY(run_folded_mention_finish(cfg, params, pb, P, planes, vm1, ws + L.hm2, msk, st));
   // (5) the two pair-sized layer-1 contractions on the folded weights
-  if (planes) {
-    const __bf16* ct = reinterpret_cast<const __bf16*>(pb + P.p_ctxt);
-    const __bf16* ci = reinterpret_cast<const __bf16*>(pb + P.p_cimg);
-    DRIN_TRY(launch_gemm_x3_planes(xt_hi, xt_exact ? nullptr : xt_hi + MD, D, ct, ct + (size_t)D * D, D, nullptr, ws + L.h_text, D, M, D,
-                                   D, st, psk));
-    if (if16)        // one fp16 pass on the plane the stream kernel wrote
+  const __bf16* ct = reinterpret_cast<const __bf16*>(pb + P.p_ctxt);
+  if (planes)
+    DRIN_TRY(launch_gemm_x3_planes(xt_hi, sa.xt_lo, D, ct, ct + (size_t)D * D, D, nullptr, ws + L.h_text, D, M, D, D, st, psk));
+  else
+    DRIN_TRY(launch_gemm_nt({{tokens ? ws + L.xt : (const float*)b->entity_text, D}, {pb + P.c_txt, D}, nullptr, ws + L.h_text, D, M, D, D}, prec, st));
+  switch (plan.form) {
+    case ImageForm::kGeneric:
+      DRIN_TRY(launch_gemm_nt({{(const float*)b->entity_image, R}, {pb + P.c_img, R}, nullptr, ws + L.h_image, D, M, D, R}, prec, st));
+      break;
+    case ImageForm::kF16Plane:   // on the plane the stream kernel wrote
       DRIN_TRY(launch_gemm_f16_planes(xi_hi, R, pb + P.p_cimg_f16, R, ws + L.xi_scale, pb + P.cimg_f16_scale, ws + L.h_image, D, M, D, R,
                                       st, psk));
-    else if (xi_planes)
-      DRIN_TRY(launch_gemm_x3_planes(xi_hi, bf16_feat ? nullptr : xi_hi + MR, R, ci, ci + (size_t)D * R, R, nullptr, ws + L.h_image, D, M,
-                                     D, R, st, psk));
-    else if (side.S > 0) {   // the row tiles the side stream did not take, once it is done with its own
+      break;
+    case ImageForm::kStreamPlanes:
+      DRIN_TRY(launch_gemm_x3_planes(xi_hi, sa.xi_lo, R, xi_ci.w_hi, xi_ci.w_lo, R, nullptr, ws + L.h_image, D, M, D, R, st, psk));
+      break;
+    case ImageForm::kBf16Rows:
+    case ImageForm::kSplitRows:   // whole, or the row tiles the side stream did not take, once it is done with its own
       DRIN_TRY(side_join.join());
-      DRIN_TRY(image_rows_product(st, RowTiles{side.S, -1, 0}));
-    } else if (bf16_feat)  // the bf16 image rows are read in place as the (only) plane of the A operand
-      DRIN_TRY(launch_gemm_x3_planes(b->entity_image, nullptr, R, ci, ci + (size_t)D * R, R, nullptr, ws + L.h_image, D, M, D, R, st, psk));
-    else
-      DRIN_TRY(launch_gemm_nt_bf16x3(xi_ci, st, psk));
-  } else {
-    const float* x_t = tokens ? ws + L.xt : b->entity_text;
-    DRIN_TRY(launch_gemm_nt({{x_t, D}, {pb + P.c_txt, D}, nullptr, ws + L.h_text, D, M, D, D}, prec, st));
-    DRIN_TRY(launch_gemm_nt({{(const float*)b->entity_image, R}, {pb + P.c_img, R}, nullptr, ws + L.h_image, D, M, D, R}, prec, st));
+      DRIN_TRY(image_rows_product(st, RowTiles{plan.S, -1, 0}));
+      break;
   }
   // The two pair kernels walk the same candidate chunks as the stream kernel (FusedLayout::chunks: whole mentions from 2 048
   // mentions up - their share of that change: row kernels 1.385 -> 1.27 ms at 4 096 mentions; 64 mentions with whole-mention
@@ -658,11 +664,8 @@ static int forward_prepared_on_stream(const drin_config* cfg, const drin_batch* 
   pa.beta = L1.ln_bias;
   pa.e0m = ws + L.e0m;
   pa.e1m = ws + L.e1m;
-  pa.et1 = planes ? nullptr : ws + L.et1;
-  if (planes) {
-    pa.et1_hi = e1_hi;
-    pa.et1_lo = e1_hi + MD;
-  }
+  if (planes) pa.et1_hi = e1_hi, pa.et1_lo = e1_hi + MD;
+  else pa.et1 = ws + L.et1;
   pa.s2_part = ws + L.s2_part;
   pa.chunks = L.chunks;
   DRIN_TRY(launch_pair_layer1(pa, st));
@@ -679,20 +682,18 @@ int32_t drin_workgroups_per_mention(const drin_config* cfg, int32_t cached) {
   if (validate_config(cfg) != DRIN_OK || fused_supported(cfg) != DRIN_OK) return 0;
   if (cached) return cached_chunks_per_mention(*cfg);
   FusedLayout L;
-  L.build(*cfg);
+  L.build(*cfg, folded_plan(*cfg, false));
   return L.chunks;
 }
 
 int32_t drin_image_contraction_side_tiles(const drin_config* cfg, int32_t indexed) {
   if (validate_config(cfg) != DRIN_OK || fused_supported(cfg) != DRIN_OK) return 0;
-  return (int32_t)image_side_plan(cfg, indexed != 0, false).S;
+  return (int32_t)folded_plan(*cfg, indexed != 0).S;
 }
 
 int32_t drin_image_contraction_passes(const drin_config* cfg, int32_t indexed) {
   if (validate_config(cfg) != DRIN_OK || fused_supported(cfg) != DRIN_OK) return 0;
-  if (cfg->precision == DRIN_PREC_F32) return 0;
-  if (if16_gate(cfg, indexed != 0)) return 1;
-  return cfg->feature_dtype == DRIN_FEAT_BF16 ? 2 : 3;
+  return folded_plan(*cfg, indexed != 0).passes;
 }
 
 int drin_index_status(int32_t* index_status, void* stream) {
@@ -717,7 +718,7 @@ int drin_index_status(int32_t* index_status, void* stream) {
 size_t drin_fused_workspace_bytes(const drin_config* cfg) {
   if (validate_config(cfg) != DRIN_OK || fused_supported(cfg) != DRIN_OK) return 0;
   FusedLayout L;
-  L.build(*cfg);
+  L.build(*cfg, folded_plan(*cfg, false));
   return L.total * sizeof(float);
 }
 
@@ -744,14 +745,15 @@ int drin_forward_prepared_head(const drin_config* cfg, const drin_batch* b, cons
     set_error("drin_forward_prepared: NULL argument");
     return DRIN_E_NULL;
   }
+  const FoldedPlan plan = folded_plan(*cfg, b->entity_index != nullptr);
   FusedLayout L;
-  L.build(*cfg);
+  L.build(*cfg, plan);
   if (workspace_bytes < L.total * sizeof(float) || !aligned16(workspace)) {
     set_error("drin_forward_prepared: workspace has %zu bytes (needs %zu) or is not 16-byte aligned", workspace_bytes,
               L.total * sizeof(float));
     return DRIN_E_WORKSPACE;
   }
-  return forward_prepared_on_stream(cfg, b, params, prepared, workspace, scores, (hipStream_t)stream, head);
+  return forward_prepared_on_stream(cfg, b, params, prepared, workspace, scores, (hipStream_t)stream, head, plan, L);
 }
 
 }  // extern "C"

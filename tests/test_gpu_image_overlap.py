@@ -1,4 +1,4 @@
-"""The concurrent schedule of the gathered-row image contraction (fused_forward.hip: image_side_plan): an eager
+"""The concurrent schedule of the gathered-row image contraction (fused_forward.hip: the side schedule of folded_plan): an eager
 `drin_forward_prepared` call runs the first row tiles of x_i C_i^T as persistent workgroups on the library's side stream, under
 the entity stream pass, and the rest at full grid behind it; a call under stream capture keeps the one launch.  Every tile is
 computed by the same code with the same K split either way, so the scores must be THE SAME BITS: `torch.equal`, no tolerance."""

@@ -1,4 +1,4 @@
-"""IN-PROCESS grid over the side schedule of x_i C_i^T (fused_forward.hip: image_side_plan) on ONE resident batch: G persistent
+"""IN-PROCESS grid over the side schedule of x_i C_i^T (fused_forward.hip: folded_plan) on ONE resident batch: G persistent
 workgroups take the first f of the row tiles on the library's side stream, under the entity stream pass.  Needs a PROBE build of
 the library, whose plan is set between calls (the shipped library has constants and no setter):
 

@@ -293,6 +293,12 @@ EXPORTS = {
     "drin_table_topk_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int64]),
     "drin_table_topk": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32,
                                   C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # DRIN behind a first stage (csrc/cross_edges.hip, csrc/table_topk.hip):
+    # (mention_clip_image, mention_clip_text, table_clip_text, table_clip_image, index, num_entities, batch, num_candidates, width,
+    #  scale, eps, miet, mtei, index_status, stream), (scores, rows, batch, n, k, out_scores, out_rows, out_slots, stream)
+    "drin_cross_modal_edges": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
+                                         C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "drin_rank_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "drin_ghmfc_mention_forward_workspace_bytes": (C.c_size_t, [C.POINTER(DrinGhmfcConfigC)]),
     "drin_ghmfc_mention_forward": (C.c_int, [C.POINTER(DrinGhmfcConfigC), C.POINTER(DrinGhmfcBatchC), C.POINTER(DrinGhmfcParamsC), C.c_void_p,
                                              C.c_size_t, C.c_void_p, C.c_void_p]),

@@ -8,7 +8,9 @@
 //   k_topk_merge      per mention: the running list and the slice lists -> the new running list of kp (key, row), sorted
 //   k_topk_finish     per mention: sort kp (score, row) by the contract, write the first k
 //   k_pad_rows        x [B, D] -> [round4(B), D], zero rows behind
-// and the entry points drin_row_inv_norms, drin_topk_update, drin_table_topk(_workspace_bytes).  The block of dot products is
+//   k_rank_rows       per mention: the first k of n caller-given (score, row) pairs by the contract, with the input column of each
+//                     (drin_rank_rows: the rerank behind a second-stage scoring)
+// and the entry points drin_row_inv_norms, drin_topk_update, drin_table_topk(_workspace_bytes), drin_rank_rows.  The block of dot products is
 // ENTITY-major, as the product y[Ec, Bp] = rows_chunk x^T leaves it: element (mention b, column c) at block[c * ld + b].
 // No atomics, no scratch memory; a workgroup of the three selection kernels is ONE wave, so its barriers order that wave's LDS
 // traffic and wait for nobody.
@@ -261,6 +263,48 @@ __global__ void __launch_bounds__(64) k_topk_finish(const float* __restrict__ ke
   }
 }
 
+// One mention: n (score, row) pairs of a caller's list - a row may be named twice - sorted by the contract with one more rule,
+// between equal scores on equal rows the lower input column (slot) first, so the order is total on any input.  A bitonic sort
+// over P = the power of two >= n entries of (order key, slot, row) in LDS; the P - n padding entries carry key 0 - below every
+// score's key - and rank last.  The first k are written: scores canonical (key_of_order), rows, and the slots when asked for.
+constexpr int kMaxRankRows = 4096;   // 16 bytes per entry: 64 KB of LDS at most
+__device__ __forceinline__ bool ranks_before3(uint32_t ka, int64_t ra, uint32_t sa, uint32_t kb, int64_t rb, uint32_t sb) {
+  return ka > kb || (ka == kb && (ra < rb || (ra == rb && sa < sb)));
+}
+__global__ void __launch_bounds__(256) k_rank_rows(const float* __restrict__ scores, const int64_t* __restrict__ rows, int n, int P, int k,
+                                                   float* __restrict__ out_scores, int64_t* __restrict__ out_rows,
+                                                   int32_t* __restrict__ out_slots) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char rank_lds[];
+  int64_t* sr = reinterpret_cast<int64_t*>(rank_lds);          // [P]
+  uint32_t* sk = reinterpret_cast<uint32_t*>(sr + P);          // [P]
+  uint32_t* ss = sk + P;                                       // [P]
+  const int tid = threadIdx.x;
+  const int64_t b = blockIdx.x;
+  for (int i = tid; i < P; i += 256) {
+    const bool real = i < n;
+    sk[i] = real ? order_key(scores[b * n + i]) : 0u;
+    sr[i] = real ? rows[b * n + i] : kNoRow;
+    ss[i] = (uint32_t)i;
+  }
+  __syncthreads();
+  for (int k2 = 2; k2 <= P; k2 <<= 1)
+    for (int j = k2 >> 1; j > 0; j >>= 1) {
+      for (int t = tid; t < (P >> 1); t += 256) {
+        const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), p = i | j;
+        const uint32_t ki = sk[i], kq = sk[p], si = ss[i], sq = ss[p];
+        const int64_t ri = sr[i], rq = sr[p];
+        const bool swap = ((i & k2) == 0) ? ranks_before3(kq, rq, sq, ki, ri, si) : ranks_before3(ki, ri, si, kq, rq, sq);
+        if (swap) sk[i] = kq, sr[i] = rq, ss[i] = sq, sk[p] = ki, sr[p] = ri, ss[p] = si;
+      }
+      __syncthreads();
+    }
+  for (int i = tid; i < k; i += 256) {   // k <= n: never a padding entry
+    out_scores[b * k + i] = key_of_order(sk[i]);
+    out_rows[b * k + i] = sr[i];
+    if (out_slots != nullptr) out_slots[b * k + i] = (int32_t)ss[i];
+  }
+}
+
 size_t topk_scratch_bytes(int64_t batch, int64_t cols, int kp) { return (size_t)cdiv(cols, kSlice) * (size_t)batch * kp * sizeof(uint64_t); }
 int64_t slices_of(int64_t cols) { return cdiv(cols, kSlice); }
 
@@ -281,6 +325,18 @@ int launch_topk_update(const float* block, int64_t ld, int batch, int64_t cols, 
 int launch_topk_finish(const float* keys, const int64_t* rows, int batch, int kp, int k, float* out_keys, int64_t* out_rows, hipStream_t st) {
   return timed(DRIN_KC_EDGE, st, "k_topk_finish", [&] {
     hipLaunchKernelGGL(k_topk_finish, dim3((unsigned)batch), dim3(64), 0, st, keys, rows, kp, k, out_keys, out_rows);
+  });
+}
+
+int launch_rank_rows(const float* scores, const int64_t* rows, int batch, int n, int k, float* out_scores, int64_t* out_rows,
+                     int32_t* out_slots, hipStream_t st) {
+  int P = 1;
+  while (P < n) P <<= 1;
+  const int lds = P * 16;
+  static DynLdsOptIn opt_in;
+  DRIN_TRY(ensure_dynamic_lds(opt_in, reinterpret_cast<const void*>(k_rank_rows), kMaxRankRows * 16, "hipFuncSetAttribute(rank_rows)"));
+  return timed(DRIN_KC_EDGE, st, "k_rank_rows", [&] {
+    hipLaunchKernelGGL(k_rank_rows, dim3((unsigned)batch), dim3(256), lds, st, scores, rows, n, P, k, out_scores, out_rows, out_slots);
   });
 }
 
@@ -502,4 +558,28 @@ int drin_table_topk(const float* x, const float* rows, const float* row_inv_norm
   // silently and stays last), ordered by the contract
   DRIN_TRY(launch_cosine_gather(x, rows, list, num_entities, scores, B, kp, D, cosine_eps, nullptr, 0, st));
   return launch_topk_finish(scores, list, B, kp, k, out_scores, out_rows, st);
+}
+
+int drin_rank_rows(const float* scores, const int64_t* rows, int32_t batch, int32_t n, int32_t k, float* out_scores, int64_t* out_rows,
+                   int32_t* out_slots, void* stream) {
+  const char* who = "drin_rank_rows";
+  if (!scores || !rows || !out_scores || !out_rows) {
+    set_error("%s: %s is NULL", who, !scores ? "scores" : !rows ? "rows" : !out_scores ? "out_scores" : "out_rows");
+    return DRIN_E_NULL;
+  }
+  if ((reinterpret_cast<uintptr_t>(scores) & 3u) != 0 || (reinterpret_cast<uintptr_t>(out_scores) & 3u) != 0 ||
+      (reinterpret_cast<uintptr_t>(out_slots) & 3u) != 0 || (reinterpret_cast<uintptr_t>(rows) & 7u) != 0 ||
+      (reinterpret_cast<uintptr_t>(out_rows) & 7u) != 0) {
+    set_error("%s: scores, out_scores and out_slots must be 4-byte, rows and out_rows 8-byte aligned", who);
+    return DRIN_E_ALIGN;
+  }
+  DRIN_TRY(check_count(who, "batch", batch, 1, kMaxGridY));
+  DRIN_TRY(check_count(who, "n", n, 1, kMaxRankRows));
+  DRIN_TRY(check_count(who, "k", k, 1, kMaxRankRows));
+  if (k > n) {
+    set_error("%s: k = %d exceeds n = %d", who, k, n);
+    return DRIN_E_SHAPE;
+  }
+  DRIN_BIND_DEVICE(stream, out_scores, who);
+  return launch_rank_rows(scores, rows, batch, n, k, out_scores, out_rows, out_slots, (hipStream_t)stream);
 }

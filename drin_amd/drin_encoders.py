@@ -183,6 +183,9 @@ class EncoderModel(Model):
         raise NotImplementedError("Model.attribute (gradient x input attribution) under a transformer / none mention encoder is out of "
                                   "scope of DESIGN.md section 31: the linear mention encoder only")
 
+    def link(self, *args, **kwargs):
+        raise NotImplementedError(f"Model.link (table-form batches: IndexedBatch / EntityTable behind a first stage) {NOT_BUILT}")
+
     # ---- the forward -----------------------------------------------------------------------------------------------------
     def forward(self, batch) -> torch.Tensor:
         if isinstance(batch, IndexedBatch):

@@ -148,6 +148,27 @@ class EntityTable:
         self._cache: Optional[torch.Tensor] = None
         self._cache_key = None
         self._pooled = None
+        # stored CLIP embeddings [E, C] of the entities (set_clip): what the two CLIP edges of candidates chosen at run time are
+        # formed from (IndexedBatch.from_clip); the per-entity cache does not depend on them - not part of _table_key
+        self.clip_text: Optional[torch.Tensor] = None
+        self.clip_image: Optional[torch.Tensor] = None
+
+    def set_clip(self, clip_text: torch.Tensor, clip_image: torch.Tensor) -> "EntityTable":
+        """The entities' projected CLIP embeddings (`CLIPModel`'s `text_embeds` / `image_embeds`, preprocess/clip.py:158-172):
+        `[E, C]` float32 each, `C % 4 == 0`, moved to the table's device.  `IndexedBatch.from_clip` and `Model.link` read them."""
+        E = self.num_entities
+        for name, t in (("clip_text", clip_text), ("clip_image", clip_image)):
+            if not torch.is_tensor(t) or t.dtype != torch.float32:
+                raise ValueError(f"EntityTable.set_clip: {name} must be a float32 tensor (got {getattr(t, 'dtype', type(t).__name__)})")
+            if t.dim() != 2 or t.shape[0] != E:
+                raise ValueError(f"EntityTable.set_clip: {name} has shape {tuple(t.shape)}, expected [{E}, C]")
+            if t.shape[1] == 0 or t.shape[1] % 4 != 0:
+                raise ValueError(f"EntityTable.set_clip: {name} has width {t.shape[1]}: C must be a positive multiple of 4")
+        if clip_text.shape[1] != clip_image.shape[1]:
+            raise ValueError(f"EntityTable.set_clip: clip_text and clip_image differ in width ({clip_text.shape[1]}, {clip_image.shape[1]})")
+        dev = self.text.device
+        self.clip_text, self.clip_image = clip_text.detach().to(dev).contiguous(), clip_image.detach().to(dev).contiguous()
+        return self
 
     # a row whose largest |x| exceeds this many times the median row's can dominate a mention's mean_n(ii ei): the mixed-f16
     # format is then not used for the table (see enable_cache)
@@ -258,6 +279,7 @@ class EntityTable:
         mv = lambda t: None if t is None else t.to(device)  # noqa: E731
         moved = EntityTable(mv(self.text), mv(self.mask), mv(self.image), mv(self.object), mv(self.object_score))
         moved.cache_enabled, moved.cache_format, moved.cache_format_forced = self.cache_enabled, self.cache_format, self.cache_format_forced
+        moved.clip_text, moved.clip_image = mv(self.clip_text), mv(self.clip_image)
         return moved
 
     def gather(self, index: torch.Tensor):
@@ -276,6 +298,56 @@ class IndexedBatch:
             raise ValueError("mention part must be the first 7 tensors of the 14-sequence (drin/data.py:110-117)")
         self.mention, self.table, self.candidates = list(mention), table, candidates
         self.miet_similarity, self.mtei_similarity = miet_similarity, mtei_similarity
+
+    @classmethod
+    @torch.no_grad()
+    def from_clip(cls, mention: Sequence[torch.Tensor], table: EntityTable, candidates: torch.Tensor, clip_image: torch.Tensor,
+                  clip_text: torch.Tensor, *, model: Optional["Model"] = None) -> "IndexedBatch":
+        """An `IndexedBatch` whose two CLIP edges are formed HERE, for candidates chosen at run time (`Model.link`, a first stage's
+        rows): `miet[b, n] = s cos(clip_image[b], table.clip_text[candidates[b, n]])`, `mtei[b, n] = s cos(clip_text[b],
+        table.clip_image[candidates[b, n]])` by `drin_cross_modal_edges` - `CLIPModel`'s `logits_per_image` / `logits_per_text`
+        (preprocess/clip.py:158-172) from stored embeddings, `s = cfg.clip_logit_scale`.  `clip_image`, `clip_text`: the mentions'
+        projected CLIP embeddings `[B, C]` float32; `table` needs `set_clip`.  GPU only.  More than `Model.MAX_CALL_MENTIONS`
+        mentions run in slices; `B = 0` gives empty matrices.  A candidate outside the table is clamped and reported: with `model`
+        into its status words, watched as its forward watches them (`check_indices`, `validate_indices`) - `model` also supplies
+        `cfg`; without a model the check is made here, at one synchronisation."""
+        cfg = model.cfg if model is not None else default_config()
+        if table.clip_text is None or table.clip_image is None:
+            raise ValueError("IndexedBatch.from_clip: the table has no CLIP rows: call table.set_clip(clip_text, clip_image)")
+        if candidates.dim() != 2:
+            raise ValueError(f"IndexedBatch.from_clip: candidates has shape {tuple(candidates.shape)}, expected [B, N]")
+        (B, N), width = candidates.shape, table.clip_text.shape[1]
+        for name, t in (("clip_image", clip_image), ("clip_text", clip_text)):
+            if not torch.is_tensor(t) or t.dtype != torch.float32 or tuple(t.shape) != (B, width):
+                raise ValueError(f"IndexedBatch.from_clip: {name} must be float32 [{B}, {width}] (got {getattr(t, 'dtype', None)} "
+                                 f"{tuple(getattr(t, 'shape', ()))})")
+        dev = candidates.device
+        if dev.type != "cuda":
+            raise RuntimeError("IndexedBatch.from_clip runs on an AMD GPU only (no CPU / eager fallback); move the batch to 'cuda'")
+        if any(t.device != dev for t in (clip_image, clip_text, table.clip_text, table.clip_image)):
+            raise RuntimeError("IndexedBatch.from_clip: the candidates, the mentions' CLIP rows and the table's must be on one device")
+        index = candidates.detach().to(torch.int64).contiguous()
+        xi, xt = clip_image.detach().contiguous(), clip_text.detach().contiguous()
+        miet = torch.empty(B, N, dtype=torch.float32, device=dev)
+        mtei = torch.empty(B, N, dtype=torch.float32, device=dev)
+        if B > 0 and N > 0:
+            lib = _lib.load()
+            status = model._status_words(dev) if model is not None else torch.zeros(4, dtype=torch.int32, device=dev)
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            step = (type(model) if model is not None else Model).MAX_CALL_MENTIONS
+            for b0 in range(0, B, step):
+                sl = slice(b0, min(B, b0 + step))
+                _lib.check(lib.drin_cross_modal_edges(_ptr(xi[sl]), _ptr(xt[sl]), _ptr(table.clip_text), _ptr(table.clip_image),
+                                                      _ptr(index[sl]), table.num_entities, sl.stop - b0, N, width,
+                                                      cfg.clip_logit_scale, cfg.cosine_eps, _ptr(miet[sl]), _ptr(mtei[sl]),
+                                                      _ptr(status), stream))
+            if model is not None:
+                model._watch_indices(dev)
+            elif not torch.cuda.is_current_stream_capturing():
+                words = status.cpu()
+                if int(words[0]) != 0:
+                    Model._raise_bad_index(words.tolist())
+        return cls(mention, table, candidates, miet, mtei)
 
     def gathered(self) -> List[torch.Tensor]:
         """The equivalent 14-sequence (entity rows materialised with torch indexing)."""
@@ -772,6 +844,7 @@ class Model(nn.Module):
         `p.data.mul_(...)`, EMA / weight swapping through `.data`, an external kernel - need this call."""
         if self._prepared is not None:
             self._prepared.invalidate()
+        self.__dict__.pop("_link_inv", None)                  # link's inverse row norms: the same rule for writes into `rows`
         return self
 
     # ---- flat buckets (SURVEY.md 8e: one all-reduce per step; train.py:55-56: one Adam launch) -------------------------
@@ -857,6 +930,7 @@ class Model(nn.Module):
         # bookkeeping, not state (a copy starts with none; its first table-form call makes its own status words)
         state = self.__dict__.copy()
         state["_index_watch"], state["_index_pool"], state["_index_status"] = [], [], {}
+        state.pop("_link_inv", None)                          # (and link's norms cache holds the caller's `rows`)
         return state
 
     # ---- candidate rows outside the entity tables (drin/data.py:87-93 raises IndexError) ------------------------------
@@ -1137,6 +1211,86 @@ class Model(nn.Module):
                 miet_similarity=leaves["miet_similarity"].detach() * g["miet_similarity"],
                 mtei_similarity=leaves["mtei_similarity"].detach() * g["mtei_similarity"])
         return out
+
+    @torch.no_grad()
+    def link(self, mention: Sequence[torch.Tensor], table: EntityTable, k: int, clip_image: torch.Tensor, clip_text: torch.Tensor, *,
+             candidates: Optional[torch.Tensor] = None, queries: Optional[torch.Tensor] = None, rows: Optional[torch.Tensor] = None):
+        """DRIN as the second stage behind a first stage, against a device-resident table: the `k` best of
+        `N = cfg.num_candidates_model` candidate rows per mention by the model's own score - `LinkResult(scores [B, k], rows [B, k])`,
+        table rows, ordered by the contract of include/drin_hip.h (higher score first, the lower row between equal scores, between
+        equal scores on equal rows the earlier candidate slot, NaN last; scores canonical: +0.0 for -0.0, one quiet NaN).
+        `mention`: the seven mention-side tensors of the 14-sequence; `clip_image` / `clip_text`: the mentions' projected CLIP
+        embeddings `[B, C]` float32; `table` with `set_clip` rows.  The candidates are EITHER `candidates [B, N]` int64 rows of the
+        table (for example `ghmfc_model.link(...).rows`) OR come from a cosine first stage: `queries [B, Dq]` against `rows [E, Dq]`
+        (float32), the `N` best by `drin_table_topk` in the model's precision (N <= 256; inverse row norms cached per version of
+        the `rows` tensor, which the model keeps a reference to until another one is given).  ALL `N` slots are candidates: in linking there is no answer slot (the reference's loss and metric drop the last
+        column, common/utils.py:36-37), so none is dropped.  Then `IndexedBatch.from_clip` forms the two CLIP edges, the model's
+        own forward scores the batch on whatever route it takes (the per-entity cache when the table has it enabled) and
+        `drin_rank_rows` orders each mention's list.  `eval()` only, no gradient, GPU only."""
+        from .ghmfc_table import LinkResult, row_inv_norms, table_topk
+        if self.training:
+            raise RuntimeError("Model.link: ranking is eval() only (no gradient flows through a top-k): call .eval()")
+        first_stage = queries is not None or rows is not None
+        if first_stage == (candidates is not None):
+            raise ValueError("Model.link: give exactly one first stage - `candidates` [B, N], or `queries` [B, Dq] with `rows` [E, Dq]")
+        if first_stage and (queries is None or rows is None):
+            raise ValueError("Model.link: `queries` [B, Dq] and `rows` [E, Dq] go together")
+        N, k = self.cfg.num_candidates_model, int(k)
+        if candidates is not None and (candidates.dim() != 2 or candidates.shape[1] != N):
+            raise ValueError(f"Model.link: candidates has shape {tuple(candidates.shape)}, expected [B, {N}] (cfg.num_candidates_model)")
+        if k < 1 or k > N:
+            raise ValueError(f"Model.link: k = {k} is not in [1, N = {N}]")
+        if table.clip_text is None or table.clip_image is None:
+            raise ValueError("Model.link: the table has no CLIP rows: call table.set_clip(clip_text, clip_image)")
+        if first_stage:
+            if N > _lib.TOPK_MAX_K:
+                raise ValueError(f"Model.link: a cosine first stage lists at most {_lib.TOPK_MAX_K} rows and N = {N}: pass `candidates`")
+            if (queries.dim() != 2 or rows.dim() != 2 or queries.shape[1] != rows.shape[1] or rows.shape[0] != table.num_entities
+                    or queries.dtype != torch.float32 or rows.dtype != torch.float32):
+                raise ValueError(f"Model.link: queries {tuple(queries.shape)} / rows {tuple(rows.shape)} must be float32 [B, Dq] and "
+                                 f"[E = {table.num_entities}, Dq]")
+            if N > rows.shape[0]:
+                raise ValueError(f"Model.link: N = {N} candidates exceed the table's {rows.shape[0]} entities")
+            if rows.device.type != "cuda" or queries.device != rows.device:
+                raise RuntimeError("Model.link runs on an AMD GPU only (no CPU / eager fallback); move queries and rows to 'cuda'")
+            # the inverse norms, per version of the CALLER's tensor: the entry keeps that tensor alive - a key of an address and a
+            # version says nothing once the memory behind it may have been freed and handed out again - and, for a
+            # non-contiguous `rows`, the contiguous copy the norms were taken of (a copy made per call would start at version 0
+            # in whatever block the allocator hands back).  While the entry holds the tensor, an equal address means the same
+            # storage, whose version counter every in-place torch op bumps (writes through `.data`: Model.invalidate())
+            given = rows
+            key = (given.data_ptr(), given._version, tuple(given.shape), tuple(given.stride()), self.cfg.cosine_eps)
+            cached = self.__dict__.get("_link_inv")
+            if cached is None or cached[0] != key:
+                self.__dict__["_link_inv"] = cached = None                # release the stale copy before allocating
+                dense = given.detach().contiguous()
+                self.__dict__["_link_inv"] = cached = (key, row_inv_norms(dense, self.cfg.cosine_eps), given, dense)
+            rows = cached[3]
+            B = queries.shape[0]
+            if B == 0:
+                candidates = torch.empty(0, N, dtype=torch.int64, device=rows.device)
+            else:
+                step, q = self.MAX_CALL_MENTIONS, queries.detach().contiguous()
+                precision = "f32" if self.precision == _lib.PREC_F32 else "bf16x3"
+                parts = [table_topk(q[b0:b0 + step], rows, cached[1], N, self.cfg.cosine_eps, precision).rows for b0 in range(0, B, step)]
+                candidates = parts[0] if len(parts) == 1 else torch.cat(parts, 0)
+        if candidates.device.type != "cuda":
+            raise RuntimeError("Model.link runs on an AMD GPU only (no CPU / eager fallback); move the batch to 'cuda'")
+        candidates = candidates.detach().to(torch.int64).contiguous()
+        if candidates.shape[0] == 0:
+            return LinkResult(torch.empty(0, k, dtype=torch.float32, device=candidates.device),
+                              torch.empty(0, k, dtype=torch.int64, device=candidates.device))
+        batch = IndexedBatch.from_clip(mention, table, candidates, clip_image, clip_text, model=self)
+        scores = self(batch).contiguous()
+        B, dev = candidates.shape[0], candidates.device
+        out_scores = torch.empty(B, k, dtype=torch.float32, device=dev)
+        out_rows = torch.empty(B, k, dtype=torch.int64, device=dev)
+        lib, stream = _lib.load(), torch.cuda.current_stream(dev).cuda_stream
+        for b0 in range(0, B, self.MAX_CALL_MENTIONS):
+            sl = slice(b0, min(B, b0 + self.MAX_CALL_MENTIONS))
+            _lib.check(lib.drin_rank_rows(_ptr(scores[sl]), _ptr(candidates[sl]), sl.stop - b0, N, k, _ptr(out_scores[sl]),
+                                          _ptr(out_rows[sl]), None, stream))
+        return LinkResult(out_scores, out_rows)
 
     def wait_for_parameters(self) -> None:
         """Make the current stream wait for an optimiser update `train.OverlappedStep` left running on its side stream (no-op

@@ -125,6 +125,16 @@ def make_learnable_batch(cfg: DrinConfig, batch: int, seed: int, strength: float
     return plant_gold_signal(cfg, make_batch(cfg, batch, seed, **kw), strength)
 
 
+def make_clip_rows(num_entities: int, batch: int, width: int = 512, seed: int = 1, as_torch: bool = True):
+    """CLIP-like rows for a table and a batch: `(table_clip_text [E, C], table_clip_image [E, C], mention_clip_image [B, C],
+    mention_clip_text [B, C])`, unit-scale normal float32 - stand-ins for `CLIPModel`'s projected `text_embeds` / `image_embeds`
+    (preprocess/clip.py:158-172; the real weights are not available offline).  Seeded like `make_batch`, from a Philox stream
+    of its own: the draws of the other functions do not move."""
+    g = _rng(seed, 2)
+    out = [_normal(g, (num_entities, width)), _normal(g, (num_entities, width)), _normal(g, (batch, width)), _normal(g, (batch, width))]
+    return [torch.from_numpy(x) for x in out] if as_torch else out
+
+
 STATE_DICT_SHAPES = lambda D, R, layers, vector=False: (  # noqa: E731 - SURVEY.md §8(b) state_dict contract
     [
         ("vertex_encoder.mention_text_encoder.final_layer.linear.weight", (D, D)),

@@ -1075,6 +1075,34 @@ DRIN_API int drin_table_topk(const float* x, const float* rows, const float* row
                              int32_t width, int32_t k, float cosine_eps, int32_t precision, int64_t chunk_entities, void* workspace,
                              size_t workspace_bytes, float* out_scores, int64_t* out_rows, void* stream);
 
+/* ---- DRIN behind a first stage: CLIP edges for run-time candidates and a rerank ---------------- *
+ * The two CLIP edges of drin_batch (miet_similarity, mtei_similarity) for candidates that were chosen at run time, from stored
+ * CLIP embeddings: replaces preprocess/clip.py:158-172, which computes CLIPModel's logits_per_image / logits_per_text offline
+ * per pair of a fixed candidate list - exp(logit_scale) x the cosine of the projected embeddings, the scale that model.py:203
+ * divides by again (drin_config.clip_scale).
+ *   miet[b, n] = scale * cos(mention_clip_image[b, :], table_clip_text[index[b, n], :])
+ *   mtei[b, n] = scale * cos(mention_clip_text[b, :],  table_clip_image[index[b, n], :])
+ * mention rows [batch, width], table rows [num_entities, width], index int64 [batch, num_candidates], outputs [batch,
+ * num_candidates]; all fp32.  One launch, one read of index per pair.  Every output is, bit for bit, scale * what
+ * drin_cosine_rows_indexed_fwd returns for the same rows (one fp32 multiply); a zero row gives 0.  Either edge may be left
+ * out: its three pointers (mention rows, table rows, output) NULL together.  index is clamped and reported into index_status
+ * (int32[4] or NULL) as the row operations of section 23 do.  The four row pointers are 16-byte aligned, width % 4 == 0,
+ * batch 1 .. 65535, num_candidates 1 .. 65535.  Writes miet, mtei and (on a bad index) index_status, nothing else.
+ * Profiler class DRIN_KC_EDGE. */
+DRIN_API int drin_cross_modal_edges(const float* mention_clip_image, const float* mention_clip_text, const float* table_clip_text,
+                                    const float* table_clip_image, const int64_t* index, int64_t num_entities, int32_t batch,
+                                    int32_t num_candidates, int32_t width, float scale, float eps, float* miet, float* mtei,
+                                    int32_t* index_status, void* stream);
+
+/* Per mention, the first k of n (score, row) pairs - scores [batch, n], rows int64 [batch, n] - under THE ORDERING CONTRACT
+ * above, with one rule added because a caller's candidate list may name a row twice: between equal scores on equal rows, the
+ * lower slot (column of the input) ranks first.  out_scores [batch, k] come back canonical, as drin_topk_update returns its
+ * keys (+0.0 for -0.0, one quiet NaN); out_rows int64 [batch, k]; out_slots int32 [batch, k] - the column of each returned
+ * pair in the input - may be NULL.  One workgroup per mention, a bitonic sort in LDS.  1 <= k <= n <= 4096, batch 1 .. 65535;
+ * rows of any int64 value.  Writes the three outputs, nothing else. */
+DRIN_API int drin_rank_rows(const float* scores, const int64_t* rows, int32_t batch, int32_t n, int32_t k, float* out_scores,
+                            int64_t* out_rows, int32_t* out_slots, void* stream);
+
 /* ---- activation, row dropout and the span mean (GHMFC's other mention encoders) ---------------- *
  * What nn.TransformerEncoderLayer runs beside its products, attention and LayerNorms (ghmfc.py:72-90), and Avg.avg
  * (ghmfc.py:54-60) as an entry point of its own.  Checked on the host before a launch like the row operations above. */

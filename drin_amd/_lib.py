@@ -134,6 +134,13 @@ class DrinGhmfcTableC(C.Structure):    # drin_ghmfc_table: the table form of dri
                 ("entity_tokens", C.c_int32), ("candidates", C.c_void_p), ("index_status", C.c_void_p), ("rows", C.c_void_p)]
 
 
+class DrinTopkTermC(C.Structure):     # drin_topk_term: one cosine of drin_table_topk_sum's sum
+    _fields_ = [("x", C.c_void_p), ("rows", C.c_void_p), ("row_inv_norms", C.c_void_p), ("width", C.c_int32), ("weight", C.c_float)]
+
+
+TOPK_MAX_TERMS = 4                                                         # DRIN_TOPK_MAX_TERMS
+
+
 class DrinGemmRouteC(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("launches", "family", "bm", "bn", "w_planes", "a_lo", "f16", "persist", "indexed", "accumulate",
                                          "ksplit", "splits")] + [(n, C.c_int64) for n in ("tiles", "whole_tiles", "tile0", "work_items")]
@@ -293,6 +300,16 @@ EXPORTS = {
     "drin_table_topk_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int64]),
     "drin_table_topk": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32,
                                   C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # a sum of cosines against the tables (csrc/table_topk.hip):
+    # (blocks, col_inv_norms, row_scales, weights, num_terms, ld, batch, cols, out, stream),
+    # (terms, num_terms, batch, num_entities, k, chunk_entities),
+    # (terms, num_terms, num_entities, batch, k, cosine_eps, precision, chunk_entities, workspace, workspace_bytes, out_scores, out_rows,
+    #  stream)
+    "drin_topk_combine": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_float), C.c_int32,
+                                    C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]),
+    "drin_table_topk_sum_workspace_bytes": (C.c_size_t, [C.POINTER(DrinTopkTermC), C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int64]),
+    "drin_table_topk_sum": (C.c_int, [C.POINTER(DrinTopkTermC), C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int64,
+                                      C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     # DRIN behind a first stage (csrc/cross_edges.hip, csrc/table_topk.hip):
     # (mention_clip_image, mention_clip_text, table_clip_text, table_clip_image, index, num_entities, batch, num_candidates, width,
     #  scale, eps, miet, mtei, index_status, stream), (scores, rows, batch, n, k, out_scores, out_rows, out_slots, stream)

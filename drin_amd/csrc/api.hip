@@ -1666,6 +1666,18 @@ int drin_host_selftest(void) {
     DRIN_TRY(table_topk_layout_selfcheck(4096, 1000000, 768, k, 0));
     DRIN_TRY(table_topk_layout_selfcheck(kMaxGridY, 1000000, 768, k, 512));
   }
+  // the summed-cosine workspace (TopkSumLayout): tiny, the text + CLIP widths at E = 1 M and B = 4096, four terms
+  {
+    const int tiny[] = {16, 8, 8}, edges[] = {768, 512, 512}, four[] = {16, 260, 4, 768};
+    for (int64_t chunk : {(int64_t)0, (int64_t)64}) {
+      DRIN_TRY(table_topk_sum_layout_selfcheck(tiny, 3, 3, 300, 20, chunk));
+      DRIN_TRY(table_topk_sum_layout_selfcheck(tiny, 1, 1, 7, 7, chunk));
+    }
+    DRIN_TRY(table_topk_sum_layout_selfcheck(edges, 3, 4096, 1000000, 100, 0));
+    DRIN_TRY(table_topk_sum_layout_selfcheck(edges, 3, 4096, 1000000, 100, 512));
+    for (int k : {1, 100, 256}) DRIN_TRY(table_topk_sum_layout_selfcheck(four, 4, 9, 70000, k, 0));
+    DRIN_TRY(table_topk_sum_layout_selfcheck(four, 4, kMaxGridY, 1000000, 256, 0));
+  }
   // (5) for_grid_slices (internal.h), the launch loop of every sliced launcher: contiguous slices of at most kMaxGridY that cover
   //     [0, count) exactly, none for an empty count; a failing slice ends the walk and its status comes back
   for (int64_t count : {(int64_t)0, (int64_t)1, (int64_t)kMaxGridY, (int64_t)kMaxGridY + 1, 2 * (int64_t)kMaxGridY, 2 * (int64_t)kMaxGridY + 1}) {

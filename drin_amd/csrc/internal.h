@@ -322,5 +322,7 @@ int ghmfc_layout_selfcheck(int B, int N, int D, int R, int L, int P, int T);   /
 int ghmfc_table_layout_selfcheck(int B, int N, int D, int R, int L, int P, int T, bool rows, int64_t E);
 // TopkLayout (table_topk.hip): the workspace of drin_table_topk, and the rules of its kp, chunk and slice count
 int table_topk_layout_selfcheck(int B, int64_t E, int D, int k, int64_t chunk_entities);
+// TopkSumLayout (table_topk.hip): the workspace of drin_table_topk_sum for S live terms of the given widths
+int table_topk_sum_layout_selfcheck(const int* widths, int S, int B, int64_t E, int k, int64_t chunk_entities);
 
 }  // namespace drin

@@ -72,6 +72,67 @@ __global__ void __launch_bounds__(256) k_pad_rows(const float* __restrict__ x, f
     st4(out + i * 4, i < n4_in ? ld4(x + i * 4) : make_float4(0.f, 0.f, 0.f, 0.f));
 }
 
+// ---- the summed-cosine form ----------------------------------------------------------------------
+// The S blocks of dot products of one chunk -> ONE block of scores: out[c * ld + b] = sum_s block_s[c * ld + b] * inv_s[c] *
+// (scale_s[b] * weight_s), in term order, every multiply and add rounded to fp32 on its own (no contraction: the sum can be
+// restated bit for bit).  A pure stream over S blocks in and one block out: a thread keeps ONE quad of mentions - its S float4 of
+// per-mention factors are read once - and walks rows of the block, 16 bytes per lane per block; a workgroup is 2^tx_log2 quads
+// wide and 256 >> tx_log2 rows tall, so that a wave's lanes cover whole rows of a narrow block (rows are contiguous when
+// ld = Bp).  out may alias block 0: a thread reads its own 16 bytes of every block before it writes them.
+struct CombineTerms {
+  const float* block[DRIN_TOPK_MAX_TERMS];
+  const float* inv[DRIN_TOPK_MAX_TERMS];     // [cols], already moved to the chunk's first row
+  const float* scale[DRIN_TOPK_MAX_TERMS];   // [ld]
+  float weight[DRIN_TOPK_MAX_TERMS];
+};
+// (hipcc contracts a * b + c by default, and HIP's __fmul_rn / __fadd_rn are inline functions around the plain operators,
+//  compiled under that default: a multiply and an add made of them still fuse.  The operators under this pragma do not -
+//  tests/test_table_topk_sum_host.py reads the ISA for an fma.  The pragma holds under hipcc's default -ffp-contract=fast-honor-pragmas:
+//  the build must not pass -ffp-contract=fast, which ignores it)
+__device__ __forceinline__ float4 mul4_rn(float4 a, float4 b) {
+#pragma clang fp contract(off)
+  return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w);
+}
+__device__ __forceinline__ float4 mul4_rn(float4 a, float s) { return mul4_rn(a, make_float4(s, s, s, s)); }
+__device__ __forceinline__ float4 add4_rn(float4 a, float4 b) {
+#pragma clang fp contract(off)
+  return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
+}
+template <int S>
+__global__ void __launch_bounds__(256) k_topk_combine(CombineTerms t, float* out, int64_t ld, int64_t cols, int tx_log2) {
+  const int64_t q4 = ((int64_t)blockIdx.x << tx_log2 | (threadIdx.x & ((1 << tx_log2) - 1))) * 4;   // first mention of the quad
+  if (q4 >= ld) return;                                   // no barrier below
+  const int ty = threadIdx.x >> tx_log2, rows_tall = 256 >> tx_log2;
+  float4 f[S];
+#pragma unroll
+  for (int s = 0; s < S; ++s) f[s] = mul4_rn(ld4(t.scale[s] + q4), t.weight[s]);
+  for (int64_t c = (int64_t)blockIdx.y * rows_tall + ty; c < cols; c += (int64_t)gridDim.y * rows_tall) {
+    float4 v[S];
+#pragma unroll
+    for (int s = 0; s < S; ++s) v[s] = ld4(t.block[s] + c * ld + q4);
+    float4 acc = mul4_rn(mul4_rn(v[0], t.inv[0][c]), f[0]);
+#pragma unroll
+    for (int s = 1; s < S; ++s) acc = add4_rn(acc, mul4_rn(mul4_rn(v[s], t.inv[s][c]), f[s]));
+    st4(out + c * ld + q4, acc);
+  }
+}
+
+// out[i] = w_0 c_0[i], then + w_s c_s[i] for s = 1 ..: the fp32 chain over the S re-scored cosines cos [S][n], every multiply
+// and add rounded on its own; n % 4 == 0.
+struct ChainWeights {
+  float w[DRIN_TOPK_MAX_TERMS];
+};
+__global__ void __launch_bounds__(256) k_weighted_cosine_sum(const float* __restrict__ cos, int S, int64_t n4, ChainWeights cw,
+                                                             float* __restrict__ out) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+    float4 acc = mul4_rn(ld4(cos + i * 4), cw.w[0]);
+#pragma unroll
+    for (int s = 1; s < DRIN_TOPK_MAX_TERMS; ++s)          // constant indices into the argument struct
+      if (s < S) acc = add4_rn(acc, mul4_rn(ld4(cos + ((int64_t)s * n4 + i) * 4), cw.w[s]));
+    st4(out + i * 4, acc);
+  }
+}
+
 // Descending bitonic sort of 64 R composites held R per lane (element r * 64 + lane), in registers: a stride below 64 exchanges
 // lanes (__shfl_xor: no LDS traffic, no barrier), a stride from 64 up exchanges two of the lane's own registers.
 __device__ __forceinline__ uint64_t shfl_xor64(uint64_t v, int mask) {
@@ -399,7 +460,140 @@ int check_precision_topk(const char* who, int precision) {
   return DRIN_OK;
 }
 
+// ---- the summed-cosine form: launchers, the live terms of a call, the workspace --------------------------------------------
+int launch_topk_combine(const CombineTerms& t, int S, float* out, int64_t ld, int64_t cols, hipStream_t st) {
+  const int64_t quads = ld / 4;
+  int tx_log2 = 0;
+  while (tx_log2 < 8 && ((int64_t)1 << tx_log2) < quads) ++tx_log2;
+  const int64_t rows_tall = 256 >> tx_log2;
+  const int64_t gx = cdiv(quads, (int64_t)1 << tx_log2);          // ld <= 2^31 - 1: at most 2^21
+  int64_t gy = cdiv(cols, rows_tall * 8);                         // eight rows per thread; past the cap a thread walks more
+  gy = gy < 1 ? 1 : (gy > kMaxGridY ? kMaxGridY : gy);
+  auto kernel = S == 1 ? k_topk_combine<1> : S == 2 ? k_topk_combine<2> : S == 3 ? k_topk_combine<3> : k_topk_combine<4>;
+  return timed(DRIN_KC_EDGE, st, "k_topk_combine", [&] {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, st, t, out, ld, cols, tx_log2);
+  });
+}
+
+int launch_weighted_cosine_sum(const float* cos, int S, int64_t n, const ChainWeights& cw, float* out, hipStream_t st) {
+  const int64_t n4 = n / 4, blocks = cdiv(n4, 256) < 4096 ? cdiv(n4, 256) : 4096;
+  return timed(DRIN_KC_EDGE, st, "k_weighted_cosine_sum", [&] {
+    hipLaunchKernelGGL(k_weighted_cosine_sum, dim3((unsigned)blocks), dim3(256), 0, st, cos, S, n4, cw, out);
+  });
+}
+
+// The live terms of a call, in order: a term of weight 0 is dropped here, before anything looks at its pointers.  `pointers`:
+// also NULL and alignment of the live terms' three arrays (the size query reads widths and weights only).
+struct LiveTerms {
+  drin_topk_term term[DRIN_TOPK_MAX_TERMS];
+  int widths[DRIN_TOPK_MAX_TERMS];
+  int S = 0;
+};
+int live_terms(const char* who, const drin_topk_term* terms, int num_terms, bool pointers, LiveTerms* out) {
+  if (!terms) {
+    set_error("%s: terms is NULL", who);
+    return DRIN_E_NULL;
+  }
+  DRIN_TRY(check_count(who, "num_terms", num_terms, 1, DRIN_TOPK_MAX_TERMS));
+  for (int s = 0; s < num_terms; ++s) {
+    const drin_topk_term& t = terms[s];
+    if (!(t.weight - t.weight == 0.0f)) {
+      set_error("%s: term %d: weight is not finite", who, s);
+      return DRIN_E_SHAPE;
+    }
+    if (t.weight == 0.0f) continue;
+    if (t.width <= 0 || t.width % 4) {
+      set_error("%s: term %d: width %d must be a positive multiple of 4 (16-byte lane accesses)", who, s, t.width);
+      return DRIN_E_SHAPE;
+    }
+    if (pointers) {
+      const NamedPtr ptrs[] = {{"x", t.x, true}, {"rows", t.rows, true}, {"row_inv_norms", t.row_inv_norms, true}};
+      for (const NamedPtr& p : ptrs) {
+        if (!p.p) {
+          set_error("%s: term %d: %s is NULL", who, s, p.name);
+          return DRIN_E_NULL;
+        }
+        if (!aligned16(p.p)) {
+          set_error("%s: term %d: %s is not 16-byte aligned", who, s, p.name);
+          return DRIN_E_ALIGN;
+        }
+      }
+    }
+    out->widths[out->S] = t.width;
+    out->term[out->S++] = t;
+  }
+  if (out->S == 0) {
+    set_error("%s: no live term (every weight is 0)", who);
+    return DRIN_E_SHAPE;
+  }
+  return DRIN_OK;
+}
+
+// the workspace of drin_table_topk_sum: per live term the padded mentions, their factors and one block of dot products (block 0
+// takes the combined scores), the S x [batch, kp] re-scored cosines, and the selection's regions as TopkLayout has them
+struct TopkSumLayout {
+  size_t xpad[DRIN_TOPK_MAX_TERMS], scale[DRIN_TOPK_MAX_TERMS], block[DRIN_TOPK_MAX_TERMS];   // offsets in floats
+  size_t cos, keys, rows, slices, scores, total_floats;
+  int64_t chunk, num_slices;
+  int kp, Bp, S;
+  bool build(const int* widths, int terms, int batch, int64_t E, int k, int64_t chunk_entities) {
+    kp = DRIN_TOPK_KP(k), Bp = (batch + 3) & ~3, S = terms;
+    if (chunk_entities > 0) {
+      chunk = chunk_entities;
+    } else {   // a multiple of 256 rows whose S blocks together stay inside the budget (at least 256)
+      chunk = kBlockBudgetBytes / ((int64_t)S * Bp * 4) / 256 * 256;
+      chunk = chunk < 256 ? 256 : chunk;
+    }
+    chunk = chunk < E ? chunk : E;
+    if (chunk > kMaxChunk) return false;
+    num_slices = slices_of(chunk);
+    const size_t limit = SIZE_MAX / 256;   // of floats: the sum of all regions and the byte count stay representable
+    auto fits = [&](size_t a, size_t b) { return a == 0 || b <= limit / a; };
+    if (!fits((size_t)chunk * S, (size_t)Bp) || !fits((size_t)num_slices * 2, (size_t)batch * kp)) return false;
+    Arena A;
+    for (int s = 0; s < S; ++s) {
+      xpad[s] = A.take((size_t)Bp * widths[s]);
+      scale[s] = A.take((size_t)Bp);
+      block[s] = A.take((size_t)chunk * Bp);
+    }
+    cos = A.take((size_t)S * batch * kp);
+    keys = A.take((size_t)batch * kp);
+    rows = A.take((size_t)batch * kp * 2);
+    slices = A.take((size_t)num_slices * batch * kp * 2);
+    scores = A.take((size_t)batch * kp);
+    total_floats = A.total;
+    return true;
+  }
+};
+
 }  // namespace
+
+int table_topk_sum_layout_selfcheck(const int* widths, int S, int batch, int64_t E, int k, int64_t chunk_entities) {
+  TopkSumLayout W;
+  if (!W.build(widths, S, batch, E, k, chunk_entities)) {
+    set_error("selftest: TopkSumLayout does not build for S=%d B=%d E=%lld k=%d chunk=%lld", S, batch, (long long)E, k, (long long)chunk_entities);
+    return DRIN_E_WORKSPACE;
+  }
+  const size_t B = batch, kp = W.kp;
+  if (W.kp < k || W.kp > kMaxKp || (W.kp & (W.kp - 1)) || W.chunk < 1 || W.chunk > E || W.num_slices * kSlice < W.chunk ||
+      (chunk_entities == 0 && W.chunk != E && (W.chunk % 256 || (W.chunk > 256 && W.chunk * W.Bp * 4 * S > kBlockBudgetBytes)))) {
+    set_error("selftest: TopkSumLayout kp=%d chunk=%lld slices=%lld break their rules", W.kp, (long long)W.chunk, (long long)W.num_slices);
+    return DRIN_E_WORKSPACE;
+  }
+  Region ws[3 * DRIN_TOPK_MAX_TERMS + 5];
+  int n = 0;
+  for (int s = 0; s < S; ++s) {
+    ws[n++] = {"xpad", W.xpad[s], (size_t)W.Bp * widths[s]};
+    ws[n++] = {"scale", W.scale[s], (size_t)W.Bp};
+    ws[n++] = {"block", W.block[s], (size_t)W.chunk * W.Bp};
+  }
+  ws[n++] = {"cos", W.cos, (size_t)S * B * kp};
+  ws[n++] = {"keys", W.keys, B * kp};
+  ws[n++] = {"rows", W.rows, B * kp * 2};
+  ws[n++] = {"slices", W.slices, (size_t)cdiv(W.chunk, kSlice) * B * kp * 2};
+  ws[n++] = {"scores", W.scores, B * kp};
+  return regions_hold("TopkSumLayout", ws, n, W.total_floats);
+}
 
 int table_topk_layout_selfcheck(int batch, int64_t E, int D, int k, int64_t chunk_entities) {
   TopkLayout W;
@@ -557,6 +751,141 @@ int drin_table_topk(const float* x, const float* rows, const float* row_inv_norm
   // the kp selected rows of every mention, scored as drin_cosine_rows_indexed_fwd scores them (an empty entry, row -1, is clamped
   // silently and stays last), ordered by the contract
   DRIN_TRY(launch_cosine_gather(x, rows, list, num_entities, scores, B, kp, D, cosine_eps, nullptr, 0, st));
+  return launch_topk_finish(scores, list, B, kp, k, out_scores, out_rows, st);
+}
+
+int drin_topk_combine(const float* const* blocks, const float* const* col_inv_norms, const float* const* row_scales, const float* weights,
+                      int32_t num_terms, int64_t ld, int32_t batch, int64_t cols, float* out, void* stream) {
+  const char* who = "drin_topk_combine";
+  if (!blocks || !col_inv_norms || !row_scales || !weights || !out) {
+    set_error("%s: %s is NULL", who, !blocks ? "blocks" : !col_inv_norms ? "col_inv_norms" : !row_scales ? "row_scales" : !weights ? "weights" : "out");
+    return DRIN_E_NULL;
+  }
+  DRIN_TRY(check_count(who, "num_terms", num_terms, 1, DRIN_TOPK_MAX_TERMS));
+  CombineTerms t = {};
+  for (int s = 0; s < num_terms; ++s) {
+    if (!blocks[s] || !col_inv_norms[s] || !row_scales[s]) {
+      set_error("%s: term %d: %s is NULL", who, s, !blocks[s] ? "blocks" : !col_inv_norms[s] ? "col_inv_norms" : "row_scales");
+      return DRIN_E_NULL;
+    }
+    if (!aligned16(blocks[s]) || !aligned16(row_scales[s]) || (reinterpret_cast<uintptr_t>(col_inv_norms[s]) & 3u) != 0) {
+      set_error("%s: term %d: blocks and row_scales must be 16-byte, col_inv_norms 4-byte aligned", who, s);
+      return DRIN_E_ALIGN;
+    }
+    if (!(weights[s] - weights[s] == 0.0f)) {
+      set_error("%s: term %d: weight is not finite", who, s);
+      return DRIN_E_SHAPE;
+    }
+    t.block[s] = blocks[s], t.inv[s] = col_inv_norms[s], t.scale[s] = row_scales[s], t.weight[s] = weights[s];
+  }
+  if (!aligned16(out)) {
+    set_error("%s: out is not 16-byte aligned", who);
+    return DRIN_E_ALIGN;
+  }
+  DRIN_TRY(check_count(who, "batch", batch, 1, kMaxGridY));
+  DRIN_TRY(check_count(who, "cols", cols, 1, INT32_MAX));
+  if (ld % 4 != 0 || ld < ((int64_t)batch + 3) / 4 * 4 || ld > INT32_MAX) {
+    set_error("%s: ld = %lld must be a multiple of 4, at least batch rounded up to one and at most 2^31 - 1", who, (long long)ld);
+    return DRIN_E_SHAPE;
+  }
+  DRIN_BIND_DEVICE(stream, out, who);
+  return launch_topk_combine(t, num_terms, out, ld, cols, (hipStream_t)stream);
+}
+
+size_t drin_table_topk_sum_workspace_bytes(const drin_topk_term* terms, int32_t num_terms, int32_t batch, int64_t num_entities, int32_t k,
+                                           int64_t chunk_entities) {
+  const char* who = "drin_table_topk_sum_workspace_bytes";
+  LiveTerms live;
+  if (live_terms(who, terms, num_terms, false, &live) != DRIN_OK) return 0;
+  if (check_topk_shape(who, num_entities, batch, live.widths[0], k) != DRIN_OK) return 0;
+  if (chunk_entities < 0) {
+    set_error("%s: chunk_entities = %lld is negative", who, (long long)chunk_entities);
+    return 0;
+  }
+  TopkSumLayout W;
+  if (!W.build(live.widths, live.S, batch, num_entities, k, chunk_entities)) {
+    set_error("%s: chunk_entities = %lld is out of range (at most 2^30 rows, the workspace must fit in size_t)", who,
+              (long long)chunk_entities);
+    return 0;
+  }
+  return W.total_floats * sizeof(float);
+}
+
+int drin_table_topk_sum(const drin_topk_term* terms, int32_t num_terms, int64_t num_entities, int32_t batch, int32_t k, float cosine_eps,
+                        int32_t precision, int64_t chunk_entities, void* workspace, size_t workspace_bytes, float* out_scores,
+                        int64_t* out_rows, void* stream) {
+  const char* who = "drin_table_topk_sum";
+  LiveTerms live;
+  DRIN_TRY(live_terms(who, terms, num_terms, true, &live));
+  DRIN_CHECK_POINTERS(who, {"workspace", workspace, true});
+  if (!out_scores || !out_rows) {
+    set_error("%s: out_scores / out_rows is NULL", who);
+    return DRIN_E_NULL;
+  }
+  if ((reinterpret_cast<uintptr_t>(out_scores) & 3u) != 0 || (reinterpret_cast<uintptr_t>(out_rows) & 7u) != 0) {
+    set_error("%s: out_scores must be 4-byte and out_rows 8-byte aligned", who);
+    return DRIN_E_ALIGN;
+  }
+  DRIN_TRY(check_topk_shape(who, num_entities, batch, live.widths[0], k));
+  DRIN_TRY(check_precision_topk(who, precision));
+  if (chunk_entities < 0) {
+    set_error("%s: chunk_entities = %lld is negative", who, (long long)chunk_entities);
+    return DRIN_E_SHAPE;
+  }
+  TopkSumLayout W;
+  if (!W.build(live.widths, live.S, batch, num_entities, k, chunk_entities)) {
+    set_error("%s: chunk_entities = %lld is out of range (at most 2^30 rows, the workspace must fit in size_t)", who,
+              (long long)chunk_entities);
+    return DRIN_E_SHAPE;
+  }
+  if (workspace_bytes < W.total_floats * sizeof(float)) {
+    set_error("%s: workspace %zu bytes < %zu", who, workspace_bytes, W.total_floats * sizeof(float));
+    return DRIN_E_WORKSPACE;
+  }
+  DRIN_BIND_DEVICE(stream, out_scores, who);
+  RoctxRange range(who);
+  hipStream_t st = (hipStream_t)stream;
+  float* ws = static_cast<float*>(workspace);
+  const int B = batch, S = live.S, kp = W.kp, Bp = W.Bp;
+  float* keys = ws + W.keys;
+  int64_t* list = reinterpret_cast<int64_t*>(ws + W.rows);
+  uint64_t* slices = reinterpret_cast<uint64_t*>(ws + W.slices);
+  float* cos = ws + W.cos;
+  float* scores = ws + W.scores;
+  CombineTerms ct = {};
+  ChainWeights cw = {};
+  // the mentions of every term padded to Bp rows, and their factors 1 / max(|x_s[b]|, eps): unlike the single cosine, the mention
+  // norms differ from term to term and do change the ranking (the weight joins them inside the combine)
+  for (int s = 0; s < S; ++s) {
+    const drin_topk_term& t = live.term[s];
+    float* xpad = ws + W.xpad[s];
+    const int64_t n4_in = (int64_t)B * t.width / 4, n4_out = (int64_t)Bp * t.width / 4;
+    DRIN_TRY(timed(DRIN_KC_EDGE, st, "k_pad_rows", [&] {
+      hipLaunchKernelGGL(k_pad_rows, dim3((unsigned)(cdiv(n4_out, 256) < 4096 ? cdiv(n4_out, 256) : 4096)), dim3(256), 0, st, t.x, xpad, n4_in, n4_out);
+    }));
+    DRIN_TRY(launch_row_inv_norms(xpad, Bp, t.width, cosine_eps, ws + W.scale[s], st));
+    ct.block[s] = ws + W.block[s], ct.scale[s] = ws + W.scale[s], ct.weight[s] = t.weight, cw.w[s] = t.weight;
+  }
+  // per chunk of table rows: one product per live term into its own entity-major block (kernel choice: the GEMM module's, by the
+  // chunk's row count), ONE combine into block 0, then the selection on the combined scores (no inverse norms left to apply)
+  float* combined = ws + W.block[0];
+  for (int64_t e0 = 0; e0 < num_entities; e0 += W.chunk) {
+    const int64_t n = num_entities - e0 < W.chunk ? num_entities - e0 : W.chunk;
+    for (int s = 0; s < S; ++s) {
+      const drin_topk_term& t = live.term[s];
+      DRIN_TRY(launch_gemm_nt({{t.rows + e0 * t.width, t.width}, {ws + W.xpad[s], t.width}, nullptr, ws + W.block[s], Bp, n, Bp, t.width}, precision, st));
+      ct.inv[s] = t.row_inv_norms + e0;
+    }
+    DRIN_TRY(launch_topk_combine(ct, S, combined, Bp, n, st));
+    DRIN_TRY(launch_topk_update(combined, Bp, B, n, e0, nullptr, kp, keys, list, slices, e0 == 0, st));
+  }
+  // the kp selected rows scored again, term by term as drin_cosine_rows_indexed_fwd scores them (an empty entry, row -1, is clamped
+  // silently and stays last), the fp32 chain over the terms, and the order of the contract
+  for (int s = 0; s < S; ++s) {
+    const drin_topk_term& t = live.term[s];
+    DRIN_TRY(launch_cosine_gather(t.x, t.rows, list, num_entities, cos + (size_t)s * B * kp, B, kp, t.width, cosine_eps, nullptr, 0, st));
+  }
+  DRIN_TRY(launch_weighted_cosine_sum(cos, S, (int64_t)B * kp, cw, scores, st));
   return launch_topk_finish(scores, list, B, kp, k, out_scores, out_rows, st);
 }
 

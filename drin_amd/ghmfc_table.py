@@ -149,6 +149,46 @@ def table_topk(x: torch.Tensor, rows: torch.Tensor, inv_norms: torch.Tensor, k: 
     return LinkResult(scores, best)
 
 
+def table_topk_sum(terms: Sequence, k: int, eps: float, precision: str, chunk_entities: int = 0) -> LinkResult:
+    """The k best table rows for every mention by a SUM of cosines (`drin_table_topk_sum`):
+    `score(b, e) = sum_s weight_s * cos(x_s[b], rows_s[e])`.  `terms`: 1 to 4 of `(x [B, D_s], rows [E, D_s], inv_norms [E],
+    weight)` - contiguous float32 tensors on one GPU, `inv_norms = row_inv_norms(rows, eps)`; the terms share `B` and `E`, not
+    their width.  A term of weight 0 is dropped before any launch and its three tensors may be `None`.  The returned scores are
+    the fp32 chain `w_0 c_0 + w_1 c_1 + ...` over `cosine_rows_indexed` of each live term on the returned rows, bit for bit."""
+    lib = _lib.load()
+    terms = list(terms)
+    arr = (_lib.DrinTopkTermC * max(len(terms), 1))()
+    live = None
+    for s, (x, rows, inv, weight) in enumerate(terms[:len(arr)]):
+        arr[s].weight = float(weight)
+        if float(weight) == 0.0:
+            continue
+        # the library trusts the extents it is given: what the kernels index is settled here
+        for name, t in (("x", x), ("rows", rows), ("inv_norms", inv)):
+            if not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous() or t.device.type != "cuda":
+                raise ValueError(f"table_topk_sum: term {s}: {name} must be a contiguous float32 tensor on the GPU")
+        if live is None:
+            live = (x.shape[0], rows.shape[0], x.device)
+        if (x.dim() != 2 or rows.dim() != 2 or x.shape[1] != rows.shape[1] or x.shape[0] != live[0] or rows.shape[0] != live[1]
+                or tuple(inv.shape) != (live[1],) or any(t.device != live[2] for t in (x, rows, inv))):
+            raise ValueError(f"table_topk_sum: term {s}: x {tuple(x.shape)}, rows {tuple(rows.shape)}, inv_norms {tuple(inv.shape)} must be "
+                             f"[B = {live[0]}, D], [E = {live[1]}, D], [E] on one device")
+        arr[s].x, arr[s].rows, arr[s].row_inv_norms, arr[s].width = x.data_ptr(), rows.data_ptr(), inv.data_ptr(), x.shape[1]
+    if live is None:                                                       # no live term, or none at all: the library names the reason
+        _lib.check(lib.drin_table_topk_sum(arr, len(terms), 1, 1, k, eps, PRECISIONS[precision], chunk_entities, None, 0, None, None, None))
+        raise _lib.DrinError(_lib.E_SHAPE, "drin_table_topk_sum: no live term")
+    B, E, dev = live
+    nbytes = lib.drin_table_topk_sum_workspace_bytes(arr, len(terms), B, E, k, chunk_entities)
+    if nbytes == 0:
+        _lib.check(_lib.E_SHAPE)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    scores = torch.empty(B, k, dtype=torch.float32, device=dev)
+    best = torch.empty(B, k, dtype=torch.int64, device=dev)
+    _lib.check(lib.drin_table_topk_sum(arr, len(terms), E, B, k, eps, PRECISIONS[precision], chunk_entities, _ptr(ws), nbytes, _ptr(scores),
+                                       _ptr(best), _stream(dev)))
+    return LinkResult(scores, best)
+
+
 class _TableState:
     """What a model keeps for its table form (per process: not part of the state dict)."""
 

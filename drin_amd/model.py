@@ -845,6 +845,7 @@ class Model(nn.Module):
         if self._prepared is not None:
             self._prepared.invalidate()
         self.__dict__.pop("_link_inv", None)                  # link's inverse row norms: the same rule for writes into `rows`
+        self.__dict__.pop("_link_edges_inv", None)            # and into the three tables of first_stage="edges"
         return self
 
     # ---- flat buckets (one all-reduce per step; train.py:55-56: one Adam launch) -------------------------
@@ -931,6 +932,7 @@ class Model(nn.Module):
         state = self.__dict__.copy()
         state["_index_watch"], state["_index_pool"], state["_index_status"] = [], [], {}
         state.pop("_link_inv", None)                          # (and link's norms cache holds the caller's `rows`)
+        state.pop("_link_edges_inv", None)
         return state
 
     # ---- candidate rows outside the entity tables (drin/data.py:87-93 raises IndexError) ------------------------------
@@ -1214,7 +1216,8 @@ class Model(nn.Module):
 
     @torch.no_grad()
     def link(self, mention: Sequence[torch.Tensor], table: EntityTable, k: int, clip_image: torch.Tensor, clip_text: torch.Tensor, *,
-             candidates: Optional[torch.Tensor] = None, queries: Optional[torch.Tensor] = None, rows: Optional[torch.Tensor] = None):
+             candidates: Optional[torch.Tensor] = None, queries: Optional[torch.Tensor] = None, rows: Optional[torch.Tensor] = None,
+             first_stage: Optional[str] = None, edge_weights: Optional[Sequence[float]] = None):
         """DRIN as the second stage behind a first stage, against a device-resident table: the `k` best of
         `N = cfg.num_candidates_model` candidate rows per mention by the model's own score - `LinkResult(scores [B, k], rows [B, k])`,
         table rows, ordered by the contract of include/drin_hip.h (higher score first, the lower row between equal scores, between
@@ -1226,14 +1229,32 @@ class Model(nn.Module):
         the `rows` tensor, which the model keeps a reference to until another one is given).  ALL `N` slots are candidates: in linking there is no answer slot (the reference's loss and metric drop the last
         column, common/utils.py:36-37), so none is dropped.  Then `IndexedBatch.from_clip` forms the two CLIP edges, the model's
         own forward scores the batch on whatever route it takes (the per-entity cache when the table has it enabled) and
-        `drin_rank_rows` orders each mention's list.  `eval()` only, no gradient, GPU only."""
+        `drin_rank_rows` orders each mention's list.  `eval()` only, no gradient, GPU only.
+
+        `first_stage="edges"` (`candidates`, `queries` and `rows` all None): DRIN lists its own candidates,
+        the `N` best rows of the table by the sum of three of its four layer-0 edges (`drin_table_topk_sum`, the model's
+        precision, N <= 256) - `tt`: `span_mean(mention_text, start, end)` against the rows the table-form forward takes the
+        text-text edge from (the token-0 copy of `table.pooled_text` for a token-level table, the text rows of a pooled one);
+        `ti`: `clip_text` against `table.clip_image`; `it`: `clip_image` against `table.clip_text`.  The image-image edge is not a
+        term.  `edge_weights`: three floats (default `cfg.gcn_edge_enabled[0:3]`); a zero drops its term, whose tensors are then
+        not read; all three zero is refused.  The inverse row norms of the three tables are cached per tensor version (the rule
+        of `rows` above; `invalidate()` drops them).  A mention with an EMPTY span has a NaN `tt` row: all its first-stage scores
+        are NaN and its candidates are rows `0 .. N-1` by the contract - it is not treated specially."""
         from .ghmfc_table import LinkResult, row_inv_norms, table_topk
         if self.training:
             raise RuntimeError("Model.link: ranking is eval() only (no gradient flows through a top-k): call .eval()")
-        first_stage = queries is not None or rows is not None
-        if first_stage == (candidates is not None):
+        if first_stage is not None:
+            if first_stage != "edges":
+                raise ValueError(f"Model.link: first_stage = {first_stage!r} is not None or 'edges'")
+            if candidates is not None or queries is not None or rows is not None:
+                raise ValueError("Model.link: first_stage='edges' conflicts with `candidates` / `queries` / `rows`: it lists its own "
+                                 "candidates from the table - pass none of them")
+        elif edge_weights is not None:
+            raise ValueError("Model.link: `edge_weights` goes with first_stage='edges'")
+        edges, cosine_stage = first_stage is not None, queries is not None or rows is not None   # section 33's stage, section 32's
+        if not edges and cosine_stage == (candidates is not None):
             raise ValueError("Model.link: give exactly one first stage - `candidates` [B, N], or `queries` [B, Dq] with `rows` [E, Dq]")
-        if first_stage and (queries is None or rows is None):
+        if cosine_stage and (queries is None or rows is None):
             raise ValueError("Model.link: `queries` [B, Dq] and `rows` [E, Dq] go together")
         N, k = self.cfg.num_candidates_model, int(k)
         if candidates is not None and (candidates.dim() != 2 or candidates.shape[1] != N):
@@ -1242,7 +1263,9 @@ class Model(nn.Module):
             raise ValueError(f"Model.link: k = {k} is not in [1, N = {N}]")
         if table.clip_text is None or table.clip_image is None:
             raise ValueError("Model.link: the table has no CLIP rows: call table.set_clip(clip_text, clip_image)")
-        if first_stage:
+        if edges:
+            candidates = self._edge_candidates(mention, table, clip_image, clip_text, edge_weights)
+        if cosine_stage:
             if N > _lib.TOPK_MAX_K:
                 raise ValueError(f"Model.link: a cosine first stage lists at most {_lib.TOPK_MAX_K} rows and N = {N}: pass `candidates`")
             if (queries.dim() != 2 or rows.dim() != 2 or queries.shape[1] != rows.shape[1] or rows.shape[0] != table.num_entities
@@ -1291,6 +1314,64 @@ class Model(nn.Module):
             _lib.check(lib.drin_rank_rows(_ptr(scores[sl]), _ptr(candidates[sl]), sl.stop - b0, N, k, _ptr(out_scores[sl]),
                                           _ptr(out_rows[sl]), None, stream))
         return LinkResult(out_scores, out_rows)
+
+    def _edge_candidates(self, mention, table: EntityTable, clip_image, clip_text, edge_weights) -> torch.Tensor:
+        """`candidates [B, N]` of `link(first_stage="edges")`: the N best table rows by the weighted sum of the tt, ti and it
+        cosines (`table_topk_sum`); the checks of that mode."""
+        from . import row_ops
+        from .ghmfc_table import row_inv_norms, table_topk_sum
+        weights = self.cfg.gcn_edge_enabled[0:3] if edge_weights is None else tuple(edge_weights)
+        if len(weights) != 3:
+            raise ValueError(f"Model.link: edge_weights has {len(weights)} entries, expected 3 (tt, ti, it)")
+        weights = tuple(float(w) for w in weights)
+        if all(w == 0.0 for w in weights):
+            raise ValueError("Model.link: first_stage='edges' with all three edge weights zero ranks nothing")
+        if len(mention) != 7:
+            raise ValueError("Model.link: mention must be the first 7 tensors of the 14-sequence (drin/data.py:110-117)")
+        N = self.cfg.num_candidates_model                               # (link() has refused a table without CLIP rows)
+        if N > _lib.TOPK_MAX_K:
+            raise ValueError(f"Model.link: a cosine first stage lists at most {_lib.TOPK_MAX_K} rows and N = {N}: pass `candidates`")
+        if N > table.num_entities:
+            raise ValueError(f"Model.link: N = {N} candidates exceed the table's {table.num_entities} entities")
+        mtf, start, end = mention[0], mention[2], mention[3]
+        B, C = mtf.shape[0], table.clip_text.shape[1]
+        for name, t in (("clip_image", clip_image), ("clip_text", clip_text)):
+            if not torch.is_tensor(t) or t.dtype != torch.float32 or tuple(t.shape) != (B, C):
+                raise ValueError(f"Model.link: {name} must be float32 [{B}, {C}] (got {getattr(t, 'dtype', None)} "
+                                 f"{tuple(getattr(t, 'shape', ()))})")
+        if weights[0] != 0.0 and (table.text.dtype != torch.float32 or mtf.dtype != torch.float32):   # tt's tensors, when tt is a term
+            raise NotImplementedError("Model.link: first_stage='edges' reads float32 mention and table text (bf16-stored rows are not built)")
+        dev = table.text.device
+        if dev.type != "cuda" or any(t.device != dev for t in (mtf, start, end, clip_image, clip_text, table.clip_text, table.clip_image)):
+            raise RuntimeError("Model.link runs on an AMD GPU only (no CPU / eager fallback); move the batch and the table to 'cuda'")
+        if B == 0:
+            return torch.empty(0, N, dtype=torch.int64, device=dev)
+        eps = self.cfg.cosine_eps
+        # (query, table rows) per edge, in edge order; a dropped term's tensors are not touched - not even the token-0 copy is made
+        sources = ((lambda: row_ops.span_mean(mtf, start, end), lambda: table.pooled_text(self.cfg)[1] if table.text.dim() == 3 else table.text),
+                   (lambda: clip_text, lambda: table.clip_image),
+                   (lambda: clip_image, lambda: table.clip_text))
+        # the inverse norms per version of the table's tensor, under _link_inv's rule: the entry keeps the tensor (and the dense
+        # rows the norms were taken of) alive, so an equal address means the same storage
+        cache = self.__dict__.setdefault("_link_edges_inv", {})
+        terms = []
+        for s, (w, (query, rows_of)) in enumerate(zip(weights, sources)):
+            if w == 0.0:
+                terms.append((None, None, None, 0.0))
+                continue
+            given = rows_of()
+            key = (given.data_ptr(), given._version, tuple(given.shape), tuple(given.stride()), eps)
+            entry = cache.get(s)
+            if entry is None or entry[0] != key:
+                cache[s] = entry = None                                   # release the stale copy before allocating
+                dense = given.detach().contiguous()
+                cache[s] = entry = (key, row_inv_norms(dense, eps), given, dense)
+            terms.append((query().detach().contiguous(), entry[3], entry[1], w))
+        precision = "f32" if self.precision == _lib.PREC_F32 else "bf16x3"
+        step = self.MAX_CALL_MENTIONS
+        parts = [table_topk_sum([(None if x is None else x[b0:b0 + step], r, i, w) for x, r, i, w in terms], N, eps, precision).rows
+                 for b0 in range(0, B, step)]
+        return parts[0] if len(parts) == 1 else torch.cat(parts, 0)
 
     def wait_for_parameters(self) -> None:
         """Make the current stream wait for an optimiser update `train.OverlappedStep` left running on its side stream (no-op

@@ -1075,6 +1075,57 @@ DRIN_API int drin_table_topk(const float* x, const float* rows, const float* row
                              int32_t width, int32_t k, float cosine_eps, int32_t precision, int64_t chunk_entities, void* workspace,
                              size_t workspace_bytes, float* out_scores, int64_t* out_rows, void* stream);
 
+/* ---- a SUM of cosines against the tables ------------------------------------------------------------ *
+ * score(b, e) = sum_s weight_s * cos(x_s[b, :], rows_s[e, :]) over 1 .. DRIN_TOPK_MAX_TERMS (query, table) pairs that share
+ * batch and num_entities but not their width: late-fusion retrieval, and DRIN's own layer-0 evidence for a pair (the text-text
+ * edge of model.py:71-76 and the two CLIP edges of model.py:203, without the image-image edge).  THE ORDERING CONTRACT above
+ * applies. */
+#define DRIN_TOPK_MAX_TERMS 4
+typedef struct drin_topk_term { /* one cosine of the sum */
+  const float* x;             /* [batch, width] */
+  const float* rows;          /* [num_entities, width], contiguous */
+  const float* row_inv_norms; /* drin_row_inv_norms(rows, cosine_eps) */
+  int32_t width;              /* % 4 == 0 */
+  float weight;               /* finite; 0 = the term is dropped before any launch and its pointers may be NULL */
+} drin_topk_term;
+
+/* The combine alone, on caller-supplied blocks of dot products (entity-major, as drin_topk_update reads them):
+ *   out[c * ld + b] = sum_s blocks[s][c * ld + b] * col_inv_norms[s][c] * (row_scales[s][b] * weights[s])
+ * in term order, every multiply and add rounded to fp32 on its own (no contraction).  blocks, col_inv_norms, row_scales: HOST
+ * arrays of num_terms device pointers - blocks[s] [cols, ld], col_inv_norms[s] [cols], row_scales[s] [ld] (all ld entries are
+ * read) - and weights a HOST array of num_terms finite floats.  out [cols, ld] may be blocks[0].  One launch, a pure stream
+ * over num_terms blocks in and one out.  blocks, row_scales and out are 16-byte aligned; ld % 4 == 0, ld >= batch rounded up to
+ * a multiple of 4; cols >= 1; batch 1 .. 65535.  `batch` only bounds ld from below: ALL ld columns of every row are combined,
+ * the padding columns included (drin_topk_update then reads the first `batch` of them).  Writes out, nothing else.  Profiler
+ * class DRIN_KC_EDGE. */
+DRIN_API int drin_topk_combine(const float* const* blocks, const float* const* col_inv_norms, const float* const* row_scales,
+                               const float* weights, int32_t num_terms, int64_t ld, int32_t batch, int64_t cols, float* out,
+                               void* stream);
+
+/* Bytes of workspace for drin_table_topk_sum; 0 on error (drin_last_error).  Reads the widths and the weights of `terms` only;
+ * a term of weight 0 takes no room.  chunk_entities = 0: the default chunk, a multiple of 256 rows whose live blocks of dot
+ * products TOGETHER stay within 256 MiB. */
+DRIN_API size_t drin_table_topk_sum_workspace_bytes(const drin_topk_term* terms, int32_t num_terms, int32_t batch, int64_t num_entities,
+                                                    int32_t k, int64_t chunk_entities);
+
+/* out_rows [batch, k] (int64) = the k best rows by the summed score for each mention, out_scores [batch, k] their scores,
+ * ordered by the contract.  `terms`: a HOST array of num_terms (1 .. 4) terms, at least one with a weight != 0.  Every x_s is
+ * padded to Bp rows in the workspace and gets a per-mention factor weight_s / max(|x_s[b]|, cosine_eps) - unlike
+ * drin_table_topk, the mention norms differ per term and do change the ranking.  Per chunk of chunk_entities rows: one product
+ * per live term into that term's block[chunk, Bp] (`precision`: DRIN_PREC_BF16X3 or DRIN_PREC_F32, the kernel is the GEMM
+ * module's choice), ONE combine of the blocks into the scores (drin_topk_combine's sum), then the selection of
+ * drin_topk_update.  After the last chunk the kp selected rows are scored again: c_s = the bits drin_cosine_rows_indexed_fwd
+ * gives for (x_s, rows_s, row), then acc = w_0 * c_0; acc = acc + w_s * c_s over the live terms in order, every multiply and
+ * add rounded to fp32 on its own - out_scores ARE that chain's bits; the products' precision only decides which rows reach the
+ * list of kp.  With ONE term of weight 1 the scores of a row are drin_table_topk's bits, but the selection key carries one more
+ * fp32 factor (the mention's), so two keys that differ there may round to a tie here - broken by the lower row - and a key may
+ * overflow for a mention whose norm is at cosine_eps: which rows reach the list of kp can differ from drin_table_topk's at
+ * that boundary; the two calls agree up to such ties, not by construction.  k, batch and precision as drin_table_topk; every live width % 4 == 0; x, rows and row_inv_norms of a live term
+ * 16-byte aligned.  Writes out_scores, out_rows and the workspace, nothing else.  Profiler class DRIN_KC_EDGE. */
+DRIN_API int drin_table_topk_sum(const drin_topk_term* terms, int32_t num_terms, int64_t num_entities, int32_t batch, int32_t k,
+                                 float cosine_eps, int32_t precision, int64_t chunk_entities, void* workspace, size_t workspace_bytes,
+                                 float* out_scores, int64_t* out_rows, void* stream);
+
 /* ---- DRIN behind a first stage: CLIP edges for run-time candidates and a rerank ---------------- *
  * The two CLIP edges of drin_batch (miet_similarity, mtei_similarity) for candidates that were chosen at run time, from stored
  * CLIP embeddings: replaces preprocess/clip.py:158-172, which computes CLIPModel's logits_per_image / logits_per_text offline

@@ -315,6 +315,21 @@ EXPORTS = {
     #  scale, eps, miet, mtei, index_status, stream), (scores, rows, batch, n, k, out_scores, out_rows, out_slots, stream)
     "drin_cross_modal_edges": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
                                          C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # the same against table rows stored as row_dtype (FEAT_F32 | FEAT_BF16): the old argument lists with
+    # row_dtype behind the rows (the cross-modal edges: behind the two tables; the sum: a host int32 array behind `terms`), the
+    # two workspace queries with (row_dtype | row_dtypes, ..., precision)
+    "drin_row_inv_norms_ex": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_float, C.c_void_p, C.c_void_p]),
+    "drin_cosine_rows_indexed_fwd_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32,
+                                                  C.c_int32, C.c_float, C.c_void_p, C.c_void_p]),
+    "drin_cross_modal_edges_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32,
+                                            C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "drin_table_topk_workspace_bytes_ex": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32]),
+    "drin_table_topk_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_float,
+                                     C.c_int32, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "drin_table_topk_sum_workspace_bytes_ex": (C.c_size_t, [C.POINTER(DrinTopkTermC), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int64,
+                                                            C.c_int32, C.c_int64, C.c_int32]),
+    "drin_table_topk_sum_ex": (C.c_int, [C.POINTER(DrinTopkTermC), C.POINTER(C.c_int32), C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_float,
+                                         C.c_int32, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "drin_rank_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "drin_ghmfc_mention_forward_workspace_bytes": (C.c_size_t, [C.POINTER(DrinGhmfcConfigC)]),
     "drin_ghmfc_mention_forward": (C.c_int, [C.POINTER(DrinGhmfcConfigC), C.POINTER(DrinGhmfcBatchC), C.POINTER(DrinGhmfcParamsC), C.c_void_p,

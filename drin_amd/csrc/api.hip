@@ -1677,6 +1677,23 @@ int drin_host_selftest(void) {
     DRIN_TRY(table_topk_sum_layout_selfcheck(edges, 3, 4096, 1000000, 100, 512));
     for (int k : {1, 100, 256}) DRIN_TRY(table_topk_sum_layout_selfcheck(four, 4, 9, 70000, k, 0));
     DRIN_TRY(table_topk_sum_layout_selfcheck(four, 4, kMaxGridY, 1000000, 256, 0));
+    // bf16-stored rows: the planes of the plane route, the widened chunk of the widen route - tiny (width 16:
+    // widen in either precision), the reference widths, E = 1 M at B = 4096; one term fp32 among bf16 ones; default and explicit chunks
+    const int all_bf16[] = {DRIN_FEAT_BF16, DRIN_FEAT_BF16, DRIN_FEAT_BF16, DRIN_FEAT_BF16}, mixed[] = {DRIN_FEAT_BF16, DRIN_FEAT_F32, DRIN_FEAT_BF16};
+    const int tiny8[] = {16, 8, 8}, wide[] = {32, 16, 16};
+    for (int prec : {DRIN_PREC_F32, DRIN_PREC_BF16X3}) {
+      for (int64_t chunk : {(int64_t)0, (int64_t)64}) {
+        for (int k : {1, 100, 256}) DRIN_TRY(table_topk_layout_selfcheck(3, 300, 16, k, chunk, DRIN_FEAT_BF16, prec));
+        DRIN_TRY(table_topk_layout_selfcheck(5, 1500, 32, 64, chunk, DRIN_FEAT_BF16, prec));
+        DRIN_TRY(table_topk_sum_layout_selfcheck(tiny8, 3, 3, 300, 20, chunk, all_bf16, prec));
+        DRIN_TRY(table_topk_sum_layout_selfcheck(wide, 3, 3, 300, 20, chunk, mixed, prec));
+      }
+      DRIN_TRY(table_topk_layout_selfcheck(64, 65536, 768, 100, 0, DRIN_FEAT_BF16, prec));
+      DRIN_TRY(table_topk_layout_selfcheck(4096, 1000000, 768, 100, 0, DRIN_FEAT_BF16, prec));
+      DRIN_TRY(table_topk_layout_selfcheck(4096, 1000000, 776, 100, 0, DRIN_FEAT_BF16, prec));
+      DRIN_TRY(table_topk_sum_layout_selfcheck(edges, 3, 4096, 1000000, 100, 0, all_bf16, prec));
+      DRIN_TRY(table_topk_sum_layout_selfcheck(edges, 3, 4096, 1000000, 100, 512, mixed, prec));
+    }
   }
   // (5) for_grid_slices (internal.h), the launch loop of every sliced launcher: contiguous slices of at most kMaxGridY that cover
   //     [0, count) exactly, none for an empty count; a failing slice ends the walk and its status comes back

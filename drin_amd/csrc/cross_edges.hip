@@ -3,7 +3,8 @@
 //   mtei[b, n] = scale * cos(m_clip_text[b, :],  t_clip_image[index[b, n], :])
 // - what preprocess/clip.py:158-172 computes offline per pair as CLIPModel's logits_per_image / logits_per_text, exp(logit_scale) x
 // the cosine of the projected embeddings (model.py:203 divides by that scale again).
-//   k_cross_modal_edges<V, EDGES>   a gather of EDGES table rows per pair, shaped for that: a wave takes `per_wave` CONSECUTIVE
+//   k_cross_modal_edges<V, EDGES, RowT>   (RowT: the table rows as stored, float or __bf16 - drin_cross_modal_edges_ex, section 34)
+//                                   a gather of EDGES table rows per pair, shaped for that: a wave takes `per_wave` CONSECUTIVE
 //                                   candidates of ONE mention, 4 / EDGES of them per trip (four table rows in flight per wave);
 //                                   it holds the mention's rows (V float4 slots per lane and row) and their squared norms in
 //                                   registers across its candidates, reads its candidates' indices once, for both edges, and
@@ -18,9 +19,13 @@
 namespace drin {
 namespace {
 
+// RowT: how the TABLE rows are stored - float, or __bf16 (an 8-byte lane load of four bf16, widened exactly
+// by ld4, in the same column mapping - so the sums, their order and the bits are those of the float instantiation on the widened
+// table).  The mention rows stay fp32.
+template <typename RowT>
 struct CrossEdgeArgs {
   const float* x[2];      // mention rows [B, D] of edge 0 / 1 (one edge alone: slot 0)
-  const float* rows[2];   // table rows [E, D] of the same edge
+  const RowT* rows[2];    // table rows [E, D] of the same edge
   float* out[2];          // [B, N]
   const int64_t* index;   // [B, N]
   int64_t num_rows;
@@ -41,8 +46,8 @@ __device__ __forceinline__ int64_t readlane64(int64_t v, int src) {
 
 // V > 0: a row is V float4 slots per lane (D4 <= 64 V).  V = 0: any width - the mention rows are read again beside every trip's
 // table rows, column slot by column slot (the same sums in the same order).  grid (ceil(N / (4 per_wave)), B).
-template <int V, int EDGES>
-__global__ void __launch_bounds__(256) k_cross_modal_edges(CrossEdgeArgs a) {
+template <int V, int EDGES, typename RowT>
+__global__ void __launch_bounds__(256) k_cross_modal_edges(CrossEdgeArgs<RowT> a) {
   constexpr int K = kEdgeRowsInFlight / EDGES;   // candidates per trip
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -82,7 +87,7 @@ __global__ void __launch_bounds__(256) k_cross_modal_edges(CrossEdgeArgs a) {
     }
   }
   for (int t = 0; t < count; t += K) {
-    const float* yr[K][EDGES];
+    const RowT* yr[K][EDGES];
     bool live[K];
 #pragma unroll
     for (int k = 0; k < K; ++k) {
@@ -151,10 +156,11 @@ __global__ void __launch_bounds__(256) k_cross_modal_edges(CrossEdgeArgs a) {
   }
 }
 
-template <int EDGES>
+template <int EDGES, typename RowT>
 auto cross_edges_kernel(int D4) {
   const int slots = (D4 + 63) / 64;
-  return slots <= 1 ? k_cross_modal_edges<1, EDGES> : slots <= kEdgeMaxSlots ? k_cross_modal_edges<2, EDGES> : k_cross_modal_edges<0, EDGES>;
+  return slots <= 1 ? k_cross_modal_edges<1, EDGES, RowT>
+                    : slots <= kEdgeMaxSlots ? k_cross_modal_edges<2, EDGES, RowT> : k_cross_modal_edges<0, EDGES, RowT>;
 }
 
 // Candidates per wave: as many trips as leave every CU its sixteen waves (a short call stays one trip per wave - the mention
@@ -166,40 +172,48 @@ int cross_edges_per_wave(int B, int N, int trip) {
   return per_wave;
 }
 
-}  // namespace
-
-int launch_cross_modal_edges(const float* m_image, const float* m_text, const float* t_text, const float* t_image, const int64_t* index,
-                             int64_t num_rows, int B, int N, int D, float scale, float eps, float* miet, float* mtei, int32_t* status,
-                             hipStream_t st) {
+template <typename RowT>
+int launch_cross_modal_edges_t(const float* m_image, const float* m_text, const RowT* t_text, const RowT* t_image, const int64_t* index,
+                               int64_t num_rows, int B, int N, int D, float scale, float eps, float* miet, float* mtei, int32_t* status,
+                               hipStream_t st) {
   if (B <= 0 || N <= 0) return DRIN_OK;
-  CrossEdgeArgs a = {};
+  CrossEdgeArgs<RowT> a = {};
   int edges = 0;
   if (miet != nullptr) a.x[edges] = m_image, a.rows[edges] = t_text, a.out[edges] = miet, ++edges;
   if (mtei != nullptr) a.x[edges] = m_text, a.rows[edges] = t_image, a.out[edges] = mtei, ++edges;
   if (edges == 0) return DRIN_OK;
   a.index = index, a.num_rows = num_rows, a.N = N, a.D4 = D / 4, a.scale = scale, a.eps = eps, a.status = status;
   a.per_wave = cross_edges_per_wave(B, N, kEdgeRowsInFlight / edges);
-  auto kern = edges == 2 ? cross_edges_kernel<2>(a.D4) : cross_edges_kernel<1>(a.D4);
+  auto kern = edges == 2 ? cross_edges_kernel<2, RowT>(a.D4) : cross_edges_kernel<1, RowT>(a.D4);
+  const char* name = sizeof(RowT) == 2 ? "k_cross_modal_edges_bf16" : "k_cross_modal_edges";
   // (column groups of 4 waves, mention): B <= kMaxGridY is the entry point's bound, so one slice - the loop is the pair kernels'
   return for_grid_slices(B, [&](int64_t b0, int nb) -> int {
-    CrossEdgeArgs s = a;
+    CrossEdgeArgs<RowT> s = a;
     for (int e = 0; e < edges; ++e) s.x[e] += b0 * (int64_t)D, s.out[e] += b0 * (int64_t)N;
     s.index += b0 * (int64_t)N, s.pair_base = b0 * (int64_t)N;
-    return timed(DRIN_KC_EDGE, st, "k_cross_modal_edges", [&] {
+    return timed(DRIN_KC_EDGE, st, name, [&] {
       hipLaunchKernelGGL(kern, dim3((unsigned)cdiv(N, 4 * a.per_wave), (unsigned)nb), dim3(256), 0, st, s);
     });
   });
+}
+
+}  // namespace
+
+int launch_cross_modal_edges(const float* m_image, const float* m_text, const float* t_text, const float* t_image, const int64_t* index,
+                             int64_t num_rows, int B, int N, int D, float scale, float eps, float* miet, float* mtei, int32_t* status,
+                             hipStream_t st) {
+  return launch_cross_modal_edges_t<float>(m_image, m_text, t_text, t_image, index, num_rows, B, N, D, scale, eps, miet, mtei, status, st);
 }
 
 }  // namespace drin
 
 using namespace drin;
 
-int drin_cross_modal_edges(const float* mention_clip_image, const float* mention_clip_text, const float* table_clip_text,
-                           const float* table_clip_image, const int64_t* index, int64_t num_entities, int32_t batch,
-                           int32_t num_candidates, int32_t width, float scale, float eps, float* miet, float* mtei,
-                           int32_t* index_status, void* stream) {
-  const char* who = "drin_cross_modal_edges";
+// the checks and the launch of both spellings: `who` names the one that was called
+static int cross_modal_edges(const char* who, const float* mention_clip_image, const float* mention_clip_text, const void* table_clip_text,
+                             const void* table_clip_image, int row_dtype, const int64_t* index, int64_t num_entities, int32_t batch,
+                             int32_t num_candidates, int32_t width, float scale, float eps, float* miet, float* mtei, int32_t* index_status,
+                             void* stream) {
   // an edge is its mention rows, its table rows and its output: all three, or none of them
   const bool has_miet = mention_clip_image || table_clip_text || miet, has_mtei = mention_clip_text || table_clip_image || mtei;
   if (!has_miet && !has_mtei) {
@@ -223,11 +237,33 @@ int drin_cross_modal_edges(const float* mention_clip_image, const float* mention
     return DRIN_E_ALIGN;
   }
   DRIN_TRY(check_count(who, "num_entities", num_entities, 1, INT64_MAX / 4096));
+  DRIN_TRY(check_row_dtype(who, row_dtype, width));
   DRIN_TRY(check_width4(who, width));
   DRIN_TRY(check_count(who, "batch", batch, 1, kMaxGridY));
   DRIN_TRY(check_count(who, "num_candidates", num_candidates, 1, kMaxGridY));
   DRIN_TRY(check_count(who, "batch * num_candidates", (int64_t)batch * num_candidates, 1, INT32_MAX));
   DRIN_BIND_DEVICE(stream, miet ? miet : mtei, who);
-  return launch_cross_modal_edges(mention_clip_image, mention_clip_text, table_clip_text, table_clip_image, index, num_entities, batch,
-                                  num_candidates, width, scale, eps, miet, mtei, index_status, (hipStream_t)stream);
+  if (row_dtype == DRIN_FEAT_BF16)
+    return launch_cross_modal_edges_t<__bf16>(mention_clip_image, mention_clip_text, static_cast<const __bf16*>(table_clip_text),
+                                              static_cast<const __bf16*>(table_clip_image), index, num_entities, batch, num_candidates, width,
+                                              scale, eps, miet, mtei, index_status, (hipStream_t)stream);
+  return launch_cross_modal_edges(mention_clip_image, mention_clip_text, static_cast<const float*>(table_clip_text),
+                                  static_cast<const float*>(table_clip_image), index, num_entities, batch, num_candidates, width, scale, eps,
+                                  miet, mtei, index_status, (hipStream_t)stream);
+}
+
+int drin_cross_modal_edges(const float* mention_clip_image, const float* mention_clip_text, const float* table_clip_text,
+                           const float* table_clip_image, const int64_t* index, int64_t num_entities, int32_t batch,
+                           int32_t num_candidates, int32_t width, float scale, float eps, float* miet, float* mtei,
+                           int32_t* index_status, void* stream) {
+  return cross_modal_edges("drin_cross_modal_edges", mention_clip_image, mention_clip_text, table_clip_text, table_clip_image, DRIN_FEAT_F32,
+                           index, num_entities, batch, num_candidates, width, scale, eps, miet, mtei, index_status, stream);
+}
+
+int drin_cross_modal_edges_ex(const float* mention_clip_image, const float* mention_clip_text, const void* table_clip_text,
+                              const void* table_clip_image, int32_t row_dtype, const int64_t* index, int64_t num_entities, int32_t batch,
+                              int32_t num_candidates, int32_t width, float scale, float eps, float* miet, float* mtei,
+                              int32_t* index_status, void* stream) {
+  return cross_modal_edges("drin_cross_modal_edges_ex", mention_clip_image, mention_clip_text, table_clip_text, table_clip_image, row_dtype,
+                           index, num_entities, batch, num_candidates, width, scale, eps, miet, mtei, index_status, stream);
 }

@@ -117,6 +117,14 @@ struct NtProduct {
   const void *w_hi = nullptr, *w_lo = nullptr;   // optional pre-split bf16 planes of w (launch_split_planes_batch), row stride w.ld
   bool accumulate = false;                       // y += ... instead of y = ...
   const int64_t* x_index = nullptr;              // row m of x is row x_index[m] of a table (split-bf16 kernels only)
+  // The row-side operand STORED as bf16 (a bf16 entity table, read in place): x_bf16 addresses [rows][x.ld]
+  // bf16 and x.p is NULL.  launch_gemm_nt takes one of two routes (nt_bf16_rows_as_planes, scratch_sizes.h).  PLANES: split-bf16
+  // precision, k_red % 32 == 0, x.ld % 8 == 0, 16-byte aligned, w_hi / w_lo given - the rows ARE the hi plane of
+  // launch_gemm_x3_planes with no lo plane (exact in bf16: two MFMAs per tile pair), their bytes read once, as stored.  WIDEN:
+  // anything else - the rows are widened exactly into x_widen (rows k_red floats; DRIN_E_WORKSPACE without it) and the product
+  // runs on them as it would on fp32 rows: the same kernel on the same values.  No bias, no accumulate, no x_index.
+  const void* x_bf16 = nullptr;
+  GemmScratch x_widen;
   // the same product on the planes a workspace holds: n_out k_red bf16 of hi, then as many of lo (NULL: none)
   NtProduct with_planes(const float* hi_then_lo) const {
     NtProduct q = *this;

@@ -567,6 +567,27 @@ int launch_gemm_nt(const NtProduct& p, int precision, hipStream_t st, GemmScratc
   const int64_t ldx = p.x.ld, ldw = p.w.ld, ldy = p.ldy, M = p.rows;
   const int N = p.n_out, K = p.k_red;
   const bool accumulate = p.accumulate;
+  if (p.x_bf16 != nullptr) {   // the row-side operand stored as bf16: the plane route or the widen route (gemm.h)
+    if (accumulate || bias != nullptr || p.x_index != nullptr || x != nullptr) {
+      set_error("gemm_nt: rows stored as bf16 take no bias, no accumulate, no index and no fp32 x beside them");
+      return DRIN_E_UNSUPPORTED;
+    }
+    if (nt_bf16_rows_as_planes(precision, K, ldx) && p.w_hi != nullptr && p.w_lo != nullptr && (ldw % 8) == 0 && aligned16(p.x_bf16) &&
+        aligned16(p.w_hi) && aligned16(p.w_lo))
+      return launch_gemm_x3_planes(p.x_bf16, nullptr, ldx, p.w_hi, p.w_lo, ldw, nullptr, y, ldy, M, N, K, st, splitk);
+    if (ldx != K || (K % 4) || !aligned16(p.x_bf16)) {
+      set_error("gemm_nt: bf16-stored rows are widened as one contiguous block (ld = K = %d, a multiple of 4, 16-byte aligned)", K);
+      return DRIN_E_SHAPE;
+    }
+    if (p.x_widen.p == nullptr || p.x_widen.floats < (size_t)M * (size_t)K || !aligned16(p.x_widen.p)) {
+      set_error("gemm_nt: bf16-stored rows outside the plane kernel's contract need %zu floats of x_widen", (size_t)M * (size_t)K);
+      return DRIN_E_WORKSPACE;
+    }
+    DRIN_TRY(launch_widen_rows(p.x_bf16, p.x_widen.p, M * (int64_t)K, st));
+    NtProduct q = p;   // today's product on the widened rows, unchanged: what an fp32 table of the same values runs
+    q.x_bf16 = nullptr, q.x_widen = {}, q.x = {p.x_widen.p, K}, q.w_hi = q.w_lo = nullptr;
+    return launch_gemm_nt(q, precision, st, splitk);
+  }
   // split-bf16 contraction for the pair-sized GEMMs; the mention-sized ones (a few hundred rows) stay on
   // the exact fp32 kernel: they are latency-bound, not rate-bound
   // (the 256-row threshold measured again in round 2, same box, 16 / 64 rows instead: a 64-mention scoring call 0.551 -> 0.576 ms,

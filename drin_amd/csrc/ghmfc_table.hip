@@ -31,8 +31,11 @@ __global__ void __launch_bounds__(256) k_gather_rows(const float* __restrict__ t
 }
 
 // k_cosine_rows (stream_kernels.hip) with y = a clamped row of a table: the same lane loop, wave sums and cosine_from_sums,
-// so the bits of k_cosine_rows on the gathered rows (its scale is 1 there).
-__global__ void __launch_bounds__(256) k_cosine_gather(const float* __restrict__ x, const float* __restrict__ rows,
+// so the bits of k_cosine_rows on the gathered rows (its scale is 1 there).  RowT: how the table rows are STORED - float, or
+// __bf16 (8 bytes per lane and column quad, widened exactly by ld4: the same values in the same sums, so the bits of the float
+// instantiation on the widened table).  x stays fp32.
+template <typename RowT>
+__global__ void __launch_bounds__(256) k_cosine_gather(const float* __restrict__ x, const RowT* __restrict__ rows,
                                                        const int64_t* __restrict__ index, int64_t num_rows, float* __restrict__ out,
                                                        int64_t pairs, int N, int D4, float eps, int32_t* status, int64_t pair_base) {
   int64_t p, b;
@@ -42,7 +45,7 @@ __global__ void __launch_bounds__(256) k_cosine_gather(const float* __restrict__
   const int64_t e = clamp_row(raw, num_rows);
   if (e != raw && lane == 0) report_bad_index(status, pair_base + p, raw);
   const float* xr = x + b * (int64_t)D4 * 4;
-  const float* yr = rows + e * (int64_t)D4 * 4;
+  const RowT* yr = rows + e * (int64_t)D4 * 4;
   float xy = 0.f, xx = 0.f, yy = 0.f;
   for (int c4 = lane; c4 < D4; c4 += 64) {
     const float4 a = ld4(xr + c4 * 4), b = ld4(yr + c4 * 4);
@@ -86,8 +89,18 @@ int launch_cosine_gather(const float* x, const float* rows, const int64_t* index
   const int64_t pairs = (int64_t)B * N;
   if (pairs <= 0) return DRIN_OK;
   return timed(DRIN_KC_EDGE, st, "k_cosine_gather", [&] {
-    hipLaunchKernelGGL(k_cosine_gather, pair_grid(B, N), dim3(256), 0, st, x, rows, index, num_rows, out, pairs, N, D / 4, eps, status,
+    hipLaunchKernelGGL(k_cosine_gather<float>, pair_grid(B, N), dim3(256), 0, st, x, rows, index, num_rows, out, pairs, N, D / 4, eps, status,
                        pair_base);
+  });
+}
+
+int launch_cosine_gather_bf16(const float* x, const void* rows, const int64_t* index, int64_t num_rows, float* out, int B, int N, int D,
+                              float eps, int32_t* status, int64_t pair_base, hipStream_t st) {
+  const int64_t pairs = (int64_t)B * N;
+  if (pairs <= 0) return DRIN_OK;
+  return timed(DRIN_KC_EDGE, st, "k_cosine_gather_bf16", [&] {
+    hipLaunchKernelGGL(k_cosine_gather<__bf16>, pair_grid(B, N), dim3(256), 0, st, x, static_cast<const __bf16*>(rows), index, num_rows, out,
+                       pairs, N, D / 4, eps, status, pair_base);
   });
 }
 
@@ -141,20 +154,38 @@ int drin_entity_token_pool_indexed(const float* text, const int64_t* mask, const
                                           (hipStream_t)stream);
 }
 
-int drin_cosine_rows_indexed_fwd(const float* x, const float* rows, const int64_t* index, int64_t num_entities, float* out,
-                                 int32_t batch, int32_t num_candidates, int32_t width, float eps, int32_t* index_status, void* stream) {
-  const char* who = "drin_cosine_rows_indexed_fwd";
+// the checks and the launch of both spellings: `who` names the one that was called
+static int cosine_rows_indexed(const char* who, const float* x, const void* rows, int row_dtype, const int64_t* index, int64_t num_entities,
+                               float* out, int32_t batch, int32_t num_candidates, int32_t width, float eps, int32_t* index_status,
+                               void* stream) {
   DRIN_CHECK_POINTERS(who, {"x", x, true}, {"rows", rows, true});
   if (!out) {
     set_error("%s: out is NULL", who);
     return DRIN_E_NULL;
   }
   DRIN_TRY(check_table_args(who, index, num_entities, index_status));
+  DRIN_TRY(check_row_dtype(who, row_dtype, width));
   DRIN_TRY(check_width4(who, width));
   DRIN_TRY(check_count(who, "batch", batch, 1, INT32_MAX));
   DRIN_TRY(check_count(who, "num_candidates", num_candidates, 1, kMaxGridY));
   DRIN_TRY(check_count(who, "batch * num_candidates", (int64_t)batch * num_candidates, 1, INT32_MAX));
   DRIN_BIND_DEVICE(stream, out, who);
-  return launch_cosine_gather(x, rows, index, num_entities, out, batch, num_candidates, width, eps, index_status, 0,
+  if (row_dtype == DRIN_FEAT_BF16)
+    return launch_cosine_gather_bf16(x, rows, index, num_entities, out, batch, num_candidates, width, eps, index_status, 0,
+                                     (hipStream_t)stream);
+  return launch_cosine_gather(x, static_cast<const float*>(rows), index, num_entities, out, batch, num_candidates, width, eps, index_status, 0,
                               (hipStream_t)stream);
+}
+
+int drin_cosine_rows_indexed_fwd(const float* x, const float* rows, const int64_t* index, int64_t num_entities, float* out,
+                                 int32_t batch, int32_t num_candidates, int32_t width, float eps, int32_t* index_status, void* stream) {
+  return cosine_rows_indexed("drin_cosine_rows_indexed_fwd", x, rows, DRIN_FEAT_F32, index, num_entities, out, batch, num_candidates, width,
+                             eps, index_status, stream);
+}
+
+int drin_cosine_rows_indexed_fwd_ex(const float* x, const void* rows, int32_t row_dtype, const int64_t* index, int64_t num_entities,
+                                    float* out, int32_t batch, int32_t num_candidates, int32_t width, float eps, int32_t* index_status,
+                                    void* stream) {
+  return cosine_rows_indexed("drin_cosine_rows_indexed_fwd_ex", x, rows, row_dtype, index, num_entities, out, batch, num_candidates, width,
+                             eps, index_status, stream);
 }

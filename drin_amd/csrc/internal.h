@@ -173,6 +173,11 @@ int launch_gather_rows(const float* table, const int64_t* index, int64_t num_row
 // out[b * N + n] = cos(x[b, :], rows[index[b * N + n], :]): k_cosine_rows' lane loop on a clamped row
 int launch_cosine_gather(const float* x, const float* rows, const int64_t* index, int64_t num_rows, float* out, int B, int N, int D,
                          float eps, int32_t* status, int64_t pair_base, hipStream_t st);
+// the same against rows STORED as bf16 (widened exactly, lane by lane: the bits of the fp32 launcher on the widened table)
+int launch_cosine_gather_bf16(const float* x, const void* rows, const int64_t* index, int64_t num_rows, float* out, int B, int N, int D,
+                              float eps, int32_t* status, int64_t pair_base, hipStream_t st);
+// out[i] = (float)rows_bf16[i], n % 4 == 0, both 16-byte aligned: the widen route of an NT product on bf16-stored rows (gemm.h)
+int launch_widen_rows(const void* rows_bf16, float* out, int64_t n, hipStream_t st);
 // out[b*N + n] = scale * cos(x[b, :], y[(b*N + n) * y_stride : +D])
 // (sim1 / sim2 -> out1 / out2: optional [B*N] arrays divided by `div` in the same pass: the CLIP edges of model.py:203)
 int launch_cosine_rows(const float* x, const float* y, int64_t y_stride, float* out, int B, int N, int D, float eps,
@@ -321,8 +326,11 @@ int ghmfc_layout_selfcheck(int B, int N, int D, int R, int L, int P, int T);   /
 // buffer of drin_ghmfc_entity_rows for E entities
 int ghmfc_table_layout_selfcheck(int B, int N, int D, int R, int L, int P, int T, bool rows, int64_t E);
 // TopkLayout (table_topk.hip): the workspace of drin_table_topk, and the rules of its kp, chunk and slice count
-int table_topk_layout_selfcheck(int B, int64_t E, int D, int k, int64_t chunk_entities);
+// (row_dtype DRIN_FEAT_BF16 with the product's precision: the planes / widen region of section 34 as well)
+int table_topk_layout_selfcheck(int B, int64_t E, int D, int k, int64_t chunk_entities, int row_dtype = DRIN_FEAT_F32,
+                                int precision = DRIN_PREC_F32);
 // TopkSumLayout (table_topk.hip): the workspace of drin_table_topk_sum for S live terms of the given widths
-int table_topk_sum_layout_selfcheck(const int* widths, int S, int B, int64_t E, int k, int64_t chunk_entities);
+int table_topk_sum_layout_selfcheck(const int* widths, int S, int B, int64_t E, int k, int64_t chunk_entities, const int* dtypes = nullptr,
+                                    int precision = DRIN_PREC_F32);
 
 }  // namespace drin

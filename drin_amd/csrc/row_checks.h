@@ -43,5 +43,18 @@ inline int check_width4(const char* who, int E) {
   }
   return DRIN_OK;
 }
+// how the table rows of a link entry point are stored (the *_ex twins): DRIN_FEAT_F32, or DRIN_FEAT_BF16 - 8-byte lane loads of
+// four bf16 and 16-byte aligned rows, so width % 8 == 0.  Anything else: DRIN_E_UNSUPPORTED.
+inline int check_row_dtype(const char* who, int row_dtype, int width) {
+  if (row_dtype != DRIN_FEAT_F32 && row_dtype != DRIN_FEAT_BF16) {
+    set_error("%s: row dtype %d is not DRIN_FEAT_F32 / DRIN_FEAT_BF16", who, row_dtype);
+    return DRIN_E_UNSUPPORTED;
+  }
+  if (row_dtype == DRIN_FEAT_BF16 && (width <= 0 || width % 8)) {
+    set_error("%s: width %d of bf16-stored rows must be a positive multiple of 8 (16-byte aligned rows)", who, width);
+    return DRIN_E_SHAPE;
+  }
+  return DRIN_OK;
+}
 
 }  // namespace drin

@@ -57,6 +57,10 @@ inline bool nt_takes_bf16x3(int precision, int64_t rows) {
 }
 // pre-split (hi, lo) weight planes stream by LDS-DMA in K-blocks of 32
 inline bool nt_planes_width(int K) { return (K % 32) == 0; }
+// an NT product whose row-side operand is STORED as bf16 (NtProduct::x_bf16; row stride ldx elements, reduction K): it runs on the
+// stored rows as the hi plane of the plane kernel, else on a widened copy.  The layouts that carve the planes of the other operand
+// or the widened chunk (table_topk.hip) ask here, as launch_gemm_nt does.
+inline bool nt_bf16_rows_as_planes(int precision, int K, int64_t ldx) { return split_bf16(precision) && nt_planes_width(K) && (ldx % 8) == 0; }
 // "this call's NT weights run as planes": the pair-sized products (pair_rows rows, reductions D and R) of a split-bf16 call
 inline bool nt_weights_as_planes(int precision, int64_t pair_rows, int D, int R) {
   return split_bf16(precision) && pair_rows >= kBf16x3MinRows && nt_planes_width(D) && nt_planes_width(R);

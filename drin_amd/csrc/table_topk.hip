@@ -8,9 +8,12 @@
 //   k_topk_merge      per mention: the running list and the slice lists -> the new running list of kp (key, row), sorted
 //   k_topk_finish     per mention: sort kp (score, row) by the contract, write the first k
 //   k_pad_rows        x [B, D] -> [round4(B), D], zero rows behind
+//   k_widen_rows      bf16 rows -> the same values as fp32 (a chunk of a bf16-stored table on the widen route)
 //   k_rank_rows       per mention: the first k of n caller-given (score, row) pairs by the contract, with the input column of each
 //                     (drin_rank_rows: the rerank behind a second-stage scoring)
-// and the entry points drin_row_inv_norms, drin_topk_update, drin_table_topk(_workspace_bytes), drin_rank_rows.  The block of dot products is
+// and the entry points drin_row_inv_norms, drin_topk_update, drin_table_topk(_workspace_bytes), drin_rank_rows, with the _ex twins that
+// read table rows STORED as bf16 in place (section 34: k_row_inv_norms<__bf16>, the product routed by the GEMM module, the re-score
+// k_cosine_gather<__bf16>).  The block of dot products is
 // ENTITY-major, as the product y[Ec, Bp] = rows_chunk x^T leaves it: element (mention b, column c) at block[c * ld + b].
 // No atomics, no scratch memory; a workgroup of the three selection kernels is ONE wave, so its barriers order that wave's LDS
 // traffic and wait for nobody.
@@ -52,11 +55,13 @@ __device__ __forceinline__ uint64_t shfl64(uint64_t v, int src) {
 }
 
 // One wave per row, four rows per workgroup, the rest by grid stride: k_cosine_gather's lane loop and wave sum of its yy.
-__global__ void __launch_bounds__(256) k_row_inv_norms(const float* __restrict__ rows, int64_t num_rows, int D4, float eps,
+// RowT: float, or __bf16 for rows stored as bf16 (widened exactly by ld4: the bits of the float instantiation on the widened rows).
+template <typename RowT>
+__global__ void __launch_bounds__(256) k_row_inv_norms(const RowT* __restrict__ rows, int64_t num_rows, int D4, float eps,
                                                        float* __restrict__ out) {
   const int lane = threadIdx.x & 63;
   for (int64_t e = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); e < num_rows; e += (int64_t)gridDim.x * 4) {
-    const float* yr = rows + e * (int64_t)D4 * 4;
+    const RowT* yr = rows + e * (int64_t)D4 * 4;
     float yy = 0.f;
     for (int c4 = lane; c4 < D4; c4 += 64) {
       const float4 b = ld4(yr + c4 * 4);
@@ -65,6 +70,12 @@ __global__ void __launch_bounds__(256) k_row_inv_norms(const float* __restrict__
     yy = wave_sum(yy);
     if (lane == 0) out[e] = 1.0f / fmaxf(sqrtf(yy), eps);
   }
+}
+
+// out [n4 quads] = the bf16 values of in, widened exactly (a 16-bit shift): the chunk of a bf16-stored table that a product outside
+// the plane kernel's contract reads as fp32 (the widen route of launch_gemm_nt).  8 bytes in, 16 out per lane.
+__global__ void __launch_bounds__(256) k_widen_rows(const __bf16* __restrict__ in, float* __restrict__ out, int64_t n4) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) st4(out + i * 4, ld4(in + i * 4));
 }
 
 __global__ void __launch_bounds__(256) k_pad_rows(const float* __restrict__ x, float* __restrict__ out, int64_t n4_in, int64_t n4_out) {
@@ -404,22 +415,53 @@ int launch_rank_rows(const float* scores, const int64_t* rows, int batch, int n,
 int launch_row_inv_norms(const float* rows, int64_t num_rows, int width, float eps, float* out, hipStream_t st) {
   const int64_t blocks = row_blocks(num_rows);
   return timed(DRIN_KC_EDGE, st, "k_row_inv_norms", [&] {
-    hipLaunchKernelGGL(k_row_inv_norms, dim3((unsigned)blocks), dim3(256), 0, st, rows, num_rows, width / 4, eps, out);
+    hipLaunchKernelGGL(k_row_inv_norms<float>, dim3((unsigned)blocks), dim3(256), 0, st, rows, num_rows, width / 4, eps, out);
   });
+}
+int launch_row_inv_norms_bf16(const void* rows, int64_t num_rows, int width, float eps, float* out, hipStream_t st) {
+  const int64_t blocks = row_blocks(num_rows);
+  return timed(DRIN_KC_EDGE, st, "k_row_inv_norms_bf16", [&] {
+    hipLaunchKernelGGL(k_row_inv_norms<__bf16>, dim3((unsigned)blocks), dim3(256), 0, st, static_cast<const __bf16*>(rows), num_rows, width / 4,
+                       eps, out);
+  });
+}
+// the re-score of a list against rows of either storage
+int launch_cosine_gather_any(const float* x, const void* rows, int row_dtype, const int64_t* index, int64_t num_rows, float* out, int B, int N,
+                             int D, float eps, hipStream_t st) {
+  if (row_dtype == DRIN_FEAT_BF16) return launch_cosine_gather_bf16(x, rows, index, num_rows, out, B, N, D, eps, nullptr, 0, st);
+  return launch_cosine_gather(x, static_cast<const float*>(rows), index, num_rows, out, B, N, D, eps, nullptr, 0, st);
+}
+// the product block[n, Bp] = rows_chunk xpad^T of one chunk: fp32 rows as ever; bf16-stored rows declared as such, with the planes of
+// xpad and the widen region the layout carved - the GEMM module picks the route (gemm.h: NtProduct::x_bf16)
+int launch_chunk_product(const void* rows, int row_dtype, int64_t e0, int64_t n, int D, const float* xpad, const float* planes, float* widen,
+                         size_t widen_floats, float* block, int Bp, int precision, hipStream_t st) {
+  if (row_dtype != DRIN_FEAT_BF16)
+    return launch_gemm_nt({{static_cast<const float*>(rows) + e0 * D, D}, {xpad, D}, nullptr, block, Bp, n, Bp, D}, precision, st);
+  NtProduct p{{nullptr, D}, {xpad, D}, nullptr, block, Bp, n, Bp, D};
+  p.x_bf16 = static_cast<const uint16_t*>(rows) + e0 * D;
+  p.x_widen = scratch_at(widen, 0, widen_floats);
+  return launch_gemm_nt(p.with_planes(planes), precision, st);
 }
 
 // ---- the workspace of drin_table_topk: sized and carved from this one description -------------------------------------
+// bf16-stored rows add ONE region per product route: `planes` - the hi / lo bf16 planes of xpad, Bp D bf16
+// each, split once per call - where the GEMM module runs the table as the hi plane of launch_gemm_x3_planes
+// (nt_bf16_rows_as_planes), else `widen` - one chunk of the table as fp32.  The default chunk of the widen route also keeps that
+// region inside the budget.
 struct TopkLayout {
-  size_t xpad, block, keys, rows, slices, scores, total_floats;   // offsets in floats
+  size_t xpad, block, keys, rows, slices, scores, planes, widen, total_floats;   // offsets in floats
+  size_t planes_floats, widen_floats;
   int64_t chunk, num_slices;
   int kp, Bp;
   // false: a region does not fit in size_t / the chunk is out of range
-  bool build(int batch, int64_t E, int D, int k, int64_t chunk_entities) {
+  bool build(int batch, int64_t E, int D, int k, int64_t chunk_entities, int row_dtype = DRIN_FEAT_F32, int precision = DRIN_PREC_F32) {
     kp = DRIN_TOPK_KP(k), Bp = (batch + 3) & ~3;
+    const bool bf16 = row_dtype == DRIN_FEAT_BF16, as_planes = bf16 && nt_bf16_rows_as_planes(precision, D, D);
     if (chunk_entities > 0) {
       chunk = chunk_entities;
-    } else {   // a multiple of 256 rows whose block stays inside the budget (at least 256)
-      chunk = kBlockBudgetBytes / ((int64_t)Bp * 4) / 256 * 256;
+    } else {   // a multiple of 256 rows whose block - and widened copy - stays inside the budget (at least 256)
+      const int64_t row_bytes = (int64_t)4 * (bf16 && !as_planes && D > Bp ? D : Bp);
+      chunk = kBlockBudgetBytes / row_bytes / 256 * 256;
       chunk = chunk < 256 ? 256 : chunk;
     }
     chunk = chunk < E ? chunk : E;
@@ -427,7 +469,7 @@ struct TopkLayout {
     num_slices = slices_of(chunk);
     const size_t limit = SIZE_MAX / 64;   // of floats: the sum of six regions and the byte count stay representable
     auto fits = [&](size_t a, size_t b) { return a == 0 || b <= limit / a; };
-    if (!fits((size_t)chunk, (size_t)Bp) || !fits((size_t)num_slices * 2, (size_t)batch * kp)) return false;
+    if (!fits((size_t)chunk, (size_t)Bp) || !fits((size_t)num_slices * 2, (size_t)batch * kp) || !fits((size_t)chunk, (size_t)D)) return false;
     Arena A;
     xpad = A.take((size_t)Bp * D);
     block = A.take((size_t)chunk * Bp);
@@ -435,6 +477,9 @@ struct TopkLayout {
     rows = A.take((size_t)batch * kp * 2);
     slices = A.take((size_t)num_slices * batch * kp * 2);
     scores = A.take((size_t)batch * kp);
+    planes_floats = as_planes ? (size_t)Bp * D : 0, widen_floats = bf16 && !as_planes ? (size_t)chunk * D : 0;
+    planes = A.take(planes_floats);   // (fp32 rows: two empty regions behind the old ones - the old offsets and the old total)
+    widen = A.take(widen_floats);
     total_floats = A.total;
     return true;
   }
@@ -487,9 +532,11 @@ int launch_weighted_cosine_sum(const float* cos, int S, int64_t n, const ChainWe
 struct LiveTerms {
   drin_topk_term term[DRIN_TOPK_MAX_TERMS];
   int widths[DRIN_TOPK_MAX_TERMS];
+  int dtypes[DRIN_TOPK_MAX_TERMS];   // how term s stores its rows (row_dtypes of the *_ex twins; DRIN_FEAT_F32 without them)
   int S = 0;
 };
-int live_terms(const char* who, const drin_topk_term* terms, int num_terms, bool pointers, LiveTerms* out) {
+// row_dtypes: HOST array [num_terms] or NULL (all fp32); a dropped term's entry is not read
+int live_terms(const char* who, const drin_topk_term* terms, int num_terms, bool pointers, LiveTerms* out, const int32_t* row_dtypes = nullptr) {
   if (!terms) {
     set_error("%s: terms is NULL", who);
     return DRIN_E_NULL;
@@ -506,6 +553,8 @@ int live_terms(const char* who, const drin_topk_term* terms, int num_terms, bool
       set_error("%s: term %d: width %d must be a positive multiple of 4 (16-byte lane accesses)", who, s, t.width);
       return DRIN_E_SHAPE;
     }
+    const int dtype = row_dtypes != nullptr ? row_dtypes[s] : DRIN_FEAT_F32;
+    DRIN_TRY(check_row_dtype(who, dtype, t.width));
     if (pointers) {
       const NamedPtr ptrs[] = {{"x", t.x, true}, {"rows", t.rows, true}, {"row_inv_norms", t.row_inv_norms, true}};
       for (const NamedPtr& p : ptrs) {
@@ -520,6 +569,7 @@ int live_terms(const char* who, const drin_topk_term* terms, int num_terms, bool
       }
     }
     out->widths[out->S] = t.width;
+    out->dtypes[out->S] = dtype;
     out->term[out->S++] = t;
   }
   if (out->S == 0) {
@@ -531,17 +581,29 @@ int live_terms(const char* who, const drin_topk_term* terms, int num_terms, bool
 
 // the workspace of drin_table_topk_sum: per live term the padded mentions, their factors and one block of dot products (block 0
 // takes the combined scores), the S x [batch, kp] re-scored cosines, and the selection's regions as TopkLayout has them
+// bf16-stored terms (dtypes; NULL: none): per term on the plane route its planes of xpad; ONE widen region, as wide as the widest
+// term on the widen route - the terms' products run one after the other.
 struct TopkSumLayout {
   size_t xpad[DRIN_TOPK_MAX_TERMS], scale[DRIN_TOPK_MAX_TERMS], block[DRIN_TOPK_MAX_TERMS];   // offsets in floats
-  size_t cos, keys, rows, slices, scores, total_floats;
+  size_t planes[DRIN_TOPK_MAX_TERMS], planes_floats[DRIN_TOPK_MAX_TERMS];
+  size_t cos, keys, rows, slices, scores, widen, widen_floats, total_floats;
   int64_t chunk, num_slices;
   int kp, Bp, S;
-  bool build(const int* widths, int terms, int batch, int64_t E, int k, int64_t chunk_entities) {
+  bool build(const int* widths, int terms, int batch, int64_t E, int k, int64_t chunk_entities, const int* dtypes = nullptr,
+             int precision = DRIN_PREC_F32) {
     kp = DRIN_TOPK_KP(k), Bp = (batch + 3) & ~3, S = terms;
+    int widen_width = 0;   // the widest term that takes the widen route
+    for (int s = 0; s < S; ++s) {
+      const bool bf16 = dtypes != nullptr && dtypes[s] == DRIN_FEAT_BF16;
+      const bool as_planes = bf16 && nt_bf16_rows_as_planes(precision, widths[s], widths[s]);
+      planes_floats[s] = as_planes ? (size_t)Bp * widths[s] : 0;
+      if (bf16 && !as_planes && widths[s] > widen_width) widen_width = widths[s];
+    }
     if (chunk_entities > 0) {
       chunk = chunk_entities;
-    } else {   // a multiple of 256 rows whose S blocks together stay inside the budget (at least 256)
-      chunk = kBlockBudgetBytes / ((int64_t)S * Bp * 4) / 256 * 256;
+    } else {   // a multiple of 256 rows whose S blocks together - and the widened copy - stay inside the budget (at least 256)
+      const int64_t row_bytes = (int64_t)4 * (widen_width > (int64_t)S * Bp ? widen_width : (int64_t)S * Bp);
+      chunk = kBlockBudgetBytes / row_bytes / 256 * 256;
       chunk = chunk < 256 ? 256 : chunk;
     }
     chunk = chunk < E ? chunk : E;
@@ -549,7 +611,8 @@ struct TopkSumLayout {
     num_slices = slices_of(chunk);
     const size_t limit = SIZE_MAX / 256;   // of floats: the sum of all regions and the byte count stay representable
     auto fits = [&](size_t a, size_t b) { return a == 0 || b <= limit / a; };
-    if (!fits((size_t)chunk * S, (size_t)Bp) || !fits((size_t)num_slices * 2, (size_t)batch * kp)) return false;
+    if (!fits((size_t)chunk * S, (size_t)Bp) || !fits((size_t)num_slices * 2, (size_t)batch * kp) || !fits((size_t)chunk, (size_t)widen_width))
+      return false;
     Arena A;
     for (int s = 0; s < S; ++s) {
       xpad[s] = A.take((size_t)Bp * widths[s]);
@@ -561,6 +624,9 @@ struct TopkSumLayout {
     rows = A.take((size_t)batch * kp * 2);
     slices = A.take((size_t)num_slices * batch * kp * 2);
     scores = A.take((size_t)batch * kp);
+    for (int s = 0; s < S; ++s) planes[s] = A.take(planes_floats[s]);   // (fp32 terms: empty regions behind the old ones)
+    widen_floats = (size_t)chunk * widen_width;
+    widen = A.take(widen_floats);
     total_floats = A.total;
     return true;
   }
@@ -568,25 +634,40 @@ struct TopkSumLayout {
 
 }  // namespace
 
-int table_topk_sum_layout_selfcheck(const int* widths, int S, int batch, int64_t E, int k, int64_t chunk_entities) {
+int launch_widen_rows(const void* rows_bf16, float* out, int64_t n, hipStream_t st) {
+  if (n <= 0) return DRIN_OK;
+  const int64_t n4 = n / 4, blocks = cdiv(n4, 256) < 65536 ? cdiv(n4, 256) : 65536;   // past the cap a thread walks several quads
+  return timed(DRIN_KC_EDGE, st, "k_widen_rows", [&] {
+    hipLaunchKernelGGL(k_widen_rows, dim3((unsigned)blocks), dim3(256), 0, st, static_cast<const __bf16*>(rows_bf16), out, n4);
+  });
+}
+
+int table_topk_sum_layout_selfcheck(const int* widths, int S, int batch, int64_t E, int k, int64_t chunk_entities, const int* dtypes,
+                                    int precision) {
   TopkSumLayout W;
-  if (!W.build(widths, S, batch, E, k, chunk_entities)) {
+  if (!W.build(widths, S, batch, E, k, chunk_entities, dtypes, precision)) {
     set_error("selftest: TopkSumLayout does not build for S=%d B=%d E=%lld k=%d chunk=%lld", S, batch, (long long)E, k, (long long)chunk_entities);
     return DRIN_E_WORKSPACE;
   }
   const size_t B = batch, kp = W.kp;
   if (W.kp < k || W.kp > kMaxKp || (W.kp & (W.kp - 1)) || W.chunk < 1 || W.chunk > E || W.num_slices * kSlice < W.chunk ||
-      (chunk_entities == 0 && W.chunk != E && (W.chunk % 256 || (W.chunk > 256 && W.chunk * W.Bp * 4 * S > kBlockBudgetBytes)))) {
+      (chunk_entities == 0 && W.chunk != E &&
+       (W.chunk % 256 || (W.chunk > 256 && (W.chunk * W.Bp * 4 * S > kBlockBudgetBytes || (int64_t)W.widen_floats * 4 > kBlockBudgetBytes))))) {
     set_error("selftest: TopkSumLayout kp=%d chunk=%lld slices=%lld break their rules", W.kp, (long long)W.chunk, (long long)W.num_slices);
     return DRIN_E_WORKSPACE;
   }
-  Region ws[3 * DRIN_TOPK_MAX_TERMS + 5];
-  int n = 0;
+  Region ws[4 * DRIN_TOPK_MAX_TERMS + 6];
+  int n = 0, widest = 0;
   for (int s = 0; s < S; ++s) {
     ws[n++] = {"xpad", W.xpad[s], (size_t)W.Bp * widths[s]};
     ws[n++] = {"scale", W.scale[s], (size_t)W.Bp};
     ws[n++] = {"block", W.block[s], (size_t)W.chunk * W.Bp};
+    // what the routes index: hi + lo planes of xpad (2 bf16 = 1 float per element), or a widened chunk of the widest such term
+    const bool bf16 = dtypes != nullptr && dtypes[s] == DRIN_FEAT_BF16, as_planes = bf16 && nt_bf16_rows_as_planes(precision, widths[s], widths[s]);
+    ws[n++] = {"planes", W.planes[s], as_planes ? (size_t)W.Bp * widths[s] : 0};
+    if (bf16 && !as_planes && widths[s] > widest) widest = widths[s];
   }
+  ws[n++] = {"widen", W.widen, (size_t)W.chunk * widest};
   ws[n++] = {"cos", W.cos, (size_t)S * B * kp};
   ws[n++] = {"keys", W.keys, B * kp};
   ws[n++] = {"rows", W.rows, B * kp * 2};
@@ -595,22 +676,27 @@ int table_topk_sum_layout_selfcheck(const int* widths, int S, int batch, int64_t
   return regions_hold("TopkSumLayout", ws, n, W.total_floats);
 }
 
-int table_topk_layout_selfcheck(int batch, int64_t E, int D, int k, int64_t chunk_entities) {
+int table_topk_layout_selfcheck(int batch, int64_t E, int D, int k, int64_t chunk_entities, int row_dtype, int precision) {
   TopkLayout W;
-  if (!W.build(batch, E, D, k, chunk_entities)) {
+  if (!W.build(batch, E, D, k, chunk_entities, row_dtype, precision)) {
     set_error("selftest: TopkLayout does not build for B=%d E=%lld D=%d k=%d chunk=%lld", batch, (long long)E, D, k, (long long)chunk_entities);
     return DRIN_E_WORKSPACE;
   }
   const size_t B = batch, kp = W.kp;
   if (W.kp < k || W.kp > kMaxKp || (W.kp & (W.kp - 1)) || W.chunk < 1 || W.chunk > E || W.num_slices * kSlice < W.chunk ||
-      (chunk_entities == 0 && W.chunk != E && (W.chunk % 256 || (W.chunk > 256 && W.chunk * W.Bp * 4 > kBlockBudgetBytes)))) {
+      (chunk_entities == 0 && W.chunk != E &&
+       (W.chunk % 256 || (W.chunk > 256 && (W.chunk * W.Bp * 4 > kBlockBudgetBytes || (int64_t)W.widen_floats * 4 > kBlockBudgetBytes))))) {
     set_error("selftest: TopkLayout kp=%d chunk=%lld slices=%lld break their rules", W.kp, (long long)W.chunk, (long long)W.num_slices);
     return DRIN_E_WORKSPACE;
   }
   // what the launches index: the padded mentions, one block of dot products, the running list, every slice's list, the re-scores
+  // (bf16-stored rows: the hi + lo planes of xpad - 2 bf16 = 1 float per element - on the plane route, else one widened chunk)
+  const bool bf16 = row_dtype == DRIN_FEAT_BF16, as_planes = bf16 && nt_bf16_rows_as_planes(precision, D, D);
   const Region ws[] = {{"xpad", W.xpad, (size_t)W.Bp * D},   {"block", W.block, (size_t)W.chunk * W.Bp},
                        {"keys", W.keys, B * kp},             {"rows", W.rows, B * kp * 2},
-                       {"slices", W.slices, (size_t)cdiv(W.chunk, kSlice) * B * kp * 2}, {"scores", W.scores, B * kp}};
+                       {"slices", W.slices, (size_t)cdiv(W.chunk, kSlice) * B * kp * 2}, {"scores", W.scores, B * kp},
+                       {"planes", W.planes, as_planes ? (size_t)W.Bp * D : 0},
+                       {"widen", W.widen, bf16 && !as_planes ? (size_t)W.chunk * D : 0}};
   return regions_hold("TopkLayout", ws, (int)(sizeof(ws) / sizeof(ws[0])), W.total_floats);
 }
 
@@ -618,8 +704,10 @@ int table_topk_layout_selfcheck(int batch, int64_t E, int D, int k, int64_t chun
 
 using namespace drin;
 
-int drin_row_inv_norms(const float* rows, int64_t num_entities, int32_t width, float eps, float* out, void* stream) {
-  const char* who = "drin_row_inv_norms";
+// Each entry point below and its *_ex twin are ONE body: the twin adds how the table rows are stored, the old spelling is
+// DRIN_FEAT_F32 - the code it always ran, its bits.  `who` names the spelling that was called.
+static int row_inv_norms(const char* who, const void* rows, int row_dtype, int64_t num_entities, int32_t width, float eps, float* out,
+                         void* stream) {
   DRIN_CHECK_POINTERS(who, {"rows", rows, true});
   if (!out) {
     set_error("%s: out is NULL", who);
@@ -630,13 +718,21 @@ int drin_row_inv_norms(const float* rows, int64_t num_entities, int32_t width, f
     return DRIN_E_ALIGN;
   }
   DRIN_TRY(check_count(who, "num_entities", num_entities, 1, INT64_MAX / 4096));
+  DRIN_TRY(check_row_dtype(who, row_dtype, width));
   DRIN_TRY(check_width4(who, width));
   if (!(eps > 0.0f)) {
     set_error("%s: eps must be positive", who);
     return DRIN_E_SHAPE;
   }
   DRIN_BIND_DEVICE(stream, out, who);
-  return launch_row_inv_norms(rows, num_entities, width, eps, out, (hipStream_t)stream);
+  if (row_dtype == DRIN_FEAT_BF16) return launch_row_inv_norms_bf16(rows, num_entities, width, eps, out, (hipStream_t)stream);
+  return launch_row_inv_norms(static_cast<const float*>(rows), num_entities, width, eps, out, (hipStream_t)stream);
+}
+int drin_row_inv_norms(const float* rows, int64_t num_entities, int32_t width, float eps, float* out, void* stream) {
+  return row_inv_norms("drin_row_inv_norms", rows, DRIN_FEAT_F32, num_entities, width, eps, out, stream);
+}
+int drin_row_inv_norms_ex(const void* rows, int32_t row_dtype, int64_t num_entities, int32_t width, float eps, float* out, void* stream) {
+  return row_inv_norms("drin_row_inv_norms_ex", rows, row_dtype, num_entities, width, eps, out, stream);
 }
 
 int drin_topk_update(const float* block, int64_t ld, int32_t batch, int64_t cols, int64_t col_base, const float* col_inv_norms, int32_t k,
@@ -681,26 +777,34 @@ int drin_topk_update(const float* block, int64_t ld, int32_t batch, int64_t cols
   return DRIN_OK;
 }
 
-size_t drin_table_topk_workspace_bytes(int32_t batch, int64_t num_entities, int32_t width, int32_t k, int64_t chunk_entities) {
-  const char* who = "drin_table_topk_workspace_bytes";
+static size_t table_topk_workspace_bytes(const char* who, int32_t batch, int64_t num_entities, int32_t width, int32_t k, int64_t chunk_entities,
+                                         int row_dtype, int precision) {
   if (check_topk_shape(who, num_entities, batch, width, k) != DRIN_OK) return 0;
+  if (check_row_dtype(who, row_dtype, width) != DRIN_OK || check_precision_topk(who, precision) != DRIN_OK) return 0;
   if (chunk_entities < 0) {
     set_error("%s: chunk_entities = %lld is negative", who, (long long)chunk_entities);
     return 0;
   }
   TopkLayout W;
-  if (!W.build(batch, num_entities, width, k, chunk_entities)) {
+  if (!W.build(batch, num_entities, width, k, chunk_entities, row_dtype, precision)) {
     set_error("%s: chunk_entities = %lld is out of range (at most 2^30 rows, the workspace must fit in size_t)", who,
               (long long)chunk_entities);
     return 0;
   }
   return W.total_floats * sizeof(float);
 }
+size_t drin_table_topk_workspace_bytes(int32_t batch, int64_t num_entities, int32_t width, int32_t k, int64_t chunk_entities) {
+  return table_topk_workspace_bytes("drin_table_topk_workspace_bytes", batch, num_entities, width, k, chunk_entities, DRIN_FEAT_F32,
+                                    DRIN_PREC_F32);
+}
+size_t drin_table_topk_workspace_bytes_ex(int32_t batch, int64_t num_entities, int32_t width, int32_t k, int64_t chunk_entities,
+                                          int32_t row_dtype, int32_t precision) {
+  return table_topk_workspace_bytes("drin_table_topk_workspace_bytes_ex", batch, num_entities, width, k, chunk_entities, row_dtype, precision);
+}
 
-int drin_table_topk(const float* x, const float* rows, const float* row_inv_norms, int64_t num_entities, int32_t batch, int32_t width,
-                    int32_t k, float cosine_eps, int32_t precision, int64_t chunk_entities, void* workspace, size_t workspace_bytes,
-                    float* out_scores, int64_t* out_rows, void* stream) {
-  const char* who = "drin_table_topk";
+static int table_topk(const char* who, const float* x, const void* rows, int row_dtype, const float* row_inv_norms, int64_t num_entities,
+                      int32_t batch, int32_t width, int32_t k, float cosine_eps, int32_t precision, int64_t chunk_entities, void* workspace,
+                      size_t workspace_bytes, float* out_scores, int64_t* out_rows, void* stream) {
   DRIN_CHECK_POINTERS(who, {"x", x, true}, {"rows", rows, true}, {"row_inv_norms", row_inv_norms, true}, {"workspace", workspace, true});
   if (!out_scores || !out_rows) {
     set_error("%s: out_scores / out_rows is NULL", who);
@@ -711,13 +815,14 @@ int drin_table_topk(const float* x, const float* rows, const float* row_inv_norm
     return DRIN_E_ALIGN;
   }
   DRIN_TRY(check_topk_shape(who, num_entities, batch, width, k));
+  DRIN_TRY(check_row_dtype(who, row_dtype, width));
   DRIN_TRY(check_precision_topk(who, precision));
   if (chunk_entities < 0) {
     set_error("%s: chunk_entities = %lld is negative", who, (long long)chunk_entities);
     return DRIN_E_SHAPE;
   }
   TopkLayout W;
-  if (!W.build(batch, num_entities, width, k, chunk_entities)) {
+  if (!W.build(batch, num_entities, width, k, chunk_entities, row_dtype, precision)) {
     set_error("%s: chunk_entities = %lld is out of range (at most 2^30 rows, the workspace must fit in size_t)", who,
               (long long)chunk_entities);
     return DRIN_E_SHAPE;
@@ -731,6 +836,7 @@ int drin_table_topk(const float* x, const float* rows, const float* row_inv_norm
   hipStream_t st = (hipStream_t)stream;
   float* ws = static_cast<float*>(workspace);
   const int B = batch, D = width, kp = W.kp, Bp = W.Bp;
+  float* planes = W.planes_floats ? ws + W.planes : nullptr;
   float* xpad = ws + W.xpad;
   float* block = ws + W.block;
   float* keys = ws + W.keys;
@@ -741,17 +847,32 @@ int drin_table_topk(const float* x, const float* rows, const float* row_inv_norm
   DRIN_TRY(timed(DRIN_KC_EDGE, st, "k_pad_rows", [&] {
     hipLaunchKernelGGL(k_pad_rows, dim3((unsigned)(cdiv(n4_out, 256) < 4096 ? cdiv(n4_out, 256) : 4096)), dim3(256), 0, st, x, xpad, n4_in, n4_out);
   }));
+  // bf16-stored rows on the plane route: the padded mentions as hi / lo planes, split ONCE per call (hi: Bp D bf16, then lo)
+  if (planes != nullptr)
+    DRIN_TRY(launch_split_planes(xpad, planes, reinterpret_cast<uint16_t*>(planes) + (size_t)Bp * D, (int64_t)Bp * D, st));
   // per chunk of table rows: y[n, Bp] = rows_chunk x^T - the entities are the ROW side, so launch_gemm_nt routes every chunk by the
   // chunk's size, not by the batch's - then the selection on that block
   for (int64_t e0 = 0; e0 < num_entities; e0 += W.chunk) {
     const int64_t n = num_entities - e0 < W.chunk ? num_entities - e0 : W.chunk;
-    DRIN_TRY(launch_gemm_nt({{rows + e0 * D, D}, {xpad, D}, nullptr, block, Bp, n, Bp, D}, precision, st));
+    DRIN_TRY(launch_chunk_product(rows, row_dtype, e0, n, D, xpad, planes, ws + W.widen, W.widen_floats, block, Bp, precision, st));
     DRIN_TRY(launch_topk_update(block, Bp, B, n, e0, row_inv_norms + e0, kp, keys, list, slices, e0 == 0, st));
   }
-  // the kp selected rows of every mention, scored as drin_cosine_rows_indexed_fwd scores them (an empty entry, row -1, is clamped
-  // silently and stays last), ordered by the contract
-  DRIN_TRY(launch_cosine_gather(x, rows, list, num_entities, scores, B, kp, D, cosine_eps, nullptr, 0, st));
+  // the kp selected rows of every mention, scored as drin_cosine_rows_indexed_fwd(_ex) scores them (an empty entry, row -1, is
+  // clamped silently and stays last), ordered by the contract
+  DRIN_TRY(launch_cosine_gather_any(x, rows, row_dtype, list, num_entities, scores, B, kp, D, cosine_eps, st));
   return launch_topk_finish(scores, list, B, kp, k, out_scores, out_rows, st);
+}
+int drin_table_topk(const float* x, const float* rows, const float* row_inv_norms, int64_t num_entities, int32_t batch, int32_t width,
+                    int32_t k, float cosine_eps, int32_t precision, int64_t chunk_entities, void* workspace, size_t workspace_bytes,
+                    float* out_scores, int64_t* out_rows, void* stream) {
+  return table_topk("drin_table_topk", x, rows, DRIN_FEAT_F32, row_inv_norms, num_entities, batch, width, k, cosine_eps, precision,
+                    chunk_entities, workspace, workspace_bytes, out_scores, out_rows, stream);
+}
+int drin_table_topk_ex(const float* x, const void* rows, int32_t row_dtype, const float* row_inv_norms, int64_t num_entities, int32_t batch,
+                       int32_t width, int32_t k, float cosine_eps, int32_t precision, int64_t chunk_entities, void* workspace,
+                       size_t workspace_bytes, float* out_scores, int64_t* out_rows, void* stream) {
+  return table_topk("drin_table_topk_ex", x, rows, row_dtype, row_inv_norms, num_entities, batch, width, k, cosine_eps, precision,
+                    chunk_entities, workspace, workspace_bytes, out_scores, out_rows, stream);
 }
 
 int drin_topk_combine(const float* const* blocks, const float* const* col_inv_norms, const float* const* row_scales, const float* weights,
@@ -792,31 +913,43 @@ int drin_topk_combine(const float* const* blocks, const float* const* col_inv_no
   return launch_topk_combine(t, num_terms, out, ld, cols, (hipStream_t)stream);
 }
 
-size_t drin_table_topk_sum_workspace_bytes(const drin_topk_term* terms, int32_t num_terms, int32_t batch, int64_t num_entities, int32_t k,
-                                           int64_t chunk_entities) {
-  const char* who = "drin_table_topk_sum_workspace_bytes";
+static size_t table_topk_sum_workspace_bytes(const char* who, const drin_topk_term* terms, const int32_t* row_dtypes, int32_t num_terms,
+                                             int32_t batch, int64_t num_entities, int32_t k, int64_t chunk_entities, int precision) {
   LiveTerms live;
-  if (live_terms(who, terms, num_terms, false, &live) != DRIN_OK) return 0;
-  if (check_topk_shape(who, num_entities, batch, live.widths[0], k) != DRIN_OK) return 0;
+  if (live_terms(who, terms, num_terms, false, &live, row_dtypes) != DRIN_OK) return 0;
+  if (check_topk_shape(who, num_entities, batch, live.widths[0], k) != DRIN_OK || check_precision_topk(who, precision) != DRIN_OK) return 0;
   if (chunk_entities < 0) {
     set_error("%s: chunk_entities = %lld is negative", who, (long long)chunk_entities);
     return 0;
   }
   TopkSumLayout W;
-  if (!W.build(live.widths, live.S, batch, num_entities, k, chunk_entities)) {
+  if (!W.build(live.widths, live.S, batch, num_entities, k, chunk_entities, live.dtypes, precision)) {
     set_error("%s: chunk_entities = %lld is out of range (at most 2^30 rows, the workspace must fit in size_t)", who,
               (long long)chunk_entities);
     return 0;
   }
   return W.total_floats * sizeof(float);
 }
+size_t drin_table_topk_sum_workspace_bytes(const drin_topk_term* terms, int32_t num_terms, int32_t batch, int64_t num_entities, int32_t k,
+                                           int64_t chunk_entities) {
+  return table_topk_sum_workspace_bytes("drin_table_topk_sum_workspace_bytes", terms, nullptr, num_terms, batch, num_entities, k,
+                                        chunk_entities, DRIN_PREC_F32);
+}
+size_t drin_table_topk_sum_workspace_bytes_ex(const drin_topk_term* terms, const int32_t* row_dtypes, int32_t num_terms, int32_t batch,
+                                              int64_t num_entities, int32_t k, int64_t chunk_entities, int32_t precision) {
+  const char* who = "drin_table_topk_sum_workspace_bytes_ex";
+  if (!row_dtypes) {
+    set_error("%s: row_dtypes is NULL", who);
+    return 0;
+  }
+  return table_topk_sum_workspace_bytes(who, terms, row_dtypes, num_terms, batch, num_entities, k, chunk_entities, precision);
+}
 
-int drin_table_topk_sum(const drin_topk_term* terms, int32_t num_terms, int64_t num_entities, int32_t batch, int32_t k, float cosine_eps,
-                        int32_t precision, int64_t chunk_entities, void* workspace, size_t workspace_bytes, float* out_scores,
-                        int64_t* out_rows, void* stream) {
-  const char* who = "drin_table_topk_sum";
+static int table_topk_sum(const char* who, const drin_topk_term* terms, const int32_t* row_dtypes, int32_t num_terms, int64_t num_entities,
+                          int32_t batch, int32_t k, float cosine_eps, int32_t precision, int64_t chunk_entities, void* workspace,
+                          size_t workspace_bytes, float* out_scores, int64_t* out_rows, void* stream) {
   LiveTerms live;
-  DRIN_TRY(live_terms(who, terms, num_terms, true, &live));
+  DRIN_TRY(live_terms(who, terms, num_terms, true, &live, row_dtypes));
   DRIN_CHECK_POINTERS(who, {"workspace", workspace, true});
   if (!out_scores || !out_rows) {
     set_error("%s: out_scores / out_rows is NULL", who);
@@ -833,7 +966,7 @@ int drin_table_topk_sum(const drin_topk_term* terms, int32_t num_terms, int64_t 
     return DRIN_E_SHAPE;
   }
   TopkSumLayout W;
-  if (!W.build(live.widths, live.S, batch, num_entities, k, chunk_entities)) {
+  if (!W.build(live.widths, live.S, batch, num_entities, k, chunk_entities, live.dtypes, precision)) {
     set_error("%s: chunk_entities = %lld is out of range (at most 2^30 rows, the workspace must fit in size_t)", who,
               (long long)chunk_entities);
     return DRIN_E_SHAPE;
@@ -864,6 +997,9 @@ int drin_table_topk_sum(const drin_topk_term* terms, int32_t num_terms, int64_t 
       hipLaunchKernelGGL(k_pad_rows, dim3((unsigned)(cdiv(n4_out, 256) < 4096 ? cdiv(n4_out, 256) : 4096)), dim3(256), 0, st, t.x, xpad, n4_in, n4_out);
     }));
     DRIN_TRY(launch_row_inv_norms(xpad, Bp, t.width, cosine_eps, ws + W.scale[s], st));
+    if (W.planes_floats[s])   // a bf16-stored term on the plane route: its padded mentions as hi / lo planes, once per call
+      DRIN_TRY(launch_split_planes(xpad, ws + W.planes[s], reinterpret_cast<uint16_t*>(ws + W.planes[s]) + (size_t)Bp * t.width,
+                                   (int64_t)Bp * t.width, st));
     ct.block[s] = ws + W.block[s], ct.scale[s] = ws + W.scale[s], ct.weight[s] = t.weight, cw.w[s] = t.weight;
   }
   // per chunk of table rows: one product per live term into its own entity-major block (kernel choice: the GEMM module's, by the
@@ -873,7 +1009,8 @@ int drin_table_topk_sum(const drin_topk_term* terms, int32_t num_terms, int64_t 
     const int64_t n = num_entities - e0 < W.chunk ? num_entities - e0 : W.chunk;
     for (int s = 0; s < S; ++s) {
       const drin_topk_term& t = live.term[s];
-      DRIN_TRY(launch_gemm_nt({{t.rows + e0 * t.width, t.width}, {ws + W.xpad[s], t.width}, nullptr, ws + W.block[s], Bp, n, Bp, t.width}, precision, st));
+      DRIN_TRY(launch_chunk_product(t.rows, live.dtypes[s], e0, n, t.width, ws + W.xpad[s], W.planes_floats[s] ? ws + W.planes[s] : nullptr,
+                                    ws + W.widen, W.widen_floats, ws + W.block[s], Bp, precision, st));
       ct.inv[s] = t.row_inv_norms + e0;
     }
     DRIN_TRY(launch_topk_combine(ct, S, combined, Bp, n, st));
@@ -883,10 +1020,27 @@ int drin_table_topk_sum(const drin_topk_term* terms, int32_t num_terms, int64_t 
   // silently and stays last), the fp32 chain over the terms, and the order of the contract
   for (int s = 0; s < S; ++s) {
     const drin_topk_term& t = live.term[s];
-    DRIN_TRY(launch_cosine_gather(t.x, t.rows, list, num_entities, cos + (size_t)s * B * kp, B, kp, t.width, cosine_eps, nullptr, 0, st));
+    DRIN_TRY(launch_cosine_gather_any(t.x, t.rows, live.dtypes[s], list, num_entities, cos + (size_t)s * B * kp, B, kp, t.width, cosine_eps, st));
   }
   DRIN_TRY(launch_weighted_cosine_sum(cos, S, (int64_t)B * kp, cw, scores, st));
   return launch_topk_finish(scores, list, B, kp, k, out_scores, out_rows, st);
+}
+int drin_table_topk_sum(const drin_topk_term* terms, int32_t num_terms, int64_t num_entities, int32_t batch, int32_t k, float cosine_eps,
+                        int32_t precision, int64_t chunk_entities, void* workspace, size_t workspace_bytes, float* out_scores,
+                        int64_t* out_rows, void* stream) {
+  return table_topk_sum("drin_table_topk_sum", terms, nullptr, num_terms, num_entities, batch, k, cosine_eps, precision, chunk_entities,
+                        workspace, workspace_bytes, out_scores, out_rows, stream);
+}
+int drin_table_topk_sum_ex(const drin_topk_term* terms, const int32_t* row_dtypes, int32_t num_terms, int64_t num_entities, int32_t batch,
+                           int32_t k, float cosine_eps, int32_t precision, int64_t chunk_entities, void* workspace, size_t workspace_bytes,
+                           float* out_scores, int64_t* out_rows, void* stream) {
+  const char* who = "drin_table_topk_sum_ex";
+  if (!row_dtypes) {
+    set_error("%s: row_dtypes is NULL", who);
+    return DRIN_E_NULL;
+  }
+  return table_topk_sum(who, terms, row_dtypes, num_terms, num_entities, batch, k, cosine_eps, precision, chunk_entities, workspace,
+                        workspace_bytes, out_scores, out_rows, stream);
 }
 
 int drin_rank_rows(const float* scores, const int64_t* rows, int32_t batch, int32_t n, int32_t k, float* out_scores, int64_t* out_rows,

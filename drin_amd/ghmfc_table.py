@@ -15,7 +15,9 @@
 rows by cosine (`drin_table_topk` on the per-entity rows), scores with the bits of the cached table-form scoring.
 
 A row outside the table is clamped by the kernels and reported: `check_indices()` / `validate_indices` raise `IndexError`.
-GPU only, fp32 tables; the table is an input and gets no gradient.
+GPU only, fp32 tables; the table is an input and gets no gradient.  The link primitives of this module (`row_inv_norms`,
+`cosine_rows_indexed`, `table_topk`, `table_topk_sum`) also read `rows` STORED as bfloat16 in place - DRIN's
+`Model.link` uses that; GHMFC's own token tables stay fp32.
 """
 from __future__ import annotations
 
@@ -109,11 +111,33 @@ def pooled_candidates(table: EntityTable, index: torch.Tensor, status: Optional[
     return out
 
 
+def _row_dtype(who: str, rows: torch.Tensor) -> int:
+    """`FEAT_F32` / `FEAT_BF16` of table rows that a link primitive reads IN PLACE: contiguous float32, or
+    contiguous bfloat16 - widened exactly inside the kernels, never copied."""
+    if not torch.is_tensor(rows) or rows.dtype not in (torch.float32, torch.bfloat16) or not rows.is_contiguous():
+        raise ValueError(f"{who}: rows must be a contiguous float32 or bfloat16 tensor, read in place "
+                         f"(got {getattr(rows, 'dtype', type(rows).__name__)})")
+    return _lib.FEAT_BF16 if rows.dtype == torch.bfloat16 else _lib.FEAT_F32
+
+
+def _check_f32(who: str, name: str, t: torch.Tensor) -> None:
+    if not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous():
+        raise ValueError(f"{who}: {name} must be a contiguous float32 tensor (got {getattr(t, 'dtype', type(t).__name__)})")
+
+
 def cosine_rows_indexed(x: torch.Tensor, rows: torch.Tensor, index: torch.Tensor, eps: float,
                         status: Optional[torch.Tensor]) -> torch.Tensor:
-    """`[B, N]` = cos(x[b], rows[index[b, n]]) by `drin_cosine_rows_indexed_fwd`; no gradient."""
+    """`[B, N]` = cos(x[b], rows[index[b, n]]) by `drin_cosine_rows_indexed_fwd`; no gradient.  `rows`: float32, or bfloat16 read
+    in place (`drin_cosine_rows_indexed_fwd_ex`: the bits of the float32 call on `rows.float()`); `x` float32."""
     B, N = index.shape
     out = torch.empty(B, N, dtype=torch.float32, device=x.device)
+    if rows.dtype == torch.bfloat16:
+        x = x.detach().contiguous()
+        _check_f32("cosine_rows_indexed", "x", x)
+        _lib.check(_lib.load().drin_cosine_rows_indexed_fwd_ex(_ptr(x), _ptr(rows), _row_dtype("cosine_rows_indexed", rows), _ptr(index),
+                                                               rows.shape[0], _ptr(out), B, N, x.shape[1], eps, _ptr(status),
+                                                               _stream(x.device)))
+        return out
     _lib.check(_lib.load().drin_cosine_rows_indexed_fwd(_ptr(x.detach().contiguous()), _ptr(rows), _ptr(index), rows.shape[0], _ptr(out),
                                                         B, N, x.shape[1], eps, _ptr(status), _stream(x.device)))
     return out
@@ -127,17 +151,37 @@ class LinkResult(NamedTuple):
 
 
 def row_inv_norms(rows: torch.Tensor, eps: float) -> torch.Tensor:
-    """`[E]` = 1 / max(|rows[e]|, eps) by `drin_row_inv_norms`."""
+    """`[E]` float32 = 1 / max(|rows[e]|, eps) by `drin_row_inv_norms`; bfloat16 `rows` are read in place (`drin_row_inv_norms_ex`:
+    the bits of the float32 call on `rows.float()`)."""
     out = torch.empty(rows.shape[0], dtype=torch.float32, device=rows.device)
+    if rows.dtype == torch.bfloat16:
+        _lib.check(_lib.load().drin_row_inv_norms_ex(_ptr(rows), _row_dtype("row_inv_norms", rows), rows.shape[0], rows.shape[1], eps,
+                                                     _ptr(out), _stream(rows.device)))
+        return out
     _lib.check(_lib.load().drin_row_inv_norms(_ptr(rows), rows.shape[0], rows.shape[1], eps, _ptr(out), _stream(rows.device)))
     return out
 
 
 def table_topk(x: torch.Tensor, rows: torch.Tensor, inv_norms: torch.Tensor, k: int, eps: float, precision: str,
                chunk_entities: int = 0) -> LinkResult:
-    """The k best of `rows [E, D]` for every `x [B, D]` by cosine (`drin_table_topk`); `inv_norms`: `row_inv_norms(rows, eps)`."""
+    """The k best of `rows [E, D]` for every `x [B, D]` by cosine (`drin_table_topk`); `inv_norms`: `row_inv_norms(rows, eps)`.
+    bfloat16 `rows` are read in place (`drin_table_topk_ex`): they link exactly as `rows.float()` would; `x`
+    and `inv_norms` stay float32."""
     lib = _lib.load()
     (B, D), E = x.shape, rows.shape[0]
+    if rows.dtype == torch.bfloat16:
+        dtype = _row_dtype("table_topk", rows)
+        _check_f32("table_topk", "x", x)
+        _check_f32("table_topk", "inv_norms", inv_norms)
+        nbytes = lib.drin_table_topk_workspace_bytes_ex(B, E, D, k, chunk_entities, dtype, PRECISIONS[precision])
+        if nbytes == 0:
+            _lib.check(_lib.E_SHAPE)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        scores = torch.empty(B, k, dtype=torch.float32, device=x.device)
+        best = torch.empty(B, k, dtype=torch.int64, device=x.device)
+        _lib.check(lib.drin_table_topk_ex(_ptr(x), _ptr(rows), dtype, _ptr(inv_norms), E, B, D, k, eps, PRECISIONS[precision], chunk_entities,
+                                          _ptr(ws), nbytes, _ptr(scores), _ptr(best), _stream(x.device)))
+        return LinkResult(scores, best)
     nbytes = lib.drin_table_topk_workspace_bytes(B, E, D, k, chunk_entities)
     if nbytes == 0:
         _lib.check(_lib.E_SHAPE)
@@ -153,11 +197,13 @@ def table_topk_sum(terms: Sequence, k: int, eps: float, precision: str, chunk_en
     """The k best table rows for every mention by a SUM of cosines (`drin_table_topk_sum`):
     `score(b, e) = sum_s weight_s * cos(x_s[b], rows_s[e])`.  `terms`: 1 to 4 of `(x [B, D_s], rows [E, D_s], inv_norms [E],
     weight)` - contiguous float32 tensors on one GPU, `inv_norms = row_inv_norms(rows, eps)`; the terms share `B` and `E`, not
-    their width.  A term of weight 0 is dropped before any launch and its three tensors may be `None`.  The returned scores are
+    their width.  `rows` alone may be contiguous bfloat16 instead, term by term, read in place (`drin_table_topk_sum_ex`,
+    DESIGN.md section 34: such a term links exactly as `rows.float()` would).  A term of weight 0 is dropped before any launch and its three tensors may be `None`.  The returned scores are
     the fp32 chain `w_0 c_0 + w_1 c_1 + ...` over `cosine_rows_indexed` of each live term on the returned rows, bit for bit."""
     lib = _lib.load()
     terms = list(terms)
     arr = (_lib.DrinTopkTermC * max(len(terms), 1))()
+    dtypes = (C.c_int32 * max(len(terms), 1))()
     live = None
     for s, (x, rows, inv, weight) in enumerate(terms[:len(arr)]):
         arr[s].weight = float(weight)
@@ -165,8 +211,11 @@ def table_topk_sum(terms: Sequence, k: int, eps: float, precision: str, chunk_en
             continue
         # the library trusts the extents it is given: what the kernels index is settled here
         for name, t in (("x", x), ("rows", rows), ("inv_norms", inv)):
-            if not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous() or t.device.type != "cuda":
-                raise ValueError(f"table_topk_sum: term {s}: {name} must be a contiguous float32 tensor on the GPU")
+            stored = (torch.float32, torch.bfloat16) if name == "rows" else (torch.float32,)   # rows alone may be stored as bf16
+            if not torch.is_tensor(t) or t.dtype not in stored or not t.is_contiguous() or t.device.type != "cuda":
+                raise ValueError(f"table_topk_sum: term {s}: {name} must be a contiguous float32 tensor on the GPU"
+                                 + (" (rows: or bfloat16, read in place)" if name == "rows" else ""))
+        dtypes[s] = _lib.FEAT_BF16 if rows.dtype == torch.bfloat16 else _lib.FEAT_F32
         if live is None:
             live = (x.shape[0], rows.shape[0], x.device)
         if (x.dim() != 2 or rows.dim() != 2 or x.shape[1] != rows.shape[1] or x.shape[0] != live[0] or rows.shape[0] != live[1]
@@ -178,6 +227,16 @@ def table_topk_sum(terms: Sequence, k: int, eps: float, precision: str, chunk_en
         _lib.check(lib.drin_table_topk_sum(arr, len(terms), 1, 1, k, eps, PRECISIONS[precision], chunk_entities, None, 0, None, None, None))
         raise _lib.DrinError(_lib.E_SHAPE, "drin_table_topk_sum: no live term")
     B, E, dev = live
+    if any(d == _lib.FEAT_BF16 for d in dtypes):
+        nbytes = lib.drin_table_topk_sum_workspace_bytes_ex(arr, dtypes, len(terms), B, E, k, chunk_entities, PRECISIONS[precision])
+        if nbytes == 0:
+            _lib.check(_lib.E_SHAPE)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        scores = torch.empty(B, k, dtype=torch.float32, device=dev)
+        best = torch.empty(B, k, dtype=torch.int64, device=dev)
+        _lib.check(lib.drin_table_topk_sum_ex(arr, dtypes, len(terms), E, B, k, eps, PRECISIONS[precision], chunk_entities, _ptr(ws), nbytes,
+                                              _ptr(scores), _ptr(best), _stream(dev)))
+        return LinkResult(scores, best)
     nbytes = lib.drin_table_topk_sum_workspace_bytes(arr, len(terms), B, E, k, chunk_entities)
     if nbytes == 0:
         _lib.check(_lib.E_SHAPE)

@@ -155,17 +155,25 @@ class EntityTable:
 
     def set_clip(self, clip_text: torch.Tensor, clip_image: torch.Tensor) -> "EntityTable":
         """The entities' projected CLIP embeddings (`CLIPModel`'s `text_embeds` / `image_embeds`, preprocess/clip.py:158-172):
-        `[E, C]` float32 each, `C % 4 == 0`, moved to the table's device.  `IndexedBatch.from_clip` and `Model.link` read them."""
+        `[E, C]` float32 each, `C % 4 == 0`, moved to the table's device.  `IndexedBatch.from_clip` and `Model.link` read them.
+        Both may be bfloat16 instead (`C % 8 == 0`): stored rows that the link kernels read in place and
+        widen exactly - they link as their float32 copies would, and no float32 copy is ever made."""
         E = self.num_entities
         for name, t in (("clip_text", clip_text), ("clip_image", clip_image)):
-            if not torch.is_tensor(t) or t.dtype != torch.float32:
-                raise ValueError(f"EntityTable.set_clip: {name} must be a float32 tensor (got {getattr(t, 'dtype', type(t).__name__)})")
+            if not torch.is_tensor(t) or t.dtype not in (torch.float32, torch.bfloat16):
+                raise ValueError(f"EntityTable.set_clip: {name} must be a float32 (or bfloat16) tensor "
+                                 f"(got {getattr(t, 'dtype', type(t).__name__)})")
             if t.dim() != 2 or t.shape[0] != E:
                 raise ValueError(f"EntityTable.set_clip: {name} has shape {tuple(t.shape)}, expected [{E}, C]")
             if t.shape[1] == 0 or t.shape[1] % 4 != 0:
                 raise ValueError(f"EntityTable.set_clip: {name} has width {t.shape[1]}: C must be a positive multiple of 4")
         if clip_text.shape[1] != clip_image.shape[1]:
             raise ValueError(f"EntityTable.set_clip: clip_text and clip_image differ in width ({clip_text.shape[1]}, {clip_image.shape[1]})")
+        if clip_text.dtype != clip_image.dtype:
+            raise ValueError(f"EntityTable.set_clip: clip_text and clip_image differ in dtype ({clip_text.dtype}, {clip_image.dtype}): "
+                             "both float32 or both bfloat16")
+        if clip_text.dtype == torch.bfloat16 and clip_text.shape[1] % 8 != 0:
+            raise ValueError(f"EntityTable.set_clip: bfloat16 rows of width {clip_text.shape[1]}: C must be a multiple of 8 (16-byte rows)")
         dev = self.text.device
         self.clip_text, self.clip_image = clip_text.detach().to(dev).contiguous(), clip_image.detach().to(dev).contiguous()
         return self
@@ -307,7 +315,8 @@ class IndexedBatch:
         rows): `miet[b, n] = s cos(clip_image[b], table.clip_text[candidates[b, n]])`, `mtei[b, n] = s cos(clip_text[b],
         table.clip_image[candidates[b, n]])` by `drin_cross_modal_edges` - `CLIPModel`'s `logits_per_image` / `logits_per_text`
         (preprocess/clip.py:158-172) from stored embeddings, `s = cfg.clip_logit_scale`.  `clip_image`, `clip_text`: the mentions'
-        projected CLIP embeddings `[B, C]` float32; `table` needs `set_clip`.  GPU only.  More than `Model.MAX_CALL_MENTIONS`
+        projected CLIP embeddings `[B, C]` float32; `table` needs `set_clip` (its rows float32, or bfloat16 read in place by
+        `drin_cross_modal_edges_ex`: the bits of the float32 call on the widened rows).  GPU only.  More than `Model.MAX_CALL_MENTIONS`
         mentions run in slices; `B = 0` gives empty matrices.  A candidate outside the table is clamped and reported: with `model`
         into its status words, watched as its forward watches them (`check_indices`, `validate_indices`) - `model` also supplies
         `cfg`; without a model the check is made here, at one synchronisation."""
@@ -335,8 +344,15 @@ class IndexedBatch:
             status = model._status_words(dev) if model is not None else torch.zeros(4, dtype=torch.int32, device=dev)
             stream = torch.cuda.current_stream(dev).cuda_stream
             step = (type(model) if model is not None else Model).MAX_CALL_MENTIONS
+            stored_bf16 = table.clip_text.dtype == torch.bfloat16      # (set_clip: both tables share the dtype)
             for b0 in range(0, B, step):
                 sl = slice(b0, min(B, b0 + step))
+                if stored_bf16:
+                    _lib.check(lib.drin_cross_modal_edges_ex(_ptr(xi[sl]), _ptr(xt[sl]), _ptr(table.clip_text), _ptr(table.clip_image),
+                                                             _lib.FEAT_BF16, _ptr(index[sl]), table.num_entities, sl.stop - b0, N, width,
+                                                             cfg.clip_logit_scale, cfg.cosine_eps, _ptr(miet[sl]), _ptr(mtei[sl]),
+                                                             _ptr(status), stream))
+                    continue
                 _lib.check(lib.drin_cross_modal_edges(_ptr(xi[sl]), _ptr(xt[sl]), _ptr(table.clip_text), _ptr(table.clip_image),
                                                       _ptr(index[sl]), table.num_entities, sl.stop - b0, N, width,
                                                       cfg.clip_logit_scale, cfg.cosine_eps, _ptr(miet[sl]), _ptr(mtei[sl]),
@@ -1225,7 +1241,7 @@ class Model(nn.Module):
         `mention`: the seven mention-side tensors of the 14-sequence; `clip_image` / `clip_text`: the mentions' projected CLIP
         embeddings `[B, C]` float32; `table` with `set_clip` rows.  The candidates are EITHER `candidates [B, N]` int64 rows of the
         table (for example `ghmfc_model.link(...).rows`) OR come from a cosine first stage: `queries [B, Dq]` against `rows [E, Dq]`
-        (float32), the `N` best by `drin_table_topk` in the model's precision (N <= 256; inverse row norms cached per version of
+        (float32; `rows` may be bfloat16, read in place - DESIGN.md section 34), the `N` best by `drin_table_topk` in the model's precision (N <= 256; inverse row norms cached per version of
         the `rows` tensor, which the model keeps a reference to until another one is given).  ALL `N` slots are candidates: in linking there is no answer slot (the reference's loss and metric drop the last
         column, common/utils.py:36-37), so none is dropped.  Then `IndexedBatch.from_clip` forms the two CLIP edges, the model's
         own forward scores the batch on whatever route it takes (the per-entity cache when the table has it enabled) and
@@ -1239,7 +1255,13 @@ class Model(nn.Module):
         term.  `edge_weights`: three floats (default `cfg.gcn_edge_enabled[0:3]`); a zero drops its term, whose tensors are then
         not read; all three zero is refused.  The inverse row norms of the three tables are cached per tensor version (the rule
         of `rows` above; `invalidate()` drops them).  A mention with an EMPTY span has a NaN `tt` row: all its first-stage scores
-        are NaN and its candidates are rows `0 .. N-1` by the contract - it is not treated specially."""
+        are NaN and its candidates are rows `0 .. N-1` by the contract - it is not treated specially.
+
+        bf16-stored tables: `table.text` (with the other five feature tensors: all six bfloat16, or none) and
+        the `set_clip` rows may be bfloat16.  Every first stage reads them in place and lists what it would list on their exactly
+        widened float32 copies; `tt`'s query is then the span mean of the bfloat16 mention text read in place
+        (`drin_mention_rows_fwd`), its table the bfloat16 token-0 copy.  The second stage is the model's forward on the bf16 table
+        (route "prepared"; such a table with the cache enabled keeps its `ValueError`)."""
         from .ghmfc_table import LinkResult, row_inv_norms, table_topk
         if self.training:
             raise RuntimeError("Model.link: ranking is eval() only (no gradient flows through a top-k): call .eval()")
@@ -1269,9 +1291,10 @@ class Model(nn.Module):
             if N > _lib.TOPK_MAX_K:
                 raise ValueError(f"Model.link: a cosine first stage lists at most {_lib.TOPK_MAX_K} rows and N = {N}: pass `candidates`")
             if (queries.dim() != 2 or rows.dim() != 2 or queries.shape[1] != rows.shape[1] or rows.shape[0] != table.num_entities
-                    or queries.dtype != torch.float32 or rows.dtype != torch.float32):
+                    or queries.dtype != torch.float32 or rows.dtype not in (torch.float32, torch.bfloat16)
+                    or (rows.dtype == torch.bfloat16 and rows.shape[1] % 8 != 0)):
                 raise ValueError(f"Model.link: queries {tuple(queries.shape)} / rows {tuple(rows.shape)} must be float32 [B, Dq] and "
-                                 f"[E = {table.num_entities}, Dq]")
+                                 f"[E = {table.num_entities}, Dq] (rows: or bfloat16 with Dq % 8 == 0, read in place)")
             if N > rows.shape[0]:
                 raise ValueError(f"Model.link: N = {N} candidates exceed the table's {rows.shape[0]} entities")
             if rows.device.type != "cuda" or queries.device != rows.device:
@@ -1282,7 +1305,7 @@ class Model(nn.Module):
             # in whatever block the allocator hands back).  While the entry holds the tensor, an equal address means the same
             # storage, whose version counter every in-place torch op bumps (writes through `.data`: Model.invalidate())
             given = rows
-            key = (given.data_ptr(), given._version, tuple(given.shape), tuple(given.stride()), self.cfg.cosine_eps)
+            key = (given.data_ptr(), given._version, tuple(given.shape), tuple(given.stride()), given.dtype, self.cfg.cosine_eps)
             cached = self.__dict__.get("_link_inv")
             if cached is None or cached[0] != key:
                 self.__dict__["_link_inv"] = cached = None                # release the stale copy before allocating
@@ -1339,8 +1362,13 @@ class Model(nn.Module):
             if not torch.is_tensor(t) or t.dtype != torch.float32 or tuple(t.shape) != (B, C):
                 raise ValueError(f"Model.link: {name} must be float32 [{B}, {C}] (got {getattr(t, 'dtype', None)} "
                                  f"{tuple(getattr(t, 'shape', ()))})")
-        if weights[0] != 0.0 and (table.text.dtype != torch.float32 or mtf.dtype != torch.float32):   # tt's tensors, when tt is a term
-            raise NotImplementedError("Model.link: first_stage='edges' reads float32 mention and table text (bf16-stored rows are not built)")
+        stored = (torch.float32, torch.bfloat16)
+        if weights[0] != 0.0 and (table.text.dtype not in stored or mtf.dtype != table.text.dtype):   # tt's tensors, when tt is a term
+            raise NotImplementedError("Model.link: first_stage='edges' reads mention and table text of ONE storage, float32 or bfloat16 - all "
+                                      f"six feature tensors as bfloat16, or none (got mention {mtf.dtype}, table {table.text.dtype}: mixed "
+                                      "bf16-stored rows are not built)")
+        if weights[0] != 0.0 and mtf.dtype == torch.bfloat16 and mtf.shape[-1] % 8 != 0:
+            raise ValueError(f"Model.link: bfloat16 text rows of width {mtf.shape[-1]}: the width must be a multiple of 8")
         dev = table.text.device
         if dev.type != "cuda" or any(t.device != dev for t in (mtf, start, end, clip_image, clip_text, table.clip_text, table.clip_image)):
             raise RuntimeError("Model.link runs on an AMD GPU only (no CPU / eager fallback); move the batch and the table to 'cuda'")
@@ -1348,7 +1376,8 @@ class Model(nn.Module):
             return torch.empty(0, N, dtype=torch.int64, device=dev)
         eps = self.cfg.cosine_eps
         # (query, table rows) per edge, in edge order; a dropped term's tensors are not touched - not even the token-0 copy is made
-        sources = ((lambda: row_ops.span_mean(mtf, start, end), lambda: table.pooled_text(self.cfg)[1] if table.text.dim() == 3 else table.text),
+        sources = ((lambda: row_ops.span_mean(mtf, start, end) if mtf.dtype == torch.float32 else self._span_mean_stored(mtf, start, end),
+                    lambda: table.pooled_text(self.cfg)[1] if table.text.dim() == 3 else table.text),
                    (lambda: clip_text, lambda: table.clip_image),
                    (lambda: clip_image, lambda: table.clip_text))
         # the inverse norms per version of the table's tensor, under _link_inv's rule: the entry keeps the tensor (and the dense
@@ -1360,7 +1389,7 @@ class Model(nn.Module):
                 terms.append((None, None, None, 0.0))
                 continue
             given = rows_of()
-            key = (given.data_ptr(), given._version, tuple(given.shape), tuple(given.stride()), eps)
+            key = (given.data_ptr(), given._version, tuple(given.shape), tuple(given.stride()), given.dtype, eps)
             entry = cache.get(s)
             if entry is None or entry[0] != key:
                 cache[s] = entry = None                                   # release the stale copy before allocating
@@ -1372,6 +1401,23 @@ class Model(nn.Module):
         parts = [table_topk_sum([(None if x is None else x[b0:b0 + step], r, i, w) for x, r, i, w in terms], N, eps, precision).rows
                  for b0 in range(0, B, step)]
         return parts[0] if len(parts) == 1 else torch.cat(parts, 0)
+
+    @staticmethod
+    def _span_mean_stored(text: torch.Tensor, start: torch.Tensor, end: torch.Tensor) -> torch.Tensor:
+        """`[B, D]` float32: the span mean of bfloat16 mention text `[B, L, D]`, read in place (`drin_mention_rows_fwd` with
+        `DRIN_FEAT_BF16`: the row the fused forward takes its text-text edge from on bf16-stored features)."""
+        text = text.detach().contiguous()
+        B, L, D = text.shape
+        # the positions as the kernel reads them - int64, contiguous, on the text's device - held in locals across the launch
+        # (row_ops.span_mean's rule: any integer dtype is taken, a wrong length is refused before the launch)
+        start, end = (torch.as_tensor(t).to(text.device, torch.int64).contiguous() for t in (start, end))
+        if tuple(start.shape) != (B,) or tuple(end.shape) != (B,):
+            raise ValueError(f"Model.link: mention start {tuple(start.shape)} / end {tuple(end.shape)} are not [batch] = {(B,)}")
+        out = torch.empty(2, B, D, dtype=torch.float32, device=text.device)   # the edge row and the (equal) vertex row
+        _lib.check(_lib.load().drin_mention_rows_fwd(_ptr(text), _lib.FEAT_BF16, None, _ptr(start), _ptr(end), _lib.REPR_AVG_EXTRACT,
+                                                     _ptr(out[0]), _ptr(out[1]), None, B, L, D,
+                                                     torch.cuda.current_stream(text.device).cuda_stream))
+        return out[0]
 
     def wait_for_parameters(self) -> None:
         """Make the current stream wait for an optimiser update `train.OverlappedStep` left running on its side stream (no-op

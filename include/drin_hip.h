@@ -1029,6 +1029,20 @@ DRIN_API int drin_cosine_rows_indexed_fwd(const float* x, const float* rows, con
                                           int32_t batch, int32_t num_candidates, int32_t width, float eps, int32_t* index_status,
                                           void* stream);
 
+/* ---- linking against bf16-STORED table rows --------------------------------------------------------- *
+ * The *_ex twins of the link entry points take how the TABLE rows are stored: row_dtype = DRIN_FEAT_F32 | DRIN_FEAT_BF16 (any
+ * other value: DRIN_E_UNSUPPORTED).  THE CONTRACT: a bf16 table links exactly as its exactly-widened fp32 copy would.  The rows
+ * are read in place - 8 bytes per lane and column quad, each element widened by a 16-bit shift, the sums in the order of the
+ * fp32 kernels - and no widened copy of a table ever exists.  With DRIN_FEAT_F32 a twin runs the old entry point's code and
+ * returns its bits.  bf16 rows need width % 8 == 0 (DRIN_E_SHAPE) and 16-byte aligned rows (DRIN_E_ALIGN), refused among the
+ * argument checks before any launch.  Mentions (x), inverse norms and every output stay fp32.
+ *
+ * drin_cosine_rows_indexed_fwd with `rows` stored as row_dtype: bit for bit the old entry point on the widened table.  No
+ * product: a row kernel. */
+DRIN_API int drin_cosine_rows_indexed_fwd_ex(const float* x, const void* rows, int32_t row_dtype, const int64_t* index,
+                                             int64_t num_entities, float* out, int32_t batch, int32_t num_candidates, int32_t width,
+                                             float eps, int32_t* index_status, void* stream);
+
 /* ---- cosine top-k against the whole table ------------------------------------------------------ *
  * The k best rows of rows [num_entities, width] for every mention x [batch, width] by cosine, without a [batch, num_entities]
  * score matrix: what a first stage does (baselines/data.py ranks num_candidates_model candidates that one chose).
@@ -1047,6 +1061,10 @@ DRIN_API int drin_cosine_rows_indexed_fwd(const float* x, const float* rows, con
 
 /* out[e] = 1 / max(sqrt(sum_d rows[e, d]^2), eps) for rows [num_entities, width]; eps > 0. */
 DRIN_API int drin_row_inv_norms(const float* rows, int64_t num_entities, int32_t width, float eps, float* out, void* stream);
+/* The same for rows stored as row_dtype (the contract of the *_ex twins above: a bf16 table links exactly as its exactly-widened
+ * fp32 copy would - bit for bit the old entry point on the widened rows).  No product: a row kernel. */
+DRIN_API int drin_row_inv_norms_ex(const void* rows, int32_t row_dtype, int64_t num_entities, int32_t width, float eps, float* out,
+                                   void* stream);
 
 /* The selection alone, on caller-supplied dot products: merges the `cols` columns of `block` (table rows col_base ..
  * col_base + cols - 1, keys block[c * ld + b] * col_inv_norms[c]; col_inv_norms NULL = 1) into the running lists state_keys
@@ -1074,6 +1092,21 @@ DRIN_API size_t drin_table_topk_workspace_bytes(int32_t batch, int64_t num_entit
 DRIN_API int drin_table_topk(const float* x, const float* rows, const float* row_inv_norms, int64_t num_entities, int32_t batch,
                              int32_t width, int32_t k, float cosine_eps, int32_t precision, int64_t chunk_entities, void* workspace,
                              size_t workspace_bytes, float* out_scores, int64_t* out_rows, void* stream);
+/* drin_table_topk against rows stored as row_dtype: a bf16 table links exactly as its exactly-widened fp32 copy would.  The
+ * product of a chunk of bf16 rows takes one of two routes, chosen by the GEMM module.  PLANE route - DRIN_PREC_BF16X3 and
+ * width % 32 == 0: the chunk is, as stored, the hi plane of the plane kernel with no lo plane (two of the three split-bf16 MFMAs),
+ * against the hi / lo planes of the padded mentions, split once per call; the table's bytes are read once.  WIDEN route -
+ * DRIN_PREC_F32, or a width that misses the plane kernel: the chunk is widened into the workspace and the old product runs on
+ * it, so in DRIN_PREC_F32 the block of dot products, and with it the selected list, is what drin_table_topk computes on the widened
+ * table.  out_scores are drin_cosine_rows_indexed_fwd_ex's bits on out_rows.  The workspace query takes row_dtype and precision
+ * because the route decides the extra region: Bp * width floats of planes, or chunk * width floats of widened rows - and the
+ * default chunk (chunk_entities = 0) of the widen route keeps that region within the 256 MiB budget as well.  With DRIN_FEAT_F32
+ * both are the old entry points: their bytes, their bits. */
+DRIN_API size_t drin_table_topk_workspace_bytes_ex(int32_t batch, int64_t num_entities, int32_t width, int32_t k, int64_t chunk_entities,
+                                                   int32_t row_dtype, int32_t precision);
+DRIN_API int drin_table_topk_ex(const float* x, const void* rows, int32_t row_dtype, const float* row_inv_norms, int64_t num_entities,
+                                int32_t batch, int32_t width, int32_t k, float cosine_eps, int32_t precision, int64_t chunk_entities,
+                                void* workspace, size_t workspace_bytes, float* out_scores, int64_t* out_rows, void* stream);
 
 /* ---- a SUM of cosines against the tables ------------------------------------------------------------ *
  * score(b, e) = sum_s weight_s * cos(x_s[b, :], rows_s[e, :]) over 1 .. DRIN_TOPK_MAX_TERMS (query, table) pairs that share
@@ -1125,6 +1158,19 @@ DRIN_API size_t drin_table_topk_sum_workspace_bytes(const drin_topk_term* terms,
 DRIN_API int drin_table_topk_sum(const drin_topk_term* terms, int32_t num_terms, int64_t num_entities, int32_t batch, int32_t k,
                                  float cosine_eps, int32_t precision, int64_t chunk_entities, void* workspace, size_t workspace_bytes,
                                  float* out_scores, int64_t* out_rows, void* stream);
+/* drin_table_topk_sum with the storage of every term's rows: row_dtypes, a HOST array [num_terms] of DRIN_FEAT_F32 |
+ * DRIN_FEAT_BF16 beside the unchanged terms (terms[s].rows then addresses bf16 rows; width % 8 == 0).  Terms may mix; the entry
+ * of a dropped term (weight 0) is not read.  A bf16 table links exactly as its exactly-widened fp32 copy would: each live term's
+ * product takes the plane or the widen route as drin_table_topk_ex's does (per term: DRIN_PREC_BF16X3 and width % 32 == 0 is the
+ * plane route), the re-score is drin_cosine_rows_indexed_fwd_ex's, the chain is unchanged.  The workspace grows by Bp * width
+ * floats of planes per plane-route term and by ONE widened chunk as wide as the widest widen-route term.  All DRIN_FEAT_F32: the
+ * old entry points' bytes and bits. */
+DRIN_API size_t drin_table_topk_sum_workspace_bytes_ex(const drin_topk_term* terms, const int32_t* row_dtypes, int32_t num_terms,
+                                                       int32_t batch, int64_t num_entities, int32_t k, int64_t chunk_entities,
+                                                       int32_t precision);
+DRIN_API int drin_table_topk_sum_ex(const drin_topk_term* terms, const int32_t* row_dtypes, int32_t num_terms, int64_t num_entities,
+                                    int32_t batch, int32_t k, float cosine_eps, int32_t precision, int64_t chunk_entities, void* workspace,
+                                    size_t workspace_bytes, float* out_scores, int64_t* out_rows, void* stream);
 
 /* ---- DRIN behind a first stage: CLIP edges for run-time candidates and a rerank ---------------- *
  * The two CLIP edges of drin_batch (miet_similarity, mtei_similarity) for candidates that were chosen at run time, from stored
@@ -1144,6 +1190,13 @@ DRIN_API int drin_cross_modal_edges(const float* mention_clip_image, const float
                                     const float* table_clip_image, const int64_t* index, int64_t num_entities, int32_t batch,
                                     int32_t num_candidates, int32_t width, float scale, float eps, float* miet, float* mtei,
                                     int32_t* index_status, void* stream);
+/* The same with both CLIP tables stored as row_dtype (one dtype for both; the mentions' rows stay fp32): a bf16 table links
+ * exactly as its exactly-widened fp32 copy would - bit for bit the old entry point on the widened tables.  No product: a row
+ * kernel, four table rows in flight per wave as before. */
+DRIN_API int drin_cross_modal_edges_ex(const float* mention_clip_image, const float* mention_clip_text, const void* table_clip_text,
+                                       const void* table_clip_image, int32_t row_dtype, const int64_t* index, int64_t num_entities,
+                                       int32_t batch, int32_t num_candidates, int32_t width, float scale, float eps, float* miet,
+                                       float* mtei, int32_t* index_status, void* stream);
 
 /* Per mention, the first k of n (score, row) pairs - scores [batch, n], rows int64 [batch, n] - under THE ORDERING CONTRACT
  * above, with one rule added because a caller's candidate list may name a row twice: between equal scores on equal rows, the

@@ -197,14 +197,18 @@ int launch_cross_modal_edges_t(const float* m_image, const float* m_text, const 
   });
 }
 
-}  // namespace
-
-int launch_cross_modal_edges(const float* m_image, const float* m_text, const float* t_text, const float* t_image, const int64_t* index,
-                             int64_t num_rows, int B, int N, int D, float scale, float eps, float* miet, float* mtei, int32_t* status,
-                             hipStream_t st) {
-  return launch_cross_modal_edges_t<float>(m_image, m_text, t_text, t_image, index, num_rows, B, N, D, scale, eps, miet, mtei, status, st);
+// row_dtype: how both tables are stored (DRIN_FEAT_F32 / DRIN_FEAT_BF16)
+int launch_cross_modal_edges(const float* m_image, const float* m_text, const void* t_text, const void* t_image, int row_dtype,
+                             const int64_t* index, int64_t num_rows, int B, int N, int D, float scale, float eps, float* miet, float* mtei,
+                             int32_t* status, hipStream_t st) {
+  if (row_dtype != DRIN_FEAT_BF16)
+    return launch_cross_modal_edges_t(m_image, m_text, static_cast<const float*>(t_text), static_cast<const float*>(t_image), index, num_rows, B,
+                                      N, D, scale, eps, miet, mtei, status, st);
+  return launch_cross_modal_edges_t(m_image, m_text, static_cast<const __bf16*>(t_text), static_cast<const __bf16*>(t_image), index, num_rows, B,
+                                    N, D, scale, eps, miet, mtei, status, st);
 }
 
+}  // namespace
 }  // namespace drin
 
 using namespace drin;
@@ -243,13 +247,8 @@ static int cross_modal_edges(const char* who, const float* mention_clip_image, c
   DRIN_TRY(check_count(who, "num_candidates", num_candidates, 1, kMaxGridY));
   DRIN_TRY(check_count(who, "batch * num_candidates", (int64_t)batch * num_candidates, 1, INT32_MAX));
   DRIN_BIND_DEVICE(stream, miet ? miet : mtei, who);
-  if (row_dtype == DRIN_FEAT_BF16)
-    return launch_cross_modal_edges_t<__bf16>(mention_clip_image, mention_clip_text, static_cast<const __bf16*>(table_clip_text),
-                                              static_cast<const __bf16*>(table_clip_image), index, num_entities, batch, num_candidates, width,
-                                              scale, eps, miet, mtei, index_status, (hipStream_t)stream);
-  return launch_cross_modal_edges(mention_clip_image, mention_clip_text, static_cast<const float*>(table_clip_text),
-                                  static_cast<const float*>(table_clip_image), index, num_entities, batch, num_candidates, width, scale, eps,
-                                  miet, mtei, index_status, (hipStream_t)stream);
+  return launch_cross_modal_edges(mention_clip_image, mention_clip_text, table_clip_text, table_clip_image, row_dtype, index, num_entities, batch,
+                                  num_candidates, width, scale, eps, miet, mtei, index_status, (hipStream_t)stream);
 }
 
 int drin_cross_modal_edges(const float* mention_clip_image, const float* mention_clip_text, const float* table_clip_text,

@@ -381,7 +381,7 @@ int drin_ghmfc_forward_table(const drin_ghmfc_config* cfg, const drin_ghmfc_batc
     const int64_t pairs = (int64_t)Bc * N, p0 = (int64_t)b0 * N;
     const int64_t* cand = t.candidates + p0;
     if (t.rows) {   // per-entity rows (drin_ghmfc_entity_rows): the entity half is one cosine against gathered rows
-      DRIN_TRY(launch_cosine_gather(men, t.rows, cand, t.num_entities, scores + p0, Bc, N, D, c.cosine_eps, t.index_status, p0, st));
+      DRIN_TRY(launch_cosine_gather(men, t.rows, DRIN_FEAT_F32, cand, t.num_entities, scores + p0, Bc, N, D, c.cosine_eps, t.index_status, p0, st));
       continue;
     }
     // EntityEncoder (ghmfc.py:237-250) on the rows data.py's qid2idx gather would have delivered, and the cosine (:297-298): the

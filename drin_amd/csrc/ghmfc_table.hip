@@ -84,20 +84,15 @@ int launch_gather_rows(const float* table, const int64_t* index, int64_t num_row
   });
 }
 
-int launch_cosine_gather(const float* x, const float* rows, const int64_t* index, int64_t num_rows, float* out, int B, int N, int D,
-                         float eps, int32_t* status, int64_t pair_base, hipStream_t st) {
+int launch_cosine_gather(const float* x, const void* rows, int row_dtype, const int64_t* index, int64_t num_rows, float* out, int B, int N,
+                         int D, float eps, int32_t* status, int64_t pair_base, hipStream_t st) {
   const int64_t pairs = (int64_t)B * N;
   if (pairs <= 0) return DRIN_OK;
-  return timed(DRIN_KC_EDGE, st, "k_cosine_gather", [&] {
-    hipLaunchKernelGGL(k_cosine_gather<float>, pair_grid(B, N), dim3(256), 0, st, x, rows, index, num_rows, out, pairs, N, D / 4, eps, status,
-                       pair_base);
-  });
-}
-
-int launch_cosine_gather_bf16(const float* x, const void* rows, const int64_t* index, int64_t num_rows, float* out, int B, int N, int D,
-                              float eps, int32_t* status, int64_t pair_base, hipStream_t st) {
-  const int64_t pairs = (int64_t)B * N;
-  if (pairs <= 0) return DRIN_OK;
+  if (row_dtype != DRIN_FEAT_BF16)
+    return timed(DRIN_KC_EDGE, st, "k_cosine_gather", [&] {
+      hipLaunchKernelGGL(k_cosine_gather<float>, pair_grid(B, N), dim3(256), 0, st, x, static_cast<const float*>(rows), index, num_rows, out,
+                         pairs, N, D / 4, eps, status, pair_base);
+    });
   return timed(DRIN_KC_EDGE, st, "k_cosine_gather_bf16", [&] {
     hipLaunchKernelGGL(k_cosine_gather<__bf16>, pair_grid(B, N), dim3(256), 0, st, x, static_cast<const __bf16*>(rows), index, num_rows, out,
                        pairs, N, D / 4, eps, status, pair_base);
@@ -170,10 +165,7 @@ static int cosine_rows_indexed(const char* who, const float* x, const void* rows
   DRIN_TRY(check_count(who, "num_candidates", num_candidates, 1, kMaxGridY));
   DRIN_TRY(check_count(who, "batch * num_candidates", (int64_t)batch * num_candidates, 1, INT32_MAX));
   DRIN_BIND_DEVICE(stream, out, who);
-  if (row_dtype == DRIN_FEAT_BF16)
-    return launch_cosine_gather_bf16(x, rows, index, num_entities, out, batch, num_candidates, width, eps, index_status, 0,
-                                     (hipStream_t)stream);
-  return launch_cosine_gather(x, static_cast<const float*>(rows), index, num_entities, out, batch, num_candidates, width, eps, index_status, 0,
+  return launch_cosine_gather(x, rows, row_dtype, index, num_entities, out, batch, num_candidates, width, eps, index_status, 0,
                               (hipStream_t)stream);
 }
 

@@ -170,12 +170,11 @@ int launch_entity_token_pool_indexed(const float* text, const int64_t* mask, con
 // out[i, :] = table[index[i], :] for [E, width] fp32 rows
 int launch_gather_rows(const float* table, const int64_t* index, int64_t num_rows, float* out, int64_t count, int width,
                        int32_t* status, int64_t pair_base, hipStream_t st);
-// out[b * N + n] = cos(x[b, :], rows[index[b * N + n], :]): k_cosine_rows' lane loop on a clamped row
-int launch_cosine_gather(const float* x, const float* rows, const int64_t* index, int64_t num_rows, float* out, int B, int N, int D,
-                         float eps, int32_t* status, int64_t pair_base, hipStream_t st);
-// the same against rows STORED as bf16 (widened exactly, lane by lane: the bits of the fp32 launcher on the widened table)
-int launch_cosine_gather_bf16(const float* x, const void* rows, const int64_t* index, int64_t num_rows, float* out, int B, int N, int D,
-                              float eps, int32_t* status, int64_t pair_base, hipStream_t st);
+// out[b * N + n] = cos(x[b, :], rows[index[b * N + n], :]): k_cosine_rows' lane loop on a clamped row.  row_dtype: how `rows` are
+// stored - DRIN_FEAT_F32, or DRIN_FEAT_BF16 (widened exactly, lane by lane: the bits of the fp32 rows' launch on the widened table;
+// the launch is then timed as k_cosine_gather_bf16)
+int launch_cosine_gather(const float* x, const void* rows, int row_dtype, const int64_t* index, int64_t num_rows, float* out, int B, int N,
+                         int D, float eps, int32_t* status, int64_t pair_base, hipStream_t st);
 // out[i] = (float)rows_bf16[i], n % 4 == 0, both 16-byte aligned: the widen route of an NT product on bf16-stored rows (gemm.h)
 int launch_widen_rows(const void* rows_bf16, float* out, int64_t n, hipStream_t st);
 // out[b*N + n] = scale * cos(x[b, :], y[(b*N + n) * y_stride : +D])
@@ -325,11 +324,12 @@ int ghmfc_layout_selfcheck(int B, int N, int D, int R, int L, int P, int T);   /
 // the same layout as drin_ghmfc_forward_table carves it (rows: scored from per-entity rows, no entity regions), and the chunk
 // buffer of drin_ghmfc_entity_rows for E entities
 int ghmfc_table_layout_selfcheck(int B, int N, int D, int R, int L, int P, int T, bool rows, int64_t E);
-// TopkLayout (table_topk.hip): the workspace of drin_table_topk, and the rules of its kp, chunk and slice count
-// (row_dtype DRIN_FEAT_BF16 with the product's precision: the planes / widen region of section 34 as well)
+// TopkLayout (topk_layout.h; both are thin calls of its topk_layout_fault): the workspace of drin_table_topk - the single-table
+// form - and the rules of its kp, chunk and slice count (row_dtype DRIN_FEAT_BF16 with the product's precision: the planes / widen
+// region of section 34 as well)
 int table_topk_layout_selfcheck(int B, int64_t E, int D, int k, int64_t chunk_entities, int row_dtype = DRIN_FEAT_F32,
                                 int precision = DRIN_PREC_F32);
-// TopkSumLayout (table_topk.hip): the workspace of drin_table_topk_sum for S live terms of the given widths
+// ... and of drin_table_topk_sum - the summed form - for S live terms of the given widths
 int table_topk_sum_layout_selfcheck(const int* widths, int S, int B, int64_t E, int k, int64_t chunk_entities, const int* dtypes = nullptr,
                                     int precision = DRIN_PREC_F32);
 

@@ -13,22 +13,24 @@
 //                     (drin_rank_rows: the rerank behind a second-stage scoring)
 // and the entry points drin_row_inv_norms, drin_topk_update, drin_table_topk(_workspace_bytes), drin_rank_rows, with the _ex twins that
 // read table rows STORED as bf16 in place (section 34: k_row_inv_norms<__bf16>, the product routed by the GEMM module, the re-score
-// k_cosine_gather<__bf16>).  The block of dot products is
+// k_cosine_gather<__bf16>).  A storage-templated kernel has ONE launcher that takes the row dtype.  The workspace of drin_table_topk
+// and of drin_table_topk_sum is one description (topk_layout.h: TopkLayout; the single-table form is the summed one at S = 1
+// without the factors and the cosines), and the size query and the run of either form go through one plan_topk (section 35).
+// The block of dot products is
 // ENTITY-major, as the product y[Ec, Bp] = rows_chunk x^T leaves it: element (mention b, column c) at block[c * ld + b].
 // No atomics, no scratch memory; a workgroup of the three selection kernels is ONE wave, so its barriers order that wave's LDS
 // traffic and wait for nobody.
 #include "device_utils.h"
 #include "row_checks.h"
+#include "topk_layout.h"
 
 namespace drin {
 namespace {
 
-constexpr int kSlice = DRIN_TOPK_SLICE;   // columns per partial workgroup
+constexpr int kSlice = kTopkSlice;        // columns per partial workgroup
 constexpr int kTile = 8;                  // mentions per partial workgroup: 32 contiguous bytes of every block row
-constexpr int kMaxKp = 256;
+constexpr int kMaxKp = kTopkMaxKp;
 constexpr int kStageLd = 65;              // floats per staged mention row (64 columns + 1: the transposing writes spread over banks)
-constexpr int64_t kBlockBudgetBytes = (int64_t)256 << 20;   // the default chunk bounds the score block to this
-constexpr int64_t kMaxChunk = (int64_t)1 << 30;
 
 static_assert(DRIN_TOPK_KP(1) == 64 && DRIN_TOPK_KP(65) == 128 && DRIN_TOPK_KP(256) == kMaxKp, "kp: the power of two >= max(k, 64)");
 
@@ -412,24 +414,25 @@ int launch_rank_rows(const float* scores, const int64_t* rows, int batch, int n,
   });
 }
 
-int launch_row_inv_norms(const float* rows, int64_t num_rows, int width, float eps, float* out, hipStream_t st) {
+// row_dtype: how the rows are stored (DRIN_FEAT_F32 / DRIN_FEAT_BF16) - the instantiation and the timer's name
+int launch_row_inv_norms(const void* rows, int row_dtype, int64_t num_rows, int width, float eps, float* out, hipStream_t st) {
   const int64_t blocks = row_blocks(num_rows);
-  return timed(DRIN_KC_EDGE, st, "k_row_inv_norms", [&] {
-    hipLaunchKernelGGL(k_row_inv_norms<float>, dim3((unsigned)blocks), dim3(256), 0, st, rows, num_rows, width / 4, eps, out);
-  });
-}
-int launch_row_inv_norms_bf16(const void* rows, int64_t num_rows, int width, float eps, float* out, hipStream_t st) {
-  const int64_t blocks = row_blocks(num_rows);
+  if (row_dtype != DRIN_FEAT_BF16)
+    return timed(DRIN_KC_EDGE, st, "k_row_inv_norms", [&] {
+      hipLaunchKernelGGL(k_row_inv_norms<float>, dim3((unsigned)blocks), dim3(256), 0, st, static_cast<const float*>(rows), num_rows, width / 4,
+                         eps, out);
+    });
   return timed(DRIN_KC_EDGE, st, "k_row_inv_norms_bf16", [&] {
     hipLaunchKernelGGL(k_row_inv_norms<__bf16>, dim3((unsigned)blocks), dim3(256), 0, st, static_cast<const __bf16*>(rows), num_rows, width / 4,
                        eps, out);
   });
 }
-// the re-score of a list against rows of either storage
-int launch_cosine_gather_any(const float* x, const void* rows, int row_dtype, const int64_t* index, int64_t num_rows, float* out, int B, int N,
-                             int D, float eps, hipStream_t st) {
-  if (row_dtype == DRIN_FEAT_BF16) return launch_cosine_gather_bf16(x, rows, index, num_rows, out, B, N, D, eps, nullptr, 0, st);
-  return launch_cosine_gather(x, static_cast<const float*>(rows), index, num_rows, out, B, N, D, eps, nullptr, 0, st);
+// x [B, D] -> xpad [Bp, D], zero rows behind
+int launch_pad_rows(const float* x, float* xpad, int B, int Bp, int D, hipStream_t st) {
+  const int64_t n4_in = (int64_t)B * D / 4, n4_out = (int64_t)Bp * D / 4;
+  return timed(DRIN_KC_EDGE, st, "k_pad_rows", [&] {
+    hipLaunchKernelGGL(k_pad_rows, dim3((unsigned)(cdiv(n4_out, 256) < 4096 ? cdiv(n4_out, 256) : 4096)), dim3(256), 0, st, x, xpad, n4_in, n4_out);
+  });
 }
 // the product block[n, Bp] = rows_chunk xpad^T of one chunk: fp32 rows as ever; bf16-stored rows declared as such, with the planes of
 // xpad and the widen region the layout carved - the GEMM module picks the route (gemm.h: NtProduct::x_bf16)
@@ -442,48 +445,6 @@ int launch_chunk_product(const void* rows, int row_dtype, int64_t e0, int64_t n,
   p.x_widen = scratch_at(widen, 0, widen_floats);
   return launch_gemm_nt(p.with_planes(planes), precision, st);
 }
-
-// ---- the workspace of drin_table_topk: sized and carved from this one description -------------------------------------
-// bf16-stored rows add ONE region per product route: `planes` - the hi / lo bf16 planes of xpad, Bp D bf16
-// each, split once per call - where the GEMM module runs the table as the hi plane of launch_gemm_x3_planes
-// (nt_bf16_rows_as_planes), else `widen` - one chunk of the table as fp32.  The default chunk of the widen route also keeps that
-// region inside the budget.
-struct TopkLayout {
-  size_t xpad, block, keys, rows, slices, scores, planes, widen, total_floats;   // offsets in floats
-  size_t planes_floats, widen_floats;
-  int64_t chunk, num_slices;
-  int kp, Bp;
-  // false: a region does not fit in size_t / the chunk is out of range
-  bool build(int batch, int64_t E, int D, int k, int64_t chunk_entities, int row_dtype = DRIN_FEAT_F32, int precision = DRIN_PREC_F32) {
-    kp = DRIN_TOPK_KP(k), Bp = (batch + 3) & ~3;
-    const bool bf16 = row_dtype == DRIN_FEAT_BF16, as_planes = bf16 && nt_bf16_rows_as_planes(precision, D, D);
-    if (chunk_entities > 0) {
-      chunk = chunk_entities;
-    } else {   // a multiple of 256 rows whose block - and widened copy - stays inside the budget (at least 256)
-      const int64_t row_bytes = (int64_t)4 * (bf16 && !as_planes && D > Bp ? D : Bp);
-      chunk = kBlockBudgetBytes / row_bytes / 256 * 256;
-      chunk = chunk < 256 ? 256 : chunk;
-    }
-    chunk = chunk < E ? chunk : E;
-    if (chunk > kMaxChunk) return false;
-    num_slices = slices_of(chunk);
-    const size_t limit = SIZE_MAX / 64;   // of floats: the sum of six regions and the byte count stay representable
-    auto fits = [&](size_t a, size_t b) { return a == 0 || b <= limit / a; };
-    if (!fits((size_t)chunk, (size_t)Bp) || !fits((size_t)num_slices * 2, (size_t)batch * kp) || !fits((size_t)chunk, (size_t)D)) return false;
-    Arena A;
-    xpad = A.take((size_t)Bp * D);
-    block = A.take((size_t)chunk * Bp);
-    keys = A.take((size_t)batch * kp);
-    rows = A.take((size_t)batch * kp * 2);
-    slices = A.take((size_t)num_slices * batch * kp * 2);
-    scores = A.take((size_t)batch * kp);
-    planes_floats = as_planes ? (size_t)Bp * D : 0, widen_floats = bf16 && !as_planes ? (size_t)chunk * D : 0;
-    planes = A.take(planes_floats);   // (fp32 rows: two empty regions behind the old ones - the old offsets and the old total)
-    widen = A.take(widen_floats);
-    total_floats = A.total;
-    return true;
-  }
-};
 
 int check_topk_shape(const char* who, int64_t E, int batch, int width, int k) {
   DRIN_TRY(check_count(who, "num_entities", E, 1, INT64_MAX / 4096));
@@ -505,7 +466,31 @@ int check_precision_topk(const char* who, int precision) {
   return DRIN_OK;
 }
 
-// ---- the summed-cosine form: launchers, the live terms of a call, the workspace --------------------------------------------
+// The plan of one call of either form (topk_layout.h: TopkLayout): the checks that the size query and the run share - shape, how the
+// rows are stored, precision, chunk - then the layout, and for a run (`have` not NULL) that the caller's workspace holds it.  A
+// query maps any failure to 0 bytes; drin_last_error names `who`, the spelling that was called.
+int plan_topk(const char* who, const int* widths, const int* dtypes, int S, bool summed, int batch, int64_t E, int k, int64_t chunk_entities,
+              int precision, const size_t* have, TopkLayout* W) {
+  DRIN_TRY(check_topk_shape(who, E, batch, widths[0], k));
+  for (int s = 0; s < S; ++s) DRIN_TRY(check_row_dtype(who, dtypes[s], widths[s]));
+  DRIN_TRY(check_precision_topk(who, precision));
+  if (chunk_entities < 0) {
+    set_error("%s: chunk_entities = %lld is negative", who, (long long)chunk_entities);
+    return DRIN_E_SHAPE;
+  }
+  if (!W->build(widths, dtypes, S, summed, batch, E, k, chunk_entities, precision)) {
+    set_error("%s: chunk_entities = %lld is out of range (at most 2^30 rows, the workspace must fit in size_t)", who,
+              (long long)chunk_entities);
+    return DRIN_E_SHAPE;
+  }
+  if (have != nullptr && *have < W->total_floats * sizeof(float)) {
+    set_error("%s: workspace %zu bytes < %zu", who, *have, W->total_floats * sizeof(float));
+    return DRIN_E_WORKSPACE;
+  }
+  return DRIN_OK;
+}
+
+// ---- the summed-cosine form: launchers, the live terms of a call --------------------------------------------------------------
 int launch_topk_combine(const CombineTerms& t, int S, float* out, int64_t ld, int64_t cols, hipStream_t st) {
   const int64_t quads = ld / 4;
   int tx_log2 = 0;
@@ -579,59 +564,6 @@ int live_terms(const char* who, const drin_topk_term* terms, int num_terms, bool
   return DRIN_OK;
 }
 
-// the workspace of drin_table_topk_sum: per live term the padded mentions, their factors and one block of dot products (block 0
-// takes the combined scores), the S x [batch, kp] re-scored cosines, and the selection's regions as TopkLayout has them
-// bf16-stored terms (dtypes; NULL: none): per term on the plane route its planes of xpad; ONE widen region, as wide as the widest
-// term on the widen route - the terms' products run one after the other.
-struct TopkSumLayout {
-  size_t xpad[DRIN_TOPK_MAX_TERMS], scale[DRIN_TOPK_MAX_TERMS], block[DRIN_TOPK_MAX_TERMS];   // offsets in floats
-  size_t planes[DRIN_TOPK_MAX_TERMS], planes_floats[DRIN_TOPK_MAX_TERMS];
-  size_t cos, keys, rows, slices, scores, widen, widen_floats, total_floats;
-  int64_t chunk, num_slices;
-  int kp, Bp, S;
-  bool build(const int* widths, int terms, int batch, int64_t E, int k, int64_t chunk_entities, const int* dtypes = nullptr,
-             int precision = DRIN_PREC_F32) {
-    kp = DRIN_TOPK_KP(k), Bp = (batch + 3) & ~3, S = terms;
-    int widen_width = 0;   // the widest term that takes the widen route
-    for (int s = 0; s < S; ++s) {
-      const bool bf16 = dtypes != nullptr && dtypes[s] == DRIN_FEAT_BF16;
-      const bool as_planes = bf16 && nt_bf16_rows_as_planes(precision, widths[s], widths[s]);
-      planes_floats[s] = as_planes ? (size_t)Bp * widths[s] : 0;
-      if (bf16 && !as_planes && widths[s] > widen_width) widen_width = widths[s];
-    }
-    if (chunk_entities > 0) {
-      chunk = chunk_entities;
-    } else {   // a multiple of 256 rows whose S blocks together - and the widened copy - stay inside the budget (at least 256)
-      const int64_t row_bytes = (int64_t)4 * (widen_width > (int64_t)S * Bp ? widen_width : (int64_t)S * Bp);
-      chunk = kBlockBudgetBytes / row_bytes / 256 * 256;
-      chunk = chunk < 256 ? 256 : chunk;
-    }
-    chunk = chunk < E ? chunk : E;
-    if (chunk > kMaxChunk) return false;
-    num_slices = slices_of(chunk);
-    const size_t limit = SIZE_MAX / 256;   // of floats: the sum of all regions and the byte count stay representable
-    auto fits = [&](size_t a, size_t b) { return a == 0 || b <= limit / a; };
-    if (!fits((size_t)chunk * S, (size_t)Bp) || !fits((size_t)num_slices * 2, (size_t)batch * kp) || !fits((size_t)chunk, (size_t)widen_width))
-      return false;
-    Arena A;
-    for (int s = 0; s < S; ++s) {
-      xpad[s] = A.take((size_t)Bp * widths[s]);
-      scale[s] = A.take((size_t)Bp);
-      block[s] = A.take((size_t)chunk * Bp);
-    }
-    cos = A.take((size_t)S * batch * kp);
-    keys = A.take((size_t)batch * kp);
-    rows = A.take((size_t)batch * kp * 2);
-    slices = A.take((size_t)num_slices * batch * kp * 2);
-    scores = A.take((size_t)batch * kp);
-    for (int s = 0; s < S; ++s) planes[s] = A.take(planes_floats[s]);   // (fp32 terms: empty regions behind the old ones)
-    widen_floats = (size_t)chunk * widen_width;
-    widen = A.take(widen_floats);
-    total_floats = A.total;
-    return true;
-  }
-};
-
 }  // namespace
 
 int launch_widen_rows(const void* rows_bf16, float* out, int64_t n, hipStream_t st) {
@@ -642,62 +574,21 @@ int launch_widen_rows(const void* rows_bf16, float* out, int64_t n, hipStream_t 
   });
 }
 
+// drin_host_selftest's two spellings of the one check (topk_layout.h: topk_layout_fault)
+static int topk_layout_selfcheck(const int* widths, const int* dtypes, int S, bool summed, int batch, int64_t E, int k, int64_t chunk_entities,
+                                 int precision) {
+  const char* bad = topk_layout_fault(widths, dtypes, S, summed, batch, E, k, chunk_entities, precision);
+  if (bad == nullptr) return DRIN_OK;
+  set_error("selftest: TopkLayout (%s) S=%d B=%d E=%lld k=%d chunk=%lld: %s does not hold", summed ? "summed" : "single", S, batch, (long long)E,
+            k, (long long)chunk_entities, bad);
+  return DRIN_E_WORKSPACE;
+}
 int table_topk_sum_layout_selfcheck(const int* widths, int S, int batch, int64_t E, int k, int64_t chunk_entities, const int* dtypes,
                                     int precision) {
-  TopkSumLayout W;
-  if (!W.build(widths, S, batch, E, k, chunk_entities, dtypes, precision)) {
-    set_error("selftest: TopkSumLayout does not build for S=%d B=%d E=%lld k=%d chunk=%lld", S, batch, (long long)E, k, (long long)chunk_entities);
-    return DRIN_E_WORKSPACE;
-  }
-  const size_t B = batch, kp = W.kp;
-  if (W.kp < k || W.kp > kMaxKp || (W.kp & (W.kp - 1)) || W.chunk < 1 || W.chunk > E || W.num_slices * kSlice < W.chunk ||
-      (chunk_entities == 0 && W.chunk != E &&
-       (W.chunk % 256 || (W.chunk > 256 && (W.chunk * W.Bp * 4 * S > kBlockBudgetBytes || (int64_t)W.widen_floats * 4 > kBlockBudgetBytes))))) {
-    set_error("selftest: TopkSumLayout kp=%d chunk=%lld slices=%lld break their rules", W.kp, (long long)W.chunk, (long long)W.num_slices);
-    return DRIN_E_WORKSPACE;
-  }
-  Region ws[4 * DRIN_TOPK_MAX_TERMS + 6];
-  int n = 0, widest = 0;
-  for (int s = 0; s < S; ++s) {
-    ws[n++] = {"xpad", W.xpad[s], (size_t)W.Bp * widths[s]};
-    ws[n++] = {"scale", W.scale[s], (size_t)W.Bp};
-    ws[n++] = {"block", W.block[s], (size_t)W.chunk * W.Bp};
-    // what the routes index: hi + lo planes of xpad (2 bf16 = 1 float per element), or a widened chunk of the widest such term
-    const bool bf16 = dtypes != nullptr && dtypes[s] == DRIN_FEAT_BF16, as_planes = bf16 && nt_bf16_rows_as_planes(precision, widths[s], widths[s]);
-    ws[n++] = {"planes", W.planes[s], as_planes ? (size_t)W.Bp * widths[s] : 0};
-    if (bf16 && !as_planes && widths[s] > widest) widest = widths[s];
-  }
-  ws[n++] = {"widen", W.widen, (size_t)W.chunk * widest};
-  ws[n++] = {"cos", W.cos, (size_t)S * B * kp};
-  ws[n++] = {"keys", W.keys, B * kp};
-  ws[n++] = {"rows", W.rows, B * kp * 2};
-  ws[n++] = {"slices", W.slices, (size_t)cdiv(W.chunk, kSlice) * B * kp * 2};
-  ws[n++] = {"scores", W.scores, B * kp};
-  return regions_hold("TopkSumLayout", ws, n, W.total_floats);
+  return topk_layout_selfcheck(widths, dtypes, S, true, batch, E, k, chunk_entities, precision);
 }
-
 int table_topk_layout_selfcheck(int batch, int64_t E, int D, int k, int64_t chunk_entities, int row_dtype, int precision) {
-  TopkLayout W;
-  if (!W.build(batch, E, D, k, chunk_entities, row_dtype, precision)) {
-    set_error("selftest: TopkLayout does not build for B=%d E=%lld D=%d k=%d chunk=%lld", batch, (long long)E, D, k, (long long)chunk_entities);
-    return DRIN_E_WORKSPACE;
-  }
-  const size_t B = batch, kp = W.kp;
-  if (W.kp < k || W.kp > kMaxKp || (W.kp & (W.kp - 1)) || W.chunk < 1 || W.chunk > E || W.num_slices * kSlice < W.chunk ||
-      (chunk_entities == 0 && W.chunk != E &&
-       (W.chunk % 256 || (W.chunk > 256 && (W.chunk * W.Bp * 4 > kBlockBudgetBytes || (int64_t)W.widen_floats * 4 > kBlockBudgetBytes))))) {
-    set_error("selftest: TopkLayout kp=%d chunk=%lld slices=%lld break their rules", W.kp, (long long)W.chunk, (long long)W.num_slices);
-    return DRIN_E_WORKSPACE;
-  }
-  // what the launches index: the padded mentions, one block of dot products, the running list, every slice's list, the re-scores
-  // (bf16-stored rows: the hi + lo planes of xpad - 2 bf16 = 1 float per element - on the plane route, else one widened chunk)
-  const bool bf16 = row_dtype == DRIN_FEAT_BF16, as_planes = bf16 && nt_bf16_rows_as_planes(precision, D, D);
-  const Region ws[] = {{"xpad", W.xpad, (size_t)W.Bp * D},   {"block", W.block, (size_t)W.chunk * W.Bp},
-                       {"keys", W.keys, B * kp},             {"rows", W.rows, B * kp * 2},
-                       {"slices", W.slices, (size_t)cdiv(W.chunk, kSlice) * B * kp * 2}, {"scores", W.scores, B * kp},
-                       {"planes", W.planes, as_planes ? (size_t)W.Bp * D : 0},
-                       {"widen", W.widen, bf16 && !as_planes ? (size_t)W.chunk * D : 0}};
-  return regions_hold("TopkLayout", ws, (int)(sizeof(ws) / sizeof(ws[0])), W.total_floats);
+  return topk_layout_selfcheck(&D, &row_dtype, 1, false, batch, E, k, chunk_entities, precision);
 }
 
 }  // namespace drin
@@ -725,8 +616,7 @@ static int row_inv_norms(const char* who, const void* rows, int row_dtype, int64
     return DRIN_E_SHAPE;
   }
   DRIN_BIND_DEVICE(stream, out, who);
-  if (row_dtype == DRIN_FEAT_BF16) return launch_row_inv_norms_bf16(rows, num_entities, width, eps, out, (hipStream_t)stream);
-  return launch_row_inv_norms(static_cast<const float*>(rows), num_entities, width, eps, out, (hipStream_t)stream);
+  return launch_row_inv_norms(rows, row_dtype, num_entities, width, eps, out, (hipStream_t)stream);
 }
 int drin_row_inv_norms(const float* rows, int64_t num_entities, int32_t width, float eps, float* out, void* stream) {
   return row_inv_norms("drin_row_inv_norms", rows, DRIN_FEAT_F32, num_entities, width, eps, out, stream);
@@ -779,18 +669,8 @@ int drin_topk_update(const float* block, int64_t ld, int32_t batch, int64_t cols
 
 static size_t table_topk_workspace_bytes(const char* who, int32_t batch, int64_t num_entities, int32_t width, int32_t k, int64_t chunk_entities,
                                          int row_dtype, int precision) {
-  if (check_topk_shape(who, num_entities, batch, width, k) != DRIN_OK) return 0;
-  if (check_row_dtype(who, row_dtype, width) != DRIN_OK || check_precision_topk(who, precision) != DRIN_OK) return 0;
-  if (chunk_entities < 0) {
-    set_error("%s: chunk_entities = %lld is negative", who, (long long)chunk_entities);
-    return 0;
-  }
   TopkLayout W;
-  if (!W.build(batch, num_entities, width, k, chunk_entities, row_dtype, precision)) {
-    set_error("%s: chunk_entities = %lld is out of range (at most 2^30 rows, the workspace must fit in size_t)", who,
-              (long long)chunk_entities);
-    return 0;
-  }
+  if (plan_topk(who, &width, &row_dtype, 1, false, batch, num_entities, k, chunk_entities, precision, nullptr, &W) != DRIN_OK) return 0;
   return W.total_floats * sizeof(float);
 }
 size_t drin_table_topk_workspace_bytes(int32_t batch, int64_t num_entities, int32_t width, int32_t k, int64_t chunk_entities) {
@@ -814,39 +694,21 @@ static int table_topk(const char* who, const float* x, const void* rows, int row
     set_error("%s: out_scores must be 4-byte and out_rows 8-byte aligned", who);
     return DRIN_E_ALIGN;
   }
-  DRIN_TRY(check_topk_shape(who, num_entities, batch, width, k));
-  DRIN_TRY(check_row_dtype(who, row_dtype, width));
-  DRIN_TRY(check_precision_topk(who, precision));
-  if (chunk_entities < 0) {
-    set_error("%s: chunk_entities = %lld is negative", who, (long long)chunk_entities);
-    return DRIN_E_SHAPE;
-  }
   TopkLayout W;
-  if (!W.build(batch, num_entities, width, k, chunk_entities, row_dtype, precision)) {
-    set_error("%s: chunk_entities = %lld is out of range (at most 2^30 rows, the workspace must fit in size_t)", who,
-              (long long)chunk_entities);
-    return DRIN_E_SHAPE;
-  }
-  if (workspace_bytes < W.total_floats * sizeof(float)) {
-    set_error("%s: workspace %zu bytes < %zu", who, workspace_bytes, W.total_floats * sizeof(float));
-    return DRIN_E_WORKSPACE;
-  }
+  DRIN_TRY(plan_topk(who, &width, &row_dtype, 1, false, batch, num_entities, k, chunk_entities, precision, &workspace_bytes, &W));
   DRIN_BIND_DEVICE(stream, out_scores, who);
   RoctxRange range(who);
   hipStream_t st = (hipStream_t)stream;
   float* ws = static_cast<float*>(workspace);
   const int B = batch, D = width, kp = W.kp, Bp = W.Bp;
-  float* planes = W.planes_floats ? ws + W.planes : nullptr;
-  float* xpad = ws + W.xpad;
-  float* block = ws + W.block;
+  float* planes = W.planes_floats[0] ? ws + W.planes[0] : nullptr;
+  float* xpad = ws + W.xpad[0];
+  float* block = ws + W.block[0];
   float* keys = ws + W.keys;
   int64_t* list = reinterpret_cast<int64_t*>(ws + W.rows);
   uint64_t* slices = reinterpret_cast<uint64_t*>(ws + W.slices);
   float* scores = ws + W.scores;
-  const int64_t n4_in = (int64_t)B * D / 4, n4_out = (int64_t)Bp * D / 4;
-  DRIN_TRY(timed(DRIN_KC_EDGE, st, "k_pad_rows", [&] {
-    hipLaunchKernelGGL(k_pad_rows, dim3((unsigned)(cdiv(n4_out, 256) < 4096 ? cdiv(n4_out, 256) : 4096)), dim3(256), 0, st, x, xpad, n4_in, n4_out);
-  }));
+  DRIN_TRY(launch_pad_rows(x, xpad, B, Bp, D, st));
   // bf16-stored rows on the plane route: the padded mentions as hi / lo planes, split ONCE per call (hi: Bp D bf16, then lo)
   if (planes != nullptr)
     DRIN_TRY(launch_split_planes(xpad, planes, reinterpret_cast<uint16_t*>(planes) + (size_t)Bp * D, (int64_t)Bp * D, st));
@@ -859,7 +721,7 @@ static int table_topk(const char* who, const float* x, const void* rows, int row
   }
   // the kp selected rows of every mention, scored as drin_cosine_rows_indexed_fwd(_ex) scores them (an empty entry, row -1, is
   // clamped silently and stays last), ordered by the contract
-  DRIN_TRY(launch_cosine_gather_any(x, rows, row_dtype, list, num_entities, scores, B, kp, D, cosine_eps, st));
+  DRIN_TRY(launch_cosine_gather(x, rows, row_dtype, list, num_entities, scores, B, kp, D, cosine_eps, nullptr, 0, st));
   return launch_topk_finish(scores, list, B, kp, k, out_scores, out_rows, st);
 }
 int drin_table_topk(const float* x, const float* rows, const float* row_inv_norms, int64_t num_entities, int32_t batch, int32_t width,
@@ -917,17 +779,8 @@ static size_t table_topk_sum_workspace_bytes(const char* who, const drin_topk_te
                                              int32_t batch, int64_t num_entities, int32_t k, int64_t chunk_entities, int precision) {
   LiveTerms live;
   if (live_terms(who, terms, num_terms, false, &live, row_dtypes) != DRIN_OK) return 0;
-  if (check_topk_shape(who, num_entities, batch, live.widths[0], k) != DRIN_OK || check_precision_topk(who, precision) != DRIN_OK) return 0;
-  if (chunk_entities < 0) {
-    set_error("%s: chunk_entities = %lld is negative", who, (long long)chunk_entities);
-    return 0;
-  }
-  TopkSumLayout W;
-  if (!W.build(live.widths, live.S, batch, num_entities, k, chunk_entities, live.dtypes, precision)) {
-    set_error("%s: chunk_entities = %lld is out of range (at most 2^30 rows, the workspace must fit in size_t)", who,
-              (long long)chunk_entities);
-    return 0;
-  }
+  TopkLayout W;
+  if (plan_topk(who, live.widths, live.dtypes, live.S, true, batch, num_entities, k, chunk_entities, precision, nullptr, &W) != DRIN_OK) return 0;
   return W.total_floats * sizeof(float);
 }
 size_t drin_table_topk_sum_workspace_bytes(const drin_topk_term* terms, int32_t num_terms, int32_t batch, int64_t num_entities, int32_t k,
@@ -959,22 +812,8 @@ static int table_topk_sum(const char* who, const drin_topk_term* terms, const in
     set_error("%s: out_scores must be 4-byte and out_rows 8-byte aligned", who);
     return DRIN_E_ALIGN;
   }
-  DRIN_TRY(check_topk_shape(who, num_entities, batch, live.widths[0], k));
-  DRIN_TRY(check_precision_topk(who, precision));
-  if (chunk_entities < 0) {
-    set_error("%s: chunk_entities = %lld is negative", who, (long long)chunk_entities);
-    return DRIN_E_SHAPE;
-  }
-  TopkSumLayout W;
-  if (!W.build(live.widths, live.S, batch, num_entities, k, chunk_entities, live.dtypes, precision)) {
-    set_error("%s: chunk_entities = %lld is out of range (at most 2^30 rows, the workspace must fit in size_t)", who,
-              (long long)chunk_entities);
-    return DRIN_E_SHAPE;
-  }
-  if (workspace_bytes < W.total_floats * sizeof(float)) {
-    set_error("%s: workspace %zu bytes < %zu", who, workspace_bytes, W.total_floats * sizeof(float));
-    return DRIN_E_WORKSPACE;
-  }
+  TopkLayout W;
+  DRIN_TRY(plan_topk(who, live.widths, live.dtypes, live.S, true, batch, num_entities, k, chunk_entities, precision, &workspace_bytes, &W));
   DRIN_BIND_DEVICE(stream, out_scores, who);
   RoctxRange range(who);
   hipStream_t st = (hipStream_t)stream;
@@ -992,11 +831,8 @@ static int table_topk_sum(const char* who, const drin_topk_term* terms, const in
   for (int s = 0; s < S; ++s) {
     const drin_topk_term& t = live.term[s];
     float* xpad = ws + W.xpad[s];
-    const int64_t n4_in = (int64_t)B * t.width / 4, n4_out = (int64_t)Bp * t.width / 4;
-    DRIN_TRY(timed(DRIN_KC_EDGE, st, "k_pad_rows", [&] {
-      hipLaunchKernelGGL(k_pad_rows, dim3((unsigned)(cdiv(n4_out, 256) < 4096 ? cdiv(n4_out, 256) : 4096)), dim3(256), 0, st, t.x, xpad, n4_in, n4_out);
-    }));
-    DRIN_TRY(launch_row_inv_norms(xpad, Bp, t.width, cosine_eps, ws + W.scale[s], st));
+    DRIN_TRY(launch_pad_rows(t.x, xpad, B, Bp, t.width, st));
+    DRIN_TRY(launch_row_inv_norms(xpad, DRIN_FEAT_F32, Bp, t.width, cosine_eps, ws + W.scale[s], st));
     if (W.planes_floats[s])   // a bf16-stored term on the plane route: its padded mentions as hi / lo planes, once per call
       DRIN_TRY(launch_split_planes(xpad, ws + W.planes[s], reinterpret_cast<uint16_t*>(ws + W.planes[s]) + (size_t)Bp * t.width,
                                    (int64_t)Bp * t.width, st));
@@ -1020,7 +856,8 @@ static int table_topk_sum(const char* who, const drin_topk_term* terms, const in
   // silently and stays last), the fp32 chain over the terms, and the order of the contract
   for (int s = 0; s < S; ++s) {
     const drin_topk_term& t = live.term[s];
-    DRIN_TRY(launch_cosine_gather_any(t.x, t.rows, live.dtypes[s], list, num_entities, cos + (size_t)s * B * kp, B, kp, t.width, cosine_eps, st));
+    DRIN_TRY(launch_cosine_gather(t.x, t.rows, live.dtypes[s], list, num_entities, cos + (size_t)s * B * kp, B, kp, t.width, cosine_eps, nullptr, 0,
+                                  st));
   }
   DRIN_TRY(launch_weighted_cosine_sum(cos, S, (int64_t)B * kp, cw, scores, st));
   return launch_topk_finish(scores, list, B, kp, k, out_scores, out_rows, st);

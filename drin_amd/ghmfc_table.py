@@ -15,15 +15,15 @@
 rows by cosine (`drin_table_topk` on the per-entity rows), scores with the bits of the cached table-form scoring.
 
 A row outside the table is clamped by the kernels and reported: `check_indices()` / `validate_indices` raise `IndexError`.
-GPU only, fp32 tables; the table is an input and gets no gradient.  The link primitives of this module (`row_inv_norms`,
-`cosine_rows_indexed`, `table_topk`, `table_topk_sum`) also read `rows` STORED as bfloat16 in place - DRIN's
-`Model.link` uses that; GHMFC's own token tables stay fp32.
+GPU only, fp32 tables; the table is an input and gets no gradient.  The link primitives (`row_inv_norms`, `cosine_rows_indexed`,
+`table_topk`, `table_topk_sum`, `LinkResult`) and the index watch live in `drin_amd.table_ops`, which imports no model; they are
+re-exported here.  They also read `rows` STORED as bfloat16 in place - DRIN's `Model.link` uses that; GHMFC's
+own token tables stay fp32.
 """
 from __future__ import annotations
 
-import ctypes as C
 import os
-from typing import NamedTuple, Optional, Sequence
+from typing import Optional, Sequence
 
 import torch
 
@@ -31,6 +31,8 @@ from . import _lib
 from ._lib import _ptr, _stream
 from .attention import PRECISIONS
 from .model import EntityTable
+from .table_ops import (IndexWatch, LinkResult, _check_f32, _row_dtype, cosine_rows_indexed, decode_status,  # noqa: F401 (re-exported)
+                        row_inv_norms, table_topk, table_topk_sum)
 
 
 class GhmfcIndexedBatch:
@@ -69,10 +71,8 @@ def check_table(table: EntityTable, embed_dim: int, on_gpu: bool = True) -> None
 
 def raise_bad_index(words) -> None:
     """IndexError from the four status words the kernels leave (`report_bad_index`: flag, pair, value low / high)."""
-    w = [int(x) for x in words]
-    value = ((w[3] & 0xFFFFFFFF) << 32 | (w[2] & 0xFFFFFFFF))
-    value -= (1 << 64) if value >= (1 << 63) else 0
-    raise IndexError(f"GhmfcIndexedBatch.candidates: row {value} at pair {w[1]} (b * N + n) is outside the entity table (it was "
+    _flag, pair, value = decode_status(words)
+    raise IndexError(f"GhmfcIndexedBatch.candidates: row {value} at pair {pair} (b * N + n) is outside the entity table (it was "
                      f"clamped: the scores of that call are of the WRONG entity there); the reference's fancy index, "
                      f"baselines/data.py's qid2idx gather, raises here too")
 
@@ -111,143 +111,6 @@ def pooled_candidates(table: EntityTable, index: torch.Tensor, status: Optional[
     return out
 
 
-def _row_dtype(who: str, rows: torch.Tensor) -> int:
-    """`FEAT_F32` / `FEAT_BF16` of table rows that a link primitive reads IN PLACE: contiguous float32, or
-    contiguous bfloat16 - widened exactly inside the kernels, never copied."""
-    if not torch.is_tensor(rows) or rows.dtype not in (torch.float32, torch.bfloat16) or not rows.is_contiguous():
-        raise ValueError(f"{who}: rows must be a contiguous float32 or bfloat16 tensor, read in place "
-                         f"(got {getattr(rows, 'dtype', type(rows).__name__)})")
-    return _lib.FEAT_BF16 if rows.dtype == torch.bfloat16 else _lib.FEAT_F32
-
-
-def _check_f32(who: str, name: str, t: torch.Tensor) -> None:
-    if not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous():
-        raise ValueError(f"{who}: {name} must be a contiguous float32 tensor (got {getattr(t, 'dtype', type(t).__name__)})")
-
-
-def cosine_rows_indexed(x: torch.Tensor, rows: torch.Tensor, index: torch.Tensor, eps: float,
-                        status: Optional[torch.Tensor]) -> torch.Tensor:
-    """`[B, N]` = cos(x[b], rows[index[b, n]]) by `drin_cosine_rows_indexed_fwd`; no gradient.  `rows`: float32, or bfloat16 read
-    in place (`drin_cosine_rows_indexed_fwd_ex`: the bits of the float32 call on `rows.float()`); `x` float32."""
-    B, N = index.shape
-    out = torch.empty(B, N, dtype=torch.float32, device=x.device)
-    if rows.dtype == torch.bfloat16:
-        x = x.detach().contiguous()
-        _check_f32("cosine_rows_indexed", "x", x)
-        _lib.check(_lib.load().drin_cosine_rows_indexed_fwd_ex(_ptr(x), _ptr(rows), _row_dtype("cosine_rows_indexed", rows), _ptr(index),
-                                                               rows.shape[0], _ptr(out), B, N, x.shape[1], eps, _ptr(status),
-                                                               _stream(x.device)))
-        return out
-    _lib.check(_lib.load().drin_cosine_rows_indexed_fwd(_ptr(x.detach().contiguous()), _ptr(rows), _ptr(index), rows.shape[0], _ptr(out),
-                                                        B, N, x.shape[1], eps, _ptr(status), _stream(x.device)))
-    return out
-
-
-class LinkResult(NamedTuple):
-    """`model.link`: `scores [B, k]` float32 and `rows [B, k]` int64 table rows, best first (the ordering contract of
-    include/drin_hip.h: higher score first, the lower row between equal scores, NaN last)."""
-    scores: torch.Tensor
-    rows: torch.Tensor
-
-
-def row_inv_norms(rows: torch.Tensor, eps: float) -> torch.Tensor:
-    """`[E]` float32 = 1 / max(|rows[e]|, eps) by `drin_row_inv_norms`; bfloat16 `rows` are read in place (`drin_row_inv_norms_ex`:
-    the bits of the float32 call on `rows.float()`)."""
-    out = torch.empty(rows.shape[0], dtype=torch.float32, device=rows.device)
-    if rows.dtype == torch.bfloat16:
-        _lib.check(_lib.load().drin_row_inv_norms_ex(_ptr(rows), _row_dtype("row_inv_norms", rows), rows.shape[0], rows.shape[1], eps,
-                                                     _ptr(out), _stream(rows.device)))
-        return out
-    _lib.check(_lib.load().drin_row_inv_norms(_ptr(rows), rows.shape[0], rows.shape[1], eps, _ptr(out), _stream(rows.device)))
-    return out
-
-
-def table_topk(x: torch.Tensor, rows: torch.Tensor, inv_norms: torch.Tensor, k: int, eps: float, precision: str,
-               chunk_entities: int = 0) -> LinkResult:
-    """The k best of `rows [E, D]` for every `x [B, D]` by cosine (`drin_table_topk`); `inv_norms`: `row_inv_norms(rows, eps)`.
-    bfloat16 `rows` are read in place (`drin_table_topk_ex`): they link exactly as `rows.float()` would; `x`
-    and `inv_norms` stay float32."""
-    lib = _lib.load()
-    (B, D), E = x.shape, rows.shape[0]
-    if rows.dtype == torch.bfloat16:
-        dtype = _row_dtype("table_topk", rows)
-        _check_f32("table_topk", "x", x)
-        _check_f32("table_topk", "inv_norms", inv_norms)
-        nbytes = lib.drin_table_topk_workspace_bytes_ex(B, E, D, k, chunk_entities, dtype, PRECISIONS[precision])
-        if nbytes == 0:
-            _lib.check(_lib.E_SHAPE)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-        scores = torch.empty(B, k, dtype=torch.float32, device=x.device)
-        best = torch.empty(B, k, dtype=torch.int64, device=x.device)
-        _lib.check(lib.drin_table_topk_ex(_ptr(x), _ptr(rows), dtype, _ptr(inv_norms), E, B, D, k, eps, PRECISIONS[precision], chunk_entities,
-                                          _ptr(ws), nbytes, _ptr(scores), _ptr(best), _stream(x.device)))
-        return LinkResult(scores, best)
-    nbytes = lib.drin_table_topk_workspace_bytes(B, E, D, k, chunk_entities)
-    if nbytes == 0:
-        _lib.check(_lib.E_SHAPE)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-    scores = torch.empty(B, k, dtype=torch.float32, device=x.device)
-    best = torch.empty(B, k, dtype=torch.int64, device=x.device)
-    _lib.check(lib.drin_table_topk(_ptr(x), _ptr(rows), _ptr(inv_norms), E, B, D, k, eps, PRECISIONS[precision], chunk_entities, _ptr(ws),
-                                   nbytes, _ptr(scores), _ptr(best), _stream(x.device)))
-    return LinkResult(scores, best)
-
-
-def table_topk_sum(terms: Sequence, k: int, eps: float, precision: str, chunk_entities: int = 0) -> LinkResult:
-    """The k best table rows for every mention by a SUM of cosines (`drin_table_topk_sum`):
-    `score(b, e) = sum_s weight_s * cos(x_s[b], rows_s[e])`.  `terms`: 1 to 4 of `(x [B, D_s], rows [E, D_s], inv_norms [E],
-    weight)` - contiguous float32 tensors on one GPU, `inv_norms = row_inv_norms(rows, eps)`; the terms share `B` and `E`, not
-    their width.  `rows` alone may be contiguous bfloat16 instead, term by term, read in place (`drin_table_topk_sum_ex`,
-    DESIGN.md section 34: such a term links exactly as `rows.float()` would).  A term of weight 0 is dropped before any launch and its three tensors may be `None`.  The returned scores are
-    the fp32 chain `w_0 c_0 + w_1 c_1 + ...` over `cosine_rows_indexed` of each live term on the returned rows, bit for bit."""
-    lib = _lib.load()
-    terms = list(terms)
-    arr = (_lib.DrinTopkTermC * max(len(terms), 1))()
-    dtypes = (C.c_int32 * max(len(terms), 1))()
-    live = None
-    for s, (x, rows, inv, weight) in enumerate(terms[:len(arr)]):
-        arr[s].weight = float(weight)
-        if float(weight) == 0.0:
-            continue
-        # the library trusts the extents it is given: what the kernels index is settled here
-        for name, t in (("x", x), ("rows", rows), ("inv_norms", inv)):
-            stored = (torch.float32, torch.bfloat16) if name == "rows" else (torch.float32,)   # rows alone may be stored as bf16
-            if not torch.is_tensor(t) or t.dtype not in stored or not t.is_contiguous() or t.device.type != "cuda":
-                raise ValueError(f"table_topk_sum: term {s}: {name} must be a contiguous float32 tensor on the GPU"
-                                 + (" (rows: or bfloat16, read in place)" if name == "rows" else ""))
-        dtypes[s] = _lib.FEAT_BF16 if rows.dtype == torch.bfloat16 else _lib.FEAT_F32
-        if live is None:
-            live = (x.shape[0], rows.shape[0], x.device)
-        if (x.dim() != 2 or rows.dim() != 2 or x.shape[1] != rows.shape[1] or x.shape[0] != live[0] or rows.shape[0] != live[1]
-                or tuple(inv.shape) != (live[1],) or any(t.device != live[2] for t in (x, rows, inv))):
-            raise ValueError(f"table_topk_sum: term {s}: x {tuple(x.shape)}, rows {tuple(rows.shape)}, inv_norms {tuple(inv.shape)} must be "
-                             f"[B = {live[0]}, D], [E = {live[1]}, D], [E] on one device")
-        arr[s].x, arr[s].rows, arr[s].row_inv_norms, arr[s].width = x.data_ptr(), rows.data_ptr(), inv.data_ptr(), x.shape[1]
-    if live is None:                                                       # no live term, or none at all: the library names the reason
-        _lib.check(lib.drin_table_topk_sum(arr, len(terms), 1, 1, k, eps, PRECISIONS[precision], chunk_entities, None, 0, None, None, None))
-        raise _lib.DrinError(_lib.E_SHAPE, "drin_table_topk_sum: no live term")
-    B, E, dev = live
-    if any(d == _lib.FEAT_BF16 for d in dtypes):
-        nbytes = lib.drin_table_topk_sum_workspace_bytes_ex(arr, dtypes, len(terms), B, E, k, chunk_entities, PRECISIONS[precision])
-        if nbytes == 0:
-            _lib.check(_lib.E_SHAPE)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        scores = torch.empty(B, k, dtype=torch.float32, device=dev)
-        best = torch.empty(B, k, dtype=torch.int64, device=dev)
-        _lib.check(lib.drin_table_topk_sum_ex(arr, dtypes, len(terms), E, B, k, eps, PRECISIONS[precision], chunk_entities, _ptr(ws), nbytes,
-                                              _ptr(scores), _ptr(best), _stream(dev)))
-        return LinkResult(scores, best)
-    nbytes = lib.drin_table_topk_sum_workspace_bytes(arr, len(terms), B, E, k, chunk_entities)
-    if nbytes == 0:
-        _lib.check(_lib.E_SHAPE)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    scores = torch.empty(B, k, dtype=torch.float32, device=dev)
-    best = torch.empty(B, k, dtype=torch.int64, device=dev)
-    _lib.check(lib.drin_table_topk_sum(arr, len(terms), E, B, k, eps, PRECISIONS[precision], chunk_entities, _ptr(ws), nbytes, _ptr(scores),
-                                       _ptr(best), _stream(dev)))
-    return LinkResult(scores, best)
-
-
 class _TableState:
     """What a model keeps for its table form (per process: not part of the state dict)."""
 
@@ -261,8 +124,7 @@ class _TableState:
         self.inv_key = None
         self.pooled: Optional[torch.Tensor] = None    # per-entity token means [E, D] of train()
         self.pooled_key = None
-        self.status = {}                              # device -> int32[4]
-        self.watch, self.pool = [], []                # read-backs in flight / landed (pinned host words, event) pairs
+        self.watch = IndexWatch(raise_bad_index)      # the status words per device and their read-backs (table_ops.py)
 
 
 class TableForm:
@@ -366,26 +228,7 @@ class TableForm:
         """Raise `IndexError` if any table-form call since the last check met a candidate row outside `[0, E - 1]`, naming the
         row and the pair.  `wait=True` synchronises with the device; `wait=False` only looks at read-backs that have landed.
         `model.validate_indices = True` (or `DRIN_VALIDATE=1`) checks after every call instead."""
-        st, bad = self._tf, None
-        if wait:
-            st.watch.clear()
-            for t in st.status.values():
-                w = t.cpu()
-                if int(w[0]) != 0:
-                    bad = bad or w.tolist()
-                    t.zero_()
-        else:
-            while st.watch and st.watch[0][1].query():
-                host, ev = st.watch.pop(0)
-                if int(host[0]) != 0 and bad is None:
-                    bad = host.tolist()
-                st.pool.append((host, ev))
-            if bad is not None:
-                st.watch.clear()
-                for t in st.status.values():
-                    t.zero_()
-        if bad is not None:
-            raise_bad_index(bad)
+        self._tf.watch.check(wait)
 
     # ---- what the models' forwards call ---------------------------------------------------------------------------
     def _table_form(self, batch) -> Optional[GhmfcIndexedBatch]:
@@ -414,7 +257,7 @@ class TableForm:
             raise ValueError(f"ghmfc table form: candidates {tuple(cand.shape)} are not [B, {self.cfg.num_candidates}]")
         if self._device(tb.table.text) != dev or cand.device != dev:
             raise RuntimeError(f"ghmfc table form: the model, the candidates and the table must be on one device (table: {dev})")
-        if self._tf.watch and not torch.cuda.is_current_stream_capturing():
+        if self._tf.watch.pending() and not torch.cuda.is_current_stream_capturing():
             self.check_indices(wait=False)
         return GhmfcIndexedBatch(tb.mention, tb.table, cand.detach().to(torch.int64).contiguous())
 
@@ -424,24 +267,11 @@ class TableForm:
         return model_device(self, *like)
 
     def _status_words(self, device) -> torch.Tensor:
-        t = self._tf.status.get(device)
-        if t is None:
-            t = self._tf.status[device] = torch.zeros(4, dtype=torch.int32, device=device)
-        return t
+        return self._tf.watch.words(device)
 
     def _watch_indices(self, device) -> None:
-        """After a table-form call: raise at once when validating eagerly, else start an asynchronous read-back of the status
-        words that the next call / `check_indices(wait=False)` looks at once it has landed."""
-        if torch.cuda.is_current_stream_capturing():
-            return
-        if self.validate_indices:
-            self.check_indices()
-            return
-        st = self._tf
-        host, ev = st.pool.pop() if st.pool else (torch.empty(4, dtype=torch.int32, pin_memory=True), torch.cuda.Event())
-        host.copy_(self._status_words(device), non_blocking=True)
-        ev.record(torch.cuda.current_stream(device))
-        st.watch.append((host, ev))
+        """After a table-form call (`IndexWatch.after_call`): the eager check, or an asynchronous read-back of the status words."""
+        self._tf.watch.after_call(device, self.validate_indices)
 
     def _entity_key(self, table: EntityTable):
         """what the per-entity rows depend on: the entity weights' versions (none for an Identity final layer), the pooling, the

@@ -18,8 +18,10 @@ from typing import Dict, List, NamedTuple, Optional, Sequence
 import torch
 from torch import nn
 
-from . import _lib
+from . import _lib, row_ops
 from .config import DrinConfig, default_config
+from .table_ops import (MAX_CALL_MENTIONS, IndexWatch, LinkResult, cross_modal_edges, decode_status, in_slices, row_inv_norms, table_topk,
+                        table_topk_sum)
 
 
 # ---- parameter containers mirroring the reference's module tree (keys of SURVEY.md §8b) -------------
@@ -335,28 +337,14 @@ class IndexedBatch:
             raise RuntimeError("IndexedBatch.from_clip runs on an AMD GPU only (no CPU / eager fallback); move the batch to 'cuda'")
         if any(t.device != dev for t in (clip_image, clip_text, table.clip_text, table.clip_image)):
             raise RuntimeError("IndexedBatch.from_clip: the candidates, the mentions' CLIP rows and the table's must be on one device")
-        index = candidates.detach().to(torch.int64).contiguous()
-        xi, xt = clip_image.detach().contiguous(), clip_text.detach().contiguous()
-        miet = torch.empty(B, N, dtype=torch.float32, device=dev)
-        mtei = torch.empty(B, N, dtype=torch.float32, device=dev)
-        if B > 0 and N > 0:
-            lib = _lib.load()
+        launches = B > 0 and N > 0
+        status = None
+        if launches:
             status = model._status_words(dev) if model is not None else torch.zeros(4, dtype=torch.int32, device=dev)
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            step = (type(model) if model is not None else Model).MAX_CALL_MENTIONS
-            stored_bf16 = table.clip_text.dtype == torch.bfloat16      # (set_clip: both tables share the dtype)
-            for b0 in range(0, B, step):
-                sl = slice(b0, min(B, b0 + step))
-                if stored_bf16:
-                    _lib.check(lib.drin_cross_modal_edges_ex(_ptr(xi[sl]), _ptr(xt[sl]), _ptr(table.clip_text), _ptr(table.clip_image),
-                                                             _lib.FEAT_BF16, _ptr(index[sl]), table.num_entities, sl.stop - b0, N, width,
-                                                             cfg.clip_logit_scale, cfg.cosine_eps, _ptr(miet[sl]), _ptr(mtei[sl]),
-                                                             _ptr(status), stream))
-                    continue
-                _lib.check(lib.drin_cross_modal_edges(_ptr(xi[sl]), _ptr(xt[sl]), _ptr(table.clip_text), _ptr(table.clip_image),
-                                                      _ptr(index[sl]), table.num_entities, sl.stop - b0, N, width,
-                                                      cfg.clip_logit_scale, cfg.cosine_eps, _ptr(miet[sl]), _ptr(mtei[sl]),
-                                                      _ptr(status), stream))
+        miet, mtei = cross_modal_edges(clip_image, clip_text, table.clip_text, table.clip_image, candidates.detach().to(torch.int64),
+                                       cfg.clip_logit_scale, cfg.cosine_eps, status,
+                                       (type(model) if model is not None else Model).MAX_CALL_MENTIONS)
+        if launches:
             if model is not None:
                 model._watch_indices(dev)
             elif not torch.cuda.is_current_stream_capturing():
@@ -801,7 +789,7 @@ class Model(nn.Module):
     # grouping of the per-mention sums depends on the size of the call - csrc/fused_forward.hip: 16 / 48 / whole-list
     # workgroups - so a mention's scores in calls of different sizes agree to fp32 re-association, <= 5e-6, and are the same
     # bits every run within one call size); the one-workgroup-per-(mention, chunk) grids of the row kernels stop at 65 535 mentions
-    MAX_CALL_MENTIONS = 32768
+    MAX_CALL_MENTIONS = MAX_CALL_MENTIONS     # (table_ops.py: the primitives' default slice)
     flat_buckets = True       # flatten_parameters / grad_bucket / LibraryAdam's flat form are built (EncoderModel: not)
 
     def __new__(cls, cfg: Optional[DrinConfig] = None, *args, **kwargs):
@@ -840,9 +828,7 @@ class Model(nn.Module):
         self._layout = None
         # table-form calls: where the kernels report a candidate row outside the entity tables (drin_batch.index_status)
         self.validate_indices = os.environ.get("DRIN_VALIDATE", "") not in ("", "0")
-        self._index_status: Dict[torch.device, torch.Tensor] = {}
-        self._index_watch: List = []                          # (host copy, event): async read-backs of calls still in flight
-        self._index_pool: List = []                           # landed (pinned host words, event) pairs, re-used
+        self._index_watch = IndexWatch(Model._raise_bad_index)   # the status words per device and their read-backs (table_ops.py)
         self.register_load_state_dict_post_hook(_invalidate_after_load)
         modes = {"f32": _lib.PREC_F32, "bf16x3": _lib.PREC_BF16X3, "bf16x3_all": _lib.PREC_BF16X3_ALL, "bf16x3_if16": _lib.PREC_BF16X3_IF16}
         if precision not in modes:
@@ -944,71 +930,37 @@ class Model(nn.Module):
 
     def __getstate__(self):
         # copy.deepcopy / pickle of the Module: the index watch holds HIP events and pinned buffers of calls in flight - per-process
-        # bookkeeping, not state (a copy starts with none; its first table-form call makes its own status words)
+        # bookkeeping, not state (IndexWatch copies empty; the copy's first table-form call makes its own status words)
         state = self.__dict__.copy()
-        state["_index_watch"], state["_index_pool"], state["_index_status"] = [], [], {}
         state.pop("_link_inv", None)                          # (and link's norms cache holds the caller's `rows`)
         state.pop("_link_edges_inv", None)
         return state
 
     # ---- candidate rows outside the entity tables (drin/data.py:87-93 raises IndexError) ------------------------------
     def _status_words(self, device: torch.device) -> torch.Tensor:
-        t = self._index_status.get(device)
-        if t is None:
-            t = self._index_status[device] = torch.zeros(4, dtype=torch.int32, device=device)
-        return t
+        return self._index_watch.words(device)
 
     @staticmethod
     def _raise_bad_index(words) -> None:
-        w = [int(x) for x in words]
-        value = ((w[3] & 0xFFFFFFFF) << 32 | (w[2] & 0xFFFFFFFF))
-        value -= (1 << 64) if value >= (1 << 63) else 0
-        what = f"row {value} at pair {w[1]} (b * N + n)" if (w[2] or w[3]) else "a row of a training batch"
+        _flag, pair, value = decode_status(words)
+        what = f"row {value} at pair {pair} (b * N + n)" if value != 0 else "a row of a training batch"
         raise IndexError(f"IndexedBatch.candidates: {what} is outside the entity tables (it was clamped: the scores of that call are of the "
                          f"WRONG entity there); the reference's fancy index, drin/data.py:87-93, raises here too")
 
     def _watch_indices(self, device: torch.device) -> None:
         """After a table-form call: raise at once when validating eagerly, else start an asynchronous read-back of the status
         words which `forward` / `check_indices` look at once it has landed (no synchronisation is added to the step)."""
-        if torch.cuda.is_current_stream_capturing():          # inside a graph capture: no read-back, no event (the status words are still
-            return                                            # written by the replayed kernels: check_indices() after a replay sees them)
-        if self.validate_indices:
-            self.check_indices()
-            return
-        host, ev = self._index_pool.pop() if self._index_pool else (torch.empty(4, dtype=torch.int32, pin_memory=True), torch.cuda.Event())
-        host.copy_(self._status_words(device), non_blocking=True)
-        ev.record(torch.cuda.current_stream(device))
-        self._index_watch.append((host, ev))
+        self._index_watch.after_call(device, self.validate_indices)
 
     def check_indices(self, wait: bool = True) -> None:
         """Raise `IndexError` if any table-form call since the last check met a candidate row outside `[0, E - 1]`.  `wait=True`
         synchronises with the device (call it where the loop synchronises anyway: `MELRunner.run_epoch` does, at the epoch's
         end); `wait=False` only looks at read-backs that have already landed.  `Model(...).validate_indices = True` (or
         `DRIN_VALIDATE=1`) checks after every call instead - the reference's behaviour, at one synchronisation per call."""
-        bad = None
-        if wait:
-            self._index_watch.clear()
-            for t in self._index_status.values():
-                w = t.cpu()
-                if int(w[0]) != 0 and bad is None:
-                    bad = w.tolist()
-                if int(w[0]) != 0:
-                    t.zero_()
-        else:
-            while self._index_watch and self._index_watch[0][1].query():
-                host, ev = self._index_watch.pop(0)
-                if int(host[0]) != 0 and bad is None:
-                    bad = host.tolist()
-                self._index_pool.append((host, ev))               # pinned words and event are re-used by the next call
-            if bad is not None:
-                self._index_watch.clear()
-                for t in self._index_status.values():
-                    t.zero_()
-        if bad is not None:
-            self._raise_bad_index(bad)
+        self._index_watch.check(wait)
 
     def forward(self, batch) -> torch.Tensor:
-        if self._index_watch and not torch.cuda.is_current_stream_capturing():
+        if self._index_watch.pending() and not torch.cuda.is_current_stream_capturing():
             self.check_indices(wait=False)
         B = batch.candidates.shape[0] if isinstance(batch, IndexedBatch) else batch[0].shape[0]
         if B > self.MAX_CALL_MENTIONS:
@@ -1133,7 +1085,7 @@ class Model(nn.Module):
             if text.dtype not in (torch.float32, torch.bfloat16) or not text.is_contiguous():
                 raise ValueError(f"attribute: the token table is read in place and must be contiguous float32 or bfloat16 (got {text.dtype}"
                                  f"{'' if text.is_contiguous() else ', not contiguous'}); convert the EntityTable once")
-        if self._index_watch and not torch.cuda.is_current_stream_capturing():
+        if self._index_watch.pending() and not torch.cuda.is_current_stream_capturing():
             self.check_indices(wait=False)
         B = batch.candidates.shape[0] if isinstance(batch, IndexedBatch) else batch[0].shape[0]
         N = self.cfg.num_candidates_model
@@ -1262,7 +1214,6 @@ class Model(nn.Module):
         widened float32 copies; `tt`'s query is then the span mean of the bfloat16 mention text read in place
         (`drin_mention_rows_fwd`), its table the bfloat16 token-0 copy.  The second stage is the model's forward on the bf16 table
         (route "prepared"; such a table with the cache enabled keeps its `ValueError`)."""
-        from .ghmfc_table import LinkResult, row_inv_norms, table_topk
         if self.training:
             raise RuntimeError("Model.link: ranking is eval() only (no gradient flows through a top-k): call .eval()")
         if first_stage is not None:
@@ -1299,27 +1250,14 @@ class Model(nn.Module):
                 raise ValueError(f"Model.link: N = {N} candidates exceed the table's {rows.shape[0]} entities")
             if rows.device.type != "cuda" or queries.device != rows.device:
                 raise RuntimeError("Model.link runs on an AMD GPU only (no CPU / eager fallback); move queries and rows to 'cuda'")
-            # the inverse norms, per version of the CALLER's tensor: the entry keeps that tensor alive - a key of an address and a
-            # version says nothing once the memory behind it may have been freed and handed out again - and, for a
-            # non-contiguous `rows`, the contiguous copy the norms were taken of (a copy made per call would start at version 0
-            # in whatever block the allocator hands back).  While the entry holds the tensor, an equal address means the same
-            # storage, whose version counter every in-place torch op bumps (writes through `.data`: Model.invalidate())
-            given = rows
-            key = (given.data_ptr(), given._version, tuple(given.shape), tuple(given.stride()), given.dtype, self.cfg.cosine_eps)
-            cached = self.__dict__.get("_link_inv")
-            if cached is None or cached[0] != key:
-                self.__dict__["_link_inv"] = cached = None                # release the stale copy before allocating
-                dense = given.detach().contiguous()
-                self.__dict__["_link_inv"] = cached = (key, row_inv_norms(dense, self.cfg.cosine_eps), given, dense)
-            rows = cached[3]
+            _key, inv, _given, rows = self._norms_entry(self.__dict__, "_link_inv", rows)
             B = queries.shape[0]
             if B == 0:
                 candidates = torch.empty(0, N, dtype=torch.int64, device=rows.device)
             else:
-                step, q = self.MAX_CALL_MENTIONS, queries.detach().contiguous()
-                precision = "f32" if self.precision == _lib.PREC_F32 else "bf16x3"
-                parts = [table_topk(q[b0:b0 + step], rows, cached[1], N, self.cfg.cosine_eps, precision).rows for b0 in range(0, B, step)]
-                candidates = parts[0] if len(parts) == 1 else torch.cat(parts, 0)
+                q, precision = queries.detach().contiguous(), "f32" if self.precision == _lib.PREC_F32 else "bf16x3"
+                candidates = in_slices(B, self.MAX_CALL_MENTIONS,
+                                       lambda sl: table_topk(q[sl], rows, inv, N, self.cfg.cosine_eps, precision).rows)
         if candidates.device.type != "cuda":
             raise RuntimeError("Model.link runs on an AMD GPU only (no CPU / eager fallback); move the batch to 'cuda'")
         candidates = candidates.detach().to(torch.int64).contiguous()
@@ -1338,11 +1276,24 @@ class Model(nn.Module):
                                           _ptr(out_rows[sl]), None, stream))
         return LinkResult(out_scores, out_rows)
 
+    def _norms_entry(self, cache: dict, slot, given: torch.Tensor) -> tuple:
+        """`(key, inverse row norms, given, dense)` of `cache[slot]`, the norms cache of `link`, rebuilt when the key moved.  The
+        norms are per version of the CALLER's tensor: the entry keeps that tensor alive - a key of an address and a version says
+        nothing once the memory behind it may have been freed and handed out again - and, for a non-contiguous `given`, the
+        contiguous copy the norms were taken of (a copy made per call would start at version 0 in whatever block the allocator
+        hands back).  While the entry holds the tensor, an equal address means the same storage, whose version counter every
+        in-place torch op bumps (writes through `.data`: Model.invalidate())."""
+        key = (given.data_ptr(), given._version, tuple(given.shape), tuple(given.stride()), given.dtype, self.cfg.cosine_eps)
+        entry = cache.get(slot)
+        if entry is None or entry[0] != key:
+            cache[slot] = entry = None                                    # release the stale copy before allocating
+            dense = given.detach().contiguous()
+            cache[slot] = entry = (key, row_inv_norms(dense, self.cfg.cosine_eps), given, dense)
+        return entry
+
     def _edge_candidates(self, mention, table: EntityTable, clip_image, clip_text, edge_weights) -> torch.Tensor:
         """`candidates [B, N]` of `link(first_stage="edges")`: the N best table rows by the weighted sum of the tt, ti and it
         cosines (`table_topk_sum`); the checks of that mode."""
-        from . import row_ops
-        from .ghmfc_table import row_inv_norms, table_topk_sum
         weights = self.cfg.gcn_edge_enabled[0:3] if edge_weights is None else tuple(edge_weights)
         if len(weights) != 3:
             raise ValueError(f"Model.link: edge_weights has {len(weights)} entries, expected 3 (tt, ti, it)")
@@ -1380,27 +1331,17 @@ class Model(nn.Module):
                     lambda: table.pooled_text(self.cfg)[1] if table.text.dim() == 3 else table.text),
                    (lambda: clip_text, lambda: table.clip_image),
                    (lambda: clip_image, lambda: table.clip_text))
-        # the inverse norms per version of the table's tensor, under _link_inv's rule: the entry keeps the tensor (and the dense
-        # rows the norms were taken of) alive, so an equal address means the same storage
-        cache = self.__dict__.setdefault("_link_edges_inv", {})
+        cache = self.__dict__.setdefault("_link_edges_inv", {})           # the inverse norms, a slot per edge (_norms_entry's rule)
         terms = []
         for s, (w, (query, rows_of)) in enumerate(zip(weights, sources)):
             if w == 0.0:
                 terms.append((None, None, None, 0.0))
                 continue
-            given = rows_of()
-            key = (given.data_ptr(), given._version, tuple(given.shape), tuple(given.stride()), given.dtype, eps)
-            entry = cache.get(s)
-            if entry is None or entry[0] != key:
-                cache[s] = entry = None                                   # release the stale copy before allocating
-                dense = given.detach().contiguous()
-                cache[s] = entry = (key, row_inv_norms(dense, eps), given, dense)
-            terms.append((query().detach().contiguous(), entry[3], entry[1], w))
+            _key, inv, _given, dense = self._norms_entry(cache, s, rows_of())
+            terms.append((query().detach().contiguous(), dense, inv, w))
         precision = "f32" if self.precision == _lib.PREC_F32 else "bf16x3"
-        step = self.MAX_CALL_MENTIONS
-        parts = [table_topk_sum([(None if x is None else x[b0:b0 + step], r, i, w) for x, r, i, w in terms], N, eps, precision).rows
-                 for b0 in range(0, B, step)]
-        return parts[0] if len(parts) == 1 else torch.cat(parts, 0)
+        return in_slices(B, self.MAX_CALL_MENTIONS, lambda sl: table_topk_sum(
+            [(None if x is None else x[sl], r, i, w) for x, r, i, w in terms], N, eps, precision).rows)
 
     @staticmethod
     def _span_mean_stored(text: torch.Tensor, start: torch.Tensor, end: torch.Tensor) -> torch.Tensor:

@@ -139,6 +139,11 @@ class DrinTopkTermC(C.Structure):     # drin_topk_term: one cosine of drin_table
 
 
 TOPK_MAX_TERMS = 4                                                         # DRIN_TOPK_MAX_TERMS
+TOPK_COSINE, TOPK_RATIO = 0, 1                                             # drin_topk_form.form
+
+
+class DrinTopkFormC(C.Structure):     # drin_topk_form: the form of one term of drin_table_topk_sum_forms' sum
+    _fields_ = [("form", C.c_int32), ("x_mass", C.c_void_p), ("row_mass", C.c_void_p), ("eps", C.c_float)]
 
 
 class DrinGemmRouteC(C.Structure):
@@ -330,6 +335,21 @@ EXPORTS = {
                                                             C.c_int32, C.c_int64, C.c_int32]),
     "drin_table_topk_sum_ex": (C.c_int, [C.POINTER(DrinTopkTermC), C.POINTER(C.c_int32), C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_float,
                                          C.c_int32, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # the image-image edge as a term, the RATIO form:
+    # (obj, score, dtype, n, K, width, eps, out, mass, stream),
+    # (x, x_mass, rows, row_mass, index, num_entities, out, batch, num_candidates, width, eps, index_status, stream),
+    # drin_topk_combine's list with `forms` behind `weights`; drin_table_topk_sum(_workspace_bytes)_ex's lists with `forms` behind `row_dtypes`
+    "drin_object_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p,
+                                   C.c_void_p]),
+    "drin_ratio_rows_indexed_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32,
+                                              C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p]),
+    "drin_topk_combine_forms": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_float),
+                                          C.POINTER(DrinTopkFormC), C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]),
+    "drin_table_topk_sum_forms_workspace_bytes": (C.c_size_t, [C.POINTER(DrinTopkTermC), C.POINTER(C.c_int32), C.POINTER(DrinTopkFormC),
+                                                               C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_int32]),
+    "drin_table_topk_sum_forms": (C.c_int, [C.POINTER(DrinTopkTermC), C.POINTER(C.c_int32), C.POINTER(DrinTopkFormC), C.c_int32, C.c_int64,
+                                            C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p,
+                                            C.c_void_p, C.c_void_p]),
     "drin_rank_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "drin_ghmfc_mention_forward_workspace_bytes": (C.c_size_t, [C.POINTER(DrinGhmfcConfigC)]),
     "drin_ghmfc_mention_forward": (C.c_int, [C.POINTER(DrinGhmfcConfigC), C.POINTER(DrinGhmfcBatchC), C.POINTER(DrinGhmfcParamsC), C.c_void_p,

@@ -11,6 +11,8 @@
 //   k_widen_rows      bf16 rows -> the same values as fp32 (a chunk of a bf16-stored table on the widen route)
 //   k_rank_rows       per mention: the first k of n caller-given (score, row) pairs by the contract, with the input column of each
 //                     (drin_rank_rows: the rerank behind a second-stage scoring)
+//   k_object_rows     the image-image edge as a term (section 36): the score-weighted sum of one side's normalised object rows and the
+//                     sum of its scores; k_topk_forms_combine: the combine of a call with a RATIO term; k_ratio_gather: its re-score
 // and the entry points drin_row_inv_norms, drin_topk_update, drin_table_topk(_workspace_bytes), drin_rank_rows, with the _ex twins that
 // read table rows STORED as bf16 in place (section 34: k_row_inv_norms<__bf16>, the product routed by the GEMM module, the re-score
 // k_cosine_gather<__bf16>).  A storage-templated kernel has ONE launcher that takes the row dtype.  The workspace of drin_table_topk
@@ -143,6 +145,157 @@ __global__ void __launch_bounds__(256) k_weighted_cosine_sum(const float* __rest
     for (int s = 1; s < DRIN_TOPK_MAX_TERMS; ++s)          // constant indices into the argument struct
       if (s < S) acc = add4_rn(acc, mul4_rn(ld4(cos + ((int64_t)s * n4 + i) * 4), cw.w[s]));
     st4(out + i * 4, acc);
+  }
+}
+
+// ---- the RATIO form: the image-image edge as a term -----------------------------------------------------
+// out[r, :] = sum_j score[r, j] obj[r, j, :] / max(|obj[r, j, :]|, eps), mass[r] = sum_j score[r, j]: the side of model.py:84-92
+// that belongs to one mention (K = Km) or one entity (K = Ke).  One wave per output row, four per workgroup, the rest by grid
+// stride; lanes take column quads lane, lane + 64, ... as k_row_inv_norms does.  REG (R4 <= 512): an object row is read ONCE into
+// eight float4 slots per lane (k_miei_lds keeps its row the same way) and stays there between its norm and its scaled
+// accumulation.  Past that the wave takes the K scales first (lane j keeps scale j) and reads every row a second time.  Either way:
+// yy in the lane order of k_row_inv_norms, one division per object row, fp32 FMAs and the score sum in ascending j.
+// T: float, or __bf16 for objects and scores stored as bf16 (widened exactly: the bits of the float instantiation on the widened values).
+constexpr int kObjectMaxK = 16;
+template <typename T, bool REG>
+__global__ void __launch_bounds__(256) k_object_rows(const T* __restrict__ obj, const T* __restrict__ score, int64_t n, int K, int R4,
+                                                     float eps, float* __restrict__ out, float* __restrict__ mass) {
+  const int lane = threadIdx.x & 63;
+  for (int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < n; r += (int64_t)gridDim.x * 4) {
+    const T* rows = obj + r * K * (int64_t)R4 * 4;
+    const T* sc = score + r * K;
+    float* dst = out + r * (int64_t)R4 * 4;
+    float m = 0.f;
+    if (REG) {
+      float4 acc[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) acc[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+      for (int j = 0; j < K; ++j) {
+        const T* yr = rows + j * (int64_t)R4 * 4;
+        float4 v[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          const int c4 = lane + 64 * k;
+          v[k] = c4 < R4 ? ld4_stream(yr + c4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);   // read once
+        }
+        float yy = 0.f;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) yy += dot4(v[k], v[k]);   // (an empty slot adds +0: the lane loop's sum)
+        yy = wave_sum(yy);
+        const float w = (float)sc[j];
+        const float s = w / fmaxf(sqrtf(yy), eps);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) acc[k] = fma4(s, v[k], acc[k]);
+        m += w;
+      }
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const int c4 = lane + 64 * k;
+        if (c4 < R4) st4(dst + c4 * 4, acc[k]);
+      }
+    } else {
+      float mine = 0.f;                                      // lane j keeps the scale of object row j (K <= 16 < 64)
+      for (int j = 0; j < K; ++j) {
+        const T* yr = rows + j * (int64_t)R4 * 4;
+        float yy = 0.f;
+        for (int c4 = lane; c4 < R4; c4 += 64) {
+          const float4 b = ld4(yr + c4 * 4);
+          yy += dot4(b, b);
+        }
+        yy = wave_sum(yy);
+        const float w = (float)sc[j];
+        const float s = w / fmaxf(sqrtf(yy), eps);
+        if (lane == j) mine = s;
+        m += w;
+      }
+      for (int c0 = 0; c0 < R4; c0 += 64) {                  // wave-uniform trips: the scales are read across lanes
+        const int c4 = c0 + lane;
+        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int j = 0; j < K; ++j) {
+          const float s = __shfl(mine, j);
+          if (c4 < R4) acc = fma4(s, ld4(rows + (j * (int64_t)R4 + c4) * 4), acc);
+        }
+        if (c4 < R4) st4(dst + c4 * 4, acc);
+      }
+    }
+    if (lane == 0) mass[r] = m;
+  }
+}
+
+// x_mass [B] -> [Bp], zeros behind: the per-mention factor region of a RATIO term
+__global__ void __launch_bounds__(256) k_pad_mass(const float* __restrict__ x, float* __restrict__ out, int B, int Bp) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < Bp) out[i] = i < B ? x[i] : 0.f;
+}
+
+// The combine with a form per term (bit s of ratio_mask: term s is a RATIO): a COSINE term is k_topk_combine's step, with its
+// sequence and bits; a RATIO term reads the masses where the other reads inverse norms and factors - t.inv[s] = row_mass at the
+// chunk's first row, t.scale[s] = x_mass padded to ld - and is d = row_mass[c] x_mass[b]; d = d + eps; t = block / d; t = t w,
+// each rounded to fp32 on its own, the divide correctly rounded.  The mask is uniform over the launch: scalar branches.
+struct FormTerms {
+  CombineTerms t;
+  float eps[DRIN_TOPK_MAX_TERMS];
+  uint32_t ratio_mask;
+};
+__device__ __forceinline__ float4 div4_rn(float4 a, float4 b) {
+#pragma clang fp contract(off)
+  return make_float4(a.x / b.x, a.y / b.y, a.z / b.z, a.w / b.w);
+}
+template <int S>
+__global__ void __launch_bounds__(256) k_topk_forms_combine(FormTerms ft, float* out, int64_t ld, int64_t cols, int tx_log2) {
+  const CombineTerms& t = ft.t;
+  const int64_t q4 = ((int64_t)blockIdx.x << tx_log2 | (threadIdx.x & ((1 << tx_log2) - 1))) * 4;   // first mention of the quad
+  if (q4 >= ld) return;                                   // no barrier below
+  const int ty = threadIdx.x >> tx_log2, rows_tall = 256 >> tx_log2;
+  float4 f[S];                                            // COSINE: scale x weight; RATIO: the mentions' masses
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+    const float4 g = ld4(t.scale[s] + q4);
+    f[s] = (ft.ratio_mask >> s & 1u) ? g : mul4_rn(g, t.weight[s]);
+  }
+  for (int64_t c = (int64_t)blockIdx.y * rows_tall + ty; c < cols; c += (int64_t)gridDim.y * rows_tall) {
+    float4 v[S];
+#pragma unroll
+    for (int s = 0; s < S; ++s) v[s] = ld4(t.block[s] + c * ld + q4);
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+      float4 term;
+      if (ft.ratio_mask >> s & 1u) {
+        const float e = ft.eps[s];
+        const float4 d = add4_rn(mul4_rn(f[s], t.inv[s][c]), make_float4(e, e, e, e));
+        term = mul4_rn(div4_rn(v[s], d), t.weight[s]);
+      } else {
+        term = mul4_rn(mul4_rn(v[s], t.inv[s][c]), f[s]);
+      }
+      acc = s == 0 ? term : add4_rn(acc, term);
+    }
+    st4(out + c * ld + q4, acc);
+  }
+}
+
+// out[b, n] = (x[b] . rows[index[b, n]]) / (x_mass[b] row_mass[index[b, n]] + eps): k_cosine_gather's wave per pair, lane loop, dot4 and
+// wave_sum of xy on a clamped row, then the ratio - product, sum and divide rounded one by one (the combine's sequence).
+__global__ void __launch_bounds__(256) k_ratio_gather(const float* __restrict__ x, const float* __restrict__ x_mass,
+                                                      const float* __restrict__ rows, const float* __restrict__ row_mass,
+                                                      const int64_t* __restrict__ index, int64_t num_rows, float* __restrict__ out,
+                                                      int64_t pairs, int N, int D4, float eps, int32_t* status, int64_t pair_base) {
+  int64_t p, b;
+  if (!wave_pair(pairs, N, p, b)) return;
+  const int lane = threadIdx.x & 63;
+  const int64_t raw = index[p];
+  const int64_t e = raw < 0 ? 0 : (raw >= num_rows ? num_rows - 1 : raw);
+  if (e != raw && lane == 0) report_bad_index(status, pair_base + p, raw);
+  const float* xr = x + b * (int64_t)D4 * 4;
+  const float* yr = rows + e * (int64_t)D4 * 4;
+  float xy = 0.f;
+  for (int c4 = lane; c4 < D4; c4 += 64) xy += dot4(ld4(xr + c4 * 4), ld4(yr + c4 * 4));
+  xy = wave_sum(xy);
+  if (lane == 0) {
+#pragma clang fp contract(off)
+    float d = x_mass[b] * row_mass[e];
+    d = d + eps;
+    out[p] = xy / d;
   }
 }
 
@@ -512,16 +665,96 @@ int launch_weighted_cosine_sum(const float* cos, int S, int64_t n, const ChainWe
   });
 }
 
+// ---- the RATIO form: launchers ------------------------------------------------------------------------------------------------
+// the combine of a call with at least one RATIO term (none: launch_topk_combine, the old launch); the grid is launch_topk_combine's
+int launch_topk_forms_combine(const FormTerms& ft, int S, float* out, int64_t ld, int64_t cols, hipStream_t st) {
+  const int64_t quads = ld / 4;
+  int tx_log2 = 0;
+  while (tx_log2 < 8 && ((int64_t)1 << tx_log2) < quads) ++tx_log2;
+  const int64_t rows_tall = 256 >> tx_log2;
+  const int64_t gx = cdiv(quads, (int64_t)1 << tx_log2);
+  int64_t gy = cdiv(cols, rows_tall * 8);
+  gy = gy < 1 ? 1 : (gy > kMaxGridY ? kMaxGridY : gy);
+  auto kernel = S == 1 ? k_topk_forms_combine<1> : S == 2 ? k_topk_forms_combine<2> : S == 3 ? k_topk_forms_combine<3> : k_topk_forms_combine<4>;
+  return timed(DRIN_KC_EDGE, st, "k_topk_forms_combine", [&] {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, st, ft, out, ld, cols, tx_log2);
+  });
+}
+
+int launch_pad_mass(const float* x_mass, float* out, int B, int Bp, hipStream_t st) {
+  return timed(DRIN_KC_EDGE, st, "k_pad_mass", [&] {
+    hipLaunchKernelGGL(k_pad_mass, dim3((unsigned)cdiv(Bp, 256)), dim3(256), 0, st, x_mass, out, B, Bp);
+  });
+}
+
+int launch_ratio_gather(const float* x, const float* x_mass, const float* rows, const float* row_mass, const int64_t* index, int64_t num_rows,
+                        float* out, int B, int N, int D, float eps, int32_t* status, hipStream_t st) {
+  const int64_t pairs = (int64_t)B * N;
+  if (pairs <= 0) return DRIN_OK;
+  return timed(DRIN_KC_EDGE, st, "k_ratio_gather", [&] {
+    hipLaunchKernelGGL(k_ratio_gather, pair_grid(B, N), dim3(256), 0, st, x, x_mass, rows, row_mass, index, num_rows, out, pairs, N, D / 4, eps,
+                       status, (int64_t)0);
+  });
+}
+
+// dtype: how objects and scores are stored - the instantiation and the timer's name; rows by grid stride: no cap on n to slice for
+template <typename T>
+int launch_object_rows_as(const char* name, const void* obj, const void* score, int64_t n, int K, int R, float eps, float* out, float* mass,
+                          hipStream_t st) {
+  const int64_t blocks = row_blocks(n);
+  auto kernel = R / 4 <= 512 ? k_object_rows<T, true> : k_object_rows<T, false>;
+  return timed(DRIN_KC_POOL, st, name, [&] {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, st, static_cast<const T*>(obj), static_cast<const T*>(score), n, K, R / 4, eps,
+                       out, mass);
+  });
+}
+int launch_object_rows(const void* obj, const void* score, int dtype, int64_t n, int K, int R, float eps, float* out, float* mass, hipStream_t st) {
+  if (dtype != DRIN_FEAT_BF16) return launch_object_rows_as<float>("k_object_rows", obj, score, n, K, R, eps, out, mass, st);
+  return launch_object_rows_as<__bf16>("k_object_rows_bf16", obj, score, n, K, R, eps, out, mass, st);
+}
+
+bool is_finite32(float v) { return v - v == 0.0f; }
+
 // The live terms of a call, in order: a term of weight 0 is dropped here, before anything looks at its pointers.  `pointers`:
 // also NULL and alignment of the live terms' three arrays (the size query reads widths and weights only).
 struct LiveTerms {
   drin_topk_term term[DRIN_TOPK_MAX_TERMS];
   int widths[DRIN_TOPK_MAX_TERMS];
   int dtypes[DRIN_TOPK_MAX_TERMS];   // how term s stores its rows (row_dtypes of the *_ex twins; DRIN_FEAT_F32 without them)
+  drin_topk_form form[DRIN_TOPK_MAX_TERMS];   // the form of term s (forms of the *_forms entry points; DRIN_TOPK_COSINE without them)
+  uint32_t ratio_mask = 0;           // bit s: live term s is a DRIN_TOPK_RATIO
   int S = 0;
 };
-// row_dtypes: HOST array [num_terms] or NULL (all fp32); a dropped term's entry is not read
-int live_terms(const char* who, const drin_topk_term* terms, int num_terms, bool pointers, LiveTerms* out, const int32_t* row_dtypes = nullptr) {
+// the form entry of term s, checked: form, that a RATIO term's rows are fp32, eps, and (`pointers`) its two mass arrays
+int check_form(const char* who, int s, const drin_topk_form& f, int dtype, bool pointers) {
+  if (f.form != DRIN_TOPK_COSINE && f.form != DRIN_TOPK_RATIO) {
+    set_error("%s: term %d: form %d is not DRIN_TOPK_COSINE / DRIN_TOPK_RATIO", who, s, f.form);
+    return DRIN_E_UNSUPPORTED;
+  }
+  if (f.form == DRIN_TOPK_COSINE) return DRIN_OK;
+  if (dtype != DRIN_FEAT_F32) {
+    set_error("%s: term %d: the rows of a DRIN_TOPK_RATIO term are fp32 (row dtype %d)", who, s, dtype);
+    return DRIN_E_UNSUPPORTED;
+  }
+  if (!is_finite32(f.eps)) {
+    set_error("%s: term %d: eps is not finite", who, s);
+    return DRIN_E_SHAPE;
+  }
+  if (!pointers) return DRIN_OK;
+  if (!f.x_mass || !f.row_mass) {
+    set_error("%s: term %d: %s is NULL", who, s, !f.x_mass ? "x_mass" : "row_mass");
+    return DRIN_E_NULL;
+  }
+  if ((reinterpret_cast<uintptr_t>(f.x_mass) & 3u) != 0 || (reinterpret_cast<uintptr_t>(f.row_mass) & 3u) != 0) {
+    set_error("%s: term %d: x_mass and row_mass must be 4-byte aligned", who, s);
+    return DRIN_E_ALIGN;
+  }
+  return DRIN_OK;
+}
+// row_dtypes: HOST array [num_terms] or NULL (all fp32); forms: HOST array [num_terms] or NULL (all cosines); a dropped term's
+// entries are not read
+int live_terms(const char* who, const drin_topk_term* terms, int num_terms, bool pointers, LiveTerms* out, const int32_t* row_dtypes = nullptr,
+               const drin_topk_form* forms = nullptr) {
   if (!terms) {
     set_error("%s: terms is NULL", who);
     return DRIN_E_NULL;
@@ -540,9 +773,14 @@ int live_terms(const char* who, const drin_topk_term* terms, int num_terms, bool
     }
     const int dtype = row_dtypes != nullptr ? row_dtypes[s] : DRIN_FEAT_F32;
     DRIN_TRY(check_row_dtype(who, dtype, t.width));
+    drin_topk_form form = {};   // DRIN_TOPK_COSINE
+    if (forms != nullptr) form = forms[s];
+    DRIN_TRY(check_form(who, s, form, dtype, pointers));
+    const bool ratio = form.form == DRIN_TOPK_RATIO;
     if (pointers) {
-      const NamedPtr ptrs[] = {{"x", t.x, true}, {"rows", t.rows, true}, {"row_inv_norms", t.row_inv_norms, true}};
+      const NamedPtr ptrs[] = {{"x", t.x, true}, {"rows", t.rows, true}, {"row_inv_norms", t.row_inv_norms, !ratio}};
       for (const NamedPtr& p : ptrs) {
+        if (!p.required) continue;                            // a RATIO term's inverse norms are not read
         if (!p.p) {
           set_error("%s: term %d: %s is NULL", who, s, p.name);
           return DRIN_E_NULL;
@@ -555,6 +793,8 @@ int live_terms(const char* who, const drin_topk_term* terms, int num_terms, bool
     }
     out->widths[out->S] = t.width;
     out->dtypes[out->S] = dtype;
+    out->form[out->S] = form;
+    if (ratio) out->ratio_mask |= 1u << out->S;
     out->term[out->S++] = t;
   }
   if (out->S == 0) {
@@ -737,16 +977,37 @@ int drin_table_topk_ex(const float* x, const void* rows, int32_t row_dtype, cons
                     chunk_entities, workspace, workspace_bytes, out_scores, out_rows, stream);
 }
 
-int drin_topk_combine(const float* const* blocks, const float* const* col_inv_norms, const float* const* row_scales, const float* weights,
-                      int32_t num_terms, int64_t ld, int32_t batch, int64_t cols, float* out, void* stream) {
-  const char* who = "drin_topk_combine";
+// drin_topk_combine and drin_topk_combine_forms are ONE body: forms NULL (the old spelling) or all cosines is the old launch
+static int topk_combine(const char* who, const float* const* blocks, const float* const* col_inv_norms, const float* const* row_scales,
+                        const float* weights, const drin_topk_form* forms, int32_t num_terms, int64_t ld, int32_t batch, int64_t cols, float* out,
+                        void* stream) {
   if (!blocks || !col_inv_norms || !row_scales || !weights || !out) {
     set_error("%s: %s is NULL", who, !blocks ? "blocks" : !col_inv_norms ? "col_inv_norms" : !row_scales ? "row_scales" : !weights ? "weights" : "out");
     return DRIN_E_NULL;
   }
   DRIN_TRY(check_count(who, "num_terms", num_terms, 1, DRIN_TOPK_MAX_TERMS));
-  CombineTerms t = {};
+  FormTerms ft = {};
+  CombineTerms& t = ft.t;
   for (int s = 0; s < num_terms; ++s) {
+    if (forms != nullptr && forms[s].form != DRIN_TOPK_COSINE) {   // a RATIO term: the masses stand where inverse norms and factors do
+      const drin_topk_form& f = forms[s];
+      DRIN_TRY(check_form(who, s, f, DRIN_FEAT_F32, true));
+      if (!blocks[s]) {
+        set_error("%s: term %d: blocks is NULL", who, s);
+        return DRIN_E_NULL;
+      }
+      if (!aligned16(blocks[s]) || !aligned16(f.x_mass)) {
+        set_error("%s: term %d: blocks and x_mass must be 16-byte aligned", who, s);
+        return DRIN_E_ALIGN;
+      }
+      if (!is_finite32(weights[s])) {
+        set_error("%s: term %d: weight is not finite", who, s);
+        return DRIN_E_SHAPE;
+      }
+      t.block[s] = blocks[s], t.inv[s] = f.row_mass, t.scale[s] = f.x_mass, t.weight[s] = weights[s];
+      ft.eps[s] = f.eps, ft.ratio_mask |= 1u << s;
+      continue;
+    }
     if (!blocks[s] || !col_inv_norms[s] || !row_scales[s]) {
       set_error("%s: term %d: %s is NULL", who, s, !blocks[s] ? "blocks" : !col_inv_norms[s] ? "col_inv_norms" : "row_scales");
       return DRIN_E_NULL;
@@ -772,13 +1033,23 @@ int drin_topk_combine(const float* const* blocks, const float* const* col_inv_no
     return DRIN_E_SHAPE;
   }
   DRIN_BIND_DEVICE(stream, out, who);
-  return launch_topk_combine(t, num_terms, out, ld, cols, (hipStream_t)stream);
+  if (ft.ratio_mask == 0) return launch_topk_combine(t, num_terms, out, ld, cols, (hipStream_t)stream);
+  return launch_topk_forms_combine(ft, num_terms, out, ld, cols, (hipStream_t)stream);
+}
+int drin_topk_combine(const float* const* blocks, const float* const* col_inv_norms, const float* const* row_scales, const float* weights,
+                      int32_t num_terms, int64_t ld, int32_t batch, int64_t cols, float* out, void* stream) {
+  return topk_combine("drin_topk_combine", blocks, col_inv_norms, row_scales, weights, nullptr, num_terms, ld, batch, cols, out, stream);
+}
+int drin_topk_combine_forms(const float* const* blocks, const float* const* col_inv_norms, const float* const* row_scales, const float* weights,
+                            const drin_topk_form* forms, int32_t num_terms, int64_t ld, int32_t batch, int64_t cols, float* out, void* stream) {
+  return topk_combine("drin_topk_combine_forms", blocks, col_inv_norms, row_scales, weights, forms, num_terms, ld, batch, cols, out, stream);
 }
 
 static size_t table_topk_sum_workspace_bytes(const char* who, const drin_topk_term* terms, const int32_t* row_dtypes, int32_t num_terms,
-                                             int32_t batch, int64_t num_entities, int32_t k, int64_t chunk_entities, int precision) {
+                                             int32_t batch, int64_t num_entities, int32_t k, int64_t chunk_entities, int precision,
+                                             const drin_topk_form* forms = nullptr) {
   LiveTerms live;
-  if (live_terms(who, terms, num_terms, false, &live, row_dtypes) != DRIN_OK) return 0;
+  if (live_terms(who, terms, num_terms, false, &live, row_dtypes, forms) != DRIN_OK) return 0;
   TopkLayout W;
   if (plan_topk(who, live.widths, live.dtypes, live.S, true, batch, num_entities, k, chunk_entities, precision, nullptr, &W) != DRIN_OK) return 0;
   return W.total_floats * sizeof(float);
@@ -798,11 +1069,11 @@ size_t drin_table_topk_sum_workspace_bytes_ex(const drin_topk_term* terms, const
   return table_topk_sum_workspace_bytes(who, terms, row_dtypes, num_terms, batch, num_entities, k, chunk_entities, precision);
 }
 
-static int table_topk_sum(const char* who, const drin_topk_term* terms, const int32_t* row_dtypes, int32_t num_terms, int64_t num_entities,
-                          int32_t batch, int32_t k, float cosine_eps, int32_t precision, int64_t chunk_entities, void* workspace,
-                          size_t workspace_bytes, float* out_scores, int64_t* out_rows, void* stream) {
+static int table_topk_sum(const char* who, const drin_topk_term* terms, const int32_t* row_dtypes, const drin_topk_form* forms,
+                          int32_t num_terms, int64_t num_entities, int32_t batch, int32_t k, float cosine_eps, int32_t precision,
+                          int64_t chunk_entities, void* workspace, size_t workspace_bytes, float* out_scores, int64_t* out_rows, void* stream) {
   LiveTerms live;
-  DRIN_TRY(live_terms(who, terms, num_terms, true, &live, row_dtypes));
+  DRIN_TRY(live_terms(who, terms, num_terms, true, &live, row_dtypes, forms));
   DRIN_CHECK_POINTERS(who, {"workspace", workspace, true});
   if (!out_scores || !out_rows) {
     set_error("%s: out_scores / out_rows is NULL", who);
@@ -824,15 +1095,22 @@ static int table_topk_sum(const char* who, const drin_topk_term* terms, const in
   uint64_t* slices = reinterpret_cast<uint64_t*>(ws + W.slices);
   float* cos = ws + W.cos;
   float* scores = ws + W.scores;
-  CombineTerms ct = {};
+  FormTerms ft = {};                    // (without a RATIO term only its CombineTerms are used: the old launch)
+  CombineTerms& ct = ft.t;
   ChainWeights cw = {};
+  ft.ratio_mask = live.ratio_mask;
   // the mentions of every term padded to Bp rows, and their factors 1 / max(|x_s[b]|, eps): unlike the single cosine, the mention
   // norms differ from term to term and do change the ranking (the weight joins them inside the combine)
   for (int s = 0; s < S; ++s) {
     const drin_topk_term& t = live.term[s];
     float* xpad = ws + W.xpad[s];
     DRIN_TRY(launch_pad_rows(t.x, xpad, B, Bp, t.width, st));
-    DRIN_TRY(launch_row_inv_norms(xpad, DRIN_FEAT_F32, Bp, t.width, cosine_eps, ws + W.scale[s], st));
+    if (live.ratio_mask >> s & 1u) {   // a RATIO term: the factor region holds the mentions' masses, padded with zeros
+      DRIN_TRY(launch_pad_mass(live.form[s].x_mass, ws + W.scale[s], B, Bp, st));
+      ft.eps[s] = live.form[s].eps;
+    } else {
+      DRIN_TRY(launch_row_inv_norms(xpad, DRIN_FEAT_F32, Bp, t.width, cosine_eps, ws + W.scale[s], st));
+    }
     if (W.planes_floats[s])   // a bf16-stored term on the plane route: its padded mentions as hi / lo planes, once per call
       DRIN_TRY(launch_split_planes(xpad, ws + W.planes[s], reinterpret_cast<uint16_t*>(ws + W.planes[s]) + (size_t)Bp * t.width,
                                    (int64_t)Bp * t.width, st));
@@ -847,15 +1125,23 @@ static int table_topk_sum(const char* who, const drin_topk_term* terms, const in
       const drin_topk_term& t = live.term[s];
       DRIN_TRY(launch_chunk_product(t.rows, live.dtypes[s], e0, n, t.width, ws + W.xpad[s], W.planes_floats[s] ? ws + W.planes[s] : nullptr,
                                     ws + W.widen, W.widen_floats, ws + W.block[s], Bp, precision, st));
-      ct.inv[s] = t.row_inv_norms + e0;
+      ct.inv[s] = ((live.ratio_mask >> s & 1u) ? live.form[s].row_mass : t.row_inv_norms) + e0;
     }
-    DRIN_TRY(launch_topk_combine(ct, S, combined, Bp, n, st));
+    if (live.ratio_mask == 0)
+      DRIN_TRY(launch_topk_combine(ct, S, combined, Bp, n, st));
+    else
+      DRIN_TRY(launch_topk_forms_combine(ft, S, combined, Bp, n, st));
     DRIN_TRY(launch_topk_update(combined, Bp, B, n, e0, nullptr, kp, keys, list, slices, e0 == 0, st));
   }
   // the kp selected rows scored again, term by term as drin_cosine_rows_indexed_fwd scores them (an empty entry, row -1, is clamped
   // silently and stays last), the fp32 chain over the terms, and the order of the contract
   for (int s = 0; s < S; ++s) {
     const drin_topk_term& t = live.term[s];
+    if (live.ratio_mask >> s & 1u) {   // drin_ratio_rows_indexed_fwd's bits
+      DRIN_TRY(launch_ratio_gather(t.x, live.form[s].x_mass, t.rows, live.form[s].row_mass, list, num_entities, cos + (size_t)s * B * kp, B, kp,
+                                   t.width, live.form[s].eps, nullptr, st));
+      continue;
+    }
     DRIN_TRY(launch_cosine_gather(t.x, t.rows, live.dtypes[s], list, num_entities, cos + (size_t)s * B * kp, B, kp, t.width, cosine_eps, nullptr, 0,
                                   st));
   }
@@ -865,7 +1151,7 @@ static int table_topk_sum(const char* who, const drin_topk_term* terms, const in
 int drin_table_topk_sum(const drin_topk_term* terms, int32_t num_terms, int64_t num_entities, int32_t batch, int32_t k, float cosine_eps,
                         int32_t precision, int64_t chunk_entities, void* workspace, size_t workspace_bytes, float* out_scores,
                         int64_t* out_rows, void* stream) {
-  return table_topk_sum("drin_table_topk_sum", terms, nullptr, num_terms, num_entities, batch, k, cosine_eps, precision, chunk_entities,
+  return table_topk_sum("drin_table_topk_sum", terms, nullptr, nullptr, num_terms, num_entities, batch, k, cosine_eps, precision, chunk_entities,
                         workspace, workspace_bytes, out_scores, out_rows, stream);
 }
 int drin_table_topk_sum_ex(const drin_topk_term* terms, const int32_t* row_dtypes, int32_t num_terms, int64_t num_entities, int32_t batch,
@@ -876,8 +1162,73 @@ int drin_table_topk_sum_ex(const drin_topk_term* terms, const int32_t* row_dtype
     set_error("%s: row_dtypes is NULL", who);
     return DRIN_E_NULL;
   }
-  return table_topk_sum(who, terms, row_dtypes, num_terms, num_entities, batch, k, cosine_eps, precision, chunk_entities, workspace,
+  return table_topk_sum(who, terms, row_dtypes, nullptr, num_terms, num_entities, batch, k, cosine_eps, precision, chunk_entities, workspace,
                         workspace_bytes, out_scores, out_rows, stream);
+}
+size_t drin_table_topk_sum_forms_workspace_bytes(const drin_topk_term* terms, const int32_t* row_dtypes, const drin_topk_form* forms,
+                                                 int32_t num_terms, int32_t batch, int64_t num_entities, int32_t k, int64_t chunk_entities,
+                                                 int32_t precision) {
+  return table_topk_sum_workspace_bytes("drin_table_topk_sum_forms_workspace_bytes", terms, row_dtypes, num_terms, batch, num_entities, k,
+                                        chunk_entities, precision, forms);
+}
+int drin_table_topk_sum_forms(const drin_topk_term* terms, const int32_t* row_dtypes, const drin_topk_form* forms, int32_t num_terms,
+                              int64_t num_entities, int32_t batch, int32_t k, float cosine_eps, int32_t precision, int64_t chunk_entities,
+                              void* workspace, size_t workspace_bytes, float* out_scores, int64_t* out_rows, void* stream) {
+  return table_topk_sum("drin_table_topk_sum_forms", terms, row_dtypes, forms, num_terms, num_entities, batch, k, cosine_eps, precision,
+                        chunk_entities, workspace, workspace_bytes, out_scores, out_rows, stream);
+}
+
+int drin_object_rows(const void* obj, const void* score, int32_t dtype, int64_t n, int32_t K, int32_t width, float eps, float* out, float* mass,
+                     void* stream) {
+  const char* who = "drin_object_rows";
+  DRIN_CHECK_POINTERS(who, {"obj", obj, true}, {"out", out, true});
+  if (!score || !mass) {
+    set_error("%s: %s is NULL", who, !score ? "score" : "mass");
+    return DRIN_E_NULL;
+  }
+  DRIN_TRY(check_row_dtype(who, dtype, width));
+  if ((reinterpret_cast<uintptr_t>(score) & (dtype == DRIN_FEAT_BF16 ? 1u : 3u)) != 0 || (reinterpret_cast<uintptr_t>(mass) & 3u) != 0) {
+    set_error("%s: score must be aligned to its element and mass 4-byte aligned", who);
+    return DRIN_E_ALIGN;
+  }
+  DRIN_TRY(check_count(who, "n", n, 1, INT64_MAX / 4096));
+  DRIN_TRY(check_count(who, "K", K, 1, kObjectMaxK));
+  DRIN_TRY(check_width4(who, width));
+  if (!(eps > 0.0f)) {
+    set_error("%s: eps must be positive", who);
+    return DRIN_E_SHAPE;
+  }
+  DRIN_BIND_DEVICE(stream, out, who);
+  return launch_object_rows(obj, score, dtype, n, K, width, eps, out, mass, (hipStream_t)stream);
+}
+
+int drin_ratio_rows_indexed_fwd(const float* x, const float* x_mass, const float* rows, const float* row_mass, const int64_t* index,
+                                int64_t num_entities, float* out, int32_t batch, int32_t num_candidates, int32_t width, float eps,
+                                int32_t* index_status, void* stream) {
+  const char* who = "drin_ratio_rows_indexed_fwd";
+  DRIN_CHECK_POINTERS(who, {"x", x, true}, {"rows", rows, true});
+  if (!x_mass || !row_mass || !index || !out) {
+    set_error("%s: %s is NULL", who, !x_mass ? "x_mass" : !row_mass ? "row_mass" : !index ? "index" : "out");
+    return DRIN_E_NULL;
+  }
+  if ((reinterpret_cast<uintptr_t>(index) & 7u) != 0 || (reinterpret_cast<uintptr_t>(index_status) & 3u) != 0 ||
+      (reinterpret_cast<uintptr_t>(x_mass) & 3u) != 0 || (reinterpret_cast<uintptr_t>(row_mass) & 3u) != 0 ||
+      (reinterpret_cast<uintptr_t>(out) & 3u) != 0) {
+    set_error("%s: index must be 8-byte, x_mass, row_mass, out and index_status 4-byte aligned", who);
+    return DRIN_E_ALIGN;
+  }
+  DRIN_TRY(check_count(who, "num_entities", num_entities, 1, INT64_MAX / 4096));
+  DRIN_TRY(check_width4(who, width));
+  if (!is_finite32(eps)) {
+    set_error("%s: eps is not finite", who);
+    return DRIN_E_SHAPE;
+  }
+  DRIN_TRY(check_count(who, "batch", batch, 1, INT32_MAX));
+  DRIN_TRY(check_count(who, "num_candidates", num_candidates, 1, kMaxGridY));
+  DRIN_TRY(check_count(who, "batch * num_candidates", (int64_t)batch * num_candidates, 1, INT32_MAX));
+  DRIN_BIND_DEVICE(stream, out, who);
+  return launch_ratio_gather(x, x_mass, rows, row_mass, index, num_entities, out, batch, num_candidates, width, eps, index_status,
+                             (hipStream_t)stream);
 }
 
 int drin_rank_rows(const float* scores, const int64_t* rows, int32_t batch, int32_t n, int32_t k, float* out_scores, int64_t* out_rows,

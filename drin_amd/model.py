@@ -20,8 +20,8 @@ from torch import nn
 
 from . import _lib, row_ops
 from .config import DrinConfig, default_config
-from .table_ops import (MAX_CALL_MENTIONS, IndexWatch, LinkResult, cross_modal_edges, decode_status, in_slices, row_inv_norms, table_topk,
-                        table_topk_sum)
+from .table_ops import (MAX_CALL_MENTIONS, IndexWatch, LinkResult, RatioTerm, cross_modal_edges, decode_status, in_slices, object_rows,
+                        row_inv_norms, table_topk, table_topk_sum)
 
 
 # ---- parameter containers mirroring the reference's module tree (keys of SURVEY.md §8b) -------------
@@ -150,6 +150,7 @@ class EntityTable:
         self._cache: Optional[torch.Tensor] = None
         self._cache_key = None
         self._pooled = None
+        self._object_rows = None
         # stored CLIP embeddings [E, C] of the entities (set_clip): what the two CLIP edges of candidates chosen at run time are
         # formed from (IndexedBatch.from_clip); the per-entity cache does not depend on them - not part of _table_key
         self.clip_text: Optional[torch.Tensor] = None
@@ -237,10 +238,10 @@ class EntityTable:
         return "f32"
 
     def invalidate(self) -> "EntityTable":
-        """Drop the per-entity cache and the pooled-text copy.  Needed only after the tables were edited through a path
-        PyTorch's version counters do not see (`t.data.copy_(...)`, an external kernel writing the storage): in-place torch
+        """Drop the per-entity cache, the pooled-text copy and the rows of `object_rows`.  Needed only after the tables were edited
+        through a path PyTorch's version counters do not see (`t.data.copy_(...)`, an external kernel writing the storage): in-place torch
         ops on the tensors and replaced tensors are detected by themselves."""
-        self._cache, self._cache_key, self._pooled, self._scale_scan = None, None, None, None
+        self._cache, self._cache_key, self._pooled, self._scale_scan, self._object_rows = None, None, None, None, None
         return self
 
     def _table_key(self):
@@ -284,6 +285,27 @@ class EntityTable:
             text = self.text.contiguous()
             self._pooled = (key, _pool_tokens(text, self.mask), text[:, 0, :].contiguous())   # [E, D] each
         return self._pooled[1], self._pooled[2]
+
+    @torch.no_grad()
+    def object_rows(self, cfg: DrinConfig):
+        """`(u [E, R], T [E])` float32: the entity side of the image-image edge (`model.py:84-92`) per ENTITY,
+        `u[e] = sum_j es[e, j] eobj[e, j] / max(|eobj[e, j]|, cfg.cosine_eps)` and `T[e] = sum_j es[e, j]` by `drin_object_rows`.
+        Neither depends on the weights: built once per version of `object` / `object_score` (the rule of `pooled_text`;
+        `invalidate()` drops them).  The two tables share one storage, float32 or bfloat16 read in place; `u` is float32 either way."""
+        obj, score = self.object, self.object_score
+        if obj is None or score is None:
+            raise ValueError("EntityTable.object_rows: the table has no object rows (`object` / `object_score` is None)")
+        if obj.dim() == 4 and obj.shape[2] == 1:
+            obj = obj[:, :, 0, :]                                         # the mean over one region row is that row
+        if obj.dim() != 3 or tuple(score.shape) != tuple(obj.shape[:2]):
+            raise NotImplementedError(f"EntityTable.object_rows: object {tuple(self.object.shape)} / object_score {tuple(score.shape)} must be "
+                                      "[E, Ke, (1,) R] and [E, Ke] (a region mean over more than one row is not built)")
+        key = (self.object.data_ptr(), self.object._version, tuple(self.object.shape), score.data_ptr(), score._version, cfg.cosine_eps)
+        if self._object_rows is None or self._object_rows[0] != key:
+            self._object_rows = None                                      # release the stale rows before allocating
+            u, mass = object_rows(obj.detach().contiguous(), score.detach().contiguous(), cfg.cosine_eps)
+            self._object_rows = (key, u, mass)
+        return self._object_rows[1], self._object_rows[2]
 
     def to(self, device) -> "EntityTable":
         mv = lambda t: None if t is None else t.to(device)  # noqa: E731
@@ -1203,10 +1225,14 @@ class Model(nn.Module):
         the `N` best rows of the table by the sum of three of its four layer-0 edges (`drin_table_topk_sum`, the model's
         precision, N <= 256) - `tt`: `span_mean(mention_text, start, end)` against the rows the table-form forward takes the
         text-text edge from (the token-0 copy of `table.pooled_text` for a token-level table, the text rows of a pooled one);
-        `ti`: `clip_text` against `table.clip_image`; `it`: `clip_image` against `table.clip_text`.  The image-image edge is not a
-        term.  `edge_weights`: three floats (default `cfg.gcn_edge_enabled[0:3]`); a zero drops its term, whose tensors are then
-        not read; all three zero is refused.  The inverse row norms of the three tables are cached per tensor version (the rule
-        of `rows` above; `invalidate()` drops them).  A mention with an EMPTY span has a NaN `tt` row: all its first-stage scores
+        `ti`: `clip_text` against `table.clip_image`; `it`: `clip_image` against `table.clip_text`.  The image-image edge `ii` joins as a
+        fourth term when `edge_weights` has four entries and the fourth is not zero: `drin_object_rows` of
+        `mention[5]` / `mention[6]` against `table.object_rows(cfg)`, the RATIO form `(q . u) / (S T + cfg.miei_eps)` of
+        `drin_table_topk_sum_forms` - all four edges the model reads at layer 0; `(0, 0, 0, 1)` ranks by it alone and reads no text
+        and no CLIP rows.  `edge_weights`: three floats (default `cfg.gcn_edge_enabled[0:3]`) or four; a zero drops its term, whose
+        tensors are then not read; all zero is refused.  Three entries make the three-term call as it was: its launches, its bits.
+        The inverse row norms of the three tables are cached per tensor version (the rule of `rows` above; `invalidate()` drops
+        them); `u` and `T` per version of the table's object tensors (`EntityTable.object_rows`).  A mention with an EMPTY span has a NaN `tt` row: all its first-stage scores
         are NaN and its candidates are rows `0 .. N-1` by the contract - it is not treated specially.
 
         bf16-stored tables: `table.text` (with the other five feature tensors: all six bfloat16, or none) and
@@ -1293,13 +1319,16 @@ class Model(nn.Module):
 
     def _edge_candidates(self, mention, table: EntityTable, clip_image, clip_text, edge_weights) -> torch.Tensor:
         """`candidates [B, N]` of `link(first_stage="edges")`: the N best table rows by the weighted sum of the tt, ti and it
-        cosines (`table_topk_sum`); the checks of that mode."""
+        cosines (`table_topk_sum`) and, with a fourth weight, of the image-image edge as a `RatioTerm`; the checks of that mode."""
         weights = self.cfg.gcn_edge_enabled[0:3] if edge_weights is None else tuple(edge_weights)
-        if len(weights) != 3:
-            raise ValueError(f"Model.link: edge_weights has {len(weights)} entries, expected 3 (tt, ti, it)")
+        if len(weights) not in (3, 4):
+            raise ValueError(f"Model.link: edge_weights has {len(weights)} entries, expected 3 (tt, ti, it) or 4 (tt, ti, it, ii)")
         weights = tuple(float(w) for w in weights)
         if all(w == 0.0 for w in weights):
-            raise ValueError("Model.link: first_stage='edges' with all three edge weights zero ranks nothing")
+            raise ValueError(f"Model.link: first_stage='edges' with all {'three' if len(weights) == 3 else 'four'} edge weights zero "
+                             "ranks nothing")
+        w_ii = weights[3] if len(weights) == 4 else 0.0                   # the image-image edge: a RATIO term behind the three cosines
+        weights = weights[:3]
         if len(mention) != 7:
             raise ValueError("Model.link: mention must be the first 7 tensors of the 14-sequence (drin/data.py:110-117)")
         N = self.cfg.num_candidates_model                               # (link() has refused a table without CLIP rows)
@@ -1320,8 +1349,20 @@ class Model(nn.Module):
                                       "bf16-stored rows are not built)")
         if weights[0] != 0.0 and mtf.dtype == torch.bfloat16 and mtf.shape[-1] % 8 != 0:
             raise ValueError(f"Model.link: bfloat16 text rows of width {mtf.shape[-1]}: the width must be a multiple of 8")
+        mobj, mscore = mention[5], mention[6]
+        if w_ii != 0.0:                                                   # ii's tensors, when ii is a term
+            if table.object is None or table.object_score is None:
+                raise ValueError("Model.link: the image-image edge needs the table's object rows (`object` / `object_score` is None)")
+            if mobj.dim() == 4 and mobj.shape[2] == 1:
+                mobj = mobj[:, :, 0, :]                                   # the mean over one region row is that row
+            if mobj.dim() != 3 or tuple(mscore.shape) != tuple(mobj.shape[:2]) or mobj.dtype != table.object.dtype or mscore.dtype != mobj.dtype:
+                raise NotImplementedError(f"Model.link: the image-image edge reads mention objects [B, Km, (1,) R] and scores [B, Km] in the "
+                                          f"table's storage (got {tuple(mention[5].shape)} {mention[5].dtype}, {tuple(mscore.shape)} "
+                                          f"{mscore.dtype}, table {table.object.dtype}; a region mean over more than one row is not built)")
         dev = table.text.device
-        if dev.type != "cuda" or any(t.device != dev for t in (mtf, start, end, clip_image, clip_text, table.clip_text, table.clip_image)):
+        placed = (mtf, start, end, clip_image, clip_text, table.clip_text, table.clip_image)
+        placed += (mobj, mscore, table.object, table.object_score) if w_ii != 0.0 else ()
+        if dev.type != "cuda" or any(t.device != dev for t in placed):
             raise RuntimeError("Model.link runs on an AMD GPU only (no CPU / eager fallback); move the batch and the table to 'cuda'")
         if B == 0:
             return torch.empty(0, N, dtype=torch.int64, device=dev)
@@ -1340,6 +1381,12 @@ class Model(nn.Module):
             _key, inv, _given, dense = self._norms_entry(cache, s, rows_of())
             terms.append((query().detach().contiguous(), dense, inv, w))
         precision = "f32" if self.precision == _lib.PREC_F32 else "bf16x3"
+        if w_ii != 0.0:
+            u, T = table.object_rows(self.cfg)
+            q, S = object_rows(mobj.detach().contiguous(), mscore.detach().contiguous(), eps)
+            return in_slices(B, self.MAX_CALL_MENTIONS, lambda sl: table_topk_sum(
+                [(None if x is None else x[sl], r, i, w) for x, r, i, w in terms] + [RatioTerm(q[sl], S[sl], u, T, w_ii, self.cfg.miei_eps)],
+                N, eps, precision).rows)
         return in_slices(B, self.MAX_CALL_MENTIONS, lambda sl: table_topk_sum(
             [(None if x is None else x[sl], r, i, w) for x, r, i, w in terms], N, eps, precision).rows)
 

@@ -5,6 +5,7 @@ table form both stand on, in a module that imports neither of them.
   body - checks, workspace query, allocation, the call, the result - for table rows stored as float32 or as bfloat16 read in place
   (DESIGN.md section 34); the storage decides only which spelling of the entry point is called (float32 rows keep the old one, whose
   name the library's error texts carry) and whether the row dtype is among its arguments;
+* the image-image edge as a term of `table_topk_sum` (DESIGN.md section 36): `object_rows`, `ratio_rows_indexed` and `RatioTerm`;
 * `IndexWatch`: the status words into which the kernels report a candidate row outside the table, their asynchronous read-backs and
   the check that turns them into an `IndexError` - one instance per model, which supplies the message.
 
@@ -102,6 +103,58 @@ def table_topk(x: torch.Tensor, rows: torch.Tensor, inv_norms: torch.Tensor, k: 
     return LinkResult(scores, best)
 
 
+class RatioTerm(NamedTuple):
+    """A term of `table_topk_sum` in the RATIO form: `weight * (x[b] . rows[e]) / (x_mass[b] * row_mass[e] +
+    eps)`.  `x [B, R]`, `x_mass [B]`, `rows [E, R]`, `row_mass [E]`: contiguous float32 on the GPU - for DRIN's image-image edge the
+    two results of `object_rows` per side, with `eps = cfg.miei_eps`."""
+    x: Optional[torch.Tensor]
+    x_mass: Optional[torch.Tensor]
+    rows: Optional[torch.Tensor]
+    row_mass: Optional[torch.Tensor]
+    weight: float
+    eps: float
+
+
+def object_rows(objects: torch.Tensor, scores: torch.Tensor, eps: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`(rows [n, R], mass [n])` float32 by `drin_object_rows`: `rows[r] = sum_j scores[r, j] objects[r, j] / max(|objects[r, j]|,
+    eps)`, `mass[r] = sum_j scores[r, j]` - one side of the image-image edge (`model.py:84-92`).  `objects
+    [n, K, R]` and `scores [n, K]` share one storage, float32 or bfloat16 read in place (the bits of the float32 call on the widened
+    values); `1 <= K <= 16`.  No gradient."""
+    who = "object_rows"
+    dtype = _row_dtype(who, objects)
+    if not torch.is_tensor(scores) or scores.dtype != objects.dtype or not scores.is_contiguous() or scores.device != objects.device:
+        raise ValueError(f"{who}: scores must be a contiguous {objects.dtype} tensor on the objects' device "
+                         f"(got {getattr(scores, 'dtype', type(scores).__name__)})")
+    if objects.dim() != 3 or tuple(scores.shape) != tuple(objects.shape[:2]):
+        raise ValueError(f"{who}: objects {tuple(objects.shape)} / scores {tuple(scores.shape)} must be [n, K, R] and [n, K]")
+    n, K, R = objects.shape
+    rows = torch.empty(n, R, dtype=torch.float32, device=objects.device)
+    mass = torch.empty(n, dtype=torch.float32, device=objects.device)
+    if n > 0:
+        _lib.check(_lib.load().drin_object_rows(_ptr(objects), _ptr(scores), dtype, n, K, R, eps, _ptr(rows), _ptr(mass),
+                                                _stream(objects.device)))
+    return rows, mass
+
+
+def ratio_rows_indexed(x: torch.Tensor, x_mass: torch.Tensor, rows: torch.Tensor, row_mass: torch.Tensor, index: torch.Tensor, eps: float,
+                       status: Optional[torch.Tensor]) -> torch.Tensor:
+    """`[B, N]` = (x[b] . rows[index[b, n]]) / (x_mass[b] * row_mass[index[b, n]] + eps) by `drin_ratio_rows_indexed_fwd`: the
+    re-score of a `RatioTerm`; all float32, no gradient.  A row outside the table is clamped and reported into `status`."""
+    who = "ratio_rows_indexed"
+    x = x.detach().contiguous()
+    for name, t in (("x", x), ("x_mass", x_mass), ("rows", rows), ("row_mass", row_mass)):
+        _check_f32(who, name, t)
+    B, N = index.shape
+    if (x.dim() != 2 or rows.dim() != 2 or x.shape[1] != rows.shape[1] or x.shape[0] != B or tuple(x_mass.shape) != (B,)
+            or tuple(row_mass.shape) != (rows.shape[0],) or index.dtype != torch.int64 or not index.is_contiguous()):
+        raise ValueError(f"{who}: x {tuple(x.shape)}, x_mass {tuple(x_mass.shape)}, rows {tuple(rows.shape)}, row_mass {tuple(row_mass.shape)} "
+                         f"must be [B = {B}, R], [B], [E, R], [E] and index contiguous int64 [B, N]")
+    out = torch.empty(B, N, dtype=torch.float32, device=x.device)
+    _lib.check(_lib.load().drin_ratio_rows_indexed_fwd(_ptr(x), _ptr(x_mass), _ptr(rows), _ptr(row_mass), _ptr(index), rows.shape[0], _ptr(out),
+                                                       B, N, x.shape[1], eps, _ptr(status), _stream(x.device)))
+    return out
+
+
 def table_topk_sum(terms: Sequence, k: int, eps: float, precision: str, chunk_entities: int = 0) -> LinkResult:
     """The k best table rows for every mention by a SUM of cosines (`drin_table_topk_sum`):
     `score(b, e) = sum_s weight_s * cos(x_s[b], rows_s[e])`.  `terms`: 1 to 4 of `(x [B, D_s], rows [E, D_s], inv_norms [E],
@@ -109,13 +162,38 @@ def table_topk_sum(terms: Sequence, k: int, eps: float, precision: str, chunk_en
     their width.  `rows` alone may be contiguous bfloat16 instead, term by term, read in place (`drin_table_topk_sum_ex`,
     DESIGN.md section 34: such a term links exactly as `rows.float()` would).  A term of weight 0 is dropped before any launch and
     its three tensors may be `None`.  The returned scores are the fp32 chain `w_0 c_0 + w_1 c_1 + ...` over `cosine_rows_indexed`
-    of each live term on the returned rows, bit for bit."""
+    of each live term on the returned rows, bit for bit.
+
+    A term may instead be a `RatioTerm(x, x_mass, rows, row_mass, weight, eps)` (all float32): it contributes
+    `weight * (x[b] . rows[e]) / (x_mass[b] * row_mass[e] + eps)`, `c_s` of the chain is then `ratio_rows_indexed`'s, and the call goes
+    through `drin_table_topk_sum_forms`.  A call with 4-tuples only takes exactly the route above."""
     lib = _lib.load()
     terms = list(terms)
     arr = (_lib.DrinTopkTermC * max(len(terms), 1))()
     dtypes = (C.c_int32 * max(len(terms), 1))()
-    live = None
-    for s, (x, rows, inv, weight) in enumerate(terms[:len(arr)]):
+    forms = (_lib.DrinTopkFormC * max(len(terms), 1))()
+    live, ratios = None, False
+    for s, term in enumerate(terms[:len(arr)]):
+        if isinstance(term, RatioTerm):
+            x, rows, inv, weight = term.x, term.rows, None, term.weight
+            arr[s].weight = float(weight)
+            if float(weight) == 0.0:
+                continue
+            for name, t in (("x", x), ("x_mass", term.x_mass), ("rows", rows), ("row_mass", term.row_mass)):
+                if not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous() or t.device.type != "cuda":
+                    raise ValueError(f"table_topk_sum: term {s}: {name} must be a contiguous float32 tensor on the GPU")
+            if live is None:
+                live = (x.shape[0], rows.shape[0], x.device)
+            if (x.dim() != 2 or rows.dim() != 2 or x.shape[1] != rows.shape[1] or x.shape[0] != live[0] or rows.shape[0] != live[1]
+                    or tuple(term.x_mass.shape) != (live[0],) or tuple(term.row_mass.shape) != (live[1],)
+                    or any(t.device != live[2] for t in (x, rows, term.x_mass, term.row_mass))):
+                raise ValueError(f"table_topk_sum: term {s}: x {tuple(x.shape)}, x_mass {tuple(term.x_mass.shape)}, rows {tuple(rows.shape)}, "
+                                 f"row_mass {tuple(term.row_mass.shape)} must be [B = {live[0]}, R], [B], [E = {live[1]}, R], [E] on one device")
+            arr[s].x, arr[s].rows, arr[s].width = x.data_ptr(), rows.data_ptr(), x.shape[1]
+            forms[s].form, forms[s].x_mass, forms[s].row_mass, forms[s].eps = _lib.TOPK_RATIO, term.x_mass.data_ptr(), term.row_mass.data_ptr(), term.eps
+            ratios = True
+            continue
+        x, rows, inv, weight = term
         arr[s].weight = float(weight)
         if float(weight) == 0.0:
             continue
@@ -137,6 +215,12 @@ def table_topk_sum(terms: Sequence, k: int, eps: float, precision: str, chunk_en
         _lib.check(lib.drin_table_topk_sum(arr, len(terms), 1, 1, k, eps, PRECISIONS[precision], chunk_entities, None, 0, None, None, None))
         raise _lib.DrinError(_lib.E_SHAPE, "drin_table_topk_sum: no live term")
     (B, E, dev), prec = live, PRECISIONS[precision]
+    if ratios:                                                             # a live RATIO term: the entry points that take the forms
+        nbytes = lib.drin_table_topk_sum_forms_workspace_bytes(arr, dtypes, forms, len(terms), B, E, k, chunk_entities, prec)
+        ws, scores, best = _topk_buffers(nbytes, B, k, dev)
+        _lib.check(lib.drin_table_topk_sum_forms(arr, dtypes, forms, len(terms), E, B, k, eps, prec, chunk_entities, _ptr(ws), nbytes,
+                                                 _ptr(scores), _ptr(best), _stream(dev)))
+        return LinkResult(scores, best)
     stored = any(d == _lib.FEAT_BF16 for d in dtypes)
     head = (arr, dtypes) if stored else (arr,)
     nbytes = _entry("drin_table_topk_sum_workspace_bytes", stored)(*head, len(terms), B, E, k, chunk_entities, *((prec,) if stored else ()))

@@ -1111,8 +1111,8 @@ DRIN_API int drin_table_topk_ex(const float* x, const void* rows, int32_t row_dt
 /* ---- a SUM of cosines against the tables ------------------------------------------------------------ *
  * score(b, e) = sum_s weight_s * cos(x_s[b, :], rows_s[e, :]) over 1 .. DRIN_TOPK_MAX_TERMS (query, table) pairs that share
  * batch and num_entities but not their width: late-fusion retrieval, and DRIN's own layer-0 evidence for a pair (the text-text
- * edge of model.py:71-76 and the two CLIP edges of model.py:203, without the image-image edge).  THE ORDERING CONTRACT above
- * applies. */
+ * edge of model.py:71-76 and the two CLIP edges of model.py:203; the image-image edge of model.py:84-92 is no cosine of one row
+ * against one row and enters as a term of the RATIO form below).  THE ORDERING CONTRACT above applies. */
 #define DRIN_TOPK_MAX_TERMS 4
 typedef struct drin_topk_term { /* one cosine of the sum */
   const float* x;             /* [batch, width] */
@@ -1171,6 +1171,76 @@ DRIN_API size_t drin_table_topk_sum_workspace_bytes_ex(const drin_topk_term* ter
 DRIN_API int drin_table_topk_sum_ex(const drin_topk_term* terms, const int32_t* row_dtypes, int32_t num_terms, int64_t num_entities,
                                     int32_t batch, int32_t k, float cosine_eps, int32_t precision, int64_t chunk_entities, void* workspace,
                                     size_t workspace_bytes, float* out_scores, int64_t* out_rows, void* stream);
+
+/* ---- the image-image edge as a term: the RATIO form ---------------------------------------------------- *
+ * model.py:78-92 scores a pair by  ii(b, e) = sum_{i < Km, j < Ke} cos(mobj[b, i], eobj[e, j]) ms[b, i] es[e, j] / (sum_{i, j}
+ * ms[b, i] es[e, j] + 1e-9).  Each norm of the cosine is clamped on its own (cosine_from_sums), so the double sum factors into one
+ * row per mention and one row per entity:
+ *   q[b] = sum_i ms[b, i] mobj[b, i] / max(|mobj[b, i]|, cosine_eps)   S[b] = sum_i ms[b, i]
+ *   u[e] = sum_j es[e, j] eobj[e, j] / max(|eobj[e, j]|, cosine_eps)   T[e] = sum_j es[e, j]
+ *   ii(b, e) = (q[b] . u[e]) / (S[b] T[e] + 1e-9)          exactly, in real arithmetic
+ * - one more product of the kind drin_table_topk_sum runs per chunk, behind a RATIO where a cosine has a product of inverse
+ * norms.
+ *
+ * drin_object_rows replaces the per-pair double loop of model.py:84-92 on either side: out[r, :] = sum_j score[r, j] obj[r, j, :] /
+ * max(|obj[r, j, :]|, eps) and mass[r] = sum_j score[r, j] for obj [n, K, width] and score [n, K], both stored as dtype
+ * (DRIN_FEAT_F32 | DRIN_FEAT_BF16, read in place and widened exactly: the bits of the fp32 call on the widened values); out
+ * [n, width] and mass [n] are fp32.  Per object row one scale score / max(norm, eps) (one fp32 division), then fp32 FMAs into the
+ * accumulator and a plain fp32 sum of the scores, both in ascending j.  One wave per output row; every object row is read once
+ * (twice past width 2048).  1 <= K <= 16, width % 4 == 0 (% 8 for bf16), eps > 0, n as drin_row_inv_norms; obj and out 16-byte
+ * aligned.  No atomics: the same bits every run.  Profiler class DRIN_KC_POOL. */
+DRIN_API int drin_object_rows(const void* obj, const void* score, int32_t dtype, int64_t n, int32_t K, int32_t width, float eps,
+                              float* out, float* mass, void* stream);
+
+/* The form of term s of a sum: a HOST array parallel to `terms`, like row_dtypes. */
+#define DRIN_TOPK_COSINE 0
+#define DRIN_TOPK_RATIO 1
+typedef struct drin_topk_form { /* form of term s; a NULL array = all DRIN_TOPK_COSINE */
+  int32_t form;
+  const float* x_mass;   /* RATIO: [batch]         */
+  const float* row_mass; /* RATIO: [num_entities]  */
+  float eps;             /* RATIO: added to the product of the masses (drin_config.miei_eps = 1e-9f for DRIN) */
+} drin_topk_form;
+
+/* out[b, n] = (x[b, :] . rows[index[b, n], :]) / (x_mass[b] * row_mass[index[b, n]] + eps): the re-score of a RATIO term.  The dot
+ * product is drin_cosine_rows_indexed_fwd's (fp32 FMA, its lane order and wave sum); then d = x_mass * row_mass, d = d + eps,
+ * out = dot / d, each rounded to fp32 on its own with a correctly rounded divide.  x [batch, width], rows [num_entities, width],
+ * x_mass [batch], row_mass [num_entities], out [batch, num_candidates]: all fp32.  An index outside [0, num_entities) is clamped
+ * before an address is formed from it and reported into index_status (int32[4] or NULL) as drin_cosine_rows_indexed_fwd does.
+ * width % 4 == 0, eps finite; x and rows 16-byte aligned; batch, num_candidates as drin_cosine_rows_indexed_fwd.  Two runs give
+ * the same bits.  Profiler class DRIN_KC_EDGE. */
+DRIN_API int drin_ratio_rows_indexed_fwd(const float* x, const float* x_mass, const float* rows, const float* row_mass,
+                                         const int64_t* index, int64_t num_entities, float* out, int32_t batch, int32_t num_candidates,
+                                         int32_t width, float eps, int32_t* index_status, void* stream);
+
+/* drin_topk_combine with the form of every term.  forms NULL, or all DRIN_TOPK_COSINE: drin_topk_combine's launch and bits.  A
+ * DRIN_TOPK_RATIO term s contributes, per element, d = row_mass[c] * x_mass[b]; d = d + eps; t = blocks[s][c * ld + b] / d;
+ * t = t * weights[s]; acc = acc + t (acc = t for term 0) - every operation rounded to fp32 on its own, no contraction, a correctly
+ * rounded divide; the cosine terms keep their sequence.  HERE forms[s].x_mass is [ld] (16-byte aligned, all ld entries are read:
+ * pad it with zeros) and forms[s].row_mass is [cols], already at the block's first column; col_inv_norms[s] and row_scales[s] of
+ * a RATIO term are not read and may be NULL.  Still one launch; out may be blocks[0]. */
+DRIN_API int drin_topk_combine_forms(const float* const* blocks, const float* const* col_inv_norms, const float* const* row_scales,
+                                     const float* weights, const drin_topk_form* forms, int32_t num_terms, int64_t ld, int32_t batch,
+                                     int64_t cols, float* out, void* stream);
+
+/* drin_table_topk_sum_ex with the form of every term: forms, a HOST array [num_terms] or NULL (all DRIN_TOPK_COSINE); row_dtypes
+ * may be NULL here (all DRIN_FEAT_F32).  forms NULL or all DRIN_TOPK_COSINE: drin_table_topk_sum_ex's bytes and bits through the
+ * same plan - there is no second body.  A DRIN_TOPK_RATIO term contributes weight * (x[b] . rows[e]) / (x_mass[b] * row_mass[e] +
+ * eps): its row_inv_norms is not read and may be NULL, its rows are fp32 (a DRIN_FEAT_BF16 entry for it: DRIN_E_UNSUPPORTED among
+ * the argument checks), x_mass and row_mass are 4-byte aligned device arrays and eps is finite.  It occupies an ordinary slot of
+ * the workspace - its padded mentions, its block, and the per-mention factor region holding x_mass padded to Bp with zeros - so
+ * THE WORKSPACE QUERY RETURNS EXACTLY WHAT drin_table_topk_sum_workspace_bytes_ex RETURNS for the same widths, dtypes, batch,
+ * num_entities, k, chunk and precision.  Per chunk its product is the GEMM module's choice like any fp32 term's and the one
+ * combine is drin_topk_combine_forms'.  The re-score of a RATIO term is drin_ratio_rows_indexed_fwd's bits: out_scores ARE the
+ * chain acc = w_0 c_0; acc = acc + w_s c_s of drin_table_topk_sum over those and drin_cosine_rows_indexed_fwd(_ex)'s bits.  The
+ * entry of a dropped term (weight 0) is not read. */
+DRIN_API size_t drin_table_topk_sum_forms_workspace_bytes(const drin_topk_term* terms, const int32_t* row_dtypes,
+                                                          const drin_topk_form* forms, int32_t num_terms, int32_t batch,
+                                                          int64_t num_entities, int32_t k, int64_t chunk_entities, int32_t precision);
+DRIN_API int drin_table_topk_sum_forms(const drin_topk_term* terms, const int32_t* row_dtypes, const drin_topk_form* forms,
+                                       int32_t num_terms, int64_t num_entities, int32_t batch, int32_t k, float cosine_eps,
+                                       int32_t precision, int64_t chunk_entities, void* workspace, size_t workspace_bytes,
+                                       float* out_scores, int64_t* out_rows, void* stream);
 
 /* ---- DRIN behind a first stage: CLIP edges for run-time candidates and a rerank ---------------- *
  * The two CLIP edges of drin_batch (miet_similarity, mtei_similarity) for candidates that were chosen at run time, from stored
